@@ -13,8 +13,12 @@ Launch: one process per GPU.  Under torchrun (`python -m torch.distributed.run -
 the ranks come from the environment; a plain `python bench.py --gpus N` starts the N ranks itself (fresh child
 processes, created before this process has touched a GPU) and relays rank 0's line.
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement) with `roofline` for the dominant kernel and
-`cpu_baseline` (the oracle = CPU port of the reference, timed on this host's cores on a bounded sample).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`, the counters of the timed region).  `--full` adds everything else on the same line: the stand-alone and
+in-timed-region kernel durations, `roofline` for the dominant kernel, the counter identity against single passes, the
+in-order and same-batch legs, the sequential-mode leg, the C4 / C5 legs at N > 1, coverage, and `cpu_baseline` (the oracle =
+CPU port of the reference, timed on this host's cores on a bounded sample).  `--dump-outputs DIR` writes the arrays the last
+timed step computed (bench.dump_outputs).
 """
 import argparse
 import hashlib
@@ -132,6 +136,27 @@ def algorithmic_bytes(m, n, aligners=1):
     return (np.ceil(2 * m / 8) + np.ceil(2 * n / 8) + 4 * aligners).sum()
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs writes at most this much (under 64 MB, whichever way a megabyte is counted)
+DUMP_SEED = 20240607  # the fixed sample of pairs when the whole arrays would exceed DUMP_BYTES
+
+
+def dump_outputs(path, penalties, counters):
+    """--dump-outputs: what the caller of the timed path receives, as float64 .npy files (exact for int32 penalties and counts
+    below 2^53): <aligner>.npy = the last timed step's penalty per pair of rank 0's batch (nw, leap, greedy; C3 runs no NW),
+    counters.npy = {total, nw_ok, leap_ok, greedy_ok} summed over the timed steps (and ranks).  Where the penalty arrays would
+    exceed DUMP_BYTES, every one of them is reduced to the same seeded sample of pairs, whose indices go to pair_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    n = len(next(iter(penalties.values())))
+    keep = (DUMP_BYTES - 4096) // (8 * (len(penalties) + 1))  # room for the sampled arrays plus the index array
+    if n * 8 * len(penalties) > DUMP_BYTES - 4096:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+        penalties = {k: v[idx] for k, v in penalties.items()}
+        np.save(os.path.join(path, "pair_index.npy"), idx.astype(np.float64))
+    for name, v in penalties.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(v, dtype=np.float64))
+    np.save(os.path.join(path, "counters.npy"), np.asarray(counters, dtype=np.float64))
+
+
 class QuietStdout:
     """The contract is ONE JSON line on stdout.  RCCL, Gloo and the HIP runtime print banners to fd 1 from C code, so fd 1
     points at stderr while the benchmark runs and is put back (after flushing C stdio) only for the JSON line."""
@@ -164,6 +189,12 @@ def parse_args():
     ap.add_argument("--total-pairs", type=int, default=0,
                     help="strong scaling: this many pairs in total, split into contiguous shards over the ranks "
                          "(e.g. --workload C4 --total-pairs 10000000); default is weak scaling with --pairs per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (per-kernel durations, roofline, counter identity, "
+                         "in-order / same-batch / sequential / C4 / C5 legs, coverage, CPU baseline and parity); the --no-* and "
+                         "--cpu-sample / --extra-* options below tune these legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's penalty arrays and the timed region's counters as DIR/<name>.npy")
     ap.add_argument("--cpu-sample", type=int, default=300_000)
     ap.add_argument("--no-in-order", action="store_true", help="skip the extra in-order leg (ms_per_step_in_order)")
     ap.add_argument("--no-standalone", action="store_true",
@@ -178,9 +209,13 @@ def parse_args():
                     help="resident batches the timed steps rotate over (step s uses batch s mod R), so that no step finds its "
                          "input in the 256 MiB Infinity Cache where an earlier step left it; 0 = as many as it takes for the "
                          "ASCII of R batches to exceed 1 GiB (6 at C2), 1 = one batch re-read every step")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
+WARM_S = 0.25  # after the --warmup steps, the warm-up goes on for this long (wall clock, GPU busy)
 LLC_BYTES = 256 << 20  # MI355X Infinity Cache (MI355X_MICROARCH.md): what a re-read working set must exceed to come from HBM
 
 
@@ -306,6 +341,7 @@ def run(args, asm, eng, torch, dist, stream, rank, world, cfg, params, first, n,
     d_alt = {a: eng.malloc(4 * n) for a in aligners} if PACK_MODE == 3 else d_pen
     calls = [0]
     it = [0]  # steps issued since the last reset: which batch is next
+    last_out = [d_pen]  # the output arrays the latest step wrote (--dump-outputs)
 
     def step(timers=None, b=None, repack=True):
         if b is None:
@@ -317,8 +353,10 @@ def run(args, asm, eng, torch, dist, stream, rank, world, cfg, params, first, n,
                 o = d_alt if calls[0] & 1 else d_pen
                 calls[0] += 1
                 eng.run_benchmark_async(b, params, o.get(asm.NW), o.get(asm.LEAP), o.get(asm.GREEDY), d_cnt, repack=3)
+                last_out[0] = o
             else:
                 eng.run_benchmark_async(b, params, d_nw, d_leap, d_greedy, d_cnt, repack=(PACK_MODE if repack else 0))
+                last_out[0] = d_pen
             return
         seq = [("pack", lambda: eng.pack_async(b))]
         for a in aligners:
@@ -340,30 +378,41 @@ def run(args, asm, eng, torch, dist, stream, rank, world, cfg, params, first, n,
     for _ in range(max(args.warmup, len(batches))):  # every batch is packed (and its second plane set allocated) once
         step()
     eng.pipeline_join_async()
-    # stand-alone durations: a separately instrumented pass with the kernels one after the other on one stream (what a
-    # kernel costs when it has the GPU to itself; in the timed region Greedy shares it with NW and LEAP) — run before
-    # the timed region, where it also tells which kernel is the dominant one
-    names = ("pack", "nw", "leap", "greedy")
-    timers = {}
-    for _ in range(3 if args.no_standalone else min(args.steps, 20)):
-        step(timers)
+    # ... and then the GPU is kept busy for WARM_S more: after a few milliseconds of work the steps still run ~2 % slower than
+    # at their steady pace (C2, --steps 200: 0.207 ms after 5 warm-up steps, 0.2025 after 500)
     eng.synchronize()
-    kernel_ms = {k: float(np.mean([t.elapsed_ms() for t in v])) for k, v in timers.items()}
-    dom = max(kernel_ms, key=kernel_ms.get)
-    same_timers = {}
-    if len(batches) > 1 and not args.no_standalone:  # the same pass over ONE batch: what the Infinity Cache gives a re-read
-        for _ in range(min(args.steps, 20)):
-            step(same_timers, b=batch)
+    t_warm = time.perf_counter()
+    while time.perf_counter() - t_warm < WARM_S:
+        for _ in range(len(batches)):
+            step()
+        eng.pipeline_join_async()
         eng.synchronize()
-    kernel_ms_same = {k: float(np.mean([t.elapsed_ms() for t in v])) for k, v in same_timers.items()}
+    names = ("pack", "nw", "leap", "greedy")
+    if args.full:
+        # stand-alone durations: a separately instrumented pass with the kernels one after the other on one stream (what a
+        # kernel costs when it has the GPU to itself; in the timed region Greedy shares it with NW and LEAP) — run before
+        # the timed region, where it also tells which kernel is the dominant one
+        timers = {}
+        for _ in range(3 if args.no_standalone else min(args.steps, 20)):
+            step(timers)
+        eng.synchronize()
+        kernel_ms = {k: float(np.mean([t.elapsed_ms() for t in v])) for k, v in timers.items()}
+        dom = max(kernel_ms, key=kernel_ms.get)
+        same_timers = {}
+        if len(batches) > 1 and not args.no_standalone:  # the same pass over ONE batch: what the Infinity Cache gives a re-read
+            for _ in range(min(args.steps, 20)):
+                step(same_timers, b=batch)
+            eng.synchronize()
+        kernel_ms_same = {k: float(np.mean([t.elapsed_ms() for t in v])) for k, v in same_timers.items()}
     if dist is not None:  # warm the collective up outside the timed region (RCCL builds its rings on first use)
         dist.all_reduce(torch.zeros(4, dtype=torch.int64, device=coll_device))
     barrier()
     counters.zero_()
-    # the dominant kernel's duration INSIDE the timed region: HIP events recorded by the library on the stream that kernel
-    # is launched on (Greedy: the handle's side stream, beside NW -> LEAP); only this one kernel is bracketed, because an
-    # event record keeps the next kernel of its stream from starting early (all four cost ~8 % of the step)
-    eng.profile_enable(args.steps, 1 << names.index(dom))
+    if args.full:
+        # the dominant kernel's duration INSIDE the timed region: HIP events recorded by the library on the stream that kernel
+        # is launched on (Greedy: the handle's side stream, beside NW -> LEAP); only this one kernel is bracketed, because an
+        # event record keeps the next kernel of its stream from starting early (all four cost ~8 % of the step)
+        eng.profile_enable(args.steps, 1 << names.index(dom))
     ev_ar = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
     torch.cuda.synchronize()
     it[0] = 0  # timed step s reads batch s mod R
@@ -398,6 +447,46 @@ def run(args, asm, eng, torch, dist, stream, rank, world, cfg, params, first, n,
         elapsed = max(float(p.item()) for p in parts)
 
     cnt = counters.cpu().numpy().copy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {asm.ALIGNER_NAMES[a]: eng.to_host(last_out[0][a], n) for a in aligners}, cnt)
+    job_pairs = args.total_pairs if args.total_pairs else world * n  # pairs one step aligns, over all ranks
+    out = {
+        "metric": "alignments/sec (1e6-pair batch, 100bp, err=0.10) per GPU; NW penalty bit-exact %",
+        "value": job_pairs * args.steps / elapsed,
+        "unit": "read pairs/s through " + "+".join(asm.ALIGNER_NAMES[a].upper() if a == asm.NW else asm.ALIGNER_NAMES[a].capitalize()
+                                                   for a in aligners)
+                + " (whole job; consecutive steps " + ("overlap" if steps_form(asm, aligners, params) == 3 else
+                                                        "pipeline their pack" if steps_form(asm, aligners, params) == 2 else "run in order")
+                + ", inputs rotate over resident batches; value_in_order = the same steps strictly in order)",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if args.total_pairs else "weak",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic",
+        "config": {
+            "workload": f"{args.workload}: {n} pairs per GPU, len {cfg.len_lo}-{cfg.len_hi}, {edit_model(asm, cfg)}, "
+                        f"k={params.k}, x=o=e={params.x},{params.o},{params.e}, aligners "
+                        + "+".join(asm.ALIGNER_NAMES[a] for a in aligners) + ", greedy tails=clean",
+            "pairs_per_gpu": n,
+            "sharding": "independent pairs, contiguous shard per rank, one 32-byte all-reduce of counters",
+            "steps_run": STEP_FORMS[steps_form(asm, aligners, params)],
+            "rotation": f"{len(batches)} resident batches of {n} pairs, step s reads batch s mod {len(batches)} "
+                        f"({len(batches) * batch.ascii_bytes / 2**20:.0f} MiB of ASCII against a 256 MiB Infinity Cache)",
+        },
+        "ms_per_step_per_rank": per_rank_ms,
+        "allreduce_ms": allreduce_ms,
+        "accuracy_pct": {asm.ALIGNER_NAMES[a]: 100.0 * float(cnt[1 + a]) / float(cnt[0]) for a in aligners}
+        if asm.NW in aligners else None,
+        "counters": {"total": int(cnt[0]), "nw_ok": int(cnt[1]), "leap_ok": int(cnt[2]), "greedy_ok": int(cnt[3]),
+                     "expected_total": job_pairs * args.steps},
+    }
+    if not args.full:
+        return out if rank == 0 else None
+
     region = eng.profile_read(args.steps)
     eng.profile_enable(0, 0)
     q_dom = names.index(dom)
@@ -472,8 +561,6 @@ def run(args, asm, eng, torch, dist, stream, rank, world, cfg, params, first, n,
     # leave the penalties of the CLEAN-mode batch in d_pen for the parity leg below
     step(b=batch, repack=False)
     eng.synchronize()
-    total_pairs = (args.total_pairs if args.total_pairs else world * n) * args.steps
-    value = total_pairs / elapsed
     hb = batch.download()
     m_len, n_len = hb.lengths()
     if dom == "pack":
@@ -484,52 +571,20 @@ def run(args, asm, eng, torch, dist, stream, rank, world, cfg, params, first, n,
     alone = alg_bytes / (kernel_ms[dom] * 1e-3) / 1e9
     pmc, pmc_why = load_pmc(args.workload)
     entry = pmc_for(pmc, dom, n)
-    out = {
-        "metric": "alignments/sec (1e6-pair batch, 100bp, err=0.10) per GPU; NW penalty bit-exact %",
-        "value": value,
-        "unit": "read pairs/s through " + "+".join(asm.ALIGNER_NAMES[a].upper() if a == asm.NW else asm.ALIGNER_NAMES[a].capitalize()
-                                                   for a in aligners)
-                + " (whole job; consecutive steps " + ("overlap" if steps_form(asm, aligners, params) == 3 else
-                                                        "pipeline their pack" if steps_form(asm, aligners, params) == 2 else "run in order")
-                + ", inputs rotate over resident batches; value_in_order = the same steps strictly in order)",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong" if args.total_pairs else "weak",
-        "vs_baseline": None,
-        "dtype": "u64",
-        "data": "synthetic",
-        "config": {
-            "workload": f"{args.workload}: {n} pairs per GPU, len {cfg.len_lo}-{cfg.len_hi}, {edit_model(asm, cfg)}, "
-                        f"k={params.k}, x=o=e={params.x},{params.o},{params.e}, aligners "
-                        + "+".join(asm.ALIGNER_NAMES[a] for a in aligners) + ", greedy tails=clean",
-            "pairs_per_gpu": n,
-            "sharding": "independent pairs, contiguous shard per rank, one 32-byte all-reduce of counters",
-            "steps_run": STEP_FORMS[steps_form(asm, aligners, params)],
-            "rotation": f"{len(batches)} resident batches of {n} pairs, step s reads batch s mod {len(batches)} "
-                        f"({len(batches) * batch.ascii_bytes / 2**20:.0f} MiB of ASCII against a 256 MiB Infinity Cache)",
-        },
+    out["counters"].update({"expected": expected, "as_expected": [int(v) for v in cnt] == expected,
+                            "per_batch_single_pass_rank0": per_batch, "steps_per_batch": uses})
+    out.update({
         "ms_per_step_in_order": in_order_ms,
-        "value_in_order": ((args.total_pairs if args.total_pairs else world * n) / (in_order_ms * 1e-3)) if in_order_ms else None,
+        "value_in_order": (job_pairs / (in_order_ms * 1e-3)) if in_order_ms else None,
         "ms_per_step_same_batch": same_batch_ms,
         "pack_GBps": {"rotating": pack_gbps(batch, n, kernel_ms.get("pack")),
                       "same_batch": pack_gbps(batch, n, kernel_ms_same.get("pack")),
                       "bytes": "ASCII read + 68 B of planes and lengths written per pair"},
         "kernel_ms_same_batch": kernel_ms_same or None,
-        "ms_per_step_per_rank": per_rank_ms,
-        "allreduce_ms": allreduce_ms,
         "kernel_ms_in_timed_region": region_ms,
         "kernel_ms": kernel_ms,
         "kernel_pairs_per_s": {k: n / (v * 1e-3) for k, v in kernel_ms.items()},
         "leap_greedy_pairs_per_s_per_gpu": n / ((kernel_ms.get("leap", 0) + kernel_ms.get("greedy", 0)) * 1e-3),
-        "accuracy_pct": {asm.ALIGNER_NAMES[a]: 100.0 * float(cnt[1 + a]) / float(cnt[0]) for a in aligners}
-        if asm.NW in aligners else None,
-        "counters": {"total": int(cnt[0]), "nw_ok": int(cnt[1]), "leap_ok": int(cnt[2]), "greedy_ok": int(cnt[3]),
-                     "expected_total": (args.total_pairs if args.total_pairs else world * n) * args.steps,
-                     "expected": expected, "as_expected": [int(v) for v in cnt] == expected,
-                     "per_batch_single_pass_rank0": per_batch, "steps_per_batch": uses},
         "coverage_pct": coverage,
         "sequential_mode": sequential,
         **(extra or {}),
@@ -552,7 +607,7 @@ def run(args, asm, eng, torch, dist, stream, rank, world, cfg, params, first, n,
             "standalone": {"avg_launch_ms": kernel_ms[dom], "achieved": alone, "frac": alone / HBM_PEAK_GBPS},
             "valu": valu_roofline(entry, pmc, kernel_ms[dom]) if pmc else None,
         },
-    }
+    })
     if world == 1 and not args.no_cpu_baseline:
         out.update(cpu_baseline_and_parity(asm, eng, hb, batch, params, aligners, args.cpu_sample, d_pen))
     return out

@@ -54,3 +54,24 @@ def test_steps_per_batch_counts():
         uses = [len(range(j, steps, rot)) for j in range(rot)]
         assert sum(uses) == steps and max(uses) - min(uses) <= 1
         assert uses == [sum(1 for s in range(steps) if s % rot == j) for j in range(rot)]
+
+
+def test_dump_outputs_stays_under_its_budget_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: float64 files; arrays too large for the budget become the same seeded sample of pairs on every run."""
+    import numpy as np
+
+    b = _bench()
+    small = {k: np.arange(1000, dtype=np.int32) * (i + 1) for i, k in enumerate(("nw", "leap", "greedy"))}
+    b.dump_outputs(str(tmp_path / "small"), small, np.array([3, 2, 1, 0], np.int64))
+    assert sorted(os.listdir(tmp_path / "small")) == ["counters.npy", "greedy.npy", "leap.npy", "nw.npy"]
+    assert np.load(tmp_path / "small" / "leap.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "small" / "greedy.npy"), 3.0 * np.arange(1000))
+    assert np.load(tmp_path / "small" / "counters.npy").tolist() == [3, 2, 1, 0]
+    n = 4_000_000
+    big = {k: (np.arange(n, dtype=np.int32) + i) % 101 for i, k in enumerate(("nw", "leap", "greedy"))}
+    for run in ("a", "b"):
+        b.dump_outputs(str(tmp_path / run), big, np.zeros(4))
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= b.DUMP_BYTES
+    idx = np.load(tmp_path / "a" / "pair_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "pair_index.npy")) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "leap.npy"), (idx + 1) % 101)

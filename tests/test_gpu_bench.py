@@ -36,7 +36,7 @@ def test_self_started_ranks_share_one_stream_with_the_collective(asm, oracle):
     n, steps, rot = 20000, 4, 3
     extra_total, extra_steps = 30001, 2   # an odd total: the strong split gives the ranks different shard sizes
     out = _bench({"ASM_DIST_BACKEND": "gloo"}, "--gpus", "2", "--pairs", str(n), "--steps", str(steps), "--warmup", "1", "--rotate", str(rot),
-                 "--cpu-sample", "20000", "--no-cpu-baseline", "--extra-pairs", str(extra_total), "--extra-steps", str(extra_steps))
+                 "--cpu-sample", "20000", "--no-cpu-baseline", "--extra-pairs", str(extra_total), "--extra-steps", str(extra_steps), "--full")
     assert out["n_gpus"] == 2 and len(out["ms_per_step_per_rank"]) == 2 and out["allreduce_ms"] is not None
     # rotating inputs: step s of rank r reads batch s mod R, batch j of rank r = shard r + j * world of the seeded stream, so the
     # counters are the oracle's counts of shards 0..5, shards 0 and 1 (used by steps 0 and 3) twice
@@ -64,7 +64,8 @@ def test_self_started_ranks_share_one_stream_with_the_collective(asm, oracle):
 
 def test_single_rank_through_rccl_and_sequential_leg(asm, oracle):
     n, steps = 30000, 4
-    out = _bench({"ASM_FORCE_DIST": "1"}, "--pairs", str(n), "--steps", str(steps), "--warmup", "1", "--cpu-sample", "30000", "--rotate", "2")
+    out = _bench({"ASM_FORCE_DIST": "1"}, "--pairs", str(n), "--steps", str(steps), "--warmup", "1", "--cpu-sample", "30000", "--rotate", "2",
+                 "--full")
     want = 2 * _expected_counts(asm, oracle, 0, n) + 2 * _expected_counts(asm, oracle, n, n)   # two batches, two steps each
     c = out["counters"]
     assert [c["total"], c["nw_ok"], c["leap_ok"], c["greedy_ok"]] == want.tolist()
@@ -75,6 +76,29 @@ def test_single_rank_through_rccl_and_sequential_leg(asm, oracle):
     assert seq["greedy_bit_exact_pct_vs_oracle_sequential"] == 100.0
     assert seq["pairs_where_sequential_differs_from_clean_pct"] > 0       # the two modes really differ on this input
     assert out["roofline"]["frac"] > 0 and out["cpu_baseline"]["value"] > 0
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(asm, oracle, tmp_path):
+    """Without --full the line carries the headline and the counters of the timed region only; --dump-outputs writes the
+    penalties of the last timed step (step 2 of 3 reads batch 2 mod 2 = 0: pairs [0, n)) and the counters, as float64."""
+    n, steps = 20000, 3
+    out = _bench({}, "--pairs", str(n), "--steps", str(steps), "--warmup", "1", "--rotate", "2", "--dump-outputs", str(tmp_path))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in out, key
+    assert out["steps"] == steps and out["ms_per_step"] > 0 and out["dtype"] == "u64" and out["higher_is_better"] is True
+    assert abs(out["value"] - n / (out["ms_per_step"] * 1e-3)) <= 1e-6 * out["value"]
+    assert "roofline" not in out and "cpu_baseline" not in out and "sequential_mode" not in out
+    want = 2 * _expected_counts(asm, oracle, 0, n) + _expected_counts(asm, oracle, n, n)   # steps 0 and 2 read batch 0, step 1 batch 1
+    c = out["counters"]
+    assert [c["total"], c["nw_ok"], c["leap_ok"], c["greedy_ok"]] == want.tolist()
+    cfg, _, params = asm.workload("C2")
+    hb = asm.generate_pairs(cfg, 0, n)
+    ref = {"nw": oracle.nw(hb), "leap": oracle.leap(hb, params.k), "greedy": oracle.greedy(hb, params.k, mode=1)}
+    assert sorted(os.listdir(tmp_path)) == ["counters.npy", "greedy.npy", "leap.npy", "nw.npy"]
+    for name, v in ref.items():
+        got = np.load(tmp_path / (name + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, v.astype(np.float64)), name
+    assert np.load(tmp_path / "counters.npy").tolist() == want.tolist()
 
 
 def test_more_ranks_than_gpus_is_refused(asm):

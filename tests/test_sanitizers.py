@@ -31,7 +31,7 @@ def _own_reports(text):
     out = []
     blocks = re.split(r"(?m)^(?==+\d+==ERROR|==================$|\S+:\d+:\d+: runtime error:)", text)
     for b in blocks:
-        if REPORT.search(b) and not ("/root/reference/" in b and "/root/repo/" not in b):
+        if REPORT.search(b) and not ("/GASMA/" in b and ROOT + os.sep not in b):  # the reference's sources live under GASMA/
             out.append(b[:1500])
     return out
 

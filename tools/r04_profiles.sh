@@ -25,12 +25,12 @@ c2)
   python3 tools/pmc_collect.py --head $HEAD > $O/pmc_collect_c2.log 2>&1; echo "pmc c2 done"
   cp gpurun_out/final/valu_rates.txt $O/valu_rates.txt
   stats c2 --steps 200 --warmup 2 --no-cpu-baseline --no-standalone --no-sequential --no-in-order
-  python3 bench.py > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench c2 done"; tail -c 600 $O/bench_c2.json ;;
+  python3 bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench c2 done"; tail -c 600 $O/bench_c2.json ;;
 c3|c4|c5)
   W=$(echo $PART | tr a-z A-Z)
   python3 tools/pmc_collect.py --head $HEAD --workload $W --pairs 10000000 --steps 2 > $O/pmc_collect_$PART.log 2>&1; echo "pmc $PART done"
   stats $PART --workload $W --pairs 10000000 --steps 4 --warmup 1 --no-cpu-baseline --no-standalone --no-sequential --no-in-order
-  python3 bench.py --workload $W --pairs 10000000 --steps 10 --warmup 2 --cpu-sample 100000 > $O/bench_${PART}_1e7.json 2> $O/bench_$PART.err
+  python3 bench.py --full --workload $W --pairs 10000000 --steps 10 --warmup 2 --cpu-sample 100000 > $O/bench_${PART}_1e7.json 2> $O/bench_$PART.err
   echo "bench $PART done"; tail -c 400 $O/bench_${PART}_1e7.json ;;
 grids)
   { echo "# C2"; python3 tools/bench_k.py C2 1e6; echo "# C3"; python3 tools/bench_k.py C3 1e6; } > $O/greedy_band_grid.txt 2>&1; echo "band grid done"
