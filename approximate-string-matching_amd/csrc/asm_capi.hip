@@ -14,6 +14,7 @@
 #include <fcntl.h>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <sys/stat.h>
@@ -170,6 +171,18 @@ static void pool_free(asm_handle* h, void* p) {
     h->pool_idle_bytes += sz;
 }
 
+/* A call-scoped pool block of handle h: back to h's pool when it goes out of scope. */
+template <typename T>
+struct Scratch {
+    asm_handle* h;
+    T* p = nullptr;
+    explicit Scratch(asm_handle* owner) : h(owner) {}
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() { pool_free(h, p); }
+    hipError_t alloc(size_t bytes) { return pool_alloc(h, (void**)&p, bytes); }
+};
+
 /* One width class of a batch: pairs whose longer string needs `w4` granules of 128 positions. */
 struct asm_bucket {
     int64_t n = 0;
@@ -244,6 +257,55 @@ static int fail(asm_handle* h, int code, const std::string& msg) {
                         std::string(#call) + ": " + hipGetErrorString(_e));                       \
         }                                                                                         \
     } while (0)
+
+/* The only place that frees a batch's device blocks (its owner is live). */
+static void batch_release(asm_batch* b) {
+    if (!b) return;
+    asm_handle* const o = b->owner;
+    /* the pool hands blocks out again in the order of o->stream; overlapped calls that were never joined may still read these
+     * on the library's own streams */
+    if (o->tail_set) (void)hipStreamWaitEvent(o->stream, o->ev_tail, 0);
+    pool_free(o, b->d_reads);
+    pool_free(o, b->d_refs);
+    pool_free(o, b->d_read_off);
+    pool_free(o, b->d_ref_off);
+    pool_free(o, b->d_planes);
+    pool_free(o, b->d_lens);
+    pool_free(o, b->d_planes_alt);
+    pool_free(o, b->d_lens_alt);
+    for (hipEvent_t ev : b->ev_consumed)
+        if (ev) (void)hipEventDestroy(ev);
+    pool_free(o, b->d_order);
+    pool_free(o, b->d_pos);
+    pool_free(o, b->d_tails);
+    pool_free(o, b->d_tail_g0);
+    pool_free(o, b->d_tail_l0);
+    pool_free(o, b->d_tail_chunks);
+    delete b;
+}
+
+struct BatchRelease {
+    void operator()(asm_batch* b) const { batch_release(b); }
+};
+using BatchPtr = std::unique_ptr<asm_batch, BatchRelease>; /* a batch under construction, or a streamed chunk's */
+
+/* A new, empty batch of n pairs whose device blocks will come from h's pool. */
+static int batch_new(asm_handle* h, int64_t n, int greedy_mode, const char* who, BatchPtr& b) {
+    if (greedy_mode != ASM_GREEDY_CLEAN && greedy_mode != ASM_GREEDY_SEQUENTIAL)
+        return fail(h, ASM_EINVAL, std::string(who) + ": unknown greedy_mode");
+    b.reset(new asm_batch);
+    b->owner = h, b->owner_serial = h->serial;
+    b->n = n;
+    b->greedy_mode = greedy_mode;
+    return ASM_OK;
+}
+
+/* Every device block a batch owns comes from its owner's pool, whichever handle the call came through: batch_release returns
+ * it there. */
+template <typename T>
+static hipError_t batch_alloc(asm_batch* b, T** p, size_t bytes) {
+    return pool_alloc(b->owner, (void**)p, bytes);
+}
 
 static int grid_for(int64_t n) { return (int)((n + ASM_BLOCK - 1) / ASM_BLOCK); }
 
@@ -585,6 +647,40 @@ int asm_device_count(void) {
     return c;
 }
 
+/* Releases everything a handle holds — a partly created one too — and the handle itself. */
+static void handle_teardown(asm_handle* h) {
+    (void)hipSetDevice(h->device);
+    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
+    if (h->d_pair_queue) (void)hipFree(h->d_pair_queue);
+    if (h->d_sort) (void)hipFree(h->d_sort);
+    if (h->pack_stream) (void)hipStreamDestroy(h->pack_stream);
+    if (h->ev_packed) (void)hipEventDestroy(h->ev_packed);
+    if (h->ev_gate) (void)hipEventDestroy(h->ev_gate);
+    if (h->ev_leap) (void)hipEventDestroy(h->ev_leap);
+    if (h->ev_tail) (void)hipEventDestroy(h->ev_tail);
+    for (hipEvent_t ev : h->ev_out)
+        if (ev) (void)hipEventDestroy(ev);
+    if (h->acc_stream) (void)hipStreamDestroy(h->acc_stream);
+    if (h->ev_nw) (void)hipEventDestroy(h->ev_nw);
+    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
+    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
+    if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
+    if (h->d_todo) (void)hipFree(h->d_todo);
+    for (auto& t : h->g3_tables)
+        if (t.d) (void)hipFree(t.d);
+    for (hipEvent_t ev : h->prof_ev) (void)hipEventDestroy(ev);
+    (void)hipDeviceSynchronize();
+    for (char* q : h->pin_raw)
+        if (q) (void)hipHostFree(q);
+    for (auto& row : h->pin_pen)
+        for (int32_t* q : row)
+            if (q) (void)hipHostFree(q);
+    pool_release_idle(h);
+    for (auto& kv : h->pool_live) (void)hipFree(kv.first); /* batches the caller never freed */
+    delete h;
+}
+
 int asm_create(asm_handle** out, int device) {
     if (!out) return fail(nullptr, ASM_EINVAL, "asm_create: out is NULL");
     *out = nullptr;
@@ -592,7 +688,8 @@ int asm_create(asm_handle** out, int device) {
     if (hipGetDeviceCount(&c) != hipSuccess || c <= 0)
         return fail(nullptr, ASM_ENODEVICE, "asm_create: no HIP device is visible (this library has no CPU path)");
     if (device < 0 || device >= c) return fail(nullptr, ASM_EINVAL, "asm_create: device index out of range");
-    asm_handle* h = new asm_handle;
+    std::unique_ptr<asm_handle, void (*)(asm_handle*)> owned(new asm_handle, handle_teardown); /* released on every early return */
+    asm_handle* const h = owned.get();
     h->device = device;
     HIPCHK(h, hipSetDevice(device));
     HIPCHK(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
@@ -631,7 +728,7 @@ int asm_create(asm_handle** out, int device) {
         h->serial = g_next_serial++;
         g_live_handles.push_back(h);
     }
-    *out = h;
+    *out = owned.release();
     return ASM_OK;
 }
 
@@ -645,36 +742,7 @@ int asm_destroy(asm_handle* h) {
                 break;
             }
     }
-    (void)hipSetDevice(h->device);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
-    if (h->d_pair_queue) (void)hipFree(h->d_pair_queue);
-    if (h->d_sort) (void)hipFree(h->d_sort);
-    if (h->pack_stream) (void)hipStreamDestroy(h->pack_stream);
-    if (h->ev_packed) (void)hipEventDestroy(h->ev_packed);
-    if (h->ev_gate) (void)hipEventDestroy(h->ev_gate);
-    if (h->ev_leap) (void)hipEventDestroy(h->ev_leap);
-    if (h->ev_tail) (void)hipEventDestroy(h->ev_tail);
-    for (hipEvent_t ev : h->ev_out)
-        if (ev) (void)hipEventDestroy(ev);
-    if (h->acc_stream) (void)hipStreamDestroy(h->acc_stream);
-    if (h->ev_nw) (void)hipEventDestroy(h->ev_nw);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
-    if (h->d_todo) (void)hipFree(h->d_todo);
-    for (auto& t : h->g3_tables)
-        if (t.d) (void)hipFree(t.d);
-    for (hipEvent_t ev : h->prof_ev) (void)hipEventDestroy(ev);
-    (void)hipDeviceSynchronize();
-    for (char* q : h->pin_raw)
-        if (q) (void)hipHostFree(q);
-    for (auto& row : h->pin_pen)
-        for (int32_t* q : row)
-            if (q) (void)hipHostFree(q);
-    pool_release_idle(h);
-    for (auto& kv : h->pool_live) (void)hipFree(kv.first); /* batches the caller never freed */
-    delete h;
+    handle_teardown(h);
     return ASM_OK;
 }
 
@@ -739,27 +807,6 @@ int asm_generate_pairs(const asm_gen_config* cfg, int64_t first, int64_t n, uint
 
 /* ---------------------------------------------------------------------------------------------------- */
 
-static void batch_release(asm_batch* b) {
-    if (!b) return;
-    pool_free(b->owner, b->d_reads);
-    pool_free(b->owner, b->d_refs);
-    pool_free(b->owner, b->d_read_off);
-    pool_free(b->owner, b->d_ref_off);
-    pool_free(b->owner, b->d_planes);
-    pool_free(b->owner, b->d_lens);
-    pool_free(b->owner, b->d_planes_alt);
-    pool_free(b->owner, b->d_lens_alt);
-    for (hipEvent_t ev : b->ev_consumed)
-        if (ev) (void)hipEventDestroy(ev);
-    pool_free(b->owner, b->d_order);
-    pool_free(b->owner, b->d_pos);
-    pool_free(b->owner, b->d_tails);
-    pool_free(b->owner, b->d_tail_g0);
-    pool_free(b->owner, b->d_tail_l0);
-    pool_free(b->owner, b->d_tail_chunks);
-    delete b;
-}
-
 static hipError_t launch_pack(asm_handle* h, const asm_batch* b, const uint4* tails, uint4* planes, uint32_t* lens,
                               const PackBuckets& pb, const uint32_t* pos) {
     const dim3 grid((unsigned)((b->n + PACK_BLOCK - 1) / PACK_BLOCK)), block(PACK_BLOCK);
@@ -811,14 +858,12 @@ static int batch_resolve_tails(asm_handle* h, asm_batch* b, const uint8_t* init2
     if (init256) memcpy(init.code, init256, 256);
     else memset(init.code, 0, 256);
     /* scratch lives with the batch: a streamed file re-resolves every chunk, a bench step every iteration */
-    if (emit && !b->d_tails) HIPCHK(h, pool_alloc(h, (void**)&b->d_tails, sizeof(uint4) * 4 * (size_t)b->n));
+    if (emit && !b->d_tails) HIPCHK(h, batch_alloc(b, &b->d_tails, sizeof(uint4) * 4 * (size_t)b->n));
     const size_t loc_bytes = (size_t)ngroups * TAIL_GROUP * 2 * sizeof(TailOp), grp_bytes = (size_t)ngroups * 2 * sizeof(TailOp);
     const size_t carry_bytes = (size_t)ngroups * 2 * 2 * sizeof(uint4);
-    if (!b->d_tail_g0) {
-        HIPCHK(h, pool_alloc(h, (void**)&b->d_tail_g0, sizeof(uint4) * 4 * (size_t)b->n));
-        HIPCHK(h, pool_alloc(h, (void**)&b->d_tail_l0, sizeof(uint32_t) * (size_t)b->n));
-        HIPCHK(h, pool_alloc(h, (void**)&b->d_tail_chunks, loc_bytes + grp_bytes + carry_bytes + 256)); /* loc, grp, gcarry, summary[256] */
-    }
+    if (!b->d_tail_g0) HIPCHK(h, batch_alloc(b, &b->d_tail_g0, sizeof(uint4) * 4 * (size_t)b->n));
+    if (!b->d_tail_l0) HIPCHK(h, batch_alloc(b, &b->d_tail_l0, sizeof(uint32_t) * (size_t)b->n));
+    if (!b->d_tail_chunks) HIPCHK(h, batch_alloc(b, &b->d_tail_chunks, loc_bytes + grp_bytes + carry_bytes + 256)); /* loc, grp, gcarry, summary[256] */
     TailOp* const d_loc = (TailOp*)b->d_tail_chunks;
     TailOp* const d_grp = (TailOp*)(b->d_tail_chunks + loc_bytes);
     uint4* const d_carry = (uint4*)(b->d_tail_chunks + loc_bytes + grp_bytes);
@@ -847,100 +892,85 @@ static int batch_finish(asm_handle* h, asm_batch* b) {
     const int64_t n = b->n;
     const int wmax = b->maxlen <= 128 ? 1 : (b->maxlen + 127) / 128;
     unsigned int counts[4] = {0, 0, 0, 0};
-    uint8_t *d_cls = nullptr, *d_cls2 = nullptr;
-    uint32_t* d_idx = nullptr;
-    unsigned int* d_counts = nullptr;
-    void* d_tmp = nullptr;
-    int rc = ASM_OK;
-    do {
-#define TRY(call)                                                        \
-    if ((call) != hipSuccess) {                                          \
-        rc = fail(h, ASM_ENODEVICE, std::string(#call) + " failed");     \
-        break;                                                           \
+    Scratch<uint8_t> d_cls(h), d_cls2(h);
+    Scratch<uint32_t> d_idx(h);
+    Scratch<unsigned int> d_counts(h);
+    Scratch<void> d_tmp(h);
+    bool bucketed = false;
+    if (wmax > 1 && n >= 4096 && h->bucketing) {
+        HIPCHK(h, d_cls.alloc((size_t)n));
+        HIPCHK(h, d_cls2.alloc((size_t)n));
+        HIPCHK(h, d_idx.alloc(sizeof(uint32_t) * (size_t)n));
+        HIPCHK(h, d_counts.alloc(16));
+        HIPCHK(h, hipMemsetAsync(d_counts.p, 0, 16, h->stream));
+        hipLaunchKernelGGL(classify_kernel, dim3(grid_for(n)), dim3(ASM_BLOCK), 0, h->stream, b->d_read_off, b->d_ref_off,
+                           (long)n, d_cls.p, d_idx.p, d_counts.p);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(counts, d_counts.p, 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        int classes = 0;
+        for (int c = 0; c < 4; c++) classes += counts[c] ? 1 : 0;
+        bucketed = classes > 1;
+        if (bucketed) {
+            HIPCHK(h, batch_alloc(b, &b->d_order, sizeof(uint32_t) * (size_t)n));
+            HIPCHK(h, batch_alloc(b, &b->d_pos, sizeof(uint32_t) * (size_t)n));
+            size_t tmp_bytes = 0;
+            HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_cls.p, d_cls2.p, d_idx.p, b->d_order, (int)n, 0, 2,
+                                                         h->stream));
+            HIPCHK(h, d_tmp.alloc(tmp_bytes + 16));
+            HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, d_cls.p, d_cls2.p, d_idx.p, b->d_order, (int)n, 0, 2,
+                                                         h->stream)); /* stable: input order is kept inside a class */
+            hipLaunchKernelGGL(invert_order_kernel, dim3(grid_for(n)), dim3(ASM_BLOCK), 0, h->stream, b->d_order, (long)n, b->d_pos);
+            HIPCHK(h, hipGetLastError());
+        }
     }
-        bool bucketed = false;
-        if (wmax > 1 && n >= 4096 && h->bucketing) {
-            TRY(pool_alloc(h, (void**)&d_cls, (size_t)n));
-            TRY(pool_alloc(h, (void**)&d_cls2, (size_t)n));
-            TRY(pool_alloc(h, (void**)&d_idx, sizeof(uint32_t) * (size_t)n));
-            TRY(pool_alloc(h, (void**)&d_counts, 16));
-            TRY(hipMemsetAsync(d_counts, 0, 16, h->stream));
-            hipLaunchKernelGGL(classify_kernel, dim3(grid_for(n)), dim3(ASM_BLOCK), 0, h->stream, b->d_read_off, b->d_ref_off,
-                               (long)n, d_cls, d_idx, d_counts);
-            TRY(hipGetLastError());
-            TRY(hipMemcpyAsync(counts, d_counts, 16, hipMemcpyDeviceToHost, h->stream));
-            TRY(hipStreamSynchronize(h->stream));
-            int classes = 0;
-            for (int c = 0; c < 4; c++) classes += counts[c] ? 1 : 0;
-            bucketed = classes > 1;
-            if (bucketed) {
-                TRY(pool_alloc(h, (void**)&b->d_order, sizeof(uint32_t) * (size_t)n));
-                TRY(pool_alloc(h, (void**)&b->d_pos, sizeof(uint32_t) * (size_t)n));
-                size_t tmp_bytes = 0;
-                TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_cls, d_cls2, d_idx, b->d_order, (int)n, 0, 2,
-                                                       h->stream));
-                TRY(pool_alloc(h, &d_tmp, tmp_bytes + 16));
-                TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_cls, d_cls2, d_idx, b->d_order, (int)n, 0, 2,
-                                                       h->stream)); /* stable: input order is kept inside a class */
-                hipLaunchKernelGGL(invert_order_kernel, dim3(grid_for(n)), dim3(ASM_BLOCK), 0, h->stream, b->d_order, (long)n,
-                                   b->d_pos);
-                TRY(hipGetLastError());
-            }
-        }
-        // bucket table
-        b->nb = 0;
-        size_t plane_total = 0;
-        int64_t slot = 0;
-        b->pb = PackBuckets{};
-        if (!bucketed) {
-            counts[0] = counts[1] = counts[2] = counts[3] = 0;
-            counts[wmax - 1] = (unsigned int)n;
-        }
-        for (int c = 0; c < 4; c++) {
-            if (!counts[c] && !(n == 0 && c == 0)) continue;
-            asm_bucket& k = b->bk[b->nb];
-            k.n = counts[c];
-            k.w4 = c + 1;
-            k.maxlen = b->maxlen < 128 * (c + 1) ? b->maxlen : 128 * (c + 1);
-            b->pb.w4[b->nb] = k.w4;
-            b->pb.start[b->nb] = slot;
-            b->pb.plane_off[b->nb] = (long)plane_total;
-            plane_total += (size_t)4 * (size_t)k.w4 * (size_t)k.n;
-            slot += k.n;
-            b->nb++;
-        }
-        b->pb.nb = b->nb;
+    // bucket table
+    b->nb = 0;
+    size_t plane_total = 0;
+    int64_t slot = 0;
+    b->pb = PackBuckets{};
+    if (!bucketed) {
+        counts[0] = counts[1] = counts[2] = counts[3] = 0;
+        counts[wmax - 1] = (unsigned int)n;
+    }
+    for (int c = 0; c < 4; c++) {
+        if (!counts[c] && !(n == 0 && c == 0)) continue;
+        asm_bucket& k = b->bk[b->nb];
+        k.n = counts[c];
+        k.w4 = c + 1;
+        k.maxlen = b->maxlen < 128 * (c + 1) ? b->maxlen : 128 * (c + 1);
+        b->pb.w4[b->nb] = k.w4;
         b->pb.start[b->nb] = slot;
-        b->planes_total = plane_total ? plane_total : 1;
-        TRY(pool_alloc(h, (void**)&b->d_planes, sizeof(uint4) * (plane_total ? plane_total : 1)));
-        TRY(pool_alloc(h, (void**)&b->d_lens, sizeof(uint32_t) * (size_t)(n > 0 ? n : 1)));
-        for (int q = 0; q < b->nb; q++) {
-            b->bk[q].planes = b->d_planes + b->pb.plane_off[q];
-            b->bk[q].lens = b->d_lens + b->pb.start[q];
-            b->bk[q].order = b->d_order ? b->d_order + b->pb.start[q] : nullptr;
-            b->bk[q].mixed = bucketed;
-        }
-#undef TRY
-        if (b->greedy_mode == ASM_GREEDY_SEQUENTIAL) rc = batch_resolve_tails(h, b, nullptr, nullptr, true);
-        if (rc) break;
-        rc = asm_batch_pack_async(h, b);
-        if (rc) break;
-        if (hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, ASM_ENODEVICE, "batch: stream synchronize failed");
-    } while (0);
-    pool_free(h, d_cls);
-    pool_free(h, d_cls2);
-    pool_free(h, d_idx);
-    pool_free(h, d_counts);
-    pool_free(h, d_tmp);
-    return rc;
+        b->pb.plane_off[b->nb] = (long)plane_total;
+        plane_total += (size_t)4 * (size_t)k.w4 * (size_t)k.n;
+        slot += k.n;
+        b->nb++;
+    }
+    b->pb.nb = b->nb;
+    b->pb.start[b->nb] = slot;
+    b->planes_total = plane_total ? plane_total : 1;
+    HIPCHK(h, batch_alloc(b, &b->d_planes, sizeof(uint4) * (plane_total ? plane_total : 1)));
+    HIPCHK(h, batch_alloc(b, &b->d_lens, sizeof(uint32_t) * (size_t)(n > 0 ? n : 1)));
+    for (int q = 0; q < b->nb; q++) {
+        b->bk[q].planes = b->d_planes + b->pb.plane_off[q];
+        b->bk[q].lens = b->d_lens + b->pb.start[q];
+        b->bk[q].order = b->d_order ? b->d_order + b->pb.start[q] : nullptr;
+        b->bk[q].mixed = bucketed;
+    }
+    int rc = b->greedy_mode == ASM_GREEDY_SEQUENTIAL ? batch_resolve_tails(h, b, nullptr, nullptr, true) : ASM_OK;
+    if (!rc) rc = asm_batch_pack_async(h, b);
+    if (rc) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return ASM_OK;
 }
 
 int asm_batch_upload(asm_handle* h, int64_t n, const char* reads, const uint32_t* read_off, const char* refs,
                      const uint32_t* ref_off, int greedy_mode, asm_batch** out) {
     if (!h || !out || n < 0 || !read_off || !ref_off || (n > 0 && (!reads || !refs)))
         return fail(h, ASM_EINVAL, "asm_batch_upload: bad arguments");
-    if (greedy_mode != ASM_GREEDY_CLEAN && greedy_mode != ASM_GREEDY_SEQUENTIAL)
-        return fail(h, ASM_EINVAL, "asm_batch_upload: unknown greedy_mode");
+    BatchPtr b;
+    int rc = batch_new(h, n, greedy_mode, "asm_batch_upload", b);
+    if (rc) return rc;
     *out = nullptr;
     HIPCHK(h, hipSetDevice(h->device));
     int maxlen = 0;
@@ -953,36 +983,20 @@ int asm_batch_upload(asm_handle* h, int64_t n, const char* reads, const uint32_t
     }
     if (maxlen > ASM_MAX_LENGTH)
         return fail(h, ASM_EUNSUPPORTED, "asm_batch_upload: a sequence is longer than ASM_MAX_LENGTH");
-    asm_batch* b = new asm_batch;
-    b->owner = h, b->owner_serial = h->serial;
-    b->n = n;
     b->maxlen = maxlen;
-    b->greedy_mode = greedy_mode;
     b->reads_bytes = n ? read_off[n] : 0;
     b->refs_bytes = n ? ref_off[n] : 0;
-    int rc = ASM_OK;
-    do {
-#define TRY(call)                                          \
-    if ((call) != hipSuccess) {                            \
-        rc = fail(h, ASM_ENOMEM, std::string(#call) + " failed"); \
-        break;                                             \
-    }
-        TRY(pool_alloc(h, (void**)&b->d_reads, b->reads_bytes + 16));
-        TRY(pool_alloc(h, (void**)&b->d_refs, b->refs_bytes + 16));
-        TRY(pool_alloc(h, (void**)&b->d_read_off, sizeof(uint32_t) * (size_t)(n + 1)));
-        TRY(pool_alloc(h, (void**)&b->d_ref_off, sizeof(uint32_t) * (size_t)(n + 1)));
-        TRY(hipMemcpyAsync(b->d_reads, reads, b->reads_bytes, hipMemcpyHostToDevice, h->stream));
-        TRY(hipMemcpyAsync(b->d_refs, refs, b->refs_bytes, hipMemcpyHostToDevice, h->stream));
-        TRY(hipMemcpyAsync(b->d_read_off, read_off, sizeof(uint32_t) * (size_t)(n + 1), hipMemcpyHostToDevice, h->stream));
-        TRY(hipMemcpyAsync(b->d_ref_off, ref_off, sizeof(uint32_t) * (size_t)(n + 1), hipMemcpyHostToDevice, h->stream));
-#undef TRY
-        rc = batch_finish(h, b);
-    } while (0);
-    if (rc) {
-        batch_release(b);
-        return rc;
-    }
-    *out = b;
+    HIPCHK(h, batch_alloc(b.get(), &b->d_reads, b->reads_bytes + 16));
+    HIPCHK(h, batch_alloc(b.get(), &b->d_refs, b->refs_bytes + 16));
+    HIPCHK(h, batch_alloc(b.get(), &b->d_read_off, sizeof(uint32_t) * (size_t)(n + 1)));
+    HIPCHK(h, batch_alloc(b.get(), &b->d_ref_off, sizeof(uint32_t) * (size_t)(n + 1)));
+    HIPCHK(h, hipMemcpyAsync(b->d_reads, reads, b->reads_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(b->d_refs, refs, b->refs_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(b->d_read_off, read_off, sizeof(uint32_t) * (size_t)(n + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(b->d_ref_off, ref_off, sizeof(uint32_t) * (size_t)(n + 1), hipMemcpyHostToDevice, h->stream));
+    rc = batch_finish(h, b.get());
+    if (rc) return rc;
+    *out = b.release();
     return ASM_OK;
 }
 
@@ -991,84 +1005,58 @@ int asm_batch_generate(asm_handle* h, const asm_gen_config* cfg, int64_t first, 
     if (!h || !out || n < 0 || first < 0) return fail(h, ASM_EINVAL, "asm_batch_generate: bad arguments");
     int rc = check_gen(cfg);
     if (rc) return fail(h, rc, g_err);
-    if (greedy_mode != ASM_GREEDY_CLEAN && greedy_mode != ASM_GREEDY_SEQUENTIAL)
-        return fail(h, ASM_EINVAL, "asm_batch_generate: unknown greedy_mode");
+    BatchPtr b;
+    rc = batch_new(h, n, greedy_mode, "asm_batch_generate", b);
+    if (rc) return rc;
     *out = nullptr;
     HIPCHK(h, hipSetDevice(h->device));
-    asm_batch* b = new asm_batch;
-    b->owner = h, b->owner_serial = h->serial;
-    b->n = n;
-    b->greedy_mode = greedy_mode;
-    uint32_t *d_m = nullptr, *d_n = nullptr, *d_max = nullptr;
-    void* d_tmp = nullptr;
-    rc = ASM_OK;
-    do {
-#define TRY(call)                                                  \
-    if ((call) != hipSuccess) {                                    \
-        rc = fail(h, ASM_ENODEVICE, std::string(#call) + " failed"); \
-        break;                                                     \
+    const size_t cnt = (size_t)n + 1;
+    Scratch<uint32_t> d_m(h), d_n(h), d_max(h);
+    Scratch<void> d_tmp(h);
+    HIPCHK(h, d_m.alloc(sizeof(uint32_t) * cnt));
+    HIPCHK(h, d_n.alloc(sizeof(uint32_t) * cnt));
+    HIPCHK(h, d_max.alloc(sizeof(uint32_t) * 2));
+    HIPCHK(h, batch_alloc(b.get(), &b->d_read_off, sizeof(uint32_t) * cnt));
+    HIPCHK(h, batch_alloc(b.get(), &b->d_ref_off, sizeof(uint32_t) * cnt));
+    HIPCHK(h, hipMemsetAsync(d_m.p, 0, sizeof(uint32_t) * cnt, h->stream));
+    HIPCHK(h, hipMemsetAsync(d_n.p, 0, sizeof(uint32_t) * cnt, h->stream));
+    if (n > 0) {
+        hipLaunchKernelGGL(gen_lengths_kernel, dim3(grid_for(n)), dim3(ASM_BLOCK), 0, h->stream, *cfg, (long)first, (long)n,
+                           d_m.p, d_n.p);
+        HIPCHK(h, hipGetLastError());
     }
-        const size_t cnt = (size_t)n + 1;
-        TRY(pool_alloc(h, (void**)&d_m, sizeof(uint32_t) * cnt));
-        TRY(pool_alloc(h, (void**)&d_n, sizeof(uint32_t) * cnt));
-        TRY(pool_alloc(h, (void**)&d_max, sizeof(uint32_t) * 2));
-        TRY(pool_alloc(h, (void**)&b->d_read_off, sizeof(uint32_t) * cnt));
-        TRY(pool_alloc(h, (void**)&b->d_ref_off, sizeof(uint32_t) * cnt));
-        TRY(hipMemsetAsync(d_m, 0, sizeof(uint32_t) * cnt, h->stream));
-        TRY(hipMemsetAsync(d_n, 0, sizeof(uint32_t) * cnt, h->stream));
-        if (n > 0) {
-            hipLaunchKernelGGL(gen_lengths_kernel, dim3(grid_for(n)), dim3(ASM_BLOCK), 0, h->stream, *cfg, (long)first,
-                               (long)n, d_m, d_n);
-            TRY(hipGetLastError());
-        }
-        size_t tmp_bytes = 0, t2 = 0;
-        TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_m, b->d_read_off, (int)cnt, h->stream));
-        TRY(hipcub::DeviceReduce::Max(nullptr, t2, d_n, d_max, (int)cnt, h->stream));
-        if (t2 > tmp_bytes) tmp_bytes = t2;
-        TRY(pool_alloc(h, &d_tmp, tmp_bytes + 16));
-        TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_m, b->d_read_off, (int)cnt, h->stream));
-        TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_n, b->d_ref_off, (int)cnt, h->stream));
-        TRY(hipcub::DeviceReduce::Max(d_tmp, tmp_bytes, d_m, d_max, (int)cnt, h->stream));
-        TRY(hipcub::DeviceReduce::Max(d_tmp, tmp_bytes, d_n, d_max + 1, (int)cnt, h->stream));
-        uint32_t tot[2] = {0, 0}, mx[2] = {0, 0};
-        TRY(hipMemcpyAsync(&tot[0], b->d_read_off + n, 4, hipMemcpyDeviceToHost, h->stream));
-        TRY(hipMemcpyAsync(&tot[1], b->d_ref_off + n, 4, hipMemcpyDeviceToHost, h->stream));
-        TRY(hipMemcpyAsync(mx, d_max, 8, hipMemcpyDeviceToHost, h->stream));
-        TRY(hipStreamSynchronize(h->stream));
-        /* 32-bit offsets: the host-side bound (n * worst length) must stay below 4 GiB */
-        {
-            double bound = (double)n * (double)(cfg->len_hi * 2 + 2);
-            if (bound >= 4294967295.0 && (double)n * (double)(mx[0] > mx[1] ? mx[0] : mx[1]) >= 4294967295.0) {
-                rc = fail(h, ASM_EUNSUPPORTED, "asm_batch_generate: batch exceeds 4 GiB of text; split it");
-                break;
-            }
-        }
-        b->reads_bytes = tot[0];
-        b->refs_bytes = tot[1];
-        b->maxlen = (int)(mx[0] > mx[1] ? mx[0] : mx[1]);
-        if (b->maxlen > ASM_MAX_LENGTH) {
-            rc = fail(h, ASM_EUNSUPPORTED, "asm_batch_generate: a generated sequence exceeds ASM_MAX_LENGTH");
-            break;
-        }
-        TRY(pool_alloc(h, (void**)&b->d_reads, b->reads_bytes + 16));
-        TRY(pool_alloc(h, (void**)&b->d_refs, b->refs_bytes + 16));
-        if (n > 0) {
-            hipLaunchKernelGGL(gen_fill_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, *cfg, (long)first,
-                               (long)n, b->d_read_off, b->d_ref_off, b->d_reads, b->d_refs);
-            TRY(hipGetLastError());
-        }
-#undef TRY
-        rc = batch_finish(h, b);
-    } while (0);
-    pool_free(h, d_m);
-    pool_free(h, d_n);
-    pool_free(h, d_max);
-    pool_free(h, d_tmp);
-    if (rc) {
-        batch_release(b);
-        return rc;
+    size_t tmp_bytes = 0, t2 = 0;
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_m.p, b->d_read_off, (int)cnt, h->stream));
+    HIPCHK(h, hipcub::DeviceReduce::Max(nullptr, t2, d_n.p, d_max.p, (int)cnt, h->stream));
+    if (t2 > tmp_bytes) tmp_bytes = t2;
+    HIPCHK(h, d_tmp.alloc(tmp_bytes + 16));
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_m.p, b->d_read_off, (int)cnt, h->stream));
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_n.p, b->d_ref_off, (int)cnt, h->stream));
+    HIPCHK(h, hipcub::DeviceReduce::Max(d_tmp.p, tmp_bytes, d_m.p, d_max.p, (int)cnt, h->stream));
+    HIPCHK(h, hipcub::DeviceReduce::Max(d_tmp.p, tmp_bytes, d_n.p, d_max.p + 1, (int)cnt, h->stream));
+    uint32_t tot[2] = {0, 0}, mx[2] = {0, 0};
+    HIPCHK(h, hipMemcpyAsync(&tot[0], b->d_read_off + n, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&tot[1], b->d_ref_off + n, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(mx, d_max.p, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    /* 32-bit offsets: the host-side bound (n * worst length) must stay below 4 GiB */
+    const double bound = (double)n * (double)(cfg->len_hi * 2 + 2);
+    if (bound >= 4294967295.0 && (double)n * (double)(mx[0] > mx[1] ? mx[0] : mx[1]) >= 4294967295.0)
+        return fail(h, ASM_EUNSUPPORTED, "asm_batch_generate: batch exceeds 4 GiB of text; split it");
+    b->reads_bytes = tot[0];
+    b->refs_bytes = tot[1];
+    b->maxlen = (int)(mx[0] > mx[1] ? mx[0] : mx[1]);
+    if (b->maxlen > ASM_MAX_LENGTH) return fail(h, ASM_EUNSUPPORTED, "asm_batch_generate: a generated sequence exceeds ASM_MAX_LENGTH");
+    HIPCHK(h, batch_alloc(b.get(), &b->d_reads, b->reads_bytes + 16));
+    HIPCHK(h, batch_alloc(b.get(), &b->d_refs, b->refs_bytes + 16));
+    if (n > 0) {
+        hipLaunchKernelGGL(gen_fill_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, *cfg, (long)first, (long)n,
+                           b->d_read_off, b->d_ref_off, b->d_reads, b->d_refs);
+        HIPCHK(h, hipGetLastError());
     }
-    *out = b;
+    rc = batch_finish(h, b.get());
+    if (rc) return rc;
+    *out = b.release();
     return ASM_OK;
 }
 
@@ -1104,8 +1092,9 @@ int asm_batch_from_hits(asm_handle* h, const asm_reference* ref, int64_t n, cons
                         const uint64_t* hit_pos, int greedy_mode, asm_batch** out) {
     if (!h || !ref || !out || n < 0 || !read_off || (n > 0 && (!reads || !hit_pos)))
         return fail(h, ASM_EINVAL, "asm_batch_from_hits: bad arguments");
-    if (greedy_mode != ASM_GREEDY_CLEAN && greedy_mode != ASM_GREEDY_SEQUENTIAL)
-        return fail(h, ASM_EINVAL, "asm_batch_from_hits: unknown greedy_mode");
+    BatchPtr b;
+    int rc = batch_new(h, n, greedy_mode, "asm_batch_from_hits", b);
+    if (rc) return rc;
     *out = nullptr;
     HIPCHK(h, hipSetDevice(h->device));
     int maxlen = 0;
@@ -1115,61 +1104,42 @@ int asm_batch_from_hits(asm_handle* h, const asm_reference* ref, int64_t n, cons
         maxlen = m > maxlen ? m : maxlen;
     }
     if (maxlen + 1 > ASM_MAX_LENGTH) return fail(h, ASM_EUNSUPPORTED, "asm_batch_from_hits: a read is longer than ASM_MAX_LENGTH - 1");
-    asm_batch* b = new asm_batch;
-    b->owner = h, b->owner_serial = h->serial;
-    b->n = n;
     b->maxlen = maxlen + 1; /* the window is one base longer than the read (mapper/main.cpp:80) */
-    b->greedy_mode = greedy_mode;
     b->reads_bytes = n ? read_off[n] : 0;
-    unsigned long long* d_pos = nullptr;
-    uint32_t* d_wl = nullptr;
-    void* d_tmp = nullptr;
-    int rc = ASM_OK;
-    do {
-#define TRY(call)                                                        \
-    if ((call) != hipSuccess) {                                          \
-        rc = fail(h, ASM_ENODEVICE, std::string(#call) + " failed");     \
-        break;                                                           \
+    const size_t cnt = (size_t)n + 1;
+    Scratch<unsigned long long> d_pos(h);
+    Scratch<uint32_t> d_wl(h);
+    Scratch<void> d_tmp(h);
+    HIPCHK(h, batch_alloc(b.get(), &b->d_reads, b->reads_bytes + 16));
+    HIPCHK(h, batch_alloc(b.get(), &b->d_read_off, sizeof(uint32_t) * cnt));
+    HIPCHK(h, batch_alloc(b.get(), &b->d_ref_off, sizeof(uint32_t) * cnt));
+    HIPCHK(h, d_pos.alloc(sizeof(unsigned long long) * cnt));
+    HIPCHK(h, d_wl.alloc(sizeof(uint32_t) * cnt));
+    HIPCHK(h, hipMemcpyAsync(b->d_reads, reads, b->reads_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(b->d_read_off, read_off, sizeof(uint32_t) * cnt, hipMemcpyHostToDevice, h->stream));
+    if (n) HIPCHK(h, hipMemcpyAsync(d_pos.p, hit_pos, sizeof(unsigned long long) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(hit_window_lengths_kernel, dim3(grid_for(n + 1)), dim3(ASM_BLOCK), 0, h->stream, b->d_read_off, d_pos.p,
+                       (unsigned long long)ref->len, (long)n, d_wl.p);
+    HIPCHK(h, hipGetLastError());
+    size_t tmp_bytes = 0;
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_wl.p, b->d_ref_off, (int)cnt, h->stream));
+    HIPCHK(h, d_tmp.alloc(tmp_bytes + 16));
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_wl.p, b->d_ref_off, (int)cnt, h->stream));
+    uint32_t total = 0;
+    HIPCHK(h, hipMemcpyAsync(&total, b->d_ref_off + n, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    b->refs_bytes = total;
+    HIPCHK(h, batch_alloc(b.get(), &b->d_refs, b->refs_bytes + 16));
+    if (n) {
+        int64_t blocks = (n + 3) / 4;
+        blocks = blocks > 256 * 16 ? 256 * 16 : blocks;
+        hipLaunchKernelGGL(hit_window_gather_kernel, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, h->stream, ref->d_text, d_pos.p,
+                           b->d_ref_off, (long)n, b->d_refs);
+        HIPCHK(h, hipGetLastError());
     }
-        const size_t cnt = (size_t)n + 1;
-        TRY(pool_alloc(h, (void**)&b->d_reads, b->reads_bytes + 16));
-        TRY(pool_alloc(h, (void**)&b->d_read_off, sizeof(uint32_t) * cnt));
-        TRY(pool_alloc(h, (void**)&b->d_ref_off, sizeof(uint32_t) * cnt));
-        TRY(pool_alloc(h, (void**)&d_pos, sizeof(unsigned long long) * cnt));
-        TRY(pool_alloc(h, (void**)&d_wl, sizeof(uint32_t) * cnt));
-        TRY(hipMemcpyAsync(b->d_reads, reads, b->reads_bytes, hipMemcpyHostToDevice, h->stream));
-        TRY(hipMemcpyAsync(b->d_read_off, read_off, sizeof(uint32_t) * cnt, hipMemcpyHostToDevice, h->stream));
-        if (n) TRY(hipMemcpyAsync(d_pos, hit_pos, sizeof(unsigned long long) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(hit_window_lengths_kernel, dim3(grid_for(n + 1)), dim3(ASM_BLOCK), 0, h->stream, b->d_read_off,
-                           d_pos, (unsigned long long)ref->len, (long)n, d_wl);
-        TRY(hipGetLastError());
-        size_t tmp_bytes = 0;
-        TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_wl, b->d_ref_off, (int)cnt, h->stream));
-        TRY(pool_alloc(h, &d_tmp, tmp_bytes + 16));
-        TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_wl, b->d_ref_off, (int)cnt, h->stream));
-        uint32_t total = 0;
-        TRY(hipMemcpyAsync(&total, b->d_ref_off + n, 4, hipMemcpyDeviceToHost, h->stream));
-        TRY(hipStreamSynchronize(h->stream));
-        b->refs_bytes = total;
-        TRY(pool_alloc(h, (void**)&b->d_refs, b->refs_bytes + 16));
-        if (n) {
-            int64_t blocks = (n + 3) / 4;
-            blocks = blocks > 256 * 16 ? 256 * 16 : blocks;
-            hipLaunchKernelGGL(hit_window_gather_kernel, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, h->stream, ref->d_text,
-                               d_pos, b->d_ref_off, (long)n, b->d_refs);
-            TRY(hipGetLastError());
-        }
-#undef TRY
-        rc = batch_finish(h, b);
-    } while (0);
-    pool_free(h, d_pos);
-    pool_free(h, d_wl);
-    pool_free(h, d_tmp);
-    if (rc) {
-        batch_release(b);
-        return rc;
-    }
-    *out = b;
+    rc = batch_finish(h, b.get());
+    if (rc) return rc;
+    *out = b.release();
     return ASM_OK;
 }
 
@@ -1541,21 +1511,17 @@ int asm_align_batch(asm_handle* h, int aligner, int64_t n, const char* reads, co
     if (!h || !penalties) return fail(h, ASM_EINVAL, "asm_align_batch: NULL argument");
     int rc = check_params(h, aligner, p);
     if (rc) return rc;
-    asm_batch* b = nullptr;
-    rc = asm_batch_upload(h, n, reads, read_off, refs, ref_off, greedy_mode, &b);
+    asm_batch* raw = nullptr;
+    rc = asm_batch_upload(h, n, reads, read_off, refs, ref_off, greedy_mode, &raw);
     if (rc) return rc;
-    int32_t* d_out = nullptr;
-    if (pool_alloc(h, (void**)&d_out, sizeof(int32_t) * (size_t)(n > 0 ? n : 1)) != hipSuccess) {
-        batch_release(b);
-        return fail(h, ASM_ENOMEM, "asm_align_batch: hipMalloc failed");
-    }
-    rc = asm_align_batch_async(h, b, aligner, p, d_out);
-    if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, ASM_ENODEVICE, "asm_align_batch: kernel failed");
-    if (!rc && n > 0 && hipMemcpy(penalties, d_out, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(h, ASM_ENODEVICE, "asm_align_batch: copy back failed");
-    pool_free(h, d_out);
-    batch_release(b);
-    return rc;
+    BatchPtr b(raw);
+    Scratch<int32_t> d_out(h);
+    HIPCHK(h, d_out.alloc(sizeof(int32_t) * (size_t)(n > 0 ? n : 1)));
+    rc = asm_align_batch_async(h, b.get(), aligner, p, d_out.p);
+    if (rc) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (n > 0) HIPCHK(h, hipMemcpy(penalties, d_out.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    return ASM_OK;
 }
 
 int asm_simd_ed_batch_async(asm_handle* h, const asm_batch* b, int ed_threshold, int shd_enable, int mode,
@@ -1601,40 +1567,29 @@ int asm_simd_ed_mode_batch_async(asm_handle* h, const asm_batch* b, int ed_thres
     }
     /* sequential: resolve the verdict chain in batch order with two last-setter scans */
     const int init_fe = state ? state[0] : 0, init_fd = state ? state[1] : 0, init_conv = state ? state[2] : 0;
-    int32_t *d_a = nullptr, *d_b = nullptr;
     int32_t last_setter = -1, last_conv = -1;
-    void* d_tmp = nullptr;
     size_t tmp_bytes = 0;
-    do {
-#define TRY(call)                                                  \
-    if ((call) != hipSuccess) {                                    \
-        rc = fail(h, ASM_ENODEVICE, std::string(#call) + " failed"); \
-        break;                                                     \
+    Scratch<int32_t> d_a(h), d_b(h);
+    Scratch<void> d_tmp(h);
+    HIPCHK(h, d_a.alloc(sizeof(int32_t) * (size_t)n));
+    HIPCHK(h, d_b.alloc(sizeof(int32_t) * (size_t)n));
+    HIPCHK(h, hipcub::DeviceScan::InclusiveScan(nullptr, tmp_bytes, d_a.p, d_b.p, LastSetter(), (int)n, h->stream));
+    HIPCHK(h, d_tmp.alloc(tmp_bytes + 16));
+    hipLaunchKernelGGL(simd_ed_setter_kernel, g, t, 0, h->stream, (const int32_t*)d_ed, n, d_a.p);
+    HIPCHK(h, hipcub::DeviceScan::InclusiveScan(d_tmp.p, tmp_bytes, d_a.p, d_b.p, LastSetter(), (int)n, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&last_setter, d_b.p + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    hipLaunchKernelGGL(simd_ed_converge_kernel, g, t, 0, h->stream, (const int32_t*)d_ed, (const int32_t*)d_b.p, n, init_fe,
+                       init_fd, d_a.p);
+    HIPCHK(h, hipcub::DeviceScan::InclusiveScan(d_tmp.p, tmp_bytes, d_a.p, d_b.p, LastSetter(), (int)n, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&last_conv, d_b.p + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    hipLaunchKernelGGL(simd_ed_verdict_kernel, g, t, 0, h->stream, d_ed, (const int32_t*)d_b.p, n, ed_threshold, init_conv);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream)); /* last_setter and last_conv are read below */
+    if (state) { /* the state the next batch of the same stream of pairs starts from */
+        if (last_setter >= 0) state[0] = last_setter & 0xff, state[1] = last_setter >> 8;
+        if (last_conv >= 0) state[2] = last_conv;
     }
-        TRY(big_malloc(h, (void**)&d_a, sizeof(int32_t) * (size_t)n));
-        TRY(big_malloc(h, (void**)&d_b, sizeof(int32_t) * (size_t)n));
-        TRY(hipcub::DeviceScan::InclusiveScan(nullptr, tmp_bytes, d_a, d_b, LastSetter(), (int)n, h->stream));
-        TRY(big_malloc(h, &d_tmp, tmp_bytes + 16));
-        hipLaunchKernelGGL(simd_ed_setter_kernel, g, t, 0, h->stream, (const int32_t*)d_ed, n, d_a);
-        TRY(hipcub::DeviceScan::InclusiveScan(d_tmp, tmp_bytes, d_a, d_b, LastSetter(), (int)n, h->stream));
-        TRY(hipMemcpyAsync(&last_setter, d_b + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        hipLaunchKernelGGL(simd_ed_converge_kernel, g, t, 0, h->stream, (const int32_t*)d_ed, (const int32_t*)d_b, n, init_fe,
-                           init_fd, d_a);
-        TRY(hipcub::DeviceScan::InclusiveScan(d_tmp, tmp_bytes, d_a, d_b, LastSetter(), (int)n, h->stream));
-        TRY(hipMemcpyAsync(&last_conv, d_b + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        hipLaunchKernelGGL(simd_ed_verdict_kernel, g, t, 0, h->stream, d_ed, (const int32_t*)d_b, n, ed_threshold, init_conv);
-        TRY(hipGetLastError());
-        TRY(hipStreamSynchronize(h->stream)); /* the scratch below is freed on return */
-        if (state) { /* the state the next batch of the same stream of pairs starts from */
-            if (last_setter >= 0) state[0] = last_setter & 0xff, state[1] = last_setter >> 8;
-            if (last_conv >= 0) state[2] = last_conv;
-        }
-#undef TRY
-    } while (0);
-    if (d_a) (void)hipFree(d_a);
-    if (d_b) (void)hipFree(d_b);
-    if (d_tmp) (void)hipFree(d_tmp);
-    return rc;
+    return ASM_OK;
 }
 
 static int simd_ed_affine_launch(asm_handle* h, const asm_batch* b, int gap_threshold, int af_threshold, int x, int o, int e, int mode,
@@ -1807,11 +1762,26 @@ int asm_profile_read(asm_handle* h, float* ms, int cap_calls, int* n_calls) {
     return ASM_OK;
 }
 
+/* repack = 2/3: the other set of planes becomes the batch's current one.  Its own inverse: a call whose pack fails flips back. */
+static void batch_flip_planes(asm_batch* b) {
+    std::swap(b->d_planes, b->d_planes_alt);
+    std::swap(b->d_lens, b->d_lens_alt);
+    b->cur ^= 1;
+    for (int q = 0; q < b->nb; q++) {
+        b->bk[q].planes = b->d_planes + b->pb.plane_off[q];
+        b->bk[q].lens = b->d_lens + b->pb.start[q];
+    }
+}
+
 int asm_run_benchmark_async(asm_handle* h, asm_batch* b, const asm_params* p, int repack, int32_t* d_nw,
                             int32_t* d_leap, int32_t* d_greedy, const int32_t* d_answers,
                             unsigned long long* d_counters) {
     if (!h || !b || !p) return fail(h, ASM_EINVAL, "asm_run_benchmark_async: NULL argument");
-    int rc = ASM_OK;
+    /* the aligners check again; these checks come before anything is enqueued or flipped */
+    int rc = d_nw ? check_params(h, ASM_NW, p, b->maxlen) : ASM_OK;
+    if (!rc && d_leap) rc = check_params(h, ASM_LEAP, p, b->maxlen);
+    if (!rc && d_greedy) rc = check_params(h, ASM_GREEDY, p, b->maxlen);
+    if (rc) return rc;
     // Without NW in the mask, wide-band LEAP (four threads per pair, asm_wave.h) is scheduled by the Greedy penalties:
     // Greedy first, on the same stream — at wide bands both kernels are VALU-bound and side by side they gain nothing (C3:
     // 23.8 ms against 23.6 in a row), while the work-sorted LEAP saves a quarter of its time.
@@ -1848,22 +1818,15 @@ int asm_run_benchmark_async(asm_handle* h, asm_batch* b, const asm_params* p, in
          * read two calls ago (ev_consumed).  The caller guarantees that nothing enqueued since the previous call changes what
          * pack reads (the resident ASCII, the tails). */
         HIPCHK(h, hipSetDevice(h->device));
-        if (!b->d_planes_alt) {
-            HIPCHK(h, pool_alloc(h, (void**)&b->d_planes_alt, sizeof(uint4) * b->planes_total));
-            HIPCHK(h, pool_alloc(h, (void**)&b->d_lens_alt, sizeof(uint32_t) * (size_t)b->n));
-            for (hipEvent_t& ev : b->ev_consumed) HIPCHK(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        if (!b->d_planes_alt) HIPCHK(h, batch_alloc(b, &b->d_planes_alt, sizeof(uint4) * b->planes_total));
+        if (!b->d_lens_alt) HIPCHK(h, batch_alloc(b, &b->d_lens_alt, sizeof(uint32_t) * (size_t)b->n));
+        if (!b->ev_consumed[1]) {
+            for (hipEvent_t& ev : b->ev_consumed)
+                if (!ev) HIPCHK(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
             HIPCHK(h, hipEventRecord(b->ev_consumed[0], main_stream)); /* everything enqueued so far (the batch's creation) */
             HIPCHK(h, hipEventRecord(b->ev_consumed[1], main_stream));
         }
-        const int nxt = b->cur ^ 1;
-        std::swap(b->d_planes, b->d_planes_alt);
-        std::swap(b->d_lens, b->d_lens_alt);
-        b->cur = nxt;
-        for (int q = 0; q < b->nb; q++) {
-            b->bk[q].planes = b->d_planes + b->pb.plane_off[q];
-            b->bk[q].lens = b->d_lens + b->pb.start[q];
-        }
-        HIPCHK(h, hipStreamWaitEvent(h->pack_stream, b->ev_consumed[nxt], 0));
+        HIPCHK(h, hipStreamWaitEvent(h->pack_stream, b->ev_consumed[b->cur ^ 1], 0));
         /* Overlapped calls on DIFFERENT batches (a caller rotating over several resident batches): the plane set of this batch
          * was consumed long ago, so nothing above holds the pack back, and the pack chain would run as many calls ahead as the
          * host has enqueued — thousands of short pack workgroups dispatched beside every persistent Greedy kernel (0.258 ms per
@@ -1880,9 +1843,11 @@ int asm_run_benchmark_async(asm_handle* h, asm_batch* b, const asm_params* p, in
          * pack chain runs a call ahead and meets no Greedy launch: no gate there (0.229 against 0.251 gated) */
         if (h->gate_set && repack == 2) HIPCHK(h, hipStreamWaitEvent(h->pack_stream, h->ev_gate, 0));
         PROF(0, 0, h->pack_stream)
+        batch_flip_planes(b);
         h->stream = h->pack_stream;
         rc = asm_batch_pack_async(h, b);
         h->stream = main_stream;
+        if (rc) batch_flip_planes(b); /* back to the set that is packed */
         PROF(0, 1, h->pack_stream)
         if (!rc) {
             HIPCHK(h, hipEventRecord(h->ev_packed, h->pack_stream));
@@ -2030,99 +1995,77 @@ namespace {
 using asm_host::NlScan;
 using asm_host::scan_newlines;
 
-/* A batch out of raw text already in HBM (n pairs = 2n lines, every line ending in '\n'). */
-static int batch_from_device_text(asm_handle* h, const char* d_raw, size_t nbytes, int64_t n, int greedy_mode, asm_batch** out) {
-    *out = nullptr;
-    asm_batch* b = new asm_batch;
-    b->owner = h, b->owner_serial = h->serial;
-    b->n = n;
-    b->greedy_mode = greedy_mode;
-    uint32_t *d_tile = nullptr, *d_tbase = nullptr, *d_nl = nullptr, *d_m = nullptr, *d_n = nullptr, *d_max = nullptr;
-    unsigned long long *d_sa = nullptr, *d_sb = nullptr;
-    void* d_tmp = nullptr;
-    int rc = ASM_OK;
-    do {
-#define TRY(call)                                                        \
-    if ((call) != hipSuccess) {                                          \
-        rc = fail(h, ASM_ENODEVICE, std::string(#call) + " failed");     \
-        break;                                                           \
+/* Fills batch b (n pairs = 2n lines, every line ending in '\n') out of raw text already in HBM. */
+static int batch_from_device_text(asm_handle* h, const char* d_raw, size_t nbytes, asm_batch* b) {
+    const int64_t n = b->n;
+    const size_t cnt = (size_t)n + 1;
+    const long ntiles = (long)((nbytes + SEQ_TILE - 1) / SEQ_TILE);
+    Scratch<uint32_t> d_tile(h), d_tbase(h), d_nl(h), d_m(h), d_n(h), d_max(h);
+    Scratch<unsigned long long> d_sa(h), d_sb(h);
+    Scratch<void> d_tmp(h);
+    HIPCHK(h, batch_alloc(b, &b->d_read_off, sizeof(uint32_t) * cnt));
+    HIPCHK(h, batch_alloc(b, &b->d_ref_off, sizeof(uint32_t) * cnt));
+    HIPCHK(h, d_m.alloc(sizeof(uint32_t) * cnt));
+    HIPCHK(h, d_n.alloc(sizeof(uint32_t) * cnt));
+    HIPCHK(h, d_sa.alloc(sizeof(unsigned long long) * cnt));
+    HIPCHK(h, d_sb.alloc(sizeof(unsigned long long) * cnt));
+    HIPCHK(h, d_nl.alloc(sizeof(uint32_t) * (2 * (size_t)n + 2)));
+    HIPCHK(h, d_tile.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1)));
+    HIPCHK(h, d_tbase.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1)));
+    HIPCHK(h, d_max.alloc(16));
+    HIPCHK(h, hipMemsetAsync(d_max.p, 0, 16, h->stream));
+    size_t tmp_bytes = 0, t2 = 0;
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_tile.p, d_tbase.p, (int)ntiles, h->stream));
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, t2, d_m.p, b->d_read_off, (int)cnt, h->stream));
+    tmp_bytes = t2 > tmp_bytes ? t2 : tmp_bytes;
+    HIPCHK(h, d_tmp.alloc(tmp_bytes + 16));
+    if (n > 0) {
+        hipLaunchKernelGGL(seq_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, h->stream, d_raw, (long)nbytes, d_tile.p);
+        HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_tile.p, d_tbase.p, (int)ntiles, h->stream));
+        hipLaunchKernelGGL(seq_index_kernel, dim3((unsigned)ntiles), dim3(256), 0, h->stream, d_raw, (long)nbytes,
+                           (const uint32_t*)d_tbase.p, d_nl.p, (long)(2 * n));
     }
-        const size_t cnt = (size_t)n + 1;
-        const long ntiles = (long)((nbytes + SEQ_TILE - 1) / SEQ_TILE);
-        TRY(pool_alloc(h, (void**)&b->d_read_off, sizeof(uint32_t) * cnt));
-        TRY(pool_alloc(h, (void**)&b->d_ref_off, sizeof(uint32_t) * cnt));
-        TRY(pool_alloc(h, (void**)&d_m, sizeof(uint32_t) * cnt));
-        TRY(pool_alloc(h, (void**)&d_n, sizeof(uint32_t) * cnt));
-        TRY(pool_alloc(h, (void**)&d_sa, sizeof(unsigned long long) * cnt));
-        TRY(pool_alloc(h, (void**)&d_sb, sizeof(unsigned long long) * cnt));
-        TRY(pool_alloc(h, (void**)&d_nl, sizeof(uint32_t) * (2 * (size_t)n + 2)));
-        TRY(pool_alloc(h, (void**)&d_tile, sizeof(uint32_t) * ((size_t)ntiles + 1)));
-        TRY(pool_alloc(h, (void**)&d_tbase, sizeof(uint32_t) * ((size_t)ntiles + 1)));
-        TRY(pool_alloc(h, (void**)&d_max, 16));
-        TRY(hipMemsetAsync(d_max, 0, 16, h->stream));
-        size_t tmp_bytes = 0, t2 = 0;
-        TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_tile, d_tbase, (int)ntiles, h->stream));
-        TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, d_m, b->d_read_off, (int)cnt, h->stream));
-        tmp_bytes = t2 > tmp_bytes ? t2 : tmp_bytes;
-        TRY(pool_alloc(h, &d_tmp, tmp_bytes + 16));
-        if (n > 0) {
-            hipLaunchKernelGGL(seq_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, h->stream, d_raw, (long)nbytes, d_tile);
-            TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_tile, d_tbase, (int)ntiles, h->stream));
-            hipLaunchKernelGGL(seq_index_kernel, dim3((unsigned)ntiles), dim3(256), 0, h->stream, d_raw, (long)nbytes,
-                               (const uint32_t*)d_tbase, d_nl, (long)(2 * n));
-        }
-        hipLaunchKernelGGL(seq_lengths_kernel, dim3(grid_for(n + 1)), dim3(ASM_BLOCK), 0, h->stream, (const uint32_t*)d_nl, (long)n,
-                           d_m, d_n, d_sa, d_sb);
-        TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_m, b->d_read_off, (int)cnt, h->stream));
-        TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_bytes, d_n, b->d_ref_off, (int)cnt, h->stream));
-        if (n > 0) {
-            int64_t blocks = (n + ASM_BLOCK - 1) / ASM_BLOCK;
-            blocks = blocks > 1024 ? 1024 : blocks;
-            hipLaunchKernelGGL(seq_max_kernel, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, h->stream, (const uint32_t*)d_m,
-                               (const uint32_t*)d_n, (long)n, d_max);
-        }
-        TRY(hipGetLastError());
-        uint32_t tot[2] = {0, 0}, mx = 0;
-        TRY(hipMemcpyAsync(&tot[0], b->d_read_off + n, 4, hipMemcpyDeviceToHost, h->stream));
-        TRY(hipMemcpyAsync(&tot[1], b->d_ref_off + n, 4, hipMemcpyDeviceToHost, h->stream));
-        TRY(hipMemcpyAsync(&mx, d_max, 4, hipMemcpyDeviceToHost, h->stream));
-        TRY(hipStreamSynchronize(h->stream));
-        if ((int)mx > ASM_MAX_LENGTH) {
-            rc = fail(h, ASM_EUNSUPPORTED, "streamed file: a sequence is longer than ASM_MAX_LENGTH");
-            break;
-        }
-        b->reads_bytes = tot[0], b->refs_bytes = tot[1], b->maxlen = (int)mx;
-        TRY(pool_alloc(h, (void**)&b->d_reads, b->reads_bytes + 16));
-        TRY(pool_alloc(h, (void**)&b->d_refs, b->refs_bytes + 16));
-        if (n > 0) {
-            int64_t blocks = (n + 3) / 4;
-            blocks = blocks > 256 * 16 ? 256 * 16 : blocks;
-            hipLaunchKernelGGL(seq_gather_kernel, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, h->stream, d_raw,
-                               (const unsigned long long*)d_sa, (const uint32_t*)b->d_read_off, (long)n, b->d_reads);
-            hipLaunchKernelGGL(seq_gather_kernel, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, h->stream, d_raw,
-                               (const unsigned long long*)d_sb, (const uint32_t*)b->d_ref_off, (long)n, b->d_refs);
-            TRY(hipGetLastError());
-        }
-#undef TRY
-        rc = batch_finish(h, b);
-    } while (0);
-    pool_free(h, d_tile), pool_free(h, d_tbase), pool_free(h, d_nl), pool_free(h, d_m), pool_free(h, d_n);
-    pool_free(h, d_sa), pool_free(h, d_sb), pool_free(h, d_max), pool_free(h, d_tmp);
-    if (rc) {
-        batch_release(b);
-        return rc;
+    hipLaunchKernelGGL(seq_lengths_kernel, dim3(grid_for(n + 1)), dim3(ASM_BLOCK), 0, h->stream, (const uint32_t*)d_nl.p, (long)n,
+                       d_m.p, d_n.p, d_sa.p, d_sb.p);
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_m.p, b->d_read_off, (int)cnt, h->stream));
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_n.p, b->d_ref_off, (int)cnt, h->stream));
+    if (n > 0) {
+        int64_t blocks = (n + ASM_BLOCK - 1) / ASM_BLOCK;
+        blocks = blocks > 1024 ? 1024 : blocks;
+        hipLaunchKernelGGL(seq_max_kernel, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, h->stream, (const uint32_t*)d_m.p,
+                           (const uint32_t*)d_n.p, (long)n, d_max.p);
     }
-    *out = b;
-    return ASM_OK;
+    HIPCHK(h, hipGetLastError());
+    uint32_t tot[2] = {0, 0}, mx = 0;
+    HIPCHK(h, hipMemcpyAsync(&tot[0], b->d_read_off + n, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&tot[1], b->d_ref_off + n, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&mx, d_max.p, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if ((int)mx > ASM_MAX_LENGTH) return fail(h, ASM_EUNSUPPORTED, "streamed file: a sequence is longer than ASM_MAX_LENGTH");
+    b->reads_bytes = tot[0], b->refs_bytes = tot[1], b->maxlen = (int)mx;
+    HIPCHK(h, batch_alloc(b, &b->d_reads, b->reads_bytes + 16));
+    HIPCHK(h, batch_alloc(b, &b->d_refs, b->refs_bytes + 16));
+    if (n > 0) {
+        int64_t blocks = (n + 3) / 4;
+        blocks = blocks > 256 * 16 ? 256 * 16 : blocks;
+        hipLaunchKernelGGL(seq_gather_kernel, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, h->stream, d_raw,
+                           (const unsigned long long*)d_sa.p, (const uint32_t*)b->d_read_off, (long)n, b->d_reads);
+        hipLaunchKernelGGL(seq_gather_kernel, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, h->stream, d_raw,
+                           (const unsigned long long*)d_sb.p, (const uint32_t*)b->d_ref_off, (long)n, b->d_refs);
+        HIPCHK(h, hipGetLastError());
+    }
+    return batch_finish(h, b);
 }
 
 }  // namespace
 
 int asm_batch_from_text(asm_handle* h, const char* text, size_t nbytes, int greedy_mode, asm_batch** out) {
     if (!h || !out || (!text && nbytes)) return fail(h, ASM_EINVAL, "asm_batch_from_text: bad argument");
-    if (greedy_mode != ASM_GREEDY_CLEAN && greedy_mode != ASM_GREEDY_SEQUENTIAL)
-        return fail(h, ASM_EINVAL, "asm_batch_from_text: unknown greedy_mode");
+    BatchPtr b;
+    int rc = batch_new(h, 0, greedy_mode, "asm_batch_from_text", b);
+    if (rc) return rc;
     if (nbytes >= 0xfffffff0ull) return fail(h, ASM_EUNSUPPORTED, "asm_batch_from_text: more than 4 GiB of text; split it");
+    *out = nullptr;
     HIPCHK(h, hipSetDevice(h->device));
     const bool open_line = nbytes && text[nbytes - 1] != '\n';
     NlScan sc = scan_newlines(text, nbytes, 8);
@@ -2130,14 +2073,15 @@ int asm_batch_from_text(asm_handle* h, const char* text, size_t nbytes, int gree
     const bool odd = (lines & 1) != 0; /* a read without its reference line: the reference gets an empty string there */
     const size_t total = nbytes + (open_line ? 1 : 0) + (odd ? 1 : 0);
     lines += odd ? 1 : 0;
-    char* d_raw = nullptr;
-    HIPCHK(h, pool_alloc(h, (void**)&d_raw, total + 32));
-    int rc = ASM_OK;
-    if (nbytes && hipMemcpyAsync(d_raw, text, nbytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = fail(h, ASM_ENODEVICE, "asm_batch_from_text: copy failed");
-    if (!rc && total > nbytes && hipMemsetAsync(d_raw + nbytes, '\n', total - nbytes, h->stream) != hipSuccess) rc = fail(h, ASM_ENODEVICE, "asm_batch_from_text: memset failed");
-    if (!rc) rc = batch_from_device_text(h, d_raw, total, lines / 2, greedy_mode, out);
-    pool_free(h, d_raw);
-    return rc;
+    Scratch<char> d_raw(h);
+    HIPCHK(h, d_raw.alloc(total + 32));
+    if (nbytes) HIPCHK(h, hipMemcpyAsync(d_raw.p, text, nbytes, hipMemcpyHostToDevice, h->stream));
+    if (total > nbytes) HIPCHK(h, hipMemsetAsync(d_raw.p + nbytes, '\n', total - nbytes, h->stream));
+    b->n = lines / 2;
+    rc = batch_from_device_text(h, d_raw.p, total, b.get());
+    if (rc) return rc;
+    *out = b.release();
+    return ASM_OK;
 }
 
 int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, int greedy_mode, int aligner_mask,
@@ -2251,7 +2195,7 @@ int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, in
     uint8_t tail_state[256];
     memset(tail_state, 0, sizeof tail_state);
     int64_t chunk_first[2] = {0, 0}, chunk_pairs[2] = {0, 0};
-    asm_batch* chunk_batch[2] = {nullptr, nullptr};
+    BatchPtr chunk_batch[2];
     int64_t done_pairs = 0;
     int maxlen = 0;
     auto harvest = [&](int q) { /* results of the chunk that used device buffer q */
@@ -2264,8 +2208,7 @@ int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, in
             const int64_t cnt = chunk_pairs[q] < room ? chunk_pairs[q] : (room > 0 ? room : 0);
             if (cnt > 0) memcpy(dst[a] + chunk_first[q], h_pen[q][a], sizeof(int32_t) * (size_t)cnt);
         }
-        if (chunk_batch[q]) batch_release(chunk_batch[q]);
-        chunk_batch[q] = nullptr;
+        chunk_batch[q].reset();
         chunk_pairs[q] = 0;
     };
     /* The loop runs two stages per iteration, one chunk apart: SHIP chunk c (host buffer -> HBM on the copy stream) and only then
@@ -2315,17 +2258,15 @@ int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, in
         }
         if (rc) return;
         STREAM_TRY(hipStreamWaitEvent(h->stream, ev_h2d[q], 0));
-        asm_batch* b = nullptr;
-        if (!rc) rc = batch_from_device_text(h, d_raw[q], shipped, n, ASM_GREEDY_CLEAN, &b);
+        BatchPtr b;
+        if (!rc) rc = batch_new(h, n, ASM_GREEDY_CLEAN, "asm_stream_seq_file", b);
+        if (!rc) rc = batch_from_device_text(h, d_raw[q], shipped, b.get());
         if (rc) return;
         if (greedy_mode == ASM_GREEDY_SEQUENTIAL && do_greedy) { /* the chain of hurdle_matrix.h:136-137 across chunk boundaries */
-            uint8_t summary[256];
-            rc = batch_resolve_tails(h, b, nullptr, summary, false);
-            if (!rc) {
-                b->greedy_mode = ASM_GREEDY_SEQUENTIAL;
-                rc = batch_resolve_tails(h, b, tail_state, nullptr, true);
-            }
-            if (!rc) rc = asm_batch_pack_async(h, b);
+            uint8_t summary[256]; /* the summary does not depend on the state the tails are resolved from */
+            b->greedy_mode = ASM_GREEDY_SEQUENTIAL;
+            rc = batch_resolve_tails(h, b.get(), tail_state, summary, true);
+            if (!rc) rc = asm_batch_pack_async(h, b.get());
             if (!rc) rc = asm_tail_state_advance(tail_state, summary, n);
         }
         const int32_t* ans = nullptr;
@@ -2338,17 +2279,14 @@ int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, in
             ans = d_ans[q];
         }
         if (!rc)
-            rc = asm_run_benchmark_async(h, b, p, 0, do_nw ? d_pen[q][0] : nullptr, do_leap ? d_pen[q][1] : nullptr,
+            rc = asm_run_benchmark_async(h, b.get(), p, 0, do_nw ? d_pen[q][0] : nullptr, do_leap ? d_pen[q][1] : nullptr,
                                          do_greedy ? d_pen[q][2] : nullptr, ans, d_cnt);
         for (int a = 0; a < 3 && !rc; a++)
             if (d_pen[q][a]) STREAM_TRY(hipMemcpyAsync(h_pen[q][a], d_pen[q][a], sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
         STREAM_TRY(hipEventRecord(ev_done[q], h->stream));
-        if (rc) {
-            if (b) batch_release(b);
-            return;
-        }
-        chunk_batch[q] = b, chunk_first[q] = done_pairs, chunk_pairs[q] = n;
+        if (rc) return;
         maxlen = b->maxlen > maxlen ? b->maxlen : maxlen;
+        chunk_batch[q] = std::move(b), chunk_first[q] = done_pairs, chunk_pairs[q] = n;
         done_pairs += n, bytes_total += shipped, chunks++;
     };
     for (int c = 0; !last && !rc; c++) {
@@ -2421,15 +2359,19 @@ int asm_memset_async(asm_handle* h, void* d_ptr, int value, size_t bytes) {
 }
 
 struct asm_timer {
-    hipEvent_t a, b;
+    hipEvent_t a = nullptr, b = nullptr;
+    ~asm_timer() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
 };
 int asm_timer_create(asm_handle* h, void** timer) {
     if (!h || !timer) return fail(h, ASM_EINVAL, "asm_timer_create: NULL argument");
     HIPCHK(h, hipSetDevice(h->device));
-    asm_timer* t = new asm_timer;
+    std::unique_ptr<asm_timer> t(new asm_timer);
     HIPCHK(h, hipEventCreate(&t->a));
     HIPCHK(h, hipEventCreate(&t->b));
-    *timer = t;
+    *timer = t.release();
     return ASM_OK;
 }
 int asm_timer_start(asm_handle* h, void* timer) {
@@ -2450,11 +2392,7 @@ int asm_timer_elapsed_ms(asm_handle* h, void* timer, float* ms) {
     return ASM_OK;
 }
 int asm_timer_destroy(asm_handle* h, void* timer) {
-    if (!timer) return ASM_OK;
-    asm_timer* t = (asm_timer*)timer;
-    (void)hipEventDestroy(t->a);
-    (void)hipEventDestroy(t->b);
-    delete t;
+    delete (asm_timer*)timer;
     (void)h;
     return ASM_OK;
 }

@@ -987,6 +987,78 @@ def test_batches_may_outlive_their_engine(asm):
         b.close()
 
 
+@pytest.mark.parametrize("mode", ["GREEDY_SEQUENTIAL", "GREEDY_CLEAN"])  # the tail resolver's blocks made with the batch / through B
+def test_a_batch_used_through_a_second_engine(asm, oracle, mode):
+    """Blocks a batch gains after it was made (the tail resolver's, the second plane set of repack = 2 and 3) come from the pool
+    of the engine that made it, whichever engine the call goes through, and go back there when the batch is freed: nothing is
+    freed twice when both engines close, and the first engine keeps working."""
+    cfg, _, params = asm.workload("C2")
+    n = 20000
+    hb = asm.generate_pairs(cfg, 41, n)
+    nw, leap, greedy = oracle.nw(hb), oracle.leap(hb, params.k), oracle.greedy(hb, params.k, mode=0)
+    a, b = asm.Engine(0), asm.Engine(0)
+    batch = a.upload(hb, getattr(asm, mode))
+    b.resolve_tails(batch)  # a file's start: equal to a sequential-mode upload
+    assert np.array_equal(b.tail_summary(batch), oracle.tail_summary(hb))
+    sets = [[b.malloc(4 * n) for _ in range(3)] for _ in range(2)]
+    d_cnt = b.malloc(32)
+    b.run_benchmark_async(batch, params, *sets[0], d_cnt, repack=2)
+    for c in range(3):
+        b.run_benchmark_async(batch, params, *sets[c & 1], d_cnt, repack=3)
+    b.pipeline_join_async()
+    for o in sets:
+        assert np.array_equal(b.to_host(o[0], n), nw)
+        assert np.array_equal(b.to_host(o[1], n), leap)
+        assert np.array_equal(b.to_host(o[2], n), greedy)
+    for x in sets[0] + sets[1] + [d_cnt]:
+        b.free(x)
+    batch.engine = b
+    batch.free()
+    b.close()
+    assert np.array_equal(a.align(a.upload(hb, asm.GREEDY_SEQUENTIAL), asm.GREEDY, params), greedy)
+    a.close()
+
+
+@pytest.mark.parametrize("repack", [2, 3])
+def test_pipelined_call_with_invalid_parameters_changes_nothing(asm, engine, oracle, repack):
+    """A repack = 2 / 3 call whose parameters an aligner refuses fails before it enqueues anything or switches the batch to its
+    other plane set: an in-order call without a repack afterwards aligns the planes the batch had."""
+    cfg, _, params = asm.workload("C2")
+    n = 20000
+    hb = asm.generate_pairs(cfg, 43, n)
+    batch = engine.upload(hb, asm.GREEDY_CLEAN)
+    sets = [[engine.malloc(4 * n) for _ in range(3)] for _ in range(2)]
+    d_cnt = engine.malloc(32)
+    engine.run_benchmark_async(batch, params, *sets[0], d_cnt, repack=repack)  # both plane sets exist from here on
+    for bad in (asm.Params.default(k=51), asm.Params.default(k=3, x=1, o=1, e=2)):  # Greedy: k <= 50; LEAP: o >= e
+        with pytest.raises(asm.AsmError):
+            engine.run_benchmark_async(batch, bad, *sets[1], d_cnt, repack=repack)
+    engine.run_benchmark_async(batch, params, *sets[1], d_cnt, repack=0)
+    assert np.array_equal(engine.to_host(sets[1][0], n), oracle.nw(hb))
+    assert np.array_equal(engine.to_host(sets[1][1], n), oracle.leap(hb, params.k))
+    assert np.array_equal(engine.to_host(sets[1][2], n), oracle.greedy(hb, params.k, mode=1))
+    for x in sets[0] + sets[1] + [d_cnt]:
+        engine.free(x)
+
+
+def test_a_batch_freed_after_overlapped_calls_that_were_not_joined(asm, engine, oracle):
+    """asm_batch_free orders the blocks' reuse behind the overlapped calls that may still read them: a batch made next, from the
+    same blocks, aligns to the oracle."""
+    cfg, _, params = asm.workload("C2")
+    n = 30000
+    batch = engine.generate(cfg, 0, n)
+    sets = [[engine.malloc(4 * n) for _ in range(3)] for _ in range(2)]
+    d_cnt = engine.malloc(32)
+    for c in range(4):
+        engine.run_benchmark_async(batch, params, *sets[c & 1], d_cnt, repack=3)
+    batch.free()
+    hb = asm.generate_pairs(cfg, 977, n)
+    assert np.array_equal(engine.align(engine.generate(cfg, 977, n), asm.GREEDY, params), oracle.greedy(hb, params.k, mode=1))
+    engine.pipeline_join_async()
+    for x in sets[0] + sets[1] + [d_cnt]:
+        engine.free(x)
+
+
 @pytest.mark.parametrize("k", [1, 2, 3])
 def test_fast_greedy_kernel_slow_path_and_corners(asm, engine, oracle, k):
     """The straight-line Greedy kernel (csrc/asm_greedy3.h, k <= 3, unit penalties): solid blocks of mismatches leave the rank
