@@ -92,6 +92,71 @@ class GenConfig(ctypes.Structure):
                    p_ins, p_del)
 
 
+class MapParams(ctypes.Structure):
+    """asm_map_params: max errors e (0..15), both strands, k-mer bucket cap (0 = none), Greedy's k."""
+
+    _fields_ = [("max_errors", ctypes.c_int32), ("both_strands", ctypes.c_int32), ("max_occ", ctypes.c_int32),
+                ("greedy_k", ctypes.c_int32)]
+
+
+# asm_map_hit, one per read
+MAP_HIT_DTYPE = np.dtype([("seq_id", np.int32), ("pos", np.uint32), ("end", np.uint32), ("dist", np.int16), ("strand", np.uint8),
+                          ("flags", np.uint8), ("greedy_cost", np.int32)])
+MAP_MAPPED, MAP_TOO_SHORT, MAP_SEED_CAPPED, MAP_CIGAR_TRUNCATED = 1, 2, 4, 8
+MAP_MIN_K, MAP_MAX_K, MAP_MAX_READ, MAP_MAX_ERRORS = 8, 14, 511, 15
+
+
+def _as_bytes(s) -> bytes:
+    return s.encode("ascii") if isinstance(s, str) else bytes(s)
+
+
+def pack_sequences(seqs) -> Tuple[np.ndarray, np.ndarray]:
+    """Sequences (str / bytes) -> (concatenated uint8, n+1 uint64 offsets)."""
+    parts = [_as_bytes(s) for s in seqs]
+    off = np.zeros(len(parts) + 1, np.uint64)
+    if parts:
+        off[1:] = np.cumsum([len(b) for b in parts])
+    return np.frombuffer(b"".join(parts), np.uint8).copy(), off
+
+
+def read_fasta(path: str):
+    """-> [(name, sequence)]; the name is the first word of the header."""
+    out, name, chunks = [], None, []
+    with open(path) as fh:
+        for line in fh:
+            line = line.rstrip("\r\n")
+            if line.startswith(">"):
+                if name is not None:
+                    out.append((name, "".join(chunks)))
+                name, chunks = (line[1:].split() or [""])[0], []
+            elif name is not None:
+                chunks.append(line.strip())
+    if name is not None:
+        out.append((name, "".join(chunks)))
+    return out
+
+
+def read_fastq(path: str):
+    """-> [(name, sequence, quality)]; FASTA input gives quality '*'."""
+    with open(path) as fh:
+        first = fh.read(1)
+    if first == ">":
+        return [(n, s, "*") for n, s in read_fasta(path)]
+    out = []
+    with open(path) as fh:
+        while True:
+            h = fh.readline()
+            if not h:
+                break
+            if not h.strip():
+                continue
+            seq = fh.readline().rstrip("\r\n")
+            fh.readline()
+            qual = fh.readline().rstrip("\r\n")
+            out.append(((h[1:].split() or [""])[0], seq, qual))
+    return out
+
+
 # The named workloads of BASELINE.json `configs` (SURVEY.md §8d).
 def workload(name: str) -> Tuple[GenConfig, int, Params]:
     """-> (generator config, number of pairs, aligner params) for C1..C5."""
@@ -168,6 +233,9 @@ def load_library() -> ctypes.CDLL:
         "asm_count_equal_async": (i32, [vp, vp, vp, i64, vp]),
         "asm_accuracy_async": (i32, [vp, vp, vp, vp, vp, i64, vp]),
         "asm_run_benchmark_async": (i32, [vp, vp, c.POINTER(Params), i32, vp, vp, vp, vp, vp]),
+        "asm_index_build": (i32, [vp, vp, vp, c.c_int32, i32, c.POINTER(vp)]),
+        "asm_index_free": (i32, [vp, vp]),
+        "asm_map_reads": (i32, [vp, vp, i64, vp, vp, c.POINTER(MapParams), vp, vp, i32, vp]),
         "asm_device_malloc": (i32, [vp, c.c_size_t, c.POINTER(vp)]),
         "asm_device_free": (i32, [vp, vp]),
         "asm_memcpy_d2h": (i32, [vp, vp, vp, c.c_size_t]),
@@ -320,6 +388,24 @@ class Reference:
             pass
 
 
+class Index:
+    """asm_index: a k-mer index of reference sequences, resident in HBM."""
+
+    def __init__(self, engine: "Engine", ptr, k: int, lengths: Sequence[int]):
+        self.engine, self.ptr, self.k, self.lengths = engine, ptr, k, list(lengths)
+
+    def free(self) -> None:
+        if self.ptr:
+            self.engine.lib.asm_index_free(self.engine.h, self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Engine:
     """asm_handle: one per GPU.  All device work of the hot path goes through here."""
 
@@ -423,6 +509,45 @@ class Engine:
         self._chk(self.lib.asm_batch_from_hits(self.h, ref.ptr, ro.size - 1, reads.ctypes.data, ro.ctypes.data,
                                                pos.ctypes.data, greedy_mode, ctypes.byref(ptr)))
         return DeviceBatch(self, ptr)
+
+    # ---- read mapping (docs/design/mapper.md) ----
+    def build_index(self, seqs, k: int = 12) -> Index:
+        """asm_index_build over reference sequences (str / bytes, upper-cased on the device)."""
+        text, off = pack_sequences(seqs)
+        ptr = ctypes.c_void_p()
+        self._chk(self.lib.asm_index_build(self.h, text.ctypes.data if text.size else None, off.ctypes.data, len(off) - 1, int(k),
+                                           ctypes.byref(ptr)))
+        return Index(self, ptr, int(k), np.diff(off).astype(np.int64))
+
+    def map_reads(self, index: Index, reads, max_errors: int, both_strands: bool = True, max_occ: int = 0, greedy_k: int = 3,
+                  cigar_cap: int = 64, chunk: Optional[int] = None):
+        """asm_map_reads: the best hit of every read (str / bytes).  -> dict of numpy arrays, one entry per read: seq_id, pos, end,
+        dist, strand, flags, greedy_cost, mapped (bool), mapq (min(254, 60 + greedy_cost), 255 when unmapped), and `cigar`, a
+        list of CIGAR strings ('' when unmapped).  chunk: reads per library call (None: all in one)."""
+        parts = [_as_bytes(r) for r in reads]
+        n = len(parts)
+        p = MapParams(int(max_errors), 1 if both_strands else 0, int(max_occ), int(greedy_k))
+        hits = np.zeros(n, MAP_HIT_DTYPE)
+        ops = np.zeros((max(n, 1), max(cigar_cap, 1)), np.uint16)
+        nops = np.zeros(max(n, 1), np.uint8)
+        step = chunk if chunk else max(n, 1)
+        for lo in range(0, n, step):
+            hi = min(n, lo + step)
+            buf, off = pack_sequences(parts[lo:hi])
+            ro = off.astype(np.uint32)
+            sub = np.zeros(hi - lo, MAP_HIT_DTYPE)
+            sops = np.zeros((hi - lo, max(cigar_cap, 1)), np.uint16)
+            snops = np.zeros(hi - lo, np.uint8)
+            self._chk(self.lib.asm_map_reads(self.h, index.ptr, hi - lo, buf.ctypes.data if buf.size else None, ro.ctypes.data,
+                                             ctypes.byref(p), sub.ctypes.data, sops.ctypes.data if cigar_cap else None, int(cigar_cap),
+                                             snops.ctypes.data if cigar_cap else None))
+            hits[lo:hi], ops[lo:hi], nops[lo:hi] = sub, sops, snops
+        out = {name: hits[name].copy() for name in MAP_HIT_DTYPE.names}
+        out["mapped"] = (hits["flags"] & MAP_MAPPED) != 0
+        out["mapq"] = np.where(out["mapped"], np.minimum(254, 60 + hits["greedy_cost"].astype(np.int64)), 255).astype(np.int32)
+        out["cigar"] = decode_cigars(ops[:n], nops[:n], cigar_cap) if cigar_cap else [""] * n
+        out["cigar_nops"] = nops[:n].copy()
+        return out
 
     # ---- Greedy's sequential mode across batches (shards of one file / chunks of a stream) ----
     def tail_summary(self, batch: DeviceBatch) -> np.ndarray:

@@ -4,10 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -34,6 +36,7 @@
 #include "asm_tails.h"
 #include "asm_filter.h"
 #include "asm_ingest.h"
+#include "asm_map.h"
 
 struct asm_handle {
     unsigned long long serial = 0;        /* unique over the life of the process: a batch names its owner by (pointer, serial), so a
@@ -80,6 +83,8 @@ struct asm_handle {
     bool nw_bylen = true;                 /* unit-cost NW on mixed-length batches: workgroup-local sort by length (ASM_NW_BYLEN=0) */
     bool nw_banded = true;                /* banded bit-parallel NW with in-kernel full-height recompute (ASM_NW_BANDED=0) */
     bool nw_wfa = true;                   /* affine NW: banded wavefront first, full matrix for the rest (ASM_NW_WFA=0: full matrix only) */
+    int64_t map_cand_cap = (int64_t)1 << 24; /* asm_map_reads: verification candidates per round (ASM_MAP_CAND_CAP) */
+    int64_t map_chunk = (int64_t)1 << 18;    /* asm_map_reads: reads per device chunk (ASM_MAP_CHUNK) */
     std::vector<hipEvent_t> prof_ev;      /* asm_profile_enable: 8 events per recorded asm_run_benchmark_async call */
     std::vector<unsigned> prof_mask;      /* which of a call's four kernels were launched */
     int prof_cap = 0;
@@ -723,6 +728,8 @@ int asm_create(asm_handle** out, int device) {
     if ((env = getenv("ASM_NW_BYLEN"))) h->nw_bylen = env[0] != '0';       /* 0: mixed-length NW without the length sort */
     if ((env = getenv("ASM_NW_WFA"))) h->nw_wfa = env[0] != '0';           /* 0: affine NW by the full matrix only */
     if ((env = getenv("ASM_GREEDY_FAST"))) h->greedy_fast = env[0] != '0'; /* 0: FP64 Greedy kernel at k <= 3 */
+    if ((env = getenv("ASM_MAP_CAND_CAP")) && atoll(env) > 0) h->map_cand_cap = atoll(env); /* smaller: more seeding rounds */
+    if ((env = getenv("ASM_MAP_CHUNK")) && atoll(env) > 0) h->map_chunk = atoll(env);
     {
         std::lock_guard<std::mutex> lk(g_live_mu);
         h->serial = g_next_serial++;
@@ -2322,6 +2329,277 @@ int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, in
     stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     stats->seconds_read = rd.read_seconds();
     return rc;
+}
+
+/* ---- read mapping (csrc/asm_map.h, docs/design/mapper.md) ------------------------------------------------------------- */
+static_assert(sizeof(MapHit) == sizeof(asm_map_hit) && offsetof(MapHit, dist) == offsetof(asm_map_hit, dist) &&
+                  offsetof(MapHit, greedy_cost) == offsetof(asm_map_hit, greedy_cost),
+              "MapHit must have the layout of asm_map_hit");
+
+struct asm_index {
+    int device = 0;
+    int k = 0;
+    int32_t n_seqs = 0;
+    uint64_t len = 0;
+    std::vector<uint64_t> seq_off;          /* host copy, n_seqs + 1 */
+    char* d_text = nullptr;                 /* upper case */
+    unsigned long long* d_seq_off = nullptr;
+    uint32_t* d_off = nullptr;              /* 4^k + 1 bucket offsets */
+    uint32_t* d_pos = nullptr;              /* positions sorted by k-mer (ascending inside a bucket) */
+    ~asm_index() {
+        (void)hipSetDevice(device);
+        for (void* p : {(void*)d_text, (void*)d_seq_off, (void*)d_off, (void*)d_pos})
+            if (p) (void)hipFree(p);
+    }
+};
+
+static unsigned map_grid(uint64_t n, const asm_handle* h) { /* grid-stride kernels: at most 8 workgroups per CU */
+    const uint64_t want = (n + 255) / 256, cap = (uint64_t)h->num_cus * 8;
+    return (unsigned)(want < 1 ? 1 : want > cap ? cap : want);
+}
+
+int asm_index_build(asm_handle* h, const char* text, const uint64_t* seq_off, int32_t n_seqs, int k, asm_index** out) {
+    if (!out || !seq_off) return fail(h, ASM_EINVAL, "asm_index_build: NULL argument");
+    *out = nullptr;
+    if (n_seqs < 1 || n_seqs >= MAP_MAX_SEQS) return fail(h, ASM_EINVAL, "asm_index_build: n_seqs must be in [1, 2^26)");
+    if (k < ASM_MAP_MIN_K || k > ASM_MAP_MAX_K) return fail(h, ASM_EINVAL, "asm_index_build: k must be in [8, 14]");
+    if (seq_off[0] != 0) return fail(h, ASM_EINVAL, "asm_index_build: seq_off[0] must be 0");
+    for (int32_t r = 0; r < n_seqs; r++)
+        if (seq_off[r + 1] < seq_off[r]) return fail(h, ASM_EINVAL, "asm_index_build: seq_off must be non-decreasing");
+    const uint64_t len = seq_off[n_seqs];
+    if (len >= 0xffffffffull) return fail(h, ASM_EUNSUPPORTED, "asm_index_build: total reference length must be below 2^32");
+    if (len && !text) return fail(h, ASM_EINVAL, "asm_index_build: text is NULL");
+    if (!h) return fail(h, ASM_EINVAL, "asm_index_build: NULL handle");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::unique_ptr<asm_index> ix(new asm_index);
+    ix->device = h->device, ix->k = k, ix->n_seqs = n_seqs, ix->len = len;
+    ix->seq_off.assign(seq_off, seq_off + n_seqs + 1);
+    const uint32_t nb = (1u << (2 * k)) + 1u;
+    HIPCHK(h, big_malloc(h, (void**)&ix->d_text, len + 16));
+    HIPCHK(h, big_malloc(h, (void**)&ix->d_seq_off, sizeof(unsigned long long) * (size_t)(n_seqs + 1)));
+    HIPCHK(h, big_malloc(h, (void**)&ix->d_off, sizeof(uint32_t) * nb));
+    HIPCHK(h, big_malloc(h, (void**)&ix->d_pos, sizeof(uint32_t) * (len ? len : 1)));
+    if (len) HIPCHK(h, hipMemcpyAsync(ix->d_text, text, len, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(ix->d_seq_off, seq_off, sizeof(uint64_t) * (size_t)(n_seqs + 1), hipMemcpyHostToDevice, h->stream));
+    if (len) {
+        Scratch<uint32_t> keys(h), keys2(h), vals(h);
+        Scratch<void> tmp(h);
+        HIPCHK(h, keys.alloc(sizeof(uint32_t) * len));
+        HIPCHK(h, keys2.alloc(sizeof(uint32_t) * len));
+        HIPCHK(h, vals.alloc(sizeof(uint32_t) * len));
+        hipLaunchKernelGGL(map_upper_kernel, dim3(map_grid(len, h)), dim3(256), 0, h->stream, ix->d_text, (unsigned long long)len);
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL(map_kmer_key_kernel, dim3(map_grid(len, h)), dim3(256), 0, h->stream, (const char*)ix->d_text,
+                           (unsigned long long)len, (const unsigned long long*)ix->d_seq_off, (uint32_t)n_seqs, k, keys.p, vals.p);
+        HIPCHK(h, hipGetLastError());
+        size_t tmp_bytes = 0;
+        HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys.p, keys2.p, vals.p, ix->d_pos, (uint32_t)len, 0,
+                                                     2 * k + 1, h->stream));
+        HIPCHK(h, tmp.alloc(tmp_bytes + 16));
+        HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, keys.p, keys2.p, vals.p, ix->d_pos, (uint32_t)len, 0,
+                                                     2 * k + 1, h->stream)); /* stable: positions ascend inside a bucket */
+        hipLaunchKernelGGL(map_bucket_offsets_kernel, dim3(map_grid(nb, h)), dim3(256), 0, h->stream, (const uint32_t*)keys2.p,
+                           (unsigned long long)len, nb, ix->d_off);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    } else {
+        HIPCHK(h, hipMemsetAsync(ix->d_off, 0, sizeof(uint32_t) * nb, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    *out = ix.release();
+    return ASM_OK;
+}
+
+int asm_index_free(asm_handle* h, asm_index* ix) {
+    (void)h;
+    delete ix;
+    return ASM_OK;
+}
+
+/* Greedy on the windows of the mapped reads of one chunk (d_list: their indices); costs into d_cost[q] */
+static int map_greedy(asm_handle* h, const asm_index* ix, const char* d_reads, const uint32_t* d_roff, const MapHit* d_hits,
+                      const uint32_t* d_list, int64_t nl, int maxm, int greedy_k, int32_t* d_cost) {
+    BatchPtr b;
+    int rc = batch_new(h, nl, ASM_GREEDY_CLEAN, "asm_map_reads", b);
+    if (rc) return rc;
+    const size_t cnt = (size_t)nl + 1;
+    Scratch<uint32_t> qlen(h), wlen(h);
+    Scratch<void> tmp(h);
+    HIPCHK(h, qlen.alloc(sizeof(uint32_t) * cnt));
+    HIPCHK(h, wlen.alloc(sizeof(uint32_t) * cnt));
+    HIPCHK(h, batch_alloc(b.get(), &b->d_read_off, sizeof(uint32_t) * cnt));
+    HIPCHK(h, batch_alloc(b.get(), &b->d_ref_off, sizeof(uint32_t) * cnt));
+    hipLaunchKernelGGL(map_greedy_lengths_kernel, dim3(grid_for(nl + 1)), dim3(ASM_BLOCK), 0, h->stream, d_list, (long)nl, d_roff,
+                       d_hits, (const unsigned long long*)ix->d_seq_off, qlen.p, wlen.p);
+    HIPCHK(h, hipGetLastError());
+    size_t tmp_bytes = 0;
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, qlen.p, b->d_read_off, (int)cnt, h->stream));
+    HIPCHK(h, tmp.alloc(tmp_bytes + 16));
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, qlen.p, b->d_read_off, (int)cnt, h->stream));
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, wlen.p, b->d_ref_off, (int)cnt, h->stream));
+    uint32_t tot[2] = {0, 0};
+    HIPCHK(h, hipMemcpyAsync(&tot[0], b->d_read_off + nl, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&tot[1], b->d_ref_off + nl, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    b->reads_bytes = tot[0], b->refs_bytes = tot[1];
+    b->maxlen = maxm + 1; /* the window is at most one base longer than the read */
+    HIPCHK(h, batch_alloc(b.get(), &b->d_reads, b->reads_bytes + 16));
+    HIPCHK(h, batch_alloc(b.get(), &b->d_refs, b->refs_bytes + 16));
+    hipLaunchKernelGGL(map_greedy_gather_kernel, dim3(map_grid((uint64_t)nl * 64, h)), dim3(256), 0, h->stream, d_list, (long)nl,
+                       d_reads, d_roff, d_hits, (const char*)ix->d_text, (const unsigned long long*)ix->d_seq_off,
+                       (const uint32_t*)b->d_read_off, (const uint32_t*)b->d_ref_off, b->d_reads, b->d_refs);
+    HIPCHK(h, hipGetLastError());
+    rc = batch_finish(h, b.get());
+    if (rc) return rc;
+    asm_params gp;
+    asm_default_params(&gp);
+    gp.k = greedy_k, gp.x = gp.o = gp.e = 1, gp.alignment_type = ASM_ALIGN_GLOBAL;
+    return asm_align_batch_async(h, b.get(), ASM_GREEDY, &gp, d_cost);
+}
+
+} /* extern "C": the launchers below are templates */
+
+template <int W>
+static hipError_t map_launch_verify_finish(asm_handle* h, bool finish, const MapCand* cand, unsigned long long nc, const char* d_reads,
+                                           const uint32_t* d_roff, const asm_index* ix, int e, unsigned long long* keys,
+                                           const MapFinishArgs& fa) {
+    if (finish)
+        hipLaunchKernelGGL(map_finish_kernel<W>, dim3(map_grid((uint64_t)fa.n, h)), dim3(256), 0, h->stream, fa);
+    else
+        hipLaunchKernelGGL(map_verify_kernel<W>, dim3(map_grid(nc, h)), dim3(256), 0, h->stream, cand, nc, d_reads, d_roff,
+                           (const char*)ix->d_text, (const unsigned long long*)ix->d_seq_off, e, keys);
+    return hipGetLastError();
+}
+
+static hipError_t map_dispatch(asm_handle* h, int maxm, bool finish, const MapCand* cand, unsigned long long nc, const char* d_reads,
+                               const uint32_t* d_roff, const asm_index* ix, int e, unsigned long long* keys, const MapFinishArgs& fa) {
+    const int words = (maxm + 63) / 64;
+    if (words <= 1) return map_launch_verify_finish<1>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa);
+    if (words <= 2) return map_launch_verify_finish<2>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa);
+    if (words <= 4) return map_launch_verify_finish<4>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa);
+    return map_launch_verify_finish<8>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa);
+}
+
+extern "C" {
+
+/* one chunk of reads: everything on the device, results into the caller's host arrays */
+static int map_chunk(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
+                     const asm_map_params* p, asm_map_hit* out, uint16_t* cigar_ops, int cigar_cap, uint8_t* cigar_nops) {
+    const int S = p->both_strands ? 2 : 1, P = p->max_errors + 1;
+    std::vector<uint32_t> roff((size_t)n + 1);
+    int maxm = 0;
+    for (int64_t i = 0; i <= n; i++) roff[(size_t)i] = read_off[i] - read_off[0];
+    for (int64_t i = 0; i < n; i++) maxm = std::max(maxm, (int)(roff[(size_t)i + 1] - roff[(size_t)i]));
+    const size_t bytes = roff[(size_t)n];
+    const int64_t nw = n * S * P;
+    Scratch<char> d_reads(h);
+    Scratch<uint32_t> d_roff(h), d_flags(h), d_list(h);
+    Scratch<unsigned long long> d_keys(h), d_cnt(h), d_base(h);
+    Scratch<void> tmp(h);
+    Scratch<MapCand> d_cand(h);
+    Scratch<uint64_t> d_dirs(h);
+    Scratch<MapHit> d_hits(h);
+    Scratch<uint16_t> d_ops(h);
+    Scratch<uint8_t> d_nops(h);
+    Scratch<int32_t> d_cost(h);
+    HIPCHK(h, d_reads.alloc(bytes + 16));
+    HIPCHK(h, d_roff.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
+    HIPCHK(h, d_flags.alloc(sizeof(uint32_t) * (size_t)n));
+    HIPCHK(h, d_keys.alloc(sizeof(unsigned long long) * (size_t)n));
+    HIPCHK(h, d_cnt.alloc(sizeof(unsigned long long) * (size_t)nw));
+    HIPCHK(h, d_base.alloc(sizeof(unsigned long long) * (size_t)nw));
+    HIPCHK(h, hipMemcpyAsync(d_reads.p, reads + read_off[0], bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_roff.p, roff.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t) * (size_t)n, h->stream));
+    HIPCHK(h, hipMemsetAsync(d_keys.p, 0xff, sizeof(unsigned long long) * (size_t)n, h->stream));
+    hipLaunchKernelGGL(map_upper_kernel, dim3(map_grid(bytes, h)), dim3(256), 0, h->stream, d_reads.p, (unsigned long long)bytes);
+    HIPCHK(h, hipGetLastError());
+    MapSeedArgs sa;
+    sa.reads = d_reads.p, sa.roff = d_roff.p, sa.n = (long)n, sa.S = S, sa.P = P, sa.k = ix->k, sa.e = p->max_errors;
+    sa.max_occ = p->max_occ, sa.text = ix->d_text, sa.ix_off = ix->d_off, sa.ix_pos = ix->d_pos;
+    sa.seq_off = (const unsigned long long*)ix->d_seq_off, sa.n_seqs = (uint32_t)ix->n_seqs;
+    hipLaunchKernelGGL(map_seed_count_kernel, dim3(map_grid((uint64_t)nw, h)), dim3(256), 0, h->stream, sa, d_cnt.p, d_flags.p);
+    HIPCHK(h, hipGetLastError());
+    size_t tmp_bytes = 0;
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_cnt.p, d_base.p, (int)nw, h->stream));
+    HIPCHK(h, tmp.alloc(tmp_bytes + 16));
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, d_cnt.p, d_base.p, (int)nw, h->stream));
+    unsigned long long last[2] = {0, 0};
+    HIPCHK(h, hipMemcpyAsync(&last[0], d_base.p + nw - 1, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&last[1], d_cnt.p + nw - 1, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const unsigned long long total = last[0] + last[1];
+    /* rounds of at most map_cand_cap candidates: every round sees every work item and emits the part of it that falls in [c0, c1) */
+    const unsigned long long cap = std::min<unsigned long long>(total, (unsigned long long)h->map_cand_cap);
+    MapFinishArgs fa = {};
+    if (total) HIPCHK(h, d_cand.alloc(sizeof(MapCand) * cap));
+    for (unsigned long long c0 = 0; c0 < total; c0 += cap) {
+        const unsigned long long c1 = std::min(total, c0 + cap);
+        hipLaunchKernelGGL(map_seed_emit_kernel, dim3(map_grid((uint64_t)nw, h)), dim3(256), 0, h->stream, sa,
+                           (const unsigned long long*)d_base.p, (const unsigned long long*)d_cnt.p, c0, c1, d_cand.p);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, map_dispatch(h, maxm, false, d_cand.p, c1 - c0, d_reads.p, d_roff.p, ix, p->max_errors, d_keys.p, fa));
+    }
+    const int ocap = cigar_cap > 0 ? cigar_cap : 0;
+    HIPCHK(h, d_dirs.alloc(sizeof(uint64_t) * (bytes + (size_t)n)));
+    HIPCHK(h, d_hits.alloc(sizeof(MapHit) * (size_t)n));
+    HIPCHK(h, d_ops.alloc(sizeof(uint16_t) * ((size_t)n * ocap + 1)));
+    HIPCHK(h, d_nops.alloc((size_t)n));
+    fa.reads = d_reads.p, fa.roff = d_roff.p, fa.n = (long)n, fa.e = p->max_errors, fa.P = P, fa.k = ix->k, fa.cap = ocap;
+    fa.text = ix->d_text, fa.seq_off = (const unsigned long long*)ix->d_seq_off, fa.keys = d_keys.p, fa.flags = d_flags.p;
+    fa.dirs = d_dirs.p, fa.hits = d_hits.p, fa.ops = d_ops.p, fa.nops = d_nops.p;
+    HIPCHK(h, map_dispatch(h, maxm, true, nullptr, 0, d_reads.p, d_roff.p, ix, p->max_errors, d_keys.p, fa));
+    HIPCHK(h, hipMemcpyAsync(out, d_hits.p, sizeof(MapHit) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    if (ocap) {
+        HIPCHK(h, hipMemcpyAsync(cigar_ops, d_ops.p, sizeof(uint16_t) * (size_t)n * ocap, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(cigar_nops, d_nops.p, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<uint32_t> list;
+    int maxmap = 0;
+    for (int64_t i = 0; i < n; i++)
+        if (out[i].flags & ASM_MAP_MAPPED) {
+            list.push_back((uint32_t)i);
+            maxmap = std::max(maxmap, (int)(roff[(size_t)i + 1] - roff[(size_t)i]));
+        }
+    if (list.empty()) return ASM_OK;
+    const int64_t nl = (int64_t)list.size();
+    HIPCHK(h, d_list.alloc(sizeof(uint32_t) * (size_t)nl));
+    HIPCHK(h, d_cost.alloc(sizeof(int32_t) * (size_t)nl));
+    HIPCHK(h, hipMemcpyAsync(d_list.p, list.data(), sizeof(uint32_t) * (size_t)nl, hipMemcpyHostToDevice, h->stream));
+    int rc = map_greedy(h, ix, d_reads.p, d_roff.p, d_hits.p, d_list.p, nl, maxmap, p->greedy_k, d_cost.p);
+    if (rc) return rc;
+    std::vector<int32_t> cost((size_t)nl);
+    HIPCHK(h, hipMemcpyAsync(cost.data(), d_cost.p, sizeof(int32_t) * (size_t)nl, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int64_t q = 0; q < nl; q++) out[list[(size_t)q]].greedy_cost = cost[(size_t)q];
+    return ASM_OK;
+}
+
+int asm_map_reads(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
+                  const asm_map_params* p, asm_map_hit* out, uint16_t* cigar_ops, int cigar_cap, uint8_t* cigar_nops) {
+    if (!p || !ix || n < 0 || !read_off || (n > 0 && (!reads || !out))) return fail(h, ASM_EINVAL, "asm_map_reads: bad arguments");
+    if (p->max_errors < 0 || p->max_errors > ASM_MAP_MAX_ERRORS) return fail(h, ASM_EINVAL, "asm_map_reads: max_errors must be in [0, 15]");
+    if (p->both_strands != 0 && p->both_strands != 1) return fail(h, ASM_EINVAL, "asm_map_reads: both_strands must be 0 or 1");
+    if (p->max_occ < 0) return fail(h, ASM_EINVAL, "asm_map_reads: max_occ must be >= 0");
+    if (p->greedy_k < 0 || p->greedy_k > ASM_GREEDY_MAX_K) return fail(h, ASM_EINVAL, "asm_map_reads: greedy_k must be in [0, 50]");
+    if (cigar_cap < 0 || (cigar_cap > 0 && (!cigar_ops || !cigar_nops)))
+        return fail(h, ASM_EINVAL, "asm_map_reads: cigar_cap > 0 needs cigar_ops and cigar_nops");
+    for (int64_t i = 0; i < n; i++) {
+        if (read_off[i + 1] < read_off[i]) return fail(h, ASM_EINVAL, "asm_map_reads: read offsets must be non-decreasing");
+        const uint32_t m = read_off[i + 1] - read_off[i];
+        if (m < 1 || m > ASM_MAP_MAX_READ) return fail(h, ASM_EINVAL, "asm_map_reads: every read must have 1 to 511 bytes");
+    }
+    if (!h) return fail(h, ASM_EINVAL, "asm_map_reads: NULL handle");
+    if (ix->device != h->device) return fail(h, ASM_EINVAL, "asm_map_reads: the index lives on another device");
+    HIPCHK(h, hipSetDevice(h->device));
+    for (int64_t c0 = 0; c0 < n; c0 += h->map_chunk) {
+        const int64_t c1 = std::min(n, c0 + h->map_chunk);
+        const int rc = map_chunk(h, ix, c1 - c0, reads, read_off + c0, p, out + c0, cigar_cap > 0 ? cigar_ops + c0 * cigar_cap : nullptr,
+                                 cigar_cap, cigar_cap > 0 ? cigar_nops + c0 : nullptr);
+        if (rc) return rc;
+    }
+    return ASM_OK;
 }
 
 /* ---------------------------------------------------------------------------------------------------- */

@@ -1,0 +1,455 @@
+// Read mapper kernels (asm_index_build / asm_map_reads; contract: docs/design/mapper.md).
+//
+// Byte rule here: A, C, G and T match only themselves; every other byte (N, IUPAC codes, ...) mismatches everything, another N
+// included.  This is NOT the pack kernel's rule (which turns every non-base byte into A); Greedy, run on the mapped windows
+// afterwards, keeps the pack kernel's rule.
+//
+// Index:   map_upper_kernel (text to upper case), map_kmer_key_kernel (2-bit key of every k-mer that lies inside one sequence
+//          and holds only bases; 4^k = "no k-mer here"), hipcub radix sort of (key, position), map_bucket_offsets_kernel
+//          (off[b] = first sorted slot with key >= b, 4^k + 1 entries).
+// Mapping: work item = (read, strand, piece); map_seed_count_kernel sizes each item's bucket, an exclusive scan numbers the
+//          candidates, map_seed_emit_kernel writes those of one round [c0, c1) (a candidate = a piece found exactly = one
+//          verification window), map_verify_kernel<W> runs semi-global Myers/Hyyro over the window and folds the window's best
+//          (d, strand, seq, end) into the read's packed key with an integer atomicMin, map_finish_kernel<W> finds the start
+//          (reverse global bit-vector pass), runs a banded DP under the byte rule and writes the CIGAR, and map_greedy_*
+//          gather the Greedy windows of the mapped reads.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "asm_bits.h"
+
+#define MAP_MAX_READ 511      /* longest read: ceil(511 / 64) = 8 pattern words */
+#define MAP_MAX_ERRORS 15     /* 4 bits of the packed key; also the banded traceback's half-width */
+#define MAP_BAND (2 * MAP_MAX_ERRORS + 1)
+#define MAP_MAX_SEQS (1 << 26) /* 26 bits of the packed key */
+#define MAP_NO_KEY 0xffffffffffffffffull
+#define MAP_BAD_CAND 0xffffffffu
+
+/* asm_map_hit.flags (include/asm_mi355x.h) */
+#define MAP_F_MAPPED 1u
+#define MAP_F_TOO_SHORT 2u
+#define MAP_F_SEED_CAPPED 4u
+#define MAP_F_CIGAR_TRUNCATED 8u
+
+struct MapCand {  /* one verification window: T[ws, we) (global text positions) of sequence r for strand s of read `read` */
+    uint32_t read; /* MAP_BAD_CAND: the k-mer hit did not extend to the whole piece */
+    uint32_t ws, we;
+    uint32_t rs;   /* r << 1 | s */
+};
+
+/* What a device hit record looks like; the same layout as asm_map_hit of the C ABI (checked in asm_capi.hip). */
+struct MapHit {
+    int32_t seq_id;
+    uint32_t pos, end;
+    int16_t dist;
+    uint8_t strand, flags;
+    int32_t greedy_cost;
+};
+
+ASM_DEV uint32_t map_code(uint8_t c) { /* upper-case input: A 0, C 1, G 2, T 3, anything else 4 */
+    return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
+}
+ASM_DEV uint8_t map_comp(uint8_t c) {
+    return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c;
+}
+/* byte p of q_s (s = 1: reverse complement) */
+ASM_DEV uint8_t map_read_byte(const char* q, uint32_t m, uint32_t s, uint32_t p) {
+    return s ? map_comp((uint8_t)q[m - 1u - p]) : (uint8_t)q[p];
+}
+/* sequence holding global position t: the last r with seq_off[r] <= t (empty sequences are skipped over) */
+ASM_DEV uint32_t map_seq_of(const unsigned long long* seq_off, uint32_t n_seqs, unsigned long long t) {
+    uint32_t lo = 0, hi = n_seqs; /* seq_off[lo] <= t < seq_off[hi] */
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (seq_off[mid] <= t) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void map_upper_kernel(char* __restrict__ s, unsigned long long n) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (unsigned long long)gridDim.x * blockDim.x) {
+        const char c = s[i];
+        if (c >= 'a' && c <= 'z') s[i] = (char)(c - 32);
+    }
+}
+
+__global__ __launch_bounds__(256) void map_kmer_key_kernel(const char* __restrict__ text, unsigned long long len,
+                                                           const unsigned long long* __restrict__ seq_off, uint32_t n_seqs, int k,
+                                                           uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+    const uint32_t none = 1u << (2 * k);
+    for (unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; t < len;
+         t += (unsigned long long)gridDim.x * blockDim.x) {
+        uint32_t key = none;
+        const uint32_t r = map_seq_of(seq_off, n_seqs, t);
+        if (t + (unsigned long long)k <= seq_off[r + 1]) {
+            uint32_t acc = 0, bad = 0;
+            for (int q = 0; q < k; q++) {
+                const uint32_t c = map_code((uint8_t)text[t + q]);
+                bad |= c >> 2;
+                acc = (acc << 2) | (c & 3u);
+            }
+            if (!bad) key = acc;
+        }
+        keys[t] = key;
+        vals[t] = (uint32_t)t;
+    }
+}
+
+/* off[b] = number of sorted keys below b, for b in [0, nb) */
+__global__ __launch_bounds__(256) void map_bucket_offsets_kernel(const uint32_t* __restrict__ sorted, unsigned long long n,
+                                                                 uint32_t nb, uint32_t* __restrict__ off) {
+    for (uint32_t b = blockIdx.x * blockDim.x + threadIdx.x; b < nb; b += gridDim.x * blockDim.x) {
+        unsigned long long lo = 0, hi = n;
+        while (lo < hi) {
+            const unsigned long long mid = (lo + hi) >> 1;
+            if (sorted[mid] < b) lo = mid + 1; else hi = mid;
+        }
+        off[b] = (uint32_t)lo;
+    }
+}
+
+struct MapSeedArgs {
+    const char* reads;          /* upper-cased, concatenated */
+    const uint32_t* roff;       /* n + 1 */
+    long n;
+    int S, P, k, e, max_occ;    /* strands, pieces (= e + 1), k-mer length, max errors, bucket cap (0 = none) */
+    const char* text;           /* index text, upper case */
+    const uint32_t* ix_off;     /* 4^k + 1 */
+    const uint32_t* ix_pos;
+    const unsigned long long* seq_off;
+    uint32_t n_seqs;
+};
+
+/* the piece of work item w: read, strand, read offset, length and first k-mer key; false when it cannot seed (too short a read,
+ * a non-base byte in the piece) */
+ASM_DEV bool map_piece(const MapSeedArgs& a, long w, uint32_t& read, uint32_t& s, uint32_t& o, uint32_t& plen, uint32_t& key) {
+    const long per = (long)a.S * a.P;
+    read = (uint32_t)(w / per);
+    const uint32_t rem = (uint32_t)(w % per);
+    s = rem / (uint32_t)a.P;
+    const uint32_t piece = rem % (uint32_t)a.P;
+    const uint32_t r0 = a.roff[read], m = a.roff[read + 1] - r0;
+    if (m < (uint32_t)(a.P * a.k)) return false;
+    const uint32_t L = m / (uint32_t)a.P;
+    o = piece * L;
+    plen = piece == (uint32_t)a.P - 1u ? m - o : L;
+    uint32_t acc = 0, bad = 0;
+    for (uint32_t q = 0; q < plen; q++) {
+        const uint32_t c = map_code(map_read_byte(a.reads + r0, m, s, o + q));
+        bad |= c >> 2;
+        if (q < (uint32_t)a.k) acc = (acc << 2) | (c & 3u);
+    }
+    key = acc;
+    return !bad;
+}
+
+__global__ __launch_bounds__(256) void map_seed_count_kernel(MapSeedArgs a, unsigned long long* __restrict__ cnt,
+                                                             uint32_t* __restrict__ flags) {
+    const long nw = a.n * a.S * a.P;
+    for (long w = (long)blockIdx.x * blockDim.x + threadIdx.x; w < nw; w += (long)gridDim.x * blockDim.x) {
+        uint32_t read, s, o, plen, key;
+        unsigned long long c = 0;
+        if (map_piece(a, w, read, s, o, plen, key)) {
+            c = a.ix_off[key + 1] - a.ix_off[key];
+            if (a.max_occ > 0 && c > (unsigned long long)a.max_occ) {
+                c = 0;
+                atomicOr(flags + read, MAP_F_SEED_CAPPED);
+            }
+        }
+        cnt[w] = c;
+    }
+}
+
+/* candidates [c0, c1) of the exclusive scan `base` into cand[0, c1 - c0) */
+__global__ __launch_bounds__(256) void map_seed_emit_kernel(MapSeedArgs a, const unsigned long long* __restrict__ base,
+                                                            const unsigned long long* __restrict__ cnt, unsigned long long c0,
+                                                            unsigned long long c1, MapCand* __restrict__ cand) {
+    const long nw = a.n * a.S * a.P;
+    for (long w = (long)blockIdx.x * blockDim.x + threadIdx.x; w < nw; w += (long)gridDim.x * blockDim.x) {
+        const unsigned long long b = base[w], c = cnt[w];
+        if (!c || b + c <= c0 || b >= c1) continue;
+        uint32_t read, s, o, plen, key;
+        map_piece(a, w, read, s, o, plen, key);
+        const uint32_t r0 = a.roff[read], m = a.roff[read + 1] - r0;
+        const unsigned long long qlo = b < c0 ? c0 - b : 0ull, qhi = b + c > c1 ? c1 - b : c;
+        const uint32_t first = a.ix_off[key];
+        for (unsigned long long q = qlo; q < qhi; q++) {
+            const unsigned long long t = a.ix_pos[first + q];
+            const uint32_t r = map_seq_of(a.seq_off, a.n_seqs, t);
+            const unsigned long long s0 = a.seq_off[r], s1 = a.seq_off[r + 1];
+            bool ok = t + plen <= s1;
+            for (uint32_t p = (uint32_t)a.k; ok && p < plen; p++) ok = (uint8_t)a.text[t + p] == map_read_byte(a.reads + r0, m, s, o + p);
+            MapCand x;
+            x.read = ok ? read : MAP_BAD_CAND;
+            const long long lo = (long long)t - (long long)o - a.e, hi = (long long)t - (long long)o + (long long)m + a.e;
+            x.ws = (uint32_t)(lo < (long long)s0 ? (long long)s0 : lo);
+            x.we = (uint32_t)(hi > (long long)s1 ? (long long)s1 : hi);
+            x.rs = r << 1 | s;
+            cand[b + q - c0] = x;
+        }
+    }
+}
+
+/* One column step of a 64-row block of Myers' bit-vector algorithm (Hyyro's block form).  hin / return: the horizontal delta
+ * entering at the block's top / leaving at its bottom, in {-1, 0, +1}.  Bits above the pattern's last row carry junk that never
+ * reaches lower bits (carries and shifts only move upwards). */
+ASM_DEV int map_myers_step(uint64_t& Pv, uint64_t& Mv, uint64_t Eq, int hin, uint64_t& Ph_out, uint64_t& Mh_out) {
+    const uint64_t hneg = hin < 0 ? 1ull : 0ull;
+    const uint64_t Xv = Eq | Mv;
+    Eq |= hneg;
+    const uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
+    uint64_t Ph = Mv | ~(Xh | Pv);
+    uint64_t Mh = Pv & Xh;
+    Ph_out = Ph, Mh_out = Mh;
+    const int hout = (int)(Ph >> 63) - (int)(Mh >> 63);
+    Ph <<= 1;
+    Mh <<= 1;
+    Mh |= hneg;
+    Ph |= hin > 0 ? 1ull : 0ull;
+    Pv = Mh | ~(Xv | Ph);
+    Mv = Ph & Xv;
+    return hout;
+}
+
+/* Peq masks of the pattern q_s (rev = 1: read backwards, i.e. the pattern is q_s reversed); a non-base byte sets no bit */
+template <int W>
+ASM_DEV void map_build_peq(const char* q, uint32_t m, uint32_t s, bool rev, uint64_t (&peq)[4][W]) {
+#pragma unroll
+    for (int w = 0; w < W; w++) {
+        uint64_t a = 0, c = 0, g = 0, t = 0;
+        const uint32_t p0 = (uint32_t)w * 64u;
+        for (uint32_t p = p0; p < m && p < p0 + 64u; p++) {
+            const uint32_t code = map_code(map_read_byte(q, m, s, rev ? m - 1u - p : p));
+            const uint64_t bit = 1ull << (p - p0);
+            a |= code == 0u ? bit : 0ull;
+            c |= code == 1u ? bit : 0ull;
+            g |= code == 2u ? bit : 0ull;
+            t |= code == 3u ? bit : 0ull;
+        }
+        peq[0][w] = a, peq[1][w] = c, peq[2][w] = g, peq[3][w] = t;
+    }
+}
+
+/* One text column over all words of a pattern of m rows; returns the change of the last row's score. */
+template <int W>
+ASM_DEV int map_column(uint64_t (&Pv)[W], uint64_t (&Mv)[W], const uint64_t (&peq)[4][W], uint32_t code, int nw, uint32_t last_bit,
+                       int hin0) {
+    int h = hin0, delta = 0;
+#pragma unroll
+    for (int w = 0; w < W; w++) {
+        if (w < nw) {
+            const uint64_t Eq = code == 0u ? peq[0][w] : code == 1u ? peq[1][w] : code == 2u ? peq[2][w] : code == 3u ? peq[3][w] : 0ull;
+            uint64_t Ph, Mh;
+            h = map_myers_step(Pv[w], Mv[w], Eq, h, Ph, Mh);
+            if (w == nw - 1) delta = (int)((Ph >> last_bit) & 1ull) - (int)((Mh >> last_bit) & 1ull);
+        }
+    }
+    return delta;
+}
+
+/* thread per candidate: the window's best (d, end) and the read's atomicMin over the packed key
+ * d << 59 | s << 58 | r << 32 | end (end local to sequence r, exclusive) */
+template <int W>
+__global__ __launch_bounds__(256) void map_verify_kernel(const MapCand* __restrict__ cand, unsigned long long nc,
+                                                         const char* __restrict__ reads, const uint32_t* __restrict__ roff,
+                                                         const char* __restrict__ text, const unsigned long long* __restrict__ seq_off,
+                                                         int e, unsigned long long* __restrict__ keys) {
+    for (unsigned long long c = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; c < nc;
+         c += (unsigned long long)gridDim.x * blockDim.x) {
+        const MapCand x = cand[c];
+        if (x.read == MAP_BAD_CAND) continue;
+        const uint32_t r0 = roff[x.read], m = roff[x.read + 1] - r0, s = x.rs & 1u, r = x.rs >> 1;
+        uint64_t peq[4][W];
+        map_build_peq<W>(reads + r0, m, s, false, peq);
+        uint64_t Pv[W], Mv[W];
+#pragma unroll
+        for (int w = 0; w < W; w++) Pv[w] = ~0ull, Mv[w] = 0ull;
+        const int nw = (int)((m + 63u) >> 6);
+        const uint32_t last_bit = (m - 1u) & 63u;
+        int score = (int)m, best = e + 1;
+        uint32_t best_t = 0;
+        for (uint32_t t = x.ws; t < x.we; t++) {
+            score += map_column<W>(Pv, Mv, peq, map_code((uint8_t)text[t]), nw, last_bit, 0);
+            if (score < best) best = score, best_t = t + 1u; /* first end reaching the minimum */
+        }
+        if (best <= e) {
+            const unsigned long long key = (unsigned long long)best << 59 | (unsigned long long)s << 58 |
+                                           (unsigned long long)r << 32 | (unsigned long long)(best_t - (uint32_t)seq_off[r]);
+            atomicMin(keys + x.read, key);
+        }
+    }
+}
+
+struct MapFinishArgs {
+    const char* reads;
+    const uint32_t* roff;
+    long n;
+    int e, P, k, cap;
+    const char* text;
+    const unsigned long long* seq_off;
+    const unsigned long long* keys;
+    const uint32_t* flags;
+    uint64_t* dirs;      /* (m + 1) words per read, at roff[i] + i */
+    MapHit* hits;
+    uint16_t* ops;       /* [n][cap] */
+    uint8_t* nops;
+};
+
+/* thread per read: start (largest i reaching d with end j), banded traceback under the byte rule, CIGAR, hit record */
+template <int W>
+__global__ __launch_bounds__(256) void map_finish_kernel(MapFinishArgs a) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (long)gridDim.x * blockDim.x) {
+        const uint32_t r0 = a.roff[i], m = a.roff[i + 1] - r0;
+        const char* q = a.reads + r0;
+        const unsigned long long key = a.keys[i];
+        MapHit h;
+        h.seq_id = -1, h.pos = 0, h.end = 0, h.dist = -1, h.strand = 0, h.greedy_cost = -1;
+        uint32_t fl = a.flags[i];
+        if (m < (uint32_t)(a.P * a.k)) fl |= MAP_F_TOO_SHORT;
+        if (key == MAP_NO_KEY) {
+            h.flags = (uint8_t)fl;
+            a.hits[i] = h;
+            a.nops[i] = 0;
+            continue;
+        }
+        const int d = (int)(key >> 59);
+        const uint32_t s = (uint32_t)(key >> 58) & 1u, r = (uint32_t)(key >> 32) & (MAP_MAX_SEQS - 1), j = (uint32_t)key;
+        const unsigned long long s0 = a.seq_off[r];
+        /* start: reverse global pass over T[lo, j) against q_s reversed; the first length L whose distance is d gives the largest i */
+        const uint32_t lo = j >= m + (uint32_t)d ? j - m - (uint32_t)d : 0u;
+        uint32_t start = lo;
+        {
+            uint64_t peq[4][W];
+            map_build_peq<W>(q, m, s, true, peq);
+            uint64_t Pv[W], Mv[W];
+#pragma unroll
+            for (int w = 0; w < W; w++) Pv[w] = ~0ull, Mv[w] = 0ull;
+            const int nw = (int)((m + 63u) >> 6);
+            const uint32_t last_bit = (m - 1u) & 63u;
+            int score = (int)m;
+            for (uint32_t t = j; t > lo; t--) {
+                score += map_column<W>(Pv, Mv, peq, map_code((uint8_t)a.text[s0 + t - 1u]), nw, last_bit, 1);
+                if (score == d) {
+                    start = t - 1u;
+                    break;
+                }
+            }
+        }
+        /* banded DP: rows a = 0..m (read), columns b = 0..n (T[start, j)), lanes l <-> diagonal b - a = l - MAP_MAX_ERRORS;
+         * dirs: 2 bits per lane, 0 diagonal, 1 up (I), 2 left (D); ties prefer diagonal, then I, then D */
+        const int n = (int)(j - start);
+        const int INF = 2 * MAP_MAX_ERRORS + 2;
+        uint64_t* dirs = a.dirs + r0 + (uint32_t)i;
+        const char* tx = a.text + s0 + start;
+        int row[MAP_BAND];
+        uint32_t tw[MAP_BAND]; /* code of text column b = a + delta (1-based: T[start + b - 1]); 5 = outside */
+#pragma unroll
+        for (int l = 0; l < MAP_BAND; l++) {
+            const int dl = l - MAP_MAX_ERRORS;
+            row[l] = (dl >= 0 && dl <= n && dl <= d) ? dl : INF;
+            const int b = dl; /* row a = 0 before the first shift: column b = delta, its text byte is consumed at row 1 */
+            tw[l] = (b >= 0 && b < n) ? map_code((uint8_t)tx[b]) : 5u;
+        }
+        dirs[0] = 0xaaaaaaaaaaaaaaaaull; /* row 0: left */
+        for (int ar = 1; ar <= (int)m; ar++) {
+            const uint32_t rc = map_code(map_read_byte(q, m, s, (uint32_t)ar - 1u));
+            uint64_t dw = 0;
+            int left = INF;
+#pragma unroll
+            for (int l = 0; l < MAP_BAND; l++) {
+                const int dl = l - MAP_MAX_ERRORS, b = ar + dl;
+                int v = INF;
+                uint32_t dir = 0;
+                if (b >= 0 && b <= n && dl >= -d && dl <= d) {
+                    /* tw[l] holds the code of T[start + b - 1] at this row (set on the previous row's shift) */
+                    const int diag = row[l] + ((rc < 4u && rc == tw[l]) ? 0 : 1);
+                    const int up = l + 1 < MAP_BAND ? row[l + 1] + 1 : INF;
+                    const int lf = left + 1;
+                    v = diag, dir = 0u;
+                    if (up < v) v = up, dir = 1u;
+                    if (lf < v) v = lf, dir = 2u;
+                    if (b == 0) v = up, dir = 1u;
+                    if (v > INF) v = INF;
+                }
+                dw |= (uint64_t)dir << (2 * l);
+                left = v;
+                row[l] = v; /* row[l + 1] (read above as `up`) is still the previous row's value */
+            }
+            dirs[ar] = dw;
+            /* next row: column of lane l moves one to the right */
+#pragma unroll
+            for (int l = 0; l < MAP_BAND - 1; l++) tw[l] = tw[l + 1];
+            const int bn = ar + 1 + (MAP_BAND - 1 - MAP_MAX_ERRORS); /* column of the last lane on the next row */
+            tw[MAP_BAND - 1] = (bn >= 1 && bn <= n) ? map_code((uint8_t)tx[bn - 1]) : 5u;
+        }
+        /* traceback from (m, n), twice: count the runs, then write them forward */
+        int runs = 0;
+        for (int pass = 0; pass < 2; pass++) {
+            int ar = (int)m, l = n - (int)m + MAP_MAX_ERRORS, k = 0;
+            uint32_t op = 7u, len = 0;
+            while (ar > 0 || l != MAP_MAX_ERRORS) {
+                const uint32_t dir = (uint32_t)(dirs[ar] >> (2 * l)) & 3u;
+                const uint32_t o = dir == 0u ? 0u : dir == 1u ? 1u : 2u; /* M, I, D */
+                if (o != op && len) {
+                    if (pass == 1 && runs - 1 - k < a.cap) a.ops[(long)i * a.cap + (runs - 1 - k)] = (uint16_t)(len << 3 | op);
+                    k++;
+                    len = 0;
+                }
+                op = o;
+                len++;
+                if (dir == 0u) ar--;
+                else if (dir == 1u) ar--, l++;
+                else l--;
+            }
+            if (len) {
+                if (pass == 1 && runs - 1 - k < a.cap) a.ops[(long)i * a.cap + (runs - 1 - k)] = (uint16_t)(len << 3 | op);
+                k++;
+            }
+            runs = k;
+        }
+        if (runs > a.cap) fl |= MAP_F_CIGAR_TRUNCATED;
+        a.nops[i] = (uint8_t)(runs > 255 ? 255 : runs);
+        h.seq_id = (int32_t)r, h.pos = start, h.end = j, h.dist = (int16_t)d, h.strand = (uint8_t)s;
+        h.flags = (uint8_t)(fl | MAP_F_MAPPED);
+        a.hits[i] = h;
+    }
+}
+
+/* Greedy windows of the mapped reads (list = their indices): T_r[w, min(w + m + 1, len_r)) with w = pos ? pos - 1 : 0, clipped to
+ * the read's own sequence.  lens[q] = (read length, window length); the gather writes q_s and the window. */
+__global__ __launch_bounds__(256) void map_greedy_lengths_kernel(const uint32_t* __restrict__ list, long nl, const uint32_t* __restrict__ roff,
+                                                                 const MapHit* __restrict__ hits, const unsigned long long* __restrict__ seq_off,
+                                                                 uint32_t* __restrict__ qlen, uint32_t* __restrict__ wlen) {
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q > nl) return;
+    if (q == nl) { /* exclusive scans over nl + 1 entries give the totals */
+        qlen[nl] = 0u, wlen[nl] = 0u;
+        return;
+    }
+    const uint32_t i = list[q], m = roff[i + 1] - roff[i];
+    const MapHit h = hits[i];
+    const unsigned long long len_r = seq_off[h.seq_id + 1] - seq_off[h.seq_id];
+    const unsigned long long w = h.pos ? h.pos - 1u : 0u, e = w + m + 1ull < len_r ? w + m + 1ull : len_r;
+    qlen[q] = m;
+    wlen[q] = (uint32_t)(e - w);
+}
+
+__global__ __launch_bounds__(256) void map_greedy_gather_kernel(const uint32_t* __restrict__ list, long nl, const char* __restrict__ reads,
+                                                                const uint32_t* __restrict__ roff, const MapHit* __restrict__ hits,
+                                                                const char* __restrict__ text, const unsigned long long* __restrict__ seq_off,
+                                                                const uint32_t* __restrict__ qoff, const uint32_t* __restrict__ woff,
+                                                                char* __restrict__ qout, char* __restrict__ wout) {
+    const int lane = threadIdx.x & 63;
+    const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
+    for (long q = wave; q < nl; q += nwaves) { /* one wave per window */
+        const uint32_t i = list[q], r0 = roff[i], m = roff[i + 1] - r0;
+        const MapHit h = hits[i];
+        const unsigned long long w = seq_off[h.seq_id] + (h.pos ? h.pos - 1u : 0u);
+        for (uint32_t p = (uint32_t)lane; p < m; p += 64u) qout[qoff[q] + p] = (char)map_read_byte(reads + r0, m, h.strand, p);
+        const uint32_t o = woff[q], len = woff[q + 1] - o;
+        for (uint32_t p = (uint32_t)lane; p < len; p += 64u) wout[o + p] = text[w + p];
+    }
+}

@@ -328,6 +328,52 @@ int asm_pipeline_join_async(asm_handle* h);
 int asm_profile_enable(asm_handle* h, int max_calls, unsigned kernel_mask);
 int asm_profile_read(asm_handle* h, float* ms, int cap_calls, int* n_calls);
 
+/* ---- read mapping: k-mer index, pigeonhole seeding, bit-vector verification, CIGAR, Greedy ----------------------------
+ * The counterpart of the reference's read mapper (GASMA/mapper/{indexer,main}.cpp), exact by construction; the full contract is
+ * docs/design/mapper.md.  Byte rule: A, C, G, T match only themselves, every other byte mismatches everything (N against N
+ * included) — unlike the pack kernel's rule, which Greedy keeps.  Text and reads are taken upper case.
+ * Best hit of a read q (1 <= m <= 511): over q_0 = q and, with both_strands, q_1 = reverse complement (A<->T, C<->G), over
+ * every sequence r and every T_r[i, j): smallest d = Lev(q_s, T_r[i, j)), then s, then r, then smallest j, then largest i.  The
+ * read is mapped when d <= max_errors.  A read is searched only when m >= (max_errors + 1) * k (else flag TOO_SHORT).
+ * With max_occ > 0, k-mer buckets above max_occ are skipped (flag SEED_CAPPED; the answer is the best over the candidates seen).
+ *
+ * asm_index_build: text = the sequences back to back, seq_off = n_seqs + 1 offsets into it (host); k in [8, 14]; total length
+ *                  below 2^32, n_seqs in [1, 2^26).  The index ((4^k + 1) uint32 bucket offsets + one uint32 per k-mer) and the
+ *                  text stay in HBM.  Synchronous.
+ * asm_map_reads:   host in, host out; any n (chunked inside).  out[i] for read i; cigar_ops = [n][cigar_cap] entries count << 3 |
+ *                  op (0 M, 1 I, 2 D; I = read base absent from the reference, D = reference base absent from the read),
+ *                  cigar_nops[i] = entries of row i (above cigar_cap: truncated, flag CIGAR_TRUNCATED); both may be NULL
+ *                  (cigar_cap 0).  Greedy (k = greedy_k, x = o = e = 1, clean tails) runs on (q_s, T_r[w, min(w + m + 1, len_r)))
+ *                  with w = pos ? pos - 1 : 0, as mapper/main.cpp:79-95 calls it; MAPQ = min(254, 60 + greedy_cost).
+ *                  Unmapped reads: seq_id -1, pos = end = 0, dist -1, greedy_cost -1, cigar_nops 0.  Synchronous. */
+#define ASM_MAP_MAPPED 1
+#define ASM_MAP_TOO_SHORT 2
+#define ASM_MAP_SEED_CAPPED 4
+#define ASM_MAP_CIGAR_TRUNCATED 8
+#define ASM_MAP_MIN_K 8
+#define ASM_MAP_MAX_K 14
+#define ASM_MAP_MAX_READ 511
+#define ASM_MAP_MAX_ERRORS 15
+typedef struct asm_index asm_index;
+int asm_index_build(asm_handle* h, const char* text, const uint64_t* seq_off, int32_t n_seqs, int k, asm_index** out);
+int asm_index_free(asm_handle* h, asm_index* ix);
+typedef struct asm_map_params {
+    int32_t max_errors;   /* e in [0, 15]                                                   */
+    int32_t both_strands; /* 0: forward only; 1: reverse complement too                      */
+    int32_t max_occ;      /* 0 = unlimited                                                   */
+    int32_t greedy_k;     /* Greedy's band (the reference mapper uses 3); [0, 50]            */
+} asm_map_params;
+typedef struct asm_map_hit {
+    int32_t seq_id;       /* r, -1 when unmapped                                             */
+    uint32_t pos, end;    /* i, j: 0-based, T_r[pos, end)                                    */
+    int16_t dist;         /* d, -1 when unmapped                                             */
+    uint8_t strand;       /* s: 0 forward, 1 reverse complement                              */
+    uint8_t flags;        /* ASM_MAP_*                                                       */
+    int32_t greedy_cost;  /* Greedy's cost on the hit's window, -1 when unmapped             */
+} asm_map_hit;
+int asm_map_reads(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
+                  const asm_map_params* p, asm_map_hit* out, uint16_t* cigar_ops, int cigar_cap, uint8_t* cigar_nops);
+
 /* ---- plain device memory helpers (so that non-torch hosts can drive the async API) --------------------- */
 int asm_device_malloc(asm_handle* h, size_t bytes, void** d_ptr);
 int asm_device_free(asm_handle* h, void* d_ptr);

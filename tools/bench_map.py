@@ -1,0 +1,117 @@
+"""Read-mapper timings (development tool): PYTHONPATH=. python tools/bench_map.py [--ref-len 5e6] [--reads 1e6] [--len 100]
+[--errors 2 4] [--out DIR] [--profile]
+A random reference (one sequence, seeded) and reads sampled from both strands with 0..e substitutions plus 10 % random reads;
+reports the index build and the mapping of all reads (both strands), each timed with HIP events on the engine's stream around one
+synchronous library call (so host-to-device copies and the host's share of asm_map_reads are inside), plus the wall clock.
+--profile re-runs the same command under `rocprofv3 --kernel-trace --stats` (a run of its own) and prints the per-kernel totals."""
+import argparse
+import ctypes
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+import approximate_string_matching_amd as m  # noqa: E402
+
+LUT = np.frombuffer(b"ACGT", np.uint8)
+COMP = np.zeros(256, np.uint8)
+COMP[:] = np.arange(256)
+for a, b in (b"AT", b"TA", b"CG", b"GC"):
+    COMP[a] = b
+
+
+def make_inputs(ref_len, n, length, e, seed):
+    rng = np.random.default_rng(seed)
+    ref = LUT[rng.integers(0, 4, ref_len)]
+    starts = rng.integers(0, ref_len - length, n)
+    reads = ref[starts[:, None] + np.arange(length)[None, :]].copy()
+    for t in range(e):  # substitutions at random places (some may hit the same base twice: 0..e edits)
+        hit = rng.random(n) < 0.7
+        col = rng.integers(0, length, n)
+        reads[hit, col[hit]] = LUT[(np.searchsorted(LUT, reads[hit, col[hit]]) + rng.integers(1, 4, hit.sum())) % 4]
+    rev = rng.random(n) < 0.5
+    reads[rev] = COMP[reads[rev][:, ::-1]]
+    rnd = rng.random(n) < 0.1
+    reads[rnd] = LUT[rng.integers(0, 4, (int(rnd.sum()), length))]
+    return ref, reads
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ref-len", type=float, default=5e6)
+    ap.add_argument("--reads", type=float, default=1e6)
+    ap.add_argument("--len", type=int, default=100)
+    ap.add_argument("--errors", type=int, nargs="+", default=[2, 4])
+    ap.add_argument("--k", type=int, default=12)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out", default=None, help="directory for the JSON result (and the profile with --profile)")
+    ap.add_argument("--profile", action="store_true")
+    a = ap.parse_args()
+    n, ref_len = int(a.reads), int(a.ref_len)
+    if a.profile:
+        out = a.out or "bench_map_profile"
+        os.makedirs(out, exist_ok=True)
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", out, "-o", "map", "--output-format", "csv", "--",
+               sys.executable, os.path.abspath(__file__), "--ref-len", str(ref_len), "--reads", str(n), "--len", str(a.len),
+               "--k", str(a.k), "--reps", "1", "--errors", *[str(e) for e in a.errors]]
+        subprocess.run(cmd, check=True, timeout=1200)
+        for path in glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True):
+            with open(path) as fh:
+                rows = list(csv.DictReader(fh))
+            print("kernel totals (", path, ")")
+            for r in rows:
+                print("  %-60s calls %6s total ms %10.3f" % (r["Name"][:60], r["Calls"], float(r["TotalDurationNs"]) / 1e6))
+        return
+    eng = m.Engine(0)
+    lib, h = eng.lib, eng.h
+    tm = eng.timer()
+    results = {"ref_len": ref_len, "reads": n, "read_len": a.len, "k": a.k, "runs": []}
+    for e in a.errors:
+        ref, reads = make_inputs(ref_len, n, a.len, e, seed=1000 + e)
+        off = np.array([0, ref_len], np.uint64)
+        ix = ctypes.c_void_p()
+        best_ix = 1e30
+        for _ in range(a.reps):
+            if ix.value:
+                lib.asm_index_free(h, ix)
+            tm.start()
+            eng._chk(lib.asm_index_build(h, ref.ctypes.data, off.ctypes.data, 1, a.k, ctypes.byref(ix)))
+            tm.stop()
+            best_ix = min(best_ix, tm.elapsed_ms())
+        flat = np.ascontiguousarray(reads.reshape(-1))
+        ro = (np.arange(n + 1, dtype=np.uint64) * a.len).astype(np.uint32)
+        hits = np.zeros(n, m.MAP_HIT_DTYPE)
+        ops = np.zeros((n, 16), np.uint16)
+        nops = np.zeros(n, np.uint8)
+        p = m.MapParams(e, 1, 0, 3)
+        best_map, best_wall = 1e30, 1e30
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            tm.start()
+            eng._chk(lib.asm_map_reads(h, ix, n, flat.ctypes.data, ro.ctypes.data, ctypes.byref(p), hits.ctypes.data, ops.ctypes.data,
+                                       16, nops.ctypes.data))
+            tm.stop()
+            best_map = min(best_map, tm.elapsed_ms())
+            best_wall = min(best_wall, (time.perf_counter() - t0) * 1e3)
+        lib.asm_index_free(h, ix)
+        mapped = float(((hits["flags"] & m.MAP_MAPPED) != 0).mean())
+        row = {"e": e, "index_build_ms": round(best_ix, 3), "map_ms_events": round(best_map, 3), "map_ms_wall": round(best_wall, 3),
+               "reads_per_s": round(n / best_map * 1e3), "mapped_fraction": round(mapped, 4)}
+        results["runs"].append(row)
+        print(json.dumps(row))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "bench_map.json"), "w") as fh:
+            json.dump(results, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()
