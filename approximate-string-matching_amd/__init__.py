@@ -103,6 +103,7 @@ class MapParams(ctypes.Structure):
 MAP_HIT_DTYPE = np.dtype([("seq_id", np.int32), ("pos", np.uint32), ("end", np.uint32), ("dist", np.int16), ("strand", np.uint8),
                           ("flags", np.uint8), ("greedy_cost", np.int32)])
 MAP_MAPPED, MAP_TOO_SHORT, MAP_SEED_CAPPED, MAP_CIGAR_TRUNCATED = 1, 2, 4, 8
+MAP_SECONDARY, MAP_HITS_TRUNCATED, MAP_MAX_HITS = 16, 32, 256
 MAP_MIN_K, MAP_MAX_K, MAP_MAX_READ, MAP_MAX_ERRORS = 8, 14, 511, 15
 
 
@@ -236,6 +237,7 @@ def load_library() -> ctypes.CDLL:
         "asm_index_build": (i32, [vp, vp, vp, c.c_int32, i32, c.POINTER(vp)]),
         "asm_index_free": (i32, [vp, vp]),
         "asm_map_reads": (i32, [vp, vp, i64, vp, vp, c.POINTER(MapParams), vp, vp, i32, vp]),
+        "asm_map_reads_all": (i32, [vp, vp, i64, vp, vp, c.POINTER(MapParams), i32, i32, vp, vp, vp, i32, vp]),
         "asm_device_malloc": (i32, [vp, c.c_size_t, c.POINTER(vp)]),
         "asm_device_free": (i32, [vp, vp]),
         "asm_memcpy_d2h": (i32, [vp, vp, vp, c.c_size_t]),
@@ -547,6 +549,46 @@ class Engine:
         out["mapq"] = np.where(out["mapped"], np.minimum(254, 60 + hits["greedy_cost"].astype(np.int64)), 255).astype(np.int32)
         out["cigar"] = decode_cigars(ops[:n], nops[:n], cigar_cap) if cigar_cap else [""] * n
         out["cigar_nops"] = nops[:n].copy()
+        return out
+
+    def map_reads_all(self, index: Index, reads, max_errors: int, max_hits: int = 16, strata: Optional[int] = None,
+                      both_strands: bool = True, max_occ: int = 0, greedy_k: int = 3, cigar_cap: int = 64, chunk: Optional[int] = None):
+        """asm_map_reads_all: every locus within max_errors (docs/design/mapper.md, "All hits").  strata=None means max_errors
+        (all loci).  -> dict: per read `n_hits` (uncapped), `n_reported` and `read_flags` (the rank-0 record's flags, also for an
+        unmapped read: TOO_SHORT, SEED_CAPPED); flat per-hit arrays in read-then-rank order: read,
+        rank, seq_id, pos, end, dist, strand, flags, greedy_cost, mapq (min(254, 60 + greedy_cost)), and `cigar`, a list of CIGAR
+        strings.  chunk: reads per library call (None: all in one)."""
+        parts = [_as_bytes(r) for r in reads]
+        n = len(parts)
+        strata = int(max_errors) if strata is None else int(strata)
+        p = MapParams(int(max_errors), 1 if both_strands else 0, int(max_occ), int(greedy_k))
+        cap1 = max(cigar_cap, 1)
+        n_hits = np.zeros(n, np.uint32)
+        hits = np.zeros((n, max_hits), MAP_HIT_DTYPE)
+        ops = np.zeros((n, max_hits, cap1), np.uint16)
+        nops = np.zeros((n, max_hits), np.uint8)
+        step = chunk if chunk else max(n, 1)
+        for lo in range(0, n, step):
+            hi = min(n, lo + step)
+            buf, off = pack_sequences(parts[lo:hi])
+            ro = off.astype(np.uint32)
+            snh = np.zeros(hi - lo, np.uint32)
+            sub = np.zeros((hi - lo, max_hits), MAP_HIT_DTYPE)
+            sops = np.zeros((hi - lo, max_hits, cap1), np.uint16)
+            snops = np.zeros((hi - lo, max_hits), np.uint8)
+            self._chk(self.lib.asm_map_reads_all(self.h, index.ptr, hi - lo, buf.ctypes.data if buf.size else None, ro.ctypes.data,
+                                                 ctypes.byref(p), strata, int(max_hits), snh.ctypes.data, sub.ctypes.data,
+                                                 sops.ctypes.data if cigar_cap else None, int(cigar_cap),
+                                                 snops.ctypes.data if cigar_cap else None))
+            n_hits[lo:hi], hits[lo:hi], ops[lo:hi], nops[lo:hi] = snh, sub, sops, snops
+        n_rep = np.minimum(n_hits, max_hits).astype(np.int64)
+        read = np.repeat(np.arange(n, dtype=np.int64), n_rep)
+        rank = (np.arange(read.size, dtype=np.int64) - np.repeat(np.cumsum(n_rep) - n_rep, n_rep)) if read.size else read.copy()
+        flat = hits[read, rank]
+        out = {"n_hits": n_hits, "n_reported": n_rep, "read_flags": hits["flags"][:, 0].copy(), "read": read, "rank": rank}
+        out.update({name: flat[name].copy() for name in MAP_HIT_DTYPE.names})
+        out["mapq"] = np.minimum(254, 60 + flat["greedy_cost"].astype(np.int64)).astype(np.int32)
+        out["cigar"] = decode_cigars(ops[read, rank], nops[read, rank], cigar_cap) if cigar_cap else [""] * read.size
         return out
 
     # ---- Greedy's sequential mode across batches (shards of one file / chunks of a stream) ----

@@ -85,6 +85,7 @@ struct asm_handle {
     bool nw_wfa = true;                   /* affine NW: banded wavefront first, full matrix for the rest (ASM_NW_WFA=0: full matrix only) */
     int64_t map_cand_cap = (int64_t)1 << 24; /* asm_map_reads: verification candidates per round (ASM_MAP_CAND_CAP) */
     int64_t map_chunk = (int64_t)1 << 18;    /* asm_map_reads: reads per device chunk (ASM_MAP_CHUNK) */
+    int64_t map_run_cap = (int64_t)1 << 24;  /* asm_map_reads_all: run records reserved per seeding round (ASM_MAP_RUN_CAP) */
     std::vector<hipEvent_t> prof_ev;      /* asm_profile_enable: 8 events per recorded asm_run_benchmark_async call */
     std::vector<unsigned> prof_mask;      /* which of a call's four kernels were launched */
     int prof_cap = 0;
@@ -730,6 +731,7 @@ int asm_create(asm_handle** out, int device) {
     if ((env = getenv("ASM_GREEDY_FAST"))) h->greedy_fast = env[0] != '0'; /* 0: FP64 Greedy kernel at k <= 3 */
     if ((env = getenv("ASM_MAP_CAND_CAP")) && atoll(env) > 0) h->map_cand_cap = atoll(env); /* smaller: more seeding rounds */
     if ((env = getenv("ASM_MAP_CHUNK")) && atoll(env) > 0) h->map_chunk = atoll(env);
+    if ((env = getenv("ASM_MAP_RUN_CAP")) && atoll(env) > 0) h->map_run_cap = atoll(env); /* smaller: the buffer grows more often */
     {
         std::lock_guard<std::mutex> lk(g_live_mu);
         h->serial = g_next_serial++;
@@ -2416,9 +2418,10 @@ int asm_index_free(asm_handle* h, asm_index* ix) {
     return ASM_OK;
 }
 
-/* Greedy on the windows of the mapped reads of one chunk (d_list: their indices); costs into d_cost[q] */
+/* Greedy on the windows of the mapped items of one chunk (d_list: their indices into d_hits; d_iread: each item's read, NULL when
+ * item i is read i); costs into d_cost[q] */
 static int map_greedy(asm_handle* h, const asm_index* ix, const char* d_reads, const uint32_t* d_roff, const MapHit* d_hits,
-                      const uint32_t* d_list, int64_t nl, int maxm, int greedy_k, int32_t* d_cost) {
+                      const uint32_t* d_iread, const uint32_t* d_list, int64_t nl, int maxm, int greedy_k, int32_t* d_cost) {
     BatchPtr b;
     int rc = batch_new(h, nl, ASM_GREEDY_CLEAN, "asm_map_reads", b);
     if (rc) return rc;
@@ -2429,8 +2432,8 @@ static int map_greedy(asm_handle* h, const asm_index* ix, const char* d_reads, c
     HIPCHK(h, wlen.alloc(sizeof(uint32_t) * cnt));
     HIPCHK(h, batch_alloc(b.get(), &b->d_read_off, sizeof(uint32_t) * cnt));
     HIPCHK(h, batch_alloc(b.get(), &b->d_ref_off, sizeof(uint32_t) * cnt));
-    hipLaunchKernelGGL(map_greedy_lengths_kernel, dim3(grid_for(nl + 1)), dim3(ASM_BLOCK), 0, h->stream, d_list, (long)nl, d_roff,
-                       d_hits, (const unsigned long long*)ix->d_seq_off, qlen.p, wlen.p);
+    hipLaunchKernelGGL(map_greedy_lengths_kernel, dim3(grid_for(nl + 1)), dim3(ASM_BLOCK), 0, h->stream, d_list, d_iread, (long)nl,
+                       d_roff, d_hits, (const unsigned long long*)ix->d_seq_off, qlen.p, wlen.p);
     HIPCHK(h, hipGetLastError());
     size_t tmp_bytes = 0;
     HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, qlen.p, b->d_read_off, (int)cnt, h->stream));
@@ -2445,8 +2448,8 @@ static int map_greedy(asm_handle* h, const asm_index* ix, const char* d_reads, c
     b->maxlen = maxm + 1; /* the window is at most one base longer than the read */
     HIPCHK(h, batch_alloc(b.get(), &b->d_reads, b->reads_bytes + 16));
     HIPCHK(h, batch_alloc(b.get(), &b->d_refs, b->refs_bytes + 16));
-    hipLaunchKernelGGL(map_greedy_gather_kernel, dim3(map_grid((uint64_t)nl * 64, h)), dim3(256), 0, h->stream, d_list, (long)nl,
-                       d_reads, d_roff, d_hits, (const char*)ix->d_text, (const unsigned long long*)ix->d_seq_off,
+    hipLaunchKernelGGL(map_greedy_gather_kernel, dim3(map_grid((uint64_t)nl * 64, h)), dim3(256), 0, h->stream, d_list, d_iread,
+                       (long)nl, d_reads, d_roff, d_hits, (const char*)ix->d_text, (const unsigned long long*)ix->d_seq_off,
                        (const uint32_t*)b->d_read_off, (const uint32_t*)b->d_ref_off, b->d_reads, b->d_refs);
     HIPCHK(h, hipGetLastError());
     rc = batch_finish(h, b.get());
@@ -2459,12 +2462,26 @@ static int map_greedy(asm_handle* h, const asm_index* ix, const char* d_reads, c
 
 } /* extern "C": the launchers below are templates */
 
+/* asm_map_reads_all's run buffer: records [0, cap) of key / val; *counter counts every record a verify-all launch produced */
+struct MapRunBuf {
+    unsigned long long* counter;
+    unsigned long long cap;
+    unsigned long long* key;
+    uint32_t* val;
+};
+
+/* finish: fa; verify: keys; verify-all: rb (the others unused) */
 template <int W>
 static hipError_t map_launch_verify_finish(asm_handle* h, bool finish, const MapCand* cand, unsigned long long nc, const char* d_reads,
                                            const uint32_t* d_roff, const asm_index* ix, int e, unsigned long long* keys,
-                                           const MapFinishArgs& fa) {
-    if (finish)
-        hipLaunchKernelGGL(map_finish_kernel<W>, dim3(map_grid((uint64_t)fa.n, h)), dim3(256), 0, h->stream, fa);
+                                           const MapFinishArgs& fa, const MapRunBuf* rb) {
+    if (finish && fa.iread)
+        hipLaunchKernelGGL((map_finish_kernel<W, true>), dim3(map_grid((uint64_t)fa.n, h)), dim3(256), 0, h->stream, fa);
+    else if (finish)
+        hipLaunchKernelGGL((map_finish_kernel<W, false>), dim3(map_grid((uint64_t)fa.n, h)), dim3(256), 0, h->stream, fa);
+    else if (rb)
+        hipLaunchKernelGGL(map_verify_all_kernel<W>, dim3(map_grid(nc, h)), dim3(256), 0, h->stream, cand, nc, d_reads, d_roff,
+                           (const char*)ix->d_text, e, rb->counter, rb->cap, rb->key, rb->val);
     else
         hipLaunchKernelGGL(map_verify_kernel<W>, dim3(map_grid(nc, h)), dim3(256), 0, h->stream, cand, nc, d_reads, d_roff,
                            (const char*)ix->d_text, (const unsigned long long*)ix->d_seq_off, e, keys);
@@ -2472,63 +2489,93 @@ static hipError_t map_launch_verify_finish(asm_handle* h, bool finish, const Map
 }
 
 static hipError_t map_dispatch(asm_handle* h, int maxm, bool finish, const MapCand* cand, unsigned long long nc, const char* d_reads,
-                               const uint32_t* d_roff, const asm_index* ix, int e, unsigned long long* keys, const MapFinishArgs& fa) {
+                               const uint32_t* d_roff, const asm_index* ix, int e, unsigned long long* keys, const MapFinishArgs& fa,
+                               const MapRunBuf* rb = nullptr) {
     const int words = (maxm + 63) / 64;
-    if (words <= 1) return map_launch_verify_finish<1>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa);
-    if (words <= 2) return map_launch_verify_finish<2>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa);
-    if (words <= 4) return map_launch_verify_finish<4>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa);
-    return map_launch_verify_finish<8>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa);
+    if (words <= 1) return map_launch_verify_finish<1>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa, rb);
+    if (words <= 2) return map_launch_verify_finish<2>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa, rb);
+    if (words <= 4) return map_launch_verify_finish<4>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa, rb);
+    return map_launch_verify_finish<8>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa, rb);
 }
 
 extern "C" {
 
+/* The front of a chunk, shared by both mapping calls: reads uploaded and upper-cased, per-read flags cleared, every work item's
+ * candidates counted (map_seed_count_kernel) and numbered (exclusive scan); total = all candidates of the chunk. */
+struct MapFront {
+    std::vector<uint32_t> roff;
+    int maxm = 0;
+    size_t bytes = 0;
+    int64_t nw = 0;
+    unsigned long long total = 0;
+    MapSeedArgs sa = {};
+    Scratch<char> d_reads;
+    Scratch<uint32_t> d_roff, d_flags;
+    Scratch<unsigned long long> d_cnt, d_base;
+    Scratch<void> tmp;
+    explicit MapFront(asm_handle* h) : d_reads(h), d_roff(h), d_flags(h), d_cnt(h), d_base(h), tmp(h) {}
+};
+
+static int map_front(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
+                     const asm_map_params* p, MapFront& f) {
+    const int S = p->both_strands ? 2 : 1, P = p->max_errors + 1;
+    f.roff.resize((size_t)n + 1);
+    for (int64_t i = 0; i <= n; i++) f.roff[(size_t)i] = read_off[i] - read_off[0];
+    for (int64_t i = 0; i < n; i++) f.maxm = std::max(f.maxm, (int)(f.roff[(size_t)i + 1] - f.roff[(size_t)i]));
+    const size_t bytes = f.bytes = f.roff[(size_t)n];
+    const int64_t nw = f.nw = n * S * P;
+    HIPCHK(h, f.d_reads.alloc(bytes + 16));
+    HIPCHK(h, f.d_roff.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
+    HIPCHK(h, f.d_flags.alloc(sizeof(uint32_t) * (size_t)n));
+    HIPCHK(h, f.d_cnt.alloc(sizeof(unsigned long long) * (size_t)nw));
+    HIPCHK(h, f.d_base.alloc(sizeof(unsigned long long) * (size_t)nw));
+    HIPCHK(h, hipMemcpyAsync(f.d_reads.p, reads + read_off[0], bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(f.d_roff.p, f.roff.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(f.d_flags.p, 0, sizeof(uint32_t) * (size_t)n, h->stream));
+    hipLaunchKernelGGL(map_upper_kernel, dim3(map_grid(bytes, h)), dim3(256), 0, h->stream, f.d_reads.p, (unsigned long long)bytes);
+    HIPCHK(h, hipGetLastError());
+    MapSeedArgs& sa = f.sa;
+    sa.reads = f.d_reads.p, sa.roff = f.d_roff.p, sa.n = (long)n, sa.S = S, sa.P = P, sa.k = ix->k, sa.e = p->max_errors;
+    sa.max_occ = p->max_occ, sa.text = ix->d_text, sa.ix_off = ix->d_off, sa.ix_pos = ix->d_pos;
+    sa.seq_off = (const unsigned long long*)ix->d_seq_off, sa.n_seqs = (uint32_t)ix->n_seqs;
+    hipLaunchKernelGGL(map_seed_count_kernel, dim3(map_grid((uint64_t)nw, h)), dim3(256), 0, h->stream, sa, f.d_cnt.p, f.d_flags.p);
+    HIPCHK(h, hipGetLastError());
+    size_t tmp_bytes = 0;
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, f.d_cnt.p, f.d_base.p, (int)nw, h->stream));
+    HIPCHK(h, f.tmp.alloc(tmp_bytes + 16));
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(f.tmp.p, tmp_bytes, f.d_cnt.p, f.d_base.p, (int)nw, h->stream));
+    unsigned long long last[2] = {0, 0};
+    HIPCHK(h, hipMemcpyAsync(&last[0], f.d_base.p + nw - 1, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&last[1], f.d_cnt.p + nw - 1, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    f.total = last[0] + last[1];
+    return ASM_OK;
+}
+
 /* one chunk of reads: everything on the device, results into the caller's host arrays */
 static int map_chunk(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
                      const asm_map_params* p, asm_map_hit* out, uint16_t* cigar_ops, int cigar_cap, uint8_t* cigar_nops) {
-    const int S = p->both_strands ? 2 : 1, P = p->max_errors + 1;
-    std::vector<uint32_t> roff((size_t)n + 1);
-    int maxm = 0;
-    for (int64_t i = 0; i <= n; i++) roff[(size_t)i] = read_off[i] - read_off[0];
-    for (int64_t i = 0; i < n; i++) maxm = std::max(maxm, (int)(roff[(size_t)i + 1] - roff[(size_t)i]));
-    const size_t bytes = roff[(size_t)n];
-    const int64_t nw = n * S * P;
-    Scratch<char> d_reads(h);
-    Scratch<uint32_t> d_roff(h), d_flags(h), d_list(h);
-    Scratch<unsigned long long> d_keys(h), d_cnt(h), d_base(h);
-    Scratch<void> tmp(h);
+    MapFront f(h);
+    Scratch<uint32_t> d_list(h);
+    Scratch<unsigned long long> d_keys(h);
     Scratch<MapCand> d_cand(h);
     Scratch<uint64_t> d_dirs(h);
     Scratch<MapHit> d_hits(h);
     Scratch<uint16_t> d_ops(h);
     Scratch<uint8_t> d_nops(h);
     Scratch<int32_t> d_cost(h);
-    HIPCHK(h, d_reads.alloc(bytes + 16));
-    HIPCHK(h, d_roff.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
-    HIPCHK(h, d_flags.alloc(sizeof(uint32_t) * (size_t)n));
     HIPCHK(h, d_keys.alloc(sizeof(unsigned long long) * (size_t)n));
-    HIPCHK(h, d_cnt.alloc(sizeof(unsigned long long) * (size_t)nw));
-    HIPCHK(h, d_base.alloc(sizeof(unsigned long long) * (size_t)nw));
-    HIPCHK(h, hipMemcpyAsync(d_reads.p, reads + read_off[0], bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d_roff.p, roff.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t) * (size_t)n, h->stream));
     HIPCHK(h, hipMemsetAsync(d_keys.p, 0xff, sizeof(unsigned long long) * (size_t)n, h->stream));
-    hipLaunchKernelGGL(map_upper_kernel, dim3(map_grid(bytes, h)), dim3(256), 0, h->stream, d_reads.p, (unsigned long long)bytes);
-    HIPCHK(h, hipGetLastError());
-    MapSeedArgs sa;
-    sa.reads = d_reads.p, sa.roff = d_roff.p, sa.n = (long)n, sa.S = S, sa.P = P, sa.k = ix->k, sa.e = p->max_errors;
-    sa.max_occ = p->max_occ, sa.text = ix->d_text, sa.ix_off = ix->d_off, sa.ix_pos = ix->d_pos;
-    sa.seq_off = (const unsigned long long*)ix->d_seq_off, sa.n_seqs = (uint32_t)ix->n_seqs;
-    hipLaunchKernelGGL(map_seed_count_kernel, dim3(map_grid((uint64_t)nw, h)), dim3(256), 0, h->stream, sa, d_cnt.p, d_flags.p);
-    HIPCHK(h, hipGetLastError());
-    size_t tmp_bytes = 0;
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_cnt.p, d_base.p, (int)nw, h->stream));
-    HIPCHK(h, tmp.alloc(tmp_bytes + 16));
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, d_cnt.p, d_base.p, (int)nw, h->stream));
-    unsigned long long last[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(&last[0], d_base.p + nw - 1, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&last[1], d_cnt.p + nw - 1, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const unsigned long long total = last[0] + last[1];
+    if (const int rc = map_front(h, ix, n, reads, read_off, p, f)) return rc;
+    const std::vector<uint32_t>& roff = f.roff;
+    const int maxm = f.maxm, P = p->max_errors + 1;
+    const size_t bytes = f.bytes;
+    const int64_t nw = f.nw;
+    const unsigned long long total = f.total;
+    const MapSeedArgs& sa = f.sa;
+    Scratch<char>& d_reads = f.d_reads;
+    Scratch<uint32_t>& d_roff = f.d_roff;
+    Scratch<uint32_t>& d_flags = f.d_flags;
     /* rounds of at most map_cand_cap candidates: every round sees every work item and emits the part of it that falls in [c0, c1) */
     const unsigned long long cap = std::min<unsigned long long>(total, (unsigned long long)h->map_cand_cap);
     MapFinishArgs fa = {};
@@ -2536,7 +2583,7 @@ static int map_chunk(asm_handle* h, const asm_index* ix, int64_t n, const char* 
     for (unsigned long long c0 = 0; c0 < total; c0 += cap) {
         const unsigned long long c1 = std::min(total, c0 + cap);
         hipLaunchKernelGGL(map_seed_emit_kernel, dim3(map_grid((uint64_t)nw, h)), dim3(256), 0, h->stream, sa,
-                           (const unsigned long long*)d_base.p, (const unsigned long long*)d_cnt.p, c0, c1, d_cand.p);
+                           (const unsigned long long*)f.d_base.p, (const unsigned long long*)f.d_cnt.p, c0, c1, d_cand.p);
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, map_dispatch(h, maxm, false, d_cand.p, c1 - c0, d_reads.p, d_roff.p, ix, p->max_errors, d_keys.p, fa));
     }
@@ -2547,7 +2594,7 @@ static int map_chunk(asm_handle* h, const asm_index* ix, int64_t n, const char* 
     HIPCHK(h, d_nops.alloc((size_t)n));
     fa.reads = d_reads.p, fa.roff = d_roff.p, fa.n = (long)n, fa.e = p->max_errors, fa.P = P, fa.k = ix->k, fa.cap = ocap;
     fa.text = ix->d_text, fa.seq_off = (const unsigned long long*)ix->d_seq_off, fa.keys = d_keys.p, fa.flags = d_flags.p;
-    fa.dirs = d_dirs.p, fa.hits = d_hits.p, fa.ops = d_ops.p, fa.nops = d_nops.p;
+    fa.iread = nullptr, fa.idirs = nullptr, fa.dirs = d_dirs.p, fa.hits = d_hits.p, fa.ops = d_ops.p, fa.nops = d_nops.p;
     HIPCHK(h, map_dispatch(h, maxm, true, nullptr, 0, d_reads.p, d_roff.p, ix, p->max_errors, d_keys.p, fa));
     HIPCHK(h, hipMemcpyAsync(out, d_hits.p, sizeof(MapHit) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     if (ocap) {
@@ -2567,12 +2614,219 @@ static int map_chunk(asm_handle* h, const asm_index* ix, int64_t n, const char* 
     HIPCHK(h, d_list.alloc(sizeof(uint32_t) * (size_t)nl));
     HIPCHK(h, d_cost.alloc(sizeof(int32_t) * (size_t)nl));
     HIPCHK(h, hipMemcpyAsync(d_list.p, list.data(), sizeof(uint32_t) * (size_t)nl, hipMemcpyHostToDevice, h->stream));
-    int rc = map_greedy(h, ix, d_reads.p, d_roff.p, d_hits.p, d_list.p, nl, maxmap, p->greedy_k, d_cost.p);
+    int rc = map_greedy(h, ix, d_reads.p, d_roff.p, d_hits.p, nullptr, d_list.p, nl, maxmap, p->greedy_k, d_cost.p);
     if (rc) return rc;
     std::vector<int32_t> cost((size_t)nl);
     HIPCHK(h, hipMemcpyAsync(cost.data(), d_cost.p, sizeof(int32_t) * (size_t)nl, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int64_t q = 0; q < nl; q++) out[list[(size_t)q]].greedy_cost = cost[(size_t)q];
+    return ASM_OK;
+}
+
+/* asm_map_reads_all on one chunk (n < 2^31 reads, so that read << 33 fits the 64-bit run key): every window's intervals into the
+ * run buffer, a radix sort, the loci selected per read into an item list, then finish and Greedy once per item */
+static int map_chunk_all(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
+                         const asm_map_params* p, int strata, int max_hits, uint32_t* n_hits, asm_map_hit* out, uint16_t* cigar_ops,
+                         int cigar_cap, uint8_t* cigar_nops) {
+    MapFront f(h);
+    if (const int rc = map_front(h, ix, n, reads, read_off, p, f)) return rc;
+    const int e = p->max_errors;
+    Scratch<MapCand> d_cand(h);
+    Scratch<unsigned long long> d_counter(h), d_rkey(h), d_rkey2(h);
+    Scratch<uint32_t> d_rval(h), d_rval2(h);
+    Scratch<void> tmp(h);
+    unsigned long long rcap = 0, nr = 0;
+    HIPCHK(h, d_counter.alloc(sizeof(unsigned long long)));
+    HIPCHK(h, hipMemsetAsync(d_counter.p, 0, sizeof(unsigned long long), h->stream));
+    auto grow = [&](unsigned long long ncap) -> int { /* the run buffer to ncap records, keeping [0, nr) */
+        Scratch<unsigned long long> k2(h);
+        Scratch<uint32_t> v2(h);
+        HIPCHK(h, k2.alloc(sizeof(unsigned long long) * ncap));
+        HIPCHK(h, v2.alloc(sizeof(uint32_t) * ncap));
+        if (nr) {
+            HIPCHK(h, hipMemcpyAsync(k2.p, d_rkey.p, sizeof(unsigned long long) * nr, hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(v2.p, d_rval.p, sizeof(uint32_t) * nr, hipMemcpyDeviceToDevice, h->stream));
+        }
+        std::swap(d_rkey.p, k2.p);
+        std::swap(d_rval.p, v2.p);
+        rcap = ncap;
+        return ASM_OK;
+    };
+    /* the seeding rounds of map_chunk.  Before each, the buffer gets room for min(ASM_MAP_RUN_CAP, the round's candidates) more
+     * records (a window mostly gives one interval or none); after it, the run counter tells whether the buffer held the round's
+     * records.  If not, the buffer grows (keeping the earlier rounds' records), the counter goes back and the verify runs again. */
+    const unsigned long long cap = std::min<unsigned long long>(f.total, (unsigned long long)h->map_cand_cap);
+    const MapFinishArgs none = {};
+    if (f.total) HIPCHK(h, d_cand.alloc(sizeof(MapCand) * cap));
+    for (unsigned long long c0 = 0; c0 < f.total; c0 += cap) {
+        const unsigned long long c1 = std::min(f.total, c0 + cap);
+        hipLaunchKernelGGL(map_seed_emit_kernel, dim3(map_grid((uint64_t)f.nw, h)), dim3(256), 0, h->stream, f.sa,
+                           (const unsigned long long*)f.d_base.p, (const unsigned long long*)f.d_cnt.p, c0, c1, d_cand.p);
+        HIPCHK(h, hipGetLastError());
+        const unsigned long long want = nr + std::min(c1 - c0, (unsigned long long)h->map_run_cap);
+        if (want > rcap)
+            if (const int rc = grow(std::max(want, rcap + rcap / 2))) return rc;
+        for (;;) {
+            const MapRunBuf rb = {d_counter.p, rcap, d_rkey.p, d_rval.p};
+            HIPCHK(h, map_dispatch(h, f.maxm, false, d_cand.p, c1 - c0, f.d_reads.p, f.d_roff.p, ix, e, nullptr, none, &rb));
+            unsigned long long got = 0;
+            HIPCHK(h, hipMemcpyAsync(&got, d_counter.p, sizeof(got), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            if (got <= rcap) {
+                nr = got;
+                break;
+            }
+            if (const int rc = grow(std::max(got, 2 * rcap))) return rc;
+            HIPCHK(h, hipMemcpyAsync(d_counter.p, &nr, sizeof(nr), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream)); /* nr is read by the copy above before it may change */
+        }
+    }
+    if (nr > (unsigned long long)INT32_MAX) return fail(h, ASM_EUNSUPPORTED, "asm_map_reads_all: more than 2^31 - 1 run records in a chunk");
+    /* sort by (read, s, lo): only the bits in use (read < n) */
+    int rbits = 0;
+    while (rbits < 31 && (1ull << rbits) < (unsigned long long)n) rbits++;
+    const int end_bit = MAP_RUN_READ_SHIFT + rbits;
+    HIPCHK(h, d_rkey2.alloc(sizeof(unsigned long long) * (nr + 1)));
+    HIPCHK(h, d_rval2.alloc(sizeof(uint32_t) * (nr + 1)));
+    if (nr) {
+        size_t tmp_bytes = 0;
+        HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_rkey.p, d_rkey2.p, d_rval.p, d_rval2.p, (int)nr, 0, end_bit,
+                                                     h->stream));
+        HIPCHK(h, tmp.alloc(tmp_bytes + 16));
+        HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, d_rkey.p, d_rkey2.p, d_rval.p, d_rval2.p, (int)nr, 0, end_bit,
+                                                     h->stream));
+    }
+    /* loci per read: count, then (host) the item layout, then emit */
+    Scratch<uint32_t> d_nh(h), d_dbest(h), d_ibase(h), d_iread(h), d_list(h);
+    Scratch<unsigned long long> d_dbase(h), d_ikey(h), d_idirs(h);
+    HIPCHK(h, d_nh.alloc(sizeof(uint32_t) * (size_t)n));
+    HIPCHK(h, d_dbest.alloc(sizeof(uint32_t) * (size_t)n));
+    MapSelectArgs sel = {};
+    sel.rkey = d_rkey2.p, sel.rval = d_rval2.p, sel.nr = nr, sel.n = (long)n, sel.e = e, sel.strata = strata, sel.max_hits = max_hits;
+    sel.seq_off = (const unsigned long long*)ix->d_seq_off, sel.n_seqs = (uint32_t)ix->n_seqs, sel.roff = f.d_roff.p;
+    sel.n_hits = d_nh.p, sel.d_best = d_dbest.p;
+    hipLaunchKernelGGL(map_select_count_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(n_hits, d_nh.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    /* items: max(1, min(n_hits, max_hits)) per read, in read-then-rank order; dirs: (m + 1) words per item */
+    std::vector<uint32_t> ibase((size_t)n + 1);
+    std::vector<unsigned long long> dbase((size_t)n);
+    unsigned long long dwords = 0;
+    for (int64_t i = 0; i < n; i++) {
+        const uint32_t ni = n_hits[i] ? std::min<uint32_t>(n_hits[i], (uint32_t)max_hits) : 1u;
+        ibase[(size_t)i + 1] = ibase[(size_t)i] + ni;
+        dbase[(size_t)i] = dwords;
+        dwords += (unsigned long long)ni * (f.roff[(size_t)i + 1] - f.roff[(size_t)i] + 1u);
+    }
+    const int64_t ni = ibase[(size_t)n];
+    HIPCHK(h, d_ibase.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
+    HIPCHK(h, d_dbase.alloc(sizeof(unsigned long long) * (size_t)n));
+    HIPCHK(h, d_iread.alloc(sizeof(uint32_t) * (size_t)ni));
+    HIPCHK(h, d_ikey.alloc(sizeof(unsigned long long) * (size_t)ni));
+    HIPCHK(h, d_idirs.alloc(sizeof(unsigned long long) * (size_t)ni));
+    HIPCHK(h, hipMemcpyAsync(d_ibase.p, ibase.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_dbase.p, dbase.data(), sizeof(unsigned long long) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    sel.ibase = d_ibase.p, sel.dbase = d_dbase.p, sel.iread = d_iread.p, sel.ikey = d_ikey.p, sel.idirs = d_idirs.p;
+    hipLaunchKernelGGL(map_select_emit_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel);
+    HIPCHK(h, hipGetLastError());
+    /* finish per item */
+    const int ocap = cigar_cap > 0 ? cigar_cap : 0;
+    Scratch<uint64_t> d_dirs(h);
+    Scratch<MapHit> d_hits(h);
+    Scratch<uint16_t> d_ops(h);
+    Scratch<uint8_t> d_nops(h);
+    Scratch<int32_t> d_cost(h);
+    HIPCHK(h, d_dirs.alloc(sizeof(uint64_t) * dwords));
+    HIPCHK(h, d_hits.alloc(sizeof(MapHit) * (size_t)ni));
+    HIPCHK(h, d_ops.alloc(sizeof(uint16_t) * ((size_t)ni * ocap + 1)));
+    HIPCHK(h, d_nops.alloc((size_t)ni));
+    MapFinishArgs fa = {};
+    fa.reads = f.d_reads.p, fa.roff = f.d_roff.p, fa.n = (long)ni, fa.e = e, fa.P = e + 1, fa.k = ix->k, fa.cap = ocap;
+    fa.text = ix->d_text, fa.seq_off = (const unsigned long long*)ix->d_seq_off, fa.keys = d_ikey.p, fa.flags = f.d_flags.p;
+    fa.iread = d_iread.p, fa.idirs = d_idirs.p, fa.dirs = d_dirs.p, fa.hits = d_hits.p, fa.ops = d_ops.p, fa.nops = d_nops.p;
+    HIPCHK(h, map_dispatch(h, f.maxm, true, nullptr, 0, f.d_reads.p, f.d_roff.p, ix, e, nullptr, fa));
+    std::vector<asm_map_hit> hits((size_t)ni);
+    std::vector<uint16_t> ops((size_t)ni * ocap);
+    std::vector<uint8_t> nops((size_t)ni);
+    std::vector<uint32_t> iread((size_t)ni);
+    HIPCHK(h, hipMemcpyAsync(hits.data(), d_hits.p, sizeof(MapHit) * (size_t)ni, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(iread.data(), d_iread.p, sizeof(uint32_t) * (size_t)ni, hipMemcpyDeviceToHost, h->stream));
+    if (ocap) {
+        HIPCHK(h, hipMemcpyAsync(ops.data(), d_ops.p, sizeof(uint16_t) * (size_t)ni * ocap, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(nops.data(), d_nops.p, (size_t)ni, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    /* Greedy per mapped item */
+    std::vector<uint32_t> list;
+    int maxmap = 0;
+    for (int64_t q = 0; q < ni; q++)
+        if (hits[(size_t)q].flags & ASM_MAP_MAPPED) {
+            list.push_back((uint32_t)q);
+            const uint32_t i = iread[(size_t)q];
+            maxmap = std::max(maxmap, (int)(f.roff[(size_t)i + 1] - f.roff[(size_t)i]));
+        }
+    if (!list.empty()) {
+        const int64_t nl = (int64_t)list.size();
+        HIPCHK(h, d_list.alloc(sizeof(uint32_t) * (size_t)nl));
+        HIPCHK(h, d_cost.alloc(sizeof(int32_t) * (size_t)nl));
+        HIPCHK(h, hipMemcpyAsync(d_list.p, list.data(), sizeof(uint32_t) * (size_t)nl, hipMemcpyHostToDevice, h->stream));
+        const int rc = map_greedy(h, ix, f.d_reads.p, f.d_roff.p, d_hits.p, d_iread.p, d_list.p, nl, maxmap, p->greedy_k, d_cost.p);
+        if (rc) return rc;
+        std::vector<int32_t> cost((size_t)nl);
+        HIPCHK(h, hipMemcpyAsync(cost.data(), d_cost.p, sizeof(int32_t) * (size_t)nl, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int64_t q = 0; q < nl; q++) hits[list[(size_t)q]].greedy_cost = cost[(size_t)q];
+    }
+    /* into the caller's [n][max_hits] slots (a read's items are contiguous); the flags that depend on the rank are set here.  The
+     * CIGAR rows of unused slots are not written: their cigar_nops is 0. */
+    const asm_map_hit unused = {-1, 0, 0, -1, 0, 0, -1};
+    for (int64_t i = 0; i < n; i++) {
+        const uint32_t q0 = ibase[(size_t)i], cnt = ibase[(size_t)i + 1] - q0;
+        const size_t o = (size_t)i * max_hits;
+        std::copy(hits.begin() + q0, hits.begin() + q0 + cnt, out + o);
+        for (uint32_t t = 1; t < cnt; t++) out[o + t].flags |= ASM_MAP_SECONDARY;
+        if (n_hits[i] > (uint32_t)max_hits)
+            for (uint32_t t = 0; t < cnt; t++) out[o + t].flags |= ASM_MAP_HITS_TRUNCATED;
+        std::fill(out + o + cnt, out + o + max_hits, unused);
+        if (ocap) {
+            std::copy(ops.begin() + (size_t)q0 * ocap, ops.begin() + (size_t)(q0 + cnt) * ocap, cigar_ops + o * ocap);
+            std::copy(nops.begin() + q0, nops.begin() + q0 + cnt, cigar_nops + o);
+            std::fill(cigar_nops + o + cnt, cigar_nops + o + max_hits, (uint8_t)0);
+        }
+    }
+    return ASM_OK;
+}
+
+int asm_map_reads_all(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
+                      const asm_map_params* p, int strata, int max_hits, uint32_t* n_hits, asm_map_hit* out, uint16_t* cigar_ops,
+                      int cigar_cap, uint8_t* cigar_nops) {
+    if (!p || !ix || n < 0 || !read_off || (n > 0 && (!reads || !out || !n_hits)))
+        return fail(h, ASM_EINVAL, "asm_map_reads_all: bad arguments");
+    if (p->max_errors < 0 || p->max_errors > ASM_MAP_MAX_ERRORS) return fail(h, ASM_EINVAL, "asm_map_reads_all: max_errors must be in [0, 15]");
+    if (p->both_strands != 0 && p->both_strands != 1) return fail(h, ASM_EINVAL, "asm_map_reads_all: both_strands must be 0 or 1");
+    if (p->max_occ < 0) return fail(h, ASM_EINVAL, "asm_map_reads_all: max_occ must be >= 0");
+    if (p->greedy_k < 0 || p->greedy_k > ASM_GREEDY_MAX_K) return fail(h, ASM_EINVAL, "asm_map_reads_all: greedy_k must be in [0, 50]");
+    if (strata < 0 || strata > ASM_MAP_MAX_ERRORS) return fail(h, ASM_EINVAL, "asm_map_reads_all: strata must be in [0, 15]");
+    if (max_hits < 1 || max_hits > ASM_MAP_MAX_HITS) return fail(h, ASM_EINVAL, "asm_map_reads_all: max_hits must be in [1, 256]");
+    if (cigar_cap < 0 || (cigar_cap > 0 && (!cigar_ops || !cigar_nops)))
+        return fail(h, ASM_EINVAL, "asm_map_reads_all: cigar_cap > 0 needs cigar_ops and cigar_nops");
+    for (int64_t i = 0; i < n; i++) {
+        if (read_off[i + 1] < read_off[i]) return fail(h, ASM_EINVAL, "asm_map_reads_all: read offsets must be non-decreasing");
+        const uint32_t m = read_off[i + 1] - read_off[i];
+        if (m < 1 || m > ASM_MAP_MAX_READ) return fail(h, ASM_EINVAL, "asm_map_reads_all: every read must have 1 to 511 bytes");
+    }
+    if (!h) return fail(h, ASM_EINVAL, "asm_map_reads_all: NULL handle");
+    if (ix->device != h->device) return fail(h, ASM_EINVAL, "asm_map_reads_all: the index lives on another device");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int64_t step = std::min<int64_t>(h->map_chunk, (int64_t)1 << 30); /* the run key holds the read in its top 31 bits */
+    for (int64_t c0 = 0; c0 < n; c0 += step) {
+        const int64_t c1 = std::min(n, c0 + step);
+        const size_t o = (size_t)c0 * max_hits;
+        const int rc = map_chunk_all(h, ix, c1 - c0, reads, read_off + c0, p, strata, max_hits, n_hits + c0, out + o,
+                                     cigar_cap > 0 ? cigar_ops + o * cigar_cap : nullptr, cigar_cap, cigar_cap > 0 ? cigar_nops + o : nullptr);
+        if (rc) return rc;
+    }
     return ASM_OK;
 }
 

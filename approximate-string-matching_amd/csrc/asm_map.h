@@ -13,6 +13,10 @@
 //          (d, strand, seq, end) into the read's packed key with an integer atomicMin, map_finish_kernel<W> finds the start
 //          (reverse global bit-vector pass), runs a banded DP under the byte rule and writes the CIGAR, and map_greedy_*
 //          gather the Greedy windows of the mapped reads.
+// All hits (asm_map_reads_all): map_verify_all_kernel<W> appends every window's maximal intervals of ends within e to a run
+//          buffer, a radix sort orders them by (read, strand, position), map_select_count_kernel / map_select_emit_kernel merge
+//          them into loci and list the reported ones as items (read, packed key), and the finish and Greedy kernels run once per
+//          item.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -282,6 +286,163 @@ __global__ __launch_bounds__(256) void map_verify_kernel(const MapCand* __restri
     }
 }
 
+/* ---- all hits (asm_map_reads_all): every locus within e, not only the best ------------------------------------------------
+ * A window reports each maximal interval of ends with D_w <= e as a run record: key = read << 33 | s << 32 | lo and val =
+ * dmin << 20 | (jmin - lo) << 10 | (hi - lo), where lo, hi and jmin are inclusive global positions (the last text byte of an
+ * occurrence; the exclusive end is one more), so that map_seq_of(lo) is the sequence.  A window spans at most 511 + 2 * 15
+ * positions, so both offsets fit 10 bits. */
+#define MAP_RUN_READ_SHIFT 33
+#define MAP_RUN_SPAN_BITS 10
+
+/* a slot in the run buffer for each active lane: one atomicAdd per wave (lanes of a wave close intervals at the same column) */
+ASM_DEV unsigned long long map_wave_slot(unsigned long long* counter) {
+    const uint64_t mask = __ballot(1);
+    const int lane = (int)(threadIdx.x & 63u), leader = __ffsll((long long)mask) - 1;
+    const uint32_t below = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+    unsigned long long base = 0;
+    if (lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(mask));
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)base, leader), hi = (uint32_t)__shfl((int)(uint32_t)(base >> 32), leader);
+    return ((unsigned long long)hi << 32 | lo) + below;
+}
+
+ASM_DEV void map_put_run(unsigned long long* counter, unsigned long long cap, unsigned long long* __restrict__ rkey,
+                         uint32_t* __restrict__ rval, uint32_t read, uint32_t s, uint32_t lo, uint32_t hi, int dmin, uint32_t jmin) {
+    const unsigned long long slot = map_wave_slot(counter); /* the counter always advances: the host sees how many did not fit */
+    if (slot < cap) {
+        rkey[slot] = (unsigned long long)read << MAP_RUN_READ_SHIFT | (unsigned long long)s << 32 | lo;
+        rval[slot] = (uint32_t)dmin << 20 | (jmin - lo) << MAP_RUN_SPAN_BITS | (hi - lo);
+    }
+}
+
+/* thread per candidate: the column loop of map_verify_kernel<W>, but every maximal interval of ends with D_w <= e is appended to
+ * the run buffer (see above) instead of folding the window's best into an atomicMin */
+template <int W>
+__global__ __launch_bounds__(256) void map_verify_all_kernel(const MapCand* __restrict__ cand, unsigned long long nc,
+                                                             const char* __restrict__ reads, const uint32_t* __restrict__ roff,
+                                                             const char* __restrict__ text, int e, unsigned long long* counter,
+                                                             unsigned long long cap, unsigned long long* __restrict__ rkey,
+                                                             uint32_t* __restrict__ rval) {
+    for (unsigned long long c = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; c < nc;
+         c += (unsigned long long)gridDim.x * blockDim.x) {
+        const MapCand x = cand[c];
+        if (x.read == MAP_BAD_CAND) continue;
+        const uint32_t r0 = roff[x.read], m = roff[x.read + 1] - r0, s = x.rs & 1u;
+        uint64_t peq[4][W];
+        map_build_peq<W>(reads + r0, m, s, false, peq);
+        uint64_t Pv[W], Mv[W];
+#pragma unroll
+        for (int w = 0; w < W; w++) Pv[w] = ~0ull, Mv[w] = 0ull;
+        const int nw = (int)((m + 63u) >> 6);
+        const uint32_t last_bit = (m - 1u) & 63u;
+        int score = (int)m, dmin = e + 1;
+        uint32_t lo = 0, jmin = 0;
+        for (uint32_t t = x.ws; t < x.we; t++) {
+            score += map_column<W>(Pv, Mv, peq, map_code((uint8_t)text[t]), nw, last_bit, 0);
+            if (score <= e) {
+                if (dmin > e) lo = t, dmin = score, jmin = t; /* an interval opens */
+                else if (score < dmin) dmin = score, jmin = t;
+            } else if (dmin <= e) {
+                map_put_run(counter, cap, rkey, rval, x.read, s, lo, t - 1u, dmin, jmin);
+                dmin = e + 1;
+            }
+        }
+        if (dmin <= e) map_put_run(counter, cap, rkey, rval, x.read, s, lo, x.we - 1u, dmin, jmin);
+    }
+}
+
+/* first index of the sorted run keys whose read is >= `read` */
+ASM_DEV unsigned long long map_run_lower(const unsigned long long* rkey, unsigned long long nr, unsigned long long read) {
+    unsigned long long lo = 0, hi = nr;
+    while (lo < hi) {
+        const unsigned long long mid = (lo + hi) >> 1;
+        if ((rkey[mid] >> MAP_RUN_READ_SHIFT) < read) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+/* Walk the sorted run records [b, e) of one read and call f(s, r, d, j) once per locus, in (s, r, j) order: records of the same
+ * strand and sequence merge when they overlap or touch (lo <= hi + 1); d = min dmin, j = the smallest jmin among the records
+ * reaching it (inclusive global position). */
+template <class F>
+ASM_DEV void map_walk_loci(const unsigned long long* __restrict__ rkey, const uint32_t* __restrict__ rval, unsigned long long b,
+                           unsigned long long e, const unsigned long long* __restrict__ seq_off, uint32_t n_seqs, F&& f) {
+    uint32_t cs = 0, cr = 0, chi = 0, cj = 0;
+    int cd = -1;
+    unsigned long long cend = 0; /* end of sequence cr (exclusive, global) */
+    for (unsigned long long q = b; q < e; q++) {
+        const unsigned long long k = rkey[q];
+        const uint32_t v = rval[q], s = (uint32_t)(k >> 32) & 1u, lo = (uint32_t)k;
+        const uint32_t hi = lo + (v & ((1u << MAP_RUN_SPAN_BITS) - 1u)), j = lo + ((v >> MAP_RUN_SPAN_BITS) & ((1u << MAP_RUN_SPAN_BITS) - 1u));
+        const int d = (int)(v >> 20);
+        if (cd >= 0 && s == cs && (unsigned long long)lo < cend && lo <= chi + 1u) {
+            if (hi > chi) chi = hi;
+            if (d < cd || (d == cd && j < cj)) cd = d, cj = j;
+            continue;
+        }
+        if (cd >= 0) f(cs, cr, cd, cj);
+        cs = s, cr = map_seq_of(seq_off, n_seqs, lo), cend = seq_off[cr + 1], chi = hi, cd = d, cj = j;
+    }
+    if (cd >= 0) f(cs, cr, cd, cj);
+}
+
+struct MapSelectArgs {
+    const unsigned long long* rkey; /* sorted */
+    const uint32_t* rval;
+    unsigned long long nr;
+    long n;                          /* reads */
+    int e, strata, max_hits;
+    const unsigned long long* seq_off;
+    uint32_t n_seqs;
+    const uint32_t* roff;
+    uint32_t* n_hits;                /* per read: loci with d <= min(e, d_best + strata) */
+    uint32_t* d_best;                /* per read (count pass), 0 when n_hits = 0 */
+    const uint32_t* ibase;           /* per read: first item (emit pass) */
+    const unsigned long long* dbase; /* per read: dirs offset of its first item (emit pass) */
+    uint32_t* iread;                 /* per item */
+    unsigned long long* ikey;        /* per item: d << 59 | s << 58 | r << 32 | j (exclusive, local to r); MAP_NO_KEY = unmapped */
+    unsigned long long* idirs;       /* per item */
+};
+
+/* thread per read: d_best and n_hits of its loci */
+__global__ __launch_bounds__(256) void map_select_count_kernel(MapSelectArgs a) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (long)gridDim.x * blockDim.x) {
+        const unsigned long long b = map_run_lower(a.rkey, a.nr, (unsigned long long)i), e = map_run_lower(a.rkey, a.nr, (unsigned long long)i + 1);
+        int best = a.e + 1;
+        map_walk_loci(a.rkey, a.rval, b, e, a.seq_off, a.n_seqs, [&](uint32_t, uint32_t, int d, uint32_t) { best = d < best ? d : best; });
+        const int lim = best + a.strata < a.e ? best + a.strata : a.e;
+        uint32_t cnt = 0;
+        if (best <= a.e)
+            map_walk_loci(a.rkey, a.rval, b, e, a.seq_off, a.n_seqs, [&](uint32_t, uint32_t, int d, uint32_t) { cnt += d <= lim; });
+        a.n_hits[i] = cnt;
+        a.d_best[i] = best <= a.e ? (uint32_t)best : 0u;
+    }
+}
+
+/* thread per read: its items in (d, s, r, j) order, one walk per d level from d_best up (the walk itself is in (s, r, j) order);
+ * a read without loci gets one item with MAP_NO_KEY (the unmapped record) */
+__global__ __launch_bounds__(256) void map_select_emit_kernel(MapSelectArgs a) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (long)gridDim.x * blockDim.x) {
+        const uint32_t q0 = a.ibase[i], m = a.roff[i + 1] - a.roff[i];
+        const unsigned long long db = a.dbase[i];
+        const uint32_t nh = a.n_hits[i], want = nh < (uint32_t)a.max_hits ? nh : (uint32_t)a.max_hits;
+        if (!nh) {
+            a.iread[q0] = (uint32_t)i, a.ikey[q0] = MAP_NO_KEY, a.idirs[q0] = db;
+            continue;
+        }
+        const unsigned long long b = map_run_lower(a.rkey, a.nr, (unsigned long long)i), e = map_run_lower(a.rkey, a.nr, (unsigned long long)i + 1);
+        uint32_t k = 0;
+        for (int lvl = (int)a.d_best[i]; lvl <= a.e && k < want; lvl++)
+            map_walk_loci(a.rkey, a.rval, b, e, a.seq_off, a.n_seqs, [&](uint32_t s, uint32_t r, int d, uint32_t j) {
+                if (d != lvl || k >= want) return;
+                const unsigned long long jl = (unsigned long long)j + 1ull - a.seq_off[r];
+                a.iread[q0 + k] = (uint32_t)i;
+                a.ikey[q0 + k] = (unsigned long long)d << 59 | (unsigned long long)s << 58 | (unsigned long long)r << 32 | jl;
+                a.idirs[q0 + k] = db + (unsigned long long)k * (m + 1u);
+                k++;
+            });
+    }
+}
+
 struct MapFinishArgs {
     const char* reads;
     const uint32_t* roff;
@@ -289,29 +450,34 @@ struct MapFinishArgs {
     int e, P, k, cap;
     const char* text;
     const unsigned long long* seq_off;
-    const unsigned long long* keys;
-    const uint32_t* flags;
-    uint64_t* dirs;      /* (m + 1) words per read, at roff[i] + i */
-    MapHit* hits;
-    uint16_t* ops;       /* [n][cap] */
+    const unsigned long long* keys;     /* per item */
+    const uint32_t* flags;              /* per read */
+    const uint32_t* iread;              /* ITEMS: per item, its read (else the identity list: item i is read i) */
+    const unsigned long long* idirs;    /* ITEMS: per item, its dirs offset (else roff[i] + i) */
+    uint64_t* dirs;      /* (m + 1) words per item */
+    MapHit* hits;        /* per item */
+    uint16_t* ops;       /* [n items][cap] */
     uint8_t* nops;
 };
 
-/* thread per read: start (largest i reaching d with end j), banded traceback under the byte rule, CIGAR, hit record */
-template <int W>
+/* thread per item (a read and a packed key; n = items): start (largest i reaching d with end j), banded traceback under the byte
+ * rule, CIGAR, hit record.  ITEMS = false is the identity list of asm_map_reads (its own instantiation, so that the indirection
+ * costs that call nothing). */
+template <int W, bool ITEMS>
 __global__ __launch_bounds__(256) void map_finish_kernel(MapFinishArgs a) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (long)gridDim.x * blockDim.x) {
+    for (long it = (long)blockIdx.x * blockDim.x + threadIdx.x; it < a.n; it += (long)gridDim.x * blockDim.x) {
+        const long i = ITEMS ? (long)a.iread[it] : it;
         const uint32_t r0 = a.roff[i], m = a.roff[i + 1] - r0;
         const char* q = a.reads + r0;
-        const unsigned long long key = a.keys[i];
+        const unsigned long long key = a.keys[it];
         MapHit h;
         h.seq_id = -1, h.pos = 0, h.end = 0, h.dist = -1, h.strand = 0, h.greedy_cost = -1;
         uint32_t fl = a.flags[i];
         if (m < (uint32_t)(a.P * a.k)) fl |= MAP_F_TOO_SHORT;
         if (key == MAP_NO_KEY) {
             h.flags = (uint8_t)fl;
-            a.hits[i] = h;
-            a.nops[i] = 0;
+            a.hits[it] = h;
+            a.nops[it] = 0;
             continue;
         }
         const int d = (int)(key >> 59);
@@ -341,7 +507,7 @@ __global__ __launch_bounds__(256) void map_finish_kernel(MapFinishArgs a) {
          * dirs: 2 bits per lane, 0 diagonal, 1 up (I), 2 left (D); ties prefer diagonal, then I, then D */
         const int n = (int)(j - start);
         const int INF = 2 * MAP_MAX_ERRORS + 2;
-        uint64_t* dirs = a.dirs + r0 + (uint32_t)i;
+        uint64_t* dirs = a.dirs + (ITEMS ? a.idirs[it] : (unsigned long long)(r0 + (uint32_t)i));
         const char* tx = a.text + s0 + start;
         int row[MAP_BAND];
         uint32_t tw[MAP_BAND]; /* code of text column b = a + delta (1-based: T[start + b - 1]); 5 = outside */
@@ -393,7 +559,7 @@ __global__ __launch_bounds__(256) void map_finish_kernel(MapFinishArgs a) {
                 const uint32_t dir = (uint32_t)(dirs[ar] >> (2 * l)) & 3u;
                 const uint32_t o = dir == 0u ? 0u : dir == 1u ? 1u : 2u; /* M, I, D */
                 if (o != op && len) {
-                    if (pass == 1 && runs - 1 - k < a.cap) a.ops[(long)i * a.cap + (runs - 1 - k)] = (uint16_t)(len << 3 | op);
+                    if (pass == 1 && runs - 1 - k < a.cap) a.ops[it * a.cap + (runs - 1 - k)] = (uint16_t)(len << 3 | op);
                     k++;
                     len = 0;
                 }
@@ -404,22 +570,24 @@ __global__ __launch_bounds__(256) void map_finish_kernel(MapFinishArgs a) {
                 else l--;
             }
             if (len) {
-                if (pass == 1 && runs - 1 - k < a.cap) a.ops[(long)i * a.cap + (runs - 1 - k)] = (uint16_t)(len << 3 | op);
+                if (pass == 1 && runs - 1 - k < a.cap) a.ops[it * a.cap + (runs - 1 - k)] = (uint16_t)(len << 3 | op);
                 k++;
             }
             runs = k;
         }
         if (runs > a.cap) fl |= MAP_F_CIGAR_TRUNCATED;
-        a.nops[i] = (uint8_t)(runs > 255 ? 255 : runs);
+        a.nops[it] = (uint8_t)(runs > 255 ? 255 : runs);
         h.seq_id = (int32_t)r, h.pos = start, h.end = j, h.dist = (int16_t)d, h.strand = (uint8_t)s;
         h.flags = (uint8_t)(fl | MAP_F_MAPPED);
-        a.hits[i] = h;
+        a.hits[it] = h;
     }
 }
 
-/* Greedy windows of the mapped reads (list = their indices): T_r[w, min(w + m + 1, len_r)) with w = pos ? pos - 1 : 0, clipped to
- * the read's own sequence.  lens[q] = (read length, window length); the gather writes q_s and the window. */
-__global__ __launch_bounds__(256) void map_greedy_lengths_kernel(const uint32_t* __restrict__ list, long nl, const uint32_t* __restrict__ roff,
+/* Greedy windows of the mapped items (list = their indices into hits; iread = each item's read, NULL when item i is read i):
+ * T_r[w, min(w + m + 1, len_r)) with w = pos ? pos - 1 : 0, clipped to the read's own sequence.  lens[q] = (read length, window
+ * length); the gather writes q_s and the window. */
+__global__ __launch_bounds__(256) void map_greedy_lengths_kernel(const uint32_t* __restrict__ list, const uint32_t* __restrict__ iread,
+                                                                 long nl, const uint32_t* __restrict__ roff,
                                                                  const MapHit* __restrict__ hits, const unsigned long long* __restrict__ seq_off,
                                                                  uint32_t* __restrict__ qlen, uint32_t* __restrict__ wlen) {
     const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -428,15 +596,16 @@ __global__ __launch_bounds__(256) void map_greedy_lengths_kernel(const uint32_t*
         qlen[nl] = 0u, wlen[nl] = 0u;
         return;
     }
-    const uint32_t i = list[q], m = roff[i + 1] - roff[i];
-    const MapHit h = hits[i];
+    const uint32_t it = list[q], i = iread ? iread[it] : it, m = roff[i + 1] - roff[i];
+    const MapHit h = hits[it];
     const unsigned long long len_r = seq_off[h.seq_id + 1] - seq_off[h.seq_id];
     const unsigned long long w = h.pos ? h.pos - 1u : 0u, e = w + m + 1ull < len_r ? w + m + 1ull : len_r;
     qlen[q] = m;
     wlen[q] = (uint32_t)(e - w);
 }
 
-__global__ __launch_bounds__(256) void map_greedy_gather_kernel(const uint32_t* __restrict__ list, long nl, const char* __restrict__ reads,
+__global__ __launch_bounds__(256) void map_greedy_gather_kernel(const uint32_t* __restrict__ list, const uint32_t* __restrict__ iread,
+                                                                long nl, const char* __restrict__ reads,
                                                                 const uint32_t* __restrict__ roff, const MapHit* __restrict__ hits,
                                                                 const char* __restrict__ text, const unsigned long long* __restrict__ seq_off,
                                                                 const uint32_t* __restrict__ qoff, const uint32_t* __restrict__ woff,
@@ -445,8 +614,8 @@ __global__ __launch_bounds__(256) void map_greedy_gather_kernel(const uint32_t* 
     const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
     for (long q = wave; q < nl; q += nwaves) { /* one wave per window */
-        const uint32_t i = list[q], r0 = roff[i], m = roff[i + 1] - r0;
-        const MapHit h = hits[i];
+        const uint32_t it = list[q], i = iread ? iread[it] : it, r0 = roff[i], m = roff[i + 1] - r0;
+        const MapHit h = hits[it];
         const unsigned long long w = seq_off[h.seq_id] + (h.pos ? h.pos - 1u : 0u);
         for (uint32_t p = (uint32_t)lane; p < m; p += 64u) qout[qoff[q] + p] = (char)map_read_byte(reads + r0, m, h.strand, p);
         const uint32_t o = woff[q], len = woff[q + 1] - o;

@@ -2,7 +2,10 @@
 // counterpart of the reference's `my-mapper` (GASMA/mapper/main.cpp) without its on-disk index: the k-mer index is built in HBM
 // at start-up.
 //   asm-map -r ref.fa -q reads.fq [-o out.sam] [-e N] [--k 12] [--both-strands] [--max-occ N] [--chunk N]
-// Reads may be FASTQ or FASTA (QUAL '*').  Reads are processed in chunks of --chunk records, so the read file's size is not
+//           [--all-hits N [--strata S]]
+// --all-hits N writes up to N loci per read in rank order (asm_map_reads_all, strata S, default e): the primary record as without
+// it, then the secondary ones (FLAG 256, SEQ and QUAL '*'), each with NH:i:<reported> HI:i:<rank + 1> XH:i:<all loci> after NM
+// and XG.  Reads may be FASTQ or FASTA (QUAL '*').  Reads are processed in chunks of --chunk records, so the read file's size is not
 // bounded by memory.  Reads longer than ASM_MAP_MAX_READ are written unmapped.
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,7 +17,8 @@
 #include "asm_mi355x.h"
 
 static void usage() {
-    fprintf(stderr, "usage: asm-map -r ref.fa -q reads.fq [-o out.sam] [-e N] [--k 12] [--both-strands] [--max-occ N] [--chunk N]\n");
+    fprintf(stderr, "usage: asm-map -r ref.fa -q reads.fq [-o out.sam] [-e N] [--k 12] [--both-strands] [--max-occ N] [--chunk N] "
+                    "[--all-hits N [--strata S]]\n");
     exit(2);
 }
 
@@ -87,6 +91,7 @@ int main(int argc, char** argv) {
     asm_map_params p = {0, 0, 0, 3};
     int k = 12;
     long chunk = 262144;
+    int all_hits = 0, strata = -1; /* all_hits 0: the best hit only */
     std::string cl = "asm-map";
     for (int a = 1; a < argc; a++) cl += std::string(" ") + argv[a];
     for (int a = 1; a < argc; a++) {
@@ -103,9 +108,13 @@ int main(int argc, char** argv) {
         else if (s == "--both-strands") p.both_strands = 1;
         else if (s == "--max-occ") p.max_occ = atoi(val());
         else if (s == "--chunk") chunk = atol(val());
+        else if (s == "--all-hits") all_hits = atoi(val());
+        else if (s == "--strata") strata = atoi(val());
         else usage();
     }
-    if (ref_path.empty() || read_path.empty() || chunk < 1) usage();
+    if (ref_path.empty() || read_path.empty() || chunk < 1 || all_hits < 0 || (strata >= 0 && !all_hits)) usage();
+    if (strata < 0) strata = p.max_errors;
+    const int slots = all_hits ? all_hits : 1; /* records per read in the library's output */
 
     /* reference: name = first word of the header */
     std::vector<std::string> names;
@@ -172,6 +181,7 @@ int main(int argc, char** argv) {
     std::vector<asm_map_hit> hits;
     std::vector<uint16_t> ops;
     std::vector<uint8_t> nops;
+    std::vector<uint32_t> n_hits;
     long long n_total = 0, n_mapped = 0, n_long = 0;
     bool more = true;
     while (more) {
@@ -192,10 +202,15 @@ int main(int argc, char** argv) {
             ro.push_back((uint32_t)buf.size());
         }
         const int64_t n = (int64_t)ro.size() - 1;
-        hits.assign((size_t)n + 1, asm_map_hit{});
-        ops.assign((size_t)(n + 1) * cap, 0);
-        nops.assign((size_t)n + 1, 0);
-        rc = asm_map_reads(h, ix, n, buf.data(), ro.data(), &p, hits.data(), ops.data(), cap, nops.data());
+        hits.assign((size_t)(n + 1) * slots, asm_map_hit{});
+        ops.assign((size_t)(n + 1) * slots * cap, 0);
+        nops.assign((size_t)(n + 1) * slots, 0);
+        n_hits.assign((size_t)n + 1, 0);
+        if (all_hits)
+            rc = asm_map_reads_all(h, ix, n, buf.data(), ro.data(), &p, strata, all_hits, n_hits.data(), hits.data(), ops.data(), cap,
+                                   nops.data());
+        else
+            rc = asm_map_reads(h, ix, n, buf.data(), ro.data(), &p, hits.data(), ops.data(), cap, nops.data());
         if (rc) {
             fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
             return 1;
@@ -203,7 +218,7 @@ int main(int argc, char** argv) {
         for (size_t q = 0; q < recs.size(); q++) {
             const Record& rec = recs[q];
             n_total++;
-            const asm_map_hit* hp = slot[q] >= 0 ? &hits[(size_t)slot[q]] : nullptr;
+            const asm_map_hit* hp = slot[q] >= 0 ? &hits[(size_t)slot[q] * slots] : nullptr;
             if (!hp || !(hp->flags & ASM_MAP_MAPPED)) {
                 fprintf(out, "%s\t4\t*\t0\t0\t*\t*\t0\t0\t%s\t%s\n", rec.name.c_str(), rec.seq.empty() ? "*" : rec.seq.c_str(),
                         rec.qual.empty() ? "*" : rec.qual.c_str());
@@ -216,13 +231,21 @@ int main(int argc, char** argv) {
                 for (char& c : seq) c = comp(c);
                 if (qual != "*") qual.assign(rec.qual.rbegin(), rec.qual.rend());
             }
-            char cigar[4096];
-            const int nn = nops[(size_t)slot[q]];
-            if (asm_cigar_format(&ops[(size_t)slot[q] * cap], nn, cap, cigar, sizeof(cigar)) != 0 || nn > cap) strcpy(cigar, "*");
-            const int mapq = hp->greedy_cost + 60 < 254 ? hp->greedy_cost + 60 : 254;
-            fprintf(out, "%s\t%d\t%s\t%u\t%d\t%s\t*\t0\t0\t%s\t%s\tNM:i:%d\tXG:i:%d\n", rec.name.c_str(), hp->strand ? 16 : 0,
-                    names[(size_t)hp->seq_id].c_str(), hp->pos + 1, mapq, cigar, seq.c_str(), qual.empty() ? "*" : qual.c_str(),
-                    (int)hp->dist, hp->greedy_cost);
+            /* rank 0 is the primary record; with --all-hits, ranks 1.. follow as secondary records */
+            const uint32_t nh = all_hits ? n_hits[(size_t)slot[q]] : 1u, nrep = nh < (uint32_t)slots ? nh : (uint32_t)slots;
+            for (uint32_t t = 0; t < nrep; t++) {
+                const size_t o = (size_t)slot[q] * slots + t;
+                const asm_map_hit& hr = hits[o];
+                char cigar[4096];
+                const int nn = nops[o];
+                if (asm_cigar_format(&ops[o * cap], nn, cap, cigar, sizeof(cigar)) != 0 || nn > cap) strcpy(cigar, "*");
+                const int mapq = hr.greedy_cost + 60 < 254 ? hr.greedy_cost + 60 : 254;
+                fprintf(out, "%s\t%d\t%s\t%u\t%d\t%s\t*\t0\t0\t%s\t%s\tNM:i:%d\tXG:i:%d", rec.name.c_str(),
+                        (hr.strand ? 16 : 0) | (t ? 256 : 0), names[(size_t)hr.seq_id].c_str(), hr.pos + 1, mapq, cigar,
+                        t ? "*" : seq.c_str(), t || qual.empty() ? "*" : qual.c_str(), (int)hr.dist, hr.greedy_cost);
+                if (all_hits) fprintf(out, "\tNH:i:%u\tHI:i:%u\tXH:i:%u", nrep, t + 1, nh);
+                fputc('\n', out);
+            }
         }
     }
     fclose(out);

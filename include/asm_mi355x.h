@@ -345,11 +345,26 @@ int asm_profile_read(asm_handle* h, float* ms, int cap_calls, int* n_calls);
  *                  cigar_nops[i] = entries of row i (above cigar_cap: truncated, flag CIGAR_TRUNCATED); both may be NULL
  *                  (cigar_cap 0).  Greedy (k = greedy_k, x = o = e = 1, clean tails) runs on (q_s, T_r[w, min(w + m + 1, len_r)))
  *                  with w = pos ? pos - 1 : 0, as mapper/main.cpp:79-95 calls it; MAPQ = min(254, 60 + greedy_cost).
- *                  Unmapped reads: seq_id -1, pos = end = 0, dist -1, greedy_cost -1, cigar_nops 0.  Synchronous. */
+ *                  Unmapped reads: seq_id -1, pos = end = 0, dist -1, greedy_cost -1, cigar_nops 0.  Synchronous.
+ * asm_map_reads_all: every locus within max_errors, not only the best hit (SeqAn3's hit_all / hit_all_best / hit_strata).  For
+ *                  strand s, sequence r and end j, D(j) = min_i Lev(q_s, T_r[i, j)); a locus is a maximal run of consecutive ends j
+ *                  of one (s, r) with D(j) <= max_errors (never across two sequences).  Its d = min D over the run, its end j =
+ *                  the smallest end of the run reaching d, its pos = the largest i with Lev(q_s, T_r[i, j)) = d; CIGAR, Greedy and
+ *                  MAPQ as for asm_map_reads.  Loci are ranked by (d, s, r, j); with d_best the first one's d, the reported loci are
+ *                  those with d <= min(max_errors, d_best + strata), strata in [0, 15] (0: hit_all_best; >= max_errors: hit_all).
+ *                  n_hits[i] = how many (uncapped); the first min(n_hits[i], max_hits) are written to out[i][0..], max_hits in
+ *                  [1, 256]; cigar_ops = [n][max_hits][cigar_cap], cigar_nops = [n][max_hits].  Rank 0 is, field for field,
+ *                  asm_map_reads' record of the read (an unmapped read: n_hits 0 and the unmapped record at rank 0), plus flag
+ *                  HITS_TRUNCATED.  Ranks >= 1 carry flag SECONDARY; every record of a read with n_hits > max_hits carries
+ *                  HITS_TRUNCATED.  A slot beyond the reported ones: seq_id -1, pos = end = 0, dist -1, greedy_cost -1, flags 0,
+ *                  cigar_nops 0 (its cigar_ops row is not written).  Synchronous. */
 #define ASM_MAP_MAPPED 1
 #define ASM_MAP_TOO_SHORT 2
 #define ASM_MAP_SEED_CAPPED 4
 #define ASM_MAP_CIGAR_TRUNCATED 8
+#define ASM_MAP_SECONDARY 16
+#define ASM_MAP_HITS_TRUNCATED 32
+#define ASM_MAP_MAX_HITS 256
 #define ASM_MAP_MIN_K 8
 #define ASM_MAP_MAX_K 14
 #define ASM_MAP_MAX_READ 511
@@ -373,6 +388,10 @@ typedef struct asm_map_hit {
 } asm_map_hit;
 int asm_map_reads(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
                   const asm_map_params* p, asm_map_hit* out, uint16_t* cigar_ops, int cigar_cap, uint8_t* cigar_nops);
+int asm_map_reads_all(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
+                      const asm_map_params* p, int strata, int max_hits, uint32_t* n_hits /* [n] */,
+                      asm_map_hit* out /* [n][max_hits] */, uint16_t* cigar_ops /* [n][max_hits][cigar_cap] */, int cigar_cap,
+                      uint8_t* cigar_nops /* [n][max_hits] */);
 
 /* ---- plain device memory helpers (so that non-torch hosts can drive the async API) --------------------- */
 int asm_device_malloc(asm_handle* h, size_t bytes, void** d_ptr);

@@ -1,8 +1,11 @@
 """Read-mapper timings (development tool): PYTHONPATH=. python tools/bench_map.py [--ref-len 5e6] [--reads 1e6] [--len 100]
-[--errors 2 4] [--out DIR] [--profile]
+[--errors 2 4] [--all-hits N [--strata S]] [--repeats] [--out DIR] [--profile]
 A random reference (one sequence, seeded) and reads sampled from both strands with 0..e substitutions plus 10 % random reads;
 reports the index build and the mapping of all reads (both strands), each timed with HIP events on the engine's stream around one
 synchronous library call (so host-to-device copies and the host's share of asm_map_reads are inside), plus the wall clock.
+--all-hits N also times asm_map_reads_all (up to N loci per read, strata S, default e), alternating with asm_map_reads in the
+same process, and prints the hits-per-read distribution.  --repeats pastes 200 copies of a 2 kbp element (0-3 % substitutions,
+half reverse-complemented) and 6 kbp of a period-6 tandem repeat into the reference, and draws 30 % of the reads from them.
 --profile re-runs the same command under `rocprofv3 --kernel-trace --stats` (a run of its own) and prints the per-kernel totals."""
 import argparse
 import ctypes
@@ -28,10 +31,25 @@ for a, b in (b"AT", b"TA", b"CG", b"GC"):
     COMP[a] = b
 
 
-def make_inputs(ref_len, n, length, e, seed):
+def make_inputs(ref_len, n, length, e, seed, repeats=False):
     rng = np.random.default_rng(seed)
     ref = LUT[rng.integers(0, 4, ref_len)]
     starts = rng.integers(0, ref_len - length, n)
+    if repeats:  # element copies every 20 kbp from 100 kbp on, the tandem repeat at 4.5 Mbp
+        elem = LUT[rng.integers(0, 4, 2000)]
+        places = 100_000 + 20_000 * np.arange(200)
+        for c, a in enumerate(places):
+            copy = elem.copy()
+            sub = rng.random(2000) < 0.03 * (c % 4) / 3
+            copy[sub] = LUT[(np.searchsorted(LUT, copy[sub]) + rng.integers(1, 4, int(sub.sum()))) % 4]
+            ref[a:a + 2000] = COMP[copy[::-1]] if c % 2 else copy
+        tandem = np.frombuffer(b"AGGTCA" * 1000, np.uint8)
+        ref[4_500_000:4_500_000 + tandem.size] = tandem
+        rep = rng.random(n) < 0.3
+        k = int(rep.sum())
+        from_tandem = rng.random(k) < 0.1
+        starts[rep] = np.where(from_tandem, 4_500_000 + rng.integers(0, tandem.size - length, k),
+                               places[rng.integers(0, 200, k)] + rng.integers(0, 2000 - length, k))
     reads = ref[starts[:, None] + np.arange(length)[None, :]].copy()
     for t in range(e):  # substitutions at random places (some may hit the same base twice: 0..e edits)
         hit = rng.random(n) < 0.7
@@ -52,16 +70,21 @@ def main():
     ap.add_argument("--errors", type=int, nargs="+", default=[2, 4])
     ap.add_argument("--k", type=int, default=12)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--all-hits", type=int, default=0, help="also time asm_map_reads_all with up to N loci per read")
+    ap.add_argument("--strata", type=int, default=None, help="with --all-hits: strata (default e)")
+    ap.add_argument("--repeats", action="store_true", help="the reference with repeats, 30 %% of the reads from them")
     ap.add_argument("--out", default=None, help="directory for the JSON result (and the profile with --profile)")
     ap.add_argument("--profile", action="store_true")
     a = ap.parse_args()
+    extra = (["--all-hits", str(a.all_hits)] if a.all_hits else []) + (["--strata", str(a.strata)] if a.strata is not None else [])
+    extra += ["--repeats"] if a.repeats else []
     n, ref_len = int(a.reads), int(a.ref_len)
     if a.profile:
         out = a.out or "bench_map_profile"
         os.makedirs(out, exist_ok=True)
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", out, "-o", "map", "--output-format", "csv", "--",
                sys.executable, os.path.abspath(__file__), "--ref-len", str(ref_len), "--reads", str(n), "--len", str(a.len),
-               "--k", str(a.k), "--reps", "1", "--errors", *[str(e) for e in a.errors]]
+               "--k", str(a.k), "--reps", "1", "--errors", *[str(e) for e in a.errors], *extra]
         subprocess.run(cmd, check=True, timeout=1200)
         for path in glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True):
             with open(path) as fh:
@@ -73,9 +96,9 @@ def main():
     eng = m.Engine(0)
     lib, h = eng.lib, eng.h
     tm = eng.timer()
-    results = {"ref_len": ref_len, "reads": n, "read_len": a.len, "k": a.k, "runs": []}
+    results = {"ref_len": ref_len, "reads": n, "read_len": a.len, "k": a.k, "repeats": a.repeats, "all_hits": a.all_hits, "runs": []}
     for e in a.errors:
-        ref, reads = make_inputs(ref_len, n, a.len, e, seed=1000 + e)
+        ref, reads = make_inputs(ref_len, n, a.len, e, seed=1000 + e, repeats=a.repeats)
         off = np.array([0, ref_len], np.uint64)
         ix = ctypes.c_void_p()
         best_ix = 1e30
@@ -92,8 +115,14 @@ def main():
         ops = np.zeros((n, 16), np.uint16)
         nops = np.zeros(n, np.uint8)
         p = m.MapParams(e, 1, 0, 3)
-        best_map, best_wall = 1e30, 1e30
-        for _ in range(a.reps):
+        H = max(a.all_hits, 1)
+        strata = e if a.strata is None else a.strata
+        n_hits = np.zeros(n, np.uint32)
+        all_hits = np.zeros(n * H, m.MAP_HIT_DTYPE) if a.all_hits else None
+        all_ops = np.zeros(n * H * 16, np.uint16) if a.all_hits else None
+        all_nops = np.zeros(n * H, np.uint8) if a.all_hits else None
+        best_map, best_wall, best_all = 1e30, 1e30, 1e30
+        for _ in range(a.reps):  # the two calls alternate, so that both see the same machine state
             t0 = time.perf_counter()
             tm.start()
             eng._chk(lib.asm_map_reads(h, ix, n, flat.ctypes.data, ro.ctypes.data, ctypes.byref(p), hits.ctypes.data, ops.ctypes.data,
@@ -101,10 +130,23 @@ def main():
             tm.stop()
             best_map = min(best_map, tm.elapsed_ms())
             best_wall = min(best_wall, (time.perf_counter() - t0) * 1e3)
+            if a.all_hits:
+                tm.start()
+                eng._chk(lib.asm_map_reads_all(h, ix, n, flat.ctypes.data, ro.ctypes.data, ctypes.byref(p), strata, a.all_hits,
+                                               n_hits.ctypes.data, all_hits.ctypes.data, all_ops.ctypes.data, 16, all_nops.ctypes.data))
+                tm.stop()
+                best_all = min(best_all, tm.elapsed_ms())
         lib.asm_index_free(h, ix)
         mapped = float(((hits["flags"] & m.MAP_MAPPED) != 0).mean())
         row = {"e": e, "index_build_ms": round(best_ix, 3), "map_ms_events": round(best_map, 3), "map_ms_wall": round(best_wall, 3),
                "reads_per_s": round(n / best_map * 1e3), "mapped_fraction": round(mapped, 4)}
+        if a.all_hits:
+            rep_n = np.minimum(n_hits, a.all_hits)
+            row.update({"all_hits": a.all_hits, "strata": strata, "all_ms_events": round(best_all, 3),
+                        "all_reads_per_s": round(n / best_all * 1e3), "all_over_best": round(best_all / best_map, 3),
+                        "hits_per_read_mean": round(float(n_hits.mean()), 3), "reported_per_read_mean": round(float(rep_n.mean()), 3),
+                        # distribution of n_hits: 0, 1, 2-3, 4-15, 16-63, >= 64
+                        "n_hits_hist": [int(v) for v in np.histogram(n_hits, [0, 1, 2, 4, 16, 64, 2**32])[0]]})
         results["runs"].append(row)
         print(json.dumps(row))
     if a.out:
