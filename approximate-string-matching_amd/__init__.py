@@ -215,6 +215,8 @@ def load_library() -> ctypes.CDLL:
         "asm_batch_max_length": (i32, [vp]),
         "asm_batch_text_bytes": (i64, [vp]),
         "asm_batch_download": (i32, [vp, vp, vp, vp, vp, c.c_size_t, vp, c.c_size_t]),
+        "asm_batch_planes_size": (i64, [vp]),
+        "asm_batch_download_planes": (i32, [vp, vp, vp, c.c_size_t, vp, vp]),
         "asm_batch_pack_async": (i32, [vp, vp]),
         "asm_align_batch_async": (i32, [vp, vp, i32, c.POINTER(Params), vp]),
         "asm_align_batch_hinted_async": (i32, [vp, vp, i32, c.POINTER(Params), vp, vp]),
@@ -364,6 +366,17 @@ class DeviceBatch:
         self.engine._chk(lib.asm_batch_download(h, self.ptr, None, None, reads.ctypes.data, reads.size,
                                                 refs.ctypes.data, refs.size))
         return HostBatch(reads[:int(ro[-1])], ro, refs[:int(fo[-1])], fo)
+
+    def download_planes(self):
+        """The packed form: (planes uint32[4 * entries, 4], lens uint32[n], order uint32[n]), lens and order in bucketed order
+        (order = bucket slot -> pair index).  Bucket b's planes are a uint4[4][w4][size] block, buckets back to back."""
+        lib, h = self.engine.lib, self.engine.h
+        planes = np.zeros((int(lib.asm_batch_planes_size(self.ptr)), 4), np.uint32)
+        lens = np.zeros(max(self.n, 1), np.uint32)
+        order = np.zeros(max(self.n, 1), np.uint32)
+        self.engine._chk(lib.asm_batch_download_planes(h, self.ptr, planes.ctypes.data, planes.size, lens.ctypes.data,
+                                                       order.ctypes.data))
+        return planes, lens[:self.n], order[:self.n]
 
     def __del__(self):
         try:

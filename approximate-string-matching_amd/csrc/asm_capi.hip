@@ -821,26 +821,20 @@ static hipError_t launch_pack(asm_handle* h, const asm_batch* b, const uint4* ta
     const dim3 grid((unsigned)((b->n + PACK_BLOCK - 1) / PACK_BLOCK)), block(PACK_BLOCK);
     int wmax = 1;
     for (int q = 0; q < pb.nb; q++) wmax = pb.w4[q] > wmax ? pb.w4[q] : wmax;
-    // LDS staging: room for 256 strings of the batch's longest length (+ alignment slack), at least one string
-    size_t stage = (size_t)PACK_BLOCK * (size_t)(b->maxlen + 4) + 64;
-    stage = (stage + 1023) & ~(size_t)1023;
-    if (stage > PACK_SB) stage = PACK_SB;
-    if (stage < 2048) stage = 2048;
-    const size_t lds = stage + 256; /* + the over-read slack of pack_convert and the 64 bytes of padding behind the staged data
-                                       (pack_pad; the swizzle stays inside a 128-byte row) */
-#define PACK_LAUNCH(W, NV)                                                                                               \
-    hipLaunchKernelGGL((pack_kernel<W, NV>), grid, block, lds, h->stream, b->d_reads, b->d_read_off, b->d_refs,          \
-                       b->d_ref_off, tails, planes, lens, (long)b->n, pb, pos, (uint32_t)stage)
-    /* NV = staging vectors a thread may hold in registers: 7 covers 256 strings of up to 108 characters (28 KB), which only a
-     * one-granule batch can be; everything longer takes 12 */
+    // LDS: the plane arrays of both sides of 256 strings of the batch's longest length (+ alignment slack), capped; at least
+    // one string's (the rounds path then makes progress)
+    const auto side_dwords = [](size_t bytes) { return (size_t)2 * (size_t)(((bytes + 15) / 16 + 1) / 2 + 1); };
+    size_t dw = 2 * side_dwords((size_t)PACK_BLOCK * (size_t)b->maxlen + 15);
+    if (dw > PACK_LDS_MAX / 4) dw = PACK_LDS_MAX / 4;
+    if (dw < side_dwords((size_t)b->maxlen + 30)) dw = side_dwords((size_t)b->maxlen + 30);
+#define PACK_LAUNCH(W)                                                                                                   \
+    hipLaunchKernelGGL((pack_kernel<W>), grid, block, dw * 4, h->stream, b->d_reads, b->d_read_off, b->d_refs,           \
+                       b->d_ref_off, tails, planes, lens, (long)b->n, pb, pos, (uint32_t)dw)
     switch (wmax) {
-        case 1:
-            if (stage <= 7 * PACK_BLOCK * 16) PACK_LAUNCH(1, 7);
-            else PACK_LAUNCH(1, 12);
-            break;
-        case 2: PACK_LAUNCH(2, 12); break;
-        case 3: PACK_LAUNCH(3, 12); break;
-        default: PACK_LAUNCH(4, 12); break;
+        case 1: PACK_LAUNCH(1); break;
+        case 2: PACK_LAUNCH(2); break;
+        case 3: PACK_LAUNCH(3); break;
+        default: PACK_LAUNCH(4); break;
     }
 #undef PACK_LAUNCH
     return hipGetLastError();
@@ -1214,6 +1208,27 @@ int asm_batch_download(asm_handle* h, const asm_batch* b, uint32_t* read_off, ui
     if (refs) {
         if (refs_cap < b->refs_bytes) return fail(h, ASM_EINVAL, "asm_batch_download: refs buffer too small");
         HIPCHK(h, hipMemcpy(refs, b->d_refs, b->refs_bytes, hipMemcpyDeviceToHost));
+    }
+    return ASM_OK;
+}
+
+int64_t asm_batch_planes_size(const asm_batch* b) { return b ? (int64_t)b->planes_total : 0; }
+
+int asm_batch_download_planes(asm_handle* h, const asm_batch* b, uint32_t* planes, size_t planes_cap, uint32_t* lens,
+                              uint32_t* order) {
+    if (!h || !b) return fail(h, ASM_EINVAL, "asm_batch_download_planes: NULL argument");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const size_t n = (size_t)b->n;
+    if (planes) {
+        if (planes_cap < 4 * b->planes_total) return fail(h, ASM_EINVAL, "asm_batch_download_planes: planes buffer too small");
+        HIPCHK(h, hipMemcpy(planes, b->d_planes, sizeof(uint4) * b->planes_total, hipMemcpyDeviceToHost));
+    }
+    if (lens && n) HIPCHK(h, hipMemcpy(lens, b->d_lens, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    if (order && n) {
+        if (b->d_order) HIPCHK(h, hipMemcpy(order, b->d_order, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+        else
+            for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
     }
     return ASM_OK;
 }

@@ -27,17 +27,18 @@
 // its in-place byte permutation (whose only observable effect, the stale tails of later pairs, is supplied
 // through `tails` in sequential mode — see asm_tails.h).
 //
-// A workgroup owns 256 consecutive pairs.  Their ASCII is one contiguous byte range of the batch, so it is
-// staged into LDS with fully coalesced 16 B/lane loads (a thread-per-pair gather straight from HBM would touch
-// ~50 cache lines per load instruction); then every thread converts its own string out of LDS, four characters
-// per dword with SWAR byte compares (exactly 'C','G','T' set bits; every other byte is code 00).  The staging
-// buffer is XOR-swizzled per 128-byte row so that strings whose length is a multiple of 128 B do not all hit
-// one LDS bank.  Long batches are staged in rounds of whole pairs that fit the buffer.
+// A workgroup owns 256 consecutive pairs.  Their ASCII is one contiguous byte range of the batch per side, and the
+// conversion is a function of the byte alone, so it is done where the bytes land: thread t loads 16-byte vector v of
+// the range (fully coalesced) and turns it into bits [16v, 16v+16) of two plane arrays in LDS, in buffer-position
+// coordinates (bit q of plane dword j <-> byte 32j+q of the range).  After one barrier thread t cuts pair t's string
+// out of those arrays with one funnel shift per output dword.  LDS holds 2 bits per byte; when the block's planes do
+// not fit (long strings), each side is done in rounds of whole pairs that do.
 // --------------------------------------------------------------------------------------------------------
-#define PACK_SB (48 * 1024)
 #ifndef PACK_BLOCK
-#define PACK_BLOCK 256 /* pairs (threads) per pack workgroup; 128 and 64 measured: C2 59.6 and 60.8 us against 58.7, C5 1.93 and 1.71 ms against 1.28 */
+#define PACK_BLOCK 256 /* pairs (threads) per pack workgroup */
 #endif
+#define PACK_LDS_MAX (33 * 1024) /* plane bytes per workgroup: one side of 256 strings of ASM_MAX_LENGTH (32 784 B) fits */
+#define PACK_UNROLL 8            /* 16-byte vectors a thread keeps in flight */
 
 // Length buckets of a batch (mixed-length batches are grouped by the number of 128-position granules their longer
 // string needs, so that every kernel launch works on pairs of one width class).  Bucket b holds the pairs at slots
@@ -53,53 +54,95 @@ ASM_DEV uint32_t swar_zero_bytes(uint32_t t) { /* bit 7 of each byte set iff tha
     return ~(((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t | 0x7f7f7f7fu);
 }
 
-// One thread converts its string out of the (swizzled) LDS staging buffer and stores its plane granules.
+// dwords of ONE plane array for a range of `nv` vectors: two vectors per dword, plus the dword the funnel shift of a
+// string's last output word reads past the range
+ASM_DEV int pack_plane_dwords(int nv) { return ((nv + 1) >> 1) + 1; }
+
+// 16 characters -> their 16 bits of plane 0 (C|T) and plane 1 (G|T); codes A=00 C=01 G=10 T=11, any other byte 00.
+ASM_DEV void pack_vec(const uint4 q, uint32_t& p0, uint32_t& p1) {
+    const uint32_t d[4] = {q.x, q.y, q.z, q.w};
+    uint32_t f0[4], f1[4], bad = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        // Bits 1-2 of 'A','C','T','G' are 0,1,2,3: as a v_perm_b32 selector into "ACTG" they give the one base each byte
+        // could be.  For a base, plane1 = bit 2 and plane0 = bit 1 ^ bit 2; canon ^ ch is accumulated to catch other bytes.
+        const uint32_t ch = d[k], half = ch >> 1;
+        const uint32_t canon = __builtin_amdgcn_perm(0u, 0x47544341u, half & 0x03030303u);
+        bad |= canon ^ ch;
+        f0[k] = (ch ^ half) & 0x02020202u; /* bit 1 of each byte */
+        f1[k] = ch & 0x04040404u;          /* bit 2 of each byte */
+    }
+    if (bad != 0u) { /* rare: exactly 'C','G','T' set plane bits; every other byte, NUL included, is code 00 */
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t ch = d[k];
+            const uint32_t canon = __builtin_amdgcn_perm(0u, 0x47544341u, (ch >> 1) & 0x03030303u);
+            const uint32_t ok = swar_zero_bytes(canon ^ ch); /* 0x80 in every byte that is a real base */
+            f0[k] &= ok >> 6, f1[k] &= ok >> 5;
+        }
+    }
+    // gather the byte flags into bits with v_dot4_u32_u8 (weights 1,2,4,8 and 16..128 for the odd dword, accumulated
+    // onto the even one); the flags sit at bit 1 resp. 2 of their byte, so the sums come out scaled by 2 resp. 4
+    const uint32_t lo0 = __builtin_amdgcn_udot4(f0[1], 0x80402010u, __builtin_amdgcn_udot4(f0[0], 0x08040201u, 0u, false), false);
+    const uint32_t hi0 = __builtin_amdgcn_udot4(f0[3], 0x80402010u, __builtin_amdgcn_udot4(f0[2], 0x08040201u, 0u, false), false);
+    const uint32_t lo1 = __builtin_amdgcn_udot4(f1[1], 0x80402010u, __builtin_amdgcn_udot4(f1[0], 0x08040201u, 0u, false), false);
+    const uint32_t hi1 = __builtin_amdgcn_udot4(f1[3], 0x80402010u, __builtin_amdgcn_udot4(f1[2], 0x08040201u, 0u, false), false);
+    p0 = (lo0 | (hi0 << 8)) >> 1;
+    p1 = (lo1 | (hi1 << 8)) >> 2;
+}
+
+// Converts vectors [0, nvA + nvB) of the two ranges (A first) into plane arrays: A's plane 0 / plane 1 at u16 offsets
+// 0 / 2*pdA, B's at 4*pdA / 4*pdA + 2*pdB (pd = dwords per plane array).  Loads are issued PACK_UNROLL at a time.
+ASM_DEV void pack_convert_range(uint16_t* sp, const uint4* __restrict__ srcA, int nvA, int pdA, const uint4* __restrict__ srcB,
+                                int nvB, int pdB, int t) {
+    const int tot = nvA + nvB;
+#pragma unroll 1
+    for (int v0 = t; v0 < tot; v0 += PACK_UNROLL * PACK_BLOCK) {
+        uint4 r[PACK_UNROLL];
+#pragma unroll
+        for (int q = 0; q < PACK_UNROLL; q++) {
+            const int v = v0 + q * PACK_BLOCK;
+            if (v < tot) r[q] = v < nvA ? srcA[v] : srcB[v - nvA];
+        }
+#pragma unroll
+        for (int q = 0; q < PACK_UNROLL; q++) {
+            const int v = v0 + q * PACK_BLOCK;
+            if (v < tot) {
+                uint32_t p0, p1;
+                pack_vec(r[q], p0, p1);
+                uint16_t* d0 = v < nvA ? sp + v : sp + 4 * pdA + (v - nvA);
+                const int pd = v < nvA ? pdA : pdB;
+                d0[0] = (uint16_t)p0;
+                d0[2 * pd] = (uint16_t)p1;
+            }
+        }
+    }
+}
+
+// One thread cuts its string (byte offset `off` into the converted range, `len` characters) out of the plane arrays
+// P0 / P1 and stores its granules.
 template <int W4>
-ASM_DEV void pack_convert(const uint32_t* sb, uint32_t b0, int len, int w4, int s, const uint4* __restrict__ tails,
-                          long n, long pair, uint4* __restrict__ bplanes, long bn, long local) {
-    const int a0 = (int)(b0 >> 2);
-    const uint32_t sh = (b0 & 3u) * 8u;
+ASM_DEV void pack_extract(const uint32_t* P0, const uint32_t* P1, uint32_t off, int len, int w4, int s,
+                          const uint4* __restrict__ tails, long n, long pair, uint4* __restrict__ bplanes, long bn, long local) {
+    const int i = (int)(off >> 5);
+    const uint32_t sh = off & 31u;
+    uint32_t c0 = 0u, c1 = 0u; /* plane dwords i + k of the current output word k */
+    if (len > 0) c0 = P0[i], c1 = P1[i];
 #pragma unroll
     for (int g = 0; g < W4; g++) {
         if (g < w4) {
             uint32_t q0[4] = {0u, 0u, 0u, 0u}, q1[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
             for (int w = 0; w < 4; w++) {
-                const int cbase = g * 128 + w * 32;
-                if (cbase < len) {
-                    uint32_t d[9];
-#pragma unroll
-                    for (int q = 0; q < 9; q++) {
-                        const int a = a0 + (cbase >> 2) + q;
-                        d[q] = sb[a ^ (((a >> 5) & 7) << 2)];
-                    }
-                    uint32_t g0 = 0u, g1 = 0u; /* flag bytes of the previous (even) dword, gathered */
-#pragma unroll
-                    for (int q = 0; q < 8; q++) {
-                        const uint32_t ch = __builtin_amdgcn_alignbit(d[q + 1], d[q], sh);
-                        // Four characters at once.  Bits 1-2 of 'A','C','T','G' are 0,1,2,3: use them as a v_perm_b32
-                        // selector into the table "ACTG" to get the one base each byte could be, and accept the byte
-                        // only if it IS that base (exactly 'C','G','T' set plane bits; any other byte, NUL included,
-                        // is code 00 as in bit_convert.cpp:340-355).  plane1 (G|T) = bit 2, plane0 (C|T) = bit 1 ^ bit 2.
-                        const uint32_t half = ch >> 1;
-                        const uint32_t canon = __builtin_amdgcn_perm(0u, 0x47544341u, half & 0x03030303u);
-                        const uint32_t ok = swar_zero_bytes(canon ^ ch) >> 7; /* 0x01 in every byte that is a real base */
-                        const uint32_t f0 = ((ch ^ half) >> 1) & ok, f1 = (ch >> 2) & ok;
-                        /* gather the four byte flags into a nibble with one v_dot4_u32_u8 (weights 1,2,4,8; 16..128 for the odd
-                         * dword, accumulated onto the even one): a byte of the plane word per two dwords */
-                        if ((q & 1) == 0) {
-                            g0 = __builtin_amdgcn_udot4(f0, 0x08040201u, 0u, false);
-                            g1 = __builtin_amdgcn_udot4(f1, 0x08040201u, 0u, false);
-                        } else {
-                            q0[w] |= __builtin_amdgcn_udot4(f0, 0x80402010u, g0, false) << (8 * (q >> 1));
-                            q1[w] |= __builtin_amdgcn_udot4(f1, 0x80402010u, g1, false) << (8 * (q >> 1));
-                        }
-                    }
-                    // characters beyond the string's end (the next pair's bytes in the staging buffer) are dropped here,
-                    // once per 32 positions, instead of being masked out of every dword
-                    const int keep = len - cbase; /* > 0 */
+                const int k = 4 * g + w;
+                if (32 * k < len) {
+                    const uint32_t n0 = P0[i + k + 1], n1 = P1[i + k + 1];
+                    // characters beyond the string's end (the next pair's bytes) are dropped once per 32 positions
+                    const int keep = len - 32 * k; /* > 0 */
                     const uint32_t km = keep >= 32 ? ~0u : ((1u << keep) - 1u);
-                    q0[w] &= km, q1[w] &= km;
+                    q0[w] = __builtin_amdgcn_alignbit(n0, c0, sh) & km;
+                    q1[w] = __builtin_amdgcn_alignbit(n1, c1, sh) & km;
+                    c0 = n0, c1 = n1;
                 }
             }
             uint4 v0 = make_uint4(q0[0], q0[1], q0[2], q0[3]);
@@ -115,86 +158,7 @@ ASM_DEV void pack_convert(const uint32_t* sb, uint32_t b0, int len, int w4, int 
     }
 }
 
-
-// The same conversion for strings that hold nothing but A, C, G, T — what the aligners are fed almost always.  Then bits 1-2 of
-// a character ARE its code (A 00, C 01, T 10, G 11 -> plane0 = bit1 ^ bit2, plane1 = bit2) and the per-byte "is it exactly the
-// base it could be" test of pack_convert (a SWAR zero-byte test and two masks per dword: half of its instructions) shrinks to
-// accumulating canon ^ ch over the string.  Returns that accumulated difference: non-zero = some byte was not a base (or the
-// string's last dwords ran into bytes that are not), and the caller converts the string again with pack_convert, whose stores
-// overwrite these.  The staging buffer is padded with 'A's behind the last string so that running past a string's end into
-// its neighbour — or into the padding — never raises the flag by itself.
 template <int W4>
-ASM_DEV uint32_t pack_convert_acgt(const uint32_t* sb, uint32_t b0, int len, int w4, int s, const uint4* __restrict__ tails,
-                                   long n, long pair, uint4* __restrict__ bplanes, long bn, long local) {
-    const int a0 = (int)(b0 >> 2);
-    const uint32_t sh = (b0 & 3u) * 8u;
-    uint32_t bad = 0u;
-#pragma unroll
-    for (int g = 0; g < W4; g++) {
-        if (g < w4) {
-            uint32_t q0[4] = {0u, 0u, 0u, 0u}, q1[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int w = 0; w < 4; w++) {
-                const int cbase = g * 128 + w * 32;
-                if (cbase < len) {
-                    uint32_t d[9];
-#pragma unroll
-                    for (int q = 0; q < 9; q++) {
-                        const int a = a0 + (cbase >> 2) + q;
-                        d[q] = sb[a ^ (((a >> 5) & 7) << 2)];
-                    }
-                    uint32_t g0 = 0u, g1 = 0u;
-#pragma unroll
-                    for (int q = 0; q < 8; q++) {
-                        const uint32_t ch = __builtin_amdgcn_alignbit(d[q + 1], d[q], sh);
-                        const uint32_t half = ch >> 1, quarter = ch >> 2;
-                        const uint32_t canon = __builtin_amdgcn_perm(0u, 0x47544341u, half & 0x03030303u);
-                        bad |= canon ^ ch;
-                        const uint32_t f0 = (half ^ quarter) & 0x01010101u, f1 = quarter & 0x01010101u;
-                        if ((q & 1) == 0) {
-                            g0 = __builtin_amdgcn_udot4(f0, 0x08040201u, 0u, false);
-                            g1 = __builtin_amdgcn_udot4(f1, 0x08040201u, 0u, false);
-                        } else {
-                            q0[w] |= __builtin_amdgcn_udot4(f0, 0x80402010u, g0, false) << (8 * (q >> 1));
-                            q1[w] |= __builtin_amdgcn_udot4(f1, 0x80402010u, g1, false) << (8 * (q >> 1));
-                        }
-                    }
-                    const int keep = len - cbase; /* > 0 */
-                    const uint32_t km = keep >= 32 ? ~0u : ((1u << keep) - 1u);
-                    q0[w] &= km, q1[w] &= km;
-                }
-            }
-            uint4 v0 = make_uint4(q0[0], q0[1], q0[2], q0[3]);
-            uint4 v1 = make_uint4(q1[0], q1[1], q1[2], q1[3]);
-            if (tails != nullptr && g == 0) {
-                const uint4 t0 = tails[(long)(2 * s) * n + pair], t1 = tails[(long)(2 * s + 1) * n + pair];
-                v0.x |= t0.x, v0.y |= t0.y, v0.z |= t0.z, v0.w |= t0.w;
-                v1.x |= t1.x, v1.y |= t1.y, v1.z |= t1.z, v1.w |= t1.w;
-            }
-            bplanes[((long)(2 * s) * w4 + g) * bn + local] = v0;
-            bplanes[((long)(2 * s + 1) * w4 + g) * bn + local] = v1;
-        }
-    }
-    return bad;
-}
-
-// 64 bytes of 'A' behind the staged vectors (`vecs` 16-byte vectors were staged; swizzled like everything else).  Written by
-// the threads that do not store the last vectors' neighbours: no overlap with the staging stores, same barrier.
-ASM_DEV void pack_pad(uint4* s_buf, int vecs, int t) {
-    if (t < 4) {
-        const int a = 4 * (vecs + t);
-        s_buf[(a ^ (((a >> 5) & 7) << 2)) >> 2] = make_uint4(0x41414141u, 0x41414141u, 0x41414141u, 0x41414141u);
-    }
-}
-
-template <int W4>
-ASM_DEV void pack_convert_any(const uint32_t* sb, uint32_t b0, int len, int w4, int s, const uint4* __restrict__ tails, long n,
-                              long pair, uint4* __restrict__ bplanes, long bn, long local) {
-    if (pack_convert_acgt<W4>(sb, b0, len, w4, s, tails, n, pair, bplanes, bn, local) != 0u)
-        pack_convert<W4>(sb, b0, len, w4, s, tails, n, pair, bplanes, bn, local);
-}
-
-template <int W4, int NV> /* NV = staging vectors (16 B) per thread the fast path may hold in registers */
 __global__ __launch_bounds__(PACK_BLOCK) void pack_kernel(const char* __restrict__ reads,
                                                          const uint32_t* __restrict__ read_off,
                                                          const char* __restrict__ refs,
@@ -203,15 +167,14 @@ __global__ __launch_bounds__(PACK_BLOCK) void pack_kernel(const char* __restrict
                                                          uint4* __restrict__ planes, uint32_t* __restrict__ lens,
                                                          long n, PackBuckets pb,
                                                          const uint32_t* __restrict__ pos /* pair -> slot, or null */,
-                                                         uint32_t stage_bytes /* dynamic LDS staging size, <= PACK_SB */) {
-    // staging buffer sized by the host from the batch's longest string: short reads leave room for more resident
-    // workgroups per CU (5 at 100 bp instead of 3), which is what hides the HBM latency of the staging loads
-    extern __shared__ uint4 s_buf[];
+                                                         uint32_t lds_dwords /* dynamic LDS (plane arrays), in dwords */) {
+    // plane arrays sized by the host from the batch's longest string: short reads leave room for more resident workgroups
+    extern __shared__ uint32_t s_pl[];
     __shared__ uint32_t s_off[2][PACK_BLOCK + 1];
     const int t = threadIdx.x;
     const long p0 = (long)blockIdx.x * PACK_BLOCK;
     const int np = (n - p0) < PACK_BLOCK ? (int)(n - p0) : PACK_BLOCK;
-    const uint32_t* sb = reinterpret_cast<const uint32_t*>(s_buf);
+    uint16_t* const sp = reinterpret_cast<uint16_t*>(s_pl);
     // where this thread's pair lives in the bucketed layout
     const long slot = (t < np) ? (pos ? (long)pos[p0 + t] : p0 + t) : 0;
     int bk = 0;
@@ -229,43 +192,23 @@ __global__ __launch_bounds__(PACK_BLOCK) void pack_kernel(const char* __restrict
     __syncthreads();
     const uint32_t oA0 = s_off[0][t], oA1 = s_off[0][t + 1], oB0 = s_off[1][t], oB1 = s_off[1][t + 1];
     const uint32_t baseA = s_off[0][0] & ~15u, baseB = s_off[1][0] & ~15u;
-    const uint32_t bytesA = s_off[0][PACK_BLOCK] - baseA, bytesB = s_off[1][PACK_BLOCK] - baseB;
+    const int nvA = (int)((s_off[0][PACK_BLOCK] - baseA + 15u) >> 4), nvB = (int)((s_off[1][PACK_BLOCK] - baseB + 15u) >> 4);
+    const int pdA = pack_plane_dwords(nvA), pdB = pack_plane_dwords(nvB);
     if (t < np) lens[slot] = (oA1 - oA0) | ((oB1 - oB0) << 16);
 
-    if (bytesA <= stage_bytes && bytesB <= stage_bytes && bytesB <= (uint32_t)(NV * PACK_BLOCK * 16)) {
-        // Fast path (every string of the block fits the buffer): the refs' bytes are fetched into registers while the
-        // reads are being converted, so their HBM latency hides behind the SWAR work.
-        const int nvA = (int)((bytesA + 15u) >> 4), nvB = (int)((bytesB + 15u) >> 4);
-        const uint4* srcA = reinterpret_cast<const uint4*>(reads + baseA);
-        const uint4* srcB = reinterpret_cast<const uint4*>(refs + baseB);
-        for (int v = t; v < nvA; v += PACK_BLOCK) {
-            const int a = 4 * v;
-            s_buf[(a ^ (((a >> 5) & 7) << 2)) >> 2] = srcA[v];
-        }
-        pack_pad(s_buf, nvA, t);
-        uint4 rb[NV];
-#pragma unroll
-        for (int q = 0; q < NV; q++) {
-            const int v = t + q * PACK_BLOCK;
-            rb[q] = v < nvB ? srcB[v] : make_uint4(0u, 0u, 0u, 0u);
-        }
+    if (2 * (pdA + pdB) <= (int)lds_dwords) {
+        // Fast path: both sides of the whole block in one pass, one barrier
+        pack_convert_range(sp, reinterpret_cast<const uint4*>(reads + baseA), nvA, pdA,
+                           reinterpret_cast<const uint4*>(refs + baseB), nvB, pdB, t);
         __syncthreads();
-        if (t < np) pack_convert_any<W4>(sb, oA0 - baseA, (int)(oA1 - oA0), w4, 0, tails, n, p0 + t, bplanes, bn, local);
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < NV; q++) {
-            const int v = t + q * PACK_BLOCK;
-            if (v < nvB) {
-                const int a = 4 * v;
-                s_buf[(a ^ (((a >> 5) & 7) << 2)) >> 2] = rb[q];
-            }
+        if (t < np) {
+            pack_extract<W4>(s_pl, s_pl + pdA, oA0 - baseA, (int)(oA1 - oA0), w4, 0, tails, n, p0 + t, bplanes, bn, local);
+            pack_extract<W4>(s_pl + 2 * pdA, s_pl + 2 * pdA + pdB, oB0 - baseB, (int)(oB1 - oB0), w4, 1, tails, n, p0 + t,
+                             bplanes, bn, local);
         }
-        pack_pad(s_buf, nvB, t);
-        __syncthreads();
-        if (t < np) pack_convert_any<W4>(sb, oB0 - baseB, (int)(oB1 - oB0), w4, 1, tails, n, p0 + t, bplanes, bn, local);
         return;
     }
-    // General path: stage whole pairs in rounds that fit the buffer.
+    // Rounds: one side at a time, whole pairs whose planes fit.  The host sizes the LDS for at least one string.
 #pragma unroll 1
     for (int s = 0; s < 2; s++) {
         const char* str = s ? refs : reads;
@@ -275,18 +218,13 @@ __global__ __launch_bounds__(PACK_BLOCK) void pack_kernel(const char* __restrict
         while (ps < np) { /* uniform across the workgroup */
             __syncthreads();
             const uint32_t base = s_off[s][ps] & ~15u;
-            const int fits = (t >= ps && t < np && (o1 - base) <= stage_bytes) ? 1 : 0;
+            const int fits = (t >= ps && t < np && 2 * pack_plane_dwords((int)((o1 - base + 15u) >> 4)) <= (int)lds_dwords) ? 1 : 0;
             const int pe = ps + __syncthreads_count(fits); /* offsets are monotone: the fitting pairs are [ps, pe) */
-            const uint32_t hi = s_off[s][pe];
-            const int nvec = (int)((hi - base + 15u) >> 4);
+            const int nv = (int)((s_off[s][pe] - base + 15u) >> 4), pd = pack_plane_dwords(nv);
             const uint4* src = reinterpret_cast<const uint4*>(str + base);
-            for (int v = t; v < nvec; v += PACK_BLOCK) {
-                const int a = 4 * v;
-                s_buf[(a ^ (((a >> 5) & 7) << 2)) >> 2] = src[v];
-            }
-            pack_pad(s_buf, nvec, t);
+            pack_convert_range(sp, src, nv, pd, src, 0, pd, t); /* B empty (a null B pointer crashes ROCm 7.2's inliner) */
             __syncthreads();
-            if (t >= ps && t < pe) pack_convert_any<W4>(sb, o0 - base, len, w4, s, tails, n, p0 + t, bplanes, bn, local);
+            if (t >= ps && t < pe) pack_extract<W4>(s_pl, s_pl + pd, o0 - base, len, w4, s, tails, n, p0 + t, bplanes, bn, local);
             ps = pe;
         }
     }

@@ -163,6 +163,13 @@ int64_t asm_batch_text_bytes(const asm_batch* b);
 /* Copies the batch's ASCII form back to the host (buffers sized by the caller from the offsets). */
 int asm_batch_download(asm_handle* h, const asm_batch* b, uint32_t* read_off, uint32_t* ref_off,
                        char* reads, size_t reads_cap, char* refs, size_t refs_cap);
+/* uint4 entries of the batch's packed planes: all buckets back to back, bucket b a uint4[4][w4][size] block */
+int64_t asm_batch_planes_size(const asm_batch* b);
+/* Copies the packed form back to the host (synchronizes the handle's stream): planes = 4 * asm_batch_planes_size() uint32
+   (planes_cap, in uint32), lens = n words in bucketed order, order = n pair indices in bucketed order (the identity when the
+   batch is one bucket).  Any pointer may be NULL. */
+int asm_batch_download_planes(asm_handle* h, const asm_batch* b, uint32_t* planes, size_t planes_cap, uint32_t* lens,
+                              uint32_t* order);
 /* Re-runs only the pack kernel on the batch's resident ASCII (enqueue only). */
 int asm_batch_pack_async(asm_handle* h, asm_batch* b);
 
