@@ -99,11 +99,18 @@ class MapParams(ctypes.Structure):
                 ("greedy_k", ctypes.c_int32)]
 
 
+class PairParams(ctypes.Structure):
+    """asm_pair_params: projected span in [min_insert, max_insert] (0 <= min <= max <= 8192), mate rescue's error bound (-1 = off)."""
+
+    _fields_ = [("min_insert", ctypes.c_int32), ("max_insert", ctypes.c_int32), ("rescue_errors", ctypes.c_int32)]
+
+
 # asm_map_hit, one per read
 MAP_HIT_DTYPE = np.dtype([("seq_id", np.int32), ("pos", np.uint32), ("end", np.uint32), ("dist", np.int16), ("strand", np.uint8),
                           ("flags", np.uint8), ("greedy_cost", np.int32)])
 MAP_MAPPED, MAP_TOO_SHORT, MAP_SEED_CAPPED, MAP_CIGAR_TRUNCATED = 1, 2, 4, 8
 MAP_SECONDARY, MAP_HITS_TRUNCATED, MAP_MAX_HITS = 16, 32, 256
+MAP_PROPER_PAIR, MAP_RESCUED, MAP_MAX_INSERT = 64, 128, 8192
 MAP_MIN_K, MAP_MAX_K, MAP_MAX_READ, MAP_MAX_ERRORS = 8, 14, 511, 15
 
 
@@ -240,6 +247,7 @@ def load_library() -> ctypes.CDLL:
         "asm_index_free": (i32, [vp, vp]),
         "asm_map_reads": (i32, [vp, vp, i64, vp, vp, c.POINTER(MapParams), vp, vp, i32, vp]),
         "asm_map_reads_all": (i32, [vp, vp, i64, vp, vp, c.POINTER(MapParams), i32, i32, vp, vp, vp, i32, vp]),
+        "asm_map_pairs": (i32, [vp, vp, i64, vp, vp, vp, vp, c.POINTER(MapParams), c.POINTER(PairParams), vp, vp, vp, vp, i32, vp]),
         "asm_device_malloc": (i32, [vp, c.c_size_t, c.POINTER(vp)]),
         "asm_device_free": (i32, [vp, vp]),
         "asm_memcpy_d2h": (i32, [vp, vp, vp, c.c_size_t]),
@@ -602,6 +610,53 @@ class Engine:
         out.update({name: flat[name].copy() for name in MAP_HIT_DTYPE.names})
         out["mapq"] = np.minimum(254, 60 + flat["greedy_cost"].astype(np.int64)).astype(np.int32)
         out["cigar"] = decode_cigars(ops[read, rank], nops[read, rank], cigar_cap) if cigar_cap else [""] * read.size
+        return out
+
+    def map_pairs(self, index: Index, reads1, reads2, max_errors: int, min_insert: int, max_insert: int, rescue_errors: int = -1,
+                  max_occ: int = 0, greedy_k: int = 3, cigar_cap: int = 64, chunk: Optional[int] = None):
+        """asm_map_pairs: paired-end reads, FR orientation (docs/design/mapper.md, "Paired-end reads"); reads1[i] and reads2[i]
+        are the two mates of pair i, both strands are searched.  -> dict of (n, 2) arrays, column 0 mate 1 and column 1 mate 2:
+        seq_id, pos, end, dist, strand, flags, greedy_cost, mapq (min(254, 60 + greedy_cost), 255 when unmapped), mapped and
+        rescued (bool), `cigar` (n lists of 2 CIGAR strings); per pair: proper (bool), tlen and n_concordant.  chunk: pairs per
+        library call (None: all in one)."""
+        p1 = [_as_bytes(r) for r in reads1]
+        p2 = [_as_bytes(r) for r in reads2]
+        if len(p1) != len(p2):
+            raise ValueError("reads1 and reads2 must hold the same number of mates")
+        n = len(p1)
+        p = MapParams(int(max_errors), 1, int(max_occ), int(greedy_k))
+        pp = PairParams(int(min_insert), int(max_insert), int(rescue_errors))
+        cap1 = max(cigar_cap, 1)
+        hits = np.zeros((n, 2), MAP_HIT_DTYPE)
+        tlen = np.zeros(n, np.int32)
+        n_conc = np.zeros(n, np.uint32)
+        ops = np.zeros((n, 2, cap1), np.uint16)
+        nops = np.zeros((n, 2), np.uint8)
+        step = chunk if chunk else max(n, 1)
+        for lo in range(0, n, step):
+            hi = min(n, lo + step)
+            b1, o1 = pack_sequences(p1[lo:hi])
+            b2, o2 = pack_sequences(p2[lo:hi])
+            ro1, ro2 = o1.astype(np.uint32), o2.astype(np.uint32)
+            sub = np.zeros((hi - lo, 2), MAP_HIT_DTYPE)
+            stl = np.zeros(hi - lo, np.int32)
+            snc = np.zeros(hi - lo, np.uint32)
+            sops = np.zeros((hi - lo, 2, cap1), np.uint16)
+            snops = np.zeros((hi - lo, 2), np.uint8)
+            self._chk(self.lib.asm_map_pairs(self.h, index.ptr, hi - lo, b1.ctypes.data if b1.size else None, ro1.ctypes.data,
+                                             b2.ctypes.data if b2.size else None, ro2.ctypes.data, ctypes.byref(p), ctypes.byref(pp),
+                                             sub.ctypes.data, stl.ctypes.data, snc.ctypes.data, sops.ctypes.data if cigar_cap else None,
+                                             int(cigar_cap), snops.ctypes.data if cigar_cap else None))
+            hits[lo:hi], tlen[lo:hi], n_conc[lo:hi], ops[lo:hi], nops[lo:hi] = sub, stl, snc, sops, snops
+        out = {name: hits[name].copy() for name in MAP_HIT_DTYPE.names}
+        out["mapped"] = (hits["flags"] & MAP_MAPPED) != 0
+        out["rescued"] = (hits["flags"] & MAP_RESCUED) != 0
+        out["mapq"] = np.where(out["mapped"], np.minimum(254, 60 + hits["greedy_cost"].astype(np.int64)), 255).astype(np.int32)
+        out["proper"] = (hits["flags"][:, 0] & MAP_PROPER_PAIR) != 0
+        out["tlen"], out["n_concordant"] = tlen, n_conc
+        flat = decode_cigars(ops.reshape(2 * n, cap1), nops.reshape(2 * n), cigar_cap) if cigar_cap and n else [""] * (2 * n)
+        out["cigar"] = [[flat[2 * t], flat[2 * t + 1]] for t in range(n)]
+        out["cigar_nops"] = nops
         return out
 
     # ---- Greedy's sequential mode across batches (shards of one file / chunks of a stream) ----

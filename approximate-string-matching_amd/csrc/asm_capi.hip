@@ -2513,6 +2513,25 @@ static hipError_t map_dispatch(asm_handle* h, int maxm, bool finish, const MapCa
     return map_launch_verify_finish<8>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa, rb);
 }
 
+/* asm_map_pairs' rescue pass: one thread per (anchor, tile of ends); grid-stride over the anchor count the pair kernel left on the
+ * device (at most 2 np anchors) */
+template <int W>
+static hipError_t map_launch_rescue(asm_handle* h, const MapPairArgs& pa, const char* d_reads, const asm_index* ix, uint32_t ntile,
+                                    unsigned long long* rslot) {
+    hipLaunchKernelGGL(map_rescue_kernel<W>, dim3(map_grid((uint64_t)(2 * pa.np) * ntile, h)), dim3(256), 0, h->stream, pa, d_reads,
+                       (const char*)ix->d_text, ntile, rslot);
+    return hipGetLastError();
+}
+
+static hipError_t map_dispatch_rescue(asm_handle* h, int maxm, const MapPairArgs& pa, const char* d_reads, const asm_index* ix,
+                                      uint32_t ntile, unsigned long long* rslot) {
+    const int words = (maxm + 63) / 64;
+    if (words <= 1) return map_launch_rescue<1>(h, pa, d_reads, ix, ntile, rslot);
+    if (words <= 2) return map_launch_rescue<2>(h, pa, d_reads, ix, ntile, rslot);
+    if (words <= 4) return map_launch_rescue<4>(h, pa, d_reads, ix, ntile, rslot);
+    return map_launch_rescue<8>(h, pa, d_reads, ix, ntile, rslot);
+}
+
 extern "C" {
 
 /* The front of a chunk, shared by both mapping calls: reads uploaded and upper-cased, per-read flags cleared, every work item's
@@ -2531,11 +2550,23 @@ struct MapFront {
     explicit MapFront(asm_handle* h) : d_reads(h), d_roff(h), d_flags(h), d_cnt(h), d_base(h), tmp(h) {}
 };
 
-static int map_front(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
-                     const asm_map_params* p, MapFront& f) {
+/* the chunk's reads: one or more runs of reads (asm_map_pairs: the mates 1, then the mates 2), numbered in that order */
+struct MapReadsIn {
+    const char* reads;
+    const uint32_t* read_off; /* n + 1 */
+    int64_t n;
+};
+
+static int map_front(asm_handle* h, const asm_index* ix, const MapReadsIn* in, int n_in, const asm_map_params* p, MapFront& f) {
     const int S = p->both_strands ? 2 : 1, P = p->max_errors + 1;
-    f.roff.resize((size_t)n + 1);
-    for (int64_t i = 0; i <= n; i++) f.roff[(size_t)i] = read_off[i] - read_off[0];
+    int64_t n = 0;
+    for (int t = 0; t < n_in; t++) n += in[t].n;
+    f.roff.assign(1, 0u);
+    f.roff.reserve((size_t)n + 1);
+    for (int t = 0; t < n_in; t++) {
+        const uint32_t o = f.roff.back(), *ro = in[t].read_off;
+        for (int64_t i = 1; i <= in[t].n; i++) f.roff.push_back(o + (ro[i] - ro[0]));
+    }
     for (int64_t i = 0; i < n; i++) f.maxm = std::max(f.maxm, (int)(f.roff[(size_t)i + 1] - f.roff[(size_t)i]));
     const size_t bytes = f.bytes = f.roff[(size_t)n];
     const int64_t nw = f.nw = n * S * P;
@@ -2544,7 +2575,9 @@ static int map_front(asm_handle* h, const asm_index* ix, int64_t n, const char* 
     HIPCHK(h, f.d_flags.alloc(sizeof(uint32_t) * (size_t)n));
     HIPCHK(h, f.d_cnt.alloc(sizeof(unsigned long long) * (size_t)nw));
     HIPCHK(h, f.d_base.alloc(sizeof(unsigned long long) * (size_t)nw));
-    HIPCHK(h, hipMemcpyAsync(f.d_reads.p, reads + read_off[0], bytes, hipMemcpyHostToDevice, h->stream));
+    for (int64_t t = 0, o = 0; t < n_in; o += in[t].read_off[in[t].n] - in[t].read_off[0], t++)
+        HIPCHK(h, hipMemcpyAsync(f.d_reads.p + o, in[t].reads + in[t].read_off[0], in[t].read_off[in[t].n] - in[t].read_off[0],
+                                 hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(f.d_roff.p, f.roff.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(f.d_flags.p, 0, sizeof(uint32_t) * (size_t)n, h->stream));
     hipLaunchKernelGGL(map_upper_kernel, dim3(map_grid(bytes, h)), dim3(256), 0, h->stream, f.d_reads.p, (unsigned long long)bytes);
@@ -2581,7 +2614,8 @@ static int map_chunk(asm_handle* h, const asm_index* ix, int64_t n, const char* 
     Scratch<int32_t> d_cost(h);
     HIPCHK(h, d_keys.alloc(sizeof(unsigned long long) * (size_t)n));
     HIPCHK(h, hipMemsetAsync(d_keys.p, 0xff, sizeof(unsigned long long) * (size_t)n, h->stream));
-    if (const int rc = map_front(h, ix, n, reads, read_off, p, f)) return rc;
+    const MapReadsIn in = {reads, read_off, n};
+    if (const int rc = map_front(h, ix, &in, 1, p, f)) return rc;
     const std::vector<uint32_t>& roff = f.roff;
     const int maxm = f.maxm, P = p->max_errors + 1;
     const size_t bytes = f.bytes;
@@ -2638,17 +2672,21 @@ static int map_chunk(asm_handle* h, const asm_index* ix, int64_t n, const char* 
     return ASM_OK;
 }
 
-/* asm_map_reads_all on one chunk (n < 2^31 reads, so that read << 33 fits the 64-bit run key): every window's intervals into the
- * run buffer, a radix sort, the loci selected per read into an item list, then finish and Greedy once per item */
-static int map_chunk_all(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
-                         const asm_map_params* p, int strata, int max_hits, uint32_t* n_hits, asm_map_hit* out, uint16_t* cigar_ops,
-                         int cigar_cap, uint8_t* cigar_nops) {
-    MapFront f(h);
-    if (const int rc = map_front(h, ix, n, reads, read_off, p, f)) return rc;
+/* The run records of one chunk (asm_map_reads_all, asm_map_pairs), sorted by (read, s, lo): the seeding rounds of map_chunk with
+ * map_verify_all_kernel<W>, then a radix sort.  n < 2^31 reads, so that read << 33 fits the 64-bit run key. */
+struct MapRuns {
+    unsigned long long nr = 0;
+    Scratch<unsigned long long> key;
+    Scratch<uint32_t> val;
+    explicit MapRuns(asm_handle* h) : key(h), val(h) {}
+};
+
+static int map_runs(asm_handle* h, const asm_index* ix, int64_t n, const asm_map_params* p, MapFront& f, MapRuns& out,
+                    const char* who) {
     const int e = p->max_errors;
     Scratch<MapCand> d_cand(h);
-    Scratch<unsigned long long> d_counter(h), d_rkey(h), d_rkey2(h);
-    Scratch<uint32_t> d_rval(h), d_rval2(h);
+    Scratch<unsigned long long> d_counter(h), d_rkey(h);
+    Scratch<uint32_t> d_rval(h);
     Scratch<void> tmp(h);
     unsigned long long rcap = 0, nr = 0;
     HIPCHK(h, d_counter.alloc(sizeof(unsigned long long)));
@@ -2696,28 +2734,45 @@ static int map_chunk_all(asm_handle* h, const asm_index* ix, int64_t n, const ch
             HIPCHK(h, hipStreamSynchronize(h->stream)); /* nr is read by the copy above before it may change */
         }
     }
-    if (nr > (unsigned long long)INT32_MAX) return fail(h, ASM_EUNSUPPORTED, "asm_map_reads_all: more than 2^31 - 1 run records in a chunk");
+    if (nr > (unsigned long long)INT32_MAX)
+        return fail(h, ASM_EUNSUPPORTED, std::string(who) + ": more than 2^31 - 1 run records in a chunk");
     /* sort by (read, s, lo): only the bits in use (read < n) */
     int rbits = 0;
     while (rbits < 31 && (1ull << rbits) < (unsigned long long)n) rbits++;
     const int end_bit = MAP_RUN_READ_SHIFT + rbits;
-    HIPCHK(h, d_rkey2.alloc(sizeof(unsigned long long) * (nr + 1)));
-    HIPCHK(h, d_rval2.alloc(sizeof(uint32_t) * (nr + 1)));
+    HIPCHK(h, out.key.alloc(sizeof(unsigned long long) * (nr + 1)));
+    HIPCHK(h, out.val.alloc(sizeof(uint32_t) * (nr + 1)));
     if (nr) {
         size_t tmp_bytes = 0;
-        HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_rkey.p, d_rkey2.p, d_rval.p, d_rval2.p, (int)nr, 0, end_bit,
+        HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_rkey.p, out.key.p, d_rval.p, out.val.p, (int)nr, 0, end_bit,
                                                      h->stream));
         HIPCHK(h, tmp.alloc(tmp_bytes + 16));
-        HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, d_rkey.p, d_rkey2.p, d_rval.p, d_rval2.p, (int)nr, 0, end_bit,
+        HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, d_rkey.p, out.key.p, d_rval.p, out.val.p, (int)nr, 0, end_bit,
                                                      h->stream));
     }
+    out.nr = nr;
+    return ASM_OK;
+}
+
+/* asm_map_reads_all on one chunk: the sorted run records, the loci selected per read into an item list, then finish and Greedy
+ * once per item */
+static int map_chunk_all(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
+                         const asm_map_params* p, int strata, int max_hits, uint32_t* n_hits, asm_map_hit* out, uint16_t* cigar_ops,
+                         int cigar_cap, uint8_t* cigar_nops) {
+    MapFront f(h);
+    const MapReadsIn in = {reads, read_off, n};
+    if (const int rc = map_front(h, ix, &in, 1, p, f)) return rc;
+    const int e = p->max_errors;
+    MapRuns runs(h);
+    if (const int rc = map_runs(h, ix, n, p, f, runs, "asm_map_reads_all")) return rc;
+    const unsigned long long nr = runs.nr;
     /* loci per read: count, then (host) the item layout, then emit */
     Scratch<uint32_t> d_nh(h), d_dbest(h), d_ibase(h), d_iread(h), d_list(h);
     Scratch<unsigned long long> d_dbase(h), d_ikey(h), d_idirs(h);
     HIPCHK(h, d_nh.alloc(sizeof(uint32_t) * (size_t)n));
     HIPCHK(h, d_dbest.alloc(sizeof(uint32_t) * (size_t)n));
     MapSelectArgs sel = {};
-    sel.rkey = d_rkey2.p, sel.rval = d_rval2.p, sel.nr = nr, sel.n = (long)n, sel.e = e, sel.strata = strata, sel.max_hits = max_hits;
+    sel.rkey = runs.key.p, sel.rval = runs.val.p, sel.nr = nr, sel.n = (long)n, sel.e = e, sel.strata = strata, sel.max_hits = max_hits;
     sel.seq_off = (const unsigned long long*)ix->d_seq_off, sel.n_seqs = (uint32_t)ix->n_seqs, sel.roff = f.d_roff.p;
     sel.n_hits = d_nh.p, sel.d_best = d_dbest.p;
     hipLaunchKernelGGL(map_select_count_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel);
@@ -2840,6 +2895,180 @@ int asm_map_reads_all(asm_handle* h, const asm_index* ix, int64_t n, const char*
         const size_t o = (size_t)c0 * max_hits;
         const int rc = map_chunk_all(h, ix, c1 - c0, reads, read_off + c0, p, strata, max_hits, n_hits + c0, out + o,
                                      cigar_cap > 0 ? cigar_ops + o * cigar_cap : nullptr, cigar_cap, cigar_cap > 0 ? cigar_nops + o : nullptr);
+        if (rc) return rc;
+    }
+    return ASM_OK;
+}
+
+/* asm_map_pairs on one chunk of np pairs (mate 1 of pair p = read p, mate 2 = read np + p): the sorted run records, each read's loci
+ * listed (count, scan, emit), the pairing, the rescue of pairs without a concordant pair, then finish and Greedy on the identity
+ * list (one item per read) */
+static int map_chunk_pairs(asm_handle* h, const asm_index* ix, int64_t np, const char* reads1, const uint32_t* off1,
+                           const char* reads2, const uint32_t* off2, const asm_map_params* p, const asm_pair_params* pp,
+                           asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant, uint16_t* cigar_ops, int cigar_cap,
+                           uint8_t* cigar_nops) {
+    const int64_t n = 2 * np;
+    MapFront f(h);
+    const MapReadsIn in[2] = {{reads1, off1, np}, {reads2, off2, np}};
+    if (const int rc = map_front(h, ix, in, 2, p, f)) return rc;
+    const int e = p->max_errors;
+    MapRuns runs(h);
+    if (const int rc = map_runs(h, ix, n, p, f, runs, "asm_map_pairs")) return rc;
+    /* each read's loci (strata = e: all of them), listed in walk order */
+    Scratch<uint32_t> d_nh(h), d_dbest(h), d_lbase(h), d_lsplit(h), d_nconc(h), d_anchors(h), d_nanch(h), d_list(h);
+    Scratch<unsigned long long> d_lkey(h), d_lbest(h), d_ikey(h), d_rslot(h);
+    Scratch<uint8_t> d_state(h);
+    Scratch<void> tmp(h);
+    HIPCHK(h, d_nh.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
+    HIPCHK(h, d_dbest.alloc(sizeof(uint32_t) * (size_t)n));
+    HIPCHK(h, d_lbase.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
+    MapSelectArgs sel = {};
+    sel.rkey = runs.key.p, sel.rval = runs.val.p, sel.nr = runs.nr, sel.n = (long)n, sel.e = e, sel.strata = e, sel.max_hits = 1;
+    sel.seq_off = (const unsigned long long*)ix->d_seq_off, sel.n_seqs = (uint32_t)ix->n_seqs, sel.roff = f.d_roff.p;
+    sel.n_hits = d_nh.p, sel.d_best = d_dbest.p;
+    HIPCHK(h, hipMemsetAsync(d_nh.p + n, 0, sizeof(uint32_t), h->stream));
+    hipLaunchKernelGGL(map_select_count_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel);
+    HIPCHK(h, hipGetLastError());
+    size_t tmp_bytes = 0;
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_nh.p, d_lbase.p, (int)(n + 1), h->stream));
+    HIPCHK(h, tmp.alloc(tmp_bytes + 16));
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, d_nh.p, d_lbase.p, (int)(n + 1), h->stream));
+    uint32_t nloci = 0;
+    HIPCHK(h, hipMemcpyAsync(&nloci, d_lbase.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, d_lkey.alloc(sizeof(unsigned long long) * ((size_t)nloci + 1)));
+    HIPCHK(h, d_lsplit.alloc(sizeof(uint32_t) * (size_t)n));
+    HIPCHK(h, d_lbest.alloc(sizeof(unsigned long long) * (size_t)n));
+    hipLaunchKernelGGL(map_loci_emit_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel, (const uint32_t*)d_lbase.p,
+                       d_lkey.p, d_lsplit.p, d_lbest.p);
+    HIPCHK(h, hipGetLastError());
+    /* pairing */
+    HIPCHK(h, d_ikey.alloc(sizeof(unsigned long long) * (size_t)n));
+    HIPCHK(h, d_nconc.alloc(sizeof(uint32_t) * (size_t)np));
+    HIPCHK(h, d_state.alloc((size_t)np));
+    HIPCHK(h, d_nanch.alloc(sizeof(uint32_t)));
+    HIPCHK(h, hipMemsetAsync(d_nanch.p, 0, sizeof(uint32_t), h->stream));
+    const bool rescue = pp->rescue_errors >= 0;
+    if (rescue) {
+        HIPCHK(h, d_anchors.alloc(sizeof(uint32_t) * (size_t)n));
+        HIPCHK(h, d_rslot.alloc(sizeof(unsigned long long) * (size_t)n));
+        HIPCHK(h, hipMemsetAsync(d_rslot.p, 0xff, sizeof(unsigned long long) * (size_t)n, h->stream));
+    }
+    MapPairArgs pa = {};
+    pa.np = (long)np, pa.roff = f.d_roff.p, pa.lbase = d_lbase.p, pa.lsplit = d_lsplit.p, pa.lbest = d_lbest.p, pa.lkey = d_lkey.p;
+    pa.min_insert = pp->min_insert, pa.max_insert = pp->max_insert, pa.rescue = pp->rescue_errors;
+    pa.ikey = d_ikey.p, pa.n_conc = d_nconc.p, pa.state = d_state.p, pa.anchors = d_anchors.p, pa.n_anchors = d_nanch.p;
+    pa.rslot = d_rslot.p, pa.seq_off = (const unsigned long long*)ix->d_seq_off;
+    hipLaunchKernelGGL(map_pair_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, pa);
+    HIPCHK(h, hipGetLastError());
+    if (rescue) {
+        const uint32_t ntile = (uint32_t)((pp->max_insert - pp->min_insert + MAP_RESCUE_TILE) / MAP_RESCUE_TILE);
+        HIPCHK(h, map_dispatch_rescue(h, f.maxm, pa, f.d_reads.p, ix, ntile, d_rslot.p));
+        hipLaunchKernelGGL(map_rescue_pick_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, pa);
+        HIPCHK(h, hipGetLastError());
+    }
+    /* finish and Greedy: item i = read i */
+    const int ocap = cigar_cap > 0 ? cigar_cap : 0;
+    Scratch<uint64_t> d_dirs(h);
+    Scratch<MapHit> d_hits(h);
+    Scratch<uint16_t> d_ops(h);
+    Scratch<uint8_t> d_nops(h);
+    Scratch<int32_t> d_cost(h);
+    HIPCHK(h, d_dirs.alloc(sizeof(uint64_t) * (f.bytes + (size_t)n)));
+    HIPCHK(h, d_hits.alloc(sizeof(MapHit) * (size_t)n));
+    HIPCHK(h, d_ops.alloc(sizeof(uint16_t) * ((size_t)n * ocap + 1)));
+    HIPCHK(h, d_nops.alloc((size_t)n));
+    MapFinishArgs fa = {};
+    fa.reads = f.d_reads.p, fa.roff = f.d_roff.p, fa.n = (long)n, fa.e = e, fa.P = e + 1, fa.k = ix->k, fa.cap = ocap;
+    fa.text = ix->d_text, fa.seq_off = (const unsigned long long*)ix->d_seq_off, fa.keys = d_ikey.p, fa.flags = f.d_flags.p;
+    fa.iread = nullptr, fa.idirs = nullptr, fa.dirs = d_dirs.p, fa.hits = d_hits.p, fa.ops = d_ops.p, fa.nops = d_nops.p;
+    HIPCHK(h, map_dispatch(h, f.maxm, true, nullptr, 0, f.d_reads.p, f.d_roff.p, ix, e, nullptr, fa));
+    std::vector<asm_map_hit> hits((size_t)n);
+    std::vector<uint16_t> ops((size_t)n * ocap);
+    std::vector<uint8_t> nops((size_t)n), state((size_t)np);
+    HIPCHK(h, hipMemcpyAsync(hits.data(), d_hits.p, sizeof(MapHit) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(state.data(), d_state.p, (size_t)np, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(n_concordant, d_nconc.p, sizeof(uint32_t) * (size_t)np, hipMemcpyDeviceToHost, h->stream));
+    if (ocap) {
+        HIPCHK(h, hipMemcpyAsync(ops.data(), d_ops.p, sizeof(uint16_t) * (size_t)n * ocap, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(nops.data(), d_nops.p, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<uint32_t> list;
+    int maxmap = 0;
+    for (int64_t i = 0; i < n; i++)
+        if (hits[(size_t)i].flags & ASM_MAP_MAPPED) {
+            list.push_back((uint32_t)i);
+            maxmap = std::max(maxmap, (int)(f.roff[(size_t)i + 1] - f.roff[(size_t)i]));
+        }
+    if (!list.empty()) {
+        const int64_t nl = (int64_t)list.size();
+        HIPCHK(h, d_list.alloc(sizeof(uint32_t) * (size_t)nl));
+        HIPCHK(h, d_cost.alloc(sizeof(int32_t) * (size_t)nl));
+        HIPCHK(h, hipMemcpyAsync(d_list.p, list.data(), sizeof(uint32_t) * (size_t)nl, hipMemcpyHostToDevice, h->stream));
+        const int rc = map_greedy(h, ix, f.d_reads.p, f.d_roff.p, d_hits.p, nullptr, d_list.p, nl, maxmap, p->greedy_k, d_cost.p);
+        if (rc) return rc;
+        std::vector<int32_t> cost((size_t)nl);
+        HIPCHK(h, hipMemcpyAsync(cost.data(), d_cost.p, sizeof(int32_t) * (size_t)nl, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int64_t q = 0; q < nl; q++) hits[list[(size_t)q]].greedy_cost = cost[(size_t)q];
+    }
+    /* into the caller's [np][2] records; the pair flags and tlen are set here */
+    for (int64_t q = 0; q < np; q++) {
+        asm_map_hit* o = out + 2 * q;
+        o[0] = hits[(size_t)q], o[1] = hits[(size_t)(np + q)];
+        const uint8_t st = state[(size_t)q];
+        if (st == MAP_PAIR_CONCORDANT || st == MAP_PAIR_RESCUED1 || st == MAP_PAIR_RESCUED2) {
+            o[0].flags |= ASM_MAP_PROPER_PAIR, o[1].flags |= ASM_MAP_PROPER_PAIR;
+            if (st == MAP_PAIR_RESCUED1) o[0].flags |= ASM_MAP_RESCUED;
+            if (st == MAP_PAIR_RESCUED2) o[1].flags |= ASM_MAP_RESCUED;
+        }
+        const bool same = (o[0].flags & ASM_MAP_MAPPED) && (o[1].flags & ASM_MAP_MAPPED) && o[0].seq_id == o[1].seq_id;
+        tlen[q] = same ? (int32_t)(std::max(o[0].end, o[1].end) - std::min(o[0].pos, o[1].pos)) : 0;
+        if (ocap)
+            for (int t = 0; t < 2; t++) {
+                const size_t i = (size_t)(t ? np + q : q);
+                std::copy(ops.begin() + i * ocap, ops.begin() + (i + 1) * ocap, cigar_ops + ((size_t)(2 * q + t)) * ocap);
+                cigar_nops[2 * q + t] = nops[i];
+            }
+    }
+    return ASM_OK;
+}
+
+int asm_map_pairs(asm_handle* h, const asm_index* ix, int64_t n, const char* reads1, const uint32_t* off1, const char* reads2,
+                  const uint32_t* off2, const asm_map_params* p, const asm_pair_params* pp, asm_map_hit* out, int32_t* tlen,
+                  uint32_t* n_concordant, uint16_t* cigar_ops, int cigar_cap, uint8_t* cigar_nops) {
+    if (!p || !pp || !ix || n < 0 || !off1 || !off2 || (n > 0 && (!reads1 || !reads2 || !out || !tlen || !n_concordant)))
+        return fail(h, ASM_EINVAL, "asm_map_pairs: bad arguments");
+    if (p->max_errors < 0 || p->max_errors > ASM_MAP_MAX_ERRORS) return fail(h, ASM_EINVAL, "asm_map_pairs: max_errors must be in [0, 15]");
+    if (p->both_strands != 1) return fail(h, ASM_EINVAL, "asm_map_pairs: both_strands must be 1");
+    if (p->max_occ < 0) return fail(h, ASM_EINVAL, "asm_map_pairs: max_occ must be >= 0");
+    if (p->greedy_k < 0 || p->greedy_k > ASM_GREEDY_MAX_K) return fail(h, ASM_EINVAL, "asm_map_pairs: greedy_k must be in [0, 50]");
+    if (pp->min_insert < 0 || pp->min_insert > pp->max_insert || pp->max_insert > ASM_MAP_MAX_INSERT)
+        return fail(h, ASM_EINVAL, "asm_map_pairs: need 0 <= min_insert <= max_insert <= 8192");
+    if (pp->rescue_errors < -1 || pp->rescue_errors > ASM_MAP_MAX_ERRORS)
+        return fail(h, ASM_EINVAL, "asm_map_pairs: rescue_errors must be -1 (off) or in [0, 15]");
+    if (cigar_cap < 0 || (cigar_cap > 0 && (!cigar_ops || !cigar_nops)))
+        return fail(h, ASM_EINVAL, "asm_map_pairs: cigar_cap > 0 needs cigar_ops and cigar_nops");
+    for (const uint32_t* ro : {off1, off2})
+        for (int64_t i = 0; i < n; i++) {
+            if (ro[i + 1] < ro[i]) return fail(h, ASM_EINVAL, "asm_map_pairs: read offsets must be non-decreasing");
+            const uint32_t m = ro[i + 1] - ro[i];
+            if (m < 1 || m > ASM_MAP_MAX_READ) return fail(h, ASM_EINVAL, "asm_map_pairs: every mate must have 1 to 511 bytes");
+        }
+    if (n > 0 && (uint64_t)(off1[n] - off1[0]) + (off2[n] - off2[0]) >= 0xffffffffull)
+        return fail(h, ASM_EUNSUPPORTED, "asm_map_pairs: both mates' bytes must stay below 2^32");
+    if (!h) return fail(h, ASM_EINVAL, "asm_map_pairs: NULL handle");
+    if (ix->device != h->device) return fail(h, ASM_EINVAL, "asm_map_pairs: the index lives on another device");
+    HIPCHK(h, hipSetDevice(h->device));
+    /* at most map_chunk / 2 pairs per chunk; the run key holds the read (2 per pair) in its top 31 bits */
+    const int64_t step = std::max<int64_t>(1, std::min<int64_t>(h->map_chunk, (int64_t)1 << 30) / 2);
+    for (int64_t c0 = 0; c0 < n; c0 += step) {
+        const int64_t c1 = std::min(n, c0 + step);
+        const size_t o = (size_t)c0 * 2;
+        const int rc = map_chunk_pairs(h, ix, c1 - c0, reads1, off1 + c0, reads2, off2 + c0, p, pp, out + o, tlen + c0, n_concordant + c0,
+                                       cigar_cap > 0 ? cigar_ops + o * cigar_cap : nullptr, cigar_cap,
+                                       cigar_cap > 0 ? cigar_nops + o : nullptr);
         if (rc) return rc;
     }
     return ASM_OK;

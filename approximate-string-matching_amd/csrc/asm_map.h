@@ -17,6 +17,10 @@
 //          buffer, a radix sort orders them by (read, strand, position), map_select_count_kernel / map_select_emit_kernel merge
 //          them into loci and list the reported ones as items (read, packed key), and the finish and Greedy kernels run once per
 //          item.
+// Pairs (asm_map_pairs): the mates' run records as for all hits, map_loci_emit_kernel lists each read's loci, map_pair_kernel
+//          picks the best concordant pair per pair with two pointers over the mates' lists, map_rescue_kernel<W> searches a mapped
+//          mate's insert window for its partner (tiles of ends, 64-bit atomicMin per anchor), map_rescue_pick_kernel keeps the
+//          better rescued pair, and the finish and Greedy run on one item per read.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -440,6 +444,217 @@ __global__ __launch_bounds__(256) void map_select_emit_kernel(MapSelectArgs a) {
                 a.idirs[q0 + k] = db + (unsigned long long)k * (m + 1u);
                 k++;
             });
+    }
+}
+
+/* ---- paired-end reads (asm_map_pairs) ---------------------------------------------------------------------------------------
+ * A chunk of np pairs is mapped as 2 np reads: mate 1 of pair p is read p, mate 2 is read np + p.  The run records are those of
+ * asm_map_reads_all; each read's loci are listed in walk order, (s, r, j), as packed keys d << 59 | s << 58 | r << 32 | j (j
+ * exclusive, local to r).  Masking d off a key leaves (s, r, j), so a list is sorted by that and its s = 1 part follows its s = 0
+ * part.  The pairing picks one item per read (a locus key, or MAP_NO_KEY), so the finish runs on the identity list. */
+#define MAP_RESCUE_TILE 128 /* ends per rescue thread */
+#define MAP_KEY_D(k) ((int)((k) >> 59))
+#define MAP_KEY_S(k) ((uint32_t)((k) >> 58) & 1u)
+#define MAP_KEY_R(k) ((uint32_t)((k) >> 32) & (MAP_MAX_SEQS - 1))
+#define MAP_KEY_J(k) ((uint32_t)(k))
+
+/* per pair (asm_map_pairs): what the pairing decided */
+#define MAP_PAIR_NONE 0u       /* no proper pair: each mate its best hit */
+#define MAP_PAIR_CONCORDANT 1u
+#define MAP_PAIR_RESCUE 2u     /* no concordant pair, rescue on: the rescue kernels decide */
+#define MAP_PAIR_RESCUED1 3u   /* mate 1 rescued (anchor mate 2) */
+#define MAP_PAIR_RESCUED2 4u   /* mate 2 rescued (anchor mate 1) */
+
+ASM_DEV unsigned long long map_pack_key(int d, uint32_t s, uint32_t r, uint32_t j) {
+    return (unsigned long long)d << 59 | (unsigned long long)s << 58 | (unsigned long long)r << 32 | j;
+}
+
+/* thread per read: its loci keys into lkey[lbase[i], ...) in walk order (n_hits of map_select_count_kernel with strata = e), the
+ * first index of its s = 1 part into lsplit[i], and its smallest key (the best hit; MAP_NO_KEY without loci) into lbest[i] */
+__global__ __launch_bounds__(256) void map_loci_emit_kernel(MapSelectArgs a, const uint32_t* __restrict__ lbase,
+                                                            unsigned long long* __restrict__ lkey, uint32_t* __restrict__ lsplit,
+                                                            unsigned long long* __restrict__ lbest) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (long)gridDim.x * blockDim.x) {
+        const unsigned long long b = map_run_lower(a.rkey, a.nr, (unsigned long long)i), e = map_run_lower(a.rkey, a.nr, (unsigned long long)i + 1);
+        uint32_t k = lbase[i], split = 0xffffffffu;
+        unsigned long long best = MAP_NO_KEY;
+        map_walk_loci(a.rkey, a.rval, b, e, a.seq_off, a.n_seqs, [&](uint32_t s, uint32_t r, int d, uint32_t j) {
+            const unsigned long long key = map_pack_key(d, s, r, (uint32_t)((unsigned long long)j + 1ull - a.seq_off[r]));
+            if (s && split == 0xffffffffu) split = k;
+            best = key < best ? key : best;
+            lkey[k++] = key;
+        });
+        lsplit[i] = split == 0xffffffffu ? k : split;
+        lbest[i] = best;
+    }
+}
+
+struct MapPairArgs {
+    long np;                           /* pairs; mate 1 = read p, mate 2 = read np + p */
+    const uint32_t* roff;              /* 2 np + 1 */
+    const uint32_t* lbase;             /* 2 np + 1: loci of read i are lkey[lbase[i], lbase[i + 1]) */
+    const uint32_t* lsplit;            /* 2 np: the first of them with s = 1 */
+    const unsigned long long* lbest;   /* 2 np: the smallest of them (MAP_NO_KEY: none) */
+    const unsigned long long* lkey;
+    int min_insert, max_insert, rescue; /* rescue < 0: off */
+    unsigned long long* ikey;          /* per read: the item key (MAP_NO_KEY = unmapped) */
+    uint32_t* n_conc;                  /* per pair */
+    uint8_t* state;                    /* per pair: MAP_PAIR_* */
+    uint32_t* anchors;                 /* rescue anchors: read index of the anchor mate, appended */
+    uint32_t* n_anchors;
+    const unsigned long long* rslot;   /* per read (the rescued mate): d << 32 | j, ~0 = nothing */
+    const unsigned long long* seq_off;
+};
+
+/* the pair order (d_A + d_B, s_A, r, j_A, j_B) as two words */
+struct MapPairRank {
+    unsigned long long hi, lo;
+};
+ASM_DEV MapPairRank map_pair_rank(unsigned long long kA, unsigned long long kB) {
+    MapPairRank x;
+    x.hi = (unsigned long long)(MAP_KEY_D(kA) + MAP_KEY_D(kB)) << 27 | (unsigned long long)MAP_KEY_S(kA) << 26 | MAP_KEY_R(kA);
+    x.lo = (unsigned long long)MAP_KEY_J(kA) << 32 | MAP_KEY_J(kB);
+    return x;
+}
+ASM_DEV bool map_rank_less(const MapPairRank& a, const MapPairRank& b) { return a.hi != b.hi ? a.hi < b.hi : a.lo < b.lo; }
+
+/* The concordant pairs with F = a locus of list f (s = 0 part [f0, f1), mate length mF) and R = a locus of list g (s = 1 part
+ * [g0, g1)): for F in (r, j) order, the R with the same r and j_R in [j_F - mF + min_insert, j_F - mF + max_insert] are a
+ * contiguous range of g that only moves forward.  fn(kF, kR) per concordant combination. */
+template <class Fn>
+ASM_DEV void map_sweep(const unsigned long long* __restrict__ lkey, uint32_t f0, uint32_t f1, uint32_t g0, uint32_t g1, uint32_t mF,
+                       int min_insert, int max_insert, Fn&& fn) {
+    const unsigned long long RJ = (1ull << 58) - 1ull; /* (r, j) bits of a key */
+    uint32_t lo = g0, hi = g0;
+    for (uint32_t x = f0; x < f1; x++) {
+        const unsigned long long kF = lkey[x];
+        const long long r = (long long)MAP_KEY_R(kF), base = (long long)MAP_KEY_J(kF) - (long long)mF;
+        const long long jlo = base + min_insert, jhi = base + max_insert;
+        if (jhi < 1) continue; /* loci ends are >= 1 */
+        const unsigned long long want_lo = (unsigned long long)r << 32 | (unsigned long long)(jlo < 0 ? 0 : jlo > 0xffffffffll ? 0xffffffffll : jlo);
+        const unsigned long long want_hi = (unsigned long long)r << 32 | (unsigned long long)(jhi > 0xffffffffll ? 0xffffffffll : jhi);
+        while (lo < g1 && (lkey[lo] & RJ) < want_lo) lo++;
+        if (hi < lo) hi = lo;
+        while (hi < g1 && (lkey[hi] & RJ) <= want_hi) hi++;
+        for (uint32_t y = lo; y < hi; y++) fn(kF, lkey[y]);
+    }
+}
+
+/* thread per pair: the best concordant pair by pair order and n_concordant (the pairs with its d sum), else each mate's best hit
+ * (its smallest key) and, with rescue on, each mapped mate as a rescue anchor */
+__global__ __launch_bounds__(256) void map_pair_kernel(MapPairArgs a) {
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < a.np; p += (long)gridDim.x * blockDim.x) {
+        const long A = p, B = a.np + p;
+        const uint32_t mA = a.roff[A + 1] - a.roff[A], mB = a.roff[B + 1] - a.roff[B];
+        const uint32_t a0 = a.lbase[A], a1 = a.lbase[A + 1], b0 = a.lbase[B], b1 = a.lbase[B + 1];
+        const uint32_t as = a.lsplit[A], bs = a.lsplit[B];
+        MapPairRank best = {~0ull, ~0ull};
+        unsigned long long kbA = MAP_NO_KEY, kbB = MAP_NO_KEY;
+        uint32_t cnt = 0;
+        auto visit = [&](unsigned long long kA, unsigned long long kB) {
+            const MapPairRank x = map_pair_rank(kA, kB);
+            const unsigned long long sum = x.hi >> 27, bsum = best.hi >> 27;
+            if (sum < bsum) cnt = 1;
+            else if (sum == bsum && cnt != 0xffffffffu) cnt++;
+            if (map_rank_less(x, best)) best = x, kbA = kA, kbB = kB;
+        };
+        map_sweep(a.lkey, a0, as, bs, b1, mA, a.min_insert, a.max_insert, [&](unsigned long long kF, unsigned long long kR) { visit(kF, kR); });
+        map_sweep(a.lkey, b0, bs, as, a1, mB, a.min_insert, a.max_insert, [&](unsigned long long kF, unsigned long long kR) { visit(kR, kF); });
+        a.n_conc[p] = cnt;
+        if (cnt) {
+            a.ikey[A] = kbA, a.ikey[B] = kbB, a.state[p] = (uint8_t)MAP_PAIR_CONCORDANT;
+            continue;
+        }
+        const unsigned long long fA = a.lbest[A], fB = a.lbest[B]; /* the first locus in (d, s, r, j) order: the best hit */
+        a.ikey[A] = fA, a.ikey[B] = fB;
+        const bool resc = a.rescue >= 0 && (fA != MAP_NO_KEY || fB != MAP_NO_KEY);
+        a.state[p] = (uint8_t)(resc ? MAP_PAIR_RESCUE : MAP_PAIR_NONE);
+        if (resc) {
+            const uint32_t na = (fA != MAP_NO_KEY) + (fB != MAP_NO_KEY);
+            uint32_t slot = atomicAdd(a.n_anchors, na);
+            if (fA != MAP_NO_KEY) a.anchors[slot++] = (uint32_t)A;
+            if (fB != MAP_NO_KEY) a.anchors[slot] = (uint32_t)B;
+        }
+    }
+}
+
+/* the partner of read x and the window of ends [jlo, jhi] (local to the anchor's sequence, clipped to [1, len_r]) in which it is
+ * searched on strand 1 - s_X; false when the window is empty */
+ASM_DEV bool map_rescue_window(const MapPairArgs& a, uint32_t x, uint32_t& b, uint32_t& mb, long long& jlo, long long& jhi) {
+    b = x < (uint32_t)a.np ? x + (uint32_t)a.np : x - (uint32_t)a.np;
+    const uint32_t mx = a.roff[x + 1] - a.roff[x];
+    mb = a.roff[b + 1] - a.roff[b];
+    const unsigned long long k = a.ikey[x];
+    const uint32_t r = MAP_KEY_R(k);
+    const long long j = (long long)MAP_KEY_J(k), len_r = (long long)(a.seq_off[r + 1] - a.seq_off[r]);
+    if (!MAP_KEY_S(k)) jlo = j - mx + a.min_insert, jhi = j - mx + a.max_insert;
+    else jlo = j + mb - a.max_insert, jhi = j + mb - a.min_insert;
+    jlo = jlo < 1 ? 1 : jlo;
+    jhi = jhi > len_r ? len_r : jhi;
+    return jlo <= jhi;
+}
+
+/* thread per (anchor, tile of MAP_RESCUE_TILE ends): a semi-global Myers/Hyyro pass of the partner q_b (strand 1 - s_X) that starts
+ * mb + rescue columns before the tile, so that D is exact wherever D <= rescue; the tile's smallest (D, j) with D <= rescue and
+ * D < mb is folded into rslot[b] with a 64-bit atomicMin.  Every anchor has ntile tiles; the anchor count is read on the device. */
+template <int W>
+__global__ __launch_bounds__(256) void map_rescue_kernel(MapPairArgs a, const char* __restrict__ reads, const char* __restrict__ text,
+                                                         uint32_t ntile, unsigned long long* __restrict__ rslot) {
+    const unsigned long long nt = (unsigned long long)*a.n_anchors * ntile;
+    for (unsigned long long g = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; g < nt;
+         g += (unsigned long long)gridDim.x * blockDim.x) {
+        const uint32_t x = a.anchors[g / ntile], tile = (uint32_t)(g % ntile);
+        uint32_t b, mb;
+        long long jlo, jhi;
+        if (!map_rescue_window(a, x, b, mb, jlo, jhi)) continue;
+        const long long tlo = jlo + (long long)tile * MAP_RESCUE_TILE;
+        if (tlo > jhi) continue;
+        const long long thi = tlo + MAP_RESCUE_TILE - 1 < jhi ? tlo + MAP_RESCUE_TILE - 1 : jhi;
+        const unsigned long long k = a.ikey[x];
+        const uint32_t s = 1u - MAP_KEY_S(k), r = MAP_KEY_R(k);
+        const long long c0 = tlo - (long long)mb - a.rescue; /* first text column (0-based): the smallest start that can reach D <= rescue */
+        uint64_t peq[4][W];
+        map_build_peq<W>(reads + a.roff[b], mb, s, false, peq);
+        uint64_t Pv[W], Mv[W];
+#pragma unroll
+        for (int w = 0; w < W; w++) Pv[w] = ~0ull, Mv[w] = 0ull;
+        const int nw = (int)((mb + 63u) >> 6);
+        const uint32_t last_bit = (mb - 1u) & 63u;
+        const char* tx = text + a.seq_off[r];
+        int score = (int)mb, best = a.rescue + 1;
+        uint32_t best_j = 0;
+        for (long long t = c0 < 0 ? 0 : c0; t < thi; t++) {
+            score += map_column<W>(Pv, Mv, peq, map_code((uint8_t)tx[t]), nw, last_bit, 0);
+            if (t + 1 >= tlo && score < best) best = score, best_j = (uint32_t)(t + 1); /* first end reaching the minimum */
+        }
+        if (best <= a.rescue && best < (int)mb) atomicMin(rslot + b, (unsigned long long)best << 32 | best_j);
+    }
+}
+
+/* thread per pair in MAP_PAIR_RESCUE: the rescued pair of each anchor (anchor X, rescued locus Y = (d, 1 - s_X, r_X, j)), the one
+ * smaller in pair order wins; its rescued mate's item key is written */
+__global__ __launch_bounds__(256) void map_rescue_pick_kernel(MapPairArgs a) {
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < a.np; p += (long)gridDim.x * blockDim.x) {
+        if (a.state[p] != MAP_PAIR_RESCUE) continue;
+        const long A = p, B = a.np + p;
+        const unsigned long long kA = a.ikey[A], kB = a.ikey[B];
+        MapPairRank best = {~0ull, ~0ull};
+        unsigned long long key = MAP_NO_KEY;
+        long who = -1;
+        for (int x = 0; x < 2; x++) {
+            const long Y = x ? A : B; /* the rescued mate; the anchor is the other one */
+            const unsigned long long kX = x ? kB : kA, slot = a.rslot[Y];
+            if (kX == MAP_NO_KEY || slot == ~0ull) continue;
+            const unsigned long long kY = map_pack_key((int)(slot >> 32), 1u - MAP_KEY_S(kX), MAP_KEY_R(kX), (uint32_t)slot);
+            const MapPairRank rk = x ? map_pair_rank(kY, kX) : map_pair_rank(kX, kY);
+            if (map_rank_less(rk, best)) best = rk, key = kY, who = Y;
+        }
+        if (who < 0) {
+            a.state[p] = (uint8_t)MAP_PAIR_NONE;
+            continue;
+        }
+        a.ikey[who] = key;
+        a.state[p] = (uint8_t)(who == A ? MAP_PAIR_RESCUED1 : MAP_PAIR_RESCUED2);
     }
 }
 

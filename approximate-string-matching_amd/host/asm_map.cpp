@@ -3,10 +3,18 @@
 // at start-up.
 //   asm-map -r ref.fa -q reads.fq [-o out.sam] [-e N] [--k 12] [--both-strands] [--max-occ N] [--chunk N]
 //           [--all-hits N [--strata S]]
+//   asm-map -r ref.fa -1 r1.fq -2 r2.fq [-o out.sam] -e N --insert MIN,MAX [--rescue E] [--k 12] [--max-occ N] [--chunk N]
 // --all-hits N writes up to N loci per read in rank order (asm_map_reads_all, strata S, default e): the primary record as without
 // it, then the secondary ones (FLAG 256, SEQ and QUAL '*'), each with NH:i:<reported> HI:i:<rank + 1> XH:i:<all loci> after NM
 // and XG.  Reads may be FASTQ or FASTA (QUAL '*').  Reads are processed in chunks of --chunk records, so the read file's size is not
 // bounded by memory.  Reads longer than ASM_MAP_MAX_READ are written unmapped.
+// Paired mode (-1 / -2, asm_map_pairs: FR pairs with a projected span in [MIN, MAX], mate rescue with E errors) searches both
+// strands and writes mate 1 then mate 2.  QNAME is the first word without a trailing /1 or /2; the two files must name the pairs
+// alike.  FLAG = 1 | 2 (proper) | 4 / 8 (self / mate unmapped) | 16 / 32 (self / mate reverse) | 64 / 128 (mate 1 / 2); an
+// unmapped mate of a mapped mate takes its RNAME and POS; RNEXT is '=' on the same sequence and '*' when the mate is unmapped;
+// PNEXT is the mate's POS; TLEN is +tlen on the mate with the smaller POS (mate 1 when equal) and -tlen on the other.  Proper
+// pairs carry XP:i:<n_concordant>, rescued records XR:i:1.  A mate longer than ASM_MAP_MAX_READ (or empty) leaves its pair
+// unmapped.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -18,7 +26,9 @@
 
 static void usage() {
     fprintf(stderr, "usage: asm-map -r ref.fa -q reads.fq [-o out.sam] [-e N] [--k 12] [--both-strands] [--max-occ N] [--chunk N] "
-                    "[--all-hits N [--strata S]]\n");
+                    "[--all-hits N [--strata S]]\n"
+                    "       asm-map -r ref.fa -1 r1.fq -2 r2.fq [-o out.sam] -e N --insert MIN,MAX [--rescue E] [--k 12] [--max-occ N] "
+                    "[--chunk N]\n");
     exit(2);
 }
 
@@ -86,8 +96,128 @@ struct ReadFile {
     }
 };
 
+static std::string pair_name(const std::string& n) {
+    if (n.size() >= 2 && n[n.size() - 2] == '/' && (n.back() == '1' || n.back() == '2')) return n.substr(0, n.size() - 2);
+    return n;
+}
+
+static std::string revcomp(const std::string& q) {
+    std::string o(q.rbegin(), q.rend());
+    for (char& c : o) c = comp(c);
+    return o;
+}
+
+static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vector<std::string>& names, ReadFile& f1, ReadFile& f2,
+                       const asm_map_params& p, const asm_pair_params& pp, long chunk) {
+    const int cap = 64;
+    std::vector<Record> a, b;
+    std::vector<char> buf1, buf2;
+    std::vector<uint32_t> ro1, ro2;
+    std::vector<int64_t> slot;
+    std::vector<asm_map_hit> hits;
+    std::vector<int32_t> tlen;
+    std::vector<uint32_t> nconc;
+    std::vector<uint16_t> ops;
+    std::vector<uint8_t> nops;
+    long long n_pairs = 0, n_proper = 0, n_rescued = 0;
+    bool more = true;
+    while (more) {
+        a.clear(), b.clear();
+        Record r1, r2;
+        while ((long)a.size() < chunk) {
+            const bool g1 = f1.next(r1), g2 = f2.next(r2);
+            if (g1 != g2) {
+                fprintf(stderr, "asm-map: the two read files hold different numbers of records\n");
+                return 1;
+            }
+            if (!(more = g1)) break;
+            if (pair_name(r1.name) != pair_name(r2.name)) {
+                fprintf(stderr, "asm-map: mate names differ: %s and %s\n", r1.name.c_str(), r2.name.c_str());
+                return 1;
+            }
+            a.push_back(r1), b.push_back(r2);
+        }
+        if (a.empty()) break;
+        buf1.clear(), buf2.clear(), ro1.assign(1, 0), ro2.assign(1, 0), slot.assign(a.size(), -1);
+        for (size_t q = 0; q < a.size(); q++) {
+            for (char& c : a[q].seq) c = up(c);
+            for (char& c : b[q].seq) c = up(c);
+            const size_t m1 = a[q].seq.size(), m2 = b[q].seq.size();
+            if (m1 < 1 || m1 > ASM_MAP_MAX_READ || m2 < 1 || m2 > ASM_MAP_MAX_READ) continue;
+            slot[q] = (int64_t)ro1.size() - 1;
+            buf1.insert(buf1.end(), a[q].seq.begin(), a[q].seq.end());
+            buf2.insert(buf2.end(), b[q].seq.begin(), b[q].seq.end());
+            ro1.push_back((uint32_t)buf1.size()), ro2.push_back((uint32_t)buf2.size());
+        }
+        const int64_t n = (int64_t)ro1.size() - 1;
+        hits.assign((size_t)(n + 1) * 2, asm_map_hit{});
+        tlen.assign((size_t)n + 1, 0), nconc.assign((size_t)n + 1, 0);
+        ops.assign((size_t)(n + 1) * 2 * cap, 0), nops.assign((size_t)(n + 1) * 2, 0);
+        if (asm_map_pairs(h, ix, n, buf1.data(), ro1.data(), buf2.data(), ro2.data(), &p, &pp, hits.data(), tlen.data(), nconc.data(),
+                          ops.data(), cap, nops.data())) {
+            fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
+            return 1;
+        }
+        const asm_map_hit none = {-1, 0, 0, -1, 0, 0, -1};
+        for (size_t q = 0; q < a.size(); q++) {
+            n_pairs++;
+            const Record* rec[2] = {&a[q], &b[q]};
+            const asm_map_hit* hr[2] = {&none, &none};
+            if (slot[q] >= 0) hr[0] = &hits[(size_t)slot[q] * 2], hr[1] = &hits[(size_t)slot[q] * 2 + 1];
+            const bool mapped[2] = {(hr[0]->flags & ASM_MAP_MAPPED) != 0, (hr[1]->flags & ASM_MAP_MAPPED) != 0};
+            const bool proper = (hr[0]->flags & ASM_MAP_PROPER_PAIR) != 0;
+            n_proper += proper;
+            /* RNAME / POS of each record: its own, else its mapped mate's */
+            int rid[2];
+            long long pos[2];
+            for (int x = 0; x < 2; x++) {
+                const int y = mapped[x] ? x : mapped[1 - x] ? 1 - x : -1;
+                rid[x] = y < 0 ? -1 : hr[y]->seq_id;
+                pos[x] = y < 0 ? 0 : (long long)hr[y]->pos + 1;
+            }
+            const long long tl = slot[q] >= 0 ? tlen[(size_t)slot[q]] : 0;
+            const int plus = pos[0] <= pos[1] ? 0 : 1; /* the mate whose TLEN is positive */
+            for (int x = 0; x < 2; x++) {
+                const asm_map_hit& m = *hr[x];
+                const int y = 1 - x;
+                int flag = 1 | (proper ? 2 : 0) | (mapped[x] ? 0 : 4) | (mapped[y] ? 0 : 8) | (x ? 128 : 64);
+                if (mapped[x] && m.strand) flag |= 16;
+                if (mapped[y] && hr[y]->strand) flag |= 32;
+                std::string seq = rec[x]->seq, qual = rec[x]->qual;
+                char cigar[4096];
+                strcpy(cigar, "*");
+                int mapq = 0;
+                if (mapped[x]) {
+                    if (m.strand) {
+                        seq = revcomp(rec[x]->seq);
+                        if (qual != "*") qual.assign(rec[x]->qual.rbegin(), rec[x]->qual.rend());
+                    }
+                    const size_t o = (size_t)slot[q] * 2 + x;
+                    const int nn = nops[o];
+                    if (asm_cigar_format(&ops[o * cap], nn, cap, cigar, sizeof(cigar)) != 0 || nn > cap) strcpy(cigar, "*");
+                    mapq = m.greedy_cost + 60 < 254 ? m.greedy_cost + 60 : 254;
+                }
+                const char* rnext = !mapped[y] ? "*" : rid[y] == rid[x] ? "=" : names[(size_t)rid[y]].c_str();
+                fprintf(out, "%s\t%d\t%s\t%lld\t%d\t%s\t%s\t%lld\t%lld\t%s\t%s", pair_name(rec[x]->name).c_str(), flag,
+                        rid[x] < 0 ? "*" : names[(size_t)rid[x]].c_str(), pos[x], mapq, cigar, rnext, pos[y], x == plus ? tl : -tl,
+                        seq.empty() ? "*" : seq.c_str(), qual.empty() ? "*" : qual.c_str());
+                if (mapped[x]) fprintf(out, "\tNM:i:%d\tXG:i:%d", (int)m.dist, m.greedy_cost);
+                if (proper) fprintf(out, "\tXP:i:%u", nconc[(size_t)slot[q]]);
+                if (m.flags & ASM_MAP_RESCUED) {
+                    fprintf(out, "\tXR:i:1");
+                    n_rescued++;
+                }
+                fputc('\n', out);
+            }
+        }
+    }
+    fprintf(stderr, "asm-map: %lld pairs, %lld proper, %lld mates rescued\n", n_pairs, n_proper, n_rescued);
+    return 0;
+}
+
 int main(int argc, char** argv) {
-    std::string ref_path, read_path, out_path = "out.sam";
+    std::string ref_path, read_path, read2_path, out_path = "out.sam";
+    asm_pair_params pp = {-1, -1, -1};
     asm_map_params p = {0, 0, 0, 3};
     int k = 12;
     long chunk = 262144;
@@ -101,7 +231,11 @@ int main(int argc, char** argv) {
             return argv[++a];
         };
         if (s == "-r") ref_path = val();
-        else if (s == "-q") read_path = val();
+        else if (s == "-q" || s == "-1") read_path = val();
+        else if (s == "-2") read2_path = val();
+        else if (s == "--insert") {
+            if (sscanf(val(), "%d,%d", &pp.min_insert, &pp.max_insert) != 2) usage();
+        } else if (s == "--rescue") pp.rescue_errors = atoi(val());
         else if (s == "-o") out_path = val();
         else if (s == "-e") p.max_errors = atoi(val());
         else if (s == "--k") k = atoi(val());
@@ -113,6 +247,10 @@ int main(int argc, char** argv) {
         else usage();
     }
     if (ref_path.empty() || read_path.empty() || chunk < 1 || all_hits < 0 || (strata >= 0 && !all_hits)) usage();
+    const bool paired = !read2_path.empty();
+    if (paired && (all_hits || pp.min_insert < 0 || pp.max_insert < 0)) usage(); /* paired: --insert needed, --all-hits refused */
+    if (!paired && (pp.min_insert >= 0 || pp.rescue_errors >= 0)) usage();
+    if (paired) p.both_strands = 1;
     if (strata < 0) strata = p.max_errors;
     const int slots = all_hits ? all_hits : 1; /* records per read in the library's output */
 
@@ -172,6 +310,27 @@ int main(int argc, char** argv) {
     for (size_t r = 0; r < names.size(); r++)
         fprintf(out, "@SQ\tSN:%s\tLN:%llu\n", names[r].c_str(), (unsigned long long)(off[r + 1] - off[r]));
     fprintf(out, "@PG\tID:asm-map\tPN:asm-map\tVN:%s\tCL:%s\n", asm_version(), cl.c_str());
+    if (paired) {
+        FILE* rf2 = fopen(read2_path.c_str(), "r");
+        if (!rf2) {
+            fprintf(stderr, "asm-map: cannot open %s\n", read2_path.c_str());
+            return 1;
+        }
+        ReadFile reads2;
+        reads2.f = rf2;
+        {
+            int c = fgetc(rf2);
+            reads2.fasta = c == '>';
+            if (c != EOF) ungetc(c, rf2);
+        }
+        rc = write_pairs(out, h, ix, names, reads, reads2, p, pp, chunk);
+        fclose(out);
+        fclose(rf);
+        fclose(rf2);
+        asm_index_free(h, ix);
+        asm_destroy(h);
+        return rc;
+    }
 
     const int cap = 64;
     std::vector<Record> recs;

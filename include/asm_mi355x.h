@@ -364,14 +364,30 @@ int asm_profile_read(asm_handle* h, float* ms, int cap_calls, int* n_calls);
  *                  asm_map_reads' record of the read (an unmapped read: n_hits 0 and the unmapped record at rank 0), plus flag
  *                  HITS_TRUNCATED.  Ranks >= 1 carry flag SECONDARY; every record of a read with n_hits > max_hits carries
  *                  HITS_TRUNCATED.  A slot beyond the reported ones: seq_id -1, pos = end = 0, dist -1, greedy_cost -1, flags 0,
- *                  cigar_nops 0 (its cigar_ops row is not written).  Synchronous. */
+ *                  cigar_nops 0 (its cigar_ops row is not written).  Synchronous.
+ * asm_map_pairs:   paired-end reads, FR orientation (docs/design/mapper.md, "Paired-end reads").  Mate 1 of pair i is reads1 /
+ *                  off1 [i], mate 2 is reads2 / off2 [i], 1 to 511 bytes each; both_strands must be 1.  A mate's loci are those of
+ *                  asm_map_reads_all with strata = max_errors.  For loci A (mate 1) and B (mate 2), F = the one with s = 0, R = the
+ *                  one with s = 1, m_F = F's mate length: projected span L = j_R - j_F + m_F.  Concordant: same r, s_A != s_B and
+ *                  min_insert <= L <= max_insert (0 <= min_insert <= max_insert <= ASM_MAP_MAX_INSERT).  Pair order: (d_A + d_B, s_A,
+ *                  r, j_A, j_B); the best concordant pair is reported and n_concordant[i] counts the concordant pairs with its d sum
+ *                  (uncapped, saturating).  Without one, and with rescue_errors in [0, 15] (-1: off), each mapped mate X (its best
+ *                  hit) is an anchor and its partner b is searched on strand 1 - s_X in T_r over the ends that keep L in range: the
+ *                  smallest (D(j), j) with D(j) <= rescue_errors and D(j) < m_b is the rescued locus; of two rescued pairs the smaller
+ *                  in pair order is reported.  out = [n][2] records (mate 1, mate 2), cigar_ops = [n][2][cigar_cap], cigar_nops =
+ *                  [n][2], tlen[i] = max(end) - min(pos) when both mates map to the same r, else 0.  A proper pair has PROPER_PAIR on
+ *                  both records and RESCUED on a rescued one; a non-rescued proper record is, flags apart, asm_map_reads_all's record of
+ *                  that locus.  Without a proper pair each record is asm_map_reads' record of that mate.  Synchronous. */
 #define ASM_MAP_MAPPED 1
 #define ASM_MAP_TOO_SHORT 2
 #define ASM_MAP_SEED_CAPPED 4
 #define ASM_MAP_CIGAR_TRUNCATED 8
 #define ASM_MAP_SECONDARY 16
 #define ASM_MAP_HITS_TRUNCATED 32
+#define ASM_MAP_PROPER_PAIR 64
+#define ASM_MAP_RESCUED 128
 #define ASM_MAP_MAX_HITS 256
+#define ASM_MAP_MAX_INSERT 8192
 #define ASM_MAP_MIN_K 8
 #define ASM_MAP_MAX_K 14
 #define ASM_MAP_MAX_READ 511
@@ -399,6 +415,15 @@ int asm_map_reads_all(asm_handle* h, const asm_index* ix, int64_t n, const char*
                       const asm_map_params* p, int strata, int max_hits, uint32_t* n_hits /* [n] */,
                       asm_map_hit* out /* [n][max_hits] */, uint16_t* cigar_ops /* [n][max_hits][cigar_cap] */, int cigar_cap,
                       uint8_t* cigar_nops /* [n][max_hits] */);
+typedef struct asm_pair_params {
+    int32_t min_insert;    /* projected span L in [min_insert, max_insert], 0 <= min_insert <= max_insert <= 8192 */
+    int32_t max_insert;
+    int32_t rescue_errors; /* mate rescue's error bound in [0, 15]; -1 = no rescue                                  */
+} asm_pair_params;
+int asm_map_pairs(asm_handle* h, const asm_index* ix, int64_t n, const char* reads1, const uint32_t* off1, const char* reads2,
+                  const uint32_t* off2, const asm_map_params* p, const asm_pair_params* pp, asm_map_hit* out /* [n][2] */,
+                  int32_t* tlen /* [n] */, uint32_t* n_concordant /* [n] */, uint16_t* cigar_ops /* [n][2][cigar_cap] */,
+                  int cigar_cap, uint8_t* cigar_nops /* [n][2] */);
 
 /* ---- plain device memory helpers (so that non-torch hosts can drive the async API) --------------------- */
 int asm_device_malloc(asm_handle* h, size_t bytes, void** d_ptr);

@@ -6,6 +6,10 @@ synchronous library call (so host-to-device copies and the host's share of asm_m
 --all-hits N also times asm_map_reads_all (up to N loci per read, strata S, default e), alternating with asm_map_reads in the
 same process, and prints the hits-per-read distribution.  --repeats pastes 200 copies of a 2 kbp element (0-3 % substitutions,
 half reverse-complemented) and 6 kbp of a period-6 tandem repeat into the reference, and draws 30 % of the reads from them.
+--paired [--insert 200,500] [--rescue E] simulates --reads / 2 FR pairs (fragments uniform in the insert range, mates of --len
+bases with 0..e substitutions; 5 % discordant pairs: out of range, same strand or far apart; 10 % random pairs; 10 % of pairs with
+one mate carrying e+1..e+3 substitutions; with --repeats, 30 % of the fragments inside the element copies) and times asm_map_pairs
+against asm_map_reads_all (strata = e, max_hits = 1) on the same reads, alternately, and reports the proper and rescued fractions.
 --profile re-runs the same command under `rocprofv3 --kernel-trace --stats` (a run of its own) and prints the per-kernel totals."""
 import argparse
 import ctypes
@@ -73,11 +77,15 @@ def main():
     ap.add_argument("--all-hits", type=int, default=0, help="also time asm_map_reads_all with up to N loci per read")
     ap.add_argument("--strata", type=int, default=None, help="with --all-hits: strata (default e)")
     ap.add_argument("--repeats", action="store_true", help="the reference with repeats, 30 %% of the reads from them")
+    ap.add_argument("--paired", action="store_true", help="time asm_map_pairs on --reads / 2 simulated pairs")
+    ap.add_argument("--insert", default="200,500", help="with --paired: MIN,MAX of the projected span")
+    ap.add_argument("--rescue", type=int, default=-1, help="with --paired: mate rescue's error bound (-1: off)")
     ap.add_argument("--out", default=None, help="directory for the JSON result (and the profile with --profile)")
     ap.add_argument("--profile", action="store_true")
     a = ap.parse_args()
     extra = (["--all-hits", str(a.all_hits)] if a.all_hits else []) + (["--strata", str(a.strata)] if a.strata is not None else [])
     extra += ["--repeats"] if a.repeats else []
+    extra += ["--paired", "--insert", a.insert, "--rescue", str(a.rescue)] if a.paired else []
     n, ref_len = int(a.reads), int(a.ref_len)
     if a.profile:
         out = a.out or "bench_map_profile"
@@ -97,6 +105,8 @@ def main():
     lib, h = eng.lib, eng.h
     tm = eng.timer()
     results = {"ref_len": ref_len, "reads": n, "read_len": a.len, "k": a.k, "repeats": a.repeats, "all_hits": a.all_hits, "runs": []}
+    if a.paired:
+        return run_paired(a, eng, tm, n, ref_len)
     for e in a.errors:
         ref, reads = make_inputs(ref_len, n, a.len, e, seed=1000 + e, repeats=a.repeats)
         off = np.array([0, ref_len], np.uint64)
@@ -152,6 +162,111 @@ def main():
     if a.out:
         os.makedirs(a.out, exist_ok=True)
         with open(os.path.join(a.out, "bench_map.json"), "w") as fh:
+            json.dump(results, fh, indent=1)
+
+
+def make_pairs(ref, npairs, length, e, lo, hi, seed, repeats=False):
+    """-> (mates 1, mates 2) as (npairs, length) uint8 arrays; see the module docstring for the mix"""
+    rng = np.random.default_rng(seed)
+    L = ref.size
+    f = rng.integers(max(lo, length), hi + 1, npairs)
+    a = rng.integers(0, L - hi - 2100, npairs)
+    if repeats:  # the element copies of make_inputs(repeats=True)
+        rep = rng.random(npairs) < 0.3
+        places = 100_000 + 20_000 * np.arange(200)
+        a[rep] = places[rng.integers(0, 200, int(rep.sum()))] + rng.integers(0, 2000 - f[rep] + 1)
+    cols = np.arange(length)[None, :]
+    m1 = ref[a[:, None] + cols].copy()
+    b = a + f - length
+    kind = rng.random(npairs)
+    disc = kind < 0.05
+    far = disc & (kind < 0.05 / 3)
+    out_of_range = disc & ~far & (kind < 0.1 / 3)
+    b[far] = rng.integers(0, L - length, int(far.sum()))
+    b[out_of_range] = a[out_of_range] + rng.integers(hi + 100, hi + 2000, int(out_of_range.sum()))
+    m2 = ref[b[:, None] + cols].copy()
+    same = disc & ~far & ~out_of_range
+    m2[~same] = COMP[m2[~same][:, ::-1]]
+    over = (kind >= 0.05) & (kind < 0.15)
+
+    def substitute(x, rows, k):
+        for _ in range(k):
+            col = rng.integers(0, length, rows.size)
+            x[rows, col] = LUT[(np.searchsorted(LUT, x[rows, col]) + rng.integers(1, 4, rows.size)) % 4]
+
+    for x, skip in ((m1, np.zeros(npairs, bool)), (m2, over)):  # 0..e substitutions (not on the mates set below)
+        for _ in range(e):
+            hit = np.flatnonzero((rng.random(npairs) < 0.7) & ~skip)
+            substitute(x, hit, 1)
+    heavy = np.flatnonzero(over)
+    extra = rng.integers(1, 4, heavy.size)
+    for k in range(1, 4):  # e + 1 .. e + 3 substitutions, two columns apart
+        rows = heavy[extra == k]
+        col = rng.integers(0, length - 8, rows.size)
+        for z in range(e + k):
+            cc = (col + 2 * z) % length
+            m2[rows, cc] = LUT[(np.searchsorted(LUT, m2[rows, cc]) + 1) % 4]
+    rnd = (kind >= 0.15) & (kind < 0.25)
+    m1[rnd] = LUT[rng.integers(0, 4, (int(rnd.sum()), length))]
+    m2[rnd] = LUT[rng.integers(0, 4, (int(rnd.sum()), length))]
+    swap = rng.random(npairs) < 0.5
+    m1[swap], m2[swap] = m2[swap].copy(), m1[swap].copy()
+    return m1, m2
+
+
+def run_paired(a, eng, tm, n, ref_len):
+    lib, h = eng.lib, eng.h
+    lo, hi = (int(v) for v in a.insert.split(","))
+    npairs = n // 2
+    results = {"ref_len": ref_len, "pairs": npairs, "read_len": a.len, "k": a.k, "repeats": a.repeats, "insert": [lo, hi],
+               "rescue": a.rescue, "runs": []}
+    for e in a.errors:
+        ref, _ = make_inputs(ref_len, 1, a.len, 0, seed=1000 + e, repeats=a.repeats)
+        m1, m2 = make_pairs(ref, npairs, a.len, e, lo, hi, seed=2000 + e, repeats=a.repeats)
+        off = np.array([0, ref_len], np.uint64)
+        ix = ctypes.c_void_p()
+        eng._chk(lib.asm_index_build(h, ref.ctypes.data, off.ctypes.data, 1, a.k, ctypes.byref(ix)))
+        f1, f2 = np.ascontiguousarray(m1.reshape(-1)), np.ascontiguousarray(m2.reshape(-1))
+        both = np.concatenate([f1, f2])
+        ro = (np.arange(npairs + 1, dtype=np.uint64) * a.len).astype(np.uint32)
+        ro2 = (np.arange(2 * npairs + 1, dtype=np.uint64) * a.len).astype(np.uint32)
+        p = m.MapParams(e, 1, 0, 3)
+        pp = m.PairParams(lo, hi, a.rescue)
+        hits = np.zeros(2 * npairs, m.MAP_HIT_DTYPE)
+        tlen = np.zeros(npairs, np.int32)
+        nconc = np.zeros(npairs, np.uint32)
+        ops = np.zeros(2 * npairs * 16, np.uint16)
+        nops = np.zeros(2 * npairs, np.uint8)
+        n_hits = np.zeros(2 * npairs, np.uint32)
+        all_hits = np.zeros(2 * npairs, m.MAP_HIT_DTYPE)
+        all_ops = np.zeros(2 * npairs * 16, np.uint16)
+        all_nops = np.zeros(2 * npairs, np.uint8)
+        best_pairs, best_all = 1e30, 1e30
+        for _ in range(a.reps):  # alternating, so that both calls see the same machine state
+            tm.start()
+            eng._chk(lib.asm_map_pairs(h, ix, npairs, f1.ctypes.data, ro.ctypes.data, f2.ctypes.data, ro.ctypes.data, ctypes.byref(p),
+                                       ctypes.byref(pp), hits.ctypes.data, tlen.ctypes.data, nconc.ctypes.data, ops.ctypes.data, 16,
+                                       nops.ctypes.data))
+            tm.stop()
+            best_pairs = min(best_pairs, tm.elapsed_ms())
+            tm.start()
+            eng._chk(lib.asm_map_reads_all(h, ix, 2 * npairs, both.ctypes.data, ro2.ctypes.data, ctypes.byref(p), e, 1,
+                                           n_hits.ctypes.data, all_hits.ctypes.data, all_ops.ctypes.data, 16, all_nops.ctypes.data))
+            tm.stop()
+            best_all = min(best_all, tm.elapsed_ms())
+        lib.asm_index_free(h, ix)
+        fl = hits["flags"].reshape(npairs, 2)
+        row = {"e": e, "pairs_ms_events": round(best_pairs, 3), "pairs_per_s": round(npairs / best_pairs * 1e3),
+               "all_hits1_ms_events": round(best_all, 3), "pairs_over_all_hits1": round(best_pairs / best_all, 3),
+               "proper_fraction": round(float(((fl[:, 0] & m.MAP_PROPER_PAIR) != 0).mean()), 4),
+               "rescued_fraction": round(float(((fl & m.MAP_RESCUED) != 0).any(axis=1).mean()), 4),
+               "mates_mapped_fraction": round(float(((fl & m.MAP_MAPPED) != 0).mean()), 4),
+               "n_concordant_gt1_fraction": round(float((nconc > 1).mean()), 4)}
+        results["runs"].append(row)
+        print(json.dumps(row))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "bench_map_paired.json"), "w") as fh:
             json.dump(results, fh, indent=1)
 
 
