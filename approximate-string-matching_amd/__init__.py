@@ -248,6 +248,8 @@ def load_library() -> ctypes.CDLL:
         "asm_map_reads": (i32, [vp, vp, i64, vp, vp, c.POINTER(MapParams), vp, vp, i32, vp]),
         "asm_map_reads_all": (i32, [vp, vp, i64, vp, vp, c.POINTER(MapParams), i32, i32, vp, vp, vp, i32, vp]),
         "asm_map_pairs": (i32, [vp, vp, i64, vp, vp, vp, vp, c.POINTER(MapParams), c.POINTER(PairParams), vp, vp, vp, vp, i32, vp]),
+        "asm_map_pairs_all": (i32, [vp, vp, i64, vp, vp, vp, vp, c.POINTER(MapParams), c.POINTER(PairParams), i32, i32, vp, vp, vp, vp,
+                                    vp, i32, vp]),
         "asm_device_malloc": (i32, [vp, c.c_size_t, c.POINTER(vp)]),
         "asm_device_free": (i32, [vp, vp]),
         "asm_memcpy_d2h": (i32, [vp, vp, vp, c.c_size_t]),
@@ -656,6 +658,60 @@ class Engine:
         out["tlen"], out["n_concordant"] = tlen, n_conc
         flat = decode_cigars(ops.reshape(2 * n, cap1), nops.reshape(2 * n), cigar_cap) if cigar_cap and n else [""] * (2 * n)
         out["cigar"] = [[flat[2 * t], flat[2 * t + 1]] for t in range(n)]
+        out["cigar_nops"] = nops
+        return out
+
+    def map_pairs_all(self, index: Index, reads1, reads2, max_errors: int, min_insert: int, max_insert: int, max_pairs: int = 16,
+                      strata: Optional[int] = None, rescue_errors: int = -1, max_occ: int = 0, greedy_k: int = 3, cigar_cap: int = 64,
+                      chunk: Optional[int] = None):
+        """asm_map_pairs_all: every concordant pair whose d sum is within strata of the best (docs/design/mapper.md, "Secondary
+        pairs"); strata=None means 2 * max_errors (all concordant pairs).  -> dict: the fields of map_pairs shaped (n, max_pairs, 2)
+        (rank, then mate 1 / mate 2): seq_id, pos, end, dist, strand, flags, greedy_cost, mapq, mapped, rescued, cigar_nops; per
+        pair and rank (n, max_pairs): proper, tlen; per pair: n_pairs (uncapped), n_reported (min(n_pairs, max_pairs)) and
+        n_concordant; `cigar`: n lists of max_pairs pairs of CIGAR strings.  Rank 0 is map_pairs' answer.  chunk: pairs per
+        library call (None: all in one)."""
+        p1 = [_as_bytes(r) for r in reads1]
+        p2 = [_as_bytes(r) for r in reads2]
+        if len(p1) != len(p2):
+            raise ValueError("reads1 and reads2 must hold the same number of mates")
+        n, P = len(p1), int(max_pairs)
+        strata = 2 * int(max_errors) if strata is None else int(strata)
+        p = MapParams(int(max_errors), 1, int(max_occ), int(greedy_k))
+        pp = PairParams(int(min_insert), int(max_insert), int(rescue_errors))
+        cap1 = max(cigar_cap, 1)
+        hits = np.zeros((n, P, 2), MAP_HIT_DTYPE)
+        tlen = np.zeros((n, P), np.int32)
+        n_pairs = np.zeros(n, np.uint32)
+        n_conc = np.zeros(n, np.uint32)
+        ops = np.zeros((n, P, 2, cap1), np.uint16)
+        nops = np.zeros((n, P, 2), np.uint8)
+        step = chunk if chunk else max(n, 1)
+        for lo in range(0, n, step):
+            hi = min(n, lo + step)
+            b1, o1 = pack_sequences(p1[lo:hi])
+            b2, o2 = pack_sequences(p2[lo:hi])
+            ro1, ro2 = o1.astype(np.uint32), o2.astype(np.uint32)
+            sub = np.zeros((hi - lo, P, 2), MAP_HIT_DTYPE)
+            stl = np.zeros((hi - lo, P), np.int32)
+            snp = np.zeros(hi - lo, np.uint32)
+            snc = np.zeros(hi - lo, np.uint32)
+            sops = np.zeros((hi - lo, P, 2, cap1), np.uint16)
+            snops = np.zeros((hi - lo, P, 2), np.uint8)
+            self._chk(self.lib.asm_map_pairs_all(self.h, index.ptr, hi - lo, b1.ctypes.data if b1.size else None, ro1.ctypes.data,
+                                                 b2.ctypes.data if b2.size else None, ro2.ctypes.data, ctypes.byref(p), ctypes.byref(pp),
+                                                 strata, P, snp.ctypes.data, sub.ctypes.data, stl.ctypes.data, snc.ctypes.data,
+                                                 sops.ctypes.data if cigar_cap else None, int(cigar_cap),
+                                                 snops.ctypes.data if cigar_cap else None))
+            hits[lo:hi], tlen[lo:hi], n_pairs[lo:hi], n_conc[lo:hi], ops[lo:hi], nops[lo:hi] = sub, stl, snp, snc, sops, snops
+        out = {name: hits[name].copy() for name in MAP_HIT_DTYPE.names}
+        out["mapped"] = (hits["flags"] & MAP_MAPPED) != 0
+        out["rescued"] = (hits["flags"] & MAP_RESCUED) != 0
+        out["mapq"] = np.where(out["mapped"], np.minimum(254, 60 + hits["greedy_cost"].astype(np.int64)), 255).astype(np.int32)
+        out["proper"] = (hits["flags"][:, :, 0] & MAP_PROPER_PAIR) != 0
+        out["tlen"], out["n_pairs"], out["n_concordant"] = tlen, n_pairs, n_conc
+        out["n_reported"] = np.minimum(n_pairs, P).astype(np.int64)
+        flat = decode_cigars(ops.reshape(2 * n * P, cap1), nops.reshape(2 * n * P), cigar_cap) if cigar_cap and n else [""] * (2 * n * P)
+        out["cigar"] = [[[flat[2 * (t * P + k)], flat[2 * (t * P + k) + 1]] for k in range(P)] for t in range(n)]
         out["cigar_nops"] = nops
         return out
 

@@ -2900,75 +2900,94 @@ int asm_map_reads_all(asm_handle* h, const asm_index* ix, int64_t n, const char*
     return ASM_OK;
 }
 
-/* asm_map_pairs on one chunk of np pairs (mate 1 of pair p = read p, mate 2 = read np + p): the sorted run records, each read's loci
- * listed (count, scan, emit), the pairing, the rescue of pairs without a concordant pair, then finish and Greedy on the identity
- * list (one item per read) */
-static int map_chunk_pairs(asm_handle* h, const asm_index* ix, int64_t np, const char* reads1, const uint32_t* off1,
+/* asm_map_pairs' front on one chunk of np pairs (mate 1 of pair p = read p, mate 2 = read np + p): the sorted run records, each
+ * read's loci listed (count, scan, emit), the pairing and the rescue of pairs without a concordant pair.  asm_map_pairs_all shares it. */
+struct MapPairFront {
+    MapFront f;
+    MapRuns runs;
+    Scratch<uint32_t> d_nh, d_dbest, d_lbase, d_lsplit, d_nconc, d_anchors, d_nanch;
+    Scratch<unsigned long long> d_lkey, d_lbest, d_ikey, d_rslot;
+    Scratch<uint8_t> d_state;
+    Scratch<void> tmp;
+    MapPairArgs pa = {};
+    explicit MapPairFront(asm_handle* h)
+        : f(h), runs(h), d_nh(h), d_dbest(h), d_lbase(h), d_lsplit(h), d_nconc(h), d_anchors(h), d_nanch(h), d_lkey(h), d_lbest(h),
+          d_ikey(h), d_rslot(h), d_state(h), tmp(h) {}
+};
+
+static int map_pairs_front(asm_handle* h, const asm_index* ix, int64_t np, const char* reads1, const uint32_t* off1,
                            const char* reads2, const uint32_t* off2, const asm_map_params* p, const asm_pair_params* pp,
-                           asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant, uint16_t* cigar_ops, int cigar_cap,
-                           uint8_t* cigar_nops) {
+                           const char* who, MapPairFront& pf) {
     const int64_t n = 2 * np;
-    MapFront f(h);
+    MapFront& f = pf.f;
     const MapReadsIn in[2] = {{reads1, off1, np}, {reads2, off2, np}};
     if (const int rc = map_front(h, ix, in, 2, p, f)) return rc;
     const int e = p->max_errors;
-    MapRuns runs(h);
-    if (const int rc = map_runs(h, ix, n, p, f, runs, "asm_map_pairs")) return rc;
+    MapRuns& runs = pf.runs;
+    if (const int rc = map_runs(h, ix, n, p, f, runs, who)) return rc;
     /* each read's loci (strata = e: all of them), listed in walk order */
-    Scratch<uint32_t> d_nh(h), d_dbest(h), d_lbase(h), d_lsplit(h), d_nconc(h), d_anchors(h), d_nanch(h), d_list(h);
-    Scratch<unsigned long long> d_lkey(h), d_lbest(h), d_ikey(h), d_rslot(h);
-    Scratch<uint8_t> d_state(h);
-    Scratch<void> tmp(h);
-    HIPCHK(h, d_nh.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
-    HIPCHK(h, d_dbest.alloc(sizeof(uint32_t) * (size_t)n));
-    HIPCHK(h, d_lbase.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
+    HIPCHK(h, pf.d_nh.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
+    HIPCHK(h, pf.d_dbest.alloc(sizeof(uint32_t) * (size_t)n));
+    HIPCHK(h, pf.d_lbase.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
     MapSelectArgs sel = {};
     sel.rkey = runs.key.p, sel.rval = runs.val.p, sel.nr = runs.nr, sel.n = (long)n, sel.e = e, sel.strata = e, sel.max_hits = 1;
     sel.seq_off = (const unsigned long long*)ix->d_seq_off, sel.n_seqs = (uint32_t)ix->n_seqs, sel.roff = f.d_roff.p;
-    sel.n_hits = d_nh.p, sel.d_best = d_dbest.p;
-    HIPCHK(h, hipMemsetAsync(d_nh.p + n, 0, sizeof(uint32_t), h->stream));
+    sel.n_hits = pf.d_nh.p, sel.d_best = pf.d_dbest.p;
+    HIPCHK(h, hipMemsetAsync(pf.d_nh.p + n, 0, sizeof(uint32_t), h->stream));
     hipLaunchKernelGGL(map_select_count_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel);
     HIPCHK(h, hipGetLastError());
     size_t tmp_bytes = 0;
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_nh.p, d_lbase.p, (int)(n + 1), h->stream));
-    HIPCHK(h, tmp.alloc(tmp_bytes + 16));
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, d_nh.p, d_lbase.p, (int)(n + 1), h->stream));
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, pf.d_nh.p, pf.d_lbase.p, (int)(n + 1), h->stream));
+    HIPCHK(h, pf.tmp.alloc(tmp_bytes + 16));
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(pf.tmp.p, tmp_bytes, pf.d_nh.p, pf.d_lbase.p, (int)(n + 1), h->stream));
     uint32_t nloci = 0;
-    HIPCHK(h, hipMemcpyAsync(&nloci, d_lbase.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&nloci, pf.d_lbase.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, d_lkey.alloc(sizeof(unsigned long long) * ((size_t)nloci + 1)));
-    HIPCHK(h, d_lsplit.alloc(sizeof(uint32_t) * (size_t)n));
-    HIPCHK(h, d_lbest.alloc(sizeof(unsigned long long) * (size_t)n));
-    hipLaunchKernelGGL(map_loci_emit_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel, (const uint32_t*)d_lbase.p,
-                       d_lkey.p, d_lsplit.p, d_lbest.p);
+    HIPCHK(h, pf.d_lkey.alloc(sizeof(unsigned long long) * ((size_t)nloci + 1)));
+    HIPCHK(h, pf.d_lsplit.alloc(sizeof(uint32_t) * (size_t)n));
+    HIPCHK(h, pf.d_lbest.alloc(sizeof(unsigned long long) * (size_t)n));
+    hipLaunchKernelGGL(map_loci_emit_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel, (const uint32_t*)pf.d_lbase.p,
+                       pf.d_lkey.p, pf.d_lsplit.p, pf.d_lbest.p);
     HIPCHK(h, hipGetLastError());
     /* pairing */
-    HIPCHK(h, d_ikey.alloc(sizeof(unsigned long long) * (size_t)n));
-    HIPCHK(h, d_nconc.alloc(sizeof(uint32_t) * (size_t)np));
-    HIPCHK(h, d_state.alloc((size_t)np));
-    HIPCHK(h, d_nanch.alloc(sizeof(uint32_t)));
-    HIPCHK(h, hipMemsetAsync(d_nanch.p, 0, sizeof(uint32_t), h->stream));
+    HIPCHK(h, pf.d_ikey.alloc(sizeof(unsigned long long) * (size_t)n));
+    HIPCHK(h, pf.d_nconc.alloc(sizeof(uint32_t) * (size_t)np));
+    HIPCHK(h, pf.d_state.alloc((size_t)np));
+    HIPCHK(h, pf.d_nanch.alloc(sizeof(uint32_t)));
+    HIPCHK(h, hipMemsetAsync(pf.d_nanch.p, 0, sizeof(uint32_t), h->stream));
     const bool rescue = pp->rescue_errors >= 0;
     if (rescue) {
-        HIPCHK(h, d_anchors.alloc(sizeof(uint32_t) * (size_t)n));
-        HIPCHK(h, d_rslot.alloc(sizeof(unsigned long long) * (size_t)n));
-        HIPCHK(h, hipMemsetAsync(d_rslot.p, 0xff, sizeof(unsigned long long) * (size_t)n, h->stream));
+        HIPCHK(h, pf.d_anchors.alloc(sizeof(uint32_t) * (size_t)n));
+        HIPCHK(h, pf.d_rslot.alloc(sizeof(unsigned long long) * (size_t)n));
+        HIPCHK(h, hipMemsetAsync(pf.d_rslot.p, 0xff, sizeof(unsigned long long) * (size_t)n, h->stream));
     }
-    MapPairArgs pa = {};
-    pa.np = (long)np, pa.roff = f.d_roff.p, pa.lbase = d_lbase.p, pa.lsplit = d_lsplit.p, pa.lbest = d_lbest.p, pa.lkey = d_lkey.p;
-    pa.min_insert = pp->min_insert, pa.max_insert = pp->max_insert, pa.rescue = pp->rescue_errors;
-    pa.ikey = d_ikey.p, pa.n_conc = d_nconc.p, pa.state = d_state.p, pa.anchors = d_anchors.p, pa.n_anchors = d_nanch.p;
-    pa.rslot = d_rslot.p, pa.seq_off = (const unsigned long long*)ix->d_seq_off;
+    MapPairArgs& pa = pf.pa;
+    pa.np = (long)np, pa.roff = f.d_roff.p, pa.lbase = pf.d_lbase.p, pa.lsplit = pf.d_lsplit.p, pa.lbest = pf.d_lbest.p;
+    pa.lkey = pf.d_lkey.p, pa.min_insert = pp->min_insert, pa.max_insert = pp->max_insert, pa.rescue = pp->rescue_errors;
+    pa.ikey = pf.d_ikey.p, pa.n_conc = pf.d_nconc.p, pa.state = pf.d_state.p, pa.anchors = pf.d_anchors.p, pa.n_anchors = pf.d_nanch.p;
+    pa.rslot = pf.d_rslot.p, pa.seq_off = (const unsigned long long*)ix->d_seq_off;
     hipLaunchKernelGGL(map_pair_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, pa);
     HIPCHK(h, hipGetLastError());
     if (rescue) {
         const uint32_t ntile = (uint32_t)((pp->max_insert - pp->min_insert + MAP_RESCUE_TILE) / MAP_RESCUE_TILE);
-        HIPCHK(h, map_dispatch_rescue(h, f.maxm, pa, f.d_reads.p, ix, ntile, d_rslot.p));
+        HIPCHK(h, map_dispatch_rescue(h, f.maxm, pa, f.d_reads.p, ix, ntile, pf.d_rslot.p));
         hipLaunchKernelGGL(map_rescue_pick_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, pa);
         HIPCHK(h, hipGetLastError());
     }
-    /* finish and Greedy: item i = read i */
+    return ASM_OK;
+}
+
+/* asm_map_pairs' answer after map_pairs_front: finish and Greedy on the identity list (one item per read), then pair q's two records
+ * into out[2 q slots + 0, 1] with the pair flags, tlen[q slots], n_concordant[q] and the CIGAR rows of those records (slots:
+ * records per mate and pair in the caller's arrays, 1 for asm_map_pairs) */
+static int map_pairs_primary(asm_handle* h, const asm_index* ix, int64_t np, const asm_map_params* p, MapPairFront& pf, int slots,
+                             asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant, uint16_t* cigar_ops, int cigar_cap,
+                             uint8_t* cigar_nops) {
+    const int64_t n = 2 * np;
+    const int e = p->max_errors;
+    MapFront& f = pf.f;
     const int ocap = cigar_cap > 0 ? cigar_cap : 0;
+    Scratch<uint32_t> d_list(h);
     Scratch<uint64_t> d_dirs(h);
     Scratch<MapHit> d_hits(h);
     Scratch<uint16_t> d_ops(h);
@@ -2980,15 +2999,15 @@ static int map_chunk_pairs(asm_handle* h, const asm_index* ix, int64_t np, const
     HIPCHK(h, d_nops.alloc((size_t)n));
     MapFinishArgs fa = {};
     fa.reads = f.d_reads.p, fa.roff = f.d_roff.p, fa.n = (long)n, fa.e = e, fa.P = e + 1, fa.k = ix->k, fa.cap = ocap;
-    fa.text = ix->d_text, fa.seq_off = (const unsigned long long*)ix->d_seq_off, fa.keys = d_ikey.p, fa.flags = f.d_flags.p;
+    fa.text = ix->d_text, fa.seq_off = (const unsigned long long*)ix->d_seq_off, fa.keys = pf.d_ikey.p, fa.flags = f.d_flags.p;
     fa.iread = nullptr, fa.idirs = nullptr, fa.dirs = d_dirs.p, fa.hits = d_hits.p, fa.ops = d_ops.p, fa.nops = d_nops.p;
     HIPCHK(h, map_dispatch(h, f.maxm, true, nullptr, 0, f.d_reads.p, f.d_roff.p, ix, e, nullptr, fa));
     std::vector<asm_map_hit> hits((size_t)n);
     std::vector<uint16_t> ops((size_t)n * ocap);
     std::vector<uint8_t> nops((size_t)n), state((size_t)np);
     HIPCHK(h, hipMemcpyAsync(hits.data(), d_hits.p, sizeof(MapHit) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(state.data(), d_state.p, (size_t)np, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(n_concordant, d_nconc.p, sizeof(uint32_t) * (size_t)np, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(state.data(), pf.d_state.p, (size_t)np, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(n_concordant, pf.d_nconc.p, sizeof(uint32_t) * (size_t)np, hipMemcpyDeviceToHost, h->stream));
     if (ocap) {
         HIPCHK(h, hipMemcpyAsync(ops.data(), d_ops.p, sizeof(uint16_t) * (size_t)n * ocap, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(nops.data(), d_nops.p, (size_t)n, hipMemcpyDeviceToHost, h->stream));
@@ -3013,9 +3032,10 @@ static int map_chunk_pairs(asm_handle* h, const asm_index* ix, int64_t np, const
         HIPCHK(h, hipStreamSynchronize(h->stream));
         for (int64_t q = 0; q < nl; q++) hits[list[(size_t)q]].greedy_cost = cost[(size_t)q];
     }
-    /* into the caller's [np][2] records; the pair flags and tlen are set here */
+    /* into the caller's records; the pair flags and tlen are set here */
     for (int64_t q = 0; q < np; q++) {
-        asm_map_hit* o = out + 2 * q;
+        const size_t r0 = (size_t)(2 * q) * slots; /* pair q's first record */
+        asm_map_hit* o = out + r0;
         o[0] = hits[(size_t)q], o[1] = hits[(size_t)(np + q)];
         const uint8_t st = state[(size_t)q];
         if (st == MAP_PAIR_CONCORDANT || st == MAP_PAIR_RESCUED1 || st == MAP_PAIR_RESCUED2) {
@@ -3024,15 +3044,25 @@ static int map_chunk_pairs(asm_handle* h, const asm_index* ix, int64_t np, const
             if (st == MAP_PAIR_RESCUED2) o[1].flags |= ASM_MAP_RESCUED;
         }
         const bool same = (o[0].flags & ASM_MAP_MAPPED) && (o[1].flags & ASM_MAP_MAPPED) && o[0].seq_id == o[1].seq_id;
-        tlen[q] = same ? (int32_t)(std::max(o[0].end, o[1].end) - std::min(o[0].pos, o[1].pos)) : 0;
+        tlen[(size_t)q * slots] = same ? (int32_t)(std::max(o[0].end, o[1].end) - std::min(o[0].pos, o[1].pos)) : 0;
         if (ocap)
             for (int t = 0; t < 2; t++) {
                 const size_t i = (size_t)(t ? np + q : q);
-                std::copy(ops.begin() + i * ocap, ops.begin() + (i + 1) * ocap, cigar_ops + ((size_t)(2 * q + t)) * ocap);
-                cigar_nops[2 * q + t] = nops[i];
+                std::copy(ops.begin() + i * ocap, ops.begin() + (i + 1) * ocap, cigar_ops + (r0 + t) * ocap);
+                cigar_nops[r0 + t] = nops[i];
             }
     }
     return ASM_OK;
+}
+
+/* asm_map_pairs on one chunk of np pairs: the front, then finish and Greedy on the identity list */
+static int map_chunk_pairs(asm_handle* h, const asm_index* ix, int64_t np, const char* reads1, const uint32_t* off1,
+                           const char* reads2, const uint32_t* off2, const asm_map_params* p, const asm_pair_params* pp,
+                           asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant, uint16_t* cigar_ops, int cigar_cap,
+                           uint8_t* cigar_nops) {
+    MapPairFront pf(h);
+    if (const int rc = map_pairs_front(h, ix, np, reads1, off1, reads2, off2, p, pp, "asm_map_pairs", pf)) return rc;
+    return map_pairs_primary(h, ix, np, p, pf, 1, out, tlen, n_concordant, cigar_ops, cigar_cap, cigar_nops);
 }
 
 int asm_map_pairs(asm_handle* h, const asm_index* ix, int64_t n, const char* reads1, const uint32_t* off1, const char* reads2,
@@ -3069,6 +3099,188 @@ int asm_map_pairs(asm_handle* h, const asm_index* ix, int64_t n, const char* rea
         const int rc = map_chunk_pairs(h, ix, c1 - c0, reads1, off1 + c0, reads2, off2 + c0, p, pp, out + o, tlen + c0, n_concordant + c0,
                                        cigar_cap > 0 ? cigar_ops + o * cigar_cap : nullptr, cigar_cap,
                                        cigar_cap > 0 ? cigar_nops + o : nullptr);
+        if (rc) return rc;
+    }
+    return ASM_OK;
+}
+
+/* asm_map_pairs_all on one chunk of np pairs: the front and the primary answer of asm_map_pairs (rank 0), then the eligible pairs
+ * counted, ranks >= 1 listed as items (mate 1, mate 2 per pair) in pair order, their finish and Greedy, and the scatter into the
+ * caller's [np][max_pairs][2] slots.  The slots beyond rank 0 are first filled as unused on host threads, while the device works. */
+static int map_chunk_pairs_all(asm_handle* h, const asm_index* ix, int64_t np, const char* reads1, const uint32_t* off1,
+                               const char* reads2, const uint32_t* off2, const asm_map_params* p, const asm_pair_params* pp, int strata,
+                               int max_pairs, uint32_t* n_pairs, asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant,
+                               uint16_t* cigar_ops, int cigar_cap, uint8_t* cigar_nops) {
+    const int e = p->max_errors, ocap = cigar_cap > 0 ? cigar_cap : 0;
+    const asm_map_hit unused = {-1, 0, 0, -1, 0, 0, -1};
+    std::vector<std::thread> fill;
+    if (max_pairs > 1) {
+        const int64_t nt = std::min<int64_t>(4, std::max<int64_t>(1, np / 4096));
+        for (int64_t t = 0; t < nt; t++)
+            fill.emplace_back([=]() {
+                for (int64_t q = np * t / nt; q < np * (t + 1) / nt; q++) {
+                    const size_t o = (size_t)q * max_pairs;
+                    std::fill(out + 2 * (o + 1), out + 2 * (o + max_pairs), unused);
+                    std::fill(tlen + o + 1, tlen + o + max_pairs, 0);
+                    if (ocap) std::fill(cigar_nops + 2 * (o + 1), cigar_nops + 2 * (o + max_pairs), (uint8_t)0);
+                }
+            });
+    }
+    struct Join {
+        std::vector<std::thread>& t;
+        ~Join() {
+            for (std::thread& x : t) x.join();
+        }
+    } join{fill};
+    MapPairFront pf(h);
+    if (const int rc = map_pairs_front(h, ix, np, reads1, off1, reads2, off2, p, pp, "asm_map_pairs_all", pf)) return rc;
+    MapFront& f = pf.f;
+    /* eligible pairs per pair, and the layout of the secondary items (device scans) */
+    Scratch<uint32_t> d_np(h), d_sums(h), d_iread(h), d_list(h);
+    Scratch<unsigned long long> d_nitem(h), d_ndirs(h), d_ibase(h), d_dbase(h), d_ikey(h), d_idirs(h);
+    Scratch<void> tmp(h);
+    HIPCHK(h, d_np.alloc(sizeof(uint32_t) * (size_t)np));
+    HIPCHK(h, d_sums.alloc(sizeof(uint32_t) * (size_t)np));
+    for (Scratch<unsigned long long>* x : {&d_nitem, &d_ndirs, &d_ibase, &d_dbase})
+        HIPCHK(h, x->alloc(sizeof(unsigned long long) * ((size_t)np + 1)));
+    HIPCHK(h, hipMemsetAsync(d_nitem.p + np, 0, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(d_ndirs.p + np, 0, sizeof(unsigned long long), h->stream));
+    MapPairAllArgs aa = {};
+    aa.pa = pf.pa, aa.strata = strata, aa.max_pairs = max_pairs, aa.n_pairs = d_np.p, aa.sums = d_sums.p, aa.nitem = d_nitem.p;
+    aa.ndirs = d_ndirs.p, aa.ibase = d_ibase.p, aa.dbase = d_dbase.p;
+    hipLaunchKernelGGL(map_pair_count_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, aa);
+    HIPCHK(h, hipGetLastError());
+    size_t tmp_bytes = 0;
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_nitem.p, d_ibase.p, (int)(np + 1), h->stream));
+    HIPCHK(h, tmp.alloc(tmp_bytes + 16));
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, d_nitem.p, d_ibase.p, (int)(np + 1), h->stream));
+    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, d_ndirs.p, d_dbase.p, (int)(np + 1), h->stream));
+    unsigned long long tot[2] = {0, 0};
+    HIPCHK(h, hipMemcpyAsync(n_pairs, d_np.p, sizeof(uint32_t) * (size_t)np, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&tot[0], d_ibase.p + np, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&tot[1], d_dbase.p + np, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const int64_t ni = (int64_t)tot[0];
+    /* ranks >= 1: items, finish (the item-list instantiation of asm_map_reads_all) */
+    Scratch<uint64_t> d_dirs(h);
+    Scratch<MapHit> d_hits(h);
+    Scratch<uint16_t> d_ops(h);
+    Scratch<uint8_t> d_nops(h);
+    Scratch<int32_t> d_cost(h);
+    if (ni) {
+        HIPCHK(h, d_iread.alloc(sizeof(uint32_t) * (size_t)ni));
+        HIPCHK(h, d_ikey.alloc(sizeof(unsigned long long) * (size_t)ni));
+        HIPCHK(h, d_idirs.alloc(sizeof(unsigned long long) * (size_t)ni));
+        HIPCHK(h, d_dirs.alloc(sizeof(uint64_t) * tot[1]));
+        HIPCHK(h, d_hits.alloc(sizeof(MapHit) * (size_t)ni));
+        HIPCHK(h, d_ops.alloc(sizeof(uint16_t) * ((size_t)ni * ocap + 1)));
+        HIPCHK(h, d_nops.alloc((size_t)ni));
+        aa.iread = d_iread.p, aa.ikey = d_ikey.p, aa.idirs = d_idirs.p;
+        hipLaunchKernelGGL(map_pair_emit_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, aa);
+        HIPCHK(h, hipGetLastError());
+        MapFinishArgs fa = {};
+        fa.reads = f.d_reads.p, fa.roff = f.d_roff.p, fa.n = (long)ni, fa.e = e, fa.P = e + 1, fa.k = ix->k, fa.cap = ocap;
+        fa.text = ix->d_text, fa.seq_off = (const unsigned long long*)ix->d_seq_off, fa.keys = d_ikey.p, fa.flags = f.d_flags.p;
+        fa.iread = d_iread.p, fa.idirs = d_idirs.p, fa.dirs = d_dirs.p, fa.hits = d_hits.p, fa.ops = d_ops.p, fa.nops = d_nops.p;
+        HIPCHK(h, map_dispatch(h, f.maxm, true, nullptr, 0, f.d_reads.p, f.d_roff.p, ix, e, nullptr, fa));
+    }
+    /* rank 0: asm_map_pairs' answer */
+    if (const int rc = map_pairs_primary(h, ix, np, p, pf, max_pairs, out, tlen, n_concordant, cigar_ops, cigar_cap, cigar_nops))
+        return rc;
+    for (int64_t q = 0; q < np; q++)
+        if (n_pairs[q] > (uint32_t)max_pairs) {
+            out[(size_t)q * 2 * max_pairs].flags |= ASM_MAP_HITS_TRUNCATED;
+            out[(size_t)q * 2 * max_pairs + 1].flags |= ASM_MAP_HITS_TRUNCATED;
+        }
+    for (std::thread& x : fill) x.join();
+    fill.clear();
+    if (!ni) return ASM_OK;
+    std::vector<asm_map_hit> hits((size_t)ni);
+    std::vector<uint16_t> ops((size_t)ni * ocap);
+    std::vector<uint8_t> nops((size_t)ni);
+    HIPCHK(h, hipMemcpyAsync(hits.data(), d_hits.p, sizeof(MapHit) * (size_t)ni, hipMemcpyDeviceToHost, h->stream));
+    if (ocap) {
+        HIPCHK(h, hipMemcpyAsync(ops.data(), d_ops.p, sizeof(uint16_t) * (size_t)ni * ocap, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(nops.data(), d_nops.p, (size_t)ni, hipMemcpyDeviceToHost, h->stream));
+    }
+    /* Greedy on every secondary item (all are mapped), in item order */
+    std::vector<uint32_t> list((size_t)ni);
+    int maxmap = 0;
+    for (int64_t q = 0; q < np; q++)
+        if (n_pairs[q] >= 2)
+            maxmap = std::max(maxmap, (int)std::max(f.roff[(size_t)q + 1] - f.roff[(size_t)q],
+                                                    f.roff[(size_t)(np + q) + 1] - f.roff[(size_t)(np + q)]));
+    for (int64_t q = 0; q < ni; q++) list[(size_t)q] = (uint32_t)q;
+    HIPCHK(h, d_list.alloc(sizeof(uint32_t) * (size_t)ni));
+    HIPCHK(h, d_cost.alloc(sizeof(int32_t) * (size_t)ni));
+    HIPCHK(h, hipMemcpyAsync(d_list.p, list.data(), sizeof(uint32_t) * (size_t)ni, hipMemcpyHostToDevice, h->stream));
+    if (const int rc = map_greedy(h, ix, f.d_reads.p, f.d_roff.p, d_hits.p, d_iread.p, d_list.p, ni, maxmap, p->greedy_k, d_cost.p))
+        return rc;
+    std::vector<int32_t> cost((size_t)ni);
+    HIPCHK(h, hipMemcpyAsync(cost.data(), d_cost.p, sizeof(int32_t) * (size_t)ni, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    /* into the caller's slots: items 2 (t - 1) and 2 (t - 1) + 1 of a pair are rank t's mates 1 and 2 */
+    size_t it = 0;
+    for (int64_t q = 0; q < np; q++) {
+        const uint32_t want = std::min<uint32_t>(n_pairs[q], (uint32_t)max_pairs);
+        const uint8_t extra = ASM_MAP_PROPER_PAIR | ASM_MAP_SECONDARY | (n_pairs[q] > (uint32_t)max_pairs ? ASM_MAP_HITS_TRUNCATED : 0);
+        for (uint32_t t = 1; t < want; t++, it += 2) {
+            const size_t o = ((size_t)q * max_pairs + t) * 2;
+            for (int x = 0; x < 2; x++) {
+                out[o + x] = hits[it + x];
+                out[o + x].greedy_cost = cost[it + x];
+                out[o + x].flags |= extra;
+                if (ocap) {
+                    std::copy(ops.begin() + (it + x) * ocap, ops.begin() + (it + x + 1) * ocap, cigar_ops + (o + x) * ocap);
+                    cigar_nops[o + x] = nops[it + x];
+                }
+            }
+            tlen[(size_t)q * max_pairs + t] =
+                (int32_t)(std::max(out[o].end, out[o + 1].end) - std::min(out[o].pos, out[o + 1].pos));
+        }
+    }
+    return ASM_OK;
+}
+
+int asm_map_pairs_all(asm_handle* h, const asm_index* ix, int64_t n, const char* reads1, const uint32_t* off1, const char* reads2,
+                      const uint32_t* off2, const asm_map_params* p, const asm_pair_params* pp, int strata, int max_pairs,
+                      uint32_t* n_pairs, asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant, uint16_t* cigar_ops, int cigar_cap,
+                      uint8_t* cigar_nops) {
+    if (!p || !pp || !ix || n < 0 || !off1 || !off2 || (n > 0 && (!reads1 || !reads2 || !out || !tlen || !n_concordant)))
+        return fail(h, ASM_EINVAL, "asm_map_pairs_all: bad arguments");
+    if (n > 0 && !n_pairs) return fail(h, ASM_EINVAL, "asm_map_pairs_all: n_pairs is NULL");
+    if (p->max_errors < 0 || p->max_errors > ASM_MAP_MAX_ERRORS)
+        return fail(h, ASM_EINVAL, "asm_map_pairs_all: max_errors must be in [0, 15]");
+    if (p->both_strands != 1) return fail(h, ASM_EINVAL, "asm_map_pairs_all: both_strands must be 1");
+    if (p->max_occ < 0) return fail(h, ASM_EINVAL, "asm_map_pairs_all: max_occ must be >= 0");
+    if (p->greedy_k < 0 || p->greedy_k > ASM_GREEDY_MAX_K) return fail(h, ASM_EINVAL, "asm_map_pairs_all: greedy_k must be in [0, 50]");
+    if (pp->min_insert < 0 || pp->min_insert > pp->max_insert || pp->max_insert > ASM_MAP_MAX_INSERT)
+        return fail(h, ASM_EINVAL, "asm_map_pairs_all: need 0 <= min_insert <= max_insert <= 8192");
+    if (pp->rescue_errors < -1 || pp->rescue_errors > ASM_MAP_MAX_ERRORS)
+        return fail(h, ASM_EINVAL, "asm_map_pairs_all: rescue_errors must be -1 (off) or in [0, 15]");
+    if (strata < 0 || strata > 2 * ASM_MAP_MAX_ERRORS) return fail(h, ASM_EINVAL, "asm_map_pairs_all: strata must be in [0, 30]");
+    if (max_pairs < 1 || max_pairs > ASM_MAP_MAX_HITS) return fail(h, ASM_EINVAL, "asm_map_pairs_all: max_pairs must be in [1, 256]");
+    if (cigar_cap < 0 || (cigar_cap > 0 && (!cigar_ops || !cigar_nops)))
+        return fail(h, ASM_EINVAL, "asm_map_pairs_all: cigar_cap > 0 needs cigar_ops and cigar_nops");
+    for (const uint32_t* ro : {off1, off2})
+        for (int64_t i = 0; i < n; i++) {
+            if (ro[i + 1] < ro[i]) return fail(h, ASM_EINVAL, "asm_map_pairs_all: read offsets must be non-decreasing");
+            const uint32_t m = ro[i + 1] - ro[i];
+            if (m < 1 || m > ASM_MAP_MAX_READ) return fail(h, ASM_EINVAL, "asm_map_pairs_all: every mate must have 1 to 511 bytes");
+        }
+    if (n > 0 && (uint64_t)(off1[n] - off1[0]) + (off2[n] - off2[0]) >= 0xffffffffull)
+        return fail(h, ASM_EUNSUPPORTED, "asm_map_pairs_all: both mates' bytes must stay below 2^32");
+    if (!h) return fail(h, ASM_EINVAL, "asm_map_pairs_all: NULL handle");
+    if (ix->device != h->device) return fail(h, ASM_EINVAL, "asm_map_pairs_all: the index lives on another device");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int64_t step = std::max<int64_t>(1, std::min<int64_t>(h->map_chunk, (int64_t)1 << 30) / 2); /* as asm_map_pairs */
+    for (int64_t c0 = 0; c0 < n; c0 += step) {
+        const int64_t c1 = std::min(n, c0 + step);
+        const size_t o = (size_t)c0 * max_pairs * 2;
+        const int rc = map_chunk_pairs_all(h, ix, c1 - c0, reads1, off1 + c0, reads2, off2 + c0, p, pp, strata, max_pairs, n_pairs + c0,
+                                           out + o, tlen + (size_t)c0 * max_pairs, n_concordant + c0,
+                                           cigar_cap > 0 ? cigar_ops + o * cigar_cap : nullptr, cigar_cap,
+                                           cigar_cap > 0 ? cigar_nops + o : nullptr);
         if (rc) return rc;
     }
     return ASM_OK;

@@ -21,6 +21,9 @@
 //          picks the best concordant pair per pair with two pointers over the mates' lists, map_rescue_kernel<W> searches a mapped
 //          mate's insert window for its partner (tiles of ends, 64-bit atomicMin per anchor), map_rescue_pick_kernel keeps the
 //          better rescued pair, and the finish and Greedy run on one item per read.
+// Secondary pairs (asm_map_pairs_all): the front of asm_map_pairs unchanged, then map_pair_count_kernel counts each pair's eligible
+//          concordant pairs, a scan lays out their items, map_pair_emit_kernel lists ranks >= 1 in pair order, and the items' finish
+//          and Greedy run as for all hits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -655,6 +658,108 @@ __global__ __launch_bounds__(256) void map_rescue_pick_kernel(MapPairArgs a) {
         }
         a.ikey[who] = key;
         a.state[p] = (uint8_t)(who == A ? MAP_PAIR_RESCUED1 : MAP_PAIR_RESCUED2);
+    }
+}
+
+/* ---- secondary pairs (asm_map_pairs_all) -----------------------------------------------------------------------------------------
+ * The eligible pairs of pair p are its concordant combinations with d_A + d_B <= sum_best + strata.  In pair order they come, per d
+ * sum, as the s_A = 0 half and then the s_A = 1 half, each in (r, j_A, j_B) order; map_pair_walk lists either half in that order. */
+struct MapPairAllArgs {
+    MapPairArgs pa;                   /* the pairing's loci lists, item keys and states */
+    int strata, max_pairs;
+    uint32_t* n_pairs;                /* per pair: eligible pairs (uncapped, saturating) */
+    uint32_t* sums;                   /* per pair: bit s set when an eligible pair has d sum s (s <= 30) */
+    unsigned long long* nitem;        /* np + 1: secondary items per pair, 2 (min(n_pairs, max_pairs) - 1) */
+    unsigned long long* ndirs;        /* np + 1: their dirs words, (m_A + 1) + (m_B + 1) per secondary pair */
+    const unsigned long long* ibase;  /* np: exclusive scan of nitem */
+    const unsigned long long* dbase;  /* np: exclusive scan of ndirs */
+    uint32_t* iread;                  /* per secondary item: its read */
+    unsigned long long* ikey;         /* per secondary item: its locus key */
+    unsigned long long* idirs;        /* per secondary item: its dirs offset */
+};
+
+/* For each key kA of [f0, f1) (one mate's loci of one strand, (r, j) order), the keys kB of [g0, g1) (the other mate's loci of the
+ * other strand) with the same r and j_B in [j_A + clo, j_A + chi], in (r, j_B) order: a window that only moves forward.  fn(kA, kB)
+ * returns false to stop; then so does the walk (returns false). */
+template <class Fn>
+ASM_DEV bool map_pair_walk(const unsigned long long* __restrict__ lkey, uint32_t f0, uint32_t f1, uint32_t g0, uint32_t g1, long long clo,
+                           long long chi, Fn&& fn) {
+    const unsigned long long RJ = (1ull << 58) - 1ull; /* (r, j) bits of a key */
+    uint32_t lo = g0, hi = g0;
+    for (uint32_t x = f0; x < f1; x++) {
+        const unsigned long long kA = lkey[x];
+        const long long r = (long long)MAP_KEY_R(kA), jlo = (long long)MAP_KEY_J(kA) + clo, jhi = (long long)MAP_KEY_J(kA) + chi;
+        if (jhi < 1) continue; /* loci ends are >= 1 */
+        const unsigned long long want_lo = (unsigned long long)r << 32 | (unsigned long long)(jlo < 0 ? 0 : jlo > 0xffffffffll ? 0xffffffffll : jlo);
+        const unsigned long long want_hi = (unsigned long long)r << 32 | (unsigned long long)(jhi > 0xffffffffll ? 0xffffffffll : jhi);
+        while (lo < g1 && (lkey[lo] & RJ) < want_lo) lo++;
+        if (hi < lo) hi = lo;
+        while (hi < g1 && (lkey[hi] & RJ) <= want_hi) hi++;
+        for (uint32_t y = lo; y < hi; y++)
+            if (!fn(kA, lkey[y])) return false;
+    }
+    return true;
+}
+
+/* both halves of pair p in pair order within a sum: s_A = 0 (F = A: j_B in [j_A - m_A + min, j_A - m_A + max]), then s_A = 1
+ * (F = B: j_B in [j_A + m_B - max, j_A + m_B - min]) */
+template <class Fn>
+ASM_DEV void map_pair_walk_both(const MapPairArgs& a, long p, Fn&& fn) {
+    const long A = p, B = a.np + p;
+    const long long mA = (long long)(a.roff[A + 1] - a.roff[A]), mB = (long long)(a.roff[B + 1] - a.roff[B]);
+    const uint32_t a0 = a.lbase[A], a1 = a.lbase[A + 1], b0 = a.lbase[B], b1 = a.lbase[B + 1], as = a.lsplit[A], bs = a.lsplit[B];
+    if (map_pair_walk(a.lkey, a0, as, bs, b1, a.min_insert - mA, a.max_insert - mA, fn))
+        map_pair_walk(a.lkey, as, a1, b0, bs, mB - a.max_insert, mB - a.min_insert, fn);
+}
+
+/* thread per pair: n_pairs, the d sums that occur among the eligible pairs and the secondary items' sizes (0 unless CONCORDANT;
+ * sum_best is the d sum of the pair map_pair_kernel reported) */
+__global__ __launch_bounds__(256) void map_pair_count_kernel(MapPairAllArgs a) {
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < a.pa.np; p += (long)gridDim.x * blockDim.x) {
+        uint32_t cnt = 0, mask = 0;
+        unsigned long long ni = 0, nd = 0;
+        if (a.pa.state[p] == MAP_PAIR_CONCORDANT) {
+            const long A = p, B = a.pa.np + p;
+            const int lim = MAP_KEY_D(a.pa.ikey[A]) + MAP_KEY_D(a.pa.ikey[B]) + a.strata;
+            map_pair_walk_both(a.pa, p, [&](unsigned long long kA, unsigned long long kB) {
+                const int s = MAP_KEY_D(kA) + MAP_KEY_D(kB);
+                if (s <= lim) {
+                    if (cnt != 0xffffffffu) cnt++;
+                    mask |= 1u << s;
+                }
+                return true;
+            });
+            const uint32_t sec = cnt ? (cnt < (uint32_t)a.max_pairs ? cnt : (uint32_t)a.max_pairs) - 1u : 0u; /* cnt >= 1 here */
+            ni = 2ull * sec;
+            nd = (unsigned long long)sec * (a.pa.roff[A + 1] - a.pa.roff[A] + a.pa.roff[B + 1] - a.pa.roff[B] + 2u);
+        }
+        a.n_pairs[p] = cnt, a.sums[p] = mask, a.nitem[p] = ni, a.ndirs[p] = nd;
+    }
+}
+
+/* thread per pair with n_pairs >= 2: the occurring sums in ascending order, each sum's pairs in pair order; rank 0 (the pair
+ * map_pair_kernel reported) is skipped and the next min(n_pairs, max_pairs) - 1 become items (A, B) at ibase[p] */
+__global__ __launch_bounds__(256) void map_pair_emit_kernel(MapPairAllArgs a) {
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < a.pa.np; p += (long)gridDim.x * blockDim.x) {
+        const uint32_t np_ = a.n_pairs[p], want = np_ < (uint32_t)a.max_pairs ? np_ : (uint32_t)a.max_pairs;
+        if (want < 2u) continue;
+        const long A = p, B = a.pa.np + p;
+        const uint32_t mA = a.pa.roff[A + 1] - a.pa.roff[A], mB = a.pa.roff[B + 1] - a.pa.roff[B];
+        unsigned long long q = a.ibase[p], dw = a.dbase[p];
+        uint32_t k = 0, mask = a.sums[p];
+        while (mask && k < want) {
+            const int s = __ffs(mask) - 1;
+            mask &= mask - 1u;
+            map_pair_walk_both(a.pa, p, [&](unsigned long long kA, unsigned long long kB) {
+                if (MAP_KEY_D(kA) + MAP_KEY_D(kB) != s) return true;
+                if (k) {
+                    a.iread[q] = (uint32_t)A, a.ikey[q] = kA, a.idirs[q] = dw;
+                    a.iread[q + 1] = (uint32_t)B, a.ikey[q + 1] = kB, a.idirs[q + 1] = dw + mA + 1u;
+                    q += 2, dw += mA + mB + 2u;
+                }
+                return ++k < want;
+            });
+        }
     }
 }
 

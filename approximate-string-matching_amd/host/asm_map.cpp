@@ -4,6 +4,7 @@
 //   asm-map -r ref.fa -q reads.fq [-o out.sam] [-e N] [--k 12] [--both-strands] [--max-occ N] [--chunk N]
 //           [--all-hits N [--strata S]]
 //   asm-map -r ref.fa -1 r1.fq -2 r2.fq [-o out.sam] -e N --insert MIN,MAX [--rescue E] [--k 12] [--max-occ N] [--chunk N]
+//           [--all-hits N [--strata S]]
 // --all-hits N writes up to N loci per read in rank order (asm_map_reads_all, strata S, default e): the primary record as without
 // it, then the secondary ones (FLAG 256, SEQ and QUAL '*'), each with NH:i:<reported> HI:i:<rank + 1> XH:i:<all loci> after NM
 // and XG.  Reads may be FASTQ or FASTA (QUAL '*').  Reads are processed in chunks of --chunk records, so the read file's size is not
@@ -15,6 +16,11 @@
 // PNEXT is the mate's POS; TLEN is +tlen on the mate with the smaller POS (mate 1 when equal) and -tlen on the other.  Proper
 // pairs carry XP:i:<n_concordant>, rescued records XR:i:1.  A mate longer than ASM_MAP_MAX_READ (or empty) leaves its pair
 // unmapped.
+// Paired --all-hits N writes up to N concordant pairs per fragment in rank order (asm_map_pairs_all, pair strata S on the d sum,
+// default 2e), mate 1 then mate 2 for each: rank 0 as without it, then the secondary pairs (FLAG 1 | 2 | 256 | 16 / 32 | 64 / 128,
+// SEQ and QUAL '*', RNEXT '=', PNEXT the POS of the other mate of that pair, TLEN that pair's +-tlen by the rule above, tags NM and
+// XG).  Every record of a fragment with at least one concordant pair ends with NH:i:<reported pairs> HI:i:<rank + 1>
+// XH:i:<eligible pairs>; both mates of a pair share HI.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -28,7 +34,7 @@ static void usage() {
     fprintf(stderr, "usage: asm-map -r ref.fa -q reads.fq [-o out.sam] [-e N] [--k 12] [--both-strands] [--max-occ N] [--chunk N] "
                     "[--all-hits N [--strata S]]\n"
                     "       asm-map -r ref.fa -1 r1.fq -2 r2.fq [-o out.sam] -e N --insert MIN,MAX [--rescue E] [--k 12] [--max-occ N] "
-                    "[--chunk N]\n");
+                    "[--chunk N] [--all-hits N [--strata S]]\n");
     exit(2);
 }
 
@@ -108,18 +114,19 @@ static std::string revcomp(const std::string& q) {
 }
 
 static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vector<std::string>& names, ReadFile& f1, ReadFile& f2,
-                       const asm_map_params& p, const asm_pair_params& pp, long chunk) {
+                       const asm_map_params& p, const asm_pair_params& pp, long chunk, int all_hits, int strata) {
     const int cap = 64;
+    const int slots = all_hits ? all_hits : 1; /* pairs per fragment in the library's output */
     std::vector<Record> a, b;
     std::vector<char> buf1, buf2;
     std::vector<uint32_t> ro1, ro2;
     std::vector<int64_t> slot;
     std::vector<asm_map_hit> hits;
     std::vector<int32_t> tlen;
-    std::vector<uint32_t> nconc;
+    std::vector<uint32_t> nconc, npairs;
     std::vector<uint16_t> ops;
     std::vector<uint8_t> nops;
-    long long n_pairs = 0, n_proper = 0, n_rescued = 0;
+    long long n_pairs = 0, n_proper = 0, n_rescued = 0, n_secondary = 0;
     bool more = true;
     while (more) {
         a.clear(), b.clear();
@@ -150,11 +157,14 @@ static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vecto
             ro1.push_back((uint32_t)buf1.size()), ro2.push_back((uint32_t)buf2.size());
         }
         const int64_t n = (int64_t)ro1.size() - 1;
-        hits.assign((size_t)(n + 1) * 2, asm_map_hit{});
-        tlen.assign((size_t)n + 1, 0), nconc.assign((size_t)n + 1, 0);
-        ops.assign((size_t)(n + 1) * 2 * cap, 0), nops.assign((size_t)(n + 1) * 2, 0);
-        if (asm_map_pairs(h, ix, n, buf1.data(), ro1.data(), buf2.data(), ro2.data(), &p, &pp, hits.data(), tlen.data(), nconc.data(),
-                          ops.data(), cap, nops.data())) {
+        hits.assign((size_t)(n + 1) * 2 * slots, asm_map_hit{});
+        tlen.assign((size_t)(n + 1) * slots, 0), nconc.assign((size_t)n + 1, 0), npairs.assign((size_t)n + 1, 0);
+        ops.assign((size_t)(n + 1) * 2 * slots * cap, 0), nops.assign((size_t)(n + 1) * 2 * slots, 0);
+        const int rc = all_hits ? asm_map_pairs_all(h, ix, n, buf1.data(), ro1.data(), buf2.data(), ro2.data(), &p, &pp, strata, all_hits,
+                                                    npairs.data(), hits.data(), tlen.data(), nconc.data(), ops.data(), cap, nops.data())
+                                : asm_map_pairs(h, ix, n, buf1.data(), ro1.data(), buf2.data(), ro2.data(), &p, &pp, hits.data(),
+                                                tlen.data(), nconc.data(), ops.data(), cap, nops.data());
+        if (rc) {
             fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
             return 1;
         }
@@ -163,7 +173,7 @@ static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vecto
             n_pairs++;
             const Record* rec[2] = {&a[q], &b[q]};
             const asm_map_hit* hr[2] = {&none, &none};
-            if (slot[q] >= 0) hr[0] = &hits[(size_t)slot[q] * 2], hr[1] = &hits[(size_t)slot[q] * 2 + 1];
+            if (slot[q] >= 0) hr[0] = &hits[(size_t)slot[q] * 2 * slots], hr[1] = &hits[(size_t)slot[q] * 2 * slots + 1];
             const bool mapped[2] = {(hr[0]->flags & ASM_MAP_MAPPED) != 0, (hr[1]->flags & ASM_MAP_MAPPED) != 0};
             const bool proper = (hr[0]->flags & ASM_MAP_PROPER_PAIR) != 0;
             n_proper += proper;
@@ -175,7 +185,9 @@ static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vecto
                 rid[x] = y < 0 ? -1 : hr[y]->seq_id;
                 pos[x] = y < 0 ? 0 : (long long)hr[y]->pos + 1;
             }
-            const long long tl = slot[q] >= 0 ? tlen[(size_t)slot[q]] : 0;
+            const long long tl = slot[q] >= 0 ? tlen[(size_t)slot[q] * slots] : 0;
+            /* with --all-hits: NH / HI / XH on every record of a fragment with a concordant pair */
+            const uint32_t nh = all_hits && slot[q] >= 0 ? npairs[(size_t)slot[q]] : 0u, nrep = nh < (uint32_t)slots ? nh : (uint32_t)slots;
             const int plus = pos[0] <= pos[1] ? 0 : 1; /* the mate whose TLEN is positive */
             for (int x = 0; x < 2; x++) {
                 const asm_map_hit& m = *hr[x];
@@ -192,7 +204,7 @@ static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vecto
                         seq = revcomp(rec[x]->seq);
                         if (qual != "*") qual.assign(rec[x]->qual.rbegin(), rec[x]->qual.rend());
                     }
-                    const size_t o = (size_t)slot[q] * 2 + x;
+                    const size_t o = (size_t)slot[q] * 2 * slots + x;
                     const int nn = nops[o];
                     if (asm_cigar_format(&ops[o * cap], nn, cap, cigar, sizeof(cigar)) != 0 || nn > cap) strcpy(cigar, "*");
                     mapq = m.greedy_cost + 60 < 254 ? m.greedy_cost + 60 : 254;
@@ -207,11 +219,32 @@ static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vecto
                     fprintf(out, "\tXR:i:1");
                     n_rescued++;
                 }
+                if (nh) fprintf(out, "\tNH:i:%u\tHI:i:1\tXH:i:%u", nrep, nh);
                 fputc('\n', out);
+            }
+            /* secondary pairs, rank 1.., both mates mapped on one sequence */
+            for (uint32_t t = 1; t < nrep; t++) {
+                const size_t o = ((size_t)slot[q] * slots + t) * 2;
+                const asm_map_hit* sr[2] = {&hits[o], &hits[o + 1]};
+                const long long stl = tlen[(size_t)slot[q] * slots + t];
+                const int splus = sr[0]->pos <= sr[1]->pos ? 0 : 1;
+                n_secondary++;
+                for (int x = 0; x < 2; x++) {
+                    const asm_map_hit& m = *sr[x];
+                    const int flag = 1 | 2 | 256 | (m.strand ? 16 : 0) | (sr[1 - x]->strand ? 32 : 0) | (x ? 128 : 64);
+                    char cigar[4096];
+                    const int nn = nops[o + x];
+                    if (asm_cigar_format(&ops[(o + x) * cap], nn, cap, cigar, sizeof(cigar)) != 0 || nn > cap) strcpy(cigar, "*");
+                    const int mapq = m.greedy_cost + 60 < 254 ? m.greedy_cost + 60 : 254;
+                    fprintf(out, "%s\t%d\t%s\t%u\t%d\t%s\t=\t%u\t%lld\t*\t*\tNM:i:%d\tXG:i:%d\tNH:i:%u\tHI:i:%u\tXH:i:%u\n",
+                            pair_name(rec[x]->name).c_str(), flag, names[(size_t)m.seq_id].c_str(), m.pos + 1, mapq, cigar,
+                            sr[1 - x]->pos + 1, x == splus ? stl : -stl, (int)m.dist, m.greedy_cost, nrep, t + 1, nh);
+                }
             }
         }
     }
     fprintf(stderr, "asm-map: %lld pairs, %lld proper, %lld mates rescued\n", n_pairs, n_proper, n_rescued);
+    if (all_hits) fprintf(stderr, "asm-map: %lld secondary pairs\n", n_secondary);
     return 0;
 }
 
@@ -248,10 +281,10 @@ int main(int argc, char** argv) {
     }
     if (ref_path.empty() || read_path.empty() || chunk < 1 || all_hits < 0 || (strata >= 0 && !all_hits)) usage();
     const bool paired = !read2_path.empty();
-    if (paired && (all_hits || pp.min_insert < 0 || pp.max_insert < 0)) usage(); /* paired: --insert needed, --all-hits refused */
+    if (paired && (pp.min_insert < 0 || pp.max_insert < 0)) usage(); /* paired: --insert needed */
     if (!paired && (pp.min_insert >= 0 || pp.rescue_errors >= 0)) usage();
     if (paired) p.both_strands = 1;
-    if (strata < 0) strata = p.max_errors;
+    if (strata < 0) strata = paired ? 2 * p.max_errors : p.max_errors; /* paired: strata on the d sum of a pair */
     const int slots = all_hits ? all_hits : 1; /* records per read in the library's output */
 
     /* reference: name = first word of the header */
@@ -323,7 +356,7 @@ int main(int argc, char** argv) {
             reads2.fasta = c == '>';
             if (c != EOF) ungetc(c, rf2);
         }
-        rc = write_pairs(out, h, ix, names, reads, reads2, p, pp, chunk);
+        rc = write_pairs(out, h, ix, names, reads, reads2, p, pp, chunk, all_hits, strata);
         fclose(out);
         fclose(rf);
         fclose(rf2);

@@ -424,6 +424,23 @@ int asm_map_pairs(asm_handle* h, const asm_index* ix, int64_t n, const char* rea
                   const uint32_t* off2, const asm_map_params* p, const asm_pair_params* pp, asm_map_hit* out /* [n][2] */,
                   int32_t* tlen /* [n] */, uint32_t* n_concordant /* [n] */, uint16_t* cigar_ops /* [n][2][cigar_cap] */,
                   int cigar_cap, uint8_t* cigar_nops /* [n][2] */);
+/* asm_map_pairs_all: every concordant pair within strata, not only the best (docs/design/mapper.md, "Secondary pairs").  Inputs,
+ *                  loci, concordance, pair order, rescue, n_concordant and the tlen rule are asm_map_pairs'.  The eligible pairs are
+ *                  the concordant combinations of a mate-1 locus and a mate-2 locus with d_A + d_B <= sum_best + strata (sum_best =
+ *                  the smallest sum), strata in [0, 2 * ASM_MAP_MAX_ERRORS] (0: the best sum only; >= 2 max_errors: all of them).
+ *                  n_pairs[i] = how many (uncapped, saturating); the first min(n_pairs[i], max_pairs) in pair order are written to
+ *                  out[i][0..][0, 1] (mate 1, mate 2), max_pairs in [1, ASM_MAP_MAX_HITS]; tlen = [n][max_pairs], cigar_ops =
+ *                  [n][max_pairs][2][cigar_cap], cigar_nops = [n][max_pairs][2].  Rank 0 is, field for field, asm_map_pairs' answer
+ *                  (records, tlen, n_concordant, CIGARs; rescued and unpaired fragments too, with n_pairs 0), plus flag
+ *                  HITS_TRUNCATED.  A record of rank >= 1 is, flags apart, asm_map_reads_all's record of that locus (strata =
+ *                  max_errors) and carries MAPPED | PROPER_PAIR | SECONDARY; tlen[i][rank] = max(end) - min(pos) of that pair.  Every
+ *                  record of a fragment with n_pairs > max_pairs carries HITS_TRUNCATED.  An unused slot: the unused record of
+ *                  asm_map_reads_all (its cigar_ops row is not written, cigar_nops 0), tlen 0.  Synchronous. */
+int asm_map_pairs_all(asm_handle* h, const asm_index* ix, int64_t n, const char* reads1, const uint32_t* off1, const char* reads2,
+                      const uint32_t* off2, const asm_map_params* p, const asm_pair_params* pp, int strata, int max_pairs,
+                      uint32_t* n_pairs /* [n] */, asm_map_hit* out /* [n][max_pairs][2] */, int32_t* tlen /* [n][max_pairs] */,
+                      uint32_t* n_concordant /* [n] */, uint16_t* cigar_ops /* [n][max_pairs][2][cigar_cap] */, int cigar_cap,
+                      uint8_t* cigar_nops /* [n][max_pairs][2] */);
 
 /* ---- plain device memory helpers (so that non-torch hosts can drive the async API) --------------------- */
 int asm_device_malloc(asm_handle* h, size_t bytes, void** d_ptr);

@@ -10,6 +10,8 @@ half reverse-complemented) and 6 kbp of a period-6 tandem repeat into the refere
 bases with 0..e substitutions; 5 % discordant pairs: out of range, same strand or far apart; 10 % random pairs; 10 % of pairs with
 one mate carrying e+1..e+3 substitutions; with --repeats, 30 % of the fragments inside the element copies) and times asm_map_pairs
 against asm_map_reads_all (strata = e, max_hits = 1) on the same reads, alternately, and reports the proper and rescued fractions.
+--paired --all-hits N [--strata S] times asm_map_pairs_all (up to N pairs per fragment, pair strata S, default 2e) against
+asm_map_pairs instead, alternately, and prints the n_pairs distribution.
 --profile re-runs the same command under `rocprofv3 --kernel-trace --stats` (a run of its own) and prints the per-kernel totals."""
 import argparse
 import ctypes
@@ -75,7 +77,7 @@ def main():
     ap.add_argument("--k", type=int, default=12)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--all-hits", type=int, default=0, help="also time asm_map_reads_all with up to N loci per read")
-    ap.add_argument("--strata", type=int, default=None, help="with --all-hits: strata (default e)")
+    ap.add_argument("--strata", type=int, default=None, help="with --all-hits: strata (default e; --paired: 2e)")
     ap.add_argument("--repeats", action="store_true", help="the reference with repeats, 30 %% of the reads from them")
     ap.add_argument("--paired", action="store_true", help="time asm_map_pairs on --reads / 2 simulated pairs")
     ap.add_argument("--insert", default="200,500", help="with --paired: MIN,MAX of the projected span")
@@ -241,14 +243,32 @@ def run_paired(a, eng, tm, n, ref_len):
         all_hits = np.zeros(2 * npairs, m.MAP_HIT_DTYPE)
         all_ops = np.zeros(2 * npairs * 16, np.uint16)
         all_nops = np.zeros(2 * npairs, np.uint8)
+        P = max(a.all_hits, 1)
+        strata = 2 * e if a.strata is None else a.strata
+        n_pairs = np.zeros(npairs, np.uint32)
+        pa_hits = np.zeros(npairs * P * 2, m.MAP_HIT_DTYPE) if a.all_hits else None
+        pa_tlen = np.zeros(npairs * P, np.int32) if a.all_hits else None
+        pa_nconc = np.zeros(npairs, np.uint32)
+        pa_ops = np.zeros(npairs * P * 2 * 16, np.uint16) if a.all_hits else None
+        pa_nops = np.zeros(npairs * P * 2, np.uint8) if a.all_hits else None
         best_pairs, best_all = 1e30, 1e30
         for _ in range(a.reps):  # alternating, so that both calls see the same machine state
+            if a.all_hits:
+                tm.start()
+                eng._chk(lib.asm_map_pairs_all(h, ix, npairs, f1.ctypes.data, ro.ctypes.data, f2.ctypes.data, ro.ctypes.data,
+                                               ctypes.byref(p), ctypes.byref(pp), strata, a.all_hits, n_pairs.ctypes.data,
+                                               pa_hits.ctypes.data, pa_tlen.ctypes.data, pa_nconc.ctypes.data, pa_ops.ctypes.data, 16,
+                                               pa_nops.ctypes.data))
+                tm.stop()
+                best_all = min(best_all, tm.elapsed_ms())
             tm.start()
             eng._chk(lib.asm_map_pairs(h, ix, npairs, f1.ctypes.data, ro.ctypes.data, f2.ctypes.data, ro.ctypes.data, ctypes.byref(p),
                                        ctypes.byref(pp), hits.ctypes.data, tlen.ctypes.data, nconc.ctypes.data, ops.ctypes.data, 16,
                                        nops.ctypes.data))
             tm.stop()
             best_pairs = min(best_pairs, tm.elapsed_ms())
+            if a.all_hits:
+                continue
             tm.start()
             eng._chk(lib.asm_map_reads_all(h, ix, 2 * npairs, both.ctypes.data, ro2.ctypes.data, ctypes.byref(p), e, 1,
                                            n_hits.ctypes.data, all_hits.ctypes.data, all_ops.ctypes.data, 16, all_nops.ctypes.data))
@@ -262,6 +282,17 @@ def run_paired(a, eng, tm, n, ref_len):
                "rescued_fraction": round(float(((fl & m.MAP_RESCUED) != 0).any(axis=1).mean()), 4),
                "mates_mapped_fraction": round(float(((fl & m.MAP_MAPPED) != 0).mean()), 4),
                "n_concordant_gt1_fraction": round(float((nconc > 1).mean()), 4)}
+        if a.all_hits:
+            del row["all_hits1_ms_events"], row["pairs_over_all_hits1"]
+            rep_n = np.minimum(n_pairs, a.all_hits)
+            row.update({"all_hits": a.all_hits, "strata": strata, "pairs_all_ms_events": round(best_all, 3),
+                        "pairs_all_per_s": round(npairs / best_all * 1e3), "pairs_all_over_pairs": round(best_all / best_pairs, 3),
+                        "n_pairs_mean": round(float(n_pairs.mean()), 3), "reported_pairs_mean": round(float(rep_n.mean()), 3),
+                        "secondary_pairs": int(np.maximum(rep_n.astype(np.int64) - 1, 0).sum()),
+                        "rank0_equals_pairs": bool(np.array_equal(pa_nconc, nconc) and np.array_equal(
+                            pa_hits.reshape(npairs, P, 2)[:, 0]["pos"], hits.reshape(npairs, 2)["pos"])),
+                        # distribution of n_pairs: 0, 1, 2-3, 4-15, 16-63, >= 64
+                        "n_pairs_hist": [int(v) for v in np.histogram(n_pairs, [0, 1, 2, 4, 16, 64, 2**32])[0]]})
         results["runs"].append(row)
         print(json.dumps(row))
     if a.out:
