@@ -544,6 +544,47 @@ class Engine:
                                            ctypes.byref(ptr)))
         return Index(self, ptr, int(k), np.diff(off).astype(np.int64))
 
+    def _map_chunks(self, parts, chunk: Optional[int], call) -> None:
+        """The chunk loop of the map_* methods.  parts: one list of byte strings per mate; call(lo, hi, seqs) maps reads [lo, hi)
+        and returns the library's code; seqs: per list the address of the packed bytes (None when empty) and of their uint32
+        offsets."""
+        n = len(parts[0])
+        step = chunk if chunk else max(n, 1)
+        for lo in range(0, n, step):
+            hi = min(n, lo + step)
+            packed = [(buf, off.astype(np.uint32)) for buf, off in (pack_sequences(p[lo:hi]) for p in parts)]
+            seqs = [x for buf, ro in packed for x in (buf.ctypes.data if buf.size else None, ro.ctypes.data)]
+            self._chk(call(lo, hi, seqs))
+
+    @staticmethod
+    def _mates(reads1, reads2):
+        p1, p2 = [_as_bytes(r) for r in reads1], [_as_bytes(r) for r in reads2]
+        if len(p1) != len(p2):
+            raise ValueError("reads1 and reads2 must hold the same number of mates")
+        return p1, p2
+
+    @staticmethod
+    def _cigar_args(ops: np.ndarray, nops: np.ndarray, cigar_cap: int, lo: int, hi: int):
+        """cigar_ops, cigar_cap, cigar_nops of a library call that writes records [lo, hi) of the full arrays"""
+        return (ops[lo:hi].ctypes.data if cigar_cap else None, int(cigar_cap), nops[lo:hi].ctypes.data if cigar_cap else None)
+
+    @staticmethod
+    def _hit_fields(hits: np.ndarray, rescued: bool = False) -> dict:
+        """the record fields as arrays of hits' shape, plus mapped, mapq (255 when unmapped) and, for the paired calls, rescued"""
+        out = {name: hits[name].copy() for name in MAP_HIT_DTYPE.names}
+        out["mapped"] = (hits["flags"] & MAP_MAPPED) != 0
+        if rescued:
+            out["rescued"] = (hits["flags"] & MAP_RESCUED) != 0
+        out["mapq"] = np.where(out["mapped"], np.minimum(254, 60 + hits["greedy_cost"].astype(np.int64)), 255).astype(np.int32)
+        return out
+
+    @staticmethod
+    def _cigars(ops: np.ndarray, nops: np.ndarray, cigar_cap: int):
+        """one CIGAR string per record of nops, flat ('' for all when cigar_cap is 0)"""
+        if not (cigar_cap and nops.size):
+            return [""] * nops.size
+        return decode_cigars(ops.reshape(nops.size, -1), nops.reshape(-1), cigar_cap)
+
     def map_reads(self, index: Index, reads, max_errors: int, both_strands: bool = True, max_occ: int = 0, greedy_k: int = 3,
                   cigar_cap: int = 64, chunk: Optional[int] = None):
         """asm_map_reads: the best hit of every read (str / bytes).  -> dict of numpy arrays, one entry per read: seq_id, pos, end,
@@ -553,25 +594,13 @@ class Engine:
         n = len(parts)
         p = MapParams(int(max_errors), 1 if both_strands else 0, int(max_occ), int(greedy_k))
         hits = np.zeros(n, MAP_HIT_DTYPE)
-        ops = np.zeros((max(n, 1), max(cigar_cap, 1)), np.uint16)
-        nops = np.zeros(max(n, 1), np.uint8)
-        step = chunk if chunk else max(n, 1)
-        for lo in range(0, n, step):
-            hi = min(n, lo + step)
-            buf, off = pack_sequences(parts[lo:hi])
-            ro = off.astype(np.uint32)
-            sub = np.zeros(hi - lo, MAP_HIT_DTYPE)
-            sops = np.zeros((hi - lo, max(cigar_cap, 1)), np.uint16)
-            snops = np.zeros(hi - lo, np.uint8)
-            self._chk(self.lib.asm_map_reads(self.h, index.ptr, hi - lo, buf.ctypes.data if buf.size else None, ro.ctypes.data,
-                                             ctypes.byref(p), sub.ctypes.data, sops.ctypes.data if cigar_cap else None, int(cigar_cap),
-                                             snops.ctypes.data if cigar_cap else None))
-            hits[lo:hi], ops[lo:hi], nops[lo:hi] = sub, sops, snops
-        out = {name: hits[name].copy() for name in MAP_HIT_DTYPE.names}
-        out["mapped"] = (hits["flags"] & MAP_MAPPED) != 0
-        out["mapq"] = np.where(out["mapped"], np.minimum(254, 60 + hits["greedy_cost"].astype(np.int64)), 255).astype(np.int32)
-        out["cigar"] = decode_cigars(ops[:n], nops[:n], cigar_cap) if cigar_cap else [""] * n
-        out["cigar_nops"] = nops[:n].copy()
+        ops = np.zeros((n, max(cigar_cap, 1)), np.uint16)
+        nops = np.zeros(n, np.uint8)
+        self._map_chunks([parts], chunk, lambda lo, hi, seqs: self.lib.asm_map_reads(
+            self.h, index.ptr, hi - lo, *seqs, ctypes.byref(p), hits[lo:hi].ctypes.data, *self._cigar_args(ops, nops, cigar_cap, lo, hi)))
+        out = self._hit_fields(hits)
+        out["cigar"] = self._cigars(ops, nops, cigar_cap)
+        out["cigar_nops"] = nops
         return out
 
     def map_reads_all(self, index: Index, reads, max_errors: int, max_hits: int = 16, strata: Optional[int] = None,
@@ -585,25 +614,13 @@ class Engine:
         n = len(parts)
         strata = int(max_errors) if strata is None else int(strata)
         p = MapParams(int(max_errors), 1 if both_strands else 0, int(max_occ), int(greedy_k))
-        cap1 = max(cigar_cap, 1)
         n_hits = np.zeros(n, np.uint32)
         hits = np.zeros((n, max_hits), MAP_HIT_DTYPE)
-        ops = np.zeros((n, max_hits, cap1), np.uint16)
+        ops = np.zeros((n, max_hits, max(cigar_cap, 1)), np.uint16)
         nops = np.zeros((n, max_hits), np.uint8)
-        step = chunk if chunk else max(n, 1)
-        for lo in range(0, n, step):
-            hi = min(n, lo + step)
-            buf, off = pack_sequences(parts[lo:hi])
-            ro = off.astype(np.uint32)
-            snh = np.zeros(hi - lo, np.uint32)
-            sub = np.zeros((hi - lo, max_hits), MAP_HIT_DTYPE)
-            sops = np.zeros((hi - lo, max_hits, cap1), np.uint16)
-            snops = np.zeros((hi - lo, max_hits), np.uint8)
-            self._chk(self.lib.asm_map_reads_all(self.h, index.ptr, hi - lo, buf.ctypes.data if buf.size else None, ro.ctypes.data,
-                                                 ctypes.byref(p), strata, int(max_hits), snh.ctypes.data, sub.ctypes.data,
-                                                 sops.ctypes.data if cigar_cap else None, int(cigar_cap),
-                                                 snops.ctypes.data if cigar_cap else None))
-            n_hits[lo:hi], hits[lo:hi], ops[lo:hi], nops[lo:hi] = snh, sub, sops, snops
+        self._map_chunks([parts], chunk, lambda lo, hi, seqs: self.lib.asm_map_reads_all(
+            self.h, index.ptr, hi - lo, *seqs, ctypes.byref(p), strata, int(max_hits), n_hits[lo:hi].ctypes.data,
+            hits[lo:hi].ctypes.data, *self._cigar_args(ops, nops, cigar_cap, lo, hi)))
         n_rep = np.minimum(n_hits, max_hits).astype(np.int64)
         read = np.repeat(np.arange(n, dtype=np.int64), n_rep)
         rank = (np.arange(read.size, dtype=np.int64) - np.repeat(np.cumsum(n_rep) - n_rep, n_rep)) if read.size else read.copy()
@@ -611,7 +628,7 @@ class Engine:
         out = {"n_hits": n_hits, "n_reported": n_rep, "read_flags": hits["flags"][:, 0].copy(), "read": read, "rank": rank}
         out.update({name: flat[name].copy() for name in MAP_HIT_DTYPE.names})
         out["mapq"] = np.minimum(254, 60 + flat["greedy_cost"].astype(np.int64)).astype(np.int32)
-        out["cigar"] = decode_cigars(ops[read, rank], nops[read, rank], cigar_cap) if cigar_cap else [""] * read.size
+        out["cigar"] = self._cigars(ops[read, rank], nops[read, rank], cigar_cap)
         return out
 
     def map_pairs(self, index: Index, reads1, reads2, max_errors: int, min_insert: int, max_insert: int, rescue_errors: int = -1,
@@ -621,42 +638,22 @@ class Engine:
         seq_id, pos, end, dist, strand, flags, greedy_cost, mapq (min(254, 60 + greedy_cost), 255 when unmapped), mapped and
         rescued (bool), `cigar` (n lists of 2 CIGAR strings); per pair: proper (bool), tlen and n_concordant.  chunk: pairs per
         library call (None: all in one)."""
-        p1 = [_as_bytes(r) for r in reads1]
-        p2 = [_as_bytes(r) for r in reads2]
-        if len(p1) != len(p2):
-            raise ValueError("reads1 and reads2 must hold the same number of mates")
-        n = len(p1)
+        mates = self._mates(reads1, reads2)
+        n = len(mates[0])
         p = MapParams(int(max_errors), 1, int(max_occ), int(greedy_k))
         pp = PairParams(int(min_insert), int(max_insert), int(rescue_errors))
-        cap1 = max(cigar_cap, 1)
         hits = np.zeros((n, 2), MAP_HIT_DTYPE)
         tlen = np.zeros(n, np.int32)
         n_conc = np.zeros(n, np.uint32)
-        ops = np.zeros((n, 2, cap1), np.uint16)
+        ops = np.zeros((n, 2, max(cigar_cap, 1)), np.uint16)
         nops = np.zeros((n, 2), np.uint8)
-        step = chunk if chunk else max(n, 1)
-        for lo in range(0, n, step):
-            hi = min(n, lo + step)
-            b1, o1 = pack_sequences(p1[lo:hi])
-            b2, o2 = pack_sequences(p2[lo:hi])
-            ro1, ro2 = o1.astype(np.uint32), o2.astype(np.uint32)
-            sub = np.zeros((hi - lo, 2), MAP_HIT_DTYPE)
-            stl = np.zeros(hi - lo, np.int32)
-            snc = np.zeros(hi - lo, np.uint32)
-            sops = np.zeros((hi - lo, 2, cap1), np.uint16)
-            snops = np.zeros((hi - lo, 2), np.uint8)
-            self._chk(self.lib.asm_map_pairs(self.h, index.ptr, hi - lo, b1.ctypes.data if b1.size else None, ro1.ctypes.data,
-                                             b2.ctypes.data if b2.size else None, ro2.ctypes.data, ctypes.byref(p), ctypes.byref(pp),
-                                             sub.ctypes.data, stl.ctypes.data, snc.ctypes.data, sops.ctypes.data if cigar_cap else None,
-                                             int(cigar_cap), snops.ctypes.data if cigar_cap else None))
-            hits[lo:hi], tlen[lo:hi], n_conc[lo:hi], ops[lo:hi], nops[lo:hi] = sub, stl, snc, sops, snops
-        out = {name: hits[name].copy() for name in MAP_HIT_DTYPE.names}
-        out["mapped"] = (hits["flags"] & MAP_MAPPED) != 0
-        out["rescued"] = (hits["flags"] & MAP_RESCUED) != 0
-        out["mapq"] = np.where(out["mapped"], np.minimum(254, 60 + hits["greedy_cost"].astype(np.int64)), 255).astype(np.int32)
+        self._map_chunks(mates, chunk, lambda lo, hi, seqs: self.lib.asm_map_pairs(
+            self.h, index.ptr, hi - lo, *seqs, ctypes.byref(p), ctypes.byref(pp), hits[lo:hi].ctypes.data, tlen[lo:hi].ctypes.data,
+            n_conc[lo:hi].ctypes.data, *self._cigar_args(ops, nops, cigar_cap, lo, hi)))
+        out = self._hit_fields(hits, rescued=True)
         out["proper"] = (hits["flags"][:, 0] & MAP_PROPER_PAIR) != 0
         out["tlen"], out["n_concordant"] = tlen, n_conc
-        flat = decode_cigars(ops.reshape(2 * n, cap1), nops.reshape(2 * n), cigar_cap) if cigar_cap and n else [""] * (2 * n)
+        flat = self._cigars(ops, nops, cigar_cap)
         out["cigar"] = [[flat[2 * t], flat[2 * t + 1]] for t in range(n)]
         out["cigar_nops"] = nops
         return out
@@ -670,47 +667,25 @@ class Engine:
         pair and rank (n, max_pairs): proper, tlen; per pair: n_pairs (uncapped), n_reported (min(n_pairs, max_pairs)) and
         n_concordant; `cigar`: n lists of max_pairs pairs of CIGAR strings.  Rank 0 is map_pairs' answer.  chunk: pairs per
         library call (None: all in one)."""
-        p1 = [_as_bytes(r) for r in reads1]
-        p2 = [_as_bytes(r) for r in reads2]
-        if len(p1) != len(p2):
-            raise ValueError("reads1 and reads2 must hold the same number of mates")
-        n, P = len(p1), int(max_pairs)
+        mates = self._mates(reads1, reads2)
+        n, P = len(mates[0]), int(max_pairs)
         strata = 2 * int(max_errors) if strata is None else int(strata)
         p = MapParams(int(max_errors), 1, int(max_occ), int(greedy_k))
         pp = PairParams(int(min_insert), int(max_insert), int(rescue_errors))
-        cap1 = max(cigar_cap, 1)
         hits = np.zeros((n, P, 2), MAP_HIT_DTYPE)
         tlen = np.zeros((n, P), np.int32)
         n_pairs = np.zeros(n, np.uint32)
         n_conc = np.zeros(n, np.uint32)
-        ops = np.zeros((n, P, 2, cap1), np.uint16)
+        ops = np.zeros((n, P, 2, max(cigar_cap, 1)), np.uint16)
         nops = np.zeros((n, P, 2), np.uint8)
-        step = chunk if chunk else max(n, 1)
-        for lo in range(0, n, step):
-            hi = min(n, lo + step)
-            b1, o1 = pack_sequences(p1[lo:hi])
-            b2, o2 = pack_sequences(p2[lo:hi])
-            ro1, ro2 = o1.astype(np.uint32), o2.astype(np.uint32)
-            sub = np.zeros((hi - lo, P, 2), MAP_HIT_DTYPE)
-            stl = np.zeros((hi - lo, P), np.int32)
-            snp = np.zeros(hi - lo, np.uint32)
-            snc = np.zeros(hi - lo, np.uint32)
-            sops = np.zeros((hi - lo, P, 2, cap1), np.uint16)
-            snops = np.zeros((hi - lo, P, 2), np.uint8)
-            self._chk(self.lib.asm_map_pairs_all(self.h, index.ptr, hi - lo, b1.ctypes.data if b1.size else None, ro1.ctypes.data,
-                                                 b2.ctypes.data if b2.size else None, ro2.ctypes.data, ctypes.byref(p), ctypes.byref(pp),
-                                                 strata, P, snp.ctypes.data, sub.ctypes.data, stl.ctypes.data, snc.ctypes.data,
-                                                 sops.ctypes.data if cigar_cap else None, int(cigar_cap),
-                                                 snops.ctypes.data if cigar_cap else None))
-            hits[lo:hi], tlen[lo:hi], n_pairs[lo:hi], n_conc[lo:hi], ops[lo:hi], nops[lo:hi] = sub, stl, snp, snc, sops, snops
-        out = {name: hits[name].copy() for name in MAP_HIT_DTYPE.names}
-        out["mapped"] = (hits["flags"] & MAP_MAPPED) != 0
-        out["rescued"] = (hits["flags"] & MAP_RESCUED) != 0
-        out["mapq"] = np.where(out["mapped"], np.minimum(254, 60 + hits["greedy_cost"].astype(np.int64)), 255).astype(np.int32)
+        self._map_chunks(mates, chunk, lambda lo, hi, seqs: self.lib.asm_map_pairs_all(
+            self.h, index.ptr, hi - lo, *seqs, ctypes.byref(p), ctypes.byref(pp), strata, P, n_pairs[lo:hi].ctypes.data,
+            hits[lo:hi].ctypes.data, tlen[lo:hi].ctypes.data, n_conc[lo:hi].ctypes.data, *self._cigar_args(ops, nops, cigar_cap, lo, hi)))
+        out = self._hit_fields(hits, rescued=True)
         out["proper"] = (hits["flags"][:, :, 0] & MAP_PROPER_PAIR) != 0
         out["tlen"], out["n_pairs"], out["n_concordant"] = tlen, n_pairs, n_conc
         out["n_reported"] = np.minimum(n_pairs, P).astype(np.int64)
-        flat = decode_cigars(ops.reshape(2 * n * P, cap1), nops.reshape(2 * n * P), cigar_cap) if cigar_cap and n else [""] * (2 * n * P)
+        flat = self._cigars(ops, nops, cigar_cap)
         out["cigar"] = [[[flat[2 * (t * P + k)], flat[2 * (t * P + k) + 1]] for k in range(P)] for t in range(n)]
         out["cigar_nops"] = nops
         return out

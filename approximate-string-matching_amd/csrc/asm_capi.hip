@@ -21,6 +21,7 @@
 #include <string>
 #include <sys/stat.h>
 #include <thread>
+#include <type_traits>
 #include <unistd.h>
 #include <unordered_map>
 #include <vector>
@@ -2348,969 +2349,8 @@ int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, in
     return rc;
 }
 
-/* ---- read mapping (csrc/asm_map.h, docs/design/mapper.md) ------------------------------------------------------------- */
-static_assert(sizeof(MapHit) == sizeof(asm_map_hit) && offsetof(MapHit, dist) == offsetof(asm_map_hit, dist) &&
-                  offsetof(MapHit, greedy_cost) == offsetof(asm_map_hit, greedy_cost),
-              "MapHit must have the layout of asm_map_hit");
-
-struct asm_index {
-    int device = 0;
-    int k = 0;
-    int32_t n_seqs = 0;
-    uint64_t len = 0;
-    std::vector<uint64_t> seq_off;          /* host copy, n_seqs + 1 */
-    char* d_text = nullptr;                 /* upper case */
-    unsigned long long* d_seq_off = nullptr;
-    uint32_t* d_off = nullptr;              /* 4^k + 1 bucket offsets */
-    uint32_t* d_pos = nullptr;              /* positions sorted by k-mer (ascending inside a bucket) */
-    ~asm_index() {
-        (void)hipSetDevice(device);
-        for (void* p : {(void*)d_text, (void*)d_seq_off, (void*)d_off, (void*)d_pos})
-            if (p) (void)hipFree(p);
-    }
-};
-
-static unsigned map_grid(uint64_t n, const asm_handle* h) { /* grid-stride kernels: at most 8 workgroups per CU */
-    const uint64_t want = (n + 255) / 256, cap = (uint64_t)h->num_cus * 8;
-    return (unsigned)(want < 1 ? 1 : want > cap ? cap : want);
-}
-
-int asm_index_build(asm_handle* h, const char* text, const uint64_t* seq_off, int32_t n_seqs, int k, asm_index** out) {
-    if (!out || !seq_off) return fail(h, ASM_EINVAL, "asm_index_build: NULL argument");
-    *out = nullptr;
-    if (n_seqs < 1 || n_seqs >= MAP_MAX_SEQS) return fail(h, ASM_EINVAL, "asm_index_build: n_seqs must be in [1, 2^26)");
-    if (k < ASM_MAP_MIN_K || k > ASM_MAP_MAX_K) return fail(h, ASM_EINVAL, "asm_index_build: k must be in [8, 14]");
-    if (seq_off[0] != 0) return fail(h, ASM_EINVAL, "asm_index_build: seq_off[0] must be 0");
-    for (int32_t r = 0; r < n_seqs; r++)
-        if (seq_off[r + 1] < seq_off[r]) return fail(h, ASM_EINVAL, "asm_index_build: seq_off must be non-decreasing");
-    const uint64_t len = seq_off[n_seqs];
-    if (len >= 0xffffffffull) return fail(h, ASM_EUNSUPPORTED, "asm_index_build: total reference length must be below 2^32");
-    if (len && !text) return fail(h, ASM_EINVAL, "asm_index_build: text is NULL");
-    if (!h) return fail(h, ASM_EINVAL, "asm_index_build: NULL handle");
-    HIPCHK(h, hipSetDevice(h->device));
-    std::unique_ptr<asm_index> ix(new asm_index);
-    ix->device = h->device, ix->k = k, ix->n_seqs = n_seqs, ix->len = len;
-    ix->seq_off.assign(seq_off, seq_off + n_seqs + 1);
-    const uint32_t nb = (1u << (2 * k)) + 1u;
-    HIPCHK(h, big_malloc(h, (void**)&ix->d_text, len + 16));
-    HIPCHK(h, big_malloc(h, (void**)&ix->d_seq_off, sizeof(unsigned long long) * (size_t)(n_seqs + 1)));
-    HIPCHK(h, big_malloc(h, (void**)&ix->d_off, sizeof(uint32_t) * nb));
-    HIPCHK(h, big_malloc(h, (void**)&ix->d_pos, sizeof(uint32_t) * (len ? len : 1)));
-    if (len) HIPCHK(h, hipMemcpyAsync(ix->d_text, text, len, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(ix->d_seq_off, seq_off, sizeof(uint64_t) * (size_t)(n_seqs + 1), hipMemcpyHostToDevice, h->stream));
-    if (len) {
-        Scratch<uint32_t> keys(h), keys2(h), vals(h);
-        Scratch<void> tmp(h);
-        HIPCHK(h, keys.alloc(sizeof(uint32_t) * len));
-        HIPCHK(h, keys2.alloc(sizeof(uint32_t) * len));
-        HIPCHK(h, vals.alloc(sizeof(uint32_t) * len));
-        hipLaunchKernelGGL(map_upper_kernel, dim3(map_grid(len, h)), dim3(256), 0, h->stream, ix->d_text, (unsigned long long)len);
-        HIPCHK(h, hipGetLastError());
-        hipLaunchKernelGGL(map_kmer_key_kernel, dim3(map_grid(len, h)), dim3(256), 0, h->stream, (const char*)ix->d_text,
-                           (unsigned long long)len, (const unsigned long long*)ix->d_seq_off, (uint32_t)n_seqs, k, keys.p, vals.p);
-        HIPCHK(h, hipGetLastError());
-        size_t tmp_bytes = 0;
-        HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys.p, keys2.p, vals.p, ix->d_pos, (uint32_t)len, 0,
-                                                     2 * k + 1, h->stream));
-        HIPCHK(h, tmp.alloc(tmp_bytes + 16));
-        HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, keys.p, keys2.p, vals.p, ix->d_pos, (uint32_t)len, 0,
-                                                     2 * k + 1, h->stream)); /* stable: positions ascend inside a bucket */
-        hipLaunchKernelGGL(map_bucket_offsets_kernel, dim3(map_grid(nb, h)), dim3(256), 0, h->stream, (const uint32_t*)keys2.p,
-                           (unsigned long long)len, nb, ix->d_off);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    } else {
-        HIPCHK(h, hipMemsetAsync(ix->d_off, 0, sizeof(uint32_t) * nb, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    *out = ix.release();
-    return ASM_OK;
-}
-
-int asm_index_free(asm_handle* h, asm_index* ix) {
-    (void)h;
-    delete ix;
-    return ASM_OK;
-}
-
-/* Greedy on the windows of the mapped items of one chunk (d_list: their indices into d_hits; d_iread: each item's read, NULL when
- * item i is read i); costs into d_cost[q] */
-static int map_greedy(asm_handle* h, const asm_index* ix, const char* d_reads, const uint32_t* d_roff, const MapHit* d_hits,
-                      const uint32_t* d_iread, const uint32_t* d_list, int64_t nl, int maxm, int greedy_k, int32_t* d_cost) {
-    BatchPtr b;
-    int rc = batch_new(h, nl, ASM_GREEDY_CLEAN, "asm_map_reads", b);
-    if (rc) return rc;
-    const size_t cnt = (size_t)nl + 1;
-    Scratch<uint32_t> qlen(h), wlen(h);
-    Scratch<void> tmp(h);
-    HIPCHK(h, qlen.alloc(sizeof(uint32_t) * cnt));
-    HIPCHK(h, wlen.alloc(sizeof(uint32_t) * cnt));
-    HIPCHK(h, batch_alloc(b.get(), &b->d_read_off, sizeof(uint32_t) * cnt));
-    HIPCHK(h, batch_alloc(b.get(), &b->d_ref_off, sizeof(uint32_t) * cnt));
-    hipLaunchKernelGGL(map_greedy_lengths_kernel, dim3(grid_for(nl + 1)), dim3(ASM_BLOCK), 0, h->stream, d_list, d_iread, (long)nl,
-                       d_roff, d_hits, (const unsigned long long*)ix->d_seq_off, qlen.p, wlen.p);
-    HIPCHK(h, hipGetLastError());
-    size_t tmp_bytes = 0;
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, qlen.p, b->d_read_off, (int)cnt, h->stream));
-    HIPCHK(h, tmp.alloc(tmp_bytes + 16));
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, qlen.p, b->d_read_off, (int)cnt, h->stream));
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, wlen.p, b->d_ref_off, (int)cnt, h->stream));
-    uint32_t tot[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(&tot[0], b->d_read_off + nl, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&tot[1], b->d_ref_off + nl, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    b->reads_bytes = tot[0], b->refs_bytes = tot[1];
-    b->maxlen = maxm + 1; /* the window is at most one base longer than the read */
-    HIPCHK(h, batch_alloc(b.get(), &b->d_reads, b->reads_bytes + 16));
-    HIPCHK(h, batch_alloc(b.get(), &b->d_refs, b->refs_bytes + 16));
-    hipLaunchKernelGGL(map_greedy_gather_kernel, dim3(map_grid((uint64_t)nl * 64, h)), dim3(256), 0, h->stream, d_list, d_iread,
-                       (long)nl, d_reads, d_roff, d_hits, (const char*)ix->d_text, (const unsigned long long*)ix->d_seq_off,
-                       (const uint32_t*)b->d_read_off, (const uint32_t*)b->d_ref_off, b->d_reads, b->d_refs);
-    HIPCHK(h, hipGetLastError());
-    rc = batch_finish(h, b.get());
-    if (rc) return rc;
-    asm_params gp;
-    asm_default_params(&gp);
-    gp.k = greedy_k, gp.x = gp.o = gp.e = 1, gp.alignment_type = ASM_ALIGN_GLOBAL;
-    return asm_align_batch_async(h, b.get(), ASM_GREEDY, &gp, d_cost);
-}
-
-} /* extern "C": the launchers below are templates */
-
-/* asm_map_reads_all's run buffer: records [0, cap) of key / val; *counter counts every record a verify-all launch produced */
-struct MapRunBuf {
-    unsigned long long* counter;
-    unsigned long long cap;
-    unsigned long long* key;
-    uint32_t* val;
-};
-
-/* finish: fa; verify: keys; verify-all: rb (the others unused) */
-template <int W>
-static hipError_t map_launch_verify_finish(asm_handle* h, bool finish, const MapCand* cand, unsigned long long nc, const char* d_reads,
-                                           const uint32_t* d_roff, const asm_index* ix, int e, unsigned long long* keys,
-                                           const MapFinishArgs& fa, const MapRunBuf* rb) {
-    if (finish && fa.iread)
-        hipLaunchKernelGGL((map_finish_kernel<W, true>), dim3(map_grid((uint64_t)fa.n, h)), dim3(256), 0, h->stream, fa);
-    else if (finish)
-        hipLaunchKernelGGL((map_finish_kernel<W, false>), dim3(map_grid((uint64_t)fa.n, h)), dim3(256), 0, h->stream, fa);
-    else if (rb)
-        hipLaunchKernelGGL(map_verify_all_kernel<W>, dim3(map_grid(nc, h)), dim3(256), 0, h->stream, cand, nc, d_reads, d_roff,
-                           (const char*)ix->d_text, e, rb->counter, rb->cap, rb->key, rb->val);
-    else
-        hipLaunchKernelGGL(map_verify_kernel<W>, dim3(map_grid(nc, h)), dim3(256), 0, h->stream, cand, nc, d_reads, d_roff,
-                           (const char*)ix->d_text, (const unsigned long long*)ix->d_seq_off, e, keys);
-    return hipGetLastError();
-}
-
-static hipError_t map_dispatch(asm_handle* h, int maxm, bool finish, const MapCand* cand, unsigned long long nc, const char* d_reads,
-                               const uint32_t* d_roff, const asm_index* ix, int e, unsigned long long* keys, const MapFinishArgs& fa,
-                               const MapRunBuf* rb = nullptr) {
-    const int words = (maxm + 63) / 64;
-    if (words <= 1) return map_launch_verify_finish<1>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa, rb);
-    if (words <= 2) return map_launch_verify_finish<2>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa, rb);
-    if (words <= 4) return map_launch_verify_finish<4>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa, rb);
-    return map_launch_verify_finish<8>(h, finish, cand, nc, d_reads, d_roff, ix, e, keys, fa, rb);
-}
-
-/* asm_map_pairs' rescue pass: one thread per (anchor, tile of ends); grid-stride over the anchor count the pair kernel left on the
- * device (at most 2 np anchors) */
-template <int W>
-static hipError_t map_launch_rescue(asm_handle* h, const MapPairArgs& pa, const char* d_reads, const asm_index* ix, uint32_t ntile,
-                                    unsigned long long* rslot) {
-    hipLaunchKernelGGL(map_rescue_kernel<W>, dim3(map_grid((uint64_t)(2 * pa.np) * ntile, h)), dim3(256), 0, h->stream, pa, d_reads,
-                       (const char*)ix->d_text, ntile, rslot);
-    return hipGetLastError();
-}
-
-static hipError_t map_dispatch_rescue(asm_handle* h, int maxm, const MapPairArgs& pa, const char* d_reads, const asm_index* ix,
-                                      uint32_t ntile, unsigned long long* rslot) {
-    const int words = (maxm + 63) / 64;
-    if (words <= 1) return map_launch_rescue<1>(h, pa, d_reads, ix, ntile, rslot);
-    if (words <= 2) return map_launch_rescue<2>(h, pa, d_reads, ix, ntile, rslot);
-    if (words <= 4) return map_launch_rescue<4>(h, pa, d_reads, ix, ntile, rslot);
-    return map_launch_rescue<8>(h, pa, d_reads, ix, ntile, rslot);
-}
-
-extern "C" {
-
-/* The front of a chunk, shared by both mapping calls: reads uploaded and upper-cased, per-read flags cleared, every work item's
- * candidates counted (map_seed_count_kernel) and numbered (exclusive scan); total = all candidates of the chunk. */
-struct MapFront {
-    std::vector<uint32_t> roff;
-    int maxm = 0;
-    size_t bytes = 0;
-    int64_t nw = 0;
-    unsigned long long total = 0;
-    MapSeedArgs sa = {};
-    Scratch<char> d_reads;
-    Scratch<uint32_t> d_roff, d_flags;
-    Scratch<unsigned long long> d_cnt, d_base;
-    Scratch<void> tmp;
-    explicit MapFront(asm_handle* h) : d_reads(h), d_roff(h), d_flags(h), d_cnt(h), d_base(h), tmp(h) {}
-};
-
-/* the chunk's reads: one or more runs of reads (asm_map_pairs: the mates 1, then the mates 2), numbered in that order */
-struct MapReadsIn {
-    const char* reads;
-    const uint32_t* read_off; /* n + 1 */
-    int64_t n;
-};
-
-static int map_front(asm_handle* h, const asm_index* ix, const MapReadsIn* in, int n_in, const asm_map_params* p, MapFront& f) {
-    const int S = p->both_strands ? 2 : 1, P = p->max_errors + 1;
-    int64_t n = 0;
-    for (int t = 0; t < n_in; t++) n += in[t].n;
-    f.roff.assign(1, 0u);
-    f.roff.reserve((size_t)n + 1);
-    for (int t = 0; t < n_in; t++) {
-        const uint32_t o = f.roff.back(), *ro = in[t].read_off;
-        for (int64_t i = 1; i <= in[t].n; i++) f.roff.push_back(o + (ro[i] - ro[0]));
-    }
-    for (int64_t i = 0; i < n; i++) f.maxm = std::max(f.maxm, (int)(f.roff[(size_t)i + 1] - f.roff[(size_t)i]));
-    const size_t bytes = f.bytes = f.roff[(size_t)n];
-    const int64_t nw = f.nw = n * S * P;
-    HIPCHK(h, f.d_reads.alloc(bytes + 16));
-    HIPCHK(h, f.d_roff.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
-    HIPCHK(h, f.d_flags.alloc(sizeof(uint32_t) * (size_t)n));
-    HIPCHK(h, f.d_cnt.alloc(sizeof(unsigned long long) * (size_t)nw));
-    HIPCHK(h, f.d_base.alloc(sizeof(unsigned long long) * (size_t)nw));
-    for (int64_t t = 0, o = 0; t < n_in; o += in[t].read_off[in[t].n] - in[t].read_off[0], t++)
-        HIPCHK(h, hipMemcpyAsync(f.d_reads.p + o, in[t].reads + in[t].read_off[0], in[t].read_off[in[t].n] - in[t].read_off[0],
-                                 hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(f.d_roff.p, f.roff.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemsetAsync(f.d_flags.p, 0, sizeof(uint32_t) * (size_t)n, h->stream));
-    hipLaunchKernelGGL(map_upper_kernel, dim3(map_grid(bytes, h)), dim3(256), 0, h->stream, f.d_reads.p, (unsigned long long)bytes);
-    HIPCHK(h, hipGetLastError());
-    MapSeedArgs& sa = f.sa;
-    sa.reads = f.d_reads.p, sa.roff = f.d_roff.p, sa.n = (long)n, sa.S = S, sa.P = P, sa.k = ix->k, sa.e = p->max_errors;
-    sa.max_occ = p->max_occ, sa.text = ix->d_text, sa.ix_off = ix->d_off, sa.ix_pos = ix->d_pos;
-    sa.seq_off = (const unsigned long long*)ix->d_seq_off, sa.n_seqs = (uint32_t)ix->n_seqs;
-    hipLaunchKernelGGL(map_seed_count_kernel, dim3(map_grid((uint64_t)nw, h)), dim3(256), 0, h->stream, sa, f.d_cnt.p, f.d_flags.p);
-    HIPCHK(h, hipGetLastError());
-    size_t tmp_bytes = 0;
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, f.d_cnt.p, f.d_base.p, (int)nw, h->stream));
-    HIPCHK(h, f.tmp.alloc(tmp_bytes + 16));
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(f.tmp.p, tmp_bytes, f.d_cnt.p, f.d_base.p, (int)nw, h->stream));
-    unsigned long long last[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(&last[0], f.d_base.p + nw - 1, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&last[1], f.d_cnt.p + nw - 1, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    f.total = last[0] + last[1];
-    return ASM_OK;
-}
-
-/* one chunk of reads: everything on the device, results into the caller's host arrays */
-static int map_chunk(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
-                     const asm_map_params* p, asm_map_hit* out, uint16_t* cigar_ops, int cigar_cap, uint8_t* cigar_nops) {
-    MapFront f(h);
-    Scratch<uint32_t> d_list(h);
-    Scratch<unsigned long long> d_keys(h);
-    Scratch<MapCand> d_cand(h);
-    Scratch<uint64_t> d_dirs(h);
-    Scratch<MapHit> d_hits(h);
-    Scratch<uint16_t> d_ops(h);
-    Scratch<uint8_t> d_nops(h);
-    Scratch<int32_t> d_cost(h);
-    HIPCHK(h, d_keys.alloc(sizeof(unsigned long long) * (size_t)n));
-    HIPCHK(h, hipMemsetAsync(d_keys.p, 0xff, sizeof(unsigned long long) * (size_t)n, h->stream));
-    const MapReadsIn in = {reads, read_off, n};
-    if (const int rc = map_front(h, ix, &in, 1, p, f)) return rc;
-    const std::vector<uint32_t>& roff = f.roff;
-    const int maxm = f.maxm, P = p->max_errors + 1;
-    const size_t bytes = f.bytes;
-    const int64_t nw = f.nw;
-    const unsigned long long total = f.total;
-    const MapSeedArgs& sa = f.sa;
-    Scratch<char>& d_reads = f.d_reads;
-    Scratch<uint32_t>& d_roff = f.d_roff;
-    Scratch<uint32_t>& d_flags = f.d_flags;
-    /* rounds of at most map_cand_cap candidates: every round sees every work item and emits the part of it that falls in [c0, c1) */
-    const unsigned long long cap = std::min<unsigned long long>(total, (unsigned long long)h->map_cand_cap);
-    MapFinishArgs fa = {};
-    if (total) HIPCHK(h, d_cand.alloc(sizeof(MapCand) * cap));
-    for (unsigned long long c0 = 0; c0 < total; c0 += cap) {
-        const unsigned long long c1 = std::min(total, c0 + cap);
-        hipLaunchKernelGGL(map_seed_emit_kernel, dim3(map_grid((uint64_t)nw, h)), dim3(256), 0, h->stream, sa,
-                           (const unsigned long long*)f.d_base.p, (const unsigned long long*)f.d_cnt.p, c0, c1, d_cand.p);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, map_dispatch(h, maxm, false, d_cand.p, c1 - c0, d_reads.p, d_roff.p, ix, p->max_errors, d_keys.p, fa));
-    }
-    const int ocap = cigar_cap > 0 ? cigar_cap : 0;
-    HIPCHK(h, d_dirs.alloc(sizeof(uint64_t) * (bytes + (size_t)n)));
-    HIPCHK(h, d_hits.alloc(sizeof(MapHit) * (size_t)n));
-    HIPCHK(h, d_ops.alloc(sizeof(uint16_t) * ((size_t)n * ocap + 1)));
-    HIPCHK(h, d_nops.alloc((size_t)n));
-    fa.reads = d_reads.p, fa.roff = d_roff.p, fa.n = (long)n, fa.e = p->max_errors, fa.P = P, fa.k = ix->k, fa.cap = ocap;
-    fa.text = ix->d_text, fa.seq_off = (const unsigned long long*)ix->d_seq_off, fa.keys = d_keys.p, fa.flags = d_flags.p;
-    fa.iread = nullptr, fa.idirs = nullptr, fa.dirs = d_dirs.p, fa.hits = d_hits.p, fa.ops = d_ops.p, fa.nops = d_nops.p;
-    HIPCHK(h, map_dispatch(h, maxm, true, nullptr, 0, d_reads.p, d_roff.p, ix, p->max_errors, d_keys.p, fa));
-    HIPCHK(h, hipMemcpyAsync(out, d_hits.p, sizeof(MapHit) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    if (ocap) {
-        HIPCHK(h, hipMemcpyAsync(cigar_ops, d_ops.p, sizeof(uint16_t) * (size_t)n * ocap, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(cigar_nops, d_nops.p, (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    std::vector<uint32_t> list;
-    int maxmap = 0;
-    for (int64_t i = 0; i < n; i++)
-        if (out[i].flags & ASM_MAP_MAPPED) {
-            list.push_back((uint32_t)i);
-            maxmap = std::max(maxmap, (int)(roff[(size_t)i + 1] - roff[(size_t)i]));
-        }
-    if (list.empty()) return ASM_OK;
-    const int64_t nl = (int64_t)list.size();
-    HIPCHK(h, d_list.alloc(sizeof(uint32_t) * (size_t)nl));
-    HIPCHK(h, d_cost.alloc(sizeof(int32_t) * (size_t)nl));
-    HIPCHK(h, hipMemcpyAsync(d_list.p, list.data(), sizeof(uint32_t) * (size_t)nl, hipMemcpyHostToDevice, h->stream));
-    int rc = map_greedy(h, ix, d_reads.p, d_roff.p, d_hits.p, nullptr, d_list.p, nl, maxmap, p->greedy_k, d_cost.p);
-    if (rc) return rc;
-    std::vector<int32_t> cost((size_t)nl);
-    HIPCHK(h, hipMemcpyAsync(cost.data(), d_cost.p, sizeof(int32_t) * (size_t)nl, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int64_t q = 0; q < nl; q++) out[list[(size_t)q]].greedy_cost = cost[(size_t)q];
-    return ASM_OK;
-}
-
-/* The run records of one chunk (asm_map_reads_all, asm_map_pairs), sorted by (read, s, lo): the seeding rounds of map_chunk with
- * map_verify_all_kernel<W>, then a radix sort.  n < 2^31 reads, so that read << 33 fits the 64-bit run key. */
-struct MapRuns {
-    unsigned long long nr = 0;
-    Scratch<unsigned long long> key;
-    Scratch<uint32_t> val;
-    explicit MapRuns(asm_handle* h) : key(h), val(h) {}
-};
-
-static int map_runs(asm_handle* h, const asm_index* ix, int64_t n, const asm_map_params* p, MapFront& f, MapRuns& out,
-                    const char* who) {
-    const int e = p->max_errors;
-    Scratch<MapCand> d_cand(h);
-    Scratch<unsigned long long> d_counter(h), d_rkey(h);
-    Scratch<uint32_t> d_rval(h);
-    Scratch<void> tmp(h);
-    unsigned long long rcap = 0, nr = 0;
-    HIPCHK(h, d_counter.alloc(sizeof(unsigned long long)));
-    HIPCHK(h, hipMemsetAsync(d_counter.p, 0, sizeof(unsigned long long), h->stream));
-    auto grow = [&](unsigned long long ncap) -> int { /* the run buffer to ncap records, keeping [0, nr) */
-        Scratch<unsigned long long> k2(h);
-        Scratch<uint32_t> v2(h);
-        HIPCHK(h, k2.alloc(sizeof(unsigned long long) * ncap));
-        HIPCHK(h, v2.alloc(sizeof(uint32_t) * ncap));
-        if (nr) {
-            HIPCHK(h, hipMemcpyAsync(k2.p, d_rkey.p, sizeof(unsigned long long) * nr, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(v2.p, d_rval.p, sizeof(uint32_t) * nr, hipMemcpyDeviceToDevice, h->stream));
-        }
-        std::swap(d_rkey.p, k2.p);
-        std::swap(d_rval.p, v2.p);
-        rcap = ncap;
-        return ASM_OK;
-    };
-    /* the seeding rounds of map_chunk.  Before each, the buffer gets room for min(ASM_MAP_RUN_CAP, the round's candidates) more
-     * records (a window mostly gives one interval or none); after it, the run counter tells whether the buffer held the round's
-     * records.  If not, the buffer grows (keeping the earlier rounds' records), the counter goes back and the verify runs again. */
-    const unsigned long long cap = std::min<unsigned long long>(f.total, (unsigned long long)h->map_cand_cap);
-    const MapFinishArgs none = {};
-    if (f.total) HIPCHK(h, d_cand.alloc(sizeof(MapCand) * cap));
-    for (unsigned long long c0 = 0; c0 < f.total; c0 += cap) {
-        const unsigned long long c1 = std::min(f.total, c0 + cap);
-        hipLaunchKernelGGL(map_seed_emit_kernel, dim3(map_grid((uint64_t)f.nw, h)), dim3(256), 0, h->stream, f.sa,
-                           (const unsigned long long*)f.d_base.p, (const unsigned long long*)f.d_cnt.p, c0, c1, d_cand.p);
-        HIPCHK(h, hipGetLastError());
-        const unsigned long long want = nr + std::min(c1 - c0, (unsigned long long)h->map_run_cap);
-        if (want > rcap)
-            if (const int rc = grow(std::max(want, rcap + rcap / 2))) return rc;
-        for (;;) {
-            const MapRunBuf rb = {d_counter.p, rcap, d_rkey.p, d_rval.p};
-            HIPCHK(h, map_dispatch(h, f.maxm, false, d_cand.p, c1 - c0, f.d_reads.p, f.d_roff.p, ix, e, nullptr, none, &rb));
-            unsigned long long got = 0;
-            HIPCHK(h, hipMemcpyAsync(&got, d_counter.p, sizeof(got), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            if (got <= rcap) {
-                nr = got;
-                break;
-            }
-            if (const int rc = grow(std::max(got, 2 * rcap))) return rc;
-            HIPCHK(h, hipMemcpyAsync(d_counter.p, &nr, sizeof(nr), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream)); /* nr is read by the copy above before it may change */
-        }
-    }
-    if (nr > (unsigned long long)INT32_MAX)
-        return fail(h, ASM_EUNSUPPORTED, std::string(who) + ": more than 2^31 - 1 run records in a chunk");
-    /* sort by (read, s, lo): only the bits in use (read < n) */
-    int rbits = 0;
-    while (rbits < 31 && (1ull << rbits) < (unsigned long long)n) rbits++;
-    const int end_bit = MAP_RUN_READ_SHIFT + rbits;
-    HIPCHK(h, out.key.alloc(sizeof(unsigned long long) * (nr + 1)));
-    HIPCHK(h, out.val.alloc(sizeof(uint32_t) * (nr + 1)));
-    if (nr) {
-        size_t tmp_bytes = 0;
-        HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_rkey.p, out.key.p, d_rval.p, out.val.p, (int)nr, 0, end_bit,
-                                                     h->stream));
-        HIPCHK(h, tmp.alloc(tmp_bytes + 16));
-        HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, d_rkey.p, out.key.p, d_rval.p, out.val.p, (int)nr, 0, end_bit,
-                                                     h->stream));
-    }
-    out.nr = nr;
-    return ASM_OK;
-}
-
-/* asm_map_reads_all on one chunk: the sorted run records, the loci selected per read into an item list, then finish and Greedy
- * once per item */
-static int map_chunk_all(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
-                         const asm_map_params* p, int strata, int max_hits, uint32_t* n_hits, asm_map_hit* out, uint16_t* cigar_ops,
-                         int cigar_cap, uint8_t* cigar_nops) {
-    MapFront f(h);
-    const MapReadsIn in = {reads, read_off, n};
-    if (const int rc = map_front(h, ix, &in, 1, p, f)) return rc;
-    const int e = p->max_errors;
-    MapRuns runs(h);
-    if (const int rc = map_runs(h, ix, n, p, f, runs, "asm_map_reads_all")) return rc;
-    const unsigned long long nr = runs.nr;
-    /* loci per read: count, then (host) the item layout, then emit */
-    Scratch<uint32_t> d_nh(h), d_dbest(h), d_ibase(h), d_iread(h), d_list(h);
-    Scratch<unsigned long long> d_dbase(h), d_ikey(h), d_idirs(h);
-    HIPCHK(h, d_nh.alloc(sizeof(uint32_t) * (size_t)n));
-    HIPCHK(h, d_dbest.alloc(sizeof(uint32_t) * (size_t)n));
-    MapSelectArgs sel = {};
-    sel.rkey = runs.key.p, sel.rval = runs.val.p, sel.nr = nr, sel.n = (long)n, sel.e = e, sel.strata = strata, sel.max_hits = max_hits;
-    sel.seq_off = (const unsigned long long*)ix->d_seq_off, sel.n_seqs = (uint32_t)ix->n_seqs, sel.roff = f.d_roff.p;
-    sel.n_hits = d_nh.p, sel.d_best = d_dbest.p;
-    hipLaunchKernelGGL(map_select_count_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(n_hits, d_nh.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    /* items: max(1, min(n_hits, max_hits)) per read, in read-then-rank order; dirs: (m + 1) words per item */
-    std::vector<uint32_t> ibase((size_t)n + 1);
-    std::vector<unsigned long long> dbase((size_t)n);
-    unsigned long long dwords = 0;
-    for (int64_t i = 0; i < n; i++) {
-        const uint32_t ni = n_hits[i] ? std::min<uint32_t>(n_hits[i], (uint32_t)max_hits) : 1u;
-        ibase[(size_t)i + 1] = ibase[(size_t)i] + ni;
-        dbase[(size_t)i] = dwords;
-        dwords += (unsigned long long)ni * (f.roff[(size_t)i + 1] - f.roff[(size_t)i] + 1u);
-    }
-    const int64_t ni = ibase[(size_t)n];
-    HIPCHK(h, d_ibase.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
-    HIPCHK(h, d_dbase.alloc(sizeof(unsigned long long) * (size_t)n));
-    HIPCHK(h, d_iread.alloc(sizeof(uint32_t) * (size_t)ni));
-    HIPCHK(h, d_ikey.alloc(sizeof(unsigned long long) * (size_t)ni));
-    HIPCHK(h, d_idirs.alloc(sizeof(unsigned long long) * (size_t)ni));
-    HIPCHK(h, hipMemcpyAsync(d_ibase.p, ibase.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d_dbase.p, dbase.data(), sizeof(unsigned long long) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    sel.ibase = d_ibase.p, sel.dbase = d_dbase.p, sel.iread = d_iread.p, sel.ikey = d_ikey.p, sel.idirs = d_idirs.p;
-    hipLaunchKernelGGL(map_select_emit_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel);
-    HIPCHK(h, hipGetLastError());
-    /* finish per item */
-    const int ocap = cigar_cap > 0 ? cigar_cap : 0;
-    Scratch<uint64_t> d_dirs(h);
-    Scratch<MapHit> d_hits(h);
-    Scratch<uint16_t> d_ops(h);
-    Scratch<uint8_t> d_nops(h);
-    Scratch<int32_t> d_cost(h);
-    HIPCHK(h, d_dirs.alloc(sizeof(uint64_t) * dwords));
-    HIPCHK(h, d_hits.alloc(sizeof(MapHit) * (size_t)ni));
-    HIPCHK(h, d_ops.alloc(sizeof(uint16_t) * ((size_t)ni * ocap + 1)));
-    HIPCHK(h, d_nops.alloc((size_t)ni));
-    MapFinishArgs fa = {};
-    fa.reads = f.d_reads.p, fa.roff = f.d_roff.p, fa.n = (long)ni, fa.e = e, fa.P = e + 1, fa.k = ix->k, fa.cap = ocap;
-    fa.text = ix->d_text, fa.seq_off = (const unsigned long long*)ix->d_seq_off, fa.keys = d_ikey.p, fa.flags = f.d_flags.p;
-    fa.iread = d_iread.p, fa.idirs = d_idirs.p, fa.dirs = d_dirs.p, fa.hits = d_hits.p, fa.ops = d_ops.p, fa.nops = d_nops.p;
-    HIPCHK(h, map_dispatch(h, f.maxm, true, nullptr, 0, f.d_reads.p, f.d_roff.p, ix, e, nullptr, fa));
-    std::vector<asm_map_hit> hits((size_t)ni);
-    std::vector<uint16_t> ops((size_t)ni * ocap);
-    std::vector<uint8_t> nops((size_t)ni);
-    std::vector<uint32_t> iread((size_t)ni);
-    HIPCHK(h, hipMemcpyAsync(hits.data(), d_hits.p, sizeof(MapHit) * (size_t)ni, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(iread.data(), d_iread.p, sizeof(uint32_t) * (size_t)ni, hipMemcpyDeviceToHost, h->stream));
-    if (ocap) {
-        HIPCHK(h, hipMemcpyAsync(ops.data(), d_ops.p, sizeof(uint16_t) * (size_t)ni * ocap, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(nops.data(), d_nops.p, (size_t)ni, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    /* Greedy per mapped item */
-    std::vector<uint32_t> list;
-    int maxmap = 0;
-    for (int64_t q = 0; q < ni; q++)
-        if (hits[(size_t)q].flags & ASM_MAP_MAPPED) {
-            list.push_back((uint32_t)q);
-            const uint32_t i = iread[(size_t)q];
-            maxmap = std::max(maxmap, (int)(f.roff[(size_t)i + 1] - f.roff[(size_t)i]));
-        }
-    if (!list.empty()) {
-        const int64_t nl = (int64_t)list.size();
-        HIPCHK(h, d_list.alloc(sizeof(uint32_t) * (size_t)nl));
-        HIPCHK(h, d_cost.alloc(sizeof(int32_t) * (size_t)nl));
-        HIPCHK(h, hipMemcpyAsync(d_list.p, list.data(), sizeof(uint32_t) * (size_t)nl, hipMemcpyHostToDevice, h->stream));
-        const int rc = map_greedy(h, ix, f.d_reads.p, f.d_roff.p, d_hits.p, d_iread.p, d_list.p, nl, maxmap, p->greedy_k, d_cost.p);
-        if (rc) return rc;
-        std::vector<int32_t> cost((size_t)nl);
-        HIPCHK(h, hipMemcpyAsync(cost.data(), d_cost.p, sizeof(int32_t) * (size_t)nl, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (int64_t q = 0; q < nl; q++) hits[list[(size_t)q]].greedy_cost = cost[(size_t)q];
-    }
-    /* into the caller's [n][max_hits] slots (a read's items are contiguous); the flags that depend on the rank are set here.  The
-     * CIGAR rows of unused slots are not written: their cigar_nops is 0. */
-    const asm_map_hit unused = {-1, 0, 0, -1, 0, 0, -1};
-    for (int64_t i = 0; i < n; i++) {
-        const uint32_t q0 = ibase[(size_t)i], cnt = ibase[(size_t)i + 1] - q0;
-        const size_t o = (size_t)i * max_hits;
-        std::copy(hits.begin() + q0, hits.begin() + q0 + cnt, out + o);
-        for (uint32_t t = 1; t < cnt; t++) out[o + t].flags |= ASM_MAP_SECONDARY;
-        if (n_hits[i] > (uint32_t)max_hits)
-            for (uint32_t t = 0; t < cnt; t++) out[o + t].flags |= ASM_MAP_HITS_TRUNCATED;
-        std::fill(out + o + cnt, out + o + max_hits, unused);
-        if (ocap) {
-            std::copy(ops.begin() + (size_t)q0 * ocap, ops.begin() + (size_t)(q0 + cnt) * ocap, cigar_ops + o * ocap);
-            std::copy(nops.begin() + q0, nops.begin() + q0 + cnt, cigar_nops + o);
-            std::fill(cigar_nops + o + cnt, cigar_nops + o + max_hits, (uint8_t)0);
-        }
-    }
-    return ASM_OK;
-}
-
-int asm_map_reads_all(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
-                      const asm_map_params* p, int strata, int max_hits, uint32_t* n_hits, asm_map_hit* out, uint16_t* cigar_ops,
-                      int cigar_cap, uint8_t* cigar_nops) {
-    if (!p || !ix || n < 0 || !read_off || (n > 0 && (!reads || !out || !n_hits)))
-        return fail(h, ASM_EINVAL, "asm_map_reads_all: bad arguments");
-    if (p->max_errors < 0 || p->max_errors > ASM_MAP_MAX_ERRORS) return fail(h, ASM_EINVAL, "asm_map_reads_all: max_errors must be in [0, 15]");
-    if (p->both_strands != 0 && p->both_strands != 1) return fail(h, ASM_EINVAL, "asm_map_reads_all: both_strands must be 0 or 1");
-    if (p->max_occ < 0) return fail(h, ASM_EINVAL, "asm_map_reads_all: max_occ must be >= 0");
-    if (p->greedy_k < 0 || p->greedy_k > ASM_GREEDY_MAX_K) return fail(h, ASM_EINVAL, "asm_map_reads_all: greedy_k must be in [0, 50]");
-    if (strata < 0 || strata > ASM_MAP_MAX_ERRORS) return fail(h, ASM_EINVAL, "asm_map_reads_all: strata must be in [0, 15]");
-    if (max_hits < 1 || max_hits > ASM_MAP_MAX_HITS) return fail(h, ASM_EINVAL, "asm_map_reads_all: max_hits must be in [1, 256]");
-    if (cigar_cap < 0 || (cigar_cap > 0 && (!cigar_ops || !cigar_nops)))
-        return fail(h, ASM_EINVAL, "asm_map_reads_all: cigar_cap > 0 needs cigar_ops and cigar_nops");
-    for (int64_t i = 0; i < n; i++) {
-        if (read_off[i + 1] < read_off[i]) return fail(h, ASM_EINVAL, "asm_map_reads_all: read offsets must be non-decreasing");
-        const uint32_t m = read_off[i + 1] - read_off[i];
-        if (m < 1 || m > ASM_MAP_MAX_READ) return fail(h, ASM_EINVAL, "asm_map_reads_all: every read must have 1 to 511 bytes");
-    }
-    if (!h) return fail(h, ASM_EINVAL, "asm_map_reads_all: NULL handle");
-    if (ix->device != h->device) return fail(h, ASM_EINVAL, "asm_map_reads_all: the index lives on another device");
-    HIPCHK(h, hipSetDevice(h->device));
-    const int64_t step = std::min<int64_t>(h->map_chunk, (int64_t)1 << 30); /* the run key holds the read in its top 31 bits */
-    for (int64_t c0 = 0; c0 < n; c0 += step) {
-        const int64_t c1 = std::min(n, c0 + step);
-        const size_t o = (size_t)c0 * max_hits;
-        const int rc = map_chunk_all(h, ix, c1 - c0, reads, read_off + c0, p, strata, max_hits, n_hits + c0, out + o,
-                                     cigar_cap > 0 ? cigar_ops + o * cigar_cap : nullptr, cigar_cap, cigar_cap > 0 ? cigar_nops + o : nullptr);
-        if (rc) return rc;
-    }
-    return ASM_OK;
-}
-
-/* asm_map_pairs' front on one chunk of np pairs (mate 1 of pair p = read p, mate 2 = read np + p): the sorted run records, each
- * read's loci listed (count, scan, emit), the pairing and the rescue of pairs without a concordant pair.  asm_map_pairs_all shares it. */
-struct MapPairFront {
-    MapFront f;
-    MapRuns runs;
-    Scratch<uint32_t> d_nh, d_dbest, d_lbase, d_lsplit, d_nconc, d_anchors, d_nanch;
-    Scratch<unsigned long long> d_lkey, d_lbest, d_ikey, d_rslot;
-    Scratch<uint8_t> d_state;
-    Scratch<void> tmp;
-    MapPairArgs pa = {};
-    explicit MapPairFront(asm_handle* h)
-        : f(h), runs(h), d_nh(h), d_dbest(h), d_lbase(h), d_lsplit(h), d_nconc(h), d_anchors(h), d_nanch(h), d_lkey(h), d_lbest(h),
-          d_ikey(h), d_rslot(h), d_state(h), tmp(h) {}
-};
-
-static int map_pairs_front(asm_handle* h, const asm_index* ix, int64_t np, const char* reads1, const uint32_t* off1,
-                           const char* reads2, const uint32_t* off2, const asm_map_params* p, const asm_pair_params* pp,
-                           const char* who, MapPairFront& pf) {
-    const int64_t n = 2 * np;
-    MapFront& f = pf.f;
-    const MapReadsIn in[2] = {{reads1, off1, np}, {reads2, off2, np}};
-    if (const int rc = map_front(h, ix, in, 2, p, f)) return rc;
-    const int e = p->max_errors;
-    MapRuns& runs = pf.runs;
-    if (const int rc = map_runs(h, ix, n, p, f, runs, who)) return rc;
-    /* each read's loci (strata = e: all of them), listed in walk order */
-    HIPCHK(h, pf.d_nh.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
-    HIPCHK(h, pf.d_dbest.alloc(sizeof(uint32_t) * (size_t)n));
-    HIPCHK(h, pf.d_lbase.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
-    MapSelectArgs sel = {};
-    sel.rkey = runs.key.p, sel.rval = runs.val.p, sel.nr = runs.nr, sel.n = (long)n, sel.e = e, sel.strata = e, sel.max_hits = 1;
-    sel.seq_off = (const unsigned long long*)ix->d_seq_off, sel.n_seqs = (uint32_t)ix->n_seqs, sel.roff = f.d_roff.p;
-    sel.n_hits = pf.d_nh.p, sel.d_best = pf.d_dbest.p;
-    HIPCHK(h, hipMemsetAsync(pf.d_nh.p + n, 0, sizeof(uint32_t), h->stream));
-    hipLaunchKernelGGL(map_select_count_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel);
-    HIPCHK(h, hipGetLastError());
-    size_t tmp_bytes = 0;
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, pf.d_nh.p, pf.d_lbase.p, (int)(n + 1), h->stream));
-    HIPCHK(h, pf.tmp.alloc(tmp_bytes + 16));
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(pf.tmp.p, tmp_bytes, pf.d_nh.p, pf.d_lbase.p, (int)(n + 1), h->stream));
-    uint32_t nloci = 0;
-    HIPCHK(h, hipMemcpyAsync(&nloci, pf.d_lbase.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, pf.d_lkey.alloc(sizeof(unsigned long long) * ((size_t)nloci + 1)));
-    HIPCHK(h, pf.d_lsplit.alloc(sizeof(uint32_t) * (size_t)n));
-    HIPCHK(h, pf.d_lbest.alloc(sizeof(unsigned long long) * (size_t)n));
-    hipLaunchKernelGGL(map_loci_emit_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel, (const uint32_t*)pf.d_lbase.p,
-                       pf.d_lkey.p, pf.d_lsplit.p, pf.d_lbest.p);
-    HIPCHK(h, hipGetLastError());
-    /* pairing */
-    HIPCHK(h, pf.d_ikey.alloc(sizeof(unsigned long long) * (size_t)n));
-    HIPCHK(h, pf.d_nconc.alloc(sizeof(uint32_t) * (size_t)np));
-    HIPCHK(h, pf.d_state.alloc((size_t)np));
-    HIPCHK(h, pf.d_nanch.alloc(sizeof(uint32_t)));
-    HIPCHK(h, hipMemsetAsync(pf.d_nanch.p, 0, sizeof(uint32_t), h->stream));
-    const bool rescue = pp->rescue_errors >= 0;
-    if (rescue) {
-        HIPCHK(h, pf.d_anchors.alloc(sizeof(uint32_t) * (size_t)n));
-        HIPCHK(h, pf.d_rslot.alloc(sizeof(unsigned long long) * (size_t)n));
-        HIPCHK(h, hipMemsetAsync(pf.d_rslot.p, 0xff, sizeof(unsigned long long) * (size_t)n, h->stream));
-    }
-    MapPairArgs& pa = pf.pa;
-    pa.np = (long)np, pa.roff = f.d_roff.p, pa.lbase = pf.d_lbase.p, pa.lsplit = pf.d_lsplit.p, pa.lbest = pf.d_lbest.p;
-    pa.lkey = pf.d_lkey.p, pa.min_insert = pp->min_insert, pa.max_insert = pp->max_insert, pa.rescue = pp->rescue_errors;
-    pa.ikey = pf.d_ikey.p, pa.n_conc = pf.d_nconc.p, pa.state = pf.d_state.p, pa.anchors = pf.d_anchors.p, pa.n_anchors = pf.d_nanch.p;
-    pa.rslot = pf.d_rslot.p, pa.seq_off = (const unsigned long long*)ix->d_seq_off;
-    hipLaunchKernelGGL(map_pair_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, pa);
-    HIPCHK(h, hipGetLastError());
-    if (rescue) {
-        const uint32_t ntile = (uint32_t)((pp->max_insert - pp->min_insert + MAP_RESCUE_TILE) / MAP_RESCUE_TILE);
-        HIPCHK(h, map_dispatch_rescue(h, f.maxm, pa, f.d_reads.p, ix, ntile, pf.d_rslot.p));
-        hipLaunchKernelGGL(map_rescue_pick_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, pa);
-        HIPCHK(h, hipGetLastError());
-    }
-    return ASM_OK;
-}
-
-/* asm_map_pairs' answer after map_pairs_front: finish and Greedy on the identity list (one item per read), then pair q's two records
- * into out[2 q slots + 0, 1] with the pair flags, tlen[q slots], n_concordant[q] and the CIGAR rows of those records (slots:
- * records per mate and pair in the caller's arrays, 1 for asm_map_pairs) */
-static int map_pairs_primary(asm_handle* h, const asm_index* ix, int64_t np, const asm_map_params* p, MapPairFront& pf, int slots,
-                             asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant, uint16_t* cigar_ops, int cigar_cap,
-                             uint8_t* cigar_nops) {
-    const int64_t n = 2 * np;
-    const int e = p->max_errors;
-    MapFront& f = pf.f;
-    const int ocap = cigar_cap > 0 ? cigar_cap : 0;
-    Scratch<uint32_t> d_list(h);
-    Scratch<uint64_t> d_dirs(h);
-    Scratch<MapHit> d_hits(h);
-    Scratch<uint16_t> d_ops(h);
-    Scratch<uint8_t> d_nops(h);
-    Scratch<int32_t> d_cost(h);
-    HIPCHK(h, d_dirs.alloc(sizeof(uint64_t) * (f.bytes + (size_t)n)));
-    HIPCHK(h, d_hits.alloc(sizeof(MapHit) * (size_t)n));
-    HIPCHK(h, d_ops.alloc(sizeof(uint16_t) * ((size_t)n * ocap + 1)));
-    HIPCHK(h, d_nops.alloc((size_t)n));
-    MapFinishArgs fa = {};
-    fa.reads = f.d_reads.p, fa.roff = f.d_roff.p, fa.n = (long)n, fa.e = e, fa.P = e + 1, fa.k = ix->k, fa.cap = ocap;
-    fa.text = ix->d_text, fa.seq_off = (const unsigned long long*)ix->d_seq_off, fa.keys = pf.d_ikey.p, fa.flags = f.d_flags.p;
-    fa.iread = nullptr, fa.idirs = nullptr, fa.dirs = d_dirs.p, fa.hits = d_hits.p, fa.ops = d_ops.p, fa.nops = d_nops.p;
-    HIPCHK(h, map_dispatch(h, f.maxm, true, nullptr, 0, f.d_reads.p, f.d_roff.p, ix, e, nullptr, fa));
-    std::vector<asm_map_hit> hits((size_t)n);
-    std::vector<uint16_t> ops((size_t)n * ocap);
-    std::vector<uint8_t> nops((size_t)n), state((size_t)np);
-    HIPCHK(h, hipMemcpyAsync(hits.data(), d_hits.p, sizeof(MapHit) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(state.data(), pf.d_state.p, (size_t)np, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(n_concordant, pf.d_nconc.p, sizeof(uint32_t) * (size_t)np, hipMemcpyDeviceToHost, h->stream));
-    if (ocap) {
-        HIPCHK(h, hipMemcpyAsync(ops.data(), d_ops.p, sizeof(uint16_t) * (size_t)n * ocap, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(nops.data(), d_nops.p, (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    std::vector<uint32_t> list;
-    int maxmap = 0;
-    for (int64_t i = 0; i < n; i++)
-        if (hits[(size_t)i].flags & ASM_MAP_MAPPED) {
-            list.push_back((uint32_t)i);
-            maxmap = std::max(maxmap, (int)(f.roff[(size_t)i + 1] - f.roff[(size_t)i]));
-        }
-    if (!list.empty()) {
-        const int64_t nl = (int64_t)list.size();
-        HIPCHK(h, d_list.alloc(sizeof(uint32_t) * (size_t)nl));
-        HIPCHK(h, d_cost.alloc(sizeof(int32_t) * (size_t)nl));
-        HIPCHK(h, hipMemcpyAsync(d_list.p, list.data(), sizeof(uint32_t) * (size_t)nl, hipMemcpyHostToDevice, h->stream));
-        const int rc = map_greedy(h, ix, f.d_reads.p, f.d_roff.p, d_hits.p, nullptr, d_list.p, nl, maxmap, p->greedy_k, d_cost.p);
-        if (rc) return rc;
-        std::vector<int32_t> cost((size_t)nl);
-        HIPCHK(h, hipMemcpyAsync(cost.data(), d_cost.p, sizeof(int32_t) * (size_t)nl, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (int64_t q = 0; q < nl; q++) hits[list[(size_t)q]].greedy_cost = cost[(size_t)q];
-    }
-    /* into the caller's records; the pair flags and tlen are set here */
-    for (int64_t q = 0; q < np; q++) {
-        const size_t r0 = (size_t)(2 * q) * slots; /* pair q's first record */
-        asm_map_hit* o = out + r0;
-        o[0] = hits[(size_t)q], o[1] = hits[(size_t)(np + q)];
-        const uint8_t st = state[(size_t)q];
-        if (st == MAP_PAIR_CONCORDANT || st == MAP_PAIR_RESCUED1 || st == MAP_PAIR_RESCUED2) {
-            o[0].flags |= ASM_MAP_PROPER_PAIR, o[1].flags |= ASM_MAP_PROPER_PAIR;
-            if (st == MAP_PAIR_RESCUED1) o[0].flags |= ASM_MAP_RESCUED;
-            if (st == MAP_PAIR_RESCUED2) o[1].flags |= ASM_MAP_RESCUED;
-        }
-        const bool same = (o[0].flags & ASM_MAP_MAPPED) && (o[1].flags & ASM_MAP_MAPPED) && o[0].seq_id == o[1].seq_id;
-        tlen[(size_t)q * slots] = same ? (int32_t)(std::max(o[0].end, o[1].end) - std::min(o[0].pos, o[1].pos)) : 0;
-        if (ocap)
-            for (int t = 0; t < 2; t++) {
-                const size_t i = (size_t)(t ? np + q : q);
-                std::copy(ops.begin() + i * ocap, ops.begin() + (i + 1) * ocap, cigar_ops + (r0 + t) * ocap);
-                cigar_nops[r0 + t] = nops[i];
-            }
-    }
-    return ASM_OK;
-}
-
-/* asm_map_pairs on one chunk of np pairs: the front, then finish and Greedy on the identity list */
-static int map_chunk_pairs(asm_handle* h, const asm_index* ix, int64_t np, const char* reads1, const uint32_t* off1,
-                           const char* reads2, const uint32_t* off2, const asm_map_params* p, const asm_pair_params* pp,
-                           asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant, uint16_t* cigar_ops, int cigar_cap,
-                           uint8_t* cigar_nops) {
-    MapPairFront pf(h);
-    if (const int rc = map_pairs_front(h, ix, np, reads1, off1, reads2, off2, p, pp, "asm_map_pairs", pf)) return rc;
-    return map_pairs_primary(h, ix, np, p, pf, 1, out, tlen, n_concordant, cigar_ops, cigar_cap, cigar_nops);
-}
-
-int asm_map_pairs(asm_handle* h, const asm_index* ix, int64_t n, const char* reads1, const uint32_t* off1, const char* reads2,
-                  const uint32_t* off2, const asm_map_params* p, const asm_pair_params* pp, asm_map_hit* out, int32_t* tlen,
-                  uint32_t* n_concordant, uint16_t* cigar_ops, int cigar_cap, uint8_t* cigar_nops) {
-    if (!p || !pp || !ix || n < 0 || !off1 || !off2 || (n > 0 && (!reads1 || !reads2 || !out || !tlen || !n_concordant)))
-        return fail(h, ASM_EINVAL, "asm_map_pairs: bad arguments");
-    if (p->max_errors < 0 || p->max_errors > ASM_MAP_MAX_ERRORS) return fail(h, ASM_EINVAL, "asm_map_pairs: max_errors must be in [0, 15]");
-    if (p->both_strands != 1) return fail(h, ASM_EINVAL, "asm_map_pairs: both_strands must be 1");
-    if (p->max_occ < 0) return fail(h, ASM_EINVAL, "asm_map_pairs: max_occ must be >= 0");
-    if (p->greedy_k < 0 || p->greedy_k > ASM_GREEDY_MAX_K) return fail(h, ASM_EINVAL, "asm_map_pairs: greedy_k must be in [0, 50]");
-    if (pp->min_insert < 0 || pp->min_insert > pp->max_insert || pp->max_insert > ASM_MAP_MAX_INSERT)
-        return fail(h, ASM_EINVAL, "asm_map_pairs: need 0 <= min_insert <= max_insert <= 8192");
-    if (pp->rescue_errors < -1 || pp->rescue_errors > ASM_MAP_MAX_ERRORS)
-        return fail(h, ASM_EINVAL, "asm_map_pairs: rescue_errors must be -1 (off) or in [0, 15]");
-    if (cigar_cap < 0 || (cigar_cap > 0 && (!cigar_ops || !cigar_nops)))
-        return fail(h, ASM_EINVAL, "asm_map_pairs: cigar_cap > 0 needs cigar_ops and cigar_nops");
-    for (const uint32_t* ro : {off1, off2})
-        for (int64_t i = 0; i < n; i++) {
-            if (ro[i + 1] < ro[i]) return fail(h, ASM_EINVAL, "asm_map_pairs: read offsets must be non-decreasing");
-            const uint32_t m = ro[i + 1] - ro[i];
-            if (m < 1 || m > ASM_MAP_MAX_READ) return fail(h, ASM_EINVAL, "asm_map_pairs: every mate must have 1 to 511 bytes");
-        }
-    if (n > 0 && (uint64_t)(off1[n] - off1[0]) + (off2[n] - off2[0]) >= 0xffffffffull)
-        return fail(h, ASM_EUNSUPPORTED, "asm_map_pairs: both mates' bytes must stay below 2^32");
-    if (!h) return fail(h, ASM_EINVAL, "asm_map_pairs: NULL handle");
-    if (ix->device != h->device) return fail(h, ASM_EINVAL, "asm_map_pairs: the index lives on another device");
-    HIPCHK(h, hipSetDevice(h->device));
-    /* at most map_chunk / 2 pairs per chunk; the run key holds the read (2 per pair) in its top 31 bits */
-    const int64_t step = std::max<int64_t>(1, std::min<int64_t>(h->map_chunk, (int64_t)1 << 30) / 2);
-    for (int64_t c0 = 0; c0 < n; c0 += step) {
-        const int64_t c1 = std::min(n, c0 + step);
-        const size_t o = (size_t)c0 * 2;
-        const int rc = map_chunk_pairs(h, ix, c1 - c0, reads1, off1 + c0, reads2, off2 + c0, p, pp, out + o, tlen + c0, n_concordant + c0,
-                                       cigar_cap > 0 ? cigar_ops + o * cigar_cap : nullptr, cigar_cap,
-                                       cigar_cap > 0 ? cigar_nops + o : nullptr);
-        if (rc) return rc;
-    }
-    return ASM_OK;
-}
-
-/* asm_map_pairs_all on one chunk of np pairs: the front and the primary answer of asm_map_pairs (rank 0), then the eligible pairs
- * counted, ranks >= 1 listed as items (mate 1, mate 2 per pair) in pair order, their finish and Greedy, and the scatter into the
- * caller's [np][max_pairs][2] slots.  The slots beyond rank 0 are first filled as unused on host threads, while the device works. */
-static int map_chunk_pairs_all(asm_handle* h, const asm_index* ix, int64_t np, const char* reads1, const uint32_t* off1,
-                               const char* reads2, const uint32_t* off2, const asm_map_params* p, const asm_pair_params* pp, int strata,
-                               int max_pairs, uint32_t* n_pairs, asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant,
-                               uint16_t* cigar_ops, int cigar_cap, uint8_t* cigar_nops) {
-    const int e = p->max_errors, ocap = cigar_cap > 0 ? cigar_cap : 0;
-    const asm_map_hit unused = {-1, 0, 0, -1, 0, 0, -1};
-    std::vector<std::thread> fill;
-    if (max_pairs > 1) {
-        const int64_t nt = std::min<int64_t>(4, std::max<int64_t>(1, np / 4096));
-        for (int64_t t = 0; t < nt; t++)
-            fill.emplace_back([=]() {
-                for (int64_t q = np * t / nt; q < np * (t + 1) / nt; q++) {
-                    const size_t o = (size_t)q * max_pairs;
-                    std::fill(out + 2 * (o + 1), out + 2 * (o + max_pairs), unused);
-                    std::fill(tlen + o + 1, tlen + o + max_pairs, 0);
-                    if (ocap) std::fill(cigar_nops + 2 * (o + 1), cigar_nops + 2 * (o + max_pairs), (uint8_t)0);
-                }
-            });
-    }
-    struct Join {
-        std::vector<std::thread>& t;
-        ~Join() {
-            for (std::thread& x : t) x.join();
-        }
-    } join{fill};
-    MapPairFront pf(h);
-    if (const int rc = map_pairs_front(h, ix, np, reads1, off1, reads2, off2, p, pp, "asm_map_pairs_all", pf)) return rc;
-    MapFront& f = pf.f;
-    /* eligible pairs per pair, and the layout of the secondary items (device scans) */
-    Scratch<uint32_t> d_np(h), d_sums(h), d_iread(h), d_list(h);
-    Scratch<unsigned long long> d_nitem(h), d_ndirs(h), d_ibase(h), d_dbase(h), d_ikey(h), d_idirs(h);
-    Scratch<void> tmp(h);
-    HIPCHK(h, d_np.alloc(sizeof(uint32_t) * (size_t)np));
-    HIPCHK(h, d_sums.alloc(sizeof(uint32_t) * (size_t)np));
-    for (Scratch<unsigned long long>* x : {&d_nitem, &d_ndirs, &d_ibase, &d_dbase})
-        HIPCHK(h, x->alloc(sizeof(unsigned long long) * ((size_t)np + 1)));
-    HIPCHK(h, hipMemsetAsync(d_nitem.p + np, 0, sizeof(unsigned long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(d_ndirs.p + np, 0, sizeof(unsigned long long), h->stream));
-    MapPairAllArgs aa = {};
-    aa.pa = pf.pa, aa.strata = strata, aa.max_pairs = max_pairs, aa.n_pairs = d_np.p, aa.sums = d_sums.p, aa.nitem = d_nitem.p;
-    aa.ndirs = d_ndirs.p, aa.ibase = d_ibase.p, aa.dbase = d_dbase.p;
-    hipLaunchKernelGGL(map_pair_count_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, aa);
-    HIPCHK(h, hipGetLastError());
-    size_t tmp_bytes = 0;
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_nitem.p, d_ibase.p, (int)(np + 1), h->stream));
-    HIPCHK(h, tmp.alloc(tmp_bytes + 16));
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, d_nitem.p, d_ibase.p, (int)(np + 1), h->stream));
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, d_ndirs.p, d_dbase.p, (int)(np + 1), h->stream));
-    unsigned long long tot[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(n_pairs, d_np.p, sizeof(uint32_t) * (size_t)np, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&tot[0], d_ibase.p + np, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&tot[1], d_dbase.p + np, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const int64_t ni = (int64_t)tot[0];
-    /* ranks >= 1: items, finish (the item-list instantiation of asm_map_reads_all) */
-    Scratch<uint64_t> d_dirs(h);
-    Scratch<MapHit> d_hits(h);
-    Scratch<uint16_t> d_ops(h);
-    Scratch<uint8_t> d_nops(h);
-    Scratch<int32_t> d_cost(h);
-    if (ni) {
-        HIPCHK(h, d_iread.alloc(sizeof(uint32_t) * (size_t)ni));
-        HIPCHK(h, d_ikey.alloc(sizeof(unsigned long long) * (size_t)ni));
-        HIPCHK(h, d_idirs.alloc(sizeof(unsigned long long) * (size_t)ni));
-        HIPCHK(h, d_dirs.alloc(sizeof(uint64_t) * tot[1]));
-        HIPCHK(h, d_hits.alloc(sizeof(MapHit) * (size_t)ni));
-        HIPCHK(h, d_ops.alloc(sizeof(uint16_t) * ((size_t)ni * ocap + 1)));
-        HIPCHK(h, d_nops.alloc((size_t)ni));
-        aa.iread = d_iread.p, aa.ikey = d_ikey.p, aa.idirs = d_idirs.p;
-        hipLaunchKernelGGL(map_pair_emit_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, aa);
-        HIPCHK(h, hipGetLastError());
-        MapFinishArgs fa = {};
-        fa.reads = f.d_reads.p, fa.roff = f.d_roff.p, fa.n = (long)ni, fa.e = e, fa.P = e + 1, fa.k = ix->k, fa.cap = ocap;
-        fa.text = ix->d_text, fa.seq_off = (const unsigned long long*)ix->d_seq_off, fa.keys = d_ikey.p, fa.flags = f.d_flags.p;
-        fa.iread = d_iread.p, fa.idirs = d_idirs.p, fa.dirs = d_dirs.p, fa.hits = d_hits.p, fa.ops = d_ops.p, fa.nops = d_nops.p;
-        HIPCHK(h, map_dispatch(h, f.maxm, true, nullptr, 0, f.d_reads.p, f.d_roff.p, ix, e, nullptr, fa));
-    }
-    /* rank 0: asm_map_pairs' answer */
-    if (const int rc = map_pairs_primary(h, ix, np, p, pf, max_pairs, out, tlen, n_concordant, cigar_ops, cigar_cap, cigar_nops))
-        return rc;
-    for (int64_t q = 0; q < np; q++)
-        if (n_pairs[q] > (uint32_t)max_pairs) {
-            out[(size_t)q * 2 * max_pairs].flags |= ASM_MAP_HITS_TRUNCATED;
-            out[(size_t)q * 2 * max_pairs + 1].flags |= ASM_MAP_HITS_TRUNCATED;
-        }
-    for (std::thread& x : fill) x.join();
-    fill.clear();
-    if (!ni) return ASM_OK;
-    std::vector<asm_map_hit> hits((size_t)ni);
-    std::vector<uint16_t> ops((size_t)ni * ocap);
-    std::vector<uint8_t> nops((size_t)ni);
-    HIPCHK(h, hipMemcpyAsync(hits.data(), d_hits.p, sizeof(MapHit) * (size_t)ni, hipMemcpyDeviceToHost, h->stream));
-    if (ocap) {
-        HIPCHK(h, hipMemcpyAsync(ops.data(), d_ops.p, sizeof(uint16_t) * (size_t)ni * ocap, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(nops.data(), d_nops.p, (size_t)ni, hipMemcpyDeviceToHost, h->stream));
-    }
-    /* Greedy on every secondary item (all are mapped), in item order */
-    std::vector<uint32_t> list((size_t)ni);
-    int maxmap = 0;
-    for (int64_t q = 0; q < np; q++)
-        if (n_pairs[q] >= 2)
-            maxmap = std::max(maxmap, (int)std::max(f.roff[(size_t)q + 1] - f.roff[(size_t)q],
-                                                    f.roff[(size_t)(np + q) + 1] - f.roff[(size_t)(np + q)]));
-    for (int64_t q = 0; q < ni; q++) list[(size_t)q] = (uint32_t)q;
-    HIPCHK(h, d_list.alloc(sizeof(uint32_t) * (size_t)ni));
-    HIPCHK(h, d_cost.alloc(sizeof(int32_t) * (size_t)ni));
-    HIPCHK(h, hipMemcpyAsync(d_list.p, list.data(), sizeof(uint32_t) * (size_t)ni, hipMemcpyHostToDevice, h->stream));
-    if (const int rc = map_greedy(h, ix, f.d_reads.p, f.d_roff.p, d_hits.p, d_iread.p, d_list.p, ni, maxmap, p->greedy_k, d_cost.p))
-        return rc;
-    std::vector<int32_t> cost((size_t)ni);
-    HIPCHK(h, hipMemcpyAsync(cost.data(), d_cost.p, sizeof(int32_t) * (size_t)ni, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    /* into the caller's slots: items 2 (t - 1) and 2 (t - 1) + 1 of a pair are rank t's mates 1 and 2 */
-    size_t it = 0;
-    for (int64_t q = 0; q < np; q++) {
-        const uint32_t want = std::min<uint32_t>(n_pairs[q], (uint32_t)max_pairs);
-        const uint8_t extra = ASM_MAP_PROPER_PAIR | ASM_MAP_SECONDARY | (n_pairs[q] > (uint32_t)max_pairs ? ASM_MAP_HITS_TRUNCATED : 0);
-        for (uint32_t t = 1; t < want; t++, it += 2) {
-            const size_t o = ((size_t)q * max_pairs + t) * 2;
-            for (int x = 0; x < 2; x++) {
-                out[o + x] = hits[it + x];
-                out[o + x].greedy_cost = cost[it + x];
-                out[o + x].flags |= extra;
-                if (ocap) {
-                    std::copy(ops.begin() + (it + x) * ocap, ops.begin() + (it + x + 1) * ocap, cigar_ops + (o + x) * ocap);
-                    cigar_nops[o + x] = nops[it + x];
-                }
-            }
-            tlen[(size_t)q * max_pairs + t] =
-                (int32_t)(std::max(out[o].end, out[o + 1].end) - std::min(out[o].pos, out[o + 1].pos));
-        }
-    }
-    return ASM_OK;
-}
-
-int asm_map_pairs_all(asm_handle* h, const asm_index* ix, int64_t n, const char* reads1, const uint32_t* off1, const char* reads2,
-                      const uint32_t* off2, const asm_map_params* p, const asm_pair_params* pp, int strata, int max_pairs,
-                      uint32_t* n_pairs, asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant, uint16_t* cigar_ops, int cigar_cap,
-                      uint8_t* cigar_nops) {
-    if (!p || !pp || !ix || n < 0 || !off1 || !off2 || (n > 0 && (!reads1 || !reads2 || !out || !tlen || !n_concordant)))
-        return fail(h, ASM_EINVAL, "asm_map_pairs_all: bad arguments");
-    if (n > 0 && !n_pairs) return fail(h, ASM_EINVAL, "asm_map_pairs_all: n_pairs is NULL");
-    if (p->max_errors < 0 || p->max_errors > ASM_MAP_MAX_ERRORS)
-        return fail(h, ASM_EINVAL, "asm_map_pairs_all: max_errors must be in [0, 15]");
-    if (p->both_strands != 1) return fail(h, ASM_EINVAL, "asm_map_pairs_all: both_strands must be 1");
-    if (p->max_occ < 0) return fail(h, ASM_EINVAL, "asm_map_pairs_all: max_occ must be >= 0");
-    if (p->greedy_k < 0 || p->greedy_k > ASM_GREEDY_MAX_K) return fail(h, ASM_EINVAL, "asm_map_pairs_all: greedy_k must be in [0, 50]");
-    if (pp->min_insert < 0 || pp->min_insert > pp->max_insert || pp->max_insert > ASM_MAP_MAX_INSERT)
-        return fail(h, ASM_EINVAL, "asm_map_pairs_all: need 0 <= min_insert <= max_insert <= 8192");
-    if (pp->rescue_errors < -1 || pp->rescue_errors > ASM_MAP_MAX_ERRORS)
-        return fail(h, ASM_EINVAL, "asm_map_pairs_all: rescue_errors must be -1 (off) or in [0, 15]");
-    if (strata < 0 || strata > 2 * ASM_MAP_MAX_ERRORS) return fail(h, ASM_EINVAL, "asm_map_pairs_all: strata must be in [0, 30]");
-    if (max_pairs < 1 || max_pairs > ASM_MAP_MAX_HITS) return fail(h, ASM_EINVAL, "asm_map_pairs_all: max_pairs must be in [1, 256]");
-    if (cigar_cap < 0 || (cigar_cap > 0 && (!cigar_ops || !cigar_nops)))
-        return fail(h, ASM_EINVAL, "asm_map_pairs_all: cigar_cap > 0 needs cigar_ops and cigar_nops");
-    for (const uint32_t* ro : {off1, off2})
-        for (int64_t i = 0; i < n; i++) {
-            if (ro[i + 1] < ro[i]) return fail(h, ASM_EINVAL, "asm_map_pairs_all: read offsets must be non-decreasing");
-            const uint32_t m = ro[i + 1] - ro[i];
-            if (m < 1 || m > ASM_MAP_MAX_READ) return fail(h, ASM_EINVAL, "asm_map_pairs_all: every mate must have 1 to 511 bytes");
-        }
-    if (n > 0 && (uint64_t)(off1[n] - off1[0]) + (off2[n] - off2[0]) >= 0xffffffffull)
-        return fail(h, ASM_EUNSUPPORTED, "asm_map_pairs_all: both mates' bytes must stay below 2^32");
-    if (!h) return fail(h, ASM_EINVAL, "asm_map_pairs_all: NULL handle");
-    if (ix->device != h->device) return fail(h, ASM_EINVAL, "asm_map_pairs_all: the index lives on another device");
-    HIPCHK(h, hipSetDevice(h->device));
-    const int64_t step = std::max<int64_t>(1, std::min<int64_t>(h->map_chunk, (int64_t)1 << 30) / 2); /* as asm_map_pairs */
-    for (int64_t c0 = 0; c0 < n; c0 += step) {
-        const int64_t c1 = std::min(n, c0 + step);
-        const size_t o = (size_t)c0 * max_pairs * 2;
-        const int rc = map_chunk_pairs_all(h, ix, c1 - c0, reads1, off1 + c0, reads2, off2 + c0, p, pp, strata, max_pairs, n_pairs + c0,
-                                           out + o, tlen + (size_t)c0 * max_pairs, n_concordant + c0,
-                                           cigar_cap > 0 ? cigar_ops + o * cigar_cap : nullptr, cigar_cap,
-                                           cigar_cap > 0 ? cigar_nops + o : nullptr);
-        if (rc) return rc;
-    }
-    return ASM_OK;
-}
-
-int asm_map_reads(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
-                  const asm_map_params* p, asm_map_hit* out, uint16_t* cigar_ops, int cigar_cap, uint8_t* cigar_nops) {
-    if (!p || !ix || n < 0 || !read_off || (n > 0 && (!reads || !out))) return fail(h, ASM_EINVAL, "asm_map_reads: bad arguments");
-    if (p->max_errors < 0 || p->max_errors > ASM_MAP_MAX_ERRORS) return fail(h, ASM_EINVAL, "asm_map_reads: max_errors must be in [0, 15]");
-    if (p->both_strands != 0 && p->both_strands != 1) return fail(h, ASM_EINVAL, "asm_map_reads: both_strands must be 0 or 1");
-    if (p->max_occ < 0) return fail(h, ASM_EINVAL, "asm_map_reads: max_occ must be >= 0");
-    if (p->greedy_k < 0 || p->greedy_k > ASM_GREEDY_MAX_K) return fail(h, ASM_EINVAL, "asm_map_reads: greedy_k must be in [0, 50]");
-    if (cigar_cap < 0 || (cigar_cap > 0 && (!cigar_ops || !cigar_nops)))
-        return fail(h, ASM_EINVAL, "asm_map_reads: cigar_cap > 0 needs cigar_ops and cigar_nops");
-    for (int64_t i = 0; i < n; i++) {
-        if (read_off[i + 1] < read_off[i]) return fail(h, ASM_EINVAL, "asm_map_reads: read offsets must be non-decreasing");
-        const uint32_t m = read_off[i + 1] - read_off[i];
-        if (m < 1 || m > ASM_MAP_MAX_READ) return fail(h, ASM_EINVAL, "asm_map_reads: every read must have 1 to 511 bytes");
-    }
-    if (!h) return fail(h, ASM_EINVAL, "asm_map_reads: NULL handle");
-    if (ix->device != h->device) return fail(h, ASM_EINVAL, "asm_map_reads: the index lives on another device");
-    HIPCHK(h, hipSetDevice(h->device));
-    for (int64_t c0 = 0; c0 < n; c0 += h->map_chunk) {
-        const int64_t c1 = std::min(n, c0 + h->map_chunk);
-        const int rc = map_chunk(h, ix, c1 - c0, reads, read_off + c0, p, out + c0, cigar_cap > 0 ? cigar_ops + c0 * cigar_cap : nullptr,
-                                 cigar_cap, cigar_cap > 0 ? cigar_nops + c0 : nullptr);
-        if (rc) return rc;
-    }
-    return ASM_OK;
-}
+/* ---- read mapping: host side in csrc/asm_map_host.h (kernels: csrc/asm_map.h, design: docs/design/mapper.md) -------------------- */
+#include "asm_map_host.h"
 
 /* ---------------------------------------------------------------------------------------------------- */
 int asm_device_malloc(asm_handle* h, size_t bytes, void** d_ptr) {

@@ -1,0 +1,876 @@
+// Host side of the read mapper (kernels: asm_map.h; design: docs/design/mapper.md): the index, the stages every mapping call is
+// made of (check -> front -> seeding rounds -> runs -> select / pair -> finish stage -> scatter) and the C ABI entry points.
+// asm_capi.hip includes this file inside its extern "C" block: the stages (templates among them) get C++ linkage below, the entry
+// points after them C linkage.
+#pragma once
+
+static_assert(sizeof(MapHit) == sizeof(asm_map_hit) && offsetof(MapHit, dist) == offsetof(asm_map_hit, dist) &&
+                  offsetof(MapHit, greedy_cost) == offsetof(asm_map_hit, greedy_cost),
+              "MapHit must have the layout of asm_map_hit");
+
+struct asm_index {
+    int device = 0;
+    int k = 0;
+    int32_t n_seqs = 0;
+    uint64_t len = 0;
+    std::vector<uint64_t> seq_off;          /* host copy, n_seqs + 1 */
+    char* d_text = nullptr;                 /* upper case */
+    unsigned long long* d_seq_off = nullptr;
+    uint32_t* d_off = nullptr;              /* 4^k + 1 bucket offsets */
+    uint32_t* d_pos = nullptr;              /* positions sorted by k-mer (ascending inside a bucket) */
+    ~asm_index() {
+        (void)hipSetDevice(device);
+        for (void* p : {(void*)d_text, (void*)d_seq_off, (void*)d_off, (void*)d_pos})
+            if (p) (void)hipFree(p);
+    }
+};
+
+extern "C++" {
+
+static unsigned map_grid(uint64_t n, const asm_handle* h) { /* grid-stride kernels: at most 8 workgroups per CU */
+    const uint64_t want = (n + 255) / 256, cap = (uint64_t)h->num_cus * 8;
+    return (unsigned)(want < 1 ? 1 : want > cap ? cap : want);
+}
+
+/* hipcub's temporary storage: grows to the largest request; the old block goes back to the pool in stream order */
+struct MapTmp {
+    Scratch<void> s;
+    size_t cap = 0;
+    explicit MapTmp(asm_handle* h) : s(h) {}
+    hipError_t reserve(size_t bytes) {
+        if (s.p && bytes <= cap) return hipSuccess;
+        pool_free(s.h, s.p);
+        s.p = nullptr, cap = bytes;
+        return s.alloc(bytes + 16);
+    }
+};
+
+/* hipcub's two-phase calls on the handle's stream: query the temporary size, reserve it, run */
+template <class T>
+static hipError_t map_exclusive_sum(asm_handle* h, MapTmp& tmp, T* in, T* out, int64_t n) {
+    size_t bytes = 0;
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, h->stream);
+    if (e == hipSuccess) e = tmp.reserve(bytes);
+    return e != hipSuccess ? e : hipcub::DeviceScan::ExclusiveSum(tmp.s.p, bytes, in, out, (int)n, h->stream);
+}
+
+template <class K, class V, class N> /* stable: equal keys keep their order */
+static hipError_t map_sort_pairs(asm_handle* h, MapTmp& tmp, K* key_in, K* key_out, V* val_in, V* val_out, N n, int end_bit) {
+    size_t bytes = 0;
+    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key_in, key_out, val_in, val_out, n, 0, end_bit, h->stream);
+    if (e == hipSuccess) e = tmp.reserve(bytes);
+    return e != hipSuccess ? e : hipcub::DeviceRadixSort::SortPairs(tmp.s.p, bytes, key_in, key_out, val_in, val_out, n, 0, end_bit, h->stream);
+}
+
+/* fn(std::integral_constant<int, W>) with W = the 64-bit words a read of maxm bases needs, rounded up to 1, 2, 4 or 8: the one
+ * place where a read length picks an instantiation of the <W> kernels */
+template <class F>
+static hipError_t map_with_width(int maxm, F fn) {
+    const int words = (maxm + 63) / 64;
+    if (words <= 1) return fn(std::integral_constant<int, 1>{});
+    if (words <= 2) return fn(std::integral_constant<int, 2>{});
+    if (words <= 4) return fn(std::integral_constant<int, 4>{});
+    return fn(std::integral_constant<int, 8>{});
+}
+
+/* one(first, count) for every chunk of at most step out of n */
+template <class F>
+static int map_chunks(int64_t n, int64_t step, F one) {
+    for (int64_t c0 = 0; c0 < n; c0 += step)
+        if (const int rc = one(c0, std::min(n, c0 + step) - c0)) return rc;
+    return ASM_OK;
+}
+
+/* the caller's CIGAR arrays: cap operations and one count per record; cap = 0: none wanted */
+struct MapCigars {
+    uint16_t* ops;
+    int cap;
+    uint8_t* nops;
+    MapCigars at(size_t rec) const { return cap > 0 ? MapCigars{ops + rec * cap, cap, nops + rec} : MapCigars{nullptr, 0, nullptr}; }
+};
+
+/* What the argument checks of the four mapping calls look at.  off[1] and pp are NULL for the single-end calls, cap_name for the
+ * calls without strata and a cap. */
+struct MapArgs {
+    int64_t n;
+    const asm_map_params* p;
+    const uint32_t* off[2];
+    const asm_pair_params* pp;
+    const char* cap_name; /* "max_hits" / "max_pairs" */
+    int strata, strata_max, cap;
+    MapCigars cg;
+};
+
+/* Every check after the call's own "bad arguments", in the order in which they win.  Nothing is read through h or ix before the
+ * last two, so that the checks can be tested without a device. */
+static int map_check_args(asm_handle* h, const asm_index* ix, const char* who, const char* noun, const MapArgs& a) {
+    auto bad = [&](const std::string& text, int code = ASM_EINVAL) { return fail(h, code, std::string(who) + ": " + text); };
+    const asm_map_params* p = a.p;
+    if (p->max_errors < 0 || p->max_errors > ASM_MAP_MAX_ERRORS) return bad("max_errors must be in [0, 15]");
+    if (a.pp ? p->both_strands != 1 : (p->both_strands != 0 && p->both_strands != 1))
+        return bad(a.pp ? "both_strands must be 1" : "both_strands must be 0 or 1");
+    if (p->max_occ < 0) return bad("max_occ must be >= 0");
+    if (p->greedy_k < 0 || p->greedy_k > ASM_GREEDY_MAX_K) return bad("greedy_k must be in [0, 50]");
+    if (a.pp && (a.pp->min_insert < 0 || a.pp->min_insert > a.pp->max_insert || a.pp->max_insert > ASM_MAP_MAX_INSERT))
+        return bad("need 0 <= min_insert <= max_insert <= 8192");
+    if (a.pp && (a.pp->rescue_errors < -1 || a.pp->rescue_errors > ASM_MAP_MAX_ERRORS))
+        return bad("rescue_errors must be -1 (off) or in [0, 15]");
+    if (a.cap_name && (a.strata < 0 || a.strata > a.strata_max)) return bad("strata must be in [0, " + std::to_string(a.strata_max) + "]");
+    if (a.cap_name && (a.cap < 1 || a.cap > ASM_MAP_MAX_HITS)) return bad(std::string(a.cap_name) + " must be in [1, 256]");
+    if (a.cg.cap < 0 || (a.cg.cap > 0 && (!a.cg.ops || !a.cg.nops))) return bad("cigar_cap > 0 needs cigar_ops and cigar_nops");
+    for (const uint32_t* ro : a.off)
+        for (int64_t i = 0; ro && i < a.n; i++) {
+            if (ro[i + 1] < ro[i]) return bad("read offsets must be non-decreasing");
+            const uint32_t m = ro[i + 1] - ro[i];
+            if (m < 1 || m > ASM_MAP_MAX_READ) return bad(std::string("every ") + noun + " must have 1 to 511 bytes");
+        }
+    if (a.pp && a.n > 0 && (uint64_t)(a.off[0][a.n] - a.off[0][0]) + (a.off[1][a.n] - a.off[1][0]) >= 0xffffffffull)
+        return bad("both mates' bytes must stay below 2^32", ASM_EUNSUPPORTED);
+    if (!h) return bad("NULL handle");
+    if (ix->device != h->device) return bad("the index lives on another device");
+    return ASM_OK;
+}
+
+/* Greedy on the windows of the mapped items of one chunk (d_list: their indices into d_hits; d_iread: each item's read, NULL when
+ * item i is read i); costs into d_cost[q] */
+static int map_greedy(asm_handle* h, const asm_index* ix, const char* d_reads, const uint32_t* d_roff, const MapHit* d_hits,
+                      const uint32_t* d_iread, const uint32_t* d_list, int64_t nl, int maxm, int greedy_k, int32_t* d_cost) {
+    BatchPtr b;
+    int rc = batch_new(h, nl, ASM_GREEDY_CLEAN, "asm_map_reads", b);
+    if (rc) return rc;
+    const size_t cnt = (size_t)nl + 1;
+    Scratch<uint32_t> qlen(h), wlen(h);
+    MapTmp tmp(h);
+    HIPCHK(h, qlen.alloc(sizeof(uint32_t) * cnt));
+    HIPCHK(h, wlen.alloc(sizeof(uint32_t) * cnt));
+    HIPCHK(h, batch_alloc(b.get(), &b->d_read_off, sizeof(uint32_t) * cnt));
+    HIPCHK(h, batch_alloc(b.get(), &b->d_ref_off, sizeof(uint32_t) * cnt));
+    hipLaunchKernelGGL(map_greedy_lengths_kernel, dim3(grid_for(nl + 1)), dim3(ASM_BLOCK), 0, h->stream, d_list, d_iread, (long)nl,
+                       d_roff, d_hits, (const unsigned long long*)ix->d_seq_off, qlen.p, wlen.p);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, map_exclusive_sum(h, tmp, qlen.p, b->d_read_off, (int64_t)cnt));
+    HIPCHK(h, map_exclusive_sum(h, tmp, wlen.p, b->d_ref_off, (int64_t)cnt));
+    uint32_t tot[2] = {0, 0};
+    HIPCHK(h, hipMemcpyAsync(&tot[0], b->d_read_off + nl, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&tot[1], b->d_ref_off + nl, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    b->reads_bytes = tot[0], b->refs_bytes = tot[1];
+    b->maxlen = maxm + 1; /* the window is at most one base longer than the read */
+    HIPCHK(h, batch_alloc(b.get(), &b->d_reads, b->reads_bytes + 16));
+    HIPCHK(h, batch_alloc(b.get(), &b->d_refs, b->refs_bytes + 16));
+    hipLaunchKernelGGL(map_greedy_gather_kernel, dim3(map_grid((uint64_t)nl * 64, h)), dim3(256), 0, h->stream, d_list, d_iread,
+                       (long)nl, d_reads, d_roff, d_hits, (const char*)ix->d_text, (const unsigned long long*)ix->d_seq_off,
+                       (const uint32_t*)b->d_read_off, (const uint32_t*)b->d_ref_off, b->d_reads, b->d_refs);
+    HIPCHK(h, hipGetLastError());
+    rc = batch_finish(h, b.get());
+    if (rc) return rc;
+    asm_params gp;
+    asm_default_params(&gp);
+    gp.k = greedy_k, gp.x = gp.o = gp.e = 1, gp.alignment_type = ASM_ALIGN_GLOBAL;
+    return asm_align_batch_async(h, b.get(), ASM_GREEDY, &gp, d_cost);
+}
+
+/* The front of a chunk, shared by all mapping calls: reads uploaded and upper-cased, per-read flags cleared, every work item's
+ * candidates counted (map_seed_count_kernel) and numbered (exclusive scan); total = all candidates of the chunk. */
+struct MapFront {
+    std::vector<uint32_t> roff;
+    int maxm = 0;
+    size_t bytes = 0;
+    int64_t nw = 0;
+    unsigned long long total = 0;
+    MapSeedArgs sa = {};
+    Scratch<char> d_reads;
+    Scratch<uint32_t> d_roff, d_flags;
+    Scratch<unsigned long long> d_cnt, d_base;
+    explicit MapFront(asm_handle* h) : d_reads(h), d_roff(h), d_flags(h), d_cnt(h), d_base(h) {}
+    int len(size_t i) const { return (int)(roff[i + 1] - roff[i]); }
+};
+
+/* the chunk's reads: one or more runs of reads (asm_map_pairs: the mates 1, then the mates 2), numbered in that order */
+struct MapReadsIn {
+    const char* reads;
+    const uint32_t* read_off; /* n + 1 */
+    int64_t n;
+};
+
+static int map_front(asm_handle* h, const asm_index* ix, const MapReadsIn* in, int n_in, const asm_map_params* p, MapFront& f) {
+    const int S = p->both_strands ? 2 : 1, P = p->max_errors + 1;
+    int64_t n = 0;
+    for (int t = 0; t < n_in; t++) n += in[t].n;
+    f.roff.assign(1, 0u);
+    f.roff.reserve((size_t)n + 1);
+    for (int t = 0; t < n_in; t++) {
+        const uint32_t o = f.roff.back(), *ro = in[t].read_off;
+        for (int64_t i = 1; i <= in[t].n; i++) f.roff.push_back(o + (ro[i] - ro[0]));
+    }
+    for (int64_t i = 0; i < n; i++) f.maxm = std::max(f.maxm, f.len((size_t)i));
+    const size_t bytes = f.bytes = f.roff[(size_t)n];
+    const int64_t nw = f.nw = n * S * P;
+    HIPCHK(h, f.d_reads.alloc(bytes + 16));
+    HIPCHK(h, f.d_roff.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
+    HIPCHK(h, f.d_flags.alloc(sizeof(uint32_t) * (size_t)n));
+    HIPCHK(h, f.d_cnt.alloc(sizeof(unsigned long long) * (size_t)nw));
+    HIPCHK(h, f.d_base.alloc(sizeof(unsigned long long) * (size_t)nw));
+    for (int64_t t = 0, o = 0; t < n_in; o += in[t].read_off[in[t].n] - in[t].read_off[0], t++)
+        HIPCHK(h, hipMemcpyAsync(f.d_reads.p + o, in[t].reads + in[t].read_off[0], in[t].read_off[in[t].n] - in[t].read_off[0],
+                                 hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(f.d_roff.p, f.roff.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(f.d_flags.p, 0, sizeof(uint32_t) * (size_t)n, h->stream));
+    hipLaunchKernelGGL(map_upper_kernel, dim3(map_grid(bytes, h)), dim3(256), 0, h->stream, f.d_reads.p, (unsigned long long)bytes);
+    HIPCHK(h, hipGetLastError());
+    MapSeedArgs& sa = f.sa;
+    sa.reads = f.d_reads.p, sa.roff = f.d_roff.p, sa.n = (long)n, sa.S = S, sa.P = P, sa.k = ix->k, sa.e = p->max_errors;
+    sa.max_occ = p->max_occ, sa.text = ix->d_text, sa.ix_off = ix->d_off, sa.ix_pos = ix->d_pos;
+    sa.seq_off = (const unsigned long long*)ix->d_seq_off, sa.n_seqs = (uint32_t)ix->n_seqs;
+    hipLaunchKernelGGL(map_seed_count_kernel, dim3(map_grid((uint64_t)nw, h)), dim3(256), 0, h->stream, sa, f.d_cnt.p, f.d_flags.p);
+    HIPCHK(h, hipGetLastError());
+    MapTmp tmp(h);
+    HIPCHK(h, map_exclusive_sum(h, tmp, f.d_cnt.p, f.d_base.p, nw));
+    unsigned long long last[2] = {0, 0};
+    HIPCHK(h, hipMemcpyAsync(&last[0], f.d_base.p + nw - 1, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&last[1], f.d_cnt.p + nw - 1, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    f.total = last[0] + last[1];
+    return ASM_OK;
+}
+
+/* The seeding rounds of a chunk, of at most map_cand_cap candidates each: every round sees every work item, emits the part of it
+ * that falls in [c0, c1) and hands those candidates to verify(cand, count) */
+template <class V>
+static int map_seed_rounds(asm_handle* h, const MapFront& f, V verify) {
+    Scratch<MapCand> d_cand(h);
+    const unsigned long long cap = std::min<unsigned long long>(f.total, (unsigned long long)h->map_cand_cap);
+    if (f.total) HIPCHK(h, d_cand.alloc(sizeof(MapCand) * cap));
+    for (unsigned long long c0 = 0; c0 < f.total; c0 += cap) {
+        const unsigned long long c1 = std::min(f.total, c0 + cap);
+        hipLaunchKernelGGL(map_seed_emit_kernel, dim3(map_grid((uint64_t)f.nw, h)), dim3(256), 0, h->stream, f.sa,
+                           (const unsigned long long*)f.d_base.p, (const unsigned long long*)f.d_cnt.p, c0, c1, d_cand.p);
+        HIPCHK(h, hipGetLastError());
+        if (const int rc = verify((const MapCand*)d_cand.p, c1 - c0)) return rc;
+    }
+    return ASM_OK;
+}
+
+/* asm_map_reads: the best end of every read into keys (64-bit atomicMin per candidate) */
+static hipError_t map_launch_verify(asm_handle* h, const asm_index* ix, const MapFront& f, int e, const MapCand* cand,
+                                    unsigned long long nc, unsigned long long* keys) {
+    return map_with_width(f.maxm, [&](auto w) {
+        hipLaunchKernelGGL(map_verify_kernel<decltype(w)::value>, dim3(map_grid(nc, h)), dim3(256), 0, h->stream, cand, nc,
+                           (const char*)f.d_reads.p, (const uint32_t*)f.d_roff.p, (const char*)ix->d_text,
+                           (const unsigned long long*)ix->d_seq_off, e, keys);
+        return hipGetLastError();
+    });
+}
+
+/* the other calls: every candidate's run records appended to key / val [0, cap); *counter counts all of them, kept or not */
+static hipError_t map_launch_verify_all(asm_handle* h, const asm_index* ix, const MapFront& f, int e, const MapCand* cand,
+                                        unsigned long long nc, unsigned long long* counter, unsigned long long cap,
+                                        unsigned long long* key, uint32_t* val) {
+    return map_with_width(f.maxm, [&](auto w) {
+        hipLaunchKernelGGL(map_verify_all_kernel<decltype(w)::value>, dim3(map_grid(nc, h)), dim3(256), 0, h->stream, cand, nc,
+                           (const char*)f.d_reads.p, (const uint32_t*)f.d_roff.p, (const char*)ix->d_text, e, counter, cap, key, val);
+        return hipGetLastError();
+    });
+}
+
+/* The finish stage, used by all four calls.  Launch: one item per packed key (iread / idirs: each item's read and dirs offset;
+ * NULL for the identity list, item i = read i) gets its start, traceback, CIGAR and hit record on the device.  Collect: the records
+ * to the host, Greedy on the mapped items, greedy_cost into the host records.  Work may be enqueued between the two halves. */
+struct MapFinish {
+    int64_t n = 0;
+    int ocap = 0;
+    const uint32_t* d_iread = nullptr;
+    Scratch<uint64_t> d_dirs;
+    Scratch<MapHit> d_hits;
+    Scratch<uint16_t> d_ops;
+    Scratch<uint8_t> d_nops;
+    explicit MapFinish(asm_handle* h) : d_dirs(h), d_hits(h), d_ops(h), d_nops(h) {}
+};
+
+static int map_finish_launch(asm_handle* h, const asm_index* ix, const asm_map_params* p, const MapFront& f, int64_t n,
+                             const unsigned long long* keys, const uint32_t* iread, const unsigned long long* idirs,
+                             unsigned long long dir_words, int cigar_cap, MapFinish& s) {
+    s.n = n, s.ocap = cigar_cap > 0 ? cigar_cap : 0, s.d_iread = iread;
+    HIPCHK(h, s.d_dirs.alloc(sizeof(uint64_t) * dir_words));
+    HIPCHK(h, s.d_hits.alloc(sizeof(MapHit) * (size_t)n));
+    HIPCHK(h, s.d_ops.alloc(sizeof(uint16_t) * ((size_t)n * s.ocap + 1)));
+    HIPCHK(h, s.d_nops.alloc((size_t)n));
+    MapFinishArgs fa = {};
+    fa.reads = f.d_reads.p, fa.roff = f.d_roff.p, fa.n = (long)n, fa.e = p->max_errors, fa.P = p->max_errors + 1, fa.k = ix->k;
+    fa.cap = s.ocap, fa.text = ix->d_text, fa.seq_off = (const unsigned long long*)ix->d_seq_off, fa.keys = keys;
+    fa.flags = f.d_flags.p, fa.iread = iread, fa.idirs = idirs, fa.dirs = s.d_dirs.p, fa.hits = s.d_hits.p, fa.ops = s.d_ops.p;
+    fa.nops = s.d_nops.p;
+    const hipError_t launched = map_with_width(f.maxm, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        if (iread)
+            hipLaunchKernelGGL((map_finish_kernel<W, true>), dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, fa);
+        else
+            hipLaunchKernelGGL((map_finish_kernel<W, false>), dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, fa);
+        return hipGetLastError();
+    });
+    HIPCHK(h, launched);
+    return ASM_OK;
+}
+
+/* hits[n], ops[n][ocap], nops[n]: host memory, the caller's own arrays or a MapItems.  all_mapped_maxm >= 0: the caller knows that
+ * every item is mapped and no read of theirs is longer than that, which saves the pass over the flags and the wait before it. */
+static int map_finish_collect(asm_handle* h, const asm_index* ix, const asm_map_params* p, const MapFront& f, MapFinish& s,
+                              asm_map_hit* hits, uint16_t* ops, uint8_t* nops, int all_mapped_maxm = -1) {
+    const size_t n = (size_t)s.n;
+    HIPCHK(h, hipMemcpyAsync(hits, s.d_hits.p, sizeof(MapHit) * n, hipMemcpyDeviceToHost, h->stream));
+    if (s.ocap) {
+        HIPCHK(h, hipMemcpyAsync(ops, s.d_ops.p, sizeof(uint16_t) * n * s.ocap, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(nops, s.d_nops.p, n, hipMemcpyDeviceToHost, h->stream));
+    }
+    std::vector<uint32_t> list, iread;
+    int maxmap = all_mapped_maxm;
+    if (all_mapped_maxm >= 0) {
+        list.resize(n);
+        for (size_t q = 0; q < n; q++) list[q] = (uint32_t)q;
+    } else {
+        if (s.d_iread) {
+            iread.resize(n);
+            HIPCHK(h, hipMemcpyAsync(iread.data(), s.d_iread, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, h->stream));
+        }
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        maxmap = 0;
+        for (size_t q = 0; q < n; q++)
+            if (hits[q].flags & ASM_MAP_MAPPED) {
+                list.push_back((uint32_t)q);
+                maxmap = std::max(maxmap, f.len(s.d_iread ? iread[q] : q));
+            }
+    }
+    if (list.empty()) return ASM_OK;
+    const size_t nl = list.size();
+    Scratch<uint32_t> d_list(h);
+    Scratch<int32_t> d_cost(h);
+    HIPCHK(h, d_list.alloc(sizeof(uint32_t) * nl));
+    HIPCHK(h, d_cost.alloc(sizeof(int32_t) * nl));
+    HIPCHK(h, hipMemcpyAsync(d_list.p, list.data(), sizeof(uint32_t) * nl, hipMemcpyHostToDevice, h->stream));
+    if (const int rc = map_greedy(h, ix, f.d_reads.p, f.d_roff.p, s.d_hits.p, s.d_iread, d_list.p, (int64_t)nl, maxmap, p->greedy_k, d_cost.p))
+        return rc;
+    std::vector<int32_t> cost(nl);
+    HIPCHK(h, hipMemcpyAsync(cost.data(), d_cost.p, sizeof(int32_t) * nl, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (size_t q = 0; q < nl; q++) hits[list[q]].greedy_cost = cost[q];
+    return ASM_OK;
+}
+
+/* the host copy of finished items, for the calls that scatter them into the caller's slots */
+struct MapItems {
+    std::vector<asm_map_hit> hits;
+    std::vector<uint16_t> ops;
+    std::vector<uint8_t> nops;
+    int ocap;
+    MapItems(int64_t n, int ocap_) : hits((size_t)n), ops((size_t)n * ocap_), nops((size_t)n), ocap(ocap_) {}
+    void cigar_to(const MapCigars& cg, size_t rec, size_t item) const { /* item's CIGAR row into the caller's record rec */
+        if (!ocap) return;
+        std::copy(ops.begin() + item * ocap, ops.begin() + (item + 1) * ocap, cg.ops + rec * ocap);
+        cg.nops[rec] = nops[item];
+    }
+};
+
+static const asm_map_hit MAP_UNUSED_SLOT = {-1, 0, 0, -1, 0, 0, -1};
+
+/* asm_map_reads on one chunk: everything on the device, results straight into the caller's host arrays */
+static int map_chunk(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
+                     const asm_map_params* p, asm_map_hit* out, MapCigars cg) {
+    MapFront f(h);
+    Scratch<unsigned long long> d_keys(h);
+    HIPCHK(h, d_keys.alloc(sizeof(unsigned long long) * (size_t)n));
+    HIPCHK(h, hipMemsetAsync(d_keys.p, 0xff, sizeof(unsigned long long) * (size_t)n, h->stream));
+    const MapReadsIn in = {reads, read_off, n};
+    if (const int rc = map_front(h, ix, &in, 1, p, f)) return rc;
+    const int rc = map_seed_rounds(h, f, [&](const MapCand* cand, unsigned long long nc) -> int {
+        HIPCHK(h, map_launch_verify(h, ix, f, p->max_errors, cand, nc, d_keys.p));
+        return ASM_OK;
+    });
+    if (rc) return rc;
+    MapFinish fin(h);
+    if (const int rc2 = map_finish_launch(h, ix, p, f, n, d_keys.p, nullptr, nullptr, f.bytes + (size_t)n, cg.cap, fin)) return rc2;
+    return map_finish_collect(h, ix, p, f, fin, out, cg.ops, cg.nops);
+}
+
+/* The run records of one chunk (every call but asm_map_reads), sorted by (read, s, lo): the seeding rounds with
+ * map_verify_all_kernel<W>, then a radix sort.  n < 2^31 reads, so that read << 33 fits the 64-bit run key. */
+struct MapRuns {
+    unsigned long long nr = 0;
+    Scratch<unsigned long long> key;
+    Scratch<uint32_t> val;
+    explicit MapRuns(asm_handle* h) : key(h), val(h) {}
+};
+
+static int map_runs(asm_handle* h, const asm_index* ix, int64_t n, const asm_map_params* p, MapFront& f, MapRuns& out,
+                    const char* who) {
+    Scratch<unsigned long long> d_counter(h), d_rkey(h);
+    Scratch<uint32_t> d_rval(h);
+    unsigned long long rcap = 0, nr = 0;
+    HIPCHK(h, d_counter.alloc(sizeof(unsigned long long)));
+    HIPCHK(h, hipMemsetAsync(d_counter.p, 0, sizeof(unsigned long long), h->stream));
+    auto grow = [&](unsigned long long ncap) -> int { /* the run buffer to ncap records, keeping [0, nr) */
+        Scratch<unsigned long long> k2(h);
+        Scratch<uint32_t> v2(h);
+        HIPCHK(h, k2.alloc(sizeof(unsigned long long) * ncap));
+        HIPCHK(h, v2.alloc(sizeof(uint32_t) * ncap));
+        if (nr) {
+            HIPCHK(h, hipMemcpyAsync(k2.p, d_rkey.p, sizeof(unsigned long long) * nr, hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(v2.p, d_rval.p, sizeof(uint32_t) * nr, hipMemcpyDeviceToDevice, h->stream));
+        }
+        std::swap(d_rkey.p, k2.p);
+        std::swap(d_rval.p, v2.p);
+        rcap = ncap;
+        return ASM_OK;
+    };
+    /* Before each round's verify, the buffer gets room for min(ASM_MAP_RUN_CAP, the round's candidates) more records (a window
+     * mostly gives one interval or none); after it, the run counter tells whether the buffer held the round's records.  If not,
+     * the buffer grows (keeping the earlier rounds' records), the counter goes back and the verify runs again. */
+    const int rc = map_seed_rounds(h, f, [&](const MapCand* cand, unsigned long long nc) -> int {
+        const unsigned long long want = nr + std::min(nc, (unsigned long long)h->map_run_cap);
+        if (want > rcap)
+            if (const int rg = grow(std::max(want, rcap + rcap / 2))) return rg;
+        for (;;) {
+            HIPCHK(h, map_launch_verify_all(h, ix, f, p->max_errors, cand, nc, d_counter.p, rcap, d_rkey.p, d_rval.p));
+            unsigned long long got = 0;
+            HIPCHK(h, hipMemcpyAsync(&got, d_counter.p, sizeof(got), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            if (got <= rcap) {
+                nr = got;
+                return ASM_OK;
+            }
+            if (const int rg = grow(std::max(got, 2 * rcap))) return rg;
+            HIPCHK(h, hipMemcpyAsync(d_counter.p, &nr, sizeof(nr), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream)); /* nr is read by the copy above before it may change */
+        }
+    });
+    if (rc) return rc;
+    if (nr > (unsigned long long)INT32_MAX)
+        return fail(h, ASM_EUNSUPPORTED, std::string(who) + ": more than 2^31 - 1 run records in a chunk");
+    /* sort by (read, s, lo): only the bits in use (read < n) */
+    int rbits = 0;
+    while (rbits < 31 && (1ull << rbits) < (unsigned long long)n) rbits++;
+    HIPCHK(h, out.key.alloc(sizeof(unsigned long long) * (nr + 1)));
+    HIPCHK(h, out.val.alloc(sizeof(uint32_t) * (nr + 1)));
+    MapTmp tmp(h);
+    if (nr) HIPCHK(h, map_sort_pairs(h, tmp, d_rkey.p, out.key.p, d_rval.p, out.val.p, (int)nr, MAP_RUN_READ_SHIFT + rbits));
+    out.nr = nr;
+    return ASM_OK;
+}
+
+/* what map_select_count_kernel / map_select_emit_kernel / map_loci_emit_kernel read of a chunk's sorted runs */
+static MapSelectArgs map_select_args(const asm_index* ix, const MapFront& f, const MapRuns& runs, int64_t n, int e, int strata,
+                                     int max_hits, uint32_t* n_hits, uint32_t* d_best) {
+    MapSelectArgs sel = {};
+    sel.rkey = runs.key.p, sel.rval = runs.val.p, sel.nr = runs.nr, sel.n = (long)n, sel.e = e, sel.strata = strata, sel.max_hits = max_hits;
+    sel.seq_off = (const unsigned long long*)ix->d_seq_off, sel.n_seqs = (uint32_t)ix->n_seqs, sel.roff = f.d_roff.p;
+    sel.n_hits = n_hits, sel.d_best = d_best;
+    return sel;
+}
+
+/* asm_map_reads_all on one chunk: the sorted run records, the loci selected per read into an item list, the finish stage on the
+ * items, then the scatter into the caller's [n][max_hits] slots */
+static int map_chunk_all(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
+                         const asm_map_params* p, int strata, int max_hits, uint32_t* n_hits, asm_map_hit* out, MapCigars cg) {
+    MapFront f(h);
+    const MapReadsIn in = {reads, read_off, n};
+    if (const int rc = map_front(h, ix, &in, 1, p, f)) return rc;
+    MapRuns runs(h);
+    if (const int rc = map_runs(h, ix, n, p, f, runs, "asm_map_reads_all")) return rc;
+    /* loci per read: count, then (host) the item layout, then emit */
+    Scratch<uint32_t> d_nh(h), d_dbest(h), d_ibase(h), d_iread(h);
+    Scratch<unsigned long long> d_dbase(h), d_ikey(h), d_idirs(h);
+    HIPCHK(h, d_nh.alloc(sizeof(uint32_t) * (size_t)n));
+    HIPCHK(h, d_dbest.alloc(sizeof(uint32_t) * (size_t)n));
+    MapSelectArgs sel = map_select_args(ix, f, runs, n, p->max_errors, strata, max_hits, d_nh.p, d_dbest.p);
+    hipLaunchKernelGGL(map_select_count_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(n_hits, d_nh.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    /* items: max(1, min(n_hits, max_hits)) per read, in read-then-rank order; dirs: (m + 1) words per item */
+    std::vector<uint32_t> ibase((size_t)n + 1);
+    std::vector<unsigned long long> dbase((size_t)n);
+    unsigned long long dwords = 0;
+    for (int64_t i = 0; i < n; i++) {
+        const uint32_t ni = n_hits[i] ? std::min<uint32_t>(n_hits[i], (uint32_t)max_hits) : 1u;
+        ibase[(size_t)i + 1] = ibase[(size_t)i] + ni;
+        dbase[(size_t)i] = dwords;
+        dwords += (unsigned long long)ni * (f.len((size_t)i) + 1u);
+    }
+    const int64_t ni = ibase[(size_t)n];
+    HIPCHK(h, d_ibase.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
+    HIPCHK(h, d_dbase.alloc(sizeof(unsigned long long) * (size_t)n));
+    HIPCHK(h, d_iread.alloc(sizeof(uint32_t) * (size_t)ni));
+    HIPCHK(h, d_ikey.alloc(sizeof(unsigned long long) * (size_t)ni));
+    HIPCHK(h, d_idirs.alloc(sizeof(unsigned long long) * (size_t)ni));
+    HIPCHK(h, hipMemcpyAsync(d_ibase.p, ibase.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_dbase.p, dbase.data(), sizeof(unsigned long long) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    sel.ibase = d_ibase.p, sel.dbase = d_dbase.p, sel.iread = d_iread.p, sel.ikey = d_ikey.p, sel.idirs = d_idirs.p;
+    hipLaunchKernelGGL(map_select_emit_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel);
+    HIPCHK(h, hipGetLastError());
+    MapFinish fin(h);
+    if (const int rc = map_finish_launch(h, ix, p, f, ni, d_ikey.p, d_iread.p, d_idirs.p, dwords, cg.cap, fin)) return rc;
+    MapItems it(ni, fin.ocap);
+    if (const int rc = map_finish_collect(h, ix, p, f, fin, it.hits.data(), it.ops.data(), it.nops.data())) return rc;
+    /* into the caller's [n][max_hits] slots (a read's items are contiguous); the flags that depend on the rank are set here.  The
+     * CIGAR rows of unused slots are not written: their cigar_nops is 0. */
+    const int ocap = fin.ocap;
+    for (int64_t i = 0; i < n; i++) {
+        const uint32_t q0 = ibase[(size_t)i], cnt = ibase[(size_t)i + 1] - q0;
+        const size_t o = (size_t)i * max_hits;
+        std::copy(it.hits.begin() + q0, it.hits.begin() + q0 + cnt, out + o);
+        for (uint32_t t = 1; t < cnt; t++) out[o + t].flags |= ASM_MAP_SECONDARY;
+        if (n_hits[i] > (uint32_t)max_hits)
+            for (uint32_t t = 0; t < cnt; t++) out[o + t].flags |= ASM_MAP_HITS_TRUNCATED;
+        std::fill(out + o + cnt, out + o + max_hits, MAP_UNUSED_SLOT);
+        if (ocap) {
+            std::copy(it.ops.begin() + (size_t)q0 * ocap, it.ops.begin() + (size_t)(q0 + cnt) * ocap, cg.ops + o * ocap);
+            std::copy(it.nops.begin() + q0, it.nops.begin() + q0 + cnt, cg.nops + o);
+            std::fill(cg.nops + o + cnt, cg.nops + o + max_hits, (uint8_t)0);
+        }
+    }
+    return ASM_OK;
+}
+
+/* The paired calls' front on one chunk of np pairs (mate 1 of pair p = read p, mate 2 = read np + p): the sorted run records, each
+ * read's loci listed (count, scan, emit), the pairing and the rescue of pairs without a concordant pair. */
+struct MapPairFront {
+    MapFront f;
+    MapRuns runs;
+    Scratch<uint32_t> d_nh, d_dbest, d_lbase, d_lsplit, d_nconc, d_anchors, d_nanch;
+    Scratch<unsigned long long> d_lkey, d_lbest, d_ikey, d_rslot;
+    Scratch<uint8_t> d_state;
+    MapPairArgs pa = {};
+    explicit MapPairFront(asm_handle* h)
+        : f(h), runs(h), d_nh(h), d_dbest(h), d_lbase(h), d_lsplit(h), d_nconc(h), d_anchors(h), d_nanch(h), d_lkey(h), d_lbest(h),
+          d_ikey(h), d_rslot(h), d_state(h) {}
+};
+
+struct MapPairsIn { /* the two mates of a chunk's pairs */
+    const char* reads1;
+    const uint32_t* off1;
+    const char* reads2;
+    const uint32_t* off2;
+    MapPairsIn at(int64_t c0) const { return {reads1, off1 + c0, reads2, off2 + c0}; }
+};
+
+static int map_pairs_front(asm_handle* h, const asm_index* ix, int64_t np, const MapPairsIn& m, const asm_map_params* p,
+                           const asm_pair_params* pp, const char* who, MapPairFront& pf) {
+    const int64_t n = 2 * np;
+    MapFront& f = pf.f;
+    const MapReadsIn in[2] = {{m.reads1, m.off1, np}, {m.reads2, m.off2, np}};
+    if (const int rc = map_front(h, ix, in, 2, p, f)) return rc;
+    const int e = p->max_errors;
+    if (const int rc = map_runs(h, ix, n, p, f, pf.runs, who)) return rc;
+    /* each read's loci (strata = e: all of them), listed in walk order */
+    HIPCHK(h, pf.d_nh.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
+    HIPCHK(h, pf.d_dbest.alloc(sizeof(uint32_t) * (size_t)n));
+    HIPCHK(h, pf.d_lbase.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
+    const MapSelectArgs sel = map_select_args(ix, f, pf.runs, n, e, e, 1, pf.d_nh.p, pf.d_dbest.p);
+    HIPCHK(h, hipMemsetAsync(pf.d_nh.p + n, 0, sizeof(uint32_t), h->stream));
+    hipLaunchKernelGGL(map_select_count_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel);
+    HIPCHK(h, hipGetLastError());
+    MapTmp tmp(h);
+    HIPCHK(h, map_exclusive_sum(h, tmp, pf.d_nh.p, pf.d_lbase.p, n + 1));
+    uint32_t nloci = 0;
+    HIPCHK(h, hipMemcpyAsync(&nloci, pf.d_lbase.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, pf.d_lkey.alloc(sizeof(unsigned long long) * ((size_t)nloci + 1)));
+    HIPCHK(h, pf.d_lsplit.alloc(sizeof(uint32_t) * (size_t)n));
+    HIPCHK(h, pf.d_lbest.alloc(sizeof(unsigned long long) * (size_t)n));
+    hipLaunchKernelGGL(map_loci_emit_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel, (const uint32_t*)pf.d_lbase.p,
+                       pf.d_lkey.p, pf.d_lsplit.p, pf.d_lbest.p);
+    HIPCHK(h, hipGetLastError());
+    /* pairing */
+    HIPCHK(h, pf.d_ikey.alloc(sizeof(unsigned long long) * (size_t)n));
+    HIPCHK(h, pf.d_nconc.alloc(sizeof(uint32_t) * (size_t)np));
+    HIPCHK(h, pf.d_state.alloc((size_t)np));
+    HIPCHK(h, pf.d_nanch.alloc(sizeof(uint32_t)));
+    HIPCHK(h, hipMemsetAsync(pf.d_nanch.p, 0, sizeof(uint32_t), h->stream));
+    const bool rescue = pp->rescue_errors >= 0;
+    if (rescue) {
+        HIPCHK(h, pf.d_anchors.alloc(sizeof(uint32_t) * (size_t)n));
+        HIPCHK(h, pf.d_rslot.alloc(sizeof(unsigned long long) * (size_t)n));
+        HIPCHK(h, hipMemsetAsync(pf.d_rslot.p, 0xff, sizeof(unsigned long long) * (size_t)n, h->stream));
+    }
+    MapPairArgs& pa = pf.pa;
+    pa.np = (long)np, pa.roff = f.d_roff.p, pa.lbase = pf.d_lbase.p, pa.lsplit = pf.d_lsplit.p, pa.lbest = pf.d_lbest.p;
+    pa.lkey = pf.d_lkey.p, pa.min_insert = pp->min_insert, pa.max_insert = pp->max_insert, pa.rescue = pp->rescue_errors;
+    pa.ikey = pf.d_ikey.p, pa.n_conc = pf.d_nconc.p, pa.state = pf.d_state.p, pa.anchors = pf.d_anchors.p, pa.n_anchors = pf.d_nanch.p;
+    pa.rslot = pf.d_rslot.p, pa.seq_off = (const unsigned long long*)ix->d_seq_off;
+    hipLaunchKernelGGL(map_pair_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, pa);
+    HIPCHK(h, hipGetLastError());
+    if (rescue) {
+        /* one thread per (anchor, tile of ends); grid-stride over the anchor count the pair kernel left on the device (<= 2 np) */
+        const uint32_t ntile = (uint32_t)((pp->max_insert - pp->min_insert + MAP_RESCUE_TILE) / MAP_RESCUE_TILE);
+        const hipError_t launched = map_with_width(f.maxm, [&](auto w) {
+            hipLaunchKernelGGL(map_rescue_kernel<decltype(w)::value>, dim3(map_grid((uint64_t)(2 * pa.np) * ntile, h)), dim3(256), 0,
+                               h->stream, pa, (const char*)f.d_reads.p, (const char*)ix->d_text, ntile, pf.d_rslot.p);
+            return hipGetLastError();
+        });
+        HIPCHK(h, launched);
+        hipLaunchKernelGGL(map_rescue_pick_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, pa);
+        HIPCHK(h, hipGetLastError());
+    }
+    return ASM_OK;
+}
+
+/* asm_map_pairs' answer after map_pairs_front: the finish stage on the identity list (one item per read), then pair q's two records
+ * into out[2 q slots + 0, 1] with the pair flags, tlen[q slots], n_concordant[q] and the CIGAR rows of those records (slots:
+ * records per mate and pair in the caller's arrays, 1 for asm_map_pairs) */
+static int map_pairs_primary(asm_handle* h, const asm_index* ix, int64_t np, const asm_map_params* p, MapPairFront& pf, int slots,
+                             asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant, MapCigars cg) {
+    const int64_t n = 2 * np;
+    MapFront& f = pf.f;
+    MapFinish fin(h);
+    if (const int rc = map_finish_launch(h, ix, p, f, n, pf.d_ikey.p, nullptr, nullptr, f.bytes + (size_t)n, cg.cap, fin)) return rc;
+    MapItems it(n, fin.ocap);
+    std::vector<uint8_t> state((size_t)np);
+    HIPCHK(h, hipMemcpyAsync(state.data(), pf.d_state.p, (size_t)np, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(n_concordant, pf.d_nconc.p, sizeof(uint32_t) * (size_t)np, hipMemcpyDeviceToHost, h->stream));
+    if (const int rc = map_finish_collect(h, ix, p, f, fin, it.hits.data(), it.ops.data(), it.nops.data())) return rc;
+    /* into the caller's records; the pair flags and tlen are set here */
+    for (int64_t q = 0; q < np; q++) {
+        const size_t r0 = (size_t)(2 * q) * slots; /* pair q's first record */
+        asm_map_hit* o = out + r0;
+        o[0] = it.hits[(size_t)q], o[1] = it.hits[(size_t)(np + q)];
+        const uint8_t st = state[(size_t)q];
+        if (st == MAP_PAIR_CONCORDANT || st == MAP_PAIR_RESCUED1 || st == MAP_PAIR_RESCUED2) {
+            o[0].flags |= ASM_MAP_PROPER_PAIR, o[1].flags |= ASM_MAP_PROPER_PAIR;
+            if (st == MAP_PAIR_RESCUED1) o[0].flags |= ASM_MAP_RESCUED;
+            if (st == MAP_PAIR_RESCUED2) o[1].flags |= ASM_MAP_RESCUED;
+        }
+        const bool same = (o[0].flags & ASM_MAP_MAPPED) && (o[1].flags & ASM_MAP_MAPPED) && o[0].seq_id == o[1].seq_id;
+        tlen[(size_t)q * slots] = same ? (int32_t)(std::max(o[0].end, o[1].end) - std::min(o[0].pos, o[1].pos)) : 0;
+        it.cigar_to(cg, r0, (size_t)q), it.cigar_to(cg, r0 + 1, (size_t)(np + q));
+    }
+    return ASM_OK;
+}
+
+/* asm_map_pairs on one chunk of np pairs: the front, then the primary answer */
+static int map_chunk_pairs(asm_handle* h, const asm_index* ix, int64_t np, const MapPairsIn& m, const asm_map_params* p,
+                           const asm_pair_params* pp, asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant, MapCigars cg) {
+    MapPairFront pf(h);
+    if (const int rc = map_pairs_front(h, ix, np, m, p, pp, "asm_map_pairs", pf)) return rc;
+    return map_pairs_primary(h, ix, np, p, pf, 1, out, tlen, n_concordant, cg);
+}
+
+/* host threads that fill the slots beyond rank 0 of asm_map_pairs_all's arrays as unused while the device works; joined by
+ * join() or at scope exit */
+struct MapSlotFill {
+    std::vector<std::thread> t;
+    MapSlotFill(int64_t np, int max_pairs, asm_map_hit* out, int32_t* tlen, MapCigars cg) {
+        const int64_t nt = max_pairs > 1 ? std::min<int64_t>(4, std::max<int64_t>(1, np / 4096)) : 0;
+        for (int64_t k = 0; k < nt; k++)
+            t.emplace_back([=]() {
+                for (int64_t q = np * k / nt; q < np * (k + 1) / nt; q++) {
+                    const size_t o = (size_t)q * max_pairs;
+                    std::fill(out + 2 * (o + 1), out + 2 * (o + max_pairs), MAP_UNUSED_SLOT);
+                    std::fill(tlen + o + 1, tlen + o + max_pairs, 0);
+                    if (cg.cap > 0) std::fill(cg.nops + 2 * (o + 1), cg.nops + 2 * (o + max_pairs), (uint8_t)0);
+                }
+            });
+    }
+    void join() {
+        for (std::thread& x : t) x.join();
+        t.clear();
+    }
+    ~MapSlotFill() { join(); }
+};
+
+/* asm_map_pairs_all on one chunk of np pairs: the front, the eligible pairs counted, ranks >= 1 listed as items (mate 1, mate 2 per
+ * pair) in pair order and their finish kernel enqueued; then, while the device works on it, the primary answer of asm_map_pairs
+ * (rank 0); then the secondary items collected and scattered into the caller's [np][max_pairs][2] slots. */
+static int map_chunk_pairs_all(asm_handle* h, const asm_index* ix, int64_t np, const MapPairsIn& m, const asm_map_params* p,
+                               const asm_pair_params* pp, int strata, int max_pairs, uint32_t* n_pairs, asm_map_hit* out,
+                               int32_t* tlen, uint32_t* n_concordant, MapCigars cg) {
+    MapSlotFill fill(np, max_pairs, out, tlen, cg);
+    MapPairFront pf(h);
+    if (const int rc = map_pairs_front(h, ix, np, m, p, pp, "asm_map_pairs_all", pf)) return rc;
+    MapFront& f = pf.f;
+    /* eligible pairs per pair, and the layout of the secondary items (device scans) */
+    Scratch<uint32_t> d_np(h), d_sums(h), d_iread(h);
+    Scratch<unsigned long long> d_nitem(h), d_ndirs(h), d_ibase(h), d_dbase(h), d_ikey(h), d_idirs(h);
+    HIPCHK(h, d_np.alloc(sizeof(uint32_t) * (size_t)np));
+    HIPCHK(h, d_sums.alloc(sizeof(uint32_t) * (size_t)np));
+    for (Scratch<unsigned long long>* x : {&d_nitem, &d_ndirs, &d_ibase, &d_dbase})
+        HIPCHK(h, x->alloc(sizeof(unsigned long long) * ((size_t)np + 1)));
+    HIPCHK(h, hipMemsetAsync(d_nitem.p + np, 0, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(d_ndirs.p + np, 0, sizeof(unsigned long long), h->stream));
+    MapPairAllArgs aa = {};
+    aa.pa = pf.pa, aa.strata = strata, aa.max_pairs = max_pairs, aa.n_pairs = d_np.p, aa.sums = d_sums.p, aa.nitem = d_nitem.p;
+    aa.ndirs = d_ndirs.p, aa.ibase = d_ibase.p, aa.dbase = d_dbase.p;
+    hipLaunchKernelGGL(map_pair_count_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, aa);
+    HIPCHK(h, hipGetLastError());
+    MapTmp tmp(h);
+    HIPCHK(h, map_exclusive_sum(h, tmp, d_nitem.p, d_ibase.p, np + 1));
+    HIPCHK(h, map_exclusive_sum(h, tmp, d_ndirs.p, d_dbase.p, np + 1));
+    unsigned long long tot[2] = {0, 0};
+    HIPCHK(h, hipMemcpyAsync(n_pairs, d_np.p, sizeof(uint32_t) * (size_t)np, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&tot[0], d_ibase.p + np, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&tot[1], d_dbase.p + np, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const int64_t ni = (int64_t)tot[0];
+    /* ranks >= 1: items, finish kernel (the item-list instantiation of asm_map_reads_all) */
+    MapFinish fin(h);
+    if (ni) {
+        HIPCHK(h, d_iread.alloc(sizeof(uint32_t) * (size_t)ni));
+        HIPCHK(h, d_ikey.alloc(sizeof(unsigned long long) * (size_t)ni));
+        HIPCHK(h, d_idirs.alloc(sizeof(unsigned long long) * (size_t)ni));
+        aa.iread = d_iread.p, aa.ikey = d_ikey.p, aa.idirs = d_idirs.p;
+        hipLaunchKernelGGL(map_pair_emit_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, aa);
+        HIPCHK(h, hipGetLastError());
+        if (const int rc = map_finish_launch(h, ix, p, f, ni, d_ikey.p, d_iread.p, d_idirs.p, tot[1], cg.cap, fin)) return rc;
+    }
+    /* rank 0: asm_map_pairs' answer */
+    if (const int rc = map_pairs_primary(h, ix, np, p, pf, max_pairs, out, tlen, n_concordant, cg)) return rc;
+    for (int64_t q = 0; q < np; q++)
+        if (n_pairs[q] > (uint32_t)max_pairs) {
+            out[(size_t)q * 2 * max_pairs].flags |= ASM_MAP_HITS_TRUNCATED;
+            out[(size_t)q * 2 * max_pairs + 1].flags |= ASM_MAP_HITS_TRUNCATED;
+        }
+    fill.join();
+    if (!ni) return ASM_OK;
+    /* every secondary item is mapped: Greedy on all of them, in item order */
+    int maxmap = 0;
+    for (int64_t q = 0; q < np; q++)
+        if (n_pairs[q] >= 2) maxmap = std::max(maxmap, std::max(f.len((size_t)q), f.len((size_t)(np + q))));
+    MapItems it(ni, fin.ocap);
+    if (const int rc = map_finish_collect(h, ix, p, f, fin, it.hits.data(), it.ops.data(), it.nops.data(), maxmap)) return rc;
+    /* into the caller's slots: items 2 (t - 1) and 2 (t - 1) + 1 of a pair are rank t's mates 1 and 2 */
+    size_t item = 0;
+    for (int64_t q = 0; q < np; q++) {
+        const uint32_t want = std::min<uint32_t>(n_pairs[q], (uint32_t)max_pairs);
+        const uint8_t extra = ASM_MAP_PROPER_PAIR | ASM_MAP_SECONDARY | (n_pairs[q] > (uint32_t)max_pairs ? ASM_MAP_HITS_TRUNCATED : 0);
+        for (uint32_t t = 1; t < want; t++, item += 2) {
+            const size_t o = ((size_t)q * max_pairs + t) * 2;
+            for (int x = 0; x < 2; x++) {
+                out[o + x] = it.hits[item + x];
+                out[o + x].flags |= extra;
+                it.cigar_to(cg, o + x, item + x);
+            }
+            tlen[(size_t)q * max_pairs + t] = (int32_t)(std::max(out[o].end, out[o + 1].end) - std::min(out[o].pos, out[o + 1].pos));
+        }
+    }
+    return ASM_OK;
+}
+
+/* pairs per chunk: at most map_chunk / 2; the run key holds the read (2 per pair) in its top 31 bits */
+static int64_t map_pair_step(const asm_handle* h) { return std::max<int64_t>(1, std::min<int64_t>(h->map_chunk, (int64_t)1 << 30) / 2); }
+
+} /* extern "C++" */
+
+int asm_index_build(asm_handle* h, const char* text, const uint64_t* seq_off, int32_t n_seqs, int k, asm_index** out) {
+    if (!out || !seq_off) return fail(h, ASM_EINVAL, "asm_index_build: NULL argument");
+    *out = nullptr;
+    if (n_seqs < 1 || n_seqs >= MAP_MAX_SEQS) return fail(h, ASM_EINVAL, "asm_index_build: n_seqs must be in [1, 2^26)");
+    if (k < ASM_MAP_MIN_K || k > ASM_MAP_MAX_K) return fail(h, ASM_EINVAL, "asm_index_build: k must be in [8, 14]");
+    if (seq_off[0] != 0) return fail(h, ASM_EINVAL, "asm_index_build: seq_off[0] must be 0");
+    for (int32_t r = 0; r < n_seqs; r++)
+        if (seq_off[r + 1] < seq_off[r]) return fail(h, ASM_EINVAL, "asm_index_build: seq_off must be non-decreasing");
+    const uint64_t len = seq_off[n_seqs];
+    if (len >= 0xffffffffull) return fail(h, ASM_EUNSUPPORTED, "asm_index_build: total reference length must be below 2^32");
+    if (len && !text) return fail(h, ASM_EINVAL, "asm_index_build: text is NULL");
+    if (!h) return fail(h, ASM_EINVAL, "asm_index_build: NULL handle");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::unique_ptr<asm_index> ix(new asm_index);
+    ix->device = h->device, ix->k = k, ix->n_seqs = n_seqs, ix->len = len;
+    ix->seq_off.assign(seq_off, seq_off + n_seqs + 1);
+    const uint32_t nb = (1u << (2 * k)) + 1u;
+    HIPCHK(h, big_malloc(h, (void**)&ix->d_text, len + 16));
+    HIPCHK(h, big_malloc(h, (void**)&ix->d_seq_off, sizeof(unsigned long long) * (size_t)(n_seqs + 1)));
+    HIPCHK(h, big_malloc(h, (void**)&ix->d_off, sizeof(uint32_t) * nb));
+    HIPCHK(h, big_malloc(h, (void**)&ix->d_pos, sizeof(uint32_t) * (len ? len : 1)));
+    if (len) HIPCHK(h, hipMemcpyAsync(ix->d_text, text, len, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(ix->d_seq_off, seq_off, sizeof(uint64_t) * (size_t)(n_seqs + 1), hipMemcpyHostToDevice, h->stream));
+    if (len) {
+        Scratch<uint32_t> keys(h), keys2(h), vals(h);
+        MapTmp tmp(h);
+        HIPCHK(h, keys.alloc(sizeof(uint32_t) * len));
+        HIPCHK(h, keys2.alloc(sizeof(uint32_t) * len));
+        HIPCHK(h, vals.alloc(sizeof(uint32_t) * len));
+        hipLaunchKernelGGL(map_upper_kernel, dim3(map_grid(len, h)), dim3(256), 0, h->stream, ix->d_text, (unsigned long long)len);
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL(map_kmer_key_kernel, dim3(map_grid(len, h)), dim3(256), 0, h->stream, (const char*)ix->d_text,
+                           (unsigned long long)len, (const unsigned long long*)ix->d_seq_off, (uint32_t)n_seqs, k, keys.p, vals.p);
+        HIPCHK(h, hipGetLastError());
+        /* stable: positions ascend inside a bucket */
+        HIPCHK(h, map_sort_pairs(h, tmp, keys.p, keys2.p, vals.p, ix->d_pos, (uint32_t)len, 2 * k + 1));
+        hipLaunchKernelGGL(map_bucket_offsets_kernel, dim3(map_grid(nb, h)), dim3(256), 0, h->stream, (const uint32_t*)keys2.p,
+                           (unsigned long long)len, nb, ix->d_off);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    } else {
+        HIPCHK(h, hipMemsetAsync(ix->d_off, 0, sizeof(uint32_t) * nb, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    *out = ix.release();
+    return ASM_OK;
+}
+
+int asm_index_free(asm_handle* h, asm_index* ix) {
+    (void)h;
+    delete ix;
+    return ASM_OK;
+}
+
+int asm_map_reads(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
+                  const asm_map_params* p, asm_map_hit* out, uint16_t* cigar_ops, int cigar_cap, uint8_t* cigar_nops) {
+    if (!p || !ix || n < 0 || !read_off || (n > 0 && (!reads || !out))) return fail(h, ASM_EINVAL, "asm_map_reads: bad arguments");
+    const MapCigars cg = {cigar_ops, cigar_cap, cigar_nops};
+    if (const int rc = map_check_args(h, ix, "asm_map_reads", "read", {n, p, {read_off, nullptr}, nullptr, nullptr, 0, 0, 0, cg}))
+        return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    return map_chunks(n, h->map_chunk, [&](int64_t c0, int64_t cn) {
+        return map_chunk(h, ix, cn, reads, read_off + c0, p, out + c0, cg.at((size_t)c0));
+    });
+}
+
+int asm_map_reads_all(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
+                      const asm_map_params* p, int strata, int max_hits, uint32_t* n_hits, asm_map_hit* out, uint16_t* cigar_ops,
+                      int cigar_cap, uint8_t* cigar_nops) {
+    if (!p || !ix || n < 0 || !read_off || (n > 0 && (!reads || !out || !n_hits)))
+        return fail(h, ASM_EINVAL, "asm_map_reads_all: bad arguments");
+    const MapCigars cg = {cigar_ops, cigar_cap, cigar_nops};
+    if (const int rc = map_check_args(h, ix, "asm_map_reads_all", "read",
+                                      {n, p, {read_off, nullptr}, nullptr, "max_hits", strata, ASM_MAP_MAX_ERRORS, max_hits, cg}))
+        return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    /* the run key holds the read in its top 31 bits */
+    return map_chunks(n, std::min<int64_t>(h->map_chunk, (int64_t)1 << 30), [&](int64_t c0, int64_t cn) {
+        const size_t o = (size_t)c0 * max_hits;
+        return map_chunk_all(h, ix, cn, reads, read_off + c0, p, strata, max_hits, n_hits + c0, out + o, cg.at(o));
+    });
+}
+
+int asm_map_pairs(asm_handle* h, const asm_index* ix, int64_t n, const char* reads1, const uint32_t* off1, const char* reads2,
+                  const uint32_t* off2, const asm_map_params* p, const asm_pair_params* pp, asm_map_hit* out, int32_t* tlen,
+                  uint32_t* n_concordant, uint16_t* cigar_ops, int cigar_cap, uint8_t* cigar_nops) {
+    if (!p || !pp || !ix || n < 0 || !off1 || !off2 || (n > 0 && (!reads1 || !reads2 || !out || !tlen || !n_concordant)))
+        return fail(h, ASM_EINVAL, "asm_map_pairs: bad arguments");
+    const MapCigars cg = {cigar_ops, cigar_cap, cigar_nops};
+    if (const int rc = map_check_args(h, ix, "asm_map_pairs", "mate", {n, p, {off1, off2}, pp, nullptr, 0, 0, 0, cg})) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    const MapPairsIn m = {reads1, off1, reads2, off2};
+    return map_chunks(n, map_pair_step(h), [&](int64_t c0, int64_t cn) {
+        return map_chunk_pairs(h, ix, cn, m.at(c0), p, pp, out + 2 * c0, tlen + c0, n_concordant + c0, cg.at((size_t)c0 * 2));
+    });
+}
+
+int asm_map_pairs_all(asm_handle* h, const asm_index* ix, int64_t n, const char* reads1, const uint32_t* off1, const char* reads2,
+                      const uint32_t* off2, const asm_map_params* p, const asm_pair_params* pp, int strata, int max_pairs,
+                      uint32_t* n_pairs, asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant, uint16_t* cigar_ops, int cigar_cap,
+                      uint8_t* cigar_nops) {
+    if (!p || !pp || !ix || n < 0 || !off1 || !off2 || (n > 0 && (!reads1 || !reads2 || !out || !tlen || !n_concordant)))
+        return fail(h, ASM_EINVAL, "asm_map_pairs_all: bad arguments");
+    if (n > 0 && !n_pairs) return fail(h, ASM_EINVAL, "asm_map_pairs_all: n_pairs is NULL");
+    const MapCigars cg = {cigar_ops, cigar_cap, cigar_nops};
+    if (const int rc = map_check_args(h, ix, "asm_map_pairs_all", "mate",
+                                      {n, p, {off1, off2}, pp, "max_pairs", strata, 2 * ASM_MAP_MAX_ERRORS, max_pairs, cg}))
+        return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    const MapPairsIn m = {reads1, off1, reads2, off2};
+    return map_chunks(n, map_pair_step(h), [&](int64_t c0, int64_t cn) {
+        const size_t o = (size_t)c0 * max_pairs;
+        return map_chunk_pairs_all(h, ix, cn, m.at(c0), p, pp, strata, max_pairs, n_pairs + c0, out + 2 * o, tlen + o, n_concordant + c0,
+                                   cg.at(2 * o));
+    });
+}

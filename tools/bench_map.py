@@ -1,5 +1,5 @@
 """Read-mapper timings (development tool): PYTHONPATH=. python tools/bench_map.py [--ref-len 5e6] [--reads 1e6] [--len 100]
-[--errors 2 4] [--all-hits N [--strata S]] [--repeats] [--out DIR] [--profile]
+[--errors 2 4] [--all-hits N [--strata S]] [--repeats] [--out DIR] [--dump DIR] [--profile]
 A random reference (one sequence, seeded) and reads sampled from both strands with 0..e substitutions plus 10 % random reads;
 reports the index build and the mapping of all reads (both strands), each timed with HIP events on the engine's stream around one
 synchronous library call (so host-to-device copies and the host's share of asm_map_reads are inside), plus the wall clock.
@@ -12,11 +12,14 @@ one mate carrying e+1..e+3 substitutions; with --repeats, 30 % of the fragments 
 against asm_map_reads_all (strata = e, max_hits = 1) on the same reads, alternately, and reports the proper and rescued fractions.
 --paired --all-hits N [--strata S] times asm_map_pairs_all (up to N pairs per fragment, pair strata S, default 2e) against
 asm_map_pairs instead, alternately, and prints the n_pairs distribution.
+--dump DIR writes DIR/digests.json: the SHA-256 of every output array of every timed call (per e; CIGAR rows up to their nops), for comparing two builds
+of the library (ASM_MI355X_LIB, a fresh process each) for exact equality on a workload of real size.
 --profile re-runs the same command under `rocprofv3 --kernel-trace --stats` (a run of its own) and prints the per-kernel totals."""
 import argparse
 import ctypes
 import csv
 import glob
+import hashlib
 import json
 import os
 import subprocess
@@ -68,6 +71,20 @@ def make_inputs(ref_len, n, length, e, seed, repeats=False):
     return ref, reads
 
 
+def dump_digests(a, e, arrays):
+    """adds {call.array: sha256} of one e to DIR/digests.json"""
+    os.makedirs(a.dump, exist_ok=True)
+    path = os.path.join(a.dump, "digests.json")
+    table = json.load(open(path)) if os.path.exists(path) and e != a.errors[0] else {}
+    arrays = {name: v for name, v in arrays.items() if v is not None}
+    for name in [x for x in arrays if x.endswith(".ops")]:  # a CIGAR row is defined up to its nops; the rest is whatever was there
+        nops = arrays[name[:-4] + ".nops"].reshape(-1, 1)
+        arrays[name] = np.where(np.arange(16)[None, :] < nops, arrays[name].reshape(-1, 16), 0).astype(np.uint16)
+    table["e=%d" % e] = {name: hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest() for name, v in arrays.items()}
+    with open(path, "w") as fh:
+        json.dump(table, fh, indent=1, sort_keys=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref-len", type=float, default=5e6)
@@ -83,6 +100,7 @@ def main():
     ap.add_argument("--insert", default="200,500", help="with --paired: MIN,MAX of the projected span")
     ap.add_argument("--rescue", type=int, default=-1, help="with --paired: mate rescue's error bound (-1: off)")
     ap.add_argument("--out", default=None, help="directory for the JSON result (and the profile with --profile)")
+    ap.add_argument("--dump", default=None, help="directory for digests.json, the SHA-256 of every output array")
     ap.add_argument("--profile", action="store_true")
     a = ap.parse_args()
     extra = (["--all-hits", str(a.all_hits)] if a.all_hits else []) + (["--strata", str(a.strata)] if a.strata is not None else [])
@@ -149,6 +167,9 @@ def main():
                 tm.stop()
                 best_all = min(best_all, tm.elapsed_ms())
         lib.asm_index_free(h, ix)
+        if a.dump:
+            dump_digests(a, e, {"reads.hits": hits, "reads.ops": ops, "reads.nops": nops, "reads_all.n_hits": n_hits if a.all_hits else None,
+                                "reads_all.hits": all_hits, "reads_all.ops": all_ops, "reads_all.nops": all_nops})
         mapped = float(((hits["flags"] & m.MAP_MAPPED) != 0).mean())
         row = {"e": e, "index_build_ms": round(best_ix, 3), "map_ms_events": round(best_map, 3), "map_ms_wall": round(best_wall, 3),
                "reads_per_s": round(n / best_map * 1e3), "mapped_fraction": round(mapped, 4)}
@@ -275,6 +296,13 @@ def run_paired(a, eng, tm, n, ref_len):
             tm.stop()
             best_all = min(best_all, tm.elapsed_ms())
         lib.asm_index_free(h, ix)
+        if a.dump:
+            dump_digests(a, e, {"pairs.hits": hits, "pairs.tlen": tlen, "pairs.n_concordant": nconc, "pairs.ops": ops, "pairs.nops": nops,
+                                "pairs_all.n_pairs": n_pairs if a.all_hits else None, "pairs_all.hits": pa_hits, "pairs_all.tlen": pa_tlen,
+                                "pairs_all.n_concordant": pa_nconc if a.all_hits else None, "pairs_all.ops": pa_ops,
+                                "pairs_all.nops": pa_nops, "reads_all.n_hits": None if a.all_hits else n_hits,
+                                "reads_all.hits": None if a.all_hits else all_hits, "reads_all.ops": None if a.all_hits else all_ops,
+                                "reads_all.nops": None if a.all_hits else all_nops})
         fl = hits["flags"].reshape(npairs, 2)
         row = {"e": e, "pairs_ms_events": round(best_pairs, 3), "pairs_per_s": round(npairs / best_pairs * 1e3),
                "all_hits1_ms_events": round(best_all, 3), "pairs_over_all_hits1": round(best_pairs / best_all, 3),
