@@ -99,6 +99,13 @@ class MapParams(ctypes.Structure):
                 ("greedy_k", ctypes.c_int32)]
 
 
+class MapFileStats(ctypes.Structure):
+    """asm_map_file_stats"""
+    _fields_ = [("reads", ctypes.c_int64), ("mapped", ctypes.c_int64), ("too_long", ctypes.c_int64), ("records", ctypes.c_int64),
+                ("chunks", ctypes.c_int64), ("bytes_in", ctypes.c_int64), ("bytes_out", ctypes.c_int64),
+                ("seconds", ctypes.c_double), ("seconds_read", ctypes.c_double), ("seconds_write", ctypes.c_double)]
+
+
 class PairParams(ctypes.Structure):
     """asm_pair_params: projected span in [min_insert, max_insert] (0 <= min <= max <= 8192), mate rescue's error bound (-1 = off)."""
 
@@ -250,6 +257,9 @@ def load_library() -> ctypes.CDLL:
         "asm_map_pairs": (i32, [vp, vp, i64, vp, vp, vp, vp, c.POINTER(MapParams), c.POINTER(PairParams), vp, vp, vp, vp, i32, vp]),
         "asm_map_pairs_all": (i32, [vp, vp, i64, vp, vp, vp, vp, c.POINTER(MapParams), c.POINTER(PairParams), i32, i32, vp, vp, vp, vp,
                                     vp, i32, vp]),
+        "asm_map_file": (i32, [vp, vp, c.POINTER(c.c_char_p), c.c_char_p, c.c_char_p, c.c_char_p, c.POINTER(MapParams), i32, i32, i64,
+                               c.POINTER(MapFileStats)]),
+        "asm_fastq_cut": (c.c_size_t, [vp, c.c_size_t, c.POINTER(i64)]),
         "asm_device_malloc": (i32, [vp, c.c_size_t, c.POINTER(vp)]),
         "asm_device_free": (i32, [vp, vp]),
         "asm_memcpy_d2h": (i32, [vp, vp, vp, c.c_size_t]),
@@ -630,6 +640,25 @@ class Engine:
         out["mapq"] = np.minimum(254, 60 + flat["greedy_cost"].astype(np.int64)).astype(np.int32)
         out["cigar"] = self._cigars(ops[read, rank], nops[read, rank], cigar_cap)
         return out
+
+    def map_file(self, index: Index, names, fastq_path: str, sam_path: str, max_errors: int, both_strands: bool = True,
+                 max_occ: int = 0, greedy_k: int = 3, max_hits: int = 0, strata: Optional[int] = None, chunk_bytes: int = 0,
+                 header: Optional[str] = None) -> dict:
+        """asm_map_file: a four-line FASTQ file in, a SAM file out, parsed, mapped and formatted on the device (docs/design/mapper.md,
+        "Files: FASTQ in, SAM out").  names: one RNAME per sequence of the index.  max_hits=0: the best hit per read (map_reads);
+        1..256: the loci of map_reads_all with strata (None: max_errors).  header is written first, as it is.  -> the stats as a dict:
+        reads, mapped, too_long, records (SAM lines), chunks, bytes_in, bytes_out, seconds, seconds_read, seconds_write."""
+        names = [_as_bytes(nm) for nm in names]
+        if len(names) != len(index.lengths):
+            raise ValueError("names must hold one name per sequence of the index")
+        arr = (ctypes.c_char_p * max(len(names), 1))(*names)
+        p = MapParams(int(max_errors), 1 if both_strands else 0, int(max_occ), int(greedy_k))
+        st = MapFileStats()
+        strata = int(max_errors) if strata is None else int(strata)
+        self._chk(self.lib.asm_map_file(self.h, index.ptr, arr, os.fsencode(fastq_path), os.fsencode(sam_path),
+                                        None if header is None else _as_bytes(header), ctypes.byref(p), int(max_hits), strata,
+                                        int(chunk_bytes), ctypes.byref(st)))
+        return {name: getattr(st, name) for name, _ in MapFileStats._fields_}
 
     def map_pairs(self, index: Index, reads1, reads2, max_errors: int, min_insert: int, max_insert: int, rescue_errors: int = -1,
                   max_occ: int = 0, greedy_k: int = 3, cigar_cap: int = 64, chunk: Optional[int] = None):

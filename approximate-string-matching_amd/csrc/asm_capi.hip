@@ -38,6 +38,8 @@
 #include "asm_filter.h"
 #include "asm_ingest.h"
 #include "asm_map.h"
+#include "asm_fastq.h"
+#include "asm_sam.h"
 
 struct asm_handle {
     unsigned long long serial = 0;        /* unique over the life of the process: a batch names its owner by (pointer, serial), so a
@@ -2351,6 +2353,8 @@ int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, in
 
 /* ---- read mapping: host side in csrc/asm_map_host.h (kernels: csrc/asm_map.h, design: docs/design/mapper.md) -------------------- */
 #include "asm_map_host.h"
+/* asm_map_file: FASTQ in, SAM out, through the same stages */
+#include "asm_map_file.h"
 
 /* ---------------------------------------------------------------------------------------------------- */
 int asm_device_malloc(asm_handle* h, size_t bytes, void** d_ptr) {

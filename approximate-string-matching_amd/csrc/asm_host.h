@@ -1,7 +1,8 @@
 // The device-free part of the C ABI's host side: everything in libasm_mi355x.so that runs on the CPU and never calls HIP —
 // the seeded generator's host loop (asm_generate_pairs), the stale-tail state arithmetic (asm_tail_state_advance), the CIGAR
 // formatter (asm_cigar_format), and the reader side of asm_stream_seq_file: newline scanning, the persistent reader pool, and
-// the three-slot hand-over between the reader thread and the caller's thread (SeqReader).
+// the three-slot hand-over between the reader thread and the caller's thread (SeqReader); and asm_map_file's host threads: the
+// FASTQ chunk cutter (asm_fastq_cut), its reader (FastqReader) and the SAM writer (ChunkWriter).
 //
 // Kept in a header without any HIP include so that the SAME code is compiled twice: into the product by hipcc (asm_capi.hip),
 // and by plain g++ under -fsanitize=thread / address,undefined into host/asm_host_check.cpp (`make -C oracle asan`,
@@ -428,6 +429,216 @@ public:
     }
     bool failed() const { return failed_.load(); }
     double read_seconds() const { return read_seconds_; } /* after stop() */
+};
+
+// ---- four-line FASTQ (asm_map_file): chunk cutting and the reader thread --------------------------------------------------------
+/* the longest prefix of buf[0, nbytes) made of whole records (four lines each, every line ending in '\n'): its length, and how
+ * many records it holds; *lines (may be NULL) = all newlines of buf */
+inline size_t fastq_cut(const char* buf, size_t nbytes, int64_t* records, int64_t* lines = nullptr) {
+    int64_t count = 0;
+    size_t boundary = 0;
+    const char* q = buf;
+    const char* end = buf + nbytes;
+    while (q < end) {
+        const char* hit = (const char*)memchr(q, '\n', (size_t)(end - q));
+        if (!hit) break;
+        q = hit + 1;
+        if ((++count & 3) == 0) boundary = (size_t)(q - buf);
+    }
+    if (records) *records = count / 4;
+    if (lines) *lines = count;
+    return boundary;
+}
+
+struct FastqSlot { /* one (pinned) host buffer */
+    char* buf = nullptr;
+    size_t cap = 0;   /* usable bytes */
+    size_t bytes = 0; /* raw bytes to ship: whole records only */
+    int64_t records = 0;
+    int64_t extra_lines = 0; /* last chunk: lines behind the last whole record (a truncated record) */
+    bool last = false;
+    bool ready = false;
+    bool in_flight = false;
+};
+
+/* The reader thread of asm_map_file; the hand-over is SeqReader's: three slots in rotation, chunk c in slot c % 3, chunks ramping
+ * up from first_chunk to chunk.  A chunk is the carry of the one before plus `want` file bytes, cut behind its last whole record
+ * (fastq_cut); when that leaves no record at all the chunk takes more bytes, and the slot grows through grow(slot, capacity, keep)
+ * (the owner of the buffers moves the first `keep` bytes into a larger one and sets slot[q].buf and cap; false: out of memory). */
+class FastqReader {
+    const int fd_;
+    const size_t file_bytes_, chunk_, first_chunk_;
+    const std::function<void(int)> wait_shipped_;
+    const std::function<bool(int, size_t, size_t)> grow_;
+    std::mutex mu_;
+    std::condition_variable cv_;
+    std::atomic<bool> failed_{false}, stop_{false};
+    double read_seconds_ = 0;
+    std::thread reader_;
+
+    bool read_more(FastqSlot& s, int q, size_t have, size_t want, size_t file_off) {
+        if (have + want + 8 > s.cap && !grow_(q, have + want + 8 + (have + want) / 4, have)) return false;
+        for (size_t a = 0; a < want;) {
+            const ssize_t got = pread(fd_, s.buf + have + a, want - a, (off_t)(file_off + a));
+            if (got <= 0) return false;
+            a += (size_t)got;
+        }
+        return true;
+    }
+
+    void loop() {
+        std::vector<char> carry;
+        size_t file_off = 0;
+        bool eof = file_bytes_ == 0;
+        for (int c = 0; !stop_; c++) {
+            FastqSlot& s = slot[c % 3];
+            {
+                std::unique_lock<std::mutex> lk(mu_);
+                cv_.wait(lk, [&] { return stop_ || !s.ready; });
+                if (stop_) return;
+            }
+            if (s.in_flight) {
+                wait_shipped_(c % 3);
+                s.in_flight = false;
+            }
+            const auto t0 = std::chrono::steady_clock::now();
+            size_t have = carry.size();
+            bool ok = have + 8 <= s.cap || grow_(c % 3, have + 8 + chunk_, 0);
+            if (ok && have) memcpy(s.buf, carry.data(), have);
+            carry.clear();
+            int64_t records = 0, lines = 0;
+            size_t boundary = 0;
+            size_t want = c < 30 && (first_chunk_ << c) < chunk_ ? first_chunk_ << c : chunk_;
+            while (ok) {
+                if (want > file_bytes_ - file_off) want = file_bytes_ - file_off;
+                ok = read_more(s, c % 3, have, want, file_off);
+                if (!ok) break;
+                file_off += want, have += want;
+                eof = file_off >= file_bytes_;
+                if (eof && have && s.buf[have - 1] != '\n') s.buf[have++] = '\n'; /* a last line without its newline */
+                boundary = fastq_cut(s.buf, have, &records, &lines);
+                if (records > 0 || eof) break;
+                want = chunk_; /* one record longer than the chunk: take more */
+            }
+            if (ok && !eof) carry.assign(s.buf + boundary, s.buf + have);
+            read_seconds_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            if (!ok) failed_ = true;
+            {
+                std::lock_guard<std::mutex> lk(mu_);
+                s.bytes = boundary, s.records = records, s.extra_lines = eof ? lines - 4 * records : 0, s.last = eof, s.ready = true;
+            }
+            cv_.notify_all();
+            if (!ok || eof) return;
+        }
+    }
+
+public:
+    FastqSlot slot[3]; /* the caller sets buf and cap before start() */
+
+    FastqReader(int fd, size_t file_bytes, size_t chunk, size_t first_chunk, std::function<void(int)> wait_shipped,
+                std::function<bool(int, size_t, size_t)> grow)
+        : fd_(fd), file_bytes_(file_bytes), chunk_(chunk), first_chunk_(first_chunk > 0 && first_chunk < chunk ? first_chunk : chunk),
+          wait_shipped_(std::move(wait_shipped)), grow_(std::move(grow)) {}
+    ~FastqReader() { stop(); }
+    void start() { reader_ = std::thread([this] { loop(); }); }
+    FastqSlot* wait_ready(int c) { /* chunk c, in order; nullptr when reading failed */
+        FastqSlot& s = slot[c % 3];
+        {
+            std::unique_lock<std::mutex> lk(mu_);
+            cv_.wait(lk, [&] { return s.ready || failed_.load(); });
+        }
+        return failed_ ? nullptr : &s;
+    }
+    void consumed(int c, bool in_flight) {
+        FastqSlot& s = slot[c % 3];
+        s.in_flight = in_flight;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            s.ready = false;
+        }
+        cv_.notify_all();
+    }
+    void stop() {
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            stop_ = true;
+        }
+        cv_.notify_all();
+        if (reader_.joinable()) reader_.join();
+    }
+    double read_seconds() const { return read_seconds_; } /* after stop() */
+};
+
+/* The writer thread of asm_map_file: jobs (a buffer and its length) are written in the order they were given; before(job) waits for
+ * the bytes to be there (the copy out of the device), after(job) gives the buffer back. */
+class ChunkWriter {
+    FILE* f_;
+    struct Job {
+        int slot;
+        const char* buf;
+        size_t bytes;
+    };
+    const std::function<bool(int)> before_;
+    std::mutex mu_;
+    std::condition_variable cv_;
+    std::vector<Job> queue_;
+    bool busy_[3] = {false, false, false};
+    bool quit_ = false, failed_ = false;
+    double write_seconds_ = 0;
+    std::thread writer_;
+
+    void loop() {
+        for (;;) {
+            Job j;
+            {
+                std::unique_lock<std::mutex> lk(mu_);
+                cv_.wait(lk, [&] { return quit_ || !queue_.empty(); });
+                if (queue_.empty()) return;
+                j = queue_.front();
+                queue_.erase(queue_.begin());
+            }
+            bool ok = before_(j.slot);
+            const auto t0 = std::chrono::steady_clock::now();
+            if (ok && j.bytes) ok = fwrite(j.buf, 1, j.bytes, f_) == j.bytes;
+            write_seconds_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            {
+                std::lock_guard<std::mutex> lk(mu_);
+                busy_[j.slot] = false;
+                if (!ok) failed_ = true;
+            }
+            cv_.notify_all();
+        }
+    }
+
+public:
+    ChunkWriter(FILE* f, std::function<bool(int)> before) : f_(f), before_(std::move(before)) { writer_ = std::thread([this] { loop(); }); }
+    ~ChunkWriter() { finish(); }
+    void wait_idle(int slot) { /* the job that used this slot (three jobs ago) is on disk */
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [&] { return !busy_[slot]; });
+    }
+    void push(int slot, const char* buf, size_t bytes) {
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            busy_[slot] = true;
+            queue_.push_back({slot, buf, bytes});
+        }
+        cv_.notify_all();
+    }
+    bool finish() { /* writes what is queued, joins; false when a write failed */
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            quit_ = true;
+        }
+        cv_.notify_all();
+        if (writer_.joinable()) writer_.join();
+        return !failed_;
+    }
+    bool failed() {
+        std::lock_guard<std::mutex> lk(mu_);
+        return failed_;
+    }
+    double write_seconds() const { return write_seconds_; } /* after finish() */
 };
 
 }  // namespace asm_host

@@ -942,3 +942,22 @@ __global__ __launch_bounds__(256) void map_greedy_gather_kernel(const uint32_t* 
         for (uint32_t p = (uint32_t)lane; p < len; p += 64u) wout[o + p] = text[w + p];
     }
 }
+
+/* The finish stage with the records left on the device (asm_map_file): which items are mapped (n + 1 entries, the last 0, for the
+ * exclusive scan that numbers them), their list, and Greedy's costs into their records. */
+__global__ __launch_bounds__(256) void map_mapped_flag_kernel(const MapHit* __restrict__ hits, long n, uint32_t* __restrict__ flag) {
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q <= n) flag[q] = (q < n && (hits[q].flags & MAP_F_MAPPED)) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void map_mapped_list_kernel(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ slot, long n,
+                                                              uint32_t* __restrict__ list) {
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < n && flag[q]) list[slot[q]] = (uint32_t)q;
+}
+
+__global__ __launch_bounds__(256) void map_cost_kernel(const uint32_t* __restrict__ list, const int32_t* __restrict__ cost, long nl,
+                                                       MapHit* __restrict__ hits) {
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < nl) hits[list[q]].greedy_cost = cost[q];
+}

@@ -1,0 +1,367 @@
+// asm_map_file: a FASTQ file in, a SAM file out, parsed, mapped and formatted on the device (kernels: asm_fastq.h, asm_sam.h and the
+// mapper's own; stages: asm_map_host.h; reader and writer threads: asm_host.h; design: docs/design/mapper.md, "Files: FASTQ in, SAM
+// out").  asm_capi.hip includes this file inside its extern "C" block, behind asm_map_host.h.
+#pragma once
+
+extern "C++" {
+
+#define MAP_FILE_TRY(call)                                                                  \
+    do {                                                                                    \
+        hipError_t _e = (call);                                                             \
+        if (_e != hipSuccess)                                                               \
+            return fail(h, _e == hipErrorOutOfMemory ? ASM_ENOMEM : ASM_ENODEVICE,          \
+                        std::string("asm_map_file: ") + #call + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+/* What one call owns besides its threads: the files, two more streams, the pinned buffers (three in, three out, in rotation), the
+ * device buffers that other streams read (raw text: two; SAM bytes: three) and the events between them.  The destructor waits for
+ * the streams and gives everything back, on every path; the threads are declared after it, so they are joined before. */
+struct MapFilePipe {
+    asm_handle* h;
+    int fd = -1;
+    FILE* out = nullptr;
+    hipStream_t s_in = nullptr, s_out = nullptr;
+    char* pin_in[3] = {nullptr, nullptr, nullptr};
+    char* pin_out[3] = {nullptr, nullptr, nullptr};
+    size_t pin_out_cap[3] = {0, 0, 0};
+    char* d_raw[2] = {nullptr, nullptr};
+    size_t d_raw_cap[2] = {0, 0};
+    char* d_out[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t ev_shipped[3] = {nullptr, nullptr, nullptr}; /* the copy out of pinned input slot q is over */
+    hipEvent_t ev_h2d[2] = {nullptr, nullptr};              /* d_raw[q] holds its chunk */
+    hipEvent_t ev_gate = nullptr;                           /* everything enqueued on the handle's stream so far */
+    hipEvent_t ev_fmt[3] = {nullptr, nullptr, nullptr};     /* d_out[o] holds its SAM bytes */
+    hipEvent_t ev_copied[3] = {nullptr, nullptr, nullptr};  /* pin_out[o] holds them */
+    explicit MapFilePipe(asm_handle* owner) : h(owner) {}
+    hipError_t open_device() {
+        hipError_t e = hipStreamCreateWithFlags(&s_in, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&s_out, hipStreamNonBlocking);
+        for (hipEvent_t* ev : {&ev_shipped[0], &ev_shipped[1], &ev_shipped[2], &ev_h2d[0], &ev_h2d[1], &ev_gate, &ev_fmt[0], &ev_fmt[1],
+                               &ev_fmt[2], &ev_copied[0], &ev_copied[1], &ev_copied[2]})
+            if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+        return e;
+    }
+    ~MapFilePipe() {
+        (void)hipSetDevice(h->device);
+        if (s_in) (void)hipStreamSynchronize(s_in);
+        if (s_out) (void)hipStreamSynchronize(s_out);
+        (void)hipStreamSynchronize(h->stream);
+        for (hipEvent_t ev : {ev_shipped[0], ev_shipped[1], ev_shipped[2], ev_h2d[0], ev_h2d[1], ev_gate, ev_fmt[0], ev_fmt[1], ev_fmt[2],
+                              ev_copied[0], ev_copied[1], ev_copied[2]})
+            if (ev) (void)hipEventDestroy(ev);
+        if (s_in) (void)hipStreamDestroy(s_in);
+        if (s_out) (void)hipStreamDestroy(s_out);
+        for (char* q : pin_in)
+            if (q) (void)hipHostFree(q);
+        for (char* q : pin_out)
+            if (q) (void)hipHostFree(q);
+        for (char* q : d_raw) pool_free(h, q);
+        for (char* q : d_out) pool_free(h, q);
+        if (fd >= 0) close(fd);
+        if (out) fclose(out);
+    }
+};
+
+struct MapFileJob { /* what every chunk of a call shares */
+    asm_handle* h;
+    const asm_index* ix;
+    const asm_map_params* p;
+    int max_hits, strata;
+    const char* d_names;
+    const uint32_t* d_name_off;
+    MapFilePipe* pipe;
+    asm_host::ChunkWriter* writer;
+    asm_map_file_stats st = {};
+    int64_t out_seq = 0; /* device chunks handed to the writer so far */
+};
+
+/* Records [r0, r0 + rn) of the file chunk whose bytes are d_raw and whose newline positions are d_nl: one device chunk, from the
+ * record kernel to the writer's queue.  first_record: the file's records before r0 (for the message of a malformed one). */
+static int map_file_chunk(MapFileJob& j, const char* d_raw, const uint32_t* d_nl, int64_t r0, int64_t rn, int64_t first_record) {
+    asm_handle* h = j.h;
+    const asm_index* ix = j.ix;
+    const asm_map_params* p = j.p;
+    const size_t cnt = (size_t)rn + 1;
+    MapTmp tmp(h);
+    /* the records, and which of them go to the mapper */
+    Scratch<SamRec> d_recs(h);
+    Scratch<uint32_t> d_send(h), d_mlen(h), d_rd(h), d_mo(h);
+    Scratch<int32_t> d_rec_read(h);
+    Scratch<FastqCounts> d_counts(h);
+    Scratch<unsigned long long> d_start(h);
+    MAP_FILE_TRY(d_recs.alloc(sizeof(SamRec) * (size_t)rn));
+    for (Scratch<uint32_t>* x : {&d_send, &d_mlen, &d_rd, &d_mo}) MAP_FILE_TRY(x->alloc(sizeof(uint32_t) * cnt));
+    MAP_FILE_TRY(d_rec_read.alloc(sizeof(int32_t) * (size_t)rn));
+    MAP_FILE_TRY(d_counts.alloc(sizeof(FastqCounts)));
+    MAP_FILE_TRY(hipMemsetAsync(&d_counts.p->bad_min, 0xff, sizeof(uint32_t), h->stream));
+    MAP_FILE_TRY(hipMemsetAsync(&d_counts.p->too_long, 0, sizeof(uint32_t), h->stream));
+    hipLaunchKernelGGL(fastq_record_kernel, dim3(grid_for(rn + 1)), dim3(ASM_BLOCK), 0, h->stream, d_raw, d_nl, (long)r0, (long)rn,
+                       (uint32_t)ASM_MAP_MAX_READ, d_recs.p, d_send.p, d_mlen.p, d_counts.p);
+    MAP_FILE_TRY(hipGetLastError());
+    MAP_FILE_TRY(map_exclusive_sum(h, tmp, d_send.p, d_rd.p, (int64_t)cnt));
+    MAP_FILE_TRY(map_exclusive_sum(h, tmp, d_mlen.p, d_mo.p, (int64_t)cnt));
+    uint32_t tot[2] = {0, 0};
+    FastqCounts counts = {FASTQ_NO_RECORD, 0};
+    MAP_FILE_TRY(hipMemcpyAsync(&tot[0], d_rd.p + rn, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    MAP_FILE_TRY(hipMemcpyAsync(&tot[1], d_mo.p + rn, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    MAP_FILE_TRY(hipMemcpyAsync(&counts, d_counts.p, sizeof(counts), hipMemcpyDeviceToHost, h->stream));
+    MAP_FILE_TRY(hipStreamSynchronize(h->stream));
+    if (counts.bad_min != FASTQ_NO_RECORD)
+        return fail(h, ASM_EINVAL, "asm_map_file: record " + std::to_string(first_record + counts.bad_min + 1) +
+                                       " is malformed (line 1 of a record starts with '@', line 3 with '+')");
+    const int64_t ns = tot[0]; /* library reads */
+    /* compact and gather: the reads in HBM, numbered in file order */
+    MapFront f(h);
+    MAP_FILE_TRY(f.d_reads.alloc((size_t)tot[1] + 16));
+    MAP_FILE_TRY(f.d_roff.alloc(sizeof(uint32_t) * ((size_t)ns + 1)));
+    MAP_FILE_TRY(d_start.alloc(sizeof(unsigned long long) * ((size_t)ns + 1)));
+    hipLaunchKernelGGL(fastq_compact_kernel, dim3(grid_for(rn + 1)), dim3(ASM_BLOCK), 0, h->stream, (const SamRec*)d_recs.p,
+                       (const uint32_t*)d_send.p, (const uint32_t*)d_rd.p, (const uint32_t*)d_mo.p, (long)rn, d_rec_read.p, f.d_roff.p,
+                       d_start.p);
+    MAP_FILE_TRY(hipGetLastError());
+    /* map: the library's stages, fed from device memory; the records, ops and nops stay there */
+    Scratch<unsigned long long> d_keys(h);
+    MapAllItems ai(h);
+    MapFinish fin(h);
+    std::vector<uint32_t> n_hits;
+    int64_t nlines = rn;
+    if (ns > 0) {
+        hipLaunchKernelGGL(seq_gather_kernel, dim3((unsigned)std::min<int64_t>((ns + 3) / 4, 256 * 16)), dim3(ASM_BLOCK), 0, h->stream,
+                           d_raw, (const unsigned long long*)d_start.p, (const uint32_t*)f.d_roff.p, (long)ns, f.d_reads.p);
+        MAP_FILE_TRY(hipGetLastError());
+        f.roff.resize((size_t)ns + 1);
+        f.bytes = tot[1];
+        MAP_FILE_TRY(hipMemcpyAsync(f.roff.data(), f.d_roff.p, sizeof(uint32_t) * ((size_t)ns + 1), hipMemcpyDeviceToHost, h->stream));
+        MAP_FILE_TRY(hipStreamSynchronize(h->stream));
+        if (const int rc = map_front_seed(h, ix, ns, p, f)) return rc;
+        if (j.max_hits == 0) {
+            if (const int rc = map_best_keys(h, ix, ns, p, f, d_keys)) return rc;
+            if (const int rc = map_finish_launch(h, ix, p, f, ns, d_keys.p, nullptr, nullptr, f.bytes + (size_t)ns, SAM_CIGAR_CAP, fin))
+                return rc;
+        } else {
+            n_hits.resize((size_t)ns);
+            if (const int rc = map_all_items(h, ix, ns, p, j.strata, j.max_hits, f, n_hits.data(), ai, "asm_map_file")) return rc;
+            if (const int rc = map_finish_launch(h, ix, p, f, ai.ni, ai.d_ikey.p, ai.d_iread.p, ai.d_idirs.p, ai.dwords, SAM_CIGAR_CAP, fin))
+                return rc;
+            nlines = (rn - ns) + ai.ni; /* the item list is in read-then-rank order, which is SAM order */
+        }
+        if (const int rc = map_finish_device(h, ix, p, f, fin)) return rc;
+    }
+    if (nlines > (int64_t)INT32_MAX) return fail(h, ASM_EUNSUPPORTED, "asm_map_file: more than 2^31 - 1 SAM lines in a chunk");
+    /* format: the line list, every line's size, its offset, the bytes */
+    Scratch<uint32_t> d_lcnt(h), d_lbase(h), d_lrec(h), d_litem(h);
+    Scratch<unsigned long long> d_size(h), d_off(h), d_nmapped(h);
+    MAP_FILE_TRY(d_lcnt.alloc(sizeof(uint32_t) * cnt));
+    MAP_FILE_TRY(d_lbase.alloc(sizeof(uint32_t) * cnt));
+    MAP_FILE_TRY(d_lrec.alloc(sizeof(uint32_t) * (size_t)nlines));
+    MAP_FILE_TRY(d_litem.alloc(sizeof(uint32_t) * (size_t)nlines));
+    MAP_FILE_TRY(d_size.alloc(sizeof(unsigned long long) * ((size_t)nlines + 1)));
+    MAP_FILE_TRY(d_off.alloc(sizeof(unsigned long long) * ((size_t)nlines + 1)));
+    MAP_FILE_TRY(d_nmapped.alloc(sizeof(unsigned long long)));
+    MAP_FILE_TRY(hipMemsetAsync(d_nmapped.p, 0, sizeof(unsigned long long), h->stream));
+    SamArgs a = {};
+    a.raw = d_raw, a.recs = d_recs.p, a.rec_read = d_rec_read.p, a.nrec = (long)rn, a.nlines = (long)nlines;
+    a.line_rec = d_lrec.p, a.line_item = d_litem.p, a.hits = fin.d_hits.p, a.ops = fin.d_ops.p, a.nops = fin.d_nops.p;
+    a.ibase = (j.max_hits > 0 && ns > 0) ? ai.d_ibase.p : nullptr, a.n_hits = ai.d_nh.p;
+    a.names = j.d_names, a.name_off = j.d_name_off, a.line_cnt = d_lcnt.p, a.line_base = d_lbase.p, a.size = d_size.p, a.off = d_off.p;
+    a.n_mapped = d_nmapped.p;
+    hipLaunchKernelGGL(sam_line_count_kernel, dim3(grid_for(rn + 1)), dim3(ASM_BLOCK), 0, h->stream, a);
+    MAP_FILE_TRY(hipGetLastError());
+    MAP_FILE_TRY(map_exclusive_sum(h, tmp, d_lcnt.p, d_lbase.p, (int64_t)cnt));
+    hipLaunchKernelGGL(sam_line_fill_kernel, dim3(grid_for(rn)), dim3(ASM_BLOCK), 0, h->stream, a, d_lrec.p, d_litem.p);
+    hipLaunchKernelGGL(sam_size_kernel, dim3(grid_for(nlines + 1)), dim3(ASM_BLOCK), 0, h->stream, a);
+    MAP_FILE_TRY(hipGetLastError());
+    MAP_FILE_TRY(map_exclusive_sum(h, tmp, d_size.p, d_off.p, nlines + 1));
+    unsigned long long total = 0, n_mapped = 0;
+    MAP_FILE_TRY(hipMemcpyAsync(&total, d_off.p + nlines, sizeof(total), hipMemcpyDeviceToHost, h->stream));
+    MAP_FILE_TRY(hipMemcpyAsync(&n_mapped, d_nmapped.p, sizeof(n_mapped), hipMemcpyDeviceToHost, h->stream));
+    MAP_FILE_TRY(hipStreamSynchronize(h->stream));
+    /* the output slot: the writer is done with the chunk that used it three chunks ago, so its copy out of d_out is over too */
+    MapFilePipe& pp = *j.pipe;
+    const int o = (int)(j.out_seq % 3);
+    j.writer->wait_idle(o);
+    if (j.writer->failed()) return fail(h, ASM_EINVAL, "asm_map_file: writing the SAM file failed");
+    pool_free(h, pp.d_out[o]);
+    pp.d_out[o] = nullptr;
+    if (pp.pin_out_cap[o] < total) {
+        if (pp.pin_out[o]) (void)hipHostFree(pp.pin_out[o]);
+        pp.pin_out[o] = nullptr, pp.pin_out_cap[o] = 0;
+        const size_t want = (size_t)total + (size_t)total / 4 + 4096;
+        MAP_FILE_TRY(hipHostMalloc((void**)&pp.pin_out[o], want, hipHostMallocDefault));
+        pp.pin_out_cap[o] = want;
+    }
+    MAP_FILE_TRY(pool_alloc(h, (void**)&pp.d_out[o], (size_t)total + 64));
+    a.out = pp.d_out[o];
+    hipLaunchKernelGGL(sam_emit_kernel, dim3(map_grid((uint64_t)nlines * 64, h)), dim3(256), 0, h->stream, a);
+    MAP_FILE_TRY(hipGetLastError());
+    MAP_FILE_TRY(hipEventRecord(pp.ev_fmt[o], h->stream));
+    MAP_FILE_TRY(hipStreamWaitEvent(pp.s_out, pp.ev_fmt[o], 0));
+    if (total) MAP_FILE_TRY(hipMemcpyAsync(pp.pin_out[o], pp.d_out[o], (size_t)total, hipMemcpyDeviceToHost, pp.s_out));
+    MAP_FILE_TRY(hipEventRecord(pp.ev_copied[o], pp.s_out));
+    j.writer->push(o, pp.pin_out[o], (size_t)total);
+    j.out_seq++;
+    j.st.reads += rn, j.st.mapped += (int64_t)n_mapped, j.st.too_long += counts.too_long, j.st.records += nlines;
+    j.st.chunks++, j.st.bytes_out += (int64_t)total;
+    return ASM_OK;
+}
+
+/* One file chunk (nrec whole records in d_raw[0, nbytes)): the newline index, then its device chunks of at most map_chunk records */
+static int map_file_process(MapFileJob& j, const char* d_raw, size_t nbytes, int64_t nrec, int64_t first_record) {
+    asm_handle* h = j.h;
+    const long ntiles = (long)((nbytes + SEQ_TILE - 1) / SEQ_TILE), nl_lines = (long)(4 * nrec);
+    Scratch<uint32_t> d_tile(h), d_tbase(h), d_nl(h);
+    MapTmp tmp(h);
+    MAP_FILE_TRY(d_tile.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1)));
+    MAP_FILE_TRY(d_tbase.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1)));
+    MAP_FILE_TRY(d_nl.alloc(sizeof(uint32_t) * ((size_t)nl_lines + 2)));
+    hipLaunchKernelGGL(seq_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, h->stream, d_raw, (long)nbytes, d_tile.p);
+    MAP_FILE_TRY(hipGetLastError());
+    MAP_FILE_TRY(map_exclusive_sum(h, tmp, d_tile.p, d_tbase.p, (int64_t)ntiles));
+    hipLaunchKernelGGL(seq_index_kernel, dim3((unsigned)ntiles), dim3(256), 0, h->stream, d_raw, (long)nbytes, (const uint32_t*)d_tbase.p,
+                       d_nl.p, nl_lines);
+    MAP_FILE_TRY(hipGetLastError());
+    /* the run key of asm_map_reads_all holds the read in its top 31 bits */
+    return map_chunks(nrec, std::min<int64_t>(h->map_chunk, (int64_t)1 << 30), [&](int64_t r0, int64_t rn) {
+        return map_file_chunk(j, d_raw, d_nl.p, r0, rn, first_record + r0);
+    });
+}
+
+static int map_file_run(asm_handle* h, const asm_index* ix, const char* const* seq_names, const char* fastq_path, const char* sam_path,
+                        const char* header, const asm_map_params* p, int max_hits, int strata, size_t chunk, asm_map_file_stats* stats) {
+    const auto t_begin = std::chrono::steady_clock::now();
+    MapFilePipe pipe(h);
+    pipe.fd = open(fastq_path, O_RDONLY);
+    if (pipe.fd < 0) return fail(h, ASM_EINVAL, std::string("asm_map_file: cannot open ") + fastq_path);
+    struct stat st;
+    if (fstat(pipe.fd, &st) != 0) return fail(h, ASM_EINVAL, "asm_map_file: fstat failed");
+    const size_t file_bytes = (size_t)st.st_size;
+    char first = 0;
+    if (file_bytes && pread(pipe.fd, &first, 1, 0) != 1) return fail(h, ASM_EINVAL, std::string("asm_map_file: cannot read ") + fastq_path);
+    if (first == '>') return fail(h, ASM_EUNSUPPORTED, "asm_map_file: FASTA reads are not supported (the file starts with '>')");
+    pipe.out = fopen(sam_path, "wb");
+    if (!pipe.out) return fail(h, ASM_EINVAL, std::string("asm_map_file: cannot write ") + sam_path);
+    if (header && *header && fwrite(header, 1, strlen(header), pipe.out) != strlen(header))
+        return fail(h, ASM_EINVAL, "asm_map_file: writing the SAM file failed");
+    /* the RNAME table */
+    std::string names;
+    std::vector<uint32_t> name_off(1, 0u);
+    for (int32_t r = 0; r < ix->n_seqs; r++) {
+        if (!seq_names[r]) return fail(h, ASM_EINVAL, "asm_map_file: seq_names[" + std::to_string(r) + "] is NULL");
+        names += seq_names[r];
+        name_off.push_back((uint32_t)names.size());
+    }
+    Scratch<char> d_names(h);
+    Scratch<uint32_t> d_name_off(h);
+    MAP_FILE_TRY(d_names.alloc(names.size() + 16));
+    MAP_FILE_TRY(d_name_off.alloc(sizeof(uint32_t) * name_off.size()));
+    MAP_FILE_TRY(hipMemcpyAsync(d_names.p, names.data(), names.size(), hipMemcpyHostToDevice, h->stream));
+    MAP_FILE_TRY(hipMemcpyAsync(d_name_off.p, name_off.data(), sizeof(uint32_t) * name_off.size(), hipMemcpyHostToDevice, h->stream));
+    MAP_FILE_TRY(hipStreamSynchronize(h->stream));
+    MAP_FILE_TRY(pipe.open_device());
+    /* chunks ramp up from an eighth, so that the device starts after an eighth of a chunk has been read */
+    const size_t slot_cap = chunk + chunk / 4 + 4096, first_chunk = chunk >= ((size_t)8 << 20) ? chunk / 8 : chunk;
+    for (char*& q : pipe.pin_in) MAP_FILE_TRY(hipHostMalloc((void**)&q, slot_cap + 64, hipHostMallocDefault));
+    asm_host::FastqReader rd(
+        pipe.fd, file_bytes, chunk, first_chunk,
+        [&](int q) {
+            (void)hipSetDevice(h->device);
+            (void)hipEventSynchronize(pipe.ev_shipped[q]);
+        },
+        [&](int q, size_t cap, size_t keep) { /* a record longer than the buffer: a larger pinned one (no copy reads the old one now) */
+            (void)hipSetDevice(h->device);
+            char* bigger = nullptr;
+            if (hipHostMalloc((void**)&bigger, cap + 64, hipHostMallocDefault) != hipSuccess) return false;
+            if (keep) memcpy(bigger, pipe.pin_in[q], keep);
+            (void)hipHostFree(pipe.pin_in[q]);
+            pipe.pin_in[q] = bigger;
+            rd.slot[q].buf = bigger, rd.slot[q].cap = cap;
+            return true;
+        });
+    for (int q = 0; q < 3; q++) rd.slot[q].buf = pipe.pin_in[q], rd.slot[q].cap = slot_cap;
+    asm_host::ChunkWriter writer(pipe.out, [&](int o) {
+        (void)hipSetDevice(h->device);
+        return hipEventSynchronize(pipe.ev_copied[o]) == hipSuccess;
+    });
+    MapFileJob j = {h, ix, p, max_hits, strata, d_names.p, d_name_off.p, &pipe, &writer};
+    rd.start();
+
+    /* this thread: SHIP chunk c (pinned buffer -> HBM on the copy-in stream), then PROCESS chunk c - 1 while c is on its way */
+    struct Pending {
+        bool valid = false;
+        size_t bytes = 0;
+        int64_t records = 0, first_record = 0;
+    } pend[2];
+    int64_t records_seen = 0;
+    auto process = [&](int q) -> int {
+        if (!pend[q].valid) return ASM_OK;
+        pend[q].valid = false;
+        if (pend[q].records <= 0) return ASM_OK;
+        MAP_FILE_TRY(hipStreamWaitEvent(h->stream, pipe.ev_h2d[q], 0));
+        return map_file_process(j, pipe.d_raw[q], pend[q].bytes, pend[q].records, pend[q].first_record);
+    };
+    bool last = false;
+    for (int c = 0; !last; c++) {
+        asm_host::FastqSlot* sp = rd.wait_ready(c);
+        if (!sp) return fail(h, ASM_EINVAL, std::string("asm_map_file: reading ") + fastq_path + " failed");
+        asm_host::FastqSlot& s = *sp;
+        const int q = c & 1;
+        last = s.last;
+        if (s.extra_lines)
+            return fail(h, ASM_EINVAL, "asm_map_file: record " + std::to_string(records_seen + s.records + 1) +
+                                           " is truncated (the file's line count is not a multiple of 4)");
+        if (s.bytes >= 0xfffffff0ull) return fail(h, ASM_EUNSUPPORTED, "asm_map_file: a chunk of 4 GiB or more; lower chunk_bytes");
+        bool shipping = false;
+        if (s.records > 0) {
+            if (pipe.d_raw_cap[q] < s.bytes + 64) {
+                pool_free(h, pipe.d_raw[q]);
+                pipe.d_raw[q] = nullptr, pipe.d_raw_cap[q] = 0;
+                const size_t want = std::max(s.bytes + s.bytes / 4, slot_cap) + 64;
+                MAP_FILE_TRY(pool_alloc(h, (void**)&pipe.d_raw[q], want));
+                pipe.d_raw_cap[q] = want;
+            }
+            /* d_raw[q] held chunk c - 2, whose kernels are all enqueued on the handle's stream (and a block fresh from the pool may
+             * still be read by work queued there): the copy waits for them */
+            MAP_FILE_TRY(hipEventRecord(pipe.ev_gate, h->stream));
+            MAP_FILE_TRY(hipStreamWaitEvent(pipe.s_in, pipe.ev_gate, 0));
+            MAP_FILE_TRY(hipMemcpyAsync(pipe.d_raw[q], s.buf, s.bytes, hipMemcpyHostToDevice, pipe.s_in));
+            MAP_FILE_TRY(hipEventRecord(pipe.ev_shipped[c % 3], pipe.s_in));
+            MAP_FILE_TRY(hipEventRecord(pipe.ev_h2d[q], pipe.s_in));
+            shipping = true;
+        }
+        pend[q].valid = true, pend[q].bytes = s.bytes, pend[q].records = s.records, pend[q].first_record = records_seen;
+        records_seen += s.records;
+        j.st.bytes_in += (int64_t)s.bytes;
+        rd.consumed(c, shipping);
+        if (const int rc = process(q ^ 1)) return rc;
+    }
+    for (int q = 0; q < 2; q++)
+        if (const int rc = process(q)) return rc;
+    rd.stop();
+    if (!writer.finish() || fflush(pipe.out) != 0) return fail(h, ASM_EINVAL, "asm_map_file: writing the SAM file failed");
+    j.st.seconds_read = rd.read_seconds(), j.st.seconds_write = writer.write_seconds();
+    j.st.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+    if (stats) *stats = j.st;
+    return ASM_OK;
+}
+
+} /* extern "C++" */
+
+int asm_map_file(asm_handle* h, const asm_index* ix, const char* const* seq_names, const char* fastq_path, const char* sam_path,
+                 const char* header, const asm_map_params* p, int max_hits, int strata, int64_t chunk_bytes, asm_map_file_stats* stats) {
+    if (!p || !ix || !seq_names || !fastq_path || !sam_path) return fail(h, ASM_EINVAL, "asm_map_file: bad arguments");
+    if (max_hits < 0 || max_hits > ASM_MAP_MAX_HITS) return fail(h, ASM_EINVAL, "asm_map_file: max_hits must be in [0, 256]");
+    if (chunk_bytes < 0) return fail(h, ASM_EINVAL, "asm_map_file: chunk_bytes must be >= 0");
+    if (const int rc = map_check_args(h, ix, "asm_map_file", "read",
+                                      {0, p, {nullptr, nullptr}, nullptr, max_hits ? "max_hits" : nullptr, strata, ASM_MAP_MAX_ERRORS,
+                                       max_hits, {nullptr, 0, nullptr}}))
+        return rc;
+    if (stats) memset(stats, 0, sizeof *stats);
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t chunk = chunk_bytes == 0 ? (size_t)16 << 20 : (size_t)std::min<int64_t>(chunk_bytes, (int64_t)1 << 30);
+    return map_file_run(h, ix, seq_names, fastq_path, sam_path, header, p, max_hits, strata, chunk, stats);
+}
+
+size_t asm_fastq_cut(const char* buf, size_t nbytes, int64_t* records) {
+    if (!buf) nbytes = 0;
+    return asm_host::fastq_cut(buf, nbytes, records);
+}

@@ -170,7 +170,7 @@ static int map_greedy(asm_handle* h, const asm_index* ix, const char* d_reads, c
     return asm_align_batch_async(h, b.get(), ASM_GREEDY, &gp, d_cost);
 }
 
-/* The front of a chunk, shared by all mapping calls: reads uploaded and upper-cased, per-read flags cleared, every work item's
+/* The front of a chunk, shared by all mapping calls: reads in HBM (uploaded, or gathered there by asm_map_file) and upper-cased, per-read flags cleared, every work item's
  * candidates counted (map_seed_count_kernel) and numbered (exclusive scan); total = all candidates of the chunk. */
 struct MapFront {
     std::vector<uint32_t> roff;
@@ -193,28 +193,16 @@ struct MapReadsIn {
     int64_t n;
 };
 
-static int map_front(asm_handle* h, const asm_index* ix, const MapReadsIn* in, int n_in, const asm_map_params* p, MapFront& f) {
+/* The front once the reads are in HBM: f.d_reads (f.bytes bytes, any case), f.d_roff and its host copy f.roff are filled */
+static int map_front_seed(asm_handle* h, const asm_index* ix, int64_t n, const asm_map_params* p, MapFront& f) {
     const int S = p->both_strands ? 2 : 1, P = p->max_errors + 1;
-    int64_t n = 0;
-    for (int t = 0; t < n_in; t++) n += in[t].n;
-    f.roff.assign(1, 0u);
-    f.roff.reserve((size_t)n + 1);
-    for (int t = 0; t < n_in; t++) {
-        const uint32_t o = f.roff.back(), *ro = in[t].read_off;
-        for (int64_t i = 1; i <= in[t].n; i++) f.roff.push_back(o + (ro[i] - ro[0]));
-    }
+    f.maxm = 0;
     for (int64_t i = 0; i < n; i++) f.maxm = std::max(f.maxm, f.len((size_t)i));
-    const size_t bytes = f.bytes = f.roff[(size_t)n];
+    const size_t bytes = f.bytes;
     const int64_t nw = f.nw = n * S * P;
-    HIPCHK(h, f.d_reads.alloc(bytes + 16));
-    HIPCHK(h, f.d_roff.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
     HIPCHK(h, f.d_flags.alloc(sizeof(uint32_t) * (size_t)n));
     HIPCHK(h, f.d_cnt.alloc(sizeof(unsigned long long) * (size_t)nw));
     HIPCHK(h, f.d_base.alloc(sizeof(unsigned long long) * (size_t)nw));
-    for (int64_t t = 0, o = 0; t < n_in; o += in[t].read_off[in[t].n] - in[t].read_off[0], t++)
-        HIPCHK(h, hipMemcpyAsync(f.d_reads.p + o, in[t].reads + in[t].read_off[0], in[t].read_off[in[t].n] - in[t].read_off[0],
-                                 hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(f.d_roff.p, f.roff.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(f.d_flags.p, 0, sizeof(uint32_t) * (size_t)n, h->stream));
     hipLaunchKernelGGL(map_upper_kernel, dim3(map_grid(bytes, h)), dim3(256), 0, h->stream, f.d_reads.p, (unsigned long long)bytes);
     HIPCHK(h, hipGetLastError());
@@ -232,6 +220,26 @@ static int map_front(asm_handle* h, const asm_index* ix, const MapReadsIn* in, i
     HIPCHK(h, hipStreamSynchronize(h->stream));
     f.total = last[0] + last[1];
     return ASM_OK;
+}
+
+/* The front from host arrays: the runs of reads numbered and uploaded, then map_front_seed */
+static int map_front(asm_handle* h, const asm_index* ix, const MapReadsIn* in, int n_in, const asm_map_params* p, MapFront& f) {
+    int64_t n = 0;
+    for (int t = 0; t < n_in; t++) n += in[t].n;
+    f.roff.assign(1, 0u);
+    f.roff.reserve((size_t)n + 1);
+    for (int t = 0; t < n_in; t++) {
+        const uint32_t o = f.roff.back(), *ro = in[t].read_off;
+        for (int64_t i = 1; i <= in[t].n; i++) f.roff.push_back(o + (ro[i] - ro[0]));
+    }
+    const size_t bytes = f.bytes = f.roff[(size_t)n];
+    HIPCHK(h, f.d_reads.alloc(bytes + 16));
+    HIPCHK(h, f.d_roff.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
+    for (int64_t t = 0, o = 0; t < n_in; o += in[t].read_off[in[t].n] - in[t].read_off[0], t++)
+        HIPCHK(h, hipMemcpyAsync(f.d_reads.p + o, in[t].reads + in[t].read_off[0], in[t].read_off[in[t].n] - in[t].read_off[0],
+                                 hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(f.d_roff.p, f.roff.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
+    return map_front_seed(h, ix, n, p, f);
 }
 
 /* The seeding rounds of a chunk, of at most map_cand_cap candidates each: every round sees every work item, emits the part of it
@@ -356,6 +364,37 @@ static int map_finish_collect(asm_handle* h, const asm_index* ix, const asm_map_
     return ASM_OK;
 }
 
+/* The collect half for a caller that formats on the device (asm_map_file): the records, ops and nops stay in s; the mapped items
+ * are listed on the device, Greedy runs on them and a small kernel puts its costs into the device records.  Every read of the chunk
+ * bounds the mapped ones' length. */
+static int map_finish_device(asm_handle* h, const asm_index* ix, const asm_map_params* p, const MapFront& f, MapFinish& s) {
+    const size_t n = (size_t)s.n;
+    Scratch<uint32_t> d_flag(h), d_slot(h), d_list(h);
+    Scratch<int32_t> d_cost(h);
+    MapTmp tmp(h);
+    HIPCHK(h, d_flag.alloc(sizeof(uint32_t) * (n + 1)));
+    HIPCHK(h, d_slot.alloc(sizeof(uint32_t) * (n + 1)));
+    hipLaunchKernelGGL(map_mapped_flag_kernel, dim3(grid_for((int64_t)n + 1)), dim3(ASM_BLOCK), 0, h->stream, (const MapHit*)s.d_hits.p,
+                       (long)n, d_flag.p);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, map_exclusive_sum(h, tmp, d_flag.p, d_slot.p, (int64_t)n + 1));
+    uint32_t nl = 0;
+    HIPCHK(h, hipMemcpyAsync(&nl, d_slot.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!nl) return ASM_OK;
+    HIPCHK(h, d_list.alloc(sizeof(uint32_t) * nl));
+    HIPCHK(h, d_cost.alloc(sizeof(int32_t) * nl));
+    hipLaunchKernelGGL(map_mapped_list_kernel, dim3(grid_for((int64_t)n)), dim3(ASM_BLOCK), 0, h->stream, (const uint32_t*)d_flag.p,
+                       (const uint32_t*)d_slot.p, (long)n, d_list.p);
+    HIPCHK(h, hipGetLastError());
+    if (const int rc = map_greedy(h, ix, f.d_reads.p, f.d_roff.p, s.d_hits.p, s.d_iread, d_list.p, (int64_t)nl, f.maxm, p->greedy_k, d_cost.p))
+        return rc;
+    hipLaunchKernelGGL(map_cost_kernel, dim3(grid_for((int64_t)nl)), dim3(ASM_BLOCK), 0, h->stream, (const uint32_t*)d_list.p,
+                       (const int32_t*)d_cost.p, (long)nl, s.d_hits.p);
+    HIPCHK(h, hipGetLastError());
+    return ASM_OK;
+}
+
 /* the host copy of finished items, for the calls that scatter them into the caller's slots */
 struct MapItems {
     std::vector<asm_map_hit> hits;
@@ -372,20 +411,25 @@ struct MapItems {
 
 static const asm_map_hit MAP_UNUSED_SLOT = {-1, 0, 0, -1, 0, 0, -1};
 
+/* asm_map_reads' keys of a fronted chunk: the seeding rounds with map_verify_kernel<W>, every read's best end in d_keys */
+static int map_best_keys(asm_handle* h, const asm_index* ix, int64_t n, const asm_map_params* p, const MapFront& f,
+                         Scratch<unsigned long long>& d_keys) {
+    HIPCHK(h, d_keys.alloc(sizeof(unsigned long long) * (size_t)n));
+    HIPCHK(h, hipMemsetAsync(d_keys.p, 0xff, sizeof(unsigned long long) * (size_t)n, h->stream));
+    return map_seed_rounds(h, f, [&](const MapCand* cand, unsigned long long nc) -> int {
+        HIPCHK(h, map_launch_verify(h, ix, f, p->max_errors, cand, nc, d_keys.p));
+        return ASM_OK;
+    });
+}
+
 /* asm_map_reads on one chunk: everything on the device, results straight into the caller's host arrays */
 static int map_chunk(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
                      const asm_map_params* p, asm_map_hit* out, MapCigars cg) {
     MapFront f(h);
     Scratch<unsigned long long> d_keys(h);
-    HIPCHK(h, d_keys.alloc(sizeof(unsigned long long) * (size_t)n));
-    HIPCHK(h, hipMemsetAsync(d_keys.p, 0xff, sizeof(unsigned long long) * (size_t)n, h->stream));
     const MapReadsIn in = {reads, read_off, n};
     if (const int rc = map_front(h, ix, &in, 1, p, f)) return rc;
-    const int rc = map_seed_rounds(h, f, [&](const MapCand* cand, unsigned long long nc) -> int {
-        HIPCHK(h, map_launch_verify(h, ix, f, p->max_errors, cand, nc, d_keys.p));
-        return ASM_OK;
-    });
-    if (rc) return rc;
+    if (const int rc = map_best_keys(h, ix, n, p, f, d_keys)) return rc;
     MapFinish fin(h);
     if (const int rc2 = map_finish_launch(h, ix, p, f, n, d_keys.p, nullptr, nullptr, f.bytes + (size_t)n, cg.cap, fin)) return rc2;
     return map_finish_collect(h, ix, p, f, fin, out, cg.ops, cg.nops);
@@ -466,28 +510,35 @@ static MapSelectArgs map_select_args(const asm_index* ix, const MapFront& f, con
     return sel;
 }
 
-/* asm_map_reads_all on one chunk: the sorted run records, the loci selected per read into an item list, the finish stage on the
- * items, then the scatter into the caller's [n][max_hits] slots */
-static int map_chunk_all(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
-                         const asm_map_params* p, int strata, int max_hits, uint32_t* n_hits, asm_map_hit* out, MapCigars cg) {
-    MapFront f(h);
-    const MapReadsIn in = {reads, read_off, n};
-    if (const int rc = map_front(h, ix, &in, 1, p, f)) return rc;
-    MapRuns runs(h);
-    if (const int rc = map_runs(h, ix, n, p, f, runs, "asm_map_reads_all")) return rc;
+/* asm_map_reads_all's items of a fronted chunk: the sorted run records, the loci selected per read (n_hits: host, n entries) and
+ * listed as items in read-then-rank order, max(1, min(n_hits, max_hits)) per read */
+struct MapAllItems {
+    MapRuns runs;
+    Scratch<uint32_t> d_nh, d_dbest, d_ibase, d_iread;
+    Scratch<unsigned long long> d_dbase, d_ikey, d_idirs;
+    std::vector<uint32_t> ibase;           /* n + 1 */
+    std::vector<unsigned long long> dbase; /* the upload's source: lives as long as the items */
+    unsigned long long dwords = 0;
+    int64_t ni = 0;
+    explicit MapAllItems(asm_handle* h) : runs(h), d_nh(h), d_dbest(h), d_ibase(h), d_iread(h), d_dbase(h), d_ikey(h), d_idirs(h) {}
+};
+
+static int map_all_items(asm_handle* h, const asm_index* ix, int64_t n, const asm_map_params* p, int strata, int max_hits, MapFront& f,
+                         uint32_t* n_hits, MapAllItems& it, const char* who) {
+    if (const int rc = map_runs(h, ix, n, p, f, it.runs, who)) return rc;
     /* loci per read: count, then (host) the item layout, then emit */
-    Scratch<uint32_t> d_nh(h), d_dbest(h), d_ibase(h), d_iread(h);
-    Scratch<unsigned long long> d_dbase(h), d_ikey(h), d_idirs(h);
-    HIPCHK(h, d_nh.alloc(sizeof(uint32_t) * (size_t)n));
-    HIPCHK(h, d_dbest.alloc(sizeof(uint32_t) * (size_t)n));
-    MapSelectArgs sel = map_select_args(ix, f, runs, n, p->max_errors, strata, max_hits, d_nh.p, d_dbest.p);
+    HIPCHK(h, it.d_nh.alloc(sizeof(uint32_t) * (size_t)n));
+    HIPCHK(h, it.d_dbest.alloc(sizeof(uint32_t) * (size_t)n));
+    MapSelectArgs sel = map_select_args(ix, f, it.runs, n, p->max_errors, strata, max_hits, it.d_nh.p, it.d_dbest.p);
     hipLaunchKernelGGL(map_select_count_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(n_hits, d_nh.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(n_hits, it.d_nh.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     /* items: max(1, min(n_hits, max_hits)) per read, in read-then-rank order; dirs: (m + 1) words per item */
-    std::vector<uint32_t> ibase((size_t)n + 1);
-    std::vector<unsigned long long> dbase((size_t)n);
+    std::vector<uint32_t>& ibase = it.ibase;
+    ibase.assign((size_t)n + 1, 0u);
+    std::vector<unsigned long long>& dbase = it.dbase;
+    dbase.assign((size_t)n, 0ull);
     unsigned long long dwords = 0;
     for (int64_t i = 0; i < n; i++) {
         const uint32_t ni = n_hits[i] ? std::min<uint32_t>(n_hits[i], (uint32_t)max_hits) : 1u;
@@ -495,19 +546,34 @@ static int map_chunk_all(asm_handle* h, const asm_index* ix, int64_t n, const ch
         dbase[(size_t)i] = dwords;
         dwords += (unsigned long long)ni * (f.len((size_t)i) + 1u);
     }
-    const int64_t ni = ibase[(size_t)n];
-    HIPCHK(h, d_ibase.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
-    HIPCHK(h, d_dbase.alloc(sizeof(unsigned long long) * (size_t)n));
-    HIPCHK(h, d_iread.alloc(sizeof(uint32_t) * (size_t)ni));
-    HIPCHK(h, d_ikey.alloc(sizeof(unsigned long long) * (size_t)ni));
-    HIPCHK(h, d_idirs.alloc(sizeof(unsigned long long) * (size_t)ni));
-    HIPCHK(h, hipMemcpyAsync(d_ibase.p, ibase.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d_dbase.p, dbase.data(), sizeof(unsigned long long) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    sel.ibase = d_ibase.p, sel.dbase = d_dbase.p, sel.iread = d_iread.p, sel.ikey = d_ikey.p, sel.idirs = d_idirs.p;
+    const int64_t ni = it.ni = ibase[(size_t)n];
+    it.dwords = dwords;
+    HIPCHK(h, it.d_ibase.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
+    HIPCHK(h, it.d_dbase.alloc(sizeof(unsigned long long) * (size_t)n));
+    HIPCHK(h, it.d_iread.alloc(sizeof(uint32_t) * (size_t)ni));
+    HIPCHK(h, it.d_ikey.alloc(sizeof(unsigned long long) * (size_t)ni));
+    HIPCHK(h, it.d_idirs.alloc(sizeof(unsigned long long) * (size_t)ni));
+    HIPCHK(h, hipMemcpyAsync(it.d_ibase.p, ibase.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(it.d_dbase.p, dbase.data(), sizeof(unsigned long long) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    sel.ibase = it.d_ibase.p, sel.dbase = it.d_dbase.p, sel.iread = it.d_iread.p, sel.ikey = it.d_ikey.p, sel.idirs = it.d_idirs.p;
     hipLaunchKernelGGL(map_select_emit_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel);
     HIPCHK(h, hipGetLastError());
+    return ASM_OK;
+}
+
+/* asm_map_reads_all on one chunk: the front, the items, the finish stage on them, then the scatter into the caller's
+ * [n][max_hits] slots */
+static int map_chunk_all(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
+                         const asm_map_params* p, int strata, int max_hits, uint32_t* n_hits, asm_map_hit* out, MapCigars cg) {
+    MapFront f(h);
+    const MapReadsIn in = {reads, read_off, n};
+    if (const int rc = map_front(h, ix, &in, 1, p, f)) return rc;
+    MapAllItems ai(h);
+    if (const int rc = map_all_items(h, ix, n, p, strata, max_hits, f, n_hits, ai, "asm_map_reads_all")) return rc;
+    const std::vector<uint32_t>& ibase = ai.ibase;
+    const int64_t ni = ai.ni;
     MapFinish fin(h);
-    if (const int rc = map_finish_launch(h, ix, p, f, ni, d_ikey.p, d_iread.p, d_idirs.p, dwords, cg.cap, fin)) return rc;
+    if (const int rc = map_finish_launch(h, ix, p, f, ni, ai.d_ikey.p, ai.d_iread.p, ai.d_idirs.p, ai.dwords, cg.cap, fin)) return rc;
     MapItems it(ni, fin.ocap);
     if (const int rc = map_finish_collect(h, ix, p, f, fin, it.hits.data(), it.ops.data(), it.nops.data())) return rc;
     /* into the caller's [n][max_hits] slots (a read's items are contiguous); the flags that depend on the rank are set here.  The

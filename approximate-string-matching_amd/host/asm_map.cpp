@@ -5,6 +5,10 @@
 //           [--all-hits N [--strata S]]
 //   asm-map -r ref.fa -1 r1.fq -2 r2.fq [-o out.sam] -e N --insert MIN,MAX [--rescue E] [--k 12] [--max-occ N] [--chunk N]
 //           [--all-hits N [--strata S]]
+//   asm-map -r ref.fa -q reads.fq --stream [--chunk-bytes N] [-o out.sam] [-e N] [--k 12] [--both-strands] [--max-occ N]
+//           [--all-hits N [--strata S]]
+// --stream hands the FASTQ file and the SAM path to asm_map_file, which parses, maps and formats on the device while it reads and
+// writes (four-line FASTQ only; the same lines as without it); --chunk-bytes N: file bytes per chunk (default: the library's).
 // --all-hits N writes up to N loci per read in rank order (asm_map_reads_all, strata S, default e): the primary record as without
 // it, then the secondary ones (FLAG 256, SEQ and QUAL '*'), each with NH:i:<reported> HI:i:<rank + 1> XH:i:<all loci> after NM
 // and XG.  Reads may be FASTQ or FASTA (QUAL '*').  Reads are processed in chunks of --chunk records, so the read file's size is not
@@ -34,7 +38,9 @@ static void usage() {
     fprintf(stderr, "usage: asm-map -r ref.fa -q reads.fq [-o out.sam] [-e N] [--k 12] [--both-strands] [--max-occ N] [--chunk N] "
                     "[--all-hits N [--strata S]]\n"
                     "       asm-map -r ref.fa -1 r1.fq -2 r2.fq [-o out.sam] -e N --insert MIN,MAX [--rescue E] [--k 12] [--max-occ N] "
-                    "[--chunk N] [--all-hits N [--strata S]]\n");
+                    "[--chunk N] [--all-hits N [--strata S]]\n"
+                    "       asm-map -r ref.fa -q reads.fq --stream [--chunk-bytes N] [-o out.sam] [-e N] [--k 12] [--both-strands] "
+                    "[--max-occ N] [--all-hits N [--strata S]]\n");
     exit(2);
 }
 
@@ -255,6 +261,8 @@ int main(int argc, char** argv) {
     int k = 12;
     long chunk = 262144;
     int all_hits = 0, strata = -1; /* all_hits 0: the best hit only */
+    bool stream = false;
+    long long chunk_bytes = 0;
     std::string cl = "asm-map";
     for (int a = 1; a < argc; a++) cl += std::string(" ") + argv[a];
     for (int a = 1; a < argc; a++) {
@@ -277,10 +285,13 @@ int main(int argc, char** argv) {
         else if (s == "--chunk") chunk = atol(val());
         else if (s == "--all-hits") all_hits = atoi(val());
         else if (s == "--strata") strata = atoi(val());
+        else if (s == "--stream") stream = true;
+        else if (s == "--chunk-bytes") chunk_bytes = atoll(val());
         else usage();
     }
     if (ref_path.empty() || read_path.empty() || chunk < 1 || all_hits < 0 || (strata >= 0 && !all_hits)) usage();
     const bool paired = !read2_path.empty();
+    if (chunk_bytes < 0 || (chunk_bytes > 0 && !stream) || (stream && paired)) usage(); /* paired streaming: not there */
     if (paired && (pp.min_insert < 0 || pp.max_insert < 0)) usage(); /* paired: --insert needed */
     if (!paired && (pp.min_insert >= 0 || pp.rescue_errors >= 0)) usage();
     if (paired) p.both_strands = 1;
@@ -326,8 +337,12 @@ int main(int argc, char** argv) {
         reads.fasta = c == '>';
         if (c != EOF) ungetc(c, rf);
     }
-    FILE* out = fopen(out_path.c_str(), "w");
-    if (!out) {
+    if (stream && reads.fasta) {
+        fprintf(stderr, "asm-map: --stream needs FASTQ reads\n");
+        return 1;
+    }
+    FILE* out = stream ? nullptr : fopen(out_path.c_str(), "w");
+    if (!out && !stream) {
         fprintf(stderr, "asm-map: cannot write %s\n", out_path.c_str());
         return 1;
     }
@@ -339,10 +354,27 @@ int main(int argc, char** argv) {
         fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
         return 1;
     }
-    fprintf(out, "@HD\tVN:1.6\tSO:unsorted\n");
+    std::string header = "@HD\tVN:1.6\tSO:unsorted\n";
     for (size_t r = 0; r < names.size(); r++)
-        fprintf(out, "@SQ\tSN:%s\tLN:%llu\n", names[r].c_str(), (unsigned long long)(off[r + 1] - off[r]));
-    fprintf(out, "@PG\tID:asm-map\tPN:asm-map\tVN:%s\tCL:%s\n", asm_version(), cl.c_str());
+        header += "@SQ\tSN:" + names[r] + "\tLN:" + std::to_string((unsigned long long)(off[r + 1] - off[r])) + "\n";
+    header += std::string("@PG\tID:asm-map\tPN:asm-map\tVN:") + asm_version() + "\tCL:" + cl + "\n";
+    if (stream) { /* the library reads, maps, formats and writes */
+        fclose(rf);
+        std::vector<const char*> name_ptr;
+        for (const std::string& nm : names) name_ptr.push_back(nm.c_str());
+        asm_map_file_stats st;
+        rc = asm_map_file(h, ix, name_ptr.data(), read_path.c_str(), out_path.c_str(), header.c_str(), &p, all_hits, strata, chunk_bytes, &st);
+        if (rc) fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
+        asm_index_free(h, ix);
+        asm_destroy(h);
+        if (rc) return 1;
+        fprintf(stderr, "asm-map: %lld reads, %lld mapped, %lld longer than %d (unmapped)\n", (long long)st.reads, (long long)st.mapped,
+                (long long)st.too_long, ASM_MAP_MAX_READ);
+        fprintf(stderr, "asm-map: streamed %lld chunks, %lld bytes in, %lld bytes out, %.3f s (reader busy %.3f s, writer busy %.3f s)\n",
+                (long long)st.chunks, (long long)st.bytes_in, (long long)st.bytes_out, st.seconds, st.seconds_read, st.seconds_write);
+        return 0;
+    }
+    fputs(header.c_str(), out);
     if (paired) {
         FILE* rf2 = fopen(read2_path.c_str(), "r");
         if (!rf2) {

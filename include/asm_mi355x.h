@@ -442,6 +442,31 @@ int asm_map_pairs_all(asm_handle* h, const asm_index* ix, int64_t n, const char*
                       uint32_t* n_concordant /* [n] */, uint16_t* cigar_ops /* [n][max_pairs][2][cigar_cap] */, int cigar_cap,
                       uint8_t* cigar_nops /* [n][max_pairs][2] */);
 
+/* asm_map_file:    a FASTQ file in, a SAM file out (docs/design/mapper.md, "Files: FASTQ in, SAM out"); single-end, synchronous.  The
+ *                  file is read in chunks of about chunk_bytes (0: 16 MiB) cut at record boundaries; a chunk is parsed, mapped
+ *                  and formatted on the device while the next one is read and copied in and the one before is copied out and
+ *                  written.  Four-line FASTQ: record i is lines 4i .. 4i+3 by line number alone, lines end in LF or CRLF, the last
+ *                  newline may be missing; line 0 starts with '@' and QNAME is its first word, line 2 starts with '+'; SEQ is
+ *                  upper-cased, QUAL copied.  Malformed input (line 0 without '@', line 2 without '+', a line count that is not a
+ *                  multiple of 4): ASM_EINVAL, asm_last_error names the 1-based record, and what sam_path holds is unspecified.  A
+ *                  file starting with '>' (FASTA): ASM_EUNSUPPORTED.  An empty file gives the header alone.  sam_path is created or
+ *                  truncated; header (may be NULL) is written first, as it is.  The records are, byte for byte, the lines asm-map
+ *                  writes for the same reads: max_hits = 0 asm_map_reads' best hit per read, max_hits in [1, 256] the loci of
+ *                  asm_map_reads_all (strata in [0, 15]) in rank order with NH, HI and XH; seq_names = the n_seqs RNAMEs of the index;
+ *                  an unmapped, empty or too long (> ASM_MAP_MAX_READ) read gives the unmapped line; CIGAR is '*' above 64
+ *                  operations.  The output does not depend on chunk_bytes or ASM_MAP_CHUNK.
+ * asm_fastq_cut:   the length of the longest prefix of buf[0, nbytes) made of whole four-line records (every line ending in LF), and
+ *                  how many records that is; no device. */
+typedef struct asm_map_file_stats {
+    int64_t reads, mapped, too_long, records; /* FASTQ records; reads with a mapped primary; longer than ASM_MAP_MAX_READ; SAM lines */
+    int64_t chunks, bytes_in, bytes_out;      /* device chunks; FASTQ bytes; SAM bytes without the header */
+    double seconds, seconds_read, seconds_write; /* whole call; reader busy; writer busy */
+} asm_map_file_stats;
+int asm_map_file(asm_handle* h, const asm_index* ix, const char* const* seq_names /* [n_seqs] */, const char* fastq_path,
+                 const char* sam_path, const char* header, const asm_map_params* p, int max_hits, int strata, int64_t chunk_bytes,
+                 asm_map_file_stats* stats /* may be NULL */);
+size_t asm_fastq_cut(const char* buf, size_t nbytes, int64_t* records);
+
 /* ---- plain device memory helpers (so that non-torch hosts can drive the async API) --------------------- */
 int asm_device_malloc(asm_handle* h, size_t bytes, void** d_ptr);
 int asm_device_free(asm_handle* h, void* d_ptr);

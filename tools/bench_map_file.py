@@ -1,0 +1,124 @@
+"""File-to-file read mapping timings (development tool):
+PYTHONPATH=. python tools/bench_map_file.py --dir DIR [--ref-len 5e6] [--reads 1e6] [--len 100] [--errors 2] [--all-hits N]
+[--reps 3] [--chunk-bytes N] [--profile]
+Writes the workload of tools/bench_map.py as files into DIR (seeded: a reference of --ref-len bases as ref.fa and --reads reads of
+--len bases with qualities as reads.fq), then runs `asm-map` and `asm-map --stream` on them alternately, --reps times each, in this
+one call.  For every run: the wall clock of the whole process (reference parsing and index build included, the same in both) and,
+for --stream, the library's own split (whole asm_map_file call, reader busy, writer busy).  The comparison is always against the
+same asm-map without --stream on the same files; the two SAM files must be identical apart from @PG.  The files are read once
+before the first run, so every run finds them in the page cache; the SAM files go to DIR too.
+--profile runs `asm-map --stream` once under `rocprofv3 --kernel-trace --stats` (a run of its own) and prints the kernel totals."""
+import argparse
+import csv
+import glob
+import json
+import os
+import re
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+from tools.bench_map import make_inputs  # noqa: E402
+
+EXE = os.path.join(ROOT, "approximate-string-matching_amd", "asm-map")
+
+
+def write_files(a, e):
+    ref, reads = make_inputs(int(a.ref_len), int(a.reads), a.len, e, seed=1234)
+    fa, fq = os.path.join(a.dir, "ref.fa"), os.path.join(a.dir, "reads.fq")
+    with open(fa, "wb") as fh:
+        fh.write(b">ref\n")
+        body = np.full((ref.size + 69) // 70 * 71, 10, np.uint8).reshape(-1, 71)
+        flat = np.zeros(body.shape[0] * 70, np.uint8)
+        flat[:ref.size] = ref
+        body[:, :70] = flat.reshape(-1, 70)
+        out = body.reshape(-1)
+        out = out[out != 0]
+        fh.write(out.tobytes())
+    n, m = reads.shape
+    rng = np.random.default_rng(99)
+    names = np.char.add("@read", np.arange(n).astype(str)).astype(bytes)
+    quals = rng.integers(35, 74, (n, m), dtype=np.uint8)
+    with open(fq, "wb") as fh:
+        for lo in range(0, n, 100_000):
+            hi = min(n, lo + 100_000)
+            fh.write(b"".join(names[t] + b"\n" + reads[t].tobytes() + b"\n+\n" + quals[t].tobytes() + b"\n" for t in range(lo, hi)))
+    return fa, fq
+
+
+def run(cmd):
+    t0 = time.perf_counter()
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500)
+    wall = time.perf_counter() - t0
+    if r.returncode != 0:
+        raise SystemExit("failed: %s\n%s" % (" ".join(cmd), r.stderr[-2000:]))
+    return wall, r.stderr
+
+
+def body_of(path):
+    with open(path, "rb") as fh:
+        return [ln for ln in fh.read().split(b"\n") if not ln.startswith(b"@PG")]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dir", required=True, help="directory for the input and output files")
+    ap.add_argument("--ref-len", type=float, default=5e6)
+    ap.add_argument("--reads", type=float, default=1e6)
+    ap.add_argument("--len", type=int, default=100)
+    ap.add_argument("--errors", type=int, default=2)
+    ap.add_argument("--all-hits", type=int, default=0)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--chunk-bytes", type=int, default=0)
+    ap.add_argument("--profile", action="store_true")
+    a = ap.parse_args()
+    os.makedirs(a.dir, exist_ok=True)
+    fa, fq = write_files(a, a.errors)
+    for path in (fa, fq):  # into the page cache
+        with open(path, "rb") as fh:
+            while fh.read(1 << 24):
+                pass
+    flags = ["-e", str(a.errors), "--both-strands"] + (["--all-hits", str(a.all_hits)] if a.all_hits else [])
+    base = [EXE, "-r", fa, "-q", fq] + flags
+    stream = ["--stream"] + (["--chunk-bytes", str(a.chunk_bytes)] if a.chunk_bytes else [])
+    sam0, sam1 = os.path.join(a.dir, "plain.sam"), os.path.join(a.dir, "stream.sam")
+    if a.profile:
+        out = os.path.join(a.dir, "profile")
+        os.makedirs(out, exist_ok=True)
+        subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "-d", out, "-o", "map_file", "--output-format", "csv", "--"] + base +
+                       ["-o", sam1] + stream, check=True, timeout=1200)
+        for path in glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True):
+            with open(path) as fh:
+                rows = list(csv.DictReader(fh))
+            print("kernel totals (", path, ")")
+            for r in rows[:40]:
+                print("  %-60s calls %6s total %10.3f ms  avg %9.1f us" % (r["Name"][:60], r["Calls"], float(r["TotalDurationNs"]) / 1e6,
+                                                                           float(r["AverageNs"]) / 1e3))
+        return
+    result = {"reads": int(a.reads), "len": a.len, "ref_len": int(a.ref_len), "errors": a.errors, "all_hits": a.all_hits,
+              "fastq_bytes": os.path.getsize(fq), "page_cache": True, "pairs": []}
+    for rep in range(a.reps):
+        w0, err0 = run(base + ["-o", sam0])
+        w1, err1 = run(base + ["-o", sam1] + stream)
+        mt = re.search(r"([\d.]+) s \(reader busy ([\d.]+) s, writer busy ([\d.]+) s\)", err1)
+        pair = {"plain_s": round(w0, 3), "stream_s": round(w1, 3), "ratio": round(w0 / w1, 2), "call_s": float(mt.group(1)),
+                "read_s": float(mt.group(2)), "write_s": float(mt.group(3)), "faster": w1 < w0}
+        result["pairs"].append(pair)
+        print("pair %d: asm-map %.3f s, asm-map --stream %.3f s (x%.2f); asm_map_file %.3f s, reader busy %.3f s, writer busy %.3f s" %
+              (rep, w0, w1, w0 / w1, pair["call_s"], pair["read_s"], pair["write_s"]), flush=True)
+        if rep == 0:
+            result["sam_bytes"] = os.path.getsize(sam1)
+            result["identical"] = body_of(sam0) == body_of(sam1)
+            result["summary"] = err1.splitlines()[0]
+            print("SAM files identical apart from @PG:", result["identical"], flush=True)
+    result["all_faster"] = all(p["faster"] for p in result["pairs"])
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
