@@ -2010,6 +2010,8 @@ int asm_run_benchmark_async(asm_handle* h, asm_batch* b, const asm_params* p, in
     return rc;
 }
 
+#include "asm_stream.h"
+
 /* ---------------------------------------------------------------------------------------------------- */
 /* Streaming ingest: a `>read\n<ref\n` file (benchmark_utils.h:325-352) through the aligners in chunks.
  *   reader threads   pread() the next chunk into pinned host memory (three buffers in rotation) and count its newlines, so
@@ -2026,10 +2028,9 @@ using asm_host::scan_newlines;
 static int batch_from_device_text(asm_handle* h, const char* d_raw, size_t nbytes, asm_batch* b) {
     const int64_t n = b->n;
     const size_t cnt = (size_t)n + 1;
-    const long ntiles = (long)((nbytes + SEQ_TILE - 1) / SEQ_TILE);
-    Scratch<uint32_t> d_tile(h), d_tbase(h), d_nl(h), d_m(h), d_n(h), d_max(h);
+    Scratch<uint32_t> d_nl(h), d_m(h), d_n(h), d_max(h);
     Scratch<unsigned long long> d_sa(h), d_sb(h);
-    Scratch<void> d_tmp(h);
+    MapTmp tmp(h);
     HIPCHK(h, batch_alloc(b, &b->d_read_off, sizeof(uint32_t) * cnt));
     HIPCHK(h, batch_alloc(b, &b->d_ref_off, sizeof(uint32_t) * cnt));
     HIPCHK(h, d_m.alloc(sizeof(uint32_t) * cnt));
@@ -2037,25 +2038,13 @@ static int batch_from_device_text(asm_handle* h, const char* d_raw, size_t nbyte
     HIPCHK(h, d_sa.alloc(sizeof(unsigned long long) * cnt));
     HIPCHK(h, d_sb.alloc(sizeof(unsigned long long) * cnt));
     HIPCHK(h, d_nl.alloc(sizeof(uint32_t) * (2 * (size_t)n + 2)));
-    HIPCHK(h, d_tile.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1)));
-    HIPCHK(h, d_tbase.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1)));
     HIPCHK(h, d_max.alloc(16));
     HIPCHK(h, hipMemsetAsync(d_max.p, 0, 16, h->stream));
-    size_t tmp_bytes = 0, t2 = 0;
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_tile.p, d_tbase.p, (int)ntiles, h->stream));
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, t2, d_m.p, b->d_read_off, (int)cnt, h->stream));
-    tmp_bytes = t2 > tmp_bytes ? t2 : tmp_bytes;
-    HIPCHK(h, d_tmp.alloc(tmp_bytes + 16));
-    if (n > 0) {
-        hipLaunchKernelGGL(seq_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, h->stream, d_raw, (long)nbytes, d_tile.p);
-        HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_tile.p, d_tbase.p, (int)ntiles, h->stream));
-        hipLaunchKernelGGL(seq_index_kernel, dim3((unsigned)ntiles), dim3(256), 0, h->stream, d_raw, (long)nbytes,
-                           (const uint32_t*)d_tbase.p, d_nl.p, (long)(2 * n));
-    }
+    if (n > 0) HIPCHK(h, newline_index(h, tmp, d_raw, nbytes, (long)(2 * n), d_nl.p));
     hipLaunchKernelGGL(seq_lengths_kernel, dim3(grid_for(n + 1)), dim3(ASM_BLOCK), 0, h->stream, (const uint32_t*)d_nl.p, (long)n,
                        d_m.p, d_n.p, d_sa.p, d_sb.p);
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_m.p, b->d_read_off, (int)cnt, h->stream));
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_n.p, b->d_ref_off, (int)cnt, h->stream));
+    HIPCHK(h, map_exclusive_sum(h, tmp, d_m.p, b->d_read_off, (int64_t)cnt));
+    HIPCHK(h, map_exclusive_sum(h, tmp, d_n.p, b->d_ref_off, (int64_t)cnt));
     if (n > 0) {
         int64_t blocks = (n + ASM_BLOCK - 1) / ASM_BLOCK;
         blocks = blocks > 1024 ? 1024 : blocks;
@@ -2111,6 +2100,28 @@ int asm_batch_from_text(asm_handle* h, const char* text, size_t nbytes, int gree
     return ASM_OK;
 }
 
+#define SEQ_TRY(call) STREAM_TRY("asm_stream_seq_file", call)
+
+extern "C++" {
+/* Result staging of asm_stream_seq_file on the device: penalties and answers per device buffer, and "the chunk's results are in
+ * pinned memory".  The destructor waits for the device (the aligners run on the library's own streams too) before it frees. */
+struct SeqStaging {
+    asm_handle* h;
+    int32_t* d_pen[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    int32_t* d_ans[2] = {nullptr, nullptr};
+    hipEvent_t ev_done[2] = {nullptr, nullptr};
+    explicit SeqStaging(asm_handle* owner) : h(owner) {}
+    ~SeqStaging() {
+        (void)hipDeviceSynchronize();
+        for (int q = 0; q < 2; q++) {
+            if (ev_done[q]) (void)hipEventDestroy(ev_done[q]);
+            for (int a = 0; a < 3; a++) pool_free(h, d_pen[q][a]);
+            pool_free(h, d_ans[q]);
+        }
+    }
+};
+}
+
 int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, int greedy_mode, int aligner_mask,
                         int64_t chunk_bytes, int64_t max_pairs, int32_t* nw, int32_t* leap, int32_t* greedy, int64_t out_cap,
                         const int32_t* answers, int64_t n_answers, asm_stream_stats* stats) {
@@ -2121,14 +2132,9 @@ int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, in
     const bool do_nw = (aligner_mask & 1) != 0, do_leap = (aligner_mask & 2) != 0, do_greedy = (aligner_mask & 4) != 0;
     if (!(do_nw || do_leap || do_greedy)) return fail(h, ASM_EINVAL, "asm_stream_seq_file: empty aligner mask");
     HIPCHK(h, hipSetDevice(h->device));
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) return fail(h, ASM_EINVAL, std::string("asm_stream_seq_file: cannot open ") + path); /* benchmark_utils.h:350 */
-    struct stat st;
-    if (fstat(fd, &st) != 0) {
-        close(fd);
-        return fail(h, ASM_EINVAL, "asm_stream_seq_file: fstat failed");
-    }
-    const size_t file_bytes = (size_t)st.st_size;
+    StreamInput in(h, "asm_stream_seq_file");
+    size_t file_bytes = 0;
+    if (const int rc = in.open_file(path, &file_bytes)) return rc;
     size_t chunk = chunk_bytes > 0 ? (size_t)chunk_bytes : ((size_t)64 << 20);
     chunk = chunk < 4096 ? 4096 : chunk;
     if (chunk > ((size_t)1 << 30)) chunk = (size_t)1 << 30;
@@ -2139,217 +2145,126 @@ int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, in
     if (const char* env = getenv("ASM_READER_THREADS")) reader_threads = atoi(env) > 0 ? atoi(env) : reader_threads;
     const auto t_begin = std::chrono::steady_clock::now();
 
-    hipEvent_t ev_shipped[3] = {nullptr, nullptr, nullptr}; /* the H2D copy out of host slot q is over */
-    /* the reader side lives in asm_host.h (no HIP there: the same code runs under ThreadSanitizer in host/asm_host_check.cpp);
-     * the one thing it needs from the device is "has the copy out of this slot finished" */
-    /* large chunks ramp up from a sixteenth (asm_host::SeqReader): the transfer of the first chunk starts after 1/16 of a chunk
-     * has been read instead of after a whole one */
-    const size_t first_chunk = chunk >= ((size_t)32 << 20) ? chunk / 16 : chunk;
-    asm_host::SeqReader rd(fd, file_bytes, chunk, reader_threads, max_pairs, [&](int q) {
-        (void)hipSetDevice(h->device);
-        (void)hipEventSynchronize(ev_shipped[q]);
-    }, first_chunk);
-    char* d_raw[2] = {nullptr, nullptr};
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
-    int32_t* h_pen[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-    int32_t* d_pen[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-    int32_t* d_ans[2] = {nullptr, nullptr};
-    unsigned long long* d_cnt = nullptr;
-    int64_t pen_cap = 0;
-    int rc = ASM_OK;
-    auto cleanup = [&]() {
-        rd.stop();
-        (void)hipDeviceSynchronize();
-        for (hipEvent_t ev : ev_shipped)
-            if (ev) (void)hipEventDestroy(ev);
-        for (int q = 0; q < 2; q++) {
-            pool_free(h, d_raw[q]);
-            if (ev_h2d[q]) (void)hipEventDestroy(ev_h2d[q]);
-            if (ev_done[q]) (void)hipEventDestroy(ev_done[q]);
-            for (int a = 0; a < 3; a++) pool_free(h, d_pen[q][a]);
-            pool_free(h, d_ans[q]);
-        }
-        pool_free(h, d_cnt);
-        if (copy_stream) (void)hipStreamDestroy(copy_stream);
-        close(fd);
-    };
-#define STREAM_TRY(call)                                                                   \
-    if (!rc && (call) != hipSuccess) rc = fail(h, ASM_ENODEVICE, std::string(#call) + " failed")
-
     if (h->pin_raw_cap < slot_cap) { /* (re)pin */
         for (char*& q : h->pin_raw) {
             if (q) (void)hipHostFree(q);
             q = nullptr;
         }
         h->pin_raw_cap = 0;
-        for (char*& q : h->pin_raw) STREAM_TRY(hipHostMalloc((void**)&q, slot_cap + 64, hipHostMallocDefault));
-        if (!rc) h->pin_raw_cap = slot_cap;
+        for (char*& q : h->pin_raw) SEQ_TRY(hipHostMalloc((void**)&q, slot_cap + 64, hipHostMallocDefault));
+        h->pin_raw_cap = slot_cap;
     }
-    for (int q = 0; q < 3; q++) {
-        rd.slot[q].buf = h->pin_raw[q];
-        rd.slot[q].cap = slot_cap;
-        STREAM_TRY(hipEventCreateWithFlags(&ev_shipped[q], hipEventDisableTiming));
-    }
-    for (int qq = 0; qq < 2; qq++)
-        for (int a = 0; a < 3; a++) h_pen[qq][a] = h->pin_pen[qq][a];
-    pen_cap = 0; /* device staging is (re)allocated with the first chunk; the pinned side is reused when large enough */
-    STREAM_TRY(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
-    for (int q = 0; q < 2; q++) {
-        STREAM_TRY(pool_alloc(h, (void**)&d_raw[q], slot_cap + 64));
-        STREAM_TRY(hipEventCreateWithFlags(&ev_h2d[q], hipEventDisableTiming));
-        STREAM_TRY(hipEventCreateWithFlags(&ev_done[q], hipEventDisableTiming));
-    }
-    STREAM_TRY(pool_alloc(h, (void**)&d_cnt, 32));
-    STREAM_TRY(hipMemsetAsync(d_cnt, 0, 32, h->stream));
-    /* d_raw comes from the pool, whose blocks are recycled in the order of the HANDLE's stream: kernels still queued there may
-     * read the block's previous life.  The copy stream is non-blocking and would not wait for them by itself. */
-    if (!rc) {
-        hipEvent_t ev_pool = nullptr;
-        STREAM_TRY(hipEventCreateWithFlags(&ev_pool, hipEventDisableTiming));
-        STREAM_TRY(hipEventRecord(ev_pool, h->stream));
-        STREAM_TRY(hipStreamWaitEvent(copy_stream, ev_pool, 0));
-        if (ev_pool) (void)hipEventDestroy(ev_pool);
-    }
-    if (rc) {
-        cleanup();
-        return rc;
-    }
-
-    rd.start(); /* the reader thread: fills the three slots in rotation (asm_host::SeqReader) */
+    for (int q = 0; q < 3; q++) in.pin[q] = h->pin_raw[q]; /* borrowed: they stay on the handle */
+    SEQ_TRY(in.open_device(slot_cap, true, false));
+    Scratch<unsigned long long> d_cnt(h);
+    BatchPtr chunk_batch[2];
+    SeqStaging st(h); /* declared behind what it must outlive: its destructor waits for the device before anything is given back */
+    for (hipEvent_t& ev : st.ev_done) SEQ_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    SEQ_TRY(d_cnt.alloc(32));
+    SEQ_TRY(hipMemsetAsync(d_cnt.p, 0, 32, h->stream));
+    /* the reader side lives in asm_host.h (no HIP there: the same code runs under ThreadSanitizer in host/asm_host_check.cpp);
+     * the one thing it needs from the device is "has the copy out of this slot finished".  Large chunks ramp up from a sixteenth:
+     * the transfer of the first chunk starts after 1/16 of a chunk has been read instead of after a whole one */
+    const size_t first_chunk = chunk >= ((size_t)32 << 20) ? chunk / 16 : chunk;
+    asm_host::ChunkReader<asm_host::PairsFill> rd(chunk, first_chunk, in.wait_shipped(), in.fd, file_bytes, reader_threads, max_pairs);
+    for (int q = 0; q < 3; q++) rd.slot[q].buf = in.pin[q], rd.slot[q].cap = slot_cap;
+    rd.start();
 
     /* ---- caller's thread: ship, compute, harvest ---- */
     uint8_t tail_state[256];
     memset(tail_state, 0, sizeof tail_state);
     int64_t chunk_first[2] = {0, 0}, chunk_pairs[2] = {0, 0};
-    BatchPtr chunk_batch[2];
-    int64_t done_pairs = 0;
+    int64_t pen_cap = 0; /* device staging is (re)allocated with the first chunk; the pinned side is reused when large enough */
+    int64_t done_pairs = 0, chunks = 0;
+    size_t bytes_total = 0;
     int maxlen = 0;
-    auto harvest = [&](int q) { /* results of the chunk that used device buffer q */
-        if (chunk_pairs[q] <= 0 && !chunk_batch[q]) return;
-        if (hipEventSynchronize(ev_done[q]) != hipSuccess && !rc) rc = fail(h, ASM_ENODEVICE, "asm_stream_seq_file: chunk failed");
+    auto harvest = [&](int q) -> int { /* results of the chunk that used device buffer q */
+        if (chunk_pairs[q] <= 0 && !chunk_batch[q]) return ASM_OK;
+        if (hipEventSynchronize(st.ev_done[q]) != hipSuccess) return fail(h, ASM_ENODEVICE, "asm_stream_seq_file: chunk failed");
         int32_t* dst[3] = {nw, leap, greedy};
         for (int a = 0; a < 3; a++) {
-            if (!dst[a] || !h_pen[q][a]) continue;
+            if (!dst[a] || !h->pin_pen[q][a]) continue;
             const int64_t room = out_cap - chunk_first[q];
             const int64_t cnt = chunk_pairs[q] < room ? chunk_pairs[q] : (room > 0 ? room : 0);
-            if (cnt > 0) memcpy(dst[a] + chunk_first[q], h_pen[q][a], sizeof(int32_t) * (size_t)cnt);
+            if (cnt > 0) memcpy(dst[a] + chunk_first[q], h->pin_pen[q][a], sizeof(int32_t) * (size_t)cnt);
         }
         chunk_batch[q].reset();
         chunk_pairs[q] = 0;
+        return ASM_OK;
     };
-    /* The loop runs two stages per iteration, one chunk apart: SHIP chunk c (host buffer -> HBM on the copy stream) and only then
-     * PROCESS chunk c-1 (parse, pack, aligners, results back).  Processing blocks this thread twice (the parser's totals and the
-     * packed batch), so with the stages the other way round the transfer of the next chunk could not start before the current
-     * one was packed, and the copy engine idled through every parse (round 2: 1.1e8 pairs/s; the same code in this order:
-     * DESIGN.md section 4b). */
-    bool last = false;
-    int64_t chunks = 0;
-    size_t bytes_total = 0;
-    int64_t pend_pairs[2] = {0, 0};
-    size_t pend_bytes[2] = {0, 0};
-    bool pend_valid[2] = {false, false};
-    auto process = [&](int q) { /* the chunk whose text sits in d_raw[q] */
-        if (!pend_valid[q]) return;
-        pend_valid[q] = false;
-        const int64_t n = pend_pairs[q];
-        const size_t shipped = pend_bytes[q];
-        if (n <= 0 || rc) return;
-        harvest(q); /* the chunk two back used the same result staging */
+    auto process = [&](int q, size_t shipped, int64_t n, int64_t) -> int { /* the chunk whose text sits in d_raw[q] */
+        if (const int rc = harvest(q)) return rc; /* the chunk two back used the same result staging */
         if (n > pen_cap) { /* staging sized from the first chunk for a full one (its pairs per byte, times the slot's bytes, plus an
                               eighth: chunks ramp up to `chunk`); pen_cap = 0 until the first chunk — not "is the NW buffer there",
                               which a mask without NW never satisfies */
-            harvest(q ^ 1);
+            if (const int rc = harvest(q ^ 1)) return rc;
             const int64_t full = (int64_t)((double)n / (double)(shipped ? shipped : 1) * (double)slot_cap) + 1;
             const int64_t cap = (full > n ? full : n) + (full > n ? full : n) / 8 + 1024;
-            for (int qq = 0; qq < 2 && !rc; qq++)
-                for (int a = 0; a < 3 && !rc; a++) {
+            for (int qq = 0; qq < 2; qq++)
+                for (int a = 0; a < 3; a++) {
                     if (!((aligner_mask >> a) & 1)) continue;
-                    pool_free(h, d_pen[qq][a]);
-                    d_pen[qq][a] = nullptr;
+                    pool_free(h, st.d_pen[qq][a]);
+                    st.d_pen[qq][a] = nullptr;
                     if (!h->pin_pen[qq][a] || h->pin_pen_cap[qq][a] < cap) {
                         if (h->pin_pen[qq][a]) (void)hipHostFree(h->pin_pen[qq][a]);
                         h->pin_pen[qq][a] = nullptr, h->pin_pen_cap[qq][a] = 0;
-                        STREAM_TRY(hipHostMalloc((void**)&h->pin_pen[qq][a], sizeof(int32_t) * (size_t)cap, hipHostMallocDefault));
-                        if (!rc) h->pin_pen_cap[qq][a] = cap;
+                        SEQ_TRY(hipHostMalloc((void**)&h->pin_pen[qq][a], sizeof(int32_t) * (size_t)cap, hipHostMallocDefault));
+                        h->pin_pen_cap[qq][a] = cap;
                     }
-                    h_pen[qq][a] = h->pin_pen[qq][a];
-                    STREAM_TRY(pool_alloc(h, (void**)&d_pen[qq][a], sizeof(int32_t) * (size_t)cap));
+                    SEQ_TRY(pool_alloc(h, (void**)&st.d_pen[qq][a], sizeof(int32_t) * (size_t)cap));
                 }
-            for (int qq = 0; qq < 2 && !rc && answers; qq++) {
-                pool_free(h, d_ans[qq]);
-                d_ans[qq] = nullptr;
-                STREAM_TRY(pool_alloc(h, (void**)&d_ans[qq], sizeof(int32_t) * (size_t)cap));
+            for (int qq = 0; qq < 2 && answers; qq++) {
+                pool_free(h, st.d_ans[qq]);
+                st.d_ans[qq] = nullptr;
+                SEQ_TRY(pool_alloc(h, (void**)&st.d_ans[qq], sizeof(int32_t) * (size_t)cap));
             }
             pen_cap = cap;
         }
-        if (rc) return;
-        STREAM_TRY(hipStreamWaitEvent(h->stream, ev_h2d[q], 0));
         BatchPtr b;
-        if (!rc) rc = batch_new(h, n, ASM_GREEDY_CLEAN, "asm_stream_seq_file", b);
-        if (!rc) rc = batch_from_device_text(h, d_raw[q], shipped, b.get());
-        if (rc) return;
+        if (const int rc = batch_new(h, n, ASM_GREEDY_CLEAN, "asm_stream_seq_file", b)) return rc;
+        if (const int rc = batch_from_device_text(h, in.d_raw[q], shipped, b.get())) return rc;
         if (greedy_mode == ASM_GREEDY_SEQUENTIAL && do_greedy) { /* the chain of hurdle_matrix.h:136-137 across chunk boundaries */
             uint8_t summary[256]; /* the summary does not depend on the state the tails are resolved from */
             b->greedy_mode = ASM_GREEDY_SEQUENTIAL;
-            rc = batch_resolve_tails(h, b.get(), tail_state, summary, true);
-            if (!rc) rc = asm_batch_pack_async(h, b.get());
-            if (!rc) rc = asm_tail_state_advance(tail_state, summary, n);
+            if (const int rc = batch_resolve_tails(h, b.get(), tail_state, summary, true)) return rc;
+            if (const int rc = asm_batch_pack_async(h, b.get())) return rc;
+            if (const int rc = asm_tail_state_advance(tail_state, summary, n)) return rc;
         }
         const int32_t* ans = nullptr;
-        if (!rc && answers && done_pairs < n_answers) { /* read_answer_file (benchmark_utils.h:358-368): one integer per pair */
+        if (answers && done_pairs < n_answers) { /* read_answer_file (benchmark_utils.h:358-368): one integer per pair */
             const int64_t have = n_answers - done_pairs < n ? n_answers - done_pairs : n;
             std::vector<int32_t> pad((size_t)n, INT32_MIN);
             memcpy(pad.data(), answers + done_pairs, sizeof(int32_t) * (size_t)have);
-            STREAM_TRY(hipMemcpyAsync(d_ans[q], pad.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-            STREAM_TRY(hipStreamSynchronize(h->stream)); /* `pad` is pageable and about to go out of scope */
-            ans = d_ans[q];
+            SEQ_TRY(hipMemcpyAsync(st.d_ans[q], pad.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+            SEQ_TRY(hipStreamSynchronize(h->stream)); /* `pad` is pageable and about to go out of scope */
+            ans = st.d_ans[q];
         }
-        if (!rc)
-            rc = asm_run_benchmark_async(h, b.get(), p, 0, do_nw ? d_pen[q][0] : nullptr, do_leap ? d_pen[q][1] : nullptr,
-                                         do_greedy ? d_pen[q][2] : nullptr, ans, d_cnt);
-        for (int a = 0; a < 3 && !rc; a++)
-            if (d_pen[q][a]) STREAM_TRY(hipMemcpyAsync(h_pen[q][a], d_pen[q][a], sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-        STREAM_TRY(hipEventRecord(ev_done[q], h->stream));
-        if (rc) return;
+        if (const int rc = asm_run_benchmark_async(h, b.get(), p, 0, do_nw ? st.d_pen[q][0] : nullptr, do_leap ? st.d_pen[q][1] : nullptr,
+                                                   do_greedy ? st.d_pen[q][2] : nullptr, ans, d_cnt.p))
+            return rc;
+        for (int a = 0; a < 3; a++)
+            if (st.d_pen[q][a])
+                SEQ_TRY(hipMemcpyAsync(h->pin_pen[q][a], st.d_pen[q][a], sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+        SEQ_TRY(hipEventRecord(st.ev_done[q], h->stream));
         maxlen = b->maxlen > maxlen ? b->maxlen : maxlen;
         chunk_batch[q] = std::move(b), chunk_first[q] = done_pairs, chunk_pairs[q] = n;
         done_pairs += n, bytes_total += shipped, chunks++;
+        return ASM_OK;
     };
-    for (int c = 0; !last && !rc; c++) {
-        asm_host::SeqSlot* sp = rd.wait_ready(c);
-        if (!sp) {
-            rc = fail(h, ASM_EINVAL, "asm_stream_seq_file: read failed (or one pair is longer than a chunk)");
-            break;
-        }
-        asm_host::SeqSlot& s = *sp;
-        const int q = c & 1;
-        /* SHIP chunk c.  d_raw[q] held chunk c-2, which was processed (and its text gathered into the batch's own arrays, with
-         * this thread waiting for that) in the iteration before this one. */
-        last = s.last;
-        bool shipping = false;
-        if (s.pairs > 0) {
-            STREAM_TRY(hipMemcpyAsync(d_raw[q], s.buf, s.bytes, hipMemcpyHostToDevice, copy_stream));
-            STREAM_TRY(hipEventRecord(ev_shipped[c % 3], copy_stream));
-            shipping = !rc;
-            STREAM_TRY(hipEventRecord(ev_h2d[q], copy_stream));
-        }
-        pend_pairs[q] = s.pairs, pend_bytes[q] = s.bytes, pend_valid[q] = true;
-        rd.consumed(c, shipping); /* the reader may refill the slot once ev_shipped has fired */
-        /* PROCESS chunk c-1 while chunk c is on its way */
-        process(q ^ 1);
-    }
-    if (!rc && !rd.failed()) process(0), process(1); /* the last chunk shipped (only one of the two is pending) */
-    harvest(0), harvest(1);
-    if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, ASM_ENODEVICE, "asm_stream_seq_file: stream synchronize failed");
-    if (!rc && hipMemcpy(stats->counters, d_cnt, 32, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(h, ASM_ENODEVICE, "asm_stream_seq_file: counters copy failed");
-#undef STREAM_TRY
-    cleanup();
+    if (const int rc = in.run(rd, "asm_stream_seq_file: read failed (or one pair is longer than a chunk)",
+                              [](const asm_host::ChunkSlot&, int64_t) { return ASM_OK; }, process))
+        return rc;
+    for (int q = 0; q < 2; q++)
+        if (const int rc = harvest(q)) return rc;
+    SEQ_TRY(hipStreamSynchronize(h->stream));
+    SEQ_TRY(hipMemcpy(stats->counters, d_cnt.p, 32, hipMemcpyDeviceToHost));
+    rd.stop();
     stats->pairs = done_pairs, stats->chunks = chunks, stats->bytes = (int64_t)bytes_total, stats->max_length = maxlen;
     stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     stats->seconds_read = rd.read_seconds();
-    return rc;
+    return ASM_OK;
 }
+#undef SEQ_TRY
 
 /* ---- read mapping: host side in csrc/asm_map_host.h (kernels: csrc/asm_map.h, design: docs/design/mapper.md) -------------------- */
 #include "asm_map_host.h"

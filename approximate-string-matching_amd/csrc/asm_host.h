@@ -1,8 +1,9 @@
 // The device-free part of the C ABI's host side: everything in libasm_mi355x.so that runs on the CPU and never calls HIP —
 // the seeded generator's host loop (asm_generate_pairs), the stale-tail state arithmetic (asm_tail_state_advance), the CIGAR
-// formatter (asm_cigar_format), and the reader side of asm_stream_seq_file: newline scanning, the persistent reader pool, and
-// the three-slot hand-over between the reader thread and the caller's thread (SeqReader); and asm_map_file's host threads: the
-// FASTQ chunk cutter (asm_fastq_cut), its reader (FastqReader) and the SAM writer (ChunkWriter).
+// formatter (asm_cigar_format), and the host threads of the two streamed-file calls: the three-slot hand-over between a reader
+// thread and the caller's thread (ChunkReader) with its two fill policies — asm_stream_seq_file's newline scanning over the
+// persistent reader pool (PairsFill) and asm_map_file's FASTQ chunk cutter (asm_fastq_cut, FastqFill) — and the SAM writer
+// (ChunkWriter).
 //
 // Kept in a header without any HIP include so that the SAME code is compiled twice: into the product by hipcc (asm_capi.hip),
 // and by plain g++ under -fsanitize=thread / address,undefined into host/asm_host_check.cpp (`make -C oracle asan`,
@@ -20,8 +21,10 @@
 #include <chrono>
 #include <climits>
 #include <condition_variable>
+#include <deque>
 #include <functional>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -297,25 +300,32 @@ inline NlScan read_and_scan(StreamWorkers& pool, int fd, char* buf, size_t head,
     return tot;
 }
 
-struct SeqSlot { /* one (pinned) host buffer */
+struct ChunkSlot { /* one (pinned) host buffer */
     char* buf = nullptr;
-    size_t cap = 0;
-    size_t bytes = 0;     /* raw bytes to ship: whole pairs only */
-    int64_t pairs = 0;
+    size_t cap = 0;          /* usable bytes */
+    size_t bytes = 0;        /* raw bytes to ship: whole units only */
+    int64_t units = 0;       /* pairs, or FASTQ records */
+    int64_t extra_lines = 0; /* FASTQ, last chunk: lines behind the last whole record (a truncated record) */
     bool last = false;
     bool ready = false;     /* filled by the reader, not yet taken by the consumer */
     bool in_flight = false; /* the consumer has started an asynchronous copy out of it; wait_shipped(slot) tells when it is over */
 };
 
-/* The reader thread of asm_stream_seq_file and its hand-over to the caller's thread.  Three slots in rotation: the reader fills
- * slot c % 3 with chunk c — the carry of the chunk before, then `chunk` more file bytes, cut behind the last complete pair —
- * and marks it ready; the consumer takes the chunks in order (wait_ready), starts its copy out of the buffer and gives the
- * slot back (consumed), after which the reader may refill it once wait_shipped(slot) says the copy is over. */
-class SeqReader {
-    const int fd_;
-    const size_t file_bytes_, chunk_, first_chunk_;
-    const int reader_threads_;
-    const int64_t max_pairs_;
+struct ChunkCut { /* what a fill policy reports: buf[0, have) is there, buf[0, boundary) are `units` whole units */
+    size_t have = 0, boundary = 0;
+    int64_t units = 0, extra_lines = 0;
+    bool eof = false;
+};
+
+/* The reader thread of a streamed file and its hand-over to the caller's thread.  Three slots in rotation: the reader fills slot
+ * c % 3 with chunk c and marks it ready; the consumer takes the chunks in order (wait_ready), starts its copy out of the buffer
+ * and gives the slot back (consumed), after which the reader may refill it once wait_shipped(slot) says the copy is over.
+ * How a slot is filled and cut is the policy's: fill(slot, q, carry, want, cut) puts the carry (what the chunk before left behind
+ * its boundary) and about `want` more file bytes into slot q and reports the cut; false: reading failed. */
+template <class Fill>
+class ChunkReader {
+    Fill fill_;
+    const size_t chunk_, first_chunk_;
     const std::function<void(int)> wait_shipped_;
     std::mutex mu_;
     std::condition_variable cv_;
@@ -324,13 +334,9 @@ class SeqReader {
     std::thread reader_;
 
     void loop() {
-        StreamWorkers workers(reader_threads_);
         std::vector<char> carry;
-        size_t file_off = 0;
-        int64_t pairs_left = max_pairs_ > 0 ? max_pairs_ : INT64_MAX;
-        bool eof = false;
-        for (int c = 0; !eof && !stop_; c++) {
-            SeqSlot& s = slot[c % 3];
+        for (int c = 0; !stop_; c++) {
+            ChunkSlot& s = slot[c % 3];
             {
                 std::unique_lock<std::mutex> lk(mu_);
                 cv_.wait(lk, [&] { return stop_ || !s.ready; });
@@ -341,67 +347,38 @@ class SeqReader {
                 s.in_flight = false;
             }
             const auto t0 = std::chrono::steady_clock::now();
-            size_t have = carry.size();
-            if (have) memcpy(s.buf, carry.data(), have);
-            carry.clear();
             /* chunk c takes first_chunk << c file bytes until that reaches `chunk`: the consumer's pipeline (ship, parse, align) starts
              * after the FIRST chunk is in memory, so a small first chunk shortens the fill of the pipeline and the large later ones
              * keep the per-chunk costs rare */
-            size_t want = c < 30 && (first_chunk_ << c) < chunk_ ? first_chunk_ << c : chunk_;
-            if (file_off + want > file_bytes_) want = file_bytes_ - file_off;
-            if (have + want > s.cap - 8) want = s.cap - 8 - have;
-            NlScan sc = read_and_scan(workers, fd_, s.buf, have, want, (off_t)file_off, failed_);
-            file_off += want;
-            have += want;
-            eof = file_off >= file_bytes_;
-            if (eof && have && s.buf[have - 1] != '\n') { /* a last line without its newline */
-                s.buf[have++] = '\n';
-                sc.prev = sc.last, sc.last = (int64_t)have - 1, sc.count++;
-            }
-            if (eof && (sc.count & 1)) { /* a read line without its reference line: an empty reference */
-                s.buf[have++] = '\n';
-                sc.prev = sc.last, sc.last = (int64_t)have - 1, sc.count++;
-            }
-            int64_t lines = sc.count & ~(int64_t)1;
-            size_t boundary = lines == 0 ? 0 : (size_t)((lines == sc.count ? sc.last : sc.prev) + 1);
-            if (lines / 2 > pairs_left) { /* max_pairs cuts inside this chunk: find the boundary of the pairs_left-th pair */
-                const int64_t need = 2 * pairs_left;
-                const char* q = s.buf;
-                for (int64_t l = 0; l < need; l++) q = (const char*)memchr(q, '\n', (size_t)(s.buf + have - q)) + 1;
-                boundary = (size_t)(q - s.buf), lines = need;
-                eof = true;
-            }
-            if (!eof) {
-                /* (the two bytes the reader may append above stay inside the slot: reads stop at cap - 8 and every slot is
-                 * allocated with cap + 64) */
-                if (boundary == 0 && have >= s.cap - 8) failed_ = true; /* one pair longer than a whole chunk */
-                carry.assign(s.buf + boundary, s.buf + have);
-            }
-            pairs_left -= lines / 2;
-            if (pairs_left <= 0) eof = true;
+            const size_t want = c < 30 && (first_chunk_ << c) < chunk_ ? first_chunk_ << c : chunk_;
+            ChunkCut cut;
+            const bool ok = fill_(s, c % 3, carry, want, cut);
+            carry.clear();
+            if (ok && !cut.eof) carry.assign(s.buf + cut.boundary, s.buf + cut.have);
             read_seconds_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            if (!ok) failed_ = true;
             {
                 std::lock_guard<std::mutex> lk(mu_);
-                s.bytes = boundary, s.pairs = lines / 2, s.last = eof, s.ready = true;
+                s.bytes = cut.boundary, s.units = cut.units, s.extra_lines = cut.extra_lines, s.last = cut.eof, s.ready = true;
             }
             cv_.notify_all();
-            if (failed_) return;
+            if (!ok || cut.eof) return;
         }
     }
 
 public:
-    SeqSlot slot[3]; /* the caller sets buf and cap (usable bytes; allocate cap + 64) before start() */
+    ChunkSlot slot[3]; /* the caller sets buf and cap (usable bytes; allocate cap + 64) before start() */
 
-    /* first_chunk: file bytes of chunk 0 (0 or >= chunk: every chunk takes `chunk`) */
-    SeqReader(int fd, size_t file_bytes, size_t chunk, int reader_threads, int64_t max_pairs, std::function<void(int)> wait_shipped,
-              size_t first_chunk = 0)
-        : fd_(fd), file_bytes_(file_bytes), chunk_(chunk), first_chunk_(first_chunk > 0 && first_chunk < chunk ? first_chunk : chunk),
-          reader_threads_(reader_threads), max_pairs_(max_pairs), wait_shipped_(std::move(wait_shipped)) {}
-    ~SeqReader() { stop(); }
+    /* first_chunk: file bytes of chunk 0 (0 or >= chunk: every chunk takes `chunk`); fill_args: the policy's constructor's */
+    template <class... A>
+    ChunkReader(size_t chunk, size_t first_chunk, std::function<void(int)> wait_shipped, A&&... fill_args)
+        : fill_(std::forward<A>(fill_args)...), chunk_(chunk), first_chunk_(first_chunk > 0 && first_chunk < chunk ? first_chunk : chunk),
+          wait_shipped_(std::move(wait_shipped)) {}
+    ~ChunkReader() { stop(); }
     void start() { reader_ = std::thread([this] { loop(); }); }
-    /* consumer: chunk c (in order, c = 0, 1, ...); nullptr when reading failed (or one pair is longer than a chunk) */
-    SeqSlot* wait_ready(int c) {
-        SeqSlot& s = slot[c % 3];
+    /* consumer: chunk c (in order, c = 0, 1, ...); nullptr when reading failed */
+    ChunkSlot* wait_ready(int c) {
+        ChunkSlot& s = slot[c % 3];
         {
             std::unique_lock<std::mutex> lk(mu_);
             cv_.wait(lk, [&] { return s.ready || failed_.load(); });
@@ -410,7 +387,7 @@ public:
     }
     /* consumer: done with chunk c's slot, apart from an asynchronous copy out of it when `in_flight` */
     void consumed(int c, bool in_flight) {
-        SeqSlot& s = slot[c % 3];
+        ChunkSlot& s = slot[c % 3];
         s.in_flight = in_flight;
         {
             std::lock_guard<std::mutex> lk(mu_);
@@ -429,6 +406,56 @@ public:
     }
     bool failed() const { return failed_.load(); }
     double read_seconds() const { return read_seconds_; } /* after stop() */
+};
+
+/* asm_stream_seq_file's policy: `want` more file bytes through the reader pool (reads stop at cap - 8), cut behind the last
+ * complete pair; at the end of the file a missing final newline and, for an odd line count, an empty reference line are appended;
+ * max_pairs > 0 ends the stream inside the chunk that reaches it.  A pair longer than a whole slot is a failure. */
+struct PairsFill {
+    const int fd;
+    const size_t file_bytes;
+    const int reader_threads;
+    int64_t pairs_left;
+    size_t file_off = 0;
+    std::optional<StreamWorkers> workers; /* started by the reader thread with its first chunk */
+    std::atomic<bool> failed{false};
+    PairsFill(int fd_, size_t file_bytes_, int reader_threads_, int64_t max_pairs)
+        : fd(fd_), file_bytes(file_bytes_), reader_threads(reader_threads_), pairs_left(max_pairs > 0 ? max_pairs : INT64_MAX) {}
+
+    bool operator()(ChunkSlot& s, int, const std::vector<char>& carry, size_t want, ChunkCut& cut) {
+        if (!workers) workers.emplace(reader_threads);
+        size_t have = carry.size();
+        if (have) memcpy(s.buf, carry.data(), have);
+        if (file_off + want > file_bytes) want = file_bytes - file_off;
+        if (have + want > s.cap - 8) want = s.cap - 8 - have;
+        NlScan sc = read_and_scan(*workers, fd, s.buf, have, want, (off_t)file_off, failed);
+        if (failed) return false;
+        file_off += want;
+        have += want;
+        bool eof = file_off >= file_bytes;
+        if (eof && have && s.buf[have - 1] != '\n') { /* a last line without its newline */
+            s.buf[have++] = '\n';
+            sc.prev = sc.last, sc.last = (int64_t)have - 1, sc.count++;
+        }
+        if (eof && (sc.count & 1)) { /* a read line without its reference line: an empty reference */
+            s.buf[have++] = '\n';
+            sc.prev = sc.last, sc.last = (int64_t)have - 1, sc.count++;
+        }
+        int64_t lines = sc.count & ~(int64_t)1;
+        size_t boundary = lines == 0 ? 0 : (size_t)((lines == sc.count ? sc.last : sc.prev) + 1);
+        if (lines / 2 > pairs_left) { /* max_pairs cuts inside this chunk: find the boundary of the pairs_left-th pair */
+            const int64_t need = 2 * pairs_left;
+            const char* q = s.buf;
+            for (int64_t l = 0; l < need; l++) q = (const char*)memchr(q, '\n', (size_t)(s.buf + have - q)) + 1;
+            boundary = (size_t)(q - s.buf), lines = need;
+            eof = true;
+        }
+        /* (the two bytes appended above stay inside the slot: reads stop at cap - 8 and every slot is allocated with cap + 64) */
+        if (!eof && boundary == 0 && have >= s.cap - 8) return false; /* one pair longer than a whole chunk */
+        pairs_left -= lines / 2;
+        cut.have = have, cut.boundary = boundary, cut.units = lines / 2, cut.eof = eof || pairs_left <= 0;
+        return true;
+    }
 };
 
 // ---- four-line FASTQ (asm_map_file): chunk cutting and the reader thread --------------------------------------------------------
@@ -450,123 +477,41 @@ inline size_t fastq_cut(const char* buf, size_t nbytes, int64_t* records, int64_
     return boundary;
 }
 
-struct FastqSlot { /* one (pinned) host buffer */
-    char* buf = nullptr;
-    size_t cap = 0;   /* usable bytes */
-    size_t bytes = 0; /* raw bytes to ship: whole records only */
-    int64_t records = 0;
-    int64_t extra_lines = 0; /* last chunk: lines behind the last whole record (a truncated record) */
-    bool last = false;
-    bool ready = false;
-    bool in_flight = false;
-};
+/* asm_map_file's policy: one pread loop, cut behind the last whole record (fastq_cut); when that leaves no record at all the chunk
+ * takes `chunk` more bytes, and the slot grows through grow(slot, capacity, keep) (the owner of the buffers moves the first `keep`
+ * bytes into a larger one and sets slot[q].buf and cap; false: out of memory).  extra_lines is reported with the last chunk, and
+ * an empty file is one last, empty chunk. */
+struct FastqFill {
+    const int fd;
+    const size_t file_bytes, chunk;
+    const std::function<bool(int, size_t, size_t)> grow;
+    size_t file_off = 0;
+    FastqFill(int fd_, size_t file_bytes_, size_t chunk_, std::function<bool(int, size_t, size_t)> grow_)
+        : fd(fd_), file_bytes(file_bytes_), chunk(chunk_), grow(std::move(grow_)) {}
 
-/* The reader thread of asm_map_file; the hand-over is SeqReader's: three slots in rotation, chunk c in slot c % 3, chunks ramping
- * up from first_chunk to chunk.  A chunk is the carry of the one before plus `want` file bytes, cut behind its last whole record
- * (fastq_cut); when that leaves no record at all the chunk takes more bytes, and the slot grows through grow(slot, capacity, keep)
- * (the owner of the buffers moves the first `keep` bytes into a larger one and sets slot[q].buf and cap; false: out of memory). */
-class FastqReader {
-    const int fd_;
-    const size_t file_bytes_, chunk_, first_chunk_;
-    const std::function<void(int)> wait_shipped_;
-    const std::function<bool(int, size_t, size_t)> grow_;
-    std::mutex mu_;
-    std::condition_variable cv_;
-    std::atomic<bool> failed_{false}, stop_{false};
-    double read_seconds_ = 0;
-    std::thread reader_;
-
-    bool read_more(FastqSlot& s, int q, size_t have, size_t want, size_t file_off) {
-        if (have + want + 8 > s.cap && !grow_(q, have + want + 8 + (have + want) / 4, have)) return false;
-        for (size_t a = 0; a < want;) {
-            const ssize_t got = pread(fd_, s.buf + have + a, want - a, (off_t)(file_off + a));
-            if (got <= 0) return false;
-            a += (size_t)got;
+    bool operator()(ChunkSlot& s, int q, const std::vector<char>& carry, size_t want, ChunkCut& cut) {
+        size_t have = carry.size();
+        if (have + 8 > s.cap && !grow(q, have + 8 + chunk, 0)) return false;
+        if (have) memcpy(s.buf, carry.data(), have);
+        int64_t lines = 0;
+        for (;;) {
+            if (want > file_bytes - file_off) want = file_bytes - file_off;
+            if (have + want + 8 > s.cap && !grow(q, have + want + 8 + (have + want) / 4, have)) return false;
+            for (size_t a = 0; a < want;) {
+                const ssize_t got = pread(fd, s.buf + have + a, want - a, (off_t)(file_off + a));
+                if (got <= 0) return false;
+                a += (size_t)got;
+            }
+            file_off += want, have += want;
+            cut.eof = file_off >= file_bytes;
+            if (cut.eof && have && s.buf[have - 1] != '\n') s.buf[have++] = '\n'; /* a last line without its newline */
+            cut.boundary = fastq_cut(s.buf, have, &cut.units, &lines);
+            if (cut.units > 0 || cut.eof) break;
+            want = chunk; /* one record longer than the chunk: take more */
         }
+        cut.have = have, cut.extra_lines = cut.eof ? lines - 4 * cut.units : 0;
         return true;
     }
-
-    void loop() {
-        std::vector<char> carry;
-        size_t file_off = 0;
-        bool eof = file_bytes_ == 0;
-        for (int c = 0; !stop_; c++) {
-            FastqSlot& s = slot[c % 3];
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                cv_.wait(lk, [&] { return stop_ || !s.ready; });
-                if (stop_) return;
-            }
-            if (s.in_flight) {
-                wait_shipped_(c % 3);
-                s.in_flight = false;
-            }
-            const auto t0 = std::chrono::steady_clock::now();
-            size_t have = carry.size();
-            bool ok = have + 8 <= s.cap || grow_(c % 3, have + 8 + chunk_, 0);
-            if (ok && have) memcpy(s.buf, carry.data(), have);
-            carry.clear();
-            int64_t records = 0, lines = 0;
-            size_t boundary = 0;
-            size_t want = c < 30 && (first_chunk_ << c) < chunk_ ? first_chunk_ << c : chunk_;
-            while (ok) {
-                if (want > file_bytes_ - file_off) want = file_bytes_ - file_off;
-                ok = read_more(s, c % 3, have, want, file_off);
-                if (!ok) break;
-                file_off += want, have += want;
-                eof = file_off >= file_bytes_;
-                if (eof && have && s.buf[have - 1] != '\n') s.buf[have++] = '\n'; /* a last line without its newline */
-                boundary = fastq_cut(s.buf, have, &records, &lines);
-                if (records > 0 || eof) break;
-                want = chunk_; /* one record longer than the chunk: take more */
-            }
-            if (ok && !eof) carry.assign(s.buf + boundary, s.buf + have);
-            read_seconds_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            if (!ok) failed_ = true;
-            {
-                std::lock_guard<std::mutex> lk(mu_);
-                s.bytes = boundary, s.records = records, s.extra_lines = eof ? lines - 4 * records : 0, s.last = eof, s.ready = true;
-            }
-            cv_.notify_all();
-            if (!ok || eof) return;
-        }
-    }
-
-public:
-    FastqSlot slot[3]; /* the caller sets buf and cap before start() */
-
-    FastqReader(int fd, size_t file_bytes, size_t chunk, size_t first_chunk, std::function<void(int)> wait_shipped,
-                std::function<bool(int, size_t, size_t)> grow)
-        : fd_(fd), file_bytes_(file_bytes), chunk_(chunk), first_chunk_(first_chunk > 0 && first_chunk < chunk ? first_chunk : chunk),
-          wait_shipped_(std::move(wait_shipped)), grow_(std::move(grow)) {}
-    ~FastqReader() { stop(); }
-    void start() { reader_ = std::thread([this] { loop(); }); }
-    FastqSlot* wait_ready(int c) { /* chunk c, in order; nullptr when reading failed */
-        FastqSlot& s = slot[c % 3];
-        {
-            std::unique_lock<std::mutex> lk(mu_);
-            cv_.wait(lk, [&] { return s.ready || failed_.load(); });
-        }
-        return failed_ ? nullptr : &s;
-    }
-    void consumed(int c, bool in_flight) {
-        FastqSlot& s = slot[c % 3];
-        s.in_flight = in_flight;
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            s.ready = false;
-        }
-        cv_.notify_all();
-    }
-    void stop() {
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        if (reader_.joinable()) reader_.join();
-    }
-    double read_seconds() const { return read_seconds_; } /* after stop() */
 };
 
 /* The writer thread of asm_map_file: jobs (a buffer and its length) are written in the order they were given; before(job) waits for
@@ -581,7 +526,7 @@ class ChunkWriter {
     const std::function<bool(int)> before_;
     std::mutex mu_;
     std::condition_variable cv_;
-    std::vector<Job> queue_;
+    std::deque<Job> queue_;
     bool busy_[3] = {false, false, false};
     bool quit_ = false, failed_ = false;
     double write_seconds_ = 0;
@@ -595,7 +540,7 @@ class ChunkWriter {
                 cv_.wait(lk, [&] { return quit_ || !queue_.empty(); });
                 if (queue_.empty()) return;
                 j = queue_.front();
-                queue_.erase(queue_.begin());
+                queue_.pop_front();
             }
             bool ok = before_(j.slot);
             const auto t0 = std::chrono::steady_clock::now();

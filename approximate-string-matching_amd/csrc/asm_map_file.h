@@ -1,63 +1,45 @@
 // asm_map_file: a FASTQ file in, a SAM file out, parsed, mapped and formatted on the device (kernels: asm_fastq.h, asm_sam.h and the
-// mapper's own; stages: asm_map_host.h; reader and writer threads: asm_host.h; design: docs/design/mapper.md, "Files: FASTQ in, SAM
-// out").  asm_capi.hip includes this file inside its extern "C" block, behind asm_map_host.h.
+// mapper's own; stages: asm_map_host.h; input pipeline: asm_stream.h; reader and writer threads: asm_host.h; design:
+// docs/design/mapper.md, "Files: FASTQ in, SAM out").  asm_capi.hip includes this file inside its extern "C" block, behind
+// asm_map_host.h.
 #pragma once
 
 extern "C++" {
 
-#define MAP_FILE_TRY(call)                                                                  \
-    do {                                                                                    \
-        hipError_t _e = (call);                                                             \
-        if (_e != hipSuccess)                                                               \
-            return fail(h, _e == hipErrorOutOfMemory ? ASM_ENOMEM : ASM_ENODEVICE,          \
-                        std::string("asm_map_file: ") + #call + ": " + hipGetErrorString(_e)); \
-    } while (0)
+#define MAP_FILE_TRY(call) STREAM_TRY("asm_map_file", call)
 
-/* What one call owns besides its threads: the files, two more streams, the pinned buffers (three in, three out, in rotation), the
- * device buffers that other streams read (raw text: two; SAM bytes: three) and the events between them.  The destructor waits for
- * the streams and gives everything back, on every path; the threads are declared after it, so they are joined before. */
+/* What one call owns besides its threads: the input side (StreamInput, asm_stream.h) and on top of it the SAM file, the copy-out
+ * stream, three pinned output buffers in rotation, the device buffers of the SAM bytes and the events between them.  The destructor
+ * waits for the streams and gives everything back, on every path; the threads are declared after it, so they are joined before. */
 struct MapFilePipe {
     asm_handle* h;
-    int fd = -1;
+    StreamInput in;
     FILE* out = nullptr;
-    hipStream_t s_in = nullptr, s_out = nullptr;
-    char* pin_in[3] = {nullptr, nullptr, nullptr};
+    hipStream_t s_out = nullptr;
     char* pin_out[3] = {nullptr, nullptr, nullptr};
     size_t pin_out_cap[3] = {0, 0, 0};
-    char* d_raw[2] = {nullptr, nullptr};
-    size_t d_raw_cap[2] = {0, 0};
     char* d_out[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_shipped[3] = {nullptr, nullptr, nullptr}; /* the copy out of pinned input slot q is over */
-    hipEvent_t ev_h2d[2] = {nullptr, nullptr};              /* d_raw[q] holds its chunk */
-    hipEvent_t ev_gate = nullptr;                           /* everything enqueued on the handle's stream so far */
-    hipEvent_t ev_fmt[3] = {nullptr, nullptr, nullptr};     /* d_out[o] holds its SAM bytes */
-    hipEvent_t ev_copied[3] = {nullptr, nullptr, nullptr};  /* pin_out[o] holds them */
-    explicit MapFilePipe(asm_handle* owner) : h(owner) {}
-    hipError_t open_device() {
-        hipError_t e = hipStreamCreateWithFlags(&s_in, hipStreamNonBlocking);
+    hipEvent_t ev_fmt[3] = {nullptr, nullptr, nullptr};    /* d_out[o] holds its SAM bytes */
+    hipEvent_t ev_copied[3] = {nullptr, nullptr, nullptr}; /* pin_out[o] holds them */
+    explicit MapFilePipe(asm_handle* owner) : h(owner), in(owner, "asm_map_file") {}
+    hipError_t open_device(size_t slot_cap) {
+        hipError_t e = in.open_device(slot_cap, false, true);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&s_out, hipStreamNonBlocking);
-        for (hipEvent_t* ev : {&ev_shipped[0], &ev_shipped[1], &ev_shipped[2], &ev_h2d[0], &ev_h2d[1], &ev_gate, &ev_fmt[0], &ev_fmt[1],
-                               &ev_fmt[2], &ev_copied[0], &ev_copied[1], &ev_copied[2]})
+        for (hipEvent_t* ev : {&ev_fmt[0], &ev_fmt[1], &ev_fmt[2], &ev_copied[0], &ev_copied[1], &ev_copied[2]})
             if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
         return e;
     }
-    ~MapFilePipe() {
+    ~MapFilePipe() { /* the input side goes after this */
         (void)hipSetDevice(h->device);
-        if (s_in) (void)hipStreamSynchronize(s_in);
+        if (in.s_in) (void)hipStreamSynchronize(in.s_in);
         if (s_out) (void)hipStreamSynchronize(s_out);
         (void)hipStreamSynchronize(h->stream);
-        for (hipEvent_t ev : {ev_shipped[0], ev_shipped[1], ev_shipped[2], ev_h2d[0], ev_h2d[1], ev_gate, ev_fmt[0], ev_fmt[1], ev_fmt[2],
-                              ev_copied[0], ev_copied[1], ev_copied[2]})
+        for (hipEvent_t ev : {ev_fmt[0], ev_fmt[1], ev_fmt[2], ev_copied[0], ev_copied[1], ev_copied[2]})
             if (ev) (void)hipEventDestroy(ev);
-        if (s_in) (void)hipStreamDestroy(s_in);
         if (s_out) (void)hipStreamDestroy(s_out);
-        for (char* q : pin_in)
-            if (q) (void)hipHostFree(q);
         for (char* q : pin_out)
             if (q) (void)hipHostFree(q);
-        for (char* q : d_raw) pool_free(h, q);
         for (char* q : d_out) pool_free(h, q);
-        if (fd >= 0) close(fd);
         if (out) fclose(out);
     }
 };
@@ -208,18 +190,10 @@ static int map_file_chunk(MapFileJob& j, const char* d_raw, const uint32_t* d_nl
 /* One file chunk (nrec whole records in d_raw[0, nbytes)): the newline index, then its device chunks of at most map_chunk records */
 static int map_file_process(MapFileJob& j, const char* d_raw, size_t nbytes, int64_t nrec, int64_t first_record) {
     asm_handle* h = j.h;
-    const long ntiles = (long)((nbytes + SEQ_TILE - 1) / SEQ_TILE), nl_lines = (long)(4 * nrec);
-    Scratch<uint32_t> d_tile(h), d_tbase(h), d_nl(h);
+    Scratch<uint32_t> d_nl(h);
     MapTmp tmp(h);
-    MAP_FILE_TRY(d_tile.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1)));
-    MAP_FILE_TRY(d_tbase.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1)));
-    MAP_FILE_TRY(d_nl.alloc(sizeof(uint32_t) * ((size_t)nl_lines + 2)));
-    hipLaunchKernelGGL(seq_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, h->stream, d_raw, (long)nbytes, d_tile.p);
-    MAP_FILE_TRY(hipGetLastError());
-    MAP_FILE_TRY(map_exclusive_sum(h, tmp, d_tile.p, d_tbase.p, (int64_t)ntiles));
-    hipLaunchKernelGGL(seq_index_kernel, dim3((unsigned)ntiles), dim3(256), 0, h->stream, d_raw, (long)nbytes, (const uint32_t*)d_tbase.p,
-                       d_nl.p, nl_lines);
-    MAP_FILE_TRY(hipGetLastError());
+    MAP_FILE_TRY(d_nl.alloc(sizeof(uint32_t) * (4 * (size_t)nrec + 2)));
+    MAP_FILE_TRY(newline_index(h, tmp, d_raw, nbytes, (long)(4 * nrec), d_nl.p));
     /* the run key of asm_map_reads_all holds the read in its top 31 bits */
     return map_chunks(nrec, std::min<int64_t>(h->map_chunk, (int64_t)1 << 30), [&](int64_t r0, int64_t rn) {
         return map_file_chunk(j, d_raw, d_nl.p, r0, rn, first_record + r0);
@@ -230,13 +204,11 @@ static int map_file_run(asm_handle* h, const asm_index* ix, const char* const* s
                         const char* header, const asm_map_params* p, int max_hits, int strata, size_t chunk, asm_map_file_stats* stats) {
     const auto t_begin = std::chrono::steady_clock::now();
     MapFilePipe pipe(h);
-    pipe.fd = open(fastq_path, O_RDONLY);
-    if (pipe.fd < 0) return fail(h, ASM_EINVAL, std::string("asm_map_file: cannot open ") + fastq_path);
-    struct stat st;
-    if (fstat(pipe.fd, &st) != 0) return fail(h, ASM_EINVAL, "asm_map_file: fstat failed");
-    const size_t file_bytes = (size_t)st.st_size;
+    StreamInput& in = pipe.in;
+    size_t file_bytes = 0;
+    if (const int rc = in.open_file(fastq_path, &file_bytes)) return rc;
     char first = 0;
-    if (file_bytes && pread(pipe.fd, &first, 1, 0) != 1) return fail(h, ASM_EINVAL, std::string("asm_map_file: cannot read ") + fastq_path);
+    if (file_bytes && pread(in.fd, &first, 1, 0) != 1) return fail(h, ASM_EINVAL, std::string("asm_map_file: cannot read ") + fastq_path);
     if (first == '>') return fail(h, ASM_EUNSUPPORTED, "asm_map_file: FASTA reads are not supported (the file starts with '>')");
     pipe.out = fopen(sam_path, "wb");
     if (!pipe.out) return fail(h, ASM_EINVAL, std::string("asm_map_file: cannot write ") + sam_path);
@@ -257,85 +229,44 @@ static int map_file_run(asm_handle* h, const asm_index* ix, const char* const* s
     MAP_FILE_TRY(hipMemcpyAsync(d_names.p, names.data(), names.size(), hipMemcpyHostToDevice, h->stream));
     MAP_FILE_TRY(hipMemcpyAsync(d_name_off.p, name_off.data(), sizeof(uint32_t) * name_off.size(), hipMemcpyHostToDevice, h->stream));
     MAP_FILE_TRY(hipStreamSynchronize(h->stream));
-    MAP_FILE_TRY(pipe.open_device());
     /* chunks ramp up from an eighth, so that the device starts after an eighth of a chunk has been read */
     const size_t slot_cap = chunk + chunk / 4 + 4096, first_chunk = chunk >= ((size_t)8 << 20) ? chunk / 8 : chunk;
-    for (char*& q : pipe.pin_in) MAP_FILE_TRY(hipHostMalloc((void**)&q, slot_cap + 64, hipHostMallocDefault));
-    asm_host::FastqReader rd(
-        pipe.fd, file_bytes, chunk, first_chunk,
-        [&](int q) {
-            (void)hipSetDevice(h->device);
-            (void)hipEventSynchronize(pipe.ev_shipped[q]);
-        },
+    MAP_FILE_TRY(pipe.open_device(slot_cap));
+    in.own_pin = true;
+    for (char*& q : in.pin) MAP_FILE_TRY(hipHostMalloc((void**)&q, slot_cap + 64, hipHostMallocDefault));
+    asm_host::ChunkReader<asm_host::FastqFill> rd(
+        chunk, first_chunk, in.wait_shipped(), in.fd, file_bytes, chunk,
         [&](int q, size_t cap, size_t keep) { /* a record longer than the buffer: a larger pinned one (no copy reads the old one now) */
             (void)hipSetDevice(h->device);
             char* bigger = nullptr;
             if (hipHostMalloc((void**)&bigger, cap + 64, hipHostMallocDefault) != hipSuccess) return false;
-            if (keep) memcpy(bigger, pipe.pin_in[q], keep);
-            (void)hipHostFree(pipe.pin_in[q]);
-            pipe.pin_in[q] = bigger;
+            if (keep) memcpy(bigger, in.pin[q], keep);
+            (void)hipHostFree(in.pin[q]);
+            in.pin[q] = bigger;
             rd.slot[q].buf = bigger, rd.slot[q].cap = cap;
             return true;
         });
-    for (int q = 0; q < 3; q++) rd.slot[q].buf = pipe.pin_in[q], rd.slot[q].cap = slot_cap;
+    for (int q = 0; q < 3; q++) rd.slot[q].buf = in.pin[q], rd.slot[q].cap = slot_cap;
     asm_host::ChunkWriter writer(pipe.out, [&](int o) {
         (void)hipSetDevice(h->device);
         return hipEventSynchronize(pipe.ev_copied[o]) == hipSuccess;
     });
     MapFileJob j = {h, ix, p, max_hits, strata, d_names.p, d_name_off.p, &pipe, &writer};
     rd.start();
-
-    /* this thread: SHIP chunk c (pinned buffer -> HBM on the copy-in stream), then PROCESS chunk c - 1 while c is on its way */
-    struct Pending {
-        bool valid = false;
-        size_t bytes = 0;
-        int64_t records = 0, first_record = 0;
-    } pend[2];
-    int64_t records_seen = 0;
-    auto process = [&](int q) -> int {
-        if (!pend[q].valid) return ASM_OK;
-        pend[q].valid = false;
-        if (pend[q].records <= 0) return ASM_OK;
-        MAP_FILE_TRY(hipStreamWaitEvent(h->stream, pipe.ev_h2d[q], 0));
-        return map_file_process(j, pipe.d_raw[q], pend[q].bytes, pend[q].records, pend[q].first_record);
-    };
-    bool last = false;
-    for (int c = 0; !last; c++) {
-        asm_host::FastqSlot* sp = rd.wait_ready(c);
-        if (!sp) return fail(h, ASM_EINVAL, std::string("asm_map_file: reading ") + fastq_path + " failed");
-        asm_host::FastqSlot& s = *sp;
-        const int q = c & 1;
-        last = s.last;
-        if (s.extra_lines)
-            return fail(h, ASM_EINVAL, "asm_map_file: record " + std::to_string(records_seen + s.records + 1) +
-                                           " is truncated (the file's line count is not a multiple of 4)");
-        if (s.bytes >= 0xfffffff0ull) return fail(h, ASM_EUNSUPPORTED, "asm_map_file: a chunk of 4 GiB or more; lower chunk_bytes");
-        bool shipping = false;
-        if (s.records > 0) {
-            if (pipe.d_raw_cap[q] < s.bytes + 64) {
-                pool_free(h, pipe.d_raw[q]);
-                pipe.d_raw[q] = nullptr, pipe.d_raw_cap[q] = 0;
-                const size_t want = std::max(s.bytes + s.bytes / 4, slot_cap) + 64;
-                MAP_FILE_TRY(pool_alloc(h, (void**)&pipe.d_raw[q], want));
-                pipe.d_raw_cap[q] = want;
-            }
-            /* d_raw[q] held chunk c - 2, whose kernels are all enqueued on the handle's stream (and a block fresh from the pool may
-             * still be read by work queued there): the copy waits for them */
-            MAP_FILE_TRY(hipEventRecord(pipe.ev_gate, h->stream));
-            MAP_FILE_TRY(hipStreamWaitEvent(pipe.s_in, pipe.ev_gate, 0));
-            MAP_FILE_TRY(hipMemcpyAsync(pipe.d_raw[q], s.buf, s.bytes, hipMemcpyHostToDevice, pipe.s_in));
-            MAP_FILE_TRY(hipEventRecord(pipe.ev_shipped[c % 3], pipe.s_in));
-            MAP_FILE_TRY(hipEventRecord(pipe.ev_h2d[q], pipe.s_in));
-            shipping = true;
-        }
-        pend[q].valid = true, pend[q].bytes = s.bytes, pend[q].records = s.records, pend[q].first_record = records_seen;
-        records_seen += s.records;
-        j.st.bytes_in += (int64_t)s.bytes;
-        rd.consumed(c, shipping);
-        if (const int rc = process(q ^ 1)) return rc;
-    }
-    for (int q = 0; q < 2; q++)
-        if (const int rc = process(q)) return rc;
+    const int rc = in.run(
+        rd, std::string("asm_map_file: reading ") + fastq_path + " failed",
+        [&](const asm_host::ChunkSlot& s, int64_t records_seen) {
+            if (s.extra_lines)
+                return fail(h, ASM_EINVAL, "asm_map_file: record " + std::to_string(records_seen + s.units + 1) +
+                                               " is truncated (the file's line count is not a multiple of 4)");
+            if (s.bytes >= 0xfffffff0ull) return fail(h, ASM_EUNSUPPORTED, "asm_map_file: a chunk of 4 GiB or more; lower chunk_bytes");
+            j.st.bytes_in += (int64_t)s.bytes;
+            return ASM_OK;
+        },
+        [&](int q, size_t bytes, int64_t records, int64_t first_record) {
+            return map_file_process(j, in.d_raw[q], bytes, records, first_record);
+        });
+    if (rc) return rc;
     rd.stop();
     if (!writer.finish() || fflush(pipe.out) != 0) return fail(h, ASM_EINVAL, "asm_map_file: writing the SAM file failed");
     j.st.seconds_read = rd.read_seconds(), j.st.seconds_write = writer.write_seconds();

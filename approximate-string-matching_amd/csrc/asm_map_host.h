@@ -32,27 +32,7 @@ static unsigned map_grid(uint64_t n, const asm_handle* h) { /* grid-stride kerne
     return (unsigned)(want < 1 ? 1 : want > cap ? cap : want);
 }
 
-/* hipcub's temporary storage: grows to the largest request; the old block goes back to the pool in stream order */
-struct MapTmp {
-    Scratch<void> s;
-    size_t cap = 0;
-    explicit MapTmp(asm_handle* h) : s(h) {}
-    hipError_t reserve(size_t bytes) {
-        if (s.p && bytes <= cap) return hipSuccess;
-        pool_free(s.h, s.p);
-        s.p = nullptr, cap = bytes;
-        return s.alloc(bytes + 16);
-    }
-};
-
-/* hipcub's two-phase calls on the handle's stream: query the temporary size, reserve it, run */
-template <class T>
-static hipError_t map_exclusive_sum(asm_handle* h, MapTmp& tmp, T* in, T* out, int64_t n) {
-    size_t bytes = 0;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, h->stream);
-    if (e == hipSuccess) e = tmp.reserve(bytes);
-    return e != hipSuccess ? e : hipcub::DeviceScan::ExclusiveSum(tmp.s.p, bytes, in, out, (int)n, h->stream);
-}
+/* (hipcub's scratch MapTmp and map_exclusive_sum: asm_stream.h, which the streamed-file calls share) */
 
 template <class K, class V, class N> /* stable: equal keys keep their order */
 static hipError_t map_sort_pairs(asm_handle* h, MapTmp& tmp, K* key_in, K* key_out, V* val_in, V* val_out, N n, int end_bit) {

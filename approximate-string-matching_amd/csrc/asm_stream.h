@@ -1,0 +1,182 @@
+// Device side of the two streamed-file calls (asm_stream_seq_file, asm_map_file): hipcub's scratch and scans, the newline index of
+// a chunk of text in HBM, and the input pipeline — reader thread (asm_host.h) -> pinned slots -> copy-in stream -> two device
+// buffers -> the caller's processing on the handle's stream.  asm_capi.hip includes this file inside its extern "C" block.
+#pragma once
+
+extern "C++" {
+
+/* the one error path of both calls: `who` is the call's name */
+#define STREAM_TRY(who, call)                                                                    \
+    do {                                                                                         \
+        hipError_t _e = (call);                                                                  \
+        if (_e != hipSuccess)                                                                    \
+            return fail(h, _e == hipErrorOutOfMemory ? ASM_ENOMEM : ASM_ENODEVICE,               \
+                        std::string(who) + ": " + #call + ": " + hipGetErrorString(_e));         \
+    } while (0)
+
+/* hipcub's temporary storage: grows to the largest request; the old block goes back to the pool in stream order */
+struct MapTmp {
+    Scratch<void> s;
+    size_t cap = 0;
+    explicit MapTmp(asm_handle* h) : s(h) {}
+    hipError_t reserve(size_t bytes) {
+        if (s.p && bytes <= cap) return hipSuccess;
+        pool_free(s.h, s.p);
+        s.p = nullptr, cap = bytes;
+        return s.alloc(bytes + 16);
+    }
+};
+
+/* hipcub's two-phase calls on the handle's stream: query the temporary size, reserve it, run */
+template <class T>
+static hipError_t map_exclusive_sum(asm_handle* h, MapTmp& tmp, T* in, T* out, int64_t n) {
+    size_t bytes = 0;
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, h->stream);
+    if (e == hipSuccess) e = tmp.reserve(bytes);
+    return e != hipSuccess ? e : hipcub::DeviceScan::ExclusiveSum(tmp.s.p, bytes, in, out, (int)n, h->stream);
+}
+
+/* d_nl[l] = the position of the l-th newline of d_raw[0, nbytes), for the first `lines` of them (asm_ingest.h) */
+static hipError_t newline_index(asm_handle* h, MapTmp& tmp, const char* d_raw, size_t nbytes, long lines, uint32_t* d_nl) {
+    const long ntiles = (long)((nbytes + SEQ_TILE - 1) / SEQ_TILE);
+    Scratch<uint32_t> d_tile(h), d_tbase(h);
+    hipError_t e = d_tile.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1));
+    if (e == hipSuccess) e = d_tbase.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1));
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(seq_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, h->stream, d_raw, (long)nbytes, d_tile.p);
+    e = map_exclusive_sum(h, tmp, d_tile.p, d_tbase.p, (int64_t)ntiles);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(seq_index_kernel, dim3((unsigned)ntiles), dim3(256), 0, h->stream, d_raw, (long)nbytes, (const uint32_t*)d_tbase.p,
+                       d_nl, lines);
+    return hipGetLastError();
+}
+
+/* The input side of one streamed call: the file, the copy-in stream, three pinned slots in rotation (the reader thread fills them),
+ * two device buffers that the handle's stream reads, and the events between them.  The destructor waits for the streams and gives
+ * everything back, on every path; declare the reader after it, so that its thread is joined before.
+ * The two callers differ in three ways, which open_device and the pinned slots take as they are:
+ *   pinned slots  borrowed (asm_stream_seq_file keeps them on the handle between calls) or owned (asm_map_file: per call, growing)
+ *   fixed_raw     d_raw[q] allocated once for a whole slot, or on demand with the chunk that needs it
+ *   gate_each     the copy-in stream waits for the handle's stream once, before the first copy (d_raw[q] is then reused only after
+ *                 this thread has waited for the parse of the chunk before), or before every copy */
+struct StreamInput {
+    asm_handle* h;
+    const char* who;
+    int fd = -1;
+    hipStream_t s_in = nullptr;
+    char* pin[3] = {nullptr, nullptr, nullptr};
+    bool own_pin = false;
+    char* d_raw[2] = {nullptr, nullptr};
+    size_t d_raw_cap[2] = {0, 0};
+    size_t slot_cap = 0;
+    bool gate_each = false;
+    hipEvent_t ev_shipped[3] = {nullptr, nullptr, nullptr}; /* the copy out of pinned slot q is over */
+    hipEvent_t ev_h2d[2] = {nullptr, nullptr};              /* d_raw[q] holds its chunk */
+    hipEvent_t ev_gate = nullptr;                           /* everything enqueued on the handle's stream so far */
+    StreamInput(asm_handle* owner, const char* call) : h(owner), who(call) {}
+    StreamInput(const StreamInput&) = delete;
+    StreamInput& operator=(const StreamInput&) = delete;
+    ~StreamInput() {
+        (void)hipSetDevice(h->device);
+        if (s_in) (void)hipStreamSynchronize(s_in);
+        (void)hipStreamSynchronize(h->stream);
+        for (hipEvent_t ev : {ev_shipped[0], ev_shipped[1], ev_shipped[2], ev_h2d[0], ev_h2d[1], ev_gate})
+            if (ev) (void)hipEventDestroy(ev);
+        if (s_in) (void)hipStreamDestroy(s_in);
+        for (char* q : pin)
+            if (q && own_pin) (void)hipHostFree(q);
+        for (char* q : d_raw) pool_free(h, q);
+        if (fd >= 0) close(fd);
+    }
+    int open_file(const char* path, size_t* file_bytes) {
+        fd = open(path, O_RDONLY);
+        if (fd < 0) return fail(h, ASM_EINVAL, std::string(who) + ": cannot open " + path); /* benchmark_utils.h:350 */
+        struct stat st;
+        if (fstat(fd, &st) != 0) return fail(h, ASM_EINVAL, std::string(who) + ": fstat failed");
+        *file_bytes = (size_t)st.st_size;
+        return ASM_OK;
+    }
+    hipError_t gate() { /* the copy-in stream waits for what the handle's stream holds now */
+        hipError_t e = hipEventRecord(ev_gate, h->stream);
+        return e != hipSuccess ? e : hipStreamWaitEvent(s_in, ev_gate, 0);
+    }
+    hipError_t reserve_raw(int q, size_t bytes) {
+        if (d_raw_cap[q] >= bytes + 64) return hipSuccess;
+        pool_free(h, d_raw[q]);
+        d_raw[q] = nullptr, d_raw_cap[q] = 0;
+        const size_t want = std::max(bytes + bytes / 4, slot_cap) + 64;
+        const hipError_t e = pool_alloc(h, (void**)&d_raw[q], want);
+        if (e == hipSuccess) d_raw_cap[q] = want;
+        return e;
+    }
+    hipError_t open_device(size_t slot_bytes, bool fixed_raw, bool gate_every_copy) {
+        slot_cap = slot_bytes, gate_each = gate_every_copy;
+        hipError_t e = hipStreamCreateWithFlags(&s_in, hipStreamNonBlocking);
+        for (hipEvent_t* ev : {&ev_shipped[0], &ev_shipped[1], &ev_shipped[2], &ev_h2d[0], &ev_h2d[1], &ev_gate})
+            if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+        for (int q = 0; q < 2 && fixed_raw; q++)
+            if (e == hipSuccess) e = reserve_raw(q, 0);
+        /* d_raw comes from the pool, whose blocks are recycled in the order of the HANDLE's stream: kernels still queued there may
+         * read the block's previous life.  The copy stream is non-blocking and would not wait for them by itself. */
+        if (e == hipSuccess && !gate_each) e = gate();
+        return e;
+    }
+    /* SHIP chunk c: pinned slot c % 3 -> d_raw[c & 1] on the copy-in stream */
+    int ship(int c, const asm_host::ChunkSlot& s) {
+        const int q = c & 1;
+        STREAM_TRY(who, reserve_raw(q, s.bytes));
+        /* d_raw[q] held chunk c - 2, whose kernels are all enqueued on the handle's stream (and a block fresh from the pool may
+         * still be read by work queued there): the copy waits for them */
+        if (gate_each) STREAM_TRY(who, gate());
+        STREAM_TRY(who, hipMemcpyAsync(d_raw[q], s.buf, s.bytes, hipMemcpyHostToDevice, s_in));
+        STREAM_TRY(who, hipEventRecord(ev_shipped[c % 3], s_in));
+        STREAM_TRY(who, hipEventRecord(ev_h2d[q], s_in));
+        return ASM_OK;
+    }
+    std::function<void(int)> wait_shipped() { /* for the reader: the copy out of slot q is over */
+        return [this](int q) {
+            (void)hipSetDevice(h->device);
+            (void)hipEventSynchronize(ev_shipped[q]);
+        };
+    }
+    /* The caller's thread.  Two stages per iteration, one chunk apart: SHIP chunk c and only then PROCESS chunk c - 1.  Processing
+     * blocks this thread (the parser's totals), so with the stages the other way round the transfer of the next chunk could not
+     * start before the current one was parsed, and the copy engine idled through every parse.
+     * accept(slot, first_unit) sees every chunk before it is shipped; process(q, bytes, units, first_unit) runs behind the copy into
+     * d_raw[q], for every chunk that holds a unit; first_unit: the file's units before the chunk.  read_failed: the reader's message. */
+    template <class Reader, class Accept, class Process>
+    int run(Reader& rd, const std::string& read_failed, Accept accept, Process process) {
+        struct {
+            bool valid = false;
+            size_t bytes = 0;
+            int64_t units = 0, first = 0;
+        } pend[2];
+        auto flush = [&](int q) -> int {
+            if (!pend[q].valid) return ASM_OK;
+            pend[q].valid = false;
+            if (pend[q].units <= 0) return ASM_OK;
+            STREAM_TRY(who, hipStreamWaitEvent(h->stream, ev_h2d[q], 0));
+            return process(q, pend[q].bytes, pend[q].units, pend[q].first);
+        };
+        int64_t seen = 0;
+        bool last = false;
+        for (int c = 0; !last; c++) {
+            asm_host::ChunkSlot* s = rd.wait_ready(c);
+            if (!s) return fail(h, ASM_EINVAL, read_failed);
+            const int q = c & 1;
+            last = s->last;
+            if (const int rc = accept(*s, seen)) return rc;
+            if (s->units > 0)
+                if (const int rc = ship(c, *s)) return rc;
+            pend[q].valid = true, pend[q].bytes = s->bytes, pend[q].units = s->units, pend[q].first = seen;
+            seen += s->units;
+            rd.consumed(c, s->units > 0); /* the reader may refill the slot once ev_shipped has fired */
+            if (const int rc = flush(q ^ 1)) return rc;
+        }
+        for (int q = 0; q < 2; q++) /* the last chunk shipped (only one of the two is pending) */
+            if (const int rc = flush(q)) return rc;
+        return ASM_OK;
+    }
+};
+
+} /* extern "C++" */

@@ -1,12 +1,14 @@
 // TEST PROGRAM for CPU sanitizers (`make -C oracle asan`; tests/test_sanitizers.py runs the two builds): the device-free host
 // side of the C ABI — csrc/asm_host.h, the very code libasm_mi355x.so compiles — exercised without a GPU:
 //   * the generator's host loop and the `>read\n<ref\n` text it stands for,
-//   * the streaming reader (asm_stream_seq_file's reader pool + three-slot hand-over) against a consumer that "ships" each
-//     chunk asynchronously on a thread of its own, the way the copy stream does: every byte of the file must come out once, in
-//     order, cut at pair boundaries, for several chunk sizes, reader counts and max_pairs cuts, incl. files that end without
-//     a newline or on a read line,
+//   * the streaming reader (ChunkReader: the three-slot hand-over) against a consumer that "ships" each chunk asynchronously on a
+//     thread of its own, the way the copy stream does, with both of its fill policies: asm_stream_seq_file's (PairsFill, the reader
+//     pool) — every byte of the file must come out once, in order, cut at pair boundaries, for several chunk sizes, reader counts
+//     and max_pairs cuts, incl. files that end without a newline or on a read line — and asm_map_file's (FastqFill), against a
+//     plain line splitter: chunk sizes with and without ramp, CRLF, truncated records, records longer than a slot, an early stop,
+//   * asm_map_file's writer thread (ChunkWriter): order, wait_idle, and failures that must not hang,
 //   * the stale-tail state arithmetic and the CIGAR formatter at their edges.
-// Built twice: -fsanitize=thread (races in the hand-over / the pool) and -fsanitize=address,undefined (buffer edges).
+// Built twice: -fsanitize=thread (races in the hand-overs / the pool) and -fsanitize=address,undefined (buffer edges).
 // Usage: asm_host_check <scratch directory>.  Prints "host check ok" and exits 0, or says what differed and exits 1.
 #include <sys/stat.h>
 
@@ -51,7 +53,7 @@ static std::string make_text(const asm_gen_config& cfg, int64_t first, int64_t n
     return text;
 }
 
-/* Streams `text` (written to `path`) through SeqReader; returns what the consumer received, concatenated. */
+/* Streams `text` (written to `path`) through ChunkReader<PairsFill>; returns what the consumer received, concatenated. */
 static std::string stream_file(const std::string& path, const std::string& text, size_t chunk, int readers, int64_t max_pairs,
                                int64_t* pairs_seen, int* chunks_seen, bool* failed, size_t slack = (size_t)4 << 10, size_t first_chunk = 0) {
     FILE* f = fopen(path.c_str(), "wb");
@@ -61,16 +63,16 @@ static std::string stream_file(const std::string& path, const std::string& text,
     const size_t cap = chunk + slack;
     std::vector<std::vector<char>> bufs(3, std::vector<char>(cap + 64));
     std::future<void> copy[3]; /* the "copy stream": an asynchronous reader of the slot's buffer */
-    SeqReader rd(fd, text.size(), chunk, readers, max_pairs, [&](int q) {
+    ChunkReader<PairsFill> rd(chunk, first_chunk, [&](int q) {
         if (copy[q].valid()) copy[q].wait();
-    }, first_chunk);
+    }, fd, text.size(), readers, max_pairs);
     for (int q = 0; q < 3; q++) rd.slot[q].buf = bufs[(size_t)q].data(), rd.slot[q].cap = cap;
     rd.start();
     std::deque<std::string> parts; /* a deque: elements stay where they are while asynchronous copies write into them */
     *pairs_seen = 0, *chunks_seen = 0, *failed = false;
     bool last = false;
     for (int c = 0; !last; c++) {
-        SeqSlot* s = rd.wait_ready(c);
+        ChunkSlot* s = rd.wait_ready(c);
         if (!s) {
             *failed = true;
             break;
@@ -80,7 +82,7 @@ static std::string stream_file(const std::string& path, const std::string& text,
         std::string* dst = &parts.back();
         const char* src = s->buf;
         const size_t bytes = s->bytes;
-        *pairs_seen += s->pairs, *chunks_seen += 1;
+        *pairs_seen += s->units, *chunks_seen += 1;
         /* the slot's previous copy (three chunks ago) was awaited by the reader before it refilled the buffer */
         copy[c % 3] = std::async(std::launch::async, [dst, src, bytes] { dst->assign(src, bytes); });
         rd.consumed(c, true);
@@ -103,6 +105,203 @@ static std::string first_pairs(const std::string& text, int64_t pairs) { /* the 
         pos = nl + 1;
     }
     return text.substr(0, pos);
+}
+
+static void write_file(const std::string& path, const std::string& text) {
+    FILE* f = fopen(path.c_str(), "wb");
+    fwrite(text.data(), 1, text.size(), f);
+    fclose(f);
+}
+
+/* n four-line records; lengths vary, record `big` (if any) has a sequence of big_len bases */
+static std::string make_fastq(int n, const char* eol = "\n", int big = -1, int big_len = 0) {
+    std::string text;
+    for (int i = 0; i < n; i++) {
+        const size_t len = i == big ? (size_t)big_len : (size_t)(30 + (i * 37) % 120);
+        text += "@read" + std::to_string(i) + eol + std::string(len, "ACGT"[i & 3]) + eol + "+" + eol + std::string(len, (char)('!' + i % 40)) + eol;
+    }
+    return text;
+}
+
+/* the plain line splitter the FASTQ reader is compared with: whole records of four lines, and the lines behind the last one */
+static std::string fastq_whole_records(const std::string& text, int64_t* records, int64_t* extra_lines) {
+    std::vector<size_t> ends; /* one past every line (a last line without its newline gets one) */
+    for (size_t pos = 0; pos < text.size();) {
+        const size_t nl = text.find('\n', pos);
+        pos = nl == std::string::npos ? text.size() : nl + 1;
+        ends.push_back(pos);
+    }
+    *records = (int64_t)ends.size() / 4, *extra_lines = (int64_t)ends.size() % 4;
+    std::string out = text.substr(0, *records ? ends[(size_t)(4 * *records) - 1] : 0);
+    if (*records && *extra_lines == 0 && text.back() != '\n') out += '\n';
+    return out;
+}
+
+struct FastqRun {
+    std::string bytes;
+    int64_t records = 0, extra_lines = 0;
+    int chunks = 0, grown = 0;
+    bool failed = false, extra_before_last = false;
+};
+
+/* Streams `text` through ChunkReader<FastqFill>, slots of chunk + slack bytes that grow on demand (unless !may_grow); stop_at >= 0:
+ * takes that many chunks, lets the reader fill every slot, and stops it */
+static FastqRun stream_fastq(const std::string& path, const std::string& text, size_t chunk, size_t first_chunk, size_t slack,
+                             bool may_grow = true, int stop_at = -1) {
+    write_file(path, text);
+    const int fd = open(path.c_str(), O_RDONLY);
+    FastqRun r;
+    std::vector<std::vector<char>> bufs(3, std::vector<char>(chunk + slack + 64));
+    std::future<void> copy[3];
+    ChunkReader<FastqFill> rd(
+        chunk, first_chunk,
+        [&](int q) {
+            if (copy[q].valid()) copy[q].wait();
+        },
+        fd, text.size(), chunk,
+        [&](int q, size_t cap, size_t keep) { /* the reader has waited for the slot's copy before it fills it */
+            if (!may_grow) return false;
+            std::vector<char> bigger(cap + 64);
+            if (keep) memcpy(bigger.data(), bufs[(size_t)q].data(), keep);
+            bufs[(size_t)q].swap(bigger);
+            rd.slot[q].buf = bufs[(size_t)q].data(), rd.slot[q].cap = cap;
+            r.grown++;
+            return true;
+        });
+    for (int q = 0; q < 3; q++) rd.slot[q].buf = bufs[(size_t)q].data(), rd.slot[q].cap = chunk + slack;
+    rd.start();
+    std::deque<std::string> parts;
+    bool last = false;
+    for (int c = 0; !last && c != stop_at; c++) {
+        ChunkSlot* s = rd.wait_ready(c);
+        if (!s) {
+            r.failed = true;
+            break;
+        }
+        last = s->last;
+        if (!last && s->extra_lines) r.extra_before_last = true;
+        r.records += s->units, r.extra_lines += s->extra_lines, r.chunks++;
+        parts.emplace_back();
+        std::string* dst = &parts.back();
+        const char* src = s->buf;
+        const size_t bytes = s->bytes;
+        copy[c % 3] = std::async(std::launch::async, [dst, src, bytes] { dst->assign(src, bytes); });
+        rd.consumed(c, true);
+        if (c % 2) std::this_thread::yield();
+    }
+    if (stop_at >= 0) std::this_thread::sleep_for(std::chrono::milliseconds(20)); /* the reader fills what is free and blocks */
+    rd.stop();
+    for (auto& fu : copy)
+        if (fu.valid()) fu.wait();
+    close(fd);
+    for (const std::string& p : parts) r.bytes += p;
+    return r;
+}
+
+static void expect_fastq(const char* what, const FastqRun& r, const std::string& text) {
+    int64_t records = 0, extra = 0;
+    const std::string want = fastq_whole_records(text, &records, &extra);
+    EXPECT(!r.failed, "%s: stream failed", what);
+    EXPECT(r.records == records && r.extra_lines == extra && !r.extra_before_last, "%s: %lld records + %lld lines, want %lld + %lld", what,
+           (long long)r.records, (long long)r.extra_lines, (long long)records, (long long)extra);
+    EXPECT(r.bytes == want, "%s: bytes differ (%zu against %zu)", what, r.bytes.size(), want.size());
+}
+
+static void check_fastq_reader(const std::string& path) {
+    const std::string text = make_fastq(3000);
+    FastqRun flat, ramp;
+    for (size_t chunk : {(size_t)600, (size_t)4096, (size_t)65536, (size_t)1 << 20}) {
+        flat = stream_fastq(path, text, chunk, 0, chunk / 4 + 4096);
+        expect_fastq("flat chunks", flat, text);
+        ramp = stream_fastq(path, text, chunk, chunk / 8, chunk / 4 + 4096);
+        expect_fastq("ramped chunks", ramp, text);
+        EXPECT(chunk >= text.size() || ramp.chunks > flat.chunks, "chunk %zu: ramp %d chunks against %d", chunk, ramp.chunks, flat.chunks);
+    }
+    expect_fastq("CRLF", stream_fastq(path, make_fastq(500, "\r\n"), 5000, 0, 4096), make_fastq(500, "\r\n"));
+    expect_fastq("missing final newline", stream_fastq(path, text.substr(0, text.size() - 1), 30000, 0, 4096), text.substr(0, text.size() - 1));
+    for (int extra = 1; extra <= 3; extra++) { /* a truncated last record: its first `extra` lines are there */
+        std::string cut = make_fastq(200);
+        const std::string more = make_fastq(1);
+        size_t pos = 0;
+        for (int l = 0; l < extra; l++) pos = more.find('\n', pos) + 1;
+        cut += more.substr(0, pos);
+        const FastqRun r = stream_fastq(path, cut, 3000, 0, 4096);
+        expect_fastq("truncated record", r, cut);
+        EXPECT(r.extra_lines == extra, "truncated record: %lld extra lines, want %d", (long long)r.extra_lines, extra);
+    }
+    {   /* a record longer than the chunk and the slot: the chunk takes more bytes and the slot grows; a grow that refuses fails */
+        const std::string big = make_fastq(40, "\n", 17, 20000);
+        FastqRun r = stream_fastq(path, big, 1024, 0, 64);
+        expect_fastq("long record", r, big);
+        EXPECT(r.grown > 0, "long record: the slot did not grow");
+        r = stream_fastq(path, big, 1024, 0, 64, false);
+        EXPECT(r.failed, "a grow that refuses must fail the stream");
+    }
+    {   /* an empty file is one last, empty chunk */
+        const FastqRun r = stream_fastq(path, "", 4096, 0, 4096);
+        EXPECT(!r.failed && r.chunks == 1 && r.records == 0 && r.extra_lines == 0 && r.bytes.empty(), "empty file: %d chunks", r.chunks);
+    }
+    {   /* stop() while every slot is full and the reader waits for one */
+        const FastqRun r = stream_fastq(path, text, 2000, 0, 4096, true, 2);
+        EXPECT(!r.failed && r.chunks == 2 && r.bytes == text.substr(0, r.bytes.size()), "early stop: %d chunks", r.chunks);
+    }
+}
+
+static void check_chunk_writer(const std::string& path) {
+    {   /* bytes arrive in push order through three rotating slots, whatever `before` takes; wait_idle waits for the job */
+        FILE* f = fopen(path.c_str(), "wb");
+        std::atomic<int> befores{0};
+        std::string bufs[3], want;
+        {
+            ChunkWriter w(f, [&](int o) {
+                std::this_thread::sleep_for(std::chrono::milliseconds(o + 1));
+                befores++;
+                return true;
+            });
+            for (int i = 0; i < 40; i++) {
+                const int o = i % 3;
+                w.wait_idle(o); /* the job that used the buffer three jobs ago is written */
+                EXPECT(befores >= i - 2, "wait_idle returned before job %d was written", i - 3);
+                bufs[o] = "chunk " + std::to_string(i) + std::string((size_t)(i * 97 % 5000), (char)('a' + i % 26)) + "\n";
+                want += bufs[o];
+                w.push(o, bufs[o].data(), i == 7 ? 0 : bufs[o].size()); /* an empty job still goes through before() */
+                if (i == 7) want.resize(want.size() - bufs[o].size());
+            }
+            w.wait_idle(0), w.wait_idle(1), w.wait_idle(2);
+            EXPECT(befores == 40 && !w.failed(), "writer: %d jobs went through", befores.load());
+            EXPECT(w.finish(), "writer: finish");
+        }
+        fclose(f);
+        std::string got;
+        f = fopen(path.c_str(), "rb");
+        char block[4096];
+        for (size_t k; (k = fread(block, 1, sizeof block, f)) > 0;) got.append(block, k);
+        fclose(f);
+        EXPECT(got == want, "writer: file differs (%zu bytes against %zu)", got.size(), want.size());
+    }
+    {   /* a failing before(): the job is dropped, the slot is given back, finish() says so */
+        FILE* f = fopen(path.c_str(), "wb");
+        ChunkWriter w(f, [](int o) { return o != 1; });
+        const std::string text = "some bytes\n";
+        for (int o = 0; o < 3; o++) w.push(o, text.data(), text.size());
+        for (int o = 0; o < 3; o++) w.wait_idle(o);
+        EXPECT(w.failed(), "writer: a failing before() went unnoticed");
+        EXPECT(!w.finish(), "writer: finish() after a failing before()");
+        fclose(f);
+    }
+    {   /* a file whose writes fail (unbuffered, so that fwrite itself reports it) */
+        FILE* f = fopen("/dev/full", "wb");
+        if (!f) f = fopen(path.c_str(), "rb"); /* no such device here: a stream that is not open for writing */
+        setvbuf(f, nullptr, _IONBF, 0);
+        ChunkWriter w(f, [](int) { return true; });
+        const std::string text(10000, 'x');
+        for (int i = 0; i < 5; i++) {
+            w.wait_idle(i % 3);
+            w.push(i % 3, text.data(), text.size());
+        }
+        EXPECT(!w.finish() && w.failed(), "writer: failing writes went unnoticed");
+        fclose(f);
+    }
 }
 
 int main(int argc, char** argv) {
@@ -168,6 +367,8 @@ int main(int argc, char** argv) {
         got = stream_file(path, text, 256, 2, 0, &pairs, &chunks, &failed, 16);
         EXPECT(failed, "a chunk smaller than one pair must fail");
     }
+    check_fastq_reader(path);
+    check_chunk_writer(path);
     {   /* stale-tail state: advancing over a + b untouched pairs = advancing over a, then b; a write lands where its slot goes */
         std::string err;
         uint8_t none[256], st1[256], st2[256];

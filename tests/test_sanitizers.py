@@ -3,8 +3,9 @@ target pool, so this is the CPU side only).  `make -C oracle asan` builds
   * the oracle and the host build of the fast Greedy pass under AddressSanitizer + UndefinedBehaviorSanitizer — the golden-vector
     suite and the host-check suite then run on those builds in a child interpreter (libasan preloaded), and
   * host/asm_host_check.cpp — the device-free host side of the C ABI (csrc/asm_host.h, the very code the product library compiles:
-    generator loop, tail-state arithmetic, CIGAR formatter, the reader pool and three-slot hand-over of asm_stream_seq_file) — once
-    under AddressSanitizer + UBSan and once under ThreadSanitizer.
+    generator loop, tail-state arithmetic, CIGAR formatter, the three-slot hand-over of the streamed-file calls (ChunkReader) with
+    both fill policies — asm_stream_seq_file's reader pool (PairsFill) and asm_map_file's FASTQ cutter (FastqFill) — and
+    asm_map_file's writer thread (ChunkWriter)) — once under AddressSanitizer + UBSan and once under ThreadSanitizer.
 Any sanitizer report fails the test, except reports whose frames lie in the reference's own sources (/root/reference: e.g. its
 generator prints an unterminated buffer with %s, benchmark_dataset.h:229,234 — not ours to fix)."""
 import os
