@@ -618,8 +618,8 @@ class Engine:
         """asm_map_reads_all: every locus within max_errors (docs/design/mapper.md, "All hits").  strata=None means max_errors
         (all loci).  -> dict: per read `n_hits` (uncapped), `n_reported` and `read_flags` (the rank-0 record's flags, also for an
         unmapped read: TOO_SHORT, SEED_CAPPED); flat per-hit arrays in read-then-rank order: read,
-        rank, seq_id, pos, end, dist, strand, flags, greedy_cost, mapq (min(254, 60 + greedy_cost)), and `cigar`, a list of CIGAR
-        strings.  chunk: reads per library call (None: all in one)."""
+        rank, seq_id, pos, end, dist, strand, flags, greedy_cost, mapq (min(254, 60 + greedy_cost)), `cigar`, a list of CIGAR
+        strings, and cigar_nops (the uncapped number of operations).  chunk: reads per library call (None: all in one)."""
         parts = [_as_bytes(r) for r in reads]
         n = len(parts)
         strata = int(max_errors) if strata is None else int(strata)
@@ -639,6 +639,7 @@ class Engine:
         out.update({name: flat[name].copy() for name in MAP_HIT_DTYPE.names})
         out["mapq"] = np.minimum(254, 60 + flat["greedy_cost"].astype(np.int64)).astype(np.int32)
         out["cigar"] = self._cigars(ops[read, rank], nops[read, rank], cigar_cap)
+        out["cigar_nops"] = nops[read, rank]
         return out
 
     def map_file(self, index: Index, names, fastq_path: str, sam_path: str, max_errors: int, both_strands: bool = True,
