@@ -85,6 +85,8 @@ struct asm_handle {
     bool wave_kernels = true;             /* wave-per-pair kernels for 6 <= k <= 31 (ASM_WAVE=0: workgroup-per-pair LDS kernels) */
     bool nw_bylen = true;                 /* unit-cost NW on mixed-length batches: workgroup-local sort by length (ASM_NW_BYLEN=0) */
     bool nw_banded = true;                /* banded bit-parallel NW with in-kernel full-height recompute (ASM_NW_BANDED=0) */
+    bool nw_pair2 = true;                 /* unit-cost NW on one-granule batches in input order: two pairs per thread in 16-row windows
+                                             (ASM_NW_PAIR2=0: one pair per thread in a 32-row window) */
     bool nw_wfa = true;                   /* affine NW: banded wavefront first, full matrix for the rest (ASM_NW_WFA=0: full matrix only) */
     int64_t map_cand_cap = (int64_t)1 << 24; /* asm_map_reads: verification candidates per round (ASM_MAP_CAND_CAP) */
     int64_t map_chunk = (int64_t)1 << 18;    /* asm_map_reads: reads per device chunk (ASM_MAP_CHUNK) */
@@ -730,6 +732,7 @@ int asm_create(asm_handle** out, int device) {
     if ((env = getenv("ASM_POOL"))) h->pooling = env[0] != '0';            /* 0: plain hipMalloc / hipFree */
     if ((env = getenv("ASM_NW_BANDED"))) h->nw_banded = env[0] != '0';     /* 0: full-height bit-parallel NW */
     if ((env = getenv("ASM_NW_BYLEN"))) h->nw_bylen = env[0] != '0';       /* 0: mixed-length NW without the length sort */
+    if ((env = getenv("ASM_NW_PAIR2"))) h->nw_pair2 = env[0] != '0';       /* 0: one-granule NW with one pair per thread */
     if ((env = getenv("ASM_NW_WFA"))) h->nw_wfa = env[0] != '0';           /* 0: affine NW by the full matrix only */
     if ((env = getenv("ASM_GREEDY_FAST"))) h->greedy_fast = env[0] != '0'; /* 0: FP64 Greedy kernel at k <= 3 */
     if ((env = getenv("ASM_MAP_CAND_CAP")) && atoll(env) > 0) h->map_cand_cap = atoll(env); /* smaller: more seeding rounds */
@@ -1423,6 +1426,9 @@ static int align_bucket(asm_handle* h, const asm_bucket& b, int aligner, const a
                     hipLaunchKernelGGL((nw_banded_kernel<12, 64, true>), g, t, 0, h->stream, planes, lens, n, b.w4, out);
                 else
                     hipLaunchKernelGGL((nw_banded_kernel<16, 64, true>), g, t, 0, h->stream, planes, lens, n, b.w4, out);
+            } else if (b.w4 == 1 && h->nw_pair2) {
+                const dim3 g2((unsigned)((b.n + 2 * ASM_BLOCK - 1) / (2 * ASM_BLOCK)));
+                hipLaunchKernelGGL(nw_banded2_kernel<4>, g2, t, 0, h->stream, planes, lens, n, b.w4, out);
             } else if (b.w4 == 1)
                 hipLaunchKernelGGL((nw_banded_kernel<4, 32, false>), g, t, 0, h->stream, planes, lens, n, b.w4, out);
             else if (b.w4 == 2)

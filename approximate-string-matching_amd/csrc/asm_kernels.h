@@ -19,6 +19,7 @@
 
 #include "asm_bits.h"
 #include "asm_gen.h"
+#include "asm_nwband.h"
 
 #define ASM_BLOCK 256
 
@@ -1117,177 +1118,7 @@ __global__ __launch_bounds__(ASM_BLOCK) void nw_unit_kernel(const uint4* __restr
     out.put(i, nw_unit_full<W64>(A0, A1, B0, B1, m, nn));
 }
 
-// --------------------------------------------------------------------------------------------------------
-// NW for unit penalties, BANDED: the same bit-parallel recurrence restricted to a 32-row window that slides down
-// the main diagonal one row per column (rows j-15 .. j+16 of column j), so a column costs ~30 VALU instructions on
-// one dword instead of ~25 per 32 rows of the full height.  Cells outside the band are taken as "one more than
-// their in-band neighbour" (vertical delta +1 for the row entering at the bottom, horizontal delta +1 for the row
-// leaving at the top), which makes every in-band value an upper bound of the true DP value and exact whenever an
-// optimal path stays inside the band.  Hence: a banded result r <= 15 IS the edit distance (then d <= r <= 15 and
-// every optimal path has |i-j| <= d); any other outcome (r > 15, or the end cell outside the band) is recomputed
-// by the full-height sweep in the same kernel.  At the benchmark's error rates no pair needs the recompute.
-// Rows beyond the read's end hold arbitrary plane bits: they only feed cells below row m, never D[m][n].
-// --------------------------------------------------------------------------------------------------------
-// The window is W = 32 or 64 rows tall (one dword / one 64-bit pair per vector): rows j-W/2+1 .. j+W/2 of column j,
-// proven exact for results up to W/2 - 1.  A kernel tries the narrow window first where the batch is short, then the
-// 64-row window, then the full-height sweep.
-template <int W>
-struct BandWord;
-template <>
-struct BandWord<32> {
-    typedef uint32_t T;
-};
-template <>
-struct BandWord<64> {
-    typedef u64 T;
-};
-
-struct NoColumnSink {
-    static constexpr bool kNeedsColumns = false;
-    template <typename WT>
-    ASM_DEV void operator()(int, WT, WT) const {}
-};
-
-// `sink(j, VP, VN)` sees the vertical delta vectors of every finished column j (1-based, in that column's window
-// coordinates); the traceback of asm_cover.h stores them.
-// all-ones / all-zeros word from bit r of the text block (one v_bfe_i32 for the 32-bit window)
-template <int W>
-ASM_DEV typename BandWord<W>::T band_text_bit(typename BandWord<W>::T b, int r);
-template <>
-ASM_DEV uint32_t band_text_bit<32>(uint32_t b, int r) {
-    return (uint32_t)__builtin_amdgcn_sbfe((int)b, r, 1);
-}
-template <>
-ASM_DEV u64 band_text_bit<64>(u64 b, int r) {
-    return 0ull - ((b >> r) & 1ull);
-}
-
-template <int ND, int W, typename Sink = NoColumnSink> /* ND = plane dwords per string (4 * w4); A arrays carry two zero dwords of padding */
-ASM_DEV int nw_band(const uint32_t (&A0)[ND + 2], const uint32_t (&A1)[ND + 2], const uint32_t (&B0)[ND],
-                    const uint32_t (&B1)[ND], int m, int nn, const Sink& sink = Sink()) {
-    typedef typename BandWord<W>::T WT;
-    constexpr int C = W / 2;          /* window top row of column j is max(1, j - C + 1) */
-    constexpr int NBLK = ND * 32 / W; /* W-column blocks */
-    constexpr WT TOP = (WT)1 << (W - 1);
-#define BLK(ARR, q) (W == 32 ? (WT)ARR[(q)] : (WT)((u64)ARR[2 * (q)] | ((u64)ARR[2 * (q) + 1] << 32)))
-    WT VP = ~(WT)0, VN = 0; /* column 0: D[i][0] = i */
-    int S = W;              /* D[bottom row of the window][column] */
-    WT lo0 = BLK(A0, 0), lo1 = BLK(A1, 0), hi0 = 0, hi1 = 0;
-
-#define NW_BAND_COLUMN(SLIDE, BW0, BW1, R)                                                           \
-    {                                                                                                 \
-        if (SLIDE) {                                                                                  \
-            lo0 = (lo0 >> 1) | (hi0 << (W - 1)), hi0 >>= 1;                                           \
-            lo1 = (lo1 >> 1) | (hi1 << (W - 1)), hi1 >>= 1;                                           \
-            VP = (VP >> 1) | TOP, VN >>= 1;                                                           \
-        }                                                                                             \
-        const WT T0 = (WT)0 - (((BW0) >> (R)) & (WT)1);                                               \
-        const WT T1 = (WT)0 - (((BW1) >> (R)) & (WT)1);                                               \
-        const WT Eq = ~((lo0 ^ T0) | (lo1 ^ T1));                                                     \
-        const WT D0 = ((((Eq & VP) + VP) ^ VP) | Eq) | VN;                                            \
-        const WT HP = VN | ~(D0 | VP);                                                                \
-        const WT HN = VP & D0;                                                                        \
-        if (SLIDE)                                                                                    \
-            S += 1 - (int)(D0 >> (W - 1));                                                            \
-        else                                                                                          \
-            S += (int)(HP >> (W - 1)) - (int)(HN >> (W - 1));                                         \
-        const WT X = (HP << 1) | (WT)1;                                                               \
-        VP = (HN << 1) | ~(D0 | X);                                                                   \
-        VN = D0 & X;                                                                                  \
-    }
-
-    // columns 1..C: the window still sits on rows 1..W
-    {
-        const WT b0 = BLK(B0, 0), b1 = BLK(B1, 0);
-        const int c1 = nn < C ? nn : C;
-        for (int r = 0; r < c1; r++) {
-            NW_BAND_COLUMN(false, b0, b1, r)
-            sink(r + 1, VP, VN);
-        }
-    }
-    // columns C+1..n: slide one row per column; the reservoir's upper word is refilled every W slides.
-    if (Sink::kNeedsColumns) {
-        // plain form: every column's (VP, VN) in that column's own window coordinates, handed to the sink
-#pragma unroll
-        for (int bq = 0; bq < NBLK; bq++) {
-            const WT b0 = BLK(B0, bq), b1 = BLK(B1, bq);
-            const int r0 = bq == 0 ? C : 0;
-            int rend = nn - W * bq;
-            rend = rend > W ? W : rend;
-            for (int r = r0; r < rend; r++) {
-                if (r == C) hi0 = BLK(A0, bq + 1), hi1 = BLK(A1, bq + 1); /* wave-uniform */
-                NW_BAND_COLUMN(true, b0, b1, r)
-                sink(W * bq + r + 1, VP, VN);
-            }
-        }
-    } else if (nn > C) {
-        // Fused form (penalty only).  Algebraically the same recurrence: instead of producing a column's vertical deltas
-        // in its own window and shifting them for the next column, produce them directly in the NEXT column's window:
-        //   VPin' = HN | ~((D0 >> 1) | HP) | TOP ,  VNin' = HP & (D0 >> 1)
-        // (the "+1 for the row entering at the bottom" is the TOP bit; the "+1 above the window" is the zero shifted
-        // into D0 >> 1).  Three instructions fewer per column.  The bottom-row diagonal deltas are shifted into an
-        // accumulator and counted once per block instead of being added column by column.
-        WT VPin = (VP >> 1) | TOP, VNin = VN >> 1;
-#pragma unroll
-        for (int bq = 0; bq < NBLK; bq++) {
-            const WT b0 = BLK(B0, bq), b1 = BLK(B1, bq);
-            const int r0 = bq == 0 ? C : 0;
-            int rend = nn - W * bq;
-            rend = rend > W ? W : rend;
-            WT acc = 0;
-            // the block's columns in two runs: the pattern window of column 32*bq + r starts at row 32*bq + r - (C-1), i.e.
-            // in pattern word bq-1 for r < C-1 and in word bq from there on
-#pragma unroll
-            for (int half = 0; half < 2; half++) {
-                constexpr int CB = W == 32 ? C - 1 : C;
-                const int ra = half == 0 ? r0 : (r0 > CB ? r0 : CB);
-                const int rb = half == 0 ? (rend < CB ? rend : CB) : rend;
-                if (W != 32 && half == 1) hi0 = BLK(A0, bq + 1), hi1 = BLK(A1, bq + 1);
-                // W = 32: the window is cut straight out of two adjacent pattern words with one v_alignbit_b32 (wave-uniform
-                // shift), no sliding state to update
-                const uint32_t p0l = W == 32 ? (half == 0 ? (bq > 0 ? A0[bq > 0 ? bq - 1 : 0] : 0u) : A0[bq]) : 0u;
-                const uint32_t p0h = W == 32 ? (half == 0 ? A0[bq] : A0[bq + 1]) : 0u;
-                const uint32_t p1l = W == 32 ? (half == 0 ? (bq > 0 ? A1[bq > 0 ? bq - 1 : 0] : 0u) : A1[bq]) : 0u;
-                const uint32_t p1h = W == 32 ? (half == 0 ? A1[bq] : A1[bq + 1]) : 0u;
-                const int shb = half == 0 ? W - CB : -CB;
-                for (int r = ra; r < rb; r++) {
-                    if (W == 32) {
-                        lo0 = (WT)__builtin_amdgcn_alignbit(p0h, p0l, (uint32_t)(r + shb));
-                        lo1 = (WT)__builtin_amdgcn_alignbit(p1h, p1l, (uint32_t)(r + shb));
-                    } else {
-                        lo0 = (lo0 >> 1) | (hi0 << (W - 1)), hi0 >>= 1;
-                        lo1 = (lo1 >> 1) | (hi1 << (W - 1)), hi1 >>= 1;
-                    }
-                    const WT T0 = band_text_bit<W>(b0, r), T1 = band_text_bit<W>(b1, r);
-                    const WT Eq = ~((lo0 ^ T0) | (lo1 ^ T1));
-                    const WT D0 = ((((Eq & VPin) + VPin) ^ VPin) | Eq) | VNin;
-                    const WT HP = VNin | ~(D0 | VPin);
-                    const WT HN = VPin & D0;
-                    acc = (acc << 1) | (D0 >> (W - 1));
-                    const WT D0s = D0 >> 1;
-                    VPin = HN | ~(D0s | HP) | TOP;
-                    VNin = HP & D0s;
-                }
-            }
-            if (rend > r0) S += (rend - r0) - (W == 32 ? __popc((uint32_t)acc) : __popcll((u64)acc));
-        }
-        // back to the last column's own window: VP = VPin << 1 (its bit 0 is always 0); VN = VNin << 1 | D0[0] — only
-        // the bits above row m are needed below, and bit 0 never is
-        VP = VPin << 1;
-        VN = VNin << 1;
-    }
-#undef NW_BAND_COLUMN
-#undef BLK
-    const int top = nn > C - 1 ? nn - (C - 1) : 1; /* window top row of the last column */
-    const int bstar = m - top;                     /* bit of row m */
-    if (bstar < 0 || bstar > W - 1) return -1;
-    const WT above = bstar == W - 1 ? (WT)0 : (~(WT)0 << (bstar + 1));
-    const int up = W == 32 ? __popc((uint32_t)(VP & above)) : __popcll((u64)(VP & above));
-    const int dn = W == 32 ? __popc((uint32_t)(VN & above)) : __popcll((u64)(VN & above));
-    const int result = S - up + dn;
-    return result <= C - 1 ? result : -1; /* proven exact only up to W/2 - 1 */
-}
-
+// (the banded sweeps themselves, nw_band<> and nw_band2x16<>, are in asm_nwband.h, which also compiles for the host)
 template <int ND, int FIRSTW>
 ASM_DEV int nw_banded_pair(const uint4* __restrict__ planes, const uint32_t* __restrict__ lens, long n, int w4, long i) {
     const uint32_t ln = lens[i];
@@ -1386,6 +1217,44 @@ __global__ __launch_bounds__(ASM_BLOCK) void nw_banded_kernel(const uint4* __res
             const long i = base + s_sorted[rank];
             out.put(i, nw_banded_pair<ND, FIRSTW>(planes, lens, n, w4, i));
         }
+    }
+}
+
+// One-granule batches in input order (config C2): a workgroup of ASM_BLOCK threads owns 2 * ASM_BLOCK consecutive pairs and
+// thread t carries pairs base + t and base + ASM_BLOCK + t through ONE sweep, each in a 16-row window in its half of the
+// dword (nw_band2x16<>): loads and both stores stay coalesced.  A half the 16-row window does not prove, and the pair of a
+// thread that has no partner, goes through nw_banded_pair<ND, 32> — the cascade 32 rows -> 64 rows -> full height of
+// nw_banded_kernel, which reads the pair's planes again — so every pair gets exactly what nw_banded_kernel gives it.
+#define NW_PAIR2_MIN_WAVES 6 /* two pairs' planes are 32 dwords: keep the allocator at 80 VGPRs or fewer */
+template <int ND>
+__global__ __launch_bounds__(ASM_BLOCK, NW_PAIR2_MIN_WAVES) void nw_banded2_kernel(const uint4* __restrict__ planes,
+                                                                                   const uint32_t* __restrict__ lens, long n, int w4,
+                                                                                   OutMap out) {
+    const long ip = (long)blockIdx.x * (2 * ASM_BLOCK) + threadIdx.x, iq = ip + ASM_BLOCK;
+    if (ip >= n) return;
+    int rp = -1, rq = -1;
+    if (iq < n) {
+        const uint32_t lp = lens[ip], lq = lens[iq];
+        uint32_t P[4][ND], Q[4][ND]; /* planes A0, A1, B0, B1 */
+#pragma unroll
+        for (int pl = 0; pl < 4; pl++) {
+#pragma unroll
+            for (int g = 0; g < ND / 4; g++) {
+                const uint4 a = planes[((long)pl * w4 + g) * n + ip], b = planes[((long)pl * w4 + g) * n + iq];
+                P[pl][4 * g] = a.x, P[pl][4 * g + 1] = a.y, P[pl][4 * g + 2] = a.z, P[pl][4 * g + 3] = a.w;
+                Q[pl][4 * g] = b.x, Q[pl][4 * g + 1] = b.y, Q[pl][4 * g + 2] = b.z, Q[pl][4 * g + 3] = b.w;
+            }
+        }
+        nw_band2x16<ND>(P[0], P[1], P[2], P[3], (int)(lp & 0xffffu), (int)(lp >> 16), Q[0], Q[1], Q[2], Q[3], (int)(lq & 0xffffu),
+                        (int)(lq >> 16), rp, rq);
+    }
+#pragma unroll 1
+    for (int h = 0; h < 2; h++) { /* one copy of the cascade for both halves */
+        const long i = h ? iq : ip;
+        int r = h ? rq : rp;
+        if (i >= n) break;
+        if (r < 0) r = nw_banded_pair<ND, 32>(planes, lens, n, w4, i);
+        out.put(i, r);
     }
 }
 
