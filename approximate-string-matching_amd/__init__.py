@@ -106,6 +106,14 @@ class MapFileStats(ctypes.Structure):
                 ("seconds", ctypes.c_double), ("seconds_read", ctypes.c_double), ("seconds_write", ctypes.c_double)]
 
 
+class MapPairsFileStats(ctypes.Structure):
+    """asm_map_pairs_file_stats"""
+    _fields_ = [("pairs", ctypes.c_int64), ("proper", ctypes.c_int64), ("rescued", ctypes.c_int64), ("unsent", ctypes.c_int64),
+                ("records", ctypes.c_int64), ("chunks", ctypes.c_int64), ("bytes_in", ctypes.c_int64), ("bytes_out", ctypes.c_int64),
+                ("carry_peak", ctypes.c_int64), ("seconds", ctypes.c_double), ("seconds_read", ctypes.c_double),
+                ("seconds_write", ctypes.c_double)]
+
+
 class PairParams(ctypes.Structure):
     """asm_pair_params: projected span in [min_insert, max_insert] (0 <= min <= max <= 8192), mate rescue's error bound (-1 = off)."""
 
@@ -260,6 +268,9 @@ def load_library() -> ctypes.CDLL:
         "asm_map_file": (i32, [vp, vp, c.POINTER(c.c_char_p), c.c_char_p, c.c_char_p, c.c_char_p, c.POINTER(MapParams), i32, i32, i64,
                                c.POINTER(MapFileStats)]),
         "asm_fastq_cut": (c.c_size_t, [vp, c.c_size_t, c.POINTER(i64)]),
+        "asm_map_pairs_file": (i32, [vp, vp, c.POINTER(c.c_char_p), c.c_char_p, c.c_char_p, c.c_char_p, c.c_char_p, c.POINTER(MapParams),
+                                     c.POINTER(PairParams), i64, c.POINTER(MapPairsFileStats)]),
+        "asm_fastq_cut_n": (c.c_size_t, [vp, c.c_size_t, i64, c.POINTER(i64)]),
         "asm_device_malloc": (i32, [vp, c.c_size_t, c.POINTER(vp)]),
         "asm_device_free": (i32, [vp, vp]),
         "asm_memcpy_d2h": (i32, [vp, vp, vp, c.c_size_t]),
@@ -660,6 +671,26 @@ class Engine:
                                         None if header is None else _as_bytes(header), ctypes.byref(p), int(max_hits), strata,
                                         int(chunk_bytes), ctypes.byref(st)))
         return {name: getattr(st, name) for name, _ in MapFileStats._fields_}
+
+    def map_pairs_file(self, index: Index, names, fastq1_path: str, fastq2_path: str, sam_path: str, max_errors: int, min_insert: int,
+                       max_insert: int, rescue_errors: int = -1, max_occ: int = 0, greedy_k: int = 3, chunk_bytes: int = 0,
+                       header: Optional[str] = None) -> dict:
+        """asm_map_pairs_file: two four-line FASTQ files in (record i of each: the mates of pair i), a paired SAM file out, parsed,
+        paired, mapped and formatted on the device (docs/design/mapper.md, "Files: two FASTQ files in, paired SAM out"); the answer
+        is map_pairs'.  names: one RNAME per sequence of the index.  header is written first, as it is.  -> the stats as a dict:
+        pairs, proper, rescued, unsent, records (SAM lines), chunks, bytes_in, bytes_out, carry_peak, seconds, seconds_read,
+        seconds_write."""
+        names = [_as_bytes(nm) for nm in names]
+        if len(names) != len(index.lengths):
+            raise ValueError("names must hold one name per sequence of the index")
+        arr = (ctypes.c_char_p * max(len(names), 1))(*names)
+        p = MapParams(int(max_errors), 1, int(max_occ), int(greedy_k))
+        pp = PairParams(int(min_insert), int(max_insert), int(rescue_errors))
+        st = MapPairsFileStats()
+        self._chk(self.lib.asm_map_pairs_file(self.h, index.ptr, arr, os.fsencode(fastq1_path), os.fsencode(fastq2_path),
+                                              os.fsencode(sam_path), None if header is None else _as_bytes(header), ctypes.byref(p),
+                                              ctypes.byref(pp), int(chunk_bytes), ctypes.byref(st)))
+        return {name: getattr(st, name) for name, _ in MapPairsFileStats._fields_}
 
     def map_pairs(self, index: Index, reads1, reads2, max_errors: int, min_insert: int, max_insert: int, rescue_errors: int = -1,
                   max_occ: int = 0, greedy_k: int = 3, cigar_cap: int = 64, chunk: Optional[int] = None):

@@ -2276,6 +2276,8 @@ int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, in
 #include "asm_map_host.h"
 /* asm_map_file: FASTQ in, SAM out, through the same stages */
 #include "asm_map_file.h"
+/* asm_map_pairs_file: two FASTQ files in, paired SAM out */
+#include "asm_map_pairs_file.h"
 
 /* ---------------------------------------------------------------------------------------------------- */
 int asm_device_malloc(asm_handle* h, size_t bytes, void** d_ptr) {

@@ -6,6 +6,11 @@
 //   (exclusive scans over the sent flags and the sent lengths)
 //   fastq_compact_kernel  the sent records numbered as library reads: read offsets and source positions
 //   seq_gather_kernel     (asm_ingest.h) the reads' bytes, one wave per read
+// Two files in step (asm_map_pairs_file): the chunk holds the mate-1 records and then as many mate-2 records, fastq_record_kernel
+// runs over each half, and
+//   fastq_pair_kernel          one thread per pair: sent when both mates are, the two QNAMEs compared without /1 and /2
+//   (exclusive scans over the sent flags and over each mate's sent lengths)
+//   fastq_pair_compact_kernel  mate 1 of sent pair q = library read q, mate 2 = read ns + q: read offsets and source positions
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -72,4 +77,56 @@ __global__ __launch_bounds__(256) void fastq_compact_kernel(const SamRec* __rest
     const bool sent = send[i] != 0u;
     rec_read[i] = sent ? (int32_t)rd[i] : -1;
     if (sent) roff[rd[i]] = mo[i], start[rd[i]] = recs[i].seq;
+}
+
+struct FastqPairCounts {
+    uint32_t name_min; /* smallest pair of the range whose mates' names differ, FASTQ_NO_RECORD: none */
+    uint32_t unsent;   /* pairs with an empty or too long mate */
+};
+
+/* pairs [0, n) of a device chunk: recs = [2][n] (mate 1 of every pair, then mate 2), send1 / send2 and mlen1 / mlen2 what
+ * fastq_record_kernel left for the two halves (n + 1 entries each).  psend, len1 and len2 get n + 1 entries, the last 0. */
+__global__ __launch_bounds__(256) void fastq_pair_kernel(const char* __restrict__ raw, const SamRec* __restrict__ recs, long n,
+                                                         const uint32_t* __restrict__ send1, const uint32_t* __restrict__ send2,
+                                                         const uint32_t* __restrict__ mlen1, const uint32_t* __restrict__ mlen2,
+                                                         uint32_t* __restrict__ psend, uint32_t* __restrict__ len1,
+                                                         uint32_t* __restrict__ len2, FastqPairCounts* __restrict__ counts) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool unsent = false;
+    if (i == n) psend[n] = 0u, len1[n] = 0u, len2[n] = 0u;
+    if (i < n) {
+        const SamRec a = recs[i], b = recs[n + i];
+        const bool sent = send1[i] != 0u && send2[i] != 0u;
+        psend[i] = sent ? 1u : 0u;
+        len1[i] = sent ? mlen1[i] : 0u;
+        len2[i] = sent ? mlen2[i] : 0u;
+        unsent = !sent;
+        const uint32_t la = sam_pair_name_len(raw, a), lb = sam_pair_name_len(raw, b);
+        bool same = la == lb;
+        for (uint32_t t = 0; same && t < la; t++) same = raw[a.name + t] == raw[b.name + t];
+        if (!same) atomicMin(&counts->name_min, (uint32_t)i);
+    }
+    const unsigned long long um = __ballot(unsent);
+    if ((threadIdx.x & 63) == 0 && um) atomicAdd(&counts->unsent, (uint32_t)__popcll(um));
+}
+
+/* rd = exclusive scan of psend, mo1 / mo2 = exclusive scans of len1 / len2 (n + 1 entries each; entry n = the totals): the reads of
+ * the chunk's ns sent pairs in map_pairs_front's layout, the mates 1 and then the mates 2 */
+__global__ __launch_bounds__(256) void fastq_pair_compact_kernel(const SamRec* __restrict__ recs, const uint32_t* __restrict__ psend,
+                                                                 const uint32_t* __restrict__ rd, const uint32_t* __restrict__ mo1,
+                                                                 const uint32_t* __restrict__ mo2, long n, int32_t* __restrict__ rec_read,
+                                                                 uint32_t* __restrict__ roff, unsigned long long* __restrict__ start) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    const uint32_t ns = rd[n], bytes1 = mo1[n];
+    if (i == n) {
+        roff[2u * ns] = bytes1 + mo2[n];
+        return;
+    }
+    const bool sent = psend[i] != 0u;
+    rec_read[i] = sent ? (int32_t)rd[i] : -1;
+    if (sent) {
+        roff[rd[i]] = mo1[i], start[rd[i]] = recs[i].seq;
+        roff[ns + rd[i]] = bytes1 + mo2[i], start[ns + rd[i]] = recs[n + i].seq;
+    }
 }

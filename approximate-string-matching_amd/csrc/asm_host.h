@@ -2,8 +2,8 @@
 // the seeded generator's host loop (asm_generate_pairs), the stale-tail state arithmetic (asm_tail_state_advance), the CIGAR
 // formatter (asm_cigar_format), and the host threads of the two streamed-file calls: the three-slot hand-over between a reader
 // thread and the caller's thread (ChunkReader) with its two fill policies — asm_stream_seq_file's newline scanning over the
-// persistent reader pool (PairsFill) and asm_map_file's FASTQ chunk cutter (asm_fastq_cut, FastqFill) — and the SAM writer
-// (ChunkWriter).
+// persistent reader pool (PairsFill) and asm_map_file's FASTQ chunk cutter (asm_fastq_cut, FastqFill) and asm_map_pairs_file's two
+// files in step (asm_fastq_cut_n, FastqPairFill) — and the SAM writer (ChunkWriter).
 //
 // Kept in a header without any HIP include so that the SAME code is compiled twice: into the product by hipcc (asm_capi.hip),
 // and by plain g++ under -fsanitize=thread / address,undefined into host/asm_host_check.cpp (`make -C oracle asan`,
@@ -304,6 +304,7 @@ struct ChunkSlot { /* one (pinned) host buffer */
     char* buf = nullptr;
     size_t cap = 0;          /* usable bytes */
     size_t bytes = 0;        /* raw bytes to ship: whole units only */
+    size_t bytes1 = 0;       /* two files in step: the bytes of file 1's records, in front of file 2's */
     int64_t units = 0;       /* pairs, or FASTQ records */
     int64_t extra_lines = 0; /* FASTQ, last chunk: lines behind the last whole record (a truncated record) */
     bool last = false;
@@ -312,7 +313,7 @@ struct ChunkSlot { /* one (pinned) host buffer */
 };
 
 struct ChunkCut { /* what a fill policy reports: buf[0, have) is there, buf[0, boundary) are `units` whole units */
-    size_t have = 0, boundary = 0;
+    size_t have = 0, boundary = 0, bytes1 = 0;
     int64_t units = 0, extra_lines = 0;
     bool eof = false;
 };
@@ -359,7 +360,7 @@ class ChunkReader {
             if (!ok) failed_ = true;
             {
                 std::lock_guard<std::mutex> lk(mu_);
-                s.bytes = cut.boundary, s.units = cut.units, s.extra_lines = cut.extra_lines, s.last = cut.eof, s.ready = true;
+                s.bytes = cut.boundary, s.bytes1 = cut.bytes1, s.units = cut.units, s.extra_lines = cut.extra_lines, s.last = cut.eof, s.ready = true;
             }
             cv_.notify_all();
             if (!ok || cut.eof) return;
@@ -406,6 +407,7 @@ public:
     }
     bool failed() const { return failed_.load(); }
     double read_seconds() const { return read_seconds_; } /* after stop() */
+    const Fill& policy() const { return fill_; }          /* what the policy keeps for its caller: after the last chunk or stop() */
 };
 
 /* asm_stream_seq_file's policy: `want` more file bytes through the reader pool (reads stop at cap - 8), cut behind the last
@@ -477,6 +479,22 @@ inline size_t fastq_cut(const char* buf, size_t nbytes, int64_t* records, int64_
     return boundary;
 }
 
+/* the first max_records whole records of buf[0, nbytes), or all of them when there are fewer: their length and how many they are */
+inline size_t fastq_cut_n(const char* buf, size_t nbytes, int64_t max_records, int64_t* records) {
+    int64_t count = 0;
+    size_t boundary = 0;
+    const char* q = buf;
+    const char* end = buf + nbytes;
+    while (q < end && count < 4 * max_records) {
+        const char* hit = (const char*)memchr(q, '\n', (size_t)(end - q));
+        if (!hit) break;
+        q = hit + 1;
+        if ((++count & 3) == 0) boundary = (size_t)(q - buf);
+    }
+    if (records) *records = count / 4;
+    return boundary;
+}
+
 /* asm_map_file's policy: one pread loop, cut behind the last whole record (fastq_cut); when that leaves no record at all the chunk
  * takes `chunk` more bytes, and the slot grows through grow(slot, capacity, keep) (the owner of the buffers moves the first `keep`
  * bytes into a larger one and sets slot[q].buf and cap; false: out of memory).  extra_lines is reported with the last chunk, and
@@ -511,6 +529,83 @@ struct FastqFill {
         }
         cut.have = have, cut.extra_lines = cut.eof ? lines - 4 * cut.units : 0;
         return true;
+    }
+};
+
+/* asm_map_pairs_file's policy: two FASTQ files in step.  A slot holds [R whole records of file 1][R whole records of file 2] with
+ * the same R, bytes1 = the length of the first region; what a file has behind its R-th record stays in a carry of the policy's own
+ * (have == boundary: the reader's generic carry stays empty).  The chunk's `want` bytes are split between the files in proportion
+ * to what each has left (carry included), so the files reach their ends together and neither carry grows with the file:
+ * carry_peak = the largest sum of the two carries.  No pair in reach (a record longer than the chunk): `chunk` more bytes, the slot
+ * grows through grow().  The stream ends when both files are read, or when one of them is and holds no further record while the
+ * other does.  For the caller, after the last chunk: records[f] = the whole records seen of file f, extra_lines[f] = the lines
+ * behind the last one of a file read to its end (a truncated record), more[f] = file f holds records beyond the last pair. */
+struct FastqPairFill {
+    const int fd[2];
+    const size_t file_bytes[2], chunk;
+    const std::function<bool(int, size_t, size_t)> grow;
+    size_t file_off[2] = {0, 0};
+    std::vector<char> carry[2];
+    bool closed[2] = {false, false}; /* the file's last line has its newline */
+    int64_t records[2] = {0, 0}, extra_lines[2] = {0, 0};
+    bool more[2] = {false, false};
+    size_t carry_peak = 0;
+    FastqPairFill(int fd1, int fd2, size_t bytes1, size_t bytes2, size_t chunk_, std::function<bool(int, size_t, size_t)> grow_)
+        : fd{fd1, fd2}, file_bytes{bytes1, bytes2}, chunk(chunk_), grow(std::move(grow_)) {}
+
+    bool operator()(ChunkSlot& s, int q, const std::vector<char>&, size_t want, ChunkCut& cut) {
+        for (bool again = false;; again = true) {
+            /* how many bytes of each file the slot should hold */
+            const size_t left[2] = {file_bytes[0] - file_off[0], file_bytes[1] - file_off[1]};
+            const long double rest[2] = {(long double)(left[0] + carry[0].size()), (long double)(left[1] + carry[1].size())};
+            size_t take[2];
+            for (int f = 0; f < 2; f++) {
+                const size_t share = rest[0] + rest[1] > 0 ? (size_t)((long double)want * rest[f] / (rest[0] + rest[1])) : 0;
+                take[f] = again ? share + 1 : share > carry[f].size() ? share - carry[f].size() : 0; /* again: progress in both */
+                if (take[f] > left[f]) take[f] = left[f];
+            }
+            const size_t need = carry[0].size() + take[0] + carry[1].size() + take[1] + 16;
+            if (need > s.cap && !grow(q, need + need / 4, 0)) return false;
+            size_t at[2], have[2], cutat[2];
+            int64_t n[2], lines[2];
+            for (int f = 0; f < 2; f++) {
+                char* dst = s.buf + (f ? have[0] : 0);
+                at[f] = (size_t)(dst - s.buf), have[f] = carry[f].size();
+                if (have[f]) memcpy(dst, carry[f].data(), have[f]);
+                for (size_t a = 0; a < take[f];) {
+                    const ssize_t got = pread(fd[f], dst + have[f] + a, take[f] - a, (off_t)(file_off[f] + a));
+                    if (got <= 0) return false;
+                    a += (size_t)got;
+                }
+                file_off[f] += take[f], have[f] += take[f];
+                if (file_off[f] >= file_bytes[f] && !closed[f]) { /* a last line without its newline */
+                    if (have[f] && dst[have[f] - 1] != '\n') dst[have[f]++] = '\n';
+                    closed[f] = true;
+                }
+                cutat[f] = fastq_cut(dst, have[f], &n[f], &lines[f]);
+            }
+            const bool done[2] = {file_off[0] >= file_bytes[0], file_off[1] >= file_bytes[1]};
+            const int64_t R = n[0] < n[1] ? n[0] : n[1];
+            const bool dry[2] = {done[0] && n[0] == 0, done[1] && n[1] == 0}; /* the file holds no further record */
+            const bool eof = (done[0] && done[1]) || (dry[0] && n[1] > 0) || (dry[1] && n[0] > 0);
+            if (R == 0 && !eof) { /* no whole pair yet: keep everything and take more */
+                for (int f = 0; f < 2; f++) carry[f].assign(s.buf + at[f], s.buf + at[f] + have[f]);
+                want = chunk;
+                continue;
+            }
+            for (int f = 0; f < 2; f++)
+                if (n[f] > R) cutat[f] = fastq_cut_n(s.buf + at[f], have[f], R, nullptr);
+            if (eof)
+                for (int f = 0; f < 2; f++)
+                    records[f] += n[f], extra_lines[f] = done[f] ? lines[f] - 4 * n[f] : 0, more[f] = !done[f] || n[f] > R;
+            else
+                records[0] += R, records[1] += R;
+            for (int f = 0; f < 2; f++) carry[f].assign(s.buf + at[f] + cutat[f], s.buf + at[f] + have[f]);
+            if (!eof && carry[0].size() + carry[1].size() > carry_peak) carry_peak = carry[0].size() + carry[1].size();
+            if (cutat[1] && at[1] != cutat[0]) memmove(s.buf + cutat[0], s.buf + at[1], cutat[1]); /* file 2's records behind file 1's */
+            cut.have = cut.boundary = cutat[0] + cutat[1], cut.bytes1 = cutat[0], cut.units = R, cut.eof = eof;
+            return true;
+        }
     }
 };
 

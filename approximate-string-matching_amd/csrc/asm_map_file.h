@@ -21,7 +21,7 @@ struct MapFilePipe {
     char* d_out[3] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fmt[3] = {nullptr, nullptr, nullptr};    /* d_out[o] holds its SAM bytes */
     hipEvent_t ev_copied[3] = {nullptr, nullptr, nullptr}; /* pin_out[o] holds them */
-    explicit MapFilePipe(asm_handle* owner) : h(owner), in(owner, "asm_map_file") {}
+    explicit MapFilePipe(asm_handle* owner, const char* who = "asm_map_file") : h(owner), in(owner, who) {}
     hipError_t open_device(size_t slot_cap) {
         hipError_t e = in.open_device(slot_cap, false, true);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&s_out, hipStreamNonBlocking);
@@ -43,6 +43,39 @@ struct MapFilePipe {
         if (out) fclose(out);
     }
 };
+
+/* The output side of one device chunk, for both file calls: a's sizes and offsets are there and `total` is their sum.  Takes the
+ * next output slot of the rotation (the writer is done with the chunk that used it three chunks ago, so its copy out of d_out is
+ * over too), emits the nlines lines into it, starts the copy out on the copy-out stream and queues the write. */
+template <bool PAIRED>
+static int map_file_hand_over(MapFilePipe& pp, asm_host::ChunkWriter& writer, int64_t& out_seq, SamArgs& a, int64_t nlines,
+                              unsigned long long total) {
+    asm_handle* h = pp.h;
+    const char* who = pp.in.who;
+    const int o = (int)(out_seq % 3);
+    writer.wait_idle(o);
+    if (writer.failed()) return fail(h, ASM_EINVAL, std::string(who) + ": writing the SAM file failed");
+    pool_free(h, pp.d_out[o]);
+    pp.d_out[o] = nullptr;
+    if (pp.pin_out_cap[o] < total) {
+        if (pp.pin_out[o]) (void)hipHostFree(pp.pin_out[o]);
+        pp.pin_out[o] = nullptr, pp.pin_out_cap[o] = 0;
+        const size_t want = (size_t)total + (size_t)total / 4 + 4096;
+        STREAM_TRY(who, hipHostMalloc((void**)&pp.pin_out[o], want, hipHostMallocDefault));
+        pp.pin_out_cap[o] = want;
+    }
+    STREAM_TRY(who, pool_alloc(h, (void**)&pp.d_out[o], (size_t)total + 64));
+    a.out = pp.d_out[o];
+    hipLaunchKernelGGL(sam_emit_kernel<PAIRED>, dim3(map_grid((uint64_t)nlines * 64, h)), dim3(256), 0, h->stream, a);
+    STREAM_TRY(who, hipGetLastError());
+    STREAM_TRY(who, hipEventRecord(pp.ev_fmt[o], h->stream));
+    STREAM_TRY(who, hipStreamWaitEvent(pp.s_out, pp.ev_fmt[o], 0));
+    if (total) STREAM_TRY(who, hipMemcpyAsync(pp.pin_out[o], pp.d_out[o], (size_t)total, hipMemcpyDeviceToHost, pp.s_out));
+    STREAM_TRY(who, hipEventRecord(pp.ev_copied[o], pp.s_out));
+    writer.push(o, pp.pin_out[o], (size_t)total);
+    out_seq++;
+    return ASM_OK;
+}
 
 struct MapFileJob { /* what every chunk of a call shares */
     asm_handle* h;
@@ -151,37 +184,14 @@ static int map_file_chunk(MapFileJob& j, const char* d_raw, const uint32_t* d_nl
     MAP_FILE_TRY(hipGetLastError());
     MAP_FILE_TRY(map_exclusive_sum(h, tmp, d_lcnt.p, d_lbase.p, (int64_t)cnt));
     hipLaunchKernelGGL(sam_line_fill_kernel, dim3(grid_for(rn)), dim3(ASM_BLOCK), 0, h->stream, a, d_lrec.p, d_litem.p);
-    hipLaunchKernelGGL(sam_size_kernel, dim3(grid_for(nlines + 1)), dim3(ASM_BLOCK), 0, h->stream, a);
+    hipLaunchKernelGGL(sam_size_kernel<false>, dim3(grid_for(nlines + 1)), dim3(ASM_BLOCK), 0, h->stream, a);
     MAP_FILE_TRY(hipGetLastError());
     MAP_FILE_TRY(map_exclusive_sum(h, tmp, d_size.p, d_off.p, nlines + 1));
     unsigned long long total = 0, n_mapped = 0;
     MAP_FILE_TRY(hipMemcpyAsync(&total, d_off.p + nlines, sizeof(total), hipMemcpyDeviceToHost, h->stream));
     MAP_FILE_TRY(hipMemcpyAsync(&n_mapped, d_nmapped.p, sizeof(n_mapped), hipMemcpyDeviceToHost, h->stream));
     MAP_FILE_TRY(hipStreamSynchronize(h->stream));
-    /* the output slot: the writer is done with the chunk that used it three chunks ago, so its copy out of d_out is over too */
-    MapFilePipe& pp = *j.pipe;
-    const int o = (int)(j.out_seq % 3);
-    j.writer->wait_idle(o);
-    if (j.writer->failed()) return fail(h, ASM_EINVAL, "asm_map_file: writing the SAM file failed");
-    pool_free(h, pp.d_out[o]);
-    pp.d_out[o] = nullptr;
-    if (pp.pin_out_cap[o] < total) {
-        if (pp.pin_out[o]) (void)hipHostFree(pp.pin_out[o]);
-        pp.pin_out[o] = nullptr, pp.pin_out_cap[o] = 0;
-        const size_t want = (size_t)total + (size_t)total / 4 + 4096;
-        MAP_FILE_TRY(hipHostMalloc((void**)&pp.pin_out[o], want, hipHostMallocDefault));
-        pp.pin_out_cap[o] = want;
-    }
-    MAP_FILE_TRY(pool_alloc(h, (void**)&pp.d_out[o], (size_t)total + 64));
-    a.out = pp.d_out[o];
-    hipLaunchKernelGGL(sam_emit_kernel, dim3(map_grid((uint64_t)nlines * 64, h)), dim3(256), 0, h->stream, a);
-    MAP_FILE_TRY(hipGetLastError());
-    MAP_FILE_TRY(hipEventRecord(pp.ev_fmt[o], h->stream));
-    MAP_FILE_TRY(hipStreamWaitEvent(pp.s_out, pp.ev_fmt[o], 0));
-    if (total) MAP_FILE_TRY(hipMemcpyAsync(pp.pin_out[o], pp.d_out[o], (size_t)total, hipMemcpyDeviceToHost, pp.s_out));
-    MAP_FILE_TRY(hipEventRecord(pp.ev_copied[o], pp.s_out));
-    j.writer->push(o, pp.pin_out[o], (size_t)total);
-    j.out_seq++;
+    if (const int rc = map_file_hand_over<false>(*j.pipe, *j.writer, j.out_seq, a, nlines, total)) return rc;
     j.st.reads += rn, j.st.mapped += (int64_t)n_mapped, j.st.too_long += counts.too_long, j.st.records += nlines;
     j.st.chunks++, j.st.bytes_out += (int64_t)total;
     return ASM_OK;
@@ -200,6 +210,24 @@ static int map_file_process(MapFileJob& j, const char* d_raw, size_t nbytes, int
     });
 }
 
+/* the RNAME table on the device: the names back to back and their n_seqs + 1 offsets */
+static int map_file_names(asm_handle* h, const asm_index* ix, const char* const* seq_names, const char* who, Scratch<char>& d_names,
+                          Scratch<uint32_t>& d_name_off) {
+    std::string names;
+    std::vector<uint32_t> name_off(1, 0u);
+    for (int32_t r = 0; r < ix->n_seqs; r++) {
+        if (!seq_names[r]) return fail(h, ASM_EINVAL, std::string(who) + ": seq_names[" + std::to_string(r) + "] is NULL");
+        names += seq_names[r];
+        name_off.push_back((uint32_t)names.size());
+    }
+    STREAM_TRY(who, d_names.alloc(names.size() + 16));
+    STREAM_TRY(who, d_name_off.alloc(sizeof(uint32_t) * name_off.size()));
+    STREAM_TRY(who, hipMemcpyAsync(d_names.p, names.data(), names.size(), hipMemcpyHostToDevice, h->stream));
+    STREAM_TRY(who, hipMemcpyAsync(d_name_off.p, name_off.data(), sizeof(uint32_t) * name_off.size(), hipMemcpyHostToDevice, h->stream));
+    STREAM_TRY(who, hipStreamSynchronize(h->stream));
+    return ASM_OK;
+}
+
 static int map_file_run(asm_handle* h, const asm_index* ix, const char* const* seq_names, const char* fastq_path, const char* sam_path,
                         const char* header, const asm_map_params* p, int max_hits, int strata, size_t chunk, asm_map_file_stats* stats) {
     const auto t_begin = std::chrono::steady_clock::now();
@@ -214,21 +242,9 @@ static int map_file_run(asm_handle* h, const asm_index* ix, const char* const* s
     if (!pipe.out) return fail(h, ASM_EINVAL, std::string("asm_map_file: cannot write ") + sam_path);
     if (header && *header && fwrite(header, 1, strlen(header), pipe.out) != strlen(header))
         return fail(h, ASM_EINVAL, "asm_map_file: writing the SAM file failed");
-    /* the RNAME table */
-    std::string names;
-    std::vector<uint32_t> name_off(1, 0u);
-    for (int32_t r = 0; r < ix->n_seqs; r++) {
-        if (!seq_names[r]) return fail(h, ASM_EINVAL, "asm_map_file: seq_names[" + std::to_string(r) + "] is NULL");
-        names += seq_names[r];
-        name_off.push_back((uint32_t)names.size());
-    }
     Scratch<char> d_names(h);
     Scratch<uint32_t> d_name_off(h);
-    MAP_FILE_TRY(d_names.alloc(names.size() + 16));
-    MAP_FILE_TRY(d_name_off.alloc(sizeof(uint32_t) * name_off.size()));
-    MAP_FILE_TRY(hipMemcpyAsync(d_names.p, names.data(), names.size(), hipMemcpyHostToDevice, h->stream));
-    MAP_FILE_TRY(hipMemcpyAsync(d_name_off.p, name_off.data(), sizeof(uint32_t) * name_off.size(), hipMemcpyHostToDevice, h->stream));
-    MAP_FILE_TRY(hipStreamSynchronize(h->stream));
+    if (const int rc = map_file_names(h, ix, seq_names, "asm_map_file", d_names, d_name_off)) return rc;
     /* chunks ramp up from an eighth, so that the device starts after an eighth of a chunk has been read */
     const size_t slot_cap = chunk + chunk / 4 + 4096, first_chunk = chunk >= ((size_t)8 << 20) ? chunk / 8 : chunk;
     MAP_FILE_TRY(pipe.open_device(slot_cap));

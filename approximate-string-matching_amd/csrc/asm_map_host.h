@@ -202,8 +202,8 @@ static int map_front_seed(asm_handle* h, const asm_index* ix, int64_t n, const a
     return ASM_OK;
 }
 
-/* The front from host arrays: the runs of reads numbered and uploaded, then map_front_seed */
-static int map_front(asm_handle* h, const asm_index* ix, const MapReadsIn* in, int n_in, const asm_map_params* p, MapFront& f) {
+/* The runs of reads numbered and uploaded: f.d_reads, f.d_roff, f.roff and f.bytes */
+static int map_front_upload(asm_handle* h, const MapReadsIn* in, int n_in, MapFront& f) {
     int64_t n = 0;
     for (int t = 0; t < n_in; t++) n += in[t].n;
     f.roff.assign(1, 0u);
@@ -219,7 +219,13 @@ static int map_front(asm_handle* h, const asm_index* ix, const MapReadsIn* in, i
         HIPCHK(h, hipMemcpyAsync(f.d_reads.p + o, in[t].reads + in[t].read_off[0], in[t].read_off[in[t].n] - in[t].read_off[0],
                                  hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(f.d_roff.p, f.roff.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
-    return map_front_seed(h, ix, n, p, f);
+    return ASM_OK;
+}
+
+/* The front from host arrays: the upload, then map_front_seed */
+static int map_front(asm_handle* h, const asm_index* ix, const MapReadsIn* in, int n_in, const asm_map_params* p, MapFront& f) {
+    if (const int rc = map_front_upload(h, in, n_in, f)) return rc;
+    return map_front_seed(h, ix, (int64_t)f.roff.size() - 1, p, f);
 }
 
 /* The seeding rounds of a chunk, of at most map_cand_cap candidates each: every round sees every work item, emits the part of it
@@ -598,12 +604,13 @@ struct MapPairsIn { /* the two mates of a chunk's pairs */
     MapPairsIn at(int64_t c0) const { return {reads1, off1 + c0, reads2, off2 + c0}; }
 };
 
-static int map_pairs_front(asm_handle* h, const asm_index* ix, int64_t np, const MapPairsIn& m, const asm_map_params* p,
-                           const asm_pair_params* pp, const char* who, MapPairFront& pf) {
+/* The paired front once the 2 np reads are in HBM (pf.f.d_reads, d_roff, roff and bytes are filled: uploaded by map_pairs_front,
+ * or gathered there by asm_map_pairs_file) */
+static int map_pairs_front_seed(asm_handle* h, const asm_index* ix, int64_t np, const asm_map_params* p, const asm_pair_params* pp,
+                                const char* who, MapPairFront& pf) {
     const int64_t n = 2 * np;
     MapFront& f = pf.f;
-    const MapReadsIn in[2] = {{m.reads1, m.off1, np}, {m.reads2, m.off2, np}};
-    if (const int rc = map_front(h, ix, in, 2, p, f)) return rc;
+    if (const int rc = map_front_seed(h, ix, n, p, f)) return rc;
     const int e = p->max_errors;
     if (const int rc = map_runs(h, ix, n, p, f, pf.runs, who)) return rc;
     /* each read's loci (strata = e: all of them), listed in walk order */
@@ -657,6 +664,14 @@ static int map_pairs_front(asm_handle* h, const asm_index* ix, int64_t np, const
         HIPCHK(h, hipGetLastError());
     }
     return ASM_OK;
+}
+
+/* The paired front from host arrays: the mates 1 and then the mates 2 uploaded, then map_pairs_front_seed */
+static int map_pairs_front(asm_handle* h, const asm_index* ix, int64_t np, const MapPairsIn& m, const asm_map_params* p,
+                           const asm_pair_params* pp, const char* who, MapPairFront& pf) {
+    const MapReadsIn in[2] = {{m.reads1, m.off1, np}, {m.reads2, m.off2, np}};
+    if (const int rc = map_front_upload(h, in, 2, pf.f)) return rc;
+    return map_pairs_front_seed(h, ix, np, p, pp, who, pf);
 }
 
 /* asm_map_pairs' answer after map_pairs_front: the finish stage on the identity list (one item per read), then pair q's two records

@@ -1,9 +1,10 @@
-// SAM lines of asm_map_file (contract: docs/design/mapper.md, "Files: FASTQ in, SAM out"): the text of one output line, written
-// once for three users.  sam_format<Sink> walks the fields of a line in order and hands every piece to a sink:
+// SAM lines of asm_map_file and asm_map_pairs_file (contract: docs/design/mapper.md, "Files: FASTQ in, SAM out" and "Files: two
+// FASTQ files in, paired SAM out"): the text of one output line, single-end or paired, written once for three users.  sam_format<Sink> walks the fields of a line in order and hands every piece to a sink:
 //   SamSizeSink  adds the lengths                      (sam_size_kernel: one thread per line)
 //   SamLaneSink  stores the bytes p = lane (mod 64)    (sam_emit_kernel: one wave per line, 64 contiguous bytes per store)
 // so the size and the bytes cannot disagree.  The part above the kernels holds no HIP: host/sam_host_check.cpp compiles it with
-// plain g++ under ASan + UBSan and runs the lane sink for lanes 0..63 in turn (tests/test_map_file_host.py).
+// plain g++ under ASan + UBSan and runs the lane sink for lanes 0..63 in turn (tests/test_map_file_host.py,
+// tests/test_map_pairs_file_host.py).
 #pragma once
 #include <stdint.h>
 
@@ -40,6 +41,16 @@ struct SamLine {
     uint32_t rname_len;
     int all; /* max_hits > 0: NH, HI and XH follow */
     uint32_t n_reported, n_hits;
+    /* a record of a pair (asm_map_pairs_file); 0: a single-end line, and nothing below is read */
+    int paired;
+    uint32_t mate;                 /* 0: mate 1, 1: mate 2 */
+    int proper, rescued;           /* the pair is proper; this record was rescued */
+    int mate_mapped;               /* the other mate's record; the fields below are not read without it */
+    int32_t mate_seq_id;
+    uint32_t mate_pos, mate_strand;
+    const char* mate_rname;
+    uint32_t mate_rname_len;
+    uint32_t tlen, n_concordant;   /* max(end) - min(pos) when both mates lie on one sequence, else 0 */
 };
 
 enum { SAM_COPY = 0, SAM_UPPER = 1, SAM_REVCOMP = 2, SAM_REVERSE = 3 };
@@ -99,31 +110,39 @@ SAM_HD void sam_int(Sink& o, int32_t v) {
     o.num(v < 0 ? 0u - (uint32_t)v : (uint32_t)v);
 }
 
-/* QNAME FLAG RNAME POS MAPQ CIGAR * 0 0 SEQ QUAL [NM XG [NH HI XH]] */
+/* QNAME of a paired record: the first word without a trailing /1 or /2 (pair_name of host/asm_map.cpp) */
+SAM_HD uint32_t sam_pair_name_len(const char* raw, const SamRec& r) {
+    const uint32_t n = r.name_len;
+    return (n >= 2u && raw[r.name + n - 2u] == '/' && (raw[r.name + n - 1u] == '1' || raw[r.name + n - 1u] == '2')) ? n - 2u : n;
+}
+
+/* QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL [NM XG] [XP] [XR] [NH HI XH]; a single-end line has RNEXT '*', PNEXT 0
+ * and TLEN 0, a paired one borrows RNAME and POS from its mapped mate when it is unmapped itself (write_pairs of host/asm_map.cpp) */
 template <class Sink>
 SAM_HD void sam_format(const SamLine& l, Sink& o) {
     const SamRec& r = l.rec;
-    o.bytes(l.raw + r.name, r.name_len, SAM_COPY);
-    if (!l.mapped) {
-        SAM_LIT(o, "\t4\t*\t0\t0\t*\t*\t0\t0\t");
-        if (r.seq_len) o.bytes(l.raw + r.seq, r.seq_len, SAM_UPPER);
-        else o.ch('*');
-        o.ch('\t');
-        if (r.qual_len) o.bytes(l.raw + r.qual, r.qual_len, SAM_COPY);
-        else o.ch('*');
-        o.ch('\n');
-        return;
-    }
+    const bool pair = l.paired != 0, own = l.mapped != 0, lent = pair && !own && l.mate_mapped;
+    o.bytes(l.raw + r.name, pair ? sam_pair_name_len(l.raw, r) : r.name_len, SAM_COPY);
     o.ch('\t');
-    o.num((l.strand ? 16u : 0u) | (l.rank ? 256u : 0u));
+    if (pair)
+        o.num(1u | (l.proper ? 2u : 0u) | (own ? 0u : 4u) | (l.mate_mapped ? 0u : 8u) | (own && l.strand ? 16u : 0u) |
+              (l.mate_mapped && l.mate_strand ? 32u : 0u) | (l.mate ? 128u : 64u));
+    else
+        o.num(own ? (l.strand ? 16u : 0u) | (l.rank ? 256u : 0u) : 4u);
     o.ch('\t');
-    o.bytes(l.rname, l.rname_len, SAM_COPY);
+    /* POS columns of this line and of the mate's: each its own, else the other's, else 0 */
+    const uint32_t pos_x = own ? l.pos + 1u : lent ? l.mate_pos + 1u : 0u;
+    const uint32_t pos_y = !pair ? 0u : l.mate_mapped ? l.mate_pos + 1u : own ? l.pos + 1u : 0u;
+    if (own) o.bytes(l.rname, l.rname_len, SAM_COPY);
+    else if (lent) o.bytes(l.mate_rname, l.mate_rname_len, SAM_COPY);
+    else o.ch('*');
     o.ch('\t');
-    o.num(l.pos + 1u);
+    o.num(pos_x);
     o.ch('\t');
-    sam_int(o, l.greedy_cost + 60 < 254 ? l.greedy_cost + 60 : 254);
+    if (own) sam_int(o, l.greedy_cost + 60 < 254 ? l.greedy_cost + 60 : 254);
+    else o.ch('0');
     o.ch('\t');
-    if (l.nops > (uint32_t)SAM_CIGAR_CAP) {
+    if (!own || l.nops > (uint32_t)SAM_CIGAR_CAP) {
         o.ch('*');
     } else {
         for (uint32_t i = 0; i < l.nops; i++) {
@@ -131,20 +150,38 @@ SAM_HD void sam_format(const SamLine& l, Sink& o) {
             o.ch("MID=X???"[l.ops[i] & 7]);
         }
     }
-    SAM_LIT(o, "\t*\t0\t0\t");
-    if (l.rank) {
+    o.ch('\t');
+    if (!pair || !l.mate_mapped) o.ch('*');
+    else if (!own || l.mate_seq_id == l.seq_id) o.ch('=');
+    else o.bytes(l.mate_rname, l.mate_rname_len, SAM_COPY);
+    o.ch('\t');
+    o.num(pos_y);
+    o.ch('\t');
+    /* +tlen on the mate with the smaller POS column, mate 1 when they are equal */
+    if (pair && l.tlen != 0 && !(l.mate ? pos_x < pos_y : pos_x <= pos_y)) o.ch('-');
+    o.num(pair ? l.tlen : 0u);
+    o.ch('\t');
+    if (own && l.rank) {
         SAM_LIT(o, "*\t*");
     } else {
-        o.bytes(l.raw + r.seq, r.seq_len, l.strand ? SAM_REVCOMP : SAM_UPPER);
+        if (r.seq_len) o.bytes(l.raw + r.seq, r.seq_len, own && l.strand ? SAM_REVCOMP : SAM_UPPER);
+        else o.ch('*');
         o.ch('\t');
-        if (r.qual_len) o.bytes(l.raw + r.qual, r.qual_len, l.strand ? SAM_REVERSE : SAM_COPY);
+        if (r.qual_len) o.bytes(l.raw + r.qual, r.qual_len, own && l.strand ? SAM_REVERSE : SAM_COPY);
         else o.ch('*');
     }
-    SAM_LIT(o, "\tNM:i:");
-    sam_int(o, l.dist);
-    SAM_LIT(o, "\tXG:i:");
-    sam_int(o, l.greedy_cost);
-    if (l.all) {
+    if (own) {
+        SAM_LIT(o, "\tNM:i:");
+        sam_int(o, l.dist);
+        SAM_LIT(o, "\tXG:i:");
+        sam_int(o, l.greedy_cost);
+    }
+    if (pair && l.proper) {
+        SAM_LIT(o, "\tXP:i:");
+        o.num(l.n_concordant);
+    }
+    if (pair && l.rescued) SAM_LIT(o, "\tXR:i:1");
+    if (own && l.all) {
         SAM_LIT(o, "\tNH:i:");
         o.num(l.n_reported);
         SAM_LIT(o, "\tHI:i:");
@@ -189,6 +226,13 @@ struct SamArgs {
     const unsigned long long* off; /* its exclusive scan */
     unsigned long long* n_mapped;  /* += lines of rank 0 that are mapped */
     char* out;
+    /* asm_map_pairs_file (the <true> kernels): nrec pairs, recs = [2][nrec] (mate 1 of every pair, then mate 2), rec_read = pair ->
+     * sent pair; hits, ops and nops = [2][n_sent]; line 2q + x is mate x of pair q and the line list is not read */
+    const uint8_t* pair_state;     /* per sent pair: MAP_PAIR_* */
+    const uint32_t* n_conc;        /* per sent pair */
+    long n_sent;
+    unsigned long long* n_proper;  /* += proper pairs */
+    unsigned long long* n_rescued; /* += rescued records */
 };
 
 /* lines per record: one, or with all hits one per item of its read */
@@ -215,6 +259,34 @@ __global__ __launch_bounds__(256) void sam_line_fill_kernel(SamArgs a, uint32_t*
     }
 }
 
+/* line 2q + x of a chunk of pairs: mate x of pair q, with what the line shows of the other mate; the pair flags and tlen by the
+ * rules of asm_map_pairs (map_pairs_primary) */
+__device__ inline SamLine sam_load_pair_line(const SamArgs& a, long l) {
+    SamLine s = {};
+    const long q = l >> 1;
+    const uint32_t x = (uint32_t)(l & 1);
+    s.raw = a.raw, s.rec = a.recs[(long)x * a.nrec + q], s.paired = 1, s.mate = x;
+    const int32_t rd = a.rec_read[q];
+    if (rd < 0) return s;
+    const long ix = (long)x * a.n_sent + rd, iy = (long)(1u - x) * a.n_sent + rd;
+    const MapHit h = a.hits[ix], g = a.hits[iy];
+    const uint32_t st = a.pair_state[rd];
+    s.proper = st == MAP_PAIR_CONCORDANT || st == MAP_PAIR_RESCUED1 || st == MAP_PAIR_RESCUED2;
+    s.rescued = st == (x ? MAP_PAIR_RESCUED2 : MAP_PAIR_RESCUED1);
+    s.n_concordant = a.n_conc[rd];
+    if (h.flags & MAP_F_MAPPED) {
+        s.mapped = 1, s.seq_id = h.seq_id, s.pos = h.pos, s.dist = h.dist, s.greedy_cost = h.greedy_cost, s.strand = h.strand;
+        s.ops = a.ops + (size_t)ix * SAM_CIGAR_CAP, s.nops = a.nops[ix];
+        s.rname = a.names + a.name_off[h.seq_id], s.rname_len = a.name_off[h.seq_id + 1] - a.name_off[h.seq_id];
+    }
+    if (g.flags & MAP_F_MAPPED) {
+        s.mate_mapped = 1, s.mate_seq_id = g.seq_id, s.mate_pos = g.pos, s.mate_strand = g.strand;
+        s.mate_rname = a.names + a.name_off[g.seq_id], s.mate_rname_len = a.name_off[g.seq_id + 1] - a.name_off[g.seq_id];
+    }
+    if (s.mapped && s.mate_mapped && h.seq_id == g.seq_id) s.tlen = (h.end > g.end ? h.end : g.end) - (h.pos < g.pos ? h.pos : g.pos);
+    return s;
+}
+
 __device__ inline SamLine sam_load_line(const SamArgs& a, long l) {
     SamLine s = {};
     const uint32_t rec = a.line_rec[l], it = a.line_item[l];
@@ -232,26 +304,42 @@ __device__ inline SamLine sam_load_line(const SamArgs& a, long l) {
     return s;
 }
 
+/* the two kernels below serve both calls: PAIRED picks the load step at compile time (one body holding both makes the compiler merge
+ * their stores into the line through a pointer, which costs a stack slot and the single-end path a third more registers) */
+template <bool PAIRED>
+__device__ inline SamLine sam_load(const SamArgs& a, long l) {
+    if constexpr (PAIRED) return sam_load_pair_line(a, l);
+    else return sam_load_line(a, l);
+}
+
 /* one thread per line: its exact byte length */
+template <bool PAIRED>
 __global__ __launch_bounds__(256) void sam_size_kernel(SamArgs a) {
     const long l = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    bool primary = false;
+    bool primary = false, proper = false, rescued = false;
     if (l < a.nlines) {
-        const SamLine s = sam_load_line(a, l);
+        const SamLine s = sam_load<PAIRED>(a, l);
         a.size[l] = sam_line_size(s);
         primary = s.mapped && s.rank == 0u;
+        proper = s.paired && s.proper && s.mate == 0u, rescued = s.paired && s.rescued;
     } else if (l == a.nlines) {
         a.size[l] = 0ull;
     }
     const unsigned long long m = __ballot(primary);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(a.n_mapped, (unsigned long long)__popcll(m));
+    if constexpr (PAIRED) { /* the counts of a chunk of pairs */
+        const unsigned long long mp = __ballot(proper), mr = __ballot(rescued);
+        if ((threadIdx.x & 63) == 0 && mp) atomicAdd(a.n_proper, (unsigned long long)__popcll(mp));
+        if ((threadIdx.x & 63) == 0 && mr) atomicAdd(a.n_rescued, (unsigned long long)__popcll(mr));
+    }
 }
 
 /* one wave per line: every lane walks the line's pieces and stores its own bytes, 64 contiguous bytes per store */
+template <bool PAIRED>
 __global__ __launch_bounds__(256) void sam_emit_kernel(SamArgs a) {
     const uint32_t lane = threadIdx.x & 63u;
     const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-    for (long l = wave; l < a.nlines; l += nwaves) sam_line_emit(sam_load_line(a, l), a.out + a.off[l], lane);
+    for (long l = wave; l < a.nlines; l += nwaves) sam_line_emit(sam_load<PAIRED>(a, l), a.out + a.off[l], lane);
 }
 #endif /* __HIPCC__ */

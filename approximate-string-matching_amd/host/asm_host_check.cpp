@@ -5,11 +5,14 @@
 //     thread of its own, the way the copy stream does, with both of its fill policies: asm_stream_seq_file's (PairsFill, the reader
 //     pool) — every byte of the file must come out once, in order, cut at pair boundaries, for several chunk sizes, reader counts
 //     and max_pairs cuts, incl. files that end without a newline or on a read line — and asm_map_file's (FastqFill), against a
-//     plain line splitter: chunk sizes with and without ramp, CRLF, truncated records, records longer than a slot, an early stop,
+//     plain line splitter: chunk sizes with and without ramp, CRLF, truncated records, records longer than a slot, an early stop —
+//     and asm_map_pairs_file's (FastqPairFill: two files in step): equal record counts in both regions of every chunk, both files
+//     restored, the carry bounded by the chunk, a longer file and a truncated record in either file,
 //   * asm_map_file's writer thread (ChunkWriter): order, wait_idle, and failures that must not hang,
 //   * the stale-tail state arithmetic and the CIGAR formatter at their edges.
 // Built twice: -fsanitize=thread (races in the hand-overs / the pool) and -fsanitize=address,undefined (buffer edges).
 // Usage: asm_host_check <scratch directory>.  Prints "host check ok" and exits 0, or says what differed and exits 1.
+//        asm_host_check --pairs r1.fq r2.fq <chunk bytes> <out>: the chunks FastqPairFill makes of two files, for a test to read.
 #include <sys/stat.h>
 
 #include <cstdlib>
@@ -247,6 +250,180 @@ static void check_fastq_reader(const std::string& path) {
     }
 }
 
+struct PairChunk {
+    std::string bytes;
+    size_t bytes1 = 0;
+    int64_t units = 0;
+};
+struct PairRun {
+    std::deque<PairChunk> chunks;
+    bool failed = false;
+    int grown = 0;
+    size_t carry_peak = 0;
+    int64_t records[2] = {0, 0}, extra_lines[2] = {0, 0};
+    bool more[2] = {false, false};
+};
+
+/* Streams the two files through ChunkReader<FastqPairFill>, slots of chunk + slack bytes that grow on demand */
+static PairRun stream_fastq_pairs(const std::string& path1, const std::string& path2, size_t chunk, size_t first_chunk, size_t slack) {
+    PairRun r;
+    const int fd1 = open(path1.c_str(), O_RDONLY), fd2 = open(path2.c_str(), O_RDONLY);
+    struct stat st1, st2;
+    if (fd1 < 0 || fd2 < 0 || fstat(fd1, &st1) != 0 || fstat(fd2, &st2) != 0) {
+        r.failed = true;
+        return r;
+    }
+    std::vector<std::vector<char>> bufs(3, std::vector<char>(chunk + slack + 64));
+    std::future<void> copy[3];
+    ChunkReader<FastqPairFill> rd(
+        chunk, first_chunk,
+        [&](int q) {
+            if (copy[q].valid()) copy[q].wait();
+        },
+        fd1, fd2, (size_t)st1.st_size, (size_t)st2.st_size, chunk,
+        [&](int q, size_t cap, size_t keep) {
+            std::vector<char> bigger(cap + 64);
+            if (keep) memcpy(bigger.data(), bufs[(size_t)q].data(), keep);
+            bufs[(size_t)q].swap(bigger);
+            rd.slot[q].buf = bufs[(size_t)q].data(), rd.slot[q].cap = cap;
+            r.grown++;
+            return true;
+        });
+    for (int q = 0; q < 3; q++) rd.slot[q].buf = bufs[(size_t)q].data(), rd.slot[q].cap = chunk + slack;
+    rd.start();
+    bool last = false;
+    for (int c = 0; !last; c++) {
+        ChunkSlot* s = rd.wait_ready(c);
+        if (!s) {
+            r.failed = true;
+            break;
+        }
+        last = s->last;
+        r.chunks.emplace_back();
+        PairChunk* dst = &r.chunks.back();
+        dst->bytes1 = s->bytes1, dst->units = s->units;
+        const char* src = s->buf;
+        const size_t bytes = s->bytes;
+        copy[c % 3] = std::async(std::launch::async, [dst, src, bytes] { dst->bytes.assign(src, bytes); });
+        rd.consumed(c, true);
+        if (c % 2) std::this_thread::yield();
+    }
+    rd.stop();
+    for (auto& fu : copy)
+        if (fu.valid()) fu.wait();
+    const FastqPairFill& pol = rd.policy();
+    r.carry_peak = pol.carry_peak;
+    for (int f = 0; f < 2; f++) r.records[f] = pol.records[f], r.extra_lines[f] = pol.extra_lines[f], r.more[f] = pol.more[f];
+    close(fd1), close(fd2);
+    return r;
+}
+
+/* `asm_host_check --pairs f1 f2 chunk out` (tests/test_map_pairs_file_host.py): every chunk as u64 units, bytes1, bytes and the
+ * bytes, then u64 0xffffffffffffffff, failed, carry_peak, records[2], extra_lines[2], more[2] */
+static int dump_fastq_pairs(const char* f1, const char* f2, size_t chunk, const char* out_path) {
+    const PairRun r = stream_fastq_pairs(f1, f2, chunk, chunk >= 8192 ? chunk / 8 : 0, chunk / 4 + 4096);
+    FILE* out = fopen(out_path, "wb");
+    if (!out) return 2;
+    auto put = [&](uint64_t v) { fwrite(&v, 8, 1, out); };
+    for (const PairChunk& c : r.chunks) {
+        put((uint64_t)c.units), put(c.bytes1), put(c.bytes.size());
+        fwrite(c.bytes.data(), 1, c.bytes.size(), out);
+    }
+    put(~0ull), put(r.failed), put(r.carry_peak);
+    for (int f = 0; f < 2; f++) put((uint64_t)r.records[f]);
+    for (int f = 0; f < 2; f++) put((uint64_t)r.extra_lines[f]);
+    for (int f = 0; f < 2; f++) put(r.more[f]);
+    return fclose(out) == 0 ? 0 : 2;
+}
+
+/* the first n records of a FASTQ text */
+static std::string first_records(const std::string& text, int64_t n) {
+    size_t pos = 0;
+    for (int64_t l = 0; l < 4 * n; l++) pos = text.find('\n', pos) + 1;
+    return text.substr(0, pos);
+}
+
+static void expect_pairs(const char* what, const PairRun& r, const std::string& t1, const std::string& t2, int64_t pairs, size_t chunk) {
+    EXPECT(!r.failed, "%s: stream failed", what);
+    std::string got[2];
+    int64_t units = 0;
+    for (const PairChunk& c : r.chunks) {
+        int64_t n1 = 0, n2 = 0, l1 = 0, l2 = 0;
+        const size_t b1 = fastq_cut(c.bytes.data(), c.bytes1, &n1, &l1);
+        const size_t b2 = fastq_cut(c.bytes.data() + c.bytes1, c.bytes.size() - c.bytes1, &n2, &l2);
+        EXPECT(c.bytes1 <= c.bytes.size() && b1 == c.bytes1 && b2 == c.bytes.size() - c.bytes1 && n1 == c.units && n2 == c.units && l1 == 4 * n1 &&
+                   l2 == 4 * n2,
+               "%s: a chunk of %lld units holds %lld and %lld records", what, (long long)c.units, (long long)n1, (long long)n2);
+        got[0].append(c.bytes, 0, c.bytes1), got[1].append(c.bytes, c.bytes1, std::string::npos);
+        units += c.units;
+    }
+    EXPECT(units == pairs, "%s: %lld pairs, want %lld", what, (long long)units, (long long)pairs);
+    const std::string w1 = first_records(t1, pairs), w2 = first_records(t2, pairs);
+    EXPECT(got[0] == w1 && got[1] == w2, "%s: bytes differ (%zu, %zu against %zu, %zu)", what, got[0].size(), got[1].size(), w1.size(), w2.size());
+    EXPECT(chunk == 0 || r.carry_peak <= chunk, "%s: carry peak %zu above the chunk %zu", what, r.carry_peak, chunk);
+}
+
+static std::string make_mates(int n, int len_lo, int len_step, int len_mod, const char* eol = "\n") {
+    std::string text;
+    for (int i = 0; i < n; i++) {
+        const size_t len = (size_t)(len_lo + (i * len_step) % len_mod);
+        text += "@frag" + std::to_string(i) + eol + std::string(len, "ACGT"[i & 3]) + eol + "+" + eol + std::string(len, (char)('!' + i % 40)) + eol;
+    }
+    return text;
+}
+
+static void check_fastq_pair_reader(const std::string& dir) {
+    const std::string p1 = dir + "/asm_host_check.r1.fq", p2 = dir + "/asm_host_check.r2.fq";
+    const std::string t1 = make_mates(2000, 30, 7, 31), t2 = make_mates(2000, 200, 13, 101);
+    write_file(p1, t1), write_file(p2, t2);
+    for (size_t chunk : {(size_t)4096, (size_t)65536, (size_t)1 << 20}) {
+        expect_pairs("flat chunks", stream_fastq_pairs(p1, p2, chunk, 0, chunk / 4 + 4096), t1, t2, 2000, chunk);
+        const PairRun ramp = stream_fastq_pairs(p1, p2, chunk, chunk / 8, chunk / 4 + 4096);
+        expect_pairs("ramped chunks", ramp, t1, t2, 2000, chunk);
+        EXPECT(ramp.records[0] == 2000 && ramp.records[1] == 2000 && !ramp.more[0] && !ramp.more[1] && !ramp.extra_lines[0] && !ramp.extra_lines[1],
+               "ramped chunks: the end of the stream");
+    }
+    {   /* CRLF in one file, no final newline in the other */
+        const std::string c1 = make_mates(300, 40, 1, 1, "\r\n"), c2 = t2.substr(0, first_records(t2, 300).size() - 1);
+        write_file(p1, c1), write_file(p2, c2);
+        expect_pairs("CRLF and a missing final newline", stream_fastq_pairs(p1, p2, 5000, 0, 4096), c1, c2 + "\n", 300, 5000);
+    }
+    {   /* records longer than chunk and slot: more bytes are taken and the slot grows */
+        const std::string b1 = make_fastq(40, "\n", 17, 20000), b2 = make_fastq(40, "\n", 3, 9000);
+        write_file(p1, b1), write_file(p2, b2);
+        const PairRun r = stream_fastq_pairs(p1, p2, 1024, 0, 64);
+        expect_pairs("long records", r, b1, b2, 40, 0);
+        EXPECT(r.grown > 0, "long records: the slot did not grow");
+    }
+    {   /* two empty files: one last, empty chunk */
+        write_file(p1, ""), write_file(p2, "");
+        const PairRun r = stream_fastq_pairs(p1, p2, 4096, 0, 4096);
+        EXPECT(!r.failed && r.chunks.size() == 1 && r.chunks[0].units == 0 && r.chunks[0].bytes.empty() && !r.more[0] && !r.more[1], "two empty files");
+    }
+    for (int longer = 0; longer < 2; longer++) { /* one file holds more records: the pairs come through, then more[] says which */
+        const std::string a = first_records(t1, 700 + 300 * (longer == 0)), b = first_records(t2, 700 + 300 * (longer == 1));
+        write_file(p1, a), write_file(p2, b);
+        const PairRun r = stream_fastq_pairs(p1, p2, 8192, 0, 4096);
+        expect_pairs("a longer file", r, a, b, 700, 0);
+        EXPECT(r.more[longer] && !r.more[1 - longer] && r.records[1 - longer] == 700 && r.records[longer] > 700 && !r.extra_lines[0] && !r.extra_lines[1],
+               "a longer file: more %d %d", (int)r.more[0], (int)r.more[1]);
+    }
+    for (int f = 0; f < 2; f++)
+        for (int extra = 1; extra <= 3; extra++) { /* a truncated last record in file f */
+            std::string a = first_records(t1, 200), b = first_records(t2, 200);
+            std::string& cut = f ? b : a;
+            size_t pos = cut.size();
+            for (int l = 0; l < 4 - extra; l++) pos = cut.rfind('\n', pos - 2) + 1;
+            cut.resize(pos);
+            write_file(p1, a), write_file(p2, b);
+            const PairRun r = stream_fastq_pairs(p1, p2, 3000, 0, 4096);
+            expect_pairs("a truncated record", r, a, b, 199, 0);
+            EXPECT(r.extra_lines[f] == extra && r.extra_lines[1 - f] == 0 && r.records[f] == 199 && r.records[1 - f] == 200,
+                   "a truncated record in file %d: %lld extra lines, want %d", f + 1, (long long)r.extra_lines[f], extra);
+        }
+    remove(p1.c_str()), remove(p2.c_str());
+}
+
 static void check_chunk_writer(const std::string& path) {
     {   /* bytes arrive in push order through three rotating slots, whatever `before` takes; wait_idle waits for the job */
         FILE* f = fopen(path.c_str(), "wb");
@@ -305,6 +482,7 @@ static void check_chunk_writer(const std::string& path) {
 }
 
 int main(int argc, char** argv) {
+    if (argc == 6 && std::string(argv[1]) == "--pairs") return dump_fastq_pairs(argv[2], argv[3], (size_t)atoll(argv[4]), argv[5]);
     const std::string dir = argc > 1 ? argv[1] : "/tmp";
     const std::string path = dir + "/asm_host_check.seq";
     asm_gen_config cfg;
@@ -368,6 +546,7 @@ int main(int argc, char** argv) {
         EXPECT(failed, "a chunk smaller than one pair must fail");
     }
     check_fastq_reader(path);
+    check_fastq_pair_reader(dir);
     check_chunk_writer(path);
     {   /* stale-tail state: advancing over a + b untouched pairs = advancing over a, then b; a write lands where its slot goes */
         std::string err;

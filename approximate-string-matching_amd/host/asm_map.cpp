@@ -9,6 +9,8 @@
 //           [--all-hits N [--strata S]]
 // --stream hands the FASTQ file and the SAM path to asm_map_file, which parses, maps and formats on the device while it reads and
 // writes (four-line FASTQ only; the same lines as without it); --chunk-bytes N: file bytes per chunk (default: the library's).
+// --stream-pairs does the same for paired mode through asm_map_pairs_file (two four-line FASTQ files; the lines of -1 / -2 without
+// --all-hits); --stream together with -2 is a usage error.
 // --all-hits N writes up to N loci per read in rank order (asm_map_reads_all, strata S, default e): the primary record as without
 // it, then the secondary ones (FLAG 256, SEQ and QUAL '*'), each with NH:i:<reported> HI:i:<rank + 1> XH:i:<all loci> after NM
 // and XG.  Reads may be FASTQ or FASTA (QUAL '*').  Reads are processed in chunks of --chunk records, so the read file's size is not
@@ -40,7 +42,9 @@ static void usage() {
                     "       asm-map -r ref.fa -1 r1.fq -2 r2.fq [-o out.sam] -e N --insert MIN,MAX [--rescue E] [--k 12] [--max-occ N] "
                     "[--chunk N] [--all-hits N [--strata S]]\n"
                     "       asm-map -r ref.fa -q reads.fq --stream [--chunk-bytes N] [-o out.sam] [-e N] [--k 12] [--both-strands] "
-                    "[--max-occ N] [--all-hits N [--strata S]]\n");
+                    "[--max-occ N] [--all-hits N [--strata S]]\n"
+                    "       asm-map -r ref.fa -1 r1.fq -2 r2.fq --stream-pairs [--chunk-bytes N] [-o out.sam] -e N --insert MIN,MAX "
+                    "[--rescue E] [--k 12] [--max-occ N]\n");
     exit(2);
 }
 
@@ -261,7 +265,7 @@ int main(int argc, char** argv) {
     int k = 12;
     long chunk = 262144;
     int all_hits = 0, strata = -1; /* all_hits 0: the best hit only */
-    bool stream = false;
+    bool stream = false, stream_pairs = false;
     long long chunk_bytes = 0;
     std::string cl = "asm-map";
     for (int a = 1; a < argc; a++) cl += std::string(" ") + argv[a];
@@ -286,12 +290,14 @@ int main(int argc, char** argv) {
         else if (s == "--all-hits") all_hits = atoi(val());
         else if (s == "--strata") strata = atoi(val());
         else if (s == "--stream") stream = true;
+        else if (s == "--stream-pairs") stream_pairs = true;
         else if (s == "--chunk-bytes") chunk_bytes = atoll(val());
         else usage();
     }
     if (ref_path.empty() || read_path.empty() || chunk < 1 || all_hits < 0 || (strata >= 0 && !all_hits)) usage();
     const bool paired = !read2_path.empty();
-    if (chunk_bytes < 0 || (chunk_bytes > 0 && !stream) || (stream && paired)) usage(); /* paired streaming: not there */
+    if (chunk_bytes < 0 || (chunk_bytes > 0 && !stream && !stream_pairs) || (stream && paired)) usage(); /* paired: --stream-pairs */
+    if (stream_pairs && (!paired || all_hits || stream)) usage(); /* secondary pairs from files: not there */
     if (paired && (pp.min_insert < 0 || pp.max_insert < 0)) usage(); /* paired: --insert needed */
     if (!paired && (pp.min_insert >= 0 || pp.rescue_errors >= 0)) usage();
     if (paired) p.both_strands = 1;
@@ -341,8 +347,23 @@ int main(int argc, char** argv) {
         fprintf(stderr, "asm-map: --stream needs FASTQ reads\n");
         return 1;
     }
-    FILE* out = stream ? nullptr : fopen(out_path.c_str(), "w");
-    if (!out && !stream) {
+    if (stream_pairs) { /* both files must be FASTQ */
+        bool fasta2 = false;
+        if (FILE* f2 = fopen(read2_path.c_str(), "r")) {
+            fasta2 = fgetc(f2) == '>';
+            fclose(f2);
+        } else {
+            fprintf(stderr, "asm-map: cannot open %s\n", read2_path.c_str());
+            return 1;
+        }
+        if (reads.fasta || fasta2) {
+            fprintf(stderr, "asm-map: --stream-pairs needs FASTQ reads\n");
+            return 1;
+        }
+    }
+    const bool library_writes = stream || stream_pairs;
+    FILE* out = library_writes ? nullptr : fopen(out_path.c_str(), "w");
+    if (!out && !library_writes) {
         fprintf(stderr, "asm-map: cannot write %s\n", out_path.c_str());
         return 1;
     }
@@ -370,6 +391,23 @@ int main(int argc, char** argv) {
         if (rc) return 1;
         fprintf(stderr, "asm-map: %lld reads, %lld mapped, %lld longer than %d (unmapped)\n", (long long)st.reads, (long long)st.mapped,
                 (long long)st.too_long, ASM_MAP_MAX_READ);
+        fprintf(stderr, "asm-map: streamed %lld chunks, %lld bytes in, %lld bytes out, %.3f s (reader busy %.3f s, writer busy %.3f s)\n",
+                (long long)st.chunks, (long long)st.bytes_in, (long long)st.bytes_out, st.seconds, st.seconds_read, st.seconds_write);
+        return 0;
+    }
+    if (stream_pairs) { /* the library reads both files, pairs, maps, formats and writes */
+        fclose(rf);
+        std::vector<const char*> name_ptr;
+        for (const std::string& nm : names) name_ptr.push_back(nm.c_str());
+        asm_map_pairs_file_stats st;
+        rc = asm_map_pairs_file(h, ix, name_ptr.data(), read_path.c_str(), read2_path.c_str(), out_path.c_str(), header.c_str(), &p, &pp,
+                                chunk_bytes, &st);
+        if (rc) fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
+        asm_index_free(h, ix);
+        asm_destroy(h);
+        if (rc) return 1;
+        fprintf(stderr, "asm-map: %lld pairs, %lld proper, %lld mates rescued\n", (long long)st.pairs, (long long)st.proper,
+                (long long)st.rescued);
         fprintf(stderr, "asm-map: streamed %lld chunks, %lld bytes in, %lld bytes out, %.3f s (reader busy %.3f s, writer busy %.3f s)\n",
                 (long long)st.chunks, (long long)st.bytes_in, (long long)st.bytes_out, st.seconds, st.seconds_read, st.seconds_write);
         return 0;

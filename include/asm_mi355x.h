@@ -467,6 +467,30 @@ int asm_map_file(asm_handle* h, const asm_index* ix, const char* const* seq_name
                  asm_map_file_stats* stats /* may be NULL */);
 size_t asm_fastq_cut(const char* buf, size_t nbytes, int64_t* records);
 
+/* asm_map_pairs_file: two FASTQ files in, a paired SAM file out (docs/design/mapper.md, "Files: two FASTQ files in, paired SAM out");
+ *                  synchronous.  Record i of fastq1_path and record i of fastq2_path are the mates of pair i; each file follows
+ *                  asm_map_file's input contract.  The two files are read in step, about chunk_bytes (0: 16 MiB) of both together
+ *                  per chunk, and a chunk is parsed, paired, mapped and formatted on the device while the next one is read and the
+ *                  one before is written.  The answer is asm_map_pairs' (best concordant pair, mate rescue; both_strands must be
+ *                  1): after `header`, two lines per pair, mate 1 then mate 2, byte for byte the lines asm-map -1 -2 writes.  QNAME
+ *                  is the first word without a trailing /1 or /2 and must be the same for both mates.  A pair with an empty or too
+ *                  long (> ASM_MAP_MAX_READ) mate gives two unmapped lines.  ASM_EINVAL, naming the 1-based record and the file: a
+ *                  malformed or truncated record, files with different numbers of records, mates whose names differ; the first
+ *                  device chunk that holds an error reports it, a malformed record of file 1 before one of file 2 before a name,
+ *                  each with its smallest record.  ASM_EUNSUPPORTED: a file starting with '>'.  Two empty files give the header
+ *                  alone.  The output does not depend on chunk_bytes or ASM_MAP_CHUNK.
+ * asm_fastq_cut_n: asm_fastq_cut bounded to the first max_records records; no device. */
+typedef struct asm_map_pairs_file_stats {
+    int64_t pairs, proper, rescued, unsent;   /* fragments; proper pairs; rescued mates; pairs with an empty or too long mate */
+    int64_t records, chunks, bytes_in, bytes_out, carry_peak; /* SAM lines; device chunks; FASTQ bytes of both files; SAM bytes without
+                                                                 the header; the most bytes the reader held back between two chunks */
+    double seconds, seconds_read, seconds_write; /* whole call; reader busy; writer busy */
+} asm_map_pairs_file_stats;
+int asm_map_pairs_file(asm_handle* h, const asm_index* ix, const char* const* seq_names /* [n_seqs] */, const char* fastq1_path,
+                       const char* fastq2_path, const char* sam_path, const char* header, const asm_map_params* p,
+                       const asm_pair_params* pp, int64_t chunk_bytes, asm_map_pairs_file_stats* stats /* may be NULL */);
+size_t asm_fastq_cut_n(const char* buf, size_t nbytes, int64_t max_records, int64_t* records);
+
 /* ---- plain device memory helpers (so that non-torch hosts can drive the async API) --------------------- */
 int asm_device_malloc(asm_handle* h, size_t bytes, void** d_ptr);
 int asm_device_free(asm_handle* h, void* d_ptr);

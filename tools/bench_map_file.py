@@ -1,13 +1,16 @@
 """File-to-file read mapping timings (development tool):
 PYTHONPATH=. python tools/bench_map_file.py --dir DIR [--ref-len 5e6] [--reads 1e6] [--len 100] [--errors 2] [--all-hits N]
-[--reps 3] [--chunk-bytes N] [--profile]
+[--reps 3] [--chunk-bytes N] [--profile] [--paired [--insert 200,500] [--rescue E]]
 Writes the workload of tools/bench_map.py as files into DIR (seeded: a reference of --ref-len bases as ref.fa and --reads reads of
 --len bases with qualities as reads.fq), then runs `asm-map` and `asm-map --stream` on them alternately, --reps times each, in this
 one call.  For every run: the wall clock of the whole process (reference parsing and index build included, the same in both) and,
 for --stream, the library's own split (whole asm_map_file call, reader busy, writer busy).  The comparison is always against the
 same asm-map without --stream on the same files; the two SAM files must be identical apart from @PG.  The files are read once
 before the first run, so every run finds them in the page cache; the SAM files go to DIR too.
---profile runs `asm-map --stream` once under `rocprofv3 --kernel-trace --stats` (a run of its own) and prints the kernel totals."""
+--paired writes the paired workload of tools/bench_map.py --paired instead (--reads / 2 pairs, as r1.fq and r2.fq) and compares
+`asm-map -1 -2` with `asm-map -1 -2 --stream-pairs`; the streamed runs also report the reader's carry_peak (from a library call of
+its own on the same files, Engine.map_pairs_file).
+--profile runs `asm-map --stream` (or --stream-pairs) once under `rocprofv3 --kernel-trace --stats` (a run of its own) and prints the kernel totals."""
 import argparse
 import csv
 import glob
@@ -23,14 +26,26 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-from tools.bench_map import make_inputs  # noqa: E402
+from tools.bench_map import make_inputs, make_pairs  # noqa: E402
 
 EXE = os.path.join(ROOT, "approximate-string-matching_amd", "asm-map")
 
 
+def write_fastq(path, reads, prefix, seed):
+    n, m = reads.shape
+    rng = np.random.default_rng(seed)
+    names = np.char.add(prefix, np.arange(n).astype(str)).astype(bytes)
+    quals = rng.integers(35, 74, (n, m), dtype=np.uint8)
+    with open(path, "wb") as fh:
+        for lo in range(0, n, 100_000):
+            hi = min(n, lo + 100_000)
+            fh.write(b"".join(names[t] + b"\n" + reads[t].tobytes() + b"\n+\n" + quals[t].tobytes() + b"\n" for t in range(lo, hi)))
+
+
 def write_files(a, e):
-    ref, reads = make_inputs(int(a.ref_len), int(a.reads), a.len, e, seed=1234)
-    fa, fq = os.path.join(a.dir, "ref.fa"), os.path.join(a.dir, "reads.fq")
+    """-> the reference and the read files (one, or with --paired the two mates' files)"""
+    ref, reads = make_inputs(int(a.ref_len), 1 if a.paired else int(a.reads), a.len, e, seed=1234)
+    fa = os.path.join(a.dir, "ref.fa")
     with open(fa, "wb") as fh:
         fh.write(b">ref\n")
         body = np.full((ref.size + 69) // 70 * 71, 10, np.uint8).reshape(-1, 71)
@@ -40,15 +55,16 @@ def write_files(a, e):
         out = body.reshape(-1)
         out = out[out != 0]
         fh.write(out.tobytes())
-    n, m = reads.shape
-    rng = np.random.default_rng(99)
-    names = np.char.add("@read", np.arange(n).astype(str)).astype(bytes)
-    quals = rng.integers(35, 74, (n, m), dtype=np.uint8)
-    with open(fq, "wb") as fh:
-        for lo in range(0, n, 100_000):
-            hi = min(n, lo + 100_000)
-            fh.write(b"".join(names[t] + b"\n" + reads[t].tobytes() + b"\n+\n" + quals[t].tobytes() + b"\n" for t in range(lo, hi)))
-    return fa, fq
+    if a.paired:
+        lo, hi = (int(v) for v in a.insert.split(","))
+        m1, m2 = make_pairs(ref, int(a.reads) // 2, a.len, e, lo, hi, seed=4321)
+        fqs = [os.path.join(a.dir, "r1.fq"), os.path.join(a.dir, "r2.fq")]
+        write_fastq(fqs[0], m1, "@frag", 99)
+        write_fastq(fqs[1], m2, "@frag", 100)
+        return fa, fqs
+    fq = os.path.join(a.dir, "reads.fq")
+    write_fastq(fq, reads, "@read", 99)
+    return fa, [fq]
 
 
 def run(cmd):
@@ -76,16 +92,23 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--chunk-bytes", type=int, default=0)
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--paired", action="store_true", help="asm-map -1 -2 against --stream-pairs on --reads / 2 simulated pairs")
+    ap.add_argument("--insert", default="200,500", help="with --paired: MIN,MAX of the projected span")
+    ap.add_argument("--rescue", type=int, default=-1, help="with --paired: mate rescue's error bound (-1: off)")
     a = ap.parse_args()
     os.makedirs(a.dir, exist_ok=True)
-    fa, fq = write_files(a, a.errors)
-    for path in (fa, fq):  # into the page cache
+    fa, fqs = write_files(a, a.errors)
+    for path in [fa] + fqs:  # into the page cache
         with open(path, "rb") as fh:
             while fh.read(1 << 24):
                 pass
-    flags = ["-e", str(a.errors), "--both-strands"] + (["--all-hits", str(a.all_hits)] if a.all_hits else [])
-    base = [EXE, "-r", fa, "-q", fq] + flags
-    stream = ["--stream"] + (["--chunk-bytes", str(a.chunk_bytes)] if a.chunk_bytes else [])
+    if a.paired:
+        flags = ["-e", str(a.errors), "--insert", a.insert] + (["--rescue", str(a.rescue)] if a.rescue >= 0 else [])
+        base = [EXE, "-r", fa, "-1", fqs[0], "-2", fqs[1]] + flags
+    else:
+        flags = ["-e", str(a.errors), "--both-strands"] + (["--all-hits", str(a.all_hits)] if a.all_hits else [])
+        base = [EXE, "-r", fa, "-q", fqs[0]] + flags
+    stream = ["--stream-pairs" if a.paired else "--stream"] + (["--chunk-bytes", str(a.chunk_bytes)] if a.chunk_bytes else [])
     sam0, sam1 = os.path.join(a.dir, "plain.sam"), os.path.join(a.dir, "stream.sam")
     if a.profile:
         out = os.path.join(a.dir, "profile")
@@ -101,7 +124,8 @@ def main():
                                                                            float(r["AverageNs"]) / 1e3))
         return
     result = {"reads": int(a.reads), "len": a.len, "ref_len": int(a.ref_len), "errors": a.errors, "all_hits": a.all_hits,
-              "fastq_bytes": os.path.getsize(fq), "page_cache": True, "pairs": []}
+              "paired": a.paired, "insert": a.insert if a.paired else None, "rescue": a.rescue if a.paired else None,
+              "fastq_bytes": sum(os.path.getsize(fq) for fq in fqs), "page_cache": True, "pairs": []}
     for rep in range(a.reps):
         w0, err0 = run(base + ["-o", sam0])
         w1, err1 = run(base + ["-o", sam1] + stream)
@@ -109,14 +133,25 @@ def main():
         pair = {"plain_s": round(w0, 3), "stream_s": round(w1, 3), "ratio": round(w0 / w1, 2), "call_s": float(mt.group(1)),
                 "read_s": float(mt.group(2)), "write_s": float(mt.group(3)), "faster": w1 < w0}
         result["pairs"].append(pair)
-        print("pair %d: asm-map %.3f s, asm-map --stream %.3f s (x%.2f); asm_map_file %.3f s, reader busy %.3f s, writer busy %.3f s" %
-              (rep, w0, w1, w0 / w1, pair["call_s"], pair["read_s"], pair["write_s"]), flush=True)
+        print("pair %d: asm-map %.3f s, asm-map %s %.3f s (x%.2f); library call %.3f s, reader busy %.3f s, writer busy %.3f s" %
+              (rep, w0, stream[0], w1, w0 / w1, pair["call_s"], pair["read_s"], pair["write_s"]), flush=True)
         if rep == 0:
             result["sam_bytes"] = os.path.getsize(sam1)
             result["identical"] = body_of(sam0) == body_of(sam1)
             result["summary"] = err1.splitlines()[0]
             print("SAM files identical apart from @PG:", result["identical"], flush=True)
     result["all_faster"] = all(p["faster"] for p in result["pairs"])
+    if a.paired:  # the reader's carry, which the tool does not print: one library call on the same files
+        import approximate_string_matching_amd as m
+
+        eng = m.Engine(0)
+        ref, _ = make_inputs(int(a.ref_len), 1, a.len, a.errors, seed=1234)
+        ix = eng.build_index([ref.tobytes().decode()], k=12)
+        lo, hi = (int(v) for v in a.insert.split(","))
+        st = eng.map_pairs_file(ix, ["ref"], fqs[0], fqs[1], sam1, a.errors, lo, hi, rescue_errors=a.rescue, chunk_bytes=a.chunk_bytes)
+        result["library"] = {k: (round(v, 3) if isinstance(v, float) else v) for k, v in st.items()}
+        ix.free()
+        eng.close()
     print(json.dumps(result))
 
 
