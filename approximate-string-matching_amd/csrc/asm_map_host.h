@@ -46,11 +46,7 @@ static hipError_t map_sort_pairs(asm_handle* h, MapTmp& tmp, K* key_in, K* key_o
  * place where a read length picks an instantiation of the <W> kernels */
 template <class F>
 static hipError_t map_with_width(int maxm, F fn) {
-    const int words = (maxm + 63) / 64;
-    if (words <= 1) return fn(std::integral_constant<int, 1>{});
-    if (words <= 2) return fn(std::integral_constant<int, 2>{});
-    if (words <= 4) return fn(std::integral_constant<int, 4>{});
-    return fn(std::integral_constant<int, 8>{});
+    return with_const_of<1, 2, 4, 8>((maxm + 63) / 64, fn);
 }
 
 /* one(first, count) for every chunk of at most step out of n */
