@@ -653,6 +653,14 @@ class Engine:
         out["cigar_nops"] = nops[read, rank]
         return out
 
+    @staticmethod
+    def _rnames(index: Index, names):
+        """seq_names of the two file calls: one RNAME per sequence of the index, as a C array"""
+        names = [_as_bytes(nm) for nm in names]
+        if len(names) != len(index.lengths):
+            raise ValueError("names must hold one name per sequence of the index")
+        return (ctypes.c_char_p * max(len(names), 1))(*names)
+
     def map_file(self, index: Index, names, fastq_path: str, sam_path: str, max_errors: int, both_strands: bool = True,
                  max_occ: int = 0, greedy_k: int = 3, max_hits: int = 0, strata: Optional[int] = None, chunk_bytes: int = 0,
                  header: Optional[str] = None) -> dict:
@@ -660,10 +668,7 @@ class Engine:
         "Files: FASTQ in, SAM out").  names: one RNAME per sequence of the index.  max_hits=0: the best hit per read (map_reads);
         1..256: the loci of map_reads_all with strata (None: max_errors).  header is written first, as it is.  -> the stats as a dict:
         reads, mapped, too_long, records (SAM lines), chunks, bytes_in, bytes_out, seconds, seconds_read, seconds_write."""
-        names = [_as_bytes(nm) for nm in names]
-        if len(names) != len(index.lengths):
-            raise ValueError("names must hold one name per sequence of the index")
-        arr = (ctypes.c_char_p * max(len(names), 1))(*names)
+        arr = self._rnames(index, names)
         p = MapParams(int(max_errors), 1 if both_strands else 0, int(max_occ), int(greedy_k))
         st = MapFileStats()
         strata = int(max_errors) if strata is None else int(strata)
@@ -680,10 +685,7 @@ class Engine:
         is map_pairs'.  names: one RNAME per sequence of the index.  header is written first, as it is.  -> the stats as a dict:
         pairs, proper, rescued, unsent, records (SAM lines), chunks, bytes_in, bytes_out, carry_peak, seconds, seconds_read,
         seconds_write."""
-        names = [_as_bytes(nm) for nm in names]
-        if len(names) != len(index.lengths):
-            raise ValueError("names must hold one name per sequence of the index")
-        arr = (ctypes.c_char_p * max(len(names), 1))(*names)
+        arr = self._rnames(index, names)
         p = MapParams(int(max_errors), 1, int(max_occ), int(greedy_k))
         pp = PairParams(int(min_insert), int(max_insert), int(rescue_errors))
         st = MapPairsFileStats()

@@ -1977,22 +1977,16 @@ static int batch_from_device_text(asm_handle* h, const char* d_raw, size_t nbyte
     HIPCHK(h, d_max.alloc(16));
     HIPCHK(h, hipMemsetAsync(d_max.p, 0, 16, h->stream));
     if (n > 0) HIPCHK(h, newline_index(h, tmp, d_raw, nbytes, (long)(2 * n), d_nl.p));
-    hipLaunchKernelGGL(seq_lengths_kernel, dim3(grid_for(n + 1)), dim3(ASM_BLOCK), 0, h->stream, (const uint32_t*)d_nl.p, (long)n,
-                       d_m.p, d_n.p, d_sa.p, d_sb.p);
+    HIPCHK(h, launch(h, seq_lengths_kernel, grid_for(n + 1), ASM_BLOCK, (const uint32_t*)d_nl.p, (long)n, d_m.p, d_n.p, d_sa.p, d_sb.p));
     HIPCHK(h, map_exclusive_sum(h, tmp, d_m.p, b->d_read_off, (int64_t)cnt));
     HIPCHK(h, map_exclusive_sum(h, tmp, d_n.p, b->d_ref_off, (int64_t)cnt));
     if (n > 0) {
         int64_t blocks = (n + ASM_BLOCK - 1) / ASM_BLOCK;
         blocks = blocks > 1024 ? 1024 : blocks;
-        hipLaunchKernelGGL(seq_max_kernel, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, h->stream, (const uint32_t*)d_m.p,
-                           (const uint32_t*)d_n.p, (long)n, d_max.p);
+        HIPCHK(h, launch(h, seq_max_kernel, (unsigned)blocks, ASM_BLOCK, (const uint32_t*)d_m.p, (const uint32_t*)d_n.p, (long)n, d_max.p));
     }
-    HIPCHK(h, hipGetLastError());
     uint32_t tot[2] = {0, 0}, mx = 0;
-    HIPCHK(h, hipMemcpyAsync(&tot[0], b->d_read_off + n, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&tot[1], b->d_ref_off + n, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&mx, d_max.p, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, fetch(h, {fetched(&tot[0], b->d_read_off + n), fetched(&tot[1], b->d_ref_off + n), fetched(&mx, d_max.p)}));
     if ((int)mx > ASM_MAX_LENGTH) return fail(h, ASM_EUNSUPPORTED, "streamed file: a sequence is longer than ASM_MAX_LENGTH");
     b->reads_bytes = tot[0], b->refs_bytes = tot[1], b->maxlen = (int)mx;
     HIPCHK(h, batch_alloc(b, &b->d_reads, b->reads_bytes + 16));
@@ -2000,11 +1994,10 @@ static int batch_from_device_text(asm_handle* h, const char* d_raw, size_t nbyte
     if (n > 0) {
         int64_t blocks = (n + 3) / 4;
         blocks = blocks > 256 * 16 ? 256 * 16 : blocks;
-        hipLaunchKernelGGL(seq_gather_kernel, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, h->stream, d_raw,
-                           (const unsigned long long*)d_sa.p, (const uint32_t*)b->d_read_off, (long)n, b->d_reads);
-        hipLaunchKernelGGL(seq_gather_kernel, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, h->stream, d_raw,
-                           (const unsigned long long*)d_sb.p, (const uint32_t*)b->d_ref_off, (long)n, b->d_refs);
-        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, launch(h, seq_gather_kernel, (unsigned)blocks, ASM_BLOCK, d_raw, (const unsigned long long*)d_sa.p,
+                         (const uint32_t*)b->d_read_off, (long)n, b->d_reads));
+        HIPCHK(h, launch(h, seq_gather_kernel, (unsigned)blocks, ASM_BLOCK, d_raw, (const unsigned long long*)d_sb.p,
+                         (const uint32_t*)b->d_ref_off, (long)n, b->d_refs));
     }
     return batch_finish(h, b);
 }

@@ -32,7 +32,7 @@ static unsigned map_grid(uint64_t n, const asm_handle* h) { /* grid-stride kerne
     return (unsigned)(want < 1 ? 1 : want > cap ? cap : want);
 }
 
-/* (hipcub's scratch MapTmp and map_exclusive_sum: asm_stream.h, which the streamed-file calls share) */
+/* (launch, fetch, hipcub's scratch MapTmp and map_exclusive_sum: asm_stream.h, which the streamed-file calls share) */
 
 template <class K, class V, class N> /* stable: equal keys keep their order */
 static hipError_t map_sort_pairs(asm_handle* h, MapTmp& tmp, K* key_in, K* key_out, V* val_in, V* val_out, N n, int end_bit) {
@@ -121,23 +121,19 @@ static int map_greedy(asm_handle* h, const asm_index* ix, const char* d_reads, c
     HIPCHK(h, wlen.alloc(sizeof(uint32_t) * cnt));
     HIPCHK(h, batch_alloc(b.get(), &b->d_read_off, sizeof(uint32_t) * cnt));
     HIPCHK(h, batch_alloc(b.get(), &b->d_ref_off, sizeof(uint32_t) * cnt));
-    hipLaunchKernelGGL(map_greedy_lengths_kernel, dim3(grid_for(nl + 1)), dim3(ASM_BLOCK), 0, h->stream, d_list, d_iread, (long)nl,
-                       d_roff, d_hits, (const unsigned long long*)ix->d_seq_off, qlen.p, wlen.p);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, map_greedy_lengths_kernel, grid_for(nl + 1), ASM_BLOCK, d_list, d_iread, (long)nl, d_roff, d_hits,
+                     (const unsigned long long*)ix->d_seq_off, qlen.p, wlen.p));
     HIPCHK(h, map_exclusive_sum(h, tmp, qlen.p, b->d_read_off, (int64_t)cnt));
     HIPCHK(h, map_exclusive_sum(h, tmp, wlen.p, b->d_ref_off, (int64_t)cnt));
     uint32_t tot[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(&tot[0], b->d_read_off + nl, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&tot[1], b->d_ref_off + nl, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, fetch(h, {fetched(&tot[0], b->d_read_off + nl), fetched(&tot[1], b->d_ref_off + nl)}));
     b->reads_bytes = tot[0], b->refs_bytes = tot[1];
     b->maxlen = maxm + 1; /* the window is at most one base longer than the read */
     HIPCHK(h, batch_alloc(b.get(), &b->d_reads, b->reads_bytes + 16));
     HIPCHK(h, batch_alloc(b.get(), &b->d_refs, b->refs_bytes + 16));
-    hipLaunchKernelGGL(map_greedy_gather_kernel, dim3(map_grid((uint64_t)nl * 64, h)), dim3(256), 0, h->stream, d_list, d_iread,
-                       (long)nl, d_reads, d_roff, d_hits, (const char*)ix->d_text, (const unsigned long long*)ix->d_seq_off,
-                       (const uint32_t*)b->d_read_off, (const uint32_t*)b->d_ref_off, b->d_reads, b->d_refs);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, map_greedy_gather_kernel, map_grid((uint64_t)nl * 64, h), 256, d_list, d_iread, (long)nl, d_reads, d_roff, d_hits,
+                     (const char*)ix->d_text, (const unsigned long long*)ix->d_seq_off, (const uint32_t*)b->d_read_off,
+                     (const uint32_t*)b->d_ref_off, b->d_reads, b->d_refs));
     rc = batch_finish(h, b.get());
     if (rc) return rc;
     asm_params gp;
@@ -180,20 +176,16 @@ static int map_front_seed(asm_handle* h, const asm_index* ix, int64_t n, const a
     HIPCHK(h, f.d_cnt.alloc(sizeof(unsigned long long) * (size_t)nw));
     HIPCHK(h, f.d_base.alloc(sizeof(unsigned long long) * (size_t)nw));
     HIPCHK(h, hipMemsetAsync(f.d_flags.p, 0, sizeof(uint32_t) * (size_t)n, h->stream));
-    hipLaunchKernelGGL(map_upper_kernel, dim3(map_grid(bytes, h)), dim3(256), 0, h->stream, f.d_reads.p, (unsigned long long)bytes);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, map_upper_kernel, map_grid(bytes, h), 256, f.d_reads.p, (unsigned long long)bytes));
     MapSeedArgs& sa = f.sa;
     sa.reads = f.d_reads.p, sa.roff = f.d_roff.p, sa.n = (long)n, sa.S = S, sa.P = P, sa.k = ix->k, sa.e = p->max_errors;
     sa.max_occ = p->max_occ, sa.text = ix->d_text, sa.ix_off = ix->d_off, sa.ix_pos = ix->d_pos;
     sa.seq_off = (const unsigned long long*)ix->d_seq_off, sa.n_seqs = (uint32_t)ix->n_seqs;
-    hipLaunchKernelGGL(map_seed_count_kernel, dim3(map_grid((uint64_t)nw, h)), dim3(256), 0, h->stream, sa, f.d_cnt.p, f.d_flags.p);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, map_seed_count_kernel, map_grid((uint64_t)nw, h), 256, sa, f.d_cnt.p, f.d_flags.p));
     MapTmp tmp(h);
     HIPCHK(h, map_exclusive_sum(h, tmp, f.d_cnt.p, f.d_base.p, nw));
     unsigned long long last[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(&last[0], f.d_base.p + nw - 1, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&last[1], f.d_cnt.p + nw - 1, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, fetch(h, {fetched(&last[0], f.d_base.p + nw - 1), fetched(&last[1], f.d_cnt.p + nw - 1)}));
     f.total = last[0] + last[1];
     return ASM_OK;
 }
@@ -233,9 +225,8 @@ static int map_seed_rounds(asm_handle* h, const MapFront& f, V verify) {
     if (f.total) HIPCHK(h, d_cand.alloc(sizeof(MapCand) * cap));
     for (unsigned long long c0 = 0; c0 < f.total; c0 += cap) {
         const unsigned long long c1 = std::min(f.total, c0 + cap);
-        hipLaunchKernelGGL(map_seed_emit_kernel, dim3(map_grid((uint64_t)f.nw, h)), dim3(256), 0, h->stream, f.sa,
-                           (const unsigned long long*)f.d_base.p, (const unsigned long long*)f.d_cnt.p, c0, c1, d_cand.p);
-        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, launch(h, map_seed_emit_kernel, map_grid((uint64_t)f.nw, h), 256, f.sa, (const unsigned long long*)f.d_base.p,
+                         (const unsigned long long*)f.d_cnt.p, c0, c1, d_cand.p));
         if (const int rc = verify((const MapCand*)d_cand.p, c1 - c0)) return rc;
     }
     return ASM_OK;
@@ -245,10 +236,8 @@ static int map_seed_rounds(asm_handle* h, const MapFront& f, V verify) {
 static hipError_t map_launch_verify(asm_handle* h, const asm_index* ix, const MapFront& f, int e, const MapCand* cand,
                                     unsigned long long nc, unsigned long long* keys) {
     return map_with_width(f.maxm, [&](auto w) {
-        hipLaunchKernelGGL(map_verify_kernel<decltype(w)::value>, dim3(map_grid(nc, h)), dim3(256), 0, h->stream, cand, nc,
-                           (const char*)f.d_reads.p, (const uint32_t*)f.d_roff.p, (const char*)ix->d_text,
-                           (const unsigned long long*)ix->d_seq_off, e, keys);
-        return hipGetLastError();
+        return launch(h, map_verify_kernel<decltype(w)::value>, map_grid(nc, h), 256, cand, nc, (const char*)f.d_reads.p,
+                      (const uint32_t*)f.d_roff.p, (const char*)ix->d_text, (const unsigned long long*)ix->d_seq_off, e, keys);
     });
 }
 
@@ -257,9 +246,8 @@ static hipError_t map_launch_verify_all(asm_handle* h, const asm_index* ix, cons
                                         unsigned long long nc, unsigned long long* counter, unsigned long long cap,
                                         unsigned long long* key, uint32_t* val) {
     return map_with_width(f.maxm, [&](auto w) {
-        hipLaunchKernelGGL(map_verify_all_kernel<decltype(w)::value>, dim3(map_grid(nc, h)), dim3(256), 0, h->stream, cand, nc,
-                           (const char*)f.d_reads.p, (const uint32_t*)f.d_roff.p, (const char*)ix->d_text, e, counter, cap, key, val);
-        return hipGetLastError();
+        return launch(h, map_verify_all_kernel<decltype(w)::value>, map_grid(nc, h), 256, cand, nc, (const char*)f.d_reads.p,
+                      (const uint32_t*)f.d_roff.p, (const char*)ix->d_text, e, counter, cap, key, val);
     });
 }
 
@@ -292,11 +280,7 @@ static int map_finish_launch(asm_handle* h, const asm_index* ix, const asm_map_p
     fa.nops = s.d_nops.p;
     const hipError_t launched = map_with_width(f.maxm, [&](auto w) {
         constexpr int W = decltype(w)::value;
-        if (iread)
-            hipLaunchKernelGGL((map_finish_kernel<W, true>), dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, fa);
-        else
-            hipLaunchKernelGGL((map_finish_kernel<W, false>), dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, fa);
-        return hipGetLastError();
+        return launch(h, iread ? map_finish_kernel<W, true> : map_finish_kernel<W, false>, map_grid((uint64_t)n, h), 256, fa);
     });
     HIPCHK(h, launched);
     return ASM_OK;
@@ -356,24 +340,19 @@ static int map_finish_device(asm_handle* h, const asm_index* ix, const asm_map_p
     MapTmp tmp(h);
     HIPCHK(h, d_flag.alloc(sizeof(uint32_t) * (n + 1)));
     HIPCHK(h, d_slot.alloc(sizeof(uint32_t) * (n + 1)));
-    hipLaunchKernelGGL(map_mapped_flag_kernel, dim3(grid_for((int64_t)n + 1)), dim3(ASM_BLOCK), 0, h->stream, (const MapHit*)s.d_hits.p,
-                       (long)n, d_flag.p);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, map_mapped_flag_kernel, grid_for((int64_t)n + 1), ASM_BLOCK, (const MapHit*)s.d_hits.p, (long)n, d_flag.p));
     HIPCHK(h, map_exclusive_sum(h, tmp, d_flag.p, d_slot.p, (int64_t)n + 1));
     uint32_t nl = 0;
-    HIPCHK(h, hipMemcpyAsync(&nl, d_slot.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, fetch(h, {fetched(&nl, d_slot.p + n)}));
     if (!nl) return ASM_OK;
     HIPCHK(h, d_list.alloc(sizeof(uint32_t) * nl));
     HIPCHK(h, d_cost.alloc(sizeof(int32_t) * nl));
-    hipLaunchKernelGGL(map_mapped_list_kernel, dim3(grid_for((int64_t)n)), dim3(ASM_BLOCK), 0, h->stream, (const uint32_t*)d_flag.p,
-                       (const uint32_t*)d_slot.p, (long)n, d_list.p);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, map_mapped_list_kernel, grid_for((int64_t)n), ASM_BLOCK, (const uint32_t*)d_flag.p, (const uint32_t*)d_slot.p,
+                     (long)n, d_list.p));
     if (const int rc = map_greedy(h, ix, f.d_reads.p, f.d_roff.p, s.d_hits.p, s.d_iread, d_list.p, (int64_t)nl, f.maxm, p->greedy_k, d_cost.p))
         return rc;
-    hipLaunchKernelGGL(map_cost_kernel, dim3(grid_for((int64_t)nl)), dim3(ASM_BLOCK), 0, h->stream, (const uint32_t*)d_list.p,
-                       (const int32_t*)d_cost.p, (long)nl, s.d_hits.p);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, map_cost_kernel, grid_for((int64_t)nl), ASM_BLOCK, (const uint32_t*)d_list.p, (const int32_t*)d_cost.p, (long)nl,
+                     s.d_hits.p));
     return ASM_OK;
 }
 
@@ -457,8 +436,7 @@ static int map_runs(asm_handle* h, const asm_index* ix, int64_t n, const asm_map
         for (;;) {
             HIPCHK(h, map_launch_verify_all(h, ix, f, p->max_errors, cand, nc, d_counter.p, rcap, d_rkey.p, d_rval.p));
             unsigned long long got = 0;
-            HIPCHK(h, hipMemcpyAsync(&got, d_counter.p, sizeof(got), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
+            HIPCHK(h, fetch(h, {fetched(&got, d_counter.p)}));
             if (got <= rcap) {
                 nr = got;
                 return ASM_OK;
@@ -512,10 +490,8 @@ static int map_all_items(asm_handle* h, const asm_index* ix, int64_t n, const as
     HIPCHK(h, it.d_nh.alloc(sizeof(uint32_t) * (size_t)n));
     HIPCHK(h, it.d_dbest.alloc(sizeof(uint32_t) * (size_t)n));
     MapSelectArgs sel = map_select_args(ix, f, it.runs, n, p->max_errors, strata, max_hits, it.d_nh.p, it.d_dbest.p);
-    hipLaunchKernelGGL(map_select_count_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(n_hits, it.d_nh.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, launch(h, map_select_count_kernel, map_grid((uint64_t)n, h), 256, sel));
+    HIPCHK(h, fetch(h, {fetched(n_hits, it.d_nh.p, (size_t)n)}));
     /* items: max(1, min(n_hits, max_hits)) per read, in read-then-rank order; dirs: (m + 1) words per item */
     std::vector<uint32_t>& ibase = it.ibase;
     ibase.assign((size_t)n + 1, 0u);
@@ -538,8 +514,7 @@ static int map_all_items(asm_handle* h, const asm_index* ix, int64_t n, const as
     HIPCHK(h, hipMemcpyAsync(it.d_ibase.p, ibase.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(it.d_dbase.p, dbase.data(), sizeof(unsigned long long) * (size_t)n, hipMemcpyHostToDevice, h->stream));
     sel.ibase = it.d_ibase.p, sel.dbase = it.d_dbase.p, sel.iread = it.d_iread.p, sel.ikey = it.d_ikey.p, sel.idirs = it.d_idirs.p;
-    hipLaunchKernelGGL(map_select_emit_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, map_select_emit_kernel, map_grid((uint64_t)n, h), 256, sel));
     return ASM_OK;
 }
 
@@ -615,19 +590,16 @@ static int map_pairs_front_seed(asm_handle* h, const asm_index* ix, int64_t np, 
     HIPCHK(h, pf.d_lbase.alloc(sizeof(uint32_t) * ((size_t)n + 1)));
     const MapSelectArgs sel = map_select_args(ix, f, pf.runs, n, e, e, 1, pf.d_nh.p, pf.d_dbest.p);
     HIPCHK(h, hipMemsetAsync(pf.d_nh.p + n, 0, sizeof(uint32_t), h->stream));
-    hipLaunchKernelGGL(map_select_count_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, map_select_count_kernel, map_grid((uint64_t)n, h), 256, sel));
     MapTmp tmp(h);
     HIPCHK(h, map_exclusive_sum(h, tmp, pf.d_nh.p, pf.d_lbase.p, n + 1));
     uint32_t nloci = 0;
-    HIPCHK(h, hipMemcpyAsync(&nloci, pf.d_lbase.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, fetch(h, {fetched(&nloci, pf.d_lbase.p + n)}));
     HIPCHK(h, pf.d_lkey.alloc(sizeof(unsigned long long) * ((size_t)nloci + 1)));
     HIPCHK(h, pf.d_lsplit.alloc(sizeof(uint32_t) * (size_t)n));
     HIPCHK(h, pf.d_lbest.alloc(sizeof(unsigned long long) * (size_t)n));
-    hipLaunchKernelGGL(map_loci_emit_kernel, dim3(map_grid((uint64_t)n, h)), dim3(256), 0, h->stream, sel, (const uint32_t*)pf.d_lbase.p,
-                       pf.d_lkey.p, pf.d_lsplit.p, pf.d_lbest.p);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, map_loci_emit_kernel, map_grid((uint64_t)n, h), 256, sel, (const uint32_t*)pf.d_lbase.p, pf.d_lkey.p, pf.d_lsplit.p,
+                     pf.d_lbest.p));
     /* pairing */
     HIPCHK(h, pf.d_ikey.alloc(sizeof(unsigned long long) * (size_t)n));
     HIPCHK(h, pf.d_nconc.alloc(sizeof(uint32_t) * (size_t)np));
@@ -645,19 +617,16 @@ static int map_pairs_front_seed(asm_handle* h, const asm_index* ix, int64_t np, 
     pa.lkey = pf.d_lkey.p, pa.min_insert = pp->min_insert, pa.max_insert = pp->max_insert, pa.rescue = pp->rescue_errors;
     pa.ikey = pf.d_ikey.p, pa.n_conc = pf.d_nconc.p, pa.state = pf.d_state.p, pa.anchors = pf.d_anchors.p, pa.n_anchors = pf.d_nanch.p;
     pa.rslot = pf.d_rslot.p, pa.seq_off = (const unsigned long long*)ix->d_seq_off;
-    hipLaunchKernelGGL(map_pair_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, pa);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, map_pair_kernel, map_grid((uint64_t)np, h), 256, pa));
     if (rescue) {
         /* one thread per (anchor, tile of ends); grid-stride over the anchor count the pair kernel left on the device (<= 2 np) */
         const uint32_t ntile = (uint32_t)((pp->max_insert - pp->min_insert + MAP_RESCUE_TILE) / MAP_RESCUE_TILE);
         const hipError_t launched = map_with_width(f.maxm, [&](auto w) {
-            hipLaunchKernelGGL(map_rescue_kernel<decltype(w)::value>, dim3(map_grid((uint64_t)(2 * pa.np) * ntile, h)), dim3(256), 0,
-                               h->stream, pa, (const char*)f.d_reads.p, (const char*)ix->d_text, ntile, pf.d_rslot.p);
-            return hipGetLastError();
+            return launch(h, map_rescue_kernel<decltype(w)::value>, map_grid((uint64_t)(2 * pa.np) * ntile, h), 256, pa,
+                          (const char*)f.d_reads.p, (const char*)ix->d_text, ntile, pf.d_rslot.p);
         });
         HIPCHK(h, launched);
-        hipLaunchKernelGGL(map_rescue_pick_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, pa);
-        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, launch(h, map_rescue_pick_kernel, map_grid((uint64_t)np, h), 256, pa));
     }
     return ASM_OK;
 }
@@ -755,16 +724,12 @@ static int map_chunk_pairs_all(asm_handle* h, const asm_index* ix, int64_t np, c
     MapPairAllArgs aa = {};
     aa.pa = pf.pa, aa.strata = strata, aa.max_pairs = max_pairs, aa.n_pairs = d_np.p, aa.sums = d_sums.p, aa.nitem = d_nitem.p;
     aa.ndirs = d_ndirs.p, aa.ibase = d_ibase.p, aa.dbase = d_dbase.p;
-    hipLaunchKernelGGL(map_pair_count_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, aa);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, map_pair_count_kernel, map_grid((uint64_t)np, h), 256, aa));
     MapTmp tmp(h);
     HIPCHK(h, map_exclusive_sum(h, tmp, d_nitem.p, d_ibase.p, np + 1));
     HIPCHK(h, map_exclusive_sum(h, tmp, d_ndirs.p, d_dbase.p, np + 1));
     unsigned long long tot[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(n_pairs, d_np.p, sizeof(uint32_t) * (size_t)np, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&tot[0], d_ibase.p + np, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&tot[1], d_dbase.p + np, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, fetch(h, {fetched(n_pairs, d_np.p, (size_t)np), fetched(&tot[0], d_ibase.p + np), fetched(&tot[1], d_dbase.p + np)}));
     const int64_t ni = (int64_t)tot[0];
     /* ranks >= 1: items, finish kernel (the item-list instantiation of asm_map_reads_all) */
     MapFinish fin(h);
@@ -773,8 +738,7 @@ static int map_chunk_pairs_all(asm_handle* h, const asm_index* ix, int64_t np, c
         HIPCHK(h, d_ikey.alloc(sizeof(unsigned long long) * (size_t)ni));
         HIPCHK(h, d_idirs.alloc(sizeof(unsigned long long) * (size_t)ni));
         aa.iread = d_iread.p, aa.ikey = d_ikey.p, aa.idirs = d_idirs.p;
-        hipLaunchKernelGGL(map_pair_emit_kernel, dim3(map_grid((uint64_t)np, h)), dim3(256), 0, h->stream, aa);
-        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, launch(h, map_pair_emit_kernel, map_grid((uint64_t)np, h), 256, aa));
         if (const int rc = map_finish_launch(h, ix, p, f, ni, d_ikey.p, d_iread.p, d_idirs.p, tot[1], cg.cap, fin)) return rc;
     }
     /* rank 0: asm_map_pairs' answer */
@@ -844,16 +808,12 @@ int asm_index_build(asm_handle* h, const char* text, const uint64_t* seq_off, in
         HIPCHK(h, keys.alloc(sizeof(uint32_t) * len));
         HIPCHK(h, keys2.alloc(sizeof(uint32_t) * len));
         HIPCHK(h, vals.alloc(sizeof(uint32_t) * len));
-        hipLaunchKernelGGL(map_upper_kernel, dim3(map_grid(len, h)), dim3(256), 0, h->stream, ix->d_text, (unsigned long long)len);
-        HIPCHK(h, hipGetLastError());
-        hipLaunchKernelGGL(map_kmer_key_kernel, dim3(map_grid(len, h)), dim3(256), 0, h->stream, (const char*)ix->d_text,
-                           (unsigned long long)len, (const unsigned long long*)ix->d_seq_off, (uint32_t)n_seqs, k, keys.p, vals.p);
-        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, launch(h, map_upper_kernel, map_grid(len, h), 256, ix->d_text, (unsigned long long)len));
+        HIPCHK(h, launch(h, map_kmer_key_kernel, map_grid(len, h), 256, (const char*)ix->d_text, (unsigned long long)len,
+                         (const unsigned long long*)ix->d_seq_off, (uint32_t)n_seqs, k, keys.p, vals.p));
         /* stable: positions ascend inside a bucket */
         HIPCHK(h, map_sort_pairs(h, tmp, keys.p, keys2.p, vals.p, ix->d_pos, (uint32_t)len, 2 * k + 1));
-        hipLaunchKernelGGL(map_bucket_offsets_kernel, dim3(map_grid(nb, h)), dim3(256), 0, h->stream, (const uint32_t*)keys2.p,
-                           (unsigned long long)len, nb, ix->d_off);
-        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, launch(h, map_bucket_offsets_kernel, map_grid(nb, h), 256, (const uint32_t*)keys2.p, (unsigned long long)len, nb, ix->d_off));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     } else {
         HIPCHK(h, hipMemsetAsync(ix->d_off, 0, sizeof(uint32_t) * nb, h->stream));

@@ -1,5 +1,6 @@
-// Device side of the two streamed-file calls (asm_stream_seq_file, asm_map_file): hipcub's scratch and scans, the newline index of
-// a chunk of text in HBM, and the input pipeline — reader thread (asm_host.h) -> pinned slots -> copy-in stream -> two device
+// Device side of the streamed-file calls (asm_stream_seq_file, asm_map_file, asm_map_pairs_file): the checked launch and the
+// "scalars back, one wait" step that the mapper's host stages use too, hipcub's scratch and scans, the newline index of a chunk of
+// text in HBM, and the input pipeline — reader thread (asm_host.h) -> pinned slots -> copy-in stream -> two device
 // buffers -> the caller's processing on the handle's stream.  asm_capi.hip includes this file inside its extern "C" block.
 #pragma once
 
@@ -13,6 +14,30 @@ extern "C++" {
             return fail(h, _e == hipErrorOutOfMemory ? ASM_ENOMEM : ASM_ENODEVICE,               \
                         std::string(who) + ": " + #call + ": " + hipGetErrorString(_e));         \
     } while (0)
+
+/* A kernel launch on the handle's stream and what hipGetLastError() says about it: one expression for HIPCHK / STREAM_TRY */
+template <class... P, class... A>
+static hipError_t launch(asm_handle* h, void (*kernel)(P...), unsigned grid, unsigned block, A&&... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, h->stream, std::forward<A>(args)...);
+    return hipGetLastError();
+}
+
+/* One copy of fetch(): `bytes` from device memory into host memory */
+struct Fetch {
+    void* dst;
+    const void* src;
+    size_t bytes;
+};
+template <class T>
+static Fetch fetched(T* dst, const T* src, size_t count = 1) {
+    return {dst, src, sizeof(T) * count};
+}
+/* "Scan, then read the totals": the copies to the host on the handle's stream, in order, and then one wait for all of them */
+static hipError_t fetch(asm_handle* h, std::initializer_list<Fetch> what) {
+    for (const Fetch& f : what)
+        if (const hipError_t e = hipMemcpyAsync(f.dst, f.src, f.bytes, hipMemcpyDeviceToHost, h->stream)) return e;
+    return hipStreamSynchronize(h->stream);
+}
 
 /* hipcub's temporary storage: grows to the largest request; the old block goes back to the pool in stream order */
 struct MapTmp {
@@ -42,13 +67,10 @@ static hipError_t newline_index(asm_handle* h, MapTmp& tmp, const char* d_raw, s
     Scratch<uint32_t> d_tile(h), d_tbase(h);
     hipError_t e = d_tile.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1));
     if (e == hipSuccess) e = d_tbase.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1));
+    if (e == hipSuccess) e = launch(h, seq_count_kernel, (unsigned)ntiles, 256, d_raw, (long)nbytes, d_tile.p);
+    if (e == hipSuccess) e = map_exclusive_sum(h, tmp, d_tile.p, d_tbase.p, (int64_t)ntiles);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(seq_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, h->stream, d_raw, (long)nbytes, d_tile.p);
-    e = map_exclusive_sum(h, tmp, d_tile.p, d_tbase.p, (int64_t)ntiles);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(seq_index_kernel, dim3((unsigned)ntiles), dim3(256), 0, h->stream, d_raw, (long)nbytes, (const uint32_t*)d_tbase.p,
-                       d_nl, lines);
-    return hipGetLastError();
+    return launch(h, seq_index_kernel, (unsigned)ntiles, 256, d_raw, (long)nbytes, (const uint32_t*)d_tbase.p, d_nl, lines);
 }
 
 /* The input side of one streamed call: the file, the copy-in stream, three pinned slots in rotation (the reader thread fills them),

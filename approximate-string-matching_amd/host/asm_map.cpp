@@ -258,6 +258,13 @@ static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vecto
     return 0;
 }
 
+/* the second report line of --stream and --stream-pairs: what the two calls' stats share */
+template <class Stats>
+static void report_streamed(const Stats& st) {
+    fprintf(stderr, "asm-map: streamed %lld chunks, %lld bytes in, %lld bytes out, %.3f s (reader busy %.3f s, writer busy %.3f s)\n",
+            (long long)st.chunks, (long long)st.bytes_in, (long long)st.bytes_out, st.seconds, st.seconds_read, st.seconds_write);
+}
+
 int main(int argc, char** argv) {
     std::string ref_path, read_path, read2_path, out_path = "out.sam";
     asm_pair_params pp = {-1, -1, -1};
@@ -391,8 +398,7 @@ int main(int argc, char** argv) {
         if (rc) return 1;
         fprintf(stderr, "asm-map: %lld reads, %lld mapped, %lld longer than %d (unmapped)\n", (long long)st.reads, (long long)st.mapped,
                 (long long)st.too_long, ASM_MAP_MAX_READ);
-        fprintf(stderr, "asm-map: streamed %lld chunks, %lld bytes in, %lld bytes out, %.3f s (reader busy %.3f s, writer busy %.3f s)\n",
-                (long long)st.chunks, (long long)st.bytes_in, (long long)st.bytes_out, st.seconds, st.seconds_read, st.seconds_write);
+        report_streamed(st);
         return 0;
     }
     if (stream_pairs) { /* the library reads both files, pairs, maps, formats and writes */
@@ -408,8 +414,7 @@ int main(int argc, char** argv) {
         if (rc) return 1;
         fprintf(stderr, "asm-map: %lld pairs, %lld proper, %lld mates rescued\n", (long long)st.pairs, (long long)st.proper,
                 (long long)st.rescued);
-        fprintf(stderr, "asm-map: streamed %lld chunks, %lld bytes in, %lld bytes out, %.3f s (reader busy %.3f s, writer busy %.3f s)\n",
-                (long long)st.chunks, (long long)st.bytes_in, (long long)st.bytes_out, st.seconds, st.seconds_read, st.seconds_write);
+        report_streamed(st);
         return 0;
     }
     fputs(header.c_str(), out);

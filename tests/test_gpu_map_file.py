@@ -250,6 +250,30 @@ def test_chunking_does_not_change_the_output(asm, engine, ref, index, tmp_path, 
             monkeypatch.delenv("ASM_MAP_CHUNK")
 
 
+@pytest.mark.parametrize("at", [0, 6])
+def test_record_longer_than_the_pinned_slot(engine, ref, index, tmp_path, at):
+    """chunk_bytes=1000 gives pinned slots of 1000 + 1000 / 4 + 4096 = 5,346 bytes; a record whose sequence and quality are 6,000
+    bytes each does not fit one, so the reader has the slot replaced by a larger one: as the file's first record, and in the middle
+    of it behind a carry.  The bytes are those of the library's calls and those of the default chunk, which holds the whole file."""
+    rng = random.Random(73)
+    recs = records_for(make_reads(ref, 2, 12, seed=79), seed=7)
+    recs.insert(at, ("long", "".join(rng.choice("ACGT") for _ in range(6000)), quals(rng, 6000)))
+    fq = tmp_path / "r.fq"
+    write_fastq(fq, recs)
+    want = expected_lines(engine, index, recs, 2)
+    out = {}
+    for chunk_bytes in (0, 1000):
+        sam = tmp_path / ("c%d.sam" % chunk_bytes)
+        st = engine.map_file(index, NAMES, str(fq), str(sam), 2, chunk_bytes=chunk_bytes)
+        got = sam_lines(sam)
+        compare(got, want)
+        check_stats(st, got, recs)
+        assert st["too_long"] == 1 and st["bytes_in"] == os.path.getsize(fq)
+        out[chunk_bytes] = (open(sam, "rb").read(), st["chunks"])
+    assert out[1000][0] == out[0][0]
+    assert out[0][1] == 1 and out[1000][1] > 1
+
+
 def test_format_corners(engine, ref, index, tmp_path):
     rng = random.Random(61)
     good = make_reads(ref, 2, 40, seed=59)

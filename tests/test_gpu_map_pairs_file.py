@@ -202,6 +202,30 @@ def test_chunking_does_not_change_the_output(asm, engine, ref, index, tmp_path, 
         small.close()
 
 
+@pytest.mark.parametrize("at", [0, 6])
+def test_record_longer_than_the_pinned_slot(engine, ref, index, tmp_path, at):
+    """chunk_bytes=1000 gives pinned slots of 1000 + 1000 / 4 + 4096 = 5,346 bytes; a mate 1 whose sequence and quality are 6,000
+    bytes each does not fit one, so the reader has the slot replaced by a larger one: as the files' first pair, and in the middle of
+    them behind the carries.  The bytes are those of the library's call and those of the default chunk, which holds both files."""
+    rng = random.Random(923)
+    r1s, r2s, _ = make_pairs(ref, E, 12, seed=929)
+    recs1, recs2 = mates_for(r1s, r2s, seed=15)
+    recs1.insert(at, ("long/1", "".join(rng.choice("ACGT") for _ in range(6000)), quals(rng, 6000)))
+    recs2.insert(at, ("long/2", ref[1][30_000:30_100].upper(), quals(rng, 100)))
+    want, counts = expected_lines(engine, index, recs1, recs2, E, 4)
+    assert counts["unsent"] == 1
+    out = {}
+    for chunk_bytes in (0, 1000):
+        st, sam = run_file(engine, index, tmp_path, recs1, recs2, 4, tag="c%d" % chunk_bytes, chunk_bytes=chunk_bytes)
+        got = sam_lines(sam)
+        compare(got, want)
+        check_stats(st, counts, got, 0, sam)
+        assert st["unsent"] == 1
+        out[chunk_bytes] = (open(sam, "rb").read(), st["chunks"])
+    assert out[1000][0] == out[0][0]
+    assert out[0][1] == 1 and out[1000][1] > 1
+
+
 def test_format_corners(engine, ref, index, tmp_path):
     rng = random.Random(919)
     r1s, r2s, _ = make_pairs(ref, E, 48, seed=913)
