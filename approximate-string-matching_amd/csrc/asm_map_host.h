@@ -370,7 +370,7 @@ struct MapItems {
     }
 };
 
-static const asm_map_hit MAP_UNUSED_SLOT = {-1, 0, 0, -1, 0, 0, -1};
+static const asm_map_hit MAP_UNUSED_SLOT = MAP_HIT_UNMAPPED;
 
 /* asm_map_reads' keys of a fronted chunk: the seeding rounds with map_verify_kernel<W>, every read's best end in d_keys */
 static int map_best_keys(asm_handle* h, const asm_index* ix, int64_t n, const asm_map_params* p, const MapFront& f,

@@ -28,6 +28,7 @@ from tests import map_cases as mc
 from tests import test_gpu_map_all as tall
 from tests import test_gpu_map_file as tfile
 from tests import test_gpu_map_pairs as tpairs
+from tests.map_cases import mid_edit, pair_reads
 from tests.test_gpu_map import got_tuple, make_reference, strand_read, walk_cigar
 from tests.test_map_all_host import build_bruteforce_all
 from tests.test_map_host import BASES, bf_map, build_bruteforce, revcomp
@@ -175,49 +176,6 @@ def test_each_width_equals_brute_force(asm, engine, oracle, cells, seqs, c):
     costs = oracle.greedy(asm.HostBatch.from_strings(greedy_pairs(reads, up, out, idx)), k=3, mode=1)
     assert np.array_equal(out["greedy_cost"][idx], costs)
     assert np.array_equal(out["mapq"][idx], np.minimum(254, 60 + costs))
-
-
-def mid_edit(rng, src, m, x, kind):
-    """a forward read of m bases from the start of src (upper case, at least m + x long) with x edits in its middle: a run of
-    inserted bases, a run of deleted reference bases, or spaced substitutions; -> (read, reference bases spanned)"""
-    h = m // 2
-    if kind == "ins":
-        ins = "".join(rng.choice([b for b in BASES if b not in (src[h - 1], src[h])]) for _ in range(x))
-        return src[:h] + ins + src[h:m - x], m - x
-    if kind == "del":
-        return src[:h] + src[h + x:m + x], m + x
-    q = list(src[:m])
-    for t in range(x):
-        p = int((t + 0.5) * m / x)
-        q[p] = rng.choice([b for b in BASES if b != q[p]])
-    return "".join(q), m
-
-
-def pair_reads(seqs, lengths, e, k, seed):
-    """FR pairs with mates of one length each: mate 1 an exact copy, mate 2 with e edits (concordant), with more than e edits or
-    too short to seed (left to the rescue)"""
-    rng = random.Random(seed)
-    up = upper(seqs)
-    r1s, r2s = [], []
-    for m in lengths:
-        if m < (e + 1) * k:
-            continue
-        for v in range(6):
-            r = mc.BIG[v % 3]
-            f = 2 * m + 40 + rng.randrange(60)
-            a = rng.randrange(1000, len(up[r]) - f - 1000)
-            x = e if v < 3 else min(15, e + 2)
-            kind = ("ins", "del", "sub")[v % 3]
-            span = m + (x if kind == "del" else -x if kind == "ins" else 0)  # mate 2 keeps its end a + f
-            q2, _ = mid_edit(rng, up[r][a + f - span:a + f + 40], m, x, kind)
-            if v == 5:
-                q2 = q2[:max(8, min(m, (e + 1) * k - 1))]  # too short to seed when e > 0
-            q1, q2 = up[r][a:a + m], revcomp(q2)
-            if "N" in up[r][a - 40:a + f + 40]:
-                continue
-            r1s.append(q1 if v % 2 else q2)
-            r2s.append(q2 if v % 2 else q1)
-    return r1s, r2s
 
 
 @pytest.mark.parametrize("c", SWEEP, ids=cell_id)
