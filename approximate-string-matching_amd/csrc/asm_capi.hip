@@ -41,6 +41,48 @@
 #include "asm_fastq.h"
 #include "asm_sam.h"
 
+/* What asm_run_benchmark_async (asm_step.h) keeps from call to call: the library's three streams beside the caller's, the events
+ * that order the four, and the bookkeeping of a run of pipelined (repack = 2 / 3) calls. */
+struct StepPipe {
+    hipStream_t side_stream = nullptr;    /* Greedy beside the NW -> LEAP chain */
+    hipStream_t pack_stream = nullptr;    /* repack = 2 / 3: packs for this call while the previous call still aligns */
+    hipStream_t acc_stream = nullptr;     /* repack = 3: NW -> LEAP -> counters of a call, the counters behind both of its chains */
+    hipEvent_t ev_packed = nullptr, ev_fork = nullptr, ev_join = nullptr, ev_leap = nullptr;
+    hipEvent_t ev_gate = nullptr;         /* repack = 2: the next call's pack starts behind this point of the current call */
+    bool gate_set = false;
+    hipEvent_t ev_tail = nullptr;         /* the end of the latest overlapped call (repack = 3), on acc_stream */
+    bool tail_set = false;                /* there were such calls: join_into before other streams or the host rely on them; only a
+                                             later call with repack != 3, which joins them into the caller's stream for good, clears it */
+    hipEvent_t ev_out[2] = {nullptr, nullptr}; /* repack = 3: the counters of the call before last (same output arrays) are done */
+    unsigned calls3 = 0;                  /* overlapped calls of this run: call c records ev_out[c & 1], call c + 2 waits for it */
+    const void* last3_out[3] = {nullptr, nullptr, nullptr}; /* the output arrays of the previous overlapped call (misuse guard) */
+    bool last3_valid = false;
+    bool pipe_prev = false;               /* the previous call packed on pack_stream: it is ordered behind the caller's stream already */
+    hipError_t open() { /* the streams in this order: the runtime deals its hardware queues out by it */
+        for (hipStream_t* s : {&side_stream, &pack_stream, &acc_stream})
+            if (hipError_t e = hipStreamCreateWithFlags(s, hipStreamNonBlocking)) return e;
+        for (hipEvent_t* ev : {&ev_packed, &ev_fork, &ev_join, &ev_leap, &ev_gate, &ev_tail, &ev_out[0], &ev_out[1]})
+            if (hipError_t e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) return e;
+        return hipSuccess;
+    }
+    void close() { /* a partly opened one too */
+        for (hipStream_t s : {side_stream, pack_stream, acc_stream})
+            if (s) (void)hipStreamDestroy(s);
+        for (hipEvent_t ev : {ev_packed, ev_fork, ev_join, ev_leap, ev_gate, ev_tail, ev_out[0], ev_out[1]})
+            if (ev) (void)hipEventDestroy(ev);
+    }
+    /* joins the overlapped calls into stream s: everything they enqueued is ordered before what s gets next */
+    hipError_t join_into(hipStream_t s) const { return tail_set ? hipStreamWaitEvent(s, ev_tail, 0) : hipSuccess; }
+    /* the misuse guard of repack = 3: would this call write an array the previous overlapped call's counters may still read? */
+    bool names_previous_outputs(const void* nw, const void* leap, const void* greedy) const {
+        return last3_valid && ((nw && nw == last3_out[0]) || (leap && leap == last3_out[1]) || (greedy && greedy == last3_out[2]));
+    }
+    /* Forgetting the run, in the halves its two callers need.  A call with repack != 3: the next overlapped call starts a new run */
+    void end_overlapped_run() { last3_valid = false, calls3 = 0; }
+    /* ... asm_pipeline_join_async: the next pipelined call forks from the caller's stream again, with any output set (calls3 goes on) */
+    void rejoin_caller() { pipe_prev = false, last3_valid = false; }
+};
+
 struct asm_handle {
     unsigned long long serial = 0;        /* unique over the life of the process: a batch names its owner by (pointer, serial), so a
                                              new handle that happens to get a destroyed one's address is not taken for it */
@@ -48,21 +90,8 @@ struct asm_handle {
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     unsigned long long* d_pair_queue = nullptr; /* chunk counter of the wave-per-pair Greedy kernel (PairQueue, asm_wave.h) */
-    hipStream_t side_stream = nullptr;    /* asm_run_benchmark_async runs Greedy beside the NW -> LEAP chain */
-    hipStream_t pack_stream = nullptr;    /* ... and, with repack = 2, packs for this call while the previous call still aligns */
-    hipEvent_t ev_packed = nullptr;
-    hipEvent_t ev_nw = nullptr;
-    hipStream_t acc_stream = nullptr;     /* repack = 3: the counters of a call, behind both of its chains */
-    hipEvent_t ev_leap = nullptr, ev_tail = nullptr;
-    bool tail_set = false;
-    hipEvent_t ev_out[2] = {nullptr, nullptr}; /* repack = 3: the counters of the call before last (same output arrays) are done */
-    unsigned calls3 = 0;
-    const void* last3_out[3] = {nullptr, nullptr, nullptr}; /* the output arrays of the previous overlapped call (misuse guard) */
-    bool last3_valid = false;
-    bool pipe_prev = false;               /* the previous asm_run_benchmark_async call was a pipelined one (repack 2 or 3) */
-    hipEvent_t ev_gate = nullptr;         /* repack = 2: the next call's pack starts behind this point of the current call */
-    bool gate_set = false;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_switch = nullptr;
+    StepPipe pipe;                        /* asm_run_benchmark_async: the library's own streams and what orders them (asm_step.h) */
+    hipEvent_t ev_switch = nullptr;       /* switch_stream: the new stream behind the old one */
     bool overlap = true;                  /* ASM_OVERLAP=0: everything on one stream */
     std::string err;
     int num_cus = 256;
@@ -275,7 +304,7 @@ static void batch_release(asm_batch* b) {
     asm_handle* const o = b->owner;
     /* the pool hands blocks out again in the order of o->stream; overlapped calls that were never joined may still read these
      * on the library's own streams */
-    if (o->tail_set) (void)hipStreamWaitEvent(o->stream, o->ev_tail, 0);
+    (void)o->pipe.join_into(o->stream);
     pool_free(o, b->d_reads);
     pool_free(o, b->d_refs);
     pool_free(o, b->d_read_off);
@@ -675,20 +704,9 @@ int asm_device_count(void) {
 static void handle_teardown(asm_handle* h) {
     (void)hipSetDevice(h->device);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
+    h->pipe.close();
     if (h->d_pair_queue) (void)hipFree(h->d_pair_queue);
     if (h->d_sort) (void)hipFree(h->d_sort);
-    if (h->pack_stream) (void)hipStreamDestroy(h->pack_stream);
-    if (h->ev_packed) (void)hipEventDestroy(h->ev_packed);
-    if (h->ev_gate) (void)hipEventDestroy(h->ev_gate);
-    if (h->ev_leap) (void)hipEventDestroy(h->ev_leap);
-    if (h->ev_tail) (void)hipEventDestroy(h->ev_tail);
-    for (hipEvent_t ev : h->ev_out)
-        if (ev) (void)hipEventDestroy(ev);
-    if (h->acc_stream) (void)hipStreamDestroy(h->acc_stream);
-    if (h->ev_nw) (void)hipEventDestroy(h->ev_nw);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
     if (h->d_todo) (void)hipFree(h->d_todo);
     for (auto& t : h->g3_tables)
@@ -718,18 +736,8 @@ int asm_create(asm_handle** out, int device) {
     HIPCHK(h, hipSetDevice(device));
     HIPCHK(h, hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
     h->stream = h->own_stream;
-    HIPCHK(h, hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
+    HIPCHK(h, h->pipe.open());
     HIPCHK(h, hipMalloc((void**)&h->d_pair_queue, sizeof(unsigned long long)));
-    HIPCHK(h, hipStreamCreateWithFlags(&h->pack_stream, hipStreamNonBlocking));
-    HIPCHK(h, hipEventCreateWithFlags(&h->ev_packed, hipEventDisableTiming));
-    HIPCHK(h, hipEventCreateWithFlags(&h->ev_gate, hipEventDisableTiming));
-    HIPCHK(h, hipStreamCreateWithFlags(&h->acc_stream, hipStreamNonBlocking));
-    HIPCHK(h, hipEventCreateWithFlags(&h->ev_nw, hipEventDisableTiming));
-    HIPCHK(h, hipEventCreateWithFlags(&h->ev_leap, hipEventDisableTiming));
-    HIPCHK(h, hipEventCreateWithFlags(&h->ev_tail, hipEventDisableTiming));
-    for (hipEvent_t& ev : h->ev_out) HIPCHK(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    HIPCHK(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    HIPCHK(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
     HIPCHK(h, hipEventCreateWithFlags(&h->ev_switch, hipEventDisableTiming));
     hipDeviceProp_t prop;
     HIPCHK(h, hipGetDeviceProperties(&prop, device));
@@ -784,7 +792,7 @@ static int switch_stream(asm_handle* h, hipStream_t next) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipEventRecord(h->ev_switch, h->stream));
     HIPCHK(h, hipStreamWaitEvent(next, h->ev_switch, 0));
-    if (h->tail_set) HIPCHK(h, hipStreamWaitEvent(next, h->ev_tail, 0)); /* overlapped calls end on the library's own streams */
+    HIPCHK(h, h->pipe.join_into(next)); /* overlapped calls end on the library's own streams */
     h->stream = next;
     return ASM_OK;
 }
@@ -806,16 +814,7 @@ int asm_synchronize(asm_handle* h) {
     if (!h) return fail(nullptr, ASM_EINVAL, "asm_synchronize: NULL handle");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->tail_set) HIPCHK(h, hipStreamSynchronize(h->acc_stream)); /* calls with repack = 3 end on the library's own streams */
-    return ASM_OK;
-}
-
-int asm_pipeline_join_async(asm_handle* h) {
-    if (!h) return fail(nullptr, ASM_EINVAL, "asm_pipeline_join_async: NULL handle");
-    HIPCHK(h, hipSetDevice(h->device));
-    if (h->tail_set) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_tail, 0));
-    h->pipe_prev = false; /* the next pipelined call starts behind this point of the caller's stream: any output set may follow */
-    h->last3_valid = false;
+    if (h->pipe.tail_set) HIPCHK(h, hipStreamSynchronize(h->pipe.acc_stream)); /* calls with repack = 3 end on the library's own streams */
     return ASM_OK;
 }
 
@@ -1672,279 +1671,7 @@ int asm_accuracy_async(asm_handle* h, const int32_t* d_nw, const int32_t* d_leap
     return ASM_OK;
 }
 
-int asm_profile_enable(asm_handle* h, int max_calls, unsigned kernel_mask) {
-    if (!h || max_calls < 0) return fail(h, ASM_EINVAL, "asm_profile_enable: bad argument");
-    h->prof_select = kernel_mask & 0xfu;
-    HIPCHK(h, hipSetDevice(h->device));
-    for (hipEvent_t ev : h->prof_ev) (void)hipEventDestroy(ev);
-    h->prof_ev.clear();
-    h->prof_mask.clear();
-    h->prof_cap = 0;
-    for (int i = 0; i < 8 * max_calls; i++) {
-        hipEvent_t ev;
-        HIPCHK(h, hipEventCreate(&ev));
-        h->prof_ev.push_back(ev);
-    }
-    h->prof_cap = max_calls;
-    return ASM_OK;
-}
-
-int asm_profile_read(asm_handle* h, float* ms, int cap_calls, int* n_calls) {
-    if (!h || !n_calls || (cap_calls > 0 && !ms)) return fail(h, ASM_EINVAL, "asm_profile_read: NULL argument");
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->side_stream) HIPCHK(h, hipStreamSynchronize(h->side_stream));
-    if (h->pack_stream) HIPCHK(h, hipStreamSynchronize(h->pack_stream));
-    if (h->acc_stream) HIPCHK(h, hipStreamSynchronize(h->acc_stream));
-    const int n = (int)h->prof_mask.size();
-    *n_calls = n;
-    for (int c = 0; c < n && c < cap_calls; c++)
-        for (int q = 0; q < 4; q++) {
-            float v = -1.0f;
-            if (h->prof_mask[(size_t)c] & (1u << q))
-                HIPCHK(h, hipEventElapsedTime(&v, h->prof_ev[(size_t)(8 * c + 2 * q)], h->prof_ev[(size_t)(8 * c + 2 * q + 1)]));
-            ms[4 * c + q] = v;
-        }
-    return ASM_OK;
-}
-
-/* repack = 2/3: the other set of planes becomes the batch's current one.  Its own inverse: a call whose pack fails flips back. */
-static void batch_flip_planes(asm_batch* b) {
-    std::swap(b->d_planes, b->d_planes_alt);
-    std::swap(b->d_lens, b->d_lens_alt);
-    b->cur ^= 1;
-    for (int q = 0; q < b->nb; q++) {
-        b->bk[q].planes = b->d_planes + b->pb.plane_off[q];
-        b->bk[q].lens = b->d_lens + b->pb.start[q];
-    }
-}
-
-/* asm_run_benchmark_async reaches its other streams through the ordinary entry points, which launch on h->stream: for the life
- * of this object that is `s`, and afterwards what it was before, on every way out of the scope. */
-struct StreamBorrow {
-    asm_handle* const h;
-    const hipStream_t back;
-    StreamBorrow(asm_handle* handle, hipStream_t s) : h(handle), back(handle->stream) { h->stream = s; }
-    StreamBorrow(const StreamBorrow&) = delete;
-    StreamBorrow& operator=(const StreamBorrow&) = delete;
-    ~StreamBorrow() { h->stream = back; }
-};
-
-int asm_run_benchmark_async(asm_handle* h, asm_batch* b, const asm_params* p, int repack, int32_t* d_nw,
-                            int32_t* d_leap, int32_t* d_greedy, const int32_t* d_answers,
-                            unsigned long long* d_counters) {
-    if (!h || !b || !p) return fail(h, ASM_EINVAL, "asm_run_benchmark_async: NULL argument");
-    /* the aligners check again; these checks come before anything is enqueued or flipped */
-    int rc = d_nw ? check_params(h, ASM_NW, p, b->maxlen) : ASM_OK;
-    if (!rc && d_leap) rc = check_params(h, ASM_LEAP, p, b->maxlen);
-    if (!rc && d_greedy) rc = check_params(h, ASM_GREEDY, p, b->maxlen);
-    if (rc) return rc;
-    // Without NW in the mask, wide-band LEAP (four threads per pair, asm_wave.h) is scheduled by the Greedy penalties:
-    // Greedy first, on the same stream — at wide bands both kernels are VALU-bound and side by side they gain nothing (C3:
-    // 23.8 ms against 23.6 in a row), while the work-sorted LEAP saves a quarter of its time.
-    const bool greedy_first_shape = d_greedy && d_leap && !d_nw && p->k > 5 && h->leap_hint && h->wave_kernels;
-    /* A call that asks for overlapped steps but has the Greedy-first shape (or no pairs) runs as a pipelined-pack call: it is
-     * ordered like one (behind every earlier overlapped call), and the bookkeeping of the overlapped form starts afresh. */
-    if (repack == 3 && (b->n <= 0 || greedy_first_shape)) repack = 2;
-    // optional per-kernel timing inside the caller's timed region: events on the stream each kernel is launched on
-    hipEvent_t* pe = nullptr;
-    unsigned pmask = 0u;
-    if ((int)h->prof_mask.size() < h->prof_cap) pe = &h->prof_ev[8 * h->prof_mask.size()];
-#define PROF(q, which, stream_)                                              \
-    if (pe && !rc && (h->prof_select & (1u << (q)))) {                       \
-        HIPCHK(h, hipEventRecord(pe[2 * (q) + (which)], (stream_)));         \
-        pmask |= 1u << (q);                                                  \
-    }
-    hipStream_t main_stream = h->stream;
-    /* the contract of repack = 3: consecutive overlapped calls write different arrays (the previous call's counters may still be
-     * reading its own).  A caller that forgets is told so instead of getting a race. */
-    if (repack == 3 && h->last3_valid && ((d_nw && d_nw == h->last3_out[0]) || (d_leap && d_leap == h->last3_out[1]) ||
-                                          (d_greedy && d_greedy == h->last3_out[2])))
-        return fail(h, ASM_EINVAL, "asm_run_benchmark_async: repack = 3 needs output arrays that alternate between two sets (these "
-                                   "were the previous call's); asm_pipeline_join_async first to reuse them");
-    if (repack != 3) h->last3_valid = false, h->calls3 = 0;
-    if (repack != 3 && h->tail_set) { /* earlier overlapped calls: everything of theirs before anything of this one */
-        HIPCHK(h, hipSetDevice(h->device));
-        HIPCHK(h, hipStreamWaitEvent(main_stream, h->ev_tail, 0));
-        h->tail_set = false;
-    }
-    bool pipelined = false;
-    if ((repack == 2 || repack == 3) && b->n > 0) {
-        /* Pipelined repack: pack fills the OTHER set of planes on its own stream, so it runs beside the aligners of the previous
-         * call (which read the current set) instead of behind them; this call's aligners wait for it.  The set it fills was last
-         * read two calls ago (ev_consumed).  The caller guarantees that nothing enqueued since the previous call changes what
-         * pack reads (the resident ASCII, the tails). */
-        HIPCHK(h, hipSetDevice(h->device));
-        if (!b->d_planes_alt) HIPCHK(h, batch_alloc(b, &b->d_planes_alt, sizeof(uint4) * b->planes_total));
-        if (!b->d_lens_alt) HIPCHK(h, batch_alloc(b, &b->d_lens_alt, sizeof(uint32_t) * (size_t)b->n));
-        if (!b->ev_consumed[1]) {
-            for (hipEvent_t& ev : b->ev_consumed)
-                if (!ev) HIPCHK(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            HIPCHK(h, hipEventRecord(b->ev_consumed[0], main_stream)); /* everything enqueued so far (the batch's creation) */
-            HIPCHK(h, hipEventRecord(b->ev_consumed[1], main_stream));
-        }
-        HIPCHK(h, hipStreamWaitEvent(h->pack_stream, b->ev_consumed[b->cur ^ 1], 0));
-        /* Overlapped calls on DIFFERENT batches (a caller rotating over several resident batches): the plane set of this batch
-         * was consumed long ago, so nothing above holds the pack back, and the pack chain would run as many calls ahead as the
-         * host has enqueued — thousands of short pack workgroups dispatched beside every persistent Greedy kernel (0.258 ms per
-         * step against 0.218 on one batch).  Pace it as one batch paces itself: the pack of call c behind the counters of call
-         * c - 2 (the event that also frees that call's output arrays). */
-        if (repack == 3 && h->calls3 >= 2) HIPCHK(h, hipStreamWaitEvent(h->pack_stream, h->ev_out[h->calls3 & 1u], 0));
-        if (!h->pipe_prev) { /* first of a run of pipelined calls: behind whatever the caller's stream holds so far */
-            HIPCHK(h, hipEventRecord(h->ev_fork, main_stream));
-            HIPCHK(h, hipStreamWaitEvent(h->pack_stream, h->ev_fork, 0));
-        }
-        /* ... and not before the previous call's persistent Greedy kernel is resident everywhere: pack's thousands of short
-         * workgroups, dispatched at the same moment, keep Greedy's 122 KB-LDS workgroups off the CUs (0.280 ms/step); behind
-         * the previous NW they find Greedy running and take the slots NW left (0.238).  With overlapped calls (repack = 3) the
-         * pack chain runs a call ahead and meets no Greedy launch: no gate there (0.229 against 0.251 gated) */
-        if (h->gate_set && repack == 2) HIPCHK(h, hipStreamWaitEvent(h->pack_stream, h->ev_gate, 0));
-        PROF(0, 0, h->pack_stream)
-        batch_flip_planes(b);
-        {
-            StreamBorrow on(h, h->pack_stream);
-            rc = asm_batch_pack_async(h, b);
-        }
-        if (rc) batch_flip_planes(b); /* back to the set that is packed */
-        PROF(0, 1, h->pack_stream)
-        if (!rc) {
-            HIPCHK(h, hipEventRecord(h->ev_packed, h->pack_stream));
-            HIPCHK(h, hipStreamWaitEvent(main_stream, h->ev_packed, 0));
-        }
-        pipelined = true;
-    } else if (repack) {
-        PROF(0, 0, main_stream)
-        rc = asm_batch_pack_async(h, b);
-        PROF(0, 1, main_stream)
-    }
-    // Greedy depends only on the packed planes, NW -> LEAP form their own chain (LEAP is scheduled by the NW penalties):
-    // run Greedy on a side stream so that the two chains fill each other's launch gaps and tail waves.
-    const bool greedy_first = greedy_first_shape && !rc;
-    if (greedy_first) {
-        PROF(3, 0, main_stream)
-        rc = asm_align_batch_async(h, b, ASM_GREEDY, p, d_greedy);
-        PROF(3, 1, main_stream)
-    }
-    if (repack == 3 && pipelined && !rc) {
-        h->last3_out[0] = d_nw, h->last3_out[1] = d_leap, h->last3_out[2] = d_greedy;
-        h->last3_valid = true;
-        /* OVERLAPPED calls: nothing of this call waits for the previous call's Greedy, and the caller's stream is not joined
-         * here (asm_pipeline_join_async does that).  Three chains run through consecutive calls — NW -> LEAP -> counters -> NW
-         * -> ... on a stream of the library, Greedy -> Greedy on the side stream, pack -> pack on the pack stream; a call's
-         * counters wait for its Greedy, and their event also frees the call's plane set for the pack two calls later (and, with
-         * the caller alternating output arrays, says those arrays may be written again). */
-        /* the output arrays were last written two calls ago (the caller alternates): behind that call's counters.  For calls
-         * on ONE batch ev_packed already implies it; calls on different batches have nothing else that orders them. */
-        hipEvent_t out_free = h->ev_out[h->calls3 & 1u];
-        if (h->calls3 >= 2) {
-            HIPCHK(h, hipStreamWaitEvent(main_stream, out_free, 0));
-            if (d_greedy) HIPCHK(h, hipStreamWaitEvent(h->side_stream, out_free, 0));
-        }
-        if (d_greedy) {
-            /* one side stream: Greedy kernels of consecutive calls in a row.  Alternating two streams, so that the next call's
-             * workgroups move in as the previous call's leave, was measured at 0.273 ms/step against 0.233 — two persistent
-             * kernels that each want a CU's LDS keep each other out */
-            hipStream_t side = h->side_stream;
-            HIPCHK(h, hipStreamWaitEvent(side, h->ev_packed, 0));
-            PROF(3, 0, side)
-            {
-                StreamBorrow on(h, side);
-                rc = asm_align_batch_async(h, b, ASM_GREEDY, p, d_greedy);
-            }
-            PROF(3, 1, side)
-            if (!rc) HIPCHK(h, hipEventRecord(h->ev_join, side));
-        }
-        /* NW -> LEAP -> counters of a call, then the next call's NW, in a row on ONE stream (when all three are asked for).
-         * Rounds 3-4 launched NW on the caller's stream and LEAP + counters on a stream of the library; under torch the two
-         * shared a hardware queue (the runtime spreads streams over four, the handle's idle own stream holds one), which
-         * serialised them in exactly this order — and that order is the fast one: with GPU_MAX_HW_QUEUES=8, where the next NW
-         * really starts beside this call's LEAP and counters, a step takes 0.219 ms against 0.204.  Saying so explicitly makes
-         * the step independent of how the host's streams happen to map to queues (same box: 0.206 at four queues, 0.208 at
-         * eight). */
-        hipStream_t chain = (d_nw && d_leap) ? h->acc_stream : main_stream;
-        if (chain != main_stream) HIPCHK(h, hipStreamWaitEvent(chain, h->ev_packed, 0));
-        if (!rc && d_nw) {
-            PROF(1, 0, chain)
-            {
-                StreamBorrow on(h, chain);
-                rc = asm_align_batch_async(h, b, ASM_NW, p, d_nw);
-            }
-            PROF(1, 1, chain)
-        }
-        hipStream_t ls = (d_nw && d_leap) ? h->acc_stream : main_stream;
-        if (!rc && d_leap) {
-            if (ls != chain) {
-                HIPCHK(h, hipEventRecord(h->ev_nw, chain));
-                HIPCHK(h, hipStreamWaitEvent(ls, h->ev_nw, 0));
-            }
-            PROF(2, 0, ls)
-            {
-                StreamBorrow on(h, ls);
-                rc = asm_align_batch_hinted_async(h, b, ASM_LEAP, p, d_nw, d_leap);
-            }
-            PROF(2, 1, ls)
-        }
-        if (pe) h->prof_mask.push_back(pmask);
-        if (rc) return rc;
-        HIPCHK(h, hipEventRecord(h->ev_leap, ls));
-        HIPCHK(h, hipStreamWaitEvent(h->acc_stream, h->ev_leap, 0));
-        if (d_greedy) HIPCHK(h, hipStreamWaitEvent(h->acc_stream, h->ev_join, 0));
-        if (d_counters) {
-            {
-                StreamBorrow on(h, h->acc_stream);
-                rc = asm_accuracy_async(h, d_nw, d_leap, d_greedy, d_answers, b->n, d_counters);
-            }
-            if (rc) return rc;
-        }
-        HIPCHK(h, hipEventRecord(b->ev_consumed[b->cur], h->acc_stream));
-        HIPCHK(h, hipEventRecord(out_free, h->acc_stream));
-        h->calls3++;
-        HIPCHK(h, hipEventRecord(h->ev_tail, h->acc_stream));
-        h->tail_set = true;
-        h->pipe_prev = true;
-        return ASM_OK;
-    }
-    const bool fork = h->overlap && d_greedy && (d_nw || d_leap) && !rc && !greedy_first;
-    if (fork) {
-        HIPCHK(h, hipEventRecord(h->ev_fork, main_stream));
-        HIPCHK(h, hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
-        PROF(3, 0, h->side_stream)
-        {
-            StreamBorrow on(h, h->side_stream);
-            rc = asm_align_batch_async(h, b, ASM_GREEDY, p, d_greedy);
-        }
-        PROF(3, 1, h->side_stream)
-        if (!rc) HIPCHK(h, hipEventRecord(h->ev_join, h->side_stream));
-    }
-    if (!rc && d_nw) {
-        PROF(1, 0, main_stream)
-        rc = asm_align_batch_async(h, b, ASM_NW, p, d_nw);
-        PROF(1, 1, main_stream)
-        if (!rc && repack == 2) {
-            HIPCHK(h, hipEventRecord(h->ev_gate, main_stream));
-            h->gate_set = true;
-        }
-    }
-    /* LEAP is scheduled by the NW penalties just computed (same work, sorted inside each workgroup) */
-    if (!rc && d_leap) {
-        PROF(2, 0, main_stream)
-        rc = asm_align_batch_hinted_async(h, b, ASM_LEAP, p, greedy_first ? d_greedy : d_nw, d_leap);
-        PROF(2, 1, main_stream)
-    }
-    if (fork) {
-        if (!rc) HIPCHK(h, hipStreamWaitEvent(main_stream, h->ev_join, 0));
-    } else if (!rc && d_greedy && !greedy_first) {
-        PROF(3, 0, main_stream)
-        rc = asm_align_batch_async(h, b, ASM_GREEDY, p, d_greedy);
-        PROF(3, 1, main_stream)
-    }
-#undef PROF
-    if (pe) h->prof_mask.push_back(pmask);
-    if (pipelined && !rc) HIPCHK(h, hipEventRecord(b->ev_consumed[b->cur], main_stream)); /* Greedy's stream has joined above */
-    if (!rc && d_counters) rc = asm_accuracy_async(h, d_nw, d_leap, d_greedy, d_answers, b->n, d_counters);
-    h->pipe_prev = pipelined;
-    return rc;
-}
+#include "asm_step.h" /* asm_run_benchmark_async, asm_pipeline_join_async, asm_profile_enable / asm_profile_read */
 
 #include "asm_stream.h"
 

@@ -1059,6 +1059,75 @@ def test_a_batch_freed_after_overlapped_calls_that_were_not_joined(asm, engine, 
         engine.free(x)
 
 
+# ---- the step scheduler by output mask: every non-empty subset of {NW, LEAP, Greedy} under every repack ----
+_STEP_SENTINEL = 0x5A5A5A5A  # memset byte 0x5A: what an array that was not asked for must still hold
+_STEP_SUBSETS = [(True, False, False), (False, True, False), (False, False, True), (True, True, False), (True, False, True),
+                 (False, True, True), (True, True, True)]
+# k = 3 on 2,500 pairs: several workgroups of every kernel, no multiple of 256 or 512, more than one chunk of the persistent Greedy
+# queue; and LEAP + Greedy without NW at a wide band (the Greedy-first shape) on 1,500
+_STEP_GRID = [("C2", 2500, s) for s in _STEP_SUBSETS] + [("C3", 1500, (False, True, True))]
+_STEP_CALLS = 5
+
+
+@pytest.fixture(scope="module")
+def step_workloads(asm, engine, oracle):
+    """Per workload of the grid: the resident batch, the oracle's (NW, LEAP, Greedy) penalties, two sets of three output arrays
+    and the counters.  Made once; the tests only read the penalties."""
+    made = {}
+    for wl, n in {(wl, n) for wl, n, _ in _STEP_GRID}:
+        cfg, _, params = asm.workload(wl)
+        hb = asm.generate_pairs(cfg, 29, n)
+        want = (oracle.nw(hb), oracle.leap(hb, params.k), oracle.greedy(hb, params.k, mode=1))
+        made[wl] = dict(n=n, params=params, batch=engine.upload(hb, asm.GREEDY_CLEAN), want=want,
+                        sets=[[engine.malloc(4 * n) for _ in range(3)] for _ in range(2)], d_cnt=engine.malloc(32))
+    yield made
+    for w in made.values():
+        for x in w["sets"][0] + w["sets"][1] + [w["d_cnt"]]:
+            engine.free(x)
+
+
+@pytest.mark.parametrize("profiled", [False, True])
+@pytest.mark.parametrize("repack", [0, 1, 2, 3])
+@pytest.mark.parametrize("wl,n,subset", _STEP_GRID, ids=lambda v: "".join("NLG"[i] for i in range(3) if v[i]) if isinstance(v, tuple) else str(v))
+def test_step_schedule_for_every_output_mask(asm, engine, step_workloads, wl, n, subset, repack, profiled):
+    """asm_run_benchmark_async writes exactly the arrays it is given, whatever the schedule: five calls in a row without a sync
+    (overlapped ones alternate two sets of arrays and end with a join).  Every array asked for holds the oracle's penalties,
+    every other array still holds the sentinel, and the counters are the exact sums under the rule of asm_accuracy_async:
+    total_tests counts every pair, and without NW (no answers array here) no pair has a correct answer.  With profiling on,
+    asm_profile_read gives a positive time exactly for the stages that ran and -1 for the others."""
+    w = step_workloads[wl]
+    sets, d_cnt, want = w["sets"], w["d_cnt"], w["want"]
+    for x in sets[0] + sets[1]:
+        engine.memset_async(x, 0x5A, 4 * n)
+    engine.memset_async(d_cnt, 0, 32)
+    engine.synchronize()  # the library's own streams are not ordered behind these memsets in the middle of a pipelined run
+    if profiled:
+        engine.profile_enable(_STEP_CALLS, 0xF)
+    for c in range(_STEP_CALLS):
+        o = [x if asked else None for x, asked in zip(sets[c & 1] if repack == 3 else sets[0], subset)]
+        engine.run_benchmark_async(w["batch"], w["params"], o[0], o[1], o[2], d_cnt, repack=repack)
+    if repack == 3:
+        engine.pipeline_join_async()
+    if profiled:
+        ms = engine.profile_read(_STEP_CALLS + 3)
+        engine.profile_enable(0, 0)
+        assert ms.shape == (_STEP_CALLS, 4)
+        for q, ran in enumerate((repack != 0,) + subset):
+            assert (ms[:, q] > 0).all() if ran else (ms[:, q] == -1).all(), (q, ran, ms)
+    for s_i, arrays in enumerate(sets):
+        written = repack == 3 or s_i == 0
+        for a, x in enumerate(arrays):
+            got = engine.to_host(x, n)
+            if written and subset[a]:
+                assert np.array_equal(got, want[a]), (s_i, asm.ALIGNER_NAMES[a])
+            else:
+                assert (got == _STEP_SENTINEL).all(), (s_i, asm.ALIGNER_NAMES[a])
+    nw, leap, greedy = want
+    per_call = [n, n if subset[0] else 0, int((leap == nw).sum()) if subset[0] and subset[1] else 0,
+                int((greedy == nw).sum()) if subset[0] and subset[2] else 0]
+    assert engine.to_host(d_cnt, 4, np.uint64).tolist() == [_STEP_CALLS * v for v in per_call]
+
+
 @pytest.mark.parametrize("k", [1, 2, 3])
 def test_fast_greedy_kernel_slow_path_and_corners(asm, engine, oracle, k):
     """The straight-line Greedy kernel (csrc/asm_greedy3.h, k <= 3, unit penalties): solid blocks of mismatches leave the rank
