@@ -19,6 +19,7 @@
 
 #include "asm_bits.h"
 #include "asm_gen.h"
+#include "asm_leapunit.h"
 #include "asm_nwband.h"
 
 #define ASM_BLOCK 256
@@ -512,206 +513,9 @@ __global__ __launch_bounds__(ASM_BLOCK, GREEDY_PERSIST_MIN_WAVES(K, UNIT)) void 
 
 // --------------------------------------------------------------------------------------------------------
 // LEAP (banded affine Landau-Vishkin, "BAG"), unit penalties x = o = e = 1, lanes in registers, one thread
-// per pair.  Follows LV::run (LEAP_SIMD/LV_BAG.cpp:127-245) with init(k,200,ED_GLOBAL,1,1,1); the scalar
-// character loop count_ID_length (:9-23) becomes a count-trailing-zeros on the lane's mismatch bit-vector.
-// Only generation e-1 is live, so three registers per lane replace the four [2k+3][201]
-// tables.  W64 = number of 64-bit words per vector (2: len <= 128, 4: len <= 256).
+// per pair: leap_unit_pair, with the word vectors VW / vw_* and leap_lane_mask that the other LEAP kernels
+// below share, is in asm_leapunit.h (host-buildable: host/leap_host_check.cpp).
 // --------------------------------------------------------------------------------------------------------
-template <int W64>
-struct VW {
-    u64 w[W64];
-};
-
-// first set bit at or after `from` in a W64-word vector, or W64*64 when none.  `from` in [0, W64*64].
-// Only the word `from` falls into needs its low bits dropped (one 64-bit shift, taken mod 64 by the hardware); the words
-// above it count from their own bit 0, the words below it not at all.
-template <int W64>
-ASM_DEV int vw_next_one(const VW<W64>& v, int from) {
-    const int q = from >> 6;
-    u64 x = v.w[W64 - 1];
-#pragma unroll
-    for (int qq = W64 - 2; qq >= 0; qq--) x = q == qq ? v.w[qq] : x;
-    const u64 y = x >> (from & 63);
-    int res = W64 * 64;
-#pragma unroll
-    for (int qq = W64 - 1; qq >= 1; qq--) /* descending: the lowest non-empty word above `from` wins */
-        if (qq > q && v.w[qq]) res = qq * 64 + __builtin_ctzll(v.w[qq]);
-    if (y) res = from + __builtin_ctzll(y);
-    return from >= W64 * 64 ? W64 * 64 : res;
-}
-
-// The same scan for a caller that keeps, per vector, "first set bit in the words above word q" (W64 * 64 when none) for every q
-// but the last: v_ffbl_b32 gives 0xFFFFFFFF for an empty word, and with saturating adds an empty shifted word turns into a candidate
-// that loses the final min — no zero tests, no compare-and-select chain behind the shift (asm_bits.h, v_next_one_from_fb).
-/* Up to three words per vector the fall-backs cost no registers the compiler was not already spending (it hoists the upper
- * words' ctz out of the generation loop either way: 59 and 90 VGPRs before and after at two and three words).  From four words
- * on they do — 120 -> 146 and 165 -> 209 VGPRs at four and six words, a wave per SIMD less — and the wider classes of C5 lost
- * what the shorter scan gained: those keep vw_next_one. */
-#define VW_SCAN_FB(W64) ((W64) <= 3)
-template <int W64>
-struct VWAbove {
-    unsigned fb[W64 > 1 ? W64 - 1 : 1];
-};
-template <int W64>
-ASM_DEV VWAbove<W64> vw_above(const VW<W64>& v) {
-    VWAbove<W64> r;
-    unsigned run = W64 * 64u;
-#pragma unroll
-    for (int q = W64 - 2; q >= 0; q--) {
-        run = v.w[q + 1] ? (unsigned)(q + 1) * 64u + (unsigned)__builtin_ctzll(v.w[q + 1]) : run;
-        r.fb[q] = run;
-    }
-    return r;
-}
-template <int W64>
-ASM_DEV int vw_next_one_fb(const VW<W64>& v, const VWAbove<W64>& ab, int from) { /* = vw_next_one(v, from) for from >= 0 */
-    u64 x = v.w[W64 - 1];
-    unsigned f = W64 * 64u;
-#pragma unroll
-    for (int q = W64 - 2; q >= 0; q--) { /* the nested tests leave the word `from` falls into, and what lies above it */
-        const bool below = from < (q + 1) * 64;
-        x = below ? v.w[q] : x;
-        f = below ? ab.fb[q] : f;
-    }
-    const u64 y = x >> (from & 63);
-    const unsigned c = min(v_ffbl_raw((unsigned)y), __builtin_elementwise_add_sat(v_ffbl_raw((unsigned)(y >> 32)), 32u));
-    return (int)min(__builtin_elementwise_add_sat((unsigned)from, c), f);
-}
-
-// bit p of the result = bit (p - s) of v (bits move away from index 0), s in [0, 63]
-template <int W64>
-ASM_DEV VW<W64> vw_away0_small(const VW<W64>& v, int s) {
-    VW<W64> r;
-#pragma unroll
-    for (int q = 0; q < W64; q++) {
-        u64 lo = q > 0 ? v.w[q - 1] : 0ull;
-        r.w[q] = (v.w[q] << s) | (s ? (lo >> (64 - s)) : 0ull);
-    }
-    return r;
-}
-
-template <int W64>
-ASM_DEV VW<W64> vw_low_ones(int len) {
-    VW<W64> r;
-#pragma unroll
-    for (int q = 0; q < W64; q++) {
-        const int rel = len - q * 64;
-        r.w[q] = rel <= 0 ? 0ull : (rel >= 64 ? ~0ull : ((1ull << rel) - 1ull));
-    }
-    return r;
-}
-
-template <int W64>
-ASM_DEV void load_planes(const uint4* __restrict__ planes, long n, int w4, long i, VW<W64>& A0, VW<W64>& A1,
-                         VW<W64>& B0, VW<W64>& B1) {
-#pragma unroll
-    for (int g = 0; g < (W64 + 1) / 2; g++) { /* an odd W64 takes only the low half of its last granule */
-        uint4 qa0 = make_uint4(0u, 0u, 0u, 0u), qa1 = qa0, qb0 = qa0, qb1 = qa0;
-        if (g < w4) { /* a vector wider than the batch's granule count has empty upper words */
-            qa0 = planes[((long)0 * w4 + g) * n + i];
-            qa1 = planes[((long)1 * w4 + g) * n + i];
-            qb0 = planes[((long)2 * w4 + g) * n + i];
-            qb1 = planes[((long)3 * w4 + g) * n + i];
-        }
-        A0.w[2 * g] = (u64)qa0.x | ((u64)qa0.y << 32), A1.w[2 * g] = (u64)qa1.x | ((u64)qa1.y << 32);
-        B0.w[2 * g] = (u64)qb0.x | ((u64)qb0.y << 32), B1.w[2 * g] = (u64)qb1.x | ((u64)qb1.y << 32);
-        if (2 * g + 1 < W64) {
-            A0.w[2 * g + 1] = (u64)qa0.z | ((u64)qa0.w << 32), A1.w[2 * g + 1] = (u64)qa1.z | ((u64)qa1.w << 32);
-            B0.w[2 * g + 1] = (u64)qb0.z | ((u64)qb0.w << 32), B1.w[2 * g + 1] = (u64)qb1.z | ((u64)qb1.w << 32);
-        }
-    }
-}
-
-// Mismatch vector of LEAP lane d = l - mid (LV_BAG.cpp:13-18): position p = max(read idx, ref idx);
-// d < 0 compares A[p-|d|] with B[p], d > 0 compares A[p] with B[p-d].  Positions where either string has
-// run out (the NUL padding of LV::load_reads, LV_BAG.cpp:116-117) and all positions >= len are mismatches.
-template <int W64>
-ASM_DEV VW<W64> leap_lane_mask(const VW<W64>& A0, const VW<W64>& A1, const VW<W64>& B0, const VW<W64>& B1,
-                               const VW<W64>& VA, const VW<W64>& VB, int d) {
-    VW<W64> r;
-    const int s = d < 0 ? -d : d;
-    if (d < 0) {
-        VW<W64> a0 = vw_away0_small<W64>(A0, s), a1 = vw_away0_small<W64>(A1, s), va = vw_away0_small<W64>(VA, s);
-#pragma unroll
-        for (int q = 0; q < W64; q++) r.w[q] = (a0.w[q] ^ B0.w[q]) | (a1.w[q] ^ B1.w[q]) | ~(va.w[q] & VB.w[q]);
-    } else {
-        VW<W64> b0 = vw_away0_small<W64>(B0, s), b1 = vw_away0_small<W64>(B1, s), vb = vw_away0_small<W64>(VB, s);
-#pragma unroll
-        for (int q = 0; q < W64; q++) r.w[q] = (A0.w[q] ^ b0.w[q]) | (A1.w[q] ^ b1.w[q]) | ~(VA.w[q] & vb.w[q]);
-    }
-    return r;
-}
-
-template <int K, int W64>
-ASM_DEV int leap_unit_pair(const uint4* __restrict__ planes, const uint32_t* __restrict__ lens, long n, int w4, long i) {
-    constexpr int NL = 2 * K + 1;
-    const uint32_t ln = lens[i];
-    const int m = (int)(ln & 0xffffu), nn = (int)(ln >> 16);
-    const int len = m > nn ? m : nn; /* benchmark_utils.h:162 */
-    VW<W64> A0, A1, B0, B1;
-    load_planes<W64>(planes, n, w4, i, A0, A1, B0, B1);
-    const VW<W64> VA = vw_low_ones<W64>(m), VB = vw_low_ones<W64>(nn);
-
-    VW<W64> mask[NL];
-#pragma unroll
-    for (int j = 0; j < NL; j++) mask[j] = leap_lane_mask<W64>(A0, A1, B0, B1, VA, VB, j - K);
-
-    // Generation e-1 state per lane: `end` only (-2 = never reached, LV_BAG.cpp:95-101).  With o == ext (here 1 == 1) the
-    // I and D tables carry no information of their own: I[l][e] is taken from end[l-1][e-o] when that is > I[l-1][e-ext],
-    // else from I[l-1][e-ext] (LV_BAG.cpp:166-176) — the same generation e-1 on both sides — and end[.][g] >= I[.][g]
-    // whenever I[.][g] >= 0, because a lane's start is max(end+1, I, D) (:186-201) and its end is never before its start.
-    // So I[l][e] = end[l-1][e-1] + top if that end is >= 0, else -2; likewise D from lane l+1.  And since -2 + {0,1} and
-    // -2 + 1 stay negative, start = max(end+1, end_up+top, end_dn+bot) needs no selects: it is negative exactly when all
-    // three sources are -2.
-    int en[NL];
-#pragma unroll
-    for (int j = 0; j < NL; j++) en[j] = -2;
-    VWAbove<W64> above[NL];
-#pragma unroll
-    for (int j = 0; j < NL; j++) above[j] = vw_above<W64>(mask[j]);
-
-    int result = -1;
-    // e = 0: only the main diagonal is live in ED_GLOBAL (LV_BAG.cpp:102-104,131-147)
-    {
-        int e0 = vw_next_one<W64>(mask[K], 0);
-        e0 = e0 > len ? len : e0;
-        en[K] = e0;
-        if (e0 == len) result = 0;
-    }
-    for (int e = 1; e <= ASM_LEAP_AF_THRESHOLD && result < 0; e++) {
-        int en2[NL];
-        bool pass = false;
-#pragma unroll
-        for (int j = 0; j < NL; j++) {
-            const int d = j - K;
-            const int top = d >= 0 ? 1 : 0, bot = d <= 0 ? 1 : 0;
-            const int e_up = j > 0 ? en[j - 1] : -2;
-            const int e_dn = j < NL - 1 ? en[j + 1] : -2;
-            int st = en[j] + 1;                        /* :186-187 */
-            st = e_up + top > st ? e_up + top : st;    /* I_pos, :166-176,193-194 */
-            st = e_dn + bot > st ? e_dn + bot : st;    /* D_pos, :179-182,200-201 */
-            int enew = -2;
-            if (st >= 0) {
-                const int from = st > len ? len : st;
-                /* count_ID_length (:9-23) as a saturating scan: first mismatch at or after `from`, capped at len; enew = max(t, st)
-                 * is the reference's "a start beyond the end stays where it is" (t >= from = st whenever st <= len) */
-                int t = VW_SCAN_FB(W64) ? vw_next_one_fb<W64>(mask[j], above[j], from) : vw_next_one<W64>(mask[j], from);
-                t = t > len ? len : t;
-                enew = t > st ? t : st;
-                if (enew == len) { /* :220-238 */
-                    const int diff = d < 0 ? -d : d;
-                    const int conv = e + diff; /* o + (diff-1)*ext with o = ext = 1 */
-                    if (conv <= ASM_LEAP_AF_THRESHOLD) pass = true;
-                }
-            }
-            en2[j] = enew;
-        }
-#pragma unroll
-        for (int j = 0; j < NL; j++) en[j] = en2[j];
-        if (pass) result = e; /* final_ED (LV_BAG.cpp:228,356-358), not converge_ED */
-    }
-    return result;
-}
 
 template <int K, int W64>
 __global__ __launch_bounds__(ASM_BLOCK) void leap_unit_kernel(const uint4* __restrict__ planes,
@@ -753,13 +557,15 @@ __global__ __launch_bounds__(ASM_BLOCK) void leap_unit_hint_kernel(const uint4* 
         }
     }
     __syncthreads();
-    if (t == 0) { /* exclusive scan of 64 bins */
-        int run = 0;
-        for (int b = 0; b < 64; b++) {
-            const int c = s_bin[b];
-            s_bin[b] = run;
-            run += c;
+    if (t < 64) { /* exclusive scan of 64 bins in the first wave: bin t ends up with the count of all bins below it */
+        const int c = s_bin[t];
+        int run = c;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int up = __shfl_up(run, off, 64);
+            run += t >= off ? up : 0;
         }
+        s_bin[t] = run - c;
     }
     __syncthreads();
 #pragma unroll
