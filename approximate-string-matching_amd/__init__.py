@@ -114,6 +114,12 @@ class MapPairsFileStats(ctypes.Structure):
                 ("seconds_write", ctypes.c_double)]
 
 
+class IndexFileStats(ctypes.Structure):
+    """asm_index_file_stats"""
+    _fields_ = [("n_seqs", ctypes.c_int64), ("bases", ctypes.c_int64), ("bytes_in", ctypes.c_int64), ("chunks", ctypes.c_int64),
+                ("seconds", ctypes.c_double), ("seconds_read", ctypes.c_double), ("seconds_index", ctypes.c_double)]
+
+
 class PairParams(ctypes.Structure):
     """asm_pair_params: projected span in [min_insert, max_insert] (0 <= min <= max <= 8192), mate rescue's error bound (-1 = off)."""
 
@@ -127,6 +133,7 @@ MAP_MAPPED, MAP_TOO_SHORT, MAP_SEED_CAPPED, MAP_CIGAR_TRUNCATED = 1, 2, 4, 8
 MAP_SECONDARY, MAP_HITS_TRUNCATED, MAP_MAX_HITS = 16, 32, 256
 MAP_PROPER_PAIR, MAP_RESCUED, MAP_MAX_INSERT = 64, 128, 8192
 MAP_MIN_K, MAP_MAX_K, MAP_MAX_READ, MAP_MAX_ERRORS = 8, 14, 511, 15
+FASTA_TILE = 4096  # ASM_FASTA_TILE: the bytes one workgroup of build_index_file's parser takes, 16 per thread
 
 
 def _as_bytes(s) -> bytes:
@@ -271,6 +278,12 @@ def load_library() -> ctypes.CDLL:
         "asm_map_pairs_file": (i32, [vp, vp, c.POINTER(c.c_char_p), c.c_char_p, c.c_char_p, c.c_char_p, c.c_char_p, c.POINTER(MapParams),
                                      c.POINTER(PairParams), i64, c.POINTER(MapPairsFileStats)]),
         "asm_fastq_cut_n": (c.c_size_t, [vp, c.c_size_t, i64, c.POINTER(i64)]),
+        "asm_index_build_file": (i32, [vp, c.c_char_p, i32, i64, c.POINTER(vp), c.POINTER(IndexFileStats)]),
+        "asm_index_n_seqs": (c.c_int32, [vp]),
+        "asm_index_seq_len": (c.c_uint64, [vp, c.c_int32]),
+        "asm_index_seq_name": (c.c_char_p, [vp, c.c_int32]),
+        "asm_index_get_text": (i32, [vp, vp, c.c_uint64, c.c_uint64, vp]),
+        "asm_fasta_cut": (c.c_size_t, [vp, c.c_size_t, i32, c.POINTER(i32)]),
         "asm_device_malloc": (i32, [vp, c.c_size_t, c.POINTER(vp)]),
         "asm_device_free": (i32, [vp, vp]),
         "asm_memcpy_d2h": (i32, [vp, vp, vp, c.c_size_t]),
@@ -437,8 +450,15 @@ class Reference:
 class Index:
     """asm_index: a k-mer index of reference sequences, resident in HBM."""
 
-    def __init__(self, engine: "Engine", ptr, k: int, lengths: Sequence[int]):
+    def __init__(self, engine: "Engine", ptr, k: int, lengths: Sequence[int], names: Optional[Sequence[str]] = None):
         self.engine, self.ptr, self.k, self.lengths = engine, ptr, k, list(lengths)
+        self.names = [""] * len(self.lengths) if names is None else list(names)
+
+    def text(self, start: int, n: int) -> bytes:
+        """asm_index_get_text: bytes [start, start + n) of the upper-cased text, by global offsets."""
+        buf = ctypes.create_string_buffer(max(int(n), 1))
+        self.engine._chk(self.engine.lib.asm_index_get_text(self.engine.h, self.ptr, int(start), int(n), buf))
+        return buf.raw[:int(n)]
 
     def free(self) -> None:
         if self.ptr:
@@ -564,6 +584,17 @@ class Engine:
         self._chk(self.lib.asm_index_build(self.h, text.ctypes.data if text.size else None, off.ctypes.data, len(off) - 1, int(k),
                                            ctypes.byref(ptr)))
         return Index(self, ptr, int(k), np.diff(off).astype(np.int64))
+
+    def build_index_file(self, path: str, k: int = 12, chunk_bytes: int = 0):
+        """asm_index_build_file: the index of a FASTA file, read, parsed and indexed without a host copy of the text
+        (docs/design/mapper.md, "Reference: FASTA in, index out").  -> (Index with .names and .lengths from the file, the stats as a
+        dict: n_seqs, bases, bytes_in, chunks, seconds, seconds_read, seconds_index)."""
+        ptr, st = ctypes.c_void_p(), IndexFileStats()
+        self._chk(self.lib.asm_index_build_file(self.h, os.fsencode(path), int(k), int(chunk_bytes), ctypes.byref(ptr), ctypes.byref(st)))
+        n = self.lib.asm_index_n_seqs(ptr)
+        index = Index(self, ptr, int(k), [int(self.lib.asm_index_seq_len(ptr, r)) for r in range(n)],
+                      [self.lib.asm_index_seq_name(ptr, r).decode("latin-1") for r in range(n)])
+        return index, {name: getattr(st, name) for name, _ in IndexFileStats._fields_}
 
     def _map_chunks(self, parts, chunk: Optional[int], call) -> None:
         """The chunk loop of the map_* methods.  parts: one list of byte strings per mate; call(lo, hi, seqs) maps reads [lo, hi)

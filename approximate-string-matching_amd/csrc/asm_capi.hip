@@ -40,6 +40,7 @@
 #include "asm_map.h"
 #include "asm_fastq.h"
 #include "asm_sam.h"
+#include "asm_fasta.h"
 
 /* What asm_run_benchmark_async (asm_step.h) keeps from call to call: the library's three streams beside the caller's, the events
  * that order the four, and the bookkeeping of a run of pipelined (repack = 2 / 3) calls. */
@@ -1928,6 +1929,8 @@ int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, in
 #include "asm_map_file.h"
 /* asm_map_pairs_file: two FASTQ files in, paired SAM out */
 #include "asm_map_pairs_file.h"
+/* asm_index_build_file: FASTA in, index out */
+#include "asm_index_file.h"
 
 /* ---------------------------------------------------------------------------------------------------- */
 int asm_device_malloc(asm_handle* h, size_t bytes, void** d_ptr) {

@@ -1,9 +1,10 @@
 // The device-free part of the C ABI's host side: everything in libasm_mi355x.so that runs on the CPU and never calls HIP —
 // the seeded generator's host loop (asm_generate_pairs), the stale-tail state arithmetic (asm_tail_state_advance), the CIGAR
 // formatter (asm_cigar_format), and the host threads of the two streamed-file calls: the three-slot hand-over between a reader
-// thread and the caller's thread (ChunkReader) with its two fill policies — asm_stream_seq_file's newline scanning over the
-// persistent reader pool (PairsFill) and asm_map_file's FASTQ chunk cutter (asm_fastq_cut, FastqFill) and asm_map_pairs_file's two
-// files in step (asm_fastq_cut_n, FastqPairFill) — and the SAM writer (ChunkWriter).
+// thread and the caller's thread (ChunkReader) with its four fill policies — asm_stream_seq_file's newline scanning over the
+// persistent reader pool (PairsFill), asm_map_file's FASTQ chunk cutter (asm_fastq_cut, FastqFill), asm_map_pairs_file's two
+// files in step (asm_fastq_cut_n, FastqPairFill) and asm_index_build_file's FASTA cutter (asm_fasta_cut, FastaFill) — and the SAM
+// writer (ChunkWriter).
 //
 // Kept in a header without any HIP include so that the SAME code is compiled twice: into the product by hipcc (asm_capi.hip),
 // and by plain g++ under -fsanitize=thread / address,undefined into host/asm_host_check.cpp (`make -C oracle asan`,
@@ -606,6 +607,58 @@ struct FastqPairFill {
             cut.have = cut.boundary = cutat[0] + cutat[1], cut.bytes1 = cutat[0], cut.units = R, cut.eof = eof;
             return true;
         }
+    }
+};
+
+/* ---- FASTA (asm_index_build_file): chunk cutting and the reader thread ---------------------------------------------------------- */
+/* How much of buf[0, nbytes) to ship: a chunk may end anywhere except inside a header line, so all of it, unless its last line is a
+ * header line without its newline yet: then what lies in front of that line's '>'.  at_line_start: buf[0] begins a line (else it goes
+ * on with a sequence line).  *ends_in_line: the shipped prefix ends inside a line, so the next buffer starts with at_line_start = 0.
+ * Only the last line is looked at: a sequence line of any length is cut like any other bytes. */
+inline size_t fasta_cut(const char* buf, size_t nbytes, int at_line_start, int* ends_in_line) {
+    const char* nl = nbytes ? (const char*)memrchr(buf, '\n', nbytes) : nullptr;
+    const size_t s = nl ? (size_t)(nl - buf) + 1 : 0; /* where the last line begins */
+    const size_t cut = (s < nbytes && (nl || at_line_start) && buf[s] == '>') ? s : nbytes;
+    if (ends_in_line) *ends_in_line = cut ? buf[cut - 1] != '\n' : !at_line_start;
+    return cut;
+}
+
+/* asm_index_build_file's policy: one pread loop, cut by fasta_cut; the end of the file ends the last line.  Only a header line
+ * longer than the slot takes `chunk` more bytes and grows the slot through grow() (FastqFill's hook).  units = the shipped lines,
+ * whole or not (newlines + 1), so that the consumer can size the chunk's newline index; an empty file is one last, empty chunk. */
+struct FastaFill {
+    const int fd;
+    const size_t file_bytes, chunk;
+    const std::function<bool(int, size_t, size_t)> grow;
+    size_t file_off = 0;
+    int at_line_start = 1;
+    FastaFill(int fd_, size_t file_bytes_, size_t chunk_, std::function<bool(int, size_t, size_t)> grow_)
+        : fd(fd_), file_bytes(file_bytes_), chunk(chunk_), grow(std::move(grow_)) {}
+
+    bool operator()(ChunkSlot& s, int q, const std::vector<char>& carry, size_t want, ChunkCut& cut) {
+        size_t have = carry.size();
+        if (have + 8 > s.cap && !grow(q, have + 8 + chunk, 0)) return false;
+        if (have) memcpy(s.buf, carry.data(), have);
+        int in_line = 0;
+        for (;;) {
+            if (want > file_bytes - file_off) want = file_bytes - file_off;
+            if (have + want + 8 > s.cap && !grow(q, have + want + 8 + (have + want) / 4, have)) return false;
+            for (size_t a = 0; a < want;) {
+                const ssize_t got = pread(fd, s.buf + have + a, want - a, (off_t)(file_off + a));
+                if (got <= 0) return false;
+                a += (size_t)got;
+            }
+            file_off += want, have += want;
+            cut.eof = file_off >= file_bytes;
+            cut.boundary = cut.eof ? have : fasta_cut(s.buf, have, at_line_start, &in_line);
+            if (cut.boundary > 0 || cut.eof) break;
+            want = chunk; /* one header line longer than the chunk: take more */
+        }
+        at_line_start = !in_line;
+        int64_t newlines = 0;
+        for (size_t a = 0; a < cut.boundary; a++) newlines += s.buf[a] == '\n'; /* (vectorised by the compiler) */
+        cut.have = have, cut.units = cut.boundary ? newlines + 1 : 0;
+        return true;
     }
 };
 

@@ -107,20 +107,9 @@ struct MapFileSession {
         return ASM_OK;
     }
 
-    /* For the reader's policy, on the reader's thread: a record (or pair) longer than slot q gets a larger pinned one, with the
-     * first `keep` bytes of the old one.  No copy reads the old one now: the reader has waited for the one out of it. */
+    /* For the reader's policy: a record (or pair) longer than slot q gets a larger pinned one (StreamInput::grow_pin) */
     std::function<bool(int, size_t, size_t)> grow() {
-        return [this](int q, size_t cap, size_t keep) {
-            StreamInput& in = pipe.in;
-            (void)hipSetDevice(h->device);
-            char* bigger = nullptr;
-            if (hipHostMalloc((void**)&bigger, cap + 64, hipHostMallocDefault) != hipSuccess) return false;
-            if (keep) memcpy(bigger, in.pin[q], keep);
-            (void)hipHostFree(in.pin[q]);
-            in.pin[q] = bigger;
-            slots[q].buf = bigger, slots[q].cap = cap;
-            return true;
-        };
+        return [this](int q, size_t cap, size_t keep) { return pipe.in.grow_pin(slots, q, cap, keep); };
     }
 
     /* The reader (built on first_chunk, chunk and grow()) through the input pipeline, from its start to its stop: accept sees every

@@ -14,6 +14,7 @@ struct asm_index {
     int32_t n_seqs = 0;
     uint64_t len = 0;
     std::vector<uint64_t> seq_off;          /* host copy, n_seqs + 1 */
+    std::vector<std::string> names;         /* asm_index_build_file: n_seqs names; asm_index_build: none */
     char* d_text = nullptr;                 /* upper case */
     unsigned long long* d_seq_off = nullptr;
     uint32_t* d_off = nullptr;              /* 4^k + 1 bucket offsets */
@@ -777,6 +778,34 @@ static int map_chunk_pairs_all(asm_handle* h, const asm_index* ix, int64_t np, c
 /* pairs per chunk: at most map_chunk / 2; the run key holds the read (2 per pair) in its top 31 bits */
 static int64_t map_pair_step(const asm_handle* h) { return std::max<int64_t>(1, std::min<int64_t>(h->map_chunk, (int64_t)1 << 30) / 2); }
 
+/* The index stage of asm_index_build and asm_index_build_file: ix holds its text in HBM (d_text, len; any case) and its sequence
+ * offsets (d_seq_off, seq_off, n_seqs), the copies into them queued on the handle's stream.  The k-mer keys, the stable sort (positions
+ * ascend inside a bucket) and the bucket offsets; d_off and d_pos are allocated here, when the text length is known.  Waits for the
+ * stream. */
+static int map_index_stage(asm_handle* h, asm_index* ix) {
+    const uint64_t len = ix->len;
+    const int k = ix->k;
+    const uint32_t nb = (1u << (2 * k)) + 1u;
+    HIPCHK(h, big_malloc(h, (void**)&ix->d_off, sizeof(uint32_t) * nb));
+    HIPCHK(h, big_malloc(h, (void**)&ix->d_pos, sizeof(uint32_t) * (len ? len : 1)));
+    if (len) {
+        Scratch<uint32_t> keys(h), keys2(h), vals(h);
+        MapTmp tmp(h);
+        HIPCHK(h, keys.alloc(sizeof(uint32_t) * len));
+        HIPCHK(h, keys2.alloc(sizeof(uint32_t) * len));
+        HIPCHK(h, vals.alloc(sizeof(uint32_t) * len));
+        HIPCHK(h, launch(h, map_upper_kernel, map_grid(len, h), 256, ix->d_text, (unsigned long long)len));
+        HIPCHK(h, launch(h, map_kmer_key_kernel, map_grid(len, h), 256, (const char*)ix->d_text, (unsigned long long)len,
+                         (const unsigned long long*)ix->d_seq_off, (uint32_t)ix->n_seqs, k, keys.p, vals.p));
+        HIPCHK(h, map_sort_pairs(h, tmp, keys.p, keys2.p, vals.p, ix->d_pos, (uint32_t)len, 2 * k + 1));
+        HIPCHK(h, launch(h, map_bucket_offsets_kernel, map_grid(nb, h), 256, (const uint32_t*)keys2.p, (unsigned long long)len, nb, ix->d_off));
+    } else {
+        HIPCHK(h, hipMemsetAsync(ix->d_off, 0, sizeof(uint32_t) * nb, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return ASM_OK;
+}
+
 } /* extern "C++" */
 
 int asm_index_build(asm_handle* h, const char* text, const uint64_t* seq_off, int32_t n_seqs, int k, asm_index** out) {
@@ -795,30 +824,11 @@ int asm_index_build(asm_handle* h, const char* text, const uint64_t* seq_off, in
     std::unique_ptr<asm_index> ix(new asm_index);
     ix->device = h->device, ix->k = k, ix->n_seqs = n_seqs, ix->len = len;
     ix->seq_off.assign(seq_off, seq_off + n_seqs + 1);
-    const uint32_t nb = (1u << (2 * k)) + 1u;
     HIPCHK(h, big_malloc(h, (void**)&ix->d_text, len + 16));
     HIPCHK(h, big_malloc(h, (void**)&ix->d_seq_off, sizeof(unsigned long long) * (size_t)(n_seqs + 1)));
-    HIPCHK(h, big_malloc(h, (void**)&ix->d_off, sizeof(uint32_t) * nb));
-    HIPCHK(h, big_malloc(h, (void**)&ix->d_pos, sizeof(uint32_t) * (len ? len : 1)));
     if (len) HIPCHK(h, hipMemcpyAsync(ix->d_text, text, len, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(ix->d_seq_off, seq_off, sizeof(uint64_t) * (size_t)(n_seqs + 1), hipMemcpyHostToDevice, h->stream));
-    if (len) {
-        Scratch<uint32_t> keys(h), keys2(h), vals(h);
-        MapTmp tmp(h);
-        HIPCHK(h, keys.alloc(sizeof(uint32_t) * len));
-        HIPCHK(h, keys2.alloc(sizeof(uint32_t) * len));
-        HIPCHK(h, vals.alloc(sizeof(uint32_t) * len));
-        HIPCHK(h, launch(h, map_upper_kernel, map_grid(len, h), 256, ix->d_text, (unsigned long long)len));
-        HIPCHK(h, launch(h, map_kmer_key_kernel, map_grid(len, h), 256, (const char*)ix->d_text, (unsigned long long)len,
-                         (const unsigned long long*)ix->d_seq_off, (uint32_t)n_seqs, k, keys.p, vals.p));
-        /* stable: positions ascend inside a bucket */
-        HIPCHK(h, map_sort_pairs(h, tmp, keys.p, keys2.p, vals.p, ix->d_pos, (uint32_t)len, 2 * k + 1));
-        HIPCHK(h, launch(h, map_bucket_offsets_kernel, map_grid(nb, h), 256, (const uint32_t*)keys2.p, (unsigned long long)len, nb, ix->d_off));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    } else {
-        HIPCHK(h, hipMemsetAsync(ix->d_off, 0, sizeof(uint32_t) * nb, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
+    if (const int rc = map_index_stage(h, ix.get())) return rc;
     *out = ix.release();
     return ASM_OK;
 }
@@ -826,6 +836,27 @@ int asm_index_build(asm_handle* h, const char* text, const uint64_t* seq_off, in
 int asm_index_free(asm_handle* h, asm_index* ix) {
     (void)h;
     delete ix;
+    return ASM_OK;
+}
+
+int32_t asm_index_n_seqs(const asm_index* ix) { return ix ? ix->n_seqs : 0; }
+
+uint64_t asm_index_seq_len(const asm_index* ix, int32_t r) {
+    return ix && r >= 0 && r < ix->n_seqs ? ix->seq_off[(size_t)r + 1] - ix->seq_off[(size_t)r] : 0;
+}
+
+const char* asm_index_seq_name(const asm_index* ix, int32_t r) {
+    return ix && r >= 0 && (size_t)r < ix->names.size() ? ix->names[(size_t)r].c_str() : "";
+}
+
+int asm_index_get_text(asm_handle* h, const asm_index* ix, uint64_t start, uint64_t n, char* dst) {
+    if (!ix || (n && !dst)) return fail(h, ASM_EINVAL, "asm_index_get_text: NULL argument");
+    if (start > ix->len || n > ix->len - start) return fail(h, ASM_EINVAL, "asm_index_get_text: the range must lie inside the text");
+    if (!h) return fail(h, ASM_EINVAL, "asm_index_get_text: NULL handle");
+    if (ix->device != h->device) return fail(h, ASM_EINVAL, "asm_index_get_text: the index lives on another device");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (n) HIPCHK(h, hipMemcpyAsync(dst, ix->d_text + start, n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return ASM_OK;
 }
 

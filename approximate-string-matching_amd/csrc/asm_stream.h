@@ -61,16 +61,22 @@ static hipError_t map_exclusive_sum(asm_handle* h, MapTmp& tmp, T* in, T* out, i
     return e != hipSuccess ? e : hipcub::DeviceScan::ExclusiveSum(tmp.s.p, bytes, in, out, (int)n, h->stream);
 }
 
-/* d_nl[l] = the position of the l-th newline of d_raw[0, nbytes), for the first `lines` of them (asm_ingest.h) */
-static hipError_t newline_index(asm_handle* h, MapTmp& tmp, const char* d_raw, size_t nbytes, long lines, uint32_t* d_nl) {
+/* d_nl[l] = the position of the l-th newline of d_raw[0, nbytes), for the first `lines` of them (asm_ingest.h); d_tbase: per tile of
+ * SEQ_TILE bytes, the newlines before it */
+static hipError_t newline_index(asm_handle* h, MapTmp& tmp, const char* d_raw, size_t nbytes, long lines, uint32_t* d_nl,
+                                Scratch<uint32_t>& d_tbase) {
     const long ntiles = (long)((nbytes + SEQ_TILE - 1) / SEQ_TILE);
-    Scratch<uint32_t> d_tile(h), d_tbase(h);
+    Scratch<uint32_t> d_tile(h);
     hipError_t e = d_tile.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1));
     if (e == hipSuccess) e = d_tbase.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1));
     if (e == hipSuccess) e = launch(h, seq_count_kernel, (unsigned)ntiles, 256, d_raw, (long)nbytes, d_tile.p);
     if (e == hipSuccess) e = map_exclusive_sum(h, tmp, d_tile.p, d_tbase.p, (int64_t)ntiles);
     if (e != hipSuccess) return e;
     return launch(h, seq_index_kernel, (unsigned)ntiles, 256, d_raw, (long)nbytes, (const uint32_t*)d_tbase.p, d_nl, lines);
+}
+static hipError_t newline_index(asm_handle* h, MapTmp& tmp, const char* d_raw, size_t nbytes, long lines, uint32_t* d_nl) {
+    Scratch<uint32_t> d_tbase(h);
+    return newline_index(h, tmp, d_raw, nbytes, lines, d_nl, d_tbase);
 }
 
 /* The input side of one streamed call: the file, the copy-in stream, three pinned slots in rotation (the reader thread fills them),
@@ -155,6 +161,18 @@ struct StreamInput {
         STREAM_TRY(who, hipEventRecord(ev_h2d[q], s_in));
         return ASM_OK;
     }
+    /* For a reader's policy, on the reader's thread, when the pinned slots are owned: a unit longer than slot q gets a larger pinned
+     * one, with the first `keep` bytes of the old one.  No copy reads the old one now: the reader has waited for the one out of it. */
+    bool grow_pin(asm_host::ChunkSlot* slots, int q, size_t cap, size_t keep) {
+        (void)hipSetDevice(h->device);
+        char* bigger = nullptr;
+        if (hipHostMalloc((void**)&bigger, cap + 64, hipHostMallocDefault) != hipSuccess) return false;
+        if (keep) memcpy(bigger, pin[q], keep);
+        (void)hipHostFree(pin[q]);
+        pin[q] = bigger;
+        slots[q].buf = bigger, slots[q].cap = cap;
+        return true;
+    }
     std::function<void(int)> wait_shipped() { /* for the reader: the copy out of slot q is over */
         return [this](int q) {
             (void)hipSetDevice(h->device);
@@ -165,9 +183,11 @@ struct StreamInput {
      * blocks this thread (the parser's totals), so with the stages the other way round the transfer of the next chunk could not
      * start before the current one was parsed, and the copy engine idled through every parse.
      * accept(slot, first_unit) sees every chunk before it is shipped; process(q, bytes, units, first_unit) runs behind the copy into
-     * d_raw[q], for every chunk that holds a unit; first_unit: the file's units before the chunk.  read_failed: the reader's message. */
+     * d_raw[q], for every chunk that holds a unit; first_unit: the file's units before the chunk.  read_failed: the reader's message.
+     * hold_slots: a chunk's pinned slot goes back to the reader after the chunk has been processed instead of after its copy has been
+     * started, for a process() that reads the slot (two slots are then held while the reader fills the third). */
     template <class Reader, class Accept, class Process>
-    int run(Reader& rd, const std::string& read_failed, Accept accept, Process process) {
+    int run(Reader& rd, const std::string& read_failed, Accept accept, Process process, bool hold_slots = false) {
         struct {
             bool valid = false;
             size_t bytes = 0;
@@ -192,8 +212,9 @@ struct StreamInput {
                 if (const int rc = ship(c, *s)) return rc;
             pend[q].valid = true, pend[q].bytes = s->bytes, pend[q].units = s->units, pend[q].first = seen;
             seen += s->units;
-            rd.consumed(c, s->units > 0); /* the reader may refill the slot once ev_shipped has fired */
+            if (!hold_slots) rd.consumed(c, s->units > 0); /* the reader may refill the slot once ev_shipped has fired */
             if (const int rc = flush(q ^ 1)) return rc;
+            if (hold_slots && c > 0) rd.consumed(c - 1, true);
         }
         for (int q = 0; q < 2; q++) /* the last chunk shipped (only one of the two is pending) */
             if (const int rc = flush(q)) return rc;

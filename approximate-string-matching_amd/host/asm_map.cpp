@@ -11,6 +11,10 @@
 // writes (four-line FASTQ only; the same lines as without it); --chunk-bytes N: file bytes per chunk (default: the library's).
 // --stream-pairs does the same for paired mode through asm_map_pairs_file (two four-line FASTQ files; the lines of -1 / -2 without
 // --all-hits); --stream together with -2 is a usage error.
+// --ref-stream (any mode) builds the index with asm_index_build_file, which reads and parses the reference on the device, and takes
+// the names and lengths for @SQ and RNAME from the index; without it the reference is parsed here.  The SAM is the same.
+//   asm-map -r ref.fa --bench-ref N [--k 12]
+// maps nothing: it builds the index N times each way, alternately, and prints the seconds of every build.
 // --all-hits N writes up to N loci per read in rank order (asm_map_reads_all, strata S, default e): the primary record as without
 // it, then the secondary ones (FLAG 256, SEQ and QUAL '*'), each with NH:i:<reported> HI:i:<rank + 1> XH:i:<all loci> after NM
 // and XG.  Reads may be FASTQ or FASTA (QUAL '*').  Reads are processed in chunks of --chunk records, so the read file's size is not
@@ -31,6 +35,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <chrono>
 #include <string>
 #include <vector>
 
@@ -44,7 +49,8 @@ static void usage() {
                     "       asm-map -r ref.fa -q reads.fq --stream [--chunk-bytes N] [-o out.sam] [-e N] [--k 12] [--both-strands] "
                     "[--max-occ N] [--all-hits N [--strata S]]\n"
                     "       asm-map -r ref.fa -1 r1.fq -2 r2.fq --stream-pairs [--chunk-bytes N] [-o out.sam] -e N --insert MIN,MAX "
-                    "[--rescue E] [--k 12] [--max-occ N]\n");
+                    "[--rescue E] [--k 12] [--max-occ N]\n"
+                    "       any of them with --ref-stream: the reference is read and parsed by the library\n");
     exit(2);
 }
 
@@ -265,6 +271,79 @@ static void report_streamed(const Stats& st) {
             (long long)st.chunks, (long long)st.bytes_in, (long long)st.bytes_out, st.seconds, st.seconds_read, st.seconds_write);
 }
 
+/* the reference, parsed here: name = first word of the header; off starts as {0} */
+static bool parse_reference(const std::string& ref_path, std::vector<std::string>& names, std::vector<uint64_t>& off, std::string& text) {
+    FILE* f = fopen(ref_path.c_str(), "r");
+    if (!f) {
+        fprintf(stderr, "asm-map: cannot open %s\n", ref_path.c_str());
+        return false;
+    }
+    std::string line;
+    while (get_line(f, line)) {
+        if (!line.empty() && line[0] == '>') {
+            if (!names.empty()) off.push_back(text.size());
+            names.push_back(first_word(line.substr(1)));
+        } else if (!names.empty()) {
+            for (char c : line)
+                if (c != ' ' && c != '\t') text.push_back(up(c));
+        }
+    }
+    fclose(f);
+    if (names.empty()) {
+        fprintf(stderr, "asm-map: no sequence in %s\n", ref_path.c_str());
+        return false;
+    }
+    off.push_back(text.size());
+    return true;
+}
+
+/* --bench-ref N: the two ways from the reference file to its index, alternately in one process, N times each; one line of seconds
+ * per build on stdout (tools/bench_index_file.py reads them) */
+static int bench_reference(const std::string& ref_path, int k, int reps) {
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+        return std::chrono::duration<double>(b - a).count();
+    };
+    asm_handle* h = nullptr;
+    if (asm_create(&h, 0)) {
+        fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
+        return 1;
+    }
+    for (int rep = 0; rep < reps; rep++) {
+        asm_index* ix = nullptr;
+        {
+            std::vector<std::string> names;
+            std::vector<uint64_t> off(1, 0);
+            std::string text;
+            const auto t0 = now();
+            if (!parse_reference(ref_path, names, off, text)) return 1;
+            const auto t1 = now();
+            const int rc = asm_index_build(h, text.data(), off.data(), (int32_t)names.size(), k, &ix);
+            const auto t2 = now();
+            if (rc) {
+                fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
+                return 1;
+            }
+            printf("host seconds %.6f parse %.6f index_build %.6f bases %llu\n", secs(t0, t2), secs(t0, t1), secs(t1, t2),
+                   (unsigned long long)text.size());
+            asm_index_free(h, ix);
+        }
+        asm_index_file_stats st;
+        const auto t0 = now();
+        const int rc = asm_index_build_file(h, ref_path.c_str(), k, 0, &ix, &st);
+        const auto t1 = now();
+        if (rc) {
+            fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
+            return 1;
+        }
+        printf("file seconds %.6f reader_busy %.6f index_stage %.6f chunks %lld bases %lld\n", secs(t0, t1), st.seconds_read, st.seconds_index,
+               (long long)st.chunks, (long long)st.bases);
+        asm_index_free(h, ix);
+    }
+    asm_destroy(h);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     std::string ref_path, read_path, read2_path, out_path = "out.sam";
     asm_pair_params pp = {-1, -1, -1};
@@ -272,7 +351,8 @@ int main(int argc, char** argv) {
     int k = 12;
     long chunk = 262144;
     int all_hits = 0, strata = -1; /* all_hits 0: the best hit only */
-    bool stream = false, stream_pairs = false;
+    bool stream = false, stream_pairs = false, ref_stream = false;
+    int bench_ref = 0;
     long long chunk_bytes = 0;
     std::string cl = "asm-map";
     for (int a = 1; a < argc; a++) cl += std::string(" ") + argv[a];
@@ -298,10 +378,12 @@ int main(int argc, char** argv) {
         else if (s == "--strata") strata = atoi(val());
         else if (s == "--stream") stream = true;
         else if (s == "--stream-pairs") stream_pairs = true;
+        else if (s == "--ref-stream") ref_stream = true;
+        else if (s == "--bench-ref") bench_ref = atoi(val());
         else if (s == "--chunk-bytes") chunk_bytes = atoll(val());
         else usage();
     }
-    if (ref_path.empty() || read_path.empty() || chunk < 1 || all_hits < 0 || (strata >= 0 && !all_hits)) usage();
+    if (ref_path.empty() || (read_path.empty() && bench_ref < 1) || chunk < 1 || all_hits < 0 || (strata >= 0 && !all_hits)) usage();
     const bool paired = !read2_path.empty();
     if (chunk_bytes < 0 || (chunk_bytes > 0 && !stream && !stream_pairs) || (stream && paired)) usage(); /* paired: --stream-pairs */
     if (stream_pairs && (!paired || all_hits || stream)) usage(); /* secondary pairs from files: not there */
@@ -311,33 +393,11 @@ int main(int argc, char** argv) {
     if (strata < 0) strata = paired ? 2 * p.max_errors : p.max_errors; /* paired: strata on the d sum of a pair */
     const int slots = all_hits ? all_hits : 1; /* records per read in the library's output */
 
-    /* reference: name = first word of the header */
+    if (bench_ref > 0) return bench_reference(ref_path, k, bench_ref);
     std::vector<std::string> names;
     std::vector<uint64_t> off(1, 0);
     std::string text;
-    {
-        FILE* f = fopen(ref_path.c_str(), "r");
-        if (!f) {
-            fprintf(stderr, "asm-map: cannot open %s\n", ref_path.c_str());
-            return 1;
-        }
-        std::string line;
-        while (get_line(f, line)) {
-            if (!line.empty() && line[0] == '>') {
-                if (!names.empty()) off.push_back(text.size());
-                names.push_back(first_word(line.substr(1)));
-            } else if (!names.empty()) {
-                for (char c : line)
-                    if (c != ' ' && c != '\t') text.push_back(up(c));
-            }
-        }
-        fclose(f);
-        if (names.empty()) {
-            fprintf(stderr, "asm-map: no sequence in %s\n", ref_path.c_str());
-            return 1;
-        }
-        off.push_back(text.size());
-    }
+    if (!ref_stream && !parse_reference(ref_path, names, off, text)) return 1;
     FILE* rf = fopen(read_path.c_str(), "r");
     if (!rf) {
         fprintf(stderr, "asm-map: cannot open %s\n", read_path.c_str());
@@ -377,11 +437,18 @@ int main(int argc, char** argv) {
     asm_handle* h = nullptr;
     asm_index* ix = nullptr;
     int rc = asm_create(&h, 0);
-    if (!rc) rc = asm_index_build(h, text.data(), off.data(), (int32_t)names.size(), k, &ix);
+    if (!rc)
+        rc = ref_stream ? asm_index_build_file(h, ref_path.c_str(), k, 0, &ix, nullptr)
+                        : asm_index_build(h, text.data(), off.data(), (int32_t)names.size(), k, &ix);
     if (rc) {
         fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
         return 1;
     }
+    if (ref_stream) /* the index knows its sequences */
+        for (int32_t r = 0; r < asm_index_n_seqs(ix); r++) {
+            names.push_back(asm_index_seq_name(ix, r));
+            off.push_back(off.back() + asm_index_seq_len(ix, r));
+        }
     std::string header = "@HD\tVN:1.6\tSO:unsorted\n";
     for (size_t r = 0; r < names.size(); r++)
         header += "@SQ\tSN:" + names[r] + "\tLN:" + std::to_string((unsigned long long)(off[r + 1] - off[r])) + "\n";

@@ -491,6 +491,39 @@ int asm_map_pairs_file(asm_handle* h, const asm_index* ix, const char* const* se
                        const asm_pair_params* pp, int64_t chunk_bytes, asm_map_pairs_file_stats* stats /* may be NULL */);
 size_t asm_fastq_cut_n(const char* buf, size_t nbytes, int64_t max_records, int64_t* records);
 
+/* asm_index_build_file: asm_index_build from a FASTA file (docs/design/mapper.md, "Reference: FASTA in, index out"); synchronous.  The
+ *                  file is read in chunks of about chunk_bytes (0: 16 MiB) that may end anywhere except inside a header line, so a
+ *                  sequence line may have any length; a chunk is parsed on the device while the next one is read and copied in.
+ *                  The file: lines end in LF or CRLF, the last newline may be missing.  A line whose first byte is '>' is a header
+ *                  line and starts a new sequence; its name is the first word behind the '>' (blanks and tabs are skipped, the word
+ *                  ends at a blank, a tab or the line's end without its CR; it may be empty).  Every other line behind the first
+ *                  header is a sequence line: all of its bytes go into the text except blank, tab, CR and LF, a-z in upper case,
+ *                  every other byte ('N', '*', '-', a '>' inside a line) as it is, for the byte rule above.  Lines before the first
+ *                  header are ignored.  A header followed at once by a header or by the end of the file gives a sequence of length
+ *                  0.  The sequences lie back to back in file order, seq_off as for asm_index_build.  ASM_EINVAL: a file that cannot
+ *                  be opened, a file without a header line ("no sequence in <path>"), 2^26 sequences or more; ASM_EUNSUPPORTED: a
+ *                  text of 2^32 - 1 bytes or more.  On an error *out is NULL.  The index does not depend on chunk_bytes.
+ * asm_index_n_seqs, asm_index_seq_len, asm_index_seq_name, asm_index_get_text: what an index holds, from either call: its sequences,
+ *                  the length of sequence r (0 when r is out of range), its name ("" for an index from asm_index_build or r out of
+ *                  range; valid until asm_index_free) and bytes [start, start + n) of the upper-cased text, by global offsets
+ *                  (synchronous).
+ * asm_fasta_cut:   how much of buf[0, nbytes) the reader ships as one chunk: all of it, unless its last line is a header line still
+ *                  without its newline, then the bytes in front of that line; at_line_start: buf[0] begins a line; *ends_in_line:
+ *                  the shipped prefix ends inside a line (the next buffer's at_line_start is then 0).  No device.
+ * ASM_FASTA_TILE:  the bytes one workgroup of the parser takes, 16 per thread: where the parser's edges are. */
+#define ASM_FASTA_TILE 4096
+typedef struct asm_index_file_stats {
+    int64_t n_seqs, bases, bytes_in, chunks;     /* sequences; text length; file bytes; file chunks */
+    double seconds, seconds_read, seconds_index; /* whole call; reader busy; k-mer keys + sort + bucket offsets */
+} asm_index_file_stats;
+int asm_index_build_file(asm_handle* h, const char* fasta_path, int k, int64_t chunk_bytes, asm_index** out,
+                         asm_index_file_stats* stats /* may be NULL */);
+int32_t asm_index_n_seqs(const asm_index* ix);
+uint64_t asm_index_seq_len(const asm_index* ix, int32_t r);
+const char* asm_index_seq_name(const asm_index* ix, int32_t r);
+int asm_index_get_text(asm_handle* h, const asm_index* ix, uint64_t start, uint64_t n, char* dst);
+size_t asm_fasta_cut(const char* buf, size_t nbytes, int at_line_start, int* ends_in_line);
+
 /* ---- plain device memory helpers (so that non-torch hosts can drive the async API) --------------------- */
 int asm_device_malloc(asm_handle* h, size_t bytes, void** d_ptr);
 int asm_device_free(asm_handle* h, void* d_ptr);
