@@ -3,13 +3,11 @@ that the other GPU modules do not pin, bit for bit against the oracle.  The arms
 every case is 1,061 pairs, two full 512-pair workgroups of the widest kernels and a ragged tail of 37.  One-granule cases use
 the C2 configuration (100 bp); a length class is random_ragged_batch with its lengths inside the class, so that the batch's
 longest string, which picks the kernel, is known."""
-import os
-
 import numpy as np
 import pytest
 
 from tests.oracle_binding import SIMD_WARM_STATE
-from tests.util import random_ragged_batch
+from tests.util import check, engine_with, random_ragged_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -42,25 +40,6 @@ def inputs(asm):
         return made[key]
 
     return get
-
-
-def check(name, got, want, hb):
-    bad = np.nonzero(got != want)[0]
-    assert bad.size == 0, (f"{name}: {bad.size}/{hb.n} differ; first {bad[:5]} got {got[bad[:5]]} want {want[bad[:5]]} "
-                           f"pair {hb.pair(int(bad[0]))}")
-
-
-def engine_with(asm, switch):
-    """A second handle created with `switch`=0 (the switches are read once, at creation)."""
-    old = os.environ.get(switch)
-    os.environ[switch] = "0"
-    try:
-        return asm.Engine(0)
-    finally:
-        if old is None:
-            del os.environ[switch]
-        else:
-            os.environ[switch] = old
 
 
 @pytest.fixture(scope="module")
