@@ -541,11 +541,12 @@ class Engine:
                         capacity: Optional[int] = None, answers: Optional[np.ndarray] = None):
         """asm_stream_seq_file: `benchmark::read_string_file` + `run` (benchmark_utils.h:325-385) for a file of any size, streamed
         through pinned buffers with the parse, the pack and the aligners of one chunk overlapping the transfer of the next.
-        -> (dict aligner -> int32[pairs], StreamStats).  capacity: entries of the result arrays (default: an upper bound from
-        the file size; shorter reads need a larger bound, or max_pairs)."""
+        -> (dict aligner -> int32[pairs], StreamStats).  capacity: entries of the result arrays (default: max_pairs, or an upper
+        bound from the file size: a pair takes at least two bytes, the newlines of two lines of zero bytes, which the parser
+        reads as two empty strings, so a file of B bytes holds at most B // 2 + 1 pairs)."""
         if capacity is None:
             try:
-                capacity = max_pairs if max_pairs > 0 else os.path.getsize(path) // 4 + 16
+                capacity = max_pairs if max_pairs > 0 else os.path.getsize(path) // 2 + 16
             except OSError:
                 capacity = 16  # the library reports the unreadable file (benchmark_utils.h:350 only prints)
         mask = sum(1 << a for a in aligners)
