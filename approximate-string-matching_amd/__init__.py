@@ -114,6 +114,11 @@ class MapPairsFileStats(ctypes.Structure):
                 ("seconds_write", ctypes.c_double)]
 
 
+class SamSortStats(ctypes.Structure):
+    """asm_sam_sort_stats"""
+    _fields_ = [("lines", ctypes.c_int64), ("bytes_held", ctypes.c_int64), ("slabs", ctypes.c_int64), ("seconds_sort", ctypes.c_double)]
+
+
 class IndexFileStats(ctypes.Structure):
     """asm_index_file_stats"""
     _fields_ = [("n_seqs", ctypes.c_int64), ("bases", ctypes.c_int64), ("bytes_in", ctypes.c_int64), ("chunks", ctypes.c_int64),
@@ -278,6 +283,11 @@ def load_library() -> ctypes.CDLL:
         "asm_map_pairs_file": (i32, [vp, vp, c.POINTER(c.c_char_p), c.c_char_p, c.c_char_p, c.c_char_p, c.c_char_p, c.POINTER(MapParams),
                                      c.POINTER(PairParams), i64, c.POINTER(MapPairsFileStats)]),
         "asm_fastq_cut_n": (c.c_size_t, [vp, c.c_size_t, i64, c.POINTER(i64)]),
+        "asm_map_file_sorted": (i32, [vp, vp, c.POINTER(c.c_char_p), c.c_char_p, c.c_char_p, c.c_char_p, c.POINTER(MapParams), i32, i32, i64,
+                                      i64, c.POINTER(MapFileStats), c.POINTER(SamSortStats)]),
+        "asm_map_pairs_file_sorted": (i32, [vp, vp, c.POINTER(c.c_char_p), c.c_char_p, c.c_char_p, c.c_char_p, c.c_char_p,
+                                            c.POINTER(MapParams), c.POINTER(PairParams), i64, i64, c.POINTER(MapPairsFileStats),
+                                            c.POINTER(SamSortStats)]),
         "asm_index_build_file": (i32, [vp, c.c_char_p, i32, i64, c.POINTER(vp), c.POINTER(IndexFileStats)]),
         "asm_index_n_seqs": (c.c_int32, [vp]),
         "asm_index_seq_len": (c.c_uint64, [vp, c.c_int32]),
@@ -695,36 +705,49 @@ class Engine:
 
     def map_file(self, index: Index, names, fastq_path: str, sam_path: str, max_errors: int, both_strands: bool = True,
                  max_occ: int = 0, greedy_k: int = 3, max_hits: int = 0, strata: Optional[int] = None, chunk_bytes: int = 0,
-                 header: Optional[str] = None) -> dict:
+                 header: Optional[str] = None, sort: bool = False, max_device_bytes: int = 0) -> dict:
         """asm_map_file: a four-line FASTQ file in, a SAM file out, parsed, mapped and formatted on the device (docs/design/mapper.md,
         "Files: FASTQ in, SAM out").  names: one RNAME per sequence of the index.  max_hits=0: the best hit per read (map_reads);
         1..256: the loci of map_reads_all with strata (None: max_errors).  header is written first, as it is.  -> the stats as a dict:
-        reads, mapped, too_long, records (SAM lines), chunks, bytes_in, bytes_out, seconds, seconds_read, seconds_write."""
+        reads, mapped, too_long, records (SAM lines), chunks, bytes_in, bytes_out, seconds, seconds_read, seconds_write.
+        sort=True: asm_map_file_sorted, the same lines in coordinate order ("Sorted output"; max_device_bytes caps what is held on
+        the device, 0: no cap); the dict then holds the sort's stats too, under "sort": lines, bytes_held, slabs, seconds_sort."""
         arr = self._rnames(index, names)
         p = MapParams(int(max_errors), 1 if both_strands else 0, int(max_occ), int(greedy_k))
         st = MapFileStats()
         strata = int(max_errors) if strata is None else int(strata)
-        self._chk(self.lib.asm_map_file(self.h, index.ptr, arr, os.fsencode(fastq_path), os.fsencode(sam_path),
-                                        None if header is None else _as_bytes(header), ctypes.byref(p), int(max_hits), strata,
-                                        int(chunk_bytes), ctypes.byref(st)))
-        return {name: getattr(st, name) for name, _ in MapFileStats._fields_}
+        args = (self.h, index.ptr, arr, os.fsencode(fastq_path), os.fsencode(sam_path), None if header is None else _as_bytes(header),
+                ctypes.byref(p), int(max_hits), strata, int(chunk_bytes))
+        if not sort:
+            self._chk(self.lib.asm_map_file(*args, ctypes.byref(st)))
+            return {name: getattr(st, name) for name, _ in MapFileStats._fields_}
+        sst = SamSortStats()
+        self._chk(self.lib.asm_map_file_sorted(*args, int(max_device_bytes), ctypes.byref(st), ctypes.byref(sst)))
+        return dict({name: getattr(st, name) for name, _ in MapFileStats._fields_},
+                    sort={name: getattr(sst, name) for name, _ in SamSortStats._fields_})
 
     def map_pairs_file(self, index: Index, names, fastq1_path: str, fastq2_path: str, sam_path: str, max_errors: int, min_insert: int,
                        max_insert: int, rescue_errors: int = -1, max_occ: int = 0, greedy_k: int = 3, chunk_bytes: int = 0,
-                       header: Optional[str] = None) -> dict:
+                       header: Optional[str] = None, sort: bool = False, max_device_bytes: int = 0) -> dict:
         """asm_map_pairs_file: two four-line FASTQ files in (record i of each: the mates of pair i), a paired SAM file out, parsed,
         paired, mapped and formatted on the device (docs/design/mapper.md, "Files: two FASTQ files in, paired SAM out"); the answer
         is map_pairs'.  names: one RNAME per sequence of the index.  header is written first, as it is.  -> the stats as a dict:
         pairs, proper, rescued, unsent, records (SAM lines), chunks, bytes_in, bytes_out, carry_peak, seconds, seconds_read,
-        seconds_write."""
+        seconds_write.  sort=True: asm_map_pairs_file_sorted, the same lines in coordinate order; max_device_bytes and the "sort" entry
+        of the dict as for map_file."""
         arr = self._rnames(index, names)
         p = MapParams(int(max_errors), 1, int(max_occ), int(greedy_k))
         pp = PairParams(int(min_insert), int(max_insert), int(rescue_errors))
         st = MapPairsFileStats()
-        self._chk(self.lib.asm_map_pairs_file(self.h, index.ptr, arr, os.fsencode(fastq1_path), os.fsencode(fastq2_path),
-                                              os.fsencode(sam_path), None if header is None else _as_bytes(header), ctypes.byref(p),
-                                              ctypes.byref(pp), int(chunk_bytes), ctypes.byref(st)))
-        return {name: getattr(st, name) for name, _ in MapPairsFileStats._fields_}
+        args = (self.h, index.ptr, arr, os.fsencode(fastq1_path), os.fsencode(fastq2_path), os.fsencode(sam_path),
+                None if header is None else _as_bytes(header), ctypes.byref(p), ctypes.byref(pp), int(chunk_bytes))
+        if not sort:
+            self._chk(self.lib.asm_map_pairs_file(*args, ctypes.byref(st)))
+            return {name: getattr(st, name) for name, _ in MapPairsFileStats._fields_}
+        sst = SamSortStats()
+        self._chk(self.lib.asm_map_pairs_file_sorted(*args, int(max_device_bytes), ctypes.byref(st), ctypes.byref(sst)))
+        return dict({name: getattr(st, name) for name, _ in MapPairsFileStats._fields_},
+                    sort={name: getattr(sst, name) for name, _ in SamSortStats._fields_})
 
     def map_pairs(self, index: Index, reads1, reads2, max_errors: int, min_insert: int, max_insert: int, rescue_errors: int = -1,
                   max_occ: int = 0, greedy_k: int = 3, cigar_cap: int = 64, chunk: Optional[int] = None):

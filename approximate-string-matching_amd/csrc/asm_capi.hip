@@ -1925,6 +1925,8 @@ int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, in
 
 /* ---- read mapping: host side in csrc/asm_map_host.h (kernels: csrc/asm_map.h, design: docs/design/mapper.md) -------------------- */
 #include "asm_map_host.h"
+/* what the sorted file calls keep on the device, their sort and their gather */
+#include "asm_sam_sort.h"
 /* asm_map_file: FASTQ in, SAM out, through the same stages */
 #include "asm_map_file.h"
 /* asm_map_pairs_file: two FASTQ files in, paired SAM out */

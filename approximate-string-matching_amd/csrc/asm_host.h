@@ -734,4 +734,18 @@ public:
     double write_seconds() const { return write_seconds_; } /* after finish() */
 };
 
+/* The output slabs of the sorted file calls (asm_sam_sort.h): off[0 .. n] are the byte offsets of n lines laid back to back and
+ * off[n] their total.  -> the cuts c[0] = 0 < c[1] < ... < c[k] = n: slab s holds the lines [c[s], c[s + 1]), as many as fit into
+ * `cap` bytes and always at least one, so a slab is longer than cap only when it is a single line that is.  n = 0 gives {0}. */
+inline std::vector<size_t> sam_slab_cuts(const uint64_t* off, size_t n, uint64_t cap) {
+    std::vector<size_t> cuts(1, 0);
+    for (size_t at = 0; at < n;) {
+        size_t end = at + 1;
+        while (end < n && off[end + 1] - off[at] <= cap) end++;
+        cuts.push_back(end);
+        at = end;
+    }
+    return cuts;
+}
+
 }  // namespace asm_host

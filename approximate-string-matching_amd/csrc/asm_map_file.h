@@ -66,6 +66,7 @@ struct MapFileSession {
         double seconds_read;
     } st = {};
     std::unique_ptr<asm_host::ChunkWriter> writer;
+    std::unique_ptr<SamSortHold> sort; /* the sorted calls: the formatted chunks stay on the device until finish() (asm_sam_sort.h) */
     MapFileSession(asm_handle* owner, const char* call, size_t chunk_bytes)
         : h(owner), who(call), pipe(owner, call), d_names(owner), d_name_off(owner), chunk(chunk_bytes) {}
 
@@ -134,9 +135,12 @@ struct MapFileSession {
         return ASM_OK;
     }
 
-    /* after run() and the call's own last checks: the SAM file complete, and the shared fields of the call's stats */
+    /* after run() and the call's own last checks: the SAM file complete (a sorted call writes all of it here, in slabs of at most a
+     * chunk), and the shared fields of the call's stats */
     template <class Stats>
     int finish(Stats& out) {
+        if (sort)
+            if (const int rc = sort->flush(pipe, *writer, out_seq, chunk)) return rc;
         if (!writer->finish() || fflush(pipe.out) != 0) return bad("writing the SAM file failed");
         out.chunks = st.chunks, out.bytes_in = st.bytes_in, out.bytes_out = st.bytes_out, out.records = st.records;
         out.seconds_read = st.seconds_read, out.seconds_write = writer->write_seconds();
@@ -200,6 +204,11 @@ static int map_file_format(MapFileSession& ss, MapTmp& tmp, SamArgs& a, unsigned
     STREAM_TRY(who, map_exclusive_sum(h, tmp, d_size.p, d_off.p, nlines + 1));
     unsigned long long total = 0;
     STREAM_TRY(who, fetch(h, {fetched(&total, d_off.p + nlines), fetched(n, d_n.p, NC)}));
+    if (ss.sort) { /* a sorted call: the lines are emitted into a block that stays on the device, and nothing is written yet */
+        if (const int rc = ss.sort->hold<PAIRED>(a, total)) return rc;
+        ss.st.records += nlines, ss.st.chunks++, ss.st.bytes_out += (int64_t)total;
+        return ASM_OK;
+    }
     const int o = (int)(ss.out_seq % 3);
     ss.writer->wait_idle(o);
     if (ss.writer->failed()) return ss.bad("writing the SAM file failed");
@@ -330,9 +339,12 @@ static int map_file_chunk(MapReadsFileJob& j, const char* d_raw, const uint32_t*
     return ASM_OK;
 }
 
-static int map_file_run(asm_handle* h, const asm_index* ix, const char* const* seq_names, const char* fastq_path, const char* sam_path,
-                        const char* header, const asm_map_params* p, int max_hits, int strata, size_t chunk, asm_map_file_stats* stats) {
-    MapFileSession ss(h, "asm_map_file", chunk);
+/* sort_cap: NULL for asm_map_file, max_device_bytes for asm_map_file_sorted */
+static int map_file_run(asm_handle* h, const char* who, const asm_index* ix, const char* const* seq_names, const char* fastq_path,
+                        const char* sam_path, const char* header, const asm_map_params* p, int max_hits, int strata, size_t chunk,
+                        asm_map_file_stats* stats, const int64_t* sort_cap, asm_sam_sort_stats* sort_stats) {
+    MapFileSession ss(h, who, chunk);
+    if (sort_cap) ss.sort.reset(new SamSortHold(h, who, ix->n_seqs, (size_t)*sort_cap));
     StreamInput& in = ss.pipe.in;
     size_t file_bytes = 0;
     if (const int rc = in.open_file(fastq_path, &file_bytes)) return rc;
@@ -340,7 +352,7 @@ static int map_file_run(asm_handle* h, const asm_index* ix, const char* const* s
     asm_host::ChunkReader<asm_host::FastqFill> rd(chunk, ss.first_chunk, in.wait_shipped(), in.fd, file_bytes, chunk, ss.grow());
     MapReadsFileJob j = {{ss, ix, p}, max_hits, strata};
     const int rc = ss.run(
-        rd, std::string("asm_map_file: reading ") + fastq_path + " failed",
+        rd, std::string(who) + ": reading " + fastq_path + " failed",
         [&](const asm_host::ChunkSlot& s, int64_t records_seen) {
             if (s.extra_lines)
                 return ss.bad("record " + std::to_string(records_seen + s.units + 1) +
@@ -357,24 +369,48 @@ static int map_file_run(asm_handle* h, const asm_index* ix, const char* const* s
     if (rc) return rc;
     if (const int rf = ss.finish(j.st)) return rf;
     if (stats) *stats = j.st;
+    if (sort_stats && ss.sort) *sort_stats = ss.sort->st;
     return ASM_OK;
+}
+
+/* max_device_bytes of the two sorted calls: checked behind chunk_bytes */
+static int map_file_sort_cap(asm_handle* h, const char* who, const int64_t* sort_cap) {
+    return sort_cap && *sort_cap < 0 ? fail(h, ASM_EINVAL, std::string(who) + ": max_device_bytes must be >= 0") : (int)ASM_OK;
+}
+
+/* asm_map_file and asm_map_file_sorted (`who`): the argument checks, then the call */
+static int map_file_call(const char* who, asm_handle* h, const asm_index* ix, const char* const* seq_names, const char* fastq_path,
+                         const char* sam_path, const char* header, const asm_map_params* p, int max_hits, int strata, int64_t chunk_bytes,
+                         asm_map_file_stats* stats, const int64_t* sort_cap, asm_sam_sort_stats* sort_stats) {
+    const std::string name = who;
+    if (!p || !ix || !seq_names || !fastq_path || !sam_path) return fail(h, ASM_EINVAL, name + ": bad arguments");
+    if (max_hits < 0 || max_hits > ASM_MAP_MAX_HITS) return fail(h, ASM_EINVAL, name + ": max_hits must be in [0, 256]");
+    size_t chunk = 0;
+    if (const int rc = map_file_chunk_bytes(h, who, chunk_bytes, &chunk)) return rc;
+    if (const int rc = map_file_sort_cap(h, who, sort_cap)) return rc;
+    if (const int rc = map_check_args(h, ix, who, "read",
+                                      {0, p, {nullptr, nullptr}, nullptr, max_hits ? "max_hits" : nullptr, strata, ASM_MAP_MAX_ERRORS,
+                                       max_hits, {nullptr, 0, nullptr}}))
+        return rc;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (sort_stats) memset(sort_stats, 0, sizeof *sort_stats);
+    HIPCHK(h, hipSetDevice(h->device));
+    return map_file_run(h, who, ix, seq_names, fastq_path, sam_path, header, p, max_hits, strata, chunk, stats, sort_cap, sort_stats);
 }
 
 } /* extern "C++" */
 
 int asm_map_file(asm_handle* h, const asm_index* ix, const char* const* seq_names, const char* fastq_path, const char* sam_path,
                  const char* header, const asm_map_params* p, int max_hits, int strata, int64_t chunk_bytes, asm_map_file_stats* stats) {
-    if (!p || !ix || !seq_names || !fastq_path || !sam_path) return fail(h, ASM_EINVAL, "asm_map_file: bad arguments");
-    if (max_hits < 0 || max_hits > ASM_MAP_MAX_HITS) return fail(h, ASM_EINVAL, "asm_map_file: max_hits must be in [0, 256]");
-    size_t chunk = 0;
-    if (const int rc = map_file_chunk_bytes(h, "asm_map_file", chunk_bytes, &chunk)) return rc;
-    if (const int rc = map_check_args(h, ix, "asm_map_file", "read",
-                                      {0, p, {nullptr, nullptr}, nullptr, max_hits ? "max_hits" : nullptr, strata, ASM_MAP_MAX_ERRORS,
-                                       max_hits, {nullptr, 0, nullptr}}))
-        return rc;
-    if (stats) memset(stats, 0, sizeof *stats);
-    HIPCHK(h, hipSetDevice(h->device));
-    return map_file_run(h, ix, seq_names, fastq_path, sam_path, header, p, max_hits, strata, chunk, stats);
+    return map_file_call("asm_map_file", h, ix, seq_names, fastq_path, sam_path, header, p, max_hits, strata, chunk_bytes, stats, nullptr,
+                         nullptr);
+}
+
+int asm_map_file_sorted(asm_handle* h, const asm_index* ix, const char* const* seq_names, const char* fastq_path, const char* sam_path,
+                        const char* header, const asm_map_params* p, int max_hits, int strata, int64_t chunk_bytes,
+                        int64_t max_device_bytes, asm_map_file_stats* stats, asm_sam_sort_stats* sort_stats) {
+    return map_file_call("asm_map_file_sorted", h, ix, seq_names, fastq_path, sam_path, header, p, max_hits, strata, chunk_bytes, stats,
+                         &max_device_bytes, sort_stats);
 }
 
 size_t asm_fastq_cut(const char* buf, size_t nbytes, int64_t* records) {

@@ -89,10 +89,12 @@ static int map_pairs_file_chunk(MapPairsFileJob& j, const char* d_raw, const uin
     return ASM_OK;
 }
 
-static int map_pairs_file_run(asm_handle* h, const asm_index* ix, const char* const* seq_names, const char* const path[2],
+/* sort_cap: NULL for asm_map_pairs_file, max_device_bytes for asm_map_pairs_file_sorted */
+static int map_pairs_file_run(asm_handle* h, const char* who, const asm_index* ix, const char* const* seq_names, const char* const path[2],
                               const char* sam_path, const char* header, const asm_map_params* p, const asm_pair_params* pp, size_t chunk,
-                              asm_map_pairs_file_stats* stats) {
-    MapFileSession ss(h, "asm_map_pairs_file", chunk);
+                              asm_map_pairs_file_stats* stats, const int64_t* sort_cap, asm_sam_sort_stats* sort_stats) {
+    MapFileSession ss(h, who, chunk);
+    if (sort_cap) ss.sort.reset(new SamSortHold(h, who, ix->n_seqs, (size_t)*sort_cap));
     StreamInput& in = ss.pipe.in;
     struct Fd { /* file 2 (file 1 is the input side's) */
         int fd = -1;
@@ -112,7 +114,7 @@ static int map_pairs_file_run(asm_handle* h, const asm_index* ix, const char* co
                                                       chunk, ss.grow());
     MapPairsFileJob j = {{ss, ix, p}, pp};
     const int rc = ss.run(
-        rd, std::string("asm_map_pairs_file: reading ") + path[0] + " or " + path[1] + " failed",
+        rd, std::string(who) + ": reading " + path[0] + " or " + path[1] + " failed",
         [](const asm_host::ChunkSlot&, int64_t) { return (int)ASM_OK; },
         [&](int q, size_t bytes, int64_t R, int64_t first_record) {
             return map_file_device_chunks(ss, in.d_raw[q], bytes, 8 * R, R, map_pair_step(h), [&](const uint32_t* d_nl, int64_t r0, int64_t rn) {
@@ -133,7 +135,26 @@ static int map_pairs_file_run(asm_handle* h, const asm_index* ix, const char* co
     if (const int rf = ss.finish(j.st)) return rf;
     j.st.carry_peak = (int64_t)end.carry_peak;
     if (stats) *stats = j.st;
+    if (sort_stats && ss.sort) *sort_stats = ss.sort->st;
     return ASM_OK;
+}
+
+/* asm_map_pairs_file and asm_map_pairs_file_sorted (`who`): the argument checks, then the call */
+static int map_pairs_file_call(const char* who, asm_handle* h, const asm_index* ix, const char* const* seq_names, const char* fastq1_path,
+                               const char* fastq2_path, const char* sam_path, const char* header, const asm_map_params* p,
+                               const asm_pair_params* pp, int64_t chunk_bytes, asm_map_pairs_file_stats* stats, const int64_t* sort_cap,
+                               asm_sam_sort_stats* sort_stats) {
+    if (!p || !pp || !ix || !seq_names || !fastq1_path || !fastq2_path || !sam_path)
+        return fail(h, ASM_EINVAL, std::string(who) + ": bad arguments");
+    size_t chunk = 0;
+    if (const int rc = map_file_chunk_bytes(h, who, chunk_bytes, &chunk)) return rc;
+    if (const int rc = map_file_sort_cap(h, who, sort_cap)) return rc;
+    if (const int rc = map_check_args(h, ix, who, "mate", {0, p, {nullptr, nullptr}, pp, nullptr, 0, 0, 0, {nullptr, 0, nullptr}})) return rc;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (sort_stats) memset(sort_stats, 0, sizeof *sort_stats);
+    HIPCHK(h, hipSetDevice(h->device));
+    const char* const path[2] = {fastq1_path, fastq2_path};
+    return map_pairs_file_run(h, who, ix, seq_names, path, sam_path, header, p, pp, chunk, stats, sort_cap, sort_stats);
 }
 
 } /* extern "C++" */
@@ -141,16 +162,16 @@ static int map_pairs_file_run(asm_handle* h, const asm_index* ix, const char* co
 int asm_map_pairs_file(asm_handle* h, const asm_index* ix, const char* const* seq_names, const char* fastq1_path, const char* fastq2_path,
                        const char* sam_path, const char* header, const asm_map_params* p, const asm_pair_params* pp, int64_t chunk_bytes,
                        asm_map_pairs_file_stats* stats) {
-    if (!p || !pp || !ix || !seq_names || !fastq1_path || !fastq2_path || !sam_path)
-        return fail(h, ASM_EINVAL, "asm_map_pairs_file: bad arguments");
-    size_t chunk = 0;
-    if (const int rc = map_file_chunk_bytes(h, "asm_map_pairs_file", chunk_bytes, &chunk)) return rc;
-    if (const int rc = map_check_args(h, ix, "asm_map_pairs_file", "mate", {0, p, {nullptr, nullptr}, pp, nullptr, 0, 0, 0, {nullptr, 0, nullptr}}))
-        return rc;
-    if (stats) memset(stats, 0, sizeof *stats);
-    HIPCHK(h, hipSetDevice(h->device));
-    const char* const path[2] = {fastq1_path, fastq2_path};
-    return map_pairs_file_run(h, ix, seq_names, path, sam_path, header, p, pp, chunk, stats);
+    return map_pairs_file_call("asm_map_pairs_file", h, ix, seq_names, fastq1_path, fastq2_path, sam_path, header, p, pp, chunk_bytes, stats,
+                               nullptr, nullptr);
+}
+
+int asm_map_pairs_file_sorted(asm_handle* h, const asm_index* ix, const char* const* seq_names, const char* fastq1_path,
+                              const char* fastq2_path, const char* sam_path, const char* header, const asm_map_params* p,
+                              const asm_pair_params* pp, int64_t chunk_bytes, int64_t max_device_bytes, asm_map_pairs_file_stats* stats,
+                              asm_sam_sort_stats* sort_stats) {
+    return map_pairs_file_call("asm_map_pairs_file_sorted", h, ix, seq_names, fastq1_path, fastq2_path, sam_path, header, p, pp,
+                               chunk_bytes, stats, &max_device_bytes, sort_stats);
 }
 
 size_t asm_fastq_cut_n(const char* buf, size_t nbytes, int64_t max_records, int64_t* records) {

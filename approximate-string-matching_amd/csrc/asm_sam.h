@@ -202,6 +202,17 @@ SAM_HD void sam_line_emit(const SamLine& l, char* out, uint32_t lane) {
     sam_format(l, s);
 }
 
+/* The coordinate-sort key of the line sam_format writes for l (asm_map_file_sorted, asm_sam_sort.h): tid << 32 | POS, where tid is
+ * the sequence whose name stands in the RNAME column (n_seqs for '*', which sorts behind every sequence) and POS the number in the
+ * POS column.  own and lent are sam_format's: an unmapped mate that borrows RNAME and POS sorts with its mapped mate.
+ * tests/test_sam_sort_host.py reads the key back from the text of every case. */
+SAM_HD uint64_t sam_sort_key(const SamLine& l, int32_t n_seqs) {
+    const bool pair = l.paired != 0, own = l.mapped != 0, lent = pair && !own && l.mate_mapped;
+    const uint32_t tid = own ? (uint32_t)l.seq_id : lent ? (uint32_t)l.mate_seq_id : (uint32_t)n_seqs;
+    const uint32_t pos_x = own ? l.pos + 1u : lent ? l.mate_pos + 1u : 0u;
+    return (uint64_t)tid << 32 | pos_x;
+}
+
 #if defined(__HIPCC__)
 #include "asm_map.h"
 

@@ -13,6 +13,11 @@
 // --all-hits); --stream together with -2 is a usage error.
 // --ref-stream (any mode) builds the index with asm_index_build_file, which reads and parses the reference on the device, and takes
 // the names and lengths for @SQ and RNAME from the index; without it the reference is parsed here.  The SAM is the same.
+// --sort (any mapping mode) writes the same lines in coordinate order: ascending (index of RNAME among the reference's sequences, POS),
+// '*' behind every sequence, lines with equal keys in the order they have without --sort; the header's first line then reads
+// SO:coordinate.  With --stream / --stream-pairs the library sorts on the device (asm_map_file_sorted, asm_map_pairs_file_sorted;
+// --sort-mem BYTES: the most device memory the held SAM text and its tables may take, default no cap); without them the lines are
+// built as always and sorted here, by the key read from their text.  The two ways give the same file.
 //   asm-map -r ref.fa --bench-ref N [--k 12]
 // maps nothing: it builds the index N times each way, alternately, and prints the seconds of every build.
 // --all-hits N writes up to N loci per read in rank order (asm_map_reads_all, strata S, default e): the primary record as without
@@ -35,8 +40,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <chrono>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "asm_mi355x.h"
@@ -50,7 +57,8 @@ static void usage() {
                     "[--max-occ N] [--all-hits N [--strata S]]\n"
                     "       asm-map -r ref.fa -1 r1.fq -2 r2.fq --stream-pairs [--chunk-bytes N] [-o out.sam] -e N --insert MIN,MAX "
                     "[--rescue E] [--k 12] [--max-occ N]\n"
-                    "       any of them with --ref-stream: the reference is read and parsed by the library\n");
+                    "       any of them with --ref-stream: the reference is read and parsed by the library\n"
+                    "       any of them with --sort: coordinate-sorted output (--stream, --stream-pairs: on the device, [--sort-mem BYTES])\n");
     exit(2);
 }
 
@@ -264,6 +272,43 @@ static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vecto
     return 0;
 }
 
+/* --sort without --stream: the SAM lines text[0, len), as the modes below built them, in coordinate order.  The key is read from a
+ * line's own RNAME and POS columns: (index of RNAME in names, names.size() for '*' or a name that is none of them) << 32 | POS. */
+static bool write_sorted(FILE* file, const char* text, size_t len, const std::vector<std::string>& names) {
+    std::unordered_map<std::string, uint64_t> tid;
+    for (size_t r = 0; r < names.size(); r++) tid.emplace(names[r], (uint64_t)r);
+    struct Line {
+        uint64_t key;
+        const char* at;
+        size_t bytes;
+    };
+    std::vector<Line> lines;
+    for (size_t a = 0; a < len;) {
+        const char* nl = (const char*)memchr(text + a, '\n', len - a);
+        const size_t end = nl ? (size_t)(nl - text) + 1 : len;
+        size_t tab[4], ntab = 0;
+        for (size_t i = a; i < end && ntab < 4; i++)
+            if (text[i] == '\t') tab[ntab++] = i;
+        uint64_t key = (uint64_t)names.size() << 32;
+        if (ntab == 4) {
+            const auto it = tid.find(std::string(text + tab[1] + 1, tab[2] - tab[1] - 1));
+            key = (it == tid.end() ? (uint64_t)names.size() : it->second) << 32 | strtoull(text + tab[2] + 1, nullptr, 10);
+        }
+        lines.push_back({key, text + a, end - a});
+        a = end;
+    }
+    std::stable_sort(lines.begin(), lines.end(), [](const Line& x, const Line& y) { return x.key < y.key; });
+    for (const Line& l : lines)
+        if (fwrite(l.at, 1, l.bytes, file) != l.bytes) return false;
+    return true;
+}
+
+/* the report line of --sort with --stream or --stream-pairs */
+static void report_sorted(const asm_sam_sort_stats& st) {
+    fprintf(stderr, "asm-map: sorted %lld lines, %lld bytes held on the device, %lld slabs, %.3f s\n", (long long)st.lines,
+            (long long)st.bytes_held, (long long)st.slabs, st.seconds_sort);
+}
+
 /* the second report line of --stream and --stream-pairs: what the two calls' stats share */
 template <class Stats>
 static void report_streamed(const Stats& st) {
@@ -351,9 +396,9 @@ int main(int argc, char** argv) {
     int k = 12;
     long chunk = 262144;
     int all_hits = 0, strata = -1; /* all_hits 0: the best hit only */
-    bool stream = false, stream_pairs = false, ref_stream = false;
+    bool stream = false, stream_pairs = false, ref_stream = false, sort = false;
     int bench_ref = 0;
-    long long chunk_bytes = 0;
+    long long chunk_bytes = 0, sort_mem = -1;
     std::string cl = "asm-map";
     for (int a = 1; a < argc; a++) cl += std::string(" ") + argv[a];
     for (int a = 1; a < argc; a++) {
@@ -381,12 +426,17 @@ int main(int argc, char** argv) {
         else if (s == "--ref-stream") ref_stream = true;
         else if (s == "--bench-ref") bench_ref = atoi(val());
         else if (s == "--chunk-bytes") chunk_bytes = atoll(val());
+        else if (s == "--sort") sort = true;
+        else if (s == "--sort-mem") {
+            if ((sort_mem = atoll(val())) < 0) usage();
+        }
         else usage();
     }
     if (ref_path.empty() || (read_path.empty() && bench_ref < 1) || chunk < 1 || all_hits < 0 || (strata >= 0 && !all_hits)) usage();
     const bool paired = !read2_path.empty();
     if (chunk_bytes < 0 || (chunk_bytes > 0 && !stream && !stream_pairs) || (stream && paired)) usage(); /* paired: --stream-pairs */
     if (stream_pairs && (!paired || all_hits || stream)) usage(); /* secondary pairs from files: not there */
+    if (sort_mem >= 0 && (!sort || (!stream && !stream_pairs))) usage(); /* --sort-mem: the device-side sort's */
     if (paired && (pp.min_insert < 0 || pp.max_insert < 0)) usage(); /* paired: --insert needed */
     if (!paired && (pp.min_insert >= 0 || pp.rescue_errors >= 0)) usage();
     if (paired) p.both_strands = 1;
@@ -429,11 +479,26 @@ int main(int argc, char** argv) {
         }
     }
     const bool library_writes = stream || stream_pairs;
-    FILE* out = library_writes ? nullptr : fopen(out_path.c_str(), "w");
+    /* the modes below write their lines to `out`: the file itself, or with --sort a buffer that finish_output sorts into the file */
+    FILE* file = library_writes ? nullptr : fopen(out_path.c_str(), "w");
+    char* held = nullptr;
+    size_t held_bytes = 0;
+    FILE* out = sort && file ? open_memstream(&held, &held_bytes) : file;
     if (!out && !library_writes) {
         fprintf(stderr, "asm-map: cannot write %s\n", out_path.c_str());
         return 1;
     }
+    auto finish_output = [&](int rc) {
+        fclose(out);
+        if (!sort) return rc;
+        if (!rc && !write_sorted(file, held, held_bytes, names)) {
+            fprintf(stderr, "asm-map: writing %s failed\n", out_path.c_str());
+            rc = 1;
+        }
+        free(held);
+        fclose(file);
+        return rc;
+    };
     asm_handle* h = nullptr;
     asm_index* ix = nullptr;
     int rc = asm_create(&h, 0);
@@ -449,7 +514,7 @@ int main(int argc, char** argv) {
             names.push_back(asm_index_seq_name(ix, r));
             off.push_back(off.back() + asm_index_seq_len(ix, r));
         }
-    std::string header = "@HD\tVN:1.6\tSO:unsorted\n";
+    std::string header = sort ? "@HD\tVN:1.6\tSO:coordinate\n" : "@HD\tVN:1.6\tSO:unsorted\n";
     for (size_t r = 0; r < names.size(); r++)
         header += "@SQ\tSN:" + names[r] + "\tLN:" + std::to_string((unsigned long long)(off[r + 1] - off[r])) + "\n";
     header += std::string("@PG\tID:asm-map\tPN:asm-map\tVN:") + asm_version() + "\tCL:" + cl + "\n";
@@ -458,7 +523,11 @@ int main(int argc, char** argv) {
         std::vector<const char*> name_ptr;
         for (const std::string& nm : names) name_ptr.push_back(nm.c_str());
         asm_map_file_stats st;
-        rc = asm_map_file(h, ix, name_ptr.data(), read_path.c_str(), out_path.c_str(), header.c_str(), &p, all_hits, strata, chunk_bytes, &st);
+        asm_sam_sort_stats sst;
+        rc = sort ? asm_map_file_sorted(h, ix, name_ptr.data(), read_path.c_str(), out_path.c_str(), header.c_str(), &p, all_hits, strata,
+                                        chunk_bytes, sort_mem < 0 ? 0 : sort_mem, &st, &sst)
+                  : asm_map_file(h, ix, name_ptr.data(), read_path.c_str(), out_path.c_str(), header.c_str(), &p, all_hits, strata,
+                                 chunk_bytes, &st);
         if (rc) fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
         asm_index_free(h, ix);
         asm_destroy(h);
@@ -466,6 +535,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "asm-map: %lld reads, %lld mapped, %lld longer than %d (unmapped)\n", (long long)st.reads, (long long)st.mapped,
                 (long long)st.too_long, ASM_MAP_MAX_READ);
         report_streamed(st);
+        if (sort) report_sorted(sst);
         return 0;
     }
     if (stream_pairs) { /* the library reads both files, pairs, maps, formats and writes */
@@ -473,8 +543,11 @@ int main(int argc, char** argv) {
         std::vector<const char*> name_ptr;
         for (const std::string& nm : names) name_ptr.push_back(nm.c_str());
         asm_map_pairs_file_stats st;
-        rc = asm_map_pairs_file(h, ix, name_ptr.data(), read_path.c_str(), read2_path.c_str(), out_path.c_str(), header.c_str(), &p, &pp,
-                                chunk_bytes, &st);
+        asm_sam_sort_stats sst;
+        rc = sort ? asm_map_pairs_file_sorted(h, ix, name_ptr.data(), read_path.c_str(), read2_path.c_str(), out_path.c_str(),
+                                              header.c_str(), &p, &pp, chunk_bytes, sort_mem < 0 ? 0 : sort_mem, &st, &sst)
+                  : asm_map_pairs_file(h, ix, name_ptr.data(), read_path.c_str(), read2_path.c_str(), out_path.c_str(), header.c_str(), &p,
+                                       &pp, chunk_bytes, &st);
         if (rc) fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
         asm_index_free(h, ix);
         asm_destroy(h);
@@ -482,9 +555,10 @@ int main(int argc, char** argv) {
         fprintf(stderr, "asm-map: %lld pairs, %lld proper, %lld mates rescued\n", (long long)st.pairs, (long long)st.proper,
                 (long long)st.rescued);
         report_streamed(st);
+        if (sort) report_sorted(sst);
         return 0;
     }
-    fputs(header.c_str(), out);
+    fputs(header.c_str(), file);
     if (paired) {
         FILE* rf2 = fopen(read2_path.c_str(), "r");
         if (!rf2) {
@@ -498,8 +572,7 @@ int main(int argc, char** argv) {
             reads2.fasta = c == '>';
             if (c != EOF) ungetc(c, rf2);
         }
-        rc = write_pairs(out, h, ix, names, reads, reads2, p, pp, chunk, all_hits, strata);
-        fclose(out);
+        rc = finish_output(write_pairs(out, h, ix, names, reads, reads2, p, pp, chunk, all_hits, strata));
         fclose(rf);
         fclose(rf2);
         asm_index_free(h, ix);
@@ -582,10 +655,10 @@ int main(int argc, char** argv) {
             }
         }
     }
-    fclose(out);
+    rc = finish_output(0);
     fclose(rf);
     asm_index_free(h, ix);
     asm_destroy(h);
     fprintf(stderr, "asm-map: %lld reads, %lld mapped, %lld longer than %d (unmapped)\n", n_total, n_mapped, n_long, ASM_MAP_MAX_READ);
-    return 0;
+    return rc;
 }

@@ -491,6 +491,33 @@ int asm_map_pairs_file(asm_handle* h, const asm_index* ix, const char* const* se
                        const asm_pair_params* pp, int64_t chunk_bytes, asm_map_pairs_file_stats* stats /* may be NULL */);
 size_t asm_fastq_cut_n(const char* buf, size_t nbytes, int64_t max_records, int64_t* records);
 
+/* asm_map_file_sorted, asm_map_pairs_file_sorted: the two file calls with coordinate-sorted output (docs/design/mapper.md, "Sorted
+ *                  output"); synchronous.  Input contract, answers, error reports and the first stats struct are those of the
+ *                  unsorted call, under the sorted call's name.  The file holds `header` (as it is; the library does not edit it)
+ *                  and then the lines the unsorted call writes, byte for byte, in ascending order of (tid, POS) as the line shows
+ *                  them: tid = the index of its RNAME in seq_names, n_seqs for '*' (behind everything), POS its POS column.  An
+ *                  unmapped mate that borrows RNAME and POS sorts with its mate; secondary lines sort each by its own key.  Lines
+ *                  with equal keys keep the unsorted call's order (file order, then rank, then mate 1 before mate 2).  The output
+ *                  does not depend on chunk_bytes or ASM_MAP_CHUNK.  The whole SAM text stays on the device until the last chunk is
+ *                  formatted and is then sorted there and written in slabs of at most max(chunk_bytes, the longest line) bytes;
+ *                  max_device_bytes caps the held text plus the line tables (0: no cap but the device's memory; negative:
+ *                  ASM_EINVAL).  When the cap or the allocator says no: ASM_ENOMEM, asm_last_error says that sorted output keeps the
+ *                  whole SAM text on the device and names the bytes reached; what sam_path holds is then unspecified and the handle
+ *                  stays usable.  2^32 lines or more: ASM_EUNSUPPORTED.  An input error fails the call before any sorted byte is
+ *                  written.  An empty input gives the header alone. */
+typedef struct asm_sam_sort_stats {
+    int64_t lines, bytes_held, slabs;  /* lines sorted; SAM bytes kept on the device; output slabs written */
+    double seconds_sort;               /* from the last chunk formatted to the last slab handed to the writer */
+} asm_sam_sort_stats;
+int asm_map_file_sorted(asm_handle* h, const asm_index* ix, const char* const* seq_names /* [n_seqs] */, const char* fastq_path,
+                        const char* sam_path, const char* header, const asm_map_params* p, int max_hits, int strata, int64_t chunk_bytes,
+                        int64_t max_device_bytes, asm_map_file_stats* stats /* may be NULL */,
+                        asm_sam_sort_stats* sort_stats /* may be NULL */);
+int asm_map_pairs_file_sorted(asm_handle* h, const asm_index* ix, const char* const* seq_names /* [n_seqs] */, const char* fastq1_path,
+                              const char* fastq2_path, const char* sam_path, const char* header, const asm_map_params* p,
+                              const asm_pair_params* pp, int64_t chunk_bytes, int64_t max_device_bytes,
+                              asm_map_pairs_file_stats* stats /* may be NULL */, asm_sam_sort_stats* sort_stats /* may be NULL */);
+
 /* asm_index_build_file: asm_index_build from a FASTA file (docs/design/mapper.md, "Reference: FASTA in, index out"); synchronous.  The
  *                  file is read in chunks of about chunk_bytes (0: 16 MiB) that may end anywhere except inside a header line, so a
  *                  sequence line may have any length; a chunk is parsed on the device while the next one is read and copied in.

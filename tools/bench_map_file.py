@@ -1,6 +1,6 @@
 """File-to-file read mapping timings (development tool):
 PYTHONPATH=. python tools/bench_map_file.py --dir DIR [--ref-len 5e6] [--reads 1e6] [--len 100] [--errors 2] [--all-hits N]
-[--reps 3] [--chunk-bytes N] [--profile] [--paired [--insert 200,500] [--rescue E]]
+[--reps 3] [--chunk-bytes N] [--profile] [--paired [--insert 200,500] [--rescue E]] [--sort] [--exe PATH]
 Writes the workload of tools/bench_map.py as files into DIR (seeded: a reference of --ref-len bases as ref.fa and --reads reads of
 --len bases with qualities as reads.fq), then runs `asm-map` and `asm-map --stream` on them alternately, --reps times each, in this
 one call.  For every run: the wall clock of the whole process (reference parsing and index build included, the same in both) and,
@@ -10,7 +10,13 @@ before the first run, so every run finds them in the page cache; the SAM files g
 --paired writes the paired workload of tools/bench_map.py --paired instead (--reads / 2 pairs, as r1.fq and r2.fq) and compares
 `asm-map -1 -2` with `asm-map -1 -2 --stream-pairs`; the streamed runs also report the reader's carry_peak (from a library call of
 its own on the same files, Engine.map_pairs_file).
---profile runs `asm-map --stream` (or --stream-pairs) once under `rocprofv3 --kernel-trace --stats` (a run of its own) and prints the kernel totals."""
+--profile runs `asm-map --stream` (or --stream-pairs) once under `rocprofv3 --kernel-trace --stats` (a run of its own) and prints the kernel totals.
+--sort times coordinate-sorted output instead (docs/design/mapper.md, "Sorted output"): in one process and on one index, the
+unsorted and the sorted library call alternately, --reps times each after one warm-up of each, with the sort's own seconds and the
+slabs; the sorted file is checked once against Python's stable sort of the unsorted one; and a device-to-device hipMemcpyAsync of as
+many bytes as the gather kernel moves is timed with events, the yardstick for that kernel.  With --profile the traced run is
+`asm-map --stream --sort`, whose kernel totals hold the sort's split (radix sort, scan, sam_line_gather_kernel).
+--exe PATH runs another build's asm-map in the tool legs (for a comparison of two builds on the same files)."""
 import argparse
 import csv
 import glob
@@ -81,6 +87,64 @@ def body_of(path):
         return [ln for ln in fh.read().split(b"\n") if not ln.startswith(b"@PG")]
 
 
+def sort_leg(a, fqs, result):
+    """the unsorted and the sorted library call, alternately; -> result"""
+    import torch
+
+    import approximate_string_matching_amd as m
+
+    eng = m.Engine(0)
+    ref, _ = make_inputs(int(a.ref_len), 1, a.len, a.errors, seed=1234)
+    ix = eng.build_index([ref.tobytes().decode()], k=12)
+    sams = [os.path.join(a.dir, "lib_unsorted.sam"), os.path.join(a.dir, "lib_sorted.sam")]
+
+    def call(sort):
+        kw = dict(chunk_bytes=a.chunk_bytes, sort=sort)
+        if a.paired:
+            lo, hi = (int(v) for v in a.insert.split(","))
+            return eng.map_pairs_file(ix, ["ref"], fqs[0], fqs[1], sams[sort], a.errors, lo, hi, rescue_errors=a.rescue, **kw)
+        return eng.map_file(ix, ["ref"], fqs[0], sams[sort], a.errors, max_hits=a.all_hits, **kw)
+
+    call(False), call(True)  # warm-up: code objects, the pool, pinned buffers
+    with open(sams[0], "rb") as fh:
+        lines = fh.read().split(b"\n")[:-1]
+
+    def key(ln):
+        c = ln.split(b"\t", 4)
+        return (1 if c[2] == b"*" else 0, int(c[3]))
+
+    with open(sams[1], "rb") as fh:
+        result["sorted_is_python_sort"] = fh.read() == b"".join(ln + b"\n" for ln in sorted(lines, key=key))
+    print("sorted file equals Python's stable sort of the unsorted file:", result["sorted_is_python_sort"], flush=True)
+    result["pairs"] = []
+    for rep in range(a.reps):
+        st0, st1 = call(False), call(True)
+        pair = {"unsorted_s": round(st0["seconds"], 4), "sorted_s": round(st1["seconds"], 4), "ratio": round(st1["seconds"] / st0["seconds"], 3),
+                "sort_s": round(st1["sort"]["seconds_sort"], 4), "slabs": st1["sort"]["slabs"], "lines": st1["sort"]["lines"],
+                "bytes_held": st1["sort"]["bytes_held"], "write_s": [round(st0["seconds_write"], 4), round(st1["seconds_write"], 4)]}
+        result["pairs"].append(pair)
+        print("pair %d: unsorted call %.4f s, sorted call %.4f s (x%.3f), of it sort to last slab %.4f s; %d lines, %d bytes held, %d slabs" %
+              (rep, pair["unsorted_s"], pair["sorted_s"], pair["ratio"], pair["sort_s"], pair["lines"], pair["bytes_held"], pair["slabs"]), flush=True)
+    # the yardstick of sam_line_gather_kernel: the same number of bytes, device to device, as one hipMemcpyAsync
+    n = int(result["pairs"][-1]["bytes_held"])
+    src, dst = torch.zeros(n, dtype=torch.uint8, device="cuda"), torch.empty(n, dtype=torch.uint8, device="cuda")
+    times = []
+    for _ in range(12):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        dst.copy_(src)
+        t1.record()
+        t1.synchronize()
+        times.append(t0.elapsed_time(t1) * 1e-3)
+    best = sorted(times[2:])
+    result["d2d_memcpy"] = {"bytes": n, "median_s": best[len(best) // 2], "min_s": best[0], "gb_per_s": round(n / best[len(best) // 2] / 1e9, 1)}
+    print("device-to-device copy of %d bytes: median %.6f s (%.1f GB/s)" % (n, result["d2d_memcpy"]["median_s"], result["d2d_memcpy"]["gb_per_s"]),
+          flush=True)
+    ix.free()
+    eng.close()
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dir", required=True, help="directory for the input and output files")
@@ -95,6 +159,8 @@ def main():
     ap.add_argument("--paired", action="store_true", help="asm-map -1 -2 against --stream-pairs on --reads / 2 simulated pairs")
     ap.add_argument("--insert", default="200,500", help="with --paired: MIN,MAX of the projected span")
     ap.add_argument("--rescue", type=int, default=-1, help="with --paired: mate rescue's error bound (-1: off)")
+    ap.add_argument("--sort", action="store_true", help="the sorted library call against the unsorted one; with --profile: asm-map --stream --sort")
+    ap.add_argument("--exe", default=EXE, help="the asm-map to run in the tool legs")
     a = ap.parse_args()
     os.makedirs(a.dir, exist_ok=True)
     fa, fqs = write_files(a, a.errors)
@@ -104,11 +170,13 @@ def main():
                 pass
     if a.paired:
         flags = ["-e", str(a.errors), "--insert", a.insert] + (["--rescue", str(a.rescue)] if a.rescue >= 0 else [])
-        base = [EXE, "-r", fa, "-1", fqs[0], "-2", fqs[1]] + flags
+        base = [a.exe, "-r", fa, "-1", fqs[0], "-2", fqs[1]] + flags
     else:
         flags = ["-e", str(a.errors), "--both-strands"] + (["--all-hits", str(a.all_hits)] if a.all_hits else [])
-        base = [EXE, "-r", fa, "-q", fqs[0]] + flags
+        base = [a.exe, "-r", fa, "-q", fqs[0]] + flags
     stream = ["--stream-pairs" if a.paired else "--stream"] + (["--chunk-bytes", str(a.chunk_bytes)] if a.chunk_bytes else [])
+    if a.sort and a.profile:
+        stream.append("--sort")
     sam0, sam1 = os.path.join(a.dir, "plain.sam"), os.path.join(a.dir, "stream.sam")
     if a.profile:
         out = os.path.join(a.dir, "profile")
@@ -119,13 +187,16 @@ def main():
             with open(path) as fh:
                 rows = list(csv.DictReader(fh))
             print("kernel totals (", path, ")")
-            for r in rows[:40]:
+            for r in (rows if a.sort else rows[:40]):  # --sort: the sort's kernels are short and stand far down the list
                 print("  %-60s calls %6s total %10.3f ms  avg %9.1f us" % (r["Name"][:60], r["Calls"], float(r["TotalDurationNs"]) / 1e6,
                                                                            float(r["AverageNs"]) / 1e3))
         return
     result = {"reads": int(a.reads), "len": a.len, "ref_len": int(a.ref_len), "errors": a.errors, "all_hits": a.all_hits,
               "paired": a.paired, "insert": a.insert if a.paired else None, "rescue": a.rescue if a.paired else None,
               "fastq_bytes": sum(os.path.getsize(fq) for fq in fqs), "page_cache": True, "pairs": []}
+    if a.sort:
+        print(json.dumps(sort_leg(a, fqs, result)))
+        return
     for rep in range(a.reps):
         w0, err0 = run(base + ["-o", sam0])
         w1, err1 = run(base + ["-o", sam1] + stream)
