@@ -135,6 +135,7 @@ class PairParams(ctypes.Structure):
 MAP_HIT_DTYPE = np.dtype([("seq_id", np.int32), ("pos", np.uint32), ("end", np.uint32), ("dist", np.int16), ("strand", np.uint8),
                           ("flags", np.uint8), ("greedy_cost", np.int32)])
 MAP_MAPPED, MAP_TOO_SHORT, MAP_SEED_CAPPED, MAP_CIGAR_TRUNCATED = 1, 2, 4, 8
+MAPQ_REFERENCE, MAPQ_GAP = 0, 1  # asm_map_set_mapq_model
 MAP_SECONDARY, MAP_HITS_TRUNCATED, MAP_MAX_HITS = 16, 32, 256
 MAP_PROPER_PAIR, MAP_RESCUED, MAP_MAX_INSERT = 64, 128, 8192
 MAP_MIN_K, MAP_MAX_K, MAP_MAX_READ, MAP_MAX_ERRORS = 8, 14, 511, 15
@@ -277,6 +278,9 @@ def load_library() -> ctypes.CDLL:
         "asm_map_pairs": (i32, [vp, vp, i64, vp, vp, vp, vp, c.POINTER(MapParams), c.POINTER(PairParams), vp, vp, vp, vp, i32, vp]),
         "asm_map_pairs_all": (i32, [vp, vp, i64, vp, vp, vp, vp, c.POINTER(MapParams), c.POINTER(PairParams), i32, i32, vp, vp, vp, vp,
                                     vp, i32, vp]),
+        "asm_map_set_mapq_model": (i32, [vp, i32]),
+        "asm_map_get_mapq_model": (i32, [vp]),
+        "asm_map_last_mapq": (i32, [vp, vp, i64]),
         "asm_map_file": (i32, [vp, vp, c.POINTER(c.c_char_p), c.c_char_p, c.c_char_p, c.c_char_p, c.POINTER(MapParams), i32, i32, i64,
                                c.POINTER(MapFileStats)]),
         "asm_fastq_cut": (c.c_size_t, [vp, c.c_size_t, c.POINTER(i64)]),
@@ -607,17 +611,34 @@ class Engine:
                       [self.lib.asm_index_seq_name(ptr, r).decode("latin-1") for r in range(n)])
         return index, {name: getattr(st, name) for name, _ in IndexFileStats._fields_}
 
-    def _map_chunks(self, parts, chunk: Optional[int], call) -> None:
+    def set_mapq_model(self, model) -> None:
+        """asm_map_set_mapq_model: MAPQ_REFERENCE / "reference" (the default, min(254, 60 + greedy_cost)) or MAPQ_GAP / "gap" (the
+        repeat- and pair-aware model of docs/design/mapper.md, "Mapping quality") for every later map_* call of this engine."""
+        self._chk(self.lib.asm_map_set_mapq_model(self.h, {"reference": MAPQ_REFERENCE, "gap": MAPQ_GAP}.get(model, model)))
+
+    def mapq_model(self) -> int:
+        return int(self.lib.asm_map_get_mapq_model(self.h))
+
+    def last_mapq(self, count: int) -> np.ndarray:
+        """asm_map_last_mapq: uint8[count], the MAPQ of every record slot of the last in-memory library call, in its `out` layout"""
+        out = np.zeros(int(count), np.uint8)
+        self._chk(self.lib.asm_map_last_mapq(self.h, out.ctypes.data if count else None, int(count)))
+        return out
+
+    def _map_chunks(self, parts, chunk: Optional[int], call, slots: int = 1) -> np.ndarray:
         """The chunk loop of the map_* methods.  parts: one list of byte strings per mate; call(lo, hi, seqs) maps reads [lo, hi)
         and returns the library's code; seqs: per list the address of the packed bytes (None when empty) and of their uint32
-        offsets."""
+        offsets.  -> uint8 (n, slots): the MAPQ of every record slot by the engine's model (asm_map_last_mapq after every call)."""
         n = len(parts[0])
         step = chunk if chunk else max(n, 1)
+        mq = np.zeros((n, slots), np.uint8)
         for lo in range(0, n, step):
             hi = min(n, lo + step)
             packed = [(buf, off.astype(np.uint32)) for buf, off in (pack_sequences(p[lo:hi]) for p in parts)]
             seqs = [x for buf, ro in packed for x in (buf.ctypes.data if buf.size else None, ro.ctypes.data)]
             self._chk(call(lo, hi, seqs))
+            mq[lo:hi] = self.last_mapq((hi - lo) * slots).reshape(hi - lo, slots)
+        return mq
 
     @staticmethod
     def _mates(reads1, reads2):
@@ -638,6 +659,8 @@ class Engine:
         out["mapped"] = (hits["flags"] & MAP_MAPPED) != 0
         if rescued:
             out["rescued"] = (hits["flags"] & MAP_RESCUED) != 0
+        # kept for compatibility: always the reference rule, 255 when unmapped.  The value to use is `mapping_quality`, which the
+        # map_* methods add: the library's MAPQ by the engine's model (set_mapq_model), 0 when unmapped, as the SAM files carry it.
         out["mapq"] = np.where(out["mapped"], np.minimum(254, 60 + hits["greedy_cost"].astype(np.int64)), 255).astype(np.int32)
         return out
 
@@ -652,16 +675,19 @@ class Engine:
                   cigar_cap: int = 64, chunk: Optional[int] = None):
         """asm_map_reads: the best hit of every read (str / bytes).  -> dict of numpy arrays, one entry per read: seq_id, pos, end,
         dist, strand, flags, greedy_cost, mapped (bool), mapq (min(254, 60 + greedy_cost), 255 when unmapped), and `cigar`, a
-        list of CIGAR strings ('' when unmapped).  chunk: reads per library call (None: all in one)."""
+        list of CIGAR strings ('' when unmapped), and mapping_quality.  mapping_quality (uint8) is the MAPQ to use: the library's
+        value by the engine's model (set_mapq_model), 0 when unmapped, the number the SAM files carry in column 5; every map_*
+        sibling has it in the shape of its records.  The older `mapq` is kept for compatibility and is always the reference rule.  chunk: reads per library call (None: all in one)."""
         parts = [_as_bytes(r) for r in reads]
         n = len(parts)
         p = MapParams(int(max_errors), 1 if both_strands else 0, int(max_occ), int(greedy_k))
         hits = np.zeros(n, MAP_HIT_DTYPE)
         ops = np.zeros((n, max(cigar_cap, 1)), np.uint16)
         nops = np.zeros(n, np.uint8)
-        self._map_chunks([parts], chunk, lambda lo, hi, seqs: self.lib.asm_map_reads(
+        mq = self._map_chunks([parts], chunk, lambda lo, hi, seqs: self.lib.asm_map_reads(
             self.h, index.ptr, hi - lo, *seqs, ctypes.byref(p), hits[lo:hi].ctypes.data, *self._cigar_args(ops, nops, cigar_cap, lo, hi)))
         out = self._hit_fields(hits)
+        out["mapping_quality"] = mq.reshape(n)
         out["cigar"] = self._cigars(ops, nops, cigar_cap)
         out["cigar_nops"] = nops
         return out
@@ -681,16 +707,18 @@ class Engine:
         hits = np.zeros((n, max_hits), MAP_HIT_DTYPE)
         ops = np.zeros((n, max_hits, max(cigar_cap, 1)), np.uint16)
         nops = np.zeros((n, max_hits), np.uint8)
-        self._map_chunks([parts], chunk, lambda lo, hi, seqs: self.lib.asm_map_reads_all(
+        mq = self._map_chunks([parts], chunk, lambda lo, hi, seqs: self.lib.asm_map_reads_all(
             self.h, index.ptr, hi - lo, *seqs, ctypes.byref(p), strata, int(max_hits), n_hits[lo:hi].ctypes.data,
-            hits[lo:hi].ctypes.data, *self._cigar_args(ops, nops, cigar_cap, lo, hi)))
+            hits[lo:hi].ctypes.data, *self._cigar_args(ops, nops, cigar_cap, lo, hi)), slots=int(max_hits))
         n_rep = np.minimum(n_hits, max_hits).astype(np.int64)
         read = np.repeat(np.arange(n, dtype=np.int64), n_rep)
         rank = (np.arange(read.size, dtype=np.int64) - np.repeat(np.cumsum(n_rep) - n_rep, n_rep)) if read.size else read.copy()
         flat = hits[read, rank]
         out = {"n_hits": n_hits, "n_reported": n_rep, "read_flags": hits["flags"][:, 0].copy(), "read": read, "rank": rank}
         out.update({name: flat[name].copy() for name in MAP_HIT_DTYPE.names})
+        # kept for compatibility: always the reference rule; `mapping_quality` below is the value to use
         out["mapq"] = np.minimum(254, 60 + flat["greedy_cost"].astype(np.int64)).astype(np.int32)
+        out["mapping_quality"] = mq[read, rank]
         out["cigar"] = self._cigars(ops[read, rank], nops[read, rank], cigar_cap)
         out["cigar_nops"] = nops[read, rank]
         return out
@@ -765,10 +793,11 @@ class Engine:
         n_conc = np.zeros(n, np.uint32)
         ops = np.zeros((n, 2, max(cigar_cap, 1)), np.uint16)
         nops = np.zeros((n, 2), np.uint8)
-        self._map_chunks(mates, chunk, lambda lo, hi, seqs: self.lib.asm_map_pairs(
+        mq = self._map_chunks(mates, chunk, lambda lo, hi, seqs: self.lib.asm_map_pairs(
             self.h, index.ptr, hi - lo, *seqs, ctypes.byref(p), ctypes.byref(pp), hits[lo:hi].ctypes.data, tlen[lo:hi].ctypes.data,
-            n_conc[lo:hi].ctypes.data, *self._cigar_args(ops, nops, cigar_cap, lo, hi)))
+            n_conc[lo:hi].ctypes.data, *self._cigar_args(ops, nops, cigar_cap, lo, hi)), slots=2)
         out = self._hit_fields(hits, rescued=True)
+        out["mapping_quality"] = mq
         out["proper"] = (hits["flags"][:, 0] & MAP_PROPER_PAIR) != 0
         out["tlen"], out["n_concordant"] = tlen, n_conc
         flat = self._cigars(ops, nops, cigar_cap)
@@ -796,10 +825,12 @@ class Engine:
         n_conc = np.zeros(n, np.uint32)
         ops = np.zeros((n, P, 2, max(cigar_cap, 1)), np.uint16)
         nops = np.zeros((n, P, 2), np.uint8)
-        self._map_chunks(mates, chunk, lambda lo, hi, seqs: self.lib.asm_map_pairs_all(
+        mq = self._map_chunks(mates, chunk, lambda lo, hi, seqs: self.lib.asm_map_pairs_all(
             self.h, index.ptr, hi - lo, *seqs, ctypes.byref(p), ctypes.byref(pp), strata, P, n_pairs[lo:hi].ctypes.data,
-            hits[lo:hi].ctypes.data, tlen[lo:hi].ctypes.data, n_conc[lo:hi].ctypes.data, *self._cigar_args(ops, nops, cigar_cap, lo, hi)))
+            hits[lo:hi].ctypes.data, tlen[lo:hi].ctypes.data, n_conc[lo:hi].ctypes.data, *self._cigar_args(ops, nops, cigar_cap, lo, hi)),
+            slots=2 * P)
         out = self._hit_fields(hits, rescued=True)
+        out["mapping_quality"] = mq.reshape(n, P, 2)
         out["proper"] = (hits["flags"][:, :, 0] & MAP_PROPER_PAIR) != 0
         out["tlen"], out["n_pairs"], out["n_concordant"] = tlen, n_pairs, n_conc
         out["n_reported"] = np.minimum(n_pairs, P).astype(np.int64)

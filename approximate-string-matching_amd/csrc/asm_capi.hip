@@ -121,6 +121,9 @@ struct asm_handle {
     int64_t map_cand_cap = (int64_t)1 << 24; /* asm_map_reads: verification candidates per round (ASM_MAP_CAND_CAP) */
     int64_t map_chunk = (int64_t)1 << 18;    /* asm_map_reads: reads per device chunk (ASM_MAP_CHUNK) */
     int64_t map_run_cap = (int64_t)1 << 24;  /* asm_map_reads_all: run records reserved per seeding round (ASM_MAP_RUN_CAP) */
+    int mapq_model = 0;                   /* asm_map_set_mapq_model: ASM_MAPQ_REFERENCE or ASM_MAPQ_GAP */
+    std::vector<uint8_t> last_mapq;       /* asm_map_last_mapq: one byte per record slot of the last in-memory mapping call */
+    bool last_mapq_valid = false;
     std::vector<hipEvent_t> prof_ev;      /* asm_profile_enable: 8 events per recorded asm_run_benchmark_async call */
     std::vector<unsigned> prof_mask;      /* which of a call's four kernels were launched */
     int prof_cap = 0;

@@ -24,6 +24,9 @@
 // Secondary pairs (asm_map_pairs_all): the front of asm_map_pairs unchanged, then map_pair_count_kernel counts each pair's eligible
 //          concordant pairs, a scan lays out their items, map_pair_emit_kernel lists ranks >= 1 in pair order, and the items' finish
 //          and Greedy run as for all hits.
+// Mapping quality (ASM_MAPQ_GAP only): map_mapq_kernel folds each read's sorted run records into (d1, n1, d2), its MAPQ bytes and,
+//          for the best-hit calls, its best key (they take the run path then, not the atomicMin); map_pair_mapq_kernel folds each
+//          pair's concordant combinations and writes both records' bytes; map_pair_item_mapq_kernel does the secondary pairs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -322,6 +325,80 @@ __global__ __launch_bounds__(256) void map_pair_emit_kernel(MapPairAllArgs a) {
             a.iread[q + 1] = (uint32_t)B, a.ikey[q + 1] = kB, a.idirs[q + 1] = dw + mA + 1u;
             q += 2, dw += mA + mB + 2u;
         });
+    }
+}
+
+/* ---- mapping quality under MAP_MAPQ_GAP (the rules: asm_map_core.h) ---- */
+struct MapMapqArgs {
+    const unsigned long long* rkey; /* the run records, sorted */
+    const uint32_t* rval;
+    unsigned long long nr;
+    long n;                          /* reads */
+    int e;
+    const unsigned long long* seq_off;
+    uint32_t n_seqs;
+    const uint32_t* flags;           /* per read */
+    uint8_t *rq, *rd1;               /* per read: Q_read and d1 (e + 1: no locus) */
+    unsigned long long* best;        /* per read: its best hit's key (the best-hit calls); NULL: not wanted */
+    const uint32_t* ibase;           /* all hits: first item of every read (n + 1); NULL: no items */
+    const unsigned long long* ikey;  /* all hits: per item, its locus key */
+    uint8_t* mapq;                   /* all hits: per item */
+};
+
+/* thread per read: its run records (contiguous after the sort) folded into (d1, n1, d2); Q_read, d1 and, where wanted, the best
+ * hit's key and the MAPQ of the read's items */
+__global__ __launch_bounds__(256) void map_mapq_kernel(MapMapqArgs a) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (long)gridDim.x * blockDim.x) {
+        const MapRange g = map_read_runs(a.rkey, a.nr, i);
+        const MapMapqRead x = map_mapq_read(a.rkey, a.rval, g.b, g.e, a.seq_off, a.n_seqs, a.e);
+        const uint32_t q = map_mapq_read_q(x, a.flags[i]);
+        a.rq[i] = (uint8_t)q, a.rd1[i] = (uint8_t)x.d1;
+        if (a.best) a.best[i] = x.best;
+        if (a.ibase)
+            for (uint32_t it = a.ibase[i]; it < a.ibase[i + 1]; it++) a.mapq[it] = (uint8_t)map_mapq_locus(a.ikey[it], x.d1, q);
+    }
+}
+
+struct MapPairMapqArgs {
+    MapPairArgs pa;          /* the pairing's loci lists, item keys and final states */
+    int e;
+    const uint32_t* flags;   /* per read */
+    const uint8_t *rq, *rd1; /* per read (map_mapq_kernel) */
+    uint8_t* mapq;           /* per read: the MAPQ of its record in the pair's answer */
+    uint8_t *pq, *ps1;       /* per pair: Q_pair and S1 (CONCORDANT pairs; else 0), for the secondary pairs */
+    /* map_pair_item_mapq_kernel: the secondary items, two per pair (mate 1, mate 2) */
+    long ni;
+    const uint32_t* iread;
+    const unsigned long long* ikey;
+    uint8_t* imapq;
+};
+
+/* thread per pair: its concordant combinations folded into (S1, N1, S2), then both records' MAPQ by the pair's state */
+__global__ __launch_bounds__(256) void map_pair_mapq_kernel(MapPairMapqArgs a) {
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < a.pa.np; p += (long)gridDim.x * blockDim.x) {
+        const long A = p, B = a.pa.np + p;
+        const uint32_t st = a.pa.state[p];
+        const unsigned long long kA = a.pa.ikey[A], kB = a.pa.ikey[B];
+        uint32_t q_pair = 0u, qA, qB;
+        int S1 = 0;
+        if (st == MAP_PAIR_CONCORDANT) {
+            const MapMapqPair x = map_mapq_pair(a.pa, p);
+            q_pair = map_mapq_pair_q(x, MAP_KEY_D(kA), MAP_KEY_D(kB), a.e, a.flags[A] | a.flags[B]);
+            S1 = x.S1;
+        }
+        map_mapq_pair_records(st, kA, kB, a.rq[A], a.rq[B], (int)a.rd1[A], (int)a.rd1[B], q_pair, qA, qB);
+        a.mapq[A] = (uint8_t)qA, a.mapq[B] = (uint8_t)qB;
+        a.pq[p] = (uint8_t)q_pair, a.ps1[p] = (uint8_t)S1;
+    }
+}
+
+/* thread per secondary pair (items 2 t and 2 t + 1: its mates 1 and 2) */
+__global__ __launch_bounds__(256) void map_pair_item_mapq_kernel(MapPairMapqArgs a) {
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; 2 * t < a.ni; t += (long)gridDim.x * blockDim.x) {
+        const long A = (long)a.iread[2 * t], B = (long)a.iread[2 * t + 1], p = A;
+        uint32_t qA, qB;
+        map_mapq_secondary(a.ikey[2 * t], a.ikey[2 * t + 1], (int)a.ps1[p], a.rq[A], a.rq[B], (int)a.rd1[A], (int)a.rd1[B], a.pq[p], qA, qB);
+        a.imapq[2 * t] = (uint8_t)qA, a.imapq[2 * t + 1] = (uint8_t)qB;
     }
 }
 

@@ -447,6 +447,93 @@ MAP_HD void map_pair_ranked(const MapPairArgs& a, long p, uint32_t mask, uint32_
     }
 }
 
+/* ---- mapping quality (docs/design/mapper.md, "Mapping quality") ----
+ * MAP_MAPQ_REFERENCE: min(254, 60 + greedy_cost) of a mapped record; MAP_MAPQ_GAP: T(n, g) from what the exact search proves, the
+ * number n of loci (pairs) that tie for the best and a lower bound g >= 1 on the edit gap to the nearest alternative.  An unmapped
+ * record has 0 under both. */
+#define MAP_MAPQ_REFERENCE 0
+#define MAP_MAPQ_GAP 1
+#define MAP_MAPQ_CAPPED 20u /* the most a read with skipped buckets, or a rescued mate, may claim: a gap of 1 */
+MAP_HD int map_mapq_reference(bool mapped, int greedy_cost) { return !mapped ? 0 : greedy_cost + 60 < 254 ? greedy_cost + 60 : 254; }
+MAP_HD uint32_t map_mapq_table(uint32_t n, int g) {
+    if (n == 0u) return 0u;
+    if (n == 1u) return g >= 3 ? 60u : g >= 1 ? 20u * (uint32_t)g : 0u;
+    return n == 2u ? 3u : n <= 4u ? 1u : 0u;
+}
+/* One read's loci folded: d1 = the smallest d (e + 1: no locus), n1 = the loci at d1, d2 = the smallest d > d1 (e + 1: none, the
+ * search proves that nothing closer exists), best = the smallest locus key (MAP_NO_KEY: no locus), the best hit. */
+struct MapMapqRead {
+    int d1, d2;
+    uint32_t n1;
+    unsigned long long best;
+};
+MAP_HD MapMapqRead map_mapq_read(const unsigned long long* __restrict__ rkey, const uint32_t* __restrict__ rval, unsigned long long b,
+                                 unsigned long long e_, const unsigned long long* __restrict__ seq_off, uint32_t n_seqs, int e) {
+    MapMapqRead o = {e + 1, e + 1, 0u, MAP_NO_KEY};
+    map_walk_loci(rkey, rval, b, e_, seq_off, n_seqs, [&](uint32_t s, uint32_t r, int d, uint32_t j) {
+        const unsigned long long key = map_locus_key(seq_off, s, r, d, j);
+        o.best = key < o.best ? key : o.best;
+        if (d < o.d1) o.d2 = o.d1, o.d1 = d, o.n1 = 1u;
+        else if (d == o.d1) o.n1++;
+        else if (d < o.d2) o.d2 = d;
+    });
+    return o;
+}
+/* Q_read of a folded read with the per-read flags fl; 0 without a locus */
+MAP_HD uint32_t map_mapq_read_q(const MapMapqRead& x, uint32_t fl) {
+    const uint32_t q = map_mapq_table(x.n1, x.d2 - x.d1);
+    return (fl & MAP_F_SEED_CAPPED) && q > MAP_MAPQ_CAPPED ? MAP_MAPQ_CAPPED : q;
+}
+/* Q_locus: the single-end value of a record at the locus `key` of a read with (d1, Q_read) */
+MAP_HD uint32_t map_mapq_locus(unsigned long long key, int d1, uint32_t q_read) {
+    return key != MAP_NO_KEY && MAP_KEY_D(key) == d1 ? q_read : 0u;
+}
+/* One pair's concordant combinations folded: S1 = the best d sum, N1 = the combinations with it (saturating, n_concordant; 0: none),
+ * S2 = the smallest d sum > S1 (-1: none) */
+struct MapMapqPair {
+    int S1, S2;
+    uint32_t N1;
+};
+MAP_HD MapMapqPair map_mapq_pair(const MapPairArgs& a, long p) {
+    MapMapqPair o = {-1, -1, 0u};
+    map_pair_walk_both(a, p, [&](unsigned long long kA, unsigned long long kB) {
+        const int s = MAP_KEY_D(kA) + MAP_KEY_D(kB);
+        if (o.N1 == 0u || s < o.S1) o.S2 = o.S1, o.S1 = s, o.N1 = 1u;
+        else if (s == o.S1) o.N1 += o.N1 != 0xffffffffu;
+        else if (o.S2 < 0 || s < o.S2) o.S2 = s;
+        return true;
+    });
+    return o;
+}
+/* Q_pair of a folded pair whose best pair's mates lie at d_A and d_B; fl: both mates' per-read flags or-ed.  The second term of
+ * g bounds every pair that uses a locus the search did not see: it lies beyond e, the mate it replaces within max(d_A, d_B). */
+MAP_HD uint32_t map_mapq_pair_q(const MapMapqPair& x, int dA, int dB, int e, uint32_t fl) {
+    int g = e + 1 - (dA > dB ? dA : dB);
+    if (x.S2 >= 0 && x.S2 - x.S1 < g) g = x.S2 - x.S1;
+    const uint32_t q = map_mapq_table(x.N1, g);
+    return (fl & MAP_F_SEED_CAPPED) && q > MAP_MAPQ_CAPPED ? MAP_MAPQ_CAPPED : q;
+}
+/* The two records of a pair in state st whose items lie at kA and kB: qA, qB.  rq, rd1: each mate's Q_read and d1; q_pair: of the
+ * pair (read only when CONCORDANT). */
+MAP_HD void map_mapq_pair_records(uint32_t st, unsigned long long kA, unsigned long long kB, uint32_t rqA, uint32_t rqB, int d1A, int d1B,
+                                  uint32_t q_pair, uint32_t& qA, uint32_t& qB) {
+    qA = map_mapq_locus(kA, d1A, rqA), qB = map_mapq_locus(kB, d1B, rqB); /* no proper pair: each mate its single-end value */
+    if (st == MAP_PAIR_CONCORDANT) {
+        qA = qA > q_pair ? qA : q_pair, qB = qB > q_pair ? qB : q_pair;
+    } else if (st == MAP_PAIR_RESCUED1) { /* the anchor (mate 2) keeps its value; the rescued mate: no gap above 1 */
+        qA = qB < MAP_MAPQ_CAPPED ? qB : MAP_MAPQ_CAPPED;
+    } else if (st == MAP_PAIR_RESCUED2) {
+        qB = qA < MAP_MAPQ_CAPPED ? qA : MAP_MAPQ_CAPPED;
+    }
+}
+/* A secondary pair's two records (items kA, kB of a pair whose best d sum is S1): a pair that ties for the best is treated as the
+ * best one, one with a larger sum gets 0 */
+MAP_HD void map_mapq_secondary(unsigned long long kA, unsigned long long kB, int S1, uint32_t rqA, uint32_t rqB, int d1A, int d1B,
+                               uint32_t q_pair, uint32_t& qA, uint32_t& qB) {
+    qA = qB = 0u;
+    if (MAP_KEY_D(kA) + MAP_KEY_D(kB) == S1) map_mapq_pair_records(MAP_PAIR_CONCORDANT, kA, kB, rqA, rqB, d1A, d1B, q_pair, qA, qB);
+}
+
 /* Banded DP of q_s against tx[0, n): rows a = 0..m (read), columns b = 0..n, lanes l <-> diagonal b - a = l - MAP_MAX_ERRORS, only
  * the diagonals within d; dirs[a]: 2 bits per lane, 0 diagonal, 1 up (I), 2 left (D); ties prefer diagonal, then I, then D. */
 MAP_HD void map_band_fill(const char* q, uint32_t m, uint32_t s, const char* tx, int n, int d, uint64_t* dirs) {

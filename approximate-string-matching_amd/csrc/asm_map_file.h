@@ -300,17 +300,22 @@ static int map_file_chunk(MapReadsFileJob& j, const char* d_raw, const uint32_t*
     Scratch<unsigned long long> d_keys(h);
     MapAllItems ai(h);
     MapFinish fin(h);
+    MapRuns runs(h);
+    MapMapq mm(h); /* ASM_MAPQ_GAP: the items' MAPQ bytes, which stay on the device like the records */
+    const bool gap = h->mapq_model == ASM_MAPQ_GAP;
     std::vector<uint32_t> n_hits;
     int64_t nlines = rn;
     if (ns > 0) {
         if (const int rc = map_front_seed(h, ix, ns, p, f)) return rc;
         if (j.max_hits == 0) {
-            if (const int rc = map_best_keys(h, ix, ns, p, f, d_keys)) return rc;
+            if (const int rc = gap ? map_best_keys_gap(h, ix, ns, p, f, who, runs, mm, d_keys) : map_best_keys(h, ix, ns, p, f, d_keys)) return rc;
             if (const int rc = map_finish_launch(h, ix, p, f, ns, d_keys.p, nullptr, nullptr, f.bytes + (size_t)ns, SAM_CIGAR_CAP, fin))
                 return rc;
         } else {
             n_hits.resize((size_t)ns);
             if (const int rc = map_all_items(h, ix, ns, p, j.strata, j.max_hits, f, n_hits.data(), ai, who)) return rc;
+            if (gap)
+                if (const int rc = map_mapq_reads(h, ix, f, ai.runs, ns, p->max_errors, mm, nullptr, ai.d_ibase.p, ai.d_ikey.p, ai.ni)) return rc;
             if (const int rc = map_finish_launch(h, ix, p, f, ai.ni, ai.d_ikey.p, ai.d_iread.p, ai.d_idirs.p, ai.dwords, SAM_CIGAR_CAP, fin))
                 return rc;
             nlines = (rn - ns) + ai.ni; /* the item list is in read-then-rank order, which is SAM order */
@@ -327,6 +332,7 @@ static int map_file_chunk(MapReadsFileJob& j, const char* d_raw, const uint32_t*
     SamArgs a = {};
     a.raw = d_raw, a.recs = d_recs.p, a.rec_read = d_rec_read.p, a.nrec = (long)rn, a.nlines = (long)nlines;
     a.line_rec = d_lrec.p, a.line_item = d_litem.p;
+    a.mapq = mm.d_item;
     a.hits = fin.d_hits.p, a.ops = fin.d_ops.p, a.nops = fin.d_nops.p, a.ibase = (j.max_hits > 0 && ns > 0) ? ai.d_ibase.p : nullptr;
     a.n_hits = ai.d_nh.p, a.line_cnt = d_lcnt.p, a.line_base = d_lbase.p;
     /* the line list reads nrec, rec_read, ibase, line_cnt and line_base of a; what the tail sets (names, size, off, n_mapped) it does not */

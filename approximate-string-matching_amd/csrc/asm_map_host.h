@@ -384,19 +384,6 @@ static int map_best_keys(asm_handle* h, const asm_index* ix, int64_t n, const as
     });
 }
 
-/* asm_map_reads on one chunk: everything on the device, results straight into the caller's host arrays */
-static int map_chunk(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
-                     const asm_map_params* p, asm_map_hit* out, MapCigars cg) {
-    MapFront f(h);
-    Scratch<unsigned long long> d_keys(h);
-    const MapReadsIn in = {reads, read_off, n};
-    if (const int rc = map_front(h, ix, &in, 1, p, f)) return rc;
-    if (const int rc = map_best_keys(h, ix, n, p, f, d_keys)) return rc;
-    MapFinish fin(h);
-    if (const int rc2 = map_finish_launch(h, ix, p, f, n, d_keys.p, nullptr, nullptr, f.bytes + (size_t)n, cg.cap, fin)) return rc2;
-    return map_finish_collect(h, ix, p, f, fin, out, cg.ops, cg.nops);
-}
-
 /* The run records of one chunk (every call but asm_map_reads), sorted by (read, s, lo): the seeding rounds with
  * map_verify_all_kernel<W>, then a radix sort.  n < 2^31 reads, so that read << 33 fits the 64-bit run key. */
 struct MapRuns {
@@ -471,6 +458,76 @@ static MapSelectArgs map_select_args(const asm_index* ix, const MapFront& f, con
     return sel;
 }
 
+/* Mapping quality under ASM_MAPQ_GAP (the model: docs/design/mapper.md, "Mapping quality"; the rules: asm_map_core.h).  Per read
+ * Q_read and d1, and per item of a call its MAPQ byte, next to the device records. */
+struct MapMapq {
+    Scratch<uint8_t> rq, rd1, item, pq, ps1, sec;
+    const uint8_t* d_item = nullptr; /* per item of the finish stage: item.p, or rq.p where item i is read i with its best hit */
+    explicit MapMapq(asm_handle* h) : rq(h), rd1(h), item(h), pq(h), ps1(h), sec(h) {}
+};
+
+/* map_mapq_kernel over a chunk's sorted runs: rq and rd1; best: every read's best key (NULL: not wanted); ibase / ikey / ni: the
+ * items of asm_map_reads_all, whose bytes go to m.item (ibase NULL: none) */
+static int map_mapq_reads(asm_handle* h, const asm_index* ix, const MapFront& f, const MapRuns& runs, int64_t n, int e, MapMapq& m,
+                          unsigned long long* best, const uint32_t* ibase, const unsigned long long* ikey, int64_t ni) {
+    HIPCHK(h, m.rq.alloc((size_t)n + 1));
+    HIPCHK(h, m.rd1.alloc((size_t)n + 1));
+    if (ibase) HIPCHK(h, m.item.alloc((size_t)ni + 1));
+    MapMapqArgs a = {};
+    a.rkey = runs.key.p, a.rval = runs.val.p, a.nr = runs.nr, a.n = (long)n, a.e = e;
+    a.seq_off = (const unsigned long long*)ix->d_seq_off, a.n_seqs = (uint32_t)ix->n_seqs, a.flags = f.d_flags.p;
+    a.rq = m.rq.p, a.rd1 = m.rd1.p, a.best = best, a.ibase = ibase, a.ikey = ikey, a.mapq = m.item.p;
+    HIPCHK(h, launch(h, map_mapq_kernel, map_grid((uint64_t)n, h), 256, a));
+    m.d_item = ibase ? m.item.p : m.rq.p;
+    return ASM_OK;
+}
+
+/* the reference model's value of host records: what every in-memory call leaves for asm_map_last_mapq under ASM_MAPQ_REFERENCE */
+static void map_mapq_from_records(const asm_map_hit* out, size_t count, uint8_t* mq) {
+    for (size_t t = 0; t < count; t++) mq[t] = (uint8_t)map_mapq_reference((out[t].flags & ASM_MAP_MAPPED) != 0, out[t].greedy_cost);
+}
+
+/* An in-memory mapping call's body with the handle's MAPQ slots around it: `count` record slots, valid once the call succeeded */
+template <class F>
+static int map_mapq_call(asm_handle* h, size_t count, F body) {
+    h->last_mapq_valid = false;
+    h->last_mapq.assign(count, 0);
+    const int rc = body();
+    h->last_mapq_valid = rc == ASM_OK;
+    return rc;
+}
+
+/* asm_map_reads' keys under ASM_MAPQ_GAP, where the fold needs every locus: the sorted runs of the other calls instead of the
+ * atomicMin, then map_mapq_kernel, which leaves every read's best key (rank 0 of asm_map_reads_all: the same hit) and its MAPQ */
+static int map_best_keys_gap(asm_handle* h, const asm_index* ix, int64_t n, const asm_map_params* p, MapFront& f, const char* who,
+                             MapRuns& runs, MapMapq& mm, Scratch<unsigned long long>& d_keys) {
+    HIPCHK(h, d_keys.alloc(sizeof(unsigned long long) * (size_t)n));
+    if (const int rc = map_runs(h, ix, n, p, f, runs, who)) return rc;
+    return map_mapq_reads(h, ix, f, runs, n, p->max_errors, mm, d_keys.p, nullptr, nullptr, 0);
+}
+
+/* asm_map_reads on one chunk: everything on the device, results straight into the caller's host arrays */
+static int map_chunk(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
+                     const asm_map_params* p, asm_map_hit* out, MapCigars cg, uint8_t* mq) {
+    MapFront f(h);
+    Scratch<unsigned long long> d_keys(h);
+    const MapReadsIn in = {reads, read_off, n};
+    if (const int rc = map_front(h, ix, &in, 1, p, f)) return rc;
+    MapRuns runs(h);
+    MapMapq mm(h);
+    if (h->mapq_model == ASM_MAPQ_GAP) {
+        if (const int rc = map_best_keys_gap(h, ix, n, p, f, "asm_map_reads", runs, mm, d_keys)) return rc;
+    } else if (const int rc = map_best_keys(h, ix, n, p, f, d_keys)) {
+        return rc;
+    }
+    MapFinish fin(h);
+    if (const int rc2 = map_finish_launch(h, ix, p, f, n, d_keys.p, nullptr, nullptr, f.bytes + (size_t)n, cg.cap, fin)) return rc2;
+    if (mm.d_item) HIPCHK(h, hipMemcpyAsync(mq, mm.d_item, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    if (const int rc = map_finish_collect(h, ix, p, f, fin, out, cg.ops, cg.nops)) return rc;
+    if (!mm.d_item) map_mapq_from_records(out, (size_t)n, mq);
+    return ASM_OK;
+}
+
 /* asm_map_reads_all's items of a fronted chunk: the sorted run records, the loci selected per read (n_hits: host, n entries) and
  * listed as items in read-then-rank order, max(1, min(n_hits, max_hits)) per read */
 struct MapAllItems {
@@ -522,7 +579,8 @@ static int map_all_items(asm_handle* h, const asm_index* ix, int64_t n, const as
 /* asm_map_reads_all on one chunk: the front, the items, the finish stage on them, then the scatter into the caller's
  * [n][max_hits] slots */
 static int map_chunk_all(asm_handle* h, const asm_index* ix, int64_t n, const char* reads, const uint32_t* read_off,
-                         const asm_map_params* p, int strata, int max_hits, uint32_t* n_hits, asm_map_hit* out, MapCigars cg) {
+                         const asm_map_params* p, int strata, int max_hits, uint32_t* n_hits, asm_map_hit* out, MapCigars cg,
+                         uint8_t* mq) {
     MapFront f(h);
     const MapReadsIn in = {reads, read_off, n};
     if (const int rc = map_front(h, ix, &in, 1, p, f)) return rc;
@@ -533,6 +591,13 @@ static int map_chunk_all(asm_handle* h, const asm_index* ix, int64_t n, const ch
     MapFinish fin(h);
     if (const int rc = map_finish_launch(h, ix, p, f, ni, ai.d_ikey.p, ai.d_iread.p, ai.d_idirs.p, ai.dwords, cg.cap, fin)) return rc;
     MapItems it(ni, fin.ocap);
+    MapMapq mm(h);
+    std::vector<uint8_t> imq; /* ASM_MAPQ_GAP: per item */
+    if (h->mapq_model == ASM_MAPQ_GAP) {
+        if (const int rc = map_mapq_reads(h, ix, f, ai.runs, n, p->max_errors, mm, nullptr, ai.d_ibase.p, ai.d_ikey.p, ni)) return rc;
+        imq.resize((size_t)ni);
+        HIPCHK(h, hipMemcpyAsync(imq.data(), mm.d_item, (size_t)ni, hipMemcpyDeviceToHost, h->stream));
+    }
     if (const int rc = map_finish_collect(h, ix, p, f, fin, it.hits.data(), it.ops.data(), it.nops.data())) return rc;
     /* into the caller's [n][max_hits] slots (a read's items are contiguous); the flags that depend on the rank are set here.  The
      * CIGAR rows of unused slots are not written: their cigar_nops is 0. */
@@ -550,7 +615,9 @@ static int map_chunk_all(asm_handle* h, const asm_index* ix, int64_t n, const ch
             std::copy(it.nops.begin() + q0, it.nops.begin() + q0 + cnt, cg.nops + o);
             std::fill(cg.nops + o + cnt, cg.nops + o + max_hits, (uint8_t)0);
         }
+        if (!imq.empty()) std::copy(imq.begin() + q0, imq.begin() + q0 + cnt, mq + o); /* unused slots stay 0 */
     }
+    if (imq.empty()) map_mapq_from_records(out, (size_t)n * max_hits, mq);
     return ASM_OK;
 }
 
@@ -561,11 +628,13 @@ struct MapPairFront {
     MapRuns runs;
     Scratch<uint32_t> d_nh, d_dbest, d_lbase, d_lsplit, d_nconc, d_anchors, d_nanch;
     Scratch<unsigned long long> d_lkey, d_lbest, d_ikey, d_rslot;
-    Scratch<uint8_t> d_state;
+    Scratch<uint8_t> d_state, d_mapq; /* d_mapq: ASM_MAPQ_GAP, per read: the MAPQ of its record in the pair's answer */
+    MapMapq mm;
+    MapPairMapqArgs ma = {};
     MapPairArgs pa = {};
     explicit MapPairFront(asm_handle* h)
         : f(h), runs(h), d_nh(h), d_dbest(h), d_lbase(h), d_lsplit(h), d_nconc(h), d_anchors(h), d_nanch(h), d_lkey(h), d_lbest(h),
-          d_ikey(h), d_rslot(h), d_state(h) {}
+          d_ikey(h), d_rslot(h), d_state(h), d_mapq(h), mm(h) {}
 };
 
 struct MapPairsIn { /* the two mates of a chunk's pairs */
@@ -629,6 +698,16 @@ static int map_pairs_front_seed(asm_handle* h, const asm_index* ix, int64_t np, 
         HIPCHK(h, launched);
         HIPCHK(h, launch(h, map_rescue_pick_kernel, map_grid((uint64_t)np, h), 256, pa));
     }
+    if (h->mapq_model == ASM_MAPQ_GAP) { /* the states are final: every read folded, then every pair */
+        if (const int rc = map_mapq_reads(h, ix, f, pf.runs, n, e, pf.mm, nullptr, nullptr, nullptr, 0)) return rc;
+        HIPCHK(h, pf.d_mapq.alloc((size_t)n + 1));
+        HIPCHK(h, pf.mm.pq.alloc((size_t)np + 1));
+        HIPCHK(h, pf.mm.ps1.alloc((size_t)np + 1));
+        MapPairMapqArgs& ma = pf.ma;
+        ma.pa = pa, ma.e = e, ma.flags = f.d_flags.p, ma.rq = pf.mm.rq.p, ma.rd1 = pf.mm.rd1.p, ma.mapq = pf.d_mapq.p;
+        ma.pq = pf.mm.pq.p, ma.ps1 = pf.mm.ps1.p;
+        HIPCHK(h, launch(h, map_pair_mapq_kernel, map_grid((uint64_t)np, h), 256, ma));
+    }
     return ASM_OK;
 }
 
@@ -644,10 +723,15 @@ static int map_pairs_front(asm_handle* h, const asm_index* ix, int64_t np, const
  * into out[2 q slots + 0, 1] with the pair flags, tlen[q slots], n_concordant[q] and the CIGAR rows of those records (slots:
  * records per mate and pair in the caller's arrays, 1 for asm_map_pairs) */
 static int map_pairs_primary(asm_handle* h, const asm_index* ix, int64_t np, const asm_map_params* p, MapPairFront& pf, int slots,
-                             asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant, MapCigars cg) {
+                             asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant, MapCigars cg, uint8_t* mq) {
     const int64_t n = 2 * np;
     MapFront& f = pf.f;
     MapFinish fin(h);
+    std::vector<uint8_t> imq; /* ASM_MAPQ_GAP: per read */
+    if (pf.d_mapq.p) {
+        imq.resize((size_t)n);
+        HIPCHK(h, hipMemcpyAsync(imq.data(), pf.d_mapq.p, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    }
     if (const int rc = map_finish_launch(h, ix, p, f, n, pf.d_ikey.p, nullptr, nullptr, f.bytes + (size_t)n, cg.cap, fin)) return rc;
     MapItems it(n, fin.ocap);
     std::vector<uint8_t> state((size_t)np);
@@ -668,16 +752,19 @@ static int map_pairs_primary(asm_handle* h, const asm_index* ix, int64_t np, con
         const bool same = (o[0].flags & ASM_MAP_MAPPED) && (o[1].flags & ASM_MAP_MAPPED) && o[0].seq_id == o[1].seq_id;
         tlen[(size_t)q * slots] = same ? (int32_t)(std::max(o[0].end, o[1].end) - std::min(o[0].pos, o[1].pos)) : 0;
         it.cigar_to(cg, r0, (size_t)q), it.cigar_to(cg, r0 + 1, (size_t)(np + q));
+        if (!imq.empty()) mq[r0] = imq[(size_t)q], mq[r0 + 1] = imq[(size_t)(np + q)];
+        else map_mapq_from_records(o, 2, mq + r0);
     }
     return ASM_OK;
 }
 
 /* asm_map_pairs on one chunk of np pairs: the front, then the primary answer */
 static int map_chunk_pairs(asm_handle* h, const asm_index* ix, int64_t np, const MapPairsIn& m, const asm_map_params* p,
-                           const asm_pair_params* pp, asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant, MapCigars cg) {
+                           const asm_pair_params* pp, asm_map_hit* out, int32_t* tlen, uint32_t* n_concordant, MapCigars cg,
+                           uint8_t* mq) {
     MapPairFront pf(h);
     if (const int rc = map_pairs_front(h, ix, np, m, p, pp, "asm_map_pairs", pf)) return rc;
-    return map_pairs_primary(h, ix, np, p, pf, 1, out, tlen, n_concordant, cg);
+    return map_pairs_primary(h, ix, np, p, pf, 1, out, tlen, n_concordant, cg, mq);
 }
 
 /* host threads that fill the slots beyond rank 0 of asm_map_pairs_all's arrays as unused while the device works; joined by
@@ -708,7 +795,7 @@ struct MapSlotFill {
  * (rank 0); then the secondary items collected and scattered into the caller's [np][max_pairs][2] slots. */
 static int map_chunk_pairs_all(asm_handle* h, const asm_index* ix, int64_t np, const MapPairsIn& m, const asm_map_params* p,
                                const asm_pair_params* pp, int strata, int max_pairs, uint32_t* n_pairs, asm_map_hit* out,
-                               int32_t* tlen, uint32_t* n_concordant, MapCigars cg) {
+                               int32_t* tlen, uint32_t* n_concordant, MapCigars cg, uint8_t* mq) {
     MapSlotFill fill(np, max_pairs, out, tlen, cg);
     MapPairFront pf(h);
     if (const int rc = map_pairs_front(h, ix, np, m, p, pp, "asm_map_pairs_all", pf)) return rc;
@@ -742,8 +829,17 @@ static int map_chunk_pairs_all(asm_handle* h, const asm_index* ix, int64_t np, c
         HIPCHK(h, launch(h, map_pair_emit_kernel, map_grid((uint64_t)np, h), 256, aa));
         if (const int rc = map_finish_launch(h, ix, p, f, ni, d_ikey.p, d_iread.p, d_idirs.p, tot[1], cg.cap, fin)) return rc;
     }
+    std::vector<uint8_t> imq; /* ASM_MAPQ_GAP: per secondary item */
+    if (ni && h->mapq_model == ASM_MAPQ_GAP) {
+        HIPCHK(h, pf.mm.sec.alloc((size_t)ni));
+        MapPairMapqArgs ma = pf.ma;
+        ma.ni = (long)ni, ma.iread = d_iread.p, ma.ikey = d_ikey.p, ma.imapq = pf.mm.sec.p;
+        HIPCHK(h, launch(h, map_pair_item_mapq_kernel, map_grid((uint64_t)ni / 2, h), 256, ma));
+        imq.resize((size_t)ni);
+        HIPCHK(h, hipMemcpyAsync(imq.data(), pf.mm.sec.p, (size_t)ni, hipMemcpyDeviceToHost, h->stream));
+    }
     /* rank 0: asm_map_pairs' answer */
-    if (const int rc = map_pairs_primary(h, ix, np, p, pf, max_pairs, out, tlen, n_concordant, cg)) return rc;
+    if (const int rc = map_pairs_primary(h, ix, np, p, pf, max_pairs, out, tlen, n_concordant, cg, mq)) return rc;
     for (int64_t q = 0; q < np; q++)
         if (n_pairs[q] > (uint32_t)max_pairs) {
             out[(size_t)q * 2 * max_pairs].flags |= ASM_MAP_HITS_TRUNCATED;
@@ -768,6 +864,7 @@ static int map_chunk_pairs_all(asm_handle* h, const asm_index* ix, int64_t np, c
                 out[o + x] = it.hits[item + x];
                 out[o + x].flags |= extra;
                 it.cigar_to(cg, o + x, item + x);
+                mq[o + x] = imq.empty() ? (uint8_t)map_mapq_reference(true, out[o + x].greedy_cost) : imq[item + x];
             }
             tlen[(size_t)q * max_pairs + t] = (int32_t)(std::max(out[o].end, out[o + 1].end) - std::min(out[o].pos, out[o + 1].pos));
         }
@@ -867,8 +964,12 @@ int asm_map_reads(asm_handle* h, const asm_index* ix, int64_t n, const char* rea
     if (const int rc = map_check_args(h, ix, "asm_map_reads", "read", {n, p, {read_off, nullptr}, nullptr, nullptr, 0, 0, 0, cg}))
         return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    return map_chunks(n, h->map_chunk, [&](int64_t c0, int64_t cn) {
-        return map_chunk(h, ix, cn, reads, read_off + c0, p, out + c0, cg.at((size_t)c0));
+    /* under ASM_MAPQ_GAP the run key holds the read in its top 31 bits */
+    const int64_t step = h->mapq_model == ASM_MAPQ_GAP ? std::min<int64_t>(h->map_chunk, (int64_t)1 << 30) : h->map_chunk;
+    return map_mapq_call(h, (size_t)n, [&] {
+        return map_chunks(n, step, [&](int64_t c0, int64_t cn) {
+            return map_chunk(h, ix, cn, reads, read_off + c0, p, out + c0, cg.at((size_t)c0), h->last_mapq.data() + c0);
+        });
     });
 }
 
@@ -883,9 +984,12 @@ int asm_map_reads_all(asm_handle* h, const asm_index* ix, int64_t n, const char*
         return rc;
     HIPCHK(h, hipSetDevice(h->device));
     /* the run key holds the read in its top 31 bits */
-    return map_chunks(n, std::min<int64_t>(h->map_chunk, (int64_t)1 << 30), [&](int64_t c0, int64_t cn) {
-        const size_t o = (size_t)c0 * max_hits;
-        return map_chunk_all(h, ix, cn, reads, read_off + c0, p, strata, max_hits, n_hits + c0, out + o, cg.at(o));
+    return map_mapq_call(h, (size_t)n * max_hits, [&] {
+        return map_chunks(n, std::min<int64_t>(h->map_chunk, (int64_t)1 << 30), [&](int64_t c0, int64_t cn) {
+            const size_t o = (size_t)c0 * max_hits;
+            return map_chunk_all(h, ix, cn, reads, read_off + c0, p, strata, max_hits, n_hits + c0, out + o, cg.at(o),
+                                 h->last_mapq.data() + o);
+        });
     });
 }
 
@@ -898,8 +1002,11 @@ int asm_map_pairs(asm_handle* h, const asm_index* ix, int64_t n, const char* rea
     if (const int rc = map_check_args(h, ix, "asm_map_pairs", "mate", {n, p, {off1, off2}, pp, nullptr, 0, 0, 0, cg})) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     const MapPairsIn m = {reads1, off1, reads2, off2};
-    return map_chunks(n, map_pair_step(h), [&](int64_t c0, int64_t cn) {
-        return map_chunk_pairs(h, ix, cn, m.at(c0), p, pp, out + 2 * c0, tlen + c0, n_concordant + c0, cg.at((size_t)c0 * 2));
+    return map_mapq_call(h, 2 * (size_t)n, [&] {
+        return map_chunks(n, map_pair_step(h), [&](int64_t c0, int64_t cn) {
+            return map_chunk_pairs(h, ix, cn, m.at(c0), p, pp, out + 2 * c0, tlen + c0, n_concordant + c0, cg.at((size_t)c0 * 2),
+                                   h->last_mapq.data() + 2 * c0);
+        });
     });
 }
 
@@ -916,9 +1023,32 @@ int asm_map_pairs_all(asm_handle* h, const asm_index* ix, int64_t n, const char*
         return rc;
     HIPCHK(h, hipSetDevice(h->device));
     const MapPairsIn m = {reads1, off1, reads2, off2};
-    return map_chunks(n, map_pair_step(h), [&](int64_t c0, int64_t cn) {
-        const size_t o = (size_t)c0 * max_pairs;
-        return map_chunk_pairs_all(h, ix, cn, m.at(c0), p, pp, strata, max_pairs, n_pairs + c0, out + 2 * o, tlen + o, n_concordant + c0,
-                                   cg.at(2 * o));
+    return map_mapq_call(h, 2 * (size_t)n * max_pairs, [&] {
+        return map_chunks(n, map_pair_step(h), [&](int64_t c0, int64_t cn) {
+            const size_t o = (size_t)c0 * max_pairs;
+            return map_chunk_pairs_all(h, ix, cn, m.at(c0), p, pp, strata, max_pairs, n_pairs + c0, out + 2 * o, tlen + o,
+                                       n_concordant + c0, cg.at(2 * o), h->last_mapq.data() + 2 * o);
+        });
     });
+}
+
+int asm_map_set_mapq_model(asm_handle* h, int model) { /* the model is checked first, so that the check needs no device */
+    if (model != ASM_MAPQ_REFERENCE && model != ASM_MAPQ_GAP)
+        return fail(h, ASM_EINVAL, "asm_map_set_mapq_model: model must be ASM_MAPQ_REFERENCE (0) or ASM_MAPQ_GAP (1)");
+    if (!h) return fail(nullptr, ASM_EINVAL, "asm_map_set_mapq_model: NULL handle");
+    h->mapq_model = model;
+    return ASM_OK;
+}
+
+int asm_map_get_mapq_model(const asm_handle* h) { return h ? h->mapq_model : ASM_MAPQ_REFERENCE; }
+
+int asm_map_last_mapq(asm_handle* h, uint8_t* dst, int64_t count) {
+    if (count < 0) return fail(h, ASM_EINVAL, "asm_map_last_mapq: count must be >= 0");
+    if (count > 0 && !dst) return fail(h, ASM_EINVAL, "asm_map_last_mapq: dst is NULL");
+    if (!h) return fail(nullptr, ASM_EINVAL, "asm_map_last_mapq: NULL handle");
+    if (!h->last_mapq_valid) return fail(h, ASM_EINVAL, "asm_map_last_mapq: no in-memory mapping call has succeeded on this handle");
+    if ((uint64_t)count != h->last_mapq.size())
+        return fail(h, ASM_EINVAL, "asm_map_last_mapq: count must be the last call's record slots (" + std::to_string(h->last_mapq.size()) + ")");
+    std::copy(h->last_mapq.begin(), h->last_mapq.end(), dst);
+    return ASM_OK;
 }

@@ -34,6 +34,7 @@ struct SamLine {
     int32_t seq_id;
     uint32_t pos;
     int32_t dist, greedy_cost;
+    int32_t mapq; /* column 5 of a mapped line, by the call's MAPQ model (the loaders below; docs/design/mapper.md, "Mapping quality") */
     uint32_t strand, rank;
     const uint16_t* ops; /* count << 3 | op */
     uint32_t nops;
@@ -139,7 +140,7 @@ SAM_HD void sam_format(const SamLine& l, Sink& o) {
     o.ch('\t');
     o.num(pos_x);
     o.ch('\t');
-    if (own) sam_int(o, l.greedy_cost + 60 < 254 ? l.greedy_cost + 60 : 254);
+    if (own) sam_int(o, l.mapq);
     else o.ch('0');
     o.ch('\t');
     if (!own || l.nops > (uint32_t)SAM_CIGAR_CAP) {
@@ -227,6 +228,7 @@ struct SamArgs {
     const MapHit* hits;         /* per item */
     const uint16_t* ops;        /* [items][SAM_CIGAR_CAP] */
     const uint8_t* nops;
+    const uint8_t* mapq;        /* per item: its MAPQ byte (ASM_MAPQ_GAP); NULL: the reference model, read off the record's greedy_cost */
     const uint32_t* ibase;      /* all hits: first item of every library read (n + 1); NULL: item i is read i */
     const uint32_t* n_hits;     /* all hits: loci per library read, uncapped */
     const char* names;          /* RNAME table: the names back to back */
@@ -287,6 +289,7 @@ __device__ inline SamLine sam_load_pair_line(const SamArgs& a, long l) {
     s.n_concordant = a.n_conc[rd];
     if (h.flags & MAP_F_MAPPED) {
         s.mapped = 1, s.seq_id = h.seq_id, s.pos = h.pos, s.dist = h.dist, s.greedy_cost = h.greedy_cost, s.strand = h.strand;
+        s.mapq = a.mapq ? (int32_t)a.mapq[ix] : map_mapq_reference(true, h.greedy_cost);
         s.ops = a.ops + (size_t)ix * SAM_CIGAR_CAP, s.nops = a.nops[ix];
         s.rname = a.names + a.name_off[h.seq_id], s.rname_len = a.name_off[h.seq_id + 1] - a.name_off[h.seq_id];
     }
@@ -306,6 +309,7 @@ __device__ inline SamLine sam_load_line(const SamArgs& a, long l) {
     const MapHit h = a.hits[it];
     if (!(h.flags & MAP_F_MAPPED)) return s;
     s.mapped = 1, s.seq_id = h.seq_id, s.pos = h.pos, s.dist = h.dist, s.greedy_cost = h.greedy_cost, s.strand = h.strand;
+    s.mapq = a.mapq ? (int32_t)a.mapq[it] : map_mapq_reference(true, h.greedy_cost);
     s.ops = a.ops + (size_t)it * SAM_CIGAR_CAP, s.nops = a.nops[it];
     s.rname = a.names + a.name_off[h.seq_id], s.rname_len = a.name_off[h.seq_id + 1] - a.name_off[h.seq_id];
     if (a.ibase) {

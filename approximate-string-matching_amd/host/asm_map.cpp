@@ -18,6 +18,9 @@
 // SO:coordinate.  With --stream / --stream-pairs the library sorts on the device (asm_map_file_sorted, asm_map_pairs_file_sorted;
 // --sort-mem BYTES: the most device memory the held SAM text and its tables may take, default no cap); without them the lines are
 // built as always and sorted here, by the key read from their text.  The two ways give the same file.
+// --mapq reference|gap (any mapping mode; default reference) picks the model of column 5 (asm_map_set_mapq_model): reference is
+// min(254, 60 + greedy_cost), gap the repeat- and pair-aware value of docs/design/mapper.md, "Mapping quality".  The streamed modes
+// let the library format it; the others read it with asm_map_last_mapq, so both ways write the same file under either model.
 //   asm-map -r ref.fa --bench-ref N [--k 12]
 // maps nothing: it builds the index N times each way, alternately, and prints the seconds of every build.
 // --all-hits N writes up to N loci per read in rank order (asm_map_reads_all, strata S, default e): the primary record as without
@@ -58,6 +61,7 @@ static void usage() {
                     "       asm-map -r ref.fa -1 r1.fq -2 r2.fq --stream-pairs [--chunk-bytes N] [-o out.sam] -e N --insert MIN,MAX "
                     "[--rescue E] [--k 12] [--max-occ N]\n"
                     "       any of them with --ref-stream: the reference is read and parsed by the library\n"
+                    "       any of them with --mapq reference|gap: the model of the MAPQ column (default reference)\n"
                     "       any of them with --sort: coordinate-sorted output (--stream, --stream-pairs: on the device, [--sort-mem BYTES])\n");
     exit(2);
 }
@@ -149,7 +153,7 @@ static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vecto
     std::vector<int32_t> tlen;
     std::vector<uint32_t> nconc, npairs;
     std::vector<uint16_t> ops;
-    std::vector<uint8_t> nops;
+    std::vector<uint8_t> nops, mq;
     long long n_pairs = 0, n_proper = 0, n_rescued = 0, n_secondary = 0;
     bool more = true;
     while (more) {
@@ -188,7 +192,8 @@ static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vecto
                                                     npairs.data(), hits.data(), tlen.data(), nconc.data(), ops.data(), cap, nops.data())
                                 : asm_map_pairs(h, ix, n, buf1.data(), ro1.data(), buf2.data(), ro2.data(), &p, &pp, hits.data(),
                                                 tlen.data(), nconc.data(), ops.data(), cap, nops.data());
-        if (rc) {
+        mq.assign((size_t)(n + 1) * 2 * slots, 0);
+        if (rc || asm_map_last_mapq(h, mq.data(), n * 2 * slots)) {
             fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
             return 1;
         }
@@ -231,7 +236,7 @@ static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vecto
                     const size_t o = (size_t)slot[q] * 2 * slots + x;
                     const int nn = nops[o];
                     if (asm_cigar_format(&ops[o * cap], nn, cap, cigar, sizeof(cigar)) != 0 || nn > cap) strcpy(cigar, "*");
-                    mapq = m.greedy_cost + 60 < 254 ? m.greedy_cost + 60 : 254;
+                    mapq = mq[o];
                 }
                 const char* rnext = !mapped[y] ? "*" : rid[y] == rid[x] ? "=" : names[(size_t)rid[y]].c_str();
                 fprintf(out, "%s\t%d\t%s\t%lld\t%d\t%s\t%s\t%lld\t%lld\t%s\t%s", pair_name(rec[x]->name).c_str(), flag,
@@ -259,7 +264,7 @@ static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vecto
                     char cigar[4096];
                     const int nn = nops[o + x];
                     if (asm_cigar_format(&ops[(o + x) * cap], nn, cap, cigar, sizeof(cigar)) != 0 || nn > cap) strcpy(cigar, "*");
-                    const int mapq = m.greedy_cost + 60 < 254 ? m.greedy_cost + 60 : 254;
+                    const int mapq = mq[o + x];
                     fprintf(out, "%s\t%d\t%s\t%u\t%d\t%s\t=\t%u\t%lld\t*\t*\tNM:i:%d\tXG:i:%d\tNH:i:%u\tHI:i:%u\tXH:i:%u\n",
                             pair_name(rec[x]->name).c_str(), flag, names[(size_t)m.seq_id].c_str(), m.pos + 1, mapq, cigar,
                             sr[1 - x]->pos + 1, x == splus ? stl : -stl, (int)m.dist, m.greedy_cost, nrep, t + 1, nh);
@@ -399,6 +404,7 @@ int main(int argc, char** argv) {
     bool stream = false, stream_pairs = false, ref_stream = false, sort = false;
     int bench_ref = 0;
     long long chunk_bytes = 0, sort_mem = -1;
+    int mapq_model = ASM_MAPQ_REFERENCE;
     std::string cl = "asm-map";
     for (int a = 1; a < argc; a++) cl += std::string(" ") + argv[a];
     for (int a = 1; a < argc; a++) {
@@ -427,6 +433,11 @@ int main(int argc, char** argv) {
         else if (s == "--bench-ref") bench_ref = atoi(val());
         else if (s == "--chunk-bytes") chunk_bytes = atoll(val());
         else if (s == "--sort") sort = true;
+        else if (s == "--mapq") {
+            const std::string m = val();
+            if (m != "reference" && m != "gap") usage();
+            mapq_model = m == "gap" ? ASM_MAPQ_GAP : ASM_MAPQ_REFERENCE;
+        }
         else if (s == "--sort-mem") {
             if ((sort_mem = atoll(val())) < 0) usage();
         }
@@ -502,6 +513,7 @@ int main(int argc, char** argv) {
     asm_handle* h = nullptr;
     asm_index* ix = nullptr;
     int rc = asm_create(&h, 0);
+    if (!rc) rc = asm_map_set_mapq_model(h, mapq_model);
     if (!rc)
         rc = ref_stream ? asm_index_build_file(h, ref_path.c_str(), k, 0, &ix, nullptr)
                         : asm_index_build(h, text.data(), off.data(), (int32_t)names.size(), k, &ix);
@@ -587,7 +599,7 @@ int main(int argc, char** argv) {
     std::vector<int64_t> slot; /* record -> index in the library call, -1 = not sent (too long) */
     std::vector<asm_map_hit> hits;
     std::vector<uint16_t> ops;
-    std::vector<uint8_t> nops;
+    std::vector<uint8_t> nops, mq;
     std::vector<uint32_t> n_hits;
     long long n_total = 0, n_mapped = 0, n_long = 0;
     bool more = true;
@@ -618,6 +630,8 @@ int main(int argc, char** argv) {
                                    nops.data());
         else
             rc = asm_map_reads(h, ix, n, buf.data(), ro.data(), &p, hits.data(), ops.data(), cap, nops.data());
+        mq.assign((size_t)(n + 1) * slots, 0);
+        if (!rc) rc = asm_map_last_mapq(h, mq.data(), n * slots);
         if (rc) {
             fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
             return 1;
@@ -646,7 +660,7 @@ int main(int argc, char** argv) {
                 char cigar[4096];
                 const int nn = nops[o];
                 if (asm_cigar_format(&ops[o * cap], nn, cap, cigar, sizeof(cigar)) != 0 || nn > cap) strcpy(cigar, "*");
-                const int mapq = hr.greedy_cost + 60 < 254 ? hr.greedy_cost + 60 : 254;
+                const int mapq = mq[o];
                 fprintf(out, "%s\t%d\t%s\t%u\t%d\t%s\t*\t0\t0\t%s\t%s\tNM:i:%d\tXG:i:%d", rec.name.c_str(),
                         (hr.strand ? 16 : 0) | (t ? 256 : 0), names[(size_t)hr.seq_id].c_str(), hr.pos + 1, mapq, cigar,
                         t ? "*" : seq.c_str(), t || qual.empty() ? "*" : qual.c_str(), (int)hr.dist, hr.greedy_cost);

@@ -13,6 +13,9 @@
 // Output argv[2], per case: per read {i32 seq_id, u32 pos, end, i32 dist, u32 strand, flags, nops, u16 ops[min(nops, cap)]} (the
 // best hit; in a paired case the pairing's item), then per read {u32 n, each u64 locus key in (s, r, j) order}, then, paired, per
 // pair {u32 state, n_concordant, u64 item key of A and of B, u32 n_pairs, u32 listed = min(n_pairs, pair_cap), each u64 kA, kB}.
+// With a third argument `--mapq` (tests/test_mapq_host.py) every case goes on with the mapping-quality folds (map_mapq_kernel,
+// map_pair_mapq_kernel): per read {u32 d1, n1, d2, Q_read}, then, paired, per pair {i32 S1, u32 N1, i32 S2, u32 Q_pair, MAPQ of
+// the record of A and of B}.
 #include <stdio.h>
 #include <string.h>
 
@@ -69,7 +72,7 @@ static Index build_index(const std::string& text, const std::vector<u64>& seq_of
 
 template <int W>
 static void run_case(const std::string& text, const std::vector<u64>& seq_off, const Index& ix, const Case& c, const std::string& reads,
-                     const std::vector<uint32_t>& roff, FILE* out) {
+                     const std::vector<uint32_t>& roff, FILE* out, bool mapq) {
     const long n = (long)roff.size() - 1;
     const uint32_t n_seqs = (uint32_t)seq_off.size() - 1;
     /* seeding and both verifications: map_seed_count / emit, map_verify_kernel (atomicMin), map_verify_all_kernel (run buffer) */
@@ -178,10 +181,33 @@ static void run_case(const std::string& text, const std::vector<u64>& seq_off, c
         put32(out, cnt), put32(out, (uint32_t)(list.size() / 2));
         put(out, list.data(), 8 * list.size());
     }
+    if (!mapq) return;
+    /* mapping quality: map_mapq_kernel per read, map_pair_mapq_kernel per pair (no bucket cap here, so no read is SEED_CAPPED) */
+    std::vector<uint32_t> rq(n);
+    std::vector<int> rd1(n);
+    for (long i = 0; i < n; i++) {
+        const MapRange g = map_read_runs(rkey.data(), rkey.size(), i);
+        const MapMapqRead x = map_mapq_read(rkey.data(), rval.data(), g.b, g.e, seq_off.data(), n_seqs, (int)c.e);
+        rq[i] = map_mapq_read_q(x, 0u), rd1[i] = x.d1;
+        if (x.best != lbest[i]) rq[i] = 0xffffffffu; /* the fold's best key is the loci list's */
+        put32(out, (uint32_t)x.d1), put32(out, x.n1), put32(out, (uint32_t)x.d2), put32(out, rq[i]);
+    }
+    for (long p = 0; p < np; p++) {
+        const long A = p, B = np + p;
+        MapMapqPair x = {-1, -1, 0u};
+        uint32_t q_pair = 0, qA, qB;
+        if (state[p] == MAP_PAIR_CONCORDANT) {
+            x = map_mapq_pair(pa, p);
+            q_pair = map_mapq_pair_q(x, MAP_KEY_D(ikey[A]), MAP_KEY_D(ikey[B]), (int)c.e, 0u);
+        }
+        map_mapq_pair_records(state[p], ikey[A], ikey[B], rq[A], rq[B], rd1[A], rd1[B], q_pair, qA, qB);
+        put32(out, (uint32_t)x.S1), put32(out, x.N1), put32(out, (uint32_t)x.S2), put32(out, q_pair), put32(out, qA), put32(out, qB);
+    }
 }
 
 int main(int argc, char** argv) {
-    if (argc != 3) return 2;
+    const bool mapq = argc == 4 && strcmp(argv[3], "--mapq") == 0;
+    if (argc != 3 && !mapq) return 2;
     FILE* in = fopen(argv[1], "rb");
     FILE* out = fopen(argv[2], "wb");
     if (!in || !out) return 2;
@@ -201,10 +227,10 @@ int main(int argc, char** argv) {
         const int nw = (int)(maxm + 63) / 64;
         if (!index.count(c.k)) index[c.k] = build_index(text, seq_off, c.k);
         const Index& ix = index[c.k];
-        if (nw <= 1) run_case<1>(text, seq_off, ix, c, reads, roff, out);
-        else if (nw <= 2) run_case<2>(text, seq_off, ix, c, reads, roff, out);
-        else if (nw <= 4) run_case<4>(text, seq_off, ix, c, reads, roff, out);
-        else run_case<8>(text, seq_off, ix, c, reads, roff, out);
+        if (nw <= 1) run_case<1>(text, seq_off, ix, c, reads, roff, out, mapq);
+        else if (nw <= 2) run_case<2>(text, seq_off, ix, c, reads, roff, out, mapq);
+        else if (nw <= 4) run_case<4>(text, seq_off, ix, c, reads, roff, out, mapq);
+        else run_case<8>(text, seq_off, ix, c, reads, roff, out, mapq);
     }
     fclose(in);
     return fclose(out) == 0 ? 0 : 4;

@@ -14,6 +14,7 @@
 
 #include <vector>
 
+#include "../csrc/asm_map_core.h"
 #include "../csrc/asm_sam.h"
 
 static bool get(FILE* f, void* p, size_t n) { return n == 0 || fread(p, 1, n, f) == n; }
@@ -40,6 +41,7 @@ int main(int argc, char** argv) {
         l.mapped = (int)u[0], l.seq_id = (int32_t)u[1], l.pos = u[2], l.dist = (int32_t)u[3], l.greedy_cost = (int32_t)u[4];
         l.strand = u[5], l.rank = u[6], l.nops = u[7], l.all = (int)u[8], l.n_reported = u[9], l.n_hits = u[10];
         l.ops = ops.data(), l.rname = rname.data(), l.rname_len = rname_len;
+        l.mapq = map_mapq_reference(l.mapped != 0, l.greedy_cost); /* the cases carry no MAPQ of their own: the reference model's */
         uint32_t v[10], mate_rname_len = 0;
         std::vector<char> mate_rname;
         if (pairs) {

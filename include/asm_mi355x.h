@@ -442,6 +442,24 @@ int asm_map_pairs_all(asm_handle* h, const asm_index* ix, int64_t n, const char*
                       uint32_t* n_concordant /* [n] */, uint16_t* cigar_ops /* [n][max_pairs][2][cigar_cap] */, int cigar_cap,
                       uint8_t* cigar_nops /* [n][max_pairs][2] */);
 
+/* Mapping quality (docs/design/mapper.md, "Mapping quality"): the model is handle state, like the stream, and all eight mapping
+ * calls honour it.  ASM_MAPQ_REFERENCE (the default): MAPQ = min(254, 60 + greedy_cost) of a mapped record.  ASM_MAPQ_GAP: what
+ * the exact search proves, T(n, g) with n the loci (or concordant pairs) that tie for the best and g a lower bound on the edit gap to
+ * the nearest alternative: T(1, g) = min(60, 20 g), T(2) = 3, T(3..4) = 1, T(>= 5) = 0; at most 20 for a SEED_CAPPED read and for a
+ * rescued mate; 0 for a locus or pair that is not the best.  Unmapped records and unused slots have 0 under both.  The records,
+ * CIGARs and greedy_cost of every call are the same under both models; under ASM_MAPQ_GAP the best-hit calls take the all-hits
+ * path to the loci, which costs time.
+ * asm_map_set_mapq_model: a model other than the two is ASM_EINVAL.
+ * asm_map_last_mapq: the MAPQ of every record slot of the last successful in-memory mapping call on this handle (asm_map_reads,
+ *                  asm_map_reads_all, asm_map_pairs, asm_map_pairs_all), in the layout of that call's `out` array: count must be
+ *                  its n, n * max_hits, 2 n or 2 n * max_pairs; any other count, or no earlier call, is ASM_EINVAL.  asm_map_hit
+ *                  is a full 20-byte record, so the value travels beside it.  The file calls write it into column 5. */
+#define ASM_MAPQ_REFERENCE 0
+#define ASM_MAPQ_GAP 1
+int asm_map_set_mapq_model(asm_handle* h, int model);
+int asm_map_get_mapq_model(const asm_handle* h);
+int asm_map_last_mapq(asm_handle* h, uint8_t* dst /* [count] */, int64_t count);
+
 /* asm_map_file:    a FASTQ file in, a SAM file out (docs/design/mapper.md, "Files: FASTQ in, SAM out"); single-end, synchronous.  The
  *                  file is read in chunks of about chunk_bytes (0: 16 MiB) cut at record boundaries; a chunk is parsed, mapped
  *                  and formatted on the device while the next one is read and copied in and the one before is copied out and

@@ -14,6 +14,9 @@ against asm_map_reads_all (strata = e, max_hits = 1) on the same reads, alternat
 asm_map_pairs instead, alternately, and prints the n_pairs distribution.
 --dump DIR writes DIR/digests.json: the SHA-256 of every output array of every timed call (per e; CIGAR rows up to their nops), for comparing two builds
 of the library (ASM_MI355X_LIB, a fresh process each) for exact equality on a workload of real size.
+--mapq reference|gap sets the engine's MAPQ model (docs/design/mapper.md, "Mapping quality") before anything is timed; under gap
+asm_map_reads takes the runs path, which is what the option is there to price.  Every row also lists the timed call's
+milliseconds of each repeat (map_ms_reps), so that a run shows its own spread.
 --profile re-runs the same command under `rocprofv3 --kernel-trace --stats` (a run of its own) and prints the per-kernel totals."""
 import argparse
 import ctypes
@@ -102,8 +105,10 @@ def main():
     ap.add_argument("--out", default=None, help="directory for the JSON result (and the profile with --profile)")
     ap.add_argument("--dump", default=None, help="directory for digests.json, the SHA-256 of every output array")
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--mapq", choices=["reference", "gap"], default="reference", help="the engine's MAPQ model")
     a = ap.parse_args()
-    extra = (["--all-hits", str(a.all_hits)] if a.all_hits else []) + (["--strata", str(a.strata)] if a.strata is not None else [])
+    extra = ["--mapq", a.mapq]
+    extra += (["--all-hits", str(a.all_hits)] if a.all_hits else []) + (["--strata", str(a.strata)] if a.strata is not None else [])
     extra += ["--repeats"] if a.repeats else []
     extra += ["--paired", "--insert", a.insert, "--rescue", str(a.rescue)] if a.paired else []
     n, ref_len = int(a.reads), int(a.ref_len)
@@ -122,9 +127,10 @@ def main():
                 print("  %-60s calls %6s total ms %10.3f" % (r["Name"][:60], r["Calls"], float(r["TotalDurationNs"]) / 1e6))
         return
     eng = m.Engine(0)
+    eng.set_mapq_model(a.mapq)
     lib, h = eng.lib, eng.h
     tm = eng.timer()
-    results = {"ref_len": ref_len, "reads": n, "read_len": a.len, "k": a.k, "repeats": a.repeats, "all_hits": a.all_hits, "runs": []}
+    results = {"ref_len": ref_len, "reads": n, "read_len": a.len, "k": a.k, "mapq": a.mapq, "repeats": a.repeats, "all_hits": a.all_hits, "runs": []}
     if a.paired:
         return run_paired(a, eng, tm, n, ref_len)
     for e in a.errors:
@@ -152,6 +158,7 @@ def main():
         all_ops = np.zeros(n * H * 16, np.uint16) if a.all_hits else None
         all_nops = np.zeros(n * H, np.uint8) if a.all_hits else None
         best_map, best_wall, best_all = 1e30, 1e30, 1e30
+        map_reps = []
         for _ in range(a.reps):  # the two calls alternate, so that both see the same machine state
             t0 = time.perf_counter()
             tm.start()
@@ -159,6 +166,7 @@ def main():
                                        16, nops.ctypes.data))
             tm.stop()
             best_map = min(best_map, tm.elapsed_ms())
+            map_reps.append(round(tm.elapsed_ms(), 3))
             best_wall = min(best_wall, (time.perf_counter() - t0) * 1e3)
             if a.all_hits:
                 tm.start()
@@ -171,7 +179,7 @@ def main():
             dump_digests(a, e, {"reads.hits": hits, "reads.ops": ops, "reads.nops": nops, "reads_all.n_hits": n_hits if a.all_hits else None,
                                 "reads_all.hits": all_hits, "reads_all.ops": all_ops, "reads_all.nops": all_nops})
         mapped = float(((hits["flags"] & m.MAP_MAPPED) != 0).mean())
-        row = {"e": e, "index_build_ms": round(best_ix, 3), "map_ms_events": round(best_map, 3), "map_ms_wall": round(best_wall, 3),
+        row = {"e": e, "mapq": a.mapq, "index_build_ms": round(best_ix, 3), "map_ms_events": round(best_map, 3), "map_ms_reps": map_reps, "map_ms_wall": round(best_wall, 3),
                "reads_per_s": round(n / best_map * 1e3), "mapped_fraction": round(mapped, 4)}
         if a.all_hits:
             rep_n = np.minimum(n_hits, a.all_hits)
@@ -273,6 +281,7 @@ def run_paired(a, eng, tm, n, ref_len):
         pa_ops = np.zeros(npairs * P * 2 * 16, np.uint16) if a.all_hits else None
         pa_nops = np.zeros(npairs * P * 2, np.uint8) if a.all_hits else None
         best_pairs, best_all = 1e30, 1e30
+        pairs_reps = []
         for _ in range(a.reps):  # alternating, so that both calls see the same machine state
             if a.all_hits:
                 tm.start()
@@ -288,6 +297,7 @@ def run_paired(a, eng, tm, n, ref_len):
                                        nops.ctypes.data))
             tm.stop()
             best_pairs = min(best_pairs, tm.elapsed_ms())
+            pairs_reps.append(round(tm.elapsed_ms(), 3))
             if a.all_hits:
                 continue
             tm.start()
@@ -304,7 +314,7 @@ def run_paired(a, eng, tm, n, ref_len):
                                 "reads_all.hits": None if a.all_hits else all_hits, "reads_all.ops": None if a.all_hits else all_ops,
                                 "reads_all.nops": None if a.all_hits else all_nops})
         fl = hits["flags"].reshape(npairs, 2)
-        row = {"e": e, "pairs_ms_events": round(best_pairs, 3), "pairs_per_s": round(npairs / best_pairs * 1e3),
+        row = {"e": e, "mapq": a.mapq, "pairs_ms_events": round(best_pairs, 3), "pairs_ms_reps": pairs_reps, "pairs_per_s": round(npairs / best_pairs * 1e3),
                "all_hits1_ms_events": round(best_all, 3), "pairs_over_all_hits1": round(best_pairs / best_all, 3),
                "proper_fraction": round(float(((fl[:, 0] & m.MAP_PROPER_PAIR) != 0).mean()), 4),
                "rescued_fraction": round(float(((fl & m.MAP_RESCUED) != 0).any(axis=1).mean()), 4),
