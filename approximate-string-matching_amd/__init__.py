@@ -136,6 +136,7 @@ MAP_HIT_DTYPE = np.dtype([("seq_id", np.int32), ("pos", np.uint32), ("end", np.u
                           ("flags", np.uint8), ("greedy_cost", np.int32)])
 MAP_MAPPED, MAP_TOO_SHORT, MAP_SEED_CAPPED, MAP_CIGAR_TRUNCATED = 1, 2, 4, 8
 MAPQ_REFERENCE, MAPQ_GAP = 0, 1  # asm_map_set_mapq_model
+SAM_TAG_MD, MAP_MD_CAP = 1, 80  # asm_map_set_sam_tags; ASM_MAP_MD_CAP: an MD tag and its NUL always fit
 MAP_SECONDARY, MAP_HITS_TRUNCATED, MAP_MAX_HITS = 16, 32, 256
 MAP_PROPER_PAIR, MAP_RESCUED, MAP_MAX_INSERT = 64, 128, 8192
 MAP_MIN_K, MAP_MAX_K, MAP_MAX_READ, MAP_MAX_ERRORS = 8, 14, 511, 15
@@ -281,6 +282,9 @@ def load_library() -> ctypes.CDLL:
         "asm_map_set_mapq_model": (i32, [vp, i32]),
         "asm_map_get_mapq_model": (i32, [vp]),
         "asm_map_last_mapq": (i32, [vp, vp, i64]),
+        "asm_map_set_sam_tags": (i32, [vp, c.c_uint]),
+        "asm_map_get_sam_tags": (c.c_uint, [vp]),
+        "asm_md_format": (i32, [vp, i32, c.c_char_p, i32, c.c_char_p, i32, vp, c.c_size_t]),
         "asm_map_file": (i32, [vp, vp, c.POINTER(c.c_char_p), c.c_char_p, c.c_char_p, c.c_char_p, c.POINTER(MapParams), i32, i32, i64,
                                c.POINTER(MapFileStats)]),
         "asm_fastq_cut": (c.c_size_t, [vp, c.c_size_t, c.POINTER(i64)]),
@@ -618,6 +622,17 @@ class Engine:
 
     def mapq_model(self) -> int:
         return int(self.lib.asm_map_get_mapq_model(self.h))
+
+    def set_sam_tags(self, md: bool = False) -> None:
+        """asm_map_set_sam_tags: the optional tags of the lines map_file and map_pairs_file write (sorted or not).  md=True: every
+        line that shows a CIGAR carries MD:Z behind XG (docs/design/mapper.md, "MD tag"), built on the device.  The default, nothing
+        set, leaves every byte as it is.  The in-memory map_* calls carry no MD; md_format gives it from their records."""
+        self._chk(self.lib.asm_map_set_sam_tags(self.h, SAM_TAG_MD if md else 0))
+
+    @property
+    def sam_tags(self) -> int:
+        """asm_map_get_sam_tags: the mask in force (SAM_TAG_MD)"""
+        return int(self.lib.asm_map_get_sam_tags(self.h))
 
     def last_mapq(self, count: int) -> np.ndarray:
         """asm_map_last_mapq: uint8[count], the MAPQ of every record slot of the last in-memory library call, in its `out` layout"""
@@ -1054,6 +1069,27 @@ def decode_cigars(ops: np.ndarray, nops: np.ndarray, cap: int, reverse: bool = F
             row = row[::-1]
         out.append("".join(f"{int(v) >> 3}{letters[int(v) & 7]}" for v in row))
     return out
+
+
+def md_format(ops, read_on_strand, ref_window) -> str:
+    """asm_md_format: the MD:Z tag of one record, on the host (no device).  ops: its CIGAR, as a string of M, I and D runs ("40M1D60M",
+    as the map_* methods return it) or as an encoded row (count << 3 | op); read_on_strand: the read as the alignment sees it (the
+    reverse complement for strand 1); ref_window: the reference bases [pos, end) of the record's sequence.  Both are upper-cased."""
+    if isinstance(ops, (str, bytes)):
+        import re
+
+        text = ops.decode("ascii") if isinstance(ops, bytes) else ops
+        runs = re.findall(r"(\d+)([MID])", text)
+        if "".join(c + o for c, o in runs) != text:
+            raise ValueError("a CIGAR of M, I and D runs is wanted")
+        ops = [int(c) << 3 | "MID".index(o) for c, o in runs]
+    row = np.ascontiguousarray(ops, np.uint16).reshape(-1)
+    q, w = _as_bytes(read_on_strand), _as_bytes(ref_window)
+    out = ctypes.create_string_buffer(12 * (len(w) + row.size + 2))  # a letter or a caret, and a number in front, per byte and run
+    n = load_library().asm_md_format(row.ctypes.data if row.size else None, int(row.size), q, len(q), w, len(w), out, len(out))
+    if n < 0:
+        raise AsmError(n, load_library().asm_last_error(None).decode())
+    return out.raw[:n].decode("ascii")
 
 
 class Timer:

@@ -124,6 +124,7 @@ struct asm_handle {
     int mapq_model = 0;                   /* asm_map_set_mapq_model: ASM_MAPQ_REFERENCE or ASM_MAPQ_GAP */
     std::vector<uint8_t> last_mapq;       /* asm_map_last_mapq: one byte per record slot of the last in-memory mapping call */
     bool last_mapq_valid = false;
+    unsigned sam_tags = 0;                /* asm_map_set_sam_tags: the optional tags of the file calls' lines (ASM_SAM_TAG_MD) */
     std::vector<hipEvent_t> prof_ev;      /* asm_profile_enable: 8 events per recorded asm_run_benchmark_async call */
     std::vector<unsigned> prof_mask;      /* which of a call's four kernels were launched */
     int prof_cap = 0;

@@ -27,12 +27,15 @@
 // Mapping quality (ASM_MAPQ_GAP only): map_mapq_kernel folds each read's sorted run records into (d1, n1, d2), its MAPQ bytes and,
 //          for the best-hit calls, its best key (they take the run path then, not the atomicMin); map_pair_mapq_kernel folds each
 //          pair's concordant combinations and writes both records' bytes; map_pair_item_mapq_kernel does the secondary pairs.
+// MD tag (the file calls under ASM_SAM_TAG_MD only): map_md_kernel writes every finished item's MD:Z row (the rule: asm_md.h) next
+//          to its record, from the item's CIGAR row, its read and the text.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "asm_bits.h"
 #include "asm_map_core.h"
+#include "asm_md.h"
 
 __global__ __launch_bounds__(256) void map_upper_kernel(char* __restrict__ s, unsigned long long n) {
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
@@ -491,4 +494,43 @@ __global__ __launch_bounds__(256) void map_cost_kernel(const uint32_t* __restric
                                                        MapHit* __restrict__ hits) {
     const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q < nl) hits[list[q]].greedy_cost = cost[q];
+}
+
+/* ---- the MD:Z tag (the rule and the 78-byte bound: asm_md.h) ---- */
+static_assert(MD_MAX_EDITS == MAP_MAX_ERRORS && MAP_MAX_READ <= 999, "the bound on an MD tag rests on the mapper's limits");
+struct MapMdArgs {
+    const char* reads;               /* upper-cased, concatenated */
+    const uint32_t* roff;
+    long n;                          /* items */
+    const uint32_t* iread;           /* per item, its read; NULL: item i is read i */
+    const MapHit* hits;              /* per item */
+    const uint16_t* ops;             /* [n][cap] */
+    const uint8_t* nops;
+    int cap;
+    const char* text;
+    const unsigned long long* seq_off;
+    char* md;                        /* [n][MD_ROW_CAP] */
+    uint8_t* md_len;                 /* per item; 0: unmapped, or more than cap operations (the line's CIGAR is '*') */
+};
+
+/* thread per finished item: the row is written straight into the item's slot (byte stores, at most 78 of them; no private copy),
+ * then its length.  The sink is bounded by the row, and a row that does not consume its read and window exactly, which the finish
+ * kernel never writes, gets length 0. */
+__global__ __launch_bounds__(256) void map_md_kernel(MapMdArgs a) {
+    const long it = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (it >= a.n) return;
+    const MapHit h = a.hits[it];
+    const uint32_t nops = a.nops[it];
+    uint32_t len = 0;
+    if ((h.flags & MAP_F_MAPPED) && nops <= (uint32_t)a.cap) {
+        const long i = a.iread ? (long)a.iread[it] : it;
+        const uint32_t r0 = a.roff[i], m = a.roff[i + 1] - r0, s = h.strand;
+        const char* q = a.reads + r0;
+        MdRowSink o{a.md + (size_t)it * MD_ROW_CAP, (uint32_t)MD_ROW_CAP};
+        const char* w = a.text + a.seq_off[h.seq_id] + h.pos;
+        const bool ok = md_format(a.ops + (size_t)it * a.cap, nops, [&](uint32_t p) { return map_read_byte(q, m, s, p); }, m,
+                                  [&](uint32_t p) { return w[p]; }, h.end - h.pos, o);
+        if (ok && o.cur <= (uint32_t)MD_ROW_CAP) len = o.cur;
+    }
+    a.md_len[it] = (uint8_t)len;
 }

@@ -332,7 +332,7 @@ static int map_file_chunk(MapReadsFileJob& j, const char* d_raw, const uint32_t*
     SamArgs a = {};
     a.raw = d_raw, a.recs = d_recs.p, a.rec_read = d_rec_read.p, a.nrec = (long)rn, a.nlines = (long)nlines;
     a.line_rec = d_lrec.p, a.line_item = d_litem.p;
-    a.mapq = mm.d_item;
+    a.mapq = mm.d_item, a.md = fin.d_md.p, a.md_len = fin.d_md_len.p;
     a.hits = fin.d_hits.p, a.ops = fin.d_ops.p, a.nops = fin.d_nops.p, a.ibase = (j.max_hits > 0 && ns > 0) ? ai.d_ibase.p : nullptr;
     a.n_hits = ai.d_nh.p, a.line_cnt = d_lcnt.p, a.line_base = d_lbase.p;
     /* the line list reads nrec, rec_read, ibase, line_cnt and line_base of a; what the tail sets (names, size, off, n_mapped) it does not */

@@ -263,7 +263,9 @@ struct MapFinish {
     Scratch<MapHit> d_hits;
     Scratch<uint16_t> d_ops;
     Scratch<uint8_t> d_nops;
-    explicit MapFinish(asm_handle* h) : d_dirs(h), d_hits(h), d_ops(h), d_nops(h) {}
+    Scratch<char> d_md;        /* ASM_SAM_TAG_MD, the file calls: the items' MD rows and their lengths (map_finish_device), else NULL */
+    Scratch<uint8_t> d_md_len;
+    explicit MapFinish(asm_handle* h) : d_dirs(h), d_hits(h), d_ops(h), d_nops(h), d_md(h), d_md_len(h) {}
 };
 
 static int map_finish_launch(asm_handle* h, const asm_index* ix, const asm_map_params* p, const MapFront& f, int64_t n,
@@ -336,6 +338,15 @@ static int map_finish_collect(asm_handle* h, const asm_index* ix, const asm_map_
  * bounds the mapped ones' length. */
 static int map_finish_device(asm_handle* h, const asm_index* ix, const asm_map_params* p, const MapFront& f, MapFinish& s) {
     const size_t n = (size_t)s.n;
+    if ((h->sam_tags & ASM_SAM_TAG_MD) && n) { /* the items' MD rows: they need the records' pos, end and strand, not their costs */
+        HIPCHK(h, s.d_md.alloc(n * MD_ROW_CAP));
+        HIPCHK(h, s.d_md_len.alloc(n));
+        MapMdArgs ma = {};
+        ma.reads = f.d_reads.p, ma.roff = f.d_roff.p, ma.n = (long)n, ma.iread = s.d_iread, ma.hits = s.d_hits.p, ma.ops = s.d_ops.p;
+        ma.nops = s.d_nops.p, ma.cap = s.ocap, ma.text = ix->d_text, ma.seq_off = (const unsigned long long*)ix->d_seq_off;
+        ma.md = s.d_md.p, ma.md_len = s.d_md_len.p;
+        HIPCHK(h, launch(h, map_md_kernel, grid_for((int64_t)n), ASM_BLOCK, ma));
+    }
     Scratch<uint32_t> d_flag(h), d_slot(h), d_list(h);
     Scratch<int32_t> d_cost(h);
     MapTmp tmp(h);
@@ -1041,6 +1052,33 @@ int asm_map_set_mapq_model(asm_handle* h, int model) { /* the model is checked f
 }
 
 int asm_map_get_mapq_model(const asm_handle* h) { return h ? h->mapq_model : ASM_MAPQ_REFERENCE; }
+
+static_assert(ASM_MAP_MD_CAP == MD_ROW_CAP, "the ABI's ASM_MAP_MD_CAP is the MD row of asm_md.h");
+
+int asm_map_set_sam_tags(asm_handle* h, unsigned mask) { /* the mask is checked first, so that the check needs no device */
+    if (mask & ~(unsigned)ASM_SAM_TAG_MD) return fail(h, ASM_EINVAL, "asm_map_set_sam_tags: mask may hold ASM_SAM_TAG_MD (1) only");
+    if (!h) return fail(nullptr, ASM_EINVAL, "asm_map_set_sam_tags: NULL handle");
+    h->sam_tags = mask;
+    return ASM_OK;
+}
+
+unsigned asm_map_get_sam_tags(const asm_handle* h) { return h ? h->sam_tags : 0u; }
+
+int asm_md_format(const uint16_t* ops, int nops, const char* read_on_strand, int read_len, const char* ref_window, int ref_len,
+                  char* out, size_t out_cap) {
+    if (nops < 0 || read_len < 0 || ref_len < 0 || (nops > 0 && !ops) || (read_len > 0 && !read_on_strand) || (ref_len > 0 && !ref_window) ||
+        !out)
+        return fail(nullptr, ASM_EINVAL, "asm_md_format: bad arguments");
+    MdRowSink o{out, out_cap > 0x7fffffffull ? 0x7fffffffu : (uint32_t)out_cap}; /* the length is returned as an int */
+    /* upper case on both sides, as the mapper holds its reads and its text */
+    const bool ok = md_format(ops, (uint32_t)nops, [&](uint32_t p) { return sam_upper(read_on_strand[p]); }, (uint32_t)read_len,
+                              [&](uint32_t p) { return sam_upper(ref_window[p]); }, (uint32_t)ref_len, o);
+    if (!ok)
+        return fail(nullptr, ASM_EINVAL, "asm_md_format: the row must hold M, I and D only and consume exactly read_len read and ref_len reference bases");
+    if (o.cur >= o.cap) return fail(nullptr, ASM_EINVAL, "asm_md_format: out_cap is too small");
+    out[o.cur] = 0;
+    return (int)o.cur;
+}
 
 int asm_map_last_mapq(asm_handle* h, uint8_t* dst, int64_t count) {
     if (count < 0) return fail(h, ASM_EINVAL, "asm_map_last_mapq: count must be >= 0");

@@ -82,6 +82,7 @@ static int map_pairs_file_chunk(MapPairsFileJob& j, const char* d_raw, const uin
     SamArgs a = {};
     a.raw = d_raw, a.recs = d_recs.p, a.rec_read = d_rec_read.p, a.nrec = (long)rn, a.nlines = (long)(2 * rn);
     a.hits = fin.d_hits.p, a.ops = fin.d_ops.p, a.nops = fin.d_nops.p, a.mapq = pf.d_mapq.p;
+    a.md = fin.d_md.p, a.md_len = fin.d_md_len.p;
     a.pair_state = pf.d_state.p, a.n_conc = pf.d_nconc.p, a.n_sent = (long)ns;
     unsigned long long n[3] = {0, 0, 0}; /* mapped, proper, rescued */
     if (const int rc = map_file_format<true>(ss, tmp, a, n)) return rc;

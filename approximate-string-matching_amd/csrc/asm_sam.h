@@ -52,6 +52,9 @@ struct SamLine {
     const char* mate_rname;
     uint32_t mate_rname_len;
     uint32_t tlen, n_concordant;   /* max(end) - min(pos) when both mates lie on one sequence, else 0 */
+    /* the MD:Z tag of a mapped line (asm_md.h; asm_map_set_sam_tags); md_len 0: none, and md is not read */
+    const char* md;
+    uint32_t md_len;
 };
 
 enum { SAM_COPY = 0, SAM_UPPER = 1, SAM_REVCOMP = 2, SAM_REVERSE = 3 };
@@ -117,7 +120,7 @@ SAM_HD uint32_t sam_pair_name_len(const char* raw, const SamRec& r) {
     return (n >= 2u && raw[r.name + n - 2u] == '/' && (raw[r.name + n - 1u] == '1' || raw[r.name + n - 1u] == '2')) ? n - 2u : n;
 }
 
-/* QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL [NM XG] [XP] [XR] [NH HI XH]; a single-end line has RNEXT '*', PNEXT 0
+/* QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL [NM XG [MD]] [XP] [XR] [NH HI XH]; a single-end line has RNEXT '*', PNEXT 0
  * and TLEN 0, a paired one borrows RNAME and POS from its mapped mate when it is unmapped itself (write_pairs of host/asm_map.cpp) */
 template <class Sink>
 SAM_HD void sam_format(const SamLine& l, Sink& o) {
@@ -176,6 +179,10 @@ SAM_HD void sam_format(const SamLine& l, Sink& o) {
         sam_int(o, l.dist);
         SAM_LIT(o, "\tXG:i:");
         sam_int(o, l.greedy_cost);
+        if (l.md_len) {
+            SAM_LIT(o, "\tMD:Z:");
+            o.bytes(l.md, l.md_len, SAM_COPY);
+        }
     }
     if (pair && l.proper) {
         SAM_LIT(o, "\tXP:i:");
@@ -229,6 +236,8 @@ struct SamArgs {
     const uint16_t* ops;        /* [items][SAM_CIGAR_CAP] */
     const uint8_t* nops;
     const uint8_t* mapq;        /* per item: its MAPQ byte (ASM_MAPQ_GAP); NULL: the reference model, read off the record's greedy_cost */
+    const char* md;             /* per item: its MD row, [items][MD_ROW_CAP] (map_md_kernel); NULL: the tag is off */
+    const uint8_t* md_len;      /* per item: the row's bytes in use, 0: the line carries no MD */
     const uint32_t* ibase;      /* all hits: first item of every library read (n + 1); NULL: item i is read i */
     const uint32_t* n_hits;     /* all hits: loci per library read, uncapped */
     const char* names;          /* RNAME table: the names back to back */
@@ -292,6 +301,7 @@ __device__ inline SamLine sam_load_pair_line(const SamArgs& a, long l) {
         s.mapq = a.mapq ? (int32_t)a.mapq[ix] : map_mapq_reference(true, h.greedy_cost);
         s.ops = a.ops + (size_t)ix * SAM_CIGAR_CAP, s.nops = a.nops[ix];
         s.rname = a.names + a.name_off[h.seq_id], s.rname_len = a.name_off[h.seq_id + 1] - a.name_off[h.seq_id];
+        if (a.md) s.md = a.md + (size_t)ix * MD_ROW_CAP, s.md_len = a.md_len[ix];
     }
     if (g.flags & MAP_F_MAPPED) {
         s.mate_mapped = 1, s.mate_seq_id = g.seq_id, s.mate_pos = g.pos, s.mate_strand = g.strand;
@@ -312,6 +322,7 @@ __device__ inline SamLine sam_load_line(const SamArgs& a, long l) {
     s.mapq = a.mapq ? (int32_t)a.mapq[it] : map_mapq_reference(true, h.greedy_cost);
     s.ops = a.ops + (size_t)it * SAM_CIGAR_CAP, s.nops = a.nops[it];
     s.rname = a.names + a.name_off[h.seq_id], s.rname_len = a.name_off[h.seq_id + 1] - a.name_off[h.seq_id];
+    if (a.md) s.md = a.md + (size_t)it * MD_ROW_CAP, s.md_len = a.md_len[it];
     if (a.ibase) {
         const int32_t rd = a.rec_read[rec];
         s.all = 1, s.rank = it - a.ibase[rd], s.n_reported = a.ibase[rd + 1] - a.ibase[rd], s.n_hits = a.n_hits[rd];

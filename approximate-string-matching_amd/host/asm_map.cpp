@@ -21,6 +21,10 @@
 // --mapq reference|gap (any mapping mode; default reference) picks the model of column 5 (asm_map_set_mapq_model): reference is
 // min(254, 60 + greedy_cost), gap the repeat- and pair-aware value of docs/design/mapper.md, "Mapping quality".  The streamed modes
 // let the library format it; the others read it with asm_map_last_mapq, so both ways write the same file under either model.
+// --md (any mapping mode) adds MD:Z:<tag> behind XG:i:<n> on every line that shows a CIGAR (docs/design/mapper.md, "MD tag").  The
+// streamed modes set the handle's tag mask (asm_map_set_sam_tags) and the library builds the tag on the device; the others call
+// asm_md_format per record, on the reference window from the text parsed here or, under --ref-stream, from asm_index_get_text.  Both
+// ways write the same file.
 //   asm-map -r ref.fa --bench-ref N [--k 12]
 // maps nothing: it builds the index N times each way, alternately, and prints the seconds of every build.
 // --all-hits N writes up to N loci per read in rank order (asm_map_reads_all, strata S, default e): the primary record as without
@@ -62,6 +66,7 @@ static void usage() {
                     "[--rescue E] [--k 12] [--max-occ N]\n"
                     "       any of them with --ref-stream: the reference is read and parsed by the library\n"
                     "       any of them with --mapq reference|gap: the model of the MAPQ column (default reference)\n"
+                    "       any of them with --md: MD:Z on every line that shows a CIGAR\n"
                     "       any of them with --sort: coordinate-sorted output (--stream, --stream-pairs: on the device, [--sort-mem BYTES])\n");
     exit(2);
 }
@@ -141,8 +146,28 @@ static std::string revcomp(const std::string& q) {
     return o;
 }
 
+/* --md without --stream: "\tMD:Z:<tag>" of one record ("" without --md and for a row of more than cap operations, whose CIGAR
+ * column is '*'); text: the upper-cased reference, parsed here or, under --ref-stream, read back from the index; seq: the read as
+ * the file holds it, upper case */
+struct MdSource {
+    bool on;
+    const std::string* text;
+    const std::vector<uint64_t>* off;
+    std::string tag(const asm_map_hit& hr, const uint16_t* ops, int nn, int cap, const std::string& seq) const {
+        if (!on || nn > cap) return "";
+        char md[ASM_MAP_MD_CAP];
+        const std::string qs = hr.strand ? revcomp(seq) : seq;
+        if (asm_md_format(ops, nn, qs.data(), (int)qs.size(), text->data() + (*off)[(size_t)hr.seq_id] + hr.pos, (int)(hr.end - hr.pos), md,
+                          sizeof md) < 0) {
+            fprintf(stderr, "asm-map: %s\n", asm_last_error(nullptr));
+            exit(1);
+        }
+        return std::string("\tMD:Z:") + md;
+    }
+};
+
 static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vector<std::string>& names, ReadFile& f1, ReadFile& f2,
-                       const asm_map_params& p, const asm_pair_params& pp, long chunk, int all_hits, int strata) {
+                       const asm_map_params& p, const asm_pair_params& pp, long chunk, int all_hits, int strata, const MdSource& mds) {
     const int cap = 64;
     const int slots = all_hits ? all_hits : 1; /* pairs per fragment in the library's output */
     std::vector<Record> a, b;
@@ -228,6 +253,7 @@ static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vecto
                 char cigar[4096];
                 strcpy(cigar, "*");
                 int mapq = 0;
+                std::string md;
                 if (mapped[x]) {
                     if (m.strand) {
                         seq = revcomp(rec[x]->seq);
@@ -237,12 +263,13 @@ static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vecto
                     const int nn = nops[o];
                     if (asm_cigar_format(&ops[o * cap], nn, cap, cigar, sizeof(cigar)) != 0 || nn > cap) strcpy(cigar, "*");
                     mapq = mq[o];
+                    md = mds.tag(m, &ops[o * cap], nn, cap, rec[x]->seq);
                 }
                 const char* rnext = !mapped[y] ? "*" : rid[y] == rid[x] ? "=" : names[(size_t)rid[y]].c_str();
                 fprintf(out, "%s\t%d\t%s\t%lld\t%d\t%s\t%s\t%lld\t%lld\t%s\t%s", pair_name(rec[x]->name).c_str(), flag,
                         rid[x] < 0 ? "*" : names[(size_t)rid[x]].c_str(), pos[x], mapq, cigar, rnext, pos[y], x == plus ? tl : -tl,
                         seq.empty() ? "*" : seq.c_str(), qual.empty() ? "*" : qual.c_str());
-                if (mapped[x]) fprintf(out, "\tNM:i:%d\tXG:i:%d", (int)m.dist, m.greedy_cost);
+                if (mapped[x]) fprintf(out, "\tNM:i:%d\tXG:i:%d%s", (int)m.dist, m.greedy_cost, md.c_str());
                 if (proper) fprintf(out, "\tXP:i:%u", nconc[(size_t)slot[q]]);
                 if (m.flags & ASM_MAP_RESCUED) {
                     fprintf(out, "\tXR:i:1");
@@ -265,9 +292,10 @@ static int write_pairs(FILE* out, asm_handle* h, asm_index* ix, const std::vecto
                     const int nn = nops[o + x];
                     if (asm_cigar_format(&ops[(o + x) * cap], nn, cap, cigar, sizeof(cigar)) != 0 || nn > cap) strcpy(cigar, "*");
                     const int mapq = mq[o + x];
-                    fprintf(out, "%s\t%d\t%s\t%u\t%d\t%s\t=\t%u\t%lld\t*\t*\tNM:i:%d\tXG:i:%d\tNH:i:%u\tHI:i:%u\tXH:i:%u\n",
+                    fprintf(out, "%s\t%d\t%s\t%u\t%d\t%s\t=\t%u\t%lld\t*\t*\tNM:i:%d\tXG:i:%d%s\tNH:i:%u\tHI:i:%u\tXH:i:%u\n",
                             pair_name(rec[x]->name).c_str(), flag, names[(size_t)m.seq_id].c_str(), m.pos + 1, mapq, cigar,
-                            sr[1 - x]->pos + 1, x == splus ? stl : -stl, (int)m.dist, m.greedy_cost, nrep, t + 1, nh);
+                            sr[1 - x]->pos + 1, x == splus ? stl : -stl, (int)m.dist, m.greedy_cost,
+                            mds.tag(m, &ops[(o + x) * cap], nn, cap, rec[x]->seq).c_str(), nrep, t + 1, nh);
                 }
             }
         }
@@ -401,7 +429,7 @@ int main(int argc, char** argv) {
     int k = 12;
     long chunk = 262144;
     int all_hits = 0, strata = -1; /* all_hits 0: the best hit only */
-    bool stream = false, stream_pairs = false, ref_stream = false, sort = false;
+    bool stream = false, stream_pairs = false, ref_stream = false, sort = false, md = false;
     int bench_ref = 0;
     long long chunk_bytes = 0, sort_mem = -1;
     int mapq_model = ASM_MAPQ_REFERENCE;
@@ -433,6 +461,7 @@ int main(int argc, char** argv) {
         else if (s == "--bench-ref") bench_ref = atoi(val());
         else if (s == "--chunk-bytes") chunk_bytes = atoll(val());
         else if (s == "--sort") sort = true;
+        else if (s == "--md") md = true;
         else if (s == "--mapq") {
             const std::string m = val();
             if (m != "reference" && m != "gap") usage();
@@ -514,6 +543,7 @@ int main(int argc, char** argv) {
     asm_index* ix = nullptr;
     int rc = asm_create(&h, 0);
     if (!rc) rc = asm_map_set_mapq_model(h, mapq_model);
+    if (!rc && md && (stream || stream_pairs)) rc = asm_map_set_sam_tags(h, ASM_SAM_TAG_MD);
     if (!rc)
         rc = ref_stream ? asm_index_build_file(h, ref_path.c_str(), k, 0, &ix, nullptr)
                         : asm_index_build(h, text.data(), off.data(), (int32_t)names.size(), k, &ix);
@@ -571,6 +601,14 @@ int main(int argc, char** argv) {
         return 0;
     }
     fputs(header.c_str(), file);
+    if (md && ref_stream) { /* the index holds the only copy of the text */
+        text.resize((size_t)off.back());
+        if (asm_index_get_text(h, ix, 0, off.back(), &text[0])) {
+            fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
+            return 1;
+        }
+    }
+    const MdSource mds = {md, &text, &off};
     if (paired) {
         FILE* rf2 = fopen(read2_path.c_str(), "r");
         if (!rf2) {
@@ -584,7 +622,7 @@ int main(int argc, char** argv) {
             reads2.fasta = c == '>';
             if (c != EOF) ungetc(c, rf2);
         }
-        rc = finish_output(write_pairs(out, h, ix, names, reads, reads2, p, pp, chunk, all_hits, strata));
+        rc = finish_output(write_pairs(out, h, ix, names, reads, reads2, p, pp, chunk, all_hits, strata, mds));
         fclose(rf);
         fclose(rf2);
         asm_index_free(h, ix);
@@ -661,9 +699,10 @@ int main(int argc, char** argv) {
                 const int nn = nops[o];
                 if (asm_cigar_format(&ops[o * cap], nn, cap, cigar, sizeof(cigar)) != 0 || nn > cap) strcpy(cigar, "*");
                 const int mapq = mq[o];
-                fprintf(out, "%s\t%d\t%s\t%u\t%d\t%s\t*\t0\t0\t%s\t%s\tNM:i:%d\tXG:i:%d", rec.name.c_str(),
+                fprintf(out, "%s\t%d\t%s\t%u\t%d\t%s\t*\t0\t0\t%s\t%s\tNM:i:%d\tXG:i:%d%s", rec.name.c_str(),
                         (hr.strand ? 16 : 0) | (t ? 256 : 0), names[(size_t)hr.seq_id].c_str(), hr.pos + 1, mapq, cigar,
-                        t ? "*" : seq.c_str(), t || qual.empty() ? "*" : qual.c_str(), (int)hr.dist, hr.greedy_cost);
+                        t ? "*" : seq.c_str(), t || qual.empty() ? "*" : qual.c_str(), (int)hr.dist, hr.greedy_cost,
+                        mds.tag(hr, &ops[o * cap], nn, cap, rec.seq).c_str());
                 if (all_hits) fprintf(out, "\tNH:i:%u\tHI:i:%u\tXH:i:%u", nrep, t + 1, nh);
                 fputc('\n', out);
             }

@@ -460,6 +460,30 @@ int asm_map_set_mapq_model(asm_handle* h, int model);
 int asm_map_get_mapq_model(const asm_handle* h);
 int asm_map_last_mapq(asm_handle* h, uint8_t* dst /* [count] */, int64_t count);
 
+/* Optional SAM tags (docs/design/mapper.md, "MD tag"): a mask on the handle, like the MAPQ model; 0 (the default) leaves every byte
+ * of every call as it is.  The four file calls (asm_map_file, asm_map_pairs_file and their _sorted forms) honour it.
+ * ASM_SAM_TAG_MD:  every line that shows a CIGAR carries MD:Z:<tag> directly behind XG:i:<n>: primaries, secondaries (SEQ '*'), both
+ *                  mates, rescued mates.  A line whose CIGAR is '*' carries none: unmapped lines, an unmapped mate that borrows
+ *                  RNAME and POS, a row of more than 64 operations.  The tag walks the CIGAR over the read on the alignment's
+ *                  strand against T_r[pos, end) under the byte rule above (N against N mismatches): a number for every run of
+ *                  matches (0 included), the reference byte of a mismatch, '^' and the reference bytes of a deletion; insertions
+ *                  write nothing.  Reference bytes as the upper-cased text holds them, a byte outside A-Z as 'N'.  Letters in the
+ *                  tag plus inserted bases of the CIGAR = dist (NM).  At most 78 bytes (15 single-base deletions, 16 three-digit
+ *                  numbers); ASM_MAP_MD_CAP is the row a tag and its NUL always fit.  The tag is built on the device.
+ * asm_map_set_sam_tags: a mask with any other bit, or a NULL handle, is ASM_EINVAL; the mask is checked first.
+ * asm_md_format:   the same rule on the host, no device: the counterpart of asm_cigar_format for the in-memory calls, whose record
+ *                  slots carry no MD.  ops[0, nops) is a CIGAR row (count << 3 | op; M, I and D only), read_on_strand the read as
+ *                  the alignment sees it (the reverse complement for strand 1), ref_window T_r[pos, end), e.g. from
+ *                  asm_index_get_text; both are upper-cased here.  Returns the tag's length, out NUL-terminated.  ASM_EINVAL: a
+ *                  NULL argument, a negative length, a row with another operation or one that does not consume exactly read_len
+ *                  read and ref_len reference bases, or out_cap below the tag's length + 1; nothing is written beyond out_cap. */
+#define ASM_SAM_TAG_MD 1
+#define ASM_MAP_MD_CAP 80
+int asm_map_set_sam_tags(asm_handle* h, unsigned mask);
+unsigned asm_map_get_sam_tags(const asm_handle* h);
+int asm_md_format(const uint16_t* ops, int nops, const char* read_on_strand, int read_len, const char* ref_window, int ref_len,
+                  char* out, size_t out_cap);
+
 /* asm_map_file:    a FASTQ file in, a SAM file out (docs/design/mapper.md, "Files: FASTQ in, SAM out"); single-end, synchronous.  The
  *                  file is read in chunks of about chunk_bytes (0: 16 MiB) cut at record boundaries; a chunk is parsed, mapped
  *                  and formatted on the device while the next one is read and copied in and the one before is copied out and

@@ -1,6 +1,6 @@
 """File-to-file read mapping timings (development tool):
 PYTHONPATH=. python tools/bench_map_file.py --dir DIR [--ref-len 5e6] [--reads 1e6] [--len 100] [--errors 2] [--all-hits N]
-[--reps 3] [--chunk-bytes N] [--profile] [--paired [--insert 200,500] [--rescue E]] [--sort] [--exe PATH] [--mapq reference|gap]
+[--reps 3] [--chunk-bytes N] [--profile] [--paired [--insert 200,500] [--rescue E]] [--sort] [--exe PATH] [--mapq reference|gap] [--md]
 Writes the workload of tools/bench_map.py as files into DIR (seeded: a reference of --ref-len bases as ref.fa and --reads reads of
 --len bases with qualities as reads.fq), then runs `asm-map` and `asm-map --stream` on them alternately, --reps times each, in this
 one call.  For every run: the wall clock of the whole process (reference parsing and index build included, the same in both) and,
@@ -18,6 +18,8 @@ many bytes as the gather kernel moves is timed with events, the yardstick for th
 `asm-map --stream --sort`, whose kernel totals hold the sort's split (radix sort, scan, sam_line_gather_kernel).
 --mapq gap runs every leg under ASM_MAPQ_GAP (asm-map --mapq gap, Engine.set_mapq_model): the price of the repeat- and pair-aware
 MAPQ, whose best-hit calls take the runs path.  The default passes no option, so that --exe may name an older asm-map.
+--md runs every leg with the MD:Z tag (asm-map --md, Engine.set_sam_tags): the price of the tag, which map_md_kernel builds on the
+device in the streamed legs and asm_md_format on the host in the others.  The default passes no option, as for --mapq.
 --exe PATH runs another build's asm-map in the tool legs (for a comparison of two builds on the same files)."""
 import argparse
 import csv
@@ -97,6 +99,8 @@ def sort_leg(a, fqs, result):
 
     eng = m.Engine(0)
     eng.set_mapq_model(a.mapq)
+    if a.md:
+        eng.set_sam_tags(md=True)
     ref, _ = make_inputs(int(a.ref_len), 1, a.len, a.errors, seed=1234)
     ix = eng.build_index([ref.tobytes().decode()], k=12)
     sams = [os.path.join(a.dir, "lib_unsorted.sam"), os.path.join(a.dir, "lib_sorted.sam")]
@@ -165,6 +169,7 @@ def main():
     ap.add_argument("--sort", action="store_true", help="the sorted library call against the unsorted one; with --profile: asm-map --stream --sort")
     ap.add_argument("--exe", default=EXE, help="the asm-map to run in the tool legs")
     ap.add_argument("--mapq", choices=["reference", "gap"], default="reference", help="the MAPQ model of every leg")
+    ap.add_argument("--md", action="store_true", help="MD:Z on every leg")
     a = ap.parse_args()
     os.makedirs(a.dir, exist_ok=True)
     fa, fqs = write_files(a, a.errors)
@@ -180,6 +185,8 @@ def main():
         base = [a.exe, "-r", fa, "-q", fqs[0]] + flags
     if a.mapq != "reference":
         base += ["--mapq", a.mapq]
+    if a.md:
+        base += ["--md"]
     stream = ["--stream-pairs" if a.paired else "--stream"] + (["--chunk-bytes", str(a.chunk_bytes)] if a.chunk_bytes else [])
     if a.sort and a.profile:
         stream.append("--sort")
@@ -197,7 +204,7 @@ def main():
                 print("  %-60s calls %6s total %10.3f ms  avg %9.1f us" % (r["Name"][:60], r["Calls"], float(r["TotalDurationNs"]) / 1e6,
                                                                            float(r["AverageNs"]) / 1e3))
         return
-    result = {"mapq": a.mapq, "reads": int(a.reads), "len": a.len, "ref_len": int(a.ref_len), "errors": a.errors, "all_hits": a.all_hits,
+    result = {"mapq": a.mapq, "md": a.md, "reads": int(a.reads), "len": a.len, "ref_len": int(a.ref_len), "errors": a.errors, "all_hits": a.all_hits,
               "paired": a.paired, "insert": a.insert if a.paired else None, "rescue": a.rescue if a.paired else None,
               "fastq_bytes": sum(os.path.getsize(fq) for fq in fqs), "page_cache": True, "pairs": []}
     if a.sort:
@@ -223,6 +230,8 @@ def main():
 
         eng = m.Engine(0)
         eng.set_mapq_model(a.mapq)
+        if a.md:
+            eng.set_sam_tags(md=True)
         ref, _ = make_inputs(int(a.ref_len), 1, a.len, a.errors, seed=1234)
         ix = eng.build_index([ref.tobytes().decode()], k=12)
         lo, hi = (int(v) for v in a.insert.split(","))
