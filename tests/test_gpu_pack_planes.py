@@ -1,6 +1,6 @@
 """pack_kernel's output read back bit for bit: the uint4[4][w4][bn] bucketed planes and the lens words, against a numpy packer
 written from the rule (A=00 C=01 G=10 T=11; any byte other than exactly 'C', 'G', 'T' is 00; bits at and beyond a string's
-length are 0).  Clean mode only: the sequential-mode tails are checked through Greedy in test_gpu_parity.py."""
+length are 0).  Clean mode only: the sequential-mode tails are read back the same way in test_gpu_tail_planes.py."""
 import numpy as np
 import pytest
 
