@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/asm_mi355x.h"
+#include "asm_launch.h"
 #include "asm_host.h"
 #include "asm_kernels.h"
 #include "asm_greedy3_kernel.h"
@@ -228,6 +229,17 @@ struct Scratch {
     hipError_t alloc(size_t bytes) { return pool_alloc(h, (void**)&p, bytes); }
 };
 
+/* ... and a call-scoped block from big_malloc, outside the pool: freed when it goes out of scope. */
+template <typename T>
+struct BigScratch {
+    T* p = nullptr;
+    BigScratch() = default;
+    BigScratch(const BigScratch&) = delete;
+    BigScratch& operator=(const BigScratch&) = delete;
+    ~BigScratch() { (void)hipFree(p); }
+    hipError_t alloc(asm_handle* h, size_t bytes) { return big_malloc(h, (void**)&p, bytes); }
+};
+
 /* One width class of a batch: pairs whose longer string needs `w4` granules of 128 positions. */
 struct asm_bucket {
     int64_t n = 0;
@@ -302,6 +314,17 @@ static int fail(asm_handle* h, int code, const std::string& msg) {
                         std::string(#call) + ": " + hipGetErrorString(_e));                       \
         }                                                                                         \
     } while (0)
+
+/* A kernel launch on the handle's stream (launch_on, asm_launch.h) and its error: one expression for HIPCHK / STREAM_TRY.  The
+ * stream is always h->stream: the step scheduler reaches its other streams by borrowing that (StreamBorrow, asm_step.h). */
+template <class... P, class... A>
+static hipError_t launch_lds(asm_handle* h, void (*kernel)(P...), unsigned grid, unsigned block, size_t lds, A&&... args) {
+    return launch_on(h->stream, kernel, grid, block, lds, std::forward<A>(args)...);
+}
+template <class... P, class... A>
+static hipError_t launch(asm_handle* h, void (*kernel)(P...), unsigned grid, unsigned block, A&&... args) {
+    return launch_on(h->stream, kernel, grid, block, 0, std::forward<A>(args)...);
+}
 
 /* The only place that frees a batch's device blocks (its owner is live). */
 static void batch_release(asm_batch* b) {
@@ -406,8 +429,7 @@ static hipError_t launch_persistent(asm_handle* h, Kern kern, int64_t n, Args...
     int64_t blocks = (int64_t)per_cu * h->num_cus;
     const int64_t need = (n + ASM_BLOCK - 1) / ASM_BLOCK;
     if (blocks > need) blocks = need;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, h->stream, args...);
-    return hipGetLastError();
+    return launch(h, kern, (unsigned)blocks, ASM_BLOCK, args...);
 }
 
 #ifdef GREEDY_DIAG
@@ -457,19 +479,12 @@ static hipError_t launch_greedy_fast(asm_handle* h, const asm_bucket& b, const G
      * end: stand-alone 1 / 2 / 3 waves take 130 / 118 / 107 us, inside asm_run_benchmark_async's overlapped step 0.234 / 0.227 /
      * 0.244 ms per step (1.5 and 2.5 waves: 0.237, —).  The other instantiations were removed in round 4 (last in 312851a). */
     constexpr int NT = G3_THREADS;
-    auto kern = greedy_fast_kernel<K, NT>;
-    const size_t lds = g3_lds_bytes(K, NT);
-    { /* more than 64 KB of dynamic LDS has to be asked for */
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    int64_t blocks = h->num_cus; /* one workgroup per CU (LDS) */
+    int64_t blocks = h->num_cus; /* one workgroup per CU (LDS: the table alone is 33 KB, with the lane vectors above 64 KB at every K) */
     const int64_t need = (b.n + NT - 1) / NT;
     if (blocks > need) blocks = need;
     const G3Sig sig = {ga.sig_match, ga.sig_mismatch, ga.sig_indel};
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NT), lds, h->stream, (const uint4*)b.planes, (const uint32_t*)b.lens,
-                       (long)b.n, b.w4, sig, h->d_g3_table, out, cig, h->refill_greedy);
-    return hipGetLastError();
+    return launch_lds(h, greedy_fast_kernel<K, NT>, (unsigned)blocks, NT, g3_lds_bytes(K, NT), (const uint4*)b.planes,
+                      (const uint32_t*)b.lens, (long)b.n, b.w4, sig, h->d_g3_table, out, cig, h->refill_greedy);
 }
 
 /* Thread-per-pair Greedy, k <= 16: the straight-line integer-key kernel for the benchmark's own configuration (k <= 3, unit
@@ -496,43 +511,35 @@ static hipError_t launch_greedy(asm_handle* h, const asm_bucket& b, const Greedy
                               0.180 at C2, but 0.120 against 0.104 at C4's 2.5 % errors, where four threads per pair have little to do) */
 template <int K, int W64>
 static hipError_t launch_leap_unit_w(asm_handle* h, const asm_bucket& b, OutMap out, const int32_t* hint) {
-    if (hint && h->leap_hint) {
-        const unsigned blocks = (unsigned)((b.n + LEAP_HINT_PAIRS - 1) / LEAP_HINT_PAIRS);
-        hipLaunchKernelGGL((leap_unit_hint_kernel<K, W64>), dim3(blocks), dim3(ASM_BLOCK), 0, h->stream, b.planes, b.lens,
-                           (long)b.n, b.w4, out, hint);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL((leap_unit_kernel<K, W64>), dim3(grid_for(b.n)), dim3(ASM_BLOCK), 0, h->stream, b.planes, b.lens,
-                       (long)b.n, b.w4, out);
-    return hipGetLastError();
+    if (hint && h->leap_hint)
+        return launch(h, leap_unit_hint_kernel<K, W64>, (unsigned)((b.n + LEAP_HINT_PAIRS - 1) / LEAP_HINT_PAIRS), ASM_BLOCK, b.planes,
+                      b.lens, (long)b.n, b.w4, out, hint);
+    return launch(h, leap_unit_kernel<K, W64>, grid_for(b.n), ASM_BLOCK, b.planes, b.lens, (long)b.n, b.w4, out);
 }
 
 template <int K, int W64>
 static hipError_t launch_leap_general_w(asm_handle* h, const asm_bucket& b, const asm_params* p, OutMap out) {
-    const dim3 grid((unsigned)((b.n + LEAP_GEN_THREADS - 1) / LEAP_GEN_THREADS)), block(LEAP_GEN_THREADS);
+    const unsigned grid = (unsigned)((b.n + LEAP_GEN_THREADS - 1) / LEAP_GEN_THREADS);
     const RingGeometry rg(p->x, p->o, p->e);
     /* bytes (every stored position + 2 fits) halve the LDS and double the waves per CU, but four threads then write into one
      * dword: worth it only where shorts would leave the CU underfilled */
     const bool bytes = b.maxlen + 4 <= 255 && rg.lds_bytes(2 * K + 1, LEAP_GEN_THREADS, 2) > 20 * 1024;
-    if (bytes)
-        hipLaunchKernelGGL((leap_general_kernel<K, W64, uint8_t>), grid, block, rg.lds_bytes(2 * K + 1, LEAP_GEN_THREADS, 1), h->stream,
-                           b.planes, b.lens, (long)b.n, b.w4, (int)p->x, (int)p->o, (int)p->e, rg.gm, rg.gi, out);
-    else
-        hipLaunchKernelGGL((leap_general_kernel<K, W64, uint16_t>), grid, block, rg.lds_bytes(2 * K + 1, LEAP_GEN_THREADS, 2), h->stream,
-                           b.planes, b.lens, (long)b.n, b.w4, (int)p->x, (int)p->o, (int)p->e, rg.gm, rg.gi, out);
-    return hipGetLastError();
+    const auto go = [&](auto kernel, size_t entry_bytes) {
+        return launch_lds(h, kernel, grid, LEAP_GEN_THREADS, rg.lds_bytes(2 * K + 1, LEAP_GEN_THREADS, entry_bytes), b.planes, b.lens,
+                          (long)b.n, b.w4, (int)p->x, (int)p->o, (int)p->e, rg.gm, rg.gi, out);
+    };
+    return bytes ? go(leap_general_kernel<K, W64, uint8_t>, 1) : go(leap_general_kernel<K, W64, uint16_t>, 2);
 }
 
 /* Affine NW: banded wavefront pass (|d| <= 7), a second one with |d| <= 15 over the pairs the first could not settle
  * (strings up to 128 only), then the full-matrix kernel over what is left.  Two todo lists of n + 1 words each. */
 template <int K, int W64, typename EnT>
-static void launch_nw_wfa_pass(asm_handle* h, const asm_bucket& b, const asm_params* p, OutMap out, const uint32_t* in_list,
-                               const uint32_t* in_count, uint32_t* todo, uint32_t* todo_count) {
+static hipError_t launch_nw_wfa_pass(asm_handle* h, const asm_bucket& b, const asm_params* p, OutMap out, const uint32_t* in_list,
+                                     const uint32_t* in_count, uint32_t* todo, uint32_t* todo_count) {
     const WfaRings rg(p->x, p->o, p->e);
-    const dim3 grid((unsigned)((b.n + LEAP_GEN_THREADS - 1) / LEAP_GEN_THREADS)), block(LEAP_GEN_THREADS);
-    hipLaunchKernelGGL((nw_wfa_kernel<K, W64, EnT, false>), grid, block, rg.lds_bytes(2 * K + 1, LEAP_GEN_THREADS, sizeof(EnT)),
-                       h->stream, b.planes, b.lens, (long)b.n, b.w4, (int)p->x, (int)p->o, (int)p->e, rg.gm, rg.gi, out, in_list,
-                       in_count, todo, todo_count);
+    return launch_lds(h, nw_wfa_kernel<K, W64, EnT, false>, (unsigned)((b.n + LEAP_GEN_THREADS - 1) / LEAP_GEN_THREADS), LEAP_GEN_THREADS,
+                      rg.lds_bytes(2 * K + 1, LEAP_GEN_THREADS, sizeof(EnT)), b.planes, b.lens, (long)b.n, b.w4, (int)p->x, (int)p->o,
+                      (int)p->e, rg.gm, rg.gi, out, in_list, in_count, todo, todo_count);
 }
 
 template <int W64, int MAXROWS>
@@ -546,27 +553,24 @@ static int launch_nw_wfa(asm_handle* h, const asm_bucket& b, const asm_params* p
     bool bytes = false; /* strings up to 128: every stored position + 2 fits a byte, half the LDS */
     if constexpr (W64 == 2) {
         bytes = true;
-        launch_nw_wfa_pass<NW_WFA_K, 2, uint8_t>(h, b, p, out, nullptr, nullptr, list_a + 1, list_a);
+        HIPCHK(h, (launch_nw_wfa_pass<NW_WFA_K, 2, uint8_t>(h, b, p, out, nullptr, nullptr, list_a + 1, list_a)));
     }
-    if (!bytes) launch_nw_wfa_pass<NW_WFA_K, W64, uint16_t>(h, b, p, out, nullptr, nullptr, list_a + 1, list_a);
+    if (!bytes) HIPCHK(h, (launch_nw_wfa_pass<NW_WFA_K, W64, uint16_t>(h, b, p, out, nullptr, nullptr, list_a + 1, list_a)));
     const uint32_t* rest = list_a;
     const size_t en = b.maxlen + 2 <= 255 ? 1 : 2;
     if (nw_oct_lds(2 * W64, NW_WFA_K2, rg.gm, rg.gi, en) <= 64 * 1024) {
         /* the unsettled percent or two: eight threads per pair, |d| <= 15 (asm_wave.h) */
-        const dim3 grid((unsigned)std::min<int64_t>((b.n + NW_OCT_PAIRS - 1) / NW_OCT_PAIRS, (int64_t)h->num_cus * 16));
-        if (en == 1)
-            hipLaunchKernelGGL((nw_oct_kernel<2 * W64, uint8_t>), grid, dim3(NW_OCT_THREADS), nw_oct_lds(2 * W64, NW_WFA_K2, rg.gm, rg.gi, 1),
-                               h->stream, b.planes, b.lens, (long)b.n, b.w4, NW_WFA_K2, (int)p->x, (int)p->o, (int)p->e, rg.gm, rg.gi, out,
-                               (const uint32_t*)(list_a + 1), (const uint32_t*)list_a, list_b + 1, list_b);
-        else
-            hipLaunchKernelGGL((nw_oct_kernel<2 * W64, uint16_t>), grid, dim3(NW_OCT_THREADS), nw_oct_lds(2 * W64, NW_WFA_K2, rg.gm, rg.gi, 2),
-                               h->stream, b.planes, b.lens, (long)b.n, b.w4, NW_WFA_K2, (int)p->x, (int)p->o, (int)p->e, rg.gm, rg.gi, out,
-                               (const uint32_t*)(list_a + 1), (const uint32_t*)list_a, list_b + 1, list_b);
+        const unsigned grid = (unsigned)std::min<int64_t>((b.n + NW_OCT_PAIRS - 1) / NW_OCT_PAIRS, (int64_t)h->num_cus * 16);
+        const auto oct = [&](auto kernel) {
+            return launch_lds(h, kernel, grid, NW_OCT_THREADS, nw_oct_lds(2 * W64, NW_WFA_K2, rg.gm, rg.gi, en), b.planes, b.lens,
+                              (long)b.n, b.w4, NW_WFA_K2, (int)p->x, (int)p->o, (int)p->e, rg.gm, rg.gi, out, list_a + 1, list_a,
+                              list_b + 1, list_b);
+        };
+        HIPCHK(h, en == 1 ? oct(nw_oct_kernel<2 * W64, uint8_t>) : oct(nw_oct_kernel<2 * W64, uint16_t>));
         rest = list_b;
     }
-    hipLaunchKernelGGL((nw_affine_kernel<W64, MAXROWS>), dim3((unsigned)((b.n + 63) / 64)), dim3(64), 0, h->stream, b.planes,
-                       b.lens, (long)b.n, b.w4, (int)p->x, (int)p->o, (int)p->e, out, rest + 1, rest);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, nw_affine_kernel<W64, MAXROWS>, (unsigned)((b.n + 63) / 64), 64, b.planes, b.lens, (long)b.n, b.w4, (int)p->x,
+                     (int)p->o, (int)p->e, out, rest + 1, rest));
     return ASM_OK;
 }
 
@@ -596,28 +600,25 @@ static int cover_full_matrix(asm_handle* h, const asm_bucket& b, const asm_param
     int64_t chunk = (int64_t)((size_t)(6ull << 30) / per_pair);
     chunk = chunk < 64 ? 64 : chunk;
     chunk = chunk > count ? count : chunk;
-    uint32_t* d_scratch = nullptr;
-    HIPCHK(h, big_malloc(h, (void**)&d_scratch, per_pair * (size_t)chunk));
-    int rc = ASM_OK;
-    for (int64_t lo = 0; lo < count && !rc; lo += chunk) {
+    BigScratch<uint32_t> d_scratch;
+    HIPCHK(h, d_scratch.alloc(h, per_pair * (size_t)chunk));
+    for (int64_t lo = 0; lo < count; lo += chunk) {
         const int64_t c = count - lo < chunk ? count - lo : chunk;
-        const dim3 grid((unsigned)((c + 63) / 64)), block(64);
         /* without a list the chunk is a contiguous run of slots: shift the base pointers like cover_bucket does */
         const uint4* pl = d_list ? planes : planes + lo;
         const uint32_t* ln = d_list ? lens : lens + lo;
         const uint32_t* od = (d_list || !order) ? order : order + lo;
         const long base = d_list ? slice_lo : slice_lo + lo;
         const uint32_t* list = d_list ? d_list + lo : nullptr;
-        with_const_of<2, 4, 8>((b.maxlen + 63) / 64, [&](auto w) { /* 64-bit words per string; rows = positions they hold */
+        const hipError_t e = with_const_of<2, 4, 8>((b.maxlen + 63) / 64, [&](auto w) { /* 64-bit words per string; rows = positions they hold */
             constexpr int W64 = decltype(w)::value;
-            hipLaunchKernelGGL((nw_trace_affine_kernel<W64, 64 * W64>), grid, block, 0, h->stream, pl, ln, (long)c, (long)b.n, b.w4,
-                               (int)p->x, (int)p->o, (int)p->e, d_scratch, cols8, list, od, base, ca);
+            return launch(h, nw_trace_affine_kernel<W64, 64 * W64>, (unsigned)((c + 63) / 64), 64, pl, ln, (long)c, (long)b.n, b.w4,
+                          (int)p->x, (int)p->o, (int)p->e, d_scratch.p, cols8, list, od, base, ca);
         });
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
-            rc = fail(h, ASM_ENODEVICE, "asm_coverage: full-matrix traceback kernel failed");
+        if (e != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
+            return fail(h, ASM_ENODEVICE, "asm_coverage: full-matrix traceback kernel failed");
     }
-    (void)hipFree(d_scratch);
-    return rc;
+    return ASM_OK;
 }
 
 /* forward sweep + traceback/coverage for one width class with window W; pairs the band cannot answer go through the
@@ -630,57 +631,46 @@ static int cover_bucket(asm_handle* h, const asm_bucket& b, const asm_params* p,
     const int64_t cols = b.maxlen > 0 ? b.maxlen : 1;
     int64_t slice = (int64_t)(6ll << 30) / (cols * (int64_t)sizeof(Cell));
     slice = slice > b.n ? b.n : (slice < 4096 ? 4096 : slice);
-    int rc = grow_device(h, h->d_todo, h->todo_cap, (size_t)slice + 1);
-    if (rc) return rc;
-    Cell* d_trace = nullptr;
-    int32_t* d_band = nullptr;
-    HIPCHK(h, big_malloc(h, (void**)&d_trace, (size_t)cols * (size_t)slice * sizeof(Cell)));
-    if (big_malloc(h, (void**)&d_band, sizeof(int32_t) * (size_t)slice) != hipSuccess) {
-        (void)hipFree(d_trace);
-        return fail(h, ASM_ENOMEM, "asm_coverage: hipMalloc failed");
-    }
-    for (int64_t lo = 0; lo < b.n && !rc; lo += slice) {
+    if (const int rc = grow_device(h, h->d_todo, h->todo_cap, (size_t)slice + 1)) return rc;
+    BigScratch<Cell> d_trace;
+    BigScratch<int32_t> d_band;
+    HIPCHK(h, d_trace.alloc(h, (size_t)cols * (size_t)slice * sizeof(Cell)));
+    if (d_band.alloc(h, sizeof(int32_t) * (size_t)slice) != hipSuccess) return fail(h, ASM_ENOMEM, "asm_coverage: hipMalloc failed");
+    for (int64_t lo = 0; lo < b.n; lo += slice) {
         const int64_t cnt = b.n - lo < slice ? b.n - lo : slice;
         // a slice is addressed as a sub-batch: plane rows keep the bucket's stride, so pass shifted base pointers
         const uint4* planes = b.planes + lo;
         const uint32_t* lens = b.lens + lo;
         const uint32_t* order = b.order ? b.order + lo : nullptr;
         uint32_t todo_count = 0;
-        if (hipMemsetAsync(h->d_todo, 0, sizeof(uint32_t), h->stream) != hipSuccess) rc = fail(h, ASM_ENODEVICE, "asm_coverage: memset failed");
+        if (hipMemsetAsync(h->d_todo, 0, sizeof(uint32_t), h->stream) != hipSuccess) return fail(h, ASM_ENODEVICE, "asm_coverage: memset failed");
         // the kernels index planes as [(p*w4+g)*n + i] with n = pairs of the BUCKET: use dedicated strided variants
-        hipLaunchKernelGGL((nw_trace_forward_kernel<ND, W>), dim3(grid_for(cnt)), dim3(ASM_BLOCK), 0, h->stream, planes, lens,
-                           (long)cnt, (long)b.n, b.w4, d_trace, d_band);
-        hipLaunchKernelGGL((nw_trace_cover_kernel<ND / 2, W>), dim3(grid_for(cnt)), dim3(ASM_BLOCK), 0, h->stream, planes, lens,
-                           (long)cnt, (long)b.n, b.w4, (const Cell*)d_trace, (const int32_t*)d_band, order, lo, ca, h->d_todo + 1,
-                           h->d_todo);
-        if (!rc && (hipGetLastError() != hipSuccess ||
-                    hipMemcpyAsync(&todo_count, h->d_todo, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                    hipStreamSynchronize(h->stream) != hipSuccess))
-            rc = fail(h, ASM_ENODEVICE, "asm_coverage: kernel failed");
-        if (!rc && todo_count) rc = cover_full_matrix(h, b, p, planes, lens, order, lo, h->d_todo + 1, (int64_t)todo_count, ca);
+        if (launch(h, nw_trace_forward_kernel<ND, W>, grid_for(cnt), ASM_BLOCK, planes, lens, (long)cnt, (long)b.n, b.w4, d_trace.p,
+                   d_band.p) != hipSuccess ||
+            launch(h, nw_trace_cover_kernel<ND / 2, W>, grid_for(cnt), ASM_BLOCK, planes, lens, (long)cnt, (long)b.n, b.w4, d_trace.p,
+                   d_band.p, order, lo, ca, h->d_todo + 1, h->d_todo) != hipSuccess ||
+            hipMemcpyAsync(&todo_count, h->d_todo, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+            hipStreamSynchronize(h->stream) != hipSuccess)
+            return fail(h, ASM_ENODEVICE, "asm_coverage: kernel failed");
+        if (todo_count)
+            if (const int rc = cover_full_matrix(h, b, p, planes, lens, order, lo, h->d_todo + 1, (int64_t)todo_count, ca)) return rc;
     }
-    (void)hipFree(d_trace);
-    (void)hipFree(d_band);
-    return rc;
+    return ASM_OK;
 }
 
 /* SIMD_ED events of one bucket (asm_filter.h) */
 static int launch_simd_ed_events(asm_handle* h, const asm_bucket& b, int T, int shd, OutMap ev, int ed_mode) {
-    const dim3 grid((unsigned)((b.n + SIMD_ED_THREADS - 1) / SIMD_ED_THREADS)), block(SIMD_ED_THREADS);
-    with_const_of<2, 4>((b.maxlen + 63) / 64, [&](auto w) {
-        constexpr int W64 = decltype(w)::value;
-        if (T <= ASM_FILTER_REG_MAX_T && ed_mode != 1 && ed_mode != 2) { /* every lane live from generation 0; else: run-time form */
-            with_const<1, ASM_FILTER_REG_MAX_T>(T, [&](auto t) {
-                hipLaunchKernelGGL((simd_ed_kernel<decltype(t)::value, W64>), grid, block, 0, h->stream, b.planes, b.lens, (long)b.n,
-                                   b.w4, T, shd, 0, ev);
-            });
-        } else {
-            const size_t lds = (size_t)2 * (2 * T + 3) * SIMD_ED_THREADS * sizeof(short);
-            hipLaunchKernelGGL((simd_ed_kernel<0, W64>), grid, block, lds, h->stream, b.planes, b.lens, (long)b.n, b.w4, T, shd,
-                               ed_mode, ev);
-        }
-    });
-    HIPCHK(h, hipGetLastError());
+    const unsigned grid = (unsigned)((b.n + SIMD_ED_THREADS - 1) / SIMD_ED_THREADS);
+    HIPCHK(h, (with_const_of<2, 4>((b.maxlen + 63) / 64, [&](auto w) {
+               constexpr int W64 = decltype(w)::value;
+               if (T <= ASM_FILTER_REG_MAX_T && ed_mode != 1 && ed_mode != 2) /* every lane live from generation 0; else: run-time form */
+                   return with_const<1, ASM_FILTER_REG_MAX_T>(T, [&](auto t) {
+                       return launch(h, simd_ed_kernel<decltype(t)::value, W64>, grid, SIMD_ED_THREADS, b.planes, b.lens, (long)b.n, b.w4,
+                                     T, shd, 0, ev);
+                   });
+               const size_t lds = (size_t)2 * (2 * T + 3) * SIMD_ED_THREADS * sizeof(short);
+               return launch_lds(h, simd_ed_kernel<0, W64>, grid, SIMD_ED_THREADS, lds, b.planes, b.lens, (long)b.n, b.w4, T, shd, ed_mode, ev);
+           })));
     return ASM_OK;
 }
 
@@ -841,7 +831,6 @@ int asm_generate_pairs(const asm_gen_config* cfg, int64_t first, int64_t n, uint
 
 static hipError_t launch_pack(asm_handle* h, const asm_batch* b, const uint4* tails, uint4* planes, uint32_t* lens,
                               const PackBuckets& pb, const uint32_t* pos) {
-    const dim3 grid((unsigned)((b->n + PACK_BLOCK - 1) / PACK_BLOCK)), block(PACK_BLOCK);
     int wmax = 1;
     for (int q = 0; q < pb.nb; q++) wmax = pb.w4[q] > wmax ? pb.w4[q] : wmax;
     // LDS: the plane arrays of both sides of 256 strings of the batch's longest length (+ alignment slack), capped; at least
@@ -850,11 +839,10 @@ static hipError_t launch_pack(asm_handle* h, const asm_batch* b, const uint4* ta
     size_t dw = 2 * side_dwords((size_t)PACK_BLOCK * (size_t)b->maxlen + 15);
     if (dw > PACK_LDS_MAX / 4) dw = PACK_LDS_MAX / 4;
     if (dw < side_dwords((size_t)b->maxlen + 30)) dw = side_dwords((size_t)b->maxlen + 30);
-    with_const<1, 4>(wmax, [&](auto w) {
-        hipLaunchKernelGGL((pack_kernel<decltype(w)::value>), grid, block, dw * 4, h->stream, b->d_reads, b->d_read_off, b->d_refs,
-                           b->d_ref_off, tails, planes, lens, (long)b->n, pb, pos, (uint32_t)dw);
+    return with_const<1, 4>(wmax, [&](auto w) {
+        return launch_lds(h, pack_kernel<decltype(w)::value>, (unsigned)((b->n + PACK_BLOCK - 1) / PACK_BLOCK), PACK_BLOCK, dw * 4,
+                          b->d_reads, b->d_read_off, b->d_refs, b->d_ref_off, tails, planes, lens, (long)b->n, pb, pos, (uint32_t)dw);
     });
-    return hipGetLastError();
 }
 
 int asm_batch_pack_async(asm_handle* h, asm_batch* b) {
@@ -891,14 +879,12 @@ static int batch_resolve_tails(asm_handle* h, asm_batch* b, const uint8_t* init2
     PackBuckets one{};
     one.nb = 1, one.w4[0] = 1, one.start[0] = 0, one.start[1] = b->n, one.plane_off[0] = 0;
     HIPCHK(h, launch_pack(h, b, nullptr, b->d_tail_g0, b->d_tail_l0, one, nullptr));
-    hipLaunchKernelGGL(tails_chunk_kernel, dim3((unsigned)ngroups), dim3(2 * TAIL_GROUP), 0, h->stream, b->d_tail_g0, b->d_tail_l0,
-                       (long)b->n, d_loc, d_grp);
-    hipLaunchKernelGGL(tails_carry_kernel, dim3(1), dim3(8 * TAIL_CARRY_SEGS), 0, h->stream, (const uint32_t*)d_grp, (uint32_t*)d_carry,
-                       ngroups, init, summary256 ? d_sum : (uint8_t*)nullptr);
+    HIPCHK(h, launch(h, tails_chunk_kernel, (unsigned)ngroups, 2 * TAIL_GROUP, b->d_tail_g0, b->d_tail_l0, (long)b->n, d_loc, d_grp));
+    HIPCHK(h, launch(h, tails_carry_kernel, 1, 8 * TAIL_CARRY_SEGS, (const uint32_t*)d_grp, (uint32_t*)d_carry, ngroups, init,
+                     summary256 ? d_sum : (uint8_t*)nullptr));
     if (emit)
-        hipLaunchKernelGGL(tails_emit_kernel, dim3((unsigned)ngroups), dim3(2 * TAIL_GROUP), 0, h->stream, b->d_tail_g0, b->d_tail_l0,
-                           (long)b->n, (const TailOp*)d_loc, (const uint4*)d_carry, b->d_tails);
-    HIPCHK(h, hipGetLastError());
+        HIPCHK(h, launch(h, tails_emit_kernel, (unsigned)ngroups, 2 * TAIL_GROUP, b->d_tail_g0, b->d_tail_l0, (long)b->n,
+                         (const TailOp*)d_loc, (const uint4*)d_carry, b->d_tails));
     if (summary256) {
         HIPCHK(h, hipMemcpyAsync(summary256, d_sum, 256, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -923,9 +909,7 @@ static int batch_finish(asm_handle* h, asm_batch* b) {
         HIPCHK(h, d_idx.alloc(sizeof(uint32_t) * (size_t)n));
         HIPCHK(h, d_counts.alloc(16));
         HIPCHK(h, hipMemsetAsync(d_counts.p, 0, 16, h->stream));
-        hipLaunchKernelGGL(classify_kernel, dim3(grid_for(n)), dim3(ASM_BLOCK), 0, h->stream, b->d_read_off, b->d_ref_off,
-                           (long)n, d_cls.p, d_idx.p, d_counts.p);
-        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, launch(h, classify_kernel, grid_for(n), ASM_BLOCK, b->d_read_off, b->d_ref_off, (long)n, d_cls.p, d_idx.p, d_counts.p));
         HIPCHK(h, hipMemcpyAsync(counts, d_counts.p, 16, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         int classes = 0;
@@ -940,8 +924,7 @@ static int batch_finish(asm_handle* h, asm_batch* b) {
             HIPCHK(h, d_tmp.alloc(tmp_bytes + 16));
             HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, d_cls.p, d_cls2.p, d_idx.p, b->d_order, (int)n, 0, 2,
                                                          h->stream)); /* stable: input order is kept inside a class */
-            hipLaunchKernelGGL(invert_order_kernel, dim3(grid_for(n)), dim3(ASM_BLOCK), 0, h->stream, b->d_order, (long)n, b->d_pos);
-            HIPCHK(h, hipGetLastError());
+            HIPCHK(h, launch(h, invert_order_kernel, grid_for(n), ASM_BLOCK, b->d_order, (long)n, b->d_pos));
         }
     }
     // bucket table
@@ -1040,11 +1023,7 @@ int asm_batch_generate(asm_handle* h, const asm_gen_config* cfg, int64_t first, 
     HIPCHK(h, batch_alloc(b.get(), &b->d_ref_off, sizeof(uint32_t) * cnt));
     HIPCHK(h, hipMemsetAsync(d_m.p, 0, sizeof(uint32_t) * cnt, h->stream));
     HIPCHK(h, hipMemsetAsync(d_n.p, 0, sizeof(uint32_t) * cnt, h->stream));
-    if (n > 0) {
-        hipLaunchKernelGGL(gen_lengths_kernel, dim3(grid_for(n)), dim3(ASM_BLOCK), 0, h->stream, *cfg, (long)first, (long)n,
-                           d_m.p, d_n.p);
-        HIPCHK(h, hipGetLastError());
-    }
+    if (n > 0) HIPCHK(h, launch(h, gen_lengths_kernel, grid_for(n), ASM_BLOCK, *cfg, (long)first, (long)n, d_m.p, d_n.p));
     size_t tmp_bytes = 0, t2 = 0;
     HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_m.p, b->d_read_off, (int)cnt, h->stream));
     HIPCHK(h, hipcub::DeviceReduce::Max(nullptr, t2, d_n.p, d_max.p, (int)cnt, h->stream));
@@ -1069,11 +1048,9 @@ int asm_batch_generate(asm_handle* h, const asm_gen_config* cfg, int64_t first, 
     if (b->maxlen > ASM_MAX_LENGTH) return fail(h, ASM_EUNSUPPORTED, "asm_batch_generate: a generated sequence exceeds ASM_MAX_LENGTH");
     HIPCHK(h, batch_alloc(b.get(), &b->d_reads, b->reads_bytes + 16));
     HIPCHK(h, batch_alloc(b.get(), &b->d_refs, b->refs_bytes + 16));
-    if (n > 0) {
-        hipLaunchKernelGGL(gen_fill_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, *cfg, (long)first, (long)n,
-                           b->d_read_off, b->d_ref_off, b->d_reads, b->d_refs);
-        HIPCHK(h, hipGetLastError());
-    }
+    if (n > 0)
+        HIPCHK(h, launch(h, gen_fill_kernel, (unsigned)((n + 63) / 64), 64, *cfg, (long)first, (long)n, b->d_read_off, b->d_ref_off,
+                         b->d_reads, b->d_refs));
     rc = batch_finish(h, b.get());
     if (rc) return rc;
     *out = b.release();
@@ -1138,9 +1115,8 @@ int asm_batch_from_hits(asm_handle* h, const asm_reference* ref, int64_t n, cons
     HIPCHK(h, hipMemcpyAsync(b->d_reads, reads, b->reads_bytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(b->d_read_off, read_off, sizeof(uint32_t) * cnt, hipMemcpyHostToDevice, h->stream));
     if (n) HIPCHK(h, hipMemcpyAsync(d_pos.p, hit_pos, sizeof(unsigned long long) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(hit_window_lengths_kernel, dim3(grid_for(n + 1)), dim3(ASM_BLOCK), 0, h->stream, b->d_read_off, d_pos.p,
-                       (unsigned long long)ref->len, (long)n, d_wl.p);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, hit_window_lengths_kernel, grid_for(n + 1), ASM_BLOCK, b->d_read_off, d_pos.p, (unsigned long long)ref->len,
+                     (long)n, d_wl.p));
     size_t tmp_bytes = 0;
     HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_wl.p, b->d_ref_off, (int)cnt, h->stream));
     HIPCHK(h, d_tmp.alloc(tmp_bytes + 16));
@@ -1153,9 +1129,7 @@ int asm_batch_from_hits(asm_handle* h, const asm_reference* ref, int64_t n, cons
     if (n) {
         int64_t blocks = (n + 3) / 4;
         blocks = blocks > 256 * 16 ? 256 * 16 : blocks;
-        hipLaunchKernelGGL(hit_window_gather_kernel, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, h->stream, ref->d_text, d_pos.p,
-                           b->d_ref_off, (long)n, b->d_refs);
-        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, launch(h, hit_window_gather_kernel, (unsigned)blocks, ASM_BLOCK, ref->d_text, d_pos.p, b->d_ref_off, (long)n, b->d_refs));
     }
     rc = batch_finish(h, b.get());
     if (rc) return rc;
@@ -1308,21 +1282,21 @@ static int align_bucket(asm_handle* h, const asm_bucket& b, int aligner, const a
             HIPCHK(h, launch_greedy_group(h->stream, planes, lens, b.n, b.w4, (int)p->k, ga, out, cig, h->num_cus));
         } else if (p->k <= ASM_WAVE_MAX_K && h->wave_kernels && unit && !ga.semi) {
             HIPCHK(h, hipMemsetAsync(h->d_pair_queue, 0, sizeof(unsigned long long), h->stream));
-            launch_wave_per_pair(h->stream, greedy_wave_kernel<true>, b.n, h->num_cus, planes, lens, (long)b.n, b.w4, (int)p->k, ga,
-                                 out, cig, h->d_pair_queue, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
+            HIPCHK(h, launch_wave_per_pair(h->stream, greedy_wave_kernel<true>, b.n, h->num_cus, planes, lens, (long)b.n, b.w4, (int)p->k,
+                                           ga, out, cig, h->d_pair_queue, (const uint32_t*)nullptr, (const uint32_t*)nullptr));
         } else if (p->k <= ASM_WAVE_MAX_K && h->wave_kernels && (long)p->o + 62L * p->e < 16000L) {
             HIPCHK(h, hipMemsetAsync(h->d_pair_queue, 0, sizeof(unsigned long long), h->stream));
-            launch_wave_per_pair(h->stream, greedy_wave_kernel<false>, b.n, h->num_cus, planes, lens, (long)b.n, b.w4, (int)p->k, ga,
-                                 out, cig, h->d_pair_queue, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
+            HIPCHK(h, launch_wave_per_pair(h->stream, greedy_wave_kernel<false>, b.n, h->num_cus, planes, lens, (long)b.n, b.w4, (int)p->k,
+                                           ga, out, cig, h->d_pair_queue, (const uint32_t*)nullptr, (const uint32_t*)nullptr));
         } else if (h->wave_kernels && (long)p->o + 100L * p->e < 16000L)
-            launch_greedy_wave2(h->stream, planes, lens, b.n, b.w4, (int)p->k, ga, out, cig, h->num_cus);
+            HIPCHK(h, launch_greedy_wave2(h->stream, planes, lens, b.n, b.w4, (int)p->k, ga, out, cig, h->num_cus));
         else
-            launch_greedy_wide(h->stream, planes, lens, b.n, b.w4, p->k, ga, out, cig);
+            HIPCHK(h, launch_greedy_wide(h->stream, planes, lens, b.n, b.w4, p->k, ga, out, cig));
     } else if (aligner == ASM_LEAP) {
         if (p->leap_mode != ASM_LEAP_GLOBAL) {
             /* LV's other ED_modes have no caller in the reference: one kernel serves them, the workgroup-per-pair form that takes
              * any band and any penalties (asm_wide.h) */
-            launch_leap_wide(h->stream, planes, lens, b.n, b.w4, p->k, p->x, p->o, p->e, out, (int)p->leap_mode);
+            HIPCHK(h, launch_leap_wide(h->stream, planes, lens, b.n, b.w4, p->k, p->x, p->o, p->e, out, (int)p->leap_mode));
         } else if (unit && p->k >= 1 && ((p->k <= LEAP_UNIT_WIDE_K && b.maxlen <= 384) || (p->k <= LEAP_UNIT_MAX_K && b.maxlen <= 128))) {
             /* thread per pair, band lanes in registers: k <= 5 at any length; k = 6..10 for strings of one granule, where the
              * four-threads-per-pair kernel is 1.6-2 x slower (C2, 10^6 pairs, k = 6 / 8 / 10: 0.085 / 0.089 / 0.111 ms against
@@ -1356,8 +1330,7 @@ static int align_bucket(asm_handle* h, const asm_bucket& b, int aligner, const a
                 uint8_t* const d_keys2 = d_keys + n;
                 void* const d_tmp = (void*)(((uintptr_t)(d_keys2 + n) + 255) & ~(uintptr_t)255);
                 const int div = unit ? 1 : (int)(p->e < p->x ? p->e : p->x);
-                hipLaunchKernelGGL(leap_sort_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, qhint, out, (long)n,
-                                   div, d_keys, d_idx);
+                HIPCHK(h, launch(h, leap_sort_keys_kernel, (unsigned)((n + 255) / 256), 256, qhint, out, (long)n, div, d_keys, d_idx));
                 HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_keys, d_keys2, d_idx, d_perm, (int)n, 0, 6, h->stream));
                 qperm = d_perm;
             }
@@ -1369,36 +1342,36 @@ static int align_bucket(asm_handle* h, const asm_bucket& b, int aligner, const a
                        return b.maxlen + 2 <= 255 ? quad(w, uint8_t{}) : quad(w, uint16_t{}); /* every stored position + 2 fits a byte */
                    })));
         } else {
-            launch_leap_wide(h->stream, planes, lens, b.n, b.w4, p->k, p->x, p->o, p->e, out);
+            HIPCHK(h, launch_leap_wide(h->stream, planes, lens, b.n, b.w4, p->k, p->x, p->o, p->e, out));
         }
     } else {
         if (unit) {
             /* The one w4 -> kernel mapping of unit-cost NW.  A width class of w4 granules has ND = 4 * w4 plane dwords = 2 * w4
              * 64-bit words per string: full height is nw_unit_kernel<2 * w4>, banded nw_banded_kernel<ND, first window, SORT>
              * with a first window of 32 rows for one granule and 64 above. */
-            const dim3 g(grid_for(b.n)), t(ASM_BLOCK);
+            const unsigned g = grid_for(b.n);
             const long n = (long)b.n;
-            const auto banded = [&](auto sort, dim3 grid) {
-                with_const<1, 4>(b.w4, [&](auto w) {
+            const auto banded = [&](auto sort, unsigned grid) {
+                return with_const<1, 4>(b.w4, [&](auto w) {
                     constexpr int W4 = decltype(w)::value;
-                    hipLaunchKernelGGL((nw_banded_kernel<4 * W4, (W4 == 1 ? 32 : 64), decltype(sort)::value>), grid, t, 0, h->stream,
-                                       planes, lens, n, b.w4, out);
+                    return launch(h, nw_banded_kernel<4 * W4, (W4 == 1 ? 32 : 64), decltype(sort)::value>, grid, ASM_BLOCK, planes, lens, n,
+                                  b.w4, out);
                 });
             };
             if (!h->nw_banded) {
-                with_const<1, 4>(b.w4, [&](auto w) {
-                    hipLaunchKernelGGL(nw_unit_kernel<2 * decltype(w)::value>, g, t, 0, h->stream, planes, lens, n, b.w4, out);
-                });
+                HIPCHK(h, (with_const<1, 4>(b.w4, [&](auto w) {
+                           return launch(h, nw_unit_kernel<2 * decltype(w)::value>, g, ASM_BLOCK, planes, lens, n, b.w4, out);
+                       })));
             } else if (b.mixed && h->nw_bylen) { /* a width class of a mixed-length batch: workgroup-local sort by length */
                 /* (measured and dropped in round 4: ONE wave per 256-pair sort window working through its four length quartiles in
                  * turn, so that every wave of the grid gets the same mix — C5, 10^7 pairs: 2.16-2.21 ms against 2.12 for this form;
                  * the dispatcher does not pile the long quartiles on one SIMD) */
-                banded(std::true_type{}, dim3((unsigned)((b.n + NW_SORT_PAIRS - 1) / NW_SORT_PAIRS)));
+                HIPCHK(h, banded(std::true_type{}, (unsigned)((b.n + NW_SORT_PAIRS - 1) / NW_SORT_PAIRS)));
             } else if (b.w4 == 1 && h->nw_pair2) {
-                const dim3 g2((unsigned)((b.n + 2 * ASM_BLOCK - 1) / (2 * ASM_BLOCK)));
-                hipLaunchKernelGGL(nw_banded2_kernel<4>, g2, t, 0, h->stream, planes, lens, n, b.w4, out);
+                HIPCHK(h, launch(h, nw_banded2_kernel<4>, (unsigned)((b.n + 2 * ASM_BLOCK - 1) / (2 * ASM_BLOCK)), ASM_BLOCK, planes, lens, n,
+                                 b.w4, out));
             } else {
-                banded(std::false_type{}, g);
+                HIPCHK(h, banded(std::false_type{}, g));
             }
         } else {
             /* a zero penalty makes the wavefront read the generation it is writing (ring slot s - 0): plain Gotoh handles it */
@@ -1410,11 +1383,10 @@ static int align_bucket(asm_handle* h, const asm_bucket& b, int aligner, const a
                 });
                 if (rc != ASM_OK) return rc;
             } else {
-                launch_nw_affine(h->stream, planes, lens, b.n, b.w4, b.maxlen, p->x, p->o, p->e, out);
+                HIPCHK(h, launch_nw_affine(h->stream, planes, lens, b.n, b.w4, b.maxlen, p->x, p->o, p->e, out));
             }
         }
     }
-    HIPCHK(h, hipGetLastError());
     return ASM_OK;
 }
 
@@ -1521,15 +1493,13 @@ int asm_simd_ed_mode_batch_async(asm_handle* h, const asm_batch* b, int ed_thres
         }))
         return rc;
     const long n = (long)b->n;
-    const dim3 g(grid_for(b->n)), t(ASM_BLOCK);
+    const unsigned g = grid_for(b->n), t = ASM_BLOCK;
     if (ed_mode == ASM_LEAP_LOCAL || ed_mode == ASM_LEAP_SEMI_FREE_END) { /* no converge_ED, no carried state: SEQUENTIAL = CLEAN */
-        hipLaunchKernelGGL(simd_ed_final_kernel, g, t, 0, h->stream, d_ed, n);
-        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, launch(h, simd_ed_final_kernel, g, t, d_ed, n));
         return ASM_OK;
     }
     if (mode == ASM_FILTER_CLEAN) {
-        hipLaunchKernelGGL(simd_ed_clean_kernel, g, t, 0, h->stream, d_ed, n, ed_threshold);
-        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, launch(h, simd_ed_clean_kernel, g, t, d_ed, n, ed_threshold));
         return ASM_OK;
     }
     /* sequential: resolve the verdict chain in batch order with two last-setter scans */
@@ -1542,15 +1512,13 @@ int asm_simd_ed_mode_batch_async(asm_handle* h, const asm_batch* b, int ed_thres
     HIPCHK(h, d_b.alloc(sizeof(int32_t) * (size_t)n));
     HIPCHK(h, hipcub::DeviceScan::InclusiveScan(nullptr, tmp_bytes, d_a.p, d_b.p, LastSetter(), (int)n, h->stream));
     HIPCHK(h, d_tmp.alloc(tmp_bytes + 16));
-    hipLaunchKernelGGL(simd_ed_setter_kernel, g, t, 0, h->stream, (const int32_t*)d_ed, n, d_a.p);
+    HIPCHK(h, launch(h, simd_ed_setter_kernel, g, t, d_ed, n, d_a.p));
     HIPCHK(h, hipcub::DeviceScan::InclusiveScan(d_tmp.p, tmp_bytes, d_a.p, d_b.p, LastSetter(), (int)n, h->stream));
     HIPCHK(h, hipMemcpyAsync(&last_setter, d_b.p + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    hipLaunchKernelGGL(simd_ed_converge_kernel, g, t, 0, h->stream, (const int32_t*)d_ed, (const int32_t*)d_b.p, n, init_fe,
-                       init_fd, d_a.p);
+    HIPCHK(h, launch(h, simd_ed_converge_kernel, g, t, d_ed, d_b.p, n, init_fe, init_fd, d_a.p));
     HIPCHK(h, hipcub::DeviceScan::InclusiveScan(d_tmp.p, tmp_bytes, d_a.p, d_b.p, LastSetter(), (int)n, h->stream));
     HIPCHK(h, hipMemcpyAsync(&last_conv, d_b.p + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    hipLaunchKernelGGL(simd_ed_verdict_kernel, g, t, 0, h->stream, d_ed, (const int32_t*)d_b.p, n, ed_threshold, init_conv);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, simd_ed_verdict_kernel, g, t, d_ed, d_b.p, n, ed_threshold, init_conv));
     HIPCHK(h, hipStreamSynchronize(h->stream)); /* last_setter and last_conv are read below */
     if (state) { /* the state the next batch of the same stream of pairs starts from */
         if (last_setter >= 0) state[0] = last_setter & 0xff, state[1] = last_setter >> 8;
@@ -1559,12 +1527,6 @@ int asm_simd_ed_mode_batch_async(asm_handle* h, const asm_batch* b, int ed_thres
     return ASM_OK;
 }
 
-static int simd_ed_affine_launch(asm_handle* h, const asm_batch* b, int gap_threshold, int af_threshold, int x, int o, int e, int mode,
-                                 int32_t* d_ed);
-int asm_simd_ed_affine_batch_async(asm_handle* h, const asm_batch* b, int gap_threshold, int af_threshold, int x, int o, int e,
-                                   int32_t* d_ed) {
-    return simd_ed_affine_launch(h, b, gap_threshold, af_threshold, x, o, e, ASM_LEAP_GLOBAL, d_ed);
-}
 static int simd_ed_affine_launch(asm_handle* h, const asm_batch* b, int gap_threshold, int af_threshold, int x, int o, int e, int mode,
                                  int32_t* d_ed) {
     if (!h || !b || !d_ed) return fail(h, ASM_EINVAL, "asm_simd_ed_affine_batch_async: NULL argument");
@@ -1588,21 +1550,19 @@ static int simd_ed_affine_launch(asm_handle* h, const asm_batch* b, int gap_thre
      * kept as it is. */
     if (lds > 150 * 1024) return fail(h, ASM_EINVAL, "asm_simd_ed_affine_batch_async: generation rings exceed the LDS");
     return for_each_bucket(b, d_ed, [&](const asm_bucket& k, OutMap out) -> int {
-        if (k.maxlen <= 128) { /* four threads per pair (thread per pair measured 0.28/0.71/3.5 ms per 10^6 C2 pairs at gap 3/8/30 against 0.29/0.46/0.79) */
-            const size_t qlds = simd_quad_lds(gap_threshold, rg.gm, rg.gi);
-            hipLaunchKernelGGL(simd_ed_affine_quad_kernel, dim3((unsigned)((k.n + 15) / 16)), dim3(64), qlds, h->stream, k.planes, k.lens,
-                               (long)k.n, k.w4, gap_threshold, af_threshold, x, o, e, rg.gm, rg.gi, mode, out);
-        } else { /* thread per pair: the only instantiation kept is the one for strings beyond one granule */
-            const dim3 grid((unsigned)((k.n + threads - 1) / threads)), block((unsigned)threads);
-            if (lds > 64 * 1024)
-                HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&simd_ed_affine_kernel<4>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(simd_ed_affine_kernel<4>, grid, block, lds, h->stream, k.planes, k.lens, (long)k.n, k.w4, gap_threshold,
-                               af_threshold, x, o, e, rg.gm, rg.gi, mode, out);
-        }
-        HIPCHK(h, hipGetLastError());
+        if (k.maxlen <= 128) /* four threads per pair (thread per pair measured 0.28/0.71/3.5 ms per 10^6 C2 pairs at gap 3/8/30 against 0.29/0.46/0.79) */
+            HIPCHK(h, launch_lds(h, simd_ed_affine_quad_kernel, (unsigned)((k.n + 15) / 16), 64, simd_quad_lds(gap_threshold, rg.gm, rg.gi),
+                                 k.planes, k.lens, (long)k.n, k.w4, gap_threshold, af_threshold, x, o, e, rg.gm, rg.gi, mode, out));
+        else /* thread per pair: the only instantiation kept is the one for strings beyond one granule */
+            HIPCHK(h, launch_lds(h, simd_ed_affine_kernel<4>, (unsigned)((k.n + threads - 1) / threads), (unsigned)threads, lds, k.planes,
+                                 k.lens, (long)k.n, k.w4, gap_threshold, af_threshold, x, o, e, rg.gm, rg.gi, mode, out));
         return ASM_OK;
     });
+}
+
+int asm_simd_ed_affine_batch_async(asm_handle* h, const asm_batch* b, int gap_threshold, int af_threshold, int x, int o, int e,
+                                   int32_t* d_ed) {
+    return simd_ed_affine_launch(h, b, gap_threshold, af_threshold, x, o, e, ASM_LEAP_GLOBAL, d_ed);
 }
 
 int asm_simd_ed_affine_shd_batch_async(asm_handle* h, const asm_batch* b, int gap_threshold, int af_threshold, int x, int o, int e,
@@ -1619,15 +1579,13 @@ int asm_simd_ed_affine_mode_batch_async(asm_handle* h, const asm_batch* b, int g
                                    "(the reference reads 2*SHD_threshold+1 of its 2*gap_threshold+1 lane masks)");
     const int rc = simd_ed_affine_launch(h, b, gap_threshold, af_threshold, x, o, e, mode, d_ed);
     if (rc != ASM_OK || b->n == 0) return rc;
-    for_each_bucket(b, d_ed, [&](const asm_bucket& k, OutMap out) {
-        with_const_of<2, 4>((k.maxlen + 63) / 64, [&](auto w) {
-            hipLaunchKernelGGL(simd_affine_shd_kernel<decltype(w)::value>, dim3(grid_for(k.n)), dim3(ASM_BLOCK), 0, h->stream, k.planes,
-                               k.lens, (long)k.n, k.w4, gap_threshold, shd_threshold, out);
-        });
+    return for_each_bucket(b, d_ed, [&](const asm_bucket& k, OutMap out) -> int {
+        HIPCHK(h, (with_const_of<2, 4>((k.maxlen + 63) / 64, [&](auto w) {
+                   return launch(h, simd_affine_shd_kernel<decltype(w)::value>, grid_for(k.n), ASM_BLOCK, k.planes, k.lens, (long)k.n, k.w4,
+                                 gap_threshold, shd_threshold, out);
+               })));
         return ASM_OK;
     });
-    HIPCHK(h, hipGetLastError());
-    return ASM_OK;
 }
 
 int asm_shd_filter_batch_async(asm_handle* h, const asm_batch* b, int max_error, int32_t* d_pass) {
@@ -1636,15 +1594,12 @@ int asm_shd_filter_batch_async(asm_handle* h, const asm_batch* b, int max_error,
         return fail(h, ASM_EINVAL, "asm_shd_filter_batch_async: max_error must be in [0, 16] (MAX_ERROR_AVX)");
     if (b->n == 0) return ASM_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    for_each_bucket(b, d_pass, [&](const asm_bucket& k, OutMap out) {
-        with_const_of<2, 4>((k.maxlen + 63) / 64, [&](auto w) {
-            hipLaunchKernelGGL(shd_kernel<decltype(w)::value>, dim3(grid_for(k.n)), dim3(ASM_BLOCK), 0, h->stream, k.planes, k.lens,
-                               (long)k.n, k.w4, max_error, out);
-        });
+    return for_each_bucket(b, d_pass, [&](const asm_bucket& k, OutMap out) -> int {
+        HIPCHK(h, (with_const_of<2, 4>((k.maxlen + 63) / 64, [&](auto w) {
+                   return launch(h, shd_kernel<decltype(w)::value>, grid_for(k.n), ASM_BLOCK, k.planes, k.lens, (long)k.n, k.w4, max_error, out);
+               })));
         return ASM_OK;
     });
-    HIPCHK(h, hipGetLastError());
-    return ASM_OK;
 }
 
 int asm_count_equal_async(asm_handle* h, const int32_t* d_a, const int32_t* d_b, int64_t n, unsigned long long* d_count) {
@@ -1653,8 +1608,7 @@ int asm_count_equal_async(asm_handle* h, const int32_t* d_a, const int32_t* d_b,
     HIPCHK(h, hipSetDevice(h->device));
     int64_t blocks = (n + ASM_BLOCK - 1) / ASM_BLOCK;
     if (blocks > 512) blocks = 512;
-    hipLaunchKernelGGL(count_equal_kernel, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, h->stream, d_a, d_b, (long)n, d_count);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, count_equal_kernel, (unsigned)blocks, ASM_BLOCK, d_a, d_b, (long)n, d_count));
     return ASM_OK;
 }
 
@@ -1670,9 +1624,7 @@ int asm_accuracy_async(asm_handle* h, const int32_t* d_nw, const int32_t* d_leap
      * made this kernel 38 us at 10^6 pairs (rocprof, round 1); 128 grid-striding workgroups keep the loads wide enough */
     blocks = blocks < 1 ? 1 : (blocks > 128 ? 128 : blocks);
     if (!d_nw && !d_answers) blocks = 1; /* nothing to compare with: total_tests only */
-    hipLaunchKernelGGL(accuracy_kernel, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, h->stream, d_nw, d_leap, d_greedy,
-                       d_answers, (long)n, d_counters);
-    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, launch(h, accuracy_kernel, (unsigned)blocks, ASM_BLOCK, d_nw, d_leap, d_greedy, d_answers, (long)n, d_counters));
     return ASM_OK;
 }
 

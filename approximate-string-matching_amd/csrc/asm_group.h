@@ -19,6 +19,7 @@
 
 #include "asm_bits.h"
 #include "asm_kernels.h"
+#include "asm_launch.h"
 
 #define DPP_QUAD_XOR1 0xB1        /* quad_perm [1,0,3,2] */
 #define DPP_QUAD_XOR2 0x4E        /* quad_perm [2,3,0,1] */
@@ -256,9 +257,7 @@ static inline hipError_t launch_greedy_group_tl(hipStream_t stream, const uint4*
     int64_t blocks = (int64_t)per_cu * num_cus;
     const int64_t need = (n * T + ASM_BLOCK - 1) / ASM_BLOCK;
     if (blocks > need) blocks = need;
-    hipLaunchKernelGGL((greedy_group_kernel<T, LPT>), dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, stream, planes, lens, (long)n, w4, k,
-                       ga, out, cig);
-    return hipGetLastError();
+    return launch_on(stream, greedy_group_kernel<T, LPT>, (unsigned)blocks, ASM_BLOCK, 0, planes, lens, (long)n, w4, k, ga, out, cig);
 }
 
 static inline hipError_t launch_greedy_group(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4, int k,

@@ -33,7 +33,7 @@ static unsigned map_grid(uint64_t n, const asm_handle* h) { /* grid-stride kerne
     return (unsigned)(want < 1 ? 1 : want > cap ? cap : want);
 }
 
-/* (launch, fetch, hipcub's scratch MapTmp and map_exclusive_sum: asm_stream.h, which the streamed-file calls share) */
+/* (launch: asm_capi.hip; fetch, hipcub's scratch MapTmp and map_exclusive_sum: asm_stream.h, which the streamed-file calls share) */
 
 template <class K, class V, class N> /* stable: equal keys keep their order */
 static hipError_t map_sort_pairs(asm_handle* h, MapTmp& tmp, K* key_in, K* key_out, V* val_in, V* val_out, N n, int end_bit) {

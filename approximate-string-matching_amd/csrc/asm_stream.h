@@ -1,4 +1,4 @@
-// Device side of the streamed-file calls (asm_stream_seq_file, asm_map_file, asm_map_pairs_file): the checked launch and the
+// Device side of the streamed-file calls (asm_stream_seq_file, asm_map_file, asm_map_pairs_file): the
 // "scalars back, one wait" step that the mapper's host stages use too, hipcub's scratch and scans, the newline index of a chunk of
 // text in HBM, and the input pipeline — reader thread (asm_host.h) -> pinned slots -> copy-in stream -> two device
 // buffers -> the caller's processing on the handle's stream.  asm_capi.hip includes this file inside its extern "C" block.
@@ -14,13 +14,6 @@ extern "C++" {
             return fail(h, _e == hipErrorOutOfMemory ? ASM_ENOMEM : ASM_ENODEVICE,               \
                         std::string(who) + ": " + #call + ": " + hipGetErrorString(_e));         \
     } while (0)
-
-/* A kernel launch on the handle's stream and what hipGetLastError() says about it: one expression for HIPCHK / STREAM_TRY */
-template <class... P, class... A>
-static hipError_t launch(asm_handle* h, void (*kernel)(P...), unsigned grid, unsigned block, A&&... args) {
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, h->stream, std::forward<A>(args)...);
-    return hipGetLastError();
-}
 
 /* One copy of fetch(): `bytes` from device memory into host memory */
 struct Fetch {

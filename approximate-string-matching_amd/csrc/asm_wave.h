@@ -9,6 +9,7 @@
 
 #include "asm_bits.h"
 #include "asm_kernels.h"
+#include "asm_launch.h"
 
 #define ASM_WAVE_MAX_K 31
 
@@ -335,24 +336,17 @@ static inline hipError_t launch_leap_quad(hipStream_t stream, const uint4* plane
                                           const uint32_t* perm) {
     const size_t lds1 = unit ? leap_quad_lds(W32, k, 2, 0, sizeof(EnT)) : leap_quad_lds(W32, k, gm, gi, sizeof(EnT));
     if (hint && !perm && 4 * lds1 + 512 <= 64 * 1024) { /* work-sorted inside workgroups of four waves (64 pairs) */
-        const dim3 grid((unsigned)((n + 4 * LEAP_QUAD_PAIRS - 1) / (4 * LEAP_QUAD_PAIRS))), block(4 * LEAP_QUAD_THREADS);
-        if (unit)
-            hipLaunchKernelGGL((leap_quad_kernel<W32, EnT, true, 4>), grid, block, 4 * lds1, stream, planes, lens, (long)n, w4, k, 1, 1, 1,
-                               2, 0, out, hint, nullptr);
-        else
-            hipLaunchKernelGGL((leap_quad_kernel<W32, EnT, false, 4>), grid, block, 4 * lds1, stream, planes, lens, (long)n, w4, k, x, o,
-                               e, gm, gi, out, hint, nullptr);
-        return hipGetLastError();
+        const unsigned grid = (unsigned)((n + 4 * LEAP_QUAD_PAIRS - 1) / (4 * LEAP_QUAD_PAIRS)), block = 4 * LEAP_QUAD_THREADS;
+        return unit ? launch_on(stream, leap_quad_kernel<W32, EnT, true, 4>, grid, block, 4 * lds1, planes, lens, (long)n, w4, k, 1, 1, 1,
+                                2, 0, out, hint, nullptr)
+                    : launch_on(stream, leap_quad_kernel<W32, EnT, false, 4>, grid, block, 4 * lds1, planes, lens, (long)n, w4, k, x, o,
+                                e, gm, gi, out, hint, nullptr);
     }
-    const dim3 grid((unsigned)((n + LEAP_QUAD_PAIRS - 1) / LEAP_QUAD_PAIRS)), block(LEAP_QUAD_THREADS);
-    if (unit) {
-        hipLaunchKernelGGL((leap_quad_kernel<W32, EnT, true, 1>), grid, block, lds1, stream, planes, lens, (long)n, w4, k, 1, 1, 1, 2, 0,
-                           out, nullptr, perm);
-    } else {
-        hipLaunchKernelGGL((leap_quad_kernel<W32, EnT, false, 1>), grid, block, lds1, stream, planes, lens, (long)n, w4, k, x, o, e, gm,
-                           gi, out, nullptr, perm);
-    }
-    return hipGetLastError();
+    const unsigned grid = (unsigned)((n + LEAP_QUAD_PAIRS - 1) / LEAP_QUAD_PAIRS), block = LEAP_QUAD_THREADS;
+    return unit ? launch_on(stream, leap_quad_kernel<W32, EnT, true, 1>, grid, block, lds1, planes, lens, (long)n, w4, k, 1, 1, 1, 2, 0,
+                            out, nullptr, perm)
+                : launch_on(stream, leap_quad_kernel<W32, EnT, false, 1>, grid, block, lds1, planes, lens, (long)n, w4, k, x, o, e, gm,
+                            gi, out, nullptr, perm);
 }
 
 // --------------------------------------------------------------------------------------------------------
@@ -835,21 +829,20 @@ __global__ __launch_bounds__(GREEDY_WAVE2_THREADS) void greedy_wave2_kernel(cons
     }
 }
 
-static inline void launch_greedy_wave2(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4, int k,
-                                       const GreedyArgs& ga, OutMap out, CigarSink cig, int num_cus) {
+static inline hipError_t launch_greedy_wave2(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4, int k,
+                                             const GreedyArgs& ga, OutMap out, CigarSink cig, int num_cus) {
     int64_t blocks = (int64_t)num_cus * 16; /* two waves each; the kernel strides over the pairs */
     if (blocks > n) blocks = n;
-    hipLaunchKernelGGL(greedy_wave2_kernel, dim3((unsigned)blocks), dim3(GREEDY_WAVE2_THREADS), 0, stream, planes, lens, (long)n,
-                       w4, k, ga, out, cig);
+    return launch_on(stream, greedy_wave2_kernel, (unsigned)blocks, GREEDY_WAVE2_THREADS, 0, planes, lens, (long)n, w4, k, ga, out, cig);
 }
 
 template <typename Kern, typename... Args>
-static inline void launch_wave_per_pair(hipStream_t stream, Kern kern, int64_t n, int num_cus, Args... args) {
+static inline hipError_t launch_wave_per_pair(hipStream_t stream, Kern kern, int64_t n, int num_cus, Args... args) {
     int per_cu = 8;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, ASM_BLOCK, 0);
     if (per_cu < 1) per_cu = 1;
     int64_t blocks = (int64_t)per_cu * num_cus;
     const int64_t need = (n + 3) / 4; /* four waves (pairs in flight) per workgroup */
     if (blocks > need) blocks = need;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(ASM_BLOCK), 0, stream, args...);
+    return launch_on(stream, kern, (unsigned)blocks, ASM_BLOCK, 0, args...);
 }

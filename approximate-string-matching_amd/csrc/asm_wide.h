@@ -10,6 +10,7 @@
 
 #include "asm_bits.h"
 #include "asm_kernels.h"
+#include "asm_launch.h"
 
 #define ASM_WIDE_MAX_K 63       /* 2k+1 <= 127 lanes -> one 128-thread workgroup                         */
 #define ASM_WIDE_MAX_PENALTY 15 /* LEAP history ring depth 16; NW boundary values stay inside int16       */
@@ -118,19 +119,14 @@ __global__ __launch_bounds__(ASM_WIDE_THREADS) void leap_wide_kernel(const uint4
     }
 }
 
-static inline void launch_leap_wide(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4,
-                                    int k, int x, int o, int e, OutMap out, int mode = 0) {
-    int64_t blocks = n < 256 * 32 ? n : 256 * 32;
+static inline hipError_t launch_leap_wide(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4,
+                                          int k, int x, int o, int e, OutMap out, int mode = 0) {
+    const unsigned blocks = (unsigned)(n < 256 * 32 ? n : 256 * 32);
     const int maxw = w4 * 2;
-    if (maxw <= 2)
-        hipLaunchKernelGGL(leap_wide_kernel<2>, dim3((unsigned)blocks), dim3(ASM_WIDE_THREADS), 0, stream, planes, lens,
-                           (long)n, w4, k, x, o, e, mode, out);
-    else if (maxw <= 4)
-        hipLaunchKernelGGL(leap_wide_kernel<4>, dim3((unsigned)blocks), dim3(ASM_WIDE_THREADS), 0, stream, planes, lens,
-                           (long)n, w4, k, x, o, e, mode, out);
-    else
-        hipLaunchKernelGGL(leap_wide_kernel<8>, dim3((unsigned)blocks), dim3(ASM_WIDE_THREADS), 0, stream, planes, lens,
-                           (long)n, w4, k, x, o, e, mode, out);
+    const auto go = [&](auto kernel) {
+        return launch_on(stream, kernel, blocks, ASM_WIDE_THREADS, 0, planes, lens, (long)n, w4, k, x, o, e, mode, out);
+    };
+    return maxw <= 2 ? go(leap_wide_kernel<2>) : maxw <= 4 ? go(leap_wide_kernel<4>) : go(leap_wide_kernel<8>);
 }
 
 // --------------------------------------------------------------------------------------------------------
@@ -259,11 +255,10 @@ __global__ __launch_bounds__(ASM_WIDE_THREADS) void greedy_wide_kernel(const uin
     }
 }
 
-static inline void launch_greedy_wide(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4,
-                                      int k, const GreedyArgs& ga, OutMap out, CigarSink cig) {
-    int64_t blocks = n < 256 * 32 ? n : 256 * 32;
-    hipLaunchKernelGGL(greedy_wide_kernel, dim3((unsigned)blocks), dim3(ASM_WIDE_THREADS), 0, stream, planes, lens, (long)n,
-                       w4, k, ga, out, cig);
+static inline hipError_t launch_greedy_wide(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4,
+                                            int k, const GreedyArgs& ga, OutMap out, CigarSink cig) {
+    const unsigned blocks = (unsigned)(n < 256 * 32 ? n : 256 * 32);
+    return launch_on(stream, greedy_wide_kernel, blocks, ASM_WIDE_THREADS, 0, planes, lens, (long)n, w4, k, ga, out, cig);
 }
 
 // --------------------------------------------------------------------------------------------------------
@@ -361,16 +356,10 @@ __global__ __launch_bounds__(64) void nw_affine_kernel(const uint4* __restrict__
     out.put(i, result);
 }
 
-static inline void launch_nw_affine(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4,
-                                    int maxlen, int x, int o, int e, OutMap out) {
-    const dim3 g((unsigned)((n + 63) / 64)), t(64);
-    if (maxlen <= 128)
-        hipLaunchKernelGGL((nw_affine_kernel<2, 128>), g, t, 0, stream, planes, lens, (long)n, w4, x, o, e, out,
-                           (const uint32_t*)nullptr, (const uint32_t*)nullptr);
-    else if (maxlen <= 256)
-        hipLaunchKernelGGL((nw_affine_kernel<4, 256>), g, t, 0, stream, planes, lens, (long)n, w4, x, o, e, out,
-                           (const uint32_t*)nullptr, (const uint32_t*)nullptr);
-    else
-        hipLaunchKernelGGL((nw_affine_kernel<8, 512>), g, t, 0, stream, planes, lens, (long)n, w4, x, o, e, out,
-                           (const uint32_t*)nullptr, (const uint32_t*)nullptr);
+static inline hipError_t launch_nw_affine(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4,
+                                          int maxlen, int x, int o, int e, OutMap out) {
+    const auto go = [&](auto kernel) { /* every pair of the bucket: no todo list */
+        return launch_on(stream, kernel, (unsigned)((n + 63) / 64), 64, 0, planes, lens, (long)n, w4, x, o, e, out, nullptr, nullptr);
+    };
+    return maxlen <= 128 ? go(nw_affine_kernel<2, 128>) : maxlen <= 256 ? go(nw_affine_kernel<4, 256>) : go(nw_affine_kernel<8, 512>);
 }

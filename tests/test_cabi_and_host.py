@@ -52,6 +52,21 @@ def test_product_never_touches_the_oracle():
     assert "oracle" not in deps and "amdhip64" in deps
 
 
+def test_kernels_are_launched_through_the_one_checked_primitive():
+    """csrc/ names the launch macro once, in launch_on (asm_launch.h), and reads the launch error there; the only other reads are
+    the four that clear an error on purpose (pool_alloc, big_malloc and g3_prepare in asm_capi.hip, SamSortHold::alloc in asm_sam_sort.h)."""
+    csrc = os.path.join(ROOT, "approximate-string-matching_amd", "csrc")
+    counts = {"hipLaunchKernelGGL": {}, "hipGetLastError": {}}
+    for f in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, f), errors="ignore").read()
+        for word, per_file in counts.items():
+            if text.count(word):
+                per_file[f] = text.count(word)
+    assert counts["hipLaunchKernelGGL"] == {"asm_launch.h": 1}
+    assert counts["hipGetLastError"] == {"asm_launch.h": 1, "asm_capi.hip": 3, "asm_sam_sort.h": 1}
+    assert open(os.path.join(csrc, "asm_capi.hip")).read().count("(void)hipGetLastError();") == 3
+
+
 def test_generator_is_deterministic_and_sliceable(asm):
     cfg, _, _ = asm.workload("C2")
     a = asm.generate_pairs(cfg, 0, 3000)

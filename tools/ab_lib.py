@@ -1,7 +1,8 @@
 """Same-box A/B of two builds of the library (development tool, GPU box):
     PYTHONPATH=. python tools/ab_lib.py approximate-string-matching_amd/libasm_base.so approximate-string-matching_amd/libasm_mi355x.so C3:2e6 C2:1e6
 Each (library, workload) is timed in a fresh process (the library path is read at import), `rounds` times, interleaved; prints the
-per-kernel medians side by side.  LEAP is timed un-hinted and hinted by the Greedy penalties (the shape of C3's step)."""
+per-kernel medians side by side, each with the lowest and highest of its rounds (the spread of one library's own rounds is the noise
+a difference between two has to exceed); a child that fails ends the run.  LEAP is timed un-hinted and hinted by the Greedy penalties (the shape of C3's step)."""
 import json, os, statistics, subprocess, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,11 +40,10 @@ for r in range(rounds):
             env = dict(os.environ, ASM_MI355X_LIB=os.path.abspath(lib), PYTHONPATH=ROOT)
             p = subprocess.run([sys.executable, "-c", CHILD, name, n], env=env, capture_output=True, text=True, timeout=600)
             if p.returncode != 0:
-                print("FAILED", lib, w, p.stderr[-800:], flush=True)
-                continue
+                sys.exit("FAILED %s %s (exit %d)\n%s" % (lib, w, p.returncode, p.stderr[-800:]))  # nothing more on a device that faulted
             d = json.loads(p.stdout.strip().splitlines()[-1])
             for k, v in d.items():
                 res.setdefault((w, k), {}).setdefault(lib, []).append(v)
 for (w, k), by in sorted(res.items()):
-    row = "  ".join("%s %.4f" % (os.path.basename(l)[6:-3], statistics.median(v)) for l, v in by.items())
+    row = "  ".join("%s %.4f [%.4f..%.4f]" % (os.path.basename(l)[6:-3], statistics.median(v), min(v), max(v)) for l, v in by.items())
     print("%-10s %-18s %s" % (w, k, row), flush=True)
