@@ -137,6 +137,7 @@ MAP_HIT_DTYPE = np.dtype([("seq_id", np.int32), ("pos", np.uint32), ("end", np.u
 MAP_MAPPED, MAP_TOO_SHORT, MAP_SEED_CAPPED, MAP_CIGAR_TRUNCATED = 1, 2, 4, 8
 MAPQ_REFERENCE, MAPQ_GAP = 0, 1  # asm_map_set_mapq_model
 SAM_TAG_MD, MAP_MD_CAP = 1, 80  # asm_map_set_sam_tags; ASM_MAP_MD_CAP: an MD tag and its NUL always fit
+OUT_SAM, OUT_BAM, BGZF_PAYLOAD = 0, 1, 65280  # asm_map_set_output_format; ASM_BGZF_PAYLOAD: uncompressed bytes per BGZF block
 MAP_SECONDARY, MAP_HITS_TRUNCATED, MAP_MAX_HITS = 16, 32, 256
 MAP_PROPER_PAIR, MAP_RESCUED, MAP_MAX_INSERT = 64, 128, 8192
 MAP_MIN_K, MAP_MAX_K, MAP_MAX_READ, MAP_MAX_ERRORS = 8, 14, 511, 15
@@ -284,6 +285,10 @@ def load_library() -> ctypes.CDLL:
         "asm_map_last_mapq": (i32, [vp, vp, i64]),
         "asm_map_set_sam_tags": (i32, [vp, c.c_uint]),
         "asm_map_get_sam_tags": (c.c_uint, [vp]),
+        "asm_map_set_output_format": (i32, [vp, i32]),
+        "asm_map_get_output_format": (i32, [vp]),
+        "asm_bgzf_bound": (c.c_size_t, [c.c_size_t, i32]),
+        "asm_bgzf_frame": (i32, [vp, vp, c.c_size_t, i32, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
         "asm_md_format": (i32, [vp, i32, c.c_char_p, i32, c.c_char_p, i32, vp, c.c_size_t]),
         "asm_map_file": (i32, [vp, vp, c.POINTER(c.c_char_p), c.c_char_p, c.c_char_p, c.c_char_p, c.POINTER(MapParams), i32, i32, i64,
                                c.POINTER(MapFileStats)]),
@@ -633,6 +638,27 @@ class Engine:
     def sam_tags(self) -> int:
         """asm_map_get_sam_tags: the mask in force (SAM_TAG_MD)"""
         return int(self.lib.asm_map_get_sam_tags(self.h))
+
+    def set_output_format(self, fmt) -> None:
+        """asm_map_set_output_format: OUT_SAM / "sam" (the default) or OUT_BAM / "bam": what map_file and map_pairs_file (sorted or
+        not) write to sam_path.  BAM: the records encoded and BGZF-framed (stored blocks) on the device, and what they say is what
+        the SAM lines say (docs/design/mapper.md, "BAM output")."""
+        self._chk(self.lib.asm_map_set_output_format(self.h, {"sam": OUT_SAM, "bam": OUT_BAM}.get(fmt, fmt)))
+
+    @property
+    def output_format(self) -> int:
+        """asm_map_get_output_format: the format in force (OUT_SAM, OUT_BAM)"""
+        return int(self.lib.asm_map_get_output_format(self.h))
+
+    def bgzf_frame(self, data: bytes, eof: bool = True) -> bytes:
+        """asm_bgzf_frame: data in BGZF blocks of BGZF_PAYLOAD bytes (stored deflate, the last one shorter, none for b""), framed
+        by the device kernel of the BAM file calls; eof: the 28-byte EOF block behind them.  gzip.decompress gives data back."""
+        data = bytes(data)
+        cap = int(self.lib.asm_bgzf_bound(len(data), int(eof)))
+        out = ctypes.create_string_buffer(max(cap, 1))
+        got = ctypes.c_size_t(0)
+        self._chk(self.lib.asm_bgzf_frame(self.h, data if data else None, len(data), int(eof), out, cap, ctypes.byref(got)))
+        return out.raw[: got.value]
 
     def last_mapq(self, count: int) -> np.ndarray:
         """asm_map_last_mapq: uint8[count], the MAPQ of every record slot of the last in-memory library call, in its `out` layout"""

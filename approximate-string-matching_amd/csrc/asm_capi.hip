@@ -41,6 +41,7 @@
 #include "asm_map.h"
 #include "asm_fastq.h"
 #include "asm_sam.h"
+#include "asm_bam.h"
 #include "asm_fasta.h"
 
 /* What asm_run_benchmark_async (asm_step.h) keeps from call to call: the library's three streams beside the caller's, the events
@@ -126,6 +127,7 @@ struct asm_handle {
     std::vector<uint8_t> last_mapq;       /* asm_map_last_mapq: one byte per record slot of the last in-memory mapping call */
     bool last_mapq_valid = false;
     unsigned sam_tags = 0;                /* asm_map_set_sam_tags: the optional tags of the file calls' lines (ASM_SAM_TAG_MD) */
+    int out_format = 0;                   /* asm_map_set_output_format: what the file calls write, ASM_OUT_SAM or ASM_OUT_BAM */
     std::vector<hipEvent_t> prof_ev;      /* asm_profile_enable: 8 events per recorded asm_run_benchmark_async call */
     std::vector<unsigned> prof_mask;      /* which of a call's four kernels were launched */
     int prof_cap = 0;
@@ -1881,6 +1883,10 @@ int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, in
 
 /* ---- read mapping: host side in csrc/asm_map_host.h (kernels: csrc/asm_map.h, design: docs/design/mapper.md) -------------------- */
 #include "asm_map_host.h"
+/* the BGZF container of the file calls' BAM output: frame kernel, record stream, asm_bgzf_frame */
+#include "asm_bgzf.h"
+/* the output side of the file calls: the rotation of output slots and the report of a failed write */
+#include "asm_map_out.h"
 /* what the sorted file calls keep on the device, their sort and their gather */
 #include "asm_sam_sort.h"
 /* asm_map_file: FASTQ in, SAM out, through the same stages */

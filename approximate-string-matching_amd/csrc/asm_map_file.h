@@ -67,6 +67,7 @@ struct MapFileSession {
     } st = {};
     std::unique_ptr<asm_host::ChunkWriter> writer;
     std::unique_ptr<SamSortHold> sort; /* the sorted calls: the formatted chunks stay on the device until finish() (asm_sam_sort.h) */
+    std::unique_ptr<BgzfStream> bam;   /* ASM_OUT_BAM: the records are BAM's and leave through the BGZF record stream (asm_bgzf.h) */
     MapFileSession(asm_handle* owner, const char* call, size_t chunk_bytes)
         : h(owner), who(call), pipe(owner, call), d_names(owner), d_name_off(owner), chunk(chunk_bytes) {}
 
@@ -85,7 +86,6 @@ struct MapFileSession {
         }
         pipe.out = fopen(sam_path, "wb");
         if (!pipe.out) return bad(std::string("cannot write ") + sam_path);
-        if (header && *header && fwrite(header, 1, strlen(header), pipe.out) != strlen(header)) return bad("writing the SAM file failed");
         std::string names;
         std::vector<uint32_t> name_off(1, 0u);
         for (int32_t r = 0; r < ix->n_seqs; r++) {
@@ -93,6 +93,29 @@ struct MapFileSession {
             names += seq_names[r];
             name_off.push_back((uint32_t)names.size());
         }
+        std::vector<uint8_t> head; /* what the file starts with: the header as it is, or the BAM header in BGZF blocks of its own */
+        if (h->out_format == ASM_OUT_BAM) {
+            std::string text("BAM\1", 4);
+            const auto u32 = [&text](uint64_t v) {
+                for (int b = 0; b < 4; b++) text += (char)(v >> (8 * b));
+            };
+            const size_t l_text = header ? strlen(header) : 0;
+            if (l_text > 0x7fffffffull) return bad("a header of 2 GiB or more cannot be a BAM header", ASM_EUNSUPPORTED);
+            u32(l_text);
+            text.append(header ? header : "", l_text);
+            u32((uint64_t)ix->n_seqs);
+            for (int32_t r = 0; r < ix->n_seqs; r++) {
+                u32(strlen(seq_names[r]) + 1);
+                text.append(seq_names[r], strlen(seq_names[r]) + 1);
+                u32(asm_index_seq_len(ix, r));
+            }
+            bgzf_frame_host(text.data(), text.size(), 0, head);
+            bam.reset(new BgzfStream(h));
+            STREAM_TRY(who, bam->open());
+        } else if (header) {
+            head.assign(header, header + strlen(header));
+        }
+        if (!head.empty() && fwrite(head.data(), 1, head.size(), pipe.out) != head.size()) return map_out_failed(h, who);
         STREAM_TRY(who, d_names.alloc(names.size() + 16));
         STREAM_TRY(who, d_name_off.alloc(sizeof(uint32_t) * name_off.size()));
         STREAM_TRY(who, hipMemcpyAsync(d_names.p, names.data(), names.size(), hipMemcpyHostToDevice, h->stream));
@@ -139,9 +162,20 @@ struct MapFileSession {
      * chunk), and the shared fields of the call's stats */
     template <class Stats>
     int finish(Stats& out) {
-        if (sort)
-            if (const int rc = sort->flush(pipe, *writer, out_seq, chunk)) return rc;
-        if (!writer->finish() || fflush(pipe.out) != 0) return bad("writing the SAM file failed");
+        if (sort) {
+            size_t written = 0;
+            if (const int rc = sort->flush(pipe, *writer, out_seq, chunk, bam.get(), &written)) return rc;
+            st.bytes_out += (int64_t)written;
+        }
+        if (bam) { /* what the last chunk or slab left of the record stream, and the EOF block */
+            int o = 0;
+            const size_t bytes = bam->tail_bytes();
+            if (const int rc = map_out_slot(h, who, pipe, *writer, out_seq, bytes, &o)) return rc;
+            STREAM_TRY(who, bam->tail(pipe.d_out[o]));
+            if (const int rc = map_out_ship(h, who, pipe, *writer, out_seq, o, bytes)) return rc;
+            st.bytes_out += (int64_t)bytes;
+        }
+        if (!writer->finish() || fflush(pipe.out) != 0) return map_out_failed(h, who);
         out.chunks = st.chunks, out.bytes_in = st.bytes_in, out.bytes_out = st.bytes_out, out.records = st.records;
         out.seconds_read = st.seconds_read, out.seconds_write = writer->write_seconds();
         out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
@@ -156,9 +190,31 @@ struct MapFileJob { /* what every chunk of a file call shares; each call derives
 };
 
 /* the report of a chunk's smallest malformed record (1-based in its file); file: 1 or 2, 0 for the call that reads one */
+static int map_file_bad_record(MapFileSession& ss, int64_t record, int file, const char* what) {
+    return ss.bad("record " + std::to_string(record) + (file ? " of file " + std::to_string(file) : std::string()) + what);
+}
 static int map_file_malformed(MapFileSession& ss, int64_t record, int file) {
-    return ss.bad("record " + std::to_string(record) + (file ? " of file " + std::to_string(file) : std::string()) +
-                  " is malformed (line 1 of a record starts with '@', line 3 with '+')");
+    return map_file_bad_record(ss, record, file, " is malformed (line 1 of a record starts with '@', line 3 with '+')");
+}
+
+/* ASM_OUT_BAM, behind a chunk's malformed records and in front of its other errors: the chunk's smallest record whose QNAME no BAM
+ * record can hold (d_recs: the chunk's rn records; PAIRED: [2][rn], file 1 before file 2), reported as a malformed one is.  Under
+ * ASM_OUT_SAM nothing is launched. */
+template <bool PAIRED>
+static int map_file_bam_names(MapFileSession& ss, const char* d_raw, const SamRec* d_recs, int64_t rn, int64_t first_record) {
+    if (!ss.bam || rn == 0) return ASM_OK;
+    asm_handle* h = ss.h;
+    Scratch<uint32_t> d_long(h);
+    uint32_t min_long[2] = {FASTQ_NO_RECORD, FASTQ_NO_RECORD};
+    STREAM_TRY(ss.who, d_long.alloc(sizeof min_long));
+    STREAM_TRY(ss.who, hipMemsetAsync(d_long.p, 0xff, sizeof min_long, h->stream));
+    STREAM_TRY(ss.who, launch(h, bam_name_check_kernel<PAIRED>, grid_for((PAIRED ? 2 : 1) * rn), ASM_BLOCK, d_raw, d_recs, (long)rn, d_long.p));
+    STREAM_TRY(ss.who, fetch(h, {fetched(min_long, (const uint32_t*)d_long.p, 2)}));
+    for (int f = 0; f < 2; f++)
+        if (min_long[f] != FASTQ_NO_RECORD)
+            return map_file_bad_record(ss, first_record + min_long[f] + 1, PAIRED ? f + 1 : 0,
+                                       " has a QNAME of more than 254 bytes, which a BAM record cannot hold");
+    return ASM_OK;
 }
 
 /* The gather stage of one device chunk, for both file calls: n library reads of `bytes` bytes in all.  compact(d_start) launches
@@ -200,37 +256,28 @@ static int map_file_format(MapFileSession& ss, MapTmp& tmp, SamArgs& a, unsigned
     STREAM_TRY(who, hipMemsetAsync(d_n.p, 0, sizeof(unsigned long long) * NC, h->stream));
     a.names = ss.d_names.p, a.name_off = ss.d_name_off.p, a.size = d_size.p, a.off = d_off.p, a.n_mapped = d_n.p;
     if (PAIRED) a.n_proper = d_n.p + 1, a.n_rescued = d_n.p + 2;
-    STREAM_TRY(who, launch(h, sam_size_kernel<PAIRED>, grid_for(nlines + 1), ASM_BLOCK, a));
+    const bool bam = ss.bam != nullptr;
+    STREAM_TRY(who, launch(h, bam ? bam_size_kernel<PAIRED> : sam_size_kernel<PAIRED>, grid_for(nlines + 1), ASM_BLOCK, a));
     STREAM_TRY(who, map_exclusive_sum(h, tmp, d_size.p, d_off.p, nlines + 1));
     unsigned long long total = 0;
     STREAM_TRY(who, fetch(h, {fetched(&total, d_off.p + nlines), fetched(n, d_n.p, NC)}));
     if (ss.sort) { /* a sorted call: the lines are emitted into a block that stays on the device, and nothing is written yet */
-        if (const int rc = ss.sort->hold<PAIRED>(a, total)) return rc;
-        ss.st.records += nlines, ss.st.chunks++, ss.st.bytes_out += (int64_t)total;
+        if (const int rc = ss.sort->hold<PAIRED>(a, total, bam)) return rc;
+        ss.st.records += nlines, ss.st.chunks++;
+        if (!bam) ss.st.bytes_out += (int64_t)total; /* BAM: the framed bytes, known when the slabs are cut (finish()) */
         return ASM_OK;
     }
-    const int o = (int)(ss.out_seq % 3);
-    ss.writer->wait_idle(o);
-    if (ss.writer->failed()) return ss.bad("writing the SAM file failed");
-    pool_free(h, pp.d_out[o]);
-    pp.d_out[o] = nullptr;
-    if (pp.pin_out_cap[o] < total) {
-        if (pp.pin_out[o]) (void)hipHostFree(pp.pin_out[o]);
-        pp.pin_out[o] = nullptr, pp.pin_out_cap[o] = 0;
-        const size_t want = (size_t)total + (size_t)total / 4 + 4096;
-        STREAM_TRY(who, hipHostMalloc((void**)&pp.pin_out[o], want, hipHostMallocDefault));
-        pp.pin_out_cap[o] = want;
-    }
-    STREAM_TRY(who, pool_alloc(h, (void**)&pp.d_out[o], (size_t)total + 64));
+    /* BAM: the records go behind the stream's carry in a staging block, and what leaves is the whole blocks framed from it */
+    const size_t bytes = bam ? ss.bam->framed((size_t)total) : (size_t)total;
+    int o = 0;
+    if (const int rc = map_out_slot(h, who, pp, *ss.writer, ss.out_seq, bytes, &o)) return rc;
+    Scratch<char> d_stage(h);
     a.out = pp.d_out[o];
-    STREAM_TRY(who, launch(h, sam_emit_kernel<PAIRED>, map_grid((uint64_t)nlines * 64, h), 256, a));
-    STREAM_TRY(who, hipEventRecord(pp.ev_fmt[o], h->stream));
-    STREAM_TRY(who, hipStreamWaitEvent(pp.s_out, pp.ev_fmt[o], 0));
-    if (total) STREAM_TRY(who, hipMemcpyAsync(pp.pin_out[o], pp.d_out[o], (size_t)total, hipMemcpyDeviceToHost, pp.s_out));
-    STREAM_TRY(who, hipEventRecord(pp.ev_copied[o], pp.s_out));
-    ss.writer->push(o, pp.pin_out[o], (size_t)total);
-    ss.out_seq++;
-    ss.st.records += nlines, ss.st.chunks++, ss.st.bytes_out += (int64_t)total;
+    if (bam) STREAM_TRY(who, ss.bam->stage((size_t)total, d_stage, &a.out));
+    STREAM_TRY(who, launch(h, bam ? bam_emit_kernel<PAIRED> : sam_emit_kernel<PAIRED>, map_grid((uint64_t)nlines * 64, h), 256, a));
+    if (bam) STREAM_TRY(who, ss.bam->frame(d_stage, (size_t)total, pp.d_out[o]));
+    if (const int rc = map_out_ship(h, who, pp, *ss.writer, ss.out_seq, o, bytes)) return rc;
+    ss.st.records += nlines, ss.st.chunks++, ss.st.bytes_out += (int64_t)bytes;
     return ASM_OK;
 }
 
@@ -288,6 +335,7 @@ static int map_file_chunk(MapReadsFileJob& j, const char* d_raw, const uint32_t*
     FastqCounts counts = {FASTQ_NO_RECORD, 0};
     STREAM_TRY(who, fetch(h, {fetched(&tot[0], d_rd.p + rn), fetched(&tot[1], d_mo.p + rn), fetched(&counts, d_counts.p)}));
     if (counts.bad_min != FASTQ_NO_RECORD) return map_file_malformed(ss, first_record + counts.bad_min + 1, 0);
+    if (const int rc = map_file_bam_names<false>(ss, d_raw, d_recs.p, rn, first_record)) return rc;
     const int64_t ns = tot[0]; /* library reads */
     /* compact and gather: the reads in HBM, numbered in file order */
     MapFront f(h);

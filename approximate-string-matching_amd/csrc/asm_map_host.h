@@ -1064,6 +1064,16 @@ int asm_map_set_sam_tags(asm_handle* h, unsigned mask) { /* the mask is checked 
 
 unsigned asm_map_get_sam_tags(const asm_handle* h) { return h ? h->sam_tags : 0u; }
 
+int asm_map_set_output_format(asm_handle* h, int format) { /* the value is checked first, so that the check needs no device */
+    if (format != ASM_OUT_SAM && format != ASM_OUT_BAM)
+        return fail(h, ASM_EINVAL, "asm_map_set_output_format: format must be ASM_OUT_SAM (0) or ASM_OUT_BAM (1)");
+    if (!h) return fail(nullptr, ASM_EINVAL, "asm_map_set_output_format: NULL handle");
+    h->out_format = format;
+    return ASM_OK;
+}
+
+int asm_map_get_output_format(const asm_handle* h) { return h ? h->out_format : ASM_OUT_SAM; }
+
 int asm_md_format(const uint16_t* ops, int nops, const char* read_on_strand, int read_len, const char* ref_window, int ref_len,
                   char* out, size_t out_cap) {
     if (nops < 0 || read_len < 0 || ref_len < 0 || (nops > 0 && !ops) || (read_len > 0 && !read_on_strand) || (ref_len > 0 && !ref_window) ||

@@ -58,6 +58,7 @@ static int map_pairs_file_chunk(MapPairsFileJob& j, const char* d_raw, const uin
                               fetched(counts, d_counts.p, 2), fetched(&pcounts, d_pcounts.p)}));
     for (int f = 0; f < 2; f++)
         if (counts[f].bad_min != FASTQ_NO_RECORD) return map_file_malformed(ss, first_record + counts[f].bad_min + 1, f + 1);
+    if (const int rc = map_file_bam_names<true>(ss, d_raw, d_recs.p, rn, first_record)) return rc;
     if (pcounts.name_min != FASTQ_NO_RECORD)
         return ss.bad("the mates of record " + std::to_string(first_record + pcounts.name_min + 1) +
                       " have different names (QNAME is the first word without a trailing /1 or /2)");

@@ -74,6 +74,15 @@ SAM_HD char sam_src_byte(const char* s, uint32_t n, uint32_t idx, int mode) {
     return mode == SAM_COPY ? s[idx] : mode == SAM_UPPER ? sam_upper(s[idx]) : mode == SAM_REVERSE ? s[n - 1u - idx] : sam_comp(sam_upper(s[n - 1u - idx]));
 }
 
+/* bytes r .. r + 3 of the eight bytes lo, hi (little endian), r in [0, 3]: one v_alignbyte_b32 */
+SAM_HD uint32_t sam_funnel(uint32_t hi, uint32_t lo, uint32_t r) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbyte(hi, lo, r);
+#else
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8u * r));
+#endif
+}
+
 struct SamSizeSink {
     uint64_t cur = 0;
     SAM_HD void ch(char) { cur++; }

@@ -26,15 +26,6 @@ struct alignas(4) SamQuad {
     uint32_t w[4];
 };
 
-/* bytes r .. r + 3 of the eight bytes lo, hi (little endian), r in [0, 3]: one v_alignbyte_b32 */
-SAM_HD uint32_t sam_funnel(uint32_t hi, uint32_t lo, uint32_t r) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_alignbyte(hi, lo, r);
-#else
-    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8u * r));
-#endif
-}
-
 /* Lane g of SAM_GATHER_LANES copies its share of src[0, len) to dst[0, len); source and destination are byte-aligned independently.
  * Up to 15 head bytes bring the destination to a 16-byte boundary, one byte per lane; then 16-byte stores, lane g the chunks g, g +
  * 16, ...; then up to 15 tail bytes, one per lane.  A chunk's 16 source bytes lie anywhere: they are cut out of the five aligned
@@ -106,7 +97,10 @@ __global__ __launch_bounds__(256) void sam_line_gather_kernel(const unsigned lon
 }
 
 /* What a sorted call holds on the device, and its two steps: hold() in place of a chunk's copy-out, flush() after the last chunk.
- * Every allocation is counted against max_device_bytes first (cap; 0: none); the blocks go back to the pool with the session. */
+ * Every allocation of the hold (the held text, the line tables, the sort's arrays) is counted against max_device_bytes first (cap;
+ * 0: none); the blocks go back to the pool with the session.  Not counted, as in the unsorted call: the output slots of the rotation
+ * (at most a slab each) and, under ASM_OUT_BAM, a slab's staging block (the stream's carry of less than a BGZF block plus the
+ * slab), which lives for one slab. */
 struct SamSortHold {
     asm_handle* h;
     const char* who;
@@ -155,9 +149,10 @@ struct SamSortHold {
         used -= bytes;
     }
 
-    /* A chunk's `total` SAM bytes, sized and scanned (a.size, a.off): emitted into a block that stays, with the chunk's line tables */
+    /* A chunk's `total` SAM bytes (bam: BAM record bytes), sized and scanned (a.size, a.off): emitted into a block that stays, with
+     * the chunk's line tables */
     template <bool PAIRED>
-    int hold(SamArgs& a, unsigned long long total) {
+    int hold(SamArgs& a, unsigned long long total, bool bam) {
         const int64_t nlines = a.nlines;
         if ((uint64_t)st.lines + (uint64_t)nlines >= ((uint64_t)1 << 32)) return fail(h, ASM_EUNSUPPORTED, std::string(who) + ": 2^32 SAM lines or more");
         const size_t table = sizeof(unsigned long long) * (size_t)std::max<int64_t>(nlines, 1);
@@ -166,7 +161,7 @@ struct SamSortHold {
         for (unsigned long long** t : {&c.key, &c.src, &c.size})
             if (const int rc = alloc(t, table)) return rc;
         a.out = c.text;
-        STREAM_TRY(who, launch(h, sam_emit_kernel<PAIRED>, map_grid((uint64_t)nlines * 64, h), 256, a));
+        STREAM_TRY(who, launch(h, bam ? bam_emit_kernel<PAIRED> : sam_emit_kernel<PAIRED>, map_grid((uint64_t)nlines * 64, h), 256, a));
         if (nlines) STREAM_TRY(who, launch(h, sam_sort_key_kernel<PAIRED>, grid_for(nlines), ASM_BLOCK, a, n_seqs, c.key, c.src, c.size));
         chunks.push_back(c);
         st.lines += nlines, st.bytes_held += (int64_t)total;
@@ -174,9 +169,11 @@ struct SamSortHold {
     }
 
     /* After the last chunk: sort, offsets, and the lines gathered slab by slab (at most slab_cap bytes, or one line) into the pipe's
-     * output rotation; out_seq counts the writer's jobs.  The writer still has to be finished by the caller. */
+     * output rotation; out_seq counts the writer's jobs.  The writer still has to be finished by the caller.  bz: the BAM call's
+     * record stream; a slab is then gathered behind the stream's carry and leaves as the whole blocks framed from it, *framed bytes
+     * in all (not touched without bz). */
     template <class Pipe>
-    int flush(Pipe& pp, asm_host::ChunkWriter& writer, int64_t& out_seq, size_t slab_cap) {
+    int flush(Pipe& pp, asm_host::ChunkWriter& writer, int64_t& out_seq, size_t slab_cap, BgzfStream* bz, size_t* framed) {
         const auto t0 = std::chrono::steady_clock::now();
         const size_t n = (size_t)st.lines;
         if (n == 0) return ASM_OK;
@@ -228,28 +225,18 @@ struct SamSortHold {
         for (size_t s = 0; s + 1 < cuts.size(); s++) {
             const size_t i0 = cuts[s], cnt = cuts[s + 1] - i0;
             const size_t bytes = (size_t)(h_off[cuts[s + 1]] - h_off[i0]);
-            /* the next slot of the rotation, as map_file_format takes it: the writer is done with the job that used it */
-            const int o = (int)(out_seq % 3);
-            writer.wait_idle(o);
-            if (writer.failed()) return fail(h, ASM_EINVAL, std::string(who) + ": writing the SAM file failed");
-            pool_free(h, pp.d_out[o]);
-            pp.d_out[o] = nullptr;
-            if (pp.pin_out_cap[o] < bytes) {
-                if (pp.pin_out[o]) (void)hipHostFree(pp.pin_out[o]);
-                pp.pin_out[o] = nullptr, pp.pin_out_cap[o] = 0;
-                const size_t want = bytes + bytes / 4 + 4096;
-                STREAM_TRY(who, hipHostMalloc((void**)&pp.pin_out[o], want, hipHostMallocDefault));
-                pp.pin_out_cap[o] = want;
-            }
-            STREAM_TRY(who, pool_alloc(h, (void**)&pp.d_out[o], bytes + 64));
+            const size_t out_bytes = bz ? bz->framed(bytes) : bytes;
+            int o = 0;
+            if (const int rc = map_out_slot(h, who, pp, writer, out_seq, out_bytes, &o)) return rc;
+            Scratch<char> d_stage(h);
+            char* to = pp.d_out[o];
+            if (bz) STREAM_TRY(who, bz->stage(bytes, d_stage, &to));
             STREAM_TRY(who, launch(h, sam_line_gather_kernel, map_grid((uint64_t)cnt * SAM_GATHER_LANES, h), 256, (const u64*)psrc + i0,
-                                   (const u64*)off + i0, (long)cnt, (u64)h_off[i0], pp.d_out[o]));
-            STREAM_TRY(who, hipEventRecord(pp.ev_fmt[o], h->stream));
-            STREAM_TRY(who, hipStreamWaitEvent(pp.s_out, pp.ev_fmt[o], 0));
-            STREAM_TRY(who, hipMemcpyAsync(pp.pin_out[o], pp.d_out[o], bytes, hipMemcpyDeviceToHost, pp.s_out));
-            STREAM_TRY(who, hipEventRecord(pp.ev_copied[o], pp.s_out));
-            writer.push(o, pp.pin_out[o], bytes);
-            out_seq++, st.slabs++;
+                                   (const u64*)off + i0, (long)cnt, (u64)h_off[i0], to));
+            if (bz) STREAM_TRY(who, bz->frame(d_stage, bytes, pp.d_out[o]));
+            if (const int rc = map_out_ship(h, who, pp, writer, out_seq, o, out_bytes)) return rc;
+            st.slabs++;
+            if (bz) *framed += out_bytes;
         }
         st.seconds_sort = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         return ASM_OK;

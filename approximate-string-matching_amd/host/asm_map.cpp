@@ -25,6 +25,9 @@
 // streamed modes set the handle's tag mask (asm_map_set_sam_tags) and the library builds the tag on the device; the others call
 // asm_md_format per record, on the reference window from the text parsed here or, under --ref-stream, from asm_index_get_text.  Both
 // ways write the same file.
+// --bam (--stream and --stream-pairs only, with or without --sort) makes the library write BAM to -o (asm_map_set_output_format;
+// docs/design/mapper.md, "BAM output"): the same records, encoded and BGZF-framed in stored blocks on the device.  The header text
+// and every other option are as for SAM.  With any other mode it is a usage error.
 //   asm-map -r ref.fa --bench-ref N [--k 12]
 // maps nothing: it builds the index N times each way, alternately, and prints the seconds of every build.
 // --all-hits N writes up to N loci per read in rank order (asm_map_reads_all, strata S, default e): the primary record as without
@@ -67,6 +70,7 @@ static void usage() {
                     "       any of them with --ref-stream: the reference is read and parsed by the library\n"
                     "       any of them with --mapq reference|gap: the model of the MAPQ column (default reference)\n"
                     "       any of them with --md: MD:Z on every line that shows a CIGAR\n"
+                    "       --stream, --stream-pairs with --bam: BAM output (BGZF with stored blocks), encoded on the device\n"
                     "       any of them with --sort: coordinate-sorted output (--stream, --stream-pairs: on the device, [--sort-mem BYTES])\n");
     exit(2);
 }
@@ -429,7 +433,7 @@ int main(int argc, char** argv) {
     int k = 12;
     long chunk = 262144;
     int all_hits = 0, strata = -1; /* all_hits 0: the best hit only */
-    bool stream = false, stream_pairs = false, ref_stream = false, sort = false, md = false;
+    bool stream = false, stream_pairs = false, ref_stream = false, sort = false, md = false, bam = false;
     int bench_ref = 0;
     long long chunk_bytes = 0, sort_mem = -1;
     int mapq_model = ASM_MAPQ_REFERENCE;
@@ -462,6 +466,7 @@ int main(int argc, char** argv) {
         else if (s == "--chunk-bytes") chunk_bytes = atoll(val());
         else if (s == "--sort") sort = true;
         else if (s == "--md") md = true;
+        else if (s == "--bam") bam = true;
         else if (s == "--mapq") {
             const std::string m = val();
             if (m != "reference" && m != "gap") usage();
@@ -476,6 +481,10 @@ int main(int argc, char** argv) {
     const bool paired = !read2_path.empty();
     if (chunk_bytes < 0 || (chunk_bytes > 0 && !stream && !stream_pairs) || (stream && paired)) usage(); /* paired: --stream-pairs */
     if (stream_pairs && (!paired || all_hits || stream)) usage(); /* secondary pairs from files: not there */
+    if (bam && !stream && !stream_pairs) {
+        fprintf(stderr, "asm-map: --bam needs --stream or --stream-pairs (the library writes BAM from the streamed modes only)\n");
+        usage();
+    }
     if (sort_mem >= 0 && (!sort || (!stream && !stream_pairs))) usage(); /* --sort-mem: the device-side sort's */
     if (paired && (pp.min_insert < 0 || pp.max_insert < 0)) usage(); /* paired: --insert needed */
     if (!paired && (pp.min_insert >= 0 || pp.rescue_errors >= 0)) usage();
@@ -544,6 +553,7 @@ int main(int argc, char** argv) {
     int rc = asm_create(&h, 0);
     if (!rc) rc = asm_map_set_mapq_model(h, mapq_model);
     if (!rc && md && (stream || stream_pairs)) rc = asm_map_set_sam_tags(h, ASM_SAM_TAG_MD);
+    if (!rc && bam) rc = asm_map_set_output_format(h, ASM_OUT_BAM);
     if (!rc)
         rc = ref_stream ? asm_index_build_file(h, ref_path.c_str(), k, 0, &ix, nullptr)
                         : asm_index_build(h, text.data(), off.data(), (int32_t)names.size(), k, &ix);

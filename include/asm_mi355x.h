@@ -484,6 +484,31 @@ unsigned asm_map_get_sam_tags(const asm_handle* h);
 int asm_md_format(const uint16_t* ops, int nops, const char* read_on_strand, int read_len, const char* ref_window, int ref_len,
                   char* out, size_t out_cap);
 
+/* BAM output (docs/design/mapper.md, "BAM output"): the format is handle state, like the MAPQ model and the tag mask; ASM_OUT_SAM (the
+ * default) leaves every byte of every call as it is.  Under ASM_OUT_BAM the four file calls (asm_map_file, asm_map_pairs_file and
+ * their _sorted forms) write a BAM file to sam_path: the records say what the SAM lines say (SAM spec 4.2; integer tags in the
+ * smallest type, SEQ bytes outside =ACMGRSVTWYHKDBN as N, QUAL 0xff when its length is not SEQ's), encoded on the device, in a BGZF
+ * container of stored deflate blocks (what `samtools view -u` writes) framed on the device.  The uncompressed stream is the BAM header
+ * (magic, `header` as l_text and text, n_ref, the names of seq_names and the lengths of the index) in blocks of its own, then the
+ * records cut every ASM_BGZF_PAYLOAD bytes counted from the first record, then the 28-byte EOF block; the file does not depend on
+ * chunk_bytes, ASM_MAP_CHUNK or max_device_bytes.  Every other argument, error report and stats field keeps its meaning: bytes_out
+ * counts the file's bytes behind the header's blocks (EOF block included), asm_sam_sort_stats.bytes_held the record bytes held.  A
+ * QNAME longer than 254 bytes cannot be a BAM record: ASM_EINVAL, asm_last_error names the 1-based record (and the file, for pairs);
+ * among the errors of one device chunk it ranks behind a malformed record and before a name mismatch.
+ * asm_map_set_output_format: another value, or a NULL handle, is ASM_EINVAL; the value is checked first.
+ * asm_map_get_output_format: ASM_OUT_SAM for a NULL handle.
+ * asm_bgzf_bound:  the bytes asm_bgzf_frame writes for n input bytes; no device.
+ * asm_bgzf_frame:  src[0, n) (host) framed into dst (host) by the device kernel the file calls use: blocks of ASM_BGZF_PAYLOAD bytes,
+ *                  the last one shorter, none at all for n = 0; with_eof: the EOF block behind them.  *dst_len = asm_bgzf_bound(n,
+ *                  with_eof).  A dst_cap below that is ASM_EINVAL, and nothing is written.  Synchronous. */
+#define ASM_OUT_SAM 0
+#define ASM_OUT_BAM 1
+#define ASM_BGZF_PAYLOAD 65280
+int asm_map_set_output_format(asm_handle* h, int format);
+int asm_map_get_output_format(const asm_handle* h);
+size_t asm_bgzf_bound(size_t n, int with_eof);
+int asm_bgzf_frame(asm_handle* h, const void* src, size_t n, int with_eof, void* dst, size_t dst_cap, size_t* dst_len);
+
 /* asm_map_file:    a FASTQ file in, a SAM file out (docs/design/mapper.md, "Files: FASTQ in, SAM out"); single-end, synchronous.  The
  *                  file is read in chunks of about chunk_bytes (0: 16 MiB) cut at record boundaries; a chunk is parsed, mapped
  *                  and formatted on the device while the next one is read and copied in and the one before is copied out and
