@@ -1003,13 +1003,17 @@ class Engine:
                                            fo.ctypes.data, ctypes.byref(params), greedy_mode, out.ctypes.data))
         return out
 
+    def greedy_cigar_async(self, batch: DeviceBatch, params: Params, d_pen: int, d_ops: int, cap: int, d_nops: int) -> None:
+        """asm_greedy_cigar_batch_async into caller buffers (enqueue only): d_pen = device int32[n], d_ops = device uint16[n][cap]
+        (count << 3 | op, see decode_cigars), d_nops = device uint8[n] (above cap: the row was truncated)."""
+        self._chk(self.lib.asm_greedy_cigar_batch_async(self.h, batch.ptr, ctypes.byref(params), d_pen, d_ops, int(cap), d_nops))
+
     def greedy_with_cigar(self, batch: DeviceBatch, params: Params, cap: int = 48):
         """-> (costs int32[n], CIGAR strings) — hurdle_matrix::get_cost / get_CIGAR for every pair of the batch."""
         n = batch.n
         d_pen, d_ops, d_nops = self.malloc(4 * max(n, 1)), self.malloc(2 * cap * max(n, 1)), self.malloc(max(n, 1))
         try:
-            self._chk(self.lib.asm_greedy_cigar_batch_async(self.h, batch.ptr, ctypes.byref(params), d_pen, d_ops, cap,
-                                                            d_nops))
+            self.greedy_cigar_async(batch, params, d_pen, d_ops, cap, d_nops)
             costs = self.to_host(d_pen, n)
             ops = self.to_host(d_ops, n * cap, np.uint16).reshape(n, cap)
             nops = self.to_host(d_nops, n, np.uint8)
