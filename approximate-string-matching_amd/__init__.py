@@ -138,6 +138,7 @@ MAP_MAPPED, MAP_TOO_SHORT, MAP_SEED_CAPPED, MAP_CIGAR_TRUNCATED = 1, 2, 4, 8
 MAPQ_REFERENCE, MAPQ_GAP = 0, 1  # asm_map_set_mapq_model
 SAM_TAG_MD, MAP_MD_CAP = 1, 80  # asm_map_set_sam_tags; ASM_MAP_MD_CAP: an MD tag and its NUL always fit
 OUT_SAM, OUT_BAM, BGZF_PAYLOAD = 0, 1, 65280  # asm_map_set_output_format; ASM_BGZF_PAYLOAD: uncompressed bytes per BGZF block
+BGZF_STORED, BGZF_DEFLATE = 0, 1  # asm_map_set_bgzf_level: the BAM container's blocks
 MAP_SECONDARY, MAP_HITS_TRUNCATED, MAP_MAX_HITS = 16, 32, 256
 MAP_PROPER_PAIR, MAP_RESCUED, MAP_MAX_INSERT = 64, 128, 8192
 MAP_MIN_K, MAP_MAX_K, MAP_MAX_READ, MAP_MAX_ERRORS = 8, 14, 511, 15
@@ -289,6 +290,10 @@ def load_library() -> ctypes.CDLL:
         "asm_map_get_output_format": (i32, [vp]),
         "asm_bgzf_bound": (c.c_size_t, [c.c_size_t, i32]),
         "asm_bgzf_frame": (i32, [vp, vp, c.c_size_t, i32, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
+        "asm_map_set_bgzf_level": (i32, [vp, i32]),
+        "asm_map_get_bgzf_level": (i32, [vp]),
+        "asm_bgzf_compress": (i32, [vp, vp, c.c_size_t, i32, i32, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
+        "asm_bgzf_compress_host": (i32, [vp, c.c_size_t, i32, i32, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
         "asm_md_format": (i32, [vp, i32, c.c_char_p, i32, c.c_char_p, i32, vp, c.c_size_t]),
         "asm_map_file": (i32, [vp, vp, c.POINTER(c.c_char_p), c.c_char_p, c.c_char_p, c.c_char_p, c.POINTER(MapParams), i32, i32, i64,
                                c.POINTER(MapFileStats)]),
@@ -658,6 +663,27 @@ class Engine:
         out = ctypes.create_string_buffer(max(cap, 1))
         got = ctypes.c_size_t(0)
         self._chk(self.lib.asm_bgzf_frame(self.h, data if data else None, len(data), int(eof), out, cap, ctypes.byref(got)))
+        return out.raw[: got.value]
+
+    def set_bgzf_level(self, level) -> None:
+        """asm_map_set_bgzf_level: BGZF_STORED / "stored" (the default) or BGZF_DEFLATE / "deflate": the blocks of the BAM file the
+        file calls write.  Deflate: every block encoded on the device as the smallest of a stored, a fixed-Huffman and a
+        dynamic-Huffman deflate block (docs/design/mapper.md, "Deflate"); the uncompressed stream and its cut stay the same.  No
+        effect under OUT_SAM."""
+        self._chk(self.lib.asm_map_set_bgzf_level(self.h, {"stored": BGZF_STORED, "deflate": BGZF_DEFLATE}.get(level, level)))
+
+    def get_bgzf_level(self) -> int:
+        """asm_map_get_bgzf_level: the level in force (BGZF_STORED, BGZF_DEFLATE)"""
+        return int(self.lib.asm_map_get_bgzf_level(self.h))
+
+    def bgzf_compress(self, data: bytes, eof: bool = True, level: int = BGZF_DEFLATE) -> bytes:
+        """asm_bgzf_compress: bgzf_frame with a level, by the device kernels of the BAM file calls.  Level BGZF_STORED gives
+        bgzf_frame's bytes; BGZF_DEFLATE the bytes of bgzf_compress_host.  gzip.decompress gives data back."""
+        data = bytes(data)
+        cap = int(self.lib.asm_bgzf_bound(len(data), int(eof)))
+        out = ctypes.create_string_buffer(max(cap, 1))
+        got = ctypes.c_size_t(0)
+        self._chk(self.lib.asm_bgzf_compress(self.h, data if data else None, len(data), int(eof), int(level), out, cap, ctypes.byref(got)))
         return out.raw[: got.value]
 
     def last_mapq(self, count: int) -> np.ndarray:
@@ -1120,6 +1146,19 @@ def md_format(ops, read_on_strand, ref_window) -> str:
     if n < 0:
         raise AsmError(n, load_library().asm_last_error(None).decode())
     return out.raw[:n].decode("ascii")
+
+
+def bgzf_compress_host(data: bytes, eof: bool = True, level: int = BGZF_DEFLATE) -> bytes:
+    """asm_bgzf_compress_host: Engine.bgzf_compress without a device, by the host build of the same encoder; the same bytes"""
+    lib = load_library()
+    data = bytes(data)
+    cap = int(lib.asm_bgzf_bound(len(data), int(eof)))
+    out = ctypes.create_string_buffer(max(cap, 1))
+    got = ctypes.c_size_t(0)
+    rc = lib.asm_bgzf_compress_host(data if data else None, len(data), int(eof), int(level), out, cap, ctypes.byref(got))
+    if rc != 0:
+        raise AsmError(rc, lib.asm_last_error(None).decode())
+    return out.raw[: got.value]
 
 
 class Timer:

@@ -9,6 +9,9 @@
 // precomputed x^(512 m), the products are XOR-reduced, and one more multiplication by x^(8 * last slice's length) brings the sum to
 // the end.
 //
+// At ASM_BGZF_DEFLATE the blocks are deflate blocks instead: asm_deflate.h, which this file includes behind its first part, holds the
+// encoder, its kernel and the compaction; the device entry (bgzf_deflate_device), the record stream and the C entry points are here.
+//
 // The first part holds no HIP: the tables, the slice width, a slice's CRC, load and store, the multiplication and the block's fixed
 // bytes.  The host frames the BAM header's blocks with it (bgzf_frame_host runs the same per-slice code serially), and
 // host/bam_host_check.cpp compiles it with plain g++ under ASan + UBSan (tests/test_bam_host.py).
@@ -186,8 +189,12 @@ inline void bgzf_frame_host(const void* src, size_t n, int with_eof, std::vector
 }
 
 #if defined(__HIPCC__)
-
 __device__ const BgzfTables bgzf_device_tables = bgzf_make_tables();
+#endif
+
+#include "asm_deflate.h"
+
+#if defined(__HIPCC__)
 
 /* Workgroup b < nblocks frames src[b * BGZF_PAYLOAD, ...) (the last block: what is left of n) into dst + b * BGZF_BLOCK; workgroup
  * nblocks, when the grid has one, writes the EOF block behind them.  src: 16-byte aligned, readable to the next multiple of 16
@@ -235,15 +242,51 @@ static hipError_t bgzf_frame_device(asm_handle* h, const char* src, size_t n, in
                   (uint32_t)nblocks, (uint8_t*)dst);
 }
 
+/* The same at ASM_BGZF_DEFLATE: the blocks encoded at a fixed stride (bgzf_deflate_kernel), their sizes summed, the blocks moved
+ * together into dst (bgzf_compact_kernel) with the EOF block behind them when with_eof, and the bytes written read back into *total
+ * (one wait).  dst holds bgzf_bound(n, with_eof) bytes.  Nothing to encode launches nothing and waits for nothing. */
+static hipError_t bgzf_deflate_device(asm_handle* h, const char* src, size_t n, int with_eof, char* dst, size_t* total) {
+    typedef unsigned long long u64;
+    const size_t nblocks = bgzf_blocks(n);
+    *total = 0;
+    if (nblocks + (with_eof ? 1 : 0) == 0) return hipSuccess;
+    Scratch<uint8_t> d_tmp(h);
+    Scratch<u64> d_size(h), d_off(h);
+    MapTmp tmp(h);
+    hipError_t e = d_tmp.alloc(nblocks * DFL_STRIDE + 16);
+    if (e == hipSuccess) e = d_size.alloc(sizeof(u64) * (nblocks + 1));
+    if (e == hipSuccess) e = d_off.alloc(sizeof(u64) * (nblocks + 1));
+    if (e == hipSuccess) e = hipMemsetAsync(d_size.p + nblocks, 0, sizeof(u64), h->stream);
+    if (e == hipSuccess && nblocks)
+        e = launch(h, bgzf_deflate_kernel, (unsigned)nblocks, BGZF_THREADS, (const uint8_t*)src, (u64)n, (uint32_t)nblocks, d_tmp.p, d_size.p);
+    if (e == hipSuccess) e = map_exclusive_sum(h, tmp, d_size.p, d_off.p, (int64_t)nblocks + 1);
+    if (e == hipSuccess)
+        e = launch(h, bgzf_compact_kernel, (unsigned)(nblocks + (with_eof ? 1 : 0)), BGZF_THREADS, (const uint8_t*)d_tmp.p, (const u64*)d_size.p,
+                   (const u64*)d_off.p, (uint32_t)nblocks, (uint8_t*)dst);
+    u64 end = 0;
+    if (e == hipSuccess) e = fetch(h, {fetched(&end, (const u64*)d_off.p + nblocks)});
+    *total = (size_t)end + (with_eof ? BGZF_EOF : 0u);
+    return e;
+}
+/* src framed into dst at `level`; *total: the bytes written (ASM_BGZF_STORED: the bound, with no wait) */
+static hipError_t bgzf_level_device(asm_handle* h, int level, const char* src, size_t n, int with_eof, char* dst, size_t* total) {
+    if (level == ASM_BGZF_DEFLATE) return bgzf_deflate_device(h, src, n, with_eof, dst, total);
+    *total = bgzf_bound(n, with_eof);
+    return bgzf_frame_device(h, src, n, with_eof, dst);
+}
+
 /* The record stream of one BAM file call.  It is cut every BGZF_PAYLOAD bytes counted from its first byte, whatever the device
  * chunks or sorted slabs are that bring it: what a chunk leaves behind its last whole block stays in `carry` on the device and leads
  * the next one.  Per chunk: stage(n) gives a buffer with the carry in front and room for the chunk's n bytes; the caller fills those
- * and calls frame(), which writes framed(n) bytes of whole blocks and keeps the rest.  tail() frames what is left and the EOF block. */
+ * and calls frame(), which writes at most framed(n) bytes of whole blocks and keeps the rest.  tail() frames what is left and the EOF
+ * block, at most tail_bytes().  Both give the bytes they wrote: the bound at ASM_BGZF_STORED, what the encoder made of it at
+ * ASM_BGZF_DEFLATE (read back with one wait). */
 struct BgzfStream {
     asm_handle* h;
     Scratch<char> carry;
     size_t carry_len = 0;
-    explicit BgzfStream(asm_handle* owner) : h(owner), carry(owner) {}
+    const int level;
+    explicit BgzfStream(asm_handle* owner) : h(owner), carry(owner), level(owner->bgzf_level) {}
     hipError_t open() { return carry.alloc(BGZF_PAYLOAD + BGZF_SRC_PAD); }
     size_t framed(size_t n) const { return (carry_len + n) / BGZF_PAYLOAD * BGZF_BLOCK; }
     size_t tail_bytes() const { return bgzf_bound(carry_len, 1); }
@@ -252,14 +295,14 @@ struct BgzfStream {
         *fresh = buf.p + carry_len;
         return carry_len ? hipMemcpyAsync(buf.p, carry.p, carry_len, hipMemcpyDeviceToDevice, h->stream) : hipSuccess;
     }
-    hipError_t frame(const Scratch<char>& buf, size_t n, char* dst) {
+    hipError_t frame(const Scratch<char>& buf, size_t n, char* dst, size_t* written) {
         const size_t whole = (carry_len + n) / BGZF_PAYLOAD * BGZF_PAYLOAD, rest = carry_len + n - whole;
-        if (const hipError_t e = bgzf_frame_device(h, buf.p, whole, 0, dst)) return e;
+        if (const hipError_t e = bgzf_level_device(h, level, buf.p, whole, 0, dst, written)) return e;
         carry_len = rest;
         return rest ? hipMemcpyAsync(carry.p, buf.p + whole, rest, hipMemcpyDeviceToDevice, h->stream) : hipSuccess;
     }
-    hipError_t tail(char* dst) {
-        const hipError_t e = bgzf_frame_device(h, carry.p, carry_len, 1, dst);
+    hipError_t tail(char* dst, size_t* written) {
+        const hipError_t e = bgzf_level_device(h, level, carry.p, carry_len, 1, dst, written);
         carry_len = 0;
         return e;
     }
@@ -274,23 +317,59 @@ static_assert(ASM_BGZF_PAYLOAD == BGZF_PAYLOAD, "the ABI's ASM_BGZF_PAYLOAD is t
 
 size_t asm_bgzf_bound(size_t n, int with_eof) { return bgzf_bound(n, with_eof); }
 
-int asm_bgzf_frame(asm_handle* h, const void* src, size_t n, int with_eof, void* dst, size_t dst_cap, size_t* dst_len) {
-    const char* who = "asm_bgzf_frame";
-    if (!h || (n && !src) || !dst_len) return fail(h, ASM_EINVAL, "asm_bgzf_frame: NULL argument");
+static int bgzf_level_check(asm_handle* h, const std::string& who, int level) {
+    if (level != ASM_BGZF_STORED && level != ASM_BGZF_DEFLATE)
+        return fail(h, ASM_EINVAL, who + ": level must be ASM_BGZF_STORED (0) or ASM_BGZF_DEFLATE (1)");
+    return ASM_OK;
+}
+int asm_map_set_bgzf_level(asm_handle* h, int level) {
+    if (const int rc = bgzf_level_check(h, "asm_map_set_bgzf_level", level)) return rc;
+    if (!h) return fail(h, ASM_EINVAL, "asm_map_set_bgzf_level: NULL handle");
+    h->bgzf_level = level;
+    return ASM_OK;
+}
+int asm_map_get_bgzf_level(const asm_handle* h) { return h ? h->bgzf_level : ASM_BGZF_STORED; }
+
+/* asm_bgzf_frame and asm_bgzf_compress (`name`) */
+static int bgzf_frame_call(const char* name, asm_handle* h, const void* src, size_t n, int with_eof, int level, void* dst, size_t dst_cap,
+                           size_t* dst_len) {
+    const char* who = name;
+    const std::string call = name;
+    if (const int rc = bgzf_level_check(h, call, level)) return rc;
+    if (!h || (n && !src) || !dst_len) return fail(h, ASM_EINVAL, call + ": NULL argument");
     const size_t need = bgzf_bound(n, with_eof);
-    if (dst_cap < need || (need && !dst))
-        return fail(h, ASM_EINVAL, "asm_bgzf_frame: dst_cap is below asm_bgzf_bound (" + std::to_string(need) + " bytes)");
-    if (bgzf_blocks(n) >= 0xffffffffull) return fail(h, ASM_EUNSUPPORTED, "asm_bgzf_frame: 2^32 blocks or more");
+    if (dst_cap < need || (need && !dst)) return fail(h, ASM_EINVAL, call + ": dst_cap is below asm_bgzf_bound (" + std::to_string(need) + " bytes)");
+    if (bgzf_blocks(n) >= 0xffffffffull) return fail(h, ASM_EUNSUPPORTED, call + ": 2^32 blocks or more");
     *dst_len = 0;
     HIPCHK(h, hipSetDevice(h->device));
     Scratch<char> d_src(h), d_dst(h);
     STREAM_TRY(who, d_src.alloc(n + BGZF_SRC_PAD));
     STREAM_TRY(who, d_dst.alloc(need + 1));
     if (n) STREAM_TRY(who, hipMemcpyAsync(d_src.p, src, n, hipMemcpyHostToDevice, h->stream));
-    STREAM_TRY(who, bgzf_frame_device(h, d_src.p, n, with_eof, d_dst.p));
-    if (need) STREAM_TRY(who, hipMemcpyAsync(dst, d_dst.p, need, hipMemcpyDeviceToHost, h->stream));
+    size_t written = 0;
+    STREAM_TRY(who, bgzf_level_device(h, level, d_src.p, n, with_eof, d_dst.p, &written));
+    if (written) STREAM_TRY(who, hipMemcpyAsync(dst, d_dst.p, written, hipMemcpyDeviceToHost, h->stream));
     STREAM_TRY(who, hipStreamSynchronize(h->stream));
-    *dst_len = need;
+    *dst_len = written;
+    return ASM_OK;
+}
+int asm_bgzf_frame(asm_handle* h, const void* src, size_t n, int with_eof, void* dst, size_t dst_cap, size_t* dst_len) {
+    return bgzf_frame_call("asm_bgzf_frame", h, src, n, with_eof, ASM_BGZF_STORED, dst, dst_cap, dst_len);
+}
+int asm_bgzf_compress(asm_handle* h, const void* src, size_t n, int with_eof, int level, void* dst, size_t dst_cap, size_t* dst_len) {
+    return bgzf_frame_call("asm_bgzf_compress", h, src, n, with_eof, level, dst, dst_cap, dst_len);
+}
+int asm_bgzf_compress_host(const void* src, size_t n, int with_eof, int level, void* dst, size_t dst_cap, size_t* dst_len) {
+    const std::string call = "asm_bgzf_compress_host";
+    if (const int rc = bgzf_level_check(nullptr, call, level)) return rc;
+    if ((n && !src) || !dst_len) return fail(nullptr, ASM_EINVAL, call + ": NULL argument");
+    const size_t need = bgzf_bound(n, with_eof);
+    if (dst_cap < need || (need && !dst)) return fail(nullptr, ASM_EINVAL, call + ": dst_cap is below asm_bgzf_bound (" + std::to_string(need) + " bytes)");
+    *dst_len = 0;
+    std::vector<uint8_t> out;
+    bgzf_compress_host(src, n, with_eof, level, out, nullptr);
+    if (!out.empty()) memcpy(dst, out.data(), out.size());
+    *dst_len = out.size();
     return ASM_OK;
 }
 #endif /* __HIPCC__ */

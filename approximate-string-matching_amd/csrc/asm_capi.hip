@@ -128,6 +128,7 @@ struct asm_handle {
     bool last_mapq_valid = false;
     unsigned sam_tags = 0;                /* asm_map_set_sam_tags: the optional tags of the file calls' lines (ASM_SAM_TAG_MD) */
     int out_format = 0;                   /* asm_map_set_output_format: what the file calls write, ASM_OUT_SAM or ASM_OUT_BAM */
+    int bgzf_level = 0;                   /* asm_map_set_bgzf_level: the BAM container's blocks, ASM_BGZF_STORED or ASM_BGZF_DEFLATE */
     std::vector<hipEvent_t> prof_ev;      /* asm_profile_enable: 8 events per recorded asm_run_benchmark_async call */
     std::vector<unsigned> prof_mask;      /* which of a call's four kernels were launched */
     int prof_cap = 0;

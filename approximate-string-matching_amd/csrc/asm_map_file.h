@@ -109,7 +109,7 @@ struct MapFileSession {
                 text.append(seq_names[r], strlen(seq_names[r]) + 1);
                 u32(asm_index_seq_len(ix, r));
             }
-            bgzf_frame_host(text.data(), text.size(), 0, head);
+            bgzf_compress_host(text.data(), text.size(), 0, h->bgzf_level, head, nullptr);
             bam.reset(new BgzfStream(h));
             STREAM_TRY(who, bam->open());
         } else if (header) {
@@ -169,9 +169,9 @@ struct MapFileSession {
         }
         if (bam) { /* what the last chunk or slab left of the record stream, and the EOF block */
             int o = 0;
-            const size_t bytes = bam->tail_bytes();
-            if (const int rc = map_out_slot(h, who, pipe, *writer, out_seq, bytes, &o)) return rc;
-            STREAM_TRY(who, bam->tail(pipe.d_out[o]));
+            size_t bytes = 0;
+            if (const int rc = map_out_slot(h, who, pipe, *writer, out_seq, bam->tail_bytes(), &o)) return rc;
+            STREAM_TRY(who, bam->tail(pipe.d_out[o], &bytes));
             if (const int rc = map_out_ship(h, who, pipe, *writer, out_seq, o, bytes)) return rc;
             st.bytes_out += (int64_t)bytes;
         }
@@ -267,15 +267,16 @@ static int map_file_format(MapFileSession& ss, MapTmp& tmp, SamArgs& a, unsigned
         if (!bam) ss.st.bytes_out += (int64_t)total; /* BAM: the framed bytes, known when the slabs are cut (finish()) */
         return ASM_OK;
     }
-    /* BAM: the records go behind the stream's carry in a staging block, and what leaves is the whole blocks framed from it */
-    const size_t bytes = bam ? ss.bam->framed((size_t)total) : (size_t)total;
+    /* BAM: the records go behind the stream's carry in a staging block, and what leaves is the whole blocks framed from it: the slot
+     * has room for their stored form, and `bytes` becomes what the container's level made of them */
+    size_t bytes = bam ? ss.bam->framed((size_t)total) : (size_t)total;
     int o = 0;
     if (const int rc = map_out_slot(h, who, pp, *ss.writer, ss.out_seq, bytes, &o)) return rc;
     Scratch<char> d_stage(h);
     a.out = pp.d_out[o];
     if (bam) STREAM_TRY(who, ss.bam->stage((size_t)total, d_stage, &a.out));
     STREAM_TRY(who, launch(h, bam ? bam_emit_kernel<PAIRED> : sam_emit_kernel<PAIRED>, map_grid((uint64_t)nlines * 64, h), 256, a));
-    if (bam) STREAM_TRY(who, ss.bam->frame(d_stage, (size_t)total, pp.d_out[o]));
+    if (bam) STREAM_TRY(who, ss.bam->frame(d_stage, (size_t)total, pp.d_out[o], &bytes));
     if (const int rc = map_out_ship(h, who, pp, *ss.writer, ss.out_seq, o, bytes)) return rc;
     ss.st.records += nlines, ss.st.chunks++, ss.st.bytes_out += (int64_t)bytes;
     return ASM_OK;

@@ -225,7 +225,7 @@ struct SamSortHold {
         for (size_t s = 0; s + 1 < cuts.size(); s++) {
             const size_t i0 = cuts[s], cnt = cuts[s + 1] - i0;
             const size_t bytes = (size_t)(h_off[cuts[s + 1]] - h_off[i0]);
-            const size_t out_bytes = bz ? bz->framed(bytes) : bytes;
+            size_t out_bytes = bz ? bz->framed(bytes) : bytes; /* BAM: the slot's room, then what the container's level wrote */
             int o = 0;
             if (const int rc = map_out_slot(h, who, pp, writer, out_seq, out_bytes, &o)) return rc;
             Scratch<char> d_stage(h);
@@ -233,7 +233,7 @@ struct SamSortHold {
             if (bz) STREAM_TRY(who, bz->stage(bytes, d_stage, &to));
             STREAM_TRY(who, launch(h, sam_line_gather_kernel, map_grid((uint64_t)cnt * SAM_GATHER_LANES, h), 256, (const u64*)psrc + i0,
                                    (const u64*)off + i0, (long)cnt, (u64)h_off[i0], to));
-            if (bz) STREAM_TRY(who, bz->frame(d_stage, bytes, pp.d_out[o]));
+            if (bz) STREAM_TRY(who, bz->frame(d_stage, bytes, pp.d_out[o], &out_bytes));
             if (const int rc = map_out_ship(h, who, pp, writer, out_seq, o, out_bytes)) return rc;
             st.slabs++;
             if (bz) *framed += out_bytes;

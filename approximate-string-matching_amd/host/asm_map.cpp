@@ -27,7 +27,8 @@
 // ways write the same file.
 // --bam (--stream and --stream-pairs only, with or without --sort) makes the library write BAM to -o (asm_map_set_output_format;
 // docs/design/mapper.md, "BAM output"): the same records, encoded and BGZF-framed in stored blocks on the device.  The header text
-// and every other option are as for SAM.  With any other mode it is a usage error.
+// and every other option are as for SAM.  With any other mode it is a usage error.  --bam-level 0|1 (with --bam; default 0) is the
+// container's level (asm_map_set_bgzf_level; docs/design/mapper.md, "Deflate"): 1 deflates every block on the device.
 //   asm-map -r ref.fa --bench-ref N [--k 12]
 // maps nothing: it builds the index N times each way, alternately, and prints the seconds of every build.
 // --all-hits N writes up to N loci per read in rank order (asm_map_reads_all, strata S, default e): the primary record as without
@@ -71,6 +72,7 @@ static void usage() {
                     "       any of them with --mapq reference|gap: the model of the MAPQ column (default reference)\n"
                     "       any of them with --md: MD:Z on every line that shows a CIGAR\n"
                     "       --stream, --stream-pairs with --bam: BAM output (BGZF with stored blocks), encoded on the device\n"
+                    "       --bam with --bam-level 0|1: 0 (default) stored blocks, 1 deflate blocks compressed on the device\n"
                     "       any of them with --sort: coordinate-sorted output (--stream, --stream-pairs: on the device, [--sort-mem BYTES])\n");
     exit(2);
 }
@@ -434,6 +436,7 @@ int main(int argc, char** argv) {
     long chunk = 262144;
     int all_hits = 0, strata = -1; /* all_hits 0: the best hit only */
     bool stream = false, stream_pairs = false, ref_stream = false, sort = false, md = false, bam = false;
+    int bam_level = -1; /* --bam-level: not given */
     int bench_ref = 0;
     long long chunk_bytes = 0, sort_mem = -1;
     int mapq_model = ASM_MAPQ_REFERENCE;
@@ -467,6 +470,11 @@ int main(int argc, char** argv) {
         else if (s == "--sort") sort = true;
         else if (s == "--md") md = true;
         else if (s == "--bam") bam = true;
+        else if (s == "--bam-level") {
+            const std::string v = val();
+            if (v != "0" && v != "1") usage();
+            bam_level = v == "1" ? ASM_BGZF_DEFLATE : ASM_BGZF_STORED;
+        }
         else if (s == "--mapq") {
             const std::string m = val();
             if (m != "reference" && m != "gap") usage();
@@ -483,6 +491,10 @@ int main(int argc, char** argv) {
     if (stream_pairs && (!paired || all_hits || stream)) usage(); /* secondary pairs from files: not there */
     if (bam && !stream && !stream_pairs) {
         fprintf(stderr, "asm-map: --bam needs --stream or --stream-pairs (the library writes BAM from the streamed modes only)\n");
+        usage();
+    }
+    if (bam_level >= 0 && !bam) {
+        fprintf(stderr, "asm-map: --bam-level needs --bam (the level is the BAM container's)\n");
         usage();
     }
     if (sort_mem >= 0 && (!sort || (!stream && !stream_pairs))) usage(); /* --sort-mem: the device-side sort's */
@@ -554,6 +566,7 @@ int main(int argc, char** argv) {
     if (!rc) rc = asm_map_set_mapq_model(h, mapq_model);
     if (!rc && md && (stream || stream_pairs)) rc = asm_map_set_sam_tags(h, ASM_SAM_TAG_MD);
     if (!rc && bam) rc = asm_map_set_output_format(h, ASM_OUT_BAM);
+    if (!rc && bam_level >= 0) rc = asm_map_set_bgzf_level(h, bam_level);
     if (!rc)
         rc = ref_stream ? asm_index_build_file(h, ref_path.c_str(), k, 0, &ix, nullptr)
                         : asm_index_build(h, text.data(), off.data(), (int32_t)names.size(), k, &ix);

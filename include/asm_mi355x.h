@@ -500,14 +500,30 @@ int asm_md_format(const uint16_t* ops, int nops, const char* read_on_strand, int
  * asm_bgzf_bound:  the bytes asm_bgzf_frame writes for n input bytes; no device.
  * asm_bgzf_frame:  src[0, n) (host) framed into dst (host) by the device kernel the file calls use: blocks of ASM_BGZF_PAYLOAD bytes,
  *                  the last one shorter, none at all for n = 0; with_eof: the EOF block behind them.  *dst_len = asm_bgzf_bound(n,
- *                  with_eof).  A dst_cap below that is ASM_EINVAL, and nothing is written.  Synchronous. */
+ *                  with_eof).  A dst_cap below that is ASM_EINVAL, and nothing is written.  Synchronous.
+ * The container's level (docs/design/mapper.md, "Deflate") is handle state too.  ASM_BGZF_STORED (the default) leaves every byte as
+ * described above.  Under ASM_BGZF_DEFLATE every block, the header's included, is one deflate block encoded on the device: stored,
+ * fixed Huffman or dynamic Huffman, whichever has the fewest bits, so no block is longer than its stored form and an incompressible
+ * one is byte for byte the stored one.  The uncompressed stream and its cut are the same, the bytes are a function of that stream
+ * alone, and bytes_out counts the bytes really written.  The level has no effect under ASM_OUT_SAM.
+ * asm_map_set_bgzf_level: another value, or a NULL handle, is ASM_EINVAL; the value is checked first.
+ * asm_map_get_bgzf_level: ASM_BGZF_STORED for a NULL handle.
+ * asm_bgzf_compress:      asm_bgzf_frame with a level: dst_cap below asm_bgzf_bound(n, with_eof) is ASM_EINVAL at both levels, and
+ *                         *dst_len is what was written.  Level 0 gives asm_bgzf_frame's bytes.
+ * asm_bgzf_compress_host: the same bytes from the host build of the same encoder; no device, no handle. */
 #define ASM_OUT_SAM 0
 #define ASM_OUT_BAM 1
 #define ASM_BGZF_PAYLOAD 65280
+#define ASM_BGZF_STORED 0
+#define ASM_BGZF_DEFLATE 1
 int asm_map_set_output_format(asm_handle* h, int format);
 int asm_map_get_output_format(const asm_handle* h);
 size_t asm_bgzf_bound(size_t n, int with_eof);
 int asm_bgzf_frame(asm_handle* h, const void* src, size_t n, int with_eof, void* dst, size_t dst_cap, size_t* dst_len);
+int asm_map_set_bgzf_level(asm_handle* h, int level);
+int asm_map_get_bgzf_level(const asm_handle* h);
+int asm_bgzf_compress(asm_handle* h, const void* src, size_t n, int with_eof, int level, void* dst, size_t dst_cap, size_t* dst_len);
+int asm_bgzf_compress_host(const void* src, size_t n, int with_eof, int level, void* dst, size_t dst_cap, size_t* dst_len);
 
 /* asm_map_file:    a FASTQ file in, a SAM file out (docs/design/mapper.md, "Files: FASTQ in, SAM out"); single-end, synchronous.  The
  *                  file is read in chunks of about chunk_bytes (0: 16 MiB) cut at record boundaries; a chunk is parsed, mapped
