@@ -45,7 +45,7 @@ struct DeflateLds {
     uint32_t code[DFL_SYMS]; /* the bit-reversed code, its length << 16 */
     uint32_t misc[64];
 };
-enum { DFL_M_FRONT = 0, DFL_M_LAST = 16, DFL_M_CRC, DFL_M_TYPE, DFL_M_HEAD, DFL_M_BITS, DFL_M_WAVE = 32 };
+enum { DFL_M_FRONT = 0, DFL_M_LAST = 16, DFL_M_CRC, DFL_M_TYPE, DFL_M_HEAD, DFL_M_BITS, DFL_M_FIXED, DFL_M_DYN, DFL_M_WAVE = 32 };
 /* the builder's arrays inside prev */
 enum { DFL_B_W = 0, DFL_B_ORDER = DFL_SYMS, DFL_B_LEN = 2 * DFL_SYMS, DFL_B_A = 3 * DFL_SYMS, DFL_B_USED = 4 * DFL_SYMS, DFL_B_END = 4 * DFL_SYMS + 2 };
 static_assert(DFL_WTAB == 2u * BGZF_THREADS, "a thread clears two entries of wfirst");
@@ -327,7 +327,8 @@ SAM_HD uint32_t dfl_cl_order(uint32_t i) {
 
 /* One thread, behind both alphabets' lengths (b + DFL_B_LEN) and the histogram: the code-length alphabet, the three types' bit
  * counts and the choice; the chosen type's codes into L.code and its header into the bit buffer.  misc: DFL_M_TYPE, DFL_M_HEAD (the
- * bits in front of the first token), DFL_M_BITS (the whole block's). */
+ * bits in front of the first token), DFL_M_BITS (the whole block's); in the host build also DFL_M_FIXED and DFL_M_DYN, the counts
+ * of the two Huffman types, for host/deflate_host_check.cpp. */
 SAM_HD void dfl_choose(DeflateLds& L, uint32_t len) {
     uint32_t* const b = L.prev;
     const uint32_t *ll = b + DFL_B_LEN, *d = b + DFL_B_LEN + DFL_NLL;
@@ -360,6 +361,9 @@ SAM_HD void dfl_choose(DeflateLds& L, uint32_t len) {
     const uint32_t stored = 40u + 8u * len;
     const uint32_t type = stored <= fixed && stored <= dyn ? 0u : fixed <= dyn ? 1u : 2u;
     L.misc[DFL_M_TYPE] = type, L.misc[DFL_M_HEAD] = type == 2u ? head : 3u, L.misc[DFL_M_BITS] = type == 0u ? stored : type == 1u ? fixed : dyn;
+#if !defined(__HIP_DEVICE_COMPILE__)
+    L.misc[DFL_M_FIXED] = fixed, L.misc[DFL_M_DYN] = dyn;
+#endif
     if (type == 0u) return;
     dfl_put(L.bits, 0u, 1u | (type << 1), 3u);
     if (type == 1u) {
@@ -429,8 +433,8 @@ inline void dfl_build_host(DeflateLds& L) {
     }
 }
 /* The block of p[0, len), len in [1, BGZF_PAYLOAD], onto the end of out, as bgzf_deflate_kernel writes it; p as in bgzf_block_host.
- * type: the block's BTYPE. */
-inline void dfl_block_host(DeflateLds& L, const uint8_t* p, uint32_t len, std::vector<uint8_t>& out, uint32_t* type) {
+ * type: the block's BTYPE; counts: the bits dfl_choose counted for the fixed and for the dynamic form, or NULL. */
+inline void dfl_block_host(DeflateLds& L, const uint8_t* p, uint32_t len, std::vector<uint8_t>& out, uint32_t* type, uint32_t* counts = nullptr) {
     memset(&L, 0, sizeof L);
     memcpy(L.pay, p, len);
     const uint32_t crc = bgzf_block_host(p, len, nullptr);
@@ -439,6 +443,7 @@ inline void dfl_block_host(DeflateLds& L, const uint8_t* p, uint32_t len, std::v
     dfl_build_host(L);
     dfl_choose(L, len);
     *type = L.misc[DFL_M_TYPE];
+    if (counts) counts[0] = L.misc[DFL_M_FIXED], counts[1] = L.misc[DFL_M_DYN];
     const size_t blk = out.size();
     if (*type == 0u) {
         out.resize(blk + BGZF_FRONT + len + BGZF_BACK);
@@ -455,8 +460,10 @@ inline void dfl_block_host(DeflateLds& L, const uint8_t* p, uint32_t len, std::v
     memcpy(out.data() + blk + DFL_HEAD, L.bits, nbytes);
     for (uint32_t i = 0; i < BGZF_BACK; i++) out[blk + DFL_HEAD + nbytes + i] = bgzf_back_byte(i, crc, len);
 }
-/* src[0, n) in blocks at `level` onto the end of out, the EOF block behind them when with_eof; types: every block's BTYPE, or NULL */
-inline void bgzf_compress_host(const void* src, size_t n, int with_eof, int level, std::vector<uint8_t>& out, std::vector<uint32_t>* types) {
+/* src[0, n) in blocks at `level` onto the end of out, the EOF block behind them when with_eof; types: every block's BTYPE, or NULL;
+ * counts: at level 1 every block's fixed and dynamic bit counts, two entries per block, or NULL */
+inline void bgzf_compress_host(const void* src, size_t n, int with_eof, int level, std::vector<uint8_t>& out, std::vector<uint32_t>* types,
+                               std::vector<uint32_t>* counts = nullptr) {
     if (level == 0) {
         bgzf_frame_host(src, n, with_eof, out);
         if (types) types->assign(bgzf_blocks(n), 0u);
@@ -468,9 +475,10 @@ inline void bgzf_compress_host(const void* src, size_t n, int with_eof, int leve
     for (size_t at = 0; at < n; at += BGZF_PAYLOAD) {
         const uint32_t len = (uint32_t)(n - at < BGZF_PAYLOAD ? n - at : BGZF_PAYLOAD);
         memcpy(stage, (const uint8_t*)src + at, len);
-        uint32_t type = 0u;
-        dfl_block_host(lds[0], stage, len, out, &type);
+        uint32_t type = 0u, bits[2] = {0u, 0u};
+        dfl_block_host(lds[0], stage, len, out, &type, bits);
         if (types) types->push_back(type);
+        if (counts) counts->push_back(bits[0]), counts->push_back(bits[1]);
     }
     if (with_eof)
         for (uint32_t i = 0; i < BGZF_EOF; i++) out.push_back(bgzf_eof_byte(i));

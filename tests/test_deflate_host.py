@@ -10,6 +10,7 @@ import pytest
 
 from tests import bam_cases as bc
 from tests import deflate_cases as dc
+from tests import inflate_cases as ic
 from tests.test_map_file_host import san_flags
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,25 +29,145 @@ def deflate_check(tmp_path_factory):
 
 
 @pytest.fixture(scope="module")
-def checked(deflate_check, tmp_path_factory):
-    """{name: (container, [(payload length, BTYPE, block bytes)])} of the whole corpus, from the sanitizer-built checker"""
+def encoded(deflate_check, tmp_path_factory):
+    """{name: (container, [(payload length, BTYPE, block bytes)], [(fixed bits, dynamic bits)])} of the corpus and of the adversarial
+    corpus, from the sanitizer-built checker in its `counts` form"""
     tmp = tmp_path_factory.mktemp("deflate_corpus")
     out = {}
-    for name, src in dc.corpus().items():
+    for name, src in every_payload().items():
         inp, dst = tmp / "in.bin", tmp / "out.bgzf"
         inp.write_bytes(src)
-        r = subprocess.run([deflate_check, str(inp), str(dst), "1"], capture_output=True, text=True, timeout=120)
+        r = subprocess.run([deflate_check, str(inp), str(dst), "1", "counts"], capture_output=True, text=True, timeout=120)
         assert r.returncode == 0, (name, r.returncode, r.stderr[-3000:])      # a sanitizer report ends the run with another status
         assert r.stderr == "", (name, r.stderr[-3000:])
-        out[name] = (dst.read_bytes(), [tuple(int(v) for v in ln.split()) for ln in r.stdout.split("\n") if ln])
+        rows = [tuple(int(v) for v in ln.split()) for ln in r.stdout.split("\n") if ln]
+        assert all(len(row) == 5 for row in rows)
+        out[name] = (dst.read_bytes(), [row[:3] for row in rows], [row[3:] for row in rows])
     return out
 
 
-def test_every_payload_inflates(checked):
-    for name, src in dc.corpus().items():
-        data, printed = checked[name]
-        blocks = dc.check_container(data, src)
-        assert printed == [(len(b["payload"]), dc.btype(b), b["bsize"]) for b in blocks], name
+@pytest.fixture(scope="module")
+def checked(encoded):
+    """{name: (container, [(payload length, BTYPE, block bytes)])}"""
+    return {name: row[:2] for name, row in encoded.items()}
+
+
+def every_payload():
+    return dict(dc.corpus(), **{name: src for name, (src, _) in dc.adversarial().items()})
+
+
+def decoded(encoded, name, src):
+    """the container's checks and check_tokens on every block of one entry -> the decoded blocks"""
+    data, printed, counts = encoded[name]
+    blocks = dc.check_container(data, src)
+    assert printed == [(len(b["payload"]), dc.btype(b), b["bsize"]) for b in blocks], name
+    return [dc.check_tokens(b, b["payload"], c) for b, c in zip(blocks, counts)]
+
+
+def test_every_payload_inflates(encoded):
+    """and every block keeps the contract, read back token by token (deflate_cases.check_tokens)"""
+    for name, src in every_payload().items():
+        decoded(encoded, name, src)
+
+
+@pytest.mark.parametrize("letter", "abcdefg")
+def test_adversarial_payloads_reach_their_edges(encoded, letter):
+    """every entry of deflate_cases.adversarial() asserts the property it was built for on the decoded blocks: (a) an unlimited
+    literal/length depth above 15 under a longest code of exactly 15, (b) a code-length depth above 7 under a longest code of 7, both
+    within (c)'s measured cap over package-merge, (d) the header's run symbols, (e) the match rules, (f) window and table edges, (g)
+    a token of at least 40 bits.
+
+    Not built: the distance-alphabet variant of (a) (the distance trees of the (a) entries are 11 and 12 deep, and a deeper one
+    was not searched for; dfl_lengths at limit 15 over 2 to 286 symbols is covered by test_lengths_under_the_limit) and
+    (g)'s window of 1-bit literals: 1 024 places without a match over two byte values, which have 16 4-grams between them, cannot
+    be laid out."""
+    names = [n for n in dc.adversarial() if n[0] == letter]
+    assert names
+    for name in names:
+        src, prop = dc.adversarial()[name]
+        infs = decoded(encoded, name, src)
+        prop(infs)
+        print("%-45s %s" % (name, [(i["btype"], len(i["tokens"])) for i in infs]))
+
+
+def test_the_plain_form_prints_three_columns(deflate_check, checked, tmp_path):
+    name = "records %d" % (2 * dc.P + 1)
+    inp = tmp_path / "in.bin"
+    inp.write_bytes(dc.corpus()[name])
+    r = subprocess.run([deflate_check, str(inp), str(tmp_path / "out.bgzf"), "1"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stderr == ""
+    assert [tuple(int(v) for v in ln.split()) for ln in r.stdout.split("\n") if ln] == checked[name][1]
+    assert (tmp_path / "out.bgzf").read_bytes() == checked[name][0]
+
+
+def test_stored_wins_its_tie_with_fixed(checked, encoded):
+    (n, typ, bsize), (fixed, dyn) = checked["c stored ties with fixed"][1][0], encoded["c stored ties with fixed"][2][0]
+    assert (n, typ, bsize) == (30, 0, 61) and fixed == 40 + 8 * n and dyn > fixed
+
+
+# ---- dfl_lengths, driven directly -----------------------------------------------------------------------------------------------------
+# The Kraft repair of dfl_lengths runs only when the unlimited tree is deeper than the limit.  The (a) and (b) entries of the adversarial
+# corpus bring that about in whole blocks; here dfl_lengths is driven by itself, over many more shapes.  Measured on the cases below,
+# the bits under dfl_lengths' code over the bits under the package-merge code of the same limit (the optimum), where the limit binds:
+#
+#   limit   cases where it binds   worst ratio   at             cap = worst + (worst - 1) / 10
+#   7       33                     1.11004       fibonacci 19   1.1211
+#   15      811                    1.00266       fibonacci 27   1.00293
+#
+# The repair is zlib's and is not optimal; the cap catches one that degrades by more than a tenth of its own excess.
+def weight_sets(n):
+    fib = [1, 1]
+    while len(fib) < n:
+        fib.append(fib[-1] + fib[-2])
+    return dict(fibonacci=[min(v, 832040) for v in fib[:n]], powers=[1 << min(i, 20) for i in range(n)], flat=[5] * n,
+                fibonacci_down=[min(v, 832040) for v in fib[:n]][::-1])
+
+
+def lengths_cases():
+    cases = [(7, kind, w) for n in range(2, 20) for kind, w in weight_sets(n).items()]
+    cases += [(15, kind, w) for n in range(2, 287) for kind, w in weight_sets(n).items()]
+    # an unused symbol in between, as the encoder's alphabets have them
+    cases += [(15, "gaps", [v if i % 3 else 0 for i, v in enumerate(weight_sets(40)["fibonacci"])])]
+    return cases
+
+
+LENGTHS_CAP = {7: 1.1211, 15: 1.00293}
+
+
+def test_lengths_under_the_limit(deflate_check, tmp_path):
+    """dfl_lengths through the checker's `lengths` mode, under ASan + UBSan: Fibonacci, power-of-two and flat weights, 2 to 19 symbols
+    at limit 7 and 2 to 286 at limit 15.  Every code is complete and within the limit, a rarer symbol never has the shorter code, and
+    the bits stay within the cap over package-merge's (the table above)."""
+    cases = lengths_cases()
+    inp = tmp_path / "cases.txt"
+    inp.write_text("".join("%d %s\n" % (limit, " ".join(map(str, w))) for limit, _, w in cases))
+    r = subprocess.run([deflate_check, "lengths", "@" + str(inp)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stderr == "", (r.returncode, r.stderr[-3000:])
+    rows = [[int(v) for v in ln.split()] for ln in r.stdout.split("\n") if ln]
+    assert len(rows) == len(cases)
+    worst, binding = {7: (1.0, None), 15: (1.0, None)}, {7: 0, 15: 0}
+    for (limit, kind, w), lens in zip(cases, rows):
+        used = [i for i, v in enumerate(w) if v]
+        assert len(lens) == len(w) and all((lens[i] > 0) == (w[i] > 0) for i in range(len(w))), (limit, kind, len(w))
+        assert max(lens) <= limit and ic.kraft(lens) == 1 << 15, (limit, kind, len(w), lens)
+        by_weight = sorted(used, key=lambda i: (w[i], -lens[i]))
+        assert all(lens[i] >= lens[j] for i, j in zip(by_weight, by_weight[1:])), ("a rarer symbol with the shorter code", limit, kind, len(w))
+        huff, best = ic.huffman_lengths(w), ic.package_merge_lengths(w, limit)
+        if max(huff) <= limit:
+            assert ic.cost(w, lens) == ic.cost(w, huff), "where the limit does not bind the code is a Huffman code"
+            continue
+        binding[limit] += 1
+        ratio = ic.cost(w, lens) / ic.cost(w, best)
+        assert ratio >= 1.0
+        if ratio > worst[limit][0]:
+            worst[limit] = (ratio, "%s %d" % (kind, len(w)))
+    for limit in (7, 15):
+        print("limit %d: %d cases where it binds, worst ratio to package-merge %.5f at %s" % (limit, binding[limit], *worst[limit]))
+        assert binding[limit] >= 10
+        assert worst[limit][0] <= LENGTHS_CAP[limit], (limit, worst[limit])
+    # the single case on the command line
+    r = subprocess.run([deflate_check, "lengths", "7"] + [str(v) for v in cases[40][2]], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stderr == "" and [int(v) for v in r.stdout.split()] == rows[40]
 
 
 def test_incompressible_is_the_stored_container(checked):
@@ -116,7 +237,7 @@ def compress_host(lib, src, level, eof=True, cap=None):
 
 def test_library_host_call_equals_the_checker(asm, checked):
     lib = asm.load_library()
-    for name, src in dc.corpus().items():
+    for name, src in every_payload().items():
         rc, data, _ = compress_host(lib, src, asm.BGZF_STORED)
         assert rc == 0 and data == bc.frame_stored(src), name
         rc, data, _ = compress_host(lib, src, asm.BGZF_DEFLATE)
