@@ -1,14 +1,18 @@
 // BAM records of the file calls under ASM_OUT_BAM (contract: docs/design/mapper.md, "BAM output"): the binary record of one output
 // line, single-end or paired, in the shape of asm_sam.h.  bam_format<Sink> walks the fields of a record in order (SAM spec 4.2,
 // little endian) and hands every piece to a sink:
-//   BamSizeSink  adds the lengths                      (bam_size_kernel: one thread per record)
-//   BamLaneSink  stores the bytes p = lane (mod 64)    (bam_emit_kernel: one wave per record, 64 contiguous bytes per store)
+//   BamSizeSink  adds the lengths                      (line_size_kernel<BamRecord, .>: one thread per record)
+//   BamLaneSink  stores the bytes p = lane (mod 64)    (line_emit_kernel<BamRecord, .>: one wave per record, 64 contiguous bytes per store)
 // so the size and the bytes cannot disagree.  What a record says is what sam_format's line says: the same own / lent rules, the same
-// flag, MAPQ and tags in the same order; the loaders are asm_sam.h's, unchanged.  The part above the kernels holds no HIP:
-// host/bam_host_check.cpp compiles it with plain g++ under ASan + UBSan and runs the lane sink for lanes 0..63 in turn
-// (tests/test_bam_host.py).
+// flag, MAPQ and tags in the same order; the loaders and the two kernels are asm_sam.h's, which take the record as their format tag
+// (BamRecord; line_kernels picks the pair to launch).  bam_header_bytes builds what the file's record stream starts with.  The part
+// above the kernels holds no HIP: host/bam_host_check.cpp compiles it with plain g++ under ASan + UBSan and runs the lane sink for
+// lanes 0..63 in turn (tests/test_bam_host.py).
 #pragma once
 #include <stdint.h>
+#include <string.h>
+
+#include <vector>
 
 #include "asm_sam.h"
 
@@ -168,36 +172,41 @@ SAM_HD bool bam_name_too_long(const char* raw, const SamRec& r, bool pair) {
     return (pair ? sam_pair_name_len(raw, r) : r.name_len) > BAM_NAME_MAX;
 }
 
-#if defined(__HIPCC__)
-
-/* sam_size_kernel and sam_emit_kernel with the BAM record in place of the line: the same arguments, loaders and counters */
-template <bool PAIRED>
-__global__ __launch_bounds__(256) void bam_size_kernel(SamArgs a) {
-    const long l = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    bool primary = false, proper = false, rescued = false;
-    if (l < a.nlines) {
-        const SamLine s = sam_load<PAIRED>(a, l);
-        a.size[l] = bam_record_size(s);
-        primary = s.mapped && s.rank == 0u;
-        proper = s.paired && s.proper && s.mate == 0u, rescued = s.paired && s.rescued;
-    } else if (l == a.nlines) {
-        a.size[l] = 0ull;
+/* The BAM header (SAM spec 4.2) as the record stream's first bytes, unframed: magic, l_text, the text, n_ref, and per reference
+ * sequence l_name, the name with its NUL and l_ref.  text: l_text bytes, which may be NULL when l_text is 0. */
+inline std::vector<uint8_t> bam_header_bytes(const char* text, size_t l_text, const char* const* names, const uint32_t* lengths, size_t n_ref) {
+    std::vector<uint8_t> out = {'B', 'A', 'M', 1};
+    const auto u32 = [&out](uint64_t v) {
+        for (int b = 0; b < 4; b++) out.push_back((uint8_t)(v >> (8 * b)));
+    };
+    u32(l_text);
+    if (l_text) out.insert(out.end(), text, text + l_text);
+    u32(n_ref);
+    for (size_t r = 0; r < n_ref; r++) {
+        const size_t l_name = strlen(names[r]) + 1;
+        u32(l_name);
+        out.insert(out.end(), names[r], names[r] + l_name);
+        u32(lengths[r]);
     }
-    const unsigned long long m = __ballot(primary);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(a.n_mapped, (unsigned long long)__popcll(m));
-    if constexpr (PAIRED) {
-        const unsigned long long mp = __ballot(proper), mr = __ballot(rescued);
-        if ((threadIdx.x & 63) == 0 && mp) atomicAdd(a.n_proper, (unsigned long long)__popcll(mp));
-        if ((threadIdx.x & 63) == 0 && mr) atomicAdd(a.n_rescued, (unsigned long long)__popcll(mr));
-    }
+    return out;
 }
 
+#if defined(__HIPCC__)
+
+struct BamRecord { /* the format tag of asm_sam.h's line_size_kernel and line_emit_kernel */
+    SAM_HD static uint64_t size(const SamLine& l) { return bam_record_size(l); }
+    SAM_HD static void emit(const SamLine& l, char* out, uint32_t lane) { bam_record_emit(l, out, lane); }
+};
+
+/* The size and the emit kernel of a file call's output lines, by format and call: the one place that tests the format for a launch */
+struct LineKernels {
+    void (*size)(SamArgs);
+    void (*emit)(SamArgs);
+};
 template <bool PAIRED>
-__global__ __launch_bounds__(256) void bam_emit_kernel(SamArgs a) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-    for (long l = wave; l < a.nlines; l += nwaves) bam_record_emit(sam_load<PAIRED>(a, l), a.out + a.off[l], lane);
+static LineKernels line_kernels(bool bam) {
+    if (bam) return {line_size_kernel<BamRecord, PAIRED>, line_emit_kernel<BamRecord, PAIRED>};
+    return {line_size_kernel<SamText, PAIRED>, line_emit_kernel<SamText, PAIRED>};
 }
 
 /* Records [0, n) of a device chunk (PAIRED: [2][n], mate 1 of every pair and then mate 2): min_long[f] = the smallest record of file f

@@ -1886,7 +1886,7 @@ int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, in
 #include "asm_map_host.h"
 /* the BGZF container of the file calls' BAM output: frame kernel, record stream, asm_bgzf_frame */
 #include "asm_bgzf.h"
-/* the output side of the file calls: the rotation of output slots and the report of a failed write */
+/* the output side of the file calls: MapOutput (file, output slots, writer, record stream) and the report of a failed write */
 #include "asm_map_out.h"
 /* what the sorted file calls keep on the device, their sort and their gather */
 #include "asm_sam_sort.h"

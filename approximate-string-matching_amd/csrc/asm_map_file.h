@@ -1,75 +1,43 @@
 // asm_map_file: a FASTQ file in, a SAM file out, parsed, mapped and formatted on the device (kernels: asm_fastq.h, asm_sam.h and the
 // mapper's own; stages: asm_map_host.h; input pipeline: asm_stream.h; reader and writer threads: asm_host.h; design:
-// docs/design/mapper.md, "Files: FASTQ in, SAM out").  First what it shares with asm_map_pairs_file.h: the output pipe
-// (MapFilePipe), the session of one call (MapFileSession), the gather stage and the format tail of a device chunk
+// docs/design/mapper.md, "Files: FASTQ in, SAM out"; output side: MapOutput of asm_map_out.h).  First what it shares with
+// asm_map_pairs_file.h: the session of one call (MapFileSession), the gather stage and the format tail of a device chunk
 // (map_file_gather, map_file_format<PAIRED>); then asm_map_file's own chunk function and entry point.  asm_capi.hip includes this
-// file inside its extern "C" block, behind asm_map_host.h.
+// file inside its extern "C" block, behind asm_sam_sort.h.
 #pragma once
 
 extern "C++" {
 
-/* What one call owns besides its threads: the input side (StreamInput, asm_stream.h) and on top of it the SAM file, the copy-out
- * stream, three pinned output buffers in rotation, the device buffers of the SAM bytes and the events between them.  The destructor
- * waits for the streams and gives everything back, on every path; the threads are declared after it, so they are joined before. */
-struct MapFilePipe {
-    asm_handle* h;
-    StreamInput in;
-    FILE* out = nullptr;
-    hipStream_t s_out = nullptr;
-    char* pin_out[3] = {nullptr, nullptr, nullptr};
-    size_t pin_out_cap[3] = {0, 0, 0};
-    char* d_out[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_fmt[3] = {nullptr, nullptr, nullptr};    /* d_out[o] holds its SAM bytes */
-    hipEvent_t ev_copied[3] = {nullptr, nullptr, nullptr}; /* pin_out[o] holds them */
-    MapFilePipe(asm_handle* owner, const char* who) : h(owner), in(owner, who) {}
-    hipError_t open_device(size_t slot_cap) {
-        hipError_t e = in.open_device(slot_cap, false, true);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&s_out, hipStreamNonBlocking);
-        for (hipEvent_t* ev : {&ev_fmt[0], &ev_fmt[1], &ev_fmt[2], &ev_copied[0], &ev_copied[1], &ev_copied[2]})
-            if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
-        return e;
-    }
-    ~MapFilePipe() { /* the input side goes after this */
-        (void)hipSetDevice(h->device);
-        if (in.s_in) (void)hipStreamSynchronize(in.s_in);
-        if (s_out) (void)hipStreamSynchronize(s_out);
-        (void)hipStreamSynchronize(h->stream);
-        for (hipEvent_t ev : {ev_fmt[0], ev_fmt[1], ev_fmt[2], ev_copied[0], ev_copied[1], ev_copied[2]})
-            if (ev) (void)hipEventDestroy(ev);
-        if (s_out) (void)hipStreamDestroy(s_out);
-        for (char* q : pin_out)
-            if (q) (void)hipHostFree(q);
-        for (char* q : d_out) pool_free(h, q);
-        if (out) fclose(out);
-    }
-};
-
-/* One file call, asm_map_file or asm_map_pairs_file (`who`), above its pipe: everything the two calls set up, run and tear down in
- * the same way.  open() probes the input files for FASTA, opens the SAM file and writes the header, puts the RNAME table on the
- * device, sizes and pins the input slots and starts the writer; grow() is the reader's way to a larger pinned slot; run() drives the
- * input pipeline; finish() ends the writer and fills the fields the two stats structs share.  The call itself keeps what differs:
- * its files, its reader policy, what it accepts and how a chunk is processed.  Declare the reader after the session, so that its
- * thread is joined first; the writer goes before the pipe, whose buffers it reads. */
+/* One file call, asm_map_file or asm_map_pairs_file (`who`), above its input side (StreamInput, asm_stream.h) and its output side
+ * (MapOutput, asm_map_out.h): everything the two calls set up, run and tear down in the same way.  open() probes the input files for
+ * FASTA, opens the output with the header, puts the RNAME table on the device and sizes and pins the input slots; grow() is the
+ * reader's way to a larger pinned slot; run() drives the input pipeline; finish() completes the output and fills the fields the two
+ * stats structs share.  The call itself keeps what differs: its files, its reader policy, what it accepts and how a chunk is
+ * processed.  Declare the reader after the session, so that its thread is joined first.  Members go in reverse order of their
+ * declaration: what the sorted call holds, then the output side (its writer thread first), then the input side; the destructor
+ * waits for the copy-in stream in front of them all. */
 struct MapFileSession {
     asm_handle* h;
     const char* who;
     const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
-    MapFilePipe pipe;
+    StreamInput in;
+    MapOutput out;
     Scratch<char> d_names; /* the RNAME table: the names back to back and their n_seqs + 1 offsets */
     Scratch<uint32_t> d_name_off;
     /* chunks ramp up from an eighth, so that the device starts after an eighth of a chunk has been read */
     const size_t chunk, slot_cap = chunk + chunk / 4 + 4096, first_chunk = chunk >= ((size_t)8 << 20) ? chunk / 8 : chunk;
     asm_host::ChunkSlot* slots = nullptr; /* the reader's, from run() on */
-    int64_t out_seq = 0;                  /* device chunks handed to the writer so far */
     struct {
-        int64_t chunks, bytes_in, bytes_out, records;
+        int64_t chunks, bytes_in, records;
         double seconds_read;
     } st = {};
-    std::unique_ptr<asm_host::ChunkWriter> writer;
     std::unique_ptr<SamSortHold> sort; /* the sorted calls: the formatted chunks stay on the device until finish() (asm_sam_sort.h) */
-    std::unique_ptr<BgzfStream> bam;   /* ASM_OUT_BAM: the records are BAM's and leave through the BGZF record stream (asm_bgzf.h) */
     MapFileSession(asm_handle* owner, const char* call, size_t chunk_bytes)
-        : h(owner), who(call), pipe(owner, call), d_names(owner), d_name_off(owner), chunk(chunk_bytes) {}
+        : h(owner), who(call), in(owner, call), out(owner, call), d_names(owner), d_name_off(owner), chunk(chunk_bytes) {}
+    ~MapFileSession() {
+        (void)hipSetDevice(h->device);
+        if (in.s_in) (void)hipStreamSynchronize(in.s_in);
+    }
 
     int bad(const std::string& text, int code = ASM_EINVAL) { return fail(h, code, std::string(who) + ": " + text); }
 
@@ -84,8 +52,6 @@ struct MapFileSession {
                                " starts with '>')",
                            ASM_EUNSUPPORTED);
         }
-        pipe.out = fopen(sam_path, "wb");
-        if (!pipe.out) return bad(std::string("cannot write ") + sam_path);
         std::string names;
         std::vector<uint32_t> name_off(1, 0u);
         for (int32_t r = 0; r < ix->n_seqs; r++) {
@@ -95,45 +61,30 @@ struct MapFileSession {
         }
         std::vector<uint8_t> head; /* what the file starts with: the header as it is, or the BAM header in BGZF blocks of its own */
         if (h->out_format == ASM_OUT_BAM) {
-            std::string text("BAM\1", 4);
-            const auto u32 = [&text](uint64_t v) {
-                for (int b = 0; b < 4; b++) text += (char)(v >> (8 * b));
-            };
             const size_t l_text = header ? strlen(header) : 0;
             if (l_text > 0x7fffffffull) return bad("a header of 2 GiB or more cannot be a BAM header", ASM_EUNSUPPORTED);
-            u32(l_text);
-            text.append(header ? header : "", l_text);
-            u32((uint64_t)ix->n_seqs);
-            for (int32_t r = 0; r < ix->n_seqs; r++) {
-                u32(strlen(seq_names[r]) + 1);
-                text.append(seq_names[r], strlen(seq_names[r]) + 1);
-                u32(asm_index_seq_len(ix, r));
-            }
+            std::vector<uint32_t> lengths;
+            for (int32_t r = 0; r < ix->n_seqs; r++) lengths.push_back((uint32_t)asm_index_seq_len(ix, r));
+            const std::vector<uint8_t> text = bam_header_bytes(header, l_text, seq_names, lengths.data(), lengths.size());
             bgzf_compress_host(text.data(), text.size(), 0, h->bgzf_level, head, nullptr);
-            bam.reset(new BgzfStream(h));
-            STREAM_TRY(who, bam->open());
         } else if (header) {
             head.assign(header, header + strlen(header));
         }
-        if (!head.empty() && fwrite(head.data(), 1, head.size(), pipe.out) != head.size()) return map_out_failed(h, who);
+        if (const int rc = out.open(sam_path, head)) return rc;
         STREAM_TRY(who, d_names.alloc(names.size() + 16));
         STREAM_TRY(who, d_name_off.alloc(sizeof(uint32_t) * name_off.size()));
         STREAM_TRY(who, hipMemcpyAsync(d_names.p, names.data(), names.size(), hipMemcpyHostToDevice, h->stream));
         STREAM_TRY(who, hipMemcpyAsync(d_name_off.p, name_off.data(), sizeof(uint32_t) * name_off.size(), hipMemcpyHostToDevice, h->stream));
         STREAM_TRY(who, hipStreamSynchronize(h->stream));
-        STREAM_TRY(who, pipe.open_device(slot_cap));
-        pipe.in.own_pin = true;
-        for (char*& q : pipe.in.pin) STREAM_TRY(who, hipHostMalloc((void**)&q, slot_cap + 64, hipHostMallocDefault));
-        writer.reset(new asm_host::ChunkWriter(pipe.out, [this](int o) {
-            (void)hipSetDevice(h->device);
-            return hipEventSynchronize(pipe.ev_copied[o]) == hipSuccess;
-        }));
+        STREAM_TRY(who, in.open_device(slot_cap, false, true));
+        in.own_pin = true;
+        for (char*& q : in.pin) STREAM_TRY(who, hipHostMalloc((void**)&q, slot_cap + 64, hipHostMallocDefault));
         return ASM_OK;
     }
 
     /* For the reader's policy: a record (or pair) longer than slot q gets a larger pinned one (StreamInput::grow_pin) */
     std::function<bool(int, size_t, size_t)> grow() {
-        return [this](int q, size_t cap, size_t keep) { return pipe.in.grow_pin(slots, q, cap, keep); };
+        return [this](int q, size_t cap, size_t keep) { return in.grow_pin(slots, q, cap, keep); };
     }
 
     /* The reader (built on first_chunk, chunk and grow()) through the input pipeline, from its start to its stop: accept sees every
@@ -141,9 +92,9 @@ struct MapFileSession {
     template <class Reader, class Accept, class Process>
     int run(Reader& rd, const std::string& read_failed, Accept accept, Process process) {
         slots = rd.slot;
-        for (int q = 0; q < 3; q++) slots[q].buf = pipe.in.pin[q], slots[q].cap = slot_cap;
+        for (int q = 0; q < 3; q++) slots[q].buf = in.pin[q], slots[q].cap = slot_cap;
         rd.start();
-        const int rc = pipe.in.run(
+        const int rc = in.run(
             rd, read_failed,
             [&](const asm_host::ChunkSlot& s, int64_t seen) {
                 if (const int ra = accept(s, seen)) return ra;
@@ -158,27 +109,17 @@ struct MapFileSession {
         return ASM_OK;
     }
 
-    /* after run() and the call's own last checks: the SAM file complete (a sorted call writes all of it here, in slabs of at most a
-     * chunk), and the shared fields of the call's stats */
+    /* after run() and the call's own last checks: the output file complete (a sorted call writes all of it here, in slabs of at most
+     * a chunk), and the shared fields of the call's stats.  bytes_out is what the output's jobs shipped; for sorted SAM that is the
+     * slabs' bytes, which add up to the chunks' totals. */
     template <class Stats>
-    int finish(Stats& out) {
-        if (sort) {
-            size_t written = 0;
-            if (const int rc = sort->flush(pipe, *writer, out_seq, chunk, bam.get(), &written)) return rc;
-            st.bytes_out += (int64_t)written;
-        }
-        if (bam) { /* what the last chunk or slab left of the record stream, and the EOF block */
-            int o = 0;
-            size_t bytes = 0;
-            if (const int rc = map_out_slot(h, who, pipe, *writer, out_seq, bam->tail_bytes(), &o)) return rc;
-            STREAM_TRY(who, bam->tail(pipe.d_out[o], &bytes));
-            if (const int rc = map_out_ship(h, who, pipe, *writer, out_seq, o, bytes)) return rc;
-            st.bytes_out += (int64_t)bytes;
-        }
-        if (!writer->finish() || fflush(pipe.out) != 0) return map_out_failed(h, who);
-        out.chunks = st.chunks, out.bytes_in = st.bytes_in, out.bytes_out = st.bytes_out, out.records = st.records;
-        out.seconds_read = st.seconds_read, out.seconds_write = writer->write_seconds();
-        out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+    int finish(Stats& stats) {
+        if (sort)
+            if (const int rc = sort->flush(out, chunk)) return rc;
+        if (const int rc = out.finish(&stats.seconds_write)) return rc;
+        stats.chunks = st.chunks, stats.bytes_in = st.bytes_in, stats.bytes_out = out.bytes_out, stats.records = st.records;
+        stats.seconds_read = st.seconds_read;
+        stats.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
         return ASM_OK;
     }
 };
@@ -202,7 +143,7 @@ static int map_file_malformed(MapFileSession& ss, int64_t record, int file) {
  * ASM_OUT_SAM nothing is launched. */
 template <bool PAIRED>
 static int map_file_bam_names(MapFileSession& ss, const char* d_raw, const SamRec* d_recs, int64_t rn, int64_t first_record) {
-    if (!ss.bam || rn == 0) return ASM_OK;
+    if (!ss.out.bam || rn == 0) return ASM_OK;
     asm_handle* h = ss.h;
     Scratch<uint32_t> d_long(h);
     uint32_t min_long[2] = {FASTQ_NO_RECORD, FASTQ_NO_RECORD};
@@ -239,14 +180,12 @@ static int map_file_gather(MapFileSession& ss, const char* d_raw, int64_t n, siz
 
 /* The format tail of one device chunk, for both file calls: a holds the chunk's records, results, line list and nlines; the
  * RNAME table, size, off and the counters are set here.  Every line's size and offset, then the total and the call's counters n
- * (mapped; paired: proper and rescued too) in one wait.  Then the output side: the next output slot of the rotation (the writer is
- * done with the chunk that used it three chunks ago, so its copy out of d_out is over too), the lines emitted into it, the copy
- * out started on the copy-out stream, the write queued. */
+ * (mapped; paired: proper and rescued too) in one wait.  Then the lines are emitted: into the output (MapOutput::put), or for a
+ * sorted call into a block that stays on the device. */
 template <bool PAIRED>
 static int map_file_format(MapFileSession& ss, MapTmp& tmp, SamArgs& a, unsigned long long* n) {
     asm_handle* h = ss.h;
     const char* who = ss.who;
-    MapFilePipe& pp = ss.pipe;
     const int64_t nlines = a.nlines;
     constexpr size_t NC = PAIRED ? 3 : 1;
     Scratch<unsigned long long> d_size(h), d_off(h), d_n(h);
@@ -256,30 +195,18 @@ static int map_file_format(MapFileSession& ss, MapTmp& tmp, SamArgs& a, unsigned
     STREAM_TRY(who, hipMemsetAsync(d_n.p, 0, sizeof(unsigned long long) * NC, h->stream));
     a.names = ss.d_names.p, a.name_off = ss.d_name_off.p, a.size = d_size.p, a.off = d_off.p, a.n_mapped = d_n.p;
     if (PAIRED) a.n_proper = d_n.p + 1, a.n_rescued = d_n.p + 2;
-    const bool bam = ss.bam != nullptr;
-    STREAM_TRY(who, launch(h, bam ? bam_size_kernel<PAIRED> : sam_size_kernel<PAIRED>, grid_for(nlines + 1), ASM_BLOCK, a));
+    const bool bam = ss.out.bam != nullptr;
+    const LineKernels k = line_kernels<PAIRED>(bam);
+    STREAM_TRY(who, launch(h, k.size, grid_for(nlines + 1), ASM_BLOCK, a));
     STREAM_TRY(who, map_exclusive_sum(h, tmp, d_size.p, d_off.p, nlines + 1));
     unsigned long long total = 0;
     STREAM_TRY(who, fetch(h, {fetched(&total, d_off.p + nlines), fetched(n, d_n.p, NC)}));
-    if (ss.sort) { /* a sorted call: the lines are emitted into a block that stays on the device, and nothing is written yet */
-        if (const int rc = ss.sort->hold<PAIRED>(a, total, bam)) return rc;
-        ss.st.records += nlines, ss.st.chunks++;
-        if (!bam) ss.st.bytes_out += (int64_t)total; /* BAM: the framed bytes, known when the slabs are cut (finish()) */
-        return ASM_OK;
-    }
-    /* BAM: the records go behind the stream's carry in a staging block, and what leaves is the whole blocks framed from it: the slot
-     * has room for their stored form, and `bytes` becomes what the container's level made of them */
-    size_t bytes = bam ? ss.bam->framed((size_t)total) : (size_t)total;
-    int o = 0;
-    if (const int rc = map_out_slot(h, who, pp, *ss.writer, ss.out_seq, bytes, &o)) return rc;
-    Scratch<char> d_stage(h);
-    a.out = pp.d_out[o];
-    if (bam) STREAM_TRY(who, ss.bam->stage((size_t)total, d_stage, &a.out));
-    STREAM_TRY(who, launch(h, bam ? bam_emit_kernel<PAIRED> : sam_emit_kernel<PAIRED>, map_grid((uint64_t)nlines * 64, h), 256, a));
-    if (bam) STREAM_TRY(who, ss.bam->frame(d_stage, (size_t)total, pp.d_out[o], &bytes));
-    if (const int rc = map_out_ship(h, who, pp, *ss.writer, ss.out_seq, o, bytes)) return rc;
-    ss.st.records += nlines, ss.st.chunks++, ss.st.bytes_out += (int64_t)bytes;
-    return ASM_OK;
+    ss.st.records += nlines, ss.st.chunks++;
+    if (ss.sort) return ss.sort->hold<PAIRED>(a, total, bam); /* nothing is written yet */
+    return ss.out.put((size_t)total, [&](char* dst) {
+        a.out = dst;
+        return launch(h, k.emit, map_grid((uint64_t)nlines * 64, h), 256, a);
+    });
 }
 
 /* One file chunk (`lines` lines of whole records in d_raw[0, nbytes)), for both file calls: the newline index, then
@@ -400,7 +327,7 @@ static int map_file_run(asm_handle* h, const char* who, const asm_index* ix, con
                         asm_map_file_stats* stats, const int64_t* sort_cap, asm_sam_sort_stats* sort_stats) {
     MapFileSession ss(h, who, chunk);
     if (sort_cap) ss.sort.reset(new SamSortHold(h, who, ix->n_seqs, (size_t)*sort_cap));
-    StreamInput& in = ss.pipe.in;
+    StreamInput& in = ss.in;
     size_t file_bytes = 0;
     if (const int rc = in.open_file(fastq_path, &file_bytes)) return rc;
     if (const int rc = ss.open(ix, seq_names, 1, &in.fd, &file_bytes, &fastq_path, sam_path, header)) return rc;

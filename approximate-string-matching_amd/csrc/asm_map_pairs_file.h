@@ -97,7 +97,7 @@ static int map_pairs_file_run(asm_handle* h, const char* who, const asm_index* i
                               asm_map_pairs_file_stats* stats, const int64_t* sort_cap, asm_sam_sort_stats* sort_stats) {
     MapFileSession ss(h, who, chunk);
     if (sort_cap) ss.sort.reset(new SamSortHold(h, who, ix->n_seqs, (size_t)*sort_cap));
-    StreamInput& in = ss.pipe.in;
+    StreamInput& in = ss.in;
     struct Fd { /* file 2 (file 1 is the input side's) */
         int fd = -1;
         ~Fd() {

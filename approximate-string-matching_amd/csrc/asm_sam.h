@@ -1,9 +1,10 @@
 // SAM lines of asm_map_file and asm_map_pairs_file (contract: docs/design/mapper.md, "Files: FASTQ in, SAM out" and "Files: two
 // FASTQ files in, paired SAM out"): the text of one output line, single-end or paired, written once for three users.  sam_format<Sink> walks the fields of a line in order and hands every piece to a sink:
-//   SamSizeSink  adds the lengths                      (sam_size_kernel: one thread per line)
-//   SamLaneSink  stores the bytes p = lane (mod 64)    (sam_emit_kernel: one wave per line, 64 contiguous bytes per store)
-// so the size and the bytes cannot disagree.  The part above the kernels holds no HIP: host/sam_host_check.cpp compiles it with
-// plain g++ under ASan + UBSan and runs the lane sink for lanes 0..63 in turn (tests/test_map_file_host.py,
+//   SamSizeSink  adds the lengths                      (line_size_kernel<SamText, .>: one thread per line)
+//   SamLaneSink  stores the bytes p = lane (mod 64)    (line_emit_kernel<SamText, .>: one wave per line, 64 contiguous bytes per store)
+// so the size and the bytes cannot disagree.  The two kernels take the output format as a tag (SamText here, BamRecord in
+// asm_bam.h, whose line_kernels picks the pair to launch).  The part above the kernels holds no HIP: host/sam_host_check.cpp
+// compiles it with plain g++ under ASan + UBSan and runs the lane sink for lanes 0..63 in turn (tests/test_map_file_host.py,
 // tests/test_map_pairs_file_host.py).
 #pragma once
 #include <stdint.h>
@@ -339,22 +340,28 @@ __device__ inline SamLine sam_load_line(const SamArgs& a, long l) {
     return s;
 }
 
-/* the two kernels below serve both calls: PAIRED picks the load step at compile time (one body holding both makes the compiler merge
- * their stores into the line through a pointer, which costs a stack slot and the single-end path a third more registers) */
+/* The two kernels below serve both calls and both output formats.  PAIRED picks the load step at compile time (one body holding
+ * both makes the compiler merge their stores into the line through a pointer, which costs a stack slot and the single-end path a third
+ * more registers); FMT is what a line becomes: size(line) bytes, which emit(line, out, lane) stores (SamText; BamRecord of asm_bam.h) */
 template <bool PAIRED>
 __device__ inline SamLine sam_load(const SamArgs& a, long l) {
     if constexpr (PAIRED) return sam_load_pair_line(a, l);
     else return sam_load_line(a, l);
 }
 
+struct SamText {
+    SAM_HD static uint64_t size(const SamLine& l) { return sam_line_size(l); }
+    SAM_HD static void emit(const SamLine& l, char* out, uint32_t lane) { sam_line_emit(l, out, lane); }
+};
+
 /* one thread per line: its exact byte length */
-template <bool PAIRED>
-__global__ __launch_bounds__(256) void sam_size_kernel(SamArgs a) {
+template <class FMT, bool PAIRED>
+__global__ __launch_bounds__(256) void line_size_kernel(SamArgs a) {
     const long l = (long)blockIdx.x * blockDim.x + threadIdx.x;
     bool primary = false, proper = false, rescued = false;
     if (l < a.nlines) {
         const SamLine s = sam_load<PAIRED>(a, l);
-        a.size[l] = sam_line_size(s);
+        a.size[l] = FMT::size(s);
         primary = s.mapped && s.rank == 0u;
         proper = s.paired && s.proper && s.mate == 0u, rescued = s.paired && s.rescued;
     } else if (l == a.nlines) {
@@ -370,11 +377,11 @@ __global__ __launch_bounds__(256) void sam_size_kernel(SamArgs a) {
 }
 
 /* one wave per line: every lane walks the line's pieces and stores its own bytes, 64 contiguous bytes per store */
-template <bool PAIRED>
-__global__ __launch_bounds__(256) void sam_emit_kernel(SamArgs a) {
+template <class FMT, bool PAIRED>
+__global__ __launch_bounds__(256) void line_emit_kernel(SamArgs a) {
     const uint32_t lane = threadIdx.x & 63u;
     const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-    for (long l = wave; l < a.nlines; l += nwaves) sam_line_emit(sam_load<PAIRED>(a, l), a.out + a.off[l], lane);
+    for (long l = wave; l < a.nlines; l += nwaves) FMT::emit(sam_load<PAIRED>(a, l), a.out + a.off[l], lane);
 }
 #endif /* __HIPCC__ */

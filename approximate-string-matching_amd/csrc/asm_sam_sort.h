@@ -2,10 +2,10 @@
 // docs/design/mapper.md, "Sorted output").  A sorted call formats every device chunk as the unsorted call does, but keeps the
 // formatted block on the device with one (key, source address, size) entry per line; after the last chunk the keys are sorted
 // (stable, so equal keys keep the unsorted order), the sizes are permuted and scanned into output offsets, and
-// sam_line_gather_kernel copies the lines in sorted order into output slabs that leave through the unsorted call's pinned
-// rotation and writer.  The key itself is sam_sort_key (asm_sam.h), the slab cutter sam_slab_cuts (asm_host.h).
+// sam_line_gather_kernel copies the lines in sorted order into output slabs that leave as the unsorted call's chunks do, one
+// MapOutput::put each (asm_map_out.h).  The key itself is sam_sort_key (asm_sam.h), the slab cutter sam_slab_cuts (asm_host.h).
 // The part above the kernels holds no HIP: host/sort_host_check.cpp compiles the per-lane copy with plain g++ under ASan + UBSan
-// (tests/test_sam_sort_host.py).  asm_capi.hip includes this file inside its extern "C" block, between asm_map_host.h and
+// (tests/test_sam_sort_host.py).  asm_capi.hip includes this file inside its extern "C" block, between asm_map_out.h and
 // asm_map_file.h.
 #pragma once
 #include <stdint.h>
@@ -19,7 +19,7 @@ extern "C++" {
  * once; a whole wave per line would leave most of its 64 x 16 bytes idle on all but the longest lines, and one thread per line
  * would store 16 bytes per instruction to 64 unrelated places. */
 #define SAM_GATHER_LANES 16u
-/* bytes behind a held block's text that may be read (the copy's loads look up to 4 bytes past a line), as map_file_format pads */
+/* bytes behind a held block's text that may be read (the copy's loads look up to 4 bytes past a line), as MapOutput pads a slot */
 #define SAM_SORT_PAD 64u
 
 struct alignas(4) SamQuad {
@@ -56,7 +56,7 @@ SAM_HD void sam_gather_line(char* dst, Src src, uint64_t len, uint32_t g) {
 
 #if defined(__HIPCC__)
 
-/* one thread per line of a held chunk, behind its sam_size_kernel and scan: the line's key, where its bytes lie and how many */
+/* one thread per line of a held chunk, behind its line_size_kernel and scan: the line's key, where its bytes lie and how many */
 template <bool PAIRED>
 __global__ __launch_bounds__(256) void sam_sort_key_kernel(SamArgs a, int32_t n_seqs, unsigned long long* __restrict__ key,
                                                            unsigned long long* __restrict__ src, unsigned long long* __restrict__ size) {
@@ -161,19 +161,16 @@ struct SamSortHold {
         for (unsigned long long** t : {&c.key, &c.src, &c.size})
             if (const int rc = alloc(t, table)) return rc;
         a.out = c.text;
-        STREAM_TRY(who, launch(h, bam ? bam_emit_kernel<PAIRED> : sam_emit_kernel<PAIRED>, map_grid((uint64_t)nlines * 64, h), 256, a));
+        STREAM_TRY(who, launch(h, line_kernels<PAIRED>(bam).emit, map_grid((uint64_t)nlines * 64, h), 256, a));
         if (nlines) STREAM_TRY(who, launch(h, sam_sort_key_kernel<PAIRED>, grid_for(nlines), ASM_BLOCK, a, n_seqs, c.key, c.src, c.size));
         chunks.push_back(c);
         st.lines += nlines, st.bytes_held += (int64_t)total;
         return ASM_OK;
     }
 
-    /* After the last chunk: sort, offsets, and the lines gathered slab by slab (at most slab_cap bytes, or one line) into the pipe's
-     * output rotation; out_seq counts the writer's jobs.  The writer still has to be finished by the caller.  bz: the BAM call's
-     * record stream; a slab is then gathered behind the stream's carry and leaves as the whole blocks framed from it, *framed bytes
-     * in all (not touched without bz). */
-    template <class Pipe>
-    int flush(Pipe& pp, asm_host::ChunkWriter& writer, int64_t& out_seq, size_t slab_cap, BgzfStream* bz, size_t* framed) {
+    /* After the last chunk: sort, offsets, and the lines gathered slab by slab (at most slab_cap bytes, or one line), one put each.
+     * The output still has to be finished by the caller. */
+    int flush(MapOutput& out, size_t slab_cap) {
         const auto t0 = std::chrono::steady_clock::now();
         const size_t n = (size_t)st.lines;
         if (n == 0) return ASM_OK;
@@ -225,18 +222,12 @@ struct SamSortHold {
         for (size_t s = 0; s + 1 < cuts.size(); s++) {
             const size_t i0 = cuts[s], cnt = cuts[s + 1] - i0;
             const size_t bytes = (size_t)(h_off[cuts[s + 1]] - h_off[i0]);
-            size_t out_bytes = bz ? bz->framed(bytes) : bytes; /* BAM: the slot's room, then what the container's level wrote */
-            int o = 0;
-            if (const int rc = map_out_slot(h, who, pp, writer, out_seq, out_bytes, &o)) return rc;
-            Scratch<char> d_stage(h);
-            char* to = pp.d_out[o];
-            if (bz) STREAM_TRY(who, bz->stage(bytes, d_stage, &to));
-            STREAM_TRY(who, launch(h, sam_line_gather_kernel, map_grid((uint64_t)cnt * SAM_GATHER_LANES, h), 256, (const u64*)psrc + i0,
-                                   (const u64*)off + i0, (long)cnt, (u64)h_off[i0], to));
-            if (bz) STREAM_TRY(who, bz->frame(d_stage, bytes, pp.d_out[o], &out_bytes));
-            if (const int rc = map_out_ship(h, who, pp, writer, out_seq, o, out_bytes)) return rc;
+            if (const int rc = out.put(bytes, [&](char* to) {
+                    return launch(h, sam_line_gather_kernel, map_grid((uint64_t)cnt * SAM_GATHER_LANES, h), 256, (const u64*)psrc + i0,
+                                  (const u64*)off + i0, (long)cnt, (u64)h_off[i0], to);
+                }))
+                return rc;
             st.slabs++;
-            if (bz) *framed += out_bytes;
         }
         st.seconds_sort = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         return ASM_OK;

@@ -13,6 +13,10 @@
 //   bam_host_check bgzf <in> <out> <with_eof>
 // frames the bytes of <in> into <out> with bgzf_frame_host (the per-slice CRC, the combine and the slice copy that bgzf_frame_kernel's
 // threads run) and prints one line per block: the payload's length and its CRC-32 in hex, as the block carries it.
+//
+//   bam_host_check header <in> <out>
+// builds the BAM header with bam_header_bytes and writes it to <out>.  <in> (little endian): u32 l_text, the text; u32 n_ref; per
+// reference sequence u32 name length, the name, u32 length.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -91,8 +95,31 @@ static int bgzf(const char* in_path, const char* out_path, int with_eof) {
     return fclose(out) == 0 ? 0 : 4;
 }
 
+static int header(const char* in_path, const char* out_path) {
+    FILE* in = fopen(in_path, "rb");
+    FILE* out = fopen(out_path, "wb");
+    if (!in || !out) return 2;
+    std::vector<char> text;
+    uint32_t n_ref = 0;
+    if (!get_bytes(in, text) || !get(in, &n_ref, 4)) return 3;
+    std::vector<std::vector<char>> names(n_ref);
+    std::vector<const char*> name_ptr(n_ref);
+    std::vector<uint32_t> lengths(n_ref);
+    for (uint32_t r = 0; r < n_ref; r++) {
+        if (!get_bytes(in, names[r]) || !get(in, &lengths[r], 4)) return 3;
+        names[r].push_back('\0');
+        name_ptr[r] = names[r].data();
+    }
+    fclose(in);
+    /* an empty text comes as NULL, as a call without a header gives it */
+    const std::vector<uint8_t> bytes = bam_header_bytes(text.empty() ? nullptr : text.data(), text.size(), name_ptr.data(), lengths.data(), n_ref);
+    fwrite(bytes.data(), 1, bytes.size(), out);
+    return fclose(out) == 0 ? 0 : 4;
+}
+
 int main(int argc, char** argv) {
     if (argc == 4 && strcmp(argv[1], "records") == 0) return records(argv[2], argv[3]);
     if (argc == 5 && strcmp(argv[1], "bgzf") == 0) return bgzf(argv[2], argv[3], atoi(argv[4]));
+    if (argc == 4 && strcmp(argv[1], "header") == 0) return header(argv[2], argv[3]);
     return 2;
 }

@@ -1,7 +1,8 @@
 """BAM output on the CPU (docs/design/mapper.md, "BAM output"): the reader of tests/bam_cases.py on its hand-made records; then
 host/bam_host_check.cpp, built here under ASan + UBSan, which runs bam_format (csrc/asm_bam.h) through the lane sink for lanes 0..63
 and sam_format on the same line, so that every decoded record must print as the SAM line of the same SamLine; the host CRC, combine
-and slice copy of csrc/asm_bgzf.h against zlib; asm_bgzf_bound against the formula."""
+and slice copy of csrc/asm_bgzf.h against zlib; bam_header_bytes against the reader's encode_header; asm_bgzf_bound against the
+formula."""
 import gzip
 import os
 import random
@@ -164,6 +165,29 @@ def test_bam_format_equals_sam_format(bam_check, tmp_path):
     for v, typ in ((255, "C"), (256, "S"), (65535, "S"), (65536, "I")):
         assert [t[1] for t in seen["integer tag at %d" % v][0]["tags"] if t[0] in ("NM", "NH", "XH")] == [typ] * 3
         assert ("XP", typ, v) in seen["XP at %d" % v][0]["tags"]
+
+
+def test_header_bytes_equal_the_reader_s(bam_check, tmp_path):
+    """bam_header_bytes (csrc/asm_bam.h), what a BAM file call frames as the file's head, against bam_cases.encode_header"""
+    cases = {
+        "the hand-made references": (b"@HD\tVN:1.6\n", bc.HAND_REFS),
+        "no references": (b"@HD\tVN:1.6\n", []),
+        "an empty text": (b"", bc.HAND_REFS),
+        "a text that ends in an empty line": (b"@HD\tVN:1.6\n@CO\tx\n\n", bc.HAND_REFS),
+        "a 255-byte name": (b"@CO\tlong\n", [("n" * 255, 1), ("chrB", 0xffffffff >> 1)]),
+    }
+    for what, (text, refs) in cases.items():
+        inp, out = tmp_path / "header.bin", tmp_path / "header.out"
+        inp.write_bytes(struct.pack("<I", len(text)) + text + struct.pack("<I", len(refs)) + b"".join(
+            struct.pack("<I", len(name)) + name.encode("latin-1") + struct.pack("<I", length) for name, length in refs))
+        r = subprocess.run([bam_check, "header", str(inp), str(out)], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, (what, r.stderr[-3000:])
+        got = out.read_bytes()
+        assert got == bc.encode_header(text, refs), what
+        assert got[:4] == b"BAM\x01" and struct.unpack_from("<i", got, 4)[0] == len(text), what
+    # the reader takes the bytes back
+    text, refs = cases["a 255-byte name"]
+    assert bc.parse_bam(bc.frame_stored(bc.encode_header(text, refs)))[:2] == (text, refs)
 
 
 # ---- the container's CRC on the CPU --------------------------------------------------------------------------------------------------
