@@ -523,12 +523,12 @@ static hipError_t launch_leap_unit_w(asm_handle* h, const asm_bucket& b, OutMap 
 template <int K, int W64>
 static hipError_t launch_leap_general_w(asm_handle* h, const asm_bucket& b, const asm_params* p, OutMap out) {
     const unsigned grid = (unsigned)((b.n + LEAP_GEN_THREADS - 1) / LEAP_GEN_THREADS);
-    const RingGeometry rg(p->x, p->o, p->e);
+    const LvRings rg = LvRings::pow2(p->x, p->o, p->e);
     /* bytes (every stored position + 2 fits) halve the LDS and double the waves per CU, but four threads then write into one
      * dword: worth it only where shorts would leave the CU underfilled */
-    const bool bytes = b.maxlen + 4 <= 255 && rg.lds_bytes(2 * K + 1, LEAP_GEN_THREADS, 2) > 20 * 1024;
+    const bool bytes = b.maxlen + 4 <= 255 && rg.ring_bytes(2 * K + 1, LEAP_GEN_THREADS, 2) > 20 * 1024;
     const auto go = [&](auto kernel, size_t entry_bytes) {
-        return launch_lds(h, kernel, grid, LEAP_GEN_THREADS, rg.lds_bytes(2 * K + 1, LEAP_GEN_THREADS, entry_bytes), b.planes, b.lens,
+        return launch_lds(h, kernel, grid, LEAP_GEN_THREADS, rg.ring_bytes(2 * K + 1, LEAP_GEN_THREADS, entry_bytes), b.planes, b.lens,
                           (long)b.n, b.w4, (int)p->x, (int)p->o, (int)p->e, rg.gm, rg.gi, out);
     };
     return bytes ? go(leap_general_kernel<K, W64, uint8_t>, 1) : go(leap_general_kernel<K, W64, uint16_t>, 2);
@@ -539,9 +539,9 @@ static hipError_t launch_leap_general_w(asm_handle* h, const asm_bucket& b, cons
 template <int K, int W64, typename EnT>
 static hipError_t launch_nw_wfa_pass(asm_handle* h, const asm_bucket& b, const asm_params* p, OutMap out, const uint32_t* in_list,
                                      const uint32_t* in_count, uint32_t* todo, uint32_t* todo_count) {
-    const WfaRings rg(p->x, p->o, p->e);
+    const LvRings rg = LvRings::exact(p->x, p->o, p->e);
     return launch_lds(h, nw_wfa_kernel<K, W64, EnT, false>, (unsigned)((b.n + LEAP_GEN_THREADS - 1) / LEAP_GEN_THREADS), LEAP_GEN_THREADS,
-                      rg.lds_bytes(2 * K + 1, LEAP_GEN_THREADS, sizeof(EnT)), b.planes, b.lens, (long)b.n, b.w4, (int)p->x, (int)p->o,
+                      rg.ring_bytes(2 * K + 1, LEAP_GEN_THREADS, sizeof(EnT)), b.planes, b.lens, (long)b.n, b.w4, (int)p->x, (int)p->o,
                       (int)p->e, rg.gm, rg.gi, out, in_list, in_count, todo, todo_count);
 }
 
@@ -552,7 +552,7 @@ static int launch_nw_wfa(asm_handle* h, const asm_bucket& b, const asm_params* p
     uint32_t* const list_b = h->d_todo + (size_t)b.n + 1;
     HIPCHK(h, hipMemsetAsync(list_a, 0, sizeof(uint32_t), h->stream));
     HIPCHK(h, hipMemsetAsync(list_b, 0, sizeof(uint32_t), h->stream));
-    const WfaRings rg(p->x, p->o, p->e);
+    const LvRings rg = LvRings::exact(p->x, p->o, p->e);
     bool bytes = false; /* strings up to 128: every stored position + 2 fits a byte, half the LDS */
     if constexpr (W64 == 2) {
         bytes = true;
@@ -561,11 +561,12 @@ static int launch_nw_wfa(asm_handle* h, const asm_bucket& b, const asm_params* p
     if (!bytes) HIPCHK(h, (launch_nw_wfa_pass<NW_WFA_K, W64, uint16_t>(h, b, p, out, nullptr, nullptr, list_a + 1, list_a)));
     const uint32_t* rest = list_a;
     const size_t en = b.maxlen + 2 <= 255 ? 1 : 2;
-    if (nw_oct_lds(2 * W64, NW_WFA_K2, rg.gm, rg.gi, en) <= 64 * 1024) {
+    const size_t oct_lds = rg.quad_lds(NW_OCT_PAIRS, 2 * W64, NW_WFA_K2, en);
+    if (oct_lds <= 64 * 1024) {
         /* the unsettled percent or two: eight threads per pair, |d| <= 15 (asm_wave.h) */
         const unsigned grid = (unsigned)std::min<int64_t>((b.n + NW_OCT_PAIRS - 1) / NW_OCT_PAIRS, (int64_t)h->num_cus * 16);
         const auto oct = [&](auto kernel) {
-            return launch_lds(h, kernel, grid, NW_OCT_THREADS, nw_oct_lds(2 * W64, NW_WFA_K2, rg.gm, rg.gi, en), b.planes, b.lens,
+            return launch_lds(h, kernel, grid, NW_OCT_THREADS, oct_lds, b.planes, b.lens,
                               (long)b.n, b.w4, NW_WFA_K2, (int)p->x, (int)p->o, (int)p->e, rg.gm, rg.gi, out, list_a + 1, list_a,
                               list_b + 1, list_b);
         };
@@ -1296,6 +1297,7 @@ static int align_bucket(asm_handle* h, const asm_bucket& b, int aligner, const a
         else
             HIPCHK(h, launch_greedy_wide(h->stream, planes, lens, b.n, b.w4, p->k, ga, out, cig));
     } else if (aligner == ASM_LEAP) {
+        const LvRings quad_rg = unit ? LvRings::unit() : LvRings::pow2(p->x, p->o, p->e); /* leap_quad_kernel's rings (LEAP penalties are at most 15) */
         if (p->leap_mode != ASM_LEAP_GLOBAL) {
             /* LV's other ED_modes have no caller in the reference: one kernel serves them, the workgroup-per-pair form that takes
              * any band and any penalties (asm_wide.h) */
@@ -1307,14 +1309,12 @@ static int align_bucket(asm_handle* h, const asm_bucket& b, int aligner, const a
             HIPCHK(h, (with_const<1, LEAP_UNIT_MAX_K>((int)p->k,
                                                      [&](auto k) { return launch_leap_unit<decltype(k)::value>(h, b, out, hint); })));
         } else if (!unit && p->k >= 1 && ((p->k <= 5 && b.maxlen <= 256) || (p->k <= 8 && b.maxlen <= 128)) && h->wave_kernels &&
-                   RingGeometry(p->x, p->o, p->e).lds_bytes(2 * p->k + 1, LEAP_GEN_THREADS) <= 64 * 1024) {
+                   LvRings::pow2(p->x, p->o, p->e).ring_bytes(2 * p->k + 1, LEAP_GEN_THREADS, sizeof(uint16_t)) <= 64 * 1024) {
             /* general penalties, narrow band: thread per pair with an LDS generation ring */
             HIPCHK(h, (with_const<1, 8>((int)p->k, [&](auto k) { return launch_leap_general<decltype(k)::value>(h, b, p, out); })));
         } else if (h->wave_kernels && b.maxlen <= 512 &&
-                   leap_quad_lds((b.maxlen + 31) / 32, (int)p->k, unit ? 2 : RingGeometry(p->x, p->o, p->e).gm,
-                                 unit ? 0 : RingGeometry(p->x, p->o, p->e).gi, b.maxlen + 2 <= 255 ? 1 : 2) <= 64 * 1024) {
+                   quad_rg.quad_lds(LEAP_QUAD_PAIRS, (b.maxlen + 31) / 32, (int)p->k, b.maxlen + 2 <= 255 ? 1 : 2) <= 64 * 1024) {
             /* wide band: four threads per pair, generation rings and planes in LDS (asm_wave.h) */
-            const RingGeometry rg(p->x, p->o, p->e);
             const int w32 = (b.maxlen + 31) / 32;
             const int32_t* const qhint = h->leap_hint ? hint : nullptr;
             /* long-running cases (long strings or general penalties): sort the whole bucket by the hint — one 6-bit radix pass —
@@ -1339,7 +1339,7 @@ static int align_bucket(asm_handle* h, const asm_bucket& b, int aligner, const a
             }
             const auto quad = [&](auto w, auto en) { /* W 32-bit words per string; ring entries of en's type */
                 return launch_leap_quad<decltype(w)::value, decltype(en)>(h->stream, planes, lens, b.n, b.w4, (int)p->k, unit, (int)p->x,
-                                                                          (int)p->o, (int)p->e, rg.gm, rg.gi, out, qhint, qperm);
+                                                                          (int)p->o, (int)p->e, quad_rg, out, qhint, qperm);
             };
             HIPCHK(h, (with_const_of<4, 5, 6, 8, 12, 16>(w32, [&](auto w) {
                        return b.maxlen + 2 <= 255 ? quad(w, uint8_t{}) : quad(w, uint16_t{}); /* every stored position + 2 fits a byte */
@@ -1380,7 +1380,7 @@ static int align_bucket(asm_handle* h, const asm_bucket& b, int aligner, const a
             /* a zero penalty makes the wavefront read the generation it is writing (ring slot s - 0): plain Gotoh handles it */
             const bool positive = p->x >= 1 && p->o >= 1 && p->e >= 1;
             if (h->nw_wfa && positive && b.maxlen <= 256 &&
-                WfaRings(p->x, p->o, p->e).lds_bytes(2 * NW_WFA_K + 1, LEAP_GEN_THREADS, 2) <= 64 * 1024) {
+                LvRings::exact(p->x, p->o, p->e).ring_bytes(2 * NW_WFA_K + 1, LEAP_GEN_THREADS, 2) <= 64 * 1024) {
                 const int rc = with_const_of<2, 4>((b.maxlen + 63) / 64, [&](auto w) { /* 64-bit words per string; rows they hold */
                     return launch_nw_wfa<decltype(w)::value, 64 * decltype(w)::value>(h, b, p, out);
                 });
@@ -1543,19 +1543,19 @@ static int simd_ed_affine_launch(asm_handle* h, const asm_batch* b, int gap_thre
         return fail(h, ASM_EINVAL, "asm_simd_ed_affine_batch_async: penalties must satisfy 1 <= e <= o <= 15, 1 <= x <= 15");
     if (b->n == 0) return ASM_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    const RingGeometry rg(x, o, e);
+    const LvRings rg = LvRings::pow2(x, o, e);
     const int rows = 2 * gap_threshold + 3;
     int threads = 64;
-    while (threads > 16 && (size_t)(rg.gm + 2 * rg.gi) * rows * threads * sizeof(uint16_t) > 150 * 1024) threads >>= 1;
-    const size_t lds = (((size_t)(rg.gm + 2 * rg.gi) * rows * threads * sizeof(uint16_t)) + 3) & ~(size_t)3;
+    while (threads > 16 && rg.ring_bytes(rows, threads, sizeof(uint16_t)) > 150 * 1024) threads >>= 1;
+    const size_t lds = rg.ring_bytes(rows, threads, sizeof(uint16_t));
     /* threads and lds are the thread-per-pair kernel's (strings beyond one granule); the refusal below also meets batches whose
      * buckets all go to the quad kernel, which has its own LDS layout.  Stricter than needed there, but callers can observe it:
      * kept as it is. */
     if (lds > 150 * 1024) return fail(h, ASM_EINVAL, "asm_simd_ed_affine_batch_async: generation rings exceed the LDS");
     return for_each_bucket(b, d_ed, [&](const asm_bucket& k, OutMap out) -> int {
         if (k.maxlen <= 128) /* four threads per pair (thread per pair measured 0.28/0.71/3.5 ms per 10^6 C2 pairs at gap 3/8/30 against 0.29/0.46/0.79) */
-            HIPCHK(h, launch_lds(h, simd_ed_affine_quad_kernel, (unsigned)((k.n + 15) / 16), 64, simd_quad_lds(gap_threshold, rg.gm, rg.gi),
-                                 k.planes, k.lens, (long)k.n, k.w4, gap_threshold, af_threshold, x, o, e, rg.gm, rg.gi, mode, out));
+            HIPCHK(h, launch_lds(h, simd_ed_affine_quad_kernel, (unsigned)((k.n + 15) / 16), 64,
+                                 rg.quad_lds(16, SIMD_QUAD_W32, gap_threshold, sizeof(uint8_t)), k.planes, k.lens, (long)k.n, k.w4, gap_threshold, af_threshold, x, o, e, rg.gm, rg.gi, mode, out));
         else /* thread per pair: the only instantiation kept is the one for strings beyond one granule */
             HIPCHK(h, launch_lds(h, simd_ed_affine_kernel<4>, (unsigned)((k.n + threads - 1) / threads), (unsigned)threads, lds, k.planes,
                                  k.lens, (long)k.n, k.w4, gap_threshold, af_threshold, x, o, e, rg.gm, rg.gi, mode, out));

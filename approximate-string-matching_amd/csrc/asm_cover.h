@@ -90,16 +90,6 @@ __global__ __launch_bounds__(ASM_BLOCK) void nw_trace_forward_kernel(const uint4
     band_result[i] = nw_band<ND, W, TraceSink<W>>(A0, A1, B0, B1, m, nn, sink);
 }
 
-// bit p of a multi-word vector (p >= 0; 0 beyond the vector)
-template <int W64>
-ASM_DEV uint32_t vw_bit(const VW<W64>& v, int p) {
-    u64 word = 0;
-#pragma unroll
-    for (int q = 0; q < W64; q++)
-        if ((p >> 6) == q) word = v.w[q];
-    return (uint32_t)(word >> (p & 63)) & 1u;
-}
-
 // 64 bits of v starting at bit `off` (zeros beyond the vector)
 template <int W64>
 ASM_DEV u64 vw_window(const VW<W64>& v, int off) {
@@ -329,16 +319,8 @@ __global__ __launch_bounds__(ASM_BLOCK) void nw_trace_cover_kernel(const uint4* 
         if (ca.nw_nops) ca.nw_nops[pair] = (uint8_t)(ok ? (nops > 255 ? 255 : nops) : 0);
         covered = flag == COVER_YES, unknown = flag == COVER_UNKNOWN;
     }
-    if (todo != nullptr) { /* wave-aggregated append: one atomic per wave */
-        const u64 bal = __ballot(unknown != 0u);
-        if (bal) {
-            const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-            const int leader = __builtin_ctzll(bal);
-            uint32_t base = 0;
-            if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(todo_count, (uint32_t)__builtin_popcountll(bal));
-            base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-            if (unknown) todo[base + rank] = (uint32_t)i;
-        }
+    if (todo != nullptr) {
+        wave_append(todo, todo_count, unknown != 0u, (uint32_t)i);
         unknown = 0; /* the full-matrix pass answers them */
     }
     const unsigned int tc = block_sum_256(covered, s_part), tu = block_sum_256(unknown, s_part);
@@ -349,11 +331,9 @@ __global__ __launch_bounds__(ASM_BLOCK) void nw_trace_cover_kernel(const uint4* 
 }
 
 // --------------------------------------------------------------------------------------------------------
-// Full-matrix Gotoh with traceback and coverage verdict, any (x, o, e), any distance.  One thread per pair; the forward sweep is
-// nw_affine_kernel's (column blocks of 32 in registers, block boundary column through LDS) and additionally records, per
-// cell, the four facts the oracle's traceback asks for (oracle/asm_oracle.c, orc_nw_cigar_batch):
-//   bit 0  H == H[i-1][j-1] + sub      bit 1  H == E      bit 2  E == E[i][j-1] + e      bit 3  F == F[i-1][j] + e
-// packed 8 cells per dword in scratch[((i-1) * cols8 + (j-1)/8) * stride + slot] (coalesced across the pairs of a wave).
+// Full-matrix Gotoh with traceback and coverage verdict, any (x, o, e), any distance.  One thread per pair: gotoh_sweep with the
+// trace sink into `scratch` ([row][8 cells][pair]), then gotoh_traceback (asm_affine.h); the runs go to the NW CIGAR row and,
+// '=' runs of three or more, to LCM2.
 // --------------------------------------------------------------------------------------------------------
 template <int W64, int MAXROWS>
 __global__ __launch_bounds__(64) void nw_trace_affine_kernel(const uint4* __restrict__ planes, const uint32_t* __restrict__ lens,
@@ -376,120 +356,18 @@ __global__ __launch_bounds__(64) void nw_trace_affine_kernel(const uint4* __rest
         const int m = (int)(ln & 0xffffu), nn = (int)(ln >> 16);
         VW<W64> A0, A1, B0, B1;
         load_planes<W64>(planes, n, w4, i, A0, A1, B0, B1);
-        // ---------------- forward ----------------
-        for (int j0 = 0; j0 < nn; j0 += NW_CB) {
-            uint32_t tb0 = 0, tb1 = 0;
-#pragma unroll
-            for (int q = 0; q < W64; q++) {
-                if ((j0 >> 6) == q) {
-                    tb0 = (uint32_t)(B0.w[q] >> (j0 & 63));
-                    tb1 = (uint32_t)(B1.w[q] >> (j0 & 63));
-                }
-            }
-            int H[NW_CB], F[NW_CB];
-#pragma unroll
-            for (int jj = 0; jj < NW_CB; jj++) {
-                H[jj] = o + (j0 + jj) * e; /* H[0][j], j = j0+jj+1 */
-                F[jj] = NW_BIG;
-            }
-            int diag = j0 == 0 ? 0 : o + (j0 - 1) * e; /* H[0][j0] */
-            for (int r = 1; r <= m; r++) {
-                uint32_t a0 = 0, a1 = 0;
-#pragma unroll
-                for (int q = 0; q < W64; q++) {
-                    if (((r - 1) >> 6) == q) {
-                        a0 = (uint32_t)(A0.w[q] >> ((r - 1) & 63)) & 1u;
-                        a1 = (uint32_t)(A1.w[q] >> ((r - 1) & 63)) & 1u;
-                    }
-                }
-                const uint32_t mm = (tb0 ^ (0u - a0)) | (tb1 ^ (0u - a1));
-                int hleft, eleft;
-                if (j0 == 0) {
-                    hleft = o + (r - 1) * e; /* H[r][0] */
-                    eleft = NW_BIG;
-                } else {
-                    const uint32_t pk = s_bound[r][t];
-                    hleft = (int)(pk & 0xffffu);
-                    eleft = (int)(pk >> 16);
-                }
-                const int next_diag = hleft;
-                uint32_t bits[NW_CB / 8];
-#pragma unroll
-                for (int q = 0; q < NW_CB / 8; q++) bits[q] = 0u;
-#pragma unroll
-                for (int jj = 0; jj < NW_CB; jj++) {
-                    const int up = H[jj];
-                    const int fext = F[jj] + e;
-                    int f = up + o < fext ? up + o : fext;
-                    const int eext = eleft + e;
-                    int ee = hleft + o < eext ? hleft + o : eext;
-                    const int dg = diag + (((mm >> jj) & 1u) ? x : 0);
-                    int h = dg < f ? dg : f;
-                    h = ee < h ? ee : h;
-                    const uint32_t nib = (h == dg ? 1u : 0u) | (h == ee ? 2u : 0u) | (ee == eext ? 4u : 0u) | (f == fext ? 8u : 0u);
-                    bits[jj >> 3] |= nib << (4 * (jj & 7));
-                    f = f > NW_BIG ? NW_BIG : f;
-                    ee = ee > NW_BIG ? NW_BIG : ee;
-                    diag = up;
-                    H[jj] = h, F[jj] = f;
-                    hleft = h, eleft = ee;
-                }
-                diag = next_diag;
-                s_bound[r][t] = (uint32_t)hleft | ((uint32_t)eleft << 16);
-#pragma unroll
-                for (int q = 0; q < NW_CB / 8; q++)
-                    if (j0 + 8 * q < nn) scratch[((long)(r - 1) * cols8 + (j0 >> 3) + q) * stride + slot] = bits[q];
-            }
-        }
-        // ---------------- traceback (oracle/asm_oracle.c orc_nw_cigar_batch, rule by rule) ----------------
+        GotohTraceSink trace{scratch, stride, slot, cols8, {}};
+        gotoh_sweep<W64>(A0, A1, B0, B1, m, nn, x, o, e, &s_bound[0][t], 64, trace);
         VW<W64> lcm2;
 #pragma unroll
         for (int q = 0; q < W64; q++) lcm2.w[q] = 0ull;
-        int nops = 0, cur_op = -1, cur_cnt = 0;
-        int ii = m, j = nn, state = 0; /* 0 = H, 1 = E ('D'), 2 = F ('I') */
-        auto flush = [&]() {
-            if (cur_cnt > 0) {
-                if (cur_op == 3 && cur_cnt >= 3) vw_or_range<W64>(lcm2, ii, cur_cnt); /* '=' run: read [ii, ii+cnt) */
-                if (ca.nw_ops && nops < ca.nw_cap) ca.nw_ops[pair * ca.nw_cap + nops] = (uint16_t)((cur_cnt << 3) | cur_op);
-                nops++;
-            }
-            cur_cnt = 0;
+        int nops = 0;
+        auto runs = [&](int op, int count, int at) {
+            if (op == 3 && count >= 3) vw_or_range<W64>(lcm2, at, count); /* '=' run: read [at, at+count) */
+            if (ca.nw_ops && nops < ca.nw_cap) ca.nw_ops[pair * ca.nw_cap + nops] = (uint16_t)((count << 3) | op);
+            nops++;
         };
-        auto emit = [&](int op) {
-            if (op != cur_op) {
-                flush();
-                cur_op = op;
-            }
-            cur_cnt++;
-        };
-        for (int guard = 0; guard < 2 * ASM_MAX_LENGTH + 4 && (ii > 0 || j > 0); guard++) {
-            uint32_t nib = 0u;
-            if (ii > 0 && j > 0) nib = (scratch[((long)(ii - 1) * cols8 + ((j - 1) >> 3)) * stride + slot] >> (4 * ((j - 1) & 7))) & 15u;
-            if (state == 0) {
-                if (ii > 0 && j > 0 && (nib & 1u)) {
-                    const bool match = ((vw_bit<W64>(A0, ii - 1) ^ vw_bit<W64>(B0, j - 1)) |
-                                        (vw_bit<W64>(A1, ii - 1) ^ vw_bit<W64>(B1, j - 1))) == 0u;
-                    emit(match ? 3 : 4);
-                    ii--, j--;
-                } else if (j > 0 && (ii == 0 || (nib & 2u))) {
-                    state = 1; /* H == E; on row 0 H is E by construction */
-                } else {
-                    state = 2;
-                }
-            } else if (state == 1) {
-                emit(2); /* 'D' */
-                /* E[i][j] == E[i][j-1] + e, j > 1: on row 0 E[0][j] = o + (j-1) e, so always */
-                const bool ext = j > 1 && (ii == 0 || (nib & 4u));
-                if (!ext) state = 0;
-                j--;
-            } else {
-                emit(1); /* 'I' */
-                const bool ext = ii > 1 && (j == 0 || (nib & 8u));
-                if (!ext) state = 0;
-                ii--;
-            }
-        }
-        flush();
+        gotoh_traceback<W64>(A0, A1, B0, B1, m, nn, trace, runs);
         const int flag = cover_verdict<W64>(A0, A1, m, lcm2, ca, pair);
         ca.cover[pair] = (uint8_t)flag;
         if (ca.nw_nops) ca.nw_nops[pair] = (uint8_t)(nops > 255 ? 255 : nops);

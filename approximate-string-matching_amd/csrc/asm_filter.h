@@ -218,10 +218,9 @@ __global__ __launch_bounds__(SIMD_ED_THREADS) void simd_ed_kernel(const uint4* _
 // its conditions hold and reset_affine touches none — so a pair's verdict depends on everything the object has seen; that
 // chain runs through every table cell and has no parallel form.  Clean = the reference's verdict for the first pair after
 // init_affine, which is how oracle/ref_harness_simd.cpp drives the compiled reference for the pin.)
-// One thread per pair; the recurrence is LV::run's (leap_general_kernel) over SIMD_ED's own lane masks (simd_lane_mask, rebuilt
-// per use) with the read's length as the target; generation rings of 2^a > max(x, o) and 2^b > ext generations in thread-
-// private LDS columns [slot][lane row][thread], stored + 2 so that the initial zero fill is "never reached" (which also stands
-// in for the e >= penalty guards, see leap_general_kernel).  Result: get_ED() = converge_ED, the smallest e + gap(lane
+// One thread per pair; lv_affine_step (asm_affine.h) over SIMD_ED's own lane masks (simd_lane_mask, rebuilt per use) with the
+// read's length as the target; rings of LvRings::pow2 depths in thread-private LDS columns [slot][lane row][thread].
+// Result: get_ED() = converge_ED, the smallest e + gap(lane
 // distance) <= af_threshold over the lanes that reach the end in the first generation in which one does; 1000000 —
 // reset_affine's value — for a pair that reaches the end at e = 0 (run_affine returns before converge_ED is written); -1 when
 // the pair does not pass.  blockDim.x threads (64, 32 or 16: whatever lets the rings fit the LDS).
@@ -240,8 +239,9 @@ __global__ __launch_bounds__(64) void simd_ed_affine_kernel(const uint4* __restr
     uint16_t* const r_en = s_afring + t;
     uint16_t* const r_ip = r_en + gm * slot;
     uint16_t* const r_dp = r_ip + gi * slot;
+    const LvRings rg{gm, gi};
     {
-        const int words = ((gm + 2 * gi) * slot + 1) / 2;
+        const int words = (int)(rg.ring_bytes(rows, TH, sizeof(uint16_t)) / 4);
         uint32_t* const base = reinterpret_cast<uint32_t*>(s_afring);
         for (int w = t; w < words; w += TH) base[w] = 0u;
     }
@@ -273,41 +273,23 @@ __global__ __launch_bounds__(64) void simd_ed_affine_kernel(const uint4* __restr
         if (result != -2) continue;
         int dmax = e < o ? 0 : (e - o) / ext + 1; /* lanes a gap of this cost can have reached */
         dmax = (dmax > T || all_start) ? T : dmax; /* (every lane is live from the start in LOCAL / SEMI_FREE_BEGIN) */
-        const uint16_t* const en_o = r_en + ((e - o) & (gm - 1)) * slot;
-        const uint16_t* const en_x = r_en + ((e - x) & (gm - 1)) * slot;
-        const uint16_t* const ip_e = r_ip + ((e - ext) & (gi - 1)) * slot;
-        const uint16_t* const dp_e = r_dp + ((e - ext) & (gi - 1)) * slot;
-        uint16_t* const en_w = r_en + (e & (gm - 1)) * slot;
-        uint16_t* const ip_w = r_ip + (e & (gi - 1)) * slot;
-        uint16_t* const dp_w = r_dp + (e & (gi - 1)) * slot;
+        const LvRingView<uint16_t> g(r_en, r_ip, r_dp, rg, slot, e, x, o, ext);
         int conv = 1000000;
         for (int l = mid - dmax; l <= mid + dmax; l++) {
             const int top = l >= mid ? 1 : 0, bot = l <= mid ? 1 : 0;
-            const int e_up = (int)en_o[(l - 1) * TH] - 2, i_up = (int)ip_e[(l - 1) * TH] - 2;
-            const int e_dn = (int)en_o[(l + 1) * TH] - 2, d_dn = (int)dp_e[(l + 1) * TH] - 2;
-            const int own = (int)en_x[l * TH] - 2;
-            int inew = -2, dnew = -2;
-            if (e_up >= 0 && e_up > i_up)
-                inew = e_up + top; /* :533-538 */
-            else if (i_up >= 0)
-                inew = i_up + top; /* :539-544 */
-            if (e_dn >= 0 && e_dn > d_dn)
-                dnew = e_dn + bot; /* :546-547 */
-            else if (d_dn >= 0)
-                dnew = d_dn + bot; /* :548-549 */
-            int st = own >= 0 ? own + 1 : -2; /* :551-558 */
-            st = inew > st ? inew : st;
-            st = dnew > st ? dnew : st;
+            const int e_up = (int)g.en_o[(l - 1) * TH] - 2, i_up = (int)g.ip_e[(l - 1) * TH] - 2;
+            const int e_dn = (int)g.en_o[(l + 1) * TH] - 2, d_dn = (int)g.dp_e[(l + 1) * TH] - 2;
+            const int own = (int)g.en_x[l * TH] - 2;
+            const auto [inew, dnew, st] = lv_affine_step(e_up, i_up, e_dn, d_dn, own, top, bot); /* SIMD_ED.cpp:533-558 */
             int enew = -2;
             if (st >= 0) {
                 enew = simd_extend<W64>(simd_lane_mask<W64>(A0, A1, B0, B1, l - mid), st, len); /* :579-581 */
                 if (enew == len) { /* :589-603 */
-                    const int diff = l < mid ? mid - l : l - mid;
-                    const int tc = converge_rule ? e + (diff ? o + (diff - 1) * ext : 0) : e; /* :604-608: final_ED, no threshold */
+                    const int tc = converge_rule ? e + affine_gap(l < mid ? mid - l : l - mid, o, ext) : e; /* :604-608: final_ED, no threshold */
                     if ((!converge_rule || tc <= af_t) && tc < conv) conv = tc;
                 }
             }
-            en_w[l * TH] = (uint16_t)(enew + 2), ip_w[l * TH] = (uint16_t)(inew + 2), dp_w[l * TH] = (uint16_t)(dnew + 2);
+            g.en_w[l * TH] = (uint16_t)(enew + 2), g.ip_w[l * TH] = (uint16_t)(inew + 2), g.dp_w[l * TH] = (uint16_t)(dnew + 2);
         }
         if (conv != 1000000) result = conv; /* ED_pass: the generation loop ends (:609-610) */
     }
@@ -324,7 +306,9 @@ __global__ __launch_bounds__(64) void simd_ed_affine_kernel(const uint4* __restr
 // 61), which is what bounds the occupancy there, and a wave waits for the slowest of 16 pairs instead of 64.
 // ---------------------------------------------------------------------------------------------------------------------
 #define SIMD_QUAD_PD 6 /* zero dword, 4 plane dwords, zero dword */
-#define SIMD_QUAD_PW (4 * SIMD_QUAD_PD + 1)
+#define SIMD_QUAD_PW LEAP_QUAD_PAIR_DWORDS(SIMD_QUAD_PD)
+/* what LvRings::quad_lds takes for the plane part: it counts w32 + 1 dwords per plane (data and one zero dword), here 4 + 2 */
+#define SIMD_QUAD_W32 (SIMD_QUAD_PD - 1)
 ASM_DEV uint32_t simd_quad_window(const uint32_t* plane, int pos) { /* pos is already offset by the leading zero dword */
     const int q = pos >> 5;
     return __builtin_amdgcn_alignbit(plane[q + 1], plane[q], (uint32_t)(pos & 31));
@@ -363,8 +347,9 @@ __global__ __launch_bounds__(64) void simd_ed_affine_quad_kernel(const uint4* __
     const int t = threadIdx.x, pr = t >> 2, q = t & 3;
     const int rows = 2 * T + 3, mid = T + 1; /* lanes 1 .. 2T+1, guard rows 0 and 2T+2 (SIMD_ED.cpp:452-453) */
     const int slot = rows * P;
-    const int ring_words = (int)(((size_t)(gm + 2 * gi) * slot * sizeof(EnT) + 3) / 4);
-    uint32_t* const pl = s_afq + pr * PW;                               /* [P][4][PD] (+1) */
+    const LvRings rg{gm, gi};
+    const int ring_words = (int)(rg.ring_bytes(rows, P, sizeof(EnT)) / 4);
+    uint32_t* const pl = s_afq + pr * PW;                              /* [P][4][PD] (+1) */
     EnT* const r_en = reinterpret_cast<EnT*>(s_afq + P * PW) + pr;    /* [gm][rows][P] */
     EnT* const r_ip = r_en + gm * slot;                                 /* [gi][rows][P] */
     EnT* const r_dp = r_ip + gi * slot;
@@ -419,40 +404,22 @@ __global__ __launch_bounds__(64) void simd_ed_affine_quad_kernel(const uint4* __
         if (result == -2) {
             int dmax = e < o ? 0 : (e - o) / ext + 1; /* lanes a gap of this cost can have reached */
             dmax = (dmax > T || all_start) ? T : dmax;
-            const EnT* const en_o = r_en + ((e - o) & (gm - 1)) * slot;
-            const EnT* const en_x = r_en + ((e - x) & (gm - 1)) * slot;
-            const EnT* const ip_e = r_ip + ((e - ext) & (gi - 1)) * slot;
-            const EnT* const dp_e = r_dp + ((e - ext) & (gi - 1)) * slot;
-            EnT* const en_w = r_en + (e & (gm - 1)) * slot;
-            EnT* const ip_w = r_ip + (e & (gi - 1)) * slot;
-            EnT* const dp_w = r_dp + (e & (gi - 1)) * slot;
+            const LvRingView<EnT> g(r_en, r_ip, r_dp, rg, slot, e, x, o, ext);
             for (int l = mid - dmax + q; l <= mid + dmax; l += 4) {
                 const int top = l >= mid ? 1 : 0, bot = l <= mid ? 1 : 0;
-                const int e_up = (int)en_o[(l - 1) * P] - 2, i_up = (int)ip_e[(l - 1) * P] - 2;
-                const int e_dn = (int)en_o[(l + 1) * P] - 2, d_dn = (int)dp_e[(l + 1) * P] - 2;
-                const int own = (int)en_x[l * P] - 2;
-                int inew = -2, dnew = -2;
-                if (e_up >= 0 && e_up > i_up)
-                    inew = e_up + top; /* :533-538 */
-                else if (i_up >= 0)
-                    inew = i_up + top; /* :539-544 */
-                if (e_dn >= 0 && e_dn > d_dn)
-                    dnew = e_dn + bot; /* :546-547 */
-                else if (d_dn >= 0)
-                    dnew = d_dn + bot; /* :548-549 */
-                int st = own >= 0 ? own + 1 : -2; /* :551-558 */
-                st = inew > st ? inew : st;
-                st = dnew > st ? dnew : st;
+                const int e_up = (int)g.en_o[(l - 1) * P] - 2, i_up = (int)g.ip_e[(l - 1) * P] - 2;
+                const int e_dn = (int)g.en_o[(l + 1) * P] - 2, d_dn = (int)g.dp_e[(l + 1) * P] - 2;
+                const int own = (int)g.en_x[l * P] - 2;
+                const auto [inew, dnew, st] = lv_affine_step(e_up, i_up, e_dn, d_dn, own, top, bot); /* SIMD_ED.cpp:533-558 */
                 int enew = -2;
                 if (st >= 0) {
                     enew = simd_quad_extend(pl, l - mid, st, len); /* :579-581 */
                     if (enew == len) { /* :589-603 */
-                        const int diff = l < mid ? mid - l : l - mid;
-                        const int tc = converge_rule ? e + (diff ? o + (diff - 1) * ext : 0) : e;
+                        const int tc = converge_rule ? e + affine_gap(l < mid ? mid - l : l - mid, o, ext) : e;
                         if ((!converge_rule || tc <= af_t) && tc < conv) conv = tc;
                     }
                 }
-                en_w[l * P] = (EnT)(enew + 2), ip_w[l * P] = (EnT)(inew + 2), dp_w[l * P] = (EnT)(dnew + 2);
+                g.en_w[l * P] = (EnT)(enew + 2), g.ip_w[l * P] = (EnT)(inew + 2), g.dp_w[l * P] = (EnT)(dnew + 2);
             }
         }
         conv = quad_min(conv);
@@ -460,10 +427,6 @@ __global__ __launch_bounds__(64) void simd_ed_affine_quad_kernel(const uint4* __
         leap_quad_fence();
     }
     if (live && q == 0) out.put(i, result == -2 ? -1 : result);
-}
-
-static inline size_t simd_quad_lds(int T, int gm, int gi) {
-    return (size_t)16 * SIMD_QUAD_PW * sizeof(uint32_t) + (((size_t)(gm + 2 * gi) * (2 * T + 3) * 16 + 3) & ~(size_t)3);
 }
 
 // init_affine's SHD_enable / SHD_threshold (SIMD_ED.cpp:435,445-446): run_affine starts with bit_vec_filter_avx(hamming_masks + 1,

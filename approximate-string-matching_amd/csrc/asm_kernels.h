@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "asm_affine.h"
 #include "asm_bits.h"
 #include "asm_gen.h"
 #include "asm_leapunit.h"
@@ -586,24 +587,11 @@ __global__ __launch_bounds__(ASM_BLOCK) void leap_unit_hint_kernel(const uint4* 
 }
 
 // --------------------------------------------------------------------------------------------------------
-// LEAP with general penalties (x, o, ext), narrow band, one thread per pair.  The recurrence reads generations e-o,
-// e-x (end) and e-ext (I, D) (LV_BAG.cpp:166-187), so rings of GM = 2^a > max(x, o) generations of `end` and
-// GI = 2^b > ext generations of I and D are kept — per thread, as int16 (positions <= 512), in dynamic LDS laid out
-// [ring][slot][lane][thread]: thread-private columns, so no barriers and no bank conflicts; slot offsets are wave-uniform
-// (scalar).  All slots are filled with "never reached" before generation 0, which also stands in for the e >= penalty guards
-// of the reference (see the loop).
+// LEAP with general penalties (x, o, ext), narrow band, one thread per pair: lv_affine_step over rings of LvRings::pow2 depths
+// (asm_affine.h), per thread, in dynamic LDS laid out [ring][slot][lane][thread]: thread-private columns, so no barriers and no
+// bank conflicts; slot offsets are wave-uniform (scalar).
 // --------------------------------------------------------------------------------------------------------
 #define LEAP_GEN_THREADS 128
-struct RingGeometry { /* power-of-two ring depths for (x, o, e) and the LDS bytes a block of T threads with NL lanes needs */
-    int gm, gi;
-    __host__ __device__ static int pow2_above(int v) {
-        int g = 2;
-        while (g <= v) g <<= 1;
-        return g;
-    }
-    __host__ RingGeometry(int x, int o, int e) : gm(pow2_above(x > o ? x : o)), gi(pow2_above(e)) {}
-    __host__ size_t lds_bytes(int nl, int threads, size_t elem = sizeof(short)) const { return ((size_t)(gm + 2 * gi) * nl * threads * elem + 3) & ~(size_t)3; }
-};
 
 template <int K, int W64, typename EnT> /* EnT: ring element, values stored + 2 (0 = never reached) */
 __global__ __launch_bounds__(LEAP_GEN_THREADS) void leap_general_kernel(const uint4* __restrict__ planes,
@@ -633,7 +621,7 @@ __global__ __launch_bounds__(LEAP_GEN_THREADS) void leap_general_kernel(const ui
     int result = -1;
     // e = 0: only the main diagonal is live (LV_BAG.cpp:102-104,131-147)
 #pragma unroll
-    for (int j = 0; j < NL; j++) { /* every slot starts as "never reached" (see the note on guards below) */
+    for (int j = 0; j < NL; j++) { /* every slot starts as "never reached" (which stands in for the reference's guards: lv_affine_step, asm_affine.h) */
         for (int q = 0; q < gm; q++) r_en[q * SLOT + j * T] = (EnT)0;
         for (int q = 0; q < gi; q++) r_ip[q * SLOT + j * T] = (EnT)0, r_dp[q * SLOT + j * T] = (EnT)0;
     }
@@ -644,38 +632,18 @@ __global__ __launch_bounds__(LEAP_GEN_THREADS) void leap_general_kernel(const ui
         if (e0 == len) result = 0;
     }
     for (int e = 1; e <= ASM_LEAP_AF_THRESHOLD && result < 0; e++) {
-        const EnT* const en_o = r_en + ((e - o) & (gm - 1)) * SLOT;
-        const EnT* const en_x = r_en + ((e - x) & (gm - 1)) * SLOT;
-        const EnT* const ip_e = r_ip + ((e - ext) & (gi - 1)) * SLOT;
-        const EnT* const dp_e = r_dp + ((e - ext) & (gi - 1)) * SLOT;
-        EnT* const en_w = r_en + (e & (gm - 1)) * SLOT;
-        EnT* const ip_w = r_ip + (e & (gi - 1)) * SLOT;
-        EnT* const dp_w = r_dp + (e & (gi - 1)) * SLOT;
-        // The reference guards these reads with e >= o, e >= x, e >= ext (LV_BAG.cpp:166-187).  Here the guards are implied:
-        // for e < o the slot of generation e - o is that of a generation not written yet (ring depth > o), still "never
-        // reached" from the initial fill; unguarded, the five reads issue back to back instead of a branch and a wait each.
+        const LvRingView<EnT> g(r_en, r_ip, r_dp, LvRings{gm, gi}, SLOT, e, x, o, ext);
         bool pass = false;
 #pragma unroll
         for (int j = 0; j < NL; j++) {
             const int d = j - K;
             const int top = d >= 0 ? 1 : 0, bot = d <= 0 ? 1 : 0;
-            const int e_up = j > 0 ? (int)en_o[(j > 0 ? j - 1 : 0) * T] - 2 : -2;
-            const int i_up = j > 0 ? (int)ip_e[(j > 0 ? j - 1 : 0) * T] - 2 : -2;
-            const int e_dn = j < NL - 1 ? (int)en_o[(j < NL - 1 ? j + 1 : j) * T] - 2 : -2;
-            const int d_dn = j < NL - 1 ? (int)dp_e[(j < NL - 1 ? j + 1 : j) * T] - 2 : -2;
-            const int own = (int)en_x[j * T] - 2;
-            int inew = -2, dnew = -2;
-            if (e_up >= 0 && e_up > i_up)
-                inew = e_up + top; /* LV_BAG.cpp:166-167 */
-            else if (i_up >= 0)
-                inew = i_up + top; /* :172-176 */
-            if (e_dn >= 0 && e_dn > d_dn)
-                dnew = e_dn + bot; /* :179-180 */
-            else if (d_dn >= 0)
-                dnew = d_dn + bot; /* :181-182 */
-            int st = own >= 0 ? own + 1 : -2; /* :186-187 */
-            st = inew > st ? inew : st;
-            st = dnew > st ? dnew : st;
+            const int e_up = j > 0 ? (int)g.en_o[(j > 0 ? j - 1 : 0) * T] - 2 : -2;
+            const int i_up = j > 0 ? (int)g.ip_e[(j > 0 ? j - 1 : 0) * T] - 2 : -2;
+            const int e_dn = j < NL - 1 ? (int)g.en_o[(j < NL - 1 ? j + 1 : j) * T] - 2 : -2;
+            const int d_dn = j < NL - 1 ? (int)g.dp_e[(j < NL - 1 ? j + 1 : j) * T] - 2 : -2;
+            const int own = (int)g.en_x[j * T] - 2;
+            const auto [inew, dnew, st] = lv_affine_step(e_up, i_up, e_dn, d_dn, own, top, bot);
             int enew = -2;
             if (st >= 0) {
                 const int from = st > len ? len : st;
@@ -683,12 +651,10 @@ __global__ __launch_bounds__(LEAP_GEN_THREADS) void leap_general_kernel(const ui
                 r = r > len ? len : r;
                 enew = r > st ? r : st; /* st beyond the end stays st (r >= from = st otherwise) */
                 if (enew == len) { /* :220-238 */
-                    const int diff = d < 0 ? -d : d;
-                    const int conv = e + (diff ? o + (diff - 1) * ext : 0);
-                    if (conv <= ASM_LEAP_AF_THRESHOLD) pass = true;
+                    if (e + affine_gap(d < 0 ? -d : d, o, ext) <= ASM_LEAP_AF_THRESHOLD) pass = true;
                 }
             }
-            en_w[j * T] = (EnT)(enew + 2), ip_w[j * T] = (EnT)(inew + 2), dp_w[j * T] = (EnT)(dnew + 2);
+            g.en_w[j * T] = (EnT)(enew + 2), g.ip_w[j * T] = (EnT)(inew + 2), g.dp_w[j * T] = (EnT)(dnew + 2);
         }
         if (pass) result = e; /* final_ED (LV_BAG.cpp:228,356-358) */
     }
@@ -697,7 +663,8 @@ __global__ __launch_bounds__(LEAP_GEN_THREADS) void leap_general_kernel(const ui
 
 // --------------------------------------------------------------------------------------------------------
 // NW with affine gaps as a banded wavefront (furthest-reaching offsets per diagonal and score), one thread per pair —
-// the same LDS rings as leap_general_kernel.  Diagonal d = j - i (i: read characters consumed, j: reference characters),
+// the same LDS rings as leap_general_kernel, at LvRings::exact depths (slot = score mod depth, in scalar counters).
+// Diagonal d = j - i (i: read characters consumed, j: reference characters),
 // lanes d in [-K, K].  M[s][d] = furthest i with cost s ending in a match/mismatch state; I consumes the reference
 // (d-1 -> d, i unchanged), D consumes the read (d+1 -> d, i+1).  gap(L) = o + (L-1)*e, mismatch x — the model of
 // nw_affine_kernel and of the oracle (benchmark_utils.h:139-142,288).  The answer is the first s whose M on diagonal
@@ -708,11 +675,18 @@ __global__ __launch_bounds__(LEAP_GEN_THREADS) void leap_general_kernel(const ui
 // --------------------------------------------------------------------------------------------------------
 #define NW_WFA_K 7
 #define NW_WFA_K2 15 /* second pass over the pairs the first band could not settle (maxlen <= 128 only: 31 masks of 4 dwords) */
-struct WfaRings { /* ring depths of the banded wavefront: `M` needs scores s-o and s-x, I and D need s-ext; slot = score mod depth (scalar) */
-    int gm, gi;
-    __host__ WfaRings(int x, int o, int e) : gm((x > o ? x : o) + 1), gi(e + 1) {}
-    __host__ size_t lds_bytes(int nl, int threads, size_t elem) const { return ((size_t)(gm + 2 * gi) * nl * threads * elem + 3) & ~(size_t)3; }
-};
+// append `value` to list[*count ...) in the threads where `flag` holds: one atomic per wave
+ASM_DEV void wave_append(uint32_t* __restrict__ list, uint32_t* __restrict__ count, bool flag, uint32_t value) {
+    const u64 bal = __ballot(flag);
+    if (bal) {
+        const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+        const int leader = __builtin_ctzll(bal);
+        uint32_t base = 0;
+        if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(count, (uint32_t)__builtin_popcountll(bal));
+        base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
+        if (flag) list[base + rank] = value;
+    }
+}
 // EnT: bytes when every position + 2 fits (values are stored + 2, 0 = never reached), else shorts.  LISTED: the pairs come from
 // `in_list[0 .. *in_count)` (the previous pass's todo list) instead of 0..n.
 template <int K, int W64, typename EnT, bool LISTED>
@@ -839,16 +813,7 @@ __global__ __launch_bounds__(LEAP_GEN_THREADS) void nw_wfa_kernel(const uint4* _
             if (result < 0) unresolved = true;
         }
     }
-    // wave-aggregated append of the unresolved pairs
-    const u64 bal = __ballot(unresolved);
-    if (bal) {
-        const int lane = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-        uint32_t base = 0;
-        const int leader = __builtin_ctzll(bal);
-        if ((t & 63) == leader) base = atomicAdd(todo_count, (uint32_t)__builtin_popcountll(bal));
-        base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-        if (unresolved) todo[base + lane] = (uint32_t)i;
-    }
+    wave_append(todo, todo_count, unresolved, (uint32_t)i);
     if (have && !unresolved) out.put(i, result);
 }
 

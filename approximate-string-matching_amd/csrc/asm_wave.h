@@ -131,9 +131,25 @@ ASM_DEV int leap_band_extend(const uint32_t* pl, int d, int from, int m, int nn)
 // --------------------------------------------------------------------------------------------------------
 #define LEAP_QUAD_THREADS 64
 #define LEAP_QUAD_PAIRS 16
-/* planes in LDS pair-major: the 4 x PD dwords of a pair are contiguous (a window is two adjacent dwords: one address add, no
- * multiply) and pairs are an odd number of dwords apart, so the sixteen quads start in different banks */
-#define LEAP_QUAD_PAIR_DWORDS(PD) (4 * (PD) + 1)
+
+/* Thread q < 4 of a pair's group stages plane q (read plane 0/1, reference plane 0/1) into the pair's LDS block `pl`.  Planes in LDS
+ * are pair-major: the 4 x PD dwords of a pair are contiguous (a window is two adjacent dwords: one address add, no multiply), each
+ * plane ends in a zero dword, and pairs are LEAP_QUAD_PAIR_DWORDS apart, an odd number, so the groups start in different banks */
+template <int W32>
+ASM_DEV void quad_stage_planes(uint32_t* pl, const uint4* __restrict__ planes, long n, int w4, long i, int q) {
+    constexpr int PD = W32 + 1;
+#pragma unroll
+    for (int g = 0; g < (W32 + 3) / 4; g++) {
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (g < w4) v = planes[((long)q * w4 + g) * n + i];
+        uint32_t* dst = pl + q * PD + 4 * g;
+        dst[0] = v.x;
+        if (4 * g + 1 < W32) dst[1] = v.y;
+        if (4 * g + 2 < W32) dst[2] = v.z;
+        if (4 * g + 3 < W32) dst[3] = v.w;
+    }
+    pl[q * PD + W32] = 0u;
+}
 
 ASM_DEV void leap_quad_fence() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -163,7 +179,8 @@ __global__ __launch_bounds__(LEAP_QUAD_THREADS * WAVES) void leap_quad_kernel(co
     const int t = threadIdx.x & 63, pr = t >> 2, q = t & 3, wv = threadIdx.x >> 6;
     const int rows = 2 * k + 3; /* lane l at row l+1, guard rows 0 and 2k+2 */
     const int slot = rows * P;  /* elements per ring slot */
-    const int ring_words = (int)(((size_t)(gm + 2 * gi) * slot * sizeof(EnT) + 3) / 4);
+    const LvRings rg{gm, gi};
+    const int ring_words = (int)(rg.ring_bytes(slot, 1, sizeof(EnT)) / 4); /* slot = rows x P, multiplied once */
     uint32_t* const s_band = s_band_all + wv * (P * PW + ring_words);          /* this wave's block */
     uint32_t* const pl = s_band + pr * PW;                                     /* [P][4][PD] (+1) */
     EnT* const r_en = reinterpret_cast<EnT*>(s_band + P * PW) + pr;           /* [gm][rows][P] */
@@ -212,17 +229,7 @@ __global__ __launch_bounds__(LEAP_QUAD_THREADS * WAVES) void leap_quad_kernel(co
     if (live) { /* thread q of the quad stages plane q: read plane 0/1, reference plane 0/1 */
         const uint32_t ln = lens[i];
         m = (int)(ln & 0xffffu), nn = (int)(ln >> 16);
-#pragma unroll
-        for (int g = 0; g < (W32 + 3) / 4; g++) {
-            uint4 v = make_uint4(0u, 0u, 0u, 0u);
-            if (g < w4) v = planes[((long)q * w4 + g) * n + i];
-            uint32_t* dst = pl + q * PD + 4 * g;
-            dst[0] = v.x;
-            if (4 * g + 1 < W32) dst[1] = v.y;
-            if (4 * g + 2 < W32) dst[2] = v.z;
-            if (4 * g + 3 < W32) dst[3] = v.w;
-        }
-        pl[q * PD + W32] = 0u;
+        quad_stage_planes<W32>(pl, planes, n, w4, i, q);
     }
     const int len = m > nn ? m : nn; /* benchmark_utils.h:162 */
     leap_quad_fence();
@@ -263,33 +270,24 @@ __global__ __launch_bounds__(LEAP_QUAD_THREADS * WAVES) void leap_quad_kernel(co
             } else {
                 int dmax = e < o ? 0 : (e - o) / ext + 1;
                 dmax = dmax > k ? k : dmax;
-                const EnT* const en_o = r_en + ((e - o) & (gm - 1)) * slot;
-                const EnT* const en_x = r_en + ((e - x) & (gm - 1)) * slot;
-                const EnT* const ip_e = r_ip + ((e - ext) & (gi - 1)) * slot;
-                const EnT* const dp_e = r_dp + ((e - ext) & (gi - 1)) * slot;
-                EnT* const en_w = r_en + (e & (gm - 1)) * slot;
-                EnT* const ip_w = r_ip + (e & (gi - 1)) * slot;
-                EnT* const dp_w = r_dp + (e & (gi - 1)) * slot;
-                // The reference guards these reads with e >= o, e >= x, e >= ext (LV_BAG.cpp:166-187); here the slot of a generation
-                // before 0 is the slot of one not written yet (ring depth > penalty), still zero from the initial fill
+                const LvRingView<EnT> g(r_en, r_ip, r_dp, rg, slot, e, x, o, ext);
                 for (int l = k - dmax + q; l <= k + dmax; l += 4) {
                     const int d = l - k;
                     const int top = d >= 0 ? 1 : 0, bot = d <= 0 ? 1 : 0;
-                    const int e_up = (int)en_o[l * P] - 2;       /* lane l-1 sits at row l */
-                    const int i_up = (int)ip_e[l * P] - 2;
-                    const int e_dn = (int)en_o[(l + 2) * P] - 2; /* lane l+1 */
-                    const int d_dn = (int)dp_e[(l + 2) * P] - 2;
-                    const int own = (int)en_x[(l + 1) * P] - 2;
+                    const int e_up = (int)g.en_o[l * P] - 2;       /* lane l-1 sits at row l */
+                    const int i_up = (int)g.ip_e[l * P] - 2;
+                    const int e_dn = (int)g.en_o[(l + 2) * P] - 2; /* lane l+1 */
+                    const int d_dn = (int)g.dp_e[(l + 2) * P] - 2;
+                    const int own = (int)g.en_x[(l + 1) * P] - 2;
+                    /* lv_affine_step (asm_affine.h), written out: through the call the byte-ring instantiations come out with
+                     * other 16-bit compare and max forms and two VGPRs fewer, and measured about 1 % slower; written out the kernel's
+                     * instruction stream is the one it had before the step was shared */
                     int inew = -2, dnew = -2;
-                    if (e_up >= 0 && e_up > i_up)
-                        inew = e_up + top; /* LV_BAG.cpp:166-167 */
-                    else if (i_up >= 0)
-                        inew = i_up + top; /* :172-176 */
-                    if (e_dn >= 0 && e_dn > d_dn)
-                        dnew = e_dn + bot; /* :179-180 */
-                    else if (d_dn >= 0)
-                        dnew = d_dn + bot; /* :181-182 */
-                    int st = own >= 0 ? own + 1 : -2; /* :186-187 */
+                    if (e_up >= 0 && e_up > i_up) inew = e_up + top;
+                    else if (i_up >= 0) inew = i_up + top;
+                    if (e_dn >= 0 && e_dn > d_dn) dnew = e_dn + bot;
+                    else if (d_dn >= 0) dnew = d_dn + bot;
+                    int st = own >= 0 ? own + 1 : -2;
                     st = inew > st ? inew : st;
                     st = dnew > st ? dnew : st;
                     int enew = -2;
@@ -298,13 +296,9 @@ __global__ __launch_bounds__(LEAP_QUAD_THREADS * WAVES) void leap_quad_kernel(co
                         int r = leap_band_extend<PD, 1, PD>(pl, d, from, m, nn); /* count_ID_length, :9-23 */
                         r = r > len ? len : r;
                         enew = st > len ? st : r;
-                        if (enew == len) { /* :220-238 */
-                            const int diff = d < 0 ? -d : d;
-                            const int conv = e + (diff ? o + (diff - 1) * ext : 0);
-                            if (conv <= ASM_LEAP_AF_THRESHOLD) pass = 1;
-                        }
+                        if (enew == len && e + affine_gap(d < 0 ? -d : d, o, ext) <= ASM_LEAP_AF_THRESHOLD) pass = 1; /* :220-238 */
                     }
-                    en_w[(l + 1) * P] = (EnT)(enew + 2), ip_w[(l + 1) * P] = (EnT)(inew + 2), dp_w[(l + 1) * P] = (EnT)(dnew + 2);
+                    g.en_w[(l + 1) * P] = (EnT)(enew + 2), g.ip_w[(l + 1) * P] = (EnT)(inew + 2), g.dp_w[(l + 1) * P] = (EnT)(dnew + 2);
                 }
             }
         }
@@ -313,11 +307,6 @@ __global__ __launch_bounds__(LEAP_QUAD_THREADS * WAVES) void leap_quad_kernel(co
         leap_quad_fence();
     }
     if (live && q == 0) out.put(i, result);
-}
-
-static inline size_t leap_quad_lds(int w32, int k, int gm, int gi, size_t en_bytes) {
-    return (size_t)LEAP_QUAD_PAIRS * LEAP_QUAD_PAIR_DWORDS(w32 + 1) * sizeof(uint32_t) +
-           (((size_t)(gm + 2 * gi) * (2 * k + 3) * LEAP_QUAD_PAIRS * en_bytes + 3) & ~(size_t)3);
 }
 
 // keys of the global work sort: the hint (penalties) scaled into 64 bins, and the identity permutation to carry along
@@ -332,21 +321,16 @@ __global__ __launch_bounds__(256) void leap_sort_keys_kernel(const int32_t* __re
 
 template <int W32, typename EnT>
 static inline hipError_t launch_leap_quad(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4, int k,
-                                          bool unit, int x, int o, int e, int gm, int gi, OutMap out, const int32_t* hint,
-                                          const uint32_t* perm) {
-    const size_t lds1 = unit ? leap_quad_lds(W32, k, 2, 0, sizeof(EnT)) : leap_quad_lds(W32, k, gm, gi, sizeof(EnT));
-    if (hint && !perm && 4 * lds1 + 512 <= 64 * 1024) { /* work-sorted inside workgroups of four waves (64 pairs) */
-        const unsigned grid = (unsigned)((n + 4 * LEAP_QUAD_PAIRS - 1) / (4 * LEAP_QUAD_PAIRS)), block = 4 * LEAP_QUAD_THREADS;
-        return unit ? launch_on(stream, leap_quad_kernel<W32, EnT, true, 4>, grid, block, 4 * lds1, planes, lens, (long)n, w4, k, 1, 1, 1,
-                                2, 0, out, hint, nullptr)
-                    : launch_on(stream, leap_quad_kernel<W32, EnT, false, 4>, grid, block, 4 * lds1, planes, lens, (long)n, w4, k, x, o,
-                                e, gm, gi, out, hint, nullptr);
-    }
-    const unsigned grid = (unsigned)((n + LEAP_QUAD_PAIRS - 1) / LEAP_QUAD_PAIRS), block = LEAP_QUAD_THREADS;
-    return unit ? launch_on(stream, leap_quad_kernel<W32, EnT, true, 1>, grid, block, lds1, planes, lens, (long)n, w4, k, 1, 1, 1, 2, 0,
-                            out, nullptr, perm)
-                : launch_on(stream, leap_quad_kernel<W32, EnT, false, 1>, grid, block, lds1, planes, lens, (long)n, w4, k, x, o, e, gm,
-                            gi, out, nullptr, perm);
+                                          bool unit, int x, int o, int e, LvRings rg /* LvRings::unit() where unit */, OutMap out,
+                                          const int32_t* hint, const uint32_t* perm) {
+    const size_t lds1 = rg.quad_lds(LEAP_QUAD_PAIRS, W32, k, sizeof(EnT));
+    const auto go = [&](auto kernel, unsigned waves, const int32_t* hnt, const uint32_t* prm) {
+        return launch_on(stream, kernel, (unsigned)((n + waves * LEAP_QUAD_PAIRS - 1) / (waves * LEAP_QUAD_PAIRS)), waves * LEAP_QUAD_THREADS,
+                         waves * lds1, planes, lens, (long)n, w4, k, x, o, e, rg.gm, rg.gi, out, hnt, prm);
+    };
+    if (hint && !perm && 4 * lds1 + 512 <= 64 * 1024) /* work-sorted inside workgroups of four waves (64 pairs) */
+        return unit ? go(leap_quad_kernel<W32, EnT, true, 4>, 4, hint, nullptr) : go(leap_quad_kernel<W32, EnT, false, 4>, 4, hint, nullptr);
+    return unit ? go(leap_quad_kernel<W32, EnT, true, 1>, 1, nullptr, perm) : go(leap_quad_kernel<W32, EnT, false, 1>, 1, nullptr, perm);
 }
 
 // --------------------------------------------------------------------------------------------------------
@@ -398,7 +382,7 @@ __global__ __launch_bounds__(NW_OCT_THREADS) void nw_oct_kernel(const uint4* __r
     /* a fixed grid walks the list (its length is only known on the device) */
     for (long first = (long)blockIdx.x * P; first < count; first += (long)gridDim.x * P) {
     {
-        const int words = (int)(((size_t)(gm + 2 * gi) * slot * sizeof(EnT) + 3) / 4);
+        const int words = (int)(LvRings{gm, gi}.ring_bytes(slot, 1, sizeof(EnT)) / 4);
         uint32_t* const base = s_band + P * PW;
         for (int w = t; w < words; w += NW_OCT_THREADS) base[w] = 0u;
     }
@@ -409,19 +393,7 @@ __global__ __launch_bounds__(NW_OCT_THREADS) void nw_oct_kernel(const uint4* __r
     if (have) {
         const uint32_t ln = lens[i];
         m = (int)(ln & 0xffffu), nn = (int)(ln >> 16);
-        if (q < 4) { /* threads 0..3 of the group stage one plane each */
-#pragma unroll
-            for (int g = 0; g < (W32 + 3) / 4; g++) {
-                uint4 v = make_uint4(0u, 0u, 0u, 0u);
-                if (g < w4) v = planes[((long)q * w4 + g) * n + i];
-                uint32_t* dst = pl + q * PD + 4 * g;
-                dst[0] = v.x;
-                if (4 * g + 1 < W32) dst[1] = v.y;
-                if (4 * g + 2 < W32) dst[2] = v.z;
-                if (4 * g + 3 < W32) dst[3] = v.w;
-            }
-            pl[q * PD + W32] = 0u;
-        }
+        if (q < 4) quad_stage_planes<W32>(pl, planes, n, w4, i, q);
     }
     const int df = nn - m, adf = df < 0 ? -df : df;
     leap_quad_fence();
@@ -444,20 +416,14 @@ __global__ __launch_bounds__(NW_OCT_THREADS) void nw_oct_kernel(const uint4* __r
         sj_w = sj_w + 1 == gi ? 0 : sj_w + 1, sj_e = sj_e + 1 == gi ? 0 : sj_e + 1;
         int done = 0;
         if (result < 0) {
-            const EnT* const m_o = r_m + sl_o * slot;
-            const EnT* const m_x = r_m + sl_x * slot;
-            const EnT* const i_e = r_i + sj_e * slot;
-            const EnT* const d_e = r_d + sj_e * slot;
-            EnT* const m_w = r_m + sl_w * slot;
-            EnT* const i_w = r_i + sj_w * slot;
-            EnT* const d_w = r_d + sj_w * slot;
+            const LvRingView<EnT> g(r_m, r_i, r_d, slot, sl_o, sl_x, sl_w, sj_e, sj_w); /* `end` is M here */
             int dmax = s < o ? 0 : (s - o) / ext + 1;
             dmax = dmax > K ? K : dmax;
             for (int l = K - dmax + q; l <= K + dmax; l += Q) {
                 const int d = l - K;
-                const int m_lo = (int)m_o[l * P] - 2, i_lo = (int)i_e[l * P] - 2;             /* lane l-1 sits at row l */
-                const int m_hi = (int)m_o[(l + 2) * P] - 2, d_hi = (int)d_e[(l + 2) * P] - 2; /* lane l+1 */
-                const int own = (int)m_x[(l + 1) * P] - 2;
+                const int m_lo = (int)g.en_o[l * P] - 2, i_lo = (int)g.ip_e[l * P] - 2;             /* lane l-1 sits at row l */
+                const int m_hi = (int)g.en_o[(l + 2) * P] - 2, d_hi = (int)g.dp_e[(l + 2) * P] - 2; /* lane l+1 */
+                const int own = (int)g.en_x[(l + 1) * P] - 2;
                 int inew = m_lo > i_lo ? m_lo : i_lo;      /* reference character consumed: i stays, j = i + d */
                 inew = (inew >= 0 && inew + d <= nn) ? inew : -2;
                 int dnew = m_hi > d_hi ? m_hi : d_hi;      /* read character consumed */
@@ -468,7 +434,7 @@ __global__ __launch_bounds__(NW_OCT_THREADS) void nw_oct_kernel(const uint4* __r
                 int mnew = -2;
                 if (st >= 0) mnew = nw_diag_extend<PD, 1, PD>(pl, d, st, m, nn);
                 if (d == df && mnew >= m) done = 1;
-                m_w[(l + 1) * P] = (EnT)(mnew + 2), i_w[(l + 1) * P] = (EnT)(inew + 2), d_w[(l + 1) * P] = (EnT)(dnew + 2);
+                g.en_w[(l + 1) * P] = (EnT)(mnew + 2), g.ip_w[(l + 1) * P] = (EnT)(inew + 2), g.dp_w[(l + 1) * P] = (EnT)(dnew + 2);
             }
         }
 #pragma unroll
@@ -484,11 +450,6 @@ __global__ __launch_bounds__(NW_OCT_THREADS) void nw_oct_kernel(const uint4* __r
     }
     leap_quad_fence(); /* the next round refills rings and planes */
     }
-}
-
-static inline size_t nw_oct_lds(int w32, int K, int gm, int gi, size_t en_bytes) {
-    return (size_t)NW_OCT_PAIRS * LEAP_QUAD_PAIR_DWORDS(w32 + 1) * sizeof(uint32_t) +
-           (((size_t)(gm + 2 * gi) * (2 * K + 3) * NW_OCT_PAIRS * en_bytes + 3) & ~(size_t)3);
 }
 
 // --------------------------------------------------------------------------------------------------------

@@ -78,32 +78,22 @@ __global__ __launch_bounds__(ASM_WIDE_THREADS) void leap_wide_kernel(const uint4
                     const int top = d >= 0 ? 1 : 0, bot = d <= 0 ? 1 : 0;
                     const int so = (e - o) & (ASM_WIDE_RING - 1), se = (e - ext) & (ASM_WIDE_RING - 1),
                               sx = (e - x) & (ASM_WIDE_RING - 1);
-                    /* lanes t-1 / t+1; beyond the band (sentinels and inactive threads) everything is -2 */
+                    /* lanes t-1 / t+1; beyond the band (sentinels and inactive threads) everything is -2, and so is a read the
+                     * reference guards: the ring is 16 deep whatever the penalties (lv_affine_step) */
                     const int e_up = (e >= o && t > 0) ? s_end[so][t] : -2;
                     const int i_up = (e >= ext && t > 0) ? s_ip[se][t] : -2;
                     const int e_dn = (e >= o && t + 1 < nl) ? s_end[so][t + 2] : -2;
                     const int d_dn = (e >= ext && t + 1 < nl) ? s_dp[se][t + 2] : -2;
                     const int own = (e >= x) ? s_end[sx][t + 1] : -2;
-                    if (e >= o && e_up >= 0 && e_up > i_up)
-                        inew = e_up + top;
-                    else if (e >= ext && i_up >= 0)
-                        inew = i_up + top;
-                    if (e >= o && e_dn >= 0 && e_dn > d_dn)
-                        dnew = e_dn + bot;
-                    else if (e >= ext && d_dn >= 0)
-                        dnew = d_dn + bot;
-                    int st = own >= 0 ? own + 1 : -2;
-                    st = inew > st ? inew : st;
-                    st = dnew > st ? dnew : st;
+                    const LvStep s = lv_affine_step(e_up, i_up, e_dn, d_dn, own, top, bot);
+                    const int st = s.st;
+                    inew = s.inew, dnew = s.dnew;
                     if (st >= 0) {
                         const int from = st > len ? len : st;
                         int r = vw_next_one<W64>(mask, from);
                         r = r > len ? len : r;
                         enew = st > len ? st : r;
-                        if (enew == len) {
-                            const int conv = e + (diff ? o + (diff - 1) * ext : 0);
-                            if (!converge_rule || conv <= ASM_LEAP_AF_THRESHOLD) pass = 1;
-                        }
+                        if (enew == len && (!converge_rule || e + affine_gap(diff, o, ext) <= ASM_LEAP_AF_THRESHOLD)) pass = 1;
                     }
                 }
                 const int sw = e & (ASM_WIDE_RING - 1);
@@ -262,15 +252,9 @@ static inline hipError_t launch_greedy_wide(hipStream_t stream, const uint4* pla
 }
 
 // --------------------------------------------------------------------------------------------------------
-// NW with affine gaps (Gotoh), arbitrary penalties: match 0, mismatch x, gap(L) = o + (L-1)*e — the score
-// parasail's nw returns negated (benchmark_utils.h:139-142,288).  One thread per pair.  The DP matrix is
-// swept in column blocks of 32: a block's H and F rows live in registers (fully unrolled), and only the
-// block's right-hand boundary column (H, E per row, packed as two int16 in one dword) goes through LDS,
-// laid out [row][thread] so a wave's accesses hit 64 different banks.
+// NW with affine gaps (Gotoh), arbitrary penalties: gotoh_sweep (asm_affine.h), score only, one thread per pair; the block
+// boundary column in LDS [row][thread].
 // --------------------------------------------------------------------------------------------------------
-#define NW_CB 32
-#define NW_BIG 30000
-
 template <int W64, int MAXROWS>
 __global__ __launch_bounds__(64) void nw_affine_kernel(const uint4* __restrict__ planes,
                                                        const uint32_t* __restrict__ lens, long n, int w4, int x,
@@ -288,71 +272,8 @@ __global__ __launch_bounds__(64) void nw_affine_kernel(const uint4* __restrict__
     const int m = (int)(ln & 0xffffu), nn = (int)(ln >> 16);
     VW<W64> A0, A1, B0, B1;
     load_planes<W64>(planes, n, w4, i, A0, A1, B0, B1);
-    int result = nn == 0 ? (m == 0 ? 0 : o + (m - 1) * e) : 0;
-    for (int j0 = 0; j0 < nn; j0 += NW_CB) {
-        // text codes of this column block
-        uint32_t tb0 = 0, tb1 = 0;
-#pragma unroll
-        for (int q = 0; q < W64; q++) {
-            if ((j0 >> 6) == q) {
-                tb0 = (uint32_t)(B0.w[q] >> (j0 & 63));
-                tb1 = (uint32_t)(B1.w[q] >> (j0 & 63));
-            }
-        }
-        int H[NW_CB], F[NW_CB];
-#pragma unroll
-        for (int jj = 0; jj < NW_CB; jj++) {
-            H[jj] = o + (j0 + jj) * e; /* H[0][j], j = j0+jj+1 */
-            F[jj] = NW_BIG;
-        }
-        int diag = j0 == 0 ? 0 : o + (j0 - 1) * e; /* H[0][j0] */
-        for (int r = 1; r <= m; r++) {
-            // code of read character r-1, broadcast
-            uint32_t a0 = 0, a1 = 0;
-#pragma unroll
-            for (int q = 0; q < W64; q++) {
-                if (((r - 1) >> 6) == q) {
-                    a0 = (uint32_t)(A0.w[q] >> ((r - 1) & 63)) & 1u;
-                    a1 = (uint32_t)(A1.w[q] >> ((r - 1) & 63)) & 1u;
-                }
-            }
-            const uint32_t mm = (tb0 ^ (0u - a0)) | (tb1 ^ (0u - a1));
-            int hleft, eleft;
-            if (j0 == 0) {
-                hleft = o + (r - 1) * e; /* H[r][0] */
-                eleft = NW_BIG;
-            } else {
-                const uint32_t pk = s_bound[r][t];
-                hleft = (int)(pk & 0xffffu);
-                eleft = (int)(pk >> 16);
-            }
-            const int next_diag = hleft;
-#pragma unroll
-            for (int jj = 0; jj < NW_CB; jj++) {
-                const int up = H[jj];
-                int f = F[jj] + e;
-                f = up + o < f ? up + o : f;
-                int ee = eleft + e;
-                ee = hleft + o < ee ? hleft + o : ee;
-                const int dg = diag + (((mm >> jj) & 1u) ? x : 0);
-                int h = dg < f ? dg : f;
-                h = ee < h ? ee : h;
-                f = f > NW_BIG ? NW_BIG : f;
-                ee = ee > NW_BIG ? NW_BIG : ee;
-                diag = up;
-                H[jj] = h, F[jj] = f;
-                hleft = h, eleft = ee;
-            }
-            diag = next_diag;
-            s_bound[r][t] = (uint32_t)hleft | ((uint32_t)eleft << 16);
-        }
-        if (nn > j0 && nn <= j0 + NW_CB) {
-            const int want = nn - j0 - 1;
-#pragma unroll
-            for (int jj = 0; jj < NW_CB; jj++)
-                if (jj == want) result = H[jj];
-        }
-    }
+    NoCellSink sink;
+    const int result = gotoh_sweep<W64>(A0, A1, B0, B1, m, nn, x, o, e, &s_bound[0][t], 64, sink);
     out.put(i, result);
 }
 

@@ -2,7 +2,13 @@
     PYTHONPATH=. python tools/ab_lib.py approximate-string-matching_amd/libasm_base.so approximate-string-matching_amd/libasm_mi355x.so C3:2e6 C2:1e6
 Each (library, workload) is timed in a fresh process (the library path is read at import), `rounds` times, interleaved; prints the
 per-kernel medians side by side, each with the lowest and highest of its rounds (the spread of one library's own rounds is the noise
-a difference between two has to exceed); a child that fails ends the run.  LEAP is timed un-hinted and hinted by the Greedy penalties (the shape of C3's step)."""
+a difference between two has to exceed); a child that fails ends the run.  LEAP is timed un-hinted and hinted by the Greedy penalties (the shape of C3's step).
+A workload written NAME:N:general times the general-penalty kernels instead, which no benchmark workload reaches: LEAP with (2,3,1) at
+k = 3, 5, 7, 8 and with (4,6,2) at k = 3 (leap_general_kernel: short and byte rings; beyond its reach leap_quad_kernel), k = 12
+(leap_quad_kernel) and in ED mode LOCAL (leap_wide_kernel, on N/16 pairs: a workgroup per pair), NW with (2,3,1) behind the banded
+wavefront passes, the coverage counter with (2,3,1) (nw_trace_affine_kernel, N/4 pairs) and the affine SIMD_ED filter at gap 8 (the
+quad kernel up to 128 characters, thread per pair beyond).  NAME:N:general-full runs its children with ASM_NW_WFA=0 and times NW with
+(2,3,1) alone: nw_affine_kernel over every pair.  The string length picks the instantiation: C2 100, C3 150, C5 64-300."""
 import json, os, statistics, subprocess, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,6 +27,32 @@ def timed(fn):
     for _ in range(4):
         tm.start(); fn(); tm.stop(); best = min(best, tm.elapsed_ms())
     return best
+if len(sys.argv) > 3:
+    import ctypes
+    g = lambda **kw: m.Params.default(x=2, o=3, e=1, **kw)
+    dd = d[m.NW]
+    if sys.argv[3] == "general-full":
+        out["nw_affine_full"] = timed(lambda: eng.align_async(batch, m.NW, g(), dd))
+        print(json.dumps(out))
+        sys.exit(0)
+    for k in (3, 5, 7, 8):
+        out["leap_general_k%d" % k] = timed(lambda: eng.align_async(batch, m.LEAP, g(k=k), dd))
+    out["leap_general_k3_462"] = timed(lambda: eng.align_async(batch, m.LEAP, m.Params.default(k=3, x=4, o=6, e=2), dd))
+    out["leap_quad_k12"] = timed(lambda: eng.align_async(batch, m.LEAP, g(k=12), dd))
+    small = eng.generate(cfg, 1, max(n // 16, 1024))
+    out["leap_wide_local"] = timed(lambda: eng.align_async(small, m.LEAP, g(k=12, leap_mode=1), dd))
+    out["nw_wfa_oct_affine"] = timed(lambda: eng.align_async(batch, m.NW, g(), dd))
+    quarter = eng.generate(cfg, 2, max(n // 4, 1024))
+    # the C entry itself, on buffers sized here: Engine.coverage copies every CIGAR back and decodes it in Python, far longer than the kernels
+    qn, cap, cp = quarter.n, 64, g(k=3)
+    c_pen, c_ops, c_nops, c_cov, c_cnt = eng.malloc(4 * qn), eng.malloc(2 * cap * qn), eng.malloc(qn), eng.malloc(qn), eng.malloc(16)
+    eng._chk(eng.lib.asm_greedy_cigar_batch_async(eng.h, quarter.ptr, ctypes.byref(cp), c_pen, c_ops, cap, c_nops))
+    eng.memset_async(c_cnt, 0, 16)
+    out["cover_trace_affine"] = timed(lambda: eng._chk(eng.lib.asm_coverage(eng.h, quarter.ptr, ctypes.byref(cp), c_ops, cap, c_nops, 64,
+                                                                           c_cov, None, cap, None, c_cnt)))
+    out["simd_ed_affine_gap8"] = timed(lambda: eng.simd_ed_affine_async(batch, 8, 60, 2, 3, 1, dd))
+    print(json.dumps(out))
+    sys.exit(0)
 out["pack"] = timed(lambda: eng.pack_async(batch))
 out["nw"] = timed(lambda: eng.align_async(batch, m.NW, params, d[m.NW]))
 out["greedy"] = timed(lambda: eng.align_async(batch, m.GREEDY, params, d[m.GREEDY]))
@@ -35,10 +67,12 @@ rounds = int(os.environ.get("AB_ROUNDS", "3"))
 res = {}
 for r in range(rounds):
     for w in works:
-        name, n = w.split(":")
+        name, n, *kind = w.split(":")
         for lib in libs:
             env = dict(os.environ, ASM_MI355X_LIB=os.path.abspath(lib), PYTHONPATH=ROOT)
-            p = subprocess.run([sys.executable, "-c", CHILD, name, n], env=env, capture_output=True, text=True, timeout=600)
+            if kind == ["general-full"]:
+                env["ASM_NW_WFA"] = "0"  # switches are read when the handle is created
+            p = subprocess.run([sys.executable, "-c", CHILD, name, n] + kind, env=env, capture_output=True, text=True, timeout=600)
             if p.returncode != 0:
                 sys.exit("FAILED %s %s (exit %d)\n%s" % (lib, w, p.returncode, p.stderr[-800:]))  # nothing more on a device that faulted
             d = json.loads(p.stdout.strip().splitlines()[-1])
