@@ -243,53 +243,6 @@ struct BigScratch {
     hipError_t alloc(asm_handle* h, size_t bytes) { return big_malloc(h, (void**)&p, bytes); }
 };
 
-/* One width class of a batch: pairs whose longer string needs `w4` granules of 128 positions. */
-struct asm_bucket {
-    int64_t n = 0;
-    int w4 = 1;
-    int maxlen = 0;
-    uint4* planes = nullptr;    /* uint4[4][w4][n], inside asm_batch::d_planes */
-    uint32_t* lens = nullptr;   /* uint32[n],       inside asm_batch::d_lens   */
-    uint32_t* order = nullptr;  /* bucket slot -> pair index; null when the batch is one bucket in input order */
-    bool mixed = false;         /* one of several width classes of a mixed-length batch */
-};
-
-struct asm_batch {
-    asm_handle* owner = nullptr; /* whose pool the device blocks come from */
-    unsigned long long owner_serial = 0;
-    int64_t n = 0;
-    int maxlen = 0;
-    int greedy_mode = ASM_GREEDY_CLEAN;
-    size_t reads_bytes = 0, refs_bytes = 0;
-    char* d_reads = nullptr;
-    char* d_refs = nullptr;
-    uint32_t* d_read_off = nullptr;
-    uint32_t* d_ref_off = nullptr;
-    uint4* d_planes = nullptr;  /* all buckets back to back */
-    uint32_t* d_lens = nullptr; /* in bucketed order */
-    uint32_t* d_order = nullptr; /* bucketed slot -> pair index (null: identity) */
-    uint32_t* d_pos = nullptr;   /* pair index -> bucketed slot (null: identity) */
-    /* pipelined repack (asm_run_benchmark_async, repack = 2): a second set of planes/lens that the next call's pack fills
-     * while this call's aligners still read the current one */
-    uint4* d_planes_alt = nullptr;
-    uint32_t* d_lens_alt = nullptr;
-    size_t planes_total = 0;     /* uint4 entries in d_planes */
-    hipEvent_t ev_consumed[2] = {nullptr, nullptr}; /* aligners of the call that used buffer q are done */
-    int cur = 0;
-    uint4* d_tails = nullptr;    /* sequential mode: stale-tail planes, uint4[4][n] in input order */
-    uint4* d_tail_g0 = nullptr;  /* tail resolver scratch (asm_tails.h), allocated on first use: clean granule 0 in input order, */
-    uint32_t* d_tail_l0 = nullptr; /* its lengths, */
-    uint8_t* d_tail_chunks = nullptr; /* per-chunk prefixes, per-workgroup totals and carries + the 256-byte summary */
-    int nb = 1;
-    asm_bucket bk[4];
-    PackBuckets pb;
-};
-
-struct asm_reference {
-    char* d_text = nullptr;
-    size_t len = 0;
-};
-
 static thread_local std::string g_err;
 /* handles that exist: a batch remembers the handle whose pool its device blocks came from, and may be freed through another
  * handle, or after its own is gone */
@@ -329,55 +282,6 @@ static hipError_t launch(asm_handle* h, void (*kernel)(P...), unsigned grid, uns
     return launch_on(h->stream, kernel, grid, block, 0, std::forward<A>(args)...);
 }
 
-/* The only place that frees a batch's device blocks (its owner is live). */
-static void batch_release(asm_batch* b) {
-    if (!b) return;
-    asm_handle* const o = b->owner;
-    /* the pool hands blocks out again in the order of o->stream; overlapped calls that were never joined may still read these
-     * on the library's own streams */
-    (void)o->pipe.join_into(o->stream);
-    pool_free(o, b->d_reads);
-    pool_free(o, b->d_refs);
-    pool_free(o, b->d_read_off);
-    pool_free(o, b->d_ref_off);
-    pool_free(o, b->d_planes);
-    pool_free(o, b->d_lens);
-    pool_free(o, b->d_planes_alt);
-    pool_free(o, b->d_lens_alt);
-    for (hipEvent_t ev : b->ev_consumed)
-        if (ev) (void)hipEventDestroy(ev);
-    pool_free(o, b->d_order);
-    pool_free(o, b->d_pos);
-    pool_free(o, b->d_tails);
-    pool_free(o, b->d_tail_g0);
-    pool_free(o, b->d_tail_l0);
-    pool_free(o, b->d_tail_chunks);
-    delete b;
-}
-
-struct BatchRelease {
-    void operator()(asm_batch* b) const { batch_release(b); }
-};
-using BatchPtr = std::unique_ptr<asm_batch, BatchRelease>; /* a batch under construction, or a streamed chunk's */
-
-/* A new, empty batch of n pairs whose device blocks will come from h's pool. */
-static int batch_new(asm_handle* h, int64_t n, int greedy_mode, const char* who, BatchPtr& b) {
-    if (greedy_mode != ASM_GREEDY_CLEAN && greedy_mode != ASM_GREEDY_SEQUENTIAL)
-        return fail(h, ASM_EINVAL, std::string(who) + ": unknown greedy_mode");
-    b.reset(new asm_batch);
-    b->owner = h, b->owner_serial = h->serial;
-    b->n = n;
-    b->greedy_mode = greedy_mode;
-    return ASM_OK;
-}
-
-/* Every device block a batch owns comes from its owner's pool, whichever handle the call came through: batch_release returns
- * it there. */
-template <typename T>
-static hipError_t batch_alloc(asm_batch* b, T** p, size_t bytes) {
-    return pool_alloc(b->owner, (void**)p, bytes);
-}
-
 static int grid_for(int64_t n) { return (int)((n + ASM_BLOCK - 1) / ASM_BLOCK); }
 
 /* Run-time value -> template argument, the one way this library does it: fn(std::integral_constant<int, C>{}) for the first C
@@ -408,6 +312,12 @@ static int grow_device(asm_handle* h, T*& p, size_t& cap, size_t need) {
     HIPCHK(h, big_malloc(h, (void**)&p, sizeof(T) * need));
     cap = need;
     return ASM_OK;
+}
+
+/* the batch: "scalars back, one wait" and hipcub's scratch, the batch and its owner, the builder behind every constructor, the pack
+ * launch, the tail resolver's host side and the entries of batches and references */
+extern "C" {
+#include "asm_batch.h"
 }
 
 /* one(bucket, its OutMap onto `out`) for every width class of a batch, up to the first that fails */
@@ -818,414 +728,11 @@ int asm_synchronize(asm_handle* h) {
 }
 
 /* ---------------------------------------------------------------------------------------------------- */
-static int check_gen(const asm_gen_config* cfg) {
-    std::string err;
-    const int rc = asm_host::check_gen(cfg, err);
-    return rc ? fail(nullptr, rc, err) : ASM_OK;
-}
-
 int asm_generate_pairs(const asm_gen_config* cfg, int64_t first, int64_t n, uint32_t* read_off, uint32_t* ref_off,
                        char* reads, size_t reads_cap, char* refs, size_t refs_cap) {
     std::string err;
     const int rc = asm_host::generate_pairs(cfg, first, n, read_off, ref_off, reads, reads_cap, refs, refs_cap, err);
     return rc ? fail(nullptr, rc, err) : ASM_OK;
-}
-
-/* ---------------------------------------------------------------------------------------------------- */
-
-static hipError_t launch_pack(asm_handle* h, const asm_batch* b, const uint4* tails, uint4* planes, uint32_t* lens,
-                              const PackBuckets& pb, const uint32_t* pos) {
-    int wmax = 1;
-    for (int q = 0; q < pb.nb; q++) wmax = pb.w4[q] > wmax ? pb.w4[q] : wmax;
-    // LDS: the plane arrays of both sides of 256 strings of the batch's longest length (+ alignment slack), capped; at least
-    // one string's (the rounds path then makes progress)
-    const auto side_dwords = [](size_t bytes) { return (size_t)2 * (size_t)(((bytes + 15) / 16 + 1) / 2 + 1); };
-    size_t dw = 2 * side_dwords((size_t)PACK_BLOCK * (size_t)b->maxlen + 15);
-    if (dw > PACK_LDS_MAX / 4) dw = PACK_LDS_MAX / 4;
-    if (dw < side_dwords((size_t)b->maxlen + 30)) dw = side_dwords((size_t)b->maxlen + 30);
-    return with_const<1, 4>(wmax, [&](auto w) {
-        return launch_lds(h, pack_kernel<decltype(w)::value>, (unsigned)((b->n + PACK_BLOCK - 1) / PACK_BLOCK), PACK_BLOCK, dw * 4,
-                          b->d_reads, b->d_read_off, b->d_refs, b->d_ref_off, tails, planes, lens, (long)b->n, pb, pos, (uint32_t)dw);
-    });
-}
-
-int asm_batch_pack_async(asm_handle* h, asm_batch* b) {
-    if (!h || !b) return fail(h, ASM_EINVAL, "asm_batch_pack_async: NULL argument");
-    if (b->n == 0) return ASM_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, launch_pack(h, b, b->d_tails, b->d_planes, b->d_lens, b->pb, b->d_pos));
-    return ASM_OK;
-}
-
-/* ASM_GREEDY_SEQUENTIAL: derive the stale buffer tails on the device (asm_tails.h).  The resolver walks the pairs
- * in INPUT order and only needs granule 0, so it works on a temporary clean-mode, unbucketed, one-granule packing.
- * init256 (host, optional): buffer codes before the batch's first pair; summary256 (host, optional): the batch's effect on
- * the buffers (see tails_carry_kernel); emit = false stops after the summary (b->d_tails untouched). */
-static int batch_resolve_tails(asm_handle* h, asm_batch* b, const uint8_t* init256, uint8_t* summary256, bool emit) {
-    if (summary256) memset(summary256, TAIL_NONE, 256);
-    if (b->n == 0) return ASM_OK;
-    const long nchunks = (b->n + TAIL_CHUNK - 1) / TAIL_CHUNK;
-    const long ngroups = (nchunks + TAIL_GROUP - 1) / TAIL_GROUP;
-    TailState init;
-    if (init256) memcpy(init.code, init256, 256);
-    else memset(init.code, 0, 256);
-    /* scratch lives with the batch: a streamed file re-resolves every chunk, a bench step every iteration */
-    if (emit && !b->d_tails) HIPCHK(h, batch_alloc(b, &b->d_tails, sizeof(uint4) * 4 * (size_t)b->n));
-    const size_t loc_bytes = (size_t)ngroups * TAIL_GROUP * 2 * sizeof(TailOp), grp_bytes = (size_t)ngroups * 2 * sizeof(TailOp);
-    const size_t carry_bytes = (size_t)ngroups * 2 * 2 * sizeof(uint4);
-    if (!b->d_tail_g0) HIPCHK(h, batch_alloc(b, &b->d_tail_g0, sizeof(uint4) * 4 * (size_t)b->n));
-    if (!b->d_tail_l0) HIPCHK(h, batch_alloc(b, &b->d_tail_l0, sizeof(uint32_t) * (size_t)b->n));
-    if (!b->d_tail_chunks) HIPCHK(h, batch_alloc(b, &b->d_tail_chunks, loc_bytes + grp_bytes + carry_bytes + 256)); /* loc, grp, gcarry, summary[256] */
-    TailOp* const d_loc = (TailOp*)b->d_tail_chunks;
-    TailOp* const d_grp = (TailOp*)(b->d_tail_chunks + loc_bytes);
-    uint4* const d_carry = (uint4*)(b->d_tail_chunks + loc_bytes + grp_bytes);
-    uint8_t* const d_sum = b->d_tail_chunks + loc_bytes + grp_bytes + carry_bytes;
-    PackBuckets one{};
-    one.nb = 1, one.w4[0] = 1, one.start[0] = 0, one.start[1] = b->n, one.plane_off[0] = 0;
-    HIPCHK(h, launch_pack(h, b, nullptr, b->d_tail_g0, b->d_tail_l0, one, nullptr));
-    HIPCHK(h, launch(h, tails_chunk_kernel, (unsigned)ngroups, 2 * TAIL_GROUP, b->d_tail_g0, b->d_tail_l0, (long)b->n, d_loc, d_grp));
-    HIPCHK(h, launch(h, tails_carry_kernel, 1, 8 * TAIL_CARRY_SEGS, (const uint32_t*)d_grp, (uint32_t*)d_carry, ngroups, init,
-                     summary256 ? d_sum : (uint8_t*)nullptr));
-    if (emit)
-        HIPCHK(h, launch(h, tails_emit_kernel, (unsigned)ngroups, 2 * TAIL_GROUP, b->d_tail_g0, b->d_tail_l0, (long)b->n,
-                         (const TailOp*)d_loc, (const uint4*)d_carry, b->d_tails));
-    if (summary256) {
-        HIPCHK(h, hipMemcpyAsync(summary256, d_sum, 256, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return ASM_OK;
-}
-
-/* Common tail of upload/generate once ASCII + offsets are resident and b->maxlen is known: group the pairs into width
- * classes (only when the batch really mixes classes), allocate the packed form, resolve tails, pack. */
-static int batch_finish(asm_handle* h, asm_batch* b) {
-    const int64_t n = b->n;
-    const int wmax = b->maxlen <= 128 ? 1 : (b->maxlen + 127) / 128;
-    unsigned int counts[4] = {0, 0, 0, 0};
-    Scratch<uint8_t> d_cls(h), d_cls2(h);
-    Scratch<uint32_t> d_idx(h);
-    Scratch<unsigned int> d_counts(h);
-    Scratch<void> d_tmp(h);
-    bool bucketed = false;
-    if (wmax > 1 && n >= 4096 && h->bucketing) {
-        HIPCHK(h, d_cls.alloc((size_t)n));
-        HIPCHK(h, d_cls2.alloc((size_t)n));
-        HIPCHK(h, d_idx.alloc(sizeof(uint32_t) * (size_t)n));
-        HIPCHK(h, d_counts.alloc(16));
-        HIPCHK(h, hipMemsetAsync(d_counts.p, 0, 16, h->stream));
-        HIPCHK(h, launch(h, classify_kernel, grid_for(n), ASM_BLOCK, b->d_read_off, b->d_ref_off, (long)n, d_cls.p, d_idx.p, d_counts.p));
-        HIPCHK(h, hipMemcpyAsync(counts, d_counts.p, 16, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        int classes = 0;
-        for (int c = 0; c < 4; c++) classes += counts[c] ? 1 : 0;
-        bucketed = classes > 1;
-        if (bucketed) {
-            HIPCHK(h, batch_alloc(b, &b->d_order, sizeof(uint32_t) * (size_t)n));
-            HIPCHK(h, batch_alloc(b, &b->d_pos, sizeof(uint32_t) * (size_t)n));
-            size_t tmp_bytes = 0;
-            HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_cls.p, d_cls2.p, d_idx.p, b->d_order, (int)n, 0, 2,
-                                                         h->stream));
-            HIPCHK(h, d_tmp.alloc(tmp_bytes + 16));
-            HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, d_cls.p, d_cls2.p, d_idx.p, b->d_order, (int)n, 0, 2,
-                                                         h->stream)); /* stable: input order is kept inside a class */
-            HIPCHK(h, launch(h, invert_order_kernel, grid_for(n), ASM_BLOCK, b->d_order, (long)n, b->d_pos));
-        }
-    }
-    // bucket table
-    b->nb = 0;
-    size_t plane_total = 0;
-    int64_t slot = 0;
-    b->pb = PackBuckets{};
-    if (!bucketed) {
-        counts[0] = counts[1] = counts[2] = counts[3] = 0;
-        counts[wmax - 1] = (unsigned int)n;
-    }
-    for (int c = 0; c < 4; c++) {
-        if (!counts[c] && !(n == 0 && c == 0)) continue;
-        asm_bucket& k = b->bk[b->nb];
-        k.n = counts[c];
-        k.w4 = c + 1;
-        k.maxlen = b->maxlen < 128 * (c + 1) ? b->maxlen : 128 * (c + 1);
-        b->pb.w4[b->nb] = k.w4;
-        b->pb.start[b->nb] = slot;
-        b->pb.plane_off[b->nb] = (long)plane_total;
-        plane_total += (size_t)4 * (size_t)k.w4 * (size_t)k.n;
-        slot += k.n;
-        b->nb++;
-    }
-    b->pb.nb = b->nb;
-    b->pb.start[b->nb] = slot;
-    b->planes_total = plane_total ? plane_total : 1;
-    HIPCHK(h, batch_alloc(b, &b->d_planes, sizeof(uint4) * (plane_total ? plane_total : 1)));
-    HIPCHK(h, batch_alloc(b, &b->d_lens, sizeof(uint32_t) * (size_t)(n > 0 ? n : 1)));
-    for (int q = 0; q < b->nb; q++) {
-        b->bk[q].planes = b->d_planes + b->pb.plane_off[q];
-        b->bk[q].lens = b->d_lens + b->pb.start[q];
-        b->bk[q].order = b->d_order ? b->d_order + b->pb.start[q] : nullptr;
-        b->bk[q].mixed = bucketed;
-    }
-    int rc = b->greedy_mode == ASM_GREEDY_SEQUENTIAL ? batch_resolve_tails(h, b, nullptr, nullptr, true) : ASM_OK;
-    if (!rc) rc = asm_batch_pack_async(h, b);
-    if (rc) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return ASM_OK;
-}
-
-int asm_batch_upload(asm_handle* h, int64_t n, const char* reads, const uint32_t* read_off, const char* refs,
-                     const uint32_t* ref_off, int greedy_mode, asm_batch** out) {
-    if (!h || !out || n < 0 || !read_off || !ref_off || (n > 0 && (!reads || !refs)))
-        return fail(h, ASM_EINVAL, "asm_batch_upload: bad arguments");
-    BatchPtr b;
-    int rc = batch_new(h, n, greedy_mode, "asm_batch_upload", b);
-    if (rc) return rc;
-    *out = nullptr;
-    HIPCHK(h, hipSetDevice(h->device));
-    int maxlen = 0;
-    for (int64_t i = 0; i < n; i++) {
-        if (read_off[i + 1] < read_off[i] || ref_off[i + 1] < ref_off[i])
-            return fail(h, ASM_EINVAL, "asm_batch_upload: offsets must be non-decreasing");
-        int m = (int)(read_off[i + 1] - read_off[i]), nn = (int)(ref_off[i + 1] - ref_off[i]);
-        if (m > maxlen) maxlen = m;
-        if (nn > maxlen) maxlen = nn;
-    }
-    if (maxlen > ASM_MAX_LENGTH)
-        return fail(h, ASM_EUNSUPPORTED, "asm_batch_upload: a sequence is longer than ASM_MAX_LENGTH");
-    b->maxlen = maxlen;
-    b->reads_bytes = n ? read_off[n] : 0;
-    b->refs_bytes = n ? ref_off[n] : 0;
-    HIPCHK(h, batch_alloc(b.get(), &b->d_reads, b->reads_bytes + 16));
-    HIPCHK(h, batch_alloc(b.get(), &b->d_refs, b->refs_bytes + 16));
-    HIPCHK(h, batch_alloc(b.get(), &b->d_read_off, sizeof(uint32_t) * (size_t)(n + 1)));
-    HIPCHK(h, batch_alloc(b.get(), &b->d_ref_off, sizeof(uint32_t) * (size_t)(n + 1)));
-    HIPCHK(h, hipMemcpyAsync(b->d_reads, reads, b->reads_bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(b->d_refs, refs, b->refs_bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(b->d_read_off, read_off, sizeof(uint32_t) * (size_t)(n + 1), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(b->d_ref_off, ref_off, sizeof(uint32_t) * (size_t)(n + 1), hipMemcpyHostToDevice, h->stream));
-    rc = batch_finish(h, b.get());
-    if (rc) return rc;
-    *out = b.release();
-    return ASM_OK;
-}
-
-int asm_batch_generate(asm_handle* h, const asm_gen_config* cfg, int64_t first, int64_t n, int greedy_mode,
-                       asm_batch** out) {
-    if (!h || !out || n < 0 || first < 0) return fail(h, ASM_EINVAL, "asm_batch_generate: bad arguments");
-    int rc = check_gen(cfg);
-    if (rc) return fail(h, rc, g_err);
-    BatchPtr b;
-    rc = batch_new(h, n, greedy_mode, "asm_batch_generate", b);
-    if (rc) return rc;
-    *out = nullptr;
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t cnt = (size_t)n + 1;
-    Scratch<uint32_t> d_m(h), d_n(h), d_max(h);
-    Scratch<void> d_tmp(h);
-    HIPCHK(h, d_m.alloc(sizeof(uint32_t) * cnt));
-    HIPCHK(h, d_n.alloc(sizeof(uint32_t) * cnt));
-    HIPCHK(h, d_max.alloc(sizeof(uint32_t) * 2));
-    HIPCHK(h, batch_alloc(b.get(), &b->d_read_off, sizeof(uint32_t) * cnt));
-    HIPCHK(h, batch_alloc(b.get(), &b->d_ref_off, sizeof(uint32_t) * cnt));
-    HIPCHK(h, hipMemsetAsync(d_m.p, 0, sizeof(uint32_t) * cnt, h->stream));
-    HIPCHK(h, hipMemsetAsync(d_n.p, 0, sizeof(uint32_t) * cnt, h->stream));
-    if (n > 0) HIPCHK(h, launch(h, gen_lengths_kernel, grid_for(n), ASM_BLOCK, *cfg, (long)first, (long)n, d_m.p, d_n.p));
-    size_t tmp_bytes = 0, t2 = 0;
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_m.p, b->d_read_off, (int)cnt, h->stream));
-    HIPCHK(h, hipcub::DeviceReduce::Max(nullptr, t2, d_n.p, d_max.p, (int)cnt, h->stream));
-    if (t2 > tmp_bytes) tmp_bytes = t2;
-    HIPCHK(h, d_tmp.alloc(tmp_bytes + 16));
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_m.p, b->d_read_off, (int)cnt, h->stream));
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_n.p, b->d_ref_off, (int)cnt, h->stream));
-    HIPCHK(h, hipcub::DeviceReduce::Max(d_tmp.p, tmp_bytes, d_m.p, d_max.p, (int)cnt, h->stream));
-    HIPCHK(h, hipcub::DeviceReduce::Max(d_tmp.p, tmp_bytes, d_n.p, d_max.p + 1, (int)cnt, h->stream));
-    uint32_t tot[2] = {0, 0}, mx[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(&tot[0], b->d_read_off + n, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&tot[1], b->d_ref_off + n, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(mx, d_max.p, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    /* 32-bit offsets: the host-side bound (n * worst length) must stay below 4 GiB */
-    const double bound = (double)n * (double)(cfg->len_hi * 2 + 2);
-    if (bound >= 4294967295.0 && (double)n * (double)(mx[0] > mx[1] ? mx[0] : mx[1]) >= 4294967295.0)
-        return fail(h, ASM_EUNSUPPORTED, "asm_batch_generate: batch exceeds 4 GiB of text; split it");
-    b->reads_bytes = tot[0];
-    b->refs_bytes = tot[1];
-    b->maxlen = (int)(mx[0] > mx[1] ? mx[0] : mx[1]);
-    if (b->maxlen > ASM_MAX_LENGTH) return fail(h, ASM_EUNSUPPORTED, "asm_batch_generate: a generated sequence exceeds ASM_MAX_LENGTH");
-    HIPCHK(h, batch_alloc(b.get(), &b->d_reads, b->reads_bytes + 16));
-    HIPCHK(h, batch_alloc(b.get(), &b->d_refs, b->refs_bytes + 16));
-    if (n > 0)
-        HIPCHK(h, launch(h, gen_fill_kernel, (unsigned)((n + 63) / 64), 64, *cfg, (long)first, (long)n, b->d_read_off, b->d_ref_off,
-                         b->d_reads, b->d_refs));
-    rc = batch_finish(h, b.get());
-    if (rc) return rc;
-    *out = b.release();
-    return ASM_OK;
-}
-
-int asm_reference_upload(asm_handle* h, const char* text, size_t len, asm_reference** out) {
-    if (!h || !out || (!text && len)) return fail(h, ASM_EINVAL, "asm_reference_upload: bad argument");
-    *out = nullptr;
-    HIPCHK(h, hipSetDevice(h->device));
-    asm_reference* r = new asm_reference;
-    r->len = len;
-    if (big_malloc(h, (void**)&r->d_text, len + 16) != hipSuccess) {
-        delete r;
-        return fail(h, ASM_ENOMEM, "asm_reference_upload: hipMalloc failed");
-    }
-    if (len && hipMemcpy(r->d_text, text, len, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(r->d_text);
-        delete r;
-        return fail(h, ASM_ENODEVICE, "asm_reference_upload: copy failed");
-    }
-    *out = r;
-    return ASM_OK;
-}
-
-int asm_reference_free(asm_handle* h, asm_reference* r) {
-    if (h) (void)hipSetDevice(h->device);
-    if (r) {
-        (void)hipFree(r->d_text);
-        delete r;
-    }
-    return ASM_OK;
-}
-
-int asm_batch_from_hits(asm_handle* h, const asm_reference* ref, int64_t n, const char* reads, const uint32_t* read_off,
-                        const uint64_t* hit_pos, int greedy_mode, asm_batch** out) {
-    if (!h || !ref || !out || n < 0 || !read_off || (n > 0 && (!reads || !hit_pos)))
-        return fail(h, ASM_EINVAL, "asm_batch_from_hits: bad arguments");
-    BatchPtr b;
-    int rc = batch_new(h, n, greedy_mode, "asm_batch_from_hits", b);
-    if (rc) return rc;
-    *out = nullptr;
-    HIPCHK(h, hipSetDevice(h->device));
-    int maxlen = 0;
-    for (int64_t i = 0; i < n; i++) {
-        if (read_off[i + 1] < read_off[i]) return fail(h, ASM_EINVAL, "asm_batch_from_hits: offsets must be non-decreasing");
-        const int m = (int)(read_off[i + 1] - read_off[i]);
-        maxlen = m > maxlen ? m : maxlen;
-    }
-    if (maxlen + 1 > ASM_MAX_LENGTH) return fail(h, ASM_EUNSUPPORTED, "asm_batch_from_hits: a read is longer than ASM_MAX_LENGTH - 1");
-    b->maxlen = maxlen + 1; /* the window is one base longer than the read (mapper/main.cpp:80) */
-    b->reads_bytes = n ? read_off[n] : 0;
-    const size_t cnt = (size_t)n + 1;
-    Scratch<unsigned long long> d_pos(h);
-    Scratch<uint32_t> d_wl(h);
-    Scratch<void> d_tmp(h);
-    HIPCHK(h, batch_alloc(b.get(), &b->d_reads, b->reads_bytes + 16));
-    HIPCHK(h, batch_alloc(b.get(), &b->d_read_off, sizeof(uint32_t) * cnt));
-    HIPCHK(h, batch_alloc(b.get(), &b->d_ref_off, sizeof(uint32_t) * cnt));
-    HIPCHK(h, d_pos.alloc(sizeof(unsigned long long) * cnt));
-    HIPCHK(h, d_wl.alloc(sizeof(uint32_t) * cnt));
-    HIPCHK(h, hipMemcpyAsync(b->d_reads, reads, b->reads_bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(b->d_read_off, read_off, sizeof(uint32_t) * cnt, hipMemcpyHostToDevice, h->stream));
-    if (n) HIPCHK(h, hipMemcpyAsync(d_pos.p, hit_pos, sizeof(unsigned long long) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, launch(h, hit_window_lengths_kernel, grid_for(n + 1), ASM_BLOCK, b->d_read_off, d_pos.p, (unsigned long long)ref->len,
-                     (long)n, d_wl.p));
-    size_t tmp_bytes = 0;
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_wl.p, b->d_ref_off, (int)cnt, h->stream));
-    HIPCHK(h, d_tmp.alloc(tmp_bytes + 16));
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_wl.p, b->d_ref_off, (int)cnt, h->stream));
-    uint32_t total = 0;
-    HIPCHK(h, hipMemcpyAsync(&total, b->d_ref_off + n, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    b->refs_bytes = total;
-    HIPCHK(h, batch_alloc(b.get(), &b->d_refs, b->refs_bytes + 16));
-    if (n) {
-        int64_t blocks = (n + 3) / 4;
-        blocks = blocks > 256 * 16 ? 256 * 16 : blocks;
-        HIPCHK(h, launch(h, hit_window_gather_kernel, (unsigned)blocks, ASM_BLOCK, ref->d_text, d_pos.p, b->d_ref_off, (long)n, b->d_refs));
-    }
-    rc = batch_finish(h, b.get());
-    if (rc) return rc;
-    *out = b.release();
-    return ASM_OK;
-}
-
-/* ---- Greedy sequential mode across batches: shards of one file on several GPUs, or chunks of a streamed file ---- */
-int asm_batch_tail_summary(asm_handle* h, const asm_batch* b, uint8_t* summary) {
-    if (!h || !b || !summary) return fail(h, ASM_EINVAL, "asm_batch_tail_summary: NULL argument");
-    HIPCHK(h, hipSetDevice(h->device));
-    return batch_resolve_tails(h, const_cast<asm_batch*>(b), nullptr, summary, false);
-}
-
-int asm_tail_state_advance(uint8_t* state, const uint8_t* summary, int64_t n_pairs) {
-    std::string err;
-    const int rc = asm_host::tail_state_advance(state, summary, n_pairs, err);
-    return rc ? fail(nullptr, rc, err) : ASM_OK;
-}
-
-int asm_batch_resolve_tails(asm_handle* h, asm_batch* b, const uint8_t* state) {
-    if (!h || !b) return fail(h, ASM_EINVAL, "asm_batch_resolve_tails: NULL argument");
-    if (state)
-        for (int q = 0; q < 256; q++)
-            if (state[q] > 3) return fail(h, ASM_EINVAL, "asm_batch_resolve_tails: state entries are 2-bit codes (0..3)");
-    HIPCHK(h, hipSetDevice(h->device));
-    b->greedy_mode = ASM_GREEDY_SEQUENTIAL;
-    int rc = batch_resolve_tails(h, b, state, nullptr, true);
-    if (!rc) rc = asm_batch_pack_async(h, b);
-    return rc;
-}
-
-int asm_batch_free(asm_handle* h, asm_batch* b) {
-    if (!b) return ASM_OK;
-    /* The device blocks belong to the pool of the handle that created the batch, whichever handle is named here (h may be NULL):
-     * they go back THERE.  The owner is named by (address, serial): if that handle is gone — asm_destroy has released every
-     * block of its pool, this batch's included — only the record is left, also when a NEW handle lives at the old address.
-     * Look-up and release happen under one lock, so the owner cannot be destroyed in between. */
-    (void)h;
-    std::lock_guard<std::mutex> lk(g_live_mu);
-    if (!owner_is_live_locked(b->owner, b->owner_serial)) {
-        for (hipEvent_t ev : b->ev_consumed) /* events belong to the device context, not to the handle */
-            if (ev) (void)hipEventDestroy(ev);
-        delete b;
-        return ASM_OK;
-    }
-    (void)hipSetDevice(b->owner->device);
-    batch_release(b);
-    return ASM_OK;
-}
-
-int64_t asm_batch_size(const asm_batch* b) { return b ? b->n : 0; }
-int asm_batch_max_length(const asm_batch* b) { return b ? b->maxlen : 0; }
-int64_t asm_batch_text_bytes(const asm_batch* b) { return b ? (int64_t)(b->reads_bytes + b->refs_bytes) : 0; }
-
-int asm_batch_download(asm_handle* h, const asm_batch* b, uint32_t* read_off, uint32_t* ref_off, char* reads,
-                       size_t reads_cap, char* refs, size_t refs_cap) {
-    if (!h || !b) return fail(h, ASM_EINVAL, "asm_batch_download: NULL argument");
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (read_off) HIPCHK(h, hipMemcpy(read_off, b->d_read_off, sizeof(uint32_t) * (size_t)(b->n + 1), hipMemcpyDeviceToHost));
-    if (ref_off) HIPCHK(h, hipMemcpy(ref_off, b->d_ref_off, sizeof(uint32_t) * (size_t)(b->n + 1), hipMemcpyDeviceToHost));
-    if (reads) {
-        if (reads_cap < b->reads_bytes) return fail(h, ASM_EINVAL, "asm_batch_download: reads buffer too small");
-        HIPCHK(h, hipMemcpy(reads, b->d_reads, b->reads_bytes, hipMemcpyDeviceToHost));
-    }
-    if (refs) {
-        if (refs_cap < b->refs_bytes) return fail(h, ASM_EINVAL, "asm_batch_download: refs buffer too small");
-        HIPCHK(h, hipMemcpy(refs, b->d_refs, b->refs_bytes, hipMemcpyDeviceToHost));
-    }
-    return ASM_OK;
-}
-
-int64_t asm_batch_planes_size(const asm_batch* b) { return b ? (int64_t)b->planes_total : 0; }
-
-int asm_batch_download_planes(asm_handle* h, const asm_batch* b, uint32_t* planes, size_t planes_cap, uint32_t* lens,
-                              uint32_t* order) {
-    if (!h || !b) return fail(h, ASM_EINVAL, "asm_batch_download_planes: NULL argument");
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const size_t n = (size_t)b->n;
-    if (planes) {
-        if (planes_cap < 4 * b->planes_total) return fail(h, ASM_EINVAL, "asm_batch_download_planes: planes buffer too small");
-        HIPCHK(h, hipMemcpy(planes, b->d_planes, sizeof(uint4) * b->planes_total, hipMemcpyDeviceToHost));
-    }
-    if (lens && n) HIPCHK(h, hipMemcpy(lens, b->d_lens, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-    if (order && n) {
-        if (b->d_order) HIPCHK(h, hipMemcpy(order, b->d_order, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-        else
-            for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
-    }
-    return ASM_OK;
 }
 
 /* ---------------------------------------------------------------------------------------------------- */
@@ -1643,79 +1150,6 @@ int asm_accuracy_async(asm_handle* h, const int32_t* d_nw, const int32_t* d_leap
  *   compute stream   parse on the device (asm_ingest.h), pack, [sequential mode: chain the stale tails from the state the
  *                    chunks before left behind], NW / LEAP / Greedy, counters, penalties back into pinned staging
  *   caller's thread  hands results of chunk c-2 to the caller's arrays while chunk c-1 computes and chunk c is copied */
-namespace {
-using asm_host::NlScan;
-using asm_host::scan_newlines;
-
-/* Fills batch b (n pairs = 2n lines, every line ending in '\n') out of raw text already in HBM. */
-static int batch_from_device_text(asm_handle* h, const char* d_raw, size_t nbytes, asm_batch* b) {
-    const int64_t n = b->n;
-    const size_t cnt = (size_t)n + 1;
-    Scratch<uint32_t> d_nl(h), d_m(h), d_n(h), d_max(h);
-    Scratch<unsigned long long> d_sa(h), d_sb(h);
-    MapTmp tmp(h);
-    HIPCHK(h, batch_alloc(b, &b->d_read_off, sizeof(uint32_t) * cnt));
-    HIPCHK(h, batch_alloc(b, &b->d_ref_off, sizeof(uint32_t) * cnt));
-    HIPCHK(h, d_m.alloc(sizeof(uint32_t) * cnt));
-    HIPCHK(h, d_n.alloc(sizeof(uint32_t) * cnt));
-    HIPCHK(h, d_sa.alloc(sizeof(unsigned long long) * cnt));
-    HIPCHK(h, d_sb.alloc(sizeof(unsigned long long) * cnt));
-    HIPCHK(h, d_nl.alloc(sizeof(uint32_t) * (2 * (size_t)n + 2)));
-    HIPCHK(h, d_max.alloc(16));
-    HIPCHK(h, hipMemsetAsync(d_max.p, 0, 16, h->stream));
-    if (n > 0) HIPCHK(h, newline_index(h, tmp, d_raw, nbytes, (long)(2 * n), d_nl.p));
-    HIPCHK(h, launch(h, seq_lengths_kernel, grid_for(n + 1), ASM_BLOCK, (const uint32_t*)d_nl.p, (long)n, d_m.p, d_n.p, d_sa.p, d_sb.p));
-    HIPCHK(h, map_exclusive_sum(h, tmp, d_m.p, b->d_read_off, (int64_t)cnt));
-    HIPCHK(h, map_exclusive_sum(h, tmp, d_n.p, b->d_ref_off, (int64_t)cnt));
-    if (n > 0) {
-        int64_t blocks = (n + ASM_BLOCK - 1) / ASM_BLOCK;
-        blocks = blocks > 1024 ? 1024 : blocks;
-        HIPCHK(h, launch(h, seq_max_kernel, (unsigned)blocks, ASM_BLOCK, (const uint32_t*)d_m.p, (const uint32_t*)d_n.p, (long)n, d_max.p));
-    }
-    uint32_t tot[2] = {0, 0}, mx = 0;
-    HIPCHK(h, fetch(h, {fetched(&tot[0], b->d_read_off + n), fetched(&tot[1], b->d_ref_off + n), fetched(&mx, d_max.p)}));
-    if ((int)mx > ASM_MAX_LENGTH) return fail(h, ASM_EUNSUPPORTED, "streamed file: a sequence is longer than ASM_MAX_LENGTH");
-    b->reads_bytes = tot[0], b->refs_bytes = tot[1], b->maxlen = (int)mx;
-    HIPCHK(h, batch_alloc(b, &b->d_reads, b->reads_bytes + 16));
-    HIPCHK(h, batch_alloc(b, &b->d_refs, b->refs_bytes + 16));
-    if (n > 0) {
-        int64_t blocks = (n + 3) / 4;
-        blocks = blocks > 256 * 16 ? 256 * 16 : blocks;
-        HIPCHK(h, launch(h, seq_gather_kernel, (unsigned)blocks, ASM_BLOCK, d_raw, (const unsigned long long*)d_sa.p,
-                         (const uint32_t*)b->d_read_off, (long)n, b->d_reads));
-        HIPCHK(h, launch(h, seq_gather_kernel, (unsigned)blocks, ASM_BLOCK, d_raw, (const unsigned long long*)d_sb.p,
-                         (const uint32_t*)b->d_ref_off, (long)n, b->d_refs));
-    }
-    return batch_finish(h, b);
-}
-
-}  // namespace
-
-int asm_batch_from_text(asm_handle* h, const char* text, size_t nbytes, int greedy_mode, asm_batch** out) {
-    if (!h || !out || (!text && nbytes)) return fail(h, ASM_EINVAL, "asm_batch_from_text: bad argument");
-    BatchPtr b;
-    int rc = batch_new(h, 0, greedy_mode, "asm_batch_from_text", b);
-    if (rc) return rc;
-    if (nbytes >= 0xfffffff0ull) return fail(h, ASM_EUNSUPPORTED, "asm_batch_from_text: more than 4 GiB of text; split it");
-    *out = nullptr;
-    HIPCHK(h, hipSetDevice(h->device));
-    const bool open_line = nbytes && text[nbytes - 1] != '\n';
-    NlScan sc = scan_newlines(text, nbytes, 8);
-    int64_t lines = sc.count + (open_line ? 1 : 0);
-    const bool odd = (lines & 1) != 0; /* a read without its reference line: the reference gets an empty string there */
-    const size_t total = nbytes + (open_line ? 1 : 0) + (odd ? 1 : 0);
-    lines += odd ? 1 : 0;
-    Scratch<char> d_raw(h);
-    HIPCHK(h, d_raw.alloc(total + 32));
-    if (nbytes) HIPCHK(h, hipMemcpyAsync(d_raw.p, text, nbytes, hipMemcpyHostToDevice, h->stream));
-    if (total > nbytes) HIPCHK(h, hipMemsetAsync(d_raw.p + nbytes, '\n', total - nbytes, h->stream));
-    b->n = lines / 2;
-    rc = batch_from_device_text(h, d_raw.p, total, b.get());
-    if (rc) return rc;
-    *out = b.release();
-    return ASM_OK;
-}
-
 #define SEQ_TRY(call) STREAM_TRY("asm_stream_seq_file", call)
 
 extern "C++" {

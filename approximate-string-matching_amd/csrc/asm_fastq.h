@@ -5,7 +5,7 @@
 //                         sent to the mapper (1 <= m <= 511)
 //   (exclusive scans over the sent flags and the sent lengths)
 //   fastq_compact_kernel  the sent records numbered as library reads: read offsets and source positions
-//   seq_gather_kernel     (asm_ingest.h) the reads' bytes, one wave per read
+//   text_gather_kernel    (asm_ingest.h) the reads' bytes, one wave per read
 // Two files in step (asm_map_pairs_file): the chunk holds the mate-1 records and then as many mate-2 records, fastq_record_kernel
 // runs over each half, and
 //   fastq_pair_kernel          one thread per pair: sent when both mates are, the two QNAMEs compared without /1 and /2

@@ -6,7 +6,8 @@
 //   (exclusive scan of the tile counts)
 //   seq_index_kernel   byte position of every newline, in line order
 //   seq_lengths_kernel read / reference length of every pair (scanned into the batch's offset arrays)
-//   seq_gather_kernel  the strings, without markers and newlines, into the batch's two concatenated arrays
+//   text_gather_kernel the strings, without markers and newlines, into the batch's two concatenated arrays (and every other
+//                      "string i starts at start[i] of a text in HBM": FASTQ reads, the windows of seed hits)
 // after which the batch is packed like any other.  The host only counts newlines (to cut chunks at pair boundaries).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -82,15 +83,16 @@ __global__ __launch_bounds__(256) void seq_lengths_kernel(const uint32_t* __rest
     start_b[i] = (unsigned long long)(b0 + 1);
 }
 
-__global__ __launch_bounds__(256) void seq_gather_kernel(const char* __restrict__ raw, const unsigned long long* __restrict__ start,
-                                                         const uint32_t* __restrict__ off, long n, char* __restrict__ out) {
+// out[off[i], off[i + 1]) = text[start[i], ...): the launcher (launch_text_gather, asm_batch.h) owns the grid
+__global__ __launch_bounds__(256) void text_gather_kernel(const char* __restrict__ text, const unsigned long long* __restrict__ start,
+                                                          const uint32_t* __restrict__ off, long n, char* __restrict__ out) {
     const int lane = threadIdx.x & 63;
     const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
     for (long i = wave; i < n; i += nwaves) { /* one wave per string: 64 contiguous bytes per load */
         const unsigned long long s = start[i];
         const uint32_t o = off[i], len = off[i + 1] - o;
-        for (uint32_t q = (uint32_t)lane; q < len; q += 64u) out[o + q] = raw[s + q];
+        for (uint32_t q = (uint32_t)lane; q < len; q += 64u) out[o + q] = text[s + q];
     }
 }
 

@@ -171,8 +171,7 @@ static int map_file_gather(MapFileSession& ss, const char* d_raw, int64_t n, siz
     STREAM_TRY(ss.who, d_start.alloc(sizeof(unsigned long long) * ((size_t)n + 1)));
     STREAM_TRY(ss.who, compact(d_start.p));
     if (n == 0) return ASM_OK;
-    STREAM_TRY(ss.who, launch(h, seq_gather_kernel, (unsigned)std::min<int64_t>((n + 3) / 4, 256 * 16), ASM_BLOCK, d_raw,
-                              (const unsigned long long*)d_start.p, (const uint32_t*)f.d_roff.p, (long)n, f.d_reads.p));
+    STREAM_TRY(ss.who, launch_text_gather(h, d_raw, d_start.p, f.d_roff.p, n, f.d_reads.p));
     f.roff.resize((size_t)n + 1);
     STREAM_TRY(ss.who, fetch(h, {fetched(f.roff.data(), f.d_roff.p, (size_t)n + 1)}));
     return ASM_OK;

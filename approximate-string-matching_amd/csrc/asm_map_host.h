@@ -33,15 +33,7 @@ static unsigned map_grid(uint64_t n, const asm_handle* h) { /* grid-stride kerne
     return (unsigned)(want < 1 ? 1 : want > cap ? cap : want);
 }
 
-/* (launch: asm_capi.hip; fetch, hipcub's scratch MapTmp and map_exclusive_sum: asm_stream.h, which the streamed-file calls share) */
-
-template <class K, class V, class N> /* stable: equal keys keep their order */
-static hipError_t map_sort_pairs(asm_handle* h, MapTmp& tmp, K* key_in, K* key_out, V* val_in, V* val_out, N n, int end_bit) {
-    size_t bytes = 0;
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key_in, key_out, val_in, val_out, n, 0, end_bit, h->stream);
-    if (e == hipSuccess) e = tmp.reserve(bytes);
-    return e != hipSuccess ? e : hipcub::DeviceRadixSort::SortPairs(tmp.s.p, bytes, key_in, key_out, val_in, val_out, n, 0, end_bit, h->stream);
-}
+/* (launch: asm_capi.hip; fetch, hipcub's scratch MapTmp, map_exclusive_sum and map_sort_pairs: asm_batch.h, which the batch builder shares) */
 
 /* fn(std::integral_constant<int, W>) with W = the 64-bit words a read of maxm bases needs, rounded up to 1, 2, 4 or 8: the one
  * place where a read length picks an instantiation of the <W> kernels */
@@ -115,23 +107,19 @@ static int map_greedy(asm_handle* h, const asm_index* ix, const char* d_reads, c
     BatchPtr b;
     int rc = batch_new(h, nl, ASM_GREEDY_CLEAN, "asm_map_reads", b);
     if (rc) return rc;
-    const size_t cnt = (size_t)nl + 1;
+    BatchBuild bb(h, b.get(), ASM_EUNSUPPORTED, "asm_map_reads: a read is longer than ASM_MAX_LENGTH - 1"); /* map_check_args: <= 511 */
+    rc = bb.bound(maxm + 1); /* the window is at most one base longer than the read */
+    if (rc) return rc;
     Scratch<uint32_t> qlen(h), wlen(h);
-    MapTmp tmp(h);
-    HIPCHK(h, qlen.alloc(sizeof(uint32_t) * cnt));
-    HIPCHK(h, wlen.alloc(sizeof(uint32_t) * cnt));
-    HIPCHK(h, batch_alloc(b.get(), &b->d_read_off, sizeof(uint32_t) * cnt));
-    HIPCHK(h, batch_alloc(b.get(), &b->d_ref_off, sizeof(uint32_t) * cnt));
+    HIPCHK(h, qlen.alloc(sizeof(uint32_t) * ((size_t)nl + 1)));
+    HIPCHK(h, wlen.alloc(sizeof(uint32_t) * ((size_t)nl + 1)));
     HIPCHK(h, launch(h, map_greedy_lengths_kernel, grid_for(nl + 1), ASM_BLOCK, d_list, d_iread, (long)nl, d_roff, d_hits,
                      (const unsigned long long*)ix->d_seq_off, qlen.p, wlen.p));
-    HIPCHK(h, map_exclusive_sum(h, tmp, qlen.p, b->d_read_off, (int64_t)cnt));
-    HIPCHK(h, map_exclusive_sum(h, tmp, wlen.p, b->d_ref_off, (int64_t)cnt));
-    uint32_t tot[2] = {0, 0};
-    HIPCHK(h, fetch(h, {fetched(&tot[0], b->d_read_off + nl), fetched(&tot[1], b->d_ref_off + nl)}));
-    b->reads_bytes = tot[0], b->refs_bytes = tot[1];
-    b->maxlen = maxm + 1; /* the window is at most one base longer than the read */
-    HIPCHK(h, batch_alloc(b.get(), &b->d_reads, b->reads_bytes + 16));
-    HIPCHK(h, batch_alloc(b.get(), &b->d_refs, b->refs_bytes + 16));
+    rc = bb.offsets_from_lengths(BATCH_READS, qlen.p);
+    if (!rc) rc = bb.offsets_from_lengths(BATCH_REFS, wlen.p);
+    if (!rc) rc = bb.totals();
+    if (!rc) rc = bb.text_blocks();
+    if (rc) return rc;
     HIPCHK(h, launch(h, map_greedy_gather_kernel, map_grid((uint64_t)nl * 64, h), 256, d_list, d_iread, (long)nl, d_reads, d_roff, d_hits,
                      (const char*)ix->d_text, (const unsigned long long*)ix->d_seq_off, (const uint32_t*)b->d_read_off,
                      (const uint32_t*)b->d_ref_off, b->d_reads, b->d_refs));

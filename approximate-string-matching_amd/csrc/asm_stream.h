@@ -1,7 +1,7 @@
-// Device side of the streamed-file calls (asm_stream_seq_file, asm_map_file, asm_map_pairs_file): the
-// "scalars back, one wait" step that the mapper's host stages use too, hipcub's scratch and scans, the newline index of a chunk of
-// text in HBM, and the input pipeline — reader thread (asm_host.h) -> pinned slots -> copy-in stream -> two device
-// buffers -> the caller's processing on the handle's stream.  asm_capi.hip includes this file inside its extern "C" block.
+// Device side of the streamed-file calls (asm_stream_seq_file, asm_map_file, asm_map_pairs_file): their error path and the input
+// pipeline — reader thread (asm_host.h) -> pinned slots -> copy-in stream -> two device buffers -> the caller's processing on the
+// handle's stream.  ("Scalars back, one wait", hipcub's scratch and scans and the newline index of a chunk of text in HBM: asm_batch.h.)
+// asm_capi.hip includes this file inside its extern "C" block.
 #pragma once
 
 extern "C++" {
@@ -14,63 +14,6 @@ extern "C++" {
             return fail(h, _e == hipErrorOutOfMemory ? ASM_ENOMEM : ASM_ENODEVICE,               \
                         std::string(who) + ": " + #call + ": " + hipGetErrorString(_e));         \
     } while (0)
-
-/* One copy of fetch(): `bytes` from device memory into host memory */
-struct Fetch {
-    void* dst;
-    const void* src;
-    size_t bytes;
-};
-template <class T>
-static Fetch fetched(T* dst, const T* src, size_t count = 1) {
-    return {dst, src, sizeof(T) * count};
-}
-/* "Scan, then read the totals": the copies to the host on the handle's stream, in order, and then one wait for all of them */
-static hipError_t fetch(asm_handle* h, std::initializer_list<Fetch> what) {
-    for (const Fetch& f : what)
-        if (const hipError_t e = hipMemcpyAsync(f.dst, f.src, f.bytes, hipMemcpyDeviceToHost, h->stream)) return e;
-    return hipStreamSynchronize(h->stream);
-}
-
-/* hipcub's temporary storage: grows to the largest request; the old block goes back to the pool in stream order */
-struct MapTmp {
-    Scratch<void> s;
-    size_t cap = 0;
-    explicit MapTmp(asm_handle* h) : s(h) {}
-    hipError_t reserve(size_t bytes) {
-        if (s.p && bytes <= cap) return hipSuccess;
-        pool_free(s.h, s.p);
-        s.p = nullptr, cap = bytes;
-        return s.alloc(bytes + 16);
-    }
-};
-
-/* hipcub's two-phase calls on the handle's stream: query the temporary size, reserve it, run */
-template <class T>
-static hipError_t map_exclusive_sum(asm_handle* h, MapTmp& tmp, T* in, T* out, int64_t n) {
-    size_t bytes = 0;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, h->stream);
-    if (e == hipSuccess) e = tmp.reserve(bytes);
-    return e != hipSuccess ? e : hipcub::DeviceScan::ExclusiveSum(tmp.s.p, bytes, in, out, (int)n, h->stream);
-}
-
-/* d_nl[l] = the position of the l-th newline of d_raw[0, nbytes), for the first `lines` of them (asm_ingest.h); d_tbase: per tile of
- * SEQ_TILE bytes, the newlines before it */
-static hipError_t newline_index(asm_handle* h, MapTmp& tmp, const char* d_raw, size_t nbytes, long lines, uint32_t* d_nl,
-                                Scratch<uint32_t>& d_tbase) {
-    const long ntiles = (long)((nbytes + SEQ_TILE - 1) / SEQ_TILE);
-    Scratch<uint32_t> d_tile(h);
-    hipError_t e = d_tile.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1));
-    if (e == hipSuccess) e = d_tbase.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1));
-    if (e == hipSuccess) e = launch(h, seq_count_kernel, (unsigned)ntiles, 256, d_raw, (long)nbytes, d_tile.p);
-    if (e == hipSuccess) e = map_exclusive_sum(h, tmp, d_tile.p, d_tbase.p, (int64_t)ntiles);
-    if (e != hipSuccess) return e;
-    return launch(h, seq_index_kernel, (unsigned)ntiles, 256, d_raw, (long)nbytes, (const uint32_t*)d_tbase.p, d_nl, lines);
-}
-static hipError_t newline_index(asm_handle* h, MapTmp& tmp, const char* d_raw, size_t nbytes, long lines, uint32_t* d_nl) {
-    Scratch<uint32_t> d_tbase(h);
-    return newline_index(h, tmp, d_raw, nbytes, lines, d_nl, d_tbase);
-}
 
 /* The input side of one streamed call: the file, the copy-in stream, three pinned slots in rotation (the reader thread fills them),
  * two device buffers that the handle's stream reads, and the events between them.  The destructor waits for the streams and gives

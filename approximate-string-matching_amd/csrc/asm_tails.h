@@ -103,7 +103,7 @@ __device__ __forceinline__ void tail_walk(const uint4* __restrict__ planes, cons
     }
 }
 
-// Scratch layout (asm_capi.hip: batch_resolve_tails): loc[nchunks_padded][2] = a chunk's exclusive prefix inside its workgroup,
+// Scratch layout (asm_batch.h: batch_resolve_tails): loc[nchunks_padded][2] = a chunk's exclusive prefix inside its workgroup,
 // grp[ngroups][2] = a workgroup's total, gcarry[ngroups][2][2] = the buffers' planes S0, S1 before a workgroup's first pair.
 __global__ __launch_bounds__(2 * TAIL_GROUP) void tails_chunk_kernel(const uint4* __restrict__ planes,
                                                                      const uint32_t* __restrict__ lens, long n,

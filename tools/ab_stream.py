@@ -83,7 +83,7 @@ def main():
 
     # ---- the two files
     from tools.bench_map_file import write_files
-    fa, fq = write_files(types.SimpleNamespace(dir=a.dir, ref_len=5e6, reads=1e6, len=100), 2)
+    fa, (fq,) = write_files(types.SimpleNamespace(dir=a.dir, ref_len=5e6, reads=1e6, len=100, paired=False), 2)
     import approximate_string_matching_amd as m
     n = int(a.pairs)
     seq = os.path.join(a.dir, "pairs_C2_%d.seq" % n)
