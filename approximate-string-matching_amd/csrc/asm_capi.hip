@@ -28,6 +28,7 @@
 
 #include "../../include/asm_mi355x.h"
 #include "asm_launch.h"
+#include "asm_plan.h"
 #include "asm_host.h"
 #include "asm_kernels.h"
 #include "asm_greedy3_kernel.h"
@@ -332,23 +333,6 @@ static int for_each_bucket(const asm_batch* b, int32_t* out, F one) {
     return ASM_OK;
 }
 
-// Persistent launch: grid = what is resident (CUs x occupancy); each wave owns a static slice of the batch.
-template <typename Kern, typename... Args>
-static hipError_t launch_persistent(asm_handle* h, Kern kern, int64_t n, Args... args) {
-    int per_cu = 1;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, ASM_BLOCK, 0);
-    if (e != hipSuccess) return e;
-    if (per_cu < 1) per_cu = 1;
-    int64_t blocks = (int64_t)per_cu * h->num_cus;
-    const int64_t need = (n + ASM_BLOCK - 1) / ASM_BLOCK;
-    if (blocks > need) blocks = need;
-    return launch(h, kern, (unsigned)blocks, ASM_BLOCK, args...);
-}
-
-#ifdef GREEDY_DIAG
-static void* g_diag_buf = nullptr; /* diagnostic build only (never the shipped library): per-wave cycle stamps of the Greedy kernel */
-extern "C" void asm_diag_set_buffer(void* d) { g_diag_buf = d; }
-#endif
 /* Rank table of the straight-line Greedy kernel for these significance constants (asm_greedy3.h): built on the host with the
  * reference build's three roundings, uploaded once per (constants, k).  False when the constants do not have the structure
  * the integer keys need (then the FP64 kernel runs). */
@@ -383,209 +367,6 @@ static bool g3_prepare(asm_handle* h, const GreedyArgs& ga, int K) {
     h->g3_tables.push_back(t);
     h->d_g3_table = t.d;
     return t.ok;
-}
-
-template <int K>
-static hipError_t launch_greedy_fast(asm_handle* h, const asm_bucket& b, const GreedyArgs& ga, OutMap out, CigarSink cig) {
-    /* One 512-thread workgroup per CU = two waves per SIMD.  The waves of a SIMD are served oldest first and this kernel is a
-     * dense stream of 4-cycle vector operations, so a third wave adds little issue rate and a third more lanes to drain at the
-     * end: stand-alone 1 / 2 / 3 waves take 130 / 118 / 107 us, inside asm_run_benchmark_async's overlapped step 0.234 / 0.227 /
-     * 0.244 ms per step (1.5 and 2.5 waves: 0.237, —).  The other instantiations were removed in round 4 (last in 312851a). */
-    constexpr int NT = G3_THREADS;
-    int64_t blocks = h->num_cus; /* one workgroup per CU (LDS: the table alone is 33 KB, with the lane vectors above 64 KB at every K) */
-    const int64_t need = (b.n + NT - 1) / NT;
-    if (blocks > need) blocks = need;
-    const G3Sig sig = {ga.sig_match, ga.sig_mismatch, ga.sig_indel};
-    return launch_lds(h, greedy_fast_kernel<K, NT>, (unsigned)blocks, NT, g3_lds_bytes(K, NT), (const uint4*)b.planes,
-                      (const uint32_t*)b.lens, (long)b.n, b.w4, sig, h->d_g3_table, out, cig, h->refill_greedy);
-}
-
-/* Thread-per-pair Greedy, k <= 16: the straight-line integer-key kernel for the benchmark's own configuration (k <= 3, unit
- * penalties, GLOBAL), the FP64 lane-refilling kernel for everything else (unit and general penalties, GLOBAL and SEMI_GLOBAL:
- * at k = 8 with (2,3,1) 0.27 ms per 10^6 pairs against 0.87 for the wave-per-pair kernel). */
-template <int K>
-static hipError_t launch_greedy(asm_handle* h, const asm_bucket& b, const GreedyArgs& ga, OutMap out, CigarSink cig) {
-#ifdef GREEDY_DIAG
-    if (cig.ops == nullptr && g_diag_buf) cig.nops = (uint8_t*)g_diag_buf;
-#endif
-    const bool unit = ga.x == 1 && ga.o == 1 && ga.e == 1 && !ga.semi;
-    if constexpr (K <= 3) {
-        if (h->greedy_fast && unit && g3_prepare(h, ga, K)) return launch_greedy_fast<K>(h, b, ga, out, cig);
-    }
-    if (unit)
-        return launch_persistent(h, greedy_persist_kernel<K, true>, b.n, (const uint4*)b.planes, (const uint32_t*)b.lens,
-                                 (long)b.n, b.w4, ga, out, cig, h->refill_greedy);
-    return launch_persistent(h, greedy_persist_kernel<K, false>, b.n, (const uint4*)b.planes, (const uint32_t*)b.lens,
-                             (long)b.n, b.w4, ga, out, cig, h->refill_greedy);
-}
-
-#define LEAP_UNIT_WIDE_K 5 /* thread-per-pair unit-cost LEAP at every string length up to this band */
-#define LEAP_UNIT_MAX_K 10 /* ... and for strings of one granule (<= 128 characters) up to this one (k = 12: 0.148 ms against
-                              0.180 at C2, but 0.120 against 0.104 at C4's 2.5 % errors, where four threads per pair have little to do) */
-template <int K, int W64>
-static hipError_t launch_leap_unit_w(asm_handle* h, const asm_bucket& b, OutMap out, const int32_t* hint) {
-    if (hint && h->leap_hint)
-        return launch(h, leap_unit_hint_kernel<K, W64>, (unsigned)((b.n + LEAP_HINT_PAIRS - 1) / LEAP_HINT_PAIRS), ASM_BLOCK, b.planes,
-                      b.lens, (long)b.n, b.w4, out, hint);
-    return launch(h, leap_unit_kernel<K, W64>, grid_for(b.n), ASM_BLOCK, b.planes, b.lens, (long)b.n, b.w4, out);
-}
-
-template <int K, int W64>
-static hipError_t launch_leap_general_w(asm_handle* h, const asm_bucket& b, const asm_params* p, OutMap out) {
-    const unsigned grid = (unsigned)((b.n + LEAP_GEN_THREADS - 1) / LEAP_GEN_THREADS);
-    const LvRings rg = LvRings::pow2(p->x, p->o, p->e);
-    /* bytes (every stored position + 2 fits) halve the LDS and double the waves per CU, but four threads then write into one
-     * dword: worth it only where shorts would leave the CU underfilled */
-    const bool bytes = b.maxlen + 4 <= 255 && rg.ring_bytes(2 * K + 1, LEAP_GEN_THREADS, 2) > 20 * 1024;
-    const auto go = [&](auto kernel, size_t entry_bytes) {
-        return launch_lds(h, kernel, grid, LEAP_GEN_THREADS, rg.ring_bytes(2 * K + 1, LEAP_GEN_THREADS, entry_bytes), b.planes, b.lens,
-                          (long)b.n, b.w4, (int)p->x, (int)p->o, (int)p->e, rg.gm, rg.gi, out);
-    };
-    return bytes ? go(leap_general_kernel<K, W64, uint8_t>, 1) : go(leap_general_kernel<K, W64, uint16_t>, 2);
-}
-
-/* Affine NW: banded wavefront pass (|d| <= 7), a second one with |d| <= 15 over the pairs the first could not settle
- * (strings up to 128 only), then the full-matrix kernel over what is left.  Two todo lists of n + 1 words each. */
-template <int K, int W64, typename EnT>
-static hipError_t launch_nw_wfa_pass(asm_handle* h, const asm_bucket& b, const asm_params* p, OutMap out, const uint32_t* in_list,
-                                     const uint32_t* in_count, uint32_t* todo, uint32_t* todo_count) {
-    const LvRings rg = LvRings::exact(p->x, p->o, p->e);
-    return launch_lds(h, nw_wfa_kernel<K, W64, EnT, false>, (unsigned)((b.n + LEAP_GEN_THREADS - 1) / LEAP_GEN_THREADS), LEAP_GEN_THREADS,
-                      rg.ring_bytes(2 * K + 1, LEAP_GEN_THREADS, sizeof(EnT)), b.planes, b.lens, (long)b.n, b.w4, (int)p->x, (int)p->o,
-                      (int)p->e, rg.gm, rg.gi, out, in_list, in_count, todo, todo_count);
-}
-
-template <int W64, int MAXROWS>
-static int launch_nw_wfa(asm_handle* h, const asm_bucket& b, const asm_params* p, OutMap out) {
-    if (const int rc = grow_device(h, h->d_todo, h->todo_cap, 2 * ((size_t)b.n + 1))) return rc;
-    uint32_t* const list_a = h->d_todo;                 /* [0] = count, [1..] = pair slots */
-    uint32_t* const list_b = h->d_todo + (size_t)b.n + 1;
-    HIPCHK(h, hipMemsetAsync(list_a, 0, sizeof(uint32_t), h->stream));
-    HIPCHK(h, hipMemsetAsync(list_b, 0, sizeof(uint32_t), h->stream));
-    const LvRings rg = LvRings::exact(p->x, p->o, p->e);
-    bool bytes = false; /* strings up to 128: every stored position + 2 fits a byte, half the LDS */
-    if constexpr (W64 == 2) {
-        bytes = true;
-        HIPCHK(h, (launch_nw_wfa_pass<NW_WFA_K, 2, uint8_t>(h, b, p, out, nullptr, nullptr, list_a + 1, list_a)));
-    }
-    if (!bytes) HIPCHK(h, (launch_nw_wfa_pass<NW_WFA_K, W64, uint16_t>(h, b, p, out, nullptr, nullptr, list_a + 1, list_a)));
-    const uint32_t* rest = list_a;
-    const size_t en = b.maxlen + 2 <= 255 ? 1 : 2;
-    const size_t oct_lds = rg.quad_lds(NW_OCT_PAIRS, 2 * W64, NW_WFA_K2, en);
-    if (oct_lds <= 64 * 1024) {
-        /* the unsettled percent or two: eight threads per pair, |d| <= 15 (asm_wave.h) */
-        const unsigned grid = (unsigned)std::min<int64_t>((b.n + NW_OCT_PAIRS - 1) / NW_OCT_PAIRS, (int64_t)h->num_cus * 16);
-        const auto oct = [&](auto kernel) {
-            return launch_lds(h, kernel, grid, NW_OCT_THREADS, oct_lds, b.planes, b.lens,
-                              (long)b.n, b.w4, NW_WFA_K2, (int)p->x, (int)p->o, (int)p->e, rg.gm, rg.gi, out, list_a + 1, list_a,
-                              list_b + 1, list_b);
-        };
-        HIPCHK(h, en == 1 ? oct(nw_oct_kernel<2 * W64, uint8_t>) : oct(nw_oct_kernel<2 * W64, uint16_t>));
-        rest = list_b;
-    }
-    HIPCHK(h, launch(h, nw_affine_kernel<W64, MAXROWS>, (unsigned)((b.n + 63) / 64), 64, b.planes, b.lens, (long)b.n, b.w4, (int)p->x,
-                     (int)p->o, (int)p->e, out, rest + 1, rest));
-    return ASM_OK;
-}
-
-template <int K>
-static hipError_t launch_leap_general(asm_handle* h, const asm_bucket& b, const asm_params* p, OutMap out) {
-    constexpr int GMAX = K <= 5 ? 2 : 1; /* granules: bands 6..8 come here for strings of one granule only (align_bucket) */
-    if (b.maxlen > 128 * GMAX) return hipErrorInvalidValue; /* not reached */
-    return with_const<1, GMAX>((b.maxlen + 127) / 128, [&](auto g) { return launch_leap_general_w<K, 2 * decltype(g)::value>(h, b, p, out); });
-}
-
-template <int K>
-static hipError_t launch_leap_unit(asm_handle* h, const asm_bucket& b, OutMap out, const int32_t* hint) {
-    /* 64-bit words per string, one instantiation per count up to six (C5's longest class, 257-300, on five words); the wider
-     * bands (6..10 lanes each side) are kept in registers for one granule only */
-    constexpr int WMAX = K <= LEAP_UNIT_WIDE_K ? 6 : 2;
-    if (b.maxlen > 64 * WMAX) return hipErrorInvalidValue; /* not reached: align_bucket sends such buckets to the four-threads-per-pair kernel */
-    return with_const<2, WMAX>((b.maxlen + 63) / 64, [&](auto w) { return launch_leap_unit_w<K, decltype(w)::value>(h, b, out, hint); });
-}
-
-/* Full-matrix Gotoh + traceback + coverage verdict (nw_trace_affine_kernel) over `count` slots of a bucket slice: the slots
- * listed in d_list (bucket-slice indices), or slots 0..count-1 when d_list is null.  Scratch: 4 direction bits per cell. */
-static int cover_full_matrix(asm_handle* h, const asm_bucket& b, const asm_params* p, const uint4* planes, const uint32_t* lens,
-                             const uint32_t* order, long slice_lo, const uint32_t* d_list, int64_t count, const CoverArgs& ca) {
-    if (count <= 0) return ASM_OK;
-    const int rows = b.maxlen > 0 ? b.maxlen : 1, cols8 = (rows + 7) / 8;
-    const size_t per_pair = (size_t)rows * (size_t)cols8 * sizeof(uint32_t);
-    int64_t chunk = (int64_t)((size_t)(6ull << 30) / per_pair);
-    chunk = chunk < 64 ? 64 : chunk;
-    chunk = chunk > count ? count : chunk;
-    BigScratch<uint32_t> d_scratch;
-    HIPCHK(h, d_scratch.alloc(h, per_pair * (size_t)chunk));
-    for (int64_t lo = 0; lo < count; lo += chunk) {
-        const int64_t c = count - lo < chunk ? count - lo : chunk;
-        /* without a list the chunk is a contiguous run of slots: shift the base pointers like cover_bucket does */
-        const uint4* pl = d_list ? planes : planes + lo;
-        const uint32_t* ln = d_list ? lens : lens + lo;
-        const uint32_t* od = (d_list || !order) ? order : order + lo;
-        const long base = d_list ? slice_lo : slice_lo + lo;
-        const uint32_t* list = d_list ? d_list + lo : nullptr;
-        const hipError_t e = with_const_of<2, 4, 8>((b.maxlen + 63) / 64, [&](auto w) { /* 64-bit words per string; rows = positions they hold */
-            constexpr int W64 = decltype(w)::value;
-            return launch(h, nw_trace_affine_kernel<W64, 64 * W64>, (unsigned)((c + 63) / 64), 64, pl, ln, (long)c, (long)b.n, b.w4,
-                          (int)p->x, (int)p->o, (int)p->e, d_scratch.p, cols8, list, od, base, ca);
-        });
-        if (e != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
-            return fail(h, ASM_ENODEVICE, "asm_coverage: full-matrix traceback kernel failed");
-    }
-    return ASM_OK;
-}
-
-/* forward sweep + traceback/coverage for one width class with window W; pairs the band cannot answer go through the
- * full-matrix pass */
-template <int ND, int W>
-static int cover_bucket(asm_handle* h, const asm_bucket& b, const asm_params* p, const CoverArgs& ca) {
-    typedef typename TraceCell<W>::T Cell;
-    if (b.n == 0) return ASM_OK;
-    // scratch: [column][pair]; processed in slices of pairs so that it stays below ~6 GiB
-    const int64_t cols = b.maxlen > 0 ? b.maxlen : 1;
-    int64_t slice = (int64_t)(6ll << 30) / (cols * (int64_t)sizeof(Cell));
-    slice = slice > b.n ? b.n : (slice < 4096 ? 4096 : slice);
-    if (const int rc = grow_device(h, h->d_todo, h->todo_cap, (size_t)slice + 1)) return rc;
-    BigScratch<Cell> d_trace;
-    BigScratch<int32_t> d_band;
-    HIPCHK(h, d_trace.alloc(h, (size_t)cols * (size_t)slice * sizeof(Cell)));
-    if (d_band.alloc(h, sizeof(int32_t) * (size_t)slice) != hipSuccess) return fail(h, ASM_ENOMEM, "asm_coverage: hipMalloc failed");
-    for (int64_t lo = 0; lo < b.n; lo += slice) {
-        const int64_t cnt = b.n - lo < slice ? b.n - lo : slice;
-        // a slice is addressed as a sub-batch: plane rows keep the bucket's stride, so pass shifted base pointers
-        const uint4* planes = b.planes + lo;
-        const uint32_t* lens = b.lens + lo;
-        const uint32_t* order = b.order ? b.order + lo : nullptr;
-        uint32_t todo_count = 0;
-        if (hipMemsetAsync(h->d_todo, 0, sizeof(uint32_t), h->stream) != hipSuccess) return fail(h, ASM_ENODEVICE, "asm_coverage: memset failed");
-        // the kernels index planes as [(p*w4+g)*n + i] with n = pairs of the BUCKET: use dedicated strided variants
-        if (launch(h, nw_trace_forward_kernel<ND, W>, grid_for(cnt), ASM_BLOCK, planes, lens, (long)cnt, (long)b.n, b.w4, d_trace.p,
-                   d_band.p) != hipSuccess ||
-            launch(h, nw_trace_cover_kernel<ND / 2, W>, grid_for(cnt), ASM_BLOCK, planes, lens, (long)cnt, (long)b.n, b.w4, d_trace.p,
-                   d_band.p, order, lo, ca, h->d_todo + 1, h->d_todo) != hipSuccess ||
-            hipMemcpyAsync(&todo_count, h->d_todo, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-            hipStreamSynchronize(h->stream) != hipSuccess)
-            return fail(h, ASM_ENODEVICE, "asm_coverage: kernel failed");
-        if (todo_count)
-            if (const int rc = cover_full_matrix(h, b, p, planes, lens, order, lo, h->d_todo + 1, (int64_t)todo_count, ca)) return rc;
-    }
-    return ASM_OK;
-}
-
-/* SIMD_ED events of one bucket (asm_filter.h) */
-static int launch_simd_ed_events(asm_handle* h, const asm_bucket& b, int T, int shd, OutMap ev, int ed_mode) {
-    const unsigned grid = (unsigned)((b.n + SIMD_ED_THREADS - 1) / SIMD_ED_THREADS);
-    HIPCHK(h, (with_const_of<2, 4>((b.maxlen + 63) / 64, [&](auto w) {
-               constexpr int W64 = decltype(w)::value;
-               if (T <= ASM_FILTER_REG_MAX_T && ed_mode != 1 && ed_mode != 2) /* every lane live from generation 0; else: run-time form */
-                   return with_const<1, ASM_FILTER_REG_MAX_T>(T, [&](auto t) {
-                       return launch(h, simd_ed_kernel<decltype(t)::value, W64>, grid, SIMD_ED_THREADS, b.planes, b.lens, (long)b.n, b.w4,
-                                     T, shd, 0, ev);
-                   });
-               const size_t lds = (size_t)2 * (2 * T + 3) * SIMD_ED_THREADS * sizeof(short);
-               return launch_lds(h, simd_ed_kernel<0, W64>, grid, SIMD_ED_THREADS, lds, b.planes, b.lens, (long)b.n, b.w4, T, shd, ed_mode, ev);
-           })));
-    return ASM_OK;
 }
 
 extern "C" {
@@ -736,381 +517,14 @@ int asm_generate_pairs(const asm_gen_config* cfg, int64_t first, int64_t n, uint
 }
 
 /* ---------------------------------------------------------------------------------------------------- */
+/* the parameter rules (check_params_rule, asm_plan.h) on this library's error path */
 static int check_params(asm_handle* h, int aligner, const asm_params* p, int maxlen = ASM_MAX_LENGTH) {
-    if (!p) return fail(h, ASM_EINVAL, "params is NULL");
-    if (p->x < 0 || p->o < 0 || p->e < 0) return fail(h, ASM_EINVAL, "penalties must be non-negative");
-    if (aligner == ASM_GREEDY) {
-        if (p->k < 0 || p->k > ASM_GREEDY_MAX_K) return fail(h, ASM_EINVAL, "Greedy: k must be in [0, 50] (MAX_K, hurdle_matrix.h:8)");
-        if (!(p->p_match > 0 && p->p_mismatch > 0 && p->p_indel > 0)) return fail(h, ASM_EINVAL, "Greedy: probabilities must be positive");
-        if (p->alignment_type != ASM_ALIGN_GLOBAL && p->alignment_type != ASM_ALIGN_SEMI_GLOBAL)
-            return fail(h, ASM_EUNSUPPORTED, "Greedy: alignment type must be GLOBAL or SEMI_GLOBAL (LOCAL is unsupported in the reference too, hurdle_matrix.h:467)");
-    } else if (aligner == ASM_LEAP) {
-        if (p->k < 0 || p->k > ASM_WIDE_MAX_K) return fail(h, ASM_EINVAL, "LEAP: k out of range");
-        /* the recurrence reads generation e-o / e-ext / e-x: zero penalties would be same-generation reads,
-         * and LV_BAG.cpp:165 assumes open >= extend */
-        if (p->x < 1 || p->o < 1 || p->e < 1 || p->o < p->e)
-            return fail(h, ASM_EINVAL, "LEAP: need x >= 1, o >= e >= 1 (LV_BAG.cpp:165-166)");
-        if (p->x > ASM_WIDE_MAX_PENALTY || p->o > ASM_WIDE_MAX_PENALTY)
-            return fail(h, ASM_EUNSUPPORTED, "LEAP: penalties above the compiled history depth");
-        if (p->leap_mode < ASM_LEAP_GLOBAL || p->leap_mode > ASM_LEAP_SEMI_FREE_END)
-            return fail(h, ASM_EINVAL, "LEAP: leap_mode must be one of ASM_LEAP_GLOBAL/LOCAL/SEMI_FREE_BEGIN/SEMI_FREE_END");
-        if (p->leap_mode != ASM_LEAP_GLOBAL && maxlen > 512)
-            return fail(h, ASM_EUNSUPPORTED, "LEAP: the non-GLOBAL modes are built for strings up to 512 characters");
-    } else if (aligner == ASM_NW) {
-        /* nw_affine_kernel keeps H/E/F below NW_BIG (int16 halves of one dword at the block boundary): every cell is at most
-         * gap(i) + gap(j), and E/F one gap-open above that */
-        const long worst = 2L * ((long)p->o + (long)(maxlen > 0 ? maxlen - 1 : 0) * (long)p->e) + (long)p->o;
-        if (p->x > 10000 || p->o > 10000 || p->e > 10000 || worst >= (long)NW_BIG)
-            return fail(h, ASM_EUNSUPPORTED, "NW: penalties too large for this batch's longest sequence "
-                                             "(need 2*(o + (maxlen-1)*e) + o < 30000 and x, o, e <= 10000)");
-    } else {
-        return fail(h, ASM_EINVAL, "unknown aligner id");
-    }
-    return ASM_OK;
+    const ParamVerdict v = check_params_rule(aligner, p, maxlen);
+    return v.code ? fail(h, v.code, v.msg) : ASM_OK;
 }
 
-/* one aligner over one width class */
-static int align_bucket(asm_handle* h, const asm_bucket& b, int aligner, const asm_params* p, OutMap out, CigarSink cig,
-                        const int32_t* hint) {
-    if (b.n == 0) return ASM_OK;
-    const bool unit = (p->x == 1 && p->o == 1 && p->e == 1);
-    const uint4* planes = b.planes;
-    const uint32_t* lens = b.lens;
-    if (aligner == ASM_GREEDY) {
-        GreedyArgs ga;
-        ga.x = p->x, ga.o = p->o, ga.e = p->e;
-        ga.semi = p->alignment_type == ASM_ALIGN_SEMI_GLOBAL ? 1 : 0;
-        ga.sig_match = log(p->p_match / 0.25); /* hurdle_matrix.h:536-538 */
-        ga.sig_mismatch = log(p->p_mismatch / 0.25);
-        ga.sig_indel = log(p->p_indel / 2 / 0.25);
-        if (p->k >= 1 && p->k <= 16) {
-            /* thread per pair (launch_greedy).  K = 17, 18 still win at 100 bp (0.71, 0.79 ms against 0.90) but lose at 150 bp,
-             * err 0.20 (1.67, 1.83 against 1.60) */
-            HIPCHK(h, (with_const<1, 16>((int)p->k, [&](auto k) { return launch_greedy<decltype(k)::value>(h, b, ga, out, cig); })));
-        } else if (h->wave_kernels && p->k >= 32 && p->k <= 39 && (long)p->o + 110L * p->e < 16000L) {
-            /* 65..79 band lanes: sixteen threads per pair, five lanes each (asm_group.h): 1.78 ms per 10^6 C2 pairs
-             * against 2.25 ms for the two-wavefront kernel */
-            HIPCHK(h, launch_greedy_group(h->stream, planes, lens, b.n, b.w4, (int)p->k, ga, out, cig, h->num_cus));
-        } else if (p->k <= ASM_WAVE_MAX_K && h->wave_kernels && unit && !ga.semi) {
-            HIPCHK(h, hipMemsetAsync(h->d_pair_queue, 0, sizeof(unsigned long long), h->stream));
-            HIPCHK(h, launch_wave_per_pair(h->stream, greedy_wave_kernel<true>, b.n, h->num_cus, planes, lens, (long)b.n, b.w4, (int)p->k,
-                                           ga, out, cig, h->d_pair_queue, (const uint32_t*)nullptr, (const uint32_t*)nullptr));
-        } else if (p->k <= ASM_WAVE_MAX_K && h->wave_kernels && (long)p->o + 62L * p->e < 16000L) {
-            HIPCHK(h, hipMemsetAsync(h->d_pair_queue, 0, sizeof(unsigned long long), h->stream));
-            HIPCHK(h, launch_wave_per_pair(h->stream, greedy_wave_kernel<false>, b.n, h->num_cus, planes, lens, (long)b.n, b.w4, (int)p->k,
-                                           ga, out, cig, h->d_pair_queue, (const uint32_t*)nullptr, (const uint32_t*)nullptr));
-        } else if (h->wave_kernels && (long)p->o + 100L * p->e < 16000L)
-            HIPCHK(h, launch_greedy_wave2(h->stream, planes, lens, b.n, b.w4, (int)p->k, ga, out, cig, h->num_cus));
-        else
-            HIPCHK(h, launch_greedy_wide(h->stream, planes, lens, b.n, b.w4, p->k, ga, out, cig));
-    } else if (aligner == ASM_LEAP) {
-        const LvRings quad_rg = unit ? LvRings::unit() : LvRings::pow2(p->x, p->o, p->e); /* leap_quad_kernel's rings (LEAP penalties are at most 15) */
-        if (p->leap_mode != ASM_LEAP_GLOBAL) {
-            /* LV's other ED_modes have no caller in the reference: one kernel serves them, the workgroup-per-pair form that takes
-             * any band and any penalties (asm_wide.h) */
-            HIPCHK(h, launch_leap_wide(h->stream, planes, lens, b.n, b.w4, p->k, p->x, p->o, p->e, out, (int)p->leap_mode));
-        } else if (unit && p->k >= 1 && ((p->k <= LEAP_UNIT_WIDE_K && b.maxlen <= 384) || (p->k <= LEAP_UNIT_MAX_K && b.maxlen <= 128))) {
-            /* thread per pair, band lanes in registers: k <= 5 at any length; k = 6..10 for strings of one granule, where the
-             * four-threads-per-pair kernel is 1.6-2 x slower (C2, 10^6 pairs, k = 6 / 8 / 10: 0.085 / 0.089 / 0.111 ms against
-             * 0.174 / 0.181 / 0.180) */
-            HIPCHK(h, (with_const<1, LEAP_UNIT_MAX_K>((int)p->k,
-                                                     [&](auto k) { return launch_leap_unit<decltype(k)::value>(h, b, out, hint); })));
-        } else if (!unit && p->k >= 1 && ((p->k <= 5 && b.maxlen <= 256) || (p->k <= 8 && b.maxlen <= 128)) && h->wave_kernels &&
-                   LvRings::pow2(p->x, p->o, p->e).ring_bytes(2 * p->k + 1, LEAP_GEN_THREADS, sizeof(uint16_t)) <= 64 * 1024) {
-            /* general penalties, narrow band: thread per pair with an LDS generation ring */
-            HIPCHK(h, (with_const<1, 8>((int)p->k, [&](auto k) { return launch_leap_general<decltype(k)::value>(h, b, p, out); })));
-        } else if (h->wave_kernels && b.maxlen <= 512 &&
-                   quad_rg.quad_lds(LEAP_QUAD_PAIRS, (b.maxlen + 31) / 32, (int)p->k, b.maxlen + 2 <= 255 ? 1 : 2) <= 64 * 1024) {
-            /* wide band: four threads per pair, generation rings and planes in LDS (asm_wave.h) */
-            const int w32 = (b.maxlen + 31) / 32;
-            const int32_t* const qhint = h->leap_hint ? hint : nullptr;
-            /* long-running cases (long strings or general penalties): sort the whole bucket by the hint — one 6-bit radix pass —
-             * and let every single-wave workgroup take sixteen neighbours of the order; short ones sort inside the workgroup */
-            const uint32_t* qperm = nullptr;
-            if (qhint && h->leap_sort && (b.maxlen > 128 || !unit)) {
-                const size_t n = (size_t)b.n;
-                size_t tmp_bytes = 0;
-                HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (uint8_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr,
-                                                             (uint32_t*)nullptr, (int)n, 0, 6, h->stream));
-                const size_t need = 2 * n + 8 * n + tmp_bytes + 256; /* keys, keys', idx, perm, temp */
-                if (const int rc = grow_device(h, h->d_sort, h->sort_cap, need)) return rc;
-                uint32_t* const d_idx = (uint32_t*)h->d_sort;
-                uint32_t* const d_perm = d_idx + n;
-                uint8_t* const d_keys = (uint8_t*)(d_perm + n);
-                uint8_t* const d_keys2 = d_keys + n;
-                void* const d_tmp = (void*)(((uintptr_t)(d_keys2 + n) + 255) & ~(uintptr_t)255);
-                const int div = unit ? 1 : (int)(p->e < p->x ? p->e : p->x);
-                HIPCHK(h, launch(h, leap_sort_keys_kernel, (unsigned)((n + 255) / 256), 256, qhint, out, (long)n, div, d_keys, d_idx));
-                HIPCHK(h, hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_keys, d_keys2, d_idx, d_perm, (int)n, 0, 6, h->stream));
-                qperm = d_perm;
-            }
-            const auto quad = [&](auto w, auto en) { /* W 32-bit words per string; ring entries of en's type */
-                return launch_leap_quad<decltype(w)::value, decltype(en)>(h->stream, planes, lens, b.n, b.w4, (int)p->k, unit, (int)p->x,
-                                                                          (int)p->o, (int)p->e, quad_rg, out, qhint, qperm);
-            };
-            HIPCHK(h, (with_const_of<4, 5, 6, 8, 12, 16>(w32, [&](auto w) {
-                       return b.maxlen + 2 <= 255 ? quad(w, uint8_t{}) : quad(w, uint16_t{}); /* every stored position + 2 fits a byte */
-                   })));
-        } else {
-            HIPCHK(h, launch_leap_wide(h->stream, planes, lens, b.n, b.w4, p->k, p->x, p->o, p->e, out));
-        }
-    } else {
-        if (unit) {
-            /* The one w4 -> kernel mapping of unit-cost NW.  A width class of w4 granules has ND = 4 * w4 plane dwords = 2 * w4
-             * 64-bit words per string: full height is nw_unit_kernel<2 * w4>, banded nw_banded_kernel<ND, first window, SORT>
-             * with a first window of 32 rows for one granule and 64 above. */
-            const unsigned g = grid_for(b.n);
-            const long n = (long)b.n;
-            const auto banded = [&](auto sort, unsigned grid) {
-                return with_const<1, 4>(b.w4, [&](auto w) {
-                    constexpr int W4 = decltype(w)::value;
-                    return launch(h, nw_banded_kernel<4 * W4, (W4 == 1 ? 32 : 64), decltype(sort)::value>, grid, ASM_BLOCK, planes, lens, n,
-                                  b.w4, out);
-                });
-            };
-            if (!h->nw_banded) {
-                HIPCHK(h, (with_const<1, 4>(b.w4, [&](auto w) {
-                           return launch(h, nw_unit_kernel<2 * decltype(w)::value>, g, ASM_BLOCK, planes, lens, n, b.w4, out);
-                       })));
-            } else if (b.mixed && h->nw_bylen) { /* a width class of a mixed-length batch: workgroup-local sort by length */
-                /* (measured and dropped in round 4: ONE wave per 256-pair sort window working through its four length quartiles in
-                 * turn, so that every wave of the grid gets the same mix — C5, 10^7 pairs: 2.16-2.21 ms against 2.12 for this form;
-                 * the dispatcher does not pile the long quartiles on one SIMD) */
-                HIPCHK(h, banded(std::true_type{}, (unsigned)((b.n + NW_SORT_PAIRS - 1) / NW_SORT_PAIRS)));
-            } else if (b.w4 == 1 && h->nw_pair2) {
-                HIPCHK(h, launch(h, nw_banded2_kernel<4>, (unsigned)((b.n + 2 * ASM_BLOCK - 1) / (2 * ASM_BLOCK)), ASM_BLOCK, planes, lens, n,
-                                 b.w4, out));
-            } else {
-                HIPCHK(h, banded(std::false_type{}, g));
-            }
-        } else {
-            /* a zero penalty makes the wavefront read the generation it is writing (ring slot s - 0): plain Gotoh handles it */
-            const bool positive = p->x >= 1 && p->o >= 1 && p->e >= 1;
-            if (h->nw_wfa && positive && b.maxlen <= 256 &&
-                LvRings::exact(p->x, p->o, p->e).ring_bytes(2 * NW_WFA_K + 1, LEAP_GEN_THREADS, 2) <= 64 * 1024) {
-                const int rc = with_const_of<2, 4>((b.maxlen + 63) / 64, [&](auto w) { /* 64-bit words per string; rows they hold */
-                    return launch_nw_wfa<decltype(w)::value, 64 * decltype(w)::value>(h, b, p, out);
-                });
-                if (rc != ASM_OK) return rc;
-            } else {
-                HIPCHK(h, launch_nw_affine(h->stream, planes, lens, b.n, b.w4, b.maxlen, p->x, p->o, p->e, out));
-            }
-        }
-    }
-    return ASM_OK;
-}
-
-/* one aligner over a batch: what the three entry points below have in common */
-static int align_batch(asm_handle* h, const asm_batch* b, int aligner, const asm_params* p, int32_t* d_penalties, CigarSink cig,
-                       const int32_t* hint, const char* who) {
-    if (!h || !b || !d_penalties) return fail(h, ASM_EINVAL, std::string(who) + ": NULL argument");
-    if (const int rc = check_params(h, aligner, p, b->maxlen)) return rc;
-    if (b->n == 0) return ASM_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    return for_each_bucket(b, d_penalties, [&](const asm_bucket& k, OutMap out) { return align_bucket(h, k, aligner, p, out, cig, hint); });
-}
-
-int asm_align_batch_hinted_async(asm_handle* h, const asm_batch* b, int aligner, const asm_params* p,
-                                 const int32_t* d_work_hint, int32_t* d_penalties) {
-    return align_batch(h, b, aligner, p, d_penalties, CigarSink{nullptr, nullptr, 0}, d_work_hint, "asm_align_batch_hinted_async");
-}
-
-int asm_align_batch_async(asm_handle* h, const asm_batch* b, int aligner, const asm_params* p, int32_t* d_penalties) {
-    return align_batch(h, b, aligner, p, d_penalties, CigarSink{nullptr, nullptr, 0}, nullptr, "asm_align_batch_async");
-}
-
-int asm_greedy_cigar_batch_async(asm_handle* h, const asm_batch* b, const asm_params* p, int32_t* d_penalties,
-                                 uint16_t* d_ops, int cap, uint8_t* d_nops) {
-    if (!h || !b || !d_penalties || !d_ops || !d_nops || cap < 1)
-        return fail(h, ASM_EINVAL, "asm_greedy_cigar_batch_async: bad argument");
-    return align_batch(h, b, ASM_GREEDY, p, d_penalties, CigarSink{d_ops, d_nops, cap}, nullptr, "asm_greedy_cigar_batch_async");
-}
-
-int asm_cigar_format(const uint16_t* ops, int nops, int cap, char* out, size_t out_cap) {
-    return asm_host::cigar_format(ops, nops, cap, out, out_cap);
-}
-
-int asm_coverage(asm_handle* h, const asm_batch* b, const asm_params* p, const uint16_t* d_greedy_ops, int greedy_cap,
-                 const uint8_t* d_greedy_nops, int window, uint8_t* d_cover, uint16_t* d_nw_ops, int nw_cap,
-                 uint8_t* d_nw_nops, unsigned long long* d_counters) {
-    if (!h || !b || !p || !d_greedy_ops || !d_greedy_nops || !d_cover || !d_counters || greedy_cap < 1)
-        return fail(h, ASM_EINVAL, "asm_coverage: bad argument");
-    int prc = check_params(h, ASM_NW, p, b->maxlen);
-    if (prc) return prc;
-    if (window != 32 && window != 64) return fail(h, ASM_EINVAL, "asm_coverage: window must be 32 or 64");
-    if (d_nw_ops && (!d_nw_nops || nw_cap < 1)) return fail(h, ASM_EINVAL, "asm_coverage: bad NW CIGAR buffers");
-    if (b->n == 0) return ASM_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    CoverArgs ca;
-    ca.g_ops = d_greedy_ops, ca.g_nops = d_greedy_nops, ca.g_cap = greedy_cap;
-    ca.cover = d_cover, ca.nw_ops = d_nw_ops, ca.nw_nops = d_nw_nops, ca.nw_cap = nw_cap, ca.counters = d_counters;
-    int rc = ASM_OK;
-    const bool unit = p->x == 1 && p->o == 1 && p->e == 1;
-    for (int q = 0; q < b->nb && !rc; q++) {
-        const asm_bucket& k = b->bk[q];
-        if (!unit) { /* general penalties: every pair through the full matrix */
-            rc = cover_full_matrix(h, k, p, k.planes, k.lens, k.order, 0, nullptr, k.n, ca);
-            continue;
-        }
-        rc = with_const<1, 4>(k.w4, [&](auto w) { /* ND = plane dwords per string */
-            constexpr int ND = 4 * decltype(w)::value;
-            return window == 32 ? cover_bucket<ND, 32>(h, k, p, ca) : cover_bucket<ND, 64>(h, k, p, ca);
-        });
-    }
-    return rc;
-}
-
-int asm_align_batch(asm_handle* h, int aligner, int64_t n, const char* reads, const uint32_t* read_off, const char* refs,
-                    const uint32_t* ref_off, const asm_params* p, int greedy_mode, int32_t* penalties) {
-    if (!h || !penalties) return fail(h, ASM_EINVAL, "asm_align_batch: NULL argument");
-    int rc = check_params(h, aligner, p);
-    if (rc) return rc;
-    asm_batch* raw = nullptr;
-    rc = asm_batch_upload(h, n, reads, read_off, refs, ref_off, greedy_mode, &raw);
-    if (rc) return rc;
-    BatchPtr b(raw);
-    Scratch<int32_t> d_out(h);
-    HIPCHK(h, d_out.alloc(sizeof(int32_t) * (size_t)(n > 0 ? n : 1)));
-    rc = asm_align_batch_async(h, b.get(), aligner, p, d_out.p);
-    if (rc) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (n > 0) HIPCHK(h, hipMemcpy(penalties, d_out.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
-    return ASM_OK;
-}
-
-int asm_simd_ed_batch_async(asm_handle* h, const asm_batch* b, int ed_threshold, int shd_enable, int mode,
-                            int32_t* state, int32_t* d_ed) {
-    return asm_simd_ed_mode_batch_async(h, b, ed_threshold, shd_enable, mode, ASM_LEAP_GLOBAL, state, d_ed);
-}
-
-int asm_simd_ed_mode_batch_async(asm_handle* h, const asm_batch* b, int ed_threshold, int shd_enable, int mode, int ed_mode,
-                                 int32_t* state, int32_t* d_ed) {
-    if (!h || !b || !d_ed) return fail(h, ASM_EINVAL, "asm_simd_ed_batch_async: NULL argument");
-    if (ed_mode < ASM_LEAP_GLOBAL || ed_mode > ASM_LEAP_SEMI_FREE_END)
-        return fail(h, ASM_EINVAL, "asm_simd_ed_mode_batch_async: ed_mode must be one of ASM_LEAP_GLOBAL/LOCAL/SEMI_FREE_BEGIN/SEMI_FREE_END");
-    if (ed_threshold < 1 || ed_threshold > ASM_FILTER_MAX_T)
-        return fail(h, ASM_EINVAL, "asm_simd_ed_batch_async: ED threshold must be in [1, 32]");
-    if (shd_enable && ed_threshold > ASM_SHD_MAX_ERROR)
-        return fail(h, ASM_EINVAL, "asm_simd_ed_batch_async: SHD needs an ED threshold <= 16 (MAX_ERROR_AVX)");
-    if (mode != ASM_FILTER_SEQUENTIAL && mode != ASM_FILTER_CLEAN)
-        return fail(h, ASM_EINVAL, "asm_simd_ed_batch_async: unknown mode");
-    if (mode == ASM_FILTER_SEQUENTIAL && state && (state[0] < 0 || state[0] > 255 || state[1] < 0 || state[1] > 255 || state[2] < 0))
-        return fail(h, ASM_EINVAL, "asm_simd_ed_batch_async: state out of range");
-    if (b->n == 0) return ASM_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (const int rc = for_each_bucket(b, d_ed, [&](const asm_bucket& k, OutMap ev) {
-            return launch_simd_ed_events(h, k, ed_threshold, shd_enable ? 1 : 0, ev, ed_mode);
-        }))
-        return rc;
-    const long n = (long)b->n;
-    const unsigned g = grid_for(b->n), t = ASM_BLOCK;
-    if (ed_mode == ASM_LEAP_LOCAL || ed_mode == ASM_LEAP_SEMI_FREE_END) { /* no converge_ED, no carried state: SEQUENTIAL = CLEAN */
-        HIPCHK(h, launch(h, simd_ed_final_kernel, g, t, d_ed, n));
-        return ASM_OK;
-    }
-    if (mode == ASM_FILTER_CLEAN) {
-        HIPCHK(h, launch(h, simd_ed_clean_kernel, g, t, d_ed, n, ed_threshold));
-        return ASM_OK;
-    }
-    /* sequential: resolve the verdict chain in batch order with two last-setter scans */
-    const int init_fe = state ? state[0] : 0, init_fd = state ? state[1] : 0, init_conv = state ? state[2] : 0;
-    int32_t last_setter = -1, last_conv = -1;
-    size_t tmp_bytes = 0;
-    Scratch<int32_t> d_a(h), d_b(h);
-    Scratch<void> d_tmp(h);
-    HIPCHK(h, d_a.alloc(sizeof(int32_t) * (size_t)n));
-    HIPCHK(h, d_b.alloc(sizeof(int32_t) * (size_t)n));
-    HIPCHK(h, hipcub::DeviceScan::InclusiveScan(nullptr, tmp_bytes, d_a.p, d_b.p, LastSetter(), (int)n, h->stream));
-    HIPCHK(h, d_tmp.alloc(tmp_bytes + 16));
-    HIPCHK(h, launch(h, simd_ed_setter_kernel, g, t, d_ed, n, d_a.p));
-    HIPCHK(h, hipcub::DeviceScan::InclusiveScan(d_tmp.p, tmp_bytes, d_a.p, d_b.p, LastSetter(), (int)n, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&last_setter, d_b.p + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, launch(h, simd_ed_converge_kernel, g, t, d_ed, d_b.p, n, init_fe, init_fd, d_a.p));
-    HIPCHK(h, hipcub::DeviceScan::InclusiveScan(d_tmp.p, tmp_bytes, d_a.p, d_b.p, LastSetter(), (int)n, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&last_conv, d_b.p + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, launch(h, simd_ed_verdict_kernel, g, t, d_ed, d_b.p, n, ed_threshold, init_conv));
-    HIPCHK(h, hipStreamSynchronize(h->stream)); /* last_setter and last_conv are read below */
-    if (state) { /* the state the next batch of the same stream of pairs starts from */
-        if (last_setter >= 0) state[0] = last_setter & 0xff, state[1] = last_setter >> 8;
-        if (last_conv >= 0) state[2] = last_conv;
-    }
-    return ASM_OK;
-}
-
-static int simd_ed_affine_launch(asm_handle* h, const asm_batch* b, int gap_threshold, int af_threshold, int x, int o, int e, int mode,
-                                 int32_t* d_ed) {
-    if (!h || !b || !d_ed) return fail(h, ASM_EINVAL, "asm_simd_ed_affine_batch_async: NULL argument");
-    if (mode < ASM_LEAP_GLOBAL || mode > ASM_LEAP_SEMI_FREE_END)
-        return fail(h, ASM_EINVAL, "asm_simd_ed_affine_mode_batch_async: mode must be one of ASM_LEAP_GLOBAL/LOCAL/SEMI_FREE_BEGIN/SEMI_FREE_END");
-    if (gap_threshold < 1 || gap_threshold > ASM_FILTER_MAX_T)
-        return fail(h, ASM_EINVAL, "asm_simd_ed_affine_batch_async: gap threshold must be in [1, 32]");
-    if (af_threshold < 1 || af_threshold > 512)
-        return fail(h, ASM_EINVAL, "asm_simd_ed_affine_batch_async: affine threshold must be in [1, 512]");
-    if (x < 1 || x > 15 || o < 1 || o > 15 || e < 1 || e > o)
-        return fail(h, ASM_EINVAL, "asm_simd_ed_affine_batch_async: penalties must satisfy 1 <= e <= o <= 15, 1 <= x <= 15");
-    if (b->n == 0) return ASM_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    const LvRings rg = LvRings::pow2(x, o, e);
-    const int rows = 2 * gap_threshold + 3;
-    int threads = 64;
-    while (threads > 16 && rg.ring_bytes(rows, threads, sizeof(uint16_t)) > 150 * 1024) threads >>= 1;
-    const size_t lds = rg.ring_bytes(rows, threads, sizeof(uint16_t));
-    /* threads and lds are the thread-per-pair kernel's (strings beyond one granule); the refusal below also meets batches whose
-     * buckets all go to the quad kernel, which has its own LDS layout.  Stricter than needed there, but callers can observe it:
-     * kept as it is. */
-    if (lds > 150 * 1024) return fail(h, ASM_EINVAL, "asm_simd_ed_affine_batch_async: generation rings exceed the LDS");
-    return for_each_bucket(b, d_ed, [&](const asm_bucket& k, OutMap out) -> int {
-        if (k.maxlen <= 128) /* four threads per pair (thread per pair measured 0.28/0.71/3.5 ms per 10^6 C2 pairs at gap 3/8/30 against 0.29/0.46/0.79) */
-            HIPCHK(h, launch_lds(h, simd_ed_affine_quad_kernel, (unsigned)((k.n + 15) / 16), 64,
-                                 rg.quad_lds(16, SIMD_QUAD_W32, gap_threshold, sizeof(uint8_t)), k.planes, k.lens, (long)k.n, k.w4, gap_threshold, af_threshold, x, o, e, rg.gm, rg.gi, mode, out));
-        else /* thread per pair: the only instantiation kept is the one for strings beyond one granule */
-            HIPCHK(h, launch_lds(h, simd_ed_affine_kernel<4>, (unsigned)((k.n + threads - 1) / threads), (unsigned)threads, lds, k.planes,
-                                 k.lens, (long)k.n, k.w4, gap_threshold, af_threshold, x, o, e, rg.gm, rg.gi, mode, out));
-        return ASM_OK;
-    });
-}
-
-int asm_simd_ed_affine_batch_async(asm_handle* h, const asm_batch* b, int gap_threshold, int af_threshold, int x, int o, int e,
-                                   int32_t* d_ed) {
-    return simd_ed_affine_launch(h, b, gap_threshold, af_threshold, x, o, e, ASM_LEAP_GLOBAL, d_ed);
-}
-
-int asm_simd_ed_affine_shd_batch_async(asm_handle* h, const asm_batch* b, int gap_threshold, int af_threshold, int x, int o, int e,
-                                       int shd_threshold, int32_t* d_ed) {
-    if (shd_threshold < 0) return fail(h, ASM_EINVAL, "asm_simd_ed_affine_shd_batch_async: SHD threshold must be in [0, min(16, gap threshold)]");
-    return asm_simd_ed_affine_mode_batch_async(h, b, gap_threshold, af_threshold, x, o, e, shd_threshold, ASM_LEAP_GLOBAL, d_ed);
-}
-
-int asm_simd_ed_affine_mode_batch_async(asm_handle* h, const asm_batch* b, int gap_threshold, int af_threshold, int x, int o, int e,
-                                        int shd_threshold, int mode, int32_t* d_ed) {
-    if (shd_threshold < 0) return simd_ed_affine_launch(h, b, gap_threshold, af_threshold, x, o, e, mode, d_ed); /* SHD off */
-    if (shd_threshold > ASM_SHD_MAX_ERROR || shd_threshold > gap_threshold)
-        return fail(h, ASM_EINVAL, "asm_simd_ed_affine_shd_batch_async: SHD threshold must be in [0, min(16, gap threshold)] "
-                                   "(the reference reads 2*SHD_threshold+1 of its 2*gap_threshold+1 lane masks)");
-    const int rc = simd_ed_affine_launch(h, b, gap_threshold, af_threshold, x, o, e, mode, d_ed);
-    if (rc != ASM_OK || b->n == 0) return rc;
-    return for_each_bucket(b, d_ed, [&](const asm_bucket& k, OutMap out) -> int {
-        HIPCHK(h, (with_const_of<2, 4>((k.maxlen + 63) / 64, [&](auto w) {
-                   return launch(h, simd_affine_shd_kernel<decltype(w)::value>, grid_for(k.n), ASM_BLOCK, k.planes, k.lens, (long)k.n, k.w4,
-                                 gap_threshold, shd_threshold, out);
-               })));
-        return ASM_OK;
-    });
-}
-
-int asm_shd_filter_batch_async(asm_handle* h, const asm_batch* b, int max_error, int32_t* d_pass) {
-    if (!h || !b || !d_pass) return fail(h, ASM_EINVAL, "asm_shd_filter_batch_async: NULL argument");
-    if (max_error < 0 || max_error > ASM_SHD_MAX_ERROR)
-        return fail(h, ASM_EINVAL, "asm_shd_filter_batch_async: max_error must be in [0, 16] (MAX_ERROR_AVX)");
-    if (b->n == 0) return ASM_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    return for_each_bucket(b, d_pass, [&](const asm_bucket& k, OutMap out) -> int {
-        HIPCHK(h, (with_const_of<2, 4>((k.maxlen + 63) / 64, [&](auto w) {
-                   return launch(h, shd_kernel<decltype(w)::value>, grid_for(k.n), ASM_BLOCK, k.planes, k.lens, (long)k.n, k.w4, max_error, out);
-               })));
-        return ASM_OK;
-    });
-}
+/* the aligners and the filters: launchers, align_bucket / align_batch, coverage, SIMD_ED and SHD (decisions: asm_plan.h) */
+#include "asm_align_host.h"
 
 int asm_count_equal_async(asm_handle* h, const int32_t* d_a, const int32_t* d_b, int64_t n, unsigned long long* d_count) {
     if (!h || !d_a || !d_b || !d_count) return fail(h, ASM_EINVAL, "asm_count_equal_async: NULL argument");

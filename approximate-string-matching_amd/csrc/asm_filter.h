@@ -11,8 +11,6 @@
 #pragma once
 #include "asm_kernels.h"
 
-#define ASM_FILTER_MAX_T 32    /* lanes 2T+1 <= 65 */
-#define ASM_FILTER_REG_MAX_T 8 /* masks of all lanes held in registers up to here; computed per use beyond */
 #define ASM_SHD_MAX_ERROR 16   /* MAX_ERROR_AVX (LEAP_SIMD/mask.h:21): rows of the reference's begin-mask table */
 
 // events of one pair (S2)
@@ -95,7 +93,6 @@ ASM_DEV VW<W64> vw_from(int cnt) { /* bits cnt.. set: MASK_AVX_BEG row cnt-1 (ma
 // registers, lanes unrolled.  TT = 0: T at run time, lane masks rebuilt per use, the previous generation's end positions in
 // a thread-private LDS column.
 // ---------------------------------------------------------------------------------------------------------------------
-#define SIMD_ED_THREADS 128
 template <int TT, int W64>
 __global__ __launch_bounds__(SIMD_ED_THREADS) void simd_ed_kernel(const uint4* __restrict__ planes,
                                                                   const uint32_t* __restrict__ lens, long n, int w4, int t_rt,
@@ -305,10 +302,7 @@ __global__ __launch_bounds__(64) void simd_ed_affine_kernel(const uint4* __restr
 // generations.  Against one thread per pair the LDS a wave needs shrinks by four (gap 30, (2,3,1): 8 KB per wave instead of
 // 61), which is what bounds the occupancy there, and a wave waits for the slowest of 16 pairs instead of 64.
 // ---------------------------------------------------------------------------------------------------------------------
-#define SIMD_QUAD_PD 6 /* zero dword, 4 plane dwords, zero dword */
 #define SIMD_QUAD_PW LEAP_QUAD_PAIR_DWORDS(SIMD_QUAD_PD)
-/* what LvRings::quad_lds takes for the plane part: it counts w32 + 1 dwords per plane (data and one zero dword), here 4 + 2 */
-#define SIMD_QUAD_W32 (SIMD_QUAD_PD - 1)
 ASM_DEV uint32_t simd_quad_window(const uint32_t* plane, int pos) { /* pos is already offset by the leading zero dword */
     const int q = pos >> 5;
     return __builtin_amdgcn_alignbit(plane[q + 1], plane[q], (uint32_t)(pos & 31));

@@ -4,11 +4,7 @@
 #include "asm_greedy3.h"
 #include "asm_kernels.h"
 
-
-#ifndef G3_THREADS
-#define G3_THREADS 512
-#endif
-/* G3_THREADS: one workgroup per CU: 8 waves = 2 per SIMD; LDS = table + 16 B per lane vector per thread */
+/* G3_THREADS, G3_STAGE_ENTRIES: asm_limits.h */
 
 template <int NT>
 struct G3LdsStore {
@@ -24,13 +20,8 @@ struct G3LdsTable {
 /* costs of the workgroup's slice staged in LDS and written out in one coalesced sweep at the end (when the slice fits and the
  * results go to their own index): a refilling lane's scattered 4-byte store — 2.5 x write amplification at C2, 64-bit address
  * arithmetic inside the half-empty refill block — becomes one ds_write_b32 */
-#ifndef G3_STAGE_ENTRIES
-#define G3_STAGE_ENTRIES 4096
-#endif
 typedef uint16_t g3_stage_t; /* 0xFFFF: "this cost did not fit and went straight to memory" (never at 128 characters in practice) */
-constexpr size_t g3_lds_bytes(int K, int NT) {
-    return (size_t)G3_TABLE_ENTRIES * 8 + (size_t)(2 * K + 1) * NT * 16 + (size_t)G3_STAGE_ENTRIES * sizeof(g3_stage_t);
-}
+/* the kernel's dynamic LDS (table, lane vectors, this stage) is sized by g3_lds_bytes, asm_plan.h */
 
 __device__ __forceinline__ G3V g3_from_uint4(uint4 q) {
     G3V r;

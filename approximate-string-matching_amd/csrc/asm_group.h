@@ -237,33 +237,5 @@ __global__ __launch_bounds__(ASM_BLOCK, (LPT <= 3 ? 4 : LPT <= 5 ? 3 : 2)) void 
 // threads on lanes of their own with 41 VGPRs, and what the group form saves in idle threads it loses to registers (LPT lanes
 // of state per thread: 3 waves per SIMD instead of 7) and to ds_bpermute latency.  So only (16, 5) is instantiated, for the
 // 65..79 band lanes of 32 <= k <= 39; k <= 14 runs thread per pair, 15 <= k <= 31 wave per pair, k >= 40 two waves per pair.
-static inline bool greedy_group_shape(int k, int& T, int& LPT) {
-    const int nl = 2 * k + 1;
-    static const int shapes[][2] = {{16, 5}};
-    for (const auto& s : shapes)
-        if (s[0] * s[1] >= nl) {
-            T = s[0], LPT = s[1];
-            return true;
-        }
-    return false;
-}
 
-template <int T, int LPT>
-static inline hipError_t launch_greedy_group_tl(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4, int k,
-                                                const GreedyArgs& ga, OutMap out, CigarSink cig, int num_cus) {
-    int per_cu = 4;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, greedy_group_kernel<T, LPT>, ASM_BLOCK, 0);
-    if (per_cu < 1) per_cu = 1;
-    int64_t blocks = (int64_t)per_cu * num_cus;
-    const int64_t need = (n * T + ASM_BLOCK - 1) / ASM_BLOCK;
-    if (blocks > need) blocks = need;
-    return launch_on(stream, greedy_group_kernel<T, LPT>, (unsigned)blocks, ASM_BLOCK, 0, planes, lens, (long)n, w4, k, ga, out, cig);
-}
 
-static inline hipError_t launch_greedy_group(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4, int k,
-                                             const GreedyArgs& ga, OutMap out, CigarSink cig, int num_cus) {
-    int T = 0, LPT = 0;
-    if (!greedy_group_shape(k, T, LPT)) return hipErrorInvalidValue;
-    if (T == 16 && LPT == 5) return launch_greedy_group_tl<16, 5>(stream, planes, lens, n, w4, k, ga, out, cig, num_cus);
-    return hipErrorInvalidValue;
-}

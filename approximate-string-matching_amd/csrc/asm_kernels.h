@@ -23,7 +23,7 @@
 #include "asm_leapunit.h"
 #include "asm_nwband.h"
 
-#define ASM_BLOCK 256
+#include "asm_limits.h" /* ASM_BLOCK and the other shapes the dispatch reads too */
 
 // --------------------------------------------------------------------------------------------------------
 // Pack: ASCII -> bit planes.  Device counterpart of sse3_convert2bit1 (GASMA/bit_convert.cpp:248-369), minus
@@ -533,7 +533,6 @@ __global__ __launch_bounds__(ASM_BLOCK) void leap_unit_kernel(const uint4* __res
 // for ~98 % of pairs — each workgroup counting-sorts its 256 pairs by that hint in LDS and thread t takes the pair of
 // rank t, so each of the four waves works on one quartile of the workgroup's pairs, i.e. on 64 pairs that need
 // (nearly) the same number of generations.  The hint only changes the schedule, never a result.
-#define LEAP_HINT_PAIRS 256
 template <int K, int W64>
 __global__ __launch_bounds__(ASM_BLOCK) void leap_unit_hint_kernel(const uint4* __restrict__ planes,
                                                                    const uint32_t* __restrict__ lens, long n, int w4,
@@ -591,7 +590,6 @@ __global__ __launch_bounds__(ASM_BLOCK) void leap_unit_hint_kernel(const uint4* 
 // (asm_affine.h), per thread, in dynamic LDS laid out [ring][slot][lane][thread]: thread-private columns, so no barriers and no
 // bank conflicts; slot offsets are wave-uniform (scalar).
 // --------------------------------------------------------------------------------------------------------
-#define LEAP_GEN_THREADS 128
 
 template <int K, int W64, typename EnT> /* EnT: ring element, values stored + 2 (0 = never reached) */
 __global__ __launch_bounds__(LEAP_GEN_THREADS) void leap_general_kernel(const uint4* __restrict__ planes,
@@ -673,8 +671,6 @@ __global__ __launch_bounds__(LEAP_GEN_THREADS) void leap_general_kernel(const ui
 // and gap(K+1-|n-m|) to come back from: bound = 2o + (2K - |n-m|)e.  A banded result s <= bound is therefore the global
 // optimum; pairs that do not finish by then (or with |n-m| > K) are appended to `todo` for the full-matrix kernel.
 // --------------------------------------------------------------------------------------------------------
-#define NW_WFA_K 7
-#define NW_WFA_K2 15 /* second pass over the pairs the first band could not settle (maxlen <= 128 only: 31 masks of 4 dwords) */
 // append `value` to list[*count ...) in the threads where `flag` holds: one atomic per wave
 ASM_DEV void wave_append(uint32_t* __restrict__ list, uint32_t* __restrict__ count, bool flag, uint32_t value) {
     const u64 bal = __ballot(flag);
@@ -934,9 +930,7 @@ ASM_DEV int nw_banded_pair(const uint4* __restrict__ planes, const uint32_t* __r
 // thread t takes the slot of rank t (t + 256, ... for wider windows): a wave then works on a quarter of the window's lengths.
 // Loads stay inside the window (4 KB per plane granule: what a wave leaves of a sector its neighbours take from the cache),
 // results go where they always went.
-#define NW_SORT_PAIRS 256 /* slots a workgroup sorts by length: one per thread, a wave gets a quarter of the window's lengths.
-                             Measured at C5, 10^7 pairs: no sort 2.31 ms, 256 slots 2.07, 1024 slots (four per thread) 2.21 — the
-                             wider window is sorted better but its scattered 16-byte loads no longer share their sectors in cache */
+// (NW_SORT_PAIRS, the slots a workgroup sorts, and what was measured for it: asm_limits.h)
 template <int ND, int FIRSTW, bool BYLEN> /* plane dwords per string: 4 * w4; FIRSTW = 32 or 64: the first window tried */
 __global__ __launch_bounds__(ASM_BLOCK) void nw_banded_kernel(const uint4* __restrict__ planes,
                                                               const uint32_t* __restrict__ lens, long n, int w4,

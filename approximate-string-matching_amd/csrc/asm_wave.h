@@ -11,7 +11,6 @@
 #include "asm_kernels.h"
 #include "asm_launch.h"
 
-#define ASM_WAVE_MAX_K 31
 
 // DPP controls (gfx9 family): lane i reads lane i-1 / i+1 of the whole wave; lanes with no source keep `old`.
 #define DPP_WAVE_SHL1 0x130 /* lane i <- lane i+1 */
@@ -129,8 +128,6 @@ ASM_DEV int leap_band_extend(const uint32_t* pl, int d, int from, int m, int nn)
 // against 0.91 per 10^6 C3 pairs (0.52 against 0.19 at C2): every refill stalls the whole wave for two dependent global
 // round trips (lengths, then planes), 122 times per wave at 10^6 pairs.  It would need the next pair prefetched into registers.
 // --------------------------------------------------------------------------------------------------------
-#define LEAP_QUAD_THREADS 64
-#define LEAP_QUAD_PAIRS 16
 
 /* Thread q < 4 of a pair's group stages plane q (read plane 0/1, reference plane 0/1) into the pair's LDS block `pl`.  Planes in LDS
  * are pair-major: the 4 x PD dwords of a pair are contiguous (a window is two adjacent dwords: one address add, no multiply), each
@@ -319,19 +316,6 @@ __global__ __launch_bounds__(256) void leap_sort_keys_kernel(const int32_t* __re
     idx[j] = (uint32_t)j;
 }
 
-template <int W32, typename EnT>
-static inline hipError_t launch_leap_quad(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4, int k,
-                                          bool unit, int x, int o, int e, LvRings rg /* LvRings::unit() where unit */, OutMap out,
-                                          const int32_t* hint, const uint32_t* perm) {
-    const size_t lds1 = rg.quad_lds(LEAP_QUAD_PAIRS, W32, k, sizeof(EnT));
-    const auto go = [&](auto kernel, unsigned waves, const int32_t* hnt, const uint32_t* prm) {
-        return launch_on(stream, kernel, (unsigned)((n + waves * LEAP_QUAD_PAIRS - 1) / (waves * LEAP_QUAD_PAIRS)), waves * LEAP_QUAD_THREADS,
-                         waves * lds1, planes, lens, (long)n, w4, k, x, o, e, rg.gm, rg.gi, out, hnt, prm);
-    };
-    if (hint && !perm && 4 * lds1 + 512 <= 64 * 1024) /* work-sorted inside workgroups of four waves (64 pairs) */
-        return unit ? go(leap_quad_kernel<W32, EnT, true, 4>, 4, hint, nullptr) : go(leap_quad_kernel<W32, EnT, false, 4>, 4, hint, nullptr);
-    return unit ? go(leap_quad_kernel<W32, EnT, true, 1>, 1, nullptr, perm) : go(leap_quad_kernel<W32, EnT, false, 1>, 1, nullptr, perm);
-}
 
 // --------------------------------------------------------------------------------------------------------
 // Affine NW, banded wavefront, EIGHT THREADS PER PAIR — the second pass of launch_nw_wfa.  The pairs the thread-per-pair pass
@@ -340,9 +324,6 @@ static inline hipError_t launch_leap_quad(hipStream_t stream, const uint4* plane
 // dealt round-robin to eight threads, as leap_quad_kernel does, with the rings [slot][lane row][pair] and the planes in LDS
 // and the band half-width K a run-time value.  Recurrence, exactness bound and todo list as nw_wfa_kernel.
 // --------------------------------------------------------------------------------------------------------
-#define NW_OCT_THREADS 64
-#define NW_OCT_Q 8
-#define NW_OCT_PAIRS (NW_OCT_THREADS / NW_OCT_Q)
 
 // first i >= st on diagonal d (reference index i + d) at which the strings differ or either one ends (or i + d < 0)
 template <int PD, int TS, int PS>
@@ -650,7 +631,6 @@ __global__ __launch_bounds__(ASM_BLOCK) void greedy_wave_kernel(const uint4* __r
 // meet through LDS (three barriers per step).  Replaces the serial per-thread scans of greedy_wide_kernel (which stays
 // as the ASM_WAVE=0 fallback).
 // --------------------------------------------------------------------------------------------------------
-#define GREEDY_WAVE2_THREADS 128
 __global__ __launch_bounds__(GREEDY_WAVE2_THREADS) void greedy_wave2_kernel(const uint4* __restrict__ planes,
                                                                             const uint32_t* __restrict__ lens, long n, int w4,
                                                                             int k, GreedyArgs args, OutMap out, CigarSink cig) {
@@ -790,20 +770,4 @@ __global__ __launch_bounds__(GREEDY_WAVE2_THREADS) void greedy_wave2_kernel(cons
     }
 }
 
-static inline hipError_t launch_greedy_wave2(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4, int k,
-                                             const GreedyArgs& ga, OutMap out, CigarSink cig, int num_cus) {
-    int64_t blocks = (int64_t)num_cus * 16; /* two waves each; the kernel strides over the pairs */
-    if (blocks > n) blocks = n;
-    return launch_on(stream, greedy_wave2_kernel, (unsigned)blocks, GREEDY_WAVE2_THREADS, 0, planes, lens, (long)n, w4, k, ga, out, cig);
-}
 
-template <typename Kern, typename... Args>
-static inline hipError_t launch_wave_per_pair(hipStream_t stream, Kern kern, int64_t n, int num_cus, Args... args) {
-    int per_cu = 8;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, ASM_BLOCK, 0);
-    if (per_cu < 1) per_cu = 1;
-    int64_t blocks = (int64_t)per_cu * num_cus;
-    const int64_t need = (n + 3) / 4; /* four waves (pairs in flight) per workgroup */
-    if (blocks > need) blocks = need;
-    return launch_on(stream, kern, (unsigned)blocks, ASM_BLOCK, 0, args...);
-}

@@ -12,9 +12,6 @@
 #include "asm_kernels.h"
 #include "asm_launch.h"
 
-#define ASM_WIDE_MAX_K 63       /* 2k+1 <= 127 lanes -> one 128-thread workgroup                         */
-#define ASM_WIDE_MAX_PENALTY 15 /* LEAP history ring depth 16; NW boundary values stay inside int16       */
-#define ASM_WIDE_THREADS 128
 #define ASM_WIDE_RING 16
 
 // --------------------------------------------------------------------------------------------------------
@@ -109,15 +106,6 @@ __global__ __launch_bounds__(ASM_WIDE_THREADS) void leap_wide_kernel(const uint4
     }
 }
 
-static inline hipError_t launch_leap_wide(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4,
-                                          int k, int x, int o, int e, OutMap out, int mode = 0) {
-    const unsigned blocks = (unsigned)(n < 256 * 32 ? n : 256 * 32);
-    const int maxw = w4 * 2;
-    const auto go = [&](auto kernel) {
-        return launch_on(stream, kernel, blocks, ASM_WIDE_THREADS, 0, planes, lens, (long)n, w4, k, x, o, e, mode, out);
-    };
-    return maxw <= 2 ? go(leap_wide_kernel<2>) : maxw <= 4 ? go(leap_wide_kernel<4>) : go(leap_wide_kernel<8>);
-}
 
 // --------------------------------------------------------------------------------------------------------
 // Greedy, any k <= 50: workgroup per pair, thread = lane.  Same step structure as greedy_kernel<K>; the two
@@ -245,11 +233,6 @@ __global__ __launch_bounds__(ASM_WIDE_THREADS) void greedy_wide_kernel(const uin
     }
 }
 
-static inline hipError_t launch_greedy_wide(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4,
-                                            int k, const GreedyArgs& ga, OutMap out, CigarSink cig) {
-    const unsigned blocks = (unsigned)(n < 256 * 32 ? n : 256 * 32);
-    return launch_on(stream, greedy_wide_kernel, blocks, ASM_WIDE_THREADS, 0, planes, lens, (long)n, w4, k, ga, out, cig);
-}
 
 // --------------------------------------------------------------------------------------------------------
 // NW with affine gaps (Gotoh), arbitrary penalties: gotoh_sweep (asm_affine.h), score only, one thread per pair; the block
@@ -277,10 +260,3 @@ __global__ __launch_bounds__(64) void nw_affine_kernel(const uint4* __restrict__
     out.put(i, result);
 }
 
-static inline hipError_t launch_nw_affine(hipStream_t stream, const uint4* planes, const uint32_t* lens, int64_t n, int w4,
-                                          int maxlen, int x, int o, int e, OutMap out) {
-    const auto go = [&](auto kernel) { /* every pair of the bucket: no todo list */
-        return launch_on(stream, kernel, (unsigned)((n + 63) / 64), 64, 0, planes, lens, (long)n, w4, x, o, e, out, nullptr, nullptr);
-    };
-    return maxlen <= 128 ? go(nw_affine_kernel<2, 128>) : maxlen <= 256 ? go(nw_affine_kernel<4, 256>) : go(nw_affine_kernel<8, 512>);
-}
