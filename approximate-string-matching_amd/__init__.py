@@ -294,6 +294,9 @@ def load_library() -> ctypes.CDLL:
         "asm_map_get_bgzf_level": (i32, [vp]),
         "asm_bgzf_compress": (i32, [vp, vp, c.c_size_t, i32, i32, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
         "asm_bgzf_compress_host": (i32, [vp, c.c_size_t, i32, i32, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
+        "asm_bgzf_decompressed_size": (i32, [vp, c.c_size_t, c.POINTER(c.c_size_t)]),
+        "asm_bgzf_decompress": (i32, [vp, vp, c.c_size_t, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
+        "asm_bgzf_decompress_host": (i32, [vp, c.c_size_t, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
         "asm_md_format": (i32, [vp, i32, c.c_char_p, i32, c.c_char_p, i32, vp, c.c_size_t]),
         "asm_map_file": (i32, [vp, vp, c.POINTER(c.c_char_p), c.c_char_p, c.c_char_p, c.c_char_p, c.POINTER(MapParams), i32, i32, i64,
                                c.POINTER(MapFileStats)]),
@@ -684,6 +687,17 @@ class Engine:
         out = ctypes.create_string_buffer(max(cap, 1))
         got = ctypes.c_size_t(0)
         self._chk(self.lib.asm_bgzf_compress(self.h, data if data else None, len(data), int(eof), int(level), out, cap, ctypes.byref(got)))
+        return out.raw[: got.value]
+
+    def bgzf_decompress(self, data: bytes) -> bytes:
+        """asm_bgzf_decompress: a BGZF container (what bgzip, bgzf_compress and the BAM file calls write) decoded by the device's
+        deflate decoder, one wavefront per member; the bytes of bgzf_decompress_host.  Corrupt input raises AsmError naming the
+        member; plain gzip is refused (docs/design/mapper.md, "Compressed input")."""
+        data = bytes(data)
+        cap = bgzf_decompressed_size(data)
+        out = ctypes.create_string_buffer(max(cap, 1))
+        got = ctypes.c_size_t(0)
+        self._chk(self.lib.asm_bgzf_decompress(self.h, data if data else None, len(data), out, cap, ctypes.byref(got)))
         return out.raw[: got.value]
 
     def last_mapq(self, count: int) -> np.ndarray:
@@ -1267,3 +1281,28 @@ def gather_penalties(local, dist=None, dst: int = 0):
     if dist.get_rank() != dst:
         return None
     return [b[:int(s.item())] for b, s in zip(bufs, sizes)]
+
+
+def bgzf_decompressed_size(data: bytes) -> int:
+    """asm_bgzf_decompressed_size: the bytes a BGZF container decodes to, from its members' headers and trailers; nothing is decoded"""
+    lib = load_library()
+    data = bytes(data)
+    got = ctypes.c_size_t(0)
+    rc = lib.asm_bgzf_decompressed_size(data if data else None, len(data), ctypes.byref(got))
+    if rc != 0:
+        raise AsmError(rc, lib.asm_last_error(None).decode())
+    return int(got.value)
+
+
+def bgzf_decompress_host(data: bytes) -> bytes:
+    """asm_bgzf_decompress_host: Engine.bgzf_decompress without a device, by the host build of the same decoder; the same bytes and
+    the same errors"""
+    lib = load_library()
+    data = bytes(data)
+    cap = bgzf_decompressed_size(data)
+    out = ctypes.create_string_buffer(max(cap, 1))
+    got = ctypes.c_size_t(0)
+    rc = lib.asm_bgzf_decompress_host(data if data else None, len(data), out, cap, ctypes.byref(got))
+    if rc != 0:
+        raise AsmError(rc, lib.asm_last_error(None).decode())
+    return out.raw[: got.value]

@@ -734,6 +734,8 @@ int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, in
 #include "asm_map_host.h"
 /* the BGZF container of the file calls' BAM output: frame kernel, record stream, asm_bgzf_frame */
 #include "asm_bgzf.h"
+/* the container read back: the deflate decoder, bgzf_inflate_kernel, asm_bgzf_decompress */
+#include "asm_inflate.h"
 /* the output side of the file calls: MapOutput (file, output slots, writer, record stream) and the report of a failed write */
 #include "asm_map_out.h"
 /* what the sorted file calls keep on the device, their sort and their gather */

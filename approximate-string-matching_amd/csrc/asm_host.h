@@ -32,6 +32,7 @@
 
 #include "../../include/asm_mi355x.h"
 #include "asm_gen.h"
+#include "asm_bgzf_walk.h"
 
 namespace asm_host {
 
@@ -408,7 +409,9 @@ public:
     }
     bool failed() const { return failed_.load(); }
     double read_seconds() const { return read_seconds_; } /* after stop() */
-    const Fill& policy() const { return fill_; }          /* what the policy keeps for its caller: after the last chunk or stop() */
+    /* what the policy keeps for its caller: after the last chunk or stop(); what it keeps per slot (BgzfFill::info) goes with the
+     * slot's hand-over: written before the slot is ready, read before consumed() */
+    const Fill& policy() const { return fill_; }
 };
 
 /* asm_stream_seq_file's policy: `want` more file bytes through the reader pool (reads stop at cap - 8), cut behind the last
@@ -529,6 +532,81 @@ struct FastqFill {
             want = chunk; /* one record longer than the chunk: take more */
         }
         cut.have = have, cut.extra_lines = cut.eof ? lines - 4 * cut.units : 0;
+        return true;
+    }
+};
+
+/* asm_map_file's policy for a BGZF-compressed file (asm_bgzf_walk.h; docs/design/mapper.md, "Compressed input"): whole members into
+ * the slot until their ISIZE sum reaches `want`, which stays text bytes; units are members.  Every member's header is checked (magic, CM 8,
+ * FLG 4, the XLEN walk to BC, BSIZE + 1 >= 26 and within the file, ISIZE <= 65 536).  At most 64 KiB are read behind the member at
+ * hand, so the carry (a member cut by the chunk's end, still compressed) is at most 64 KiB.  The text cannot be cut into records
+ * here: that is the device's.  info[q] goes with slot q: the members (offsets in the slot, output offsets the exclusive sum of
+ * ISIZE), their text bytes, the file's members before them, and a bad header (its member's index in the file and file offset),
+ * which ends the stream behind the members in front of it. */
+struct BgzfChunkInfo {
+    std::vector<InfMember> members;
+    size_t text = 0;
+    int64_t first_member = 0;
+    size_t file_base = 0; /* the file offset of the slot's first byte */
+    BgzfWalkError err;
+};
+struct BgzfFill {
+    const int fd;
+    const size_t file_bytes;
+    const std::function<bool(int, size_t, size_t)> grow;
+    size_t file_off = 0;
+    int64_t members_seen = 0;
+    BgzfChunkInfo info[3];
+    BgzfFill(int fd_, size_t file_bytes_, std::function<bool(int, size_t, size_t)> grow_) : fd(fd_), file_bytes(file_bytes_), grow(std::move(grow_)) {}
+
+    bool operator()(ChunkSlot& s, int q, const std::vector<char>& carry, size_t want, ChunkCut& cut) {
+        BgzfChunkInfo& ci = info[q];
+        ci = BgzfChunkInfo();
+        ci.first_member = members_seen;
+        size_t have = carry.size(), at = 0;
+        if (have + 8 > s.cap && !grow(q, have + 8 + 65536, 0)) return false;
+        if (have) memcpy(s.buf, carry.data(), have);
+        ci.file_base = file_off - have;
+        for (;;) {
+            /* the member at `at` whole: 64 KiB behind `at`, or up to the end of the file */
+            size_t need = have - at < 65536 ? 65536 - (have - at) : 0;
+            if (need > file_bytes - file_off) need = file_bytes - file_off;
+            if (have + need + 8 > s.cap && !grow(q, have + need + 8 + (have + need) / 4, have)) return false;
+            for (size_t a = 0; a < need;) {
+                const ssize_t got = pread(fd, s.buf + have + a, need - a, (off_t)(file_off + a));
+                if (got <= 0) return false;
+                a += (size_t)got;
+            }
+            file_off += need, have += need;
+            if (at == have) { /* the end of the file behind a whole member */
+                cut.eof = true;
+                break;
+            }
+            const uint8_t* m = (const uint8_t*)s.buf + at;
+            uint32_t csize = 0, dstart = 0;
+            uint32_t st = bgzf_member_header(m, have - at, &csize, &dstart);
+            if (st == BGZF_IN_OK && csize > have - at) st = BGZF_IN_PAST_END;
+            uint32_t crc = 0, isize = 0;
+            if (st == BGZF_IN_OK) {
+                const uint8_t* t = m + csize - 8u;
+                crc = t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+                isize = t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24;
+                if (isize > INF_MAX_ISIZE) st = BGZF_IN_ISIZE;
+            }
+            if (st != BGZF_IN_OK) {
+                ci.err.status = st, ci.err.member = (size_t)members_seen + ci.members.size(), ci.err.offset = ci.file_base + at;
+                cut.eof = true;
+                break;
+            }
+            ci.members.push_back(InfMember{(unsigned long long)at, (unsigned long long)ci.text, csize, dstart, isize, crc});
+            at += csize, ci.text += isize;
+            if (ci.text >= want) {
+                cut.eof = at == have && file_off >= file_bytes;
+                break;
+            }
+        }
+        members_seen += (int64_t)ci.members.size();
+        cut.have = have, cut.boundary = at, cut.units = (int64_t)ci.members.size();
         return true;
     }
 };

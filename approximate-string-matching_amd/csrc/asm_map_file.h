@@ -31,6 +31,7 @@ struct MapFileSession {
         int64_t chunks, bytes_in, records;
         double seconds_read;
     } st = {};
+    std::function<size_t(const asm_host::ChunkSlot&)> text_bytes; /* set: a chunk's share of bytes_in is not the bytes it ships (BGZF) */
     std::unique_ptr<SamSortHold> sort; /* the sorted calls: the formatted chunks stay on the device until finish() (asm_sam_sort.h) */
     MapFileSession(asm_handle* owner, const char* call, size_t chunk_bytes)
         : h(owner), who(call), in(owner, call), out(owner, call), d_names(owner), d_name_off(owner), chunk(chunk_bytes) {}
@@ -99,7 +100,7 @@ struct MapFileSession {
             [&](const asm_host::ChunkSlot& s, int64_t seen) {
                 if (const int ra = accept(s, seen)) return ra;
                 if (s.bytes >= 0xfffffff0ull) return bad("a chunk of 4 GiB or more; lower chunk_bytes", ASM_EUNSUPPORTED);
-                st.bytes_in += (int64_t)s.bytes;
+                st.bytes_in += (int64_t)(text_bytes ? text_bytes(s) : s.bytes);
                 return (int)ASM_OK;
             },
             process);
@@ -320,6 +321,165 @@ static int map_file_chunk(MapReadsFileJob& j, const char* d_raw, const uint32_t*
     return ASM_OK;
 }
 
+/* ---- a BGZF-compressed FASTQ file (docs/design/mapper.md, "Compressed input") ---------------------------------------------------- */
+struct BgzfCutOut {
+    unsigned long long lines; /* the text's newlines, an appended one included */
+    unsigned long long cut;   /* the bytes of the text's whole records: behind newline 4 * (lines / 4) - 1 */
+    uint32_t appended;        /* a newline was appended behind the text (the end of the file) */
+    uint32_t pad;
+};
+/* One wavefront, behind seq_count_kernel and the exclusive sum of its tile counts (tile_base[ntiles]: all newlines): the record cut
+ * of text[0, nbytes).  is_last: a text that does not end in a newline gets one at text[nbytes] (the buffer has room).  The tile of
+ * the cut's newline is found by bisection, the newline in it by ballots over 64 bytes at a time. */
+__global__ __launch_bounds__(64) void bgzf_cut_kernel(char* __restrict__ text, unsigned long long nbytes, const uint32_t* __restrict__ tile_base,
+                                                      uint32_t ntiles, int is_last, BgzfCutOut* __restrict__ out) {
+    const uint32_t lane = threadIdx.x;
+    const unsigned long long counted = ntiles ? tile_base[ntiles] : 0ull;
+    const bool append = is_last && nbytes > 0 && text[nbytes - 1] != '\n';
+    const unsigned long long lines = counted + (append ? 1u : 0u), need = lines / 4u * 4u;
+    unsigned long long cut = 0;
+    if (need > counted) cut = nbytes + 1u; /* the appended newline closes the last record */
+    else if (need > 0) {
+        const uint32_t k = (uint32_t)(need - 1u); /* the newline to find, counted from 0 */
+        uint32_t lo = 0u, hi = ntiles - 1u;       /* the last tile with tile_base <= k */
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi + 1u) >> 1;
+            if (tile_base[mid] <= k) lo = mid;
+            else hi = mid - 1u;
+        }
+        uint32_t left = k - tile_base[lo]; /* newlines of the tile in front of it */
+        const unsigned long long t0 = (unsigned long long)lo * SEQ_TILE;
+        for (uint32_t i = 0; i < SEQ_TILE; i += 64u) {
+            const unsigned long long at = t0 + i + lane;
+            const unsigned long long mask = __ballot(at < nbytes && text[at] == '\n');
+            const uint32_t c = (uint32_t)__popcll(mask);
+            if (left < c) {
+                unsigned long long m = mask;
+                for (uint32_t d = 0; d < left; d++) m &= m - 1u;
+                cut = t0 + i + (uint32_t)__builtin_ctzll(m) + 1u;
+                break;
+            }
+            left -= c;
+        }
+    }
+    if (lane == 0u) {
+        if (append) text[nbytes] = '\n';
+        out->lines = lines, out->cut = cut, out->appended = append ? 1u : 0u, out->pad = 0u;
+    }
+}
+
+/* The device side of a BGZF input: the text left over behind a chunk's last whole record stays in `carry` on the device and leads
+ * the next chunk's text, as BgzfStream does on the output side. */
+struct BgzfInput {
+    asm_handle* h;
+    Scratch<char> carry;
+    size_t carry_len = 0, carry_cap = 0;
+    int64_t records_seen = 0;
+    asm_host::BgzfChunkInfo pend[2]; /* what the reader said of the chunks in flight, by device buffer */
+    bool pend_last[2] = {false, false};
+    explicit BgzfInput(asm_handle* owner) : h(owner), carry(owner) {}
+};
+static int map_file_member_error(MapFileSession& ss, size_t member, size_t offset, const char* what) {
+    return ss.bad("BGZF member " + std::to_string(member) + " at offset " + std::to_string(offset) + ": " + what);
+}
+
+/* One file chunk of compressed members in d_src: inflated behind the carry, cut into records on the device (one wait: the line
+ * count, the cut, the first failed member), handed to map_file_device_chunks / map_file_chunk as a plain chunk is; the rest of the
+ * text is the next carry. */
+static int map_file_gz_chunk(MapReadsFileJob& j, BgzfInput& gz, const char* d_src, const asm_host::BgzfChunkInfo& ci, bool is_last) {
+    MapFileSession& ss = j.ss;
+    asm_handle* h = ss.h;
+    const char* who = ss.who;
+    typedef unsigned long long u64;
+    const size_t nbytes = gz.carry_len + ci.text;
+    if (nbytes >= 0xfffffff0ull) return ss.bad("a chunk of 4 GiB or more of text; lower chunk_bytes", ASM_EUNSUPPORTED);
+    Scratch<char> d_text(h);
+    Scratch<InfMember> d_members(h);
+    Scratch<u64> d_bad(h);
+    Scratch<BgzfCutOut> d_cut(h);
+    Scratch<uint32_t> d_tile(h), d_tbase(h);
+    MapTmp tmp(h);
+    const uint32_t ntiles = (uint32_t)((nbytes + SEQ_TILE - 1) / SEQ_TILE);
+    STREAM_TRY(who, d_text.alloc(nbytes + 64));
+    STREAM_TRY(who, d_members.alloc(sizeof(InfMember) * (ci.members.size() + 1)));
+    STREAM_TRY(who, d_bad.alloc(sizeof(u64)));
+    STREAM_TRY(who, d_cut.alloc(sizeof(BgzfCutOut)));
+    STREAM_TRY(who, d_tile.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1)));
+    STREAM_TRY(who, d_tbase.alloc(sizeof(uint32_t) * ((size_t)ntiles + 1)));
+    if (gz.carry_len) STREAM_TRY(who, hipMemcpyAsync(d_text.p, gz.carry.p, gz.carry_len, hipMemcpyDeviceToDevice, h->stream));
+    if (!ci.members.empty())
+        STREAM_TRY(who, hipMemcpyAsync(d_members.p, ci.members.data(), sizeof(InfMember) * ci.members.size(), hipMemcpyHostToDevice, h->stream));
+    STREAM_TRY(who, bgzf_inflate_device(h, (const uint8_t*)d_src, d_members.p, ci.members.size(), (uint8_t*)d_text.p + gz.carry_len, d_bad.p));
+    STREAM_TRY(who, hipMemsetAsync(d_tile.p, 0, sizeof(uint32_t) * ((size_t)ntiles + 1), h->stream));
+    if (ntiles) {
+        STREAM_TRY(who, launch(h, seq_count_kernel, ntiles, 256, (const char*)d_text.p, (long)nbytes, d_tile.p));
+        STREAM_TRY(who, map_exclusive_sum(h, tmp, d_tile.p, d_tbase.p, (int64_t)ntiles + 1));
+    }
+    STREAM_TRY(who, launch(h, bgzf_cut_kernel, 1u, 64u, d_text.p, (u64)nbytes, (const uint32_t*)d_tbase.p, ntiles, is_last ? 1 : 0, d_cut.p));
+    u64 bad = INF_NONE_BAD;
+    BgzfCutOut cut = {};
+    STREAM_TRY(who, fetch(h, {fetched(&bad, (const u64*)d_bad.p), fetched(&cut, (const BgzfCutOut*)d_cut.p)}));
+    if (bad != INF_NONE_BAD) {
+        const size_t k = (size_t)(bad >> 8);
+        return map_file_member_error(ss, (size_t)ci.first_member + k, ci.file_base + (size_t)ci.members[k].src_off, inf_status_text((uint32_t)(bad & 0xffu)));
+    }
+    if (ci.err.status != BGZF_IN_OK) return map_file_member_error(ss, ci.err.member, ci.err.offset, bgzf_in_text(ci.err.status));
+    const int64_t records = (int64_t)(cut.lines / 4u);
+    if (is_last && (cut.lines & 3u))
+        return ss.bad("record " + std::to_string(gz.records_seen + records + 1) + " is truncated (the file's line count is not a multiple of 4)");
+    const size_t text_end = nbytes + cut.appended;
+    if (records > 0) {
+        const int64_t first_record = gz.records_seen;
+        const char* d_raw = d_text.p;
+        if (const int rc = map_file_device_chunks(ss, d_raw, (size_t)cut.cut, 4 * records, records, std::min<int64_t>(h->map_chunk, (int64_t)1 << 30),
+                                                  [&](const uint32_t* d_nl, int64_t r0, int64_t rn) {
+                                                      return map_file_chunk(j, d_raw, d_nl, r0, rn, first_record + r0);
+                                                  }))
+            return rc;
+        gz.records_seen += records;
+    }
+    const size_t rest = text_end - (size_t)cut.cut;
+    if (rest > gz.carry_cap) { /* the old carry has been copied into d_text, in stream order */
+        pool_free(h, gz.carry.p);
+        gz.carry.p = nullptr, gz.carry_cap = 0;
+        STREAM_TRY(who, gz.carry.alloc(rest + rest / 2 + 65536));
+        gz.carry_cap = rest + rest / 2 + 65536;
+    }
+    if (rest) STREAM_TRY(who, hipMemcpyAsync(gz.carry.p, d_text.p + cut.cut, rest, hipMemcpyDeviceToDevice, h->stream));
+    gz.carry_len = rest;
+    return ASM_OK;
+}
+
+/* map_file_run for a file that starts with a BGZF member */
+static int map_file_run_gz(MapFileSession& ss, MapReadsFileJob& j, const char* fastq_path, size_t file_bytes) {
+    asm_handle* h = ss.h;
+    StreamInput& in = ss.in;
+    BgzfInput gz(h);
+    asm_host::ChunkReader<asm_host::BgzfFill> rd(ss.chunk, ss.first_chunk, in.wait_shipped(), in.fd, file_bytes, ss.grow());
+    /* info[q] is read while the reader runs: slot q's hand-over (ready under the reader's mutex, refilled only after consumed())
+     * orders it, as it orders the slot's bytes */
+    const asm_host::BgzfFill& fill = rd.policy();
+    ss.text_bytes = [&](const asm_host::ChunkSlot& s) { return fill.info[(&s - rd.slot)].text; };
+    bool header_error = false; /* a bad header in a chunk without members: reported behind the chunks in front of it */
+    asm_host::BgzfChunkInfo bad_chunk;
+    int c = 0;
+    const int rc = ss.run(
+        rd, std::string(ss.who) + ": reading " + fastq_path + " failed",
+        [&](const asm_host::ChunkSlot& s, int64_t) {
+            const asm_host::BgzfChunkInfo& ci = fill.info[&s - rd.slot];
+            if (s.units > 0) gz.pend[c & 1] = ci, gz.pend_last[c & 1] = s.last;
+            else if (ci.err.status != BGZF_IN_OK) header_error = true, bad_chunk = ci;
+            c++;
+            return (int)ASM_OK;
+        },
+        [&](int q, size_t, int64_t, int64_t) { return map_file_gz_chunk(j, gz, in.d_raw[q], gz.pend[q], gz.pend_last[q]); });
+    rd.stop();
+    ss.text_bytes = nullptr; /* it refers to the reader, which ends here */
+    if (rc) return rc;
+    if (header_error) return map_file_member_error(ss, bad_chunk.err.member, bad_chunk.err.offset, bgzf_in_text(bad_chunk.err.status));
+    return ASM_OK;
+}
+
 /* sort_cap: NULL for asm_map_file, max_device_bytes for asm_map_file_sorted */
 static int map_file_run(asm_handle* h, const char* who, const asm_index* ix, const char* const* seq_names, const char* fastq_path,
                         const char* sam_path, const char* header, const asm_map_params* p, int max_hits, int strata, size_t chunk,
@@ -329,9 +489,24 @@ static int map_file_run(asm_handle* h, const char* who, const asm_index* ix, con
     StreamInput& in = ss.in;
     size_t file_bytes = 0;
     if (const int rc = in.open_file(fastq_path, &file_bytes)) return rc;
+    /* the first bytes: a BGZF member (the compressed path), plain gzip (refused), or text.  For the single-end calls only, so it
+     * stands here and not in MapFileSession::open, whose first-byte probe (FASTA) the pairs call shares; text goes on as before */
+    uint8_t probe[4096];
+    const size_t probed = file_bytes ? (size_t)std::max<ssize_t>(pread(in.fd, probe, std::min(file_bytes, sizeof probe), 0), 0) : 0;
+    const bool gzip = probed >= 2 && probe[0] == 0x1fu && probe[1] == 0x8bu;
+    if (gzip && bgzf_is_plain_gzip(probe, probed))
+        return ss.bad(std::string(fastq_path) + " is plain gzip, not BGZF (no BC subfield in its first member): recompress it with bgzip",
+                      ASM_EUNSUPPORTED);
     if (const int rc = ss.open(ix, seq_names, 1, &in.fd, &file_bytes, &fastq_path, sam_path, header)) return rc;
-    asm_host::ChunkReader<asm_host::FastqFill> rd(chunk, ss.first_chunk, in.wait_shipped(), in.fd, file_bytes, chunk, ss.grow());
     MapReadsFileJob j = {{ss, ix, p}, max_hits, strata};
+    if (gzip) {
+        if (const int rc = map_file_run_gz(ss, j, fastq_path, file_bytes)) return rc;
+        if (const int rf = ss.finish(j.st)) return rf;
+        if (stats) *stats = j.st;
+        if (sort_stats && ss.sort) *sort_stats = ss.sort->st;
+        return ASM_OK;
+    }
+    asm_host::ChunkReader<asm_host::FastqFill> rd(chunk, ss.first_chunk, in.wait_shipped(), in.fd, file_bytes, chunk, ss.grow());
     const int rc = ss.run(
         rd, std::string(who) + ": reading " + fastq_path + " failed",
         [&](const asm_host::ChunkSlot& s, int64_t records_seen) {

@@ -525,6 +525,24 @@ int asm_map_get_bgzf_level(const asm_handle* h);
 int asm_bgzf_compress(asm_handle* h, const void* src, size_t n, int with_eof, int level, void* dst, size_t dst_cap, size_t* dst_len);
 int asm_bgzf_compress_host(const void* src, size_t n, int with_eof, int level, void* dst, size_t dst_cap, size_t* dst_len);
 
+/* The container read back (docs/design/mapper.md, "Compressed input"): a BGZF file is a sequence of gzip members of at most 64 KiB,
+ * each with its compressed size (BSIZE) in a BC extra subfield and its CRC-32 and ISIZE (at most 65 536) behind its deflate stream.
+ * The host finds every member without decoding; the members are decoded independently, one wavefront each, by a complete RFC 1951
+ * decoder (stored, fixed and dynamic blocks, any number of them; zlib's two allowances for the distance code, one code of one bit
+ * or none, and no others).  Empty members are allowed anywhere, the EOF block may be missing, an empty input is an empty output.
+ * Corrupt input (a bad member header, a member reaching past the end, trailing bytes that are no member, a decoder error, an ISIZE or
+ * CRC mismatch) is ASM_EINVAL; asm_last_error names the member's 0-based index, its offset in src and what is wrong; of several bad
+ * members the first is named.  A gzip file that is not BGZF (1f 8b, no BC subfield in its first member) is ASM_EUNSUPPORTED, and the
+ * message says that bgzip makes it usable.  dst is written only when the whole container is sound.
+ *
+ * asm_bgzf_decompressed_size: walks and checks the container's headers and sums ISIZE; host only, nothing is decoded.
+ * asm_bgzf_decompress:        src (host) decoded into dst (host) by bgzf_inflate_kernel; dst_cap below the size is ASM_EINVAL.
+ * asm_bgzf_decompress_host:   the same bytes and the same errors from the host build of the same decoder; no device, no handle.
+ * asm_map_file and asm_map_file_sorted read such a file as it is (below, "Compressed input" at asm_map_file). */
+int asm_bgzf_decompressed_size(const void* src, size_t n, size_t* out_len);
+int asm_bgzf_decompress(asm_handle* h, const void* src, size_t n, void* dst, size_t dst_cap, size_t* dst_len);
+int asm_bgzf_decompress_host(const void* src, size_t n, void* dst, size_t dst_cap, size_t* dst_len);
+
 /* asm_map_file:    a FASTQ file in, a SAM file out (docs/design/mapper.md, "Files: FASTQ in, SAM out"); single-end, synchronous.  The
  *                  file is read in chunks of about chunk_bytes (0: 16 MiB) cut at record boundaries; a chunk is parsed, mapped
  *                  and formatted on the device while the next one is read and copied in and the one before is copied out and
@@ -538,6 +556,19 @@ int asm_bgzf_compress_host(const void* src, size_t n, int with_eof, int level, v
  *                  asm_map_reads_all (strata in [0, 15]) in rank order with NH, HI and XH; seq_names = the n_seqs RNAMEs of the index;
  *                  an unmapped, empty or too long (> ASM_MAP_MAX_READ) read gives the unmapped line; CIGAR is '*' above 64
  *                  operations.  The output does not depend on chunk_bytes or ASM_MAP_CHUNK.
+ *                  Compressed input (asm_map_file and asm_map_file_sorted only; docs/design/mapper.md, "Compressed input"): a file
+ *                  that starts with a BGZF member (what bgzip writes) is inflated on the device, member by member, and its
+ *                  concatenated member outputs are the FASTQ text under the contract above.  Empty members are allowed anywhere,
+ *                  the EOF block included, and the EOF block may be missing; a file that is only an EOF block is an empty file
+ *                  (the header alone is written); CR LF, lines and records may straddle members and chunks.  The SAM or BAM bytes
+ *                  equal those of the same call on the inflated text, for every chunk_bytes (which stays text bytes per chunk),
+ *                  every ASM_MAP_CHUNK and every way the text was cut into members.  bytes_in stays the FASTQ text bytes; every
+ *                  other stats field keeps its meaning.  Corrupt input (a bad member header, a member reaching past the end of the
+ *                  file, trailing bytes that are no member, a decoder error, an ISIZE or CRC mismatch): ASM_EINVAL, asm_last_error
+ *                  names the member's 0-based index and its file offset and says what is wrong; among the errors of one chunk the
+ *                  smallest member is reported, before any record error of that chunk.  A gzip file that is not BGZF (magic 1f 8b,
+ *                  no BC subfield in its first member): ASM_EUNSUPPORTED, the message says that the file is plain gzip and that
+ *                  bgzip makes it usable.  asm_map_pairs_file* and asm_index_build_file read plain text only.
  * asm_fastq_cut:   the length of the longest prefix of buf[0, nbytes) made of whole four-line records (every line ending in LF), and
  *                  how many records that is; no device. */
 typedef struct asm_map_file_stats {
