@@ -52,6 +52,20 @@ NWB_HD uint32_t nwb_pk_shr(uint32_t a, int s) {
 NWB_HD uint32_t nwb_pk_sar(uint32_t a, int s) {
     return __builtin_bit_cast(uint32_t, __builtin_bit_cast(nwb_i16x2, a) >> (nwb_i16x2)((short)s));
 }
+// One v_bitop3_b32 with the truth table TT: bit (4a + 2b + c) of TT is the result for the input bits a, b, c.  Named, not
+// left to the compiler: two-input operations next to it stay the two-input VOP2 forms, which issue in half the cycles of
+// any VOP3 one (docs/design/kernels.md, the opcode prices).
+template <int TT>
+NWB_HD uint32_t nwb_bitop3(uint32_t a, uint32_t b, uint32_t c) {
+    return __builtin_amdgcn_bitop3_b32(a, b, c, TT);
+}
+// x << 1 as v_add_u32 x, x (the compiler writes v_lshlrev_b32, which issues at half the rate of the add)
+NWB_HD uint32_t nwb_dbl(uint32_t x) {
+    uint32_t r;
+    asm("v_add_u32 %0, %1, %1" : "=v"(r) : "v"(x));
+    return r;
+}
+NWB_HD uint32_t nwb_brev(uint32_t x) { return __builtin_bitreverse32(x); }
 #else
 NWB_HD int nwb_popc(uint32_t x) { return __builtin_popcount(x); }
 NWB_HD int nwb_popc64(nwb_u64 x) { return __builtin_popcountll(x); }
@@ -69,7 +83,24 @@ NWB_HD uint32_t nwb_pk_sar(uint32_t a, int s) {
     const uint32_t hi = (uint32_t)((int32_t)(int16_t)(a >> 16) >> s) & 0xFFFFu;
     return lo | (hi << 16);
 }
+template <int TT>
+NWB_HD uint32_t nwb_bitop3(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r = 0u;
+    for (int i = 0; i < 8; i++)
+        if ((TT >> i) & 1) r |= ((i & 4) ? a : ~a) & ((i & 2) ? b : ~b) & ((i & 1) ? c : ~c);
+    return r;
+}
+NWB_HD uint32_t nwb_dbl(uint32_t x) { return x + x; }
+NWB_HD uint32_t nwb_brev(uint32_t x) {
+    x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
+    x = ((x >> 2) & 0x33333333u) | ((x & 0x33333333u) << 2);
+    x = ((x >> 4) & 0x0F0F0F0Fu) | ((x & 0x0F0F0F0Fu) << 4);
+    x = ((x >> 8) & 0x00FF00FFu) | ((x & 0x00FF00FFu) << 8);
+    return (x >> 16) | (x << 16);
+}
 #endif
+// a truth table is written as the expression itself over these three
+constexpr int NWB_A = 0xF0, NWB_B = 0xCC, NWB_C = 0xAA;
 
 // largest banded result that is proven exact in a window of 2C rows (see above)
 NWB_HD int nwb_band_bound(int C, int m, int nn) { return 2 * (C - 1) - (nn > m ? nn - m : m - nn); }
@@ -235,14 +266,23 @@ NWB_HD int nw_band(const uint32_t (&A0)[ND + 2], const uint32_t (&A1)[ND + 2], c
 // --------------------------------------------------------------------------------------------------------
 // Two pairs per thread: pair P's 16-row window in bits 0-15 of every vector, pair Q's in bits 16-31, the fused penalty-only
 // form of nw_band<> above with C = 8.  Both pairs stand at the same column, so every shift count is wave-uniform:
-//   * the add (Eq & VPin) + VPin is the packed 16-bit add, D0 >> 1 and the other shifts are packed shifts: no carry and no
-//     bit passes from one pair's half into the other's; TOP is 0x80008000;
-//   * strings are consumed in 16-bit chunks, chunk k of P below chunk k of Q (nwb_chunk2).  A column's pattern window is cut
-//     out of two adjacent chunks U, V of each plane as (U >> s) | ((V << 1) << (15 - s)), in two runs per 16-column block as
-//     in nw_band<>: the window starts in chunk bq-1 for the first 7 columns of block bq and in chunk bq from there on;
-//   * the text character's bits become all-ones / all-zeros halves by a shift left by 15 - r and an arithmetic shift right
-//     by 15;
-//   * the bottom-row diagonal deltas of a block are collected per half in `acc` and counted once per block.
+//   * the add (Eq & VPin) + VPin is the packed 16-bit add and D0 >> 1 the packed shift: no carry and no bit passes from
+//     one pair's half into the other's.  Bit 15 of each half of VPin is always 1 (the row entering at the bottom) and of VNin
+//     always 0; that makes HP's top bits 0, and with the zero that the packed D0 >> 1 shifts in, HN | ~((D0 >> 1) | HP) has
+//     its top bits set without an OR of its own;
+//   * strings are consumed in 16-bit chunks, chunk k of P below chunk k of Q (nwb_chunk2).  The pattern windows of a run of
+//     columns start in one chunk k (chunk bq-1 for the first 7 columns of block bq, chunk bq from there on, as in
+//     nw_band<>): column s of the run wants bits s..s+15 of P's string from chunk k on in the low half and the same bits of
+//     Q's in the high half.  Seen as 64 bits, that is bits s..s+31 of { Q's chunk k+1 : Q's chunk k : P's chunks k+1, k }
+//     with P's bits up to 16+s and Q's from there on: one v_bfi_b32 with a constant mask picks the low dword out of P's 32
+//     bits (nwb_run32) and the packed chunk, one v_alignbit_b32 cuts the window;
+//   * the text chunk is packed the other way round (Q below P) and bit-reversed, so that column r's bits stand at bits 15
+//     and 31 after r doublings; one packed arithmetic shift right by 15 makes them all-ones / all-zeros halves.  What the
+//     doubling carries from the low half into the high one stays below the bit that is read;
+//   * the bottom-row diagonal deltas of a block are collected in `acc`, P's entering at bit 15 and Q's at bit 31 and moving
+//     down one bit per column with a plain 32-bit shift: within the 16 columns of a block Q's bits stay above bit 15.  They
+//     are counted once per block.
+// Which opcode does what is chosen by price (docs/design/kernels.md): 13 VOP3 and 8 VOP2 instructions per column of both pairs.
 // The two pairs have their own m and n.  Columns run to max(nP, nQ).  Blocks that lie wholly inside both texts take the plain
 // column; from the block that holds min(nP, nQ) on, a column keeps the state of a half whose text has ended (FREEZE), so
 // that each half's (VPin, VNin, S) is left as of its own last column.  Each half is then read out with its own m and n as in
@@ -254,6 +294,24 @@ NWB_HD uint32_t nwb_chunk2(const uint32_t (&P)[N], const uint32_t (&Q)[N], int k
     const uint32_t p = P[k >> 1], q = Q[k >> 1];
     return (k & 1) ? (p >> 16) | (q & 0xFFFF0000u) : (p & 0xFFFFu) | (q << 16);
 }
+// chunks k and k+1 of one string as a dword (chunks outside the string's ND dwords are zero; k >= -1)
+template <int ND, int N>
+NWB_HD uint32_t nwb_run32(const uint32_t (&P)[N], int k) {
+    const int d = k < 0 ? -1 : k >> 1; /* the dword that holds chunk k in its low (k even) or high half */
+    const uint32_t lo = d >= 0 && d < ND ? P[d >= 0 && d < ND ? d : 0] : 0u;
+    if (!(k & 1)) return lo;
+    const uint32_t hi = d + 1 >= 0 && d + 1 < ND ? P[d + 1 >= 0 && d + 1 < ND ? d + 1 : 0] : 0u;
+    return nwb_alignbit(hi, lo, 16);
+}
+// a dword whose low 16 bits are chunk k of the string (zero outside it); the upper bits are arbitrary
+template <int ND, int N>
+NWB_HD uint32_t nwb_low16(const uint32_t (&P)[N], int k) {
+    if (k < 0 || k >= 2 * ND) return 0u;
+    return (k & 1) ? P[k >> 1] >> 16 : P[k >> 1];
+}
+struct NoBlockSink {
+    NWB_HD void operator()(int, uint32_t, uint32_t, int, int) const {}
+};
 
 // one half's result from its final vectors (in its last column's own window), as the tail of nw_band<>
 NWB_HD int nwb_band16_result(uint32_t vp, uint32_t vn, int S, int m, int nn) {
@@ -266,11 +324,13 @@ NWB_HD int nwb_band16_result(uint32_t vp, uint32_t vn, int S, int m, int nn) {
     return result <= nwb_band_bound(C, m, nn) ? result : -1;
 }
 
-template <int ND, int NA> /* plane dwords per string, as nw_band<>; A0/A1 the read's planes (NA >= ND dwords: the padding of
-                             nw_band<> is accepted and not read), B0/B1 the reference's */
+// `block_sink(bq, VPin, VNin, Sp, Sq)` sees the state after every 16-column block (the host check compares it)
+template <int ND, int NA, typename BlockSink = NoBlockSink> /* plane dwords per string, as nw_band<>; A0/A1 the read's planes (NA >= ND
+                             dwords: the padding of nw_band<> is accepted and not read), B0/B1 the reference's */
 NWB_HD void nw_band2x16(const uint32_t (&A0p)[NA], const uint32_t (&A1p)[NA], const uint32_t (&B0p)[ND],
                         const uint32_t (&B1p)[ND], int mp, int np, const uint32_t (&A0q)[NA], const uint32_t (&A1q)[NA],
-                        const uint32_t (&B0q)[ND], const uint32_t (&B1q)[ND], int mq, int nq, int& result_p, int& result_q) {
+                        const uint32_t (&B0q)[ND], const uint32_t (&B1q)[ND], int mq, int nq, int& result_p, int& result_q,
+                        const BlockSink& block_sink = BlockSink()) {
     constexpr int W = 16, C = 8, CB = C - 1;
     constexpr int NBLK = 2 * ND; /* 16-column blocks */
     constexpr uint32_t TOP = 0x80008000u, ONE = 0x00010001u, LOW = 0x0000FFFFu, HIGH = 0xFFFF0000u;
@@ -304,31 +364,45 @@ NWB_HD void nw_band2x16(const uint32_t (&A0p)[NA], const uint32_t (&A1p)[NA], co
     // columns C+1..max(nP, nQ), fused form: the vectors are kept in the NEXT column's window (see nw_band<>).  Bit 0 of VP is
     // lost on the way there and back; it is never above row m.
     uint32_t VPin = nwb_pk_shr(VP, 1) | TOP, VNin = nwb_pk_shr(VN, 1);
-#define NW2_COLUMNS(FREEZE, RA, RB, U0, V0, U1, V1, SHB)                                                   \
-    {                                                                                                       \
-        const uint32_t v0s = nwb_pk_shl(V0, 1), v1s = nwb_pk_shl(V1, 1);                                    \
-        for (int r = (RA); r < (RB); r++) {                                                                 \
-            const int s = r + (SHB); /* 0..15 */                                                            \
-            const uint32_t lo0 = nwb_pk_shr(U0, s) | nwb_pk_shl(v0s, 15 - s);                               \
-            const uint32_t lo1 = nwb_pk_shr(U1, s) | nwb_pk_shl(v1s, 15 - s);                               \
-            const uint32_t T0 = nwb_pk_sar(nwb_pk_shl(b0, 15 - r), 15), T1 = nwb_pk_sar(nwb_pk_shl(b1, 15 - r), 15); \
-            const uint32_t Eq = ~((lo0 ^ T0) | (lo1 ^ T1));                                                 \
-            const uint32_t D0 = ((nwb_pk_add(Eq & VPin, VPin) ^ VPin) | Eq) | VNin;                         \
-            const uint32_t HP = VNin | ~(D0 | VPin);                                                        \
-            const uint32_t HN = VPin & D0;                                                                  \
-            const uint32_t D0s = nwb_pk_shr(D0, 1);                                                         \
-            if (FREEZE) {                                                                                   \
-                const int col = W * bq + r;                                                                 \
-                const uint32_t L = (col < np ? LOW : 0u) | (col < nq ? HIGH : 0u);                          \
-                acc = nwb_pk_shr(acc, 1) | (D0 & TOP & L);                                                  \
-                VPin = ((HN | ~(D0s | HP) | TOP) & L) | (VPin & ~L);                                        \
-                VNin = ((HP & D0s) & L) | (VNin & ~L);                                                      \
-            } else {                                                                                        \
-                acc = nwb_pk_shr(acc, 1) | (D0 & TOP);                                                      \
-                VPin = HN | ~(D0s | HP) | TOP;                                                              \
-                VNin = HP & D0s;                                                                            \
-            }                                                                                               \
-        }                                                                                                   \
+    constexpr int TT_EQ = ~((NWB_A ^ NWB_B) | NWB_C) & 0xFF;  /* ~((w0 ^ T0) | x1) */
+    constexpr int TT_D0 = ((NWB_A ^ NWB_B) | NWB_C) & 0xFF;   /* (sum ^ VPin) | Eq */
+    constexpr int TT_ORN = (NWB_A | ~(NWB_B | NWB_C)) & 0xFF; /* a | ~(b | c) */
+    constexpr int TT_ACC = ((NWB_A & NWB_B) | NWB_C) & 0xFF;  /* (D0 & TOP) | acc */
+    constexpr int TT_SEL = ((NWB_A & NWB_B) | (~NWB_A & NWB_C)) & 0xFF; /* a ? b : c */
+    // the columns RA..RB-1 of block bq, whose windows start in pattern chunk K: column r wants bits s..s+15, s = r + SHB
+#define NW2_COLUMNS(FREEZE, RA, RB, K, SHB)                                                                      \
+    {                                                                                                             \
+        const uint32_t rp0 = nwb_run32<ND>(A0p, (K)), rp1 = nwb_run32<ND>(A1p, (K));                              \
+        const uint32_t u0 = nwb_chunk2<ND>(A0p, A0q, (K)), u1 = nwb_chunk2<ND>(A1p, A1q, (K));                    \
+        const uint32_t hq0 = nwb_low16<ND>(A0q, (K) + 1), hq1 = nwb_low16<ND>(A1q, (K) + 1);                      \
+        for (int r = (RA); r < (RB); r++) {                                                                       \
+            const int s = r + (SHB);                        /* 0..15 */                                           \
+            const uint32_t keep = (0x10000u << s) - 1u;     /* P's bits of the 64-bit run's low dword */           \
+            const uint32_t w0 = nwb_alignbit(hq0, nwb_bitop3<TT_SEL>(keep, rp0, u0), (uint32_t)s);                \
+            const uint32_t w1 = nwb_alignbit(hq1, nwb_bitop3<TT_SEL>(keep, rp1, u1), (uint32_t)s);                \
+            const uint32_t T0 = nwb_pk_sar(y0, 15), T1 = nwb_pk_sar(y1, 15);                                      \
+            y0 = nwb_dbl(y0), y1 = nwb_dbl(y1);                                                                   \
+            const uint32_t x1 = w1 ^ T1;                                                                          \
+            const uint32_t Eq = nwb_bitop3<TT_EQ>(w0, T0, x1);                                                    \
+            const uint32_t sum = nwb_pk_add(Eq & VPin, VPin);                                                     \
+            const uint32_t D0a = nwb_bitop3<TT_D0>(sum, VPin, Eq); /* D0 but for VNin, which HP and HN do not need: */ \
+            const uint32_t HP = nwb_bitop3<TT_ORN>(VNin, D0a, VPin); /* VNin | ~(D0 | VPin) */                     \
+            const uint32_t HN = VPin & D0a;                          /* VPin & VNin == 0 */                        \
+            const uint32_t D0s = nwb_pk_shr(D0a | VNin, 1);                                                       \
+            const uint32_t VPn = nwb_bitop3<TT_ORN>(HN, D0s, HP); /* both top bits come out set, see above */      \
+            const uint32_t VNn = HP & D0s;                                                                        \
+            if (FREEZE) {                                                                                         \
+                const int col = W * bq + r;                                                                       \
+                const uint32_t L = (col < np ? LOW : 0u) | (col < nq ? HIGH : 0u);                                \
+                acc = nwb_bitop3<TT_ACC>(D0a, TOP & L, acc >> 1); /* VNin's top bits are 0: D0a's are D0's */      \
+                VPin = (VPn & L) | (VPin & ~L);                                                                   \
+                VNin = (VNn & L) | (VNin & ~L);                                                                   \
+            } else {                                                                                              \
+                acc = nwb_bitop3<TT_ACC>(D0a, TOP, acc >> 1);                                                     \
+                VPin = VPn;                                                                                       \
+                VNin = VNn;                                                                                       \
+            }                                                                                                     \
+        }                                                                                                         \
     }
     if (nmax > C) {
 #pragma unroll
@@ -337,17 +411,16 @@ NWB_HD void nw_band2x16(const uint32_t (&A0p)[NA], const uint32_t (&A1p)[NA], co
             int rend = nmax - W * bq;
             rend = rend > W ? W : rend;
             if (rend <= r0) continue;
-            const uint32_t b0 = nwb_chunk2<ND>(B0p, B0q, bq), b1 = nwb_chunk2<ND>(B1p, B1q, bq);
-            // pattern chunks bq-1, bq, bq+1 of both planes (zeros outside the string's dwords)
-            const uint32_t a0m = nwb_chunk2<ND>(A0p, A0q, bq - 1), a0c = nwb_chunk2<ND>(A0p, A0q, bq), a0n = nwb_chunk2<ND>(A0p, A0q, bq + 1);
-            const uint32_t a1m = nwb_chunk2<ND>(A1p, A1q, bq - 1), a1c = nwb_chunk2<ND>(A1p, A1q, bq), a1n = nwb_chunk2<ND>(A1p, A1q, bq + 1);
+            // the text chunk, Q's below P's and bit-reversed: column r's bits are bits 31 - r (P) and 15 - r (Q)
+            uint32_t y0 = nwb_brev(nwb_chunk2<ND>(B0q, B0p, bq)) << r0;
+            uint32_t y1 = nwb_brev(nwb_chunk2<ND>(B1q, B1p, bq)) << r0;
             uint32_t acc = 0u;
             if (W * bq + W <= nmin) { /* the whole block lies inside both texts */
-                if (r0 < CB) NW2_COLUMNS(false, r0, CB, a0m, a0c, a1m, a1c, W - CB)
-                NW2_COLUMNS(false, (r0 > CB ? r0 : CB), W, a0c, a0n, a1c, a1n, -CB)
+                if (r0 < CB) NW2_COLUMNS(false, r0, CB, bq - 1, W - CB)
+                NW2_COLUMNS(false, (r0 > CB ? r0 : CB), W, bq, -CB)
             } else {
-                if (r0 < CB) NW2_COLUMNS(true, r0, (rend < CB ? rend : CB), a0m, a0c, a1m, a1c, W - CB)
-                NW2_COLUMNS(true, (r0 > CB ? r0 : CB), rend, a0c, a0n, a1c, a1n, -CB)
+                if (r0 < CB) NW2_COLUMNS(true, r0, (rend < CB ? rend : CB), bq - 1, W - CB)
+                NW2_COLUMNS(true, (r0 > CB ? r0 : CB), rend, bq, -CB)
             }
             // S += 1 - (the diagonal delta's bit) for every column of this block that the half's text has
             int cp = np - W * bq, cq = nq - W * bq;
@@ -355,6 +428,7 @@ NWB_HD void nw_band2x16(const uint32_t (&A0p)[NA], const uint32_t (&A1p)[NA], co
             cq = (cq > W ? W : (cq < r0 ? r0 : cq)) - r0;
             Sp += cp - nwb_popc(acc & LOW);
             Sq += cq - nwb_popc(acc >> 16);
+            block_sink(bq, VPin, VNin, Sp, Sq);
         }
     }
 #undef NW2_COLUMNS

@@ -105,7 +105,9 @@ def isa_mix(kernel_name, rows):
              "v_cndmask_b32": "k_cmp_cnd", "v_perm_b32": "k_perm", "v_dot4_u32_u8": "k_dot4", "v_bitop3_b32": "k_bitop3",
              "v_lshlrev_b64": "k_shl64", "v_lshrrev_b64": "k_shr64v", "v_lshl_add_u64": "k_add64", "v_fma_f64": "k_fma64",
              "v_mul_f64": "k_mul64", "v_cvt_f64_i32": "k_cvt", "v_readlane_b32": "k_readlane", "v_mbcnt_lo_u32_b32": "k_mbcnt",
-             "v_mbcnt_hi_u32_b32": "k_mbcnt"}
+             "v_mbcnt_hi_u32_b32": "k_mbcnt", "v_pk_lshlrev_b16": "k_pk_shl_c", "v_pk_lshrrev_b16": "k_pk_shr_c",
+             "v_pk_ashrrev_i16": "k_pk_sar_c", "v_pk_add_u16": "k_pk_add", "v_pk_sub_i16": "k_pk_sub", "v_med3_u32": "k_med3_u",
+             "v_bfe_i32": "k_bfe_i", "v_bfrev_b32": "k_bfrev", "v_add_co_u32": "k_add_co", "v_addc_co_u32": "k_addc_co"}
     total = weighted = 0.0
     unknown = collections.Counter()
     for op, cnt in valu.items():

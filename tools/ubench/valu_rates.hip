@@ -115,6 +115,24 @@ BENCH32(k_perm, "v_perm_b32 %0, %0, %1, %1")
 BENCH32(k_dot4, "v_dot4_u32_u8 %0, %0, %1, %0")
 BENCH32(k_bitop3, "v_bitop3_b32 %0, %0, %1, %1 bitop3:0x48")
 BENCH32(k_sad, "v_sad_u8 %0, %0, %1, %0")
+// the packed 16-bit instructions of nw_band2x16 (csrc/asm_nwband.h) and the other NW opcodes: shift counts from a VGPR and
+// in the compiler's form for a constant count (an inline constant for the low half, op_sel_hi:[0,1] repeats it for the high one)
+BENCH32(k_pk_shl, "v_pk_lshlrev_b16 %0, %1, %0")
+BENCH32(k_pk_shr, "v_pk_lshrrev_b16 %0, %1, %0")
+BENCH32(k_pk_sar, "v_pk_ashrrev_i16 %0, %1, %0")
+BENCH32(k_pk_shl_c, "v_pk_lshlrev_b16 %0, 1, %0 op_sel_hi:[0,1]")
+BENCH32(k_pk_shr_c, "v_pk_lshrrev_b16 %0, 1, %0 op_sel_hi:[0,1]")
+BENCH32(k_pk_sar_c, "v_pk_ashrrev_i16 %0, 15, %0 op_sel_hi:[0,1]")
+BENCH32(k_pk_add, "v_pk_add_u16 %0, %0, %1")
+BENCH32(k_pk_sub, "v_pk_sub_i16 %0, %0, %1")
+BENCH32(k_med3_u, "v_med3_u32 %0, %0, %1, %1")
+BENCH32(k_bfe_i, "v_bfe_i32 %0, %0, 3, 1")
+BENCH32(k_shl_c, "v_lshlrev_b32 %0, 1, %0")
+BENCH32(k_shr_c, "v_lshrrev_b32 %0, 1, %0")
+BENCH32(k_alignbit_c, "v_alignbit_b32 %0, %0, %1, 5")
+BENCH32(k_bfrev, "v_bfrev_b32 %0, %0")
+BENCH32(k_add_co, "v_add_co_u32 %0, vcc, %0, %1")
+BENCH32(k_addc_co, "v_addc_co_u32 %0, vcc, %0, %1, vcc")
 BENCH32(k_dpp_mov, "v_mov_b32_dpp %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf")
 BENCH32(k_dpp_wave, "v_mov_b32_dpp %0, %0 wave_shr:1 row_mask:0xf bank_mask:0xf")
 BENCH32(k_readlane, "v_readlane_b32 s20, %0, 3\n\tv_xor_b32 %0, s20, %0")
@@ -197,6 +215,8 @@ int main() {
     R(k_add); R(k_and); R(k_shl); R(k_shr_v); R(k_and_or); R(k_or3); R(k_lshl_or); R(k_add3); R(k_xad); R(k_bfe); R(k_bfi);
     R(k_ffbl); R(k_ffbh); R(k_bcnt); R(k_min); R(k_max_i); R(k_med3); R(k_max3); R(k_mul_lo); R(k_mul24); R(k_mad24);
     run("k_cmp_cnd", k_cmp_cnd, 2); run("k_cmp_s", k_cmp_s, 2); R(k_not); R(k_mbcnt); R(k_perm); R(k_dot4); R(k_bitop3); R(k_sad);
+    R(k_pk_shl); R(k_pk_shr); R(k_pk_sar); R(k_pk_shl_c); R(k_pk_shr_c); R(k_pk_sar_c); R(k_pk_add); R(k_pk_sub);
+    R(k_med3_u); R(k_bfe_i); R(k_shl_c); R(k_shr_c); R(k_alignbit_c); R(k_bfrev); R(k_add_co); R(k_addc_co);
     R(k_dpp_mov); R(k_dpp_wave);
     run("k_readlane", k_readlane, 2);
     R(k_shl64); R(k_shr64); R(k_add64); R(k_fma64); R(k_mul64); R(k_cvt);
