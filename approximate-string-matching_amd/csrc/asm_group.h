@@ -10,9 +10,9 @@
 // The group agrees on the best lane with DPP butterflies that stay inside T lanes (quad_perm, row_half_mirror, row_mirror:
 // no LDS, no barriers), and fetches the winner's highway with ds_bpermute.
 //
-// Same step structure and results as greedy_kernel<K> (hurdle_matrix.h:285-434,568-597): _update_highway_list in two
-// passes (the `reaching_destination` flag of pass 1 changes every lane's score in pass 2), _choose_best_highway as an
-// ordered fold over the few lanes that can still be accepted, _step commit, final hop.
+// The step's rules are asm_greedy_lane.h's (hurdle_matrix.h:285-434,568-597): _update_highway_list in two passes (the
+// `reaching_destination` flag of pass 1 changes every lane's score in pass 2), _choose_best_highway as an ordered fold over
+// the few lanes that can still be accepted, _step commit, final hop.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -58,15 +58,11 @@ __global__ __launch_bounds__(ASM_BLOCK, (LPT <= 3 ? 4 : LPT <= 5 ? 3 : 2)) void 
     const long ngroups = ((long)gridDim.x * blockDim.x) / T;
     const int nl = 2 * k + 1;
     const int j0 = r * LPT;           /* this thread's band lanes are j0 .. j0+LPT-1, lane = j - k */
-    const int x = args.x, o = args.o, e = args.e;
-    const bool semi = args.semi != 0;
+    const GreedyCosts pen = {args.x, args.o, args.e, args.semi != 0};
 
     for (long i = group0; i < n; i += ngroups) {
-        const uint32_t ln = lens[i];
-        int m = (int)(ln & 0xffffu), nn = (int)(ln >> 16);
-        m = m > 128 ? 128 : m; /* hurdle_matrix.h:626-627 */
-        nn = nn > 128 ? 128 : nn;
-        const int dest_lane = nn - m;
+        int m, nn, dest_lane;
+        greedy_lengths(lens[i], m, nn, dest_lane);
         V128 lo_[LPT]; /* the flipped vector (lanes, hurdle_matrix.h:452-453) is rebuilt from lo_ where a highway is looked up */
         int sp[LPT], len[LPT], nsw[LPT];
         {   /* the planes are only needed to build the lane vectors (and once more for the final hop: re-read there) */
@@ -91,26 +87,22 @@ __global__ __launch_bounds__(ASM_BLOCK, (LPT <= 3 ? 4 : LPT <= 5 ? 3 : 2)) void 
             // ---- _update_highway_list, pass 1: refresh the cached highways, hurdle counts ----
             int sw[LPT], nh[LPT];
             bool reach = false;
-            const bool first_free = semi && guard == 0;
+            const bool first_free = pen.semi && guard == 0;
 #pragma unroll
             for (int q = 0; q < LPT; q++) {
                 const int lane = j0 + q - k;
                 const bool valid = j0 + q < nl;
-                const int start_col = cur_col + fwd_col(cur_lane, lane);
+                const int start_col = greedy_start_col(cur_lane, cur_col, lane);
                 const bool stale = sp[q] < start_col;
-                const int dd = lane - cur_lane;
                 int fz, nx;
                 v_highway_from(v_flip_short_hurdles1(lo_[q]), start_col, fz, nx);
-                const int nsp = start_col + fz;
-                const int room = lane_destination(m, nn, lane) - nsp;
-                const bool hits = nsp + nx > nsp + room; /* start_col + fz + nx > destination */
-                const int nlen = hits ? (room > 0 ? room : 0) : nx;
-                sp[q] = stale ? nsp : sp[q];
-                len[q] = stale ? nlen : len[q];
-                nsw[q] = stale ? (dd < 0 ? -dd : dd) : nsw[q];
-                reach = reach || (stale && hits && valid);
-                sw[q] = first_free ? 0 : lane_penalty(cur_lane, lane, o, e);
-                nh[q] = v_pop_between(lo_[q], start_col, sp[q] + len[q]);
+                const GreedyHighway h = greedy_highway_at(start_col, fz, nx, lane_destination(m, nn, lane));
+                sp[q] = stale ? h.sp : sp[q];
+                len[q] = stale ? h.len : len[q];
+                nsw[q] = stale ? greedy_lane_distance(lane, cur_lane) : nsw[q];
+                reach = reach || (stale && h.reach && valid);
+                sw[q] = greedy_switch_cost(first_free, cur_lane, lane, pen.o, pen.e);
+                nh[q] = greedy_hurdles(lo_[q], start_col, sp[q], len[q]);
             }
             const bool reaching = group_max_u32<T>(reach ? 1u : 0u) != 0u;
             // ---- pass 2: scores; the thread's own best lane (first lane wins exact ties, hurdle_matrix.h:345-351) ----
@@ -119,21 +111,14 @@ __global__ __launch_bounds__(ASM_BLOCK, (LPT <= 3 ? 4 : LPT <= 5 ? 3 : 2)) void 
 #pragma unroll
             for (int q = 0; q < LPT; q++) {
                 const int lane = j0 + q - k;
-                const int hc = x * nh[q];
-                const int fsw = semi ? 0 : lane_penalty(lane, dest_lane, o, e);
-                const double h_sig = greedy_significance(args, len[q], nh[q], nsw[q]);
-                const double h_dst = (double)(-sw[q] - hc - fsw - x * (lane_destination(m, nn, lane) - sp[q] - len[q]));
-                const double heur = reaching ? h_dst : h_sig;
-                const int leap = reaching ? -sw[q] - fsw : -sw[q];
-                const bool take = (j0 + q < nl) && (bq < 0 || heur > bheur || (heur == bheur && leap > bleap));
+                double heur;
+                int leap;
+                greedy_score(args, pen, reaching, lane, dest_lane, lane_destination(m, nn, lane), sp[q], len[q], nsw[q], sw[q], nh[q], heur, leap);
+                const bool take = (j0 + q < nl) && (bq < 0 || greedy_beats(heur, leap, bheur, bleap));
                 bheur = take ? heur : bheur, bleap = take ? leap : bleap, bq = take ? q : bq;
             }
             // ---- arg-max over the group: order-preserving integer keys, three T-lane butterflies ----
-            unsigned long long bkey = 0ull;
-            if (bq >= 0) {
-                const unsigned long long hb = (unsigned long long)__double_as_longlong(bheur + 0.0); /* -0.0 -> +0.0: equal values, equal keys */
-                bkey = (hb >> 63) ? ~hb : (hb | 0x8000000000000000ull);
-            }
+            const unsigned long long bkey = bq >= 0 ? greedy_score_key(bheur) : 0ull;
             bq = bq < 0 ? 0 : bq;
             const unsigned khi = (unsigned)(bkey >> 32);
             const unsigned mhi = group_max_u32<T>(khi);
@@ -141,26 +126,23 @@ __global__ __launch_bounds__(ASM_BLOCK, (LPT <= 3 ? 4 : LPT <= 5 ? 3 : 2)) void 
             const unsigned klo = cand ? (unsigned)bkey : 0u;
             const unsigned mlo = group_max_u32<T>(klo);
             cand = cand && klo == mlo && bkey != 0ull;
-            const unsigned k3 = cand ? ((((unsigned)(bleap + 32768)) << 7) | (unsigned)(127 - (j0 + bq))) : 0u;
-            const unsigned m3 = group_max_u32<T>(k3);
-            const int bj = 127 - (int)(m3 & 127u); /* winning band lane, group-uniform */
+            const unsigned m3 = group_max_u32<T>(cand ? greedy_tie_key<7>(bleap, j0 + bq) : 0u);
+            const int bj = greedy_tie_key_slot<7>(m3); /* winning band lane, group-uniform */
             const int best = bj - k;
             const int owner = gbase + bj / LPT;
             // the owner's best lane IS the winner: every thread offers its own best lane's highway, all read the owner's
-            int o_sp = sp[0], o_len = len[0], o_cost = sw[0] + x * nh[0];
+            int o_sp = sp[0], o_len = len[0], o_cost = sw[0] + pen.x * nh[0];
             V128 o_vec = lo_[0];
 #pragma unroll
             for (int q = 1; q < LPT; q++) {
                 const bool is = bq == q;
-                o_sp = is ? sp[q] : o_sp, o_len = is ? len[q] : o_len, o_cost = is ? sw[q] + x * nh[q] : o_cost;
+                o_sp = is ? sp[q] : o_sp, o_len = is ? len[q] : o_len, o_cost = is ? sw[q] + pen.x * nh[q] : o_cost;
                 o_vec.lo = is ? lo_[q].lo : o_vec.lo, o_vec.hi = is ? lo_[q].hi : o_vec.hi;
             }
             const int best_sp = lane_fetch(o_sp, owner), best_len = lane_fetch(o_len, owner);
             const int best_cost = lane_fetch(o_cost, owner);
             if (best_len <= 0) break; /* hurdle_matrix.h:358-361 — uniform across the group */
-            const V128 best_vec =
-                v_make((u64)(unsigned)lane_fetch((int)(unsigned)o_vec.lo, owner) | ((u64)(unsigned)lane_fetch((int)(o_vec.lo >> 32), owner) << 32),
-                       (u64)(unsigned)lane_fetch((int)(unsigned)o_vec.hi, owner) | ((u64)(unsigned)lane_fetch((int)(o_vec.hi >> 32), owner) << 32));
+            const V128 best_vec = v_fetch_lane(o_vec, [owner](int w) { return lane_fetch(w, owner); });
             // ---- _choose_best_highway: lanes that can still be accepted (thresholds only go down from best_cost) ----
             const int best_from_sp = v_ones_from(best_vec, best_sp);
             int ti[LPT]; /* total << 16 | inter of the lanes that can still be accepted */
@@ -169,10 +151,9 @@ __global__ __launch_bounds__(ASM_BLOCK, (LPT <= 3 ? 4 : LPT <= 5 ? 3 : 2)) void 
             for (int q = 0; q < LPT; q++) {
                 const int lane = j0 + q - k;
                 const int fb = fwd_col(lane, best);
-                const int inter = sw[q] + nh[q]; /* not multiplied by x (hurdle_matrix.h:388) */
-                const int tail = x * v_pop_between_pre(best_vec, fb + sp[q] + len[q], best_sp, best_from_sp);
-                const int total = inter + lane_penalty(lane, best, o, e) + (tail > 0 ? tail : 0);
-                const bool can = (j0 + q < nl) && lane != best && !(sp[q] + fb > best_sp) && total <= best_cost && inter <= best_cost;
+                const int inter = greedy_cand_inter(sw[q], nh[q]);
+                const int total = greedy_cand_total(pen, lane, best, fb, sp[q], len[q], inter, best_vec, best_sp, best_from_sp);
+                const bool can = (j0 + q < nl) && greedy_cand_reachable(lane, best, fb, sp[q], best_sp) && total <= best_cost && inter <= best_cost;
                 ti[q] = (total << 16) | (inter & 0xffff);
                 cmask |= can ? 1u << q : 0u;
             }
@@ -184,42 +165,28 @@ __global__ __launch_bounds__(ASM_BLOCK, (LPT <= 3 ? 4 : LPT <= 5 ? 3 : 2)) void 
                 const unsigned top = group_max_u32<T>(mine);
                 if (top == 0u) break; /* group-uniform */
                 const int cj = 127 - (int)top, cq = cj % LPT, cown = gbase + cj / LPT;
-                int c_ti = ti[0], c_sp = sp[0], c_len = len[0], c_cost = sw[0] + x * nh[0];
+                int c_ti = ti[0], c_sp = sp[0], c_len = len[0], c_cost = sw[0] + pen.x * nh[0];
 #pragma unroll
                 for (int q = 1; q < LPT; q++) {
                     const bool is = cq == q;
                     c_ti = is ? ti[q] : c_ti, c_sp = is ? sp[q] : c_sp, c_len = is ? len[q] : c_len;
-                    c_cost = is ? sw[q] + x * nh[q] : c_cost;
+                    c_cost = is ? sw[q] + pen.x * nh[q] : c_cost;
                 }
                 c_ti = lane_fetch(c_ti, cown);
-                const int c_tot = c_ti >> 16, c_itr = c_ti & 0xffff;
-                if (c_tot <= small_total && c_itr <= small_inter) {
-                    small_total = c_tot, small_inter = c_itr, ch = cj;
+                if (greedy_fold_accept(c_ti >> 16, c_ti & 0xffff, small_total, small_inter)) {
+                    ch = cj;
                     ch_sp = lane_fetch(c_sp, cown), ch_len = lane_fetch(c_len, cown), ch_cost = lane_fetch(c_cost, cown);
                 }
                 if (t == cown) cmask &= cmask - 1u;
             }
-            // ---- _step commit (hurdle_matrix.h:411-433) ----
-            cost += ch_cost;
-            const int new_lane = ch - k, new_col = ch_sp + ch_len;
-            if (cig.on() && r == 0) cig.step(pair, ncig, cur_lane, new_lane, new_col - (cur_col + fwd_col(cur_lane, new_lane)));
-            cur_lane = new_lane;
-            cur_col = new_col;
-            done = cur_col >= lane_destination(m, nn, cur_lane);
+            done = greedy_commit(cig, r == 0, pair, ncig, m, nn, ch - k, ch_sp + ch_len, ch_cost, cur_lane, cur_col, cost);
         }
         if (r == 0) {
-            // ---- final hop (hurdle_matrix.h:575-590); the destination lane may lie outside the band ----
-            const int dest_col = lane_destination(m, nn, dest_lane);
-            if (cur_lane != dest_lane || cur_col < dest_col) {
-                const V128 dv = greedy_lane_vector(v_from_uint4(planes[((long)0 * w4) * n + i]), v_from_uint4(planes[((long)1 * w4) * n + i]),
-                                                   v_from_uint4(planes[((long)2 * w4) * n + i]), v_from_uint4(planes[((long)3 * w4) * n + i]),
-                                                   dest_lane);
-                const int sw_f = semi ? 0 : lane_penalty(cur_lane, dest_lane, o, e);
-                const int distance = v_pop_between(dv, cur_col + fwd_col(cur_lane, dest_lane), dest_col);
-                const int hcf = x * distance;
-                cost += sw_f + (hcf > 0 ? hcf : 0);
-                if (cig.on()) cig.step(pair, ncig, cur_lane, dest_lane, distance);
-            }
+            const auto dest_vec = [&]() { /* the planes are re-read for the destination lane's vector */
+                return greedy_lane_vector(v_from_uint4(planes[((long)0 * w4) * n + i]), v_from_uint4(planes[((long)1 * w4) * n + i]),
+                                          v_from_uint4(planes[((long)2 * w4) * n + i]), v_from_uint4(planes[((long)3 * w4) * n + i]), dest_lane);
+            };
+            greedy_final_hop(pen, cig, true, pair, ncig, m, nn, dest_lane, dest_vec, cur_lane, cur_col, cost);
             if (cig.on()) cig.finish(pair, ncig);
             out.put(i, cost);
         }

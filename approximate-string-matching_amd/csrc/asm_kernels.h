@@ -20,6 +20,7 @@
 #include "asm_affine.h"
 #include "asm_bits.h"
 #include "asm_gen.h"
+#include "asm_greedy_lane.h"
 #include "asm_leapunit.h"
 #include "asm_nwband.h"
 
@@ -263,38 +264,23 @@ __global__ __launch_bounds__(ASM_BLOCK) void invert_order_kernel(const uint32_t*
 }
 
 // --------------------------------------------------------------------------------------------------------
-// Greedy hurdle-matrix aligner, GLOBAL mode, band lanes -K..K in registers, one thread per pair.
-// Follows hurdle_matrix<int_128bit>: _construct_hurdles (hurdle_matrix.h:441-455), _update_highway_list
-// (:285-362), _choose_best_highway (:368-401), _step (:407-434), run (:568-597).  The per-lane cache
-// {starting_point,length,num_switches} persists across steps exactly as highway_info does (:26-44).
+// Greedy hurdle-matrix aligner (hurdle_matrix<int_128bit>), general form: GreedyArgs and every rule of its step are in
+// asm_greedy_lane.h (host-buildable: host/greedy_host_check.cpp); the kernels in asm_wave.h, asm_group.h and asm_wide.h hold the
+// mapping of band lanes to threads and the reductions.  The k <= 3 straight-line form is asm_greedy3.h.
+// greedy_persist_kernel below takes GreedyArgs, the significance, the lane vectors, the start column, the switch cost and the hurdle count
+// from that header and holds the rest of the step written out:
+// its 32 instantiations sit at the edge of the register file (K = 8-10 are held at two waves per SIMD by launch bounds), and on the
+// shared functions the unit-penalty instantiations allocate more registers and K = 10 spills (table in profiles/greedy_lane_ab.txt).
+// Shape (a) of host/greedy_host_check.cpp has the same serial structure but does not execute this kernel's text: a change to a rule is
+// made here as well as in the header.
+
+// A V128 held by another lane of the wave, word by word through the caller's 32-bit fetch (v_readlane, ds_bpermute)
+template <class Fetch32>
+ASM_DEV V128 v_fetch_lane(V128 v, Fetch32 fetch) {
+    return v_make((u64)(unsigned)fetch((int)(unsigned)v.lo) | ((u64)(unsigned)fetch((int)(v.lo >> 32)) << 32),
+                  (u64)(unsigned)fetch((int)(unsigned)v.hi) | ((u64)(unsigned)fetch((int)(v.hi >> 32)) << 32));
+}
 // --------------------------------------------------------------------------------------------------------
-struct GreedyArgs {
-    int x, o, e;
-    int semi; /* SEMI_GLOBAL (hurdle_matrix.h:313-316,335-338,577-580): no switch cost into the first highway, into the
-                 destination lane, or for the final hop */
-    double sig_match, sig_mismatch, sig_indel; /* hurdle_matrix.h:536-538, computed on the host with libm */
-};
-
-// hurdle_matrix.h:328-330.  With the default probabilities mismatch_sig == indel_sig bit for bit, so lanes that
-// trade a hurdle for a lane switch tie up to rounding, and the rounding sequence decides the arg-max.  The
-// reference built with its own flags (-O3 -march=native: GCC contracts a*b+c on FMA hardware) evaluates
-// fma(indel, nsw, fma(mismatch, nh, match*len)); the same three roundings are issued here explicitly.
-ASM_DEV double greedy_significance(const GreedyArgs& a, int len, int nh, int nsw) {
-    return __fma_rn(a.sig_indel, (double)nsw, __fma_rn(a.sig_mismatch, (double)nh, __dmul_rn(a.sig_match, (double)len)));
-}
-
-ASM_DEV V128 greedy_lane_vector(V128 A0, V128 A1, V128 B0, V128 B1, int lane) {
-    const int s = lane < 0 ? -lane : lane;
-    V128 m0, m1;
-    if (lane < 0) {
-        m0 = v_xor(v_toward0(A0, s), B0);
-        m1 = v_xor(v_toward0(A1, s), B1);
-    } else {
-        m0 = v_xor(v_toward0(B0, s), A0);
-        m1 = v_xor(v_toward0(B1, s), A1);
-    }
-    return v_or(m0, m1);
-}
 
 // Wave-local work queue for the persistent kernels: every wave owns a contiguous slice [q_next, q_end) of the batch
 // (static split over the resident waves: ~n/3000 pairs each, so slices are balanced to a few percent) and its lanes pull
@@ -434,7 +420,7 @@ __global__ __launch_bounds__(ASM_BLOCK, GREEDY_PERSIST_MIN_WAVES(K, UNIT)) void 
 #pragma unroll
             for (int j = 0; j < NL; j++) {
                 const int lane = j - K;
-                const int start_col = cur_col + fwd_col(cur_lane, lane);
+                const int start_col = greedy_start_col(cur_lane, cur_col, lane);
                 if (sp[j] < start_col) {
                     int d = lane - cur_lane;
                     nsw[j] = d < 0 ? -d : d;
@@ -448,8 +434,8 @@ __global__ __launch_bounds__(ASM_BLOCK, GREEDY_PERSIST_MIN_WAVES(K, UNIT)) void 
                         reaching = true;
                     }
                 }
-                sw[j] = (semi && guard == 0) ? 0 : lane_penalty(cur_lane, lane, o, e);
-                nh[j] = v_pop_between(lo_[j], start_col, sp[j] + len[j]);
+                sw[j] = greedy_switch_cost(semi && guard == 0, cur_lane, lane, o, e);
+                nh[j] = greedy_hurdles(lo_[j], start_col, sp[j], len[j]);
             }
             double best_h = -__builtin_inf();
             int best_leap = 0; /* -numeric_limits<int>::infinity() == 0 (hurdle_matrix.h:287) */

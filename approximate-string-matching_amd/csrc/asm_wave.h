@@ -434,8 +434,11 @@ __global__ __launch_bounds__(NW_OCT_THREADS) void nw_oct_kernel(const uint4* __r
 }
 
 // --------------------------------------------------------------------------------------------------------
-// Greedy, wave per pair.  Same step structure as greedy_persist_kernel<K> (hurdle_matrix.h:285-434,568-597); lane t of the
-// wave is band lane t - k.
+// Greedy, wave per pair; lane t of the wave is band lane t - k.  The step is asm_greedy_lane.h's (hurdle_matrix.h:285-434,568-597).  The
+// kernel takes from that header what leaves its instruction stream as it was (the lengths, the lane vectors on four words, the hurdle
+// count, the score's key words and the tie key) and holds the refresh, the score, the candidate test, the fold, the commit and the final
+// hop written out: with all of them on the shared functions it came out two scalar instructions longer and 0.7 % slower at C3's k = 30
+// (profiles/greedy_lane_ab.txt, run B).  A change to one of those rules is made here as well as in the header.
 // Round 4 (C3: 13.5 -> see DESIGN.md): the kernel is VALU-issue bound and a wave executes every instruction whether one band
 // lane needs it or sixty-one, so only the instruction COUNT matters.  (i) The lane vectors are built on four 32-bit words: a
 // band lane is at most 31 positions off the main diagonal, so the 128-bit shift of _construct_hurdles is four v_alignbit_b32,
@@ -444,11 +447,6 @@ __global__ __launch_bounds__(NW_OCT_THREADS) void nw_oct_kernel(const uint4* __r
 // thread; (iii) _choose_best_highway's per-lane tail count runs only when some lane passes the tests that need no count
 // (switch + hurdles within the best lane's cost, start not behind the best lane's); (iv) fwd_col without the multiply.
 // --------------------------------------------------------------------------------------------------------
-ASM_DEV uint4 w_toward0_small(uint4 v, uint32_t s /* 0..31 */) { /* utils.h:143-153 on four words, shift below 32 */
-    return make_uint4(__builtin_amdgcn_alignbit(v.y, v.x, s), __builtin_amdgcn_alignbit(v.z, v.y, s),
-                      __builtin_amdgcn_alignbit(v.w, v.z, s), v.w >> s);
-}
-ASM_DEV V128 v_from_words(uint4 q) { return v_from_uint4(q); }
 
 template <bool UNIT> /* UNIT: x = o = e = 1 at compile time */
 __global__ __launch_bounds__(ASM_BLOCK) void greedy_wave_kernel(const uint4* __restrict__ planes,
@@ -471,25 +469,11 @@ __global__ __launch_bounds__(ASM_BLOCK) void greedy_wave_kernel(const uint4* __r
         const long i = list ? (long)list[iq] : iq;
         const uint4 a0 = planes[((long)0 * w4) * n + i], a1 = planes[((long)1 * w4) * n + i];
         const uint4 b0 = planes[((long)2 * w4) * n + i], b1 = planes[((long)3 * w4) * n + i];
-        const uint32_t ln = lens[i];
-        int m = (int)(ln & 0xffffu), nn = (int)(ln >> 16);
-        m = m > 128 ? 128 : m; /* hurdle_matrix.h:626-627 */
-        nn = nn > 128 ? 128 : nn;
-        const int dest_lane = nn - m;
-        // ---- _construct_hurdles (hurdle_matrix.h:441-455): lane < 0 compares A[i + |lane|] with B[i], lane >= 0 B[i + lane] with A[i]
+        int m, nn, dest_lane;
+        greedy_lengths(lens[i], m, nn, dest_lane);
+        // ---- _construct_hurdles and the flipped vector, on four words (asm_greedy_lane.h) ----
         V128 lo_, lf_;
-        {
-            const uint4 xs0 = w_toward0_small(neg ? a0 : b0, sh), xs1 = w_toward0_small(neg ? a1 : b1, sh);
-            const uint4 y0 = neg ? b0 : a0, y1 = neg ? b1 : a1;
-            const uint4 mw = make_uint4((xs0.x ^ y0.x) | (xs1.x ^ y1.x), (xs0.y ^ y0.y) | (xs1.y ^ y1.y), (xs0.z ^ y0.z) | (xs1.z ^ y1.z),
-                                        (xs0.w ^ y0.w) | (xs1.w ^ y1.w));
-            /* flip_short_hurdles(1) (utils.h:200-216): a hurdle survives only next to another one */
-            const uint4 dn = w_toward0_small(mw, 1u);
-            const uint4 up = make_uint4(mw.x << 1, __builtin_amdgcn_alignbit(mw.y, mw.x, 31u), __builtin_amdgcn_alignbit(mw.z, mw.y, 31u),
-                                        __builtin_amdgcn_alignbit(mw.w, mw.z, 31u));
-            lo_ = v_from_words(mw);
-            lf_ = v_from_words(make_uint4(mw.x & (dn.x | up.x), mw.y & (dn.y | up.y), mw.z & (dn.z | up.z), mw.w & (dn.w | up.w)));
-        }
+        greedy_lane_words(a0, a1, b0, b1, neg, sh, lo_, lf_);
         const int dst = lane_destination(m, nn, lane);
         const V128 nlf_ = v_not(lf_);
         const unsigned fb_lf = v_upper_fallback(lf_), fb_nlf = v_upper_fallback(nlf_);
@@ -517,7 +501,7 @@ __global__ __launch_bounds__(ASM_BLOCK) void greedy_wave_kernel(const uint4* __r
                     }
                 }
                 sw = (semi && guard == 0) ? 0 : (UNIT ? adist : lane_penalty(cur_lane, lane, o, e));
-                nh = v_pop_between(lo_, start_col, sp + len);
+                nh = greedy_hurdles(lo_, start_col, sp, len);
             }
             const bool reaching = __ballot(reach) != 0ull;
             const int hc = x * nh;
@@ -530,12 +514,9 @@ __global__ __launch_bounds__(ASM_BLOCK) void greedy_wave_kernel(const uint4* __r
             }
             // arg-max of (heur, leap), first lane wins exact ties (hurdle_matrix.h:345-351): order-preserving integer
             // keys and three 32-bit wave max-reductions
-            heur = heur + 0.0; /* -0.0 -> +0.0 so that equal values have equal keys */
-            const unsigned long long hb = (unsigned long long)__double_as_longlong(heur);
-            // key = hb < 0 ? ~hb : hb | 2^63, word by word (the lower word is only needed when the upper words tie)
-            const unsigned hhi = (unsigned)(hb >> 32);
-            const unsigned sgn = (unsigned)((int)hhi >> 31); /* all ones for a negative score */
-            unsigned khi = active ? ((hhi ^ sgn) | (~sgn & 0x80000000u)) : 0u;
+            unsigned key_hi, key_lo; /* the score's order-preserving key; the lower word is only needed when the upper words tie */
+            greedy_score_key_words(heur, key_hi, key_lo);
+            const unsigned khi = active ? key_hi : 0u;
             const unsigned mhi = wave_max_u32(khi);
             bool cand = active && khi == mhi;
             // Usually one lane alone holds the maximum already in the upper word (scores of different (length, hurdles) differ
@@ -545,12 +526,11 @@ __global__ __launch_bounds__(ASM_BLOCK) void greedy_wave_kernel(const uint4* __r
             if ((cm & (cm - 1ull)) == 0ull) { /* wave-uniform; cm != 0: some active lane holds the maximum */
                 bt = __builtin_ctzll(cm);
             } else {
-                const unsigned klo = cand ? ((unsigned)hb ^ sgn) : 0u;
+                const unsigned klo = cand ? key_lo : 0u;
                 const unsigned mlo = wave_max_u32(klo);
                 cand = cand && klo == mlo;
-                const unsigned k3 = cand ? ((((unsigned)(leap + 32768)) << 6) | (unsigned)(63 - t)) : 0u;
-                const unsigned m3 = wave_max_u32(k3);
-                bt = 63 - (int)(m3 & 63u); /* wave-uniform winner */
+                const unsigned m3 = wave_max_u32(cand ? greedy_tie_key<6>(leap, t) : 0u);
+                bt = greedy_tie_key_slot<6>(m3); /* wave-uniform winner */
             }
             const int best = bt - k;
             const int best_sp = lane_read(sp, bt), best_len = lane_read(len, bt);
@@ -626,8 +606,8 @@ __global__ __launch_bounds__(ASM_BLOCK) void greedy_wave_kernel(const uint4* __r
 }
 
 // --------------------------------------------------------------------------------------------------------
-// Greedy for 32 <= k <= 50 (65..101 band lanes): TWO wavefronts per pair, thread = band lane.  The lane work and the
-// wave-level reductions are those of greedy_wave_kernel; each wave finds its own winner with DPP reductions and the two
+// Greedy for 32 <= k <= 50 (65..101 band lanes): TWO wavefronts per pair, thread = band lane.  The rules are asm_greedy_lane.h's and
+// the wave-level reductions are those of greedy_wave_kernel; each wave finds its own winner with DPP reductions and the two
 // meet through LDS (three barriers per step).  Replaces the serial per-thread scans of greedy_wide_kernel (which stays
 // as the ASM_WAVE=0 fallback).
 // --------------------------------------------------------------------------------------------------------
@@ -643,18 +623,14 @@ __global__ __launch_bounds__(GREEDY_WAVE2_THREADS) void greedy_wave2_kernel(cons
     const int nl = 2 * k + 1;
     const bool active = t < nl;
     const int lane = t - k;
-    const int x = args.x, o = args.o, e = args.e;
-    const bool semi = args.semi != 0;
+    const GreedyCosts pen = {args.x, args.o, args.e, args.semi != 0};
     for (long i = blockIdx.x; i < n; i += gridDim.x) {
         const V128 A0 = v_from_uint4(planes[((long)0 * w4) * n + i]);
         const V128 A1 = v_from_uint4(planes[((long)1 * w4) * n + i]);
         const V128 B0 = v_from_uint4(planes[((long)2 * w4) * n + i]);
         const V128 B1 = v_from_uint4(planes[((long)3 * w4) * n + i]);
-        const uint32_t ln = lens[i];
-        int m = (int)(ln & 0xffffu), nn = (int)(ln >> 16);
-        m = m > 128 ? 128 : m; /* hurdle_matrix.h:626-627 */
-        nn = nn > 128 ? 128 : nn;
-        const int dest_lane = nn - m;
+        int m, nn, dest_lane;
+        greedy_lengths(lens[i], m, nn, dest_lane);
         const V128 lo_ = greedy_lane_vector(A0, A1, B0, B1, lane);
         const V128 lf_ = v_flip_short_hurdles1(lo_);
         int sp = -1, len = 0, nsw = 128;
@@ -665,45 +641,30 @@ __global__ __launch_bounds__(GREEDY_WAVE2_THREADS) void greedy_wave2_kernel(cons
             // ---- _update_highway_list, one band lane per thread ----
             int reach = 0, sw = 0, nh = 0;
             if (active) {
-                const int start_col = cur_col + fwd_col(cur_lane, lane);
+                const int start_col = greedy_start_col(cur_lane, cur_col, lane);
                 if (sp < start_col) {
-                    const int dd = lane - cur_lane;
-                    nsw = dd < 0 ? -dd : dd;
                     int fz, nx;
                     v_highway_from(lf_, start_col, fz, nx);
-                    sp = start_col + fz;
-                    len = nx;
-                    if (start_col + fz + nx > dst) {
-                        const int c = dst - (start_col + fz);
-                        len = c > 0 ? c : 0;
-                        reach = 1;
-                    }
+                    reach = greedy_refresh(greedy_highway_at(start_col, fz, nx, dst), cur_lane, lane, sp, len, nsw) ? 1 : 0;
                 }
-                sw = (semi && guard == 0) ? 0 : lane_penalty(cur_lane, lane, o, e);
-                nh = v_pop_between(lo_, start_col, sp + len);
+                sw = greedy_switch_cost(pen.semi && guard == 0, cur_lane, lane, pen.o, pen.e);
+                nh = greedy_hurdles(lo_, start_col, sp, len);
             }
             const int reaching = __syncthreads_or(reach);
-            const int hc = x * nh;
-            double heur = greedy_significance(args, len, nh, nsw);
-            int leap = -sw;
-            if (reaching) {
-                const int fsw = semi ? 0 : lane_penalty(lane, dest_lane, o, e);
-                heur = (double)(-sw - hc - fsw - x * (dst - sp - len));
-                leap -= fsw;
-            }
-            // arg-max of (heur, leap) inside the wave, first lane wins exact ties (hurdle_matrix.h:345-351)
-            heur = heur + 0.0; /* -0.0 -> +0.0 so that equal values have equal keys */
-            const unsigned long long hb = (unsigned long long)__double_as_longlong(heur);
-            const unsigned long long key = (hb >> 63) ? ~hb : (hb | 0x8000000000000000ull);
+            const int hc = pen.x * nh;
+            double heur;
+            int leap;
+            greedy_score(args, pen, reaching != 0, lane, dest_lane, dst, sp, len, nsw, sw, nh, heur, leap);
+            // arg-max inside the wave (hurdle_matrix.h:345-351): three max-reductions over the key's words and the tie key
+            const unsigned long long key = greedy_score_key(heur);
             const unsigned khi = active ? (unsigned)(key >> 32) : 0u;
             const unsigned mhi = wave_max_u32(khi);
             bool cand = active && khi == mhi;
             const unsigned klo = cand ? (unsigned)key : 0u;
             const unsigned mlo = wave_max_u32(klo);
             cand = cand && klo == mlo;
-            const unsigned k3 = cand ? ((((unsigned)(leap + 32768)) << 6) | (unsigned)(63 - tl)) : 0u;
-            const unsigned m3 = wave_max_u32(k3);
-            const int btl = 63 - (int)(m3 & 63u);
+            const unsigned m3 = wave_max_u32(cand ? greedy_tie_key<6>(leap, tl) : 0u);
+            const int btl = greedy_tie_key_slot<6>(m3);
             if (tl == btl) { /* this wave's winner (wave 1 always has active lanes: nl >= 65) */
                 s_key[w] = active ? key : 0ull;
                 s_kleap[w] = leap;
@@ -720,11 +681,10 @@ __global__ __launch_bounds__(GREEDY_WAVE2_THREADS) void greedy_wave2_kernel(cons
             const V128 best_vec = v_make(s_vec[take1 ? 1 : 0][0], s_vec[take1 ? 1 : 0][1]);
             const int best_from_sp = v_ones_from(best_vec, best_sp);
             int inter = 0x3fffffff, total = 0x3fffffff;
-            if (active && lane != best && !(sp + fwd_col(lane, best) > best_sp)) {
-                const int endp = sp + len;
-                inter = sw + nh;
-                const int tail = x * v_pop_between_pre(best_vec, fwd_col(lane, best) + endp, best_sp, best_from_sp);
-                total = inter + lane_penalty(lane, best, o, e) + (tail > 0 ? tail : 0);
+            const int fb = fwd_col(lane, best);
+            if (active && greedy_cand_reachable(lane, best, fb, sp, best_sp)) {
+                inter = greedy_cand_inter(sw, nh);
+                total = greedy_cand_total(pen, lane, best, fb, sp, len, inter, best_vec, best_sp, best_from_sp);
             }
             // lanes that can still be accepted (thresholds only go down from best_cost), folded in lane order
             const unsigned long long cm = __ballot(total <= best_cost && inter <= best_cost);
@@ -738,31 +698,16 @@ __global__ __launch_bounds__(GREEDY_WAVE2_THREADS) void greedy_wave2_kernel(cons
                 while (cmask) {
                     const int j = 64 * ww + __builtin_ctzll(cmask);
                     cmask &= cmask - 1ull;
-                    const int tj = s_total[j], ij = s_inter[j];
-                    if (tj <= small_total && ij <= small_inter) small_total = tj, small_inter = ij, ct = j;
+                    if (greedy_fold_accept(s_total[j], s_inter[j], small_total, small_inter)) ct = j;
                 }
             }
-            // ---- _step commit (hurdle_matrix.h:411-433) ----
-            cost += s_cost[ct];
-            const int new_col = s_sp[ct] + s_len[ct];
-            if (cig.on() && t == 0) cig.step(pair, ncig, cur_lane, ct - k, new_col - (cur_col + fwd_col(cur_lane, ct - k)));
-            cur_lane = ct - k;
-            cur_col = new_col;
-            const bool done = cur_col >= lane_destination(m, nn, cur_lane);
+            const bool done = greedy_commit(cig, t == 0, pair, ncig, m, nn, ct - k, s_sp[ct] + s_len[ct], s_cost[ct], cur_lane, cur_col, cost);
             __syncthreads(); /* the LDS arrays are rewritten by the next step */
             if (done) break;
         }
         if (t == 0) {
-            // ---- final hop (hurdle_matrix.h:575-590) ----
-            const int dest_col = lane_destination(m, nn, dest_lane);
-            if (cur_lane != dest_lane || cur_col < dest_col) {
-                const V128 dv = greedy_lane_vector(A0, A1, B0, B1, dest_lane);
-                const int sw_f = semi ? 0 : lane_penalty(cur_lane, dest_lane, o, e);
-                const int distance = v_pop_between(dv, cur_col + fwd_col(cur_lane, dest_lane), dest_col);
-                const int hcf = x * distance;
-                cost += sw_f + (hcf > 0 ? hcf : 0);
-                if (cig.on()) cig.step(pair, ncig, cur_lane, dest_lane, distance);
-            }
+            greedy_final_hop(pen, cig, true, pair, ncig, m, nn, dest_lane, [&]() { return greedy_lane_vector(A0, A1, B0, B1, dest_lane); }, cur_lane,
+                             cur_col, cost);
             if (cig.on()) cig.finish(pair, ncig);
             out.put(i, cost);
         }

@@ -108,10 +108,9 @@ __global__ __launch_bounds__(ASM_WIDE_THREADS) void leap_wide_kernel(const uint4
 
 
 // --------------------------------------------------------------------------------------------------------
-// Greedy, any k <= 50: workgroup per pair, thread = lane.  Same step structure as greedy_kernel<K>; the two
-// lane loops of _update_highway_list become per-thread work plus a workgroup arg-max, and the order-dependent
-// fold of _choose_best_highway (hurdle_matrix.h:382-399: a lane is accepted only if it is no worse than the
-// LAST accepted one in both total and intermediate cost) is replayed in lane order from LDS by every thread.
+// Greedy, any k <= 50: workgroup per pair, thread = lane.  The step's rules are asm_greedy_lane.h's; the two
+// lane loops of _update_highway_list become per-thread work plus a workgroup arg-max, and both the arg-max and the
+// order-dependent fold of _choose_best_highway are replayed in lane order from LDS by every thread.
 // --------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(ASM_WIDE_THREADS) void greedy_wide_kernel(const uint4* __restrict__ planes,
                                                                        const uint32_t* __restrict__ lens, long n,
@@ -126,18 +125,14 @@ __global__ __launch_bounds__(ASM_WIDE_THREADS) void greedy_wide_kernel(const uin
     const int nl = 2 * k + 1;
     const bool active = t < nl;
     const int lane = t - k;
-    const int x = args.x, o = args.o, e = args.e;
-    const bool semi = args.semi != 0;
+    const GreedyCosts pen = {args.x, args.o, args.e, args.semi != 0};
     for (long i = blockIdx.x; i < n; i += gridDim.x) {
         const V128 A0 = v_from_uint4(planes[((long)0 * w4) * n + i]);
         const V128 A1 = v_from_uint4(planes[((long)1 * w4) * n + i]);
         const V128 B0 = v_from_uint4(planes[((long)2 * w4) * n + i]);
         const V128 B1 = v_from_uint4(planes[((long)3 * w4) * n + i]);
-        const uint32_t ln = lens[i];
-        int m = (int)(ln & 0xffffu), nn = (int)(ln >> 16);
-        m = m > 128 ? 128 : m;
-        nn = nn > 128 ? 128 : nn;
-        const int dest_lane = nn - m;
+        int m, nn, dest_lane;
+        greedy_lengths(lens[i], m, nn, dest_lane);
         const V128 lo_ = greedy_lane_vector(A0, A1, B0, B1, lane);
         const V128 lf_ = v_flip_short_hurdles1(lo_);
         int sp = -1, len = 0, nsw = 128;
@@ -147,33 +142,21 @@ __global__ __launch_bounds__(ASM_WIDE_THREADS) void greedy_wide_kernel(const uin
         for (int guard = 0; guard < 4 * 128; guard++) {
             int reach = 0, sw = 0, nh = 0;
             if (active) {
-                const int start_col = cur_col + fwd_col(cur_lane, lane);
+                const int start_col = greedy_start_col(cur_lane, cur_col, lane);
                 if (sp < start_col) {
-                    int dd = lane - cur_lane;
-                    nsw = dd < 0 ? -dd : dd;
                     int fz, nx;
                     v_highway_from(lf_, start_col, fz, nx);
-                    sp = start_col + fz;
-                    len = nx;
-                    if (start_col + fz + nx > dst) {
-                        const int c = dst - (start_col + fz);
-                        len = c > 0 ? c : 0;
-                        reach = 1;
-                    }
+                    reach = greedy_refresh(greedy_highway_at(start_col, fz, nx, dst), cur_lane, lane, sp, len, nsw) ? 1 : 0;
                 }
-                sw = (semi && guard == 0) ? 0 : lane_penalty(cur_lane, lane, o, e);
-                nh = v_pop_between(lo_, start_col, sp + len);
+                sw = greedy_switch_cost(pen.semi && guard == 0, cur_lane, lane, pen.o, pen.e);
+                nh = greedy_hurdles(lo_, start_col, sp, len);
             }
             const int reaching = __syncthreads_or(reach);
-            const int hc = x * nh;
+            const int hc = pen.x * nh;
             if (active) {
-                double heur = greedy_significance(args, len, nh, nsw);
-                int leap = -sw;
-                if (reaching) {
-                    const int fsw = semi ? 0 : lane_penalty(lane, dest_lane, o, e);
-                    heur = (double)(-sw - hc - fsw - x * (dst - sp - len));
-                    leap -= fsw;
-                }
+                double heur;
+                int leap;
+                greedy_score(args, pen, reaching != 0, lane, dest_lane, dst, sp, len, nsw, sw, nh, heur, leap);
                 s_heur[t] = heur, s_leap[t] = leap;
                 s_sp[t] = sp, s_len[t] = len, s_cost[t] = sw + hc;
             }
@@ -184,7 +167,7 @@ __global__ __launch_bounds__(ASM_WIDE_THREADS) void greedy_wide_kernel(const uin
             for (int j = 0; j < nl; j++) {
                 const double hj = s_heur[j];
                 const int lj = s_leap[j];
-                if (hj > best_h || (hj == best_h && lj > best_leap)) best_h = hj, best_leap = lj, bt = j;
+                if (greedy_beats(hj, lj, best_h, best_leap)) best_h = hj, best_leap = lj, bt = j;
             }
             const int best = bt - k, best_sp = s_sp[bt], best_len = s_len[bt], best_cost = s_cost[bt];
             if (best_len <= 0) break; /* uniform across the workgroup */
@@ -193,39 +176,24 @@ __global__ __launch_bounds__(ASM_WIDE_THREADS) void greedy_wide_kernel(const uin
             const V128 best_vec = v_make(s_vec[0], s_vec[1]);
             const int best_from_sp = v_ones_from(best_vec, best_sp);
             int inter = 0x3fffffff, total = 0x3fffffff;
-            if (active && lane != best && !(sp + fwd_col(lane, best) > best_sp)) {
-                const int endp = sp + len;
-                inter = sw + v_pop_between(lo_, cur_col + fwd_col(cur_lane, lane), endp);
-                const int tail = x * v_pop_between_pre(best_vec, fwd_col(lane, best) + endp, best_sp, best_from_sp);
-                total = inter + lane_penalty(lane, best, o, e) + (tail > 0 ? tail : 0);
+            const int fb = fwd_col(lane, best);
+            if (active && greedy_cand_reachable(lane, best, fb, sp, best_sp)) {
+                inter = greedy_cand_inter(sw, nh);
+                total = greedy_cand_total(pen, lane, best, fb, sp, len, inter, best_vec, best_sp, best_from_sp);
             }
             s_inter[t] = inter, s_total[t] = total;
             __syncthreads();
             int small_inter = best_cost, small_total = best_cost, ct = bt;
             for (int j = 0; j < nl; j++) {
-                const int tj = s_total[j], ij = s_inter[j];
-                if (j != bt && tj <= small_total && ij <= small_inter) small_total = tj, small_inter = ij, ct = j;
+                if (greedy_fold_accept(s_total[j], s_inter[j], small_total, small_inter)) ct = j; /* the best lane's own slot holds no candidate */
             }
-            const int ch = ct - k;
-            cost += s_cost[ct];
-            if (cig.on() && t == 0)
-                cig.step(pair, ncig, cur_lane, ch, s_sp[ct] + s_len[ct] - (cur_col + fwd_col(cur_lane, ch)));
-            cur_lane = ch;
-            cur_col = s_sp[ct] + s_len[ct];
-            const bool done = cur_col >= lane_destination(m, nn, ch);
+            const bool done = greedy_commit(cig, t == 0, pair, ncig, m, nn, ct - k, s_sp[ct] + s_len[ct], s_cost[ct], cur_lane, cur_col, cost);
             __syncthreads(); /* LDS arrays are rewritten by the next step */
             if (done) break;
         }
         if (t == 0) {
-            const int dest_col = lane_destination(m, nn, dest_lane);
-            if (cur_lane != dest_lane || cur_col < dest_col) {
-                const V128 dv = greedy_lane_vector(A0, A1, B0, B1, dest_lane);
-                const int sw_f = semi ? 0 : lane_penalty(cur_lane, dest_lane, o, e);
-                const int distance = v_pop_between(dv, cur_col + fwd_col(cur_lane, dest_lane), dest_col);
-                const int hc = x * distance;
-                cost += sw_f + (hc > 0 ? hc : 0);
-                if (cig.on()) cig.step(pair, ncig, cur_lane, dest_lane, distance);
-            }
+            greedy_final_hop(pen, cig, true, pair, ncig, m, nn, dest_lane, [&]() { return greedy_lane_vector(A0, A1, B0, B1, dest_lane); }, cur_lane,
+                             cur_col, cost);
             if (cig.on()) cig.finish(pair, ncig);
             out.put(i, cost);
         }

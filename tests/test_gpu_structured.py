@@ -89,7 +89,7 @@ def test_greedy_unit_penalties(asm, engine, oracle, batches, k):
     """k <= 3: greedy_fast_kernel; 4 .. 16 the thread-per-pair ladder; 17, 31 a wave per pair; 32, 39 sixteen threads per pair;
     40 the two-wavefront kernel."""
     hb, _ = batches(100, 128, k, True)
-    greedy_case(asm, engine, oracle, hb, k, UNIT, "default", cigars=k in (3, 12, 17, 32))
+    greedy_case(asm, engine, oracle, hb, k, UNIT, "default", cigars=k in (3, 12, 17, 32, 40))
 
 
 @pytest.mark.parametrize("k", [1, 2, 3])
@@ -101,14 +101,14 @@ def test_greedy_narrow_bands_on_the_fp64_kernel(asm, engine_slow_greedy, oracle,
 @pytest.mark.parametrize("k", [3, 16, 17, 32, 39, 40])
 def test_greedy_general_penalties(asm, engine, oracle, batches, k):
     hb, _ = batches(100, 128, k, True)
-    greedy_case(asm, engine, oracle, hb, k, (2, 3, 1), "default", cigars=k in (3, 17, 32))
+    greedy_case(asm, engine, oracle, hb, k, (2, 3, 1), "default", cigars=k in (3, 17, 32, 40))
 
 
 @pytest.mark.parametrize("k", [17, 40])
 def test_greedy_workgroup_per_pair_fallback(asm, engine_no_wave, oracle, batches, k):
     hb, _ = batches(100, 128, k, True)
     greedy_case(asm, engine_no_wave, oracle, hb, k, UNIT, "ASM_WAVE=0", cigars=k == 17)
-    greedy_case(asm, engine_no_wave, oracle, hb, k, (2, 3, 1), "ASM_WAVE=0")
+    greedy_case(asm, engine_no_wave, oracle, hb, k, (2, 3, 1), "ASM_WAVE=0", cigars=True)
 
 
 # ---- LEAP ----

@@ -1,0 +1,192 @@
+"""Host logic of the general ("FP64") Greedy kernels: the rules of the step (csrc/asm_greedy_lane.h on csrc/asm_bits.h), compiled for
+the CPU (host/greedy_host_check.cpp) and driven serially in the three shapes the kernels use them in — (a) one loop over all lanes with
+a serial arg-max and fold (greedy_persist_kernel, greedy_wide_kernel), (b) per-lane values, arg-max by maxima over the key words and the
+tie key, the wave kernel's early-outs, candidate mask and ordered fold (greedy_wave_kernel, greedy_wave2_kernel), (c) the band in T
+slices of LPT lanes with the select-form refresh and keys with 127 - lane (greedy_group_kernel) — each through the real CigarSink and
+diffed against the oracle's cost and CIGAR, bit for bit.  Bands on both sides of every kernel's range, four penalty triples, GLOBAL and
+SEMI_GLOBAL; the pair kinds of tests/structured_cases.py, a grid of lengths around the plane words with the destination lane inside and
+outside the band, and solid blocks of hurdles.  The same source built as a stand-alone program under ASan + UBSan runs the same batches
+and must print what the library gave.  No GPU needed; the kernels around these functions are in test_gpu_dispatch.py,
+test_gpu_structured.py, test_gpu_fuzz.py and test_gpu_parity.py."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import oracle_binding
+from tests import structured_cases as sc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "approximate-string-matching_amd")
+SO = os.path.join(PKG, "libgreedy_hostcheck.so")
+_vp, _i = ctypes.c_void_p, ctypes.c_int
+
+BANDS = (1, 4, 5, 6, 16, 17, 31, 32, 39, 40, 50)
+PENALTIES = [(1, 1, 1), (2, 3, 1), (4, 6, 2), (3, 1, 1)]
+LENGTHS = (0, 1, 31, 32, 33, 63, 64, 65, 127, 128)
+CAP = 255
+PROBS = np.array(oracle_binding.DEFAULT_PROBS, np.float64)
+
+
+def group_shapes(k):
+    """(T, LPT) of shape (c) with T * LPT >= 2k + 1: the instantiated (16, 5) wherever it covers the band, a narrow and the widest form"""
+    return [s for s in ((16, 5), (8, 3), (16, 7)) if s[0] * s[1] >= 2 * k + 1][:2]
+
+
+@pytest.fixture(scope="module")
+def glh():
+    subprocess.check_call(["make", "-s", "-C", PKG, "greedycheck"])
+    lib = ctypes.CDLL(SO)
+    lib.greedy_host_batch.argtypes = [ctypes.c_long, _vp, _vp] + [_i] * 8 + [_vp, _vp, _vp, _i, _vp]
+    lib.greedy_host_lane_words.argtypes = [ctypes.c_long, _vp]
+    lib.greedy_host_lane_words.restype = ctypes.c_long
+    return lib
+
+
+def san_flags():
+    """SAN_FLAGS of oracle/Makefile"""
+    with open(os.path.join(ROOT, "oracle", "Makefile")) as fh:
+        for line in fh:
+            if line.startswith("SAN_FLAGS :="):
+                return line.split(":=", 1)[1].split()
+    raise AssertionError("oracle/Makefile has no SAN_FLAGS")
+
+
+@pytest.fixture(scope="module")
+def greedy_check_asan(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("greedy_check") / "greedy_host_check_asan")
+    src = os.path.join(PKG, "host", "greedy_host_check.cpp")
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off", "-DGREEDY_HOST_CHECK_MAIN"]
+                       + san_flags() + ["-o", exe, src, "-lm"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return exe
+
+
+def edge_pairs(seed):
+    """Every (m, n) of LENGTHS with identical content, with 10 % substitutions, and with unrelated content: |n - m| runs from 0 to 128,
+    so every band has destination lanes inside and outside it."""
+    rng = np.random.default_rng(seed)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    pairs = []
+    for m in LENGTHS:
+        for n in LENGTHS:
+            code = rng.integers(0, 4, 128)
+            text = bytes(acgt[code]).decode()
+            hit = rng.random(128) < 0.10
+            pairs.append((text[:m], text[:n]))
+            pairs.append((text[:m], bytes(acgt[np.where(hit, (code + 1 + rng.integers(0, 3, 128)) % 4, code)]).decode()[:n]))
+            pairs.append((text[:m], bytes(acgt[rng.integers(0, 4, 128)]).decode()[:n]))
+    return pairs
+
+
+def block_pairs(seed):
+    """Solid blocks of hurdles: whole strings, halves and runs of 20 to 90 mismatches at random places, so that a lane scores as one
+    long run of hurdles; some with a short insertion or deletion beside the block."""
+    rng = np.random.default_rng(seed)
+    acgt = "ACGT"
+    rnd = lambda L: "".join(acgt[i] for i in rng.integers(0, 4, L))
+    pairs = [("A" * 128, "T" * 128), ("A" * 100, "T" * 100), ("A" * 64 + "T" * 64, "T" * 64 + "A" * 64), ("A" * 70 + "C" * 58, "C" * 58 + "A" * 70),
+             ("AC" * 64, "CA" * 64), ("A" * 128, "A" * 64 + "T" * 64), ("A" * 128, "T" * 64 + "A" * 64)]
+    for _ in range(60):
+        L = int(rng.integers(40, 129))
+        a = list(rnd(L))
+        b = list(a)
+        for _ in range(int(rng.integers(1, 3))):
+            p, w = int(rng.integers(0, L)), int(rng.integers(20, 91))
+            b[p:p + w] = [acgt[(acgt.index(c) + 1) % 4] for c in b[p:p + w]]
+        if rng.random() < 0.4:
+            q = int(rng.integers(0, len(b) + 1))
+            b[q:q] = list(rnd(int(rng.integers(1, 4))))
+        if rng.random() < 0.4 and len(b) > 4:
+            q = int(rng.integers(0, len(b) - 3))
+            del b[q:q + int(rng.integers(1, 4))]
+        pairs.append(("".join(a), "".join(b)[:128]))
+    return pairs
+
+
+@pytest.fixture(scope="module")
+def corpus(asm, oracle):
+    """k -> [(name, batch, views, lens)]: the length grid and the blocks (the same for every band) and the structured kinds built for
+    the band (shifts up to k + 1, gaps of k - 1, k and k + 1) with the longer string at 64, 100 and 128."""
+    def packed(name, hb):
+        views = np.ascontiguousarray(oracle.greedy_views(hb, mode=1)).reshape(-1)
+        m, n = hb.lengths()
+        return name, hb, views, (m.astype(np.uint32) | (n.astype(np.uint32) << 16)).astype(np.uint32)
+
+    shared = [packed("grid", asm.HostBatch.from_strings(edge_pairs(5))), packed("blocks", asm.HostBatch.from_strings(block_pairs(7)))]
+    return {k: shared + [packed(f"kinds at {L}", sc.all_kinds_batch(asm, L, L, k, n=32, seed=L)) for L in (64, 100, 128)] for k in BANDS}
+
+
+def run_shape(glh, asm, hb, views, lens, shape, k, pen, semi, T=0, LPT=0):
+    x, o, e = pen
+    costs, ops, nops = np.zeros(hb.n, np.int32), np.zeros((hb.n, CAP), np.uint16), np.zeros(hb.n, np.uint8)
+    rc = glh.greedy_host_batch(hb.n, views.ctypes.data, lens.ctypes.data, shape, T, LPT, k, x, o, e, 1 if semi else 0, PROBS.ctypes.data,
+                               costs.ctypes.data, ops.ctypes.data, CAP, nops.ctypes.data)
+    assert rc == 0, rc
+    assert int(nops.max(initial=0)) < CAP
+    return costs, asm.decode_cigars(ops, nops, CAP)
+
+
+def shapes_of(k):
+    return [("a", 0, 0, 0), ("b", 1, 0, 0)] + [(f"c {T}x{LPT}", 2, T, LPT) for T, LPT in group_shapes(k)]
+
+
+def _first_bad(hb, got, want):
+    bad = [i for i in range(hb.n) if got[i] != want[i]]
+    return (len(bad), bad[0], hb.pair(bad[0]), got[bad[0]], want[bad[0]]) if bad else None
+
+
+@pytest.mark.parametrize("semi", [False, True], ids=["global", "semi_global"])
+@pytest.mark.parametrize("pen", PENALTIES)
+@pytest.mark.parametrize("k", BANDS)
+def test_three_shapes_match_the_oracle(glh, asm, oracle, corpus, k, pen, semi):
+    x, o, e = pen
+    pairs = outside = steps = 0
+    for name, hb, views, lens in corpus[k]:
+        want, want_cig = oracle.greedy(hb, k, x, o, e, mode=1, cigars=True, semi=semi)
+        for label, shape, T, LPT in shapes_of(k):
+            got, got_cig = run_shape(glh, asm, hb, views, lens, shape, k, pen, semi, T, LPT)
+            assert _first_bad(hb, got, want) is None, (name, label, "cost", _first_bad(hb, got, want))
+            assert _first_bad(hb, got_cig, want_cig) is None, (name, label, "CIGAR", _first_bad(hb, got_cig, want_cig))
+        m, n = hb.lengths()
+        pairs += hb.n
+        outside += int((np.abs(np.minimum(n, 128).astype(int) - np.minimum(m, 128).astype(int)) > k).sum())
+        steps += sum(c.count("M") > 1 for c in want_cig)
+    assert pairs >= 450 and outside >= 40 and steps > 50  # destinations outside the band were there, and pairs of several steps
+
+
+def test_shape_c_runs_where_the_band_fits():
+    assert group_shapes(39)[0] == (16, 5) and (16, 5) not in group_shapes(40) and group_shapes(50) == [(16, 7)]
+    assert all(group_shapes(k) for k in BANDS)
+
+
+def test_lane_vectors_on_words(glh, corpus):
+    """greedy_lane_words (w_toward0_small and the flip on four words) against greedy_lane_vector and v_flip_short_hurdles1, every shift
+    0..31 on both sides of the main diagonal, every pair of the corpus"""
+    for name, hb, views, lens in corpus[31]:
+        assert glh.greedy_host_lane_words(hb.n, views.ctypes.data) == 0, name
+
+
+@pytest.mark.parametrize("pen", PENALTIES)
+def test_the_same_batches_under_sanitizers(glh, greedy_check_asan, asm, corpus, pen, tmp_path):
+    """The stand-alone program reads each batch into arrays of exactly its size and prints cost and CIGAR of every shape per pair: what
+    the library gave (which the test above pins to the oracle), with no sanitizer report."""
+    x, o, e = pen
+    for k in BANDS:
+        T, LPT = group_shapes(k)[0]
+        for semi in (0, 1):
+            for name, hb, views, lens in corpus[k]:
+                path = tmp_path / "batch.bin"
+                path.write_bytes(np.int32(hb.n).tobytes() + lens.tobytes() + views.tobytes())
+                r = subprocess.run([greedy_check_asan, str(path)] + [str(v) for v in (k, x, o, e, semi, T, LPT)], capture_output=True, text=True,
+                                   timeout=120)
+                assert r.returncode == 0 and r.stderr == "", (name, k, pen, semi, r.returncode, r.stderr[-3000:])
+                lines = r.stdout.split("\n")[:-1]
+                assert lines[-1] == "lane words differing: 0" and len(lines) == hb.n + 1
+                want = [""] * hb.n
+                for label, shape, t_, l_ in shapes_of(k)[:3]:
+                    costs, cigs = run_shape(glh, asm, hb, views, lens, shape, k, pen, bool(semi), t_, l_)
+                    want = [w + (" " if w else "") + f"{int(c)} {g or '*'}" for w, c, g in zip(want, costs, cigs)]
+                assert lines[:-1] == want, (name, k, pen, semi)

@@ -8,7 +8,11 @@ k = 3, 5, 7, 8 and with (4,6,2) at k = 3 (leap_general_kernel: short and byte ri
 (leap_quad_kernel) and in ED mode LOCAL (leap_wide_kernel, on N/16 pairs: a workgroup per pair), NW with (2,3,1) behind the banded
 wavefront passes, the coverage counter with (2,3,1) (nw_trace_affine_kernel, N/4 pairs) and the affine SIMD_ED filter at gap 8 (the
 quad kernel up to 128 characters, thread per pair beyond).  NAME:N:general-full runs its children with ASM_NW_WFA=0 and times NW with
-(2,3,1) alone: nw_affine_kernel over every pair.  The string length picks the instantiation: C2 100, C3 150, C5 64-300."""
+(2,3,1) alone: nw_affine_kernel over every pair.  The string length picks the instantiation: C2 100, C3 150, C5 64-300.
+NAME:N:greedy times the general Greedy kernels alone, band by band: greedy_persist_kernel at k = 5 (flipped vectors kept), 8 (two waves
+per SIMD), 12 and 16 with unit penalties and at k = 16 with (2,3,1); greedy_wave_kernel at k = 17 and 30 with unit penalties and at k = 17
+with (2,3,1); greedy_group_kernel at k = 32; greedy_wave2_kernel at k = 40; and, in children of their own started with ASM_WAVE=0,
+k = 20 on N/16 pairs: greedy_wide_kernel, a workgroup per pair."""
 import json, os, statistics, subprocess, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,6 +35,18 @@ if len(sys.argv) > 3:
     import ctypes
     g = lambda **kw: m.Params.default(x=2, o=3, e=1, **kw)
     dd = d[m.NW]
+    if sys.argv[3] == "greedy":
+        for k in (5, 8, 12, 16, 17, 30, 32, 40):
+            out["greedy_k%d" % k] = timed(lambda: eng.align_async(batch, m.GREEDY, m.Params.default(k=k), dd))
+        for k in (16, 17):
+            out["greedy_k%d_231" % k] = timed(lambda: eng.align_async(batch, m.GREEDY, g(k=k), dd))
+        print(json.dumps(out))
+        sys.exit(0)
+    if sys.argv[3] == "greedy-wide":
+        small = eng.generate(cfg, 1, max(n // 16, 1024))
+        out["greedy_wide_k20"] = timed(lambda: eng.align_async(small, m.GREEDY, m.Params.default(k=20), dd))
+        print(json.dumps(out))
+        sys.exit(0)
     if sys.argv[3] == "general-full":
         out["nw_affine_full"] = timed(lambda: eng.align_async(batch, m.NW, g(), dd))
         print(json.dumps(out))
@@ -68,10 +84,13 @@ res = {}
 for r in range(rounds):
     for w in works:
         name, n, *kind = w.split(":")
-        for lib in libs:
+        kinds = [kind, ["greedy-wide"]] if kind == ["greedy"] else [kind]  # the fallback kernel needs children with its own switch
+        for lib, kind in ((lib, kind) for kind in kinds for lib in libs):
             env = dict(os.environ, ASM_MI355X_LIB=os.path.abspath(lib), PYTHONPATH=ROOT)
             if kind == ["general-full"]:
                 env["ASM_NW_WFA"] = "0"  # switches are read when the handle is created
+            if kind == ["greedy-wide"]:
+                env["ASM_WAVE"] = "0"
             p = subprocess.run([sys.executable, "-c", CHILD, name, n] + kind, env=env, capture_output=True, text=True, timeout=600)
             if p.returncode != 0:
                 sys.exit("FAILED %s %s (exit %d)\n%s" % (lib, w, p.returncode, p.stderr[-800:]))  # nothing more on a device that faulted
