@@ -843,7 +843,9 @@ class Engine:
         is map_pairs'.  names: one RNAME per sequence of the index.  header is written first, as it is.  -> the stats as a dict:
         pairs, proper, rescued, unsent, records (SAM lines), chunks, bytes_in, bytes_out, carry_peak, seconds, seconds_read,
         seconds_write.  sort=True: asm_map_pairs_file_sorted, the same lines in coordinate order; max_device_bytes and the "sort" entry
-        of the dict as for map_file."""
+        of the dict as for map_file.  Two bgzip-compressed (BGZF) files are taken as they are and inflated on the device; the bytes
+        written are those of the call on the inflated texts, and carry_peak then counts text bytes held on the device
+        (docs/design/mapper.md, "Compressed input for pairs").  One compressed and one text file, or plain gzip: AsmError."""
         arr = self._rnames(index, names)
         p = MapParams(int(max_errors), 1, int(max_occ), int(greedy_k))
         pp = PairParams(int(min_insert), int(max_insert), int(rescue_errors))

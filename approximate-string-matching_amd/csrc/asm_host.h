@@ -1,10 +1,10 @@
 // The device-free part of the C ABI's host side: everything in libasm_mi355x.so that runs on the CPU and never calls HIP —
 // the seeded generator's host loop (asm_generate_pairs), the stale-tail state arithmetic (asm_tail_state_advance), the CIGAR
 // formatter (asm_cigar_format), and the host threads of the two streamed-file calls: the three-slot hand-over between a reader
-// thread and the caller's thread (ChunkReader) with its four fill policies — asm_stream_seq_file's newline scanning over the
+// thread and the caller's thread (ChunkReader) with its fill policies — asm_stream_seq_file's newline scanning over the
 // persistent reader pool (PairsFill), asm_map_file's FASTQ chunk cutter (asm_fastq_cut, FastqFill), asm_map_pairs_file's two
-// files in step (asm_fastq_cut_n, FastqPairFill) and asm_index_build_file's FASTA cutter (asm_fasta_cut, FastaFill) — and the SAM
-// writer (ChunkWriter).
+// files in step (asm_fastq_cut_n, FastqPairFill) and asm_index_build_file's FASTA cutter (asm_fasta_cut, FastaFill), with the BGZF
+// forms of the two FASTQ policies (BgzfFill, BgzfPairFill) — and the SAM writer (ChunkWriter).
 //
 // Kept in a header without any HIP include so that the SAME code is compiled twice: into the product by hipcc (asm_capi.hip),
 // and by plain g++ under -fsanitize=thread / address,undefined into host/asm_host_check.cpp (`make -C oracle asan`,
@@ -412,6 +412,7 @@ public:
     /* what the policy keeps for its caller: after the last chunk or stop(); what it keeps per slot (BgzfFill::info) goes with the
      * slot's hand-over: written before the slot is ready, read before consumed() */
     const Fill& policy() const { return fill_; }
+    Fill& policy() { return fill_; } /* for what the consumer hands back to it (BgzfPairFill::feedback) */
 };
 
 /* asm_stream_seq_file's policy: `want` more file bytes through the reader pool (reads stop at cap - 8), cut behind the last
@@ -550,63 +551,174 @@ struct BgzfChunkInfo {
     size_t file_base = 0; /* the file offset of the slot's first byte */
     BgzfWalkError err;
 };
-struct BgzfFill {
-    const int fd;
-    const size_t file_bytes;
-    const std::function<bool(int, size_t, size_t)> grow;
+/* One BGZF file under a fill policy: where the reader stands in it */
+struct BgzfFile {
+    int fd;
+    size_t file_bytes;
     size_t file_off = 0;
     int64_t members_seen = 0;
+};
+/* The per-member loop both BGZF policies share.  s.buf[base, base + have) holds file f's bytes already (a compressed carry; ci.file_base
+ * is set); whole members are taken behind them, at least one, until the ISIZE sum of ci reaches `want`.  Members enter ci with their
+ * offsets in the slot (base included).  at: the bytes of [base, base + have) that are whole members; eof: the file ends behind them, or
+ * a bad header does (ci.err).  false: reading failed or the slot could not grow. */
+inline bool bgzf_fill_members(BgzfFile& f, ChunkSlot& s, int q, const std::function<bool(int, size_t, size_t)>& grow, size_t base,
+                              size_t want, BgzfChunkInfo& ci, size_t& have, size_t& at, bool& eof) {
+    at = 0, eof = false;
+    for (;;) {
+        /* the member at `at` whole: 64 KiB behind `at`, or up to the end of the file */
+        size_t need = have - at < 65536 ? 65536 - (have - at) : 0;
+        if (need > f.file_bytes - f.file_off) need = f.file_bytes - f.file_off;
+        if (base + have + need + 8 > s.cap && !grow(q, base + have + need + 8 + (base + have + need) / 4, base + have)) return false;
+        for (size_t a = 0; a < need;) {
+            const ssize_t got = pread(f.fd, s.buf + base + have + a, need - a, (off_t)(f.file_off + a));
+            if (got <= 0) return false;
+            a += (size_t)got;
+        }
+        f.file_off += need, have += need;
+        if (at == have) { /* the end of the file behind a whole member */
+            eof = true;
+            break;
+        }
+        const uint8_t* m = (const uint8_t*)s.buf + base + at;
+        uint32_t csize = 0, dstart = 0;
+        uint32_t st = bgzf_member_header(m, have - at, &csize, &dstart);
+        if (st == BGZF_IN_OK && csize > have - at) st = BGZF_IN_PAST_END;
+        uint32_t crc = 0, isize = 0;
+        if (st == BGZF_IN_OK) {
+            const uint8_t* t = m + csize - 8u;
+            crc = t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+            isize = t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24;
+            if (isize > INF_MAX_ISIZE) st = BGZF_IN_ISIZE;
+        }
+        if (st != BGZF_IN_OK) {
+            ci.err.status = st, ci.err.member = (size_t)f.members_seen + ci.members.size(), ci.err.offset = ci.file_base + at;
+            eof = true;
+            break;
+        }
+        ci.members.push_back(InfMember{(unsigned long long)(base + at), (unsigned long long)ci.text, csize, dstart, isize, crc});
+        at += csize, ci.text += isize;
+        if (ci.text >= want) {
+            eof = at == have && f.file_off >= f.file_bytes;
+            break;
+        }
+    }
+    f.members_seen += (int64_t)ci.members.size();
+    return true;
+}
+struct BgzfFill {
+    BgzfFile file;
+    const std::function<bool(int, size_t, size_t)> grow;
     BgzfChunkInfo info[3];
-    BgzfFill(int fd_, size_t file_bytes_, std::function<bool(int, size_t, size_t)> grow_) : fd(fd_), file_bytes(file_bytes_), grow(std::move(grow_)) {}
+    BgzfFill(int fd_, size_t file_bytes_, std::function<bool(int, size_t, size_t)> grow_) : file{fd_, file_bytes_}, grow(std::move(grow_)) {}
 
     bool operator()(ChunkSlot& s, int q, const std::vector<char>& carry, size_t want, ChunkCut& cut) {
         BgzfChunkInfo& ci = info[q];
         ci = BgzfChunkInfo();
-        ci.first_member = members_seen;
+        ci.first_member = file.members_seen;
         size_t have = carry.size(), at = 0;
         if (have + 8 > s.cap && !grow(q, have + 8 + 65536, 0)) return false;
         if (have) memcpy(s.buf, carry.data(), have);
-        ci.file_base = file_off - have;
-        for (;;) {
-            /* the member at `at` whole: 64 KiB behind `at`, or up to the end of the file */
-            size_t need = have - at < 65536 ? 65536 - (have - at) : 0;
-            if (need > file_bytes - file_off) need = file_bytes - file_off;
-            if (have + need + 8 > s.cap && !grow(q, have + need + 8 + (have + need) / 4, have)) return false;
-            for (size_t a = 0; a < need;) {
-                const ssize_t got = pread(fd, s.buf + have + a, need - a, (off_t)(file_off + a));
-                if (got <= 0) return false;
-                a += (size_t)got;
-            }
-            file_off += need, have += need;
-            if (at == have) { /* the end of the file behind a whole member */
-                cut.eof = true;
-                break;
-            }
-            const uint8_t* m = (const uint8_t*)s.buf + at;
-            uint32_t csize = 0, dstart = 0;
-            uint32_t st = bgzf_member_header(m, have - at, &csize, &dstart);
-            if (st == BGZF_IN_OK && csize > have - at) st = BGZF_IN_PAST_END;
-            uint32_t crc = 0, isize = 0;
-            if (st == BGZF_IN_OK) {
-                const uint8_t* t = m + csize - 8u;
-                crc = t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
-                isize = t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24;
-                if (isize > INF_MAX_ISIZE) st = BGZF_IN_ISIZE;
-            }
-            if (st != BGZF_IN_OK) {
-                ci.err.status = st, ci.err.member = (size_t)members_seen + ci.members.size(), ci.err.offset = ci.file_base + at;
-                cut.eof = true;
-                break;
-            }
-            ci.members.push_back(InfMember{(unsigned long long)at, (unsigned long long)ci.text, csize, dstart, isize, crc});
-            at += csize, ci.text += isize;
-            if (ci.text >= want) {
-                cut.eof = at == have && file_off >= file_bytes;
-                break;
-            }
-        }
-        members_seen += (int64_t)ci.members.size();
+        ci.file_base = file.file_off - have;
+        if (!bgzf_fill_members(file, s, q, grow, 0, want, ci, have, at, cut.eof)) return false;
         cut.have = have, cut.boundary = at, cut.units = (int64_t)ci.members.size();
+        return true;
+    }
+};
+
+/* asm_map_pairs_file's policy for two BGZF-compressed files (docs/design/mapper.md, "Compressed input for pairs").  A slot holds whole
+ * members of file 1 and then whole members of file 2, bytes1 the length of the first region; info[q].f[x] is BgzfFill's table for region
+ * x (its members' offsets count from the slot's start), done[x]: file x is read to its end with this chunk.  What a file has behind its
+ * last whole member (at most 64 KiB, still compressed) stays in a carry of the policy's own, as FastqPairFill's does (have == boundary).
+ * Records cannot be counted here, so `want` text bytes are split by bytes: s1 + s2 = want with
+ *     (avail1 + s1) / b1 = (avail2 + s2) / b2,   each clamped to [0, want],
+ * avail: the text bytes of the file that have been handed out and are not yet paired, b: its text bytes per record.  Until the consumer has
+ * reported a pair, avail is all text handed out and b the compressed bytes the file has left, which splits `want` in proportion to
+ * those; from then on both come from feedback(): after chunk k, left[x] text bytes of file x lay behind the cut and `pairs` had been cut
+ * in all, so avail = left + what has been handed out since chunk k, exactly, and b = (handed out up to k - left) / pairs.  The split
+ * leans towards the file that is behind by as much as it is behind, whatever is in flight between reader and consumer.  A file takes
+ * whole members until its share is reached (none for a share of 0), so it overshoots by less than one member.  A file that is read goes
+ * without a share, and the stream ends when both are, or behind a bad header.  units: the slot's members and one for the chunk itself, so
+ * that a chunk without members reaches the consumer too, which checks the ends of the files. */
+struct BgzfPairChunkInfo {
+    BgzfChunkInfo f[2];
+    bool done[2] = {false, false};
+};
+struct BgzfPairFill {
+    BgzfFile file[2];
+    const std::function<bool(int, size_t, size_t)> grow;
+    std::vector<char> carry[2];
+    bool done[2];
+    BgzfPairChunkInfo info[3];
+    static constexpr int HIST = 16; /* chunks whose hand-outs are remembered; the reader is at most 4 ahead of the feedback */
+    size_t issued[2] = {0, 0}, issued_at[HIST][2] = {};
+    int64_t chunk_no = 0;
+    std::mutex fb_mu; /* the consumer's report */
+    int64_t fb_chunk = -1, fb_pairs = 0;
+    size_t fb_left[2] = {0, 0};
+    BgzfPairFill(int fd1, int fd2, size_t bytes1, size_t bytes2, std::function<bool(int, size_t, size_t)> grow_)
+        : file{{fd1, bytes1}, {fd2, bytes2}}, grow(std::move(grow_)), done{bytes1 == 0, bytes2 == 0} {}
+
+    /* consumer: chunk `chunk` (0, 1, ...) has been cut; left: the text bytes of each file behind the cut, pairs: all pairs cut so far */
+    void feedback(int64_t chunk, size_t left1, size_t left2, int64_t pairs) {
+        std::lock_guard<std::mutex> lk(fb_mu);
+        fb_chunk = chunk, fb_left[0] = left1, fb_left[1] = left2, fb_pairs = pairs;
+    }
+    /* how many of `want` text bytes file 1 takes */
+    size_t share1(size_t want) {
+        if (done[0] || done[1]) return done[0] ? 0 : want;
+        int64_t k, pairs;
+        size_t left[2];
+        {
+            std::lock_guard<std::mutex> lk(fb_mu);
+            k = fb_chunk, pairs = fb_pairs, left[0] = fb_left[0], left[1] = fb_left[1];
+        }
+        long double avail[2], b[2];
+        const bool known = k >= 0 && chunk_no - k <= HIST && pairs > 0;
+        for (int x = 0; x < 2; x++) {
+            const size_t upto = known ? issued_at[k % HIST][x] : 0;
+            avail[x] = (long double)(known ? left[x] + (issued[x] - upto) : issued[x]);
+            b[x] = known ? (long double)(upto - left[x]) / (long double)pairs
+                         : (long double)(file[x].file_bytes - file[x].file_off + carry[x].size());
+        }
+        if (!(b[0] > 0) || !(b[1] > 0)) return b[0] > 0 ? want : b[1] > 0 ? 0 : want / 2;
+        const long double s = (b[0] * (avail[1] + (long double)want) - b[1] * avail[0]) / (b[0] + b[1]);
+        return s <= 0 ? 0 : s >= (long double)want ? want : (size_t)s;
+    }
+
+    bool operator()(ChunkSlot& s, int q, const std::vector<char>&, size_t want, ChunkCut& cut) {
+        BgzfPairChunkInfo& pi = info[q];
+        pi = BgzfPairChunkInfo();
+        const size_t s1 = share1(want);
+        const size_t share[2] = {s1, want - s1};
+        size_t base = 0;
+        bool bad = false;
+        for (int x = 0; x < 2; x++) {
+            BgzfChunkInfo& ci = pi.f[x];
+            ci.first_member = file[x].members_seen;
+            ci.file_base = file[x].file_off - carry[x].size();
+            /* a share of 0 takes nothing, unless the other file is read or takes nothing either */
+            const bool other_idle = done[1 - x] || share[1 - x] == 0;
+            if (!done[x] && !bad && (share[x] > 0 || other_idle)) {
+                size_t have = carry[x].size(), at = 0;
+                bool eof = false;
+                if (base + have + 8 > s.cap && !grow(q, base + have + 8 + 65536, base)) return false;
+                if (have) memcpy(s.buf + base, carry[x].data(), have);
+                if (!bgzf_fill_members(file[x], s, q, grow, base, share[x], ci, have, at, eof)) return false;
+                carry[x].assign(s.buf + base + at, s.buf + base + have);
+                done[x] = eof;
+                bad = ci.err.status != BGZF_IN_OK;
+                base += at;
+                issued[x] += ci.text;
+            }
+            pi.done[x] = done[x];
+            if (x == 0) cut.bytes1 = base;
+        }
+        issued_at[chunk_no % HIST][0] = issued[0], issued_at[chunk_no % HIST][1] = issued[1];
+        chunk_no++;
+        cut.have = cut.boundary = base;
+        cut.units = (int64_t)(pi.f[0].members.size() + pi.f[1].members.size()) + 1;
+        cut.eof = bad || (done[0] && done[1]);
         return true;
     }
 };

@@ -328,9 +328,36 @@ struct BgzfCutOut {
     uint32_t appended;        /* a newline was appended behind the text (the end of the file) */
     uint32_t pad;
 };
+/* One wavefront, every lane the same answer: the byte behind newline k (counted from 0) of text[0, nbytes), which holds more than k.
+ * tile_base[0 .. ntiles]: the exclusive sums of seq_count_kernel's tile counts, from any origin (tile_base[0] newlines lie in front of
+ * the text).  The newline's tile is found by bisection, the newline in it by ballots over 64 bytes at a time. */
+ASM_DEV unsigned long long seq_behind_newline(const char* __restrict__ text, unsigned long long nbytes, const uint32_t* __restrict__ tile_base,
+                                              uint32_t ntiles, uint32_t k, uint32_t lane) {
+    k += tile_base[0];
+    uint32_t lo = 0u, hi = ntiles - 1u; /* the last tile with tile_base <= k */
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1u) >> 1;
+        if (tile_base[mid] <= k) lo = mid;
+        else hi = mid - 1u;
+    }
+    uint32_t left = k - tile_base[lo]; /* newlines of the tile in front of it */
+    const unsigned long long t0 = (unsigned long long)lo * SEQ_TILE;
+    for (uint32_t i = 0; i < SEQ_TILE; i += 64u) {
+        const unsigned long long at = t0 + i + lane;
+        const unsigned long long mask = __ballot(at < nbytes && text[at] == '\n');
+        const uint32_t c = (uint32_t)__popcll(mask);
+        if (left < c) {
+            unsigned long long m = mask;
+            for (uint32_t d = 0; d < left; d++) m &= m - 1u;
+            return t0 + i + (uint32_t)__builtin_ctzll(m) + 1u;
+        }
+        left -= c;
+    }
+    return 0ull; /* not reached: the tile holds the newline */
+}
+
 /* One wavefront, behind seq_count_kernel and the exclusive sum of its tile counts (tile_base[ntiles]: all newlines): the record cut
- * of text[0, nbytes).  is_last: a text that does not end in a newline gets one at text[nbytes] (the buffer has room).  The tile of
- * the cut's newline is found by bisection, the newline in it by ballots over 64 bytes at a time. */
+ * of text[0, nbytes).  is_last: a text that does not end in a newline gets one at text[nbytes] (the buffer has room). */
 __global__ __launch_bounds__(64) void bgzf_cut_kernel(char* __restrict__ text, unsigned long long nbytes, const uint32_t* __restrict__ tile_base,
                                                       uint32_t ntiles, int is_last, BgzfCutOut* __restrict__ out) {
     const uint32_t lane = threadIdx.x;
@@ -339,29 +366,7 @@ __global__ __launch_bounds__(64) void bgzf_cut_kernel(char* __restrict__ text, u
     const unsigned long long lines = counted + (append ? 1u : 0u), need = lines / 4u * 4u;
     unsigned long long cut = 0;
     if (need > counted) cut = nbytes + 1u; /* the appended newline closes the last record */
-    else if (need > 0) {
-        const uint32_t k = (uint32_t)(need - 1u); /* the newline to find, counted from 0 */
-        uint32_t lo = 0u, hi = ntiles - 1u;       /* the last tile with tile_base <= k */
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi + 1u) >> 1;
-            if (tile_base[mid] <= k) lo = mid;
-            else hi = mid - 1u;
-        }
-        uint32_t left = k - tile_base[lo]; /* newlines of the tile in front of it */
-        const unsigned long long t0 = (unsigned long long)lo * SEQ_TILE;
-        for (uint32_t i = 0; i < SEQ_TILE; i += 64u) {
-            const unsigned long long at = t0 + i + lane;
-            const unsigned long long mask = __ballot(at < nbytes && text[at] == '\n');
-            const uint32_t c = (uint32_t)__popcll(mask);
-            if (left < c) {
-                unsigned long long m = mask;
-                for (uint32_t d = 0; d < left; d++) m &= m - 1u;
-                cut = t0 + i + (uint32_t)__builtin_ctzll(m) + 1u;
-                break;
-            }
-            left -= c;
-        }
-    }
+    else if (need > 0) cut = seq_behind_newline(text, nbytes, tile_base, ntiles, (uint32_t)(need - 1u), lane);
     if (lane == 0u) {
         if (append) text[nbytes] = '\n';
         out->lines = lines, out->cut = cut, out->appended = append ? 1u : 0u, out->pad = 0u;
@@ -450,6 +455,18 @@ static int map_file_gz_chunk(MapReadsFileJob& j, BgzfInput& gz, const char* d_sr
     return ASM_OK;
 }
 
+/* What an input file starts with: *gzip = a gzip member, which is BGZF or refused here as plain gzip; else text (or nothing).  The
+ * file calls probe at open and nowhere else; MapFileSession::open's first-byte probe (FASTA) stays apart. */
+static int map_file_probe(MapFileSession& ss, int fd, size_t file_bytes, const char* path, bool* gzip) {
+    uint8_t probe[4096];
+    const size_t probed = file_bytes ? (size_t)std::max<ssize_t>(pread(fd, probe, std::min(file_bytes, sizeof probe), 0), 0) : 0;
+    *gzip = probed >= 2 && probe[0] == 0x1fu && probe[1] == 0x8bu;
+    if (*gzip && bgzf_is_plain_gzip(probe, probed))
+        return ss.bad(std::string(path) + " is plain gzip, not BGZF (no BC subfield in its first member): recompress it with bgzip",
+                      ASM_EUNSUPPORTED);
+    return ASM_OK;
+}
+
 /* map_file_run for a file that starts with a BGZF member */
 static int map_file_run_gz(MapFileSession& ss, MapReadsFileJob& j, const char* fastq_path, size_t file_bytes) {
     asm_handle* h = ss.h;
@@ -489,14 +506,9 @@ static int map_file_run(asm_handle* h, const char* who, const asm_index* ix, con
     StreamInput& in = ss.in;
     size_t file_bytes = 0;
     if (const int rc = in.open_file(fastq_path, &file_bytes)) return rc;
-    /* the first bytes: a BGZF member (the compressed path), plain gzip (refused), or text.  For the single-end calls only, so it
-     * stands here and not in MapFileSession::open, whose first-byte probe (FASTA) the pairs call shares; text goes on as before */
-    uint8_t probe[4096];
-    const size_t probed = file_bytes ? (size_t)std::max<ssize_t>(pread(in.fd, probe, std::min(file_bytes, sizeof probe), 0), 0) : 0;
-    const bool gzip = probed >= 2 && probe[0] == 0x1fu && probe[1] == 0x8bu;
-    if (gzip && bgzf_is_plain_gzip(probe, probed))
-        return ss.bad(std::string(fastq_path) + " is plain gzip, not BGZF (no BC subfield in its first member): recompress it with bgzip",
-                      ASM_EUNSUPPORTED);
+    /* the first bytes: a BGZF member (the compressed path), plain gzip (refused), or text, which goes on as before */
+    bool gzip = false;
+    if (const int rc = map_file_probe(ss, in.fd, file_bytes, fastq_path, &gzip)) return rc;
     if (const int rc = ss.open(ix, seq_names, 1, &in.fd, &file_bytes, &fastq_path, sam_path, header)) return rc;
     MapReadsFileJob j = {{ss, ix, p}, max_hits, strata};
     if (gzip) {

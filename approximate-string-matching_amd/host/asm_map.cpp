@@ -10,7 +10,8 @@
 // --stream hands the FASTQ file and the SAM path to asm_map_file, which parses, maps and formats on the device while it reads and
 // writes (four-line FASTQ only; the same lines as without it); --chunk-bytes N: file bytes per chunk (default: the library's).
 // --stream-pairs does the same for paired mode through asm_map_pairs_file (two four-line FASTQ files; the lines of -1 / -2 without
-// --all-hits); --stream together with -2 is a usage error.
+// --all-hits); --stream together with -2 is a usage error.  Both take bgzip-compressed (BGZF) files as they are: the library probes
+// each file's first bytes and inflates on the device; the other modes parse their reads here and take text only.
 // --ref-stream (any mode) builds the index with asm_index_build_file, which reads and parses the reference on the device, and takes
 // the names and lengths for @SQ and RNAME from the index; without it the reference is parsed here.  The SAM is the same.
 // --sort (any mapping mode) writes the same lines in coordinate order: ascending (index of RNAME among the reference's sequences, POS),
@@ -68,6 +69,7 @@ static void usage() {
                     "[--max-occ N] [--all-hits N [--strata S]]\n"
                     "       asm-map -r ref.fa -1 r1.fq -2 r2.fq --stream-pairs [--chunk-bytes N] [-o out.sam] -e N --insert MIN,MAX "
                     "[--rescue E] [--k 12] [--max-occ N]\n"
+                    "       --stream takes reads.fq.gz, --stream-pairs r1.fq.gz and r2.fq.gz, as bgzip writes them (BGZF), inflated on the device\n"
                     "       any of them with --ref-stream: the reference is read and parsed by the library\n"
                     "       any of them with --mapq reference|gap: the model of the MAPQ column (default reference)\n"
                     "       any of them with --md: MD:Z on every line that shows a CIGAR\n"

@@ -568,7 +568,8 @@ int asm_bgzf_decompress_host(const void* src, size_t n, void* dst, size_t dst_ca
  *                  names the member's 0-based index and its file offset and says what is wrong; among the errors of one chunk the
  *                  smallest member is reported, before any record error of that chunk.  A gzip file that is not BGZF (magic 1f 8b,
  *                  no BC subfield in its first member): ASM_EUNSUPPORTED, the message says that the file is plain gzip and that
- *                  bgzip makes it usable.  asm_map_pairs_file* and asm_index_build_file read plain text only.
+ *                  bgzip makes it usable.  asm_map_pairs_file* take two such files ("Compressed input" there);
+ *                  asm_index_build_file reads plain text only.
  * asm_fastq_cut:   the length of the longest prefix of buf[0, nbytes) made of whole four-line records (every line ending in LF), and
  *                  how many records that is; no device. */
 typedef struct asm_map_file_stats {
@@ -593,11 +594,35 @@ size_t asm_fastq_cut(const char* buf, size_t nbytes, int64_t* records);
  *                  device chunk that holds an error reports it, a malformed record of file 1 before one of file 2 before a name,
  *                  each with its smallest record.  ASM_EUNSUPPORTED: a file starting with '>'.  Two empty files give the header
  *                  alone.  The output does not depend on chunk_bytes or ASM_MAP_CHUNK.
+ *                  Compressed input (asm_map_pairs_file and asm_map_pairs_file_sorted; docs/design/mapper.md, "Compressed input for
+ *                  pairs"): two files that each start with a BGZF member are inflated on the device, each under asm_map_file's
+ *                  "Compressed input" contract (empty members anywhere, an optional EOF block, a file that is only an EOF block is
+ *                  an empty file), and the concatenated member outputs of file f are its FASTQ text under the contract above (LF or
+ *                  CR LF, an optional last newline per file, lines and records straddling members and chunks).  The kind is probed
+ *                  from each file's first bytes at open.  The SAM or BAM bytes equal those of the same call on the two inflated
+ *                  texts, for every chunk_bytes (which stays text bytes of both files together per chunk), every ASM_MAP_CHUNK and
+ *                  every way either text was cut into members, the two files cut differently included; sorted output, BAM at both
+ *                  levels, MD, both MAPQ models and rescue run behind the text unchanged.  Both files must be of one kind: one
+ *                  BGZF file and one text file is ASM_EUNSUPPORTED, the message says which file is which kind (a file of no bytes
+ *                  goes with either).  Plain gzip in either file: ASM_EUNSUPPORTED, asm_map_file's message, naming the file.
+ *                  A corrupt container: ASM_EINVAL, "file <1|2>: BGZF member <0-based index> at offset <file offset>: <what>",
+ *                  <what> as for asm_map_file.  Of the errors of one chunk: the smallest bad member of file 1, then the smallest
+ *                  bad member of file 2, then the record errors in the order above.  The ends of the files are reported with the
+ *                  messages and record numbers above (a truncated record of a file read to its end, then a file that holds records
+ *                  without a mate), behind the pairs of the chunk that shows them; a missing mate is reported as soon as one file
+ *                  is read to its end and holds no further whole record while the other holds one, without reading the longer
+ *                  file on.  One difference to text input: line counts are learnt on the device chunk by chunk, so where the longer
+ *                  file also ends in a truncated record, the text call may have read that end already and report it, and this call
+ *                  reports the missing mate.  bytes_in stays the FASTQ text bytes of both files; carry_peak is the largest sum of
+ *                  the two texts' leftovers kept on the device between two chunks, in text bytes, and the one field a failed call
+ *                  on compressed input still sets; every other stats field keeps its meaning.  The argument checks come first and
+ *                  touch neither device, index nor file; the handle stays usable after an error.
  * asm_fastq_cut_n: asm_fastq_cut bounded to the first max_records records; no device. */
 typedef struct asm_map_pairs_file_stats {
     int64_t pairs, proper, rescued, unsent;   /* fragments; proper pairs; rescued mates; pairs with an empty or too long mate */
     int64_t records, chunks, bytes_in, bytes_out, carry_peak; /* SAM lines; device chunks; FASTQ bytes of both files; SAM bytes without
-                                                                 the header; the most bytes the reader held back between two chunks */
+                                                                 the header; the most bytes held back between two chunks: by the reader,
+                                                                 or for compressed input on the device (text bytes) */
     double seconds, seconds_read, seconds_write; /* whole call; reader busy; writer busy */
 } asm_map_pairs_file_stats;
 int asm_map_pairs_file(asm_handle* h, const asm_index* ix, const char* const* seq_names /* [n_seqs] */, const char* fastq1_path,
