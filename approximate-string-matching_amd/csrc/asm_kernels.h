@@ -23,6 +23,7 @@
 #include "asm_greedy_lane.h"
 #include "asm_leapunit.h"
 #include "asm_nwband.h"
+#include "asm_pack.h"
 
 #include "asm_limits.h" /* ASM_BLOCK and the other shapes the dispatch reads too */
 
@@ -54,103 +55,62 @@ struct PackBuckets {
     long plane_off[4];
 };
 
-ASM_DEV uint32_t swar_zero_bytes(uint32_t t) { /* bit 7 of each byte set iff that byte of t is zero (exact) */
-    return ~(((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t | 0x7f7f7f7fu);
-}
+ASM_DEV uint32_t pack_uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); } /* x is the same in every thread */
 
-// dwords of ONE plane array for a range of `nv` vectors: two vectors per dword, plus the dword the funnel shift of a
-// string's last output word reads past the range
-ASM_DEV int pack_plane_dwords(int nv) { return ((nv + 1) >> 1) + 1; }
-
-// 16 characters -> their 16 bits of plane 0 (C|T) and plane 1 (G|T); codes A=00 C=01 G=10 T=11, any other byte 00.
-ASM_DEV void pack_vec(const uint4 q, uint32_t& p0, uint32_t& p1) {
-    const uint32_t d[4] = {q.x, q.y, q.z, q.w};
-    uint32_t f0[4], f1[4], bad = 0u;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        // Bits 1-2 of 'A','C','T','G' are 0,1,2,3: as a v_perm_b32 selector into "ACTG" they give the one base each byte
-        // could be.  For a base, plane1 = bit 2 and plane0 = bit 1 ^ bit 2; canon ^ ch is accumulated to catch other bytes.
-        const uint32_t ch = d[k], half = ch >> 1;
-        const uint32_t canon = __builtin_amdgcn_perm(0u, 0x47544341u, half & 0x03030303u);
-        bad |= canon ^ ch;
-        f0[k] = (ch ^ half) & 0x02020202u; /* bit 1 of each byte */
-        f1[k] = ch & 0x04040404u;          /* bit 2 of each byte */
-    }
-    if (bad != 0u) { /* rare: exactly 'C','G','T' set plane bits; every other byte, NUL included, is code 00 */
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint32_t ch = d[k];
-            const uint32_t canon = __builtin_amdgcn_perm(0u, 0x47544341u, (ch >> 1) & 0x03030303u);
-            const uint32_t ok = swar_zero_bytes(canon ^ ch); /* 0x80 in every byte that is a real base */
-            f0[k] &= ok >> 6, f1[k] &= ok >> 5;
-        }
-    }
-    // gather the byte flags into bits with v_dot4_u32_u8 (weights 1,2,4,8 and 16..128 for the odd dword, accumulated
-    // onto the even one); the flags sit at bit 1 resp. 2 of their byte, so the sums come out scaled by 2 resp. 4
-    const uint32_t lo0 = __builtin_amdgcn_udot4(f0[1], 0x80402010u, __builtin_amdgcn_udot4(f0[0], 0x08040201u, 0u, false), false);
-    const uint32_t hi0 = __builtin_amdgcn_udot4(f0[3], 0x80402010u, __builtin_amdgcn_udot4(f0[2], 0x08040201u, 0u, false), false);
-    const uint32_t lo1 = __builtin_amdgcn_udot4(f1[1], 0x80402010u, __builtin_amdgcn_udot4(f1[0], 0x08040201u, 0u, false), false);
-    const uint32_t hi1 = __builtin_amdgcn_udot4(f1[3], 0x80402010u, __builtin_amdgcn_udot4(f1[2], 0x08040201u, 0u, false), false);
-    p0 = (lo0 | (hi0 << 8)) >> 1;
-    p1 = (lo1 | (hi1 << 8)) >> 2;
-}
-
-// Converts vectors [0, nvA + nvB) of the two ranges (A first) into plane arrays: A's plane 0 / plane 1 at u16 offsets
-// 0 / 2*pdA, B's at 4*pdA / 4*pdA + 2*pdB (pd = dwords per plane array).  Loads are issued PACK_UNROLL at a time.
+// Converts the vectors of the two ranges into plane arrays: A's plane 0 / plane 1 at u16 offsets 0 / 2*pdA, B's at 4*pdA /
+// 4*pdA + 2*pdB (pd = dwords per plane array).  Loads are issued PACK_UNROLL at a time, both sides in one loop.  Everything but t is
+// workgroup-uniform and the caller passes it from scalar registers.  The loop counts vectors with B's first one moved up to a
+// multiple of 64, so a wave's 64 vectors are always on one side: which side, the source pointer, the plane offsets, the number of
+// live threads and the loop itself are scalar work, and a thread is left with one add per address and one compare.
 ASM_DEV void pack_convert_range(uint16_t* sp, const uint4* __restrict__ srcA, int nvA, int pdA, const uint4* __restrict__ srcB,
                                 int nvB, int pdB, int t) {
-    const int tot = nvA + nvB;
+    const int startB = (nvA + 63) & ~63, tot = startB + nvB;
+    const int w0 = __builtin_amdgcn_readfirstlane(t); /* the wave's first thread */
+    const int lane = t - w0;
+    const uint32_t lane16 = 16u * (uint32_t)lane;
+    uint16_t* const spl = sp + lane;
 #pragma unroll 1
-    for (int v0 = t; v0 < tot; v0 += PACK_UNROLL * PACK_BLOCK) {
+    for (int base = 0; base < tot; base += PACK_UNROLL * PACK_BLOCK) {
         uint4 r[PACK_UNROLL];
 #pragma unroll
         for (int q = 0; q < PACK_UNROLL; q++) {
-            const int v = v0 + q * PACK_BLOCK;
-            if (v < tot) r[q] = v < nvA ? srcA[v] : srcB[v - nvA];
+            const int wv = base + q * PACK_BLOCK + w0; /* the wave's first vector: a multiple of 64 */
+            if (wv < tot) {
+                const bool sideA = wv < startB;
+                const uint4* src = sideA ? srcA + wv : srcB + (wv - startB);
+                if (lane < (sideA ? nvA : tot) - wv) r[q] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(src) + lane16);
+            }
         }
 #pragma unroll
         for (int q = 0; q < PACK_UNROLL; q++) {
-            const int v = v0 + q * PACK_BLOCK;
-            if (v < tot) {
+            const int wv = base + q * PACK_BLOCK + w0;
+            if (wv < tot) {
                 uint32_t p0, p1;
                 pack_vec(r[q], p0, p1);
-                uint16_t* d0 = v < nvA ? sp + v : sp + 4 * pdA + (v - nvA);
-                const int pd = v < nvA ? pdA : pdB;
-                d0[0] = (uint16_t)p0;
-                d0[2 * pd] = (uint16_t)p1;
+                const bool sideA = wv < startB;
+                const int at = sideA ? wv : 4 * pdA + (wv - startB);
+                if (lane < (sideA ? nvA : tot) - wv) {
+                    spl[at] = (uint16_t)p0;
+                    spl[at + 2 * (sideA ? pdA : pdB)] = (uint16_t)p1;
+                }
             }
         }
+        // every load of this turn has been used: said aloud, or the next turn's first address waits for loads it takes to be pending
+        __builtin_amdgcn_s_waitcnt(0x0f70); /* vmcnt(0) */
     }
 }
 
 // One thread cuts its string (byte offset `off` into the converted range, `len` characters) out of the plane arrays
-// P0 / P1 and stores its granules.
+// P0 / P1 (pack_cut_begin, pack_cut_granule: asm_pack.h) and stores its granules.
 template <int W4>
 ASM_DEV void pack_extract(const uint32_t* P0, const uint32_t* P1, uint32_t off, int len, int w4, int s,
                           const uint4* __restrict__ tails, long n, long pair, uint4* __restrict__ bplanes, long bn, long local) {
-    const int i = (int)(off >> 5);
-    const uint32_t sh = off & 31u;
-    uint32_t c0 = 0u, c1 = 0u; /* plane dwords i + k of the current output word k */
-    if (len > 0) c0 = P0[i], c1 = P1[i];
+    PackCut c = pack_cut_begin(P0, P1, off, len);
 #pragma unroll
     for (int g = 0; g < W4; g++) {
         if (g < w4) {
-            uint32_t q0[4] = {0u, 0u, 0u, 0u}, q1[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int w = 0; w < 4; w++) {
-                const int k = 4 * g + w;
-                if (32 * k < len) {
-                    const uint32_t n0 = P0[i + k + 1], n1 = P1[i + k + 1];
-                    // characters beyond the string's end (the next pair's bytes) are dropped once per 32 positions
-                    const int keep = len - 32 * k; /* > 0 */
-                    const uint32_t km = keep >= 32 ? ~0u : ((1u << keep) - 1u);
-                    q0[w] = __builtin_amdgcn_alignbit(n0, c0, sh) & km;
-                    q1[w] = __builtin_amdgcn_alignbit(n1, c1, sh) & km;
-                    c0 = n0, c1 = n1;
-                }
-            }
-            uint4 v0 = make_uint4(q0[0], q0[1], q0[2], q0[3]);
-            uint4 v1 = make_uint4(q1[0], q1[1], q1[2], q1[3]);
+            uint4 v0, v1;
+            pack_cut_granule(P0, P1, c, len, g, v0, v1);
             if (tails != nullptr && g == 0) {
                 const uint4 t0 = tails[(long)(2 * s) * n + pair], t1 = tails[(long)(2 * s + 1) * n + pair];
                 v0.x |= t0.x, v0.y |= t0.y, v0.z |= t0.z, v0.w |= t0.w;
@@ -195,8 +155,10 @@ __global__ __launch_bounds__(PACK_BLOCK) void pack_kernel(const char* __restrict
     if (t == 0) s_off[0][PACK_BLOCK] = read_off[p0 + np], s_off[1][PACK_BLOCK] = ref_off[p0 + np];
     __syncthreads();
     const uint32_t oA0 = s_off[0][t], oA1 = s_off[0][t + 1], oB0 = s_off[1][t], oB1 = s_off[1][t + 1];
-    const uint32_t baseA = s_off[0][0] & ~15u, baseB = s_off[1][0] & ~15u;
-    const int nvA = (int)((s_off[0][PACK_BLOCK] - baseA + 15u) >> 4), nvB = (int)((s_off[1][PACK_BLOCK] - baseB + 15u) >> 4);
+    // the block's ranges are the same in every thread: kept in scalar registers (pack_convert_range)
+    const uint32_t baseA = pack_uniform(s_off[0][0] & ~15u), baseB = pack_uniform(s_off[1][0] & ~15u);
+    const int nvA = (int)((pack_uniform(s_off[0][PACK_BLOCK]) - baseA + 15u) >> 4);
+    const int nvB = (int)((pack_uniform(s_off[1][PACK_BLOCK]) - baseB + 15u) >> 4);
     const int pdA = pack_plane_dwords(nvA), pdB = pack_plane_dwords(nvB);
     if (t < np) lens[slot] = (oA1 - oA0) | ((oB1 - oB0) << 16);
 
@@ -221,10 +183,10 @@ __global__ __launch_bounds__(PACK_BLOCK) void pack_kernel(const char* __restrict
         int ps = 0;
         while (ps < np) { /* uniform across the workgroup */
             __syncthreads();
-            const uint32_t base = s_off[s][ps] & ~15u;
+            const uint32_t base = pack_uniform(s_off[s][ps] & ~15u);
             const int fits = (t >= ps && t < np && 2 * pack_plane_dwords((int)((o1 - base + 15u) >> 4)) <= (int)lds_dwords) ? 1 : 0;
             const int pe = ps + __syncthreads_count(fits); /* offsets are monotone: the fitting pairs are [ps, pe) */
-            const int nv = (int)((s_off[s][pe] - base + 15u) >> 4), pd = pack_plane_dwords(nv);
+            const int nv = (int)((pack_uniform(s_off[s][pe]) - base + 15u) >> 4), pd = pack_plane_dwords(nv);
             const uint4* src = reinterpret_cast<const uint4*>(str + base);
             pack_convert_range(sp, src, nv, pd, src, 0, pd, t); /* B empty (a null B pointer crashes ROCm 7.2's inliner) */
             __syncthreads();

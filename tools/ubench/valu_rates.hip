@@ -75,6 +75,29 @@ struct Stamp {
         out[blockIdx.x * blockDim.x + threadIdx.x] = (uint32_t)acc ^ (uint32_t)(acc >> 32);                  \
     }
 
+// LDS instructions of pack_kernel, timed the same way: 16 independent accesses per turn, each thread at its own address (u16 t for the
+// 16-bit and 8-bit stores as pack_convert_range writes them, dword t for the loads as pack_cut reads them), one wait per turn.
+#define BENCH_LDS(name, ASM, SCALE)                                                                          \
+    __global__ __launch_bounds__(256) void name(uint32_t* out, Stamp* stamps, unsigned* gate, uint32_t a, uint32_t b) { \
+        __shared__ uint32_t lds[CH * 256 + 256];                                                             \
+        uint32_t v[CH];                                                                                      \
+        for (int c = 0; c < CH; c++) v[c] = a + threadIdx.x * 3 + c, lds[c * 256 + threadIdx.x] = v[c];      \
+        const uint32_t at = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)lds + threadIdx.x * SCALE; \
+        STAMP_BEGIN                                                                                          \
+        for (int it = 0; it < ITER / 4; it++) {                                                              \
+            _Pragma("unroll") for (int c = 0; c < CH; c++) asm volatile(ASM : "+v"(v[c]) : "v"(at + c * 1024)); \
+            asm volatile("s_waitcnt lgkmcnt(0)");                                                            \
+        }                                                                                                    \
+        STAMP_END                                                                                            \
+        uint32_t acc = lds[threadIdx.x];                                                                     \
+        for (int c = 0; c < CH; c++) acc ^= v[c];                                                            \
+        out[blockIdx.x * blockDim.x + threadIdx.x] = acc;                                                    \
+    }
+BENCH_LDS(l_write_b16, "ds_write_b16 %1, %0", 2)
+BENCH_LDS(l_write_b8, "ds_write_b8 %1, %0", 1)
+BENCH_LDS(l_write_b32, "ds_write_b32 %1, %0", 4)
+BENCH_LDS(l_read_b32, "ds_read_b32 %0, %1", 4)
+
 // FP32 controls
 BENCH32(c_fma_f32, "v_fma_f32 %0, %0, %1, %1")
 BENCH32(c_fmac_f32, "v_fmac_f32 %0, %1, %1")
@@ -113,6 +136,9 @@ BENCH32(k_not, "v_not_b32 %0, %0")
 BENCH32(k_mbcnt, "v_mbcnt_lo_u32_b32 %0, %1, %0")
 BENCH32(k_perm, "v_perm_b32 %0, %0, %1, %1")
 BENCH32(k_dot4, "v_dot4_u32_u8 %0, %0, %1, %0")
+BENCH32(k_dot4_0, "v_dot4_u32_u8 %0, %0, %1, 0") /* no accumulator: pack_vec's form */
+BENCH32(k_or, "v_or_b32 %0, %0, %1")
+BENCH32(k_lshl_or4, "v_lshl_or_b32 %0, %0, 4, %1")
 BENCH32(k_bitop3, "v_bitop3_b32 %0, %0, %1, %1 bitop3:0x48")
 BENCH32(k_sad, "v_sad_u8 %0, %0, %1, %0")
 // the packed 16-bit instructions of nw_band2x16 (csrc/asm_nwband.h) and the other NW opcodes: shift counts from a VGPR and
@@ -148,7 +174,7 @@ static std::string g_json;
 static std::vector<double> g_clocks;
 
 template <typename K>
-void run(const char* name, K kern, int instr_per_op, int waves_per_simd = 8) {
+void run(const char* name, K kern, int instr_per_op, int waves_per_simd = 8, int iter = ITER) {
     uint32_t* d;
     Stamp* st;
     const int blocks = 256 * waves_per_simd, threads = 256; /* 4 waves per block, one per SIMD */
@@ -181,7 +207,7 @@ void run(const char* name, K kern, int instr_per_op, int waves_per_simd = 8) {
     std::sort(cyc.begin(), cyc.end());
     std::sort(clk.begin(), clk.end());
     const double wave_cycles = cyc[nw / 2], sclk = clk[nw / 2];
-    const double per_wave = (double)ITER * CH * instr_per_op;
+    const double per_wave = (double)iter * CH * instr_per_op;
     // Lower bound: all waves_per_simd waves of a SIMD run their loops side by side for a wave's whole loop time.
     // Upper bound: the SIMD needs the whole span from the first wave's start to the last wave's end for them (waves that
     // were dispatched late, e.g. when the grid exactly fills the chip and a CU was full, stretch the span).
@@ -219,6 +245,9 @@ int main() {
     R(k_med3_u); R(k_bfe_i); R(k_shl_c); R(k_shr_c); R(k_alignbit_c); R(k_bfrev); R(k_add_co); R(k_addc_co);
     R(k_dpp_mov); R(k_dpp_wave);
     run("k_readlane", k_readlane, 2);
+    R(k_dot4_0); R(k_or); R(k_lshl_or4);
+    run("l_write_b16", l_write_b16, 1, 8, ITER / 4); run("l_write_b8", l_write_b8, 1, 8, ITER / 4);
+    run("l_write_b32", l_write_b32, 1, 8, ITER / 4); run("l_read_b32", l_read_b32, 1, 8, ITER / 4);
     R(k_shl64); R(k_shr64); R(k_add64); R(k_fma64); R(k_mul64); R(k_cvt);
     std::sort(g_clocks.begin(), g_clocks.end());
     printf("JSON {\"sclk_hz_median\": %.0f, \"rows\": {%s}}\n", g_clocks[g_clocks.size() / 2], g_json.c_str());
