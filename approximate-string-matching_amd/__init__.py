@@ -119,6 +119,12 @@ class SamSortStats(ctypes.Structure):
     _fields_ = [("lines", ctypes.c_int64), ("bytes_held", ctypes.c_int64), ("slabs", ctypes.c_int64), ("seconds_sort", ctypes.c_double)]
 
 
+class BamIndexStats(ctypes.Structure):
+    """asm_bam_index_stats"""
+    _fields_ = [("refs", ctypes.c_int64), ("bins", ctypes.c_int64), ("chunks", ctypes.c_int64), ("intervals", ctypes.c_int64),
+                ("no_coor", ctypes.c_int64), ("bytes", ctypes.c_int64), ("seconds_index", ctypes.c_double)]
+
+
 class IndexFileStats(ctypes.Structure):
     """asm_index_file_stats"""
     _fields_ = [("n_seqs", ctypes.c_int64), ("bases", ctypes.c_int64), ("bytes_in", ctypes.c_int64), ("chunks", ctypes.c_int64),
@@ -139,6 +145,7 @@ MAPQ_REFERENCE, MAPQ_GAP = 0, 1  # asm_map_set_mapq_model
 SAM_TAG_MD, MAP_MD_CAP = 1, 80  # asm_map_set_sam_tags; ASM_MAP_MD_CAP: an MD tag and its NUL always fit
 OUT_SAM, OUT_BAM, BGZF_PAYLOAD = 0, 1, 65280  # asm_map_set_output_format; ASM_BGZF_PAYLOAD: uncompressed bytes per BGZF block
 BGZF_STORED, BGZF_DEFLATE = 0, 1  # asm_map_set_bgzf_level: the BAM container's blocks
+BAM_INDEX_NONE, BAM_INDEX_BAI = 0, 1  # asm_map_set_bam_index: what the sorted BAM calls write beside the file
 MAP_SECONDARY, MAP_HITS_TRUNCATED, MAP_MAX_HITS = 16, 32, 256
 MAP_PROPER_PAIR, MAP_RESCUED, MAP_MAX_INSERT = 64, 128, 8192
 MAP_MIN_K, MAP_MAX_K, MAP_MAX_READ, MAP_MAX_ERRORS = 8, 14, 511, 15
@@ -294,6 +301,10 @@ def load_library() -> ctypes.CDLL:
         "asm_map_get_bgzf_level": (i32, [vp]),
         "asm_bgzf_compress": (i32, [vp, vp, c.c_size_t, i32, i32, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
         "asm_bgzf_compress_host": (i32, [vp, c.c_size_t, i32, i32, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
+        "asm_map_set_bam_index": (i32, [vp, i32]),
+        "asm_map_get_bam_index": (i32, [vp]),
+        "asm_map_last_bam_index": (i32, [vp, c.POINTER(BamIndexStats)]),
+        "asm_bam_index_host": (i32, [vp, c.c_size_t, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
         "asm_bgzf_decompressed_size": (i32, [vp, c.c_size_t, c.POINTER(c.c_size_t)]),
         "asm_bgzf_decompress": (i32, [vp, vp, c.c_size_t, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
         "asm_bgzf_decompress_host": (i32, [vp, c.c_size_t, vp, c.c_size_t, c.POINTER(c.c_size_t)]),
@@ -678,6 +689,24 @@ class Engine:
     def get_bgzf_level(self) -> int:
         """asm_map_get_bgzf_level: the level in force (BGZF_STORED, BGZF_DEFLATE)"""
         return int(self.lib.asm_map_get_bgzf_level(self.h))
+
+    def set_bam_index(self, kind) -> None:
+        """asm_map_set_bam_index: BAM_INDEX_NONE / "none" (the default) or BAM_INDEX_BAI / "bai": under OUT_BAM the sorted file calls
+        then write `<sam_path>.bai` beside the BAM file, a BAI index built on the device (docs/design/mapper.md, "BAM index").  No
+        effect under OUT_SAM or in the unsorted calls."""
+        self._chk(self.lib.asm_map_set_bam_index(self.h, {"none": BAM_INDEX_NONE, "bai": BAM_INDEX_BAI}.get(kind, kind)))
+
+    @property
+    def bam_index(self) -> int:
+        """asm_map_get_bam_index: the kind in force (BAM_INDEX_NONE, BAM_INDEX_BAI)"""
+        return int(self.lib.asm_map_get_bam_index(self.h))
+
+    def last_bam_index(self) -> dict:
+        """asm_map_last_bam_index: refs, bins, chunks, intervals, no_coor, bytes and seconds_index of the last sorted BAM call of
+        this engine that wrote an index; all zero before one"""
+        st = BamIndexStats()
+        self._chk(self.lib.asm_map_last_bam_index(self.h, ctypes.byref(st)))
+        return {name: getattr(st, name) for name, _ in BamIndexStats._fields_}
 
     def bgzf_compress(self, data: bytes, eof: bool = True, level: int = BGZF_DEFLATE) -> bytes:
         """asm_bgzf_compress: bgzf_frame with a level, by the device kernels of the BAM file calls.  Level BGZF_STORED gives
@@ -1294,6 +1323,23 @@ def bgzf_decompressed_size(data: bytes) -> int:
     if rc != 0:
         raise AsmError(rc, lib.asm_last_error(None).decode())
     return int(got.value)
+
+
+def bam_index_host(data: bytes) -> bytes:
+    """asm_bam_index_host: the BAI index of a whole coordinate-sorted BAM file, by the host build of the core the device index is
+    made of (docs/design/mapper.md, "BAM index"); no device"""
+    lib = load_library()
+    data = bytes(data)
+    cap, got = 1 << 16, ctypes.c_size_t(0)
+    for _ in range(2):
+        out = ctypes.create_string_buffer(cap)
+        rc = lib.asm_bam_index_host(data if data else None, len(data), out, cap, ctypes.byref(got))
+        if rc == 0:
+            return out.raw[: got.value]
+        if got.value <= cap:
+            break
+        cap = got.value  # the size it needs
+    raise AsmError(rc, lib.asm_last_error(None).decode())
 
 
 def bgzf_decompress_host(data: bytes) -> bytes:

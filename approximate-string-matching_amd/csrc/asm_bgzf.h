@@ -242,10 +242,20 @@ static hipError_t bgzf_frame_device(asm_handle* h, const char* src, size_t n, in
                   (uint32_t)nblocks, (uint8_t*)dst);
 }
 
+/* bgzf_frame_kernel's blocks of n payload bytes: their sizes in the file, for the sorted BAM call's index (asm_bai.h) */
+__global__ __launch_bounds__(256) void bgzf_stored_sizes_kernel(unsigned long long* __restrict__ size, uint32_t nblocks, unsigned long long n) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nblocks) return;
+    const unsigned long long left = n - (unsigned long long)b * BGZF_PAYLOAD;
+    size[b] = (left < BGZF_PAYLOAD ? left : BGZF_PAYLOAD) + BGZF_FRONT + BGZF_BACK;
+}
+
 /* The same at ASM_BGZF_DEFLATE: the blocks encoded at a fixed stride (bgzf_deflate_kernel), their sizes summed, the blocks moved
  * together into dst (bgzf_compact_kernel) with the EOF block behind them when with_eof, and the bytes written read back into *total
- * (one wait).  dst holds bgzf_bound(n, with_eof) bytes.  Nothing to encode launches nothing and waits for nothing. */
-static hipError_t bgzf_deflate_device(asm_handle* h, const char* src, size_t n, int with_eof, char* dst, size_t* total) {
+ * (one wait).  dst holds bgzf_bound(n, with_eof) bytes.  Nothing to encode launches nothing and waits for nothing.  keep: NULL, or room
+ * on the device for the blocks' sizes, copied there in stream order. */
+static hipError_t bgzf_deflate_device(asm_handle* h, const char* src, size_t n, int with_eof, char* dst, size_t* total,
+                                      unsigned long long* keep = nullptr) {
     typedef unsigned long long u64;
     const size_t nblocks = bgzf_blocks(n);
     *total = 0;
@@ -259,6 +269,7 @@ static hipError_t bgzf_deflate_device(asm_handle* h, const char* src, size_t n, 
     if (e == hipSuccess) e = hipMemsetAsync(d_size.p + nblocks, 0, sizeof(u64), h->stream);
     if (e == hipSuccess && nblocks)
         e = launch(h, bgzf_deflate_kernel, (unsigned)nblocks, BGZF_THREADS, (const uint8_t*)src, (u64)n, (uint32_t)nblocks, d_tmp.p, d_size.p);
+    if (e == hipSuccess && keep && nblocks) e = hipMemcpyAsync(keep, d_size.p, sizeof(u64) * nblocks, hipMemcpyDeviceToDevice, h->stream);
     if (e == hipSuccess) e = map_exclusive_sum(h, tmp, d_size.p, d_off.p, (int64_t)nblocks + 1);
     if (e == hipSuccess)
         e = launch(h, bgzf_compact_kernel, (unsigned)(nblocks + (with_eof ? 1 : 0)), BGZF_THREADS, (const uint8_t*)d_tmp.p, (const u64*)d_size.p,
@@ -268,10 +279,16 @@ static hipError_t bgzf_deflate_device(asm_handle* h, const char* src, size_t n, 
     *total = (size_t)end + (with_eof ? BGZF_EOF : 0u);
     return e;
 }
-/* src framed into dst at `level`; *total: the bytes written (ASM_BGZF_STORED: the bound, with no wait) */
-static hipError_t bgzf_level_device(asm_handle* h, int level, const char* src, size_t n, int with_eof, char* dst, size_t* total) {
-    if (level == ASM_BGZF_DEFLATE) return bgzf_deflate_device(h, src, n, with_eof, dst, total);
+/* src framed into dst at `level`; *total: the bytes written (ASM_BGZF_STORED: the bound, with no wait); keep: NULL, or room on the
+ * device for the size of every block framed */
+static hipError_t bgzf_level_device(asm_handle* h, int level, const char* src, size_t n, int with_eof, char* dst, size_t* total,
+                                    unsigned long long* keep = nullptr) {
+    if (level == ASM_BGZF_DEFLATE) return bgzf_deflate_device(h, src, n, with_eof, dst, total, keep);
     *total = bgzf_bound(n, with_eof);
+    if (keep && n)
+        if (const hipError_t e = launch(h, bgzf_stored_sizes_kernel, (unsigned)((bgzf_blocks(n) + 255u) / 256u), 256u, keep, (uint32_t)bgzf_blocks(n),
+                                        (unsigned long long)n))
+            return e;
     return bgzf_frame_device(h, src, n, with_eof, dst);
 }
 
@@ -280,11 +297,14 @@ static hipError_t bgzf_level_device(asm_handle* h, int level, const char* src, s
  * the next one.  Per chunk: stage(n) gives a buffer with the carry in front and room for the chunk's n bytes; the caller fills those
  * and calls frame(), which writes at most framed(n) bytes of whole blocks and keeps the rest.  tail() frames what is left and the EOF
  * block, at most tail_bytes().  Both give the bytes they wrote: the bound at ASM_BGZF_STORED, what the encoder made of it at
- * ASM_BGZF_DEFLATE (read back with one wait). */
+ * ASM_BGZF_DEFLATE (read back with one wait).  keep: NULL, or a device table with room for the size in the file of every block of the
+ * stream, in order (the sorted call's index, asm_bai.h); kept counts them. */
 struct BgzfStream {
     asm_handle* h;
     Scratch<char> carry;
     size_t carry_len = 0;
+    unsigned long long* keep = nullptr;
+    size_t kept = 0;
     const int level;
     explicit BgzfStream(asm_handle* owner) : h(owner), carry(owner), level(owner->bgzf_level) {}
     hipError_t open() { return carry.alloc(BGZF_PAYLOAD + BGZF_SRC_PAD); }
@@ -297,13 +317,13 @@ struct BgzfStream {
     }
     hipError_t frame(const Scratch<char>& buf, size_t n, char* dst, size_t* written) {
         const size_t whole = (carry_len + n) / BGZF_PAYLOAD * BGZF_PAYLOAD, rest = carry_len + n - whole;
-        if (const hipError_t e = bgzf_level_device(h, level, buf.p, whole, 0, dst, written)) return e;
-        carry_len = rest;
+        if (const hipError_t e = bgzf_level_device(h, level, buf.p, whole, 0, dst, written, keep ? keep + kept : nullptr)) return e;
+        carry_len = rest, kept += whole / BGZF_PAYLOAD;
         return rest ? hipMemcpyAsync(carry.p, buf.p + whole, rest, hipMemcpyDeviceToDevice, h->stream) : hipSuccess;
     }
     hipError_t tail(char* dst, size_t* written) {
-        const hipError_t e = bgzf_level_device(h, level, carry.p, carry_len, 1, dst, written);
-        carry_len = 0;
+        const hipError_t e = bgzf_level_device(h, level, carry.p, carry_len, 1, dst, written, keep ? keep + kept : nullptr);
+        kept += bgzf_blocks(carry_len), carry_len = 0;
         return e;
     }
 };

@@ -130,6 +130,8 @@ struct asm_handle {
     unsigned sam_tags = 0;                /* asm_map_set_sam_tags: the optional tags of the file calls' lines (ASM_SAM_TAG_MD) */
     int out_format = 0;                   /* asm_map_set_output_format: what the file calls write, ASM_OUT_SAM or ASM_OUT_BAM */
     int bgzf_level = 0;                   /* asm_map_set_bgzf_level: the BAM container's blocks, ASM_BGZF_STORED or ASM_BGZF_DEFLATE */
+    int bam_index = 0;                    /* asm_map_set_bam_index: what the sorted BAM calls write beside the file, ASM_BAM_INDEX_NONE or _BAI */
+    asm_bam_index_stats last_bai = {};    /* asm_map_last_bam_index: of the last sorted BAM call that wrote an index */
     std::vector<hipEvent_t> prof_ev;      /* asm_profile_enable: 8 events per recorded asm_run_benchmark_async call */
     std::vector<unsigned> prof_mask;      /* which of a call's four kernels were launched */
     int prof_cap = 0;
@@ -740,6 +742,8 @@ int asm_stream_seq_file(asm_handle* h, const char* path, const asm_params* p, in
 #include "asm_map_out.h"
 /* what the sorted file calls keep on the device, their sort and their gather */
 #include "asm_sam_sort.h"
+/* the BAI index beside a sorted BAM file, built from what the sort leaves on the device */
+#include "asm_bai.h"
 /* asm_map_file: FASTQ in, SAM out, through the same stages */
 #include "asm_map_file.h"
 /* asm_map_pairs_file: two FASTQ files in, paired SAM out */

@@ -33,6 +33,8 @@ struct MapFileSession {
     } st = {};
     std::function<size_t(const asm_host::ChunkSlot&)> text_bytes; /* set: a chunk's share of bytes_in is not the bytes it ships (BGZF) */
     std::unique_ptr<SamSortHold> sort; /* the sorted calls: the formatted chunks stay on the device until finish() (asm_sam_sort.h) */
+    std::vector<uint32_t> ref_len;     /* a sorted BAM call that writes an index (asm_bai.h): the sequences' lengths, and its path */
+    std::string bai_path;
     MapFileSession(asm_handle* owner, const char* call, size_t chunk_bytes)
         : h(owner), who(call), in(owner, call), out(owner, call), d_names(owner), d_name_off(owner), chunk(chunk_bytes) {}
     ~MapFileSession() {
@@ -70,6 +72,10 @@ struct MapFileSession {
             bgzf_compress_host(text.data(), text.size(), 0, h->bgzf_level, head, nullptr);
         } else if (header) {
             head.assign(header, header + strlen(header));
+        }
+        if (sort && sort->index) {
+            for (int32_t r = 0; r < ix->n_seqs; r++) ref_len.push_back((uint32_t)asm_index_seq_len(ix, r));
+            bai_path = std::string(sam_path) + ".bai";
         }
         if (const int rc = out.open(sam_path, head)) return rc;
         STREAM_TRY(who, d_names.alloc(names.size() + 16));
@@ -118,6 +124,8 @@ struct MapFileSession {
         if (sort)
             if (const int rc = sort->flush(out, chunk)) return rc;
         if (const int rc = out.finish(&stats.seconds_write)) return rc;
+        if (sort && sort->index) /* the BAM file is complete: its index, from what the sort left on the device */
+            if (const int rc = bai_index_device(*sort, out.head_bytes, ref_len, bai_path)) return rc;
         stats.chunks = st.chunks, stats.bytes_in = st.bytes_in, stats.bytes_out = out.bytes_out, stats.records = st.records;
         stats.seconds_read = st.seconds_read;
         stats.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
@@ -546,6 +554,17 @@ static int map_file_sort_cap(asm_handle* h, const char* who, const int64_t* sort
     return sort_cap && *sort_cap < 0 ? fail(h, ASM_EINVAL, std::string(who) + ": max_device_bytes must be >= 0") : (int)ASM_OK;
 }
 
+/* A sorted BAM call under ASM_BAM_INDEX_BAI, behind the other argument checks: BAI holds coordinates below 2^29 */
+static int map_file_index_check(asm_handle* h, const char* who, const asm_index* ix, const char* const* seq_names, const int64_t* sort_cap) {
+    if (!sort_cap || h->out_format != ASM_OUT_BAM || h->bam_index != ASM_BAM_INDEX_BAI) return ASM_OK;
+    for (int32_t r = 0; r < asm_index_n_seqs(ix); r++)
+        if (asm_index_seq_len(ix, r) > ((uint64_t)1 << 29))
+            return fail(h, ASM_EUNSUPPORTED, std::string(who) + ": sequence " + std::to_string(r) + " (" + (seq_names[r] ? seq_names[r] : "") + ") has " +
+                                                 std::to_string(asm_index_seq_len(ix, r)) +
+                                                 " bases; a .bai index holds coordinates below 2^29: such a reference needs a .csi index");
+    return ASM_OK;
+}
+
 /* asm_map_file and asm_map_file_sorted (`who`): the argument checks, then the call */
 static int map_file_call(const char* who, asm_handle* h, const asm_index* ix, const char* const* seq_names, const char* fastq_path,
                          const char* sam_path, const char* header, const asm_map_params* p, int max_hits, int strata, int64_t chunk_bytes,
@@ -560,6 +579,7 @@ static int map_file_call(const char* who, asm_handle* h, const asm_index* ix, co
                                       {0, p, {nullptr, nullptr}, nullptr, max_hits ? "max_hits" : nullptr, strata, ASM_MAP_MAX_ERRORS,
                                        max_hits, {nullptr, 0, nullptr}}))
         return rc;
+    if (const int rc = map_file_index_check(h, who, ix, seq_names, sort_cap)) return rc;
     if (stats) memset(stats, 0, sizeof *stats);
     if (sort_stats) memset(sort_stats, 0, sizeof *sort_stats);
     HIPCHK(h, hipSetDevice(h->device));

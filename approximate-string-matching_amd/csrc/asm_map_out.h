@@ -31,6 +31,7 @@ struct MapOutput {
     std::unique_ptr<BgzfStream> bam; /* ASM_OUT_BAM: the payload is BAM records and leaves through the BGZF record stream */
     int64_t jobs = 0;                /* handed to the writer so far */
     int64_t bytes_out = 0;           /* in those jobs: the file's bytes behind its head */
+    size_t head_bytes = 0;           /* the file's head */
     MapOutput(asm_handle* owner, const char* call) : h(owner), who(call) {}
     MapOutput(const MapOutput&) = delete;
     MapOutput& operator=(const MapOutput&) = delete;
@@ -53,6 +54,7 @@ struct MapOutput {
     int open(const char* path, const std::vector<uint8_t>& head) {
         file = fopen(path, "wb");
         if (!file) return fail(h, ASM_EINVAL, std::string(who) + ": cannot write " + path);
+        head_bytes = head.size();
         if (!head.empty() && fwrite(head.data(), 1, head.size(), file) != head.size()) return map_out_failed(h, who);
         STREAM_TRY(who, hipStreamCreateWithFlags(&s_out, hipStreamNonBlocking));
         for (hipEvent_t* ev : {&ev_fmt[0], &ev_fmt[1], &ev_fmt[2], &ev_copied[0], &ev_copied[1], &ev_copied[2]})

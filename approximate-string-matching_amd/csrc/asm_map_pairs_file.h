@@ -370,6 +370,7 @@ static int map_pairs_file_call(const char* who, asm_handle* h, const asm_index* 
     if (const int rc = map_file_chunk_bytes(h, who, chunk_bytes, &chunk)) return rc;
     if (const int rc = map_file_sort_cap(h, who, sort_cap)) return rc;
     if (const int rc = map_check_args(h, ix, who, "mate", {0, p, {nullptr, nullptr}, pp, nullptr, 0, 0, 0, {nullptr, 0, nullptr}})) return rc;
+    if (const int rc = map_file_index_check(h, who, ix, seq_names, sort_cap)) return rc;
     if (stats) memset(stats, 0, sizeof *stats);
     if (sort_stats) memset(sort_stats, 0, sizeof *sort_stats);
     HIPCHK(h, hipSetDevice(h->device));

@@ -100,12 +100,19 @@ __global__ __launch_bounds__(256) void sam_line_gather_kernel(const unsigned lon
  * Every allocation of the hold (the held text, the line tables, the sort's arrays) is counted against max_device_bytes first (cap;
  * 0: none); the blocks go back to the pool with the session.  Not counted, as in the unsorted call: the output slots of the rotation
  * (at most a slab each) and, under ASM_OUT_BAM, a slab's staging block (the stream's carry of less than a BGZF block plus the
- * slab), which lives for one slab. */
+ * slab), which lives for one slab.
+ * index: a BAM call under ASM_BAM_INDEX_BAI.  flush() then keeps the sources and offsets in output order and gives the record stream a
+ * table for its blocks' sizes; bai_index_device (asm_bai.h) builds the index from them when the output is finished, in allocations of
+ * this hold. */
 struct SamSortHold {
     asm_handle* h;
     const char* who;
     const int32_t n_seqs;
     const size_t cap;
+    const bool index;
+    unsigned long long *psrc = nullptr, *off = nullptr; /* [lines], [lines + 1]: set by flush() */
+    unsigned long long* blk_size = nullptr;             /* index: [nblk + 1], the last one 0 */
+    size_t nblk = 0;
     size_t used = 0, reached = 0;
     struct Chunk { /* one held device chunk: its SAM bytes and its line tables */
         char* text;
@@ -116,7 +123,8 @@ struct SamSortHold {
     std::vector<void*> owned; /* everything to give back */
     asm_sam_sort_stats st = {};
     SamSortHold(asm_handle* owner, const char* call, int32_t seqs, size_t max_device_bytes)
-        : h(owner), who(call), n_seqs(seqs), cap(max_device_bytes) {}
+        : h(owner), who(call), n_seqs(seqs), cap(max_device_bytes),
+          index(owner->out_format == ASM_OUT_BAM && owner->bam_index == ASM_BAM_INDEX_BAI) {}
     SamSortHold(const SamSortHold&) = delete;
     SamSortHold& operator=(const SamSortHold&) = delete;
     ~SamSortHold() {
@@ -205,7 +213,7 @@ struct SamSortHold {
         STREAM_TRY(who, map_sort_pairs(h, tmp, key, key_sorted, idx, idx_sorted, (uint32_t)n, 32 + tid_bits));
         release(key, table), release(key_sorted, table), release(idx, sizeof(uint32_t) * n);
         /* sources and sizes in output order, then the 64-bit output offsets (the scan's own count is 64-bit here: n + 1 may pass 2^31) */
-        u64 *psrc = nullptr, *psize = nullptr, *off = nullptr;
+        u64* psize = nullptr;
         if (const int rc = alloc(&psrc, table)) return rc;
         if (const int rc = alloc(&psize, table + sizeof(u64))) return rc;
         if (const int rc = alloc(&off, table + sizeof(u64))) return rc;
@@ -218,6 +226,12 @@ struct SamSortHold {
         release(src, table), release(size, table), release(idx_sorted, sizeof(uint32_t) * n), release(psize, table + sizeof(u64));
         std::vector<uint64_t> h_off(n + 1);
         STREAM_TRY(who, fetch(h, {fetched((u64*)h_off.data(), (const u64*)off, n + 1)}));
+        if (index) { /* the sizes of the record stream's blocks, as the stream frames them */
+            nblk = bgzf_blocks((size_t)h_off[n]);
+            if (const int rc = alloc(&blk_size, sizeof(u64) * (nblk + 1))) return rc;
+            STREAM_TRY(who, hipMemsetAsync(blk_size, 0, sizeof(u64) * (nblk + 1), h->stream));
+            out.bam->keep = blk_size;
+        }
         const std::vector<size_t> cuts = asm_host::sam_slab_cuts(h_off.data(), n, slab_cap);
         for (size_t s = 0; s + 1 < cuts.size(); s++) {
             const size_t i0 = cuts[s], cnt = cuts[s + 1] - i0;

@@ -30,6 +30,8 @@
 // docs/design/mapper.md, "BAM output"): the same records, encoded and BGZF-framed in stored blocks on the device.  The header text
 // and every other option are as for SAM.  With any other mode it is a usage error.  --bam-level 0|1 (with --bam; default 0) is the
 // container's level (asm_map_set_bgzf_level; docs/design/mapper.md, "Deflate"): 1 deflates every block on the device.
+// --bai (with --bam --sort under --stream or --stream-pairs) makes the library write the BAI index <out>.bai beside the BAM file
+// (asm_map_set_bam_index; docs/design/mapper.md, "BAM index"), built on the device.  Anywhere else it is a usage error.
 //   asm-map -r ref.fa --bench-ref N [--k 12]
 // maps nothing: it builds the index N times each way, alternately, and prints the seconds of every build.
 // --all-hits N writes up to N loci per read in rank order (asm_map_reads_all, strata S, default e): the primary record as without
@@ -75,6 +77,7 @@ static void usage() {
                     "       any of them with --md: MD:Z on every line that shows a CIGAR\n"
                     "       --stream, --stream-pairs with --bam: BAM output (BGZF with stored blocks), encoded on the device\n"
                     "       --bam with --bam-level 0|1: 0 (default) stored blocks, 1 deflate blocks compressed on the device\n"
+                    "       --bam --sort with --bai: the BAI index <out>.bai beside the BAM file, built on the device\n"
                     "       any of them with --sort: coordinate-sorted output (--stream, --stream-pairs: on the device, [--sort-mem BYTES])\n");
     exit(2);
 }
@@ -345,6 +348,10 @@ static bool write_sorted(FILE* file, const char* text, size_t len, const std::ve
 }
 
 /* the report line of --sort with --stream or --stream-pairs */
+static void report_index(const asm_bam_index_stats& st) {
+    fprintf(stderr, "asm-map: index of %lld bytes: %lld bins, %lld chunks, %lld windows, %lld records without coordinates, %.3f s\n",
+            (long long)st.bytes, (long long)st.bins, (long long)st.chunks, (long long)st.intervals, (long long)st.no_coor, st.seconds_index);
+}
 static void report_sorted(const asm_sam_sort_stats& st) {
     fprintf(stderr, "asm-map: sorted %lld lines, %lld bytes held on the device, %lld slabs, %.3f s\n", (long long)st.lines,
             (long long)st.bytes_held, (long long)st.slabs, st.seconds_sort);
@@ -437,7 +444,7 @@ int main(int argc, char** argv) {
     int k = 12;
     long chunk = 262144;
     int all_hits = 0, strata = -1; /* all_hits 0: the best hit only */
-    bool stream = false, stream_pairs = false, ref_stream = false, sort = false, md = false, bam = false;
+    bool stream = false, stream_pairs = false, ref_stream = false, sort = false, md = false, bam = false, bai = false;
     int bam_level = -1; /* --bam-level: not given */
     int bench_ref = 0;
     long long chunk_bytes = 0, sort_mem = -1;
@@ -472,6 +479,7 @@ int main(int argc, char** argv) {
         else if (s == "--sort") sort = true;
         else if (s == "--md") md = true;
         else if (s == "--bam") bam = true;
+        else if (s == "--bai") bai = true;
         else if (s == "--bam-level") {
             const std::string v = val();
             if (v != "0" && v != "1") usage();
@@ -493,6 +501,10 @@ int main(int argc, char** argv) {
     if (stream_pairs && (!paired || all_hits || stream)) usage(); /* secondary pairs from files: not there */
     if (bam && !stream && !stream_pairs) {
         fprintf(stderr, "asm-map: --bam needs --stream or --stream-pairs (the library writes BAM from the streamed modes only)\n");
+        usage();
+    }
+    if (bai && (!bam || !sort || (!stream && !stream_pairs))) {
+        fprintf(stderr, "asm-map: --bai needs --bam --sort with --stream or --stream-pairs (the index is of a sorted BAM file the library writes)\n");
         usage();
     }
     if (bam_level >= 0 && !bam) {
@@ -569,6 +581,7 @@ int main(int argc, char** argv) {
     if (!rc && md && (stream || stream_pairs)) rc = asm_map_set_sam_tags(h, ASM_SAM_TAG_MD);
     if (!rc && bam) rc = asm_map_set_output_format(h, ASM_OUT_BAM);
     if (!rc && bam_level >= 0) rc = asm_map_set_bgzf_level(h, bam_level);
+    if (!rc && bai) rc = asm_map_set_bam_index(h, ASM_BAM_INDEX_BAI);
     if (!rc)
         rc = ref_stream ? asm_index_build_file(h, ref_path.c_str(), k, 0, &ix, nullptr)
                         : asm_index_build(h, text.data(), off.data(), (int32_t)names.size(), k, &ix);
@@ -597,8 +610,11 @@ int main(int argc, char** argv) {
                                  chunk_bytes, &st);
         if (rc) fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
         asm_index_free(h, ix);
+        asm_bam_index_stats ist = {};
+        if (!rc && bai) (void)asm_map_last_bam_index(h, &ist);
         asm_destroy(h);
         if (rc) return 1;
+        if (bai) report_index(ist);
         fprintf(stderr, "asm-map: %lld reads, %lld mapped, %lld longer than %d (unmapped)\n", (long long)st.reads, (long long)st.mapped,
                 (long long)st.too_long, ASM_MAP_MAX_READ);
         report_streamed(st);
@@ -617,8 +633,11 @@ int main(int argc, char** argv) {
                                        &pp, chunk_bytes, &st);
         if (rc) fprintf(stderr, "asm-map: %s\n", asm_last_error(h));
         asm_index_free(h, ix);
+        asm_bam_index_stats ist = {};
+        if (!rc && bai) (void)asm_map_last_bam_index(h, &ist);
         asm_destroy(h);
         if (rc) return 1;
+        if (bai) report_index(ist);
         fprintf(stderr, "asm-map: %lld pairs, %lld proper, %lld mates rescued\n", (long long)st.pairs, (long long)st.proper,
                 (long long)st.rescued);
         report_streamed(st);

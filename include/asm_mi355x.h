@@ -657,6 +657,38 @@ int asm_map_pairs_file_sorted(asm_handle* h, const asm_index* ix, const char* co
                               const asm_pair_params* pp, int64_t chunk_bytes, int64_t max_device_bytes,
                               asm_map_pairs_file_stats* stats /* may be NULL */, asm_sam_sort_stats* sort_stats /* may be NULL */);
 
+/* BAM index (docs/design/mapper.md, "BAM index"): handle state, like the output format and the container's level.  ASM_BAM_INDEX_NONE
+ * (the default) leaves every byte, launch and allocation of every call as it is.  Under ASM_OUT_BAM and ASM_BAM_INDEX_BAI the two sorted
+ * file calls write `<sam_path>.bai` (created or truncated) when the BAM file is complete: a BAI index (SAM spec 5.2) in the canonical
+ * form of the design document, built on the device from the tables the sort leaves there.  The BAM file is byte for byte the one
+ * written without the index, and every argument, error and stats field keeps its meaning.  Under ASM_OUT_SAM and in the unsorted
+ * calls the setting has no effect and no `.bai` path is opened.  BAI holds coordinates below 2^29: a sequence of the index of more
+ * than 2^29 bases is ASM_EUNSUPPORTED, found with the argument checks before either file is opened; asm_last_error names the sequence
+ * and says that such a reference needs a .csi index.  The index tables, the block table and the image are allocations of the sorted
+ * call's hold: they count against max_device_bytes, and running out is its ASM_ENOMEM.  A failed write is ASM_EINVAL, "writing the BAM
+ * index failed".
+ * asm_map_set_bam_index:  another value, or a NULL handle, is ASM_EINVAL; the value is checked first.
+ * asm_map_get_bam_index:  ASM_BAM_INDEX_NONE for a NULL handle.
+ * asm_map_last_bam_index: of the handle's last sorted BAM call that wrote an index; all zero before one.  bins: the real bins; chunks:
+ *                         the chunks of the real bins; intervals: the sum of n_intv; no_coor: n_no_coor; bytes: the index file.
+ * asm_bam_index_host:     a whole coordinate-sorted BAM file in memory (any BGZF cut, any number of deflate blocks per member) -> the
+ *                         index's bytes, by the host build of the same core; no device, no handle.  dst_cap below the size:
+ *                         ASM_EINVAL, *dst_len = the size needed, nothing written.  A corrupt container: asm_bgzf_decompress_host's
+ *                         error.  A malformed BAM stream (bad magic, a record reaching past the end, a refID of n_ref or more, a bin
+ *                         that is not reg2bin of the record) is ASM_EINVAL and asm_last_error names the 0-based record; records out
+ *                         of (refID, pos) order, refID -1 behind everything, are ASM_EINVAL naming the first record below its
+ *                         predecessor; a position or end above 2^29 is ASM_EUNSUPPORTED. */
+#define ASM_BAM_INDEX_NONE 0
+#define ASM_BAM_INDEX_BAI 1
+typedef struct asm_bam_index_stats {
+    int64_t refs, bins, chunks, intervals, no_coor, bytes;
+    double seconds_index; /* from the BAM file complete to the index file written */
+} asm_bam_index_stats;
+int asm_map_set_bam_index(asm_handle* h, int kind);
+int asm_map_get_bam_index(const asm_handle* h);
+int asm_map_last_bam_index(asm_handle* h, asm_bam_index_stats* out);
+int asm_bam_index_host(const void* bam, size_t n, void* dst, size_t dst_cap, size_t* dst_len);
+
 /* asm_index_build_file: asm_index_build from a FASTA file (docs/design/mapper.md, "Reference: FASTA in, index out"); synchronous.  The
  *                  file is read in chunks of about chunk_bytes (0: 16 MiB) that may end anywhere except inside a header line, so a
  *                  sequence line may have any length; a chunk is parsed on the device while the next one is read and copied in.
