@@ -423,6 +423,42 @@ int asm_align_batch(asm_handle* h, int aligner, int64_t n, const char* reads, co
     return ASM_OK;
 }
 
+/* hipcub's inclusive last-setter scan on the handle's stream; the first call asks for the temporary size and reserves it */
+static hipError_t inclusive_scan_last_setter(asm_handle* h, Scratch<void>& tmp, size_t& tmp_bytes, int32_t* in, int32_t* out, long n) {
+    if (!tmp.p) {
+        if (const hipError_t e = hipcub::DeviceScan::InclusiveScan(nullptr, tmp_bytes, in, out, LastSetter(), (int)n, h->stream)) return e;
+        if (const hipError_t e = tmp.alloc(tmp_bytes + 16)) return e;
+    }
+    return hipcub::DeviceScan::InclusiveScan(tmp.p, tmp_bytes, in, out, LastSetter(), (int)n, h->stream);
+}
+
+/* Sequential mode: the events in d_ed become verdicts in batch order (S2 of asm_simd_ed.h) — setter keys, their last-setter scan,
+ * converge keys from it, their scan, verdicts — and `state` (may be null: zeros in, nothing out) becomes what the next batch of the
+ * same stream of pairs starts from.  One wait, for the two trailing scan values. */
+static int simd_ed_resolve_sequential(asm_handle* h, int32_t* d_ed, long n, int T, int32_t* state) {
+    const int init_fe = state ? state[0] : 0, init_fd = state ? state[1] : 0, init_conv = state ? state[2] : 0;
+    const unsigned g = grid_for(n), t = ASM_BLOCK;
+    int32_t last_setter = -1, last_conv = -1;
+    size_t tmp_bytes = 0;
+    Scratch<int32_t> d_a(h), d_b(h);
+    Scratch<void> d_tmp(h);
+    HIPCHK(h, d_a.alloc(sizeof(int32_t) * (size_t)n));
+    HIPCHK(h, d_b.alloc(sizeof(int32_t) * (size_t)n));
+    HIPCHK(h, launch(h, simd_ed_setter_kernel, g, t, d_ed, n, d_a.p));
+    HIPCHK(h, inclusive_scan_last_setter(h, d_tmp, tmp_bytes, d_a.p, d_b.p, n));
+    /* enqueued here, not in the fetch below: the second scan writes over d_b */
+    HIPCHK(h, hipMemcpyAsync(&last_setter, d_b.p + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, launch(h, simd_ed_converge_kernel, g, t, d_ed, d_b.p, n, init_fe, init_fd, d_a.p));
+    HIPCHK(h, inclusive_scan_last_setter(h, d_tmp, tmp_bytes, d_a.p, d_b.p, n));
+    HIPCHK(h, launch(h, simd_ed_verdict_kernel, g, t, d_ed, d_b.p, n, T, init_conv));
+    HIPCHK(h, fetch(h, {fetched(&last_conv, (const int32_t*)d_b.p + (n - 1))})); /* the wait: last_setter has arrived too */
+    if (state) {
+        if (last_setter >= 0) state[0] = last_setter & 0xff, state[1] = last_setter >> 8;
+        if (last_conv >= 0) state[2] = last_conv;
+    }
+    return ASM_OK;
+}
+
 int asm_simd_ed_batch_async(asm_handle* h, const asm_batch* b, int ed_threshold, int shd_enable, int mode,
                             int32_t* state, int32_t* d_ed) {
     return asm_simd_ed_mode_batch_async(h, b, ed_threshold, shd_enable, mode, ASM_LEAP_GLOBAL, state, d_ed);
@@ -457,29 +493,7 @@ int asm_simd_ed_mode_batch_async(asm_handle* h, const asm_batch* b, int ed_thres
         HIPCHK(h, launch(h, simd_ed_clean_kernel, g, t, d_ed, n, ed_threshold));
         return ASM_OK;
     }
-    /* sequential: resolve the verdict chain in batch order with two last-setter scans */
-    const int init_fe = state ? state[0] : 0, init_fd = state ? state[1] : 0, init_conv = state ? state[2] : 0;
-    int32_t last_setter = -1, last_conv = -1;
-    size_t tmp_bytes = 0;
-    Scratch<int32_t> d_a(h), d_b(h);
-    Scratch<void> d_tmp(h);
-    HIPCHK(h, d_a.alloc(sizeof(int32_t) * (size_t)n));
-    HIPCHK(h, d_b.alloc(sizeof(int32_t) * (size_t)n));
-    HIPCHK(h, hipcub::DeviceScan::InclusiveScan(nullptr, tmp_bytes, d_a.p, d_b.p, LastSetter(), (int)n, h->stream));
-    HIPCHK(h, d_tmp.alloc(tmp_bytes + 16));
-    HIPCHK(h, launch(h, simd_ed_setter_kernel, g, t, d_ed, n, d_a.p));
-    HIPCHK(h, hipcub::DeviceScan::InclusiveScan(d_tmp.p, tmp_bytes, d_a.p, d_b.p, LastSetter(), (int)n, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&last_setter, d_b.p + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, launch(h, simd_ed_converge_kernel, g, t, d_ed, d_b.p, n, init_fe, init_fd, d_a.p));
-    HIPCHK(h, hipcub::DeviceScan::InclusiveScan(d_tmp.p, tmp_bytes, d_a.p, d_b.p, LastSetter(), (int)n, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&last_conv, d_b.p + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, launch(h, simd_ed_verdict_kernel, g, t, d_ed, d_b.p, n, ed_threshold, init_conv));
-    HIPCHK(h, hipStreamSynchronize(h->stream)); /* last_setter and last_conv are read below */
-    if (state) { /* the state the next batch of the same stream of pairs starts from */
-        if (last_setter >= 0) state[0] = last_setter & 0xff, state[1] = last_setter >> 8;
-        if (last_conv >= 0) state[2] = last_conv;
-    }
-    return ASM_OK;
+    return simd_ed_resolve_sequential(h, d_ed, n, ed_threshold, state);
 }
 
 static int simd_ed_affine_launch(asm_handle* h, const asm_batch* b, int gap_threshold, int af_threshold, int x, int o, int e, int mode,
