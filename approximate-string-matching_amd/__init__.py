@@ -779,7 +779,8 @@ class Engine:
         """one CIGAR string per record of nops, flat ('' for all when cigar_cap is 0)"""
         if not (cigar_cap and nops.size):
             return [""] * nops.size
-        return decode_cigars(ops.reshape(nops.size, -1), nops.reshape(-1), cigar_cap)
+        # a record whose row did not fit carries MAP_CIGAR_TRUNCATED and cigar_nops > cigar_cap: its string is the stored prefix
+        return decode_cigars(ops.reshape(nops.size, -1), nops.reshape(-1), cigar_cap, truncated="prefix")
 
     def map_reads(self, index: Index, reads, max_errors: int, both_strands: bool = True, max_occ: int = 0, greedy_k: int = 3,
                   cigar_cap: int = 64, chunk: Optional[int] = None):
@@ -1076,11 +1077,13 @@ class Engine:
 
     def greedy_cigar_async(self, batch: DeviceBatch, params: Params, d_pen: int, d_ops: int, cap: int, d_nops: int) -> None:
         """asm_greedy_cigar_batch_async into caller buffers (enqueue only): d_pen = device int32[n], d_ops = device uint16[n][cap]
-        (count << 3 | op, see decode_cigars), d_nops = device uint8[n] (above cap: the row was truncated)."""
+        (count << 3 | op, see decode_cigars), d_nops = device uint8[n] (above cap: the row was truncated and holds its first cap
+        entries; the count saturates at 255, which means "255 or more": cigar_rows_truncated)."""
         self._chk(self.lib.asm_greedy_cigar_batch_async(self.h, batch.ptr, ctypes.byref(params), d_pen, d_ops, int(cap), d_nops))
 
     def greedy_with_cigar(self, batch: DeviceBatch, params: Params, cap: int = 48):
-        """-> (costs int32[n], CIGAR strings) — hurdle_matrix::get_cost / get_CIGAR for every pair of the batch."""
+        """-> (costs int32[n], CIGAR strings, nops) — hurdle_matrix::get_cost / get_CIGAR for every pair of the batch.  ValueError when
+        a row did not fit into cap entries (decode_cigars): a shortened string is not handed back as a CIGAR."""
         n = batch.n
         d_pen, d_ops, d_nops = self.malloc(4 * max(n, 1)), self.malloc(2 * cap * max(n, 1)), self.malloc(max(n, 1))
         try:
@@ -1093,29 +1096,34 @@ class Engine:
                 self.free(p)
         return costs, decode_cigars(ops, nops, cap), nops
 
-    def coverage(self, batch: DeviceBatch, params: Params, window: int = 64, cap: int = 64, want_nw_cigars: bool = False):
+    def coverage(self, batch: DeviceBatch, params: Params, window: int = 64, cap: int = 64, want_nw_cigars: bool = False,
+                 nw_cap: Optional[int] = None):
         """The harness's coverage metric for every pair: -> dict(cover uint8[n] (1/0/2), covered, undetermined,
-        greedy_cost, greedy_cigars[, nw_cigars])."""
+        greedy_cost, greedy_cigars, greedy_nops[, nw_cigars, nw_nops]).  cap: entries per Greedy CIGAR row; nw_cap: entries per NW
+        row (None: cap).  A pair whose Greedy row did not fit (greedy_nops > cap, or 255: the count saturates) has cover 2, is
+        counted in `undetermined` and has None for its greedy_cigars entry; an NW row that did not fit has None in nw_cigars."""
         n = batch.n
+        nw_cap = cap if nw_cap is None else int(nw_cap)
         d_pen, d_ops, d_nops = self.malloc(4 * max(n, 1)), self.malloc(2 * cap * max(n, 1)), self.malloc(max(n, 1))
         d_cov, d_cnt = self.malloc(max(n, 1)), self.malloc(16)
-        d_nwo = self.malloc(2 * cap * max(n, 1)) if want_nw_cigars else None
+        d_nwo = self.malloc(2 * nw_cap * max(n, 1)) if want_nw_cigars else None
         d_nwn = self.malloc(max(n, 1)) if want_nw_cigars else None
         try:
             self._chk(self.lib.asm_greedy_cigar_batch_async(self.h, batch.ptr, ctypes.byref(params), d_pen, d_ops, cap,
                                                             d_nops))
             self.memset_async(d_cnt, 0, 16)
             self._chk(self.lib.asm_coverage(self.h, batch.ptr, ctypes.byref(params), d_ops, cap, d_nops, window, d_cov,
-                                            d_nwo, cap, d_nwn, d_cnt))
+                                            d_nwo, nw_cap, d_nwn, d_cnt))
             cnt = self.to_host(d_cnt, 2, np.uint64)
             out = {"cover": self.to_host(d_cov, n, np.uint8), "covered": int(cnt[0]), "undetermined": int(cnt[1]),
                    "greedy_cost": self.to_host(d_pen, n)}
             gops = self.to_host(d_ops, n * cap, np.uint16).reshape(n, cap)
-            out["greedy_cigars"] = decode_cigars(gops, self.to_host(d_nops, n, np.uint8), cap)
+            out["greedy_nops"] = self.to_host(d_nops, n, np.uint8)
+            out["greedy_cigars"] = decode_cigars(gops, out["greedy_nops"], cap, truncated="none")
             if want_nw_cigars:
-                nops = self.to_host(d_nwn, n, np.uint8)
-                out["nw_cigars"] = decode_cigars(self.to_host(d_nwo, n * cap, np.uint16).reshape(n, cap), nops, cap,
-                                                 reverse=True)
+                out["nw_nops"] = self.to_host(d_nwn, n, np.uint8)
+                out["nw_cigars"] = decode_cigars(self.to_host(d_nwo, n * nw_cap, np.uint16).reshape(n, nw_cap), out["nw_nops"], nw_cap,
+                                                 reverse=True, truncated="none")
             return out
         finally:
             for p in (d_pen, d_ops, d_nops, d_cov, d_cnt, d_nwo, d_nwn):
@@ -1160,11 +1168,32 @@ class Engine:
         return Timer(self)
 
 
-def decode_cigars(ops: np.ndarray, nops: np.ndarray, cap: int, reverse: bool = False):
-    """Encoded rows (count << 3 | op; op 0 'M', 1 'I', 2 'D', 3 '=', 4 'X') -> CIGAR strings."""
+CIGAR_NOPS_MAX = 255  # the pair aligners' row counts are bytes that saturate: 255 means "255 or more"
+
+
+def cigar_rows_truncated(nops: np.ndarray, cap: int) -> np.ndarray:
+    """bool per row: the row is not known to be whole — nops > cap (only cap entries are stored), or nops == 255 (saturated)."""
+    nops = np.asarray(nops).astype(np.int64)
+    return (nops > int(cap)) | (nops >= CIGAR_NOPS_MAX)
+
+
+def decode_cigars(ops: np.ndarray, nops: np.ndarray, cap: int, reverse: bool = False, truncated: str = "raise"):
+    """Encoded rows (count << 3 | op; op 0 'M', 1 'I', 2 'D', 3 '=', 4 'X') -> CIGAR strings.  A row that is not known to be whole
+    (cigar_rows_truncated) is never handed back as if it were: truncated = "raise" (ValueError), "none" (None in its place), or
+    "prefix" for a caller that reports the truncation itself (the mapper's CIGAR_TRUNCATED flag): the stored entries."""
+    if truncated not in ("raise", "none", "prefix"):
+        raise ValueError("truncated must be 'raise', 'none' or 'prefix'")
     letters = "MID=X???"
+    cut = cigar_rows_truncated(nops, cap)
+    if truncated == "raise" and cut.any():
+        first = int(np.nonzero(cut)[0][0])
+        raise ValueError(f"{int(cut.sum())} CIGAR rows are truncated (first: row {first} reports {int(nops[first])} entries, "
+                         f"cap {cap}; 255 means 255 or more): give the call a larger cap")
     out = []
     for i in range(ops.shape[0]):
+        if cut[i] and truncated == "none":
+            out.append(None)
+            continue
         row = ops[i, :min(int(nops[i]), cap)]
         if reverse:
             row = row[::-1]

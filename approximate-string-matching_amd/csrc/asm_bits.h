@@ -214,7 +214,12 @@ struct OutMap {
 
 // Optional CIGAR output of the Greedy kernels (hurdle_matrix::_update_CIGAR, GASMA/hurdle_matrix.h:238-251): per pair
 // a row of `cap` uint16 entries (count << 3 | op, op 0 = 'M', 1 = 'I', 2 = 'D'; the NW traceback adds 3 = '=', 4 = 'X') and the number of entries produced
-// (which may exceed cap: the row is then truncated and the caller sees nops > cap).  ops == null disables it.
+// (which may exceed cap: the row is then truncated and the caller sees nops > cap).  The count is a byte that saturates: 255 means
+// "255 or more", so a row of cap >= 255 that reports 255 may be truncated too.  ops == null disables it.
+#define ASM_CIGAR_NOPS_MAX 255
+ASM_HD int cigar_nops_byte(int cnt) { return cnt > ASM_CIGAR_NOPS_MAX ? ASM_CIGAR_NOPS_MAX : cnt; }
+// What a reader of a row can know: it is whole only when nops <= cap and the count did not saturate.
+ASM_HD bool cigar_row_truncated(int nops, int cap) { return nops > cap || nops >= ASM_CIGAR_NOPS_MAX; }
 struct CigarSink {
     uint16_t* ops;
     uint8_t* nops;
@@ -232,5 +237,5 @@ struct CigarSink {
             emit(pair, cnt, to_lane - from_lane, 2);
         if (run > 0) emit(pair, cnt, run, 0);
     }
-    ASM_HD void finish(long pair, int cnt) const { nops[pair] = (uint8_t)(cnt > 255 ? 255 : cnt); }
+    ASM_HD void finish(long pair, int cnt) const { nops[pair] = (uint8_t)cigar_nops_byte(cnt); }
 };

@@ -20,7 +20,9 @@
 //   3. nw_trace_affine_kernel  — the full Gotoh matrix (any penalties, any distance) with four direction bits per cell
 //      (H came from the diagonal / H equals E / E extends / F extends) in a scratch array [row][8 cells][pair], then the
 //      oracle's traceback rule by rule: in H prefer the diagonal, then E ('D'), then F ('I'); inside a gap prefer extending.
-// so that no pair the harness covers (benchmark_utils.h:214-225,256-258) is left "not determined".
+// so that no pair the harness covers (benchmark_utils.h:214-225,256-258) is left "not determined" for want of an NW alignment.
+// The one case that IS flagged COVER_UNKNOWN (and counted in counters[1]) is a pair whose Greedy CIGAR row is known to be
+// truncated (cigar_row_truncated, asm_bits.h): LCM1 of half an alignment would give a confident verdict about nothing.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -122,18 +124,20 @@ struct CoverArgs {
     uint16_t* nw_ops;  /* optional NW CIGAR rows [n][nw_cap], entries in traceback (reverse) order */
     uint8_t* nw_nops;
     int nw_cap;
-    unsigned long long* counters; /* [0] += covered, [1] += undetermined */
+    unsigned long long* counters; /* [0] += covered, [1] += undetermined: pairs whose Greedy row is truncated */
+    ASM_DEV bool greedy_truncated(long pair) const { return cigar_row_truncated(g_nops[pair], g_cap); }
 };
 
 // covers(LCM(read, Greedy CIGAR, 1), LCM(read, NW CIGAR, 3)) given the read positions of the NW side's long '=' runs
-// (benchmark_coverage.h:26-67,73-91)
+// (benchmark_coverage.h:26-67,73-91); COVER_UNKNOWN when the Greedy row is truncated, and only then
 template <int W64>
 ASM_DEV int cover_verdict(const VW<W64>& A0, const VW<W64>& A1, int m, const VW<W64>& lcm2, const CoverArgs& ca, long pair) {
+    if (ca.greedy_truncated(pair)) return COVER_UNKNOWN;
     // LCM1: read positions under Greedy's 'M' runs (benchmark_coverage.h:37-62 with threshold 1)
     VW<W64> lcm1;
 #pragma unroll
     for (int q = 0; q < W64; q++) lcm1.w[q] = 0ull;
-    const int gn = ca.g_nops[pair] < ca.g_cap ? ca.g_nops[pair] : ca.g_cap;
+    const int gn = ca.g_nops[pair]; /* <= g_cap: the row is whole */
     int ridx = 0;
     for (int t = 0; t < gn; t++) {
         const uint16_t e = ca.g_ops[pair * ca.g_cap + t];
@@ -202,7 +206,7 @@ __global__ __launch_bounds__(ASM_BLOCK) void nw_trace_cover_kernel(const uint4* 
     constexpr int C = W / 2;
     __shared__ unsigned int s_part[4];
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned int covered = 0, unknown = 0;
+    unsigned int covered = 0, unknown = 0, hand_over = 0;
     if (i < cnt) {
         const long pair = order ? (long)order[i] : slice_lo + i;
         const uint32_t ln = lens[i];
@@ -316,13 +320,15 @@ __global__ __launch_bounds__(ASM_BLOCK) void nw_trace_cover_kernel(const uint4* 
         int flag = COVER_UNKNOWN;
         if (ok) flag = cover_verdict<W64>(A0, A1, m, lcm2, ca, pair);
         ca.cover[pair] = (uint8_t)flag;
-        if (ca.nw_nops) ca.nw_nops[pair] = (uint8_t)(ok ? (nops > 255 ? 255 : nops) : 0);
+        if (ca.nw_nops) ca.nw_nops[pair] = (uint8_t)(ok ? cigar_nops_byte(nops) : 0);
         covered = flag == COVER_YES, unknown = flag == COVER_UNKNOWN;
+        // What the band could not trace goes to the full-matrix pass, which answers it and counts it.  A pair whose Greedy row
+        // is truncated has its final flag here: the full matrix cannot answer it either, so it is handed over only where the
+        // caller wants the NW row it would write.
+        hand_over = todo != nullptr && !ok && (ca.nw_ops != nullptr || !ca.greedy_truncated(pair));
+        if (hand_over) unknown = 0;
     }
-    if (todo != nullptr) {
-        wave_append(todo, todo_count, unknown != 0u, (uint32_t)i);
-        unknown = 0; /* the full-matrix pass answers them */
-    }
+    if (todo != nullptr) wave_append(todo, todo_count, hand_over != 0u, (uint32_t)i);
     const unsigned int tc = block_sum_256(covered, s_part), tu = block_sum_256(unknown, s_part);
     if (threadIdx.x == 0) {
         if (tc) atomicAdd(&ca.counters[0], (unsigned long long)tc);
@@ -342,13 +348,13 @@ __global__ __launch_bounds__(64) void nw_trace_affine_kernel(const uint4* __rest
                                                              const uint32_t* __restrict__ todo /* cnt bucket slots, or null: slots 0..cnt-1 */,
                                                              const uint32_t* __restrict__ order, long slice_lo, CoverArgs ca) {
     __shared__ uint32_t s_bound[MAXROWS + 1][64];
-    __shared__ unsigned int s_cov[1];
+    __shared__ unsigned int s_cov[2]; /* covered, undetermined */
     const int t = threadIdx.x;
     const long slot = (long)blockIdx.x * 64 + t;
     const long stride = cnt;
-    if (t == 0) s_cov[0] = 0u;
+    if (t == 0) s_cov[0] = s_cov[1] = 0u;
     __syncthreads();
-    unsigned int covered = 0u;
+    unsigned int covered = 0u, unknown = 0u;
     if (slot < stride) {
         const long i = todo ? (long)todo[slot] : slot;
         const long pair = order ? (long)order[i] : slice_lo + i;
@@ -370,10 +376,12 @@ __global__ __launch_bounds__(64) void nw_trace_affine_kernel(const uint4* __rest
         gotoh_traceback<W64>(A0, A1, B0, B1, m, nn, trace, runs);
         const int flag = cover_verdict<W64>(A0, A1, m, lcm2, ca, pair);
         ca.cover[pair] = (uint8_t)flag;
-        if (ca.nw_nops) ca.nw_nops[pair] = (uint8_t)(nops > 255 ? 255 : nops);
-        covered = flag == COVER_YES;
+        if (ca.nw_nops) ca.nw_nops[pair] = (uint8_t)cigar_nops_byte(nops);
+        covered = flag == COVER_YES, unknown = flag == COVER_UNKNOWN;
     }
     if (covered) atomicAdd(&s_cov[0], 1u);
+    if (unknown) atomicAdd(&s_cov[1], 1u);
     __syncthreads();
     if (t == 0 && s_cov[0]) atomicAdd(&ca.counters[0], (unsigned long long)s_cov[0]);
+    if (t == 0 && s_cov[1]) atomicAdd(&ca.counters[1], (unsigned long long)s_cov[1]);
 }

@@ -170,7 +170,8 @@ inline int cigar_format(const uint16_t* ops, int nops, int cap, char* out, size_
         if (w < 0 || len + (size_t)w >= out_cap) return ASM_EINVAL;
         len += (size_t)w;
     }
-    return nops > cap ? ASM_EUNSUPPORTED : ASM_OK; /* truncated row */
+    /* truncated row, or one that may be: the producers' counts are bytes that saturate, 255 = "255 or more" */
+    return nops > cap || nops >= 255 ? ASM_EUNSUPPORTED : ASM_OK;
 }
 
 // ---- `>read\n<ref\n` files (benchmark_utils.h:325-352): newline scanning and the reader side of the streaming ingest ---------

@@ -467,7 +467,7 @@ public:
         if (have_cover_) {
             printf("=> Greedy           | %.3f %%\n", (double)cover_[0] / (total - (double)cover_[1]) * 100);
             if (cover_[1])
-                printf("   (%llu pairs beyond the traceback band are excluded; NW tie-break is this library's, not parasail's)\n",
+                printf("   (%llu pairs whose Greedy CIGAR has more than 96 runs are excluded; NW tie-break is this library's, not parasail's)\n",
                        cover_[1]);
         } else {
             printf("=> Greedy           | not computed (streamed run)\n");

@@ -606,6 +606,15 @@ int main(int argc, char** argv) {
         EXPECT(cigar_format(ops, 5, 8, out, sizeof out) == ASM_OK && std::string(out) == "22M1D50M1I128X", "cigar text: %s", out);
         EXPECT(cigar_format(ops, 9, 5, out, sizeof out) == ASM_EUNSUPPORTED && std::string(out) == "22M1D50M1I128X", "truncated row");
         EXPECT(cigar_format(ops, 0, 5, out, sizeof out) == ASM_OK && out[0] == 0, "empty row");
+        {   /* the count saturates: 255 is "255 or more" at any cap, 254 is a whole row where the cap holds it */
+            std::vector<uint16_t> wide(300, (uint16_t)(1 << 3 | 3));
+            std::vector<char> text(4096);
+            EXPECT(cigar_format(wide.data(), 254, 254, text.data(), text.size()) == ASM_OK && strlen(text.data()) == 2 * 254, "254 of 254");
+            for (int cap : {254, 255, 256, 300}) {
+                const int rc = cigar_format(wide.data(), 255, cap, text.data(), text.size());
+                EXPECT(rc == ASM_EUNSUPPORTED && strlen(text.data()) == 2 * (size_t)(cap < 255 ? cap : 255), "saturated count at cap %d: rc %d", cap, rc);
+            }
+        }
         for (size_t cap = 1; cap <= 15; cap++) {
             std::vector<char> small(cap); /* exactly `cap` bytes on the heap: an overrun is an ASan report */
             const int rc = cigar_format(ops, 5, 8, small.data(), cap);

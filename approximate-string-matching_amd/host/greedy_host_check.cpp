@@ -339,11 +339,12 @@ extern "C" long greedy_host_lane_words(long n, const unsigned char* views) {
 }
 
 #ifdef GREEDY_HOST_CHECK_MAIN
-// Stand-alone form (the one a sanitizer build takes): greedy_host_check BATCH k x o e semi T LPT.  BATCH holds int32 n, uint32 lens[n] and
-// the n x 256 view bytes, read into arrays of exactly that size.  Prints per pair the cost and the CIGAR of each shape (shape (c) only
-// where T * LPT covers the band), then the count of greedy_host_lane_words.
+// Stand-alone form (the one a sanitizer build takes): greedy_host_check BATCH k x o e semi T LPT [cap].  BATCH holds int32 n, uint32 lens[n]
+// and the n x 256 view bytes, read into arrays of exactly that size; the CIGAR rows are n x cap entries on the heap, exactly (cap: 255
+// unless given), so a store past a full row is a sanitizer report.  Prints per pair the cost and the CIGAR of each shape (shape (c) only
+// where T * LPT covers the band; a truncated row as its stored entries and "+<entries missing>"), then the count of greedy_host_lane_words.
 int main(int argc, char** argv) {
-    if (argc != 9) return fprintf(stderr, "usage: %s batch k x o e semi T LPT\n", argv[0]), 2;
+    if (argc != 9 && argc != 10) return fprintf(stderr, "usage: %s batch k x o e semi T LPT [cap]\n", argv[0]), 2;
     FILE* f = fopen(argv[1], "rb");
     int32_t n = 0;
     if (!f || fread(&n, sizeof n, 1, f) != 1 || n < 0) return fprintf(stderr, "%s: cannot read\n", argv[1]), 2;
@@ -353,7 +354,8 @@ int main(int argc, char** argv) {
     fclose(f);
     const int k = atoi(argv[2]), x = atoi(argv[3]), o = atoi(argv[4]), e = atoi(argv[5]), semi = atoi(argv[6]), T = atoi(argv[7]), LPT = atoi(argv[8]);
     const double probs[3] = {0.80, 0.20 / 3, 0.40 / 3};
-    const int cap = 255, shapes = T * LPT >= 2 * k + 1 ? 3 : 2;
+    const int cap = argc == 10 ? atoi(argv[9]) : 255, shapes = T * LPT >= 2 * k + 1 ? 3 : 2;
+    if (cap < 1) return fprintf(stderr, "cap must be at least 1\n"), 2;
     std::vector<std::string> lines((size_t)n);
     for (int shape = 0; shape < shapes; shape++) {
         std::vector<int32_t> costs((size_t)n);
@@ -364,7 +366,8 @@ int main(int argc, char** argv) {
             std::string& s = lines[i];
             s += (shape ? " " : "") + std::to_string(costs[i]) + " ";
             if (nops[i] == 0) s += "*";
-            for (int q = 0; q < nops[i]; q++) s += std::to_string(ops[(size_t)i * cap + q] >> 3) + "MID"[ops[(size_t)i * cap + q] & 7];
+            for (int q = 0; q < nops[i] && q < cap; q++) s += std::to_string(ops[(size_t)i * cap + q] >> 3) + "MID"[ops[(size_t)i * cap + q] & 7];
+            if (nops[i] > cap) s += "+" + std::to_string(nops[i] - cap); /* a truncated row: its stored entries, then how many are missing */
         }
     }
     for (int32_t i = 0; i < n; i++) printf("%s\n", lines[i].c_str());

@@ -190,10 +190,13 @@ int asm_align_batch_hinted_async(asm_handle* h, const asm_batch* b, int aligner,
 /* Greedy with its CIGAR (hurdle_matrix::get_CIGAR, hurdle_matrix.h:613; built by _update_CIGAR :238-251 — lane switches
  * as nI / nD, runs of matches AND mismatches as nM, and the final hop's run is the hurdle count, :589).  d_ops = device
  * uint16[n][cap], entry = count << 3 | op with op 0 'M', 1 'I', 2 'D' (3 '=' and 4 'X' appear in NW CIGARs only); d_nops = device uint8[n] = entries produced (a
- * value above cap means the row was truncated).  Enqueue only. */
+ * value above cap means the row was truncated: only the first cap entries are stored).  The count is a byte and saturates at
+ * 255: 255 means "255 or more", so with cap >= 255 a row that reports 255 may be truncated as well.  A row is known to be whole
+ * when d_nops[i] <= cap and d_nops[i] < 255.  Enqueue only. */
 int asm_greedy_cigar_batch_async(asm_handle* h, const asm_batch* b, const asm_params* p, int32_t* d_penalties,
                                  uint16_t* d_ops, int cap, uint8_t* d_nops);
-/* Host helper: formats one encoded row as the reference's string ("22M1D50M1D28M"). */
+/* Host helper: formats one encoded row as the reference's string ("22M1D50M1D28M").  Writes the stored entries (the first
+ * min(nops, cap)) and returns ASM_EUNSUPPORTED when the row is not known to be whole: nops > cap, or nops == 255 (saturated). */
 int asm_cigar_format(const uint16_t* ops, int nops, int cap, char* out, size_t out_cap);
 /* The harness's coverage counter (benchmark_utils.h:214-225,256-258; benchmark_coverage.h:26-91): for every pair,
  * does LCM(read, Greedy CIGAR, threshold 1) cover LCM(read, NW CIGAR, threshold 3)?  Needs the Greedy CIGAR rows of
@@ -201,10 +204,13 @@ int asm_cigar_format(const uint16_t* ops, int nops, int cap, char* out, size_t o
  * preference (in H the diagonal, then a gap in the read 'D', then a gap in the reference 'I'; inside a gap, extending it —
  * parasail's is internal and unpinned), for any penalties p->x, p->o, p->e the NW aligner accepts.  Unit penalties run a
  * banded bit-parallel pass with `window` = 32 or 64 rows first; pairs it cannot answer (distance above window/2 - 3) and
- * every pair under other penalties go through a full Gotoh matrix with stored directions, so every pair gets an answer:
- * d_cover[i] = 1 covers / 0 does not (2 = not determined is no longer produced); d_counters[0] += covered,
- * d_counters[1] += not determined (stays 0).  d_nw_ops (optional) receives the NW CIGAR rows in traceback (reverse) order,
- * entries as above.  Synchronous. */
+ * every pair under other penalties go through a full Gotoh matrix with stored directions, so every pair whose Greedy row is
+ * whole gets an answer: d_cover[i] = 1 covers / 0 does not.  2 = not determined is produced for exactly one case: the pair's
+ * Greedy row is truncated (d_greedy_nops[i] > greedy_cap, or d_greedy_nops[i] == 255, the saturated count), since a verdict from
+ * the stored prefix would be a verdict about half an alignment.  d_counters[0] += covered, d_counters[1] += not determined
+ * (those pairs; 0 when greedy_cap holds every row).  d_nw_ops (optional) receives the NW CIGAR rows in traceback (reverse)
+ * order, entries as above, nw_cap entries per row; d_nw_nops saturates at 255 like d_nops above, and only the first nw_cap
+ * entries of a longer row are stored.  Synchronous. */
 int asm_coverage(asm_handle* h, const asm_batch* b, const asm_params* p, const uint16_t* d_greedy_ops, int greedy_cap,
                  const uint8_t* d_greedy_nops, int window, uint8_t* d_cover, uint16_t* d_nw_ops, int nw_cap,
                  uint8_t* d_nw_nops, unsigned long long* d_counters);

@@ -190,3 +190,71 @@ def test_the_same_batches_under_sanitizers(glh, greedy_check_asan, asm, corpus, 
                     costs, cigs = run_shape(glh, asm, hb, views, lens, shape, k, pen, bool(semi), t_, l_)
                     want = [w + (" " if w else "") + f"{int(c)} {g or '*'}" for w, c, g in zip(want, costs, cigs)]
                 assert lines[:-1] == want, (name, k, pen, semi)
+
+
+# ---- the same CigarSink at caps the rows do not fit into (the device side: tests/test_gpu_cigar_rows.py) ----
+TRUNC_BANDS = (4, 17, 40)  # of BANDS: a narrow band, one wave, two waves
+TRUNC_PENALTIES = [(1, 1, 1), (2, 3, 1)]
+
+
+def _trunc_caps(R):
+    return sorted({1, 2, max(1, int(np.median(R))), max(1, int(R.max()) - 1), int(R.max()), int(R.max()) + 1})
+
+
+@pytest.mark.parametrize("pen", TRUNC_PENALTIES)
+@pytest.mark.parametrize("k", TRUNC_BANDS)
+def test_three_shapes_fill_and_overfill_their_rows(glh, asm, oracle, corpus, k, pen):
+    """Every shape at caps 1, 2, median(R), max(R) - 1, max(R) and max(R) + 1 of the batch: the cost, nops = R, and the first
+    min(R, cap) entries are the oracle's (tests/cigar_row_cases.expect_row); the rows lie between two zones of a fill no entry can
+    equal, and neither the zones nor the entries behind a row's last run change."""
+    from tests import cigar_row_cases as cr
+
+    x, o, e = pen
+    pad, fill = 256, 0xA5A5
+    cut = 0
+    for name, hb, views, lens in corpus[k]:
+        want, want_cig = oracle.greedy(hb, k, x, o, e, mode=1, cigars=True)
+        full, R = cr.expect_matrix(want_cig)
+        for cap in _trunc_caps(R):
+            for label, shape, T, LPT in shapes_of(k):
+                costs, nops = np.zeros(hb.n, np.int32), np.full(hb.n + 2 * pad, 0xA5, np.uint8)
+                buf = np.full(hb.n * cap + 2 * pad, fill, np.uint16)
+                rc = glh.greedy_host_batch(hb.n, views.ctypes.data, lens.ctypes.data, shape, T, LPT, k, x, o, e, 0, PROBS.ctypes.data,
+                                           costs.ctypes.data, buf[pad:].ctypes.data, cap, nops[pad:].ctypes.data)
+                ctx = (name, label, "cap", cap)
+                assert rc == 0 and _first_bad(hb, costs, want) is None, (ctx, rc)
+                assert (buf[:pad] == fill).all() and (buf[pad + hb.n * cap:] == fill).all(), (ctx, "a store outside the rows")
+                assert (nops[:pad] == 0xA5).all() and (nops[pad + hb.n:] == 0xA5).all(), (ctx, "a store outside the counts")
+                rows = buf[pad:pad + hb.n * cap].reshape(hb.n, cap)
+                for i in range(hb.n):
+                    row, count = cr.expect_row(want_cig[i], cap)
+                    assert int(nops[pad + i]) == count and rows[i, :len(row)].tolist() == row, (ctx, i, hb.pair(i), want_cig[i])
+                    assert (rows[i, len(row):] == fill).all(), (ctx, i, "entries behind the last run were written")
+            cut += int((R > cap).sum())
+    assert cut > 500  # rows really were overfull
+
+
+def test_truncating_caps_under_sanitizers(greedy_check_asan, asm, oracle, corpus, tmp_path):
+    """The stand-alone program with its rows allocated at exactly n x cap entries: at a cap most rows exceed, no sanitizer report,
+    and per pair the cost, the first min(R, cap) entries of the oracle's CIGAR and the number of entries that did not fit."""
+    from tests import cigar_row_cases as cr
+
+    for k in TRUNC_BANDS:
+        T, LPT = group_shapes(k)[0]
+        for x, o, e in TRUNC_PENALTIES:
+            for name, hb, views, lens in corpus[k]:
+                want, want_cig = oracle.greedy(hb, k, x, o, e, mode=1, cigars=True)
+                R = np.array([cr.run_count(c) for c in want_cig])
+                path = tmp_path / "batch.bin"
+                path.write_bytes(np.int32(hb.n).tobytes() + lens.tobytes() + views.tobytes())
+                for cap in sorted({1, 2, max(1, int(np.median(R)))}):
+                    r = subprocess.run([greedy_check_asan, str(path)] + [str(v) for v in (k, x, o, e, 0, T, LPT, cap)], capture_output=True,
+                                       text=True, timeout=120)
+                    assert r.returncode == 0 and r.stderr == "", (name, k, cap, r.returncode, r.stderr[-3000:])
+                    lines = r.stdout.split("\n")[:-1]
+                    assert lines[-1] == "lane words differing: 0" and len(lines) == hb.n + 1
+                    for i in range(hb.n):
+                        row, count = cr.expect_row(want_cig[i], cap)
+                        text = "".join(f"{v >> 3}{'MID'[v & 7]}" for v in row) or "*"
+                        one = f"{int(want[i])} {text}" + (f"+{count - cap}" if count > cap else "")
+                        assert lines[i] == " ".join([one] * len(shapes_of(k)[:3])), (name, k, (x, o, e), cap, i, lines[i], one)
